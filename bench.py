@@ -5,7 +5,7 @@ A "step" is one pass of the hot path - Codec.encode followed by Codec.decode - o
 is already resident in HBM (wav [B, T] and SSL features [B, N50, 768] as the tokenizer hands them over), on every rank.
 `value` = audio-seconds processed by all ranks / max-over-ranks wall time of K steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--seconds 10]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--seconds 10] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -28,6 +28,7 @@ MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 
 CFG_NAMES = ["conv_gemm_kernel<128,32,4,1>", "conv_gemm_kernel<128,64,2,2>", "conv_gemm_kernel<128,128,2,2>", "conv_gemm_kernel<64,128,1,4>",
              "conv_gemm_kernel<64,64,2,2>", "conv_gemm_kernel<256,128,2,2>"]
 NPROF = 4 * len(CFG_NAMES)
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs: all files together
 
 
 def parse():
@@ -54,7 +55,13 @@ def parse():
                     help="tests/test_bench_bootstrap_cpu.py: run ONLY the rank bootstrap (self-launch, rendezvous), the ranks_seen all-gather and the "
                          "scatter -> hot path -> gather exchange leg, on the gloo backend with host tensors and a STUB hot path (no codec, no "
                          "GPU, no throughput: the line carries \"selftest\": true and value null)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (codes and waveform) as DIR/<name>.npy: "
+                         "integer codes as float64, the rest float32, at most 64 MB in all (a fixed, seeded sample beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _cpu_baseline_worker(clips, seconds, reps, threads, model="1.5"):
@@ -377,6 +384,24 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: each tensor as out_dir/<name>.npy - integer codes as float64 (exact), the rest as float32.  Past DUMP_CAP_BYTES
+    in all, every array is cut to the same fraction by a seeded choice of flat indices (the same elements in every run with the same
+    arguments, so two builds compare element for element)."""
+    import numpy as np
+
+    arrays = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else torch.float64).numpy() for k, v in outputs.items()}
+    room = DUMP_CAP_BYTES - 1024 * len(arrays)  # .npy headers
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > room:
+            idx = np.random.default_rng(i).choice(a.size, max(1, a.size * room // total), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(arrays)}" + (" (seeded sample)" if total > room else ""))
+
+
 def _free_port() -> int:
     import socket
 
@@ -651,14 +676,15 @@ def main():
     wav = (synth.synth_wav_fullband(7 + rank, B, T) if args.model == "2.0" else synth.synth_wav(7 + rank, B, T)).to(dev)
     feats = synth.synth_feat(9 + rank, B, T // hop_in, spec.sem_in).transpose(1, 2).contiguous().to(dev)  # [B, N50, C] as the SSL model emits
     groups = [0]
+    last_codes = {}  # what the last step's encode returned (--dump-outputs)
 
     def step():
         if adaptive:
-            codes = codec.encode(wav.unsqueeze(1), feats.transpose(1, 2))
-            groups[0] = codes["acoustic_codes"].shape[-1]
-            return codec.decode(**codes)
-        ac, sc = codec.encode(wav.unsqueeze(1), feats.transpose(1, 2))
-        return codec.decode(ac, sc)
+            last_codes.update(codec.encode(wav.unsqueeze(1), feats.transpose(1, 2)))
+            groups[0] = last_codes["acoustic_codes"].shape[-1]
+            return codec.decode(**last_codes)
+        last_codes["acoustic_codes"], last_codes["semantic_codes"] = codec.encode(wav.unsqueeze(1), feats.transpose(1, 2))
+        return codec.decode(last_codes["acoustic_codes"], last_codes["semantic_codes"])
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -685,6 +711,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**last_codes, "wav": out})
 
     # N > 1: (a) which devices the ranks really sit on (all-gather of their UUIDs: "did RCCL see N distinct GPUs" is answerable from
     # the line), (b) the exchange step north_star names - scatter of the clips from rank 0, gather of codes + waveforms back over

@@ -392,7 +392,12 @@ class Model:
             if path is None:
                 raise ValueError("Model needs config['semantic_model_path'] (a local microsoft/wavlm-base-plus snapshot) or semantic_model=: "
                                  "the reference downloads the model (model.py:30), this machine has no network")
-            semantic_model = SSLFeatureExtractor.from_pretrained(path, SPEC_WAVLM_BASE_PLUS, device=self.device)
+            import os
+
+            # the snapshot's config.json carries the architecture, as it does for AutoModel.from_pretrained (for the published
+            # snapshot it reads back as SPEC_WAVLM_BASE_PLUS); a snapshot without one is taken to be the published model
+            has_config = os.path.isdir(str(path)) and os.path.isfile(os.path.join(str(path), "config.json"))
+            semantic_model = SSLFeatureExtractor.from_pretrained(path, None if has_config else SPEC_WAVLM_BASE_PLUS, device=self.device)
         self.semantic_model = semantic_model
         self.driver = UniSE(self.dnn, self.semantic_model, tokenizer=self.tokenizer, max_segments=max_segments)
         if config.get("ckpt_path") and dnn is None:
