@@ -405,6 +405,15 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
                            int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                            int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream);
 
+/* Test hook, as qa_hcodec_enable_taps: while on, qa_lm_generate / qa_lm_generate_sampled record the logits of the active vocabulary
+ * slice at every decode step (what the head computes before the pick / sampler), in storage of their own: turning taps on changes no
+ * token.  Not supported under a caller's stream capture (the call is refused). */
+int qa_lm_enable_taps(qa_lm* lm, int on);
+/* Test hook: copy a snapshot of the LAST generate call into `dst` (device, fp32, capacity `cap` elements; NULL: only return the
+ * count).  Returns the element count or a negative status.  Names: "logits.global" [B, global_length + 1, global_size] (the
+ * discarded last global step included), "logits.semantic" [B, semantic_length, semantic_size]. */
+int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* stream);
+
 /* Kernel-level entry point of the sampler (parity / distribution tests): CustomLlamaModel.sample_logits (llm.py:253-288) on
  * logits [B, width] (row stride ld, device).  out_index int64 [B] (device).  do_sample = 0: arg-max (first maximum).
  * Synchronises `stream`. */

@@ -75,14 +75,14 @@ def lm_state_dict(seed: int, spec: LMSpec = SPEC_UNISE) -> Dict[str, Tensor]:
 
 # ------------------------------------------------------------------------------- Llama body
 
-def _rms(x: Tensor, w: Tensor, eps: float) -> Tensor:
-    var = x.float().pow(2).mean(-1, keepdim=True)  # LlamaRMSNorm
+def _rms(x: Tensor, w: Tensor, eps: float, dtype: torch.dtype = torch.float32) -> Tensor:
+    var = x.to(dtype).pow(2).mean(-1, keepdim=True)  # LlamaRMSNorm (x.float())
     return w * (x * torch.rsqrt(var + eps))
 
 
-def _rope(n0: int, n: int, hd: int, theta: float) -> Tuple[Tensor, Tensor]:
-    inv = 1.0 / (theta ** (torch.arange(0, hd, 2, dtype=torch.int64).float() / hd))
-    fr = torch.arange(n0, n0 + n).float()[:, None] * inv[None, :]
+def _rope(n0: int, n: int, hd: int, theta: float, dtype: torch.dtype = torch.float32) -> Tuple[Tensor, Tensor]:
+    inv = 1.0 / (theta ** (torch.arange(0, hd, 2, dtype=torch.int64).to(dtype) / hd))
+    fr = torch.arange(n0, n0 + n).to(dtype)[:, None] * inv[None, :]
     emb = torch.cat((fr, fr), dim=-1)
     return emb.cos(), emb.sin()
 
@@ -106,15 +106,18 @@ class KVCache:
         return self.k[i], self.v[i]
 
 
-def llm_forward(sd: Dict[str, Tensor], x: Tensor, cache: KVCache, spec: LMSpec = SPEC_UNISE) -> Tensor:
-    """CustomLlamaModel.llm_forward (llm.py:150-227) with use_cache=True: 12 Llama layers + final norm, causal."""
+def llm_forward(sd: Dict[str, Tensor], x: Tensor, cache: KVCache, spec: LMSpec = SPEC_UNISE,
+                dtype: torch.dtype = torch.float32) -> Tensor:
+    """CustomLlamaModel.llm_forward (llm.py:150-227) with use_cache=True: 12 Llama layers + final norm, causal.  `dtype`: the
+    precision of the three places the reference computes in fp32 regardless of the weights (RMSNorm statistics, RoPE table,
+    softmax); float64 with float64 weights and inputs runs the whole body in float64."""
     b, n, d = x.shape
     h, hd = spec.n_heads, spec.hidden // spec.n_heads
     past = cache.length()
-    cos, sin = _rope(past, n, hd, spec.rope_theta)
+    cos, sin = _rope(past, n, hd, spec.rope_theta, dtype)
     for i in range(spec.n_layers):
         p = f"layers.{i}"
-        y = _rms(x, sd[p + ".input_layernorm.weight"], spec.rms_eps)
+        y = _rms(x, sd[p + ".input_layernorm.weight"], spec.rms_eps, dtype)
         q = F.linear(y, sd[p + ".self_attn.q_proj.weight"]).view(b, n, h, hd).transpose(1, 2)
         k = F.linear(y, sd[p + ".self_attn.k_proj.weight"]).view(b, n, h, hd).transpose(1, 2)
         v = F.linear(y, sd[p + ".self_attn.v_proj.weight"]).view(b, n, h, hd).transpose(1, 2)
@@ -125,14 +128,14 @@ def llm_forward(sd: Dict[str, Tensor], x: Tensor, cache: KVCache, spec: LMSpec =
         if n > 1:  # causal over (past + n) keys
             mask = torch.ones(n, past + n, dtype=torch.bool).tril(diagonal=past)
             w = w.masked_fill(~mask, float("-inf"))
-        w = F.softmax(w, dim=-1, dtype=torch.float32)
+        w = F.softmax(w, dim=-1, dtype=dtype)
         o = torch.matmul(w, vv).transpose(1, 2).reshape(b, n, d)
         x = x + F.linear(o, sd[p + ".self_attn.o_proj.weight"])
-        y = _rms(x, sd[p + ".post_attention_layernorm.weight"], spec.rms_eps)
+        y = _rms(x, sd[p + ".post_attention_layernorm.weight"], spec.rms_eps, dtype)
         y = F.linear(F.silu(F.linear(y, sd[p + ".mlp.gate_proj.weight"])) * F.linear(y, sd[p + ".mlp.up_proj.weight"]),
                      sd[p + ".mlp.down_proj.weight"])
         x = x + y
-    return _rms(x, sd["norm.weight"], spec.rms_eps)
+    return _rms(x, sd["norm.weight"], spec.rms_eps, dtype)
 
 
 def build_prompt(sd: Dict[str, Tensor], task: int, enroll_feats: Optional[Tensor], mix_feats: Tensor) -> Tensor:
@@ -186,20 +189,27 @@ def sampling_distribution(logits: Tensor, temperature: float = 0.8, top_k: int =
 def generate(sd: Dict[str, Tensor], task_name: str, enroll_feats: Optional[Tensor], mix_feats: Tensor,
              semantic_length: int, global_length: int = 32, spec: LMSpec = SPEC_UNISE, forced: Optional[Tensor] = None,
              do_sample: bool = False, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
-             generator: Optional[torch.Generator] = None, logits_out: Optional[list] = None):
+             generator: Optional[torch.Generator] = None, logits_out: Optional[list] = None,
+             dtype: torch.dtype = torch.float32):
     """LLM_SFT.generate (llm_sft.py:93-195; the test path runs do_sample=False, model.py:173).  Returns (global_ids [B,G],
     semantic_ids [B,S], tokens [B, G+1+S] raw vocabulary ids, gaps [B, G+1+S] = top-1 minus top-2 logit inside the active
     range).  `forced` (raw ids [B, G+1+S]) teacher-forces the fed-back tokens so a different implementation's stream can
-    be audited step by step; `logits_out` (a list) collects the masked full-vocabulary logits of every step."""
+    be audited step by step; `logits_out` (a list) collects the masked full-vocabulary logits of every step.  `dtype`
+    (test infrastructure, not the reference): float64 runs the same program with weights, inputs and every intermediate
+    in float64 - the high-precision yardstick of the logits tests; the default float32 is the reference's arithmetic."""
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) for k, v in sd.items()}
+        enroll_feats = None if enroll_feats is None else enroll_feats.to(dtype)
+        mix_feats = mix_feats.to(dtype)
     cache = KVCache(spec.n_layers)
-    llm_forward(sd, build_prompt(sd, TASK_MAP[task_name], enroll_feats, mix_feats), cache, spec)
+    llm_forward(sd, build_prompt(sd, TASK_MAP[task_name], enroll_feats, mix_feats), cache, spec, dtype)
     b = mix_feats.shape[0]
     toks, gaps = [], []
 
     def phase(first_id: int, steps: int, lo: int, hi: int):
         ids = torch.full((b,), first_id, dtype=torch.long)
         for _ in range(steps):
-            hs = llm_forward(sd, sd["codec_embedding.weight"][ids][:, None, :], cache, spec)
+            hs = llm_forward(sd, sd["codec_embedding.weight"][ids][:, None, :], cache, spec, dtype)
             full = F.linear(hs[:, 0], sd["output_head.weight"])
             masked = torch.full_like(full, float("-inf"))  # range mask, llm_sft.py:150-153 / :180-182
             masked[:, lo:hi] = full[:, lo:hi]

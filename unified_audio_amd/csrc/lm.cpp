@@ -18,9 +18,6 @@
 namespace qa {
 int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_sos, const float* enroll_emb,
                            const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s);
-int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate,
-                       long long ldg, const float* res, long long ldr, float* y, long long ldy, int M, int N, int K,
-                       int act, hipStream_t s, float rms_eps, int dual);
 int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
                    hipStream_t s);
 
@@ -32,7 +29,6 @@ namespace {
 struct LMLayer {
     // RMSNorm weights are folded into the consuming projections (W' = W diag(w)): qkv <- input_layernorm, gate/up <- post_attention_layernorm
     ConvW qkv, o, gate, up, down;
-    const float* gate_up = nullptr;  // decode layout: per 16-column group 16 gate rows then 16 up rows (both norm-folded)
     // fused decode step (lm_decode.hip): tile-major rows; qkv_dec pairs rotary partners (i, i + hd/2) inside a tile,
     // gu_dec holds per tile NT/2 gate rows then NT/2 up rows (both norm-folded)
     const float* qkv_dec = nullptr;
@@ -78,25 +74,27 @@ struct qa_lm {
     char* ws = nullptr;
     size_t ws_cap = 0;
     Ctx ctx;
+    // test hook (qa_lm_enable_taps): the slice logits of every decode step, in an allocation of their own (never the workspace, so
+    // turning taps on cannot move a buffer of the step); tap_n: elements of logits.global / logits.semantic of the last call (-1: none)
+    bool taps = false;
+    float* tap_buf = nullptr;
+    size_t tap_cap = 0;
+    int64_t tap_n[2] = {-1, -1};
 };
 
 namespace {
 
 int vocab_of(const qa_lm_spec& s) { return 3 + s.global_size + s.semantic_size; }
 
-// y[rows, N] = epi(x[rows, K] W^T): skinny kernel for decode-sized M, implicit GEMM otherwise
-bool skinny_ok(int64_t rows, const ConvW& w) { return rows <= 32 && w.C_in % 256 == 0; }
-
+// y[rows, N] = epi(x[rows, K] W^T) on the implicit GEMM for EVERY row count (prompt adapters and prefill): its tile configurations
+// share one k order (test_conv_gemm_tile_configurations_are_bit_identical), so a sequence's prompt gets the same bits in any batch.
+// (The skinny kernel it took up to 32 rows sums in another order: a one-sequence call differed from the same sequence in a batch.)
 int lm_linear(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, const float* res = nullptr,
-              const float* gate = nullptr, int n_rows_w = -1, const float* w_ptr = nullptr, float rms_eps = 0.f) {
+              const float* gate = nullptr) {
     if (c.dry) return QA_OK;
-    const int N = n_rows_w >= 0 ? n_rows_w : w.N;
-    const float* wp = w_ptr ? w_ptr : w.w;
-    if (skinny_ok(rows, w))
-        return launch_skinny_gemm(x, w.C_in, wp, w.b, gate, N, res, N, y, N, (int)rows, N, w.C_in, ACT_NONE, c.stream, rms_eps, 0);
-    QA_REQUIRE(rms_eps == 0.f, "lm_linear: fused RMSNorm is only available on the skinny path");
+    const int N = w.N;
     qa_conv_args a{};
-    a.x = x; a.w = wp; a.bias = w.b; a.residual = res; a.gate = gate; a.y = y;
+    a.x = x; a.w = w.w; a.bias = w.b; a.residual = res; a.gate = gate; a.y = y;
     a.B = 1; a.T_in = rows; a.C_in = w.C_in; a.T_out = rows; a.N = N;
     a.ldx = w.C_in; a.ldy = N; a.ldr = N; a.ldg = N;
     a.ksize = 1; a.stride = 1;
@@ -210,14 +208,6 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
             if (folded(p + ".mlp.gate_proj.weight", I, ln2, &g) && folded(p + ".mlp.up_proj.weight", I, ln2, &u)) {
                 pend.push_back({&L.gate.w, st.add(g)});
                 pend.push_back({&L.up.w, st.add(u)});
-                if (I % 16 == 0) {  // decode layout for the dual-accumulator skinny kernel
-                    std::vector<float> gu((size_t)2 * I * d);
-                    for (int blk = 0; blk < I / 16; ++blk) {
-                        std::memcpy(&gu[(size_t)(blk * 32) * d], &g[(size_t)(blk * 16) * d], sizeof(float) * 16 * d);
-                        std::memcpy(&gu[(size_t)(blk * 32 + 16) * d], &u[(size_t)(blk * 16) * d], sizeof(float) * 16 * d);
-                    }
-                    pend.push_back({&L.gate_up, st.add(gu)});
-                }
                 if (lm->fused_ok) {
                     const int hp = lm->nt_gu / 2;
                     std::vector<float> gd((size_t)2 * I * d);
@@ -272,7 +262,7 @@ struct LMBuffers {
     float *q, *att_part, *pmax, *mlp_part;
     int *pidx, *state;
     long long *ids_g, *ids_s;
-    int cap, S_att;
+    int cap, S_att, att_tps;  // cache capacity, the attention's split count of a replayed step and 16-key tiles per split
 };
 
 struct SampleCfg {
@@ -295,25 +285,15 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
         float* vc = b.vc + i * cache_stride;
         if (!c.dry) {
             const bool last = skip_last_mlp && i == sp.n_layers - 1;  // prefill: only the KV cache of the last layer is consumed
-            const bool dec = skinny_ok(rows, L.qkv);                   // decode step: norms fused into the weight-streaming GEMMs
-            if (dec) {
-                QA_TRY(lm_linear(c, b.x, rows, L.qkv, b.qkv, nullptr, nullptr, -1, nullptr, sp.rms_eps));
-            } else {
-                QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
-                QA_TRY(lm_linear(c, b.hn, rows, L.qkv, b.qkv));
-            }
+            QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
+            QA_TRY(lm_linear(c, b.hn, rows, L.qkv, b.qkv));
             QA_TRY(launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream));
             if (last) break;
             QA_TRY(launch_attention(b.qkv, 3 * d, kc, vc, d, b.att, d, B, n, pos0 + n, (long long)max_len * d, H, hd, scale, 1, c.stream));
             QA_TRY(lm_linear(c, b.att, rows, L.o, b.x, b.x));
-            if (dec && L.gate_up) {
-                QA_TRY(launch_skinny_gemm(b.x, d, L.gate_up, nullptr, nullptr, 0, nullptr, 0, b.u, L.gate.N, (int)rows, L.gate.N, d,
-                                          ACT_NONE, c.stream, sp.rms_eps, 1));
-            } else {
-                QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
-                QA_TRY(lm_linear(c, b.hn, rows, L.gate, b.g));
-                QA_TRY(lm_linear(c, b.hn, rows, L.up, b.u, nullptr, b.g));
-            }
+            QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
+            QA_TRY(lm_linear(c, b.hn, rows, L.gate, b.g));
+            QA_TRY(lm_linear(c, b.hn, rows, L.up, b.u, nullptr, b.g));
             QA_TRY(lm_linear(c, b.u, rows, L.down, b.x, b.x));
         }
     }
@@ -323,15 +303,18 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
 // ONE decode step as 5 launches per layer + 2 (lm_decode.hip).  Everything step-dependent (position, ids column, RNG step) is read
 // from b.state on the device, so the launch arguments are identical for every step of a phase: the sequence can be captured once
 // into a hipGraph and replayed.
+// tap (taps on): [B][tap_cols][width] logits of the phase's steps for these B rows, column = the step's col
 int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long long* ids, int ids_ld, int keep, const SampleCfg& sc,
-               hipStream_t s, int pos, int col) {  // pos / col >= 0: host-driven loop; -1: read from the device state (captured step)
+               hipStream_t s, int pos, int col,  // pos / col >= 0: host-driven loop; -1: read from the device state (captured step)
+               float* tap, int tap_cols) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H, I = sp.intermediate;
     const float scale = 1.0f / std::sqrt((float)hd);
     const long long kv_bstride = (long long)b.cap * d;
     const size_t cache_stride = (size_t)B * b.cap * d;
-    // key split of the attention launch: a workgroup's 8 waves hold 2 tiles of 16 keys each per round
-    const int S_att = pos >= 0 ? std::max(1, std::min(4, (int)ceil_div(pos + 1, lm->att_split))) : b.S_att;
+    // key split of the attention launch: split sp owns the fixed tile range [sp, sp + 1) * b.att_tps (lm_attn_kernel); a host-driven
+    // step launches the splits that hold keys, a replayed one all of them (the others write identity records): same bits either way
+    const int S_att = pos >= 0 ? std::max(1, (int)ceil_div(ceil_div(pos + 1, 16), b.att_tps)) : b.S_att;
     // cross-launch prefetch (QA_LM_PF, lm_decode.h PfArgs): which launch carries the prefetch plane for which consumer
     const long long pfk = knob(K_LM_PF);
     const bool fused_mlp = lm->mlp_fused;
@@ -367,7 +350,7 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         if (pfk & 1) pf_region(qpf, 0, L.o.w, (long long)nt_o * d * 4, d / nt_o);
         QA_TRY(launch_lm_gemv(q, GM_QKV, lm->nt_qkv, s, &qpf));
         // 2. attention over the cache (pos + 1 keys), split over S_att workgroups per (sequence, head)
-        QA_TRY(launch_lm_attn(b.q, d, kc, vc, kv_bstride, d, b.att_part, B, H, hd, S_att, b.state, scale, pos, s));
+        QA_TRY(launch_lm_attn(b.q, d, kc, vc, kv_bstride, d, b.att_part, B, H, hd, S_att, b.att_tps, b.state, scale, pos, s));
         // 3. merge of the partials + o_proj + residual
         GemvArgs o = a;
         o.att_part = b.att_part; o.S = S_att;
@@ -405,10 +388,11 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
     GemvArgs hg{};
     hg.M = B; hg.rms_eps = sp.rms_eps; hg.state = b.state; hg.pos = pos; hg.H = H; hg.hd = hd; hg.d = d;
     hg.x = b.x; hg.ldx = d; hg.w = lm->head.w + (size_t)lo * d; hg.N = width; hg.K = d;
-    hg.pmax = b.pmax; hg.pidx = b.pidx; hg.logits = sc.do_sample ? b.logits : nullptr; hg.ldl = width;
+    hg.pmax = b.pmax; hg.pidx = b.pidx; hg.logits = (sc.do_sample || tap) ? b.logits : nullptr; hg.ldl = width;
     PfArgs hpf{};
     if (pfk & 8) pf_region(hpf, 0, lm->layers[0].qkv_dec, (long long)lm->nt_qkv * d * 4, 3 * d / lm->nt_qkv);
     QA_TRY(launch_lm_gemv(hg, GM_HEAD, nt, s, &hpf));
+    if (tap) QA_TRY(launch_lm_tap(b.logits, width, B, tap, tap_cols, b.state, col, s));
     // 7. next token
     if (!sc.do_sample) {
         QA_TRY(launch_lm_pick(b.pmax, b.pidx, width / nt, B, lo, b.tok, ids, ids_ld, keep, b.state, col, s));
@@ -443,7 +427,11 @@ int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int 
     const int64_t prow = (int64_t)B * L;
     LMBuffers& b = ch.b;
     b.cap = cap;
-    b.S_att = std::max(1, std::min(4, (int)ceil_div(cap, lm->att_split)));  // captured steps: sized for the cache capacity
+    // the attention's key split, from the capacity alone (never from the batch or the step): att_split keys per split, more once
+    // four splits would not cover the cache
+    const int cap_tiles = (int)ceil_div(cap, 16);
+    b.att_tps = std::max(lm->att_split / 16, (int)ceil_div(cap_tiles, 4));
+    b.S_att = (int)ceil_div(cap_tiles, b.att_tps);
     b.x = c.arena.alloc<float>(prow * d);
     b.hn = c.arena.alloc<float>(prow * d);
     b.qkv = c.arena.alloc<float>(prow * 3 * d);
@@ -545,8 +533,12 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     // ---- decode: G+1 global tokens (the last is fed to the cache but discarded), then S semantic tokens
     int pos = L;
     const bool graphs = !capturing && (multi || use_graphs());
+    // taps: logits.global [B][G + 1][global_size], then logits.semantic [B][S][semantic_size]
+    float* const tap_base = lm->taps && !c.dry ? lm->tap_buf : nullptr;
     auto phase = [&](int which, long long first_id, int steps, int lo, int width, int keep) -> int {
         const int ids_ld = keep;
+        float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * (G + 1) * sp.global_size) : nullptr;
+        auto chain_tap = [&](const Chain& ch) { return tap ? tap + (size_t)ch.b0 * steps * width : nullptr; };
         for (Chain& ch : chains)
             QA_TRY(launch_lm_phase_init(ch.b.tok, first_id, ch.B, ch.b.state, pos, which == 0, sc.seed, ch.b0, ch.s));
         if (graphs && steps > 0) {
@@ -558,13 +550,14 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
                 uint64_t key = 0x51ull;
                 for (uint64_t v : {(uint64_t)(uintptr_t)lm->ws, (uint64_t)B, (uint64_t)nc, (uint64_t)ch.b0, (uint64_t)ch.B, (uint64_t)cap, (uint64_t)L,
                                    (uint64_t)G, (uint64_t)S, (uint64_t)Ne, (uint64_t)Nm, (uint64_t)(enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
-                                   (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF)})
+                                   (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF),
+                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch)})
                     key = mix_key(key, v);
                 if (!g.exec || g.key != key) {
                     g.reset();
                     if (!lm->cap_stream) QA_HIP(hipStreamCreateWithFlags(&lm->cap_stream, hipStreamNonBlocking));
                     QA_HIP(hipStreamBeginCapture(lm->cap_stream, hipStreamCaptureModeThreadLocal));
-                    const int st = fused_step(lm, ch.b, ch.B, lo, width, ids, ids_ld, keep, sc, lm->cap_stream, -1, -1);
+                    const int st = fused_step(lm, ch.b, ch.B, lo, width, ids, ids_ld, keep, sc, lm->cap_stream, -1, -1, chain_tap(ch), steps);
                     hipGraph_t graph = nullptr;
                     const hipError_t e = hipStreamEndCapture(lm->cap_stream, &graph);
                     if (st != QA_OK) {
@@ -584,7 +577,8 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
         }
         for (int st = 0; st < steps; ++st)
             for (Chain& ch : chains)
-                QA_TRY(fused_step(lm, ch.b, ch.B, lo, width, which == 0 ? ch.b.ids_g : ch.b.ids_s, ids_ld, keep, sc, ch.s, pos + st, st));
+                QA_TRY(fused_step(lm, ch.b, ch.B, lo, width, which == 0 ? ch.b.ids_g : ch.b.ids_s, ids_ld, keep, sc, ch.s, pos + st, st,
+                                  chain_tap(ch), steps));
         pos += steps;
         return QA_OK;
     };
@@ -614,6 +608,24 @@ int ensure_ws(qa_lm* lm, size_t bytes) {
     const size_t cap = bytes + bytes / 8;
     QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->ws), cap));
     lm->ws_cap = cap;
+    return QA_OK;
+}
+
+// the tap storage of a B x (G + 1, S) call: its own allocation, grown like the workspace (the captured steps that point into the old one
+// are keyed by its address and re-captured)
+int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) != hipSuccess) (void)hipGetLastError();
+    QA_REQUIRE(cs != hipStreamCaptureStatusActive, "qa_lm_generate: taps (a test hook) are not supported under a stream capture");
+    const size_t n = (size_t)B * ((size_t)(G + 1) * lm->spec.global_size + (size_t)S * lm->spec.semantic_size);
+    if (n <= lm->tap_cap) return QA_OK;
+    QA_HIP(hipDeviceSynchronize());  // earlier calls may still be writing the old buffer
+    for (StepGraph& g : lm->graphs) g.reset();
+    if (lm->tap_buf) QA_HIP(hipFree(lm->tap_buf));
+    lm->tap_buf = nullptr;
+    lm->tap_cap = 0;
+    QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->tap_buf), sizeof(float) * n));
+    lm->tap_cap = n;
     return QA_OK;
 }
 
@@ -652,6 +664,7 @@ void qa_lm_destroy(qa_lm* lm) {
     if (lm->ev_fork) (void)hipEventDestroy(lm->ev_fork);
     lm->store.release();
     if (lm->ws) (void)hipFree(lm->ws);
+    if (lm->tap_buf) (void)hipFree(lm->tap_buf);
     delete lm;
 }
 
@@ -669,6 +682,8 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "qa_lm_generate: bad top_k / top_p");
     QA_HIP(hipSetDevice(lm->device));
     if (sc.do_sample) QA_TRY(lm_sample_prepare());
+    lm->tap_n[0] = lm->tap_n[1] = -1;
+    if (lm->taps) QA_TRY(ensure_taps(lm, B, global_length, semantic_length, stream));
     Ctx& c = lm->ctx;
     c.stream = static_cast<hipStream_t>(stream);
     c.dry = true;
@@ -692,6 +707,9 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     if (st != QA_OK) {  // an error between the fork and the join of a multi-chain call: the chains' streams may still be running out of the
         c.stream = static_cast<hipStream_t>(stream);  // workspace the next call re-uses - quiesce them (error path only)
         for (hipStream_t cs : lm->chain_streams) (void)hipStreamSynchronize(cs);
+    } else if (lm->taps) {
+        lm->tap_n[0] = B * (int64_t)(global_length + 1) * lm->spec.global_size;
+        lm->tap_n[1] = B * (int64_t)semantic_length * lm->spec.semantic_size;
     }
     return st;
 }
@@ -710,6 +728,38 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
     const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
     return lm_generate_impl(lm, task, enroll_feats, n_enroll, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
                             semantic_ids, stream);
+}
+
+int qa_lm_enable_taps(qa_lm* lm, int on) {
+    if (!lm) {
+        set_error("qa_lm_enable_taps: null handle");
+        return QA_ERR_INVALID;
+    }
+    lm->taps = on != 0;
+    return QA_OK;
+}
+
+int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* stream) {
+    if (!lm || !name) {
+        set_error("qa_lm_tap: null argument");
+        return QA_ERR_INVALID;
+    }
+    const std::string nm(name);
+    const int which = nm == "logits.global" ? 0 : nm == "logits.semantic" ? 1 : -1;
+    if (which < 0 || lm->tap_n[which] < 0) {
+        set_error("qa_lm_tap: no intermediate named '%s' in the last call (names: logits.global, logits.semantic; taps must be on)", name);
+        return QA_ERR_MISSING;
+    }
+    const int64_t n = lm->tap_n[which];
+    if (dst) {
+        if (cap < n) {
+            set_error("qa_lm_tap: '%s' has %lld elements, capacity %lld", name, (long long)n, (long long)cap);
+            return QA_ERR_INVALID;
+        }
+        const float* src = lm->tap_buf + (which == 0 ? 0 : lm->tap_n[0]);
+        QA_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    }
+    return n;
 }
 
 int qa_sample_logits(const float* logits, int64_t B, int64_t width, int64_t ld, int32_t top_k, float top_p, float temperature,

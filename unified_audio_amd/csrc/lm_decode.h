@@ -70,12 +70,14 @@ bool lm_mlp_fused_supported(int d, int I, int nt_gu);
 int launch_lm_mlp(const GemvArgs& a, int I, int ac, const float* wd, float* partial, const float* res, long long ldr, float* y, long long ldy,
                   hipStream_t s, const PfArgs* pf = nullptr);
 int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* vc, long long kv_bstride, long long ldkv,
-                   float* part, int B, int H, int hd, int S, const int* state, float scale, int pos, hipStream_t s);
+                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s);
 int launch_lm_pick(const float* pmax, const int* pidx, int n_tiles, int B, int lo, long long* tok, long long* ids, long long ids_ld,
                    int keep, int* state, int col, hipStream_t s);
 int launch_lm_phase_init(long long* tok, long long first_id, int B, int* state, int pos, int reset_step, unsigned long long seed,
                          int seq0, hipStream_t s);
 int launch_lm_advance(int* state, hipStream_t s);
+// test hook: copy the step's slice logits [B, width] into column `col` of tap [B][n_cols][width] (col < 0: the state's column)
+int launch_lm_tap(const float* logits, int width, int B, float* tap, int n_cols, const int* state, int col, hipStream_t s);
 int lm_sample_prepare();
 int launch_lm_sample(const float* logits, long long ldl, int width, int B, int lo, int top_k, float top_p, float temperature,
                      int do_sample, long long* tok, long long* ids, long long ids_ld, int keep, const int* state, hipStream_t s);

@@ -799,8 +799,10 @@ int launch_lm_mlp(const GemvArgs& a, int I, int ac, const float* wd, float* part
                   hipStream_t s, const PfArgs* pf_in) {
     QA_REQUIRE(a.M >= 1 && a.M <= LM_MAX_ROWS && a.K == a.d && lm_mlp_fused_supported(a.d, I, 16), "lm_mlp: unsupported shape M=%d d=%d I=%d", a.M, a.d, I);
     // 16-row groups up to 32 sequences (two groups x 128 workgroups: each pulls 32 KB of x instead of 64 beside its 96 KB of weights -
-    // 144.0 -> 139.4 ms per generate at 32 segments), 32-row groups above (at 64 segments four groups = 512 workgroups lose: 207 vs 196 ms)
-    const int mt = a.M <= 32 ? 1 : 2;
+    // 144.0 -> 139.4 ms per generate at 32 segments), 32-row groups above (at 64 segments four groups = 512 workgroups lose: 207 vs 196 ms).
+    // Below hidden 512 the MT = 1 and MT = 2 instances round differently (NB = 1; measured on MI355X: the same sequence's logits differed
+    // between 32 and 33 sequences, bit-equal with QA_LM_MLP_FUSED=0): one instance, 16-row groups, for every batch there
+    const int mt = (a.M <= 32 || a.d < 512) ? 1 : 2;
     const int n_part = I / ac;
     // 9 .. 16 sequences: two groups of 8 rows on the 16-row tile (rows 8 .. 15 of a group re-read its last row): x 16 KB per workgroup
     // instead of 32; with the same split of the qkv launch 111.0 -> 109.7 ms per generate at 16 segments
@@ -825,8 +827,12 @@ int launch_lm_mlp(const GemvArgs& a, int I, int ac, const float* wd, float* part
 }
 
 // ------------------------------------------------------------------------------------------------
-// Single-query attention over the KV cache.  The 16-key tiles of a (sequence, head) are dealt round-robin to the S workgroups of
-// its split and their NW waves; a wave keeps two tiles (its K and V rows) in flight.  Lane map: LPK = HD / 4 lanes cover one key
+// Single-query attention over the KV cache.  Split sp of a (sequence, head) owns the `tps` 16-key tiles [sp tps, sp tps + tps) - a
+// fixed range derived from the cache CAPACITY (lm.cpp att_tiles_per_split), never from the key count, so a key lands in the same
+// split, wave and order whatever the number of splits launched: host-driven steps launch only the splits that hold keys, a replayed
+// step all of them, and a split past the last key writes the identity record (o = 0, m = -inf, l = 0) that att_merge skips exactly -
+// the logits are bit-identical either way (tests/test_lm_logits_gpu.py).  Inside its range the tiles are dealt round-robin to the NW
+// waves; a wave keeps two tiles (its K and V rows) in flight.  Lane map: LPK = HD / 4 lanes cover one key
 // row with one float4 each, so a load instruction reads 64 / LPK whole rows of 4 * HD contiguous bytes (full cache lines; the
 // first version gave each lane 64 contiguous bytes and touched 32 lines per instruction for 1 KB of payload).  Scores are
 // reduced over the LPK lanes of a key with shuffles, softmax is online per wave, the NW wave states are merged through LDS into
@@ -837,7 +843,7 @@ template <int HD, int NW>
 __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restrict__ q, long long ldq,
                                                           const float* __restrict__ kc, const float* __restrict__ vc,
                                                           long long kv_bstride, long long ldkv, float* __restrict__ part,
-                                                          const int* __restrict__ state, float scale, int pos) {
+                                                          const int* __restrict__ state, float scale, int pos, int tps) {
     constexpr int LPK = HD / 4;    // lanes per key row
     constexpr int KPI = 64 / LPK;  // key rows per load instruction
     constexpr int NI = 16 / KPI;   // load instructions per 16-key tile (per operand)
@@ -848,6 +854,7 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
     const int kq = lane / LPK, c4 = (lane % LPK) * 4;
     const int n_keys = (pos >= 0 ? pos : state[ST_POS]) + 1;
     const int n_tiles = (n_keys + 15) >> 4;
+    const int t0 = sp * tps, t_end = min(t0 + tps, n_tiles);  // this split's tiles (empty past the last key)
     const float* kb = kc + (long long)b * kv_bstride + h * HD + c4;
     const float* vb = vc + (long long)b * kv_bstride + h * HD + c4;
     float4 qv = *reinterpret_cast<const float4*>(q + (long long)b * ldq + h * HD + c4);
@@ -855,12 +862,12 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
     float m_run = -INFINITY, l_run = 0.f;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int it = 0;; it += 2) {
-        const int ta = (it * NW + wave) * S + sp, tb = ((it + 1) * NW + wave) * S + sp;
-        if (ta >= n_tiles) break;
+        const int ta = t0 + it * NW + wave, tb = t0 + (it + 1) * NW + wave;
+        if (ta >= t_end) break;
         float4 kt[2][NI], vt[2][NI];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const int t = u == 0 ? ta : min(tb, n_tiles - 1);  // a missing second tile re-reads a valid one and is skipped below
+            const int t = u == 0 ? ta : min(tb, t_end - 1);  // a missing second tile re-reads a valid one and is skipped below
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const int row = min(t * 16 + j * KPI + kq, n_keys - 1);  // clamp: rows past n_keys are uninitialised cache memory
@@ -871,7 +878,7 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int t = u == 0 ? ta : tb;
-            if (t >= n_tiles) break;
+            if (t >= t_end) break;
             float sc[NI];
             float tmax = -INFINITY;
 #pragma unroll
@@ -938,18 +945,18 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
 }
 
 int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* vc, long long kv_bstride, long long ldkv,
-                   float* part, int B, int H, int hd, int S, const int* state, float scale, int pos, hipStream_t s) {
-    QA_REQUIRE(S >= 1 && S <= 4, "lm_attn: bad split count %d", S);
+                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s) {
+    QA_REQUIRE(S >= 1 && S <= 4 && tps >= 1, "lm_attn: bad split count %d (%d tiles each)", S, tps);
     const dim3 grid(H, B, S);
     switch (hd) {
         case 64:
-            hipLaunchKernelGGL((lm_attn_kernel<64, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos);
+            hipLaunchKernelGGL((lm_attn_kernel<64, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps);
             break;
         case 128:
-            hipLaunchKernelGGL((lm_attn_kernel<128, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos);
+            hipLaunchKernelGGL((lm_attn_kernel<128, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps);
             break;
         case 32:
-            hipLaunchKernelGGL((lm_attn_kernel<32, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos);
+            hipLaunchKernelGGL((lm_attn_kernel<32, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps);
             break;
         default: set_error("lm_attn: head_dim=%d unsupported", hd); return QA_ERR_UNSUPPORTED;
     }
@@ -1013,6 +1020,21 @@ int launch_lm_pick(const float* pmax, const int* pidx, int n_tiles, int B, int l
                    int keep, int* state, int col, hipStream_t s) {
     hipLaunchKernelGGL(lm_pick_kernel, dim3((unsigned)ceil_div(B, PICK_SEQS)), dim3(64 * PICK_SEQS), 0, s, pmax, pidx, n_tiles, B, lo, tok, ids,
                        ids_ld, keep, state, col);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// Test hook (qa_lm_enable_taps): tap[b][col][j] = logits[b][j] for the step's column col (read from the loop state when col_arg < 0, so
+// the same launch is right inside a replayed step graph).  Runs between the head launch and the pick / sample launch, which advances col.
+__global__ void lm_tap_kernel(const float* __restrict__ logits, int width, float* __restrict__ tap, int n_cols, const int* __restrict__ state,
+                              int col_arg) {
+    const int col = col_arg >= 0 ? col_arg : state[ST_COL];
+    const int b = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= n_cols || j >= width) return;
+    tap[((long long)b * n_cols + col) * width + j] = logits[(long long)b * width + j];
+}
+int launch_lm_tap(const float* logits, int width, int B, float* tap, int n_cols, const int* state, int col, hipStream_t s) {
+    hipLaunchKernelGGL(lm_tap_kernel, dim3((unsigned)ceil_div(width, 256), (unsigned)B), dim3(256), 0, s, logits, width, tap, n_cols, state, col);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

@@ -93,6 +93,25 @@ class LLM_SFT:
                                                 temperature, top_k, top_p, gids.data_ptr(), sids.data_ptr(), stream))
         return gids, sids
 
+    def enable_taps(self, on: bool = True):
+        """Test hook: make generate record the slice logits of every decode step (qa_lm_enable_taps)."""
+        if not self._handle.value:
+            raise _lib.QuarkAudioError(-3, "LLM_SFT has no weights: call load_state_dict first")
+        _lib.check(self._lib.qa_lm_enable_taps(self._handle, int(on)))
+        return self
+
+    def tap(self, name: str) -> torch.Tensor:
+        """Test hook: flat fp32 copy of a snapshot of the last generate: "logits.global" ([B, global_length + 1, global_size]) or
+        "logits.semantic" ([B, semantic_length, semantic_size])."""
+        n = self._lib.qa_lm_tap(self._handle, name.encode(), None, 0, None)
+        if n < 0:
+            _lib.check(int(n))
+        out = torch.empty(int(n), dtype=torch.float32, device=self.device)
+        n2 = self._lib.qa_lm_tap(self._handle, name.encode(), out.data_ptr(), n, torch.cuda.current_stream(self.device).cuda_stream)
+        if n2 < 0:
+            _lib.check(int(n2))
+        return out
+
 
 def sample_logits(logits: torch.Tensor, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
                   do_sample: bool = True, seed: Optional[int] = None) -> torch.Tensor:
