@@ -221,8 +221,9 @@ int64_t qa_resolve_frame(int64_t r, int64_t L, int32_t max_pad, int32_t pad_mode
 /* ---- measurement hook (bench.py) ------------------------------------------------------------------------
  * Between qa_profile_begin() and qa_profile_end() every implicit-GEMM launch is bracketed by HIP events recorded on
  * the stream it is launched on.  qa_profile_end fills out[cfg*4 + {0,1,2,3}] = {algorithmic FLOPs, elapsed ms, launches,
- * algorithmic bytes (input frames + weights + outputs + fused residual / gate reads, each once)} for the five tile
- * configurations cfg = 0 (128x32), 1 (128x64), 2 (128x128), 3 (64x128), 4 (64x64); n_out >= 20.  Not thread-safe; process-wide. */
+ * algorithmic bytes (input frames + weights + outputs + fused residual / gate reads, each once)} for the six tile
+ * configurations cfg = 0 (128x32), 1 (128x64), 2 (128x128), 3 (64x128), 4 (64x64), 5 (256x128); n_out >= 24.  Not thread-safe;
+ * process-wide. */
 int qa_profile_begin(void);
 int qa_profile_end(double* out, int32_t n_out);
 /* qa_profile_begin_ex(mask): bit 0 = the implicit-GEMM launches (= qa_profile_begin), bit 1 = the byte-bound kernels (norms, depthwise

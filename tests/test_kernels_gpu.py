@@ -30,7 +30,7 @@ CONV_CASES = [
     dict(B=2, T=330, Cin=64, N=160, k=16, stride=8, mode="reflect"),          # ksize > 8: source-frame table rebuilt mid-tile (128x64/128 tiles)
     dict(B=3, T=97, Cin=32, N=136, k=9, stride=4, mode="reflect", res=True),  # ragged M, N % 8 == 0 only, residual, two table windows
     dict(B=1, T=300, Cin=96, N=66, k=3, mode="zero", gate=True, act=3),       # N % 4 != 0: scalar epilogue path
-    dict(B=2, T=129, Cin=512, N=512, k=1, gamma=True, res=True, post=1),      # K = 512 (BK = 16 variant), every epilogue stage but the gate
+    dict(B=2, T=129, Cin=512, N=512, k=1, gamma=True, res=True, post=1),      # K = 512, every epilogue stage but the gate (12 tiles: BK = 32 at the default knobs; BK = 16: tests/test_conv_gemm_gpu.py)
 ]
 
 
@@ -101,7 +101,7 @@ def test_conv1d_cl_matches_torch(qa_lib, gpu_device, case):
 
 @pytest.mark.parametrize("case", [0, 1, 5, 7, 8, 9, 11, 13, 14, 16])
 def test_conv_gemm_tile_configurations_are_bit_identical(qa_lib, gpu_device, knob, case):
-    """Every tile configuration of conv_gemm (QA_GEMM_CFG 1 .. 4: 128x64, 128x128 and the 64-row tiles 64x128 / 64x64 of round 4)
+    """Every tile configuration of conv_gemm (QA_GEMM_CFG 0 .. 5: 128x32, 128x64, 128x128, the 64-row tiles 64x128 / 64x64 and 256x128)
     accumulates an output element over k in the same order, so the choice of tile - which the cost model makes from M, i.e. from
     the batch size - never changes a bit: required for `a clip's result does not depend on the batch it rides in`."""
     c = CONV_CASES[case]
@@ -116,13 +116,13 @@ def test_conv_gemm_tile_configurations_are_bit_identical(qa_lib, gpu_device, kno
     res = torch.randn(B, T_out, N, generator=g).to(gpu_device) if c.get("res") else None
     gate = torch.randn(B, T_out, N, generator=g).to(gpu_device) if c.get("gate") else None
     outs = {}
-    for cfg in (-1, 1, 2, 3, 4):
+    for cfg in (-1, 0, 1, 2, 3, 4, 5):
         knob("QA_GEMM_CFG", cfg)
         outs[cfg] = conv1d_cl(qa_lib, x, w, bias, stride=stride, prologue=c.get("prologue", 0), act=c.get("act", 0), post_act=c.get("post", 0),
                               gamma=gamma, residual=res, gate=gate, T_out=T_out).clone()
     torch.cuda.synchronize()
     assert torch.isfinite(outs[-1]).all()
-    for cfg in (1, 2, 3, 4):
+    for cfg in (0, 1, 2, 3, 4, 5):
         assert torch.equal(outs[cfg], outs[-1]), f"QA_GEMM_CFG={cfg} differs from the cost model's choice"
 
 

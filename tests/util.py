@@ -26,15 +26,28 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
 
 
 def conv1d_cl(lib, x, w, bias=None, *, stride=1, pad=(0, 0), pad_mode=0, prologue=0, act=0, gamma=None, residual=None,
-              gate=None, post_act=0, T_out=None):
-    """Call qa_conv1d_cl.  x [B,T,C] cuda, w [N,k,C] cuda (library layout).  Returns y [B,T_out,N]."""
+              gate=None, post_act=0, T_out=None, in_rep=1, ldx=None, ldy=None, ldr=None, ldg=None, y_offset=None, guard=False):
+    """Call qa_conv1d_cl.  x [B,T,C] cuda, w [N,k,C] cuda (library layout).  Returns y [B,T_out,N].
+
+    x, residual and gate may be strided views (see `strided_rows`): their row strides are passed as ldx / ldr / ldg (an explicit
+    value must agree with the view).  With `guard` (implied by ldy or y_offset), y is a view with row stride ldy (default N), starting
+    y_offset floats into a buffer whose every other element holds a sentinel (`guarded_out`); after the call every element of y must
+    have been written and no sentinel may have changed, else AssertionError."""
     from unified_audio_amd import _lib
 
     B, T, Cin = x.shape
     N, k, _ = w.shape
     if T_out is None:
-        T_out = (T + pad[0] + pad[1] - k) // stride + 1
-    y = torch.full((B, T_out, N), float("nan"), device=x.device)
+        T_out = (T * max(in_rep, 1) + pad[0] + pad[1] - k) // stride + 1
+    ldx = _row_stride(x, ldx, T)
+    ldr = _row_stride(residual, ldr, T_out) if residual is not None else N
+    ldg = _row_stride(gate, ldg, T_out) if gate is not None else N
+    guard = guard or ldy is not None or y_offset is not None
+    if guard:
+        buf, y = guarded_out(B * T_out, N, ldy or N, y_offset or 0, x.device)
+        y = y.view(B, T_out, N)
+    else:
+        y = torch.full((B, T_out, N), float("nan"), device=x.device)
     a = _lib.qa_conv_args()
     a.x, a.w, a.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
     a.bias = bias.data_ptr() if bias is not None else None
@@ -42,11 +55,128 @@ def conv1d_cl(lib, x, w, bias=None, *, stride=1, pad=(0, 0), pad_mode=0, prologu
     a.residual = residual.data_ptr() if residual is not None else None
     a.gate = gate.data_ptr() if gate is not None else None
     a.B, a.T_in, a.C_in, a.T_out, a.N = B, T, Cin, T_out, N
-    a.ldx, a.ldy, a.ldr, a.ldg = Cin, N, N, N
+    a.ldx, a.ldy, a.ldr, a.ldg = ldx, y.stride(1), ldr, ldg
     a.ksize, a.stride, a.pad_left, a.pad_right, a.pad_mode = k, stride, pad[0], pad[1], pad_mode
     a.prologue, a.act, a.post_act = prologue, act, post_act
+    a.in_rep = in_rep
     _lib.check(lib.qa_conv1d_cl(C.byref(a), torch.cuda.current_stream().cuda_stream))
+    if guard:
+        check_guarded_out(buf, y.view(B * T_out, N), y_offset or 0)
     return y
+
+
+def _row_stride(t, ld, rows_per_item):
+    """Row stride of a [B, rows, C] operand that the C-ABI reads as rows of `ld` floats (item b at b * rows * ld)."""
+    ld = t.stride(1) if ld is None else ld
+    assert t.stride(2) == 1 and t.stride(1) == ld and (t.shape[0] == 1 or t.stride(0) == rows_per_item * ld), (t.stride(), ld)
+    return ld
+
+
+def strided_rows(t, ld, offset=0, generator=None):
+    """t [B, R, C] -> an equal view whose rows are `ld` floats apart, at column `offset` of each row: the other columns, and one
+    row of slack after the last, hold other random numbers, so a kernel that reads outside the view gets a wrong answer
+    but stays inside the allocation."""
+    B, R, Cc = t.shape
+    assert offset + Cc <= ld
+    buf = torch.randn((B * R + 1) * ld, generator=generator).to(t.device)
+    view = buf[:B * R * ld].view(B, R, ld)[..., offset:offset + Cc]
+    view.copy_(t)
+    return view
+
+
+SENTINEL_BITS = 0x7F7ADEAD  # a finite float (~3.3e38) that no output of these tests comes near
+GUARD_TAIL_ROWS = 256       # the tallest conv_gemm tile: a store that ignores the row mask lands here
+
+
+def guarded_out(M, N, ldy, head, device):
+    """(buffer, y): y [M, N] with row stride ldy starts `head` floats into the buffer and is NaN; the gap columns (ldy > N), the
+    head and GUARD_TAIL_ROWS rows after the last hold SENTINEL_BITS."""
+    assert ldy >= N
+    buf = torch.empty(head + (M + GUARD_TAIL_ROWS) * ldy, dtype=torch.float32, device=device)
+    buf.view(torch.int32).fill_(SENTINEL_BITS)
+    y = buf[head:head + M * ldy].view(M, ldy)[:, :N]
+    y.fill_(float("nan"))
+    return buf, y
+
+
+def check_guarded_out(buf, y, head):
+    """Every element of y [M, N] was written, and nothing else in its buffer (guarded_out)."""
+    M, N = y.shape
+    ldy = y.stride(0)
+    outside = torch.ones(buf.numel(), dtype=torch.bool, device=buf.device)
+    outside[head:head + M * ldy].view(M, ldy)[:, :N] = False
+    bits = buf.view(torch.int32)
+    bad = int((bits[outside] != SENTINEL_BITS).sum())
+    assert bad == 0, f"{bad} elements outside the [{M}, {N}] output (ldy {ldy}, offset {head}) were overwritten"
+    unwritten = int(torch.isnan(y).sum())
+    assert unwritten == 0, f"{unwritten} of the {M * N} output elements were never written"
+
+
+def conv_ref(x, w, bias, case, dtype=torch.float64, *, gamma=None, residual=None, gate=None, rows=None):
+    """Plain CPU restatement of qa_conv1d_cl in `dtype` (float64: the truth; float32: the yardstick), the op sequence of
+    tests/test_kernels_gpu._ref_conv plus the epilogue: ELU prologue, repeat_interleave by in_rep, zero or reflect padding
+    (the reference's pad1d, short-input rule included), windows . weights + bias, silu(gate) *, act, * gamma, + residual, post_act.
+
+    x [B,T,C], w [N,k,C], gate / residual [B,T_out,N] (CPU, any strides); case: stride, pad (left, right), pad_mode (0 zero,
+    1 reflect), prologue, in_rep, act, post (codes of conv1d_cl), T_out.  `rows`: the flat output rows (b * T_out + t) to compute,
+    default all.  Returns (y [R, N], scale [R, N]) where scale = |g| |gamma| (sum_k |a_k w_k| + |b|) + |r| is the magnitude the
+    rounding error of an fp32 evaluation is proportional to (a = the prologue'd im2col row, g = silu(gate)).  The library evaluates
+    ELU(v) < 0 as exp(v) - 1 (csrc/common.h), whose rounding error is relative to exp(v), not to ELU(v): every ELU, prologue
+    included, adds exp(v) for v < 0 to the scale of what it produces."""
+    from oracle.hcodec_ref import _pad1d_reflect
+
+    B, T, Cin = x.shape
+    N, k, _ = w.shape
+    stride, (pl, pr) = case.get("stride", 1), case.get("pad", (0, 0))
+    rep = max(case.get("in_rep", 1), 1)
+    T_out = case["T_out"]
+    rows = torch.arange(B * T_out) if rows is None else torch.as_tensor(rows, dtype=torch.long)
+    b_of, t_of = rows // T_out, rows % T_out
+    win = torch.empty(len(rows), k * Cin, dtype=dtype)
+    mag = torch.empty(len(rows), k * Cin, dtype=dtype)  # |a| for the error scale
+    for b in b_of.unique().tolist():
+        sel = (b_of == b).nonzero()[:, 0]
+        xb = x[b].to(dtype).T[None]  # [1, C, T]
+        mb = xb.abs()
+        if case.get("prologue"):
+            mb = F.elu(xb).abs() + _elu_exp(xb)
+            xb = F.elu(xb)
+        idx = t_of[sel, None] * stride + torch.arange(k)
+        for src, dst in ((xb, win), (mb, mag)):
+            if rep > 1:
+                src = src.repeat_interleave(rep, -1)
+            xp = _pad1d_reflect(src, pl, pr) if case.get("pad_mode", 0) == 1 else F.pad(src, (pl, pr))
+            dst[sel] = xp[0].T[idx].reshape(len(sel), k * Cin)  # [T_padded, C] -> windows
+    wf = w.to(dtype).reshape(N, k * Cin)
+    y = win @ wf.T
+    scale = mag @ wf.abs().T
+    if bias is not None:
+        y = y + bias.to(dtype)
+        scale = scale + bias.to(dtype).abs()
+    if gate is not None:
+        g = F.silu(gate.reshape(-1, N)[rows].to(dtype))
+        y, scale = g * y, g.abs() * scale
+    if case.get("act", 0) == 1:
+        scale = scale + _elu_exp(y)
+    y = act_ref(y, case.get("act", 0))
+    if gamma is not None:
+        y, scale = y * gamma.to(dtype), scale * gamma.to(dtype).abs()
+    if residual is not None:
+        r = residual.reshape(-1, N)[rows].to(dtype)
+        y, scale = y + r, scale + r.abs()
+    if case.get("post", 0) == 1:
+        scale = scale + _elu_exp(y)
+    y = act_ref(y, case.get("post", 0))
+    return y, scale
+
+
+def _elu_exp(v):
+    return torch.where(v < 0, v.clamp_max(0).exp(), torch.zeros_like(v))
+
+
+def scaled_err(y, truth, scale):
+    """max_{m,n} |y - truth| / (scale + tiny): the elementwise error in units of the operation's own magnitude (conv_ref)."""
+    return float(((y.double() - truth.double()).abs() / (scale.double() + 1e-30)).max())
 
 
 def act_ref(v, code):

@@ -194,7 +194,7 @@ int qa_profile_end_hbm(double* out, int32_t n_out) {
     return QA_OK;
 }
 
-// out[cfg*4 + {0,1,2,3}] = {algorithmic FLOPs, elapsed ms, launches, algorithmic bytes} for cfg in {128x32, 128x64, 128x128, 64x128, 64x64}
+// out[cfg*4 + {0,1,2,3}] = {algorithmic FLOPs, elapsed ms, launches, algorithmic bytes} for cfg in {128x32, 128x64, 128x128, 64x128, 64x64, 256x128}
 int qa_profile_end(double* out, int32_t n_out) {
     g_prof_on = false;
     g_prof_hbm = false;

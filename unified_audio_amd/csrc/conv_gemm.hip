@@ -407,16 +407,6 @@ template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     QA_REQUIRE(p.prologue == ACT_NONE || p.prologue == ACT_ELU, "conv_gemm: prologue %d unsupported", p.prologue);
     const long long tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    const bool prof = profile_enabled();
-    if (prof) {
-        const int cfg = BM == 256 ? PROF_CFG_256x128 : BM == 64 ? (BN == 64 ? PROF_CFG_64x64 : PROF_CFG_64x128) : (BN == 32 ? PROF_CFG_128x32 : (BN == 64 ? PROF_CFG_128x64 : PROF_CFG_128x128));
-        const double n = p.algo_n ? p.algo_n : p.N, k = p.algo_k ? p.algo_k : p.K;
-        // algorithmic bytes: every input frame, weight and output element once (+ fused residual / gate reads)
-        const double out_elems = p.am_dist ? 2.0 * (double)p.M * p.am_ld + p.M + n  // arg-min epilogue: (dist, idx) per 32 columns + |r|^2 + |e|^2
-                                            : (double)p.M * n * (1.0 + (p.res ? 1.0 : 0.0) + (p.gate ? 1.0 : 0.0));
-        const double elems = (double)p.B * p.T_in * p.C_in + n * k + out_elems;
-        profile_record_begin(cfg, 2.0 * (double)p.M * n * k, 4.0 * elems, stream, &p);
-    }
     // BK = 16 chunks need 45 KB / 35 KB of LDS, so 3-4 workgroups are co-resident per CU (BK = 32: 2) and cover each
     // other's barriers, prologues and epilogues: +10..25 % on the K = 512 layers of the aggregator stacks, +3..5 % on
     // K = 768..3072 (per-shape sweep, tools/gemm_bench.py with QA_GEMM_BK16=0 / default).  QA_GEMM_BK16 = largest K that
@@ -430,6 +420,22 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     const bool linear = linear_on && p.ksize == 1 && p.stride == 1 && p.pad_left == 0 && p.in_rep <= 1 && p.T_in == p.T_out &&
                         (p.dilation <= 1);
     const bool bk16 = BN >= 64 && p.prologue != ACT_ELU && ((p.K <= bk16_max_k && tiles >= bk16_min_tiles) || p.C_in % 32 != 0);
+    // the K loop runs K / BK whole chunks and the table form reads each chunk from ONE tap: a BK that does not divide K (and, with the
+    // table, C_in) would drop the tail of K or read past a tap's C_in channels - into the next frame or the next channel group
+    const int bk = BM == 256 || bk16 ? 16 : 32;
+    const bool table = BM != 256 && (!linear || p.prologue == ACT_ELU);  // the ELU prologue exists in the table form only
+    QA_REQUIRE(p.K % bk == 0 && (!table || p.C_in % bk == 0),
+               "conv_gemm: the %dx%d tile's BK = %d K chunk does not divide K=%d / C_in=%d", BM, BN, bk, p.K, p.C_in);
+    const bool prof = profile_enabled();
+    if (prof) {
+        const int cfg = BM == 256 ? PROF_CFG_256x128 : BM == 64 ? (BN == 64 ? PROF_CFG_64x64 : PROF_CFG_64x128) : (BN == 32 ? PROF_CFG_128x32 : (BN == 64 ? PROF_CFG_128x64 : PROF_CFG_128x128));
+        const double n = p.algo_n ? p.algo_n : p.N, k = p.algo_k ? p.algo_k : p.K;
+        // algorithmic bytes: every input frame, weight and output element once (+ fused residual / gate reads)
+        const double out_elems = p.am_dist ? 2.0 * (double)p.M * p.am_ld + p.M + n  // arg-min epilogue: (dist, idx) per 32 columns + |r|^2 + |e|^2
+                                            : (double)p.M * n * (1.0 + (p.res ? 1.0 : 0.0) + (p.gate ? 1.0 : 0.0));
+        const double elems = (double)p.B * p.T_in * p.C_in + n * k + out_elems;
+        profile_record_begin(cfg, 2.0 * (double)p.M * n * k, 4.0 * elems, stream, &p);
+    }
     if constexpr (BM == 256) {  // r06 experiment (QA_GEMM_256): LINEAR layers only, BK = 16 (61 KB of LDS: two workgroups per CU)
         QA_REQUIRE(linear && p.prologue != ACT_ELU, "conv_gemm: the 256 x 128 tile exists for LINEAR layers only");
         hipLaunchKernelGGL((conv_gemm_kernel<256, 128, 2, 2, false, 16, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
@@ -525,7 +531,9 @@ int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
         }
     }
     switch (cfg) {
-        case PROF_CFG_128x32: return launch_cfg<128, 32, 4, 1>(q, stream);
+        case PROF_CFG_128x32:  // only BK = 32 exists for this tile: C_in % 32 != 0 (possible only when forced, N > 32) takes 128 x 64
+            if (p.C_in % 32 != 0) return launch_cfg<128, 64, 2, 2>(q, stream);
+            return launch_cfg<128, 32, 4, 1>(q, stream);
         case PROF_CFG_128x64: return launch_cfg<128, 64, 2, 2>(q, stream);
         case PROF_CFG_64x128: return launch_cfg<64, 128, 1, 4>(q, stream);
         case PROF_CFG_64x64: return launch_cfg<64, 64, 2, 2>(q, stream);
