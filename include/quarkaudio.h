@@ -204,7 +204,7 @@ typedef struct qa_conv_args {
     int64_t ldy, ldr, ldg;
     int32_t ksize, stride, pad_left, pad_right, pad_mode;
     int32_t prologue;      /* 0 none, 1 ELU applied to x on load */
-    int32_t act;           /* 0 none, 1 ELU, 2 GELU(erf), 3 SiLU */
+    int32_t act;           /* 0 none, 1 ELU, 2 GELU(erf), 3 SiLU, 6 ReLU */
     int32_t post_act;      /* applied after the residual add: 0 none, 1 ELU */
     int32_t in_rep;        /* 0/1 none; r > 1: x is read as x.repeat_interleave(r) along frames (zero padding only) */
 } qa_conv_args;
@@ -365,6 +365,67 @@ int qa_bicodec_detokenize(qa_bicodec* h, const int64_t* semantic_tokens, const i
 /* test hooks, as qa_hcodec_enable_taps / qa_hcodec_tap: z_q, d_vector, prenet.down, prenet.backbone, prenet.out, gen.block{i} */
 int qa_bicodec_enable_taps(qa_bicodec* h, int on);
 int64_t qa_bicodec_tap(qa_bicodec* h, const char* name, float* dst, int64_t cap, void* stream);
+
+/* ---- BiCodec encoder side: tokenize (semantic + global tokens) -----------------------------------------------------
+ * BiCodec.get_semantic_tokens(batch) (QuarkAudio-UniSE/model/bicodec/bicodec.py:167-172): the XLSR-53 feature mix [B, N, 1024]
+ * -> Encoder (VocosBackbone 1024 -> 384 with vocos_layers ConvNeXt layers, two ratio-1 SamplingBlocks (3 x) each followed by a
+ * 2-layer VocosBackbone, Linear 384 -> latent_dim; modules/encoder_decoder/feat_encoder.py:29-92) -> FactorizedVectorQuantize.tokenize
+ * (weight-normed 1x1 in_project latent_dim -> codebook_dim, F.normalize of latents and codebook, nearest code with the first
+ * index winning a tie; modules/vq/factorized_vector_quantize.py:148-152,169-187), and BiCodec.get_global_tokens(batch)
+ * (bicodec.py:174-178): mel spectrogram of the reference clip (torchaudio MelSpectrogram, power 1, slaney, no log) -> ECAPA-TDNN latent
+ * (speaker/ecapa_tdnn.py, the pooling / x-vector head is not needed) -> PerceiverResampler (speaker/perceiver_encoder.py) -> ResidualFSQ
+ * indices (fsq/residual_fsq.py, one quantizer).  A handle of its own: a detokenize-only checkpoint never needs these weights.
+ * Weights: the `BiCodec.state_dict()` entries encoder.*, quantizer.in_project.* (weight_g / weight_v or plain weight),
+ * quantizer.codebook.weight, speaker_encoder.speaker_encoder.* (BatchNorm running statistics folded into per-channel epilogue
+ * constants), speaker_encoder.perceiver_sampler.* and speaker_encoder.quantizer.project_in.*. */
+typedef struct qa_bicodec_enc_spec {
+    int32_t input_channels;    /* 1024  encoder.input_channels (XLSR-53 hidden width) */
+    int32_t vocos_dim;         /* 384 */
+    int32_t vocos_inter;       /* 2048 */
+    int32_t vocos_layers;      /* 12    layers of the input backbone (the two backbones behind the SamplingBlocks have 2) */
+    int32_t latent_dim;        /* 1024  encoder.out_channels = quantizer.input_dim */
+    int32_t codebook_size;     /* 8192 */
+    int32_t codebook_dim;      /* 8 */
+    /* global tokens: mel_params (bicodec.py:201-221) and the speaker encoder (speaker_encoder.py:33-60) */
+    int32_t sample_rate;       /* 16000 */
+    int32_t n_fft;             /* 1024 */
+    int32_t win_length;        /* 640   must be 2 * hop_length (the framed-signal DFT) */
+    int32_t hop_length;        /* 320 */
+    float mel_fmin;            /* 10 */
+    float mel_fmax;            /* 0 = sample_rate / 2 (mel_fmax: null) */
+    int32_t mel_dim;           /* 128   num_mels = speaker_encoder.input_dim */
+    int32_t ecapa_channels;    /* 512 */
+    int32_t spk_latent_dim;    /* 128 */
+    int32_t token_num;         /* 32 */
+    int32_t n_levels;          /* 6 */
+    int32_t levels[8];         /* 4,4,4,4,4,4 */
+    int32_t perceiver_depth;   /* 2 */
+    int32_t perceiver_heads;   /* 8 */
+    int32_t perceiver_dim_head;/* 64 */
+} qa_bicodec_enc_spec;
+typedef struct qa_bicodec_enc qa_bicodec_enc;
+int qa_bicodec_enc_create(qa_bicodec_enc** out, const qa_bicodec_enc_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device);
+void qa_bicodec_enc_destroy(qa_bicodec_enc* h);
+/* feat fp32 [B, N, input_channels] channel-last (the reference's batch["feat"], contiguous) -> semantic_out int64 [B, N] */
+int qa_bicodec_get_semantic_tokens(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, int64_t* semantic_out, void* stream);
+/* wav fp32 [B, T] -> global_out int32 [B, token_num] (the reference's [B, 1, token_num]).  The mel spectrogram is taken of the
+ * reference clip of ref_len samples: wav[b, k % T] for k < ref_len, BiCodecTokenizer.get_ref_clip's tile-and-truncate
+ * (audio_tokenizer.py:54-72) as index arithmetic; ref_len <= 0 takes the rows as they are (BiCodec.get_global_tokens on batch["ref_wav"]).
+ * ref_len must exceed n_fft / 2 (the reflect padding of the centred STFT). */
+int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, int64_t ref_len, int32_t* global_out,
+                                 void* stream);
+/* BiCodec.tokenize(batch) (bicodec.py:151-165): both of the above on one stream */
+int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref, int64_t ref_len,
+                        int64_t* semantic_out, int32_t* global_out, void* stream);
+/* test hooks: enc.backbone (input backbone), enc.down (after the SamplingBlock stages), enc.out [B, N, latent_dim],
+ * vq.latent [B * N, codebook_dim] (in_project output after F.normalize); mel [B, frames, mel_dim], ecapa.layer1 [B, frames, C],
+ * ecapa.layers234 [B, frames, 3 C] (the concatenation of the three SE-Res2 block outputs), ecapa.latent [B, frames, 1536],
+ * perceiver.out [B, token_num, spk_latent_dim], fsq.bounded [B, token_num, n_levels] */
+int qa_bicodec_enc_enable_taps(qa_bicodec_enc* h, int on);
+int64_t qa_bicodec_enc_tap(qa_bicodec_enc* h, const char* name, float* dst, int64_t cap, void* stream);
+/* Wav2Vec2FeatureExtractor(do_normalize=True) on equal-length rows (audio_tokenizer.py:74-90, nothing padded):
+ * out[b, :] = (wav[b, :] - mean) / sqrt(var + eps) with the population variance; eps = 1e-7 in the reference.  out may alias wav. */
+int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float eps, void* stream);
 
 /* ---- UniSE AR-LM ------------------------------------------------------------------------------------ */
 

@@ -73,6 +73,17 @@ class qa_bicodec_spec(C.Structure):
     ]
 
 
+class qa_bicodec_enc_spec(C.Structure):
+    _fields_ = [
+        ("input_channels", C.c_int32), ("vocos_dim", C.c_int32), ("vocos_inter", C.c_int32), ("vocos_layers", C.c_int32),
+        ("latent_dim", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32),
+        ("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("win_length", C.c_int32), ("hop_length", C.c_int32),
+        ("mel_fmin", C.c_float), ("mel_fmax", C.c_float), ("mel_dim", C.c_int32), ("ecapa_channels", C.c_int32),
+        ("spk_latent_dim", C.c_int32), ("token_num", C.c_int32), ("n_levels", C.c_int32), ("levels", C.c_int32 * 8),
+        ("perceiver_depth", C.c_int32), ("perceiver_heads", C.c_int32), ("perceiver_dim_head", C.c_int32),
+    ]
+
+
 class qa_ssl_spec(C.Structure):
     _fields_ = [
         ("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8),
@@ -143,6 +154,15 @@ SYMBOLS = {
     "qa_bicodec_detokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "qa_bicodec_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "qa_bicodec_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "qa_bicodec_enc_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_bicodec_enc_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
+    "qa_bicodec_enc_destroy": (None, [C.c_void_p]),
+    "qa_bicodec_get_semantic_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_bicodec_get_global_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_bicodec_tokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "qa_bicodec_enc_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
+    "qa_bicodec_enc_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "qa_wav_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_void_p]),
     "qa_lm_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_lm_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
     "qa_lm_destroy": (None, [C.c_void_p]),
     "qa_lm_generate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,

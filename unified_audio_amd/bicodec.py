@@ -1,10 +1,14 @@
-"""Python mirror of the reference's BiCodec detokenizer, backed by libquarkaudio_hip.so.
+"""Python mirror of the reference's BiCodec, backed by libquarkaudio_hip.so.
 
     BiCodec.detokenize           <->  QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199
     BiCodecTokenizer.detokenize  <->  QuarkAudio-UniSE/model/bicodec/audio_tokenizer.py (called at model/model.py:193,223)
+    wav_normalize                <->  the Wav2Vec2FeatureExtractor normalisation in front of XLSR-53 (audio_tokenizer.py:74-90)
 
-Only the decode side is on the UniSE inference path (the LM produces the tokens); `tokenize` (wav2vec2-BERT features, ECAPA speaker
-encoder) belongs to training / data preparation and is not offered.
+The decode side is the UniSE inference path (the LM produces the tokens); `tokenize` builds the LM's training targets
+(model/model.py:96-160) and turns a speaker prompt into its 32 global tokens.
+
+    BiCodec.tokenize / get_semantic_tokens / get_global_tokens  <->  bicodec.py:151-180
+    BiCodecTokenizer.tokenize                                    <->  audio_tokenizer.py:93-103
 """
 from __future__ import annotations
 
@@ -128,6 +132,139 @@ class BiCodecSpec:
 SPEC_BICODEC = BiCodecSpec()
 
 
+@dataclass(frozen=True)
+class BiCodecEncoderSpec:
+    """The `encoder`, `quantizer`, `mel_params` and `speaker_encoder` blocks of the BiCodec `config.yaml` as `BiCodec.tokenize` uses them
+    (Encoder, feat_encoder.py:29-92; FactorizedVectorQuantize.tokenize, factorized_vector_quantize.py:148-152,169-187; MelSpectrogram,
+    bicodec.py:201-221; SpeakerEncoder.tokenize, speaker_encoder.py)."""
+
+    input_channels: int = 1024  # XLSR-53 hidden width
+    vocos_dim: int = 384
+    vocos_inter: int = 2048
+    vocos_layers: int = 12
+    latent_dim: int = 1024      # encoder.out_channels = quantizer.input_dim
+    codebook_size: int = 8192
+    codebook_dim: int = 8
+    # global tokens: mel_params (bicodec.py:201-221), speaker_encoder (speaker_encoder.py:33-60; ECAPA width and perceiver shape are
+    # fixed there: ECAPA_TDNN_GLOB_c512, PerceiverResampler defaults)
+    sample_rate: int = 16000
+    n_fft: int = 1024
+    win_length: int = 640
+    hop_length: int = 320
+    mel_fmin: float = 10.0
+    mel_fmax: float = 0.0       # 0: sample_rate / 2 (mel_fmax: null)
+    mel_dim: int = 128          # mel_params.num_mels = speaker_encoder.input_dim
+    ecapa_channels: int = 512
+    spk_latent_dim: int = 128
+    token_num: int = 32
+    fsq_levels: Tuple[int, ...] = (4, 4, 4, 4, 4, 4)
+    perceiver_depth: int = 2
+    perceiver_heads: int = 8
+    perceiver_dim_head: int = 64
+
+    @property
+    def mel_params(self) -> Dict[str, Any]:
+        return dict(sample_rate=self.sample_rate, n_fft=self.n_fft, win_length=self.win_length, hop_length=self.hop_length,
+                    mel_fmin=self.mel_fmin, mel_fmax=self.mel_fmax or None, num_mels=self.mel_dim)
+
+    @classmethod
+    def from_spec(cls, spec: BiCodecSpec, input_channels: int = 1024) -> "BiCodecEncoderSpec":
+        """The published model's encoder shares its widths with the prenet, the quantizer and the speaker encoder of `spec`."""
+        return cls(input_channels=input_channels, vocos_dim=spec.vocos_dim, vocos_inter=spec.vocos_inter, vocos_layers=spec.vocos_layers,
+                   latent_dim=spec.latent_dim, codebook_size=spec.codebook_size, codebook_dim=spec.codebook_dim, mel_dim=spec.mel_dim,
+                   spk_latent_dim=spec.spk_latent_dim, token_num=spec.token_num, fsq_levels=spec.fsq_levels)
+
+    def ref_segment_length(self, ref_segment_duration: float = 6, latent_hop_length: int = 320) -> int:
+        """BiCodecTokenizer.get_ref_clip's clip length (audio_tokenizer.py:60-64): 96 000 samples for the published configuration."""
+        return int(self.sample_rate * ref_segment_duration) // latent_hop_length * latent_hop_length
+
+    @classmethod
+    def from_config(cls, audio_tokenizer: Mapping[str, Any]) -> "BiCodecEncoderSpec":
+        """The `audio_tokenizer` section of `{model_dir}/config.yaml`: `encoder` -> Encoder(**encoder), `quantizer` ->
+        FactorizedVectorQuantize(**quantizer), `mel_params` -> MelSpectrogram, `speaker_encoder` -> SpeakerEncoder (bicodec.py:62-87).
+        A value the kernels have no path for is refused by name (QuarkAudioError -4)."""
+        def refuse(what):
+            raise _lib.QuarkAudioError(-4, f"BiCodec config.yaml: {what} - the MI355X tokenizer has no path for it")
+
+        for name in ("encoder", "quantizer"):
+            if name not in audio_tokenizer:
+                raise KeyError(f"config.yaml: audio_tokenizer.{name} is missing (bicodec.py:80-87 reads it)")
+        enc, q = dict(audio_tokenizer["encoder"]), dict(audio_tokenizer["quantizer"])
+        required = ("input_channels", "vocos_dim", "vocos_intermediate_dim", "vocos_num_layers", "out_channels")
+        missing = [k for k in required if k not in enc]
+        if missing:
+            raise TypeError(f"audio_tokenizer.encoder: missing required argument(s) {missing}")
+        unknown = [k for k in enc if k not in required and k != "sample_ratios"]
+        if unknown:
+            raise TypeError(f"audio_tokenizer.encoder: unexpected keyword argument(s) {unknown}")
+        missing = [k for k in ("input_dim", "codebook_size", "codebook_dim") if k not in q]
+        if missing:
+            raise TypeError(f"audio_tokenizer.quantizer: missing required argument(s) {missing}")
+        if [int(r) for r in enc.get("sample_ratios", (1, 1))] != [1, 1]:
+            refuse(f"encoder.sample_ratios = {list(enc['sample_ratios'])} (the two ratio-1 SamplingBlocks of the published model are built)")
+        if int(q["codebook_dim"]) == int(q["input_dim"]):
+            refuse("quantizer.input_dim == codebook_dim (Identity projections, factorized_vector_quantize.py:59-65)")
+        if int(enc["out_channels"]) != int(q["input_dim"]):
+            raise ValueError(f"BiCodec config.yaml: encoder.out_channels = {enc['out_channels']} and quantizer.input_dim = {q['input_dim']} "
+                             "must agree (get_semantic_tokens feeds one into the other)")
+        mel = dict(audio_tokenizer.get("mel_params") or {})
+        spk = dict(audio_tokenizer.get("speaker_encoder") or {})
+        d = cls()
+        mkw = dict(sample_rate=int(mel.get("sample_rate", d.sample_rate)), n_fft=int(mel.get("n_fft", d.n_fft)),
+                   win_length=int(mel.get("win_length", d.win_length)), hop_length=int(mel.get("hop_length", d.hop_length)),
+                   mel_fmin=float(mel.get("mel_fmin", d.mel_fmin)), mel_fmax=float(mel.get("mel_fmax") or 0.0),
+                   mel_dim=int(mel.get("num_mels", d.mel_dim)))
+        if mkw["win_length"] != 2 * mkw["hop_length"] or mkw["hop_length"] % 32 or mkw["n_fft"] < mkw["win_length"] or (mkw["n_fft"] - mkw["win_length"]) % 2:
+            refuse(f"mel_params.win_length = {mkw['win_length']}, hop_length = {mkw['hop_length']}, n_fft = {mkw['n_fft']} (the mel front "
+                   "frames the signal as 2 hops of a multiple of 32 samples)")
+        if int(spk.get("fsq_num_quantizers", 1)) != 1:
+            refuse(f"speaker_encoder.fsq_num_quantizers = {spk['fsq_num_quantizers']} (one FSQ stage is built)")
+        if int(spk.get("input_dim", mkw["mel_dim"])) != mkw["mel_dim"]:
+            raise ValueError(f"BiCodec config.yaml: speaker_encoder.input_dim = {spk['input_dim']} and mel_params.num_mels = "
+                             f"{mkw['mel_dim']} must agree (get_global_tokens feeds one into the other)")
+        levels = tuple(int(v) for v in spk.get("fsq_levels", d.fsq_levels))
+        if not 1 <= len(levels) <= 8 or min(levels) < 2:
+            refuse(f"speaker_encoder.fsq_levels = {list(levels)} (1 .. 8 levels of at least 2)")
+        return cls(input_channels=int(enc["input_channels"]), vocos_dim=int(enc["vocos_dim"]), vocos_inter=int(enc["vocos_intermediate_dim"]),
+                   vocos_layers=int(enc["vocos_num_layers"]), latent_dim=int(enc["out_channels"]), codebook_size=int(q["codebook_size"]),
+                   codebook_dim=int(q["codebook_dim"]), spk_latent_dim=int(spk.get("latent_dim", d.spk_latent_dim)),
+                   token_num=int(spk.get("token_num", d.token_num)), fsq_levels=levels, **mkw)
+
+    def to_c(self) -> "_lib.qa_bicodec_enc_spec":
+        s = _lib.qa_bicodec_enc_spec()
+        s.input_channels, s.vocos_dim, s.vocos_inter, s.vocos_layers = self.input_channels, self.vocos_dim, self.vocos_inter, self.vocos_layers
+        s.latent_dim, s.codebook_size, s.codebook_dim = self.latent_dim, self.codebook_size, self.codebook_dim
+        s.sample_rate, s.n_fft, s.win_length, s.hop_length = self.sample_rate, self.n_fft, self.win_length, self.hop_length
+        s.mel_fmin, s.mel_fmax, s.mel_dim, s.ecapa_channels = self.mel_fmin, self.mel_fmax, self.mel_dim, self.ecapa_channels
+        s.spk_latent_dim, s.token_num, s.n_levels = self.spk_latent_dim, self.token_num, len(self.fsq_levels)
+        for i, v in enumerate(self.fsq_levels):
+            s.levels[i] = v
+        s.perceiver_depth, s.perceiver_heads, s.perceiver_dim_head = self.perceiver_depth, self.perceiver_heads, self.perceiver_dim_head
+        return s
+
+
+SPEC_BICODEC_ENCODER = BiCodecEncoderSpec()
+# the entry whose presence makes load_state_dict build the tokenizer (then every encoder.*, quantizer.in_project.*, speaker_encoder.*
+# tensor it reads must be there); stray encoder-side entries without it are ignored, as they always were
+ENCODER_KEY = "encoder.encoder.embed.weight"
+
+
+@torch.no_grad()
+def wav_normalize(wav: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
+    """Wav2Vec2FeatureExtractor(do_normalize=True) on equal-length rows (audio_tokenizer.py:74-90, padding=True pads nothing):
+    wav [B, T] (or [T]) on the GPU -> (wav - mean) / sqrt(var + eps) per row, fp32, on the same device."""
+    if wav.dim() not in (1, 2) or wav.shape[-1] == 0:
+        raise _lib.QuarkAudioError(-1, f"wav must be [B, T] or [T] with T > 0, got {tuple(wav.shape)}")
+    if wav.device.type != "cuda":
+        raise _lib.QuarkAudioError(-1, "wav_normalize runs on the GPU: move wav to a HIP device first")
+    x = wav.to(torch.float32).contiguous()
+    out = torch.empty_like(x)
+    B, T = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _lib.check(_lib.load_library().qa_wav_normalize(x.data_ptr(), B, T, out.data_ptr(), float(eps), stream))
+    return out
+
+
 def load_config(config_path) -> Dict[str, Any]:
     """utils/file.py:116-130 (`OmegaConf.load` + the optional `base_config` merge) with PyYAML: omegaconf is not a dependency here.  A
     value that uses OmegaConf interpolation (`${...}`) cannot be resolved by a plain YAML reader and is refused rather than passed on."""
@@ -164,16 +301,22 @@ def load_config(config_path) -> Dict[str, Any]:
 
 
 class BiCodec(torch.nn.Module):
-    """`detokenize(semantic_tokens, global_tokens)` of the reference's BiCodec.  Weights in the reference's key layout
-    (`BiCodec.state_dict()` / the `model.safetensors` of the checkpoint; encoder-side entries are ignored)."""
+    """`detokenize(semantic_tokens, global_tokens)` and `tokenize(batch)` / `get_semantic_tokens` / `get_global_tokens` of the reference's
+    BiCodec.  Weights in the reference's key layout (`BiCodec.state_dict()` / the `model.safetensors` of the checkpoint).  The tokenizer
+    is built when the state dict holds encoder.encoder.embed.weight (then it needs encoder.*, quantizer.in_project.* and the
+    speaker_encoder's ECAPA / perceiver / project_in entries); a detokenize-only state dict loads as before.  The x-vector head and
+    postnet entries are ignored."""
 
-    def __init__(self, spec: BiCodecSpec = SPEC_BICODEC, *, device: str | torch.device = "cuda:0", check_tokens: bool = True):
+    def __init__(self, spec: BiCodecSpec = SPEC_BICODEC, *, device: str | torch.device = "cuda:0", check_tokens: bool = True,
+                 encoder_spec: BiCodecEncoderSpec | None = None):
         super().__init__()
         self.spec = spec
+        self.encoder_spec = encoder_spec or BiCodecEncoderSpec.from_spec(spec)
         self.device = torch.device(device)
         self.check_tokens = check_tokens
         self._lib = _lib.load_library()
         self._handle = C.c_void_p()
+        self._enc = C.c_void_p()
 
     @classmethod
     def load_from_checkpoint(cls, model_dir, device="cuda:0", spec: BiCodecSpec | None = None, **kwargs) -> "BiCodec":
@@ -182,9 +325,14 @@ class BiCodec(torch.nn.Module):
         them and goes on with random weights, bicodec.py:103-108).  `spec=` overrides the file (a directory without config.yaml)."""
         from safetensors.torch import load_file
 
+        sd = load_file(f"{model_dir}/model.safetensors")
+        encoder_spec = None
         if spec is None:
-            spec = BiCodecSpec.from_config(load_config(f"{model_dir}/config.yaml")["audio_tokenizer"])
-        return cls(spec, device=device).load_state_dict(load_file(f"{model_dir}/model.safetensors"))
+            cfg = load_config(f"{model_dir}/config.yaml")["audio_tokenizer"]
+            spec = BiCodecSpec.from_config(cfg)
+            if ENCODER_KEY in sd:  # the tokenizer's config blocks are read only when the tokenizer is built
+                encoder_spec = BiCodecEncoderSpec.from_config(cfg)
+        return cls(spec, device=device, encoder_spec=encoder_spec).load_state_dict(sd)
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = False, assign: bool = False):
         _lib.require_device()
@@ -193,8 +341,13 @@ class BiCodec(torch.nn.Module):
         handle = C.c_void_p()
         cspec = self.spec.to_c()
         _lib.check(self._lib.qa_bicodec_create(C.byref(handle), C.byref(cspec), table, n, self.device.index or 0))
-        del keep
         self._handle = handle
+        if ENCODER_KEY in state_dict:  # the tokenizer: a missing tensor is named by the library
+            enc = C.c_void_p()
+            espec = self.encoder_spec.to_c()
+            _lib.check(self._lib.qa_bicodec_enc_create(C.byref(enc), C.byref(espec), table, n, self.device.index or 0))
+            self._enc = enc
+        del keep
         return self
 
     def train(self, mode: bool = True):
@@ -232,16 +385,65 @@ class BiCodec(torch.nn.Module):
         _lib.check(self._lib.qa_bicodec_detokenize(self._handle, sem.data_ptr(), glob.data_ptr(), B, T, wav.data_ptr(), stream))
         return wav
 
+    @property
+    def has_tokenizer(self) -> bool:
+        return bool(self._enc.value)
+
+    def _require_tokenizer(self):
+        if not self._enc.value:
+            raise _lib.QuarkAudioError(-3, f"BiCodec has no tokenizer: the state dict held no {ENCODER_KEY} (a detokenize-only checkpoint); "
+                                           "tokenize needs the encoder.*, quantizer.in_project.* and speaker_encoder.* weights")
+
+    @torch.no_grad()
+    def get_semantic_tokens(self, batch: Mapping[str, torch.Tensor]) -> torch.Tensor:
+        """bicodec.py:167-172: batch["feat"] [B, N, input_channels] (the XLSR-53 hidden-state mix) -> semantic tokens int64 [B, N]."""
+        self._require_tokenizer()
+        feat = batch["feat"]
+        if feat.dim() != 3 or feat.shape[2] != self.encoder_spec.input_channels or feat.shape[1] == 0:
+            raise _lib.QuarkAudioError(-1, f"feat must be [B, N, {self.encoder_spec.input_channels}] with N > 0, got {tuple(feat.shape)}")
+        feat = feat.to(device=self.device, dtype=torch.float32).contiguous()
+        B, N, _ = feat.shape
+        out = torch.empty((B, N), dtype=torch.int64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.qa_bicodec_get_semantic_tokens(self._enc, feat.data_ptr(), B, N, out.data_ptr(), stream))
+        return out
+
+    @torch.no_grad()
+    def get_global_tokens(self, batch: Mapping[str, torch.Tensor], ref_len: int = 0) -> torch.Tensor:
+        """bicodec.py:174-178: batch["ref_wav"] [B, T] -> global tokens int32 [B, 1, token_num].  ref_len > 0 takes the mel spectrogram of
+        BiCodecTokenizer.get_ref_clip(ref_wav) of that length (tile a short row, truncate a long one) without materialising the clip."""
+        self._require_tokenizer()
+        wav = batch["ref_wav"]
+        if wav.dim() != 2 or wav.shape[1] == 0:
+            raise _lib.QuarkAudioError(-1, f"ref_wav must be [B, T], got {tuple(wav.shape)}")
+        wav = wav.to(device=self.device, dtype=torch.float32).contiguous()
+        B, T = wav.shape
+        out = torch.empty((B, 1, self.encoder_spec.token_num), dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.qa_bicodec_get_global_tokens(self._enc, wav.data_ptr(), B, T, int(ref_len), out.data_ptr(), stream))
+        return out
+
+    @torch.no_grad()
+    def tokenize(self, batch: Mapping[str, torch.Tensor], ref_len: int = 0):
+        """bicodec.py:151-165: (semantic_tokens int64 [B, N], global_tokens int32 [B, 1, token_num])."""
+        return self.get_semantic_tokens(batch), self.get_global_tokens(batch, ref_len)
+
     def enable_taps(self, on: bool = True):
         _lib.check(self._lib.qa_bicodec_enable_taps(self._handle, int(on)))
+        if self._enc.value:
+            _lib.check(self._lib.qa_bicodec_enc_enable_taps(self._enc, int(on)))
         return self
 
     def tap(self, name: str) -> torch.Tensor:
-        n = self._lib.qa_bicodec_tap(self._handle, name.encode(), None, 0, None)
+        """Intermediates of the last call: detokenize's (z_q, prenet.*, gen.block{i}, ...), get_semantic_tokens' (enc.*, vq.latent) and
+        get_global_tokens' (mel, ecapa.*, perceiver.out, fsq.bounded)."""
+        encoder_side = name.startswith(("enc.", "vq.", "mel", "ecapa.", "perceiver.", "fsq."))
+        h, fn = (self._enc, self._lib.qa_bicodec_enc_tap) if encoder_side else (self._handle, self._lib.qa_bicodec_tap)
+        n = fn(h, name.encode(), None, 0, None)
         if n < 0:
             _lib.check(int(n))
         out = torch.empty(int(n), dtype=torch.float32, device=self.device)
-        n2 = self._lib.qa_bicodec_tap(self._handle, name.encode(), out.data_ptr(), n, torch.cuda.current_stream(self.device).cuda_stream)
+        n2 = fn(h, name.encode(), out.data_ptr(), n, torch.cuda.current_stream(self.device).cuda_stream)
         if n2 < 0:
             _lib.check(int(n2))
         return out
@@ -250,6 +452,9 @@ class BiCodec(torch.nn.Module):
         if getattr(self, "_handle", None) is not None and self._handle.value:
             self._lib.qa_bicodec_destroy(self._handle)
             self._handle = C.c_void_p()
+        if getattr(self, "_enc", None) is not None and self._enc.value:
+            self._lib.qa_bicodec_enc_destroy(self._enc)
+            self._enc = C.c_void_p()
 
     def __del__(self):
         try:
@@ -259,13 +464,20 @@ class BiCodec(torch.nn.Module):
 
 
 class BiCodecTokenizer(torch.nn.Module):
-    """Decode side of the reference's BiCodecTokenizer (QuarkAudio-UniSE/model/bicodec/audio_tokenizer.py:107-120), the object
-    `Model.test_step` calls: `detokenize(global_tokens [B, 1, 32], semantic_tokens [B, T]) -> wav [B, 1, T * 320]`."""
+    """The reference's BiCodecTokenizer (QuarkAudio-UniSE/model/bicodec/audio_tokenizer.py): `detokenize(global_tokens [B, 1, 32],
+    semantic_tokens [B, T]) -> wav [B, 1, T * 320]`, the call `Model.test_step` makes, and `tokenize(wav) -> (global int32 [B, 1, 32],
+    semantic int64 [B, N])` with its parts `extract_wav2vec2_features(wav)` (normalise + XLSR-53 hidden states 11 / 14 / 16) and
+    `get_semantic_tokens(wav)`.  The XLSR-53 front-end is `feature_extractor=` (an SSLFeatureExtractor built with SPEC_XLSR53_BICODEC)
+    or, loaded on first use, `{model_dir}/wav2vec2-large-xlsr-53` (audio_tokenizer.py:47-52)."""
 
-    def __init__(self, model_dir=None, device="cuda:0", *, model: BiCodec | None = None, spec: BiCodecSpec | None = None, **kwargs):
+    def __init__(self, model_dir=None, device="cuda:0", *, model: BiCodec | None = None, spec: BiCodecSpec | None = None,
+                 feature_extractor=None, **kwargs):
         super().__init__()
         self.model_dir = model_dir
         self.config = None
+        if feature_extractor is not None:
+            self._check_extractor(feature_extractor)
+        self._feature_extractor = feature_extractor
         if model is None:
             if model_dir is None:
                 raise ValueError("BiCodecTokenizer needs model_dir (with BiCodec/config.yaml and BiCodec/model.safetensors) or model=")
@@ -281,6 +493,72 @@ class BiCodecTokenizer(torch.nn.Module):
     def detokenize(self, global_tokens: torch.Tensor, semantic_tokens: torch.Tensor) -> torch.Tensor:
         return self.model.detokenize(semantic_tokens, global_tokens)
 
-    def tokenize(self, *args, **kwargs):
-        raise _lib.QuarkAudioError(-4, "BiCodec tokenize (wav2vec2-BERT features + ECAPA speaker encoder) is training-side and not part of "
-                                       "the inference path: the LM produces the tokens")
+    @staticmethod
+    def _check_extractor(fx):
+        from .ssl import SSLFeatureExtractor
+
+        if not isinstance(fx, SSLFeatureExtractor):
+            raise _lib.QuarkAudioError(-1, f"feature_extractor must be an SSLFeatureExtractor (SPEC_XLSR53_BICODEC), got {type(fx).__name__}")
+        want = {"select": (11, 14, 16), "pad": 0, "compress_exponent": 0.0}
+        have = {k: (tuple(getattr(fx.spec, k)) if k == "select" else getattr(fx.spec, k)) for k in want}
+        if have != want:
+            raise _lib.QuarkAudioError(-1, f"BiCodec averages XLSR-53 hidden states 11 / 14 / 16 of the unpadded, uncompressed input "
+                                           f"({want}); the SSLFeatureExtractor was built with {have} - use SPEC_XLSR53_BICODEC")
+
+    @property
+    def feature_extractor(self):
+        if self._feature_extractor is None:
+            if self.model_dir is None:
+                raise _lib.QuarkAudioError(-3, "no XLSR-53 front-end: pass feature_extractor= or a model_dir with wav2vec2-large-xlsr-53/")
+            import dataclasses
+            import json
+            import os
+
+            from .ssl import SPEC_XLSR53_BICODEC, SSLFeatureExtractor, SSLSpec
+
+            path = f"{self.model_dir}/wav2vec2-large-xlsr-53"
+            spec = SPEC_XLSR53_BICODEC
+            if os.path.isfile(f"{path}/config.json"):  # the snapshot's Wav2Vec2Config, with what BiCodecTokenizer does around the model
+                with open(f"{path}/config.json") as f:
+                    cfg = json.load(f)
+                names = {fl.name for fl in dataclasses.fields(SSLSpec)}
+                kw = {k: (tuple(v) if isinstance(v, list) else v) for k, v in cfg.items() if k in names}
+                spec = dataclasses.replace(SSLSpec(**kw), select=SPEC_XLSR53_BICODEC.select, pad=0, compress_exponent=0.0)
+            self._feature_extractor = SSLFeatureExtractor.from_pretrained(path, spec, device=self.device)
+        return self._feature_extractor
+
+    @torch.no_grad()
+    def extract_wav2vec2_features(self, wavs: torch.Tensor) -> torch.Tensor:
+        """audio_tokenizer.py:74-90: wavs [B, T] -> (hidden_states[11] + [14] + [16]) / 3 of the normalised rows, [B, N, 1024]."""
+        wavs = wavs.to(device=self.device, dtype=torch.float32)
+        if wavs.dim() == 1:
+            wavs = wavs.unsqueeze(0)
+        fx = self.feature_extractor
+        if wavs.dim() != 2 or wavs.shape[-1] < 400:  # the 10-sample / stride-5 conv stack needs 400 samples for one frame
+            raise _lib.QuarkAudioError(-1, f"wav must be [B, T] with T >= 400 samples (one XLSR-53 frame at 16 kHz), got {tuple(wavs.shape)}")
+        return fx(wav_normalize(wavs))
+
+    @property
+    def ref_segment_length(self) -> int:
+        """audio_tokenizer.py:60-64 from `{model_dir}/config.yaml` (sample_rate, ref_segment_duration, latent_hop_length); the published
+        values (16 kHz, 6 s, 320) without one."""
+        c = self.config or {}
+        spec = self.model.encoder_spec
+        return int(c.get("sample_rate", spec.sample_rate) * c.get("ref_segment_duration", 6)) // int(c.get("latent_hop_length", 320)) \
+            * int(c.get("latent_hop_length", 320))
+
+    @torch.no_grad()
+    def get_semantic_tokens(self, wavs: torch.Tensor) -> torch.Tensor:
+        """The semantic half of tokenize (audio_tokenizer.py:95-103 + bicodec.py:167-172): wavs [B, T] -> semantic tokens int64 [B, N]."""
+        return self.model.get_semantic_tokens({"feat": self.extract_wav2vec2_features(wavs)})
+
+    @torch.no_grad()
+    def tokenize(self, wav: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """audio_tokenizer.py:93-103: wav [B, T] -> (global_tokens int32 [B, 1, token_num], semantic_tokens int64 [B, N]).  The reference
+        clip (get_ref_clip) is formed inside the mel kernel."""
+        wav = wav.to(device=self.device, dtype=torch.float32)
+        if wav.dim() == 1:
+            wav = wav.unsqueeze(0)
+        feat = self.extract_wav2vec2_features(wav)
+        semantic, global_tokens = self.model.tokenize({"feat": feat, "ref_wav": wav, "wav": wav}, ref_len=self.ref_segment_length)
+        return global_tokens, semantic

@@ -1,6 +1,8 @@
 // bicodec.cpp - BiCodec.detokenize on the HIP kernels (host orchestration, C-ABI handle): semantic tokens [B, T] + global tokens
 // [B, token_num] -> waveform [B, T * prod(rates)], the stage the reference's UniSE test path ends with
 // (QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199, called at model/model.py:193,223).  SURVEY.md 8f-2.
+// The encoder side (qa_bicodec_enc, further down): BiCodec.tokenize (bicodec.py:151-180) - XLSR-53 features -> Encoder -> factorized
+// VQ -> semantic tokens, and reference clip -> mel -> ECAPA-TDNN latent -> PerceiverResampler -> FSQ -> global tokens.
 //
 //   z_q      FactorizedVectorQuantize.detokenize  (vq/factorized_vector_quantize.py:154-172)  one gather: codebook x out_project folded
 //   d_vector SpeakerEncoder.detokenize            (speaker/speaker_encoder.py:111-116)        gather of (FSQ code x project_out) + Linear
@@ -23,6 +25,18 @@ int launch_gather_global(const long long* tok, const float* table, float* out, i
 int launch_adaln(const float* x, const float* scale, const float* shift, long long ld_cond, float* y, int B, int T, int C, float eps,
                  hipStream_t s);
 int launch_add_rowvec(float* x, const float* v, int B, int T, int C, hipStream_t s);
+int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s);
+int launch_l2norm_rows(const float* x, float* y, long long rows, int D, hipStream_t s);
+int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s);
+int launch_spec_mag(const float* ri, int nbp, int nb, float* mag, int ldm, long long rows, hipStream_t s);
+int launch_res2_chain(const float* x, float* y, const float* wt, const float* bst, int B, int T, int C, int d, hipStream_t s);
+int launch_se_residual(const float* x, long long ldx, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
+                       float* gate, float* out, long long ldo, int B, int T, int C, int Hd, hipStream_t s);
+int launch_perceiver_ctx(const float* lat, long long lat_b, const float* x, float* ctx, int B, int n_lat, int T, int D, hipStream_t s);
+int launch_geglu(const float* h, int F, float* out, int ldo, long long rows, hipStream_t s);
+int launch_l2norm_scale(const float* x, const float* gamma, float* y, long long rows, int D, float scale, hipStream_t s);
+int launch_fsq(const float* x, const float* w, const float* bias, const int* levels, int nl, int D, long long rows, int* tokens,
+               float* bounded, hipStream_t s);
 int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate, long long ldg,
                        const float* res, long long ldr, float* y, long long ldy, int M, int N, int K, int act, hipStream_t s,
                        float rms_eps, int dual);
@@ -66,6 +80,42 @@ struct qa_bicodec {
     VocosW down[2], backbone;
     std::vector<GenBlockW> blocks;
     const float* a_final = nullptr;
+    char* ws = nullptr;
+    size_t ws_cap = 0;
+    Ctx ctx;
+};
+
+// Conv1dReluBn (ecapa_tdnn.py): the convolution with BN(ReLU(.)) as the epilogue  relu(acc + b) * s + t
+struct ConvBnW {
+    ConvW conv;
+    const float *s = nullptr, *t = nullptr;
+};
+struct SeRes2W {
+    ConvBnW c0, c2;
+    const float *res2_w = nullptr, *res2_bst = nullptr;  // [7][3][W][W] (step, tap, in, out) and [7][3][W] (bias, BN scale, BN shift)
+    const float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2 = nullptr, *se_b2 = nullptr;
+    int dilation = 1;
+};
+struct PerceiverLayerW {
+    ConvW to_q, to_kv, to_out, ff1, ff2;  // ff2's K is zero-padded from the odd GEGLU width to a multiple of 32
+};
+
+// BiCodec.get_semantic_tokens (bicodec.py:167-172): Encoder + FactorizedVectorQuantize.tokenize; BiCodec.get_global_tokens
+// (bicodec.py:174-178): mel spectrogram + ECAPA-TDNN latent + PerceiverResampler + ResidualFSQ
+struct qa_bicodec_enc {
+    qa_bicodec_enc_spec spec{};
+    int device = 0;
+    WeightStore store;
+    VocosW backbone, down[2];
+    ConvW project, in_project;
+    const float *codebook = nullptr, *e2 = nullptr;  // F.normalize(codebook) [K, D] and its squared norms
+    // global tokens
+    int nb = 0, nbp = 0, kp = 0, ff = 0, ffp = 0;  // DFT bins, bins padded to 4, filterbank K padded to 32, GEGLU width and its padding
+    ConvW dft, fbank, ecapa_out, proj_context, fsq_in;
+    ConvBnW layer1;
+    SeRes2W blocks[3];
+    std::vector<PerceiverLayerW> perceiver;
+    const float *latents = nullptr, *norm_gamma = nullptr;
     char* ws = nullptr;
     size_t ws_cap = 0;
     Ctx ctx;
@@ -126,8 +176,8 @@ struct Loader {
     }
 };
 
-void build_vocos(Loader& L, VocosW* v, const std::string& p, int C, int I, int n_layers, bool ada, float embed_gain) {
-    L.conv(&v->embed, p + ".embed", C, C, 7, true, embed_gain);
+void build_vocos(Loader& L, VocosW* v, const std::string& p, int C, int I, int n_layers, bool ada, float embed_gain, int C_in = 0) {
+    L.conv(&v->embed, p + ".embed", C, C_in > 0 ? C_in : C, 7, true, embed_gain);
     if (!ada) {
         L.vec(&v->nw, p + ".norm.weight", C);
         L.vec(&v->nb, p + ".norm.bias", C);
@@ -293,6 +343,7 @@ struct ConvOpt {
     const float *gamma = nullptr, *res = nullptr, *alpha = nullptr, *alpha2 = nullptr;
     float* y2 = nullptr;
     int64_t ldr = 0, ldy2 = 0;
+    const float* shift = nullptr;  // per-channel constant added after gamma (the residual operand with row stride 0): BN after a ReLU
 };
 
 int conv(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, float* y, int64_t ldy, int T_out, const ConvOpt& o) {
@@ -316,6 +367,10 @@ int conv(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, f
     }
     p.dilation = o.dilation;
     p.alpha = o.alpha; p.y2 = o.y2; p.alpha2 = o.alpha2; p.ldy2 = o.ldy2;
+    if (o.shift) {
+        p.res = o.shift;
+        p.ldr = 0;
+    }
     return launch_conv_gemm(p, c.stream);
 }
 
@@ -339,12 +394,14 @@ int linear(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, int a
 }
 
 // VocosBackbone.forward (blocks/vocos.py:323-335) in place on x [B, T, C]; t1 [rows, C], u [rows, I] scratch.
-// cond: AdaLN scale / shift rows of this backbone ([B, n_ada * 2 * C], entry a at offset a * 2 * C), or nullptr for plain LayerNorm
-int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, int C, const float* cond, int64_t ld_cond) {
+// cond: AdaLN scale / shift rows of this backbone ([B, n_ada * 2 * C], entry a at offset a * 2 * C), or nullptr for plain LayerNorm.
+// in: the embed convolution reads [B, T, embed.C_in] from here instead of x (the encoder's 1024 -> 384 input backbone)
+int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, int C, const float* cond, int64_t ld_cond,
+          const float* in = nullptr) {
     const int64_t rows = (int64_t)B * T;
     ConvOpt same7;
     same7.pad_left = 3; same7.pad_right = 3;
-    QA_TRY(conv(c, x, C, B, T, v.embed, t1, C, T, same7));
+    QA_TRY(conv(c, in ? in : x, in ? v.embed.C_in : C, B, T, v.embed, t1, C, T, same7));
     if (!c.dry) {
         if (cond) QA_TRY(launch_adaln(t1, cond, cond + C, ld_cond, x, B, T, C, 1e-6f, c.stream));
         else QA_TRY(launch_layernorm(t1, v.nw, v.nb, x, rows, C, 1e-6f, c.stream));
@@ -457,6 +514,344 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     return QA_OK;
 }
 
+int build_speaker(qa_bicodec_enc* h, Loader& L);
+
+int build_encoder(qa_bicodec_enc* h, const HostTable& tab) {
+    const qa_bicodec_enc_spec& sp = h->spec;
+    const int Cin = sp.input_channels, C = sp.vocos_dim, I = sp.vocos_inter, Ld = sp.latent_dim, K = sp.codebook_size, D = sp.codebook_dim;
+    QA_REQUIRE(Cin % 32 == 0 && C % 32 == 0 && I % 32 == 0 && Ld % 32 == 0 && sp.vocos_layers >= 1,
+               "bicodec encoder spec: input %d, vocos %d / %d, latent %d must be multiples of 32", Cin, C, I, Ld);
+    QA_REQUIRE(K >= 1 && D % 8 == 0 && D >= 8 && D <= 64, "bicodec encoder spec: codebook_dim %d must be a multiple of 8 in 8 .. 64", D);
+    Loader L{tab, h->store};
+    // Encoder (feat_encoder.py:29-92).  SamplingBlock with both scales 1 returns 3 x (samper.py:78-95): folded into the embed filters
+    build_vocos(L, &h->backbone, "encoder.encoder", C, I, sp.vocos_layers, false, 1.0f, Cin);
+    for (int i = 0; i < 2; ++i) build_vocos(L, &h->down[i], "encoder.downsample." + std::to_string(i) + ".1", C, I, 2, false, 3.0f);
+    L.conv(&h->project, "encoder.project", Ld, C, 1);
+    L.conv(&h->in_project, "quantizer.in_project", D, Ld, 1);
+    QA_TRY(build_speaker(h, L));
+    // F.normalize(codebook) once (factorized_vector_quantize.py:179): fp32 division by the clamped norm, like the reference
+    {
+        const float* cb = L.need("quantizer.codebook.weight", (int64_t)K * D);
+        std::vector<float> cn((size_t)K * D, 0.f), e2((size_t)K, 0.f);
+        if (cb)
+            for (int k = 0; k < K; ++k) {
+                float ss = 0.f;
+                for (int d = 0; d < D; ++d) ss = std::fmaf(cb[(size_t)k * D + d], cb[(size_t)k * D + d], ss);
+                const float n = std::max(std::sqrt(ss), 1e-12f);
+                float q = 0.f;
+                for (int d = 0; d < D; ++d) {
+                    const float v = cb[(size_t)k * D + d] / n;
+                    cn[(size_t)k * D + d] = v;
+                    q = std::fmaf(v, v, q);
+                }
+                e2[k] = q;
+            }
+        L.raw(&h->codebook, cn);
+        L.raw(&h->e2, e2);
+    }
+    if (!L.ok) return QA_ERR_MISSING;
+    QA_TRY(h->store.upload());
+    L.resolve();
+    return QA_OK;
+}
+
+double hz_to_mel_slaney(double f) {  // torchaudio.functional._hz_to_mel(mel_scale="slaney")
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = 15.0, logstep = std::log(6.4) / 27.0;
+    return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp;
+}
+double mel_to_hz_slaney(double m) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = 15.0, logstep = std::log(6.4) / 27.0;
+    return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+
+// BatchNorm1d (eval) after the ReLU: y = relu(conv) * s + t, s = w / sqrt(var + 1e-5), t = b - mean * s
+void batchnorm(Loader& L, const std::string& p, int C, std::vector<float>* s, std::vector<float>* t) {
+    const float* w = L.need(p + ".weight", C);
+    const float* b = L.need(p + ".bias", C);
+    const float* m = L.need(p + ".running_mean", C);
+    const float* v = L.need(p + ".running_var", C);
+    s->assign(C, 1.f);
+    t->assign(C, 0.f);
+    if (w && b && m && v)
+        for (int c = 0; c < C; ++c) {
+            (*s)[c] = (float)((double)w[c] / std::sqrt((double)v[c] + 1e-5));
+            (*t)[c] = (float)((double)b[c] - (double)m[c] * (*s)[c]);
+        }
+}
+void conv_bn(Loader& L, ConvBnW* dst, const std::string& p, int N, int C_in, int k) {
+    L.conv(&dst->conv, p + ".conv", N, C_in, k);
+    std::vector<float> s, t;
+    batchnorm(L, p + ".bn", N, &s, &t);
+    L.raw(&dst->s, s);
+    L.raw(&dst->t, t);
+}
+
+int build_speaker(qa_bicodec_enc* h, Loader& L) {
+    const qa_bicodec_enc_spec& sp = h->spec;
+    const int hop = sp.hop_length, nfft = sp.n_fft, C = sp.ecapa_channels, W = C / 8, D = sp.spk_latent_dim;
+    QA_REQUIRE(hop >= 16 && hop % 32 == 0 && sp.win_length == 2 * hop && nfft >= sp.win_length && (nfft - sp.win_length) % 2 == 0,
+               "bicodec encoder spec: the mel front needs win_length = 2 * hop_length, hop a multiple of 32, n_fft >= win_length "
+               "(got n_fft %d, win %d, hop %d)", nfft, sp.win_length, hop);
+    QA_REQUIRE(sp.mel_dim % 32 == 0 && C % 32 == 0 && W <= 64 && D % 32 == 0 && D <= 256 && sp.token_num >= 1 && sp.n_levels >= 1 &&
+               sp.n_levels <= 8 && sp.perceiver_depth >= 1 && sp.perceiver_heads >= 1,
+               "bicodec encoder spec: mel %d, ECAPA channels %d, speaker latent %d unsupported", sp.mel_dim, C, D);
+    for (int i = 0; i < sp.n_levels; ++i) QA_REQUIRE(sp.levels[i] >= 2, "bicodec encoder spec: FSQ level %d", sp.levels[i]);
+    // ---- mel front: framed-signal DFT (window folded into the basis) and the slaney filterbank
+    h->nb = nfft / 2 + 1;
+    h->nbp = (int)round_up(h->nb, 4);
+    h->kp = (int)round_up(h->nb, 32);
+    {
+        const int win = sp.win_length, off = (nfft - win) / 2;
+        std::vector<float> w((size_t)2 * h->nbp * win, 0.f);
+        const double two_pi = 6.283185307179586476925;
+        for (int jj = 0; jj < win; ++jj) {
+            const double wj = 0.5 - 0.5 * std::cos(two_pi * jj / win);  // periodic Hann (torch.hann_window)
+            for (int k = 0; k < h->nb; ++k) {
+                const long long ph = ((long long)k * (off + jj)) % nfft;  // exact phase reduction
+                const double a = two_pi * (double)ph / nfft;
+                w[(size_t)k * win + jj] = (float)(wj * std::cos(a));
+                w[(size_t)(h->nbp + k) * win + jj] = (float)(-wj * std::sin(a));
+            }
+        }
+        // library layout [N][ksize][C_in] with tap j, channel c <-> window sample j * hop + c: the row IS the window-ordered basis
+        h->dft.N = 2 * h->nbp; h->dft.C_in = hop; h->dft.ksize = 2;
+        L.raw(&h->dft.w, w);
+    }
+    {
+        const double fmax = sp.mel_fmax > 0 ? sp.mel_fmax : sp.sample_rate / 2;
+        const int M = sp.mel_dim;
+        std::vector<double> fpts(M + 2);
+        const double m0 = hz_to_mel_slaney(sp.mel_fmin), m1 = hz_to_mel_slaney(fmax);
+        for (int i = 0; i < M + 2; ++i) fpts[i] = mel_to_hz_slaney(m0 + (m1 - m0) * i / (M + 1));
+        std::vector<float> fb((size_t)M * h->kp, 0.f);  // [mel][bin], torchaudio.functional.melscale_fbanks(norm="slaney")
+        for (int k = 0; k < h->nb; ++k) {
+            const double f = (double)(sp.sample_rate / 2) * k / (h->nb - 1);
+            for (int m = 0; m < M; ++m) {
+                const double down = (f - fpts[m]) / (fpts[m + 1] - fpts[m]), up = (fpts[m + 2] - f) / (fpts[m + 2] - fpts[m + 1]);
+                const double v = std::max(0.0, std::min(down, up)) * 2.0 / (fpts[m + 2] - fpts[m]);
+                fb[(size_t)m * h->kp + k] = (float)v;
+            }
+        }
+        h->fbank.N = M; h->fbank.C_in = h->kp; h->fbank.ksize = 1;
+        L.raw(&h->fbank.w, fb);
+    }
+    // ---- ECAPA-TDNN up to the latent (ecapa_tdnn.py ECAPA_TDNN.forward)
+    const std::string e = "speaker_encoder.speaker_encoder";
+    conv_bn(L, &h->layer1, e + ".layer1", C, sp.mel_dim, 5);
+    for (int bi = 0; bi < 3; ++bi) {
+        SeRes2W& b = h->blocks[bi];
+        const std::string p = e + ".layer" + std::to_string(bi + 2) + ".se_res2block";
+        b.dilation = bi + 2;
+        conv_bn(L, &b.c0, p + ".0", C, C, 1);
+        conv_bn(L, &b.c2, p + ".2", C, C, 1);
+        std::vector<float> wt((size_t)7 * 3 * W * W, 0.f), bst((size_t)7 * 3 * W, 0.f);
+        for (int i = 0; i < 7; ++i) {
+            const std::string q = p + ".1.convs." + std::to_string(i);
+            const float* w = L.need(q + ".weight", (int64_t)W * W * 3);
+            const float* bb = L.need(q + ".bias", W);
+            std::vector<float> s, t;
+            batchnorm(L, p + ".1.bns." + std::to_string(i), W, &s, &t);
+            if (w && bb)
+                for (int co = 0; co < W; ++co) {
+                    for (int ci = 0; ci < W; ++ci)
+                        for (int j = 0; j < 3; ++j) wt[(((size_t)i * 3 + j) * W + ci) * W + co] = w[((size_t)co * W + ci) * 3 + j];
+                    bst[((size_t)i * 3 + 0) * W + co] = bb[co];
+                    bst[((size_t)i * 3 + 1) * W + co] = s[co];
+                    bst[((size_t)i * 3 + 2) * W + co] = t[co];
+                }
+        }
+        L.raw(&b.res2_w, wt);
+        L.raw(&b.res2_bst, bst);
+        {  // SE Linears transposed: [C][128] and [128][C] (se_residual_kernel reads them across the threads of a wave)
+            const float* w1 = L.need(p + ".3.linear1.weight", (int64_t)128 * C);
+            const float* w2 = L.need(p + ".3.linear2.weight", (int64_t)C * 128);
+            std::vector<float> t1((size_t)C * 128, 0.f), t2((size_t)128 * C, 0.f);
+            if (w1 && w2)
+                for (int o = 0; o < 128; ++o)
+                    for (int ch = 0; ch < C; ++ch) {
+                        t1[(size_t)ch * 128 + o] = w1[(size_t)o * C + ch];
+                        t2[(size_t)o * C + ch] = w2[(size_t)ch * 128 + o];
+                    }
+            L.raw(&b.se_w1, t1);
+            L.raw(&b.se_w2, t2);
+        }
+        L.vec(&b.se_b1, p + ".3.linear1.bias", 128);
+        L.vec(&b.se_b2, p + ".3.linear2.bias", C);
+    }
+    L.conv(&h->ecapa_out, e + ".conv", 1536, 3 * C, 1);
+    // ---- PerceiverResampler (perceiver_encoder.py)
+    const std::string pp = "speaker_encoder.perceiver_sampler";
+    const int inner = sp.perceiver_heads * sp.perceiver_dim_head;
+    h->ff = D * 4 * 2 / 3;  // FeedForward: int(dim * mult * 2 / 3)
+    h->ffp = (int)round_up(h->ff, 32);
+    L.conv(&h->proj_context, pp + ".proj_context", D, 1536, 1);
+    L.vec(&h->latents, pp + ".latents", (int64_t)sp.token_num * D);
+    h->perceiver.resize(sp.perceiver_depth);
+    for (int i = 0; i < sp.perceiver_depth; ++i) {
+        PerceiverLayerW& lw = h->perceiver[i];
+        const std::string q = pp + ".layers." + std::to_string(i);
+        L.conv(&lw.to_q, q + ".0.to_q", inner, D, 1, false);
+        L.conv(&lw.to_kv, q + ".0.to_kv", 2 * inner, D, 1, false);
+        L.conv(&lw.to_out, q + ".0.to_out", D, inner, 1, false);
+        L.conv(&lw.ff1, q + ".1.0", 2 * h->ff, D, 1);
+        std::vector<float> w2, wp((size_t)D * h->ffp, 0.f);
+        if (L.weight(q + ".1.2", D, h->ff, &w2))
+            for (int n = 0; n < D; ++n)
+                for (int k = 0; k < h->ff; ++k) wp[(size_t)n * h->ffp + k] = w2[(size_t)n * h->ff + k];
+        lw.ff2.N = D; lw.ff2.C_in = h->ffp; lw.ff2.ksize = 1;
+        L.raw(&lw.ff2.w, wp);
+        L.vec(&lw.ff2.b, q + ".1.2.bias", D);
+    }
+    L.vec(&h->norm_gamma, pp + ".norm.gamma", D);
+    L.conv(&h->fsq_in, "speaker_encoder.quantizer.project_in", sp.n_levels, D, 1);
+    return QA_OK;
+}
+
+int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, long long* tokens) {
+    const qa_bicodec_enc_spec& sp = h->spec;
+    const int C = sp.vocos_dim, I = sp.vocos_inter, Ld = sp.latent_dim, D = sp.codebook_dim;
+    const int64_t rows = (int64_t)B * N;
+    float* x = c.arena.alloc<float>(rows * C);
+    float* t1 = c.arena.alloc<float>(rows * C);
+    float* u = c.arena.alloc<float>(rows * std::max(I, Ld));
+    QA_TRY(vocos(c, h->backbone, x, t1, u, B, N, C, nullptr, 0, feat));
+    c.tap("enc.backbone", x, rows * C);
+    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, N, C, nullptr, 0));
+    c.tap("enc.down", x, rows * C);
+    float* z = u;  // the ConvNeXt scratch is dead: z [rows, latent]
+    QA_TRY(linear(c, x, rows, h->project, z));
+    c.tap("enc.out", z, rows * Ld);
+    float* ze = c.arena.alloc<float>(rows * D);
+    QA_TRY(linear(c, z, rows, h->in_project, ze));
+    if (!c.dry) {
+        QA_TRY(launch_l2norm_rows(ze, ze, rows, D, c.stream));
+        // one stage, no residual kept: the codebook search of rvq.hip (dist = (|e|^2 - 2 e.c) + |c|^2, lowest index on a tie)
+        QA_TRY(launch_rvq_search(ze, rows, h->codebook, h->e2, 1, sp.codebook_size, D, tokens, nullptr, 0, nullptr, c.stream));
+    }
+    c.tap("vq.latent", ze, rows * D);
+    return QA_OK;
+}
+
+int conv_bn_relu(Ctx& c, const float* x, int64_t ldx, int B, int T, const ConvBnW& w, float* y, int64_t ldy, int pad) {
+    ConvOpt o;
+    o.pad_left = pad; o.pad_right = pad; o.act = ACT_RELU; o.gamma = w.s; o.shift = w.t;
+    return conv(c, x, ldx, B, T, w.conv, y, ldy, T, o);
+}
+
+int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, int64_t ref_len, int* tokens) {
+    const qa_bicodec_enc_spec& sp = h->spec;
+    const int hop = sp.hop_length, C = sp.ecapa_channels, D = sp.spk_latent_dim, nl = sp.token_num;
+    const int nf = (int)(ref_len / hop) + 1;  // torch.stft(center=True) frames
+    const int64_t rows = (int64_t)B * nf;
+    // ---- mel spectrogram [B, nf, mel_dim]
+    float* P = c.arena.alloc<float>((size_t)B * (nf + 1) * hop);
+    float* ri = c.arena.alloc<float>((size_t)rows * 2 * h->nbp);
+    float* mag = c.arena.alloc<float>((size_t)rows * h->kp);
+    float* mel = c.arena.alloc<float>((size_t)rows * sp.mel_dim);
+    if (!c.dry) QA_TRY(launch_mel_frames(wav, B, T, ref_len, hop, nf, P, c.stream));
+    QA_TRY(conv(c, P, hop, B, nf + 1, h->dft, ri, 2 * h->nbp, nf, ConvOpt()));
+    if (!c.dry) QA_TRY(launch_spec_mag(ri, h->nbp, h->nb, mag, h->kp, rows, c.stream));
+    QA_TRY(linear(c, mag, rows, h->fbank, mel));
+    c.tap("mel", mel, rows * sp.mel_dim);
+    // ---- ECAPA-TDNN latent [B, nf, 1536]
+    float* out1 = c.arena.alloc<float>((size_t)rows * C);
+    float* cat = c.arena.alloc<float>((size_t)rows * 3 * C);
+    float* y1 = c.arena.alloc<float>((size_t)rows * C);
+    float* y2 = c.arena.alloc<float>((size_t)rows * C);
+    float* gate = c.arena.alloc<float>((size_t)B * C);
+    QA_TRY(conv_bn_relu(c, mel, sp.mel_dim, B, nf, h->layer1, out1, C, 2));
+    c.tap("ecapa.layer1", out1, rows * C);
+    const float* xin = out1;
+    int64_t ldin = C;
+    for (int bi = 0; bi < 3; ++bi) {
+        const SeRes2W& b = h->blocks[bi];
+        QA_TRY(conv_bn_relu(c, xin, ldin, B, nf, b.c0, y1, C, 0));
+        if (!c.dry) QA_TRY(launch_res2_chain(y1, y2, b.res2_w, b.res2_bst, B, nf, C, b.dilation, c.stream));
+        QA_TRY(conv_bn_relu(c, y2, C, B, nf, b.c2, y1, C, 0));
+        if (!c.dry) QA_TRY(launch_se_residual(xin, ldin, y1, b.se_w1, b.se_b1, b.se_w2, b.se_b2, gate, cat + (size_t)bi * C, 3 * C, B, nf, C,
+                                              128, c.stream));
+        xin = cat + (size_t)bi * C;
+        ldin = 3 * C;
+    }
+    c.tap("ecapa.layers234", cat, rows * 3 * C);
+    float* latent = c.arena.alloc<float>((size_t)rows * 1536);
+    {
+        ConvOpt o;
+        o.act = ACT_RELU;
+        QA_TRY(conv(c, cat, 3 * C, B, nf, h->ecapa_out, latent, 1536, nf, o));
+    }
+    c.tap("ecapa.latent", latent, rows * 1536);
+    // ---- PerceiverResampler [B, token_num, D]
+    const int inner = sp.perceiver_heads * sp.perceiver_dim_head, nk = nl + nf;
+    const int64_t lrows = (int64_t)B * nl;
+    float* xc = c.arena.alloc<float>((size_t)rows * D);
+    float* ctx = c.arena.alloc<float>((size_t)B * nk * D);
+    float* lat = c.arena.alloc<float>((size_t)lrows * D);
+    float* q = c.arena.alloc<float>((size_t)lrows * inner);
+    float* kv = c.arena.alloc<float>((size_t)B * nk * 2 * inner);
+    float* att = c.arena.alloc<float>((size_t)lrows * inner);
+    float* hh = c.arena.alloc<float>((size_t)lrows * 2 * h->ff);
+    float* gg = c.arena.alloc<float>((size_t)lrows * h->ffp);
+    float* pout = c.arena.alloc<float>((size_t)lrows * D);
+    QA_TRY(linear(c, latent, rows, h->proj_context, xc));
+    if (!c.dry) {
+        QA_TRY(launch_perceiver_ctx(h->latents, 0, xc, ctx, B, nl, nf, D, c.stream));        // cat(latents, x)
+        QA_TRY(launch_perceiver_ctx(h->latents, 0, nullptr, lat, B, nl, 0, D, c.stream));    // latents, broadcast over the batch
+    }
+    for (size_t li = 0; li < h->perceiver.size(); ++li) {
+        const PerceiverLayerW& lw = h->perceiver[li];
+        if (li > 0 && !c.dry) QA_TRY(launch_perceiver_ctx(lat, (int64_t)nl * D, nullptr, ctx, B, nl, nf, D, c.stream));
+        QA_TRY(linear(c, lat, lrows, lw.to_q, q));
+        QA_TRY(linear(c, ctx, (int64_t)B * nk, lw.to_kv, kv));
+        if (!c.dry)
+            QA_TRY(launch_attention(q, inner, kv, kv + inner, 2 * inner, att, inner, B, nl, nk, (int64_t)nk * 2 * inner, sp.perceiver_heads,
+                                    sp.perceiver_dim_head, 1.f / std::sqrt((float)sp.perceiver_dim_head), 0, c.stream));
+        QA_TRY(linear(c, att, lrows, lw.to_out, lat, ACT_NONE, lat));
+        QA_TRY(linear(c, lat, lrows, lw.ff1, hh));
+        if (!c.dry) QA_TRY(launch_geglu(hh, h->ff, gg, h->ffp, lrows, c.stream));
+        QA_TRY(linear(c, gg, lrows, lw.ff2, lat, ACT_NONE, lat));
+    }
+    if (!c.dry) QA_TRY(launch_l2norm_scale(lat, h->norm_gamma, pout, lrows, D, std::sqrt((float)D), c.stream));
+    c.tap("perceiver.out", pout, lrows * D);
+    // ---- ResidualFSQ indices
+    float* bounded = c.capture ? c.arena.alloc<float>((size_t)lrows * sp.n_levels) : nullptr;
+    if (!c.dry) QA_TRY(launch_fsq(pout, h->fsq_in.w, h->fsq_in.b, sp.levels, sp.n_levels, D, lrows, tokens, bounded, c.stream));
+    if (bounded) c.tap("fsq.bounded", bounded, lrows * sp.n_levels);
+    return QA_OK;
+}
+
+// plan (arena peak), grow the workspace, run - the pattern of qa_bicodec_detokenize
+template <class G>
+int run_enc(qa_bicodec_enc* h, void* stream, G&& graph) {
+    QA_HIP(hipSetDevice(h->device));
+    Ctx& c = h->ctx;
+    c.stream = static_cast<hipStream_t>(stream);
+    c.dry = true;
+    c.arena.begin(nullptr, 0);
+    QA_TRY(graph(c));
+    if (c.arena.peak() > h->ws_cap) {
+        if (h->ws) QA_HIP(hipFree(h->ws));
+        h->ws = nullptr;
+        h->ws_cap = 0;
+        const size_t cap = c.arena.peak() + c.arena.peak() / 8;
+        QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), cap));
+        h->ws_cap = cap;
+    }
+    c.dry = false;
+    c.taps.clear();
+    c.arena.begin(h->ws, h->ws_cap);
+    return graph(c);
+}
+
+int check_global_shape(const qa_bicodec_enc* h, int64_t B, int64_t T, int64_t ref_len) {
+    QA_REQUIRE(B > 0 && T > 0, "qa_bicodec_get_global_tokens: wav is [%lld, %lld]", (long long)B, (long long)T);
+    QA_REQUIRE(ref_len > h->spec.n_fft / 2, "qa_bicodec_get_global_tokens: a reference clip of %lld samples is too short for the centred "
+               "STFT's reflect padding (n_fft / 2 = %d)", (long long)ref_len, h->spec.n_fft / 2);
+    QA_REQUIRE(B * (ref_len / h->spec.hop_length + 2) * 3 * h->spec.ecapa_channels < (1LL << 31) && B * T < (1LL << 40),
+               "qa_bicodec_get_global_tokens: batch too large (split it)");
+    return QA_OK;
+}
+
 int ensure_ws(qa_bicodec* h, size_t bytes) {
     if (bytes <= h->ws_cap) return QA_OK;
     if (h->ws) QA_HIP(hipFree(h->ws));
@@ -522,6 +917,105 @@ int qa_bicodec_detokenize(qa_bicodec* h, const int64_t* semantic_tokens, const i
     c.taps.clear();
     c.arena.begin(h->ws, h->ws_cap);
     return detokenize_graph(h, c, (const long long*)semantic_tokens, (const long long*)global_tokens, (int)B, (int)T, wav_out);
+}
+
+int qa_bicodec_enc_create(qa_bicodec_enc** out, const qa_bicodec_enc_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
+    if (!out || !spec || !tensors) {
+        set_error("qa_bicodec_enc_create: null argument");
+        return QA_ERR_INVALID;
+    }
+    *out = nullptr;
+    QA_HIP(hipSetDevice(device));
+    std::unique_ptr<qa_bicodec_enc> h(new qa_bicodec_enc());
+    h->spec = *spec;
+    h->device = device;
+    HostTable tab(tensors, n_tensors);
+    const int st = build_encoder(h.get(), tab);
+    if (st != QA_OK) {
+        h->store.release();
+        return st;
+    }
+    *out = h.release();
+    return QA_OK;
+}
+
+void qa_bicodec_enc_destroy(qa_bicodec_enc* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    h->store.release();
+    if (h->ws) (void)hipFree(h->ws);
+    delete h;
+}
+
+int qa_bicodec_get_semantic_tokens(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, int64_t* semantic_out, void* stream) {
+    if (!h || !feat || !semantic_out) {
+        set_error("qa_bicodec_get_semantic_tokens: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(B > 0 && N > 0, "qa_bicodec_get_semantic_tokens: feat is [%lld, %lld, C]", (long long)B, (long long)N);
+    QA_REQUIRE(B * N * (int64_t)std::max(h->spec.vocos_inter, h->spec.input_channels) < (1LL << 31),
+               "qa_bicodec_get_semantic_tokens: batch too large (split it)");
+    return run_enc(h, stream, [&](Ctx& c) { return semantic_graph(h, c, feat, (int)B, (int)N, (long long*)semantic_out); });
+}
+
+int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, int64_t ref_len, int32_t* global_out, void* stream) {
+    if (!h || !wav || !global_out) {
+        set_error("qa_bicodec_get_global_tokens: null argument");
+        return QA_ERR_INVALID;
+    }
+    if (ref_len <= 0) ref_len = T;
+    QA_TRY(check_global_shape(h, B, T, ref_len));
+    return run_enc(h, stream, [&](Ctx& c) { return global_graph(h, c, wav, (int)B, T, ref_len, (int*)global_out); });
+}
+
+int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref, int64_t ref_len,
+                        int64_t* semantic_out, int32_t* global_out, void* stream) {
+    if (!h || !feat || !ref_wav || !semantic_out || !global_out) {
+        set_error("qa_bicodec_tokenize: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_TRY(qa_bicodec_get_semantic_tokens(h, feat, B, N, semantic_out, stream));
+    return qa_bicodec_get_global_tokens(h, ref_wav, B, T_ref, ref_len, global_out, stream);
+}
+
+int qa_bicodec_enc_enable_taps(qa_bicodec_enc* h, int on) {
+    if (!h) {
+        set_error("qa_bicodec_enc_enable_taps: null handle");
+        return QA_ERR_INVALID;
+    }
+    h->ctx.capture = on != 0;
+    return QA_OK;
+}
+
+int64_t qa_bicodec_enc_tap(qa_bicodec_enc* h, const char* name, float* dst, int64_t cap, void* stream) {
+    if (!h || !name) {
+        set_error("qa_bicodec_enc_tap: null argument");
+        return QA_ERR_INVALID;
+    }
+    auto it = h->ctx.taps.find(name);
+    if (it == h->ctx.taps.end()) {
+        set_error("qa_bicodec_enc_tap: no intermediate named '%s' in the last call", name);
+        return QA_ERR_MISSING;
+    }
+    if (dst) {
+        if (cap < it->second.numel) {
+            set_error("qa_bicodec_enc_tap: '%s' has %lld elements, capacity %lld", name, (long long)it->second.numel, (long long)cap);
+            return QA_ERR_INVALID;
+        }
+        QA_HIP(hipMemcpyAsync(dst, it->second.ptr, sizeof(float) * it->second.numel, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    }
+    return it->second.numel;
+}
+
+int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float eps, void* stream) {
+    if (!wav || !out) {
+        set_error("qa_wav_normalize: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(B > 0 && B < (1LL << 31) && T > 0, "qa_wav_normalize: wav is [%lld, %lld]", (long long)B, (long long)T);
+    QA_REQUIRE(eps >= 0.f, "qa_wav_normalize: eps %g < 0", (double)eps);
+    return launch_wav_normalize(wav, out, (int)B, (long long)T, eps, static_cast<hipStream_t>(stream));
 }
 
 int qa_bicodec_enable_taps(qa_bicodec* h, int on) {

@@ -1,6 +1,9 @@
-// bicodec_kernels.hip - the byte-bound pieces of BiCodec.detokenize (QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199) that are
-// not contractions: token look-ups into folded tables, AdaLayerNorm, the d-vector broadcast add.  Everything with a contraction
-// (linears, k7 / dilated k7 convolutions, the polyphase ConvTranspose1d) runs on conv_gemm.hip.
+// bicodec_kernels.hip - the pieces of BiCodec.detokenize (QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199) and BiCodec.tokenize
+// (bicodec.py:151-180) that are not plain contractions: token look-ups into folded tables, AdaLayerNorm, the d-vector broadcast add;
+// the feature normalisation, the mel framing / magnitude, the Res2 chain, SE, perceiver glue, FSQ.  Everything with a large contraction
+// (linears, k7 / dilated k7 convolutions, the polyphase ConvTranspose1d, the DFT and the mel filterbank) runs on conv_gemm.hip.
+#include <cmath>
+
 #include "kernels.h"
 
 namespace qa {
@@ -103,6 +106,376 @@ int launch_add_rowvec(float* x, const float* v, int B, int T, int C, hipStream_t
     QA_REQUIRE(C % 4 == 0, "add_rowvec: C=%d must be a multiple of 4", C);
     const long long n4 = (long long)B * T * (C / 4);
     hipLaunchKernelGGL(add_rowvec_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, s, x, v, n4, T, C);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ---------------------------------------------------------------- encoder side (BiCodec.get_semantic_tokens, bicodec.py:168-173)
+
+// Wav2Vec2FeatureExtractor(do_normalize=True) on one unpadded row (feature_extraction_wav2vec2.py zero_mean_unit_var_norm):
+// y = (x - mean) / sqrt(var + eps), population variance.  One workgroup per row; the two moments are accumulated in fp64 (the
+// reference does this in numpy float32 on the host: fp64 sums are at least as close to the exact value as its pairwise fp32 sums).
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double block_sum_d(double v, double* red) {  // 256 threads, red[4]; every thread gets the total
+    v = wave_sum_d(v);
+    __syncthreads();  // red[] may still be read by the previous call
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void wav_normalize_kernel(const float* x, float* y, long long T, float eps) {
+    __shared__ double red[4];
+    const float* xr = x + (long long)blockIdx.x * T;
+    float* yr = y + (long long)blockIdx.x * T;
+    double s = 0.0;
+    for (long long t = threadIdx.x; t < T; t += 256) s += (double)xr[t];
+    const double mean = block_sum_d(s, red) / (double)T;
+    double ss = 0.0;
+    for (long long t = threadIdx.x; t < T; t += 256) {
+        const double d = (double)xr[t] - mean;
+        ss += d * d;
+    }
+    const double var = block_sum_d(ss, red) / (double)T;
+    const float m = (float)mean, inv = (float)(1.0 / sqrt(var + (double)eps));
+    for (long long t = threadIdx.x; t < T; t += 256) yr[t] = (xr[t] - m) * inv;
+}
+int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s) {
+    QA_REQUIRE(B > 0 && T > 0, "wav_normalize: [%d, %lld]", B, T);
+    hipLaunchKernelGGL(wav_normalize_kernel, dim3((unsigned)B), dim3(256), 0, s, x, y, T, eps);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// F.normalize(x, dim=-1) on rows of D <= 64 floats (the 8-wide in_project latents in front of the codebook search,
+// factorized_vector_quantize.py:178-179): y = x / max(||x||, 1e-12).  One wave per row, lane c owns channel c.
+__global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restrict__ x, float* __restrict__ y, long long rows, int D) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float v = lane < D ? x[row * D + lane] : 0.f;
+    const float n = sqrtf(wave_sum(v * v));
+    if (lane < D) y[row * D + lane] = v / fmaxf(n, 1e-12f);
+}
+int launch_l2norm_rows(const float* x, float* y, long long rows, int D, hipStream_t s) {
+    QA_REQUIRE(D >= 1 && D <= 64, "l2norm_rows: D=%d must be 1 .. 64", D);
+    if (rows <= 0) return QA_OK;
+    hipLaunchKernelGGL(l2norm_rows_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, s, x, y, rows, D);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ---------------------------------------------------------------- encoder side: global tokens (BiCodec.get_global_tokens, bicodec.py:174-178)
+
+// The mel front as a framed signal for an implicit-GEMM DFT.  P[b, i] = clip(i - hop) for i in [0, (n_frames + 1) * hop), where clip is
+// the reference clip of ref_len samples, reflect-padded by torch.stft(center=True) (k < 0 -> -k, k >= ref_len -> 2 (ref_len - 1) - k),
+// and clip[k] = wav[k % T] is BiCodecTokenizer.get_ref_clip's tile-then-truncate as index arithmetic.  Viewed as [B, n_frames + 1, hop],
+// frame t of a window of 2 hop samples centred on t * hop is rows t and t + 1: a k = 2 convolution over hop channels.
+__global__ __launch_bounds__(256) void mel_frames_kernel(const float* __restrict__ wav, long long T, long long ref_len, int hop,
+                                                         long long n_out, float* __restrict__ P) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_out) return;
+    const int b = blockIdx.y;
+    long long k = i - hop;
+    k = k < 0 ? -k : (k >= ref_len ? 2 * (ref_len - 1) - k : k);
+    P[(long long)b * n_out + i] = wav[(long long)b * T + k % T];
+}
+int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s) {
+    QA_REQUIRE(T > 0 && ref_len > hop && B > 0, "mel_frames: T=%lld ref_len=%lld hop=%d", T, ref_len, hop);
+    const long long n_out = (long long)(n_frames + 1) * hop;
+    hipLaunchKernelGGL(mel_frames_kernel, dim3((unsigned)ceil_div(n_out, 256), (unsigned)B), dim3(256), 0, s, wav, T, ref_len, hop, n_out, P);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// |X_k| = sqrt(re^2 + im^2) of the DFT GEMM's [re (nbp) | im (nbp)] rows into [rows, ldm] with zeros from bin nb on (the K padding of
+// the filterbank GEMM)
+__global__ __launch_bounds__(256) void spec_mag_kernel(const float* __restrict__ ri, int nbp, int nb, float* __restrict__ mag, int ldm, long long n) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const long long row = g / ldm;
+    const int k = (int)(g - row * ldm);
+    float v = 0.f;
+    if (k < nb) {
+        const float re = ri[row * 2 * nbp + k], im = ri[row * 2 * nbp + nbp + k];
+        v = sqrtf(re * re + im * im);
+    }
+    mag[g] = v;
+}
+int launch_spec_mag(const float* ri, int nbp, int nb, float* mag, int ldm, long long rows, hipStream_t s) {
+    const long long n = rows * ldm;
+    if (n <= 0) return QA_OK;
+    hipLaunchKernelGGL(spec_mag_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, ri, nbp, nb, mag, ldm, n);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// Res2Conv1dReluBn (ecapa_tdnn.py Res2Conv1dReluBn, scale 8): 7 DEPENDENT width-W dilated k = 3 convolutions, each
+// sp_i = BN(ReLU(conv_i(sp_{i-1} + x_i))) (sp_0 = conv_0(x_0)), the last split passed through.  One launch per block: a workgroup owns a
+// time tile of TT = R - 2 H output frames and recomputes a halo of H = 7 d frames on each side (every step widens the receptive field by
+// d), so the chain never leaves LDS.  Frames outside [0, T) are the convolutions' zero padding and are zeroed after every step; frames
+// near the region's edge go wrong (missing neighbours) but only inside the halo.  LDS: the running split [R][W] and step i's weights
+// [3][W][W] (transposed: consecutive output channels consecutive, conflict-free), <= 80 KB.  Thread (c = tid % 64, g = tid / 64) owns
+// output channel c of the frames g, g + 16, ...; the split's 4-channel groups are wave-uniform (broadcast) float4 reads.  16 waves per
+// workgroup: at B = 16 the launch has only ~80 workgroups, so the latency of the LDS reads is hidden by waves of the same workgroup
+// (256 threads per workgroup measured 570 us per launch at 16 x 6 s).
+constexpr int RES2_R = 128;
+constexpr int RES2_THREADS = 1024;
+__global__ __launch_bounds__(RES2_THREADS) void res2_chain_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ wt,
+                                                         const float* __restrict__ bst, int T, int C, int W, int d, int TT) {
+    __shared__ __attribute__((aligned(16))) float sp[RES2_R * 64];
+    __shared__ __attribute__((aligned(16))) float sw[3 * 64 * 64];
+    constexpr int NG = RES2_THREADS / 64, NF = RES2_R / NG;
+    const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
+    const int b = blockIdx.y, H = 7 * d;
+    const int t0 = blockIdx.x * TT, rb = t0 - H;
+    const float* xb = x + (long long)b * T * C;
+    float* yb = y + (long long)b * T * C;
+    for (int e = tid; e < RES2_R * W; e += RES2_THREADS) {
+        const int f = e / W, cc = e - f * W, t = rb + f;
+        sp[f * W + cc] = (t >= 0 && t < T) ? xb[(long long)t * C + cc] : 0.f;
+    }
+    for (int i = 0; i < 7; ++i) {
+        const float* wi = wt + (long long)i * 3 * W * W;
+        for (int e = tid; e < 3 * W * W; e += RES2_THREADS) sw[e] = wi[e];
+        __syncthreads();
+        float acc[NF];
+#pragma unroll
+        for (int k = 0; k < NF; ++k) acc[k] = 0.f;
+        if (c < W) {
+            for (int j = 0; j < 3; ++j) {
+                const int off = (j - 1) * d;
+                for (int ci = 0; ci < W; ci += 4) {
+                    const float w0 = sw[(j * W + ci) * W + c], w1 = sw[(j * W + ci + 1) * W + c];
+                    const float w2 = sw[(j * W + ci + 2) * W + c], w3 = sw[(j * W + ci + 3) * W + c];
+#pragma unroll
+                    for (int k = 0; k < NF; ++k) {
+                        const int fs = g + NG * k + off;
+                        if (fs >= 0 && fs < RES2_R) {
+                            const float4 v = *reinterpret_cast<const float4*>(sp + fs * W + ci);
+                            acc[k] = fmaf(w0, v.x, acc[k]);
+                            acc[k] = fmaf(w1, v.y, acc[k]);
+                            acc[k] = fmaf(w2, v.z, acc[k]);
+                            acc[k] = fmaf(w3, v.w, acc[k]);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();  // every read of sp (and sw) for step i is done
+        if (c < W) {
+            const float bias = bst[(i * 3 + 0) * W + c], sc = bst[(i * 3 + 1) * W + c], sh = bst[(i * 3 + 2) * W + c];
+#pragma unroll
+            for (int k = 0; k < NF; ++k) {
+                const int f = g + NG * k, t = rb + f;
+                float v = 0.f;
+                if (t >= 0 && t < T) {
+                    v = fmaxf(acc[k] + bias, 0.f) * sc + sh;  // BN(ReLU(conv)): per-channel affine after the ReLU
+                    if (f >= H && f < H + TT) yb[(long long)t * C + i * W + c] = v;
+                    if (i < 6) v += xb[(long long)t * C + (i + 1) * W + c];
+                }
+                sp[f * W + c] = v;
+            }
+        }
+    }
+    for (int e = tid; e < TT * W; e += RES2_THREADS) {  // the last split passes through
+        const int f = e / W, cc = e - f * W, t = t0 + f;
+        if (t < T) yb[(long long)t * C + 7 * W + cc] = xb[(long long)t * C + 7 * W + cc];
+    }
+}
+int launch_res2_chain(const float* x, float* y, const float* wt, const float* bst, int B, int T, int C, int d, hipStream_t s) {
+    const int W = C / 8;
+    QA_REQUIRE(C % 8 == 0 && W % 4 == 0 && W <= 64, "res2_chain: C=%d (width C / 8 must be a multiple of 4, at most 64)", C);
+    QA_REQUIRE(d >= 1 && 14 * d < RES2_R, "res2_chain: dilation %d", d);
+    const int TT = RES2_R - 14 * d;
+    hipLaunchKernelGGL(res2_chain_kernel, dim3((unsigned)ceil_div(T, TT), (unsigned)B), dim3(RES2_THREADS), 0, s, x, y, wt, bst, T, C, W, d, TT);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// SE_Connect + the block's residual (ecapa_tdnn.py SE_Connect, SE_Res2Block.forward): out = x + y * sigmoid(W2 relu(W1 mean_t(y) + b1) + b2).
+// Two launches, neither of which moves a [T, C] tensor more than once: se_gate_kernel (one workgroup per batch item: time mean, the two
+// small FCs -> gate [B, C]) and se_apply_kernel (the scaled residual sum, float4 over the whole batch, written with row stride ldo: the
+// 3 block outputs are the channel slices of the concatenation the final 1x1 convolution reads).  w1t [C][Hd] and w2t [Hd][C] are the
+// Linear weights transposed at load, so that the threads of a wave read consecutive addresses in the FC loops.
+constexpr int SE_THREADS = 1024;
+__global__ __launch_bounds__(SE_THREADS) void se_gate_kernel(const float* __restrict__ y, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                             const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ gate,
+                                                             int T, int C, int Hd) {
+    extern __shared__ float sm[];
+    float* part = sm;             // [SE_THREADS]: partial time sums, thread (c, q) sums frames q, q + Q, ...
+    float* mean = sm + SE_THREADS;  // [C]
+    float* hid = mean + C;        // [Hd]
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* yb = y + (long long)b * T * C;
+    const int Q = SE_THREADS / C;  // C divides SE_THREADS (launcher)
+    {
+        const int c = tid % C, q = tid / C;
+        float a = 0.f;
+        for (int t = q; t < T; t += Q) a += yb[(long long)t * C + c];
+        part[tid] = a;
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += SE_THREADS) {
+        float a = 0.f;
+        for (int q = 0; q < Q; ++q) a += part[q * C + c];
+        mean[c] = a / (float)T;
+    }
+    __syncthreads();
+    for (int o = tid; o < Hd; o += SE_THREADS) {
+        float a = 0.f;
+#pragma unroll 8
+        for (int c = 0; c < C; ++c) a = fmaf(w1[(long long)c * Hd + o], mean[c], a);
+        hid[o] = fmaxf(a + b1[o], 0.f);
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += SE_THREADS) {
+        float a = 0.f;
+#pragma unroll 8
+        for (int o = 0; o < Hd; ++o) a = fmaf(w2[(long long)o * C + c], hid[o], a);
+        gate[(long long)b * C + c] = 1.f / (1.f + expf(-(a + b2[c])));
+    }
+}
+__global__ __launch_bounds__(256) void se_apply_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ y,
+                                                       const float* __restrict__ gate, float* __restrict__ out, long long ldo, int T, int C4,
+                                                       long long n4) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n4) return;
+    const long long row = g / C4;  // (b, t)
+    const int c = (int)(g - row * C4) * 4;
+    const long long b = row / T;
+    const float4 xv = *reinterpret_cast<const float4*>(x + row * ldx + c);
+    const float4 yv = *reinterpret_cast<const float4*>(y + row * 4 * C4 + c);
+    const float4 gv = *reinterpret_cast<const float4*>(gate + b * 4 * C4 + c);
+    float4 o;
+    o.x = xv.x + yv.x * gv.x; o.y = xv.y + yv.y * gv.y; o.z = xv.z + yv.z * gv.z; o.w = xv.w + yv.w * gv.w;
+    *reinterpret_cast<float4*>(out + row * ldo + c) = o;
+}
+int launch_se_residual(const float* x, long long ldx, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
+                       float* gate, float* out, long long ldo, int B, int T, int C, int Hd, hipStream_t s) {
+    QA_REQUIRE(C % 4 == 0 && C <= SE_THREADS && SE_THREADS % C == 0 && ldx % 4 == 0 && ldo % 4 == 0,
+               "se_residual: C=%d must divide %d (and strides be multiples of 4)", C, SE_THREADS);
+    const size_t lds = sizeof(float) * (size_t)(SE_THREADS + C + Hd);
+    QA_REQUIRE(lds <= 64 * 1024, "se_residual: C=%d, bottleneck %d", C, Hd);
+    hipLaunchKernelGGL(se_gate_kernel, dim3((unsigned)B), dim3(SE_THREADS), lds, s, y, w1, b1, w2, b2, gate, T, C, Hd);
+    QA_LAUNCH_CHECK();
+    const long long n4 = (long long)B * T * (C / 4);
+    hipLaunchKernelGGL(se_apply_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, s, x, ldx, y, gate, out, ldo, T, C / 4, n4);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// Perceiver context cat(latents, x) per batch item: ctx[b, 0:n_lat] = lat[b] (or the learned latents, broadcast, when lat_ld == 0),
+// ctx[b, n_lat:] = x[b] (skipped when x == nullptr: the context rows only change in their latent part between layers)
+__global__ __launch_bounds__(256) void perceiver_ctx_kernel(const float* __restrict__ lat, long long lat_b, const float* __restrict__ x, float* __restrict__ ctx,
+                                                            int n_lat, int T, int D, long long n) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const int rows = x ? n_lat + T : n_lat;
+    const long long b = g / ((long long)rows * D);
+    const long long r = (g / D) % rows;
+    const int c = (int)(g % D);
+    const float v = r < n_lat ? lat[b * lat_b + r * D + c] : x[(b * T + (r - n_lat)) * D + c];
+    ctx[(b * (n_lat + T) + r) * D + c] = v;
+}
+int launch_perceiver_ctx(const float* lat, long long lat_b, const float* x, float* ctx, int B, int n_lat, int T, int D, hipStream_t s) {
+    const long long n = (long long)B * (x ? n_lat + T : n_lat) * D;
+    hipLaunchKernelGGL(perceiver_ctx_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, lat, lat_b, x, ctx, n_lat, T, D, n);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// GEGLU (perceiver_encoder.py GEGLU): h [rows, 2F] = [x | gate] -> out[rows, ldo] = gelu_erf(gate) * x, zeros in columns F .. ldo - 1
+// (the K padding of the following Linear, whose F = 341 is odd)
+__global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, int F, float* __restrict__ out, int ldo, long long n) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const long long row = g / ldo;
+    const int c = (int)(g - row * ldo);
+    float v = 0.f;
+    if (c < F) {
+        const float a = h[row * 2 * F + c], z = h[row * 2 * F + F + c];
+        v = 0.5f * z * (1.f + erff(z * 0.70710678118654752f)) * a;
+    }
+    out[g] = v;
+}
+int launch_geglu(const float* h, int F, float* out, int ldo, long long rows, hipStream_t s) {
+    const long long n = rows * ldo;
+    hipLaunchKernelGGL(geglu_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, h, F, out, ldo, n);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// PerceiverResampler's final RMSNorm (perceiver_encoder.py RMSNorm): F.normalize(x) * sqrt(D) * gamma - an L2 norm clamped at 1e-12,
+// not a mean square.  One wave per row, D <= 256.
+__global__ __launch_bounds__(256) void l2norm_scale_kernel(const float* __restrict__ x, const float* __restrict__ gamma, float* __restrict__ y,
+                                                           long long rows, int D, float scale) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float v[4], ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane + 64 * k;
+        v[k] = c < D ? x[row * D + c] : 0.f;
+        ss = fmaf(v[k], v[k], ss);
+    }
+    const float n = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane + 64 * k;
+        if (c < D) y[row * D + c] = v[k] / n * scale * gamma[c];
+    }
+}
+int launch_l2norm_scale(const float* x, const float* gamma, float* y, long long rows, int D, float scale, hipStream_t s) {
+    QA_REQUIRE(D >= 1 && D <= 256, "l2norm_scale: D=%d", D);
+    hipLaunchKernelGGL(l2norm_scale_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, s, x, gamma, y, rows, D, scale);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ResidualFSQ.forward with one quantizer (residual_fsq.py:158+, finite_scalar_quantization.py:126-160): z = project_in(x) (scale 1),
+// bound(z) = tanh(z + atanh(offset / half_l)) half_l - offset, round half to even (rintf: torch.round), index = sum (q + L // 2) basis.
+// One wave per token (the projection's D products spread over the lanes, one wave_sum per level); `bounded` [rows, nl] is the test tap
+// (may be null).
+struct FsqConsts {
+    int nl;
+    int levels[8];
+    float half_l[8], offset[8], shift[8];
+};
+__global__ __launch_bounds__(256) void fsq_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                  FsqConsts q, int D, long long rows, int* __restrict__ tokens, float* __restrict__ bounded) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* xr = x + r * D;
+    int idx = 0, basis = 1;
+    for (int d = 0; d < q.nl; ++d) {
+        float z = 0.f;
+        for (int k = lane; k < D; k += 64) z = fmaf(w[d * D + k], xr[k], z);
+        z = wave_sum(z) + bias[d];
+        const float bd = tanhf(z + q.shift[d]) * q.half_l[d] - q.offset[d];
+        if (bounded && lane == 0) bounded[r * q.nl + d] = bd;
+        idx += ((int)rintf(bd) + q.levels[d] / 2) * basis;
+        basis *= q.levels[d];
+    }
+    if (lane == 0) tokens[r] = idx;
+}
+int launch_fsq(const float* x, const float* w, const float* bias, const int* levels, int nl, int D, long long rows, int* tokens,
+               float* bounded, hipStream_t s) {
+    QA_REQUIRE(nl >= 1 && nl <= 8, "fsq: %d levels", nl);
+    FsqConsts q{};
+    q.nl = nl;
+    for (int d = 0; d < nl; ++d) {  // the reference's fp32 constants: (L - 1) * (1 + 1e-3) / 2, 0.5 for even L, atanh(offset / half_l)
+        q.levels[d] = levels[d];
+        q.half_l[d] = (float)(levels[d] - 1) * 1.001f / 2.f;
+        q.offset[d] = levels[d] % 2 == 0 ? 0.5f : 0.f;
+        q.shift[d] = std::atanh(q.offset[d] / q.half_l[d]);
+    }
+    hipLaunchKernelGGL(fsq_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, s, x, w, bias, q, D, rows, tokens, bounded);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

@@ -46,7 +46,7 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
 // ---- activation codes shared by kernels (match qa_conv_args) ----
-enum { ACT_NONE = 0, ACT_ELU = 1, ACT_GELU = 2, ACT_SILU = 3, ACT_SNAKE = 4, ACT_TANH = 5 };  // SNAKE needs ConvParams::alpha (conv_gemm epilogue only)
+enum { ACT_NONE = 0, ACT_ELU = 1, ACT_GELU = 2, ACT_SILU = 3, ACT_SNAKE = 4, ACT_TANH = 5, ACT_RELU = 6 };  // SNAKE needs ConvParams::alpha (conv_gemm epilogue only)
 enum { PAD_ZERO = 0, PAD_REFLECT = 1 };
 
 // ELU(alpha=1).  exp(x) - 1 instead of expm1f: ocml's expm1f brings divergent slow paths (and scratch spills) into the GEMM
@@ -62,6 +62,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
         case ACT_GELU: return gelu_erf_f(v);
         case ACT_SILU: return silu_f(v);
         case ACT_TANH: return tanhf(v);
+        case ACT_RELU: return fmaxf(v, 0.f);
         default: return v;
     }
 }

@@ -64,6 +64,10 @@ SPEC_XLSR53 = SSLSpec(conv_bias=True, feat_extract_norm="layer", hidden_size=102
                       intermediate_size=4096, do_stable_layer_norm=True, select=(11, 14, 16))  # H-Codec 1.5
 
 
+# facebook/wav2vec2-large-xlsr-53 as BiCodecTokenizer uses it (QuarkAudio-UniSE/model/bicodec/audio_tokenizer.py:47-52,74-90): hidden
+# states 11, 14, 16 averaged, no 160-sample pad, no compression (the input is Wav2Vec2FeatureExtractor-normalised: bicodec.wav_normalize)
+SPEC_XLSR53_BICODEC = dataclasses.replace(SPEC_XLSR53, pad=0, compress_exponent=0.0)
+
 # microsoft/wavlm-base-plus as UniSE uses it (QuarkAudio-UniSE/model/model.py:30,38-51): mean of all hidden states, no compression
 SPEC_WAVLM_BASE_PLUS = SSLSpec(num_buckets=320, max_bucket_distance=800, compress_exponent=0.0)
 

@@ -472,6 +472,94 @@ def bicodec_tokens(seed: int, batch: int, frames: int, spec=None):
     return sem, glob
 
 
+def bicodec_encoder_state_dict(seed: int, spec=None) -> Dict[str, torch.Tensor]:
+    """Seeded weights with the key names / shapes of the parts of `BiCodec.state_dict()` that `get_semantic_tokens` reads
+    (bicodec.py:167-172): encoder.* (Encoder, feat_encoder.py:29-92), quantizer.in_project (weight_g / weight_v) and
+    quantizer.codebook (checked against the reference's own modules by tests/test_bicodec_tokenize_oracle_cpu.py).  `spec` is a
+    BiCodecEncoderSpec.  Scaled so that the tokens are not degenerate: the final LayerNorm keeps every frame at unit scale, the
+    in_project spreads the latents over all 8 directions, and the codebook is isotropic, so the cosine arg-max lands on many codes."""
+    from .bicodec import SPEC_BICODEC_ENCODER
+
+    spec = spec or SPEC_BICODEC_ENCODER
+    g = _Gen(seed)
+    rng, sd = g.rng, g.sd
+    C, I = spec.vocos_dim, spec.vocos_inter
+
+    def vocos(p, cin, n_layers):
+        g.conv(p + ".embed", C, cin, 7)
+        g.norm(p + ".norm", C)
+        for i in range(n_layers):
+            q = f"{p}.convnext.{i}"
+            g.conv(q + ".dwconv", C, 1, 7)
+            g.norm(q + ".norm", C)
+            g.linear(q + ".pwconv1", I, C)
+            g.linear(q + ".pwconv2", C, I)
+            sd[q + ".gamma"] = _t(rng.uniform(0.5, 1.5, size=C) / n_layers)
+        g.norm(p + ".final_layer_norm", C)
+
+    vocos("encoder.encoder", spec.input_channels, spec.vocos_layers)
+    for i in range(2):
+        vocos(f"encoder.downsample.{i}.1", C, 2)
+    g.linear("encoder.project", spec.latent_dim, C)
+    g.conv("quantizer.in_project", spec.codebook_dim, spec.latent_dim, 1, wn=True)
+    sd["quantizer.codebook.weight"] = _t(rng.standard_normal((spec.codebook_size, spec.codebook_dim)))
+    return sd
+
+
+def bicodec_speaker_state_dict(seed: int, spec=None) -> Dict[str, torch.Tensor]:
+    """Seeded weights with the key names / shapes of the parts of `BiCodec.state_dict()` that `get_global_tokens` reads
+    (bicodec.py:174-178): speaker_encoder.speaker_encoder.* (ECAPA-TDNN with BatchNorm running statistics; the pooling / x-vector head
+    is not read), speaker_encoder.perceiver_sampler.* and speaker_encoder.quantizer.project_in.  `spec` is a BiCodecEncoderSpec.
+    Scaled so that the global tokens are not degenerate: the BatchNorm statistics roughly whiten each ReLU output, the first
+    convolution is scaled for mel magnitudes (no log), and project_in spreads the L2-normalised perceiver output over all four FSQ
+    levels of every dimension."""
+    from .bicodec import SPEC_BICODEC_ENCODER
+
+    spec = spec or SPEC_BICODEC_ENCODER
+    g = _Gen(seed)
+    rng, sd = g.rng, g.sd
+    C, W = spec.ecapa_channels, spec.ecapa_channels // 8
+    p = "speaker_encoder.speaker_encoder"
+
+    def bn(name, c):
+        sd[name + ".weight"] = _t(1.0 + 0.1 * rng.standard_normal(c))
+        sd[name + ".bias"] = _t(0.1 * rng.standard_normal(c))
+        sd[name + ".running_mean"] = _t(rng.uniform(0.1, 0.4, size=c))
+        sd[name + ".running_var"] = _t(rng.uniform(0.1, 0.3, size=c))
+        sd[name + ".num_batches_tracked"] = torch.tensor(100, dtype=torch.int64)
+
+    def crb(name, cout, cin, k, gain=1.0):
+        g.conv(name + ".conv", cout, cin, k, gain=gain)
+        bn(name + ".bn", cout)
+
+    crb(p + ".layer1", C, spec.mel_dim, 5, gain=0.05)
+    for li in (2, 3, 4):
+        q = f"{p}.layer{li}.se_res2block"
+        crb(q + ".0", C, C, 1)
+        for i in range(7):
+            g.conv(f"{q}.1.convs.{i}", W, W, 3)
+            bn(f"{q}.1.bns.{i}", W)
+        crb(q + ".2", C, C, 1)
+        g.linear(q + ".3.linear1", 128, C)
+        g.linear(q + ".3.linear2", C, 128)
+    g.conv(p + ".conv", 1536, 3 * C, 1)
+    pp = "speaker_encoder.perceiver_sampler"
+    D, inner = spec.spk_latent_dim, spec.perceiver_heads * spec.perceiver_dim_head
+    ff = int(D * 4 * 2 / 3)
+    g.linear(pp + ".proj_context", D, 1536, gain=8.0)  # the ECAPA latent is small after ReLU: context and latents of one scale
+    sd[pp + ".latents"] = _t(0.5 * rng.standard_normal((spec.token_num, D)))
+    for i in range(spec.perceiver_depth):
+        q = f"{pp}.layers.{i}"
+        g.linear(q + ".0.to_q", inner, D, bias=False)
+        g.linear(q + ".0.to_kv", 2 * inner, D, bias=False)
+        g.linear(q + ".0.to_out", D, inner, bias=False)
+        g.linear(q + ".1.0", 2 * ff, D)
+        g.linear(q + ".1.2", D, ff)
+    sd[pp + ".norm.gamma"] = _t(1.0 + 0.1 * rng.standard_normal(D))
+    g.linear("speaker_encoder.quantizer.project_in", len(spec.fsq_levels), D, gain=3.0)
+    return sd
+
+
 def ssl_state_dict(spec, seed: int = 21) -> Dict[str, torch.Tensor]:
     """Seeded random weights in the transformers HubertModel / Wav2Vec2Model key layout (shapes only depend on the spec)."""
     g = torch.Generator().manual_seed(seed)
