@@ -467,13 +467,30 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
                            int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                            int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream);
 
+/* LLM_SFT.forward (llm_sft.py:37-90): teacher-forced scoring of given token streams.  With Lt = global_length + semantic_length + 2,
+ * input_ids = [0, global_ids + 3, 1, semantic_ids + 3 + global_size] and target_ids = [global_ids + 3, 1, semantic_ids + 3 + global_size, 2];
+ * the prompt is generate's, the body runs causally over all prompt + Lt positions from position 0, and output_head covers the FULL
+ * vocabulary on the last Lt rows.  Loss: F.kl_div(log_softmax(z), true_dist, 'batchmean') with true_dist = 1 - label_smoothing at the
+ * target and label_smoothing / (V - 1) elsewhere (llm.py:87-104, 0 log 0 = 0); accuracy: first arg-max == target.
+ *   global_ids int64 [B, global_length], semantic_ids int64 [B, semantic_length] (device; offsets subtracted).  The shifted ids must
+ *   lie in [0, V) - check them with qa_codes_check (the reference's nn.Embedding raises IndexError); the kernel clamps, it never reads
+ *   outside the table.
+ * Outputs (device): loss_per_seq float [B] (mean KL over the sequence's Lt rows), correct_per_seq int64 [B] (rows whose arg-max is
+ * the target), loss / acc float scalars over all B * Lt rows.  Every reduction runs in a fixed order: a sequence's values do not depend
+ * on its batch, and QA_LM_SCORE_ROWS (head rows per launch) changes no bit.  At most 4096 positions (max_position_embeddings).
+ * Asynchronous on `stream`; uses a workspace of its own (generate's buffers and captured steps are untouched). */
+int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
+                float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream);
+
 /* Test hook, as qa_hcodec_enable_taps: while on, qa_lm_generate / qa_lm_generate_sampled record the logits of the active vocabulary
  * slice at every decode step (what the head computes before the pick / sampler), in storage of their own: turning taps on changes no
  * token.  Not supported under a caller's stream capture (the call is refused). */
 int qa_lm_enable_taps(qa_lm* lm, int on);
 /* Test hook: copy a snapshot of the LAST generate call into `dst` (device, fp32, capacity `cap` elements; NULL: only return the
  * count).  Returns the element count or a negative status.  Names: "logits.global" [B, global_length + 1, global_size] (the
- * discarded last global step included), "logits.semantic" [B, semantic_length, semantic_size]. */
+ * discarded last global step included), "logits.semantic" [B, semantic_length, semantic_size]; of the LAST qa_lm_score call:
+ * "logits.forced" [B, Lt, V] (the full-vocabulary teacher-forced logits). */
 int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* stream);
 
 /* Kernel-level entry point of the sampler (parity / distribution tests): CustomLlamaModel.sample_logits (llm.py:253-288) on

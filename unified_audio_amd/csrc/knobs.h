@@ -31,7 +31,8 @@ namespace qa {
     X(LM_MLP_FUSED, "QA_LM_MLP_FUSED", 1, "decode step: gate/up + SwiGLU + down of 16 activation columns per workgroup in one launch emitting K-slice partials, summed by a reduce launch (0: separate gate/up and down launches)") \
     X(LM_PF, "QA_LM_PF", 7, "decode step: cross-launch L2 weight prefetch planes (bit mask; lm_decode.h PfArgs): 1 qkv launch -> o_proj weights, 2 o_proj launch -> fused-MLP weights, 4 MLP launch -> next layer's qkv weights (last layer: the head slice), 8 head launch -> layer 0 qkv weights") \
     X(LM_ROWSPLIT, "QA_LM_ROWSPLIT", 3, "decode step at 9 .. 16 sequences: two 8-row groups instead of one 16-row group in the qkv launch (bit 1) and the fused-MLP launch (bit 2)") \
-    X(LM_CHAINS, "QA_LM_CHAINS", 0, "generate: number of concurrent chains on internal streams (0: ceil(B / 64) - one chain serves up to 64 sequences, two row groups of 32 per launch; a count that would put more than 64 sequences into a chain is raised)")
+    X(LM_CHAINS, "QA_LM_CHAINS", 0, "generate: number of concurrent chains on internal streams (0: ceil(B / 64) - one chain serves up to 64 sequences, two row groups of 32 per launch; a count that would put more than 64 sequences into a chain is raised)") \
+    X(LM_SCORE_ROWS, "QA_LM_SCORE_ROWS", 4096, "qa_lm_score: target rows per output_head launch (the logits buffer holds this many rows of the full vocabulary; any value gives the same bits)")
 
 enum Knob {
 #define QA_KNOB_ENUM(id, name, def, doc) K_##id,

@@ -8,6 +8,9 @@
 // The whole loop is device-resident: token ids never visit the host between steps (embedding gather and arg-max read / write a
 // device int64 vector), the KV cache is owned by the handle's workspace, prefill runs on the implicit-GEMM / flash kernels
 // and each decode step on the weight-streaming skinny GEMM + single-query attention kernels.
+//
+// qa_lm_score is the other entry point, LLM_SFT.forward (llm_sft.py:37-90): the whole teacher-forced sequence through the same body
+// (every layer), output_head over the full vocabulary on the target rows, and the label-smoothed KL + accuracy (llm.py:87-104).
 #include <memory>
 
 #include <cstdlib>
@@ -20,6 +23,13 @@ int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_
                            const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s);
 int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
                    hipStream_t s);
+int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
+                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s);
+int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, const long long* tgt, float c, float sm, float* row_kl,
+                       int* row_ok, hipStream_t s);
+int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
+                         hipStream_t s);
+int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
 
 }  // namespace qa
 
@@ -80,6 +90,12 @@ struct qa_lm {
     float* tap_buf = nullptr;
     size_t tap_cap = 0;
     int64_t tap_n[2] = {-1, -1};
+    // qa_lm_score: a workspace and a tap buffer of its own, so that scoring never moves a buffer a captured decode step points into
+    char* score_ws = nullptr;
+    size_t score_ws_cap = 0;
+    float* score_tap = nullptr;  // logits.forced [B][Lt][V] of the last score call (taps on)
+    size_t score_tap_cap = 0;
+    int64_t score_tap_n = -1;
 };
 
 namespace {
@@ -273,12 +289,14 @@ struct SampleCfg {
 };
 
 // one pass of the Llama body over `n` new positions per sequence, positions pos0..pos0+n-1 (the prefill)
-int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len, bool skip_last_mlp) {
+// one_cache: every layer writes its keys / values into the same [B, max_len, d] pair (scoring: nothing reads a layer's cache after the
+// layer's own attention)
+int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len, bool skip_last_mlp, bool one_cache = false) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H;
     const int64_t rows = (int64_t)B * n;
     const float scale = 1.0f / std::sqrt((float)hd);
-    const size_t cache_stride = (size_t)B * max_len * d;
+    const size_t cache_stride = one_cache ? 0 : (size_t)B * max_len * d;
     for (int i = 0; i < sp.n_layers; ++i) {
         const LMLayer& L = lm->layers[i];
         float* kc = b.kc + i * cache_stride;
@@ -598,6 +616,76 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     return QA_OK;
 }
 
+// ---- teacher-forced scoring (llm_sft.py:37-90).  Sequences go through in groups of at most LM_MAX_ROWS (the workspace stays bounded;
+// every stage is batch-invariant, so a group boundary changes no bit).  Per group: adapters + prompt (as generate) and the codec_embedding
+// rows of input_ids behind it, the body over all Lp + Lt positions from position 0 with every layer, the final RMSNorm on the Lt target
+// rows, then output_head over the full vocabulary in chunks of QA_LM_SCORE_ROWS rows, each reduced by the row-loss kernel right behind it.
+struct ScoreArgs {
+    int task, Ne, Nm, B, G, T;
+    const float *enroll, *mix;
+    const long long *gids, *sids;
+    double eps;
+    float* loss_seq;
+    long long* correct_seq;
+    float *loss, *acc;
+};
+
+int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
+    const qa_lm_spec& sp = lm->spec;
+    const int d = sp.hidden, I = sp.intermediate, V = vocab_of(sp);
+    const int Lp = 1 + (a.enroll ? 1 + a.Ne : 0) + 1 + a.Nm, Lt = a.G + a.T + 2, n = Lp + Lt;
+    QA_REQUIRE(n <= LM_MAX_POS, "qa_lm_score: %d positions (prompt %d + targets %d) exceed max_position_embeddings %d", n, Lp, Lt, LM_MAX_POS);
+    const int GB = std::min(a.B, LM_MAX_ROWS);
+    const int64_t prow = (int64_t)GB * n, trow = (int64_t)GB * Lt;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(knob(K_LM_SCORE_ROWS), trow));
+    LMBuffers b{};
+    b.x = c.arena.alloc<float>(prow * d);
+    b.hn = c.arena.alloc<float>(prow * d);   // also the assembled prompt (before the body) and the normalised target rows (after it)
+    b.qkv = c.arena.alloc<float>(prow * 3 * d);
+    b.att = c.arena.alloc<float>(prow * d);  // also the compacted target rows (after the body)
+    b.g = c.arena.alloc<float>(prow * I);
+    b.u = c.arena.alloc<float>(prow * I);
+    b.kc = c.arena.alloc<float>(prow * d);   // one layer's cache, shared by all layers (lm_body one_cache)
+    b.vc = c.arena.alloc<float>(prow * d);
+    float* emix = c.arena.alloc<float>((size_t)GB * a.Nm * d);
+    float* eenr = a.enroll ? c.arena.alloc<float>((size_t)GB * a.Ne * d) : nullptr;
+    long long* tgt = c.arena.alloc<long long>(trow);
+    float* row_kl = c.arena.alloc<float>(trow);
+    int* row_ok = c.arena.alloc<int>(trow);
+    float* logits = c.arena.alloc<float>((size_t)chunk * V);
+    double* seq_sum = c.arena.alloc<double>(a.B);
+    if (c.dry) return QA_OK;
+    // the reference's true_dist is fp32: confidence 1 - eps and eps / (V - 1) filled into a float tensor (llm.py:95-98)
+    const float conf = (float)(1.0 - a.eps), smooth = (float)(a.eps / (V - 1));
+    for (int b0 = 0; b0 < a.B; b0 += GB) {
+        const int gb = std::min(GB, a.B - b0);
+        QA_TRY(lm_linear(c, a.mix + (size_t)b0 * a.Nm * sp.feats_dim, (int64_t)gb * a.Nm, lm->adapter, emix));
+        if (a.enroll) QA_TRY(lm_linear(c, a.enroll + (size_t)b0 * a.Ne * sp.feats_dim, (int64_t)gb * a.Ne, lm->adapter, eenr));
+        QA_TRY(launch_assemble_prompt(b.hn, lm->task_emb + (size_t)a.task * d, a.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
+                                      a.Ne, a.Nm, d, c.stream));
+        QA_HIP(hipMemcpy2DAsync(b.x, sizeof(float) * n * d, b.hn, sizeof(float) * Lp * d, sizeof(float) * Lp * d, gb, hipMemcpyDeviceToDevice,
+                                c.stream));
+        QA_TRY(launch_lm_targets(b.x + (size_t)Lp * d, (long long)n * d, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T,
+                                 a.T, V, 3, 3 + sp.global_size, tgt, gb, d, c.stream));
+        QA_TRY(lm_body(lm, c, b, gb, n, 0, n, false, true));
+        // final RMSNorm (its weight is folded into output_head) on the last Lt rows of every sequence (llm_sft.py:82)
+        QA_HIP(hipMemcpy2DAsync(b.att, sizeof(float) * Lt * d, b.x + (size_t)Lp * d, sizeof(float) * n * d, sizeof(float) * Lt * d, gb,
+                                hipMemcpyDeviceToDevice, c.stream));
+        const int64_t rows = (int64_t)gb * Lt;
+        QA_TRY(launch_rmsnorm(b.att, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
+        // output_head, V = 3 + global + semantic columns (odd for the UniSE vocabulary: the GEMM's scalar epilogue, no padding)
+        for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+            const int64_t nr = std::min(chunk, rows - r0);
+            QA_TRY(lm_linear(c, b.hn + (size_t)r0 * d, nr, lm->head, logits));
+            QA_TRY(launch_lm_row_loss(logits, V, V, nr, tgt + r0, conf, smooth, row_kl + r0, row_ok + r0, c.stream));
+            if (tap)
+                QA_HIP(hipMemcpyAsync(tap + ((size_t)b0 * Lt + r0) * V, logits, sizeof(float) * nr * V, hipMemcpyDeviceToDevice, c.stream));
+        }
+        QA_TRY(launch_lm_seq_reduce(row_kl, row_ok, gb, Lt, seq_sum + b0, a.loss_seq + b0, a.correct_seq + b0, c.stream));
+    }
+    return launch_lm_batch_reduce(seq_sum, a.correct_seq, a.B, Lt, a.loss, a.acc, c.stream);
+}
+
 int ensure_ws(qa_lm* lm, size_t bytes) {
     if (bytes <= lm->ws_cap) return QA_OK;
     QA_HIP(hipDeviceSynchronize());  // earlier calls may still be running out of the old workspace
@@ -665,6 +753,8 @@ void qa_lm_destroy(qa_lm* lm) {
     lm->store.release();
     if (lm->ws) (void)hipFree(lm->ws);
     if (lm->tap_buf) (void)hipFree(lm->tap_buf);
+    if (lm->score_ws) (void)hipFree(lm->score_ws);
+    if (lm->score_tap) (void)hipFree(lm->score_tap);
     delete lm;
 }
 
@@ -730,6 +820,66 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
                             semantic_ids, stream);
 }
 
+int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
+                float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
+    if (!lm || !mix_feats || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
+        (semantic_length > 0 && !semantic_ids)) {
+        set_error("qa_lm_score: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_score: task %d out of range (KeyError in the reference)", task);
+    QA_REQUIRE(B > 0 && n_mix > 0 && global_length >= 0 && semantic_length >= 0, "qa_lm_score: bad shape");
+    QA_REQUIRE(!enroll_feats || n_enroll > 0, "qa_lm_score: enrollment given with no frames");
+    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "qa_lm_score: label_smoothing %g outside [0, 1]", label_smoothing);
+    QA_REQUIRE(n_mix <= LM_MAX_POS && n_enroll <= LM_MAX_POS && B <= (1 << 24), "qa_lm_score: bad shape");
+    QA_HIP(hipSetDevice(lm->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+    const bool capturing = cs == hipStreamCaptureStatusActive;
+    ScoreArgs a{task, enroll_feats ? (int)n_enroll : 0, (int)n_mix, (int)B, global_length, semantic_length, enroll_feats, mix_feats,
+                reinterpret_cast<const long long*>(global_ids), reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq,
+                reinterpret_cast<long long*>(correct_per_seq), loss, acc};
+    const int Lt = global_length + semantic_length + 2;
+    lm->score_tap_n = -1;
+    float* tap = nullptr;
+    if (lm->taps) {
+        QA_REQUIRE(!capturing, "qa_lm_score: taps (a test hook) are not supported under a stream capture");
+        const size_t n = (size_t)B * Lt * vocab_of(lm->spec);
+        if (n > lm->score_tap_cap) {
+            QA_HIP(hipDeviceSynchronize());  // earlier calls may still be writing the old buffer
+            if (lm->score_tap) QA_HIP(hipFree(lm->score_tap));
+            lm->score_tap = nullptr;
+            lm->score_tap_cap = 0;
+            QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->score_tap), sizeof(float) * n));
+            lm->score_tap_cap = n;
+        }
+        tap = lm->score_tap;
+    }
+    Ctx c;
+    c.stream = s;
+    c.dry = true;
+    c.arena.begin(nullptr, 0);
+    QA_TRY(score_graph(lm, c, a, tap));
+    if (c.arena.peak() > lm->score_ws_cap) {
+        QA_REQUIRE(!capturing, "qa_lm_score under a stream capture needs %zu bytes of workspace, the handle holds %zu: make one call of the "
+                   "same shape outside the capture first", c.arena.peak(), lm->score_ws_cap);
+        QA_HIP(hipDeviceSynchronize());  // earlier calls may still be running out of the old workspace
+        if (lm->score_ws) QA_HIP(hipFree(lm->score_ws));
+        lm->score_ws = nullptr;
+        lm->score_ws_cap = 0;
+        const size_t cap = c.arena.peak() + c.arena.peak() / 8;
+        QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->score_ws), cap));
+        lm->score_ws_cap = cap;
+    }
+    c.dry = false;
+    c.arena.begin(lm->score_ws, lm->score_ws_cap);
+    QA_TRY(score_graph(lm, c, a, tap));
+    if (tap) lm->score_tap_n = (int64_t)B * Lt * vocab_of(lm->spec);
+    return QA_OK;
+}
+
 int qa_lm_enable_taps(qa_lm* lm, int on) {
     if (!lm) {
         set_error("qa_lm_enable_taps: null handle");
@@ -745,18 +895,19 @@ int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* st
         return QA_ERR_INVALID;
     }
     const std::string nm(name);
-    const int which = nm == "logits.global" ? 0 : nm == "logits.semantic" ? 1 : -1;
-    if (which < 0 || lm->tap_n[which] < 0) {
-        set_error("qa_lm_tap: no intermediate named '%s' in the last call (names: logits.global, logits.semantic; taps must be on)", name);
+    const int which = nm == "logits.global" ? 0 : nm == "logits.semantic" ? 1 : nm == "logits.forced" ? 2 : -1;
+    if (which < 0 || (which < 2 ? lm->tap_n[which] : lm->score_tap_n) < 0) {
+        set_error("qa_lm_tap: no intermediate named '%s' in the last call (names: logits.global, logits.semantic of generate, "
+                  "logits.forced of score; taps must be on)", name);
         return QA_ERR_MISSING;
     }
-    const int64_t n = lm->tap_n[which];
+    const int64_t n = which < 2 ? lm->tap_n[which] : lm->score_tap_n;
     if (dst) {
         if (cap < n) {
             set_error("qa_lm_tap: '%s' has %lld elements, capacity %lld", name, (long long)n, (long long)cap);
             return QA_ERR_INVALID;
         }
-        const float* src = lm->tap_buf + (which == 0 ? 0 : lm->tap_n[0]);
+        const float* src = which == 2 ? lm->score_tap : lm->tap_buf + (which == 0 ? 0 : lm->tap_n[0]);
         QA_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     }
     return n;

@@ -1,6 +1,7 @@
 // lm_kernels.hip - the UniSE AR-LM's prefill-side kernels: prompt assembly, RoPE + KV-cache append over a whole
 // prompt, and the skinny-M weight-streaming GEMM (per-item linears of at most 32 rows: tiny prompts here, BiCodec's d-vector / AdaLN
-// linears in bicodec.cpp).  The decode step lives in lm_decode.hip; the round-1 per-op decode kernels (embedding gather, arg-max,
+// linears in bicodec.cpp), and the teacher-forced scoring kernels (target embedding, row loss, fixed-order reduces).  The decode step
+// lives in lm_decode.hip; the round-1 per-op decode kernels (embedding gather, arg-max,
 // single-query attention behind QA_LM_UNFUSED) were removed in round 5.
 #include "kernels.h"
 
@@ -210,6 +211,185 @@ int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int
     const long long total = (long long)B * n * H * (hd / 2);
     hipLaunchKernelGGL(rope_kv_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0,
                        max_len);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Teacher-forced scoring (LLM_SFT.forward, llm_sft.py:37-90).  With Lt = G + T + 2 target positions per sequence:
+//   input_ids  = [0, g + 3, 1, s + soff]      -> codec_embedding rows at x[b, t, :] (x: rows of ldx_seq floats per sequence)
+//   target_ids = [g + 3, 1, s + soff, 2]      -> tgt[b * Lt + t]
+// Ids are clamped into [0, V) so that no read leaves the table; the caller range-checks them first (qa_codes_check: IndexError).
+__device__ __forceinline__ long long clamp_id(long long v, int V) { return v < 0 ? 0 : (v >= V ? V - 1 : v); }
+
+__global__ __launch_bounds__(256) void lm_targets_kernel(float* __restrict__ x, long long ldx_seq, const float* __restrict__ table,
+                                                         const long long* __restrict__ gids, int G, const long long* __restrict__ sids,
+                                                         int T, int V, int goff, int soff, long long* __restrict__ tgt, int B, int d) {
+    const int Lt = G + T + 2, d4 = d >> 2;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * Lt * d4) return;
+    const int c = (int)(gid % d4) * 4;
+    const int t = (int)((gid / d4) % Lt);
+    const int b = (int)(gid / ((long long)d4 * Lt));
+    long long in_id, tg;
+    if (t == 0) in_id = 0;
+    else if (t <= G) in_id = gids[(long long)b * G + t - 1] + goff;
+    else if (t == G + 1) in_id = 1;
+    else in_id = sids[(long long)b * T + t - G - 2] + soff;
+    if (t < G) tg = gids[(long long)b * G + t] + goff;
+    else if (t == G) tg = 1;
+    else if (t < Lt - 1) tg = sids[(long long)b * T + t - G - 1] + soff;
+    else tg = 2;
+    in_id = clamp_id(in_id, V);
+    *reinterpret_cast<float4*>(x + b * ldx_seq + (long long)t * d + c) = *reinterpret_cast<const float4*>(table + in_id * d + c);
+    if (c == 0) tgt[(long long)b * Lt + t] = clamp_id(tg, V);
+}
+
+int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
+                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s) {
+    QA_REQUIRE(d % 4 == 0 && ldx_seq % 4 == 0, "lm_targets: d %d / row stride must be multiples of 4", d);
+    const long long total = (long long)B * (G + T + 2) * (d / 4);
+    hipLaunchKernelGGL(lm_targets_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, ldx_seq, table, gids, G, sids, T, V,
+                       goff, soff, tgt, B, d);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// Row loss: one workgroup per row of the head's logits z [rows, V] (row stride ldl), ONE pass over the row.  Every thread keeps
+// (running max m, sum of exp(z - m), sum of z, first arg-max) over the columns it owns (j = tid + 256 i, increasing), the four waves
+// merge theirs with a fixed butterfly and thread 0 merges the four waves in order: no atomics, the same bits in any batch.
+// Label-smoothed KL against true_dist = c at the target, s elsewhere (llm.py:87-104), in closed form (0 log 0 = 0, as xlogy):
+//   kl = c log c + (V - 1) s log s - c (z_y - lse) - s (sum z - z_y - (V - 1) lse)
+struct RowStat {
+    float m, s, sz, bv;
+    int bi;
+};
+__device__ __forceinline__ RowStat row_merge(RowStat a, const RowStat& b) {
+    const float M = fmaxf(a.m, b.m);  // a part with s = 0 owns no column (m = -inf): it adds nothing, and no exp(-inf - -inf) is formed
+    a.s = (a.s > 0.f ? a.s * expf(a.m - M) : 0.f) + (b.s > 0.f ? b.s * expf(b.m - M) : 0.f);
+    a.m = M;
+    a.sz += b.sz;
+    if (b.bv > a.bv || (b.bv == a.bv && b.bi < a.bi)) {
+        a.bv = b.bv;
+        a.bi = b.bi;
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(256) void lm_row_loss_kernel(const float* __restrict__ z, long long ldl, int V, const long long* __restrict__ tgt,
+                                                          float c, float sm, float* __restrict__ row_kl, int* __restrict__ row_ok) {
+    __shared__ RowStat s_w[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* zr = z + (long long)blockIdx.x * ldl;
+    RowStat st{-INFINITY, 0.f, 0.f, -INFINITY, V};
+    int j = tid;
+    for (; j + 768 < V; j += 1024) {  // four independent loads in flight per thread
+        const float v0 = zr[j], v1 = zr[j + 256], v2 = zr[j + 512], v3 = zr[j + 768];
+        const float vm = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+        const float M = fmaxf(st.m, vm);
+        st.s = st.s * expf(st.m - M) + (expf(v0 - M) + expf(v1 - M)) + (expf(v2 - M) + expf(v3 - M));
+        st.m = M;
+        st.sz += (v0 + v1) + (v2 + v3);
+        if (v0 > st.bv) { st.bv = v0; st.bi = j; }
+        if (v1 > st.bv) { st.bv = v1; st.bi = j + 256; }
+        if (v2 > st.bv) { st.bv = v2; st.bi = j + 512; }
+        if (v3 > st.bv) { st.bv = v3; st.bi = j + 768; }
+    }
+    for (; j < V; j += 256) {
+        const float v = zr[j];
+        const float M = fmaxf(st.m, v);
+        st.s = st.s * expf(st.m - M) + expf(v - M);
+        st.m = M;
+        st.sz += v;
+        if (v > st.bv) { st.bv = v; st.bi = j; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        RowStat p;
+        p.m = __shfl_xor(st.m, o, 64);
+        p.s = __shfl_xor(st.s, o, 64);
+        p.sz = __shfl_xor(st.sz, o, 64);
+        p.bv = __shfl_xor(st.bv, o, 64);
+        p.bi = __shfl_xor(st.bi, o, 64);
+        st = (lane & o) ? row_merge(p, st) : row_merge(st, p);  // lower lanes' columns first: the same expression in every lane pair
+    }
+    if (lane == 0) s_w[wave] = st;
+    __syncthreads();
+    if (tid == 0) {
+        RowStat a = s_w[0];
+        for (int w = 1; w < 4; ++w) a = row_merge(a, s_w[w]);
+        const long long y = tgt[blockIdx.x];
+        const double lse = (double)a.m + log((double)a.s);
+        const double zy = zr[y], Vm1 = (double)(V - 1), cd = c, sd = sm;
+        double kl = (cd > 0.0 ? cd * log(cd) : 0.0) - cd * (zy - lse);
+        if (sd > 0.0) kl += Vm1 * sd * log(sd) - sd * ((double)a.sz - zy - Vm1 * lse);
+        row_kl[blockIdx.x] = (float)kl;
+        row_ok[blockIdx.x] = a.bi == (int)y;
+    }
+}
+
+int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, const long long* tgt, float c, float sm, float* row_kl,
+                       int* row_ok, hipStream_t s) {
+    if (rows <= 0) return QA_OK;
+    hipLaunchKernelGGL(lm_row_loss_kernel, dim3((unsigned)rows), dim3(256), 0, s, z, ldl, V, tgt, c, sm, row_kl, row_ok);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// Per sequence (one workgroup each): seq_sum[b] = sum of its Lt row KLs in double, loss_seq[b] = seq_sum[b] / Lt, correct_seq[b] = its
+// correct rows; thread i owns rows i, i + 256, ..., merged by a fixed LDS tree.
+__global__ __launch_bounds__(256) void lm_seq_reduce_kernel(const float* __restrict__ row_kl, const int* __restrict__ row_ok, int Lt,
+                                                            double* __restrict__ seq_sum, float* __restrict__ loss_seq,
+                                                            long long* __restrict__ correct_seq) {
+    __shared__ double s_kl[256];
+    __shared__ long long s_ok[256];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    double kl = 0.0;
+    long long ok = 0;
+    for (int t = tid; t < Lt; t += 256) {
+        kl += (double)row_kl[(long long)b * Lt + t];
+        ok += row_ok[(long long)b * Lt + t];
+    }
+    s_kl[tid] = kl;
+    s_ok[tid] = ok;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) {
+            s_kl[tid] += s_kl[tid + h];
+            s_ok[tid] += s_ok[tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        seq_sum[b] = s_kl[0];
+        loss_seq[b] = (float)(s_kl[0] / Lt);
+        correct_seq[b] = s_ok[0];
+    }
+}
+
+int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(lm_seq_reduce_kernel, dim3((unsigned)B), dim3(256), 0, s, row_kl, row_ok, Lt, seq_sum, loss_seq, correct_seq);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// The batch scalars (F.kl_div 'batchmean' over B * Lt rows, accuracy over the same rows): sequences in index order, one thread.
+__global__ void lm_batch_reduce_kernel(const double* __restrict__ seq_sum, const long long* __restrict__ correct_seq, int B, int Lt,
+                                       float* __restrict__ loss, float* __restrict__ acc) {
+    double kl = 0.0;
+    long long ok = 0;
+    for (int b = 0; b < B; ++b) {
+        kl += seq_sum[b];
+        ok += correct_seq[b];
+    }
+    const double n = (double)B * Lt;
+    *loss = (float)(kl / n);
+    *acc = (float)((double)ok / n);
+}
+
+int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s) {
+    hipLaunchKernelGGL(lm_batch_reduce_kernel, dim3(1), dim3(1), 0, s, seq_sum, correct_seq, B, Lt, loss, acc);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

@@ -1,6 +1,7 @@
 """Python mirror of the reference's UniSE AR-LM interface, backed by libquarkaudio_hip.so.
 
     LLM_SFT.generate  <->  QuarkAudio-UniSE/model/llm/llm_sft.py:93-195   (greedy path: model/model.py:173)
+    LLM_SFT.forward   <->  QuarkAudio-UniSE/model/llm/llm_sft.py:37-90    (teacher-forced loss / accuracy: Model.validation_step)
 
 Weights come in the reference's key layout (the Lightning checkpoint's `dnn.*` entries, prefix optional).
 """
@@ -30,6 +31,8 @@ class LLM_SFT:
         s.feats_dim, s.num_tasks = feats_dim, num_tasks
         s.rope_theta, s.rms_eps = 10000.0, 1e-6  # LlamaConfig defaults (llm.py:63-72)
         self._spec = s
+        self.label_smoothing = float(cfg.get("label_smoothing", 0.1))  # llm.py:24 default, conf/config.yaml:147
+        self.vocab_size = 3 + cfg["global_size"] + cfg["semantic_size"]
         self.global_offset = 3
         self.semantic_offset = 3 + cfg["global_size"]
         self._lib = _lib.load_library()
@@ -93,6 +96,58 @@ class LLM_SFT:
                                                 temperature, top_k, top_p, gids.data_ptr(), sids.data_ptr(), stream))
         return gids, sids
 
+    def _score(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids):
+        """qa_lm_score: (loss_per_seq float [B], correct_per_seq int64 [B], loss, acc 0-dim float, Lt) on the device."""
+        if not self._handle.value:
+            raise _lib.QuarkAudioError(-3, "LLM_SFT has no weights: call load_state_dict first")
+        task = self.task_map[task_name]  # KeyError like the reference
+        B = int(mix_mel.size(0))  # llm_sft.py:63: the task row is repeated mix_mel.size(0) times
+        mix = mix_feats.to(device=self.device, dtype=torch.float32).contiguous()
+        if mix.dim() != 3 or mix.shape[0] != B:
+            raise _lib.QuarkAudioError(-1, f"mix_feats must be [B={B}, N, feats_dim], got {tuple(mix.shape)}")
+        enr, n_enr = None, 0
+        if enroll_mel is not None:  # llm_sft.py:72: only the None test reads enroll_mel
+            enr = enroll_feats.to(device=self.device, dtype=torch.float32).contiguous()
+            n_enr = enr.shape[1]
+        g = global_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()  # .long() (llm_sft.py:48-49)
+        sids = semantic_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()
+        G, T = g.shape[1], sids.shape[1]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        # nn.Embedding's range check of the shifted input ids (the targets are the same ids): one count, one host synchronisation
+        shifted = torch.cat([g.reshape(-1) + self.global_offset, sids.reshape(-1) + self.semantic_offset])
+        if shifted.numel():
+            bad = C.c_int64(0)
+            _lib.check(self._lib.qa_codes_check(shifted.data_ptr(), shifted.numel(), self.vocab_size, C.byref(bad), stream))
+            if bad.value:
+                raise IndexError(f"{bad.value} input ids out of range [0, {self.vocab_size}) after the offsets (global + {self.global_offset}, "
+                                 f"semantic + {self.semantic_offset})")
+        loss_seq = torch.empty(B, dtype=torch.float32, device=self.device)
+        correct = torch.empty(B, dtype=torch.int64, device=self.device)
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.qa_lm_score(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, mix.data_ptr(), mix.shape[1], B,
+                                         g.data_ptr(), G, sids.data_ptr(), T, self.label_smoothing, loss_seq.data_ptr(), correct.data_ptr(),
+                                         out.data_ptr(), out[1:].data_ptr(), stream))
+        return loss_seq, correct, out[0], out[1], G + T + 2
+
+    @torch.no_grad()
+    def forward(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids):
+        """llm_sft.py:37-90: teacher-forced (loss, acc), 0-dim float32 device tensors.  loss = F.kl_div(log_softmax(logits), true_dist,
+        'batchmean') over the B * (G + T + 2) target rows with label smoothing `label_smoothing` (llm.py:87-104); acc = the fraction of
+        rows whose first arg-max over the full vocabulary is the target.  global_ids [B, G] / semantic_ids [B, T], int32 or int64, offsets
+        subtracted (what BiCodecTokenizer.tokenize returns; any G).  Forward only: no graph, no gradient."""
+        _, _, loss, acc, _ = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
+        return loss, acc
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    @torch.no_grad()
+    def score(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids):
+        """forward per sequence: (loss [B], acc [B]) float32 - each sequence's mean label-smoothed KL and accuracy over its own G + T + 2
+        target rows (forward's scalars are their means).  A sequence's values do not depend on the batch it is scored in."""
+        loss_seq, correct, _, _, Lt = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
+        return loss_seq, correct.to(torch.float32) / Lt
+
     def enable_taps(self, on: bool = True):
         """Test hook: make generate record the slice logits of every decode step (qa_lm_enable_taps)."""
         if not self._handle.value:
@@ -102,7 +157,7 @@ class LLM_SFT:
 
     def tap(self, name: str) -> torch.Tensor:
         """Test hook: flat fp32 copy of a snapshot of the last generate: "logits.global" ([B, global_length + 1, global_size]) or
-        "logits.semantic" ([B, semantic_length, semantic_size])."""
+        "logits.semantic" ([B, semantic_length, semantic_size]); of the last forward / score: "logits.forced" ([B, G + T + 2, vocab])."""
         n = self._lib.qa_lm_tap(self._handle, name.encode(), None, 0, None)
         if n < 0:
             _lib.check(int(n))

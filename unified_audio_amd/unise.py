@@ -52,7 +52,7 @@ def mel_frames(n_samples: int) -> int:
 
 
 class _Frames:
-    """Stand-in for a mel tensor: LLM_SFT.generate only calls `.size(1)` on it."""
+    """Stand-in for a mel tensor: LLM_SFT.generate only calls `.size(1)` on it, LLM_SFT.forward only `.size(0)`."""
 
     def __init__(self, batch: int, frames: int):
         self._shape = (batch, frames, 80)
@@ -447,6 +447,27 @@ class Model:
         if src.dim() != 2 or src.size(0) != 1:
             raise ValueError(f"src must be [1, T]: the reference's test batches hold one file (data_module.py:340), got {tuple(src.shape)}")
         return mode, enroll, src, int(fs[0]), names[0]
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx: int = 0):
+        """model.py:134-160: score the checkpoint on one held-out batch `(mode, enroll, mix, speech, interf, fs, lengths, names)` (B >= 1).
+        The LM's targets are the BiCodec tokens of the interferer for 'rtse' and of the clean speech otherwise (tokenize needs the
+        tokenizer's encoder weights); the prompt is the SSL features of the mixture (and of the enrollment when there is one).  There is
+        no Lightning here, so the values are returned instead of logged: {'valid_loss', 'valid_acc'}, 0-dim float32 device tensors."""
+        mode, enroll, mix, speech, interf, fs, lengths, names = batch
+        global_tokens, semantic_tokens = self.tokenizer.tokenize(interf if mode == "rtse" else speech)  # (B, 1, G) int32, (B, T) int64
+        mix = mix.to(self.device, torch.float32)
+        # the LM reads only mix_mel.size(0) and whether enroll_mel is None (llm_sft.py:63,72): the frame-count stand-in replaces the mel
+        mix_mel = _Frames(mix.size(0), mel_frames(mix.size(-1)))
+        mix_feats = self.extract_semantic_features(mix)
+        enroll_mel = enroll_feats = None
+        if enroll is not None:
+            enroll = enroll.to(self.device, torch.float32)
+            enroll_mel = _Frames(enroll.size(0), mel_frames(enroll.size(-1)))
+            enroll_feats = self.extract_semantic_features(enroll)
+        loss, acc = self.dnn(task_name=mode, enroll_mel=enroll_mel, enroll_feats=enroll_feats, mix_mel=mix_mel, mix_feats=mix_feats,
+                             global_ids=global_tokens.squeeze(1), semantic_ids=semantic_tokens)
+        return {"valid_loss": loss, "valid_acc": acc}
 
     @torch.no_grad()
     def test_step(self, batch, batch_idx: int = 0):
