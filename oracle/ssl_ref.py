@@ -100,6 +100,18 @@ def synth_state_dict(seed: int, spec: SSLSpec, kind: str = "hubert") -> Dict[str
     return sd
 
 
+def relative_position_bucket(rel: torch.Tensor, num_buckets: int, max_distance: int) -> torch.Tensor:
+    """WavLMAttention._relative_positions_bucket (transformers/models/wavlm/modeling_wavlm.py): rel = memory_position -
+    context_position (any shape, integer) -> bucket index in [0, num_buckets).  Saturates at |rel| >= max_distance."""
+    nb = num_buckets // 2
+    bucket = (rel > 0).long() * nb
+    a = rel.abs()
+    max_exact = nb // 2
+    large = torch.log(a.float() / max_exact) / math.log(max_distance / max_exact) * (nb - max_exact)
+    large = torch.min((max_exact + large).long(), torch.full_like(a, nb - 1))
+    return bucket + torch.where(a < max_exact, a, large)
+
+
 def _pos_conv_weight(sd: Dict[str, torch.Tensor]) -> torch.Tensor:
     """weight_norm(dim=2) of HubertPositionalConvEmbedding: w = v * g / ||v|| with the norm over (out, in) per kernel tap."""
     pre = "encoder.pos_conv_embed.conv."
@@ -151,13 +163,7 @@ def hidden_states(sd: Dict[str, torch.Tensor], wavs: torch.Tensor, spec: SSLSpec
         # owns rel_attn_embed, every layer re-uses its bias
         n = x.shape[1]
         rel = torch.arange(n)[None, :] - torch.arange(n)[:, None]  # memory_position - context_position
-        nb = spec.num_buckets // 2
-        bucket = (rel > 0).long() * nb
-        a = rel.abs()
-        max_exact = nb // 2
-        large = torch.log(a.float() / max_exact) / math.log(spec.max_bucket_distance / max_exact) * (nb - max_exact)
-        large = torch.min((max_exact + large).long(), torch.full_like(a, nb - 1))
-        bucket = bucket + torch.where(a < max_exact, a, large)
+        bucket = relative_position_bucket(rel, spec.num_buckets, spec.max_bucket_distance)
         position_bias = F.embedding(bucket, sd["encoder.layers.0.attention.rel_attn_embed.weight"]).permute(2, 0, 1)  # [H, N, N]
 
     def attention(h, pre):

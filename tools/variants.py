@@ -12,7 +12,8 @@ from unified_audio_amd import build as B  # noqa: E402
 
 
 def _transform(path):
-    """--transform FILE.py[:function]: a module with transform(source) -> source, applied to conv_gemm.hip (the product file stays untouched)."""
+    """--transform FILE.py[:function]: a module with transform(source) -> source, applied to every variant source - conv_gemm.hip and
+    those QA_VARIANT_SOURCES names (the product files stay untouched); a transform returns a source it does not target unchanged."""
     path, _, fn = path.partition(":")
     fn = fn or "transform"
     import importlib.util
@@ -39,7 +40,7 @@ def main():
             if src == "conv_gemm.hip" or src in os.environ.get("QA_VARIANT_SOURCES", "").split(","):
                 obj = os.path.join(out, src.rsplit(".", 1)[0] + ".o")
                 path = os.path.join(B.CSRC, src)
-                if transform and src == "conv_gemm.hip":
+                if transform:
                     path = os.path.join(out, src)
                     with open(path, "w") as f:
                         f.write(transform(open(os.path.join(B.CSRC, src)).read()))

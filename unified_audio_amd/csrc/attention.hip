@@ -166,6 +166,9 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
         __syncthreads();
         if (kt + 1 < n_tiles) fetch(kt + 1);
         if (dbg & 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the extra barrier stands before the tile skip: every wave of the workgroup reaches it on every tile (after the PV phase, a wave
+        // that skipped the tile missed it, so the workgroup's barriers paired up across tiles and LDS tiles were overwritten under readers)
+        if (dbg & 2) __syncthreads();
         QA_ATT_TICK(0)
         // wave-uniform skips: the whole tile is masked for this wave, or the wave owns no query at all (the last query block of a
         // sequence that is not a multiple of 128: at N = 283 three of the four waves of block 3 would multiply clamped rows)
@@ -239,7 +242,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
 #pragma unroll
             for (int t = 0; t < DT; ++t) o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * t], s[st], o[t], 0, 0, 0);
         }
-        if (dbg & 2) __syncthreads();
 #ifdef QA_ATT_TIMING
         ++n_done;
 #endif
@@ -311,4 +313,14 @@ extern "C" int qa_debug_attention(const float* q, long long ldq, const float* k,
                                   int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale, int causal, void* stream) {
     return qa::launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, causal,
                                 static_cast<hipStream_t>(stream));
+}
+
+// test hook (not part of the public header): the same, with every launch_attention parameter - the WavLM gated relative position
+// bias (gate [B, H, n_q], relbias [H, 2R + 1]), the causal window `context` and the ring mode (q_pos0, ring_end)
+extern "C" int qa_debug_attention_ex(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
+                                     long long ldo, int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale,
+                                     int causal, const float* gate, const float* relbias, int R, int context, int q_pos0, int ring_end,
+                                     void* stream) {
+    return qa::launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, causal,
+                                static_cast<hipStream_t>(stream), gate, relbias, R, context, q_pos0, ring_end);
 }
