@@ -5,7 +5,12 @@ A "step" is one pass of the hot path - Codec.encode followed by Codec.decode - o
 is already resident in HBM (wav [B, T] and SSL features [B, N50, 768] as the tokenizer hands them over), on every rank.
 `value` = audio-seconds processed by all ranks / max-over-ranks wall time of K steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--seconds 10] [--dump-outputs DIR]
+A plain run does only what that figure needs: set up, W warm-up steps, the K timed steps (with the live per-launch profile that
+`roofline` quotes), the --dump-outputs files, one JSON line.  `--full` adds every secondary measurement after the timed steps: the
+isolated and byte-bound rooflines, the PCIe-inclusive step, the UniSE LM, SSL, BiCodec and pipeline figures, the other codec
+versions and the RVQ search, the CPU baselines and, at N > 1, `ranks_seen`, the exchange step and the configs[3] / configs[4] legs.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--seconds 10] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -40,9 +45,12 @@ def parse():
     ap.add_argument("--seconds", type=float, default=10.0, help="clip length (BASELINE configs[1]: 10 s)")
     ap.add_argument("--model", choices=["1.5", "1.0", "2.0"], default="1.5",
                     help="H-Codec version (BASELINE configs[1] is 1.5; 2.0 = configs[4]'s per-GPU share: use --batch 16 --seconds 30)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, run every secondary measurement as well (isolated / HBM "
+                                                          "rooflines, PCIe, LM, SSL, BiCodec, other configurations, CPU baselines; N > 1: "
+                                                          "ranks_seen, exchange, configs[3] / configs[4] legs); the --no-* options below trim it")
+    ap.add_argument("--lean", action="store_true", help="only warm-up + timed region: what a run without --full does (older command lines)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-clips", type=int, default=2, help="clips in the bounded CPU-baseline sample")
-    ap.add_argument("--lean", action="store_true", help="profiling runs: only warm-up + timed region (no isolated / PCIe / LM / CPU passes)")
     ap.add_argument("--no-ssl", action="store_true", help="skip the secondary SSL front-end measurement")
     ap.add_argument("--no-lm", action="store_true", help="skip the secondary UniSE AR-LM tokens/sec measurement")
     ap.add_argument("--lm-batch", type=int, default=16, help="UniSE segments per GPU (BASELINE configs[2]: batch=16)")
@@ -61,6 +69,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full and args.lean:
+        ap.error("--full and --lean exclude each other")
     return args
 
 
@@ -717,9 +727,11 @@ def main():
     # N > 1: (a) which devices the ranks really sit on (all-gather of their UUIDs: "did RCCL see N distinct GPUs" is answerable from
     # the line), (b) the exchange step north_star names - scatter of the clips from rank 0, gather of codes + waveforms back over
     # RCCL (unified_audio_amd.dist.run_sharded, the code path the gloo tests exercise) - timed NEXT TO the hot path, never inside
-    # `value`: in the timed region above every rank draws its own shard, like the reference's rank-strided file lists
+    # `value`: in the timed region above every rank draws its own shard, like the reference's rank-strided file lists.
+    # Everything from here to the line is a secondary measurement: --full only.
+    full = args.full
     ranks_seen, exchange = None, None
-    if dist is not None:
+    if dist is not None and full:
         ranks_seen = collect_ranks_seen(dist, rank, local_rank, world, dev)
         try:
             K = spec.codebook_size
@@ -746,55 +758,56 @@ def main():
         except Exception as e:  # noqa: BLE001
             exchange = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
-    # the same kernels with the library's internal stream concurrency switched off (every launch alone on the device):
-    # what a kernel achieves by itself, as opposed to while it shares the CUs with the other stream's kernels
     iso = (C.c_double * NPROF)()
-    n_hbm = lib.qa_profile_hbm_kinds()
-    hbm = (C.c_double * (3 * n_hbm))()
-    _lib.check(lib.qa_set_serial(1))
-    _lib.check(lib.qa_profile_begin_ex(3))  # + the byte-bound kernels, each with its algorithmic bytes (qa_profile_end_hbm)
-    for _ in range(0 if args.lean else 2):
-        step()
-    torch.cuda.synchronize(dev)
-    _lib.check(lib.qa_profile_end_hbm(hbm, 3 * n_hbm))
-    _lib.check(lib.qa_profile_end(iso, NPROF))
-    _lib.check(lib.qa_set_serial(0))
-    hbm_rows = []
-    for k in range(n_hbm):
-        by, ms, n = hbm[3 * k], hbm[3 * k + 1], hbm[3 * k + 2]
-        if n:
-            row = {"kernel": lib.qa_profile_hbm_name(k).decode(), "launches_per_step": n / 2, "avg_us": 1e3 * ms / n,
-                   "algorithmic_bytes_per_launch": by / n, "achieved_GBps": by / (ms * 1e-3) / 1e9, "frac": by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                   "ms_per_step": ms / 2}
-            if row["kernel"].startswith("seanet_block") and args.model != "2.0":
-                # the one kernel north_star calls HBM-bound is not, in fp32: conv0 (k7, 1 -> 32) + k3 32 -> 16 + 1x1 16 -> 32 + the 32 -> 32 shortcut
-                # are 3 296 MACs per sample for 132 bytes moved: 50 FLOP/B against a ridge of 157.3 / 8 = 19.7 FLOP/B, so its floor is the
-                # matrix pipe (0.21 ms per launch), not HBM (0.085 ms) - price it against BOTH
-                flop = 2.0 * 3296.0 * B * T
-                row.update({"flop_per_launch": flop, "tflops": flop / (1e-3 * ms / n) / 1e12, "frac_of_f32_mfma_peak": flop / (1e-3 * ms / n) / 1e12 / MFMA_F32_PEAK_TFLOPS,
-                            "arithmetic_intensity_flop_per_byte": flop / (by / n), "ridge_flop_per_byte": MFMA_F32_PEAK_TFLOPS * 1e3 / HBM_PEAK_GBPS,
-                            "bound": "mfma (arithmetic intensity above the fp32 ridge: even at the matrix peak this launch would move its bytes at "
-                                     "0.40 of the HBM peak)"})
-            hbm_rows.append(row)
+    hbm_rows, pcie_elapsed = [], None
+    if full:
+        # the same kernels with the library's internal stream concurrency switched off (every launch alone on the device):
+        # what a kernel achieves by itself, as opposed to while it shares the CUs with the other stream's kernels
+        n_hbm = lib.qa_profile_hbm_kinds()
+        hbm = (C.c_double * (3 * n_hbm))()
+        _lib.check(lib.qa_set_serial(1))
+        _lib.check(lib.qa_profile_begin_ex(3))  # + the byte-bound kernels, each with its algorithmic bytes (qa_profile_end_hbm)
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize(dev)
+        _lib.check(lib.qa_profile_end_hbm(hbm, 3 * n_hbm))
+        _lib.check(lib.qa_profile_end(iso, NPROF))
+        _lib.check(lib.qa_set_serial(0))
+        for k in range(n_hbm):
+            by, ms, n = hbm[3 * k], hbm[3 * k + 1], hbm[3 * k + 2]
+            if n:
+                row = {"kernel": lib.qa_profile_hbm_name(k).decode(), "launches_per_step": n / 2, "avg_us": 1e3 * ms / n,
+                       "algorithmic_bytes_per_launch": by / n, "achieved_GBps": by / (ms * 1e-3) / 1e9, "frac": by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                       "ms_per_step": ms / 2}
+                if row["kernel"].startswith("seanet_block") and args.model != "2.0":
+                    # the one kernel north_star calls HBM-bound is not, in fp32: conv0 (k7, 1 -> 32) + k3 32 -> 16 + 1x1 16 -> 32 + the 32 -> 32 shortcut
+                    # are 3 296 MACs per sample for 132 bytes moved: 50 FLOP/B against a ridge of 157.3 / 8 = 19.7 FLOP/B, so its floor is the
+                    # matrix pipe (0.21 ms per launch), not HBM (0.085 ms) - price it against BOTH
+                    flop = 2.0 * 3296.0 * B * T
+                    row.update({"flop_per_launch": flop, "tflops": flop / (1e-3 * ms / n) / 1e12, "frac_of_f32_mfma_peak": flop / (1e-3 * ms / n) / 1e12 / MFMA_F32_PEAK_TFLOPS,
+                                "arithmetic_intensity_flop_per_byte": flop / (by / n), "ridge_flop_per_byte": MFMA_F32_PEAK_TFLOPS * 1e3 / HBM_PEAK_GBPS,
+                                "bound": "mfma (arithmetic intensity above the fp32 ridge: even at the matrix peak this launch would move its bytes at "
+                                         "0.40 of the HBM peak)"})
+                hbm_rows.append(row)
 
-    # secondary: the same step with host (pageable) tensors in and out, as HCodecTokenizer's __main__ moves them
-    # (audio_tokenizer.py:79,84: wav.to(device) ... wav_rec.cpu()); never `value`
-    wav_h, feats_h = wav.cpu(), feats.cpu()
-    torch.cuda.synchronize(dev)
-    t1 = time.perf_counter()
-    for _ in range(1 if args.lean else 2):
-        w_d, f_d = wav_h.to(dev), feats_h.to(dev)
-        if adaptive:
-            codes = codec.encode(w_d.unsqueeze(1), f_d.transpose(1, 2))
-            rec_h = codec.decode(**{k: v.cpu().to(dev) for k, v in codes.items()}).cpu()
-        else:
-            a_, s_ = codec.encode(w_d.unsqueeze(1), f_d.transpose(1, 2))
-            rec_h = codec.decode(a_.cpu().to(dev), s_.cpu().to(dev)).cpu()
-    pcie_elapsed = (time.perf_counter() - t1) / (1 if args.lean else 2)
-    del rec_h
+        # secondary: the same step with host (pageable) tensors in and out, as HCodecTokenizer's __main__ moves them
+        # (audio_tokenizer.py:79,84: wav.to(device) ... wav_rec.cpu()); never `value`
+        wav_h, feats_h = wav.cpu(), feats.cpu()
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        for _ in range(2):
+            w_d, f_d = wav_h.to(dev), feats_h.to(dev)
+            if adaptive:
+                codes = codec.encode(w_d.unsqueeze(1), f_d.transpose(1, 2))
+                rec_h = codec.decode(**{k: v.cpu().to(dev) for k, v in codes.items()}).cpu()
+            else:
+                a_, s_ = codec.encode(w_d.unsqueeze(1), f_d.transpose(1, 2))
+                rec_h = codec.decode(a_.cpu().to(dev), s_.cpu().to(dev)).cpu()
+        pcie_elapsed = (time.perf_counter() - t1) / 2
+        del rec_h
 
     lm_line = None
-    if not args.no_lm and not args.lean:
+    if full and not args.no_lm:
         del out
         log("UniSE LM generate ...")
         lm_line = lm_bench(dev, rank, world, dist, args.lm_batch)
@@ -803,7 +816,7 @@ def main():
     # per GPU; the enrollment travels with its segment, model.py:209-210) and configs[4] (H-Codec 2.0, 128 x 30 s over 8 GPUs = 16 per
     # GPU) - every rank its own share, max over ranks, each with its own exchange block
     multi = {}
-    if dist is not None and not args.lean and not args.no_extras and not args.no_multi_configs:
+    if dist is not None and full and not args.no_extras and not args.no_multi_configs:
         if not args.no_lm:
             try:
                 log("configs[3]: TSE share, 8 segments per GPU ...")
@@ -853,7 +866,7 @@ def main():
             multi["configs4_hcodec20"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
     extras = {}
-    if rank == 0 and world == 1 and not args.lean and not args.no_extras and args.model == "1.5":
+    if rank == 0 and world == 1 and full and not args.no_extras and args.model == "1.5":
         try:
             # (1) the headline at a second grouping point (G ~ N25/8 ... N25/2): the per-call threshold of
             #     Codec.encode (codec_adaptive.py:150-158) raised until about half the frames open a group
@@ -878,7 +891,7 @@ def main():
                                                                 "sequences 250 + G, RVQ over 32 x G vectors)"}
         except Exception as e:  # noqa: BLE001
             extras["hcodec15_second_grouping_point"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-    if rank == 0 and world == 1 and not args.lean and not args.no_extras and not args.no_lm:
+    if rank == 0 and world == 1 and full and not args.no_extras and not args.no_lm:
         try:
             log("UniSE LM TSE share of configs[3] (8 segments per GPU, prompt 503) ...")
             extras["unise_lm_tse_b8"] = lm_bench(dev, rank, world, None, 8, reps=1, task="tse", n_enroll=250)
@@ -907,7 +920,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extras["unise_lm_tse_b64"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
-    if rank == 0 and world == 1 and not args.lean and not args.no_extras and args.model == "1.5":
+    if rank == 0 and world == 1 and full and not args.no_extras and args.model == "1.5":
         try:
             # (3) H-Codec 2.0, the per-GPU share of BASELINE configs[4]: 16 clips x 30 s @ 48 kHz (1.17 B parameters)
             log("H-Codec 2.0 16 x 30 s (per-GPU share of configs[4]) ...")
@@ -935,7 +948,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extras["hcodec20_16x30s"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
-    if rank == 0 and world == 1 and not args.lean and not args.no_extras and args.model == "1.5":
+    if rank == 0 and world == 1 and full and not args.no_extras and args.model == "1.5":
         try:
             # (4) H-Codec 1.0 at the metric's own batch (32 x 10 s @16 kHz): the non-adaptive SEANet / ConvNeXt codec of configs[0], at size
             log("H-Codec 1.0 32 x 10 s ...")
@@ -960,7 +973,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extras["hcodec10_32x10s"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
-    if rank == 0 and world == 1 and not args.lean and not args.no_extras:
+    if rank == 0 and world == 1 and full and not args.no_extras:
         try:
             # (5) the RVQ search alone at configs[4]'s shape: 16 stages x 1024 x 512; 6 000 vectors = the per-GPU share
             #     (16 clips x 375 frames), 48 000 = the whole configuration's 128 clips on one GPU
@@ -971,7 +984,7 @@ def main():
             extras["rvq_search_6000x16"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
 
     ssl_line = None
-    if world == 1 and not args.lean and not args.no_ssl and args.model != "2.0":
+    if world == 1 and full and not args.no_ssl and args.model != "2.0":
         log("SSL front-end ...")
         try:
             ssl_line = ssl_bench(dev, args.model, B, args.seconds)
@@ -1067,8 +1080,9 @@ def main():
         line["knobs"] = {"non_default": {k: v[0] for k, v in kn.items() if v[0] != v[1]},
                          "recurrence": {k: kn[k][0] for k in ("QA_LSTM_XCD", "QA_LSTM_PERSISTENT", "QA_LSTM_TEAM") if k in kn},
                          "note": "QA_LSTM_XCD = 1: the d = 512 / 768 LSTMs run as the XCD-local in-launch recurrence (DESIGN.md section 3)"}
-        line["pcie_inclusive"] = {"value": B * T / SR / pcie_elapsed, "unit": "audio-seconds/sec", "ms_per_step": 1e3 * pcie_elapsed,
-                                  "note": "rank-0 only: wav+features H2D from pageable memory, codes D2H+H2D, waveform D2H included"}
+        if pcie_elapsed is not None:
+            line["pcie_inclusive"] = {"value": B * T / SR / pcie_elapsed, "unit": "audio-seconds/sec", "ms_per_step": 1e3 * pcie_elapsed,
+                                      "note": "rank-0 only: wav+features H2D from pageable memory, codes D2H+H2D, waveform D2H included"}
         if lm_line is not None:
             if world == 1 and not args.no_cpu_baseline and not args.no_extras:
                 log("LM cpu baseline ...")
@@ -1083,7 +1097,7 @@ def main():
                                              "tokens_per_sec": args.lm_batch * 283 / tot,
                                              "note": "Model.test_step 'se' on 16 x 5 s segments: WavLM front-end + LLM_SFT.generate + BiCodec.detokenize "
                                                      "(the codec decode the reference's test.py uses, model.py:193), stages timed back to back"}
-            if world == 1 and not args.no_extras and not args.lean:
+            if world == 1 and not args.no_extras:
                 try:
                     log("UniSE end to end, pipelined over 6 batches of 16 segments ...")
                     lm_line["end_to_end_pipelined_b16"] = unise_pipeline_bench(dev, 6, args.lm_batch)
@@ -1102,7 +1116,7 @@ def main():
             line["ssl_frontend"] = ssl_line
         if args.model == "2.0":
             line["metric"] = "audio-seconds/sec H-Codec 2.0 encode+decode @48kHz (BASELINE configs[4], per-GPU share)"
-        if not args.no_cpu_baseline and not args.lean and args.model != "2.0":
+        if full and not args.no_cpu_baseline and args.model != "2.0":
             # rank 0 only, AFTER every timed region (at N > 1 the other ranks have finished their GPU work and are leaving)
             log("cpu baseline ...")
             line["cpu_baseline"] = cpu_baseline(args.cpu_clips, args.seconds, model=args.model)

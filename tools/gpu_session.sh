@@ -4,7 +4,7 @@
 # Every step writes into gpurun_out/TAG/ (merged back by gpurun); summaries worth keeping are copied to profiles/ by hand.
 # Steps:
 #   tests[:EXPR]      pytest -m gpu (optionally -k EXPR, or a file path when EXPR contains ".py")
-#   bench[:ARGS]      python bench.py ARGS (default: the driver's default command) -> bench.json
+#   bench[:ARGS]      python bench.py --full ARGS (the headline and every secondary measurement) -> bench.json
 #   lm[:B[:REPS]]     tools/lm_bench.py (decode-step time of the UniSE LM, knobs from the environment)
 #   ab:KNOB=a,b[,c]:CMD   run CMD once per value of an environment knob, logs side by side (CMD: lm | bench-lean | hc10 | hc20)
 #   trace:NAME:CMD    rocprofv3 --kernel-trace --stats of CMD (lm | bench-lean | bench-serial | hc10 | hc20) -> NAME_kernel_stats.md
@@ -54,7 +54,7 @@ for step in "$@"; do
         *) ( time timeout 1500 python -m pytest tests -q -m gpu -k "$rest" 2>&1 | tail -25 ) 2>&1 | tee -a $O/tests.log ;;
       esac ;;
     bench)
-      ( time timeout 900 python bench.py $rest > $O/bench.json 2> $O/bench.err ) 2>&1 | tail -3 | tee -a $O/session.log
+      ( time timeout 900 python bench.py --full $rest > $O/bench.json 2> $O/bench.err ) 2>&1 | tail -3 | tee -a $O/session.log
       python - <<PY 2>&1 | tee -a $O/session.log
 import json
 d = json.load(open("$O/bench.json")); lm = d.get("unise_lm") or {}
