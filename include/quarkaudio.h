@@ -152,6 +152,38 @@ int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64
 int qa_hcodec_decode_adaptive(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B,
                               int64_t G, int64_t frames, float* wav_out, void* stream);
 
+/* Semantic decoder of H-Codec (semantic_module.Decoder, QuarkAudio-HCodec/HCodec-1.0/vq/semantic_module.py:205-300): it rebuilds
+ * the SSL features from the summed semantic code vectors.  conv1 (k3, no bias) code_dim -> channels; block i: a Conv1d k3 (stride 1)
+ * or a ConvTranspose1d k = 2 s (stride s > 1, even) from the previous width to widths[i], then two residual units; conv2 (k3, no bias)
+ * widths[n_blocks - 1] -> output_channels.  Every width a multiple of 32. */
+typedef struct qa_semantic_decoder_spec {
+    int32_t code_dim, channels, n_blocks;
+    int32_t strides[4];
+    int32_t widths[4];
+    int32_t output_channels;
+} qa_semantic_decoder_spec;
+
+/* Attach the semantic decoder to a codec handle (weights: `semantic_decoder.*` of the reference's state_dict, host memory).  It is
+ * only read by qa_hcodec_forward*; encode / decode do not change.  On failure (first missing or mis-shaped key in the error message)
+ * the handle keeps what it had. */
+int qa_hcodec_load_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec* spec, const qa_tensor* tensors, int64_t n_tensors);
+/* 1 if a semantic decoder is attached, 0 if not, negative on a null handle */
+int qa_hcodec_has_semantic_decoder(const qa_hcodec* h);
+
+/* Codec.forward in eval mode (HCodec-1.0/vq/codec.py:138-162, HCodec-2.0/vq/codec.py:54-72): encode, RVQ and decode on the device
+ * (the codes never leave it), and the semantic decoder on the looked-up semantic embedding.  wav / feat as qa_hcodec_encode;
+ * recon: fp32 [B, N25 * upsample * hop] (= decode(encode(wav, feat))); pred_feat: fp32 [B, output_channels, N25 * prod(strides)]. */
+int qa_hcodec_forward(qa_hcodec* h, const float* wav, int64_t B, int64_t T,
+                      const float* feat, int64_t feat_stride_b, int64_t feat_stride_c, int64_t feat_stride_t,
+                      int64_t n_feat_frames, float* recon, float* pred_feat, void* stream);
+/* H-Codec 1.5 (HCodec-1.5/vq/codec_adaptive.py:100-148) at the model's threshold (spec.threshold).  recon: fp32 [B, 2 * N25 * hop];
+ * pred_feat as above, from the semantic embedding de-aggregated back to N25 frames; token_lengths: int64 [B, G] written compactly
+ * into a buffer of capacity B * N25; G returned through *n_groups (one host synchronisation, as encode). */
+int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T,
+                               const float* feat, int64_t feat_stride_b, int64_t feat_stride_c, int64_t feat_stride_t,
+                               int64_t n_feat_frames, float* recon, float* pred_feat, int64_t* token_lengths, int64_t* n_groups,
+                               void* stream);
+
 /* Test hook: when enabled, encode/decode snapshot their named intermediates (costs copies; off by default). */
 int qa_hcodec_enable_taps(qa_hcodec* h, int on);
 /* Test hook: copy the named snapshot of the LAST encode/decode (still in the handle's workspace) into

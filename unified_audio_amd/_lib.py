@@ -39,6 +39,11 @@ class qa_hcodec_spec(C.Structure):
     ]
 
 
+class qa_semantic_decoder_spec(C.Structure):
+    _fields_ = [("code_dim", C.c_int32), ("channels", C.c_int32), ("n_blocks", C.c_int32), ("strides", C.c_int32 * 4),
+                ("widths", C.c_int32 * 4), ("output_channels", C.c_int32)]
+
+
 class qa_conv_args(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("gamma", C.c_void_p), ("residual", C.c_void_p),
@@ -115,6 +120,13 @@ SYMBOLS = {
     "qa_hcodec_adaptive_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "qa_hcodec_decode_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                             C.c_void_p]),
+    "qa_hcodec_load_semantic_decoder": (C.c_int, [C.c_void_p, C.POINTER(qa_semantic_decoder_spec), C.POINTER(qa_tensor), C.c_int64]),
+    "qa_hcodec_has_semantic_decoder": (C.c_int, [C.c_void_p]),
+    "qa_hcodec_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_hcodec_forward_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                             C.c_void_p]),
     "qa_hcodec_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "qa_hcodec_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "qa_rvq_search": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

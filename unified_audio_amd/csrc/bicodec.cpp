@@ -294,28 +294,19 @@ int build(qa_bicodec* h, const HostTable& tab) {
         const int cin = ch, cout = ch / 2, k = sp.kernel_sizes[i], s = sp.rates[i], pad = (k - s) / 2;
         g.stride = s; g.c_in = cin; g.c_out = cout;
         L.vec(&g.a_in, p + ".0.alpha", cin);
-        // ConvTranspose1d weight [C_in][C_out][k] (weight_norm over dim 0 = C_in).  y[q s + phi] = sum_m x[q + c0 - m] W[:, :, j0 + m s]
-        // with j0 = (phi + pad) mod s, c0 = (phi + pad) div s: a stride-1 convolution with taps jj = 0 .. n-1 <-> m = n-1-jj,
-        // pad_left = n - 1 - c0 (n = number of taps of the phase), right padding c0.
+        // ConvTranspose1d weight [C_in][C_out][k] (weight_norm over dim 0 = C_in) as s polyphase stride-1 filters (host_util.h)
         std::vector<float> w;
         const bool have = L.weight(p + ".1", cin, (int64_t)cout * k, &w);
         g.phase.resize(s);
         g.pad_left.resize(s);
         for (int phi = 0; phi < s; ++phi) {
-            const int j0 = (phi + pad) % s, c0 = (phi + pad) / s, n = (k - j0 + s - 1) / s;
-            QA_REQUIRE(n >= 1 && n - 1 - c0 >= 0, "bicodec: ConvTranspose1d phase %d of k=%d s=%d has no causal tap layout", phi, k, s);
-            std::vector<float> r((size_t)cout * n * cin, 0.f);
-            if (have)
-                for (int o = 0; o < cout; ++o)
-                    for (int jj = 0; jj < n; ++jj) {
-                        const int j = j0 + (n - 1 - jj) * s;
-                        for (int c = 0; c < cin; ++c) r[((size_t)o * n + jj) * cin + c] = w[((size_t)c * cout + o) * k + j];
-                    }
+            PolyphaseFilter pf;
+            QA_TRY(polyphase_filter(have ? w.data() : nullptr, cin, cout, k, s, pad, phi, &pf));
             ConvW& cw = g.phase[phi];
-            cw.N = cout; cw.C_in = cin; cw.ksize = n;
-            L.raw(&cw.w, r);
+            cw.N = cout; cw.C_in = cin; cw.ksize = pf.ntaps;
+            L.raw(&cw.w, pf.filter);
             L.vec(&cw.b, p + ".1.bias", cout);
-            g.pad_left[phi] = n - 1 - c0;
+            g.pad_left[phi] = pf.pad_left;
         }
         const int dil[3] = {1, 3, 9};
         for (int j = 0; j < 3; ++j) {

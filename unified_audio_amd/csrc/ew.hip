@@ -678,6 +678,22 @@ int launch_adaptive_frames(const long long* codes, int B, int Q, int G, int K, i
     return QA_OK;
 }
 
+// token_lengths [B, G] = floor(code / K) + 1 of quantizer 0 of length-injected codes [B, Q, G] (codec_adaptive.py:145: the alignment
+// matrices' row sums, which is what encode injects)
+__global__ void token_lengths_kernel(const long long* __restrict__ codes, long long* __restrict__ out, int B, int Q, int G, int K) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * G) return;
+    const int g = (int)(gid % G), b = (int)(gid / G);
+    out[gid] = floordiv_ll(codes[((long long)b * Q) * G + g], K) + 1;
+}
+int launch_token_lengths(const long long* codes, long long* out, int B, int Q, int G, int K, hipStream_t s) {
+    const long long total = (long long)B * G;
+    if (total == 0) return QA_OK;
+    hipLaunchKernelGGL(token_lengths_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, codes, out, B, Q, G, K);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
 // _deaggregate_features_from_token_lengths on index tensors (modeling_flexicodec_new.py:1007-1041, codec_adaptive.py:184-189):
 // codes [B, Q, G] (length-injected) -> plain indices [B*T, Q], each group repeated len times, rows past an item's total = 0.
 // Lengths come from `len_codes` (the reference ends up using the semantic stream's lengths for both streams).

@@ -109,6 +109,22 @@ struct qa_hcodec {
     int* host_sync = nullptr;  // pinned host scalar for the data-dependent group / frame counts
     hipStream_t side = nullptr;  // second stream: the two aggregator stacks are independent and run concurrently
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // semantic decoder (semantic_module.py:205-300): attached by qa_hcodec_load_semantic_decoder, read by forward only
+    struct SemDecBlock {
+        int stride = 1, c_out = 0;
+        ConvW conv;                // stride 1: Conv1d k3 "same"
+        std::vector<ConvW> phase;  // stride s > 1: the ConvTranspose1d as s stride-1 filters, phase phi writes rows q s + phi
+        std::vector<int> pad_left;
+        ConvW u1[2], u2[2];        // ResidualUnit: x + conv2(ELU(conv1(ELU(x))))
+    };
+    struct SemDec {
+        qa_semantic_decoder_spec spec{};
+        WeightStore store;
+        ConvW conv1, conv2;
+        std::vector<SemDecBlock> blocks;
+        ~SemDec() { store.release(); }
+    };
+    std::unique_ptr<SemDec> sdec;
     // workspace
     char* ws = nullptr;
     size_t ws_cap = 0;
@@ -851,6 +867,161 @@ int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long 
     return decode_tail(h, c, cat, B, N, wav_out);
 }
 
+// ---- Codec.forward (codec.py:138-162, codec_adaptive.py:100-148): encode -> RVQ -> decode with the codes kept on the device, and the
+// semantic decoder on the looked-up semantic embedding
+
+// SemanticDecoder.forward (semantic_module.py:294-299) on the channel-last summed semantic code vectors z [B, N, code_dim] (row
+// stride ldz) -> pred [B, output_channels, N * prod(strides)], channel-first like the reference.
+int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int64_t ldz, int B, int N, float* pred) {
+    const qa_semantic_decoder_spec& sp = sd.spec;
+    int L = N, C = sp.channels;
+    float* x = c.arena.alloc<float>((size_t)B * L * C);
+    QA_TRY(conv_op(c, z, ldz, B, L, sd.conv1, x, C, L, 1, 1, 1, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr, 0, nullptr, ACT_NONE));
+    for (const auto& blk : sd.blocks) {
+        const int s = blk.stride, co = blk.c_out, To = L * s;
+        float* y = c.arena.alloc<float>((size_t)B * To * co);
+        if (s == 1) {
+            QA_TRY(conv_same(c, x, B, L, blk.conv, y));
+        } else {  // ConvTranspose1d: phase phi writes rows q * s + phi (row stride s * co)
+            for (int phi = 0; phi < s; ++phi) {
+                const ConvW& w = blk.phase[phi];
+                QA_TRY(conv_op(c, x, C, B, L, w, y + (size_t)phi * co, (int64_t)s * co, L, 1, blk.pad_left[phi],
+                               w.ksize - 1 - blk.pad_left[phi], PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr, 0, nullptr, ACT_NONE));
+            }
+        }
+        float* t = c.arena.alloc<float>((size_t)B * To * co);
+        for (int u = 0; u < 2; ++u) {
+            QA_TRY(conv_same(c, y, B, To, blk.u1[u], t, ACT_ELU, ACT_ELU));       // ELU(conv1(ELU(y)))
+            QA_TRY(conv_same(c, t, B, To, blk.u2[u], y, ACT_NONE, ACT_NONE, y));  // y + conv2(.)
+        }
+        x = y;
+        L = To;
+        C = co;
+    }
+    const int O = sp.output_channels;
+    float* o = c.arena.alloc<float>((size_t)B * L * O);
+    QA_TRY(conv_same(c, x, B, L, sd.conv2, o));
+    c.tap("sem_dec.out", o, (int64_t)B * L * O);
+    // [B, L, O] read as a [B, C' = L, T' = O] tensor with strides (L O, O, 1): its channel-last form is [B, O, L]
+    if (!c.dry) QA_TRY(launch_to_channel_last(o, (long long)L * O, O, 1, pred, B, L, O, c.stream));
+    return QA_OK;
+}
+
+// the semantic decoder from device-resident semantic indices [B*N, Q]: the look-up decode makes, then semantic_decoder_op.  It runs on
+// the caller's stream behind the codec decoder: on a second stream next to it the call measured no faster.
+int semantic_decoder_from_codes(qa_hcodec* h, Ctx& c, const long long* is_rows, int B, int N, float* pred) {
+    const qa_hcodec_spec& sp = h->spec;
+    const int64_t rows = (int64_t)B * N;
+    float* z = c.arena.alloc<float>(rows * sp.code_dim);
+    if (!c.dry) QA_TRY(launch_rvq_lookup(is_rows, rows, h->cb_s, sp.num_quantizers, sp.codebook_size, sp.code_dim, z, sp.code_dim, c.stream));
+    return semantic_decoder_op(*h->sdec, c, z, sp.code_dim, B, N, pred);
+}
+
+int forward_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc, int64_t fst,
+                  int n_feat, int N, float* recon, float* pred) {
+    const int Q = h->spec.num_quantizers;
+    long long* ac = c.arena.alloc<long long>((size_t)B * Q * N);
+    long long* sc = c.arena.alloc<long long>((size_t)B * Q * N);
+    QA_TRY(encode_graph(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc));
+    // the decoder's own path from the codes (decode_graph), so recon is decode(encode()) bit for bit
+    long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
+    if (!c.dry) QA_TRY(launch_codes_from_bqn(sc, is, B, N, Q, c.stream));
+    QA_TRY(decode_graph(h, c, ac, sc, B, N, recon));
+    return semantic_decoder_from_codes(h, c, is, B, N, pred);
+}
+
+int forward_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
+                           int64_t fst, int n_feat, int N, float* recon, float* pred, long long* token_lengths, int* G_out) {
+    const qa_hcodec_spec& sp = h->spec;
+    const int Q = sp.num_quantizers, K = sp.codebook_size;
+    long long* ac = c.arena.alloc<long long>((size_t)B * Q * N);
+    long long* sc = c.arena.alloc<long long>((size_t)B * Q * N);
+    int G = 0;
+    QA_TRY(encode_adaptive_graph(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc, &G, sp.threshold));
+    *G_out = G;
+    // every item's groups cover all N frames (x_lens = T for the whole batch, codec_adaptive.py:106-107): decode at N frames
+    long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
+    if (!c.dry) {
+        QA_TRY(launch_token_lengths(sc, token_lengths, B, Q, G, K, c.stream));
+        QA_TRY(launch_deaggregate(sc, sc, is, B, Q, G, N, K, c.stream));  // codec_adaptive.py:134-135
+    }
+    QA_TRY(decode_adaptive_graph(h, c, ac, sc, B, G, N, recon));
+    return semantic_decoder_from_codes(h, c, is, B, N, pred);
+}
+
+// semantic_decoder.* of the reference's state_dict: every key checked in module order first (the error names the FIRST missing or
+// mis-shaped one), then folded into a store of its own
+int build_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec& sp, const HostTable& tab, std::unique_ptr<qa_hcodec::SemDec>* out) {
+    QA_REQUIRE(sp.n_blocks >= 1 && sp.n_blocks <= 4, "semantic decoder: n_blocks %d outside [1, 4]", sp.n_blocks);
+    QA_REQUIRE(sp.code_dim == h->spec.code_dim, "semantic decoder: code_dim %d != the codec's %d", sp.code_dim, h->spec.code_dim);
+    QA_REQUIRE(sp.channels > 0 && sp.channels % 32 == 0 && sp.output_channels > 0 && sp.output_channels % 32 == 0,
+               "semantic decoder: channels %d / output_channels %d must be positive multiples of 32", sp.channels, sp.output_channels);
+    for (int i = 0; i < sp.n_blocks; ++i) {
+        QA_REQUIRE(sp.widths[i] > 0 && sp.widths[i] % 32 == 0, "semantic decoder: block %d width %d must be a positive multiple of 32", i,
+                   sp.widths[i]);
+        // ConvTranspose1d(k = 2 s, padding (s + 1) // 2, output_padding s % 2) (semantic_module.py:86-104): for even s the padding is
+        // (k - s) / 2 and the output exactly s frames per input frame; odd strides are not implemented
+        QA_REQUIRE(sp.strides[i] == 1 || (sp.strides[i] >= 2 && sp.strides[i] % 2 == 0),
+                   "semantic decoder: block %d stride %d: only stride 1 and even strides are supported", i, sp.strides[i]);
+    }
+    const std::string p = "semantic_decoder.";
+    std::vector<std::pair<std::string, int64_t>> keys;
+    keys.push_back({p + "conv1.conv.weight", (int64_t)sp.channels * sp.code_dim * 3});
+    for (int i = 0, ci = sp.channels; i < sp.n_blocks; ci = sp.widths[i], ++i) {
+        const std::string bp = p + "conv_blocks." + std::to_string(i);
+        const int s = sp.strides[i], co = sp.widths[i];
+        const std::string cp = bp + (s == 1 ? ".conv.conv" : ".conv.deconv");
+        keys.push_back({cp + ".weight", (int64_t)co * ci * (s == 1 ? 3 : 2 * s)});
+        keys.push_back({cp + ".bias", co});
+        for (int u = 0; u < 2; ++u) {
+            keys.push_back({bp + ".res_units." + std::to_string(u) + ".conv1.conv.weight", (int64_t)co * co * 3});
+            keys.push_back({bp + ".res_units." + std::to_string(u) + ".conv2.weight", (int64_t)co * co});
+        }
+    }
+    keys.push_back({p + "conv2.conv.weight", (int64_t)sp.output_channels * sp.widths[sp.n_blocks - 1] * 3});
+    for (const auto& k : keys)
+        if (!tab.get(k.first, k.second)) return QA_ERR_MISSING;  // HostTable::get has set the error message
+    std::unique_ptr<qa_hcodec::SemDec> sd(new qa_hcodec::SemDec());
+    sd->spec = sp;
+    Builder b{Folder{tab, sd->store}};
+    b.conv(&sd->conv1, p + "conv1.conv", sp.channels, sp.code_dim, 3, false, false);
+    sd->blocks.resize(sp.n_blocks);
+    for (int i = 0, ci = sp.channels; i < sp.n_blocks; ci = sp.widths[i], ++i) {
+        auto& blk = sd->blocks[i];
+        const std::string bp = p + "conv_blocks." + std::to_string(i);
+        const int s = sp.strides[i], co = sp.widths[i];
+        blk.stride = s;
+        blk.c_out = co;
+        if (s == 1) {
+            b.conv(&blk.conv, bp + ".conv.conv", co, ci, 3, false, true);
+        } else {  // weight [C_in][C_out][2 s], padding s / 2
+            const float* w = b.f.need(bp + ".conv.deconv.weight", (int64_t)ci * co * 2 * s);
+            blk.phase.resize(s);
+            blk.pad_left.resize(s);
+            for (int phi = 0; phi < s; ++phi) {
+                PolyphaseFilter pf;
+                QA_TRY(polyphase_filter(w, ci, co, 2 * s, s, s / 2, phi, &pf));
+                ConvW& cw = blk.phase[phi];
+                cw.N = co; cw.C_in = ci; cw.ksize = pf.ntaps;
+                b.raw(&cw.w, pf.filter);
+                b.vec(&cw.b, bp + ".conv.deconv.bias", co);
+                blk.pad_left[phi] = pf.pad_left;
+            }
+        }
+        for (int u = 0; u < 2; ++u) {
+            const std::string up = bp + ".res_units." + std::to_string(u);
+            b.conv(&blk.u1[u], up + ".conv1.conv", co, co, 3, false, false);
+            b.conv(&blk.u2[u], up + ".conv2", co, co, 1, false, false);
+        }
+    }
+    b.conv(&sd->conv2, p + "conv2.conv", sp.output_channels, sp.widths[sp.n_blocks - 1], 3, false, false);
+    if (!b.f.ok) return b.f.status;
+    QA_TRY(sd->store.upload());
+    b.resolve();
+    *out = std::move(sd);
+    return QA_OK;
+}
+
 int ensure_workspace(qa_hcodec* h, size_t bytes) {
     if (bytes <= h->ws_cap) return QA_OK;
     if (h->ws) QA_HIP(hipFree(h->ws));  // synchronises with outstanding work
@@ -1267,6 +1438,94 @@ int qa_hcodec_decode_adaptive(qa_hcodec* h, const int64_t* ac, const int64_t* sc
     c.taps.clear();
     c.arena.begin(h->ws, h->ws_cap);
     return run_graph_checked(h, c, [&] { return decode_adaptive_graph(h, c, (const long long*)ac, (const long long*)sc, (int)B, (int)G, (int)frames, wav_out); });
+}
+
+int qa_hcodec_load_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec* spec, const qa_tensor* tensors, int64_t n_tensors) {
+    if (!h || !spec || !tensors) {
+        set_error("qa_hcodec_load_semantic_decoder: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_HIP(hipSetDevice(h->device));
+    HostTable tab(tensors, n_tensors);
+    std::unique_ptr<qa_hcodec::SemDec> sd;
+    QA_TRY(build_semantic_decoder(h, *spec, tab, &sd));
+    if (h->sdec) QA_HIP(hipDeviceSynchronize());  // the old weights may still be read by an earlier forward
+    h->sdec = std::move(sd);
+    return QA_OK;
+}
+
+int qa_hcodec_has_semantic_decoder(const qa_hcodec* h) {
+    if (!h) {
+        set_error("qa_hcodec_has_semantic_decoder: null handle");
+        return QA_ERR_INVALID;
+    }
+    return h->sdec ? 1 : 0;
+}
+
+// shared argument checks of the two forward entry points; returns N25 through *n25
+static int forward_checks(qa_hcodec* h, const char* fn, const float* wav, int64_t B, int64_t T, const float* feat, const float* recon,
+                          const float* pred, bool adaptive, int* n25) {
+    if (!h || !wav || !feat || !recon || !pred) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(h->sdec, "%s: no semantic decoder is attached (qa_hcodec_load_semantic_decoder: the checkpoint's semantic_decoder.* "
+               "weights)", fn);
+    QA_REQUIRE(!adaptive || h->spec.adaptive, "%s: this handle is not an H-Codec 1.5 model", fn);
+    QA_REQUIRE(adaptive || !h->spec.adaptive, "%s: this handle is an H-Codec 1.5 model, use qa_hcodec_forward_adaptive", fn);
+    int hop = 2;
+    for (int i = 0; i < h->spec.n_ratios; ++i) hop *= h->spec.ratios[i];
+    if (h->spec.version == 20) hop = h->spec.hop * h->spec.frame_stride;
+    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "%s: wav is [%lld, %lld]; T must be a positive multiple of %d (HCodecTokenizer.pad_wav)",
+               fn, (long long)B, (long long)T, hop);
+    QA_REQUIRE(B * T < (1LL << 31), "%s: batch of %lld x %lld samples is too large", fn, (long long)B, (long long)T);
+    int64_t up = 1;
+    for (int i = 0; i < h->sdec->spec.n_blocks; ++i) up *= h->sdec->spec.strides[i];
+    QA_REQUIRE(B * (T / hop) * up * std::max(h->sdec->spec.output_channels, h->sdec->spec.widths[0]) < (1LL << 31), "%s: pred_feat too large", fn);
+    *n25 = (int)(T / hop);
+    return QA_OK;
+}
+
+int qa_hcodec_forward(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc, int64_t fst,
+                      int64_t n_feat, float* recon, float* pred_feat, void* stream) {
+    int N = 0;
+    QA_TRY(forward_checks(h, "qa_hcodec_forward", wav, B, T, feat, recon, pred_feat, false, &N));
+    QA_HIP(hipSetDevice(h->device));
+    Ctx& c = h->ctx;
+    c.stream = static_cast<hipStream_t>(stream);
+    c.dry = true;
+    c.arena.begin(nullptr, 0);
+    QA_TRY(forward_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat));
+    QA_TRY(ensure_workspace(h, c.arena.peak()));
+    c.dry = false;
+    c.taps.clear();
+    c.arena.begin(h->ws, h->ws_cap);
+    return run_graph_checked(h, c, [&] { return forward_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat); });
+}
+
+int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
+                               int64_t fst, int64_t n_feat, float* recon, float* pred_feat, int64_t* token_lengths, int64_t* n_groups,
+                               void* stream) {
+    int N = 0;
+    QA_TRY(forward_checks(h, "qa_hcodec_forward_adaptive", wav, B, T, feat, recon, pred_feat, true, &N));
+    QA_REQUIRE(token_lengths && n_groups, "qa_hcodec_forward_adaptive: null argument");
+    QA_HIP(hipSetDevice(h->device));
+    Ctx& c = h->ctx;
+    c.stream = static_cast<hipStream_t>(stream);
+    c.dry = true;
+    c.arena.begin(nullptr, 0);
+    int G = 0;
+    QA_TRY(forward_adaptive_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat, (long long*)token_lengths, &G));
+    QA_TRY(ensure_workspace(h, c.arena.peak()));
+    c.dry = false;
+    c.taps.clear();
+    c.arena.begin(h->ws, h->ws_cap);
+    QA_TRY(run_graph_checked(h, c, [&] {
+        return forward_adaptive_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat,
+                                      (long long*)token_lengths, &G);
+    }));
+    *n_groups = G;
+    return QA_OK;
 }
 
 int qa_hcodec_enable_taps(qa_hcodec* h, int on) {

@@ -129,4 +129,27 @@ struct ConvW {
 
 inline int pad32(int c) { return (int)round_up(c, 32); }
 
+// One output phase of a ConvTranspose1d(k, stride s, padding pad) as a stride-1 convolution.  Weight w [C_in][C_out][k] (nullptr: the
+// filter stays zero).  y[q s + phi] = sum_m x[q + c0 - m] W[:, :, j0 + m s] with j0 = (phi + pad) mod s, c0 = (phi + pad) div s: a
+// stride-1 convolution with taps jj = 0 .. n-1 <-> m = n-1-jj, pad_left = n - 1 - c0 (n = number of taps of the phase), right padding
+// c0.  `filter` receives the library layout [C_out][n][C_in]; phase phi of the output is written to rows q s + phi.
+struct PolyphaseFilter {
+    std::vector<float> filter;
+    int ntaps = 0, pad_left = 0;
+};
+inline int polyphase_filter(const float* w, int cin, int cout, int k, int s, int pad, int phi, PolyphaseFilter* out) {
+    const int j0 = (phi + pad) % s, c0 = (phi + pad) / s, n = (k - j0 + s - 1) / s;
+    QA_REQUIRE(n >= 1 && n - 1 - c0 >= 0, "ConvTranspose1d phase %d of k=%d s=%d has no causal tap layout", phi, k, s);
+    out->filter.assign((size_t)cout * n * cin, 0.f);
+    if (w)
+        for (int o = 0; o < cout; ++o)
+            for (int jj = 0; jj < n; ++jj) {
+                const int j = j0 + (n - 1 - jj) * s;
+                for (int c = 0; c < cin; ++c) out->filter[((size_t)o * n + jj) * cin + c] = w[((size_t)c * cout + o) * k + j];
+            }
+    out->ntaps = n;
+    out->pad_left = n - 1 - c0;
+    return QA_OK;
+}
+
 }  // namespace qa

@@ -35,6 +35,7 @@ int launch_agg_gather(const float* x, const int* start, const int* len, const in
 int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K,
                         hipStream_t s);
 int launch_adaptive_frames(const long long* codes, int B, int Q, int G, int K, int* totals, int* tmax, hipStream_t s);
+int launch_token_lengths(const long long* codes, long long* out, int B, int Q, int G, int K, hipStream_t s);
 int launch_deaggregate(const long long* codes, const long long* len_codes, long long* out, int B, int Q, int G, int T, int K,
                        hipStream_t s);
 int launch_to_channel_last(const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T,

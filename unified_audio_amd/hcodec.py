@@ -109,8 +109,56 @@ SPEC_20 = HCodecSpec(version=20, enc_dim=1536, enc_inter=4608, enc_convnext_laye
                      dec_dim=1536, dec_inter=4608, dec_heads=24, dec_layers=2, convnext_layers=32, n_fft=1920, hop=960)
 
 
+@dataclass(frozen=True)
+class SemanticDecoderSpec:
+    """`semantic_module.Decoder` (QuarkAudio-HCodec/HCodec-1.0/vq/semantic_module.py:247-300): the codec's semantic decoder, which rebuilds
+    the SSL features from the summed semantic code vectors (`pred_feat` of `Codec.forward`).  Every shipped configuration mirrors the
+    semantic encoder: output = sem_in, width = sem_ch, strides = sem_strides, channel ratios all 1 (`from_codec_spec`)."""
+
+    code_dim: int = 512
+    output_channels: int = 768
+    decode_channels: int = 768
+    channel_ratios: Tuple[float, ...] = (1, 1)
+    strides: Tuple[int, ...] = (2, 1)
+
+    @staticmethod
+    def from_codec_spec(spec: HCodecSpec) -> "SemanticDecoderSpec":
+        return SemanticDecoderSpec(code_dim=spec.code_dim, output_channels=spec.sem_in, decode_channels=spec.sem_ch,
+                                   channel_ratios=(1,) * len(spec.sem_strides), strides=tuple(spec.sem_strides))
+
+    @staticmethod
+    def from_kwargs(kw: dict) -> "SemanticDecoderSpec":
+        """The reference's constructor keywords (decoder_config.semantic_decoder of the 1.5 YAML, semantic_decoder_config of 2.0)."""
+        strides = tuple(kw.get("strides", (1, 1)))
+        return SemanticDecoderSpec(code_dim=kw["code_dim"], output_channels=kw["output_channels"], decode_channels=kw["decode_channels"],
+                                   channel_ratios=tuple(kw.get("channel_ratios", (1,) * len(strides))), strides=strides)
+
+    @property
+    def widths(self) -> Tuple[int, ...]:
+        """output width of every DecoderBlock (semantic_module.py:276-281)"""
+        n, dc, r = len(self.strides), self.decode_channels, self.channel_ratios
+        return tuple(int(dc * r[i + 1]) if i < n - 1 else dc for i in range(n))
+
+    def to_c(self) -> "_lib.qa_semantic_decoder_spec":
+        if len(self.channel_ratios) != len(self.strides) or not 1 <= len(self.strides) <= 4:
+            raise _lib.QuarkAudioError(-1, f"semantic decoder: {len(self.strides)} strides / {len(self.channel_ratios)} channel ratios")
+        s = _lib.qa_semantic_decoder_spec()
+        s.code_dim, s.channels, s.n_blocks = self.code_dim, int(self.decode_channels * self.channel_ratios[0]), len(self.strides)
+        for i, (st, w) in enumerate(zip(self.strides, self.widths)):
+            s.strides[i], s.widths[i] = st, w
+        s.output_channels = self.output_channels
+        return s
+
+
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _semantic_decoder_spec_from_config(config: dict) -> Optional[SemanticDecoderSpec]:
+    """SemanticDecoderSpec from the reference's YAML dictionaries (1.5: decoder_config.semantic_decoder, 2.0: semantic_decoder_config);
+    None when they carry none."""
+    kw = config.get("semantic_decoder_config") or (config.get("decoder_config") or {}).get("semantic_decoder")
+    return SemanticDecoderSpec.from_kwargs(kw) if isinstance(kw, dict) else None
 
 
 def _spec_from_config(config: dict, device=None) -> HCodecSpec:
@@ -157,10 +205,12 @@ class Codec(torch.nn.Module):
 
     def __init__(self, encoder_kwargs=None, decoder_kwargs=None, quantizer_kwargs=None, adaptive_kwargs=None,
                  semantic_decoder_kwargs=None, *, spec: Optional[HCodecSpec] = None,
+                 semantic_decoder_spec: Optional[SemanticDecoderSpec] = None,
                  device: str | torch.device = "cuda:0", check_codes: bool = True):
         super().__init__()
+        adaptive_cfg = isinstance(encoder_kwargs, dict) and isinstance(adaptive_kwargs, dict) and "aggregators" in adaptive_kwargs
         if spec is None:
-            if isinstance(encoder_kwargs, dict) and isinstance(adaptive_kwargs, dict) and "aggregators" in adaptive_kwargs:
+            if adaptive_cfg:
                 spec = _spec_from_config({"encoder_config": encoder_kwargs, "decoder_config": decoder_kwargs,
                                           "quantizer_config": quantizer_kwargs, "adaptive_config": adaptive_kwargs})
             elif isinstance(encoder_kwargs, dict) and "n_fft" in encoder_kwargs:  # 2.0: Codec(enc, dec, quant, sem_enc, sem_dec)
@@ -168,12 +218,22 @@ class Codec(torch.nn.Module):
                                           "quantizer_config": quantizer_kwargs, "semantic_encoder_config": adaptive_kwargs})
             else:
                 spec = SPEC_10
+        if semantic_decoder_spec is None:
+            semantic_decoder_spec = _semantic_decoder_spec_from_config(
+                {"decoder_config": decoder_kwargs if isinstance(decoder_kwargs, dict) else None,
+                 "semantic_decoder_config": semantic_decoder_kwargs if isinstance(semantic_decoder_kwargs, dict) else None})
         self.spec = spec
+        self.semantic_decoder_spec = semantic_decoder_spec or SemanticDecoderSpec.from_codec_spec(spec)
+        # the 1.5 dynamic-threshold draw (codec_adaptive.py:91-95: infer_using_dynamic_threshold without a manual_threshold) is random
+        # per call; forward refuses it rather than use a fixed threshold
+        self.dynamic_threshold = bool(adaptive_cfg and adaptive_kwargs.get("infer_using_dynamic_threshold")
+                                      and adaptive_kwargs.get("manual_threshold") is None)
         self.device = torch.device(device)
         self.check_codes = check_codes  # decode(): refuse out-of-range codes like F.embedding (one tiny kernel + one sync)
         self._handle = C.c_void_p()
         self._lib = _lib.load_library()
         self._state = None
+        self._semantic_decoder_error = None  # why forward cannot run (no / incomplete semantic_decoder.* weights)
 
     # -- weights -------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True, assign: bool = False):
@@ -185,8 +245,16 @@ class Codec(torch.nn.Module):
         spec_c = self.spec.to_c()
         handle = C.c_void_p()
         _lib.check(self._lib.qa_hcodec_create(C.byref(handle), C.byref(spec_c), table, n, self.device.index or 0))
-        del keep
         self._handle = handle
+        # the semantic decoder (forward's pred_feat) is optional: encode / decode never read it, and a checkpoint without (all of) its
+        # weights still loads - forward then raises naming the first missing or mis-shaped key
+        try:
+            sd_c = self.semantic_decoder_spec.to_c()
+            st = self._lib.qa_hcodec_load_semantic_decoder(handle, C.byref(sd_c), table, n)
+            self._semantic_decoder_error = None if st == 0 else (st, self._lib.qa_last_error().decode("utf-8", "replace"))
+        except _lib.QuarkAudioError as e:
+            self._semantic_decoder_error = (e.status, str(e))
+        del keep
         self._state = state_dict  # a reference, not a copy: lets .to(other_gpu) rebuild the handle there
         return self
 
@@ -237,8 +305,55 @@ class Codec(torch.nn.Module):
     def float(self):
         return self
 
-    def forward(self, *args, **kwargs):
-        raise _lib.QuarkAudioError(-4, "Codec.forward is the training forward of the reference; use encode() / decode()")
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, feat: Optional[torch.Tensor] = None, use_mask=False, domain_split=None):
+        """Codec.forward in eval mode: 1.0 codec.py:138-162, 2.0 codec.py:54-72 -> (recon [B, T], pred_feat [B, sem_in, N_feat],
+        commit_loss); 1.5 codec_adaptive.py:100-148 -> {'recon', 'pred_feat', 'commit_loss', 'token_lengths' [B, G] int64}.
+
+        recon is decode(encode(x, feat)) bit for bit (the same kernels on the same device-resident codes); pred_feat is the semantic
+        decoder on the summed semantic code vectors (1.5: de-aggregated back to the 25 Hz frames first).  commit_loss is a 0-dim 0.:
+        the checked-in vector_quantize_pytorch stand-in returns zero losses, and upstream ResidualVQ (1.22.x, recalled, not diffed here)
+        adds its commitment terms only under `self.training`, which this inference module never is.  `use_mask` / `domain_split`
+        are accepted and ignored, as by the reference.  All outputs are fp32 tensors on the codec's device."""
+        self._require_loaded()
+        if self._semantic_decoder_error is not None:
+            st, msg = self._semantic_decoder_error
+            raise _lib.QuarkAudioError(st, f"Codec.forward needs the semantic decoder weights (semantic_decoder.*): {msg}")
+        if feat is None:
+            raise _lib.QuarkAudioError(-1, "Codec.forward(x, feat): feat (the SSL features) is required")
+        if self.spec.adaptive and self.dynamic_threshold:
+            raise _lib.QuarkAudioError(-4, "Codec.forward: the config draws a random similarity threshold per call "
+                                           "(infer_using_dynamic_threshold without manual_threshold); set manual_threshold")
+        if x.dim() == 2:  # H-Codec 2.0 passes wav without the channel dim
+            x = x.unsqueeze(1)
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise _lib.QuarkAudioError(-1, f"forward expects x of shape [B,1,T], got {tuple(x.shape)}")
+        if feat.dim() != 3 or feat.shape[0] != x.shape[0] or feat.shape[1] != self.spec.sem_in:
+            raise _lib.QuarkAudioError(-1, f"forward expects feat of shape [B,{self.spec.sem_in},N], got {tuple(feat.shape)}")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        feat = feat.to(device=self.device, dtype=torch.float32)
+        B, _, T = x.shape
+        n25 = T // self.spec.enc_hop
+        sds = self.semantic_decoder_spec
+        recon = torch.empty((B, n25 * self.spec.dec_upsample * self.spec.hop), dtype=torch.float32, device=self.device)
+        pred = torch.empty((B, sds.output_channels, n25 * int(math.prod(sds.strides))), dtype=torch.float32, device=self.device)
+        commit_loss = torch.zeros((), dtype=torch.float32, device=self.device)
+        sb, sch, st = feat.stride()
+        if self.spec.adaptive:
+            tl = torch.empty((B, max(n25, 1)), dtype=torch.int64, device=self.device)
+            g = C.c_int64(0)
+            _lib.check(self._lib.qa_hcodec_forward_adaptive(self._handle, x.data_ptr(), B, T, feat.data_ptr(), sb, sch, st, feat.shape[2],
+                                                            recon.data_ptr(), pred.data_ptr(), tl.data_ptr(), C.byref(g),
+                                                            _stream_ptr(self.device)))
+            G = int(g.value)
+            return {"recon": recon, "pred_feat": pred, "commit_loss": commit_loss, "token_lengths": tl.view(-1)[: B * G].view(B, G)}
+        _lib.check(self._lib.qa_hcodec_forward(self._handle, x.data_ptr(), B, T, feat.data_ptr(), sb, sch, st, feat.shape[2],
+                                               recon.data_ptr(), pred.data_ptr(), _stream_ptr(self.device)))
+        return recon, pred, commit_loss
+
+    @property
+    def has_semantic_decoder(self) -> bool:
+        return bool(self._handle.value) and self._lib.qa_hcodec_has_semantic_decoder(self._handle) == 1
 
     def _free(self):
         if getattr(self, "_handle", None) is not None and self._handle.value:
@@ -423,7 +538,12 @@ class HCodecTokenizer(torch.nn.Module):
                 if isinstance(state_dict, dict) and "state_dict" in state_dict:  # HCodec-1.5/audio_tokenizer.py:20-25
                     state_dict = state_dict["state_dict"]
             self.device = torch.device(device) if str(device) != "cpu" else torch.device("cuda:0")  # 2.0's default device='cpu': no CPU path
-            self.model = Codec(None, None, None, spec=spec, device=self.device).load_state_dict(state_dict)
+            self.model = Codec(None, None, None, spec=spec, device=self.device,
+                               semantic_decoder_spec=_semantic_decoder_spec_from_config(config) if config is not None else None)
+            ad = (config or {}).get("adaptive_config") or {}
+            self.model.dynamic_threshold = bool(spec.adaptive and ad.get("infer_using_dynamic_threshold")
+                                                and ad.get("manual_threshold") is None)
+            self.model.load_state_dict(state_dict)
         self.feature_extractor = feature_extractor
         if isinstance(feature_extractor, torch.nn.Module):
             feature_extractor.eval()  # audio_tokenizer.py:28-29: the reference puts its SSL model in eval mode at construction

@@ -7,8 +7,8 @@ seeds + outputs.
 
 `hcodec10_state_dict` produces a flat state_dict with exactly the key names / shapes of the reference's
 `Codec(None, None, None).state_dict()` (HCodec-1.0/vq/codec.py:21-136; checked by tests/test_oracle_cpu.py against the
-reference's own modules) minus the training-only `semantic_decoder.*` entries, which `Codec.encode/decode` never touch
-(codec.py:166-187).  Spec arguments are duck-typed: the product's `unified_audio_amd.HCodecSpec` and the oracle's spec
+reference's own modules) minus the `semantic_decoder.*` entries, which `Codec.encode/decode` never touch (codec.py:166-187);
+`hcodec_semantic_decoder_state_dict` draws those from a generator of its own (Codec.forward's pred_feat).  Spec arguments are duck-typed: the product's `unified_audio_amd.HCodecSpec` and the oracle's spec
 dataclasses carry the same field names.
 """
 from __future__ import annotations
@@ -250,6 +250,32 @@ def hcodec20_state_dict(seed: int, spec, head_logmag_bias: float = 1.5) -> Dict[
             g.conv(f"{bp}.res_units.{u}.conv2", sc, sc, 1, bias=False)
         g.conv(f"{bp}.conv.conv", sc, sc, 3 if s == 1 else 2 * s, bias=True)
     g.conv("semantic_encoder.conv2.conv", spec.dimension, sc, 3, bias=False)
+    return g.sd
+
+
+def hcodec_semantic_decoder_state_dict(seed: int, sd_spec) -> Dict[str, torch.Tensor]:
+    """`semantic_decoder.*` of an H-Codec checkpoint (semantic_module.py:205-300, the keys of the reference's own module), from a
+    generator of its own so that every other synth stream stays as it was.  `sd_spec`: a unified_audio_amd.SemanticDecoderSpec
+    (code_dim, output_channels, decode_channels, channel_ratios, strides)."""
+    g = _Gen(seed)
+    p = "semantic_decoder"
+    strides, dc, r = tuple(sd_spec.strides), sd_spec.decode_channels, tuple(sd_spec.channel_ratios)
+    c = int(dc * r[0])
+    g.conv(f"{p}.conv1.conv", c, sd_spec.code_dim, 3, bias=False, gain=1.5)
+    for i, s in enumerate(strides):
+        bp = f"{p}.conv_blocks.{i}"
+        co = int(dc * r[i + 1]) if i < len(strides) - 1 else dc
+        if s == 1:
+            g.conv(f"{bp}.conv.conv", co, c, 3, gain=1.5)
+        else:  # ConvTranspose1d weight [C_in, C_out, 2 s]
+            bound = 1.5 / math.sqrt(c * 2)
+            g.sd[f"{bp}.conv.deconv.weight"] = _t(g.uniform((c, co, 2 * s), bound))
+            g.sd[f"{bp}.conv.deconv.bias"] = _t(g.uniform((co,), bound))
+        for u in range(2):
+            g.conv(f"{bp}.res_units.{u}.conv1.conv", co, co, 3, bias=False, gain=1.5)
+            g.sd[f"{bp}.res_units.{u}.conv2.weight"] = _t(g.uniform((co, co, 1), 1.5 / math.sqrt(co)))
+        c = co
+    g.conv(f"{p}.conv2.conv", sd_spec.output_channels, c, 3, bias=False, gain=1.5)
     return g.sd
 
 
