@@ -70,19 +70,14 @@ struct GenBlockW {
 
 }  // namespace
 
-struct qa_bicodec {
+struct qa_bicodec : Handle {
     qa_bicodec_spec spec{};
-    int device = 0;
     int n_glob = 0, hop = 1, n_ada = 0;
-    WeightStore store;
     const float *sem_table = nullptr, *glob_table = nullptr;
     ConvW project, ada, linear_pre, linear_out, gen_in, gen_out;
     VocosW down[2], backbone;
     std::vector<GenBlockW> blocks;
     const float* a_final = nullptr;
-    char* ws = nullptr;
-    size_t ws_cap = 0;
-    Ctx ctx;
 };
 
 // Conv1dReluBn (ecapa_tdnn.py): the convolution with BN(ReLU(.)) as the epilogue  relu(acc + b) * s + t
@@ -102,10 +97,8 @@ struct PerceiverLayerW {
 
 // BiCodec.get_semantic_tokens (bicodec.py:167-172): Encoder + FactorizedVectorQuantize.tokenize; BiCodec.get_global_tokens
 // (bicodec.py:174-178): mel spectrogram + ECAPA-TDNN latent + PerceiverResampler + ResidualFSQ
-struct qa_bicodec_enc {
+struct qa_bicodec_enc : Handle {
     qa_bicodec_enc_spec spec{};
-    int device = 0;
-    WeightStore store;
     VocosW backbone, down[2];
     ConvW project, in_project;
     const float *codebook = nullptr, *e2 = nullptr;  // F.normalize(codebook) [K, D] and its squared norms
@@ -116,65 +109,11 @@ struct qa_bicodec_enc {
     SeRes2W blocks[3];
     std::vector<PerceiverLayerW> perceiver;
     const float *latents = nullptr, *norm_gamma = nullptr;
-    char* ws = nullptr;
-    size_t ws_cap = 0;
-    Ctx ctx;
 };
 
 namespace {
 
 // ---------------------------------------------------------------- weight folding (host)
-struct Loader {
-    const HostTable& tab;
-    WeightStore& st;
-    bool ok = true;
-    std::vector<std::pair<const float**, size_t>> pend;
-
-    const float* need(const std::string& name, int64_t n) {
-        const float* p = tab.get(name, n);
-        if (!p) ok = false;
-        return p;
-    }
-    void vec(const float** dst, const std::string& name, int64_t n) {
-        const float* p = need(name, n);
-        if (p) pend.push_back({dst, st.add(p, (size_t)n)});
-    }
-    void raw(const float** dst, const std::vector<float>& v) { pend.push_back({dst, st.add(v)}); }
-    // torch.nn.utils.weight_norm (dim 0) or a plain .weight: returns the [d0][rest] tensor
-    bool weight(const std::string& p, int64_t d0, int64_t rest, std::vector<float>* out) {
-        out->assign((size_t)(d0 * rest), 0.f);
-        if (tab.has(p + ".weight")) {
-            const float* w = need(p + ".weight", d0 * rest);
-            if (!w) return false;
-            std::memcpy(out->data(), w, sizeof(float) * (size_t)(d0 * rest));
-            return true;
-        }
-        const float* v = need(p + ".weight_v", d0 * rest);
-        const float* g = need(p + ".weight_g", d0);
-        if (!v || !g) return false;
-        for (int64_t i = 0; i < d0; ++i) {
-            double ss = 0.0;
-            for (int64_t j = 0; j < rest; ++j) ss += (double)v[i * rest + j] * v[i * rest + j];
-            const float scale = g[i] / (float)std::sqrt(ss);
-            for (int64_t j = 0; j < rest; ++j) (*out)[(size_t)(i * rest + j)] = v[i * rest + j] * scale;
-        }
-        return true;
-    }
-    // Conv1d / Linear weight [N][C_in][k] -> library layout [N][k][C_in] (scaled by `gain`), bias [N]
-    void conv(ConvW* dst, const std::string& p, int N, int C_in, int k, bool bias = true, float gain = 1.f) {
-        std::vector<float> w, r((size_t)N * k * C_in);
-        if (weight(p, N, (int64_t)C_in * k, &w))
-            for (int n = 0; n < N; ++n)
-                for (int c = 0; c < C_in; ++c)
-                    for (int j = 0; j < k; ++j) r[((size_t)n * k + j) * C_in + c] = w[((size_t)n * C_in + c) * k + j] * gain;
-        dst->N = N; dst->C_in = C_in; dst->ksize = k;
-        raw(&dst->w, r);
-        if (bias) vec(&dst->b, p + ".bias", N);
-    }
-    void resolve() {
-        for (auto& pv : pend) *pv.first = st.ptr(pv.second);
-    }
-};
 
 void build_vocos(Loader& L, VocosW* v, const std::string& p, int C, int I, int n_layers, bool ada, float embed_gain, int C_in = 0) {
     L.conv(&v->embed, p + ".embed", C, C_in > 0 ? C_in : C, 7, true, embed_gain);
@@ -221,7 +160,7 @@ int build(qa_bicodec* h, const HostTable& tab) {
                    "bicodec spec: ConvTranspose1d kernel %d / stride %d: length-exact up-sampling needs k - s even", sp.kernel_sizes[i], sp.rates[i]);
         h->hop *= sp.rates[i];
     }
-    Loader L{tab, h->store};
+    Loader L(tab, h->store, WN_DETECT);  // BiCodec mixes weight-normed and plain layers
     // ---- semantic tokens: table[v] = out_project(codebook[v]) + bias   (factorized_vector_quantize.py:154-172; k = 1 conv = Linear)
     {
         std::vector<float> w;
@@ -322,66 +261,22 @@ int build(qa_bicodec* h, const HostTable& tab) {
     }
     L.vec(&h->a_final, "decoder.model." + std::to_string(sp.n_rates + 1) + ".alpha", ch);
     L.conv(&h->gen_out, "decoder.model." + std::to_string(sp.n_rates + 2), 1, ch, 7);
-    if (!L.ok) return QA_ERR_MISSING;
-    QA_TRY(h->store.upload());
-    L.resolve();
-    return QA_OK;
+    return L.upload();
 }
 
 // ---------------------------------------------------------------- graph helpers
-struct ConvOpt {
-    int stride = 1, pad_left = 0, pad_right = 0, dilation = 1, act = ACT_NONE, post_act = ACT_NONE;
-    const float *gamma = nullptr, *res = nullptr, *alpha = nullptr, *alpha2 = nullptr;
-    float* y2 = nullptr;
-    int64_t ldr = 0, ldy2 = 0;
-    const float* shift = nullptr;  // per-channel constant added after gamma (the residual operand with row stride 0): BN after a ReLU
-};
-
-int conv(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, float* y, int64_t ldy, int T_out, const ConvOpt& o) {
-    if (c.dry) return QA_OK;
-    qa_conv_args a{};
-    a.x = x; a.w = w.w; a.bias = w.b; a.gamma = o.gamma; a.residual = o.res; a.y = y;
-    a.B = B; a.T_in = T_in; a.C_in = w.C_in; a.T_out = T_out; a.N = w.N;
-    a.ldx = ldx; a.ldy = ldy; a.ldr = o.ldr ? o.ldr : w.N; a.ldg = w.N;
-    a.ksize = w.ksize; a.stride = o.stride; a.pad_left = o.pad_left; a.pad_right = o.pad_right; a.pad_mode = PAD_ZERO;
-    a.act = o.act; a.post_act = o.post_act;
-    ConvParams p;
-    // conv_params_from_args checks the window span for a dense kernel: hand it the dense-equivalent paddings, then set the dilation
-    if (o.dilation > 1) {
-        a.pad_left = o.pad_left + (w.ksize - 1) * (o.dilation - 1);
-        QA_TRY(conv_params_from_args(a, &p));
-        p.pad_left = o.pad_left;
-        const int max_pad = o.pad_left > o.pad_right ? o.pad_left : o.pad_right;
-        p.Lp = (p.T_in <= max_pad) ? max_pad + 1 : p.T_in;
-    } else {
-        QA_TRY(conv_params_from_args(a, &p));
-    }
-    p.dilation = o.dilation;
-    p.alpha = o.alpha; p.y2 = o.y2; p.alpha2 = o.alpha2; p.ldy2 = o.ldy2;
-    if (o.shift) {
-        p.res = o.shift;
-        p.ldr = 0;
-    }
-    return launch_conv_gemm(p, c.stream);
-}
-
-// per_item: one row per batch item (d-vector, AdaLN conditions) - always the weight-streaming skinny GEMM, 32 rows per launch, so that an
+// One row per batch item (d-vector, AdaLN conditions): the weight-streaming skinny GEMM, 32 rows per launch, so that an
 // item's arithmetic does not depend on how many items share the call (a row-count rule - skinny up to 32 rows, implicit GEMM above -
 // made batches of more than 32 segments differ from smaller ones by 1e-5: found by the pipelined UniSE driver at 64 segments per batch)
-int linear(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, int act = ACT_NONE, const float* res = nullptr,
-           const float* gamma = nullptr, bool per_item = false) {
+int linear_per_item(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y) {
     if (c.dry) return QA_OK;
-    if (per_item && w.C_in % 256 == 0 && !gamma) {
-        for (int64_t r0 = 0; r0 < rows; r0 += 32) {
-            const int n = (int)std::min<int64_t>(32, rows - r0);
-            QA_TRY(launch_skinny_gemm(x + r0 * w.C_in, w.C_in, w.w, w.b, nullptr, 0, res ? res + r0 * w.N : nullptr, w.N, y + r0 * w.N, w.N, n, w.N,
-                                      w.C_in, act, c.stream, 0.f, 0));
-        }
-        return QA_OK;
+    if (w.C_in % 256 != 0) return linear_op(c, x, rows, w, y);
+    for (int64_t r0 = 0; r0 < rows; r0 += 32) {
+        const int n = (int)std::min<int64_t>(32, rows - r0);
+        QA_TRY(launch_skinny_gemm(x + r0 * w.C_in, w.C_in, w.w, w.b, nullptr, 0, nullptr, w.N, y + r0 * w.N, w.N, n, w.N, w.C_in, ACT_NONE,
+                                  c.stream, 0.f, 0));
     }
-    ConvOpt o;
-    o.act = act; o.res = res; o.gamma = gamma;
-    return conv(c, x, w.C_in, 1, (int)rows, w, y, w.N, (int)rows, o);
+    return QA_OK;
 }
 
 // VocosBackbone.forward (blocks/vocos.py:323-335) in place on x [B, T, C]; t1 [rows, C], u [rows, I] scratch.
@@ -392,7 +287,7 @@ int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, 
     const int64_t rows = (int64_t)B * T;
     ConvOpt same7;
     same7.pad_left = 3; same7.pad_right = 3;
-    QA_TRY(conv(c, in ? in : x, in ? v.embed.C_in : C, B, T, v.embed, t1, C, T, same7));
+    QA_TRY(conv_op(c, in ? in : x, in ? v.embed.C_in : C, B, T, v.embed, t1, C, T, same7));
     if (!c.dry) {
         if (cond) QA_TRY(launch_adaln(t1, cond, cond + C, ld_cond, x, B, T, C, 1e-6f, c.stream));
         else QA_TRY(launch_layernorm(t1, v.nw, v.nb, x, rows, C, 1e-6f, c.stream));
@@ -408,8 +303,8 @@ int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, 
                 QA_TRY(launch_dwconv(x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, C, 7, 1e-6f, c.stream));
             }
         }
-        QA_TRY(linear(c, t1, rows, w.pw1, u, ACT_GELU));
-        QA_TRY(linear(c, u, rows, w.pw2, x, ACT_NONE, x, w.gamma));
+        QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
+        QA_TRY(linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma)));
     }
     if (!c.dry) {
         QA_TRY(launch_layernorm(x, v.fw, v.fb, t1, rows, C, 1e-6f, c.stream));
@@ -431,21 +326,21 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
         QA_TRY(launch_gather_rows(sem, h->sem_table, zq, rows, sp.codebook_size, Ld, c.stream));
         QA_TRY(launch_gather_global(glob, h->glob_table, gflat, B, sp.token_num, h->n_glob, sp.spk_latent_dim, c.stream));
     }
-    QA_TRY(linear(c, gflat, B, h->project, dvec, ACT_NONE, nullptr, nullptr, true));
-    QA_TRY(linear(c, dvec, B, h->ada, cond, ACT_NONE, nullptr, nullptr, true));
+    QA_TRY(linear_per_item(c, gflat, B, h->project, dvec));
+    QA_TRY(linear_per_item(c, dvec, B, h->ada, cond));
     c.tap("z_q", zq, rows * Ld);
     c.tap("d_vector", dvec, (int64_t)B * Ld);
     // ---- prenet
     float* x = c.arena.alloc<float>(rows * C);
     float* t1 = c.arena.alloc<float>(rows * C);
     float* u = c.arena.alloc<float>(rows * I);
-    QA_TRY(linear(c, zq, rows, h->linear_pre, x));
+    QA_TRY(linear_op(c, zq, rows, h->linear_pre, x));
     for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, T, C, nullptr, 0));
     c.tap("prenet.down", x, rows * C);
     QA_TRY(vocos(c, h->backbone, x, t1, u, B, T, C, cond, h->ada.N));
     c.tap("prenet.backbone", x, rows * C);
     float* px = zq;  // z_q is dead: reuse it for the prenet output [B, T, latent]
-    QA_TRY(linear(c, x, rows, h->linear_out, px));
+    QA_TRY(linear_op(c, x, rows, h->linear_out, px));
     if (!c.dry) QA_TRY(launch_add_rowvec(px, dvec, B, T, Ld, c.stream));
     c.tap("prenet.out", px, rows * Ld);
     // ---- wave generator
@@ -454,7 +349,7 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     {
         ConvOpt o;
         o.pad_left = 3; o.pad_right = 3; o.act = ACT_SNAKE; o.alpha = h->blocks[0].a_in;
-        QA_TRY(conv(c, px, Ld, B, T, h->gen_in, s_in, ch, T, o));
+        QA_TRY(conv_op(c, px, Ld, B, T, h->gen_in, s_in, ch, T, o));
     }
     for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
         const GenBlockW& g = h->blocks[bi];
@@ -470,7 +365,7 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
             o.pad_left = g.pad_left[phi];
             o.pad_right = g.phase[phi].ksize - 1 - g.pad_left[phi];
             o.y2 = snk + (size_t)phi * co; o.alpha2 = g.unit[0].a1; o.ldy2 = (int64_t)s * co;
-            QA_TRY(conv(c, s_in, g.c_in, B, Tc, g.phase[phi], raw0 + (size_t)phi * co, (int64_t)s * co, Tc, o));
+            QA_TRY(conv_op(c, s_in, g.c_in, B, Tc, g.phase[phi], raw0 + (size_t)phi * co, (int64_t)s * co, Tc, o));
         }
         float *cur = raw0, *nxt = raw1;
         const bool last_block = bi + 1 == h->blocks.size();
@@ -480,15 +375,15 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
             ConvOpt o7;  // Snake (input, already applied) -> dilated k7 -> Snake (epilogue)
             o7.pad_left = 3 * un.dilation; o7.pad_right = 3 * un.dilation; o7.dilation = un.dilation;
             o7.act = ACT_SNAKE; o7.alpha = un.a2;
-            QA_TRY(conv(c, snk, co, B, To, un.c7, act, co, To, o7));
+            QA_TRY(conv_op(c, snk, co, B, To, un.c7, act, co, To, o7));
             ConvOpt o1;  // k1 + skip; the sum leaves raw (for the next skip) and activated (for the next convolution)
             o1.res = cur; o1.ldr = co;
             if (j < 2) {
                 o1.y2 = snk; o1.alpha2 = g.unit[j + 1].a1; o1.ldy2 = co;
-                QA_TRY(conv(c, act, co, B, To, un.c1, nxt, co, To, o1));
+                QA_TRY(conv_op(c, act, co, B, To, un.c1, nxt, co, To, o1));
             } else {  // the next consumer (next block's ConvTranspose1d / the output conv) only reads the activated sum
                 o1.post_act = ACT_SNAKE; o1.alpha = a_next_block;
-                QA_TRY(conv(c, act, co, B, To, un.c1, nxt, co, To, o1));
+                QA_TRY(conv_op(c, act, co, B, To, un.c1, nxt, co, To, o1));
             }
             std::swap(cur, nxt);
         }
@@ -500,7 +395,7 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     {
         ConvOpt o;
         o.pad_left = 3; o.pad_right = 3; o.act = ACT_TANH;
-        QA_TRY(conv(c, s_in, ch, B, Tc, h->gen_out, wav_out, 1, Tc, o));
+        QA_TRY(conv_op(c, s_in, ch, B, Tc, h->gen_out, wav_out, 1, Tc, o));
     }
     return QA_OK;
 }
@@ -513,7 +408,7 @@ int build_encoder(qa_bicodec_enc* h, const HostTable& tab) {
     QA_REQUIRE(Cin % 32 == 0 && C % 32 == 0 && I % 32 == 0 && Ld % 32 == 0 && sp.vocos_layers >= 1,
                "bicodec encoder spec: input %d, vocos %d / %d, latent %d must be multiples of 32", Cin, C, I, Ld);
     QA_REQUIRE(K >= 1 && D % 8 == 0 && D >= 8 && D <= 64, "bicodec encoder spec: codebook_dim %d must be a multiple of 8 in 8 .. 64", D);
-    Loader L{tab, h->store};
+    Loader L(tab, h->store, WN_DETECT);  // BiCodec mixes weight-normed and plain layers
     // Encoder (feat_encoder.py:29-92).  SamplingBlock with both scales 1 returns 3 x (samper.py:78-95): folded into the embed filters
     build_vocos(L, &h->backbone, "encoder.encoder", C, I, sp.vocos_layers, false, 1.0f, Cin);
     for (int i = 0; i < 2; ++i) build_vocos(L, &h->down[i], "encoder.downsample." + std::to_string(i) + ".1", C, I, 2, false, 3.0f);
@@ -540,10 +435,7 @@ int build_encoder(qa_bicodec_enc* h, const HostTable& tab) {
         L.raw(&h->codebook, cn);
         L.raw(&h->e2, e2);
     }
-    if (!L.ok) return QA_ERR_MISSING;
-    QA_TRY(h->store.upload());
-    L.resolve();
-    return QA_OK;
+    return L.upload();
 }
 
 double hz_to_mel_slaney(double f) {  // torchaudio.functional._hz_to_mel(mel_scale="slaney")
@@ -710,10 +602,10 @@ int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, l
     for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, N, C, nullptr, 0));
     c.tap("enc.down", x, rows * C);
     float* z = u;  // the ConvNeXt scratch is dead: z [rows, latent]
-    QA_TRY(linear(c, x, rows, h->project, z));
+    QA_TRY(linear_op(c, x, rows, h->project, z));
     c.tap("enc.out", z, rows * Ld);
     float* ze = c.arena.alloc<float>(rows * D);
-    QA_TRY(linear(c, z, rows, h->in_project, ze));
+    QA_TRY(linear_op(c, z, rows, h->in_project, ze));
     if (!c.dry) {
         QA_TRY(launch_l2norm_rows(ze, ze, rows, D, c.stream));
         // one stage, no residual kept: the codebook search of rvq.hip (dist = (|e|^2 - 2 e.c) + |c|^2, lowest index on a tie)
@@ -726,7 +618,7 @@ int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, l
 int conv_bn_relu(Ctx& c, const float* x, int64_t ldx, int B, int T, const ConvBnW& w, float* y, int64_t ldy, int pad) {
     ConvOpt o;
     o.pad_left = pad; o.pad_right = pad; o.act = ACT_RELU; o.gamma = w.s; o.shift = w.t;
-    return conv(c, x, ldx, B, T, w.conv, y, ldy, T, o);
+    return conv_op(c, x, ldx, B, T, w.conv, y, ldy, T, o);
 }
 
 int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, int64_t ref_len, int* tokens) {
@@ -740,9 +632,9 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     float* mag = c.arena.alloc<float>((size_t)rows * h->kp);
     float* mel = c.arena.alloc<float>((size_t)rows * sp.mel_dim);
     if (!c.dry) QA_TRY(launch_mel_frames(wav, B, T, ref_len, hop, nf, P, c.stream));
-    QA_TRY(conv(c, P, hop, B, nf + 1, h->dft, ri, 2 * h->nbp, nf, ConvOpt()));
+    QA_TRY(conv_op(c, P, hop, B, nf + 1, h->dft, ri, 2 * h->nbp, nf, ConvOpt()));
     if (!c.dry) QA_TRY(launch_spec_mag(ri, h->nbp, h->nb, mag, h->kp, rows, c.stream));
-    QA_TRY(linear(c, mag, rows, h->fbank, mel));
+    QA_TRY(linear_op(c, mag, rows, h->fbank, mel));
     c.tap("mel", mel, rows * sp.mel_dim);
     // ---- ECAPA-TDNN latent [B, nf, 1536]
     float* out1 = c.arena.alloc<float>((size_t)rows * C);
@@ -769,7 +661,7 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     {
         ConvOpt o;
         o.act = ACT_RELU;
-        QA_TRY(conv(c, cat, 3 * C, B, nf, h->ecapa_out, latent, 1536, nf, o));
+        QA_TRY(conv_op(c, cat, 3 * C, B, nf, h->ecapa_out, latent, 1536, nf, o));
     }
     c.tap("ecapa.latent", latent, rows * 1536);
     // ---- PerceiverResampler [B, token_num, D]
@@ -784,7 +676,7 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     float* hh = c.arena.alloc<float>((size_t)lrows * 2 * h->ff);
     float* gg = c.arena.alloc<float>((size_t)lrows * h->ffp);
     float* pout = c.arena.alloc<float>((size_t)lrows * D);
-    QA_TRY(linear(c, latent, rows, h->proj_context, xc));
+    QA_TRY(linear_op(c, latent, rows, h->proj_context, xc));
     if (!c.dry) {
         QA_TRY(launch_perceiver_ctx(h->latents, 0, xc, ctx, B, nl, nf, D, c.stream));        // cat(latents, x)
         QA_TRY(launch_perceiver_ctx(h->latents, 0, nullptr, lat, B, nl, 0, D, c.stream));    // latents, broadcast over the batch
@@ -792,15 +684,15 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     for (size_t li = 0; li < h->perceiver.size(); ++li) {
         const PerceiverLayerW& lw = h->perceiver[li];
         if (li > 0 && !c.dry) QA_TRY(launch_perceiver_ctx(lat, (int64_t)nl * D, nullptr, ctx, B, nl, nf, D, c.stream));
-        QA_TRY(linear(c, lat, lrows, lw.to_q, q));
-        QA_TRY(linear(c, ctx, (int64_t)B * nk, lw.to_kv, kv));
+        QA_TRY(linear_op(c, lat, lrows, lw.to_q, q));
+        QA_TRY(linear_op(c, ctx, (int64_t)B * nk, lw.to_kv, kv));
         if (!c.dry)
             QA_TRY(launch_attention(q, inner, kv, kv + inner, 2 * inner, att, inner, B, nl, nk, (int64_t)nk * 2 * inner, sp.perceiver_heads,
                                     sp.perceiver_dim_head, 1.f / std::sqrt((float)sp.perceiver_dim_head), 0, c.stream));
-        QA_TRY(linear(c, att, lrows, lw.to_out, lat, ACT_NONE, lat));
-        QA_TRY(linear(c, lat, lrows, lw.ff1, hh));
+        QA_TRY(linear_op(c, att, lrows, lw.to_out, lat, epi(ACT_NONE, lat)));
+        QA_TRY(linear_op(c, lat, lrows, lw.ff1, hh));
         if (!c.dry) QA_TRY(launch_geglu(hh, h->ff, gg, h->ffp, lrows, c.stream));
-        QA_TRY(linear(c, gg, lrows, lw.ff2, lat, ACT_NONE, lat));
+        QA_TRY(linear_op(c, gg, lrows, lw.ff2, lat, epi(ACT_NONE, lat)));
     }
     if (!c.dry) QA_TRY(launch_l2norm_scale(lat, h->norm_gamma, pout, lrows, D, std::sqrt((float)D), c.stream));
     c.tap("perceiver.out", pout, lrows * D);
@@ -811,46 +703,12 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     return QA_OK;
 }
 
-// plan (arena peak), grow the workspace, run - the pattern of qa_bicodec_detokenize
-template <class G>
-int run_enc(qa_bicodec_enc* h, void* stream, G&& graph) {
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(graph(c));
-    if (c.arena.peak() > h->ws_cap) {
-        if (h->ws) QA_HIP(hipFree(h->ws));
-        h->ws = nullptr;
-        h->ws_cap = 0;
-        const size_t cap = c.arena.peak() + c.arena.peak() / 8;
-        QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), cap));
-        h->ws_cap = cap;
-    }
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return graph(c);
-}
-
 int check_global_shape(const qa_bicodec_enc* h, int64_t B, int64_t T, int64_t ref_len) {
     QA_REQUIRE(B > 0 && T > 0, "qa_bicodec_get_global_tokens: wav is [%lld, %lld]", (long long)B, (long long)T);
     QA_REQUIRE(ref_len > h->spec.n_fft / 2, "qa_bicodec_get_global_tokens: a reference clip of %lld samples is too short for the centred "
                "STFT's reflect padding (n_fft / 2 = %d)", (long long)ref_len, h->spec.n_fft / 2);
     QA_REQUIRE(B * (ref_len / h->spec.hop_length + 2) * 3 * h->spec.ecapa_channels < (1LL << 31) && B * T < (1LL << 40),
                "qa_bicodec_get_global_tokens: batch too large (split it)");
-    return QA_OK;
-}
-
-int ensure_ws(qa_bicodec* h, size_t bytes) {
-    if (bytes <= h->ws_cap) return QA_OK;
-    if (h->ws) QA_HIP(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_cap = 0;
-    const size_t cap = bytes + bytes / 8;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), cap));
-    h->ws_cap = cap;
     return QA_OK;
 }
 
@@ -868,24 +726,12 @@ int qa_bicodec_create(qa_bicodec** out, const qa_bicodec_spec* spec, const qa_te
     std::unique_ptr<qa_bicodec> h(new qa_bicodec());
     h->spec = *spec;
     h->device = device;
-    HostTable tab(tensors, n_tensors);
-    const int st = build(h.get(), tab);
-    if (st != QA_OK) {
-        h->store.release();
-        return st;
-    }
+    QA_TRY(build(h.get(), HostTable(tensors, n_tensors)));
     *out = h.release();
     return QA_OK;
 }
 
-void qa_bicodec_destroy(qa_bicodec* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    h->store.release();
-    if (h->ws) (void)hipFree(h->ws);
-    delete h;
-}
+void qa_bicodec_destroy(qa_bicodec* h) { destroy_handle(h); }
 
 int64_t qa_bicodec_hop(const qa_bicodec* h) { return h ? h->hop : QA_ERR_INVALID; }
 
@@ -897,17 +743,9 @@ int qa_bicodec_detokenize(qa_bicodec* h, const int64_t* semantic_tokens, const i
     }
     QA_REQUIRE(B > 0 && T > 0, "qa_bicodec_detokenize: tokens are [%lld, %lld]", (long long)B, (long long)T);
     QA_REQUIRE(B * T * (int64_t)h->hop * 32 < (1LL << 31), "qa_bicodec_detokenize: batch too large (split it)");
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(detokenize_graph(h, c, (const long long*)semantic_tokens, (const long long*)global_tokens, (int)B, (int)T, wav_out));
-    QA_TRY(ensure_ws(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return detokenize_graph(h, c, (const long long*)semantic_tokens, (const long long*)global_tokens, (int)B, (int)T, wav_out);
+    return run_planned(*h, stream, [&] {
+        return detokenize_graph(h, h->ctx, (const long long*)semantic_tokens, (const long long*)global_tokens, (int)B, (int)T, wav_out);
+    });
 }
 
 int qa_bicodec_enc_create(qa_bicodec_enc** out, const qa_bicodec_enc_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
@@ -920,24 +758,12 @@ int qa_bicodec_enc_create(qa_bicodec_enc** out, const qa_bicodec_enc_spec* spec,
     std::unique_ptr<qa_bicodec_enc> h(new qa_bicodec_enc());
     h->spec = *spec;
     h->device = device;
-    HostTable tab(tensors, n_tensors);
-    const int st = build_encoder(h.get(), tab);
-    if (st != QA_OK) {
-        h->store.release();
-        return st;
-    }
+    QA_TRY(build_encoder(h.get(), HostTable(tensors, n_tensors)));
     *out = h.release();
     return QA_OK;
 }
 
-void qa_bicodec_enc_destroy(qa_bicodec_enc* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    h->store.release();
-    if (h->ws) (void)hipFree(h->ws);
-    delete h;
-}
+void qa_bicodec_enc_destroy(qa_bicodec_enc* h) { destroy_handle(h); }
 
 int qa_bicodec_get_semantic_tokens(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, int64_t* semantic_out, void* stream) {
     if (!h || !feat || !semantic_out) {
@@ -947,7 +773,7 @@ int qa_bicodec_get_semantic_tokens(qa_bicodec_enc* h, const float* feat, int64_t
     QA_REQUIRE(B > 0 && N > 0, "qa_bicodec_get_semantic_tokens: feat is [%lld, %lld, C]", (long long)B, (long long)N);
     QA_REQUIRE(B * N * (int64_t)std::max(h->spec.vocos_inter, h->spec.input_channels) < (1LL << 31),
                "qa_bicodec_get_semantic_tokens: batch too large (split it)");
-    return run_enc(h, stream, [&](Ctx& c) { return semantic_graph(h, c, feat, (int)B, (int)N, (long long*)semantic_out); });
+    return run_planned(*h, stream, [&] { return semantic_graph(h, h->ctx, feat, (int)B, (int)N, (long long*)semantic_out); });
 }
 
 int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, int64_t ref_len, int32_t* global_out, void* stream) {
@@ -957,7 +783,7 @@ int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B,
     }
     if (ref_len <= 0) ref_len = T;
     QA_TRY(check_global_shape(h, B, T, ref_len));
-    return run_enc(h, stream, [&](Ctx& c) { return global_graph(h, c, wav, (int)B, T, ref_len, (int*)global_out); });
+    return run_planned(*h, stream, [&] { return global_graph(h, h->ctx, wav, (int)B, T, ref_len, (int*)global_out); });
 }
 
 int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref, int64_t ref_len,
@@ -970,33 +796,10 @@ int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t
     return qa_bicodec_get_global_tokens(h, ref_wav, B, T_ref, ref_len, global_out, stream);
 }
 
-int qa_bicodec_enc_enable_taps(qa_bicodec_enc* h, int on) {
-    if (!h) {
-        set_error("qa_bicodec_enc_enable_taps: null handle");
-        return QA_ERR_INVALID;
-    }
-    h->ctx.capture = on != 0;
-    return QA_OK;
-}
+int qa_bicodec_enc_enable_taps(qa_bicodec_enc* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_bicodec_enc_enable_taps", on); }
 
 int64_t qa_bicodec_enc_tap(qa_bicodec_enc* h, const char* name, float* dst, int64_t cap, void* stream) {
-    if (!h || !name) {
-        set_error("qa_bicodec_enc_tap: null argument");
-        return QA_ERR_INVALID;
-    }
-    auto it = h->ctx.taps.find(name);
-    if (it == h->ctx.taps.end()) {
-        set_error("qa_bicodec_enc_tap: no intermediate named '%s' in the last call", name);
-        return QA_ERR_MISSING;
-    }
-    if (dst) {
-        if (cap < it->second.numel) {
-            set_error("qa_bicodec_enc_tap: '%s' has %lld elements, capacity %lld", name, (long long)it->second.numel, (long long)cap);
-            return QA_ERR_INVALID;
-        }
-        QA_HIP(hipMemcpyAsync(dst, it->second.ptr, sizeof(float) * it->second.numel, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    }
-    return it->second.numel;
+    return tap_read(h ? &h->ctx : nullptr, "qa_bicodec_enc_tap", name, dst, cap, stream);
 }
 
 int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float eps, void* stream) {
@@ -1009,33 +812,10 @@ int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float e
     return launch_wav_normalize(wav, out, (int)B, (long long)T, eps, static_cast<hipStream_t>(stream));
 }
 
-int qa_bicodec_enable_taps(qa_bicodec* h, int on) {
-    if (!h) {
-        set_error("qa_bicodec_enable_taps: null handle");
-        return QA_ERR_INVALID;
-    }
-    h->ctx.capture = on != 0;
-    return QA_OK;
-}
+int qa_bicodec_enable_taps(qa_bicodec* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_bicodec_enable_taps", on); }
 
 int64_t qa_bicodec_tap(qa_bicodec* h, const char* name, float* dst, int64_t cap, void* stream) {
-    if (!h || !name) {
-        set_error("qa_bicodec_tap: null argument");
-        return QA_ERR_INVALID;
-    }
-    auto it = h->ctx.taps.find(name);
-    if (it == h->ctx.taps.end()) {
-        set_error("qa_bicodec_tap: no intermediate named '%s' in the last call", name);
-        return QA_ERR_MISSING;
-    }
-    if (dst) {
-        if (cap < it->second.numel) {
-            set_error("qa_bicodec_tap: '%s' has %lld elements, capacity %lld", name, (long long)it->second.numel, (long long)cap);
-            return QA_ERR_INVALID;
-        }
-        QA_HIP(hipMemcpyAsync(dst, it->second.ptr, sizeof(float) * it->second.numel, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    }
-    return it->second.numel;
+    return tap_read(h ? &h->ctx : nullptr, "qa_bicodec_tap", name, dst, cap, stream);
 }
 
 }  // extern "C"

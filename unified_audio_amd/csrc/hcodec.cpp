@@ -66,10 +66,8 @@ constexpr int MAX_POS = 8192;
 
 using namespace qa;
 
-struct qa_hcodec {
+struct qa_hcodec : Handle {
     qa_hcodec_spec spec{};
-    int device = 0;
-    WeightStore store;
     // encoder
     const float *conv0_w = nullptr, *conv0_b = nullptr;
     std::vector<ResBlockW> res;
@@ -122,26 +120,27 @@ struct qa_hcodec {
         WeightStore store;
         ConvW conv1, conv2;
         std::vector<SemDecBlock> blocks;
-        ~SemDec() { store.release(); }
     };
     std::unique_ptr<SemDec> sdec;
-    // workspace
-    char* ws = nullptr;
-    size_t ws_cap = 0;
-    Ctx ctx;
+    ~qa_hcodec() {
+        if (e2_dev) (void)hipFree(e2_dev);
+        if (host_sync) (void)hipHostFree(host_sync);
+        if (side) (void)hipStreamDestroy(side);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+    }
 };
 
 // One StreamingTransformer with its optional streaming state (mimi/transformer.py:605-698)
-struct qa_mimi {
+struct qa_mimi : Handle {
     qa_mimi_spec spec{};
-    int device = 0;
-    WeightStore store;
     MimiW w;
     MimiStream st;       // st.B > 0: inside `with model.streaming(B)`
     float* ring = nullptr;  // backing store of the ring caches
-    char* ws = nullptr;
-    size_t ws_cap = 0;
-    Ctx ctx;
+    ~qa_mimi() {
+        if (ring) (void)hipFree(ring);
+        if (st.rope_win) (void)hipFree(st.rope_win);
+    }
 };
 
 namespace qa {
@@ -165,96 +164,8 @@ void mimi_rope_table(int hd, int pos0, int n, std::vector<float>* cs) {
     }
 }
 
-struct Folder {
-    const HostTable& tab;
-    WeightStore& store;
-    bool ok = true;
-    int status = QA_OK;
-
-    const float* need(const std::string& name, int64_t numel) {
-        const float* p = tab.get(name, numel);
-        if (!p) {
-            ok = false;
-            status = QA_ERR_MISSING;
-        }
-        return p;
-    }
-    size_t vec(const std::string& name, int64_t n) {
-        const float* p = need(name, n);
-        if (!p) return 0;
-        return store.add(p, n);
-    }
-    // Conv weight [N][C_in][k] (optionally weight-normed: prefix.weight_g / weight_v) -> [Np][k][Cp], bias -> [Np]
-    // returns offsets through the out params (pointers are resolved after upload)
-    void conv(const std::string& p, int N, int C_in, int k, bool wn, bool bias, int Np, int Cp, size_t* w_off,
-              size_t* b_off) {
-        std::vector<float> w((size_t)Np * k * Cp, 0.f);
-        const int64_t numel = (int64_t)N * C_in * k;
-        const float* v = need(p + (wn ? ".weight_v" : ".weight"), numel);
-        const float* g = wn ? need(p + ".weight_g", N) : nullptr;
-        if (v && (!wn || g)) {
-            for (int n = 0; n < N; ++n) {
-                float scale = 1.f;
-                if (wn) {
-                    // torch._weight_norm: w = v * (g / ||v||_2), norm over (C_in, k), computed in fp32
-                    double ss = 0.0;
-                    for (int64_t i = 0; i < (int64_t)C_in * k; ++i) {
-                        const float a = v[(int64_t)n * C_in * k + i];
-                        ss += (double)a * a;
-                    }
-                    scale = g[n] / (float)std::sqrt(ss);
-                }
-                for (int c = 0; c < C_in; ++c)
-                    for (int j = 0; j < k; ++j)
-                        w[((size_t)n * k + j) * Cp + c] = v[((int64_t)n * C_in + c) * k + j] * scale;
-            }
-        }
-        *w_off = store.add(w);
-        if (bias) {
-            std::vector<float> b(Np, 0.f);
-            const float* bp = need(p + ".bias", N);
-            if (bp) std::memcpy(b.data(), bp, sizeof(float) * N);
-            *b_off = store.add(b);
-        }
-    }
-};
-
-struct PendingConv {
-    ConvW* dst;
-    size_t w_off, b_off;
-    bool has_bias;
-};
-
-struct Builder {
-    Folder f;
-    std::vector<PendingConv> pend;
-    std::vector<std::pair<const float**, size_t>> pend_vec;
-
-    void conv(ConvW* dst, const std::string& p, int N, int C_in, int k, bool wn, bool bias, int Np = -1, int Cp = -1) {
-        if (Np < 0) Np = N;
-        if (Cp < 0) Cp = C_in;
-        PendingConv pc{dst, 0, 0, bias};
-        f.conv(p, N, C_in, k, wn, bias, Np, Cp, &pc.w_off, &pc.b_off);
-        dst->N = Np;
-        dst->C_in = Cp;
-        dst->ksize = k;
-        dst->algo_n = N;
-        dst->algo_cin = C_in;
-        pend.push_back(pc);
-    }
-    void vec(const float** dst, const std::string& name, int64_t n) { pend_vec.push_back({dst, f.vec(name, n)}); }
-    void raw(const float** dst, const std::vector<float>& v) { pend_vec.push_back({dst, f.store.add(v)}); }
-    void resolve() {
-        for (auto& pc : pend) {
-            pc.dst->w = f.store.ptr(pc.w_off);
-            pc.dst->b = pc.has_bias ? f.store.ptr(pc.b_off) : nullptr;
-        }
-        for (auto& pv : pend_vec) *pv.first = f.store.ptr(pv.second);
-    }
-};
-
 // rows of an LSTM matrix / bias go from PyTorch's gate-major order (i,f,g,o blocks of d) to (unit, gate)
-void build_transformer(Builder& b, TransformerW* tw, const std::string& p, int d, int n_layers, int heads, int inter = 0) {
+void build_transformer(Loader& b, TransformerW* tw, const std::string& p, int d, int n_layers, int heads, int inter = 0) {
     if (inter <= 0) inter = 4 * d;
     tw->d = d;
     tw->heads = heads;
@@ -266,10 +177,10 @@ void build_transformer(Builder& b, TransformerW* tw, const std::string& p, int d
         const std::string ap = lp + ".self_attn";
         b.vec(&L.ln1, lp + ".input_layernorm.weight", d);
         b.vec(&L.ln2, lp + ".post_attention_layernorm.weight", d);
-        const float* wih = b.f.need(ap + ".rnn.weight_ih_l0", (int64_t)4 * d * d);
-        const float* whh = b.f.need(ap + ".rnn.weight_hh_l0", (int64_t)4 * d * d);
-        const float* bih = b.f.need(ap + ".rnn.bias_ih_l0", 4 * d);
-        const float* bhh = b.f.need(ap + ".rnn.bias_hh_l0", 4 * d);
+        const float* wih = b.need(ap + ".rnn.weight_ih_l0", (int64_t)4 * d * d);
+        const float* whh = b.need(ap + ".rnn.weight_hh_l0", (int64_t)4 * d * d);
+        const float* bih = b.need(ap + ".rnn.bias_ih_l0", 4 * d);
+        const float* bhh = b.need(ap + ".rnn.bias_hh_l0", 4 * d);
         std::vector<float> wi((size_t)4 * d * d, 0.f), wh((size_t)4 * d * d, 0.f), bb((size_t)4 * d, 0.f);
         if (wih && whh && bih && bhh) {
             for (int u = 0; u < d; ++u)
@@ -288,8 +199,8 @@ void build_transformer(Builder& b, TransformerW* tw, const std::string& p, int d
         std::vector<float> wq((size_t)3 * d * d, 0.f), bq((size_t)3 * d, 0.f);
         const char* names[3] = {".q_proj", ".k_proj", ".v_proj"};
         for (int i = 0; i < 3; ++i) {
-            const float* w = b.f.need(ap + names[i] + ".weight", (int64_t)d * d);
-            const float* bi = b.f.need(ap + names[i] + ".bias", d);
+            const float* w = b.need(ap + names[i] + ".weight", (int64_t)d * d);
+            const float* bi = b.need(ap + names[i] + ".bias", d);
             if (w) std::memcpy(&wq[(size_t)i * d * d], w, sizeof(float) * d * d);
             if (bi) std::memcpy(&bq[(size_t)i * d], bi, sizeof(float) * d);
         }
@@ -320,7 +231,7 @@ void build_transformer(Builder& b, TransformerW* tw, const std::string& p, int d
     b.raw(&tw->rope, cs);
 }
 
-void build_mimi(Builder& b, MimiW* mw, const std::string& p, int d, int n_layers, int heads, int ff, int causal = 0,
+void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers, int heads, int ff, int causal = 0,
                 int context = 0) {
     mw->d = d;
     mw->heads = heads;
@@ -353,39 +264,15 @@ void build_mimi(Builder& b, MimiW* mw, const std::string& p, int d, int n_layers
 
 // ---------------------------------------------------------------- graph helpers
 
-int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, float* y, int64_t ldy, int T_out,
-            int stride, int pad_left, int pad_right, int pad_mode, int prologue, int act, const float* gamma,
-            const float* res, int64_t ldr, const float* gate, int post_act, int in_rep = 1, const float* rope = nullptr,
-            int rope_n = 0, int rope_hd = 0, int rope_T = 0, int rope_pos0 = 0) {
-    if (c.dry) return QA_OK;
-    qa_conv_args a{};
-    a.x = x; a.w = w.w; a.bias = w.b; a.gamma = gamma; a.residual = res; a.gate = gate; a.y = y;
-    a.B = B; a.T_in = T_in; a.C_in = w.C_in; a.T_out = T_out; a.N = w.N;
-    a.ldx = ldx; a.ldy = ldy; a.ldr = ldr; a.ldg = w.N;
-    a.ksize = w.ksize; a.stride = stride; a.pad_left = pad_left; a.pad_right = pad_right; a.pad_mode = pad_mode;
-    a.prologue = prologue; a.act = act; a.post_act = post_act;
-    a.in_rep = in_rep;
-    ConvParams p;
-    QA_TRY(conv_params_from_args(a, &p));
-    p.algo_n = w.algo_n;
-    p.algo_k = w.algo_cin ? w.algo_cin * w.ksize : 0;
-    p.rope = rope; p.rope_n = rope_n; p.rope_hd = rope_hd; p.rope_T = rope_T; p.rope_pos0 = rope_pos0;
-    return launch_conv_gemm(p, c.stream);
-}
-
-// plain linear over `rows` rows
-int linear_op(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, int act = ACT_NONE,
-              const float* res = nullptr, const float* gate = nullptr, const float* gamma = nullptr) {
-    return conv_op(c, x, w.C_in, 1, (int)rows, w, y, w.N, (int)rows, 1, 0, 0, PAD_ZERO, ACT_NONE, act, gamma, res, w.N,
-                   gate, ACT_NONE);
-}
-
 // "same" zero-padded stride-1 conv (vq/conv.py:33-56, semantic_module.py:28-31)
 int conv_same(Ctx& c, const float* x, int B, int T, const ConvW& w, float* y, int prologue = ACT_NONE,
               int act = ACT_NONE, const float* res = nullptr, bool causal = false) {
     const int pad = (w.ksize - 1) / 2;
-    return conv_op(c, x, w.C_in, B, T, w, y, w.N, T, 1, causal ? w.ksize - 1 : pad, causal ? 0 : pad, PAD_ZERO, prologue, act,
-                   nullptr, res, w.N, nullptr, ACT_NONE);
+    ConvOpt o = conv_geom(1, causal ? w.ksize - 1 : pad, causal ? 0 : pad);
+    o.prologue = prologue;
+    o.act = act;
+    o.res = res;
+    return conv_op(c, x, w.C_in, B, T, w, y, w.N, T, o);
 }
 
 // SConv1d geometry (encoder_modules/conv.py:195-211, non-causal): returns T_out and the paddings
@@ -433,12 +320,12 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const
         RUN(launch_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd,
                              1.0f / std::sqrt((float)hd), causal ? 1 : 0, c.stream));
         c.tap(lp + ".att", att, rows * d);
-        RUN(linear_op(c, att, rows, L.o, x, ACT_NONE, x));
+        RUN(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_attn", x, rows * d);
         RUN(launch_rmsnorm(x, L.ln2, hn, rows, d, 1e-6f, c.stream));
         RUN(linear_op(c, hn, rows, L.w1, big));
-        RUN(linear_op(c, hn, rows, L.w3, big2, ACT_NONE, nullptr, big));
-        RUN(linear_op(c, big2, rows, L.w2, x, ACT_NONE, x));
+        RUN(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
+        RUN(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_mlp", x, rows * d);
     }
 #undef RUN
@@ -470,8 +357,9 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
     const float scale = 1.0f / std::sqrt((float)hd);
     QA_TRY(launch_layernorm(x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f, c.stream));
     // fused QKV projection with the interleaved-pair RoPE of q and k applied in the GEMM epilogue (one launch less per layer)
-    QA_TRY(conv_op(c, t.hn, d, 1, (int)rows, L.in_proj, t.qkv, 3 * d, (int)rows, 1, 0, 0, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr,
-                   3 * d, nullptr, ACT_NONE, 1, rope, 2 * d, hd, N, rope_pos0));
+    ConvOpt qo;
+    qo.rope = rope; qo.rope_n = 2 * d; qo.rope_hd = hd; qo.rope_T = N; qo.rope_pos0 = rope_pos0;
+    QA_TRY(linear_op(c, t.hn, rows, L.in_proj, t.qkv, qo));
     if (st) {
         // RingKVCache.complete(): the chunk's keys / values are written first, then every query attends over the ring
         QA_TRY(launch_ring_append(t.qkv + d, t.qkv + 2 * d, 3 * d, st->kc[li], st->vc[li], B, N, d, st->cap, pos0, c.stream));
@@ -481,10 +369,10 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
         QA_TRY(launch_attention(t.qkv, 3 * d, t.qkv + d, t.qkv + 2 * d, 3 * d, t.att, d, B, N, N, (long long)N * 3 * d, H, hd, scale,
                                 mw.causal, c.stream, nullptr, nullptr, 0, mw.causal ? mw.context : 0));
     }
-    QA_TRY(linear_op(c, t.att, rows, L.out_proj, x, ACT_NONE, x, nullptr, L.ls1));
+    QA_TRY(linear_op(c, t.att, rows, L.out_proj, x, epi(ACT_NONE, x, L.ls1)));
     QA_TRY(launch_layernorm(x, L.n2w, L.n2b, t.hn, rows, d, 1e-5f, c.stream));
-    QA_TRY(linear_op(c, t.hn, rows, L.lin1, t.u, ACT_GELU));
-    return linear_op(c, t.u, rows, L.lin2, x, ACT_NONE, x, nullptr, L.ls2);
+    QA_TRY(linear_op(c, t.hn, rows, L.lin1, t.u, epi(ACT_GELU)));
+    return linear_op(c, t.u, rows, L.lin2, x, epi(ACT_NONE, x, L.ls2));
 }
 int mimi_op(Ctx& c, const MimiW& mw, float* x, int B, int N) {
     QA_REQUIRE(N <= MAX_POS, "mimi transformer: sequence of %d tokens exceeds %d", N, MAX_POS);
@@ -544,8 +432,8 @@ int convnext_op(Ctx& c, const ConvNeXtW& w, float* x, float* t1, float* u, int B
     const int64_t rows = (int64_t)B * T;
     if (c.dry) return QA_OK;
     QA_TRY(launch_dwconv(x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, d, 7, 1e-6f, c.stream, zpad_left(7, causal)));
-    QA_TRY(linear_op(c, t1, rows, w.pw1, u, ACT_GELU));
-    return linear_op(c, u, rows, w.pw2, x, ACT_NONE, x, nullptr, w.gamma);
+    QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
+    return linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma));
 }
 
 // H-Codec 2.0 CodecEncoder.forward (HCodec-2.0/vq/codec_encoder.py:62-79): wav [B, T] -> emb [B, T / (hop*stride), code_dim]
@@ -557,8 +445,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     // STFT as an implicit GEMM: the signal is a [B, T / blk, blk] "channel-last" tensor, a frame is 4 consecutive blocks
     // starting one block before 2 t (zero padded), the filter bank is the windowed DFT basis (re | im)
     float* ri = c.arena.alloc<float>(rows * 2 * nb);
-    QA_TRY(conv_op(c, wav, blk, B, T / blk, h->stft_basis, ri, 2 * nb, N50, 2, 1, 1, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr,
-                   0, nullptr, ACT_NONE));
+    QA_TRY(conv_op(c, wav, blk, B, T / blk, h->stft_basis, ri, 2 * nb, N50, conv_geom(2, 1, 1)));
     float* feat = c.arena.alloc<float>(rows * h->stft_ld);
     if (!c.dry) QA_TRY(launch_stft_post(ri, feat, rows, nb, 2 * nb, h->stft_ld, c.stream));
     c.tap("enc.stft", feat, rows * h->stft_ld);
@@ -567,8 +454,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     float* u = c.arena.alloc<float>(rows * sp.enc_inter);
     // vq/conv.py Conv1d (:39-47): zero padding (k - stride, 0) in the causal variant, (k / 2, k / 2) otherwise
     const bool cz = sp.causal != 0;
-    QA_TRY(conv_op(c, feat, h->stft_ld, B, N50, h->enc_embed, t1, d, N50, 1, cz ? 2 : 1, cz ? 0 : 1, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr,
-                   nullptr, 0, nullptr, ACT_NONE));
+    QA_TRY(conv_op(c, feat, h->stft_ld, B, N50, h->enc_embed, t1, d, N50, conv_geom(1, cz ? 2 : 1, cz ? 0 : 1)));
     if (!c.dry) QA_TRY(launch_layernorm(t1, h->enc_norm_w, h->enc_norm_b, x, rows, d, 1e-6f, c.stream));
     for (const ConvNeXtW& w : h->enc_cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz));
     c.tap("enc.prior", x, rows * d);
@@ -578,8 +464,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     const int pl = cz ? k - st : k / 2, pr = cz ? 0 : k / 2;
     const int Nf = (N50 + pl + pr - k) / st + 1;
     float* emb = c.arena.alloc<float>((size_t)B * Nf * sp.code_dim);
-    QA_TRY(conv_op(c, t1, d, B, N50, h->enc_out20, emb, sp.code_dim, Nf, st, pl, pr, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr,
-                   0, nullptr, ACT_NONE));
+    QA_TRY(conv_op(c, t1, d, B, N50, h->enc_out20, emb, sp.code_dim, Nf, conv_geom(st, pl, pr)));
     *emb_out = emb;
     *n50_out = N50;
     *nf_out = Nf;
@@ -617,8 +502,7 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
             const int k = blk.conv.ksize, pad = (k - 1) / 2;
             const int To = (Ls + 2 * pad - k) / blk.stride + 1;
             float* y = c.arena.alloc<float>((size_t)B * To * SC);
-            QA_TRY(conv_op(c, s, SC, B, Ls, blk.conv, y, SC, To, blk.stride, pad, pad, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr,
-                           nullptr, 0, nullptr, ACT_NONE));
+            QA_TRY(conv_op(c, s, SC, B, Ls, blk.conv, y, SC, To, conv_geom(blk.stride, pad, pad)));
             s = y;
             Ls = To;
         }
@@ -648,21 +532,24 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
         } else {
         float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
         // shortcut_1x1(x)
-        QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, 1, 0, 0, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr, 0, nullptr,
-                       ACT_NONE));
+        QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));
         // ELU(k3(ELU(x)))  (reflect pad 1,1)
-        QA_TRY(conv_op(c, x, C, B, L, rb.k3, hh, rb.k3.N, L, 1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT, ACT_ELU, ACT_ELU, nullptr,
-                       nullptr, 0, nullptr, ACT_NONE));
+        ConvOpt k3 = conv_geom(1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT);
+        k3.prologue = ACT_ELU;
+        k3.act = ACT_ELU;
+        QA_TRY(conv_op(c, x, C, B, L, rb.k3, hh, rb.k3.N, L, k3));
         // ELU(shortcut + 1x1(.))  -> the activation in front of the down-sampling conv is fused here
-        QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, 1, 0, 0, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, sc, C,
-                       nullptr, ACT_ELU));
+        ConvOpt pw;
+        pw.res = sc;
+        pw.ldr = C;
+        pw.post_act = ACT_ELU;
+        QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, pw));
         }
         const SGeom g = sconv_geom(L, 2 * r, r, cz);
         // the strided conv writes below the mark: allocate its output after releasing the block temporaries is not
         // possible (sc is its input), so the output is carved above them and compacted by pointer swap.
         float* y = c.arena.alloc<float>((size_t)B * g.T_out * 2 * C);
-        QA_TRY(conv_op(c, sc, C, B, L, h->down[i], y, 2 * C, g.T_out, r, g.left, g.right, PAD_REFLECT, ACT_NONE, ACT_NONE,
-                       nullptr, nullptr, 0, nullptr, ACT_NONE));
+        QA_TRY(conv_op(c, sc, C, B, L, h->down[i], y, 2 * C, g.T_out, conv_geom(r, g.left, g.right, PAD_REFLECT)));
         (void)mark;
         x = y;
         L = g.T_out;
@@ -676,8 +563,9 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
     const SGeom g = sconv_geom(N50, 4, 2, cz);
     N25 = g.T_out;
     emb = c.arena.alloc<float>((size_t)B * N25 * sp.code_dim);
-    QA_TRY(conv_op(c, x, C, B, N50, h->enc_out, emb, sp.code_dim, N25, 2, g.left, g.right, PAD_REFLECT, ACT_ELU, ACT_NONE,
-                   nullptr, nullptr, 0, nullptr, ACT_NONE));
+    ConvOpt eo = conv_geom(2, g.left, g.right, PAD_REFLECT);
+    eo.prologue = ACT_ELU;
+    QA_TRY(conv_op(c, x, C, B, N50, h->enc_out, emb, sp.code_dim, N25, eo));
     }
     c.tap("enc.emb", emb, (int64_t)B * N25 * sp.code_dim);
     QA_TRY(semantic_branch());
@@ -746,8 +634,9 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
         // H-Codec 2.0 (codec_decoder.py:30-31,64-65): x.repeat_interleave(s) -> Conv1d k = s + 1, "same" zero padding.  The
         // repetition is folded into the implicit-GEMM gather (frame r reads row r / s), nothing is materialised.
         const int k = h->dec_embed20.ksize;
-        QA_TRY(conv_op(c, cat, 2 * sp.code_dim, B, N, h->dec_embed20, x, d, N50, 1, cz ? k - 1 : k / 2, cz ? 0 : k / 2, PAD_ZERO, ACT_NONE,
-                       ACT_NONE, nullptr, nullptr, 0, nullptr, ACT_NONE, sp.frame_stride));
+        ConvOpt o = conv_geom(1, cz ? k - 1 : k / 2, cz ? 0 : k / 2);
+        o.in_rep = sp.frame_stride;
+        QA_TRY(conv_op(c, cat, 2 * sp.code_dim, B, N, h->dec_embed20, x, d, N50, o));
     } else {
         float* up = c.arena.alloc<float>(rows25 * 2 * d);
         QA_TRY(linear_op(c, cat, rows25, h->up, up));
@@ -876,7 +765,7 @@ int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int
     const qa_semantic_decoder_spec& sp = sd.spec;
     int L = N, C = sp.channels;
     float* x = c.arena.alloc<float>((size_t)B * L * C);
-    QA_TRY(conv_op(c, z, ldz, B, L, sd.conv1, x, C, L, 1, 1, 1, PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr, 0, nullptr, ACT_NONE));
+    QA_TRY(conv_op(c, z, ldz, B, L, sd.conv1, x, C, L, conv_geom(1, 1, 1)));
     for (const auto& blk : sd.blocks) {
         const int s = blk.stride, co = blk.c_out, To = L * s;
         float* y = c.arena.alloc<float>((size_t)B * To * co);
@@ -885,8 +774,8 @@ int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int
         } else {  // ConvTranspose1d: phase phi writes rows q * s + phi (row stride s * co)
             for (int phi = 0; phi < s; ++phi) {
                 const ConvW& w = blk.phase[phi];
-                QA_TRY(conv_op(c, x, C, B, L, w, y + (size_t)phi * co, (int64_t)s * co, L, 1, blk.pad_left[phi],
-                               w.ksize - 1 - blk.pad_left[phi], PAD_ZERO, ACT_NONE, ACT_NONE, nullptr, nullptr, 0, nullptr, ACT_NONE));
+                QA_TRY(conv_op(c, x, C, B, L, w, y + (size_t)phi * co, (int64_t)s * co, L,
+                               conv_geom(1, blk.pad_left[phi], w.ksize - 1 - blk.pad_left[phi])));
             }
         }
         float* t = c.arena.alloc<float>((size_t)B * To * co);
@@ -983,8 +872,8 @@ int build_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec& sp, con
         if (!tab.get(k.first, k.second)) return QA_ERR_MISSING;  // HostTable::get has set the error message
     std::unique_ptr<qa_hcodec::SemDec> sd(new qa_hcodec::SemDec());
     sd->spec = sp;
-    Builder b{Folder{tab, sd->store}};
-    b.conv(&sd->conv1, p + "conv1.conv", sp.channels, sp.code_dim, 3, false, false);
+    Loader b(tab, sd->store);
+    b.conv(&sd->conv1, p + "conv1.conv", sp.channels, sp.code_dim, 3, false);
     sd->blocks.resize(sp.n_blocks);
     for (int i = 0, ci = sp.channels; i < sp.n_blocks; ci = sp.widths[i], ++i) {
         auto& blk = sd->blocks[i];
@@ -993,9 +882,9 @@ int build_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec& sp, con
         blk.stride = s;
         blk.c_out = co;
         if (s == 1) {
-            b.conv(&blk.conv, bp + ".conv.conv", co, ci, 3, false, true);
+            b.conv(&blk.conv, bp + ".conv.conv", co, ci, 3);
         } else {  // weight [C_in][C_out][2 s], padding s / 2
-            const float* w = b.f.need(bp + ".conv.deconv.weight", (int64_t)ci * co * 2 * s);
+            const float* w = b.need(bp + ".conv.deconv.weight", (int64_t)ci * co * 2 * s);
             blk.phase.resize(s);
             blk.pad_left.resize(s);
             for (int phi = 0; phi < s; ++phi) {
@@ -1010,26 +899,13 @@ int build_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec& sp, con
         }
         for (int u = 0; u < 2; ++u) {
             const std::string up = bp + ".res_units." + std::to_string(u);
-            b.conv(&blk.u1[u], up + ".conv1.conv", co, co, 3, false, false);
-            b.conv(&blk.u2[u], up + ".conv2", co, co, 1, false, false);
+            b.conv(&blk.u1[u], up + ".conv1.conv", co, co, 3, false);
+            b.conv(&blk.u2[u], up + ".conv2", co, co, 1, false);
         }
     }
-    b.conv(&sd->conv2, p + "conv2.conv", sp.output_channels, sp.widths[sp.n_blocks - 1], 3, false, false);
-    if (!b.f.ok) return b.f.status;
-    QA_TRY(sd->store.upload());
-    b.resolve();
+    b.conv(&sd->conv2, p + "conv2.conv", sp.output_channels, sp.widths[sp.n_blocks - 1], 3, false);
+    QA_TRY(b.upload());
     *out = std::move(sd);
-    return QA_OK;
-}
-
-int ensure_workspace(qa_hcodec* h, size_t bytes) {
-    if (bytes <= h->ws_cap) return QA_OK;
-    if (h->ws) QA_HIP(hipFree(h->ws));  // synchronises with outstanding work
-    h->ws = nullptr;
-    h->ws_cap = 0;
-    const size_t cap = bytes + bytes / 8;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), cap));
-    h->ws_cap = cap;
     return QA_OK;
 }
 
@@ -1046,10 +922,10 @@ int build(qa_hcodec* h, const HostTable& tab) {
                "spec: channel counts must be multiples of 32");
     QA_REQUIRE(sp.n_fft % 2 == 0 && sp.hop > 0 && sp.n_fft > sp.hop && (sp.n_fft - sp.hop) % 2 == 0, "spec: bad STFT geometry");
     QA_REQUIRE(sp.dec_dim % sp.gn_groups == 0, "spec: dec_dim %% gn_groups != 0");
-    Builder b{Folder{tab, h->store}};
+    Loader b(tab, h->store);
     auto dw_fold_c = [&](const float** dst, const std::string& name, int k, int ch) {
         std::vector<float> w((size_t)k * ch, 0.f);
-        const float* p = b.f.need(name, (int64_t)ch * k);
+        const float* p = b.need(name, (int64_t)ch * k);
         if (p)
             for (int c = 0; c < ch; ++c)
                 for (int j = 0; j < k; ++j) w[(size_t)j * ch + c] = p[c * k + j];
@@ -1088,7 +964,7 @@ int build(qa_hcodec* h, const HostTable& tab) {
             b.raw(&h->stft_basis.w, basis);  // [2*nb][4][blk] == [2*nb][n_fft]
         }
         h->stft_ld = pad32(2 * nbins);
-        b.conv(&h->enc_embed, "encoder.embed.conv", de, 2 * nbins, 3, false, true, de, h->stft_ld);
+        b.conv(&h->enc_embed, "encoder.embed.conv", de, 2 * nbins, 3, true, 1.f, de, h->stft_ld);
         b.vec(&h->enc_norm_w, "encoder.norm.weight", de);
         b.vec(&h->enc_norm_b, "encoder.norm.bias", de);
         h->enc_cnx.resize(sp.enc_convnext_layers);
@@ -1096,26 +972,18 @@ int build(qa_hcodec* h, const HostTable& tab) {
         build_transformer(b, &h->enc_tr, "encoder.post_net.1", de, sp.enc_layers, de / 64, tr_inter(de));
         b.vec(&h->enc_fnorm_w, "encoder.final_layer_norm.weight", de);
         b.vec(&h->enc_fnorm_b, "encoder.final_layer_norm.bias", de);
-        b.conv(&h->enc_out20, "encoder.out.conv", sp.code_dim, de, 2 * sp.frame_stride + 1, false, true);
+        b.conv(&h->enc_out20, "encoder.out.conv", sp.code_dim, de, 2 * sp.frame_stride + 1);
     } else {
     // --- SEANet encoder (seanet.py:121-187)
     const std::string em = "encoder.model.";
-    {
-        std::vector<float> w0((size_t)7 * sp.n_filters), b0(sp.n_filters);
-        const float* v = b.f.need(em + "0.conv.conv.weight_v", (int64_t)sp.n_filters * 7);
-        const float* g = b.f.need(em + "0.conv.conv.weight_g", sp.n_filters);
-        const float* bi = b.f.need(em + "0.conv.conv.bias", sp.n_filters);
-        if (v && g && bi) {
-            for (int n = 0; n < sp.n_filters; ++n) {
-                double ss = 0;
-                for (int j = 0; j < 7; ++j) ss += (double)v[n * 7 + j] * v[n * 7 + j];
-                const float sc = g[n] / (float)std::sqrt(ss);
-                for (int j = 0; j < 7; ++j) w0[(size_t)j * sp.n_filters + n] = v[n * 7 + j] * sc;
-                b0[n] = bi[n];
-            }
-        }
+    b.wn = WN_FOLD;  // every SEANet convolution is weight-normed (seanet.py)
+    {   // conv0 (C_in = 1) as [7][n_filters] for launch_conv_in / launch_seanet_front
+        std::vector<float> w, w0((size_t)7 * sp.n_filters, 0.f);
+        if (b.weight(em + "0.conv.conv", sp.n_filters, 7, &w))
+            for (int n = 0; n < sp.n_filters; ++n)
+                for (int j = 0; j < 7; ++j) w0[(size_t)j * sp.n_filters + n] = w[n * 7 + j];
         b.raw(&h->conv0_w, w0);
-        b.raw(&h->conv0_b, b0);
+        b.vec(&h->conv0_b, em + "0.conv.conv.bias", sp.n_filters);
     }
     h->res.resize(sp.n_ratios);
     h->down.resize(sp.n_ratios);
@@ -1123,39 +991,40 @@ int build(qa_hcodec* h, const HostTable& tab) {
     for (int i = 0; i < sp.n_ratios; ++i) {
         const std::string rp = em + std::to_string(1 + 3 * i);
         const int hid = C / 2, hp = pad32(hid);
-        b.conv(&h->res[i].k3, rp + ".block.1.conv.conv", hid, C, 3, true, true, hp, C);
-        b.conv(&h->res[i].pw, rp + ".block.3.conv.conv", C, hid, 1, true, true, C, hp);
-        b.conv(&h->res[i].sc, rp + ".shortcut.conv.conv", C, C, 1, true, true);
-        b.conv(&h->down[i], em + std::to_string(3 + 3 * i) + ".conv.conv", 2 * C, C, 2 * sp.ratios[i], true, true);
+        b.conv(&h->res[i].k3, rp + ".block.1.conv.conv", hid, C, 3, true, 1.f, hp, C);
+        b.conv(&h->res[i].pw, rp + ".block.3.conv.conv", C, hid, 1, true, 1.f, C, hp);
+        b.conv(&h->res[i].sc, rp + ".shortcut.conv.conv", C, C, 1);
+        b.conv(&h->down[i], em + std::to_string(3 + 3 * i) + ".conv.conv", 2 * C, C, 2 * sp.ratios[i]);
         C *= 2;
     }
     QA_REQUIRE(C == sp.dimension, "spec: n_filters * 2^n_ratios = %d != dimension %d", C, sp.dimension);
     build_transformer(b, &h->enc_tr, em + std::to_string(3 * sp.n_ratios + 2), sp.dimension, sp.enc_layers, sp.enc_heads);
-    b.conv(&h->enc_out, em + std::to_string(3 * sp.n_ratios + 5) + ".conv.conv", sp.dimension, sp.dimension, 4, true, true);
+    b.conv(&h->enc_out, em + std::to_string(3 * sp.n_ratios + 5) + ".conv.conv", sp.dimension, sp.dimension, 4);
+    b.wn = WN_NONE;
     QA_REQUIRE(sp.code_dim == sp.dimension, "spec: code_dim must equal dimension");
     }
     // --- semantic encoder (semantic_module.py:157-201)
     const std::string se = "semantic_encoder.";
-    b.conv(&h->sem_in, se + "conv.conv", sp.sem_ch, sp.sem_in, 3, false, false);
+    b.conv(&h->sem_in, se + "conv.conv", sp.sem_ch, sp.sem_in, 3, false);
     h->sem_blocks.resize(sp.n_sem_strides);
     for (int i = 0; i < sp.n_sem_strides; ++i) {
         auto& blk = h->sem_blocks[i];
         const std::string bp = se + "conv_blocks." + std::to_string(i);
         for (int u = 0; u < 2; ++u) {
-            b.conv(&blk.u1[u], bp + ".res_units." + std::to_string(u) + ".conv1.conv", sp.sem_ch, sp.sem_ch, 3, false, false);
-            b.conv(&blk.u2[u], bp + ".res_units." + std::to_string(u) + ".conv2", sp.sem_ch, sp.sem_ch, 1, false, false);
+            b.conv(&blk.u1[u], bp + ".res_units." + std::to_string(u) + ".conv1.conv", sp.sem_ch, sp.sem_ch, 3, false);
+            b.conv(&blk.u2[u], bp + ".res_units." + std::to_string(u) + ".conv2", sp.sem_ch, sp.sem_ch, 1, false);
         }
         blk.stride = sp.sem_strides[i];
-        b.conv(&blk.conv, bp + ".conv.conv", sp.sem_ch, sp.sem_ch, blk.stride == 1 ? 3 : 2 * blk.stride, false, true);
+        b.conv(&blk.conv, bp + ".conv.conv", sp.sem_ch, sp.sem_ch, blk.stride == 1 ? 3 : 2 * blk.stride);
     }
-    b.conv(&h->sem_out, se + "conv2.conv", sp.code_dim, sp.sem_ch, 3, false, false);
+    b.conv(&h->sem_out, se + "conv2.conv", sp.code_dim, sp.sem_ch, 3, false);
     // --- codebooks (vector_quantize_pytorch layout: layers.{q}._codebook.embed [1, K, D])
     {
         const int64_t kd = (int64_t)sp.codebook_size * sp.code_dim;
         std::vector<float> cba((size_t)sp.num_quantizers * kd), cbs((size_t)sp.num_quantizers * kd);
         for (int q = 0; q < sp.num_quantizers; ++q) {
-            const float* a = b.f.need("quantizer.layers." + std::to_string(q) + "._codebook.embed", kd);
-            const float* s = b.f.need("semantic_quantizer.layers." + std::to_string(q) + "._codebook.embed", kd);
+            const float* a = b.need("quantizer.layers." + std::to_string(q) + "._codebook.embed", kd);
+            const float* s = b.need("semantic_quantizer.layers." + std::to_string(q) + "._codebook.embed", kd);
             if (a) std::memcpy(&cba[(size_t)q * kd], a, sizeof(float) * kd);
             if (s) std::memcpy(&cbs[(size_t)q * kd], s, sizeof(float) * kd);
         }
@@ -1165,9 +1034,9 @@ int build(qa_hcodec* h, const HostTable& tab) {
     // --- decoder (codec_decoder.py:14-67)
     const int d = sp.dec_dim;
     if (v20) {
-        b.conv(&h->dec_embed20, "decoder.embed.conv", d, 2 * sp.code_dim, sp.frame_stride + 1, false, true);
+        b.conv(&h->dec_embed20, "decoder.embed.conv", d, 2 * sp.code_dim, sp.frame_stride + 1);
     } else {
-        b.conv(&h->up, "decoder.embed.up", 2 * d, 2 * sp.code_dim, 1, false, true);
+        b.conv(&h->up, "decoder.embed.up", 2 * d, 2 * sp.code_dim, 1);
         dw_fold_c(&h->up_dw, "decoder.embed.dw.weight", 5, d);
         b.vec(&h->up_dwb, "decoder.embed.dw.bias", d);
     }
@@ -1178,8 +1047,8 @@ int build(qa_hcodec* h, const HostTable& tab) {
         b.vec(&h->dres[i].n1b, rp + ".norm1.bias", d);
         b.vec(&h->dres[i].n2w, rp + ".norm2.weight", d);
         b.vec(&h->dres[i].n2b, rp + ".norm2.bias", d);
-        b.conv(&h->dres[i].c1, rp + ".conv1.conv", d, d, 3, false, true);
-        b.conv(&h->dres[i].c2, rp + ".conv2.conv", d, d, 3, false, true);
+        b.conv(&h->dres[i].c1, rp + ".conv1.conv", d, d, 3);
+        b.conv(&h->dres[i].c2, rp + ".conv2.conv", d, d, 3);
     }
     build_transformer(b, &h->dec_tr, "decoder.prior_net.3", d, sp.dec_layers, sp.dec_heads, tr_inter(d));
     b.vec(&h->gn_w, "decoder.prior_net.7.weight", d);
@@ -1201,7 +1070,7 @@ int build(qa_hcodec* h, const HostTable& tab) {
         h->spec_ld = pad32(2 * nb);
         std::vector<float> win(Nf);
         if (tab.has("decoder.head.istft.window")) {
-            const float* wp = b.f.need("decoder.head.istft.window", Nf);
+            const float* wp = b.need("decoder.head.istft.window", Nf);
             if (wp) std::memcpy(win.data(), wp, sizeof(float) * Nf);
         } else {
             for (int n = 0; n < Nf; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / Nf));
@@ -1232,13 +1101,11 @@ int build(qa_hcodec* h, const HostTable& tab) {
         b.vec(&h->qemb_sem, "semantic_aggregator.query_embedding", sp.code_dim);
         b.vec(&h->qemb_ac, "acoustic_aggregator.query_embedding", sp.code_dim);
     }
-    if (!b.f.ok) return b.f.status;
+    QA_TRY(b.upload());
     QA_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_sync), sizeof(int) * 4));
     QA_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
     QA_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     QA_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    QA_TRY(h->store.upload());
-    b.resolve();
     // |e|^2 tables
     const int QK = sp.num_quantizers * sp.codebook_size;
     QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->e2_dev), sizeof(float) * 2 * QK));
@@ -1258,7 +1125,8 @@ int build(qa_hcodec* h, const HostTable& tab) {
 // was shared with another such kernel), runs the graph again on the per-step kernels - the call that hit the failure returns
 // valid results, and the device stops choosing the persistent kernel by itself.
 template <typename F>
-static int run_graph_checked(qa_hcodec* h, Ctx& c, F&& graph) {
+static int run_graph_checked(qa_hcodec* h, F&& graph) {
+    Ctx& c = h->ctx;
     void* ticket = nullptr;
     QA_TRY(lstm_call_begin(h->device, &ticket));
     {
@@ -1276,11 +1144,17 @@ static int run_graph_checked(qa_hcodec* h, Ctx& c, F&& graph) {
     std::fprintf(stderr, "libquarkaudio_hip: the grid barrier of the persistent LSTM recurrence timed out on device %d (shared device?); "
                          "re-running the call on the per-step kernels\n", h->device);
     lstm_force_per_step(true);
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
+    arm(c, h->ws);
     const int st = graph();
     lstm_force_per_step(false);
     return st;
+}
+
+// plan the call on the handle's workspace, then its real pass
+template <typename F>
+static int run(qa_hcodec* h, void* stream, F&& graph) {
+    QA_TRY(plan(h->device, static_cast<hipStream_t>(stream), h->ctx, h->ws, graph));
+    return run_graph_checked(h, graph);
 }
 
 extern "C" {
@@ -1295,30 +1169,12 @@ int qa_hcodec_create(qa_hcodec** out, const qa_hcodec_spec* spec, const qa_tenso
     std::unique_ptr<qa_hcodec> h(new qa_hcodec());
     h->spec = *spec;
     h->device = device;
-    HostTable tab(tensors, n_tensors);
-    const int st = build(h.get(), tab);
-    if (st != QA_OK) {
-        h->store.release();
-        if (h->e2_dev) (void)hipFree(h->e2_dev);
-        return st;
-    }
+    QA_TRY(build(h.get(), HostTable(tensors, n_tensors)));
     *out = h.release();
     return QA_OK;
 }
 
-void qa_hcodec_destroy(qa_hcodec* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    h->store.release();
-    if (h->e2_dev) (void)hipFree(h->e2_dev);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->host_sync) (void)hipHostFree(h->host_sync);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    delete h;
-}
+void qa_hcodec_destroy(qa_hcodec* h) { destroy_handle(h); }
 
 int qa_hcodec_encode(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
                      int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, void* stream) {
@@ -1333,17 +1189,7 @@ int qa_hcodec_encode(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const
                "(HCodecTokenizer.pad_wav)", (long long)B, (long long)T, hop);
     QA_REQUIRE(B * T < (1LL << 31), "qa_hcodec_encode: batch of %lld x %lld samples is too large", (long long)B, (long long)T);
     QA_REQUIRE(!h->spec.adaptive, "qa_hcodec_encode: this handle is an H-Codec 1.5 model, use qa_hcodec_encode_adaptive");
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(encode_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc));
-    QA_TRY(ensure_workspace(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return run_graph_checked(h, c, [&] { return encode_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc); });
+    return run(h, stream, [&] { return encode_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc); });
 }
 
 int qa_hcodec_decode(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t N, float* wav_out, void* stream) {
@@ -1354,17 +1200,7 @@ int qa_hcodec_decode(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t
     QA_REQUIRE(B > 0 && N > 0, "qa_hcodec_decode: codes are [%lld, Q, %lld]", (long long)B, (long long)N);
     QA_REQUIRE(B * N * (h->spec.version == 20 ? h->spec.frame_stride : 2) * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode: output too large");
     QA_REQUIRE(!h->spec.adaptive, "qa_hcodec_decode: this handle is an H-Codec 1.5 model, use qa_hcodec_decode_adaptive");
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(decode_graph(h, c, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out));
-    QA_TRY(ensure_workspace(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return run_graph_checked(h, c, [&] { return decode_graph(h, c, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out); });
+    return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out); });
 }
 
 int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
@@ -1381,19 +1217,9 @@ int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t
     QA_REQUIRE(B * T < (1LL << 31), "qa_hcodec_encode_adaptive: batch too large");
     QA_REQUIRE(threshold >= 0.f && threshold <= 1.f, "qa_hcodec_encode_adaptive: threshold %g outside [0, 1] (codec_adaptive.py:151)", threshold);
     const float thr = threshold <= 0.f ? h->spec.threshold : threshold;  // codec_adaptive.py:158
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
     int G = 0;
-    QA_TRY(encode_adaptive_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc, &G, thr));
-    QA_TRY(ensure_workspace(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    QA_TRY(run_graph_checked(h, c, [&] {
-        return encode_adaptive_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc, &G, thr);
+    QA_TRY(run(h, stream, [&] {
+        return encode_adaptive_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc, &G, thr);
     }));
     *n_groups = G;
     return QA_OK;
@@ -1406,10 +1232,10 @@ int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64
     }
     QA_REQUIRE(h->spec.adaptive && B > 0 && G > 0, "qa_hcodec_adaptive_frames: bad argument");
     QA_HIP(hipSetDevice(h->device));
-    QA_TRY(ensure_workspace(h, (size_t)(B + 64) * sizeof(int)));
+    QA_TRY(h->ws.ensure((size_t)(B + 64) * sizeof(int)));
     Ctx& c = h->ctx;
     c.stream = static_cast<hipStream_t>(stream);
-    int* totals = reinterpret_cast<int*>(h->ws);
+    int* totals = reinterpret_cast<int*>(h->ws.ptr);
     int* tmax = totals + B;
     QA_TRY(launch_adaptive_frames((const long long*)semantic_codes, (int)B, h->spec.num_quantizers, (int)G, h->spec.codebook_size,
                                   totals, tmax, c.stream));
@@ -1427,17 +1253,7 @@ int qa_hcodec_decode_adaptive(qa_hcodec* h, const int64_t* ac, const int64_t* sc
     }
     QA_REQUIRE(h->spec.adaptive, "qa_hcodec_decode_adaptive: this handle is not an H-Codec 1.5 model");
     QA_REQUIRE(B > 0 && G > 0 && frames > 0 && B * frames * 2 * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode_adaptive: bad shape");
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(decode_adaptive_graph(h, c, (const long long*)ac, (const long long*)sc, (int)B, (int)G, (int)frames, wav_out));
-    QA_TRY(ensure_workspace(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return run_graph_checked(h, c, [&] { return decode_adaptive_graph(h, c, (const long long*)ac, (const long long*)sc, (int)B, (int)G, (int)frames, wav_out); });
+    return run(h, stream, [&] { return decode_adaptive_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)G, (int)frames, wav_out); });
 }
 
 int qa_hcodec_load_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec* spec, const qa_tensor* tensors, int64_t n_tensors) {
@@ -1490,17 +1306,7 @@ int qa_hcodec_forward(qa_hcodec* h, const float* wav, int64_t B, int64_t T, cons
                       int64_t n_feat, float* recon, float* pred_feat, void* stream) {
     int N = 0;
     QA_TRY(forward_checks(h, "qa_hcodec_forward", wav, B, T, feat, recon, pred_feat, false, &N));
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(forward_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat));
-    QA_TRY(ensure_workspace(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return run_graph_checked(h, c, [&] { return forward_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat); });
+    return run(h, stream, [&] { return forward_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat); });
 }
 
 int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
@@ -1509,55 +1315,20 @@ int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_
     int N = 0;
     QA_TRY(forward_checks(h, "qa_hcodec_forward_adaptive", wav, B, T, feat, recon, pred_feat, true, &N));
     QA_REQUIRE(token_lengths && n_groups, "qa_hcodec_forward_adaptive: null argument");
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
     int G = 0;
-    QA_TRY(forward_adaptive_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat, (long long*)token_lengths, &G));
-    QA_TRY(ensure_workspace(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    QA_TRY(run_graph_checked(h, c, [&] {
-        return forward_adaptive_graph(h, c, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat,
+    QA_TRY(run(h, stream, [&] {
+        return forward_adaptive_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat,
                                       (long long*)token_lengths, &G);
     }));
     *n_groups = G;
     return QA_OK;
 }
 
-int qa_hcodec_enable_taps(qa_hcodec* h, int on) {
-    if (!h) {
-        set_error("qa_hcodec_enable_taps: null handle");
-        return QA_ERR_INVALID;
-    }
-    h->ctx.capture = on != 0;
-    return QA_OK;
-}
+int qa_hcodec_enable_taps(qa_hcodec* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_hcodec_enable_taps", on); }
 
 int64_t qa_hcodec_tap(qa_hcodec* h, const char* name, float* dst, int64_t cap, void* stream) {
-    if (!h || !name) {
-        set_error("qa_hcodec_tap: null argument");
-        return QA_ERR_INVALID;
-    }
-    auto it = h->ctx.taps.find(name);
-    if (it == h->ctx.taps.end()) {
-        set_error("qa_hcodec_tap: no intermediate named '%s' in the last call", name);
-        return QA_ERR_MISSING;
-    }
-    if (dst) {
-        if (cap < it->second.numel) {
-            set_error("qa_hcodec_tap: '%s' has %lld elements, capacity %lld", name, (long long)it->second.numel, (long long)cap);
-            return QA_ERR_INVALID;
-        }
-        QA_HIP(hipMemcpyAsync(dst, it->second.ptr, sizeof(float) * it->second.numel, hipMemcpyDeviceToDevice,
-                              static_cast<hipStream_t>(stream)));
-    }
-    return it->second.numel;
+    return tap_read(h ? &h->ctx : nullptr, "qa_hcodec_tap", name, dst, cap, stream);
 }
-
 
 /* ---- mimi StreamingTransformer ----------------------------------------------------------------------------------------- */
 
@@ -1580,53 +1351,27 @@ int qa_mimi_create(qa_mimi** out, const qa_mimi_spec* spec, const qa_tensor* ten
     m->spec = sp;
     m->device = device;
     HostTable tab(tensors, n_tensors);
-    Builder b{Folder{tab, m->store}};
+    Loader b(tab, m->store);
     build_mimi(b, &m->w, prefix, sp.d_model, sp.num_layers, sp.num_heads, sp.dim_feedforward, sp.causal, sp.context);
-    if (!b.f.ok) return b.f.status;
-    const int st = m->store.upload();
-    if (st != QA_OK) {
-        m->store.release();
-        return st;
-    }
-    b.resolve();
+    QA_TRY(b.upload());
     *out = m.release();
     return QA_OK;
 }
 
-void qa_mimi_destroy(qa_mimi* m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    (void)hipDeviceSynchronize();
-    m->store.release();
-    if (m->ring) (void)hipFree(m->ring);
-    if (m->st.rope_win) (void)hipFree(m->st.rope_win);
-    if (m->ws) (void)hipFree(m->ws);
-    delete m;
-}
+void qa_mimi_destroy(qa_mimi* m) { destroy_handle(m); }
 
 static int mimi_run(qa_mimi* m, const float* x, int B, int T, float* y, hipStream_t stream, bool streaming) {
     Ctx& c = m->ctx;
-    c.stream = stream;
     const int64_t rows = (int64_t)B * T;
-    for (int pass = 0; pass < 2; ++pass) {
-        c.dry = pass == 0;
-        c.arena.begin(c.dry ? nullptr : m->ws, c.dry ? 0 : m->ws_cap);
+    auto graph = [&]() -> int {
         const MimiTemps t = mimi_temps(c, m->w, rows);
-        if (c.dry) {
-            if (c.arena.peak() > m->ws_cap) {
-                if (m->ws) QA_HIP(hipFree(m->ws));
-                m->ws = nullptr;
-                m->ws_cap = 0;
-                QA_HIP(hipMalloc(reinterpret_cast<void**>(&m->ws), c.arena.peak() + c.arena.peak() / 8));
-                m->ws_cap = c.arena.peak() + c.arena.peak() / 8;
-            }
-            continue;
-        }
+        if (c.dry) return QA_OK;
         if (y != x) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * rows * m->w.d, hipMemcpyDeviceToDevice, stream));
         for (size_t l = 0; l < m->w.layers.size(); ++l)
             QA_TRY(mimi_layer(c, m->w, m->w.layers[l], y, t, B, T, streaming ? &m->st : nullptr, l));
-    }
-    return QA_OK;
+        return QA_OK;
+    };
+    return run_planned(*m, stream, graph);
 }
 
 int qa_mimi_forward(qa_mimi* m, const float* x, int64_t B, int64_t T, float* y, void* stream) {
@@ -1637,7 +1382,6 @@ int qa_mimi_forward(qa_mimi* m, const float* x, int64_t B, int64_t T, float* y, 
     QA_REQUIRE(B > 0 && T > 0 && T <= MAX_POS && B * T < (1LL << 31), "qa_mimi_forward: x is [%lld, %lld, d] (T <= %d)", (long long)B,
                (long long)T, MAX_POS);
     QA_REQUIRE(m->st.B == 0, "qa_mimi_forward: the handle is in streaming mode, use qa_mimi_stream_step");
-    QA_HIP(hipSetDevice(m->device));
     return mimi_run(m, x, (int)B, (int)T, y, static_cast<hipStream_t>(stream), false);
 }
 

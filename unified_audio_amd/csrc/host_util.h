@@ -1,10 +1,13 @@
-// host_util.h - host-side plumbing shared by the model graphs: weight-table lookup, the folded-weight store,
-// the per-call bump arena and the planning / execution context.
+// host_util.h - host-side plumbing shared by the model graphs: weight-table lookup, the folded-weight store and its loader,
+// the per-call bump arena, the workspace and the planning / execution context, the convolution launcher, test taps and the
+// resources every model handle owns.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "kernels.h"
@@ -41,6 +44,12 @@ class HostTable {
 // Folded weights are appended to one host blob (64-float aligned) and uploaded with a single copy.
 class WeightStore {
    public:
+    WeightStore() = default;
+    WeightStore(const WeightStore&) = delete;
+    WeightStore& operator=(const WeightStore&) = delete;
+    ~WeightStore() {
+        if (dev_) (void)hipFree(dev_);
+    }
     size_t add(const std::vector<float>& v) { return add(v.data(), v.size()); }
     size_t add(const float* p, size_t n) {
         const size_t off = blob_.size();
@@ -57,10 +66,6 @@ class WeightStore {
     }
     const float* ptr(size_t off) const { return dev_ + off; }
     size_t bytes() const { return bytes_; }
-    void release() {
-        if (dev_) (void)hipFree(dev_);
-        dev_ = nullptr;
-    }
 
    private:
     std::vector<float> blob_;
@@ -98,6 +103,29 @@ class Arena {
     size_t cap_ = 0, off_ = 0, peak_ = 0, floor_ = 0;
 };
 
+// A device buffer that only grows: ensure() frees the old buffer (hipFree waits for the work still reading it) and allocates the
+// request plus 1/8 headroom.
+struct Workspace {
+    char* ptr = nullptr;
+    size_t cap = 0;
+    Workspace() = default;
+    Workspace(const Workspace&) = delete;
+    Workspace& operator=(const Workspace&) = delete;
+    ~Workspace() {
+        if (ptr) (void)hipFree(ptr);
+    }
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return QA_OK;
+        if (ptr) QA_HIP(hipFree(ptr));
+        ptr = nullptr;
+        cap = 0;
+        const size_t grown = bytes + bytes / 8;
+        QA_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), grown));
+        cap = grown;
+        return QA_OK;
+    }
+};
+
 struct Tap {
     const float* ptr;
     int64_t numel;
@@ -128,6 +156,254 @@ struct ConvW {
 };
 
 inline int pad32(int c) { return (int)round_up(c, 32); }
+
+// ---------------------------------------------------------------- weight loading
+
+// How a layer's weight is stored in the state_dict: a plain `.weight`, torch.nn.utils.weight_norm's `.weight_g` / `.weight_v`, or
+// whichever of the two the table holds.
+enum { WN_NONE = 0, WN_FOLD = 1, WN_DETECT = 2 };
+
+// Folds tensors of a HostTable into a WeightStore.  Every fold records where its data lands; upload() copies the store to the device
+// and points the recorded destinations at it.  A missing or mis-sized tensor fails the load (QA_ERR_MISSING), and qa_last_error()
+// names it.
+class Loader {
+   public:
+    Loader(const HostTable& tab, WeightStore& store, int wn = WN_NONE) : tab(tab), wn(wn), store_(store) {}
+
+    const HostTable& tab;
+    int wn;  // the weight-norm mode of weight() and conv()
+
+    const float* need(const std::string& name, int64_t numel) {
+        const float* p = tab.get(name, numel);
+        if (!p) ok_ = false;
+        return p;
+    }
+    void vec(const float** dst, const std::string& name, int64_t n) {
+        const float* p = need(name, n);
+        if (p) pend_.push_back({dst, store_.add(p, (size_t)n)});
+    }
+    void raw(const float** dst, const std::vector<float>& v) { pend_.push_back({dst, store_.add(v)}); }
+    // the [d0][rest] weight of prefix p; weight norm over dim 0 is folded as torch._weight_norm does it: w = v * (g / ||v||_2), the
+    // sum of squares in double, the scale in fp32
+    bool weight(const std::string& p, int64_t d0, int64_t rest, std::vector<float>* out) {
+        out->assign((size_t)(d0 * rest), 0.f);
+        const int mode = wn == WN_DETECT ? (tab.has(p + ".weight") ? WN_NONE : WN_FOLD) : wn;
+        if (mode == WN_NONE) {
+            const float* w = need(p + ".weight", d0 * rest);
+            if (!w) return false;
+            std::memcpy(out->data(), w, sizeof(float) * (size_t)(d0 * rest));
+            return true;
+        }
+        const float* v = need(p + ".weight_v", d0 * rest);
+        const float* g = need(p + ".weight_g", d0);
+        if (!v || !g) return false;
+        for (int64_t i = 0; i < d0; ++i) {
+            double ss = 0.0;
+            for (int64_t j = 0; j < rest; ++j) ss += (double)v[i * rest + j] * v[i * rest + j];
+            const float scale = g[i] / (float)std::sqrt(ss);
+            for (int64_t j = 0; j < rest; ++j) (*out)[(size_t)(i * rest + j)] = v[i * rest + j] * scale;
+        }
+        return true;
+    }
+    // Conv1d / Linear weight [N][C_in][k] -> library layout [Np][k][Cp] scaled by `gain`, bias -> [Np]; Np / Cp > 0 zero-pad the
+    // output / input channels (the un-padded sizes stay in algo_n / algo_cin)
+    void conv(ConvW* dst, const std::string& p, int N, int C_in, int k, bool bias = true, float gain = 1.f, int Np = 0, int Cp = 0) {
+        if (Np <= 0) Np = N;
+        if (Cp <= 0) Cp = C_in;
+        std::vector<float> w, r((size_t)Np * k * Cp, 0.f);
+        if (weight(p, N, (int64_t)C_in * k, &w))
+            for (int n = 0; n < N; ++n)
+                for (int c = 0; c < C_in; ++c)
+                    for (int j = 0; j < k; ++j) r[((size_t)n * k + j) * Cp + c] = w[((size_t)n * C_in + c) * k + j] * gain;
+        dst->N = Np;
+        dst->C_in = Cp;
+        dst->ksize = k;
+        dst->algo_n = N;
+        dst->algo_cin = C_in;
+        raw(&dst->w, r);
+        if (bias) {
+            std::vector<float> b(Np, 0.f);
+            if (const float* bp = need(p + ".bias", N)) std::memcpy(b.data(), bp, sizeof(float) * N);
+            raw(&dst->b, b);
+        }
+    }
+    int upload() {
+        if (!ok_) return QA_ERR_MISSING;
+        QA_TRY(store_.upload());
+        for (auto& pv : pend_) *pv.first = store_.ptr(pv.second);
+        return QA_OK;
+    }
+
+   private:
+    WeightStore& store_;
+    bool ok_ = true;
+    std::vector<std::pair<const float**, size_t>> pend_;
+};
+
+// ---------------------------------------------------------------- convolution launcher
+
+// Everything of a conv_gemm launch that is not the operands' shapes.
+struct ConvOpt {
+    int stride = 1, pad_left = 0, pad_right = 0, pad_mode = PAD_ZERO;
+    int dilation = 1;  // tap j reads frame t * stride - pad_left + j * dilation (zero padding only)
+    int in_rep = 1;    // x read as x.repeat_interleave(in_rep) along frames
+    int prologue = ACT_NONE, act = ACT_NONE, post_act = ACT_NONE;
+    const float *gamma = nullptr, *res = nullptr, *gate = nullptr;
+    int64_t ldr = 0;               // residual row stride (0: N)
+    const float* shift = nullptr;  // per-channel constant added after gamma (the residual operand with row stride 0): BN after a ReLU
+    // Snake (ConvParams::alpha) and the second, activated output y2
+    const float *alpha = nullptr, *alpha2 = nullptr;
+    float* y2 = nullptr;
+    int64_t ldy2 = 0;
+    // fused interleaved-pair RoPE on the first rope_n output channels (ConvParams::rope)
+    const float* rope = nullptr;
+    int rope_n = 0, rope_hd = 0, rope_T = 0, rope_pos0 = 0;
+};
+
+// geometry only
+inline ConvOpt conv_geom(int stride, int pad_left, int pad_right, int pad_mode = PAD_ZERO) {
+    ConvOpt o;
+    o.stride = stride;
+    o.pad_left = pad_left;
+    o.pad_right = pad_right;
+    o.pad_mode = pad_mode;
+    return o;
+}
+// the epilogue of a linear: activation, residual (row stride N), gamma, gate
+inline ConvOpt epi(int act, const float* res = nullptr, const float* gamma = nullptr, const float* gate = nullptr) {
+    ConvOpt o;
+    o.act = act;
+    o.res = res;
+    o.gamma = gamma;
+    o.gate = gate;
+    return o;
+}
+
+// y [B, T_out, w.N] (row stride ldy) = conv(x [B, T_in, w.C_in] (row stride ldx), w) on the implicit GEMM; nothing in a dry pass
+inline int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, float* y, int64_t ldy, int T_out,
+                   const ConvOpt& o) {
+    if (c.dry) return QA_OK;
+    qa_conv_args a{};
+    a.x = x; a.w = w.w; a.bias = w.b; a.gamma = o.gamma; a.residual = o.res; a.gate = o.gate; a.y = y;
+    a.B = B; a.T_in = T_in; a.C_in = w.C_in; a.T_out = T_out; a.N = w.N;
+    a.ldx = ldx; a.ldy = ldy; a.ldr = o.ldr;
+    a.ksize = w.ksize; a.stride = o.stride; a.pad_left = o.pad_left; a.pad_right = o.pad_right; a.pad_mode = o.pad_mode;
+    a.prologue = o.prologue; a.act = o.act; a.post_act = o.post_act;
+    a.in_rep = o.in_rep;
+    ConvParams p;
+    if (o.dilation > 1) {
+        // conv_params_from_args checks the window span for a dense kernel: hand it the dense-equivalent paddings, then set the dilation
+        a.pad_left = o.pad_left + (w.ksize - 1) * (o.dilation - 1);
+        QA_TRY(conv_params_from_args(a, &p));
+        p.pad_left = o.pad_left;
+        const int max_pad = std::max(o.pad_left, o.pad_right);
+        p.Lp = (p.T_in <= max_pad) ? max_pad + 1 : p.T_in;
+        p.dilation = o.dilation;
+    } else {
+        QA_TRY(conv_params_from_args(a, &p));
+    }
+    p.algo_n = w.algo_n;
+    p.algo_k = w.algo_cin ? w.algo_cin * w.ksize : 0;
+    p.rope = o.rope; p.rope_n = o.rope_n; p.rope_hd = o.rope_hd; p.rope_T = o.rope_T; p.rope_pos0 = o.rope_pos0;
+    p.alpha = o.alpha; p.y2 = o.y2; p.alpha2 = o.alpha2; p.ldy2 = o.ldy2;
+    if (o.shift) {
+        p.res = o.shift;
+        p.ldr = 0;
+    }
+    return launch_conv_gemm(p, c.stream);
+}
+
+// plain linear over `rows` rows
+inline int linear_op(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, const ConvOpt& o = ConvOpt()) {
+    return conv_op(c, x, w.C_in, 1, (int)rows, w, y, w.N, (int)rows, o);
+}
+
+// ---------------------------------------------------------------- planning a call
+
+// the real pass: launches on, the taps of the previous call dropped, the arena on the workspace
+inline void arm(Ctx& c, Workspace& ws) {
+    c.dry = false;
+    c.taps.clear();
+    c.arena.begin(ws.ptr, ws.cap);
+}
+
+struct NoPreGrow {
+    int operator()(size_t) const { return QA_OK; }
+};
+
+// Set the device, run `graph` as the planning pass (allocations only), grow `ws` to the arena's peak and arm the real pass on it; the
+// caller then runs `graph` again.  `pre_grow(bytes)` runs first whenever the workspace has to grow.
+template <typename G, typename P = NoPreGrow>
+int plan(int device, hipStream_t stream, Ctx& c, Workspace& ws, G&& graph, P&& pre_grow = P()) {
+    QA_HIP(hipSetDevice(device));
+    c.stream = stream;
+    c.dry = true;
+    c.arena.begin(nullptr, 0);
+    QA_TRY(graph());
+    if (c.arena.peak() > ws.cap) QA_TRY(pre_grow(c.arena.peak()));
+    QA_TRY(ws.ensure(c.arena.peak()));
+    arm(c, ws);
+    return QA_OK;
+}
+
+// ---------------------------------------------------------------- test taps (the qa_*_tap / qa_*_enable_taps entry points)
+
+inline int taps_enable(Ctx* c, const char* fn, int on) {
+    if (!c) {
+        set_error("%s: null handle", fn);
+        return QA_ERR_INVALID;
+    }
+    c->capture = on != 0;
+    return QA_OK;
+}
+
+inline int64_t tap_read(const Ctx* c, const char* fn, const char* name, float* dst, int64_t cap, void* stream) {
+    if (!c || !name) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    auto it = c->taps.find(name);
+    if (it == c->taps.end()) {
+        set_error("%s: no intermediate named '%s' in the last call", fn, name);
+        return QA_ERR_MISSING;
+    }
+    if (dst) {
+        if (cap < it->second.numel) {
+            set_error("%s: '%s' has %lld elements, capacity %lld", fn, name, (long long)it->second.numel, (long long)cap);
+            return QA_ERR_INVALID;
+        }
+        QA_HIP(hipMemcpyAsync(dst, it->second.ptr, sizeof(float) * it->second.numel, hipMemcpyDeviceToDevice,
+                              static_cast<hipStream_t>(stream)));
+    }
+    return it->second.numel;
+}
+
+// ---------------------------------------------------------------- model handles
+
+// What every qa_* handle owns.  A handle frees its own further resources in its destructor, so a failed create and qa_*_destroy
+// release everything the same way (derived members go before these).
+struct Handle {
+    int device = 0;
+    WeightStore store;
+    Workspace ws;
+    Ctx ctx;
+};
+
+// plan a call on the handle's context and workspace, then run its real pass
+template <typename G>
+int run_planned(Handle& h, void* stream, G&& graph) {
+    QA_TRY(plan(h.device, static_cast<hipStream_t>(stream), h.ctx, h.ws, graph));
+    return graph();
+}
+
+// qa_*_destroy: wait for the handle's work on its device, then free it
+template <typename H>
+void destroy_handle(H* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    delete h;
+}
 
 // One output phase of a ConvTranspose1d(k, stride s, padding pad) as a stride-1 convolution.  Weight w [C_in][C_out][k] (nullptr: the
 // filter stays zero).  y[q s + phi] = sum_m x[q + c0 - m] W[:, :, j0 + m s] with j0 = (phi + pad) mod s, c0 = (phi + pad) div s: a

@@ -62,9 +62,8 @@ struct StepGraph {  // one captured decode step of a phase, replayable because e
     }
 };
 
-struct qa_lm {
+struct qa_lm : Handle {
     qa_lm_spec spec{};
-    int device = 0;
     bool fused_ok = false;   // the shapes fit the fused decode step (required since r05: build_lm refuses a spec that does not tile)
     bool mlp_fused = false;  // QA_LM_MLP_FUSED at create time: gate/up + SwiGLU + down as one launch + a reduce launch
     int mlp_ac = 16;         // activation columns per workgroup of that launch (8 measured equal at B = 16, -4 % at B = 64: profiles/r03_lm_ab.txt)
@@ -76,48 +75,31 @@ struct qa_lm {
     std::vector<hipEvent_t> chain_join;
     hipEvent_t ev_fork = nullptr;
     unsigned long long calls = 0;
-    WeightStore store;
     const float *task_emb = nullptr, *enroll_sos = nullptr, *mix_sos = nullptr, *codec_emb = nullptr, *ones = nullptr,
                 *rope = nullptr;  // `ones`: unit RMSNorm weight (the learned ones are folded into the projections)
     ConvW adapter, head;
     std::vector<LMLayer> layers;
-    char* ws = nullptr;
-    size_t ws_cap = 0;
-    Ctx ctx;
     // test hook (qa_lm_enable_taps): the slice logits of every decode step, in an allocation of their own (never the workspace, so
     // turning taps on cannot move a buffer of the step); tap_n: elements of logits.global / logits.semantic of the last call (-1: none)
     bool taps = false;
-    float* tap_buf = nullptr;
-    size_t tap_cap = 0;
+    Workspace tap_buf;
     int64_t tap_n[2] = {-1, -1};
     // qa_lm_score: a workspace and a tap buffer of its own, so that scoring never moves a buffer a captured decode step points into
-    char* score_ws = nullptr;
-    size_t score_ws_cap = 0;
-    float* score_tap = nullptr;  // logits.forced [B][Lt][V] of the last score call (taps on)
-    size_t score_tap_cap = 0;
+    Workspace score_ws;
+    Workspace score_tap;  // logits.forced [B][Lt][V] of the last score call (taps on)
     int64_t score_tap_n = -1;
+    ~qa_lm() {
+        for (StepGraph& g : graphs) g.reset();  // before the buffers they point into
+        if (cap_stream) (void)hipStreamDestroy(cap_stream);
+        for (hipStream_t st : chain_streams) (void)hipStreamDestroy(st);
+        for (hipEvent_t ev : chain_join) (void)hipEventDestroy(ev);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+    }
 };
 
 namespace {
 
 int vocab_of(const qa_lm_spec& s) { return 3 + s.global_size + s.semantic_size; }
-
-// y[rows, N] = epi(x[rows, K] W^T) on the implicit GEMM for EVERY row count (prompt adapters and prefill): its tile configurations
-// share one k order (test_conv_gemm_tile_configurations_are_bit_identical), so a sequence's prompt gets the same bits in any batch.
-// (The skinny kernel it took up to 32 rows sums in another order: a one-sequence call differed from the same sequence in a batch.)
-int lm_linear(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, const float* res = nullptr,
-              const float* gate = nullptr) {
-    if (c.dry) return QA_OK;
-    const int N = w.N;
-    qa_conv_args a{};
-    a.x = x; a.w = w.w; a.bias = w.b; a.residual = res; a.gate = gate; a.y = y;
-    a.B = 1; a.T_in = rows; a.C_in = w.C_in; a.T_out = rows; a.N = N;
-    a.ldx = w.C_in; a.ldy = N; a.ldr = N; a.ldg = N;
-    a.ksize = 1; a.stride = 1;
-    ConvParams p;
-    QA_TRY(conv_params_from_args(a, &p));
-    return launch_conv_gemm(p, c.stream);
-}
 
 // tile width of the head GEMV over a vocabulary slice of `width` entries (0: the slice does not tile)
 int head_nt(int width) {
@@ -145,62 +127,41 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
     // fused step did not tile it) is gone - a spec the fused step cannot tile is refused here, with the reason
     QA_REQUIRE(lm->fused_ok, "lm spec: the decode step needs hidden %% 256 == 0 (got %d), intermediate %% 256 == 0 (got %d), head_dim %% 8 == 0 and "
                "global / semantic vocabulary sizes that are multiples of 4 (got %d / %d)", d, I, sp.global_size, sp.semantic_size);
-    WeightStore& st = lm->store;
-    bool ok = true;
-    std::vector<std::pair<const float**, size_t>> pend;
-    auto vec = [&](const float** dst, const std::string& name, int64_t n) {
-        const float* p = tab.get(name, n);
-        if (!p) {
-            ok = false;
-            return;
-        }
-        pend.push_back({dst, st.add(p, n)});
-    };
-    vec(&lm->task_emb, "task_embedding.weight", (int64_t)sp.num_tasks * d);
-    vec(&lm->enroll_sos, "enroll_sos_embedding.weight", d);
-    vec(&lm->mix_sos, "mix_sos_embedding.weight", d);
-    vec(&lm->codec_emb, "codec_embedding.weight", (int64_t)V * d);
-    {
-        std::vector<float> ones(d, 1.0f);
-        pend.push_back({&lm->ones, st.add(ones)});
-    }
+    Loader L(tab, lm->store);
+    L.vec(&lm->task_emb, "task_embedding.weight", (int64_t)sp.num_tasks * d);
+    L.vec(&lm->enroll_sos, "enroll_sos_embedding.weight", d);
+    L.vec(&lm->mix_sos, "mix_sos_embedding.weight", d);
+    L.vec(&lm->codec_emb, "codec_embedding.weight", (int64_t)V * d);
+    L.raw(&lm->ones, std::vector<float>(d, 1.0f));
     // fold W' = W diag(w_norm): rows of W scaled column-wise by the RMSNorm weight that precedes the projection
     auto folded = [&](const std::string& wname, int64_t rows, const float* nw, std::vector<float>* out) -> bool {
-        const float* w = tab.get(wname, rows * d);
+        const float* w = L.need(wname, rows * d);
         if (!w || !nw) return false;
         out->resize((size_t)rows * d);
         for (int64_t r = 0; r < rows; ++r)
             for (int k = 0; k < d; ++k) (*out)[(size_t)r * d + k] = w[r * d + k] * nw[k];
         return true;
     };
-    lm->adapter.N = d; lm->adapter.C_in = sp.feats_dim;
-    vec(&lm->adapter.w, "adapter.weight", (int64_t)d * sp.feats_dim);
-    vec(&lm->adapter.b, "adapter.bias", d);
+    L.conv(&lm->adapter, "adapter", d, sp.feats_dim, 1);
     lm->head.N = V; lm->head.C_in = d;
     {
         std::vector<float> hw;
-        if (folded("output_head.weight", V, tab.get("norm.weight", d), &hw)) {
-            pend.push_back({&lm->head.w, st.add(hw)});
-        } else {
-            ok = false;
-        }
+        if (folded("output_head.weight", V, L.need("norm.weight", d), &hw)) L.raw(&lm->head.w, hw);
     }
     lm->layers.resize(sp.n_layers);
     for (int i = 0; i < sp.n_layers; ++i) {
-        LMLayer& L = lm->layers[i];
+        LMLayer& Lw = lm->layers[i];
         const std::string p = "layers." + std::to_string(i);
-        const float* ln1 = tab.get(p + ".input_layernorm.weight", d);
-        const float* ln2 = tab.get(p + ".post_attention_layernorm.weight", d);
-        if (!ln1 || !ln2) ok = false;
+        const float* ln1 = L.need(p + ".input_layernorm.weight", d);
+        const float* ln2 = L.need(p + ".post_attention_layernorm.weight", d);
         std::vector<float> wq((size_t)3 * d * d, 0.f);
         const char* nm[3] = {".self_attn.q_proj.weight", ".self_attn.k_proj.weight", ".self_attn.v_proj.weight"};
         for (int j = 0; j < 3; ++j) {
             std::vector<float> f;
-            if (!folded(p + nm[j], d, ln1, &f)) ok = false;
-            else std::memcpy(&wq[(size_t)j * d * d], f.data(), sizeof(float) * d * d);
+            if (folded(p + nm[j], d, ln1, &f)) std::memcpy(&wq[(size_t)j * d * d], f.data(), sizeof(float) * d * d);
         }
-        L.qkv.N = 3 * d; L.qkv.C_in = d;
-        pend.push_back({&L.qkv.w, st.add(wq)});
+        Lw.qkv.N = 3 * d; Lw.qkv.C_in = d;
+        L.raw(&Lw.qkv.w, wq);
         if (lm->fused_ok) {  // tile t of a section: rows [t*NT/2, (t+1)*NT/2) of each head-half, first halves then partner halves
             const int nt = lm->nt_qkv, hp = nt / 2;
             std::vector<float> wd((size_t)3 * d * d);
@@ -213,17 +174,16 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
                                 const size_t src = (size_t)sec * d + (size_t)h * hd + (size_t)half * (hd / 2) + (size_t)t * hp + j;
                                 std::memcpy(&wd[r * d], &wq[src * d], sizeof(float) * d);
                             }
-            pend.push_back({&L.qkv_dec, st.add(wd)});
+            L.raw(&Lw.qkv_dec, wd);
         }
-        L.o.N = d; L.o.C_in = d;
-        vec(&L.o.w, p + ".self_attn.o_proj.weight", (int64_t)d * d);
-        L.gate.N = I; L.gate.C_in = d;
-        L.up.N = I; L.up.C_in = d;
+        L.conv(&Lw.o, p + ".self_attn.o_proj", d, d, 1, false);
+        Lw.gate.N = I; Lw.gate.C_in = d;
+        Lw.up.N = I; Lw.up.C_in = d;
         {
             std::vector<float> g, u;
             if (folded(p + ".mlp.gate_proj.weight", I, ln2, &g) && folded(p + ".mlp.up_proj.weight", I, ln2, &u)) {
-                pend.push_back({&L.gate.w, st.add(g)});
-                pend.push_back({&L.up.w, st.add(u)});
+                L.raw(&Lw.gate.w, g);
+                L.raw(&Lw.up.w, u);
                 if (lm->fused_ok) {
                     const int hp = lm->nt_gu / 2;
                     std::vector<float> gd((size_t)2 * I * d);
@@ -231,28 +191,22 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
                         std::memcpy(&gd[(size_t)(t * 2 * hp) * d], &g[(size_t)(t * hp) * d], sizeof(float) * hp * d);
                         std::memcpy(&gd[(size_t)(t * 2 * hp + hp) * d], &u[(size_t)(t * hp) * d], sizeof(float) * hp * d);
                     }
-                    pend.push_back({&L.gu_dec, st.add(gd)});
+                    L.raw(&Lw.gu_dec, gd);
                 }
-            } else {
-                ok = false;
             }
         }
-        L.down.N = d; L.down.C_in = I;
-        vec(&L.down.w, p + ".mlp.down_proj.weight", (int64_t)I * d);
+        L.conv(&Lw.down, p + ".mlp.down_proj", d, I, 1, false);
         if (lm->fused_ok && lm->mlp_fused) {
-            const float* wdn = tab.get(p + ".mlp.down_proj.weight", (int64_t)I * d);
+            const float* wdn = L.need(p + ".mlp.down_proj.weight", (int64_t)I * d);
             if (wdn) {
                 std::vector<float> ws((size_t)I * d);
                 const int ac = lm->mlp_ac;
                 for (int j = 0; j < I / ac; ++j)
                     for (int n = 0; n < d; ++n) std::memcpy(&ws[((size_t)j * d + n) * ac], &wdn[(size_t)n * I + (size_t)j * ac], sizeof(float) * ac);
-                pend.push_back({&L.down_dec, st.add(ws)});
-            } else {
-                ok = false;
+                L.raw(&Lw.down_dec, ws);
             }
         }
     }
-    if (!ok) return QA_ERR_MISSING;
     // LlamaRotaryEmbedding (default rope): inv_freq = theta^(-2i/hd), cos / sin of pos * inv_freq in fp32
     const int half = hd / 2;
     std::vector<float> cs((size_t)LM_MAX_POS * half * 2);
@@ -264,10 +218,8 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
             cs[((size_t)t * half + i) * 2 + 1] = (float)std::sin((double)fr);
         }
     }
-    pend.push_back({&lm->rope, st.add(cs)});
-    QA_TRY(st.upload());
-    for (auto& pv : pend) *pv.first = st.ptr(pv.second);
-    return QA_OK;
+    L.raw(&lm->rope, cs);
+    return L.upload();
 }
 
 struct LMBuffers {
@@ -288,6 +240,11 @@ struct SampleCfg {
     unsigned long long seed;
 };
 
+// Every projection of the prompt adapters, the prefill and the scoring pass runs on the implicit GEMM for EVERY row count: its tile
+// configurations share one k order (test_conv_gemm_tile_configurations_are_bit_identical), so a sequence's prompt gets the same bits in
+// any batch.  (The skinny kernel it took up to 32 rows sums in another order: a one-sequence call differed from the same sequence in a
+// batch.)
+//
 // one pass of the Llama body over `n` new positions per sequence, positions pos0..pos0+n-1 (the prefill)
 // one_cache: every layer writes its keys / values into the same [B, max_len, d] pair (scoring: nothing reads a layer's cache after the
 // layer's own attention)
@@ -304,15 +261,15 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
         if (!c.dry) {
             const bool last = skip_last_mlp && i == sp.n_layers - 1;  // prefill: only the KV cache of the last layer is consumed
             QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
-            QA_TRY(lm_linear(c, b.hn, rows, L.qkv, b.qkv));
+            QA_TRY(linear_op(c, b.hn, rows, L.qkv, b.qkv));
             QA_TRY(launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream));
             if (last) break;
             QA_TRY(launch_attention(b.qkv, 3 * d, kc, vc, d, b.att, d, B, n, pos0 + n, (long long)max_len * d, H, hd, scale, 1, c.stream));
-            QA_TRY(lm_linear(c, b.att, rows, L.o, b.x, b.x));
+            QA_TRY(linear_op(c, b.att, rows, L.o, b.x, epi(ACT_NONE, b.x)));
             QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
-            QA_TRY(lm_linear(c, b.hn, rows, L.gate, b.g));
-            QA_TRY(lm_linear(c, b.hn, rows, L.up, b.u, nullptr, b.g));
-            QA_TRY(lm_linear(c, b.u, rows, L.down, b.x, b.x));
+            QA_TRY(linear_op(c, b.hn, rows, L.gate, b.g));
+            QA_TRY(linear_op(c, b.hn, rows, L.up, b.u, epi(ACT_NONE, nullptr, nullptr, b.g)));
+            QA_TRY(linear_op(c, b.u, rows, L.down, b.x, epi(ACT_NONE, b.x)));
         }
     }
     return QA_OK;
@@ -538,8 +495,8 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
         c.stream = ch.s;
         const float* mix_c = mix + (size_t)ch.b0 * Nm * sp.feats_dim;
         const float* enr_c = enroll ? enroll + (size_t)ch.b0 * Ne * sp.feats_dim : nullptr;
-        int st = lm_linear(c, mix_c, (int64_t)ch.B * Nm, lm->adapter, ch.emix);
-        if (st == QA_OK && enroll) st = lm_linear(c, enr_c, (int64_t)ch.B * Ne, lm->adapter, ch.eenr);
+        int st = linear_op(c, mix_c, (int64_t)ch.B * Nm, lm->adapter, ch.emix);
+        if (st == QA_OK && enroll) st = linear_op(c, enr_c, (int64_t)ch.B * Ne, lm->adapter, ch.eenr);
         if (st == QA_OK)
             st = launch_assemble_prompt(ch.b.x, lm->task_emb + (size_t)task * d, enroll ? lm->enroll_sos : nullptr, ch.eenr, lm->mix_sos,
                                         ch.emix, ch.B, Ne, Nm, d, ch.s);
@@ -552,7 +509,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     int pos = L;
     const bool graphs = !capturing && (multi || use_graphs());
     // taps: logits.global [B][G + 1][global_size], then logits.semantic [B][S][semantic_size]
-    float* const tap_base = lm->taps && !c.dry ? lm->tap_buf : nullptr;
+    float* const tap_base = lm->taps && !c.dry ? reinterpret_cast<float*>(lm->tap_buf.ptr) : nullptr;
     auto phase = [&](int which, long long first_id, int steps, int lo, int width, int keep) -> int {
         const int ids_ld = keep;
         float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * (G + 1) * sp.global_size) : nullptr;
@@ -566,7 +523,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
                 long long* ids = which == 0 ? ch.b.ids_g : ch.b.ids_s;
                 StepGraph& g = lm->graphs[2 * i + which];
                 uint64_t key = 0x51ull;
-                for (uint64_t v : {(uint64_t)(uintptr_t)lm->ws, (uint64_t)B, (uint64_t)nc, (uint64_t)ch.b0, (uint64_t)ch.B, (uint64_t)cap, (uint64_t)L,
+                for (uint64_t v : {(uint64_t)(uintptr_t)lm->ws.ptr, (uint64_t)B, (uint64_t)nc, (uint64_t)ch.b0, (uint64_t)ch.B, (uint64_t)cap, (uint64_t)L,
                                    (uint64_t)G, (uint64_t)S, (uint64_t)Ne, (uint64_t)Nm, (uint64_t)(enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
                                    (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF),
                                    (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch)})
@@ -659,8 +616,8 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const float conf = (float)(1.0 - a.eps), smooth = (float)(a.eps / (V - 1));
     for (int b0 = 0; b0 < a.B; b0 += GB) {
         const int gb = std::min(GB, a.B - b0);
-        QA_TRY(lm_linear(c, a.mix + (size_t)b0 * a.Nm * sp.feats_dim, (int64_t)gb * a.Nm, lm->adapter, emix));
-        if (a.enroll) QA_TRY(lm_linear(c, a.enroll + (size_t)b0 * a.Ne * sp.feats_dim, (int64_t)gb * a.Ne, lm->adapter, eenr));
+        QA_TRY(linear_op(c, a.mix + (size_t)b0 * a.Nm * sp.feats_dim, (int64_t)gb * a.Nm, lm->adapter, emix));
+        if (a.enroll) QA_TRY(linear_op(c, a.enroll + (size_t)b0 * a.Ne * sp.feats_dim, (int64_t)gb * a.Ne, lm->adapter, eenr));
         QA_TRY(launch_assemble_prompt(b.hn, lm->task_emb + (size_t)a.task * d, a.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
                                       a.Ne, a.Nm, d, c.stream));
         QA_HIP(hipMemcpy2DAsync(b.x, sizeof(float) * n * d, b.hn, sizeof(float) * Lp * d, sizeof(float) * Lp * d, gb, hipMemcpyDeviceToDevice,
@@ -676,7 +633,7 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
         // output_head, V = 3 + global + semantic columns (odd for the UniSE vocabulary: the GEMM's scalar epilogue, no padding)
         for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
             const int64_t nr = std::min(chunk, rows - r0);
-            QA_TRY(lm_linear(c, b.hn + (size_t)r0 * d, nr, lm->head, logits));
+            QA_TRY(linear_op(c, b.hn + (size_t)r0 * d, nr, lm->head, logits));
             QA_TRY(launch_lm_row_loss(logits, V, V, nr, tgt + r0, conf, smooth, row_kl + r0, row_ok + r0, c.stream));
             if (tap)
                 QA_HIP(hipMemcpyAsync(tap + ((size_t)b0 * Lt + r0) * V, logits, sizeof(float) * nr * V, hipMemcpyDeviceToDevice, c.stream));
@@ -686,35 +643,22 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     return launch_lm_batch_reduce(seq_sum, a.correct_seq, a.B, Lt, a.loss, a.acc, c.stream);
 }
 
-int ensure_ws(qa_lm* lm, size_t bytes) {
-    if (bytes <= lm->ws_cap) return QA_OK;
-    QA_HIP(hipDeviceSynchronize());  // earlier calls may still be running out of the old workspace
-    for (StepGraph& g : lm->graphs) g.reset();  // captured steps point into the old workspace
-    if (lm->ws) QA_HIP(hipFree(lm->ws));
-    lm->ws = nullptr;
-    lm->ws_cap = 0;
-    const size_t cap = bytes + bytes / 8;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->ws), cap));
-    lm->ws_cap = cap;
-    return QA_OK;
+// grow the workspace or the tap buffer of generate: earlier calls may still be running out of the old buffer, and captured steps point
+// into it (they are keyed by its address and re-captured)
+int grow_step_buffer(qa_lm* lm, Workspace& w, size_t bytes) {
+    if (bytes <= w.cap) return QA_OK;
+    QA_HIP(hipDeviceSynchronize());
+    for (StepGraph& g : lm->graphs) g.reset();
+    return w.ensure(bytes);
 }
 
-// the tap storage of a B x (G + 1, S) call: its own allocation, grown like the workspace (the captured steps that point into the old one
-// are keyed by its address and re-captured)
+// the tap storage of a B x (G + 1, S) call: its own allocation, grown like the workspace
 int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) != hipSuccess) (void)hipGetLastError();
     QA_REQUIRE(cs != hipStreamCaptureStatusActive, "qa_lm_generate: taps (a test hook) are not supported under a stream capture");
     const size_t n = (size_t)B * ((size_t)(G + 1) * lm->spec.global_size + (size_t)S * lm->spec.semantic_size);
-    if (n <= lm->tap_cap) return QA_OK;
-    QA_HIP(hipDeviceSynchronize());  // earlier calls may still be writing the old buffer
-    for (StepGraph& g : lm->graphs) g.reset();
-    if (lm->tap_buf) QA_HIP(hipFree(lm->tap_buf));
-    lm->tap_buf = nullptr;
-    lm->tap_cap = 0;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->tap_buf), sizeof(float) * n));
-    lm->tap_cap = n;
-    return QA_OK;
+    return grow_step_buffer(lm, lm->tap_buf, sizeof(float) * n);
 }
 
 }  // namespace
@@ -731,32 +675,12 @@ int qa_lm_create(qa_lm** out, const qa_lm_spec* spec, const qa_tensor* tensors, 
     std::unique_ptr<qa_lm> lm(new qa_lm());
     lm->spec = *spec;
     lm->device = device;
-    HostTable tab(tensors, n_tensors);
-    const int st = build_lm(lm.get(), tab);
-    if (st != QA_OK) {
-        lm->store.release();
-        return st;
-    }
+    QA_TRY(build_lm(lm.get(), HostTable(tensors, n_tensors)));
     *out = lm.release();
     return QA_OK;
 }
 
-void qa_lm_destroy(qa_lm* lm) {
-    if (!lm) return;
-    (void)hipSetDevice(lm->device);
-    (void)hipDeviceSynchronize();
-    for (StepGraph& g : lm->graphs) g.reset();
-    if (lm->cap_stream) (void)hipStreamDestroy(lm->cap_stream);
-    for (hipStream_t st : lm->chain_streams) (void)hipStreamDestroy(st);
-    for (hipEvent_t ev : lm->chain_join) (void)hipEventDestroy(ev);
-    if (lm->ev_fork) (void)hipEventDestroy(lm->ev_fork);
-    lm->store.release();
-    if (lm->ws) (void)hipFree(lm->ws);
-    if (lm->tap_buf) (void)hipFree(lm->tap_buf);
-    if (lm->score_ws) (void)hipFree(lm->score_ws);
-    if (lm->score_tap) (void)hipFree(lm->score_tap);
-    delete lm;
-}
+void qa_lm_destroy(qa_lm* lm) { destroy_handle(lm); }
 
 static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                             int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc,
@@ -775,25 +699,21 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     lm->tap_n[0] = lm->tap_n[1] = -1;
     if (lm->taps) QA_TRY(ensure_taps(lm, B, global_length, semantic_length, stream));
     Ctx& c = lm->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
-                          (long long*)global_ids, (long long*)semantic_ids, sc));
-    {
+    auto graph = [&] {
+        return generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
+                              (long long*)global_ids, (long long*)semantic_ids, sc);
+    };
+    QA_TRY(plan(lm->device, static_cast<hipStream_t>(stream), c, lm->ws, graph, [&](size_t bytes) -> int {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(c.stream, &cs) != hipSuccess) (void)hipGetLastError();
         // growing the workspace synchronises the device and allocates: neither is possible inside a caller's stream capture
-        QA_REQUIRE(cs != hipStreamCaptureStatusActive || c.arena.peak() <= lm->ws_cap,
+        QA_REQUIRE(cs != hipStreamCaptureStatusActive,
                    "qa_lm_generate under a stream capture needs %zu bytes of workspace, the handle holds %zu: make one call of the same shape outside "
                    "the capture first (with QA_LM_CHAINS=1 for batches above 32: a capturing caller gets the single-chain launches)",
-                   c.arena.peak(), lm->ws_cap);
-    }
-    QA_TRY(ensure_ws(lm, c.arena.peak()));
-    c.dry = false;
-    c.arena.begin(lm->ws, lm->ws_cap);
-    int st = generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
-                            (long long*)global_ids, (long long*)semantic_ids, sc);
+                   bytes, lm->ws.cap);
+        return grow_step_buffer(lm, lm->ws, bytes);
+    }));
+    int st = graph();
     if (st != QA_OK) {  // an error between the fork and the join of a multi-chain call: the chains' streams may still be running out of the
         c.stream = static_cast<hipStream_t>(stream);  // workspace the next call re-uses - quiesce them (error path only)
         for (hipStream_t cs : lm->chain_streams) (void)hipStreamSynchronize(cs);
@@ -846,36 +766,20 @@ int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_en
     float* tap = nullptr;
     if (lm->taps) {
         QA_REQUIRE(!capturing, "qa_lm_score: taps (a test hook) are not supported under a stream capture");
-        const size_t n = (size_t)B * Lt * vocab_of(lm->spec);
-        if (n > lm->score_tap_cap) {
-            QA_HIP(hipDeviceSynchronize());  // earlier calls may still be writing the old buffer
-            if (lm->score_tap) QA_HIP(hipFree(lm->score_tap));
-            lm->score_tap = nullptr;
-            lm->score_tap_cap = 0;
-            QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->score_tap), sizeof(float) * n));
-            lm->score_tap_cap = n;
-        }
-        tap = lm->score_tap;
+        const size_t bytes = sizeof(float) * (size_t)B * Lt * vocab_of(lm->spec);
+        if (bytes > lm->score_tap.cap) QA_HIP(hipDeviceSynchronize());  // earlier calls may still be writing the old buffer
+        QA_TRY(lm->score_tap.ensure(bytes));
+        tap = reinterpret_cast<float*>(lm->score_tap.ptr);
     }
     Ctx c;
-    c.stream = s;
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(score_graph(lm, c, a, tap));
-    if (c.arena.peak() > lm->score_ws_cap) {
+    auto graph = [&] { return score_graph(lm, c, a, tap); };
+    QA_TRY(plan(lm->device, s, c, lm->score_ws, graph, [&](size_t bytes) -> int {
         QA_REQUIRE(!capturing, "qa_lm_score under a stream capture needs %zu bytes of workspace, the handle holds %zu: make one call of the "
-                   "same shape outside the capture first", c.arena.peak(), lm->score_ws_cap);
+                   "same shape outside the capture first", bytes, lm->score_ws.cap);
         QA_HIP(hipDeviceSynchronize());  // earlier calls may still be running out of the old workspace
-        if (lm->score_ws) QA_HIP(hipFree(lm->score_ws));
-        lm->score_ws = nullptr;
-        lm->score_ws_cap = 0;
-        const size_t cap = c.arena.peak() + c.arena.peak() / 8;
-        QA_HIP(hipMalloc(reinterpret_cast<void**>(&lm->score_ws), cap));
-        lm->score_ws_cap = cap;
-    }
-    c.dry = false;
-    c.arena.begin(lm->score_ws, lm->score_ws_cap);
-    QA_TRY(score_graph(lm, c, a, tap));
+        return QA_OK;
+    }));
+    QA_TRY(graph());
     if (tap) lm->score_tap_n = (int64_t)B * Lt * vocab_of(lm->spec);
     return QA_OK;
 }
@@ -907,7 +811,7 @@ int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* st
             set_error("qa_lm_tap: '%s' has %lld elements, capacity %lld", name, (long long)n, (long long)cap);
             return QA_ERR_INVALID;
         }
-        const float* src = which == 2 ? lm->score_tap : lm->tap_buf + (which == 0 ? 0 : lm->tap_n[0]);
+        const float* src = reinterpret_cast<const float*>(which == 2 ? lm->score_tap.ptr : lm->tap_buf.ptr) + (which == 1 ? lm->tap_n[0] : 0);
         QA_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     }
     return n;

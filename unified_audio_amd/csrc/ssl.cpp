@@ -33,10 +33,8 @@ struct SslLayer {
 };
 }  // namespace
 
-struct qa_ssl {
+struct qa_ssl : Handle {
     qa_ssl_spec spec{};
-    int device = 0;
-    WeightStore store;
     // feature extractor
     const float *conv0_w = nullptr, *conv0_b = nullptr, *gn_w = nullptr, *gn_b = nullptr;
     std::vector<ConvW> convs;                      // layers 1..n_conv-1
@@ -48,29 +46,10 @@ struct qa_ssl {
     const float* relbias = nullptr;  // WavLM: [H][2R+1] relative position bias by clamped distance, R = rel_pos_max_distance
     std::vector<SslLayer> layers;
     std::vector<int> select;
-    char* ws = nullptr;
-    size_t ws_cap = 0;
-    Ctx ctx;
 };
 
 namespace {
 
-int conv(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, float* y, int64_t ldy, int T_out, int stride,
-         int pad_l, int pad_r, int act, const float* res = nullptr, int64_t ldr = 0) {
-    if (c.dry) return QA_OK;
-    qa_conv_args a{};
-    a.x = x; a.w = w.w; a.bias = w.b; a.residual = res; a.y = y;
-    a.B = B; a.T_in = T_in; a.C_in = w.C_in; a.T_out = T_out; a.N = w.N;
-    a.ldx = ldx; a.ldy = ldy; a.ldr = ldr;
-    a.ksize = w.ksize; a.stride = stride; a.pad_left = pad_l; a.pad_right = pad_r; a.pad_mode = PAD_ZERO;
-    a.act = act;
-    ConvParams p;
-    QA_TRY(conv_params_from_args(a, &p));
-    return launch_conv_gemm(p, c.stream);
-}
-int linear(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, int act = ACT_NONE, const float* res = nullptr) {
-    return conv(c, x, w.C_in, 1, (int)rows, w, y, w.N, (int)rows, 1, 0, 0, act, res, w.N);
-}
 int layernorm(Ctx& c, const float* x, const float* w, const float* b, float* y, int64_t rows, int C, float eps) {
     if (c.dry) return QA_OK;
     return launch_layernorm(x, w, b, y, rows, C, eps, c.stream);
@@ -105,73 +84,39 @@ int build(qa_ssl* h, const HostTable& tab) {
             h->select.push_back(sp.select[i]);
         }
 
-    WeightStore& st = h->store;
-    bool ok = true;
-    std::vector<std::pair<const float**, size_t>> pend;
-    auto vec = [&](const float** dst, const std::string& name, int64_t n) {
-        const float* p = tab.get(name, n);
-        if (!p) {
-            ok = false;
-            return;
-        }
-        pend.push_back({dst, st.add(p, n)});
-    };
-    // Conv1d weight [N, C, k] (PyTorch) -> library layout [N][k][C]
-    auto convw = [&](ConvW* w, const std::string& prefix, int N, int C, int k, bool bias) {
-        w->N = N; w->C_in = C; w->ksize = k;
-        const float* src = tab.get(prefix + ".weight", (int64_t)N * C * k);
-        if (!src) {
-            ok = false;
-            return;
-        }
-        std::vector<float> t((size_t)N * k * C);
-        for (int n = 0; n < N; ++n)
-            for (int cc = 0; cc < C; ++cc)
-                for (int j = 0; j < k; ++j) t[((size_t)n * k + j) * C + cc] = src[((size_t)n * C + cc) * k + j];
-        pend.push_back({&w->w, st.add(t)});
-        if (bias) vec(&w->b, prefix + ".bias", N);
-    };
-    auto linw = [&](ConvW* w, const std::string& prefix, int N, int C) {
-        w->N = N; w->C_in = C; w->ksize = 1;
-        vec(&w->w, prefix + ".weight", (int64_t)N * C);
-        vec(&w->b, prefix + ".bias", N);
-    };
+    Loader L(tab, h->store);
 
     // ---- feature extractor
     const int C0 = sp.conv_dim[0], k0 = sp.conv_kernel[0];
-    {
-        const float* src = tab.get("feature_extractor.conv_layers.0.conv.weight", (int64_t)C0 * k0);
-        if (src) {
-            std::vector<float> t((size_t)k0 * C0);
+    {   // layer 0 (C_in = 1) as [k][C0] for launch_ssl_conv0
+        std::vector<float> w, t((size_t)k0 * C0);
+        if (L.weight("feature_extractor.conv_layers.0.conv", C0, k0, &w))
             for (int cc = 0; cc < C0; ++cc)
-                for (int j = 0; j < k0; ++j) t[(size_t)j * C0 + cc] = src[(size_t)cc * k0 + j];
-            pend.push_back({&h->conv0_w, st.add(t)});
-        } else {
-            ok = false;
-        }
-        if (sp.conv_bias) vec(&h->conv0_b, "feature_extractor.conv_layers.0.conv.bias", C0);
+                for (int j = 0; j < k0; ++j) t[(size_t)j * C0 + cc] = w[(size_t)cc * k0 + j];
+        L.raw(&h->conv0_w, t);
+        if (sp.conv_bias) L.vec(&h->conv0_b, "feature_extractor.conv_layers.0.conv.bias", C0);
     }
     h->cln_w.assign(sp.n_conv, nullptr);
     h->cln_b.assign(sp.n_conv, nullptr);
     if (sp.feat_norm_layer) {
         for (int i = 0; i < sp.n_conv; ++i) {
             const std::string pre = "feature_extractor.conv_layers." + std::to_string(i) + ".layer_norm.";
-            vec(&h->cln_w[i], pre + "weight", sp.conv_dim[i]);
-            vec(&h->cln_b[i], pre + "bias", sp.conv_dim[i]);
+            L.vec(&h->cln_w[i], pre + "weight", sp.conv_dim[i]);
+            L.vec(&h->cln_b[i], pre + "bias", sp.conv_dim[i]);
         }
     } else {
-        vec(&h->gn_w, "feature_extractor.conv_layers.0.layer_norm.weight", C0);
-        vec(&h->gn_b, "feature_extractor.conv_layers.0.layer_norm.bias", C0);
+        L.vec(&h->gn_w, "feature_extractor.conv_layers.0.layer_norm.weight", C0);
+        L.vec(&h->gn_b, "feature_extractor.conv_layers.0.layer_norm.bias", C0);
     }
     h->convs.resize(sp.n_conv - 1);
     for (int i = 1; i < sp.n_conv; ++i)
-        convw(&h->convs[i - 1], "feature_extractor.conv_layers." + std::to_string(i) + ".conv", sp.conv_dim[i], sp.conv_dim[i - 1],
-              sp.conv_kernel[i], sp.conv_bias != 0);
+        L.conv(&h->convs[i - 1], "feature_extractor.conv_layers." + std::to_string(i) + ".conv", sp.conv_dim[i], sp.conv_dim[i - 1],
+               sp.conv_kernel[i], sp.conv_bias != 0);
     const int CL = sp.conv_dim[sp.n_conv - 1];
     // ---- feature projection
-    vec(&h->fp_ln_w, "feature_projection.layer_norm.weight", CL);
-    vec(&h->fp_ln_b, "feature_projection.layer_norm.bias", CL);
-    linw(&h->fp, "feature_projection.projection", d, CL);
+    L.vec(&h->fp_ln_w, "feature_projection.layer_norm.weight", CL);
+    L.vec(&h->fp_ln_b, "feature_projection.layer_norm.bias", CL);
+    L.conv(&h->fp, "feature_projection.projection", d, CL, 1);
     // ---- positional convolution: weight_norm(dim = 2) folded, then one [cg][k][cg] filter bank per group
     {
         const int G = sp.pos_groups, cg = d / G, k = sp.pos_kernel;
@@ -179,18 +124,19 @@ int build(qa_ssl* h, const HostTable& tab) {
         std::vector<float> wfull((size_t)d * cg * k);
         const int64_t n = (int64_t)d * cg * k;
         const float *g = nullptr, *v = nullptr;
-        if (tab.has(pre + "parametrizations.weight.original0")) {
-            g = tab.get(pre + "parametrizations.weight.original0", k);
-            v = tab.get(pre + "parametrizations.weight.original1", n);
-        } else if (tab.has(pre + "weight_g")) {
-            g = tab.get(pre + "weight_g", k);
-            v = tab.get(pre + "weight_v", n);
+        const bool wn = L.tab.has(pre + "parametrizations.weight.original0") || L.tab.has(pre + "weight_g");
+        if (L.tab.has(pre + "parametrizations.weight.original0")) {
+            g = L.need(pre + "parametrizations.weight.original0", k);
+            v = L.need(pre + "parametrizations.weight.original1", n);
+        } else if (wn) {
+            g = L.need(pre + "weight_g", k);
+            v = L.need(pre + "weight_v", n);
         } else {
-            v = tab.get(pre + "weight", n);
+            v = L.need(pre + "weight", n);
         }
-        if (!v || ((tab.has(pre + "parametrizations.weight.original0") || tab.has(pre + "weight_g")) && !g)) {
-            ok = false;
-        } else {
+        const float* bias = L.need(pre + "bias", d);
+        h->pos.resize(G);
+        if (v && bias && (g || !wn)) {
             std::vector<double> scale(k, 1.0);
             if (g)
                 for (int j = 0; j < k; ++j) {  // norm over (out, in) for every kernel position
@@ -198,10 +144,7 @@ int build(qa_ssl* h, const HostTable& tab) {
                     for (int64_t e = 0; e < (int64_t)d * cg; ++e) ss += (double)v[e * k + j] * v[e * k + j];
                     scale[j] = (double)g[j] / std::sqrt(ss);
                 }
-            const float* bias = tab.get(pre + "bias", d);
-            if (!bias) ok = false;
-            h->pos.resize(G);
-            for (int gi = 0; gi < G && bias; ++gi) {
+            for (int gi = 0; gi < G; ++gi) {
                 std::vector<float> t((size_t)cg * k * cg);
                 for (int o = 0; o < cg; ++o)
                     for (int ci = 0; ci < cg; ++ci)
@@ -209,68 +152,61 @@ int build(qa_ssl* h, const HostTable& tab) {
                             t[((size_t)o * k + j) * cg + ci] = (float)(v[((size_t)(gi * cg + o) * cg + ci) * k + j] * scale[j]);
                 ConvW& w = h->pos[gi];
                 w.N = cg; w.C_in = cg; w.ksize = k;
-                pend.push_back({&w.w, st.add(t)});
-                pend.push_back({&w.b, st.add(bias + (size_t)gi * cg, cg)});
+                L.raw(&w.w, t);
+                L.raw(&w.b, std::vector<float>(bias + (size_t)gi * cg, bias + (size_t)(gi + 1) * cg));
             }
         }
     }
-    vec(&h->enc_ln_w, "encoder.layer_norm.weight", d);
-    vec(&h->enc_ln_b, "encoder.layer_norm.bias", d);
+    L.vec(&h->enc_ln_w, "encoder.layer_norm.weight", d);
+    L.vec(&h->enc_ln_b, "encoder.layer_norm.bias", d);
     // ---- encoder layers
     h->layers.resize(sp.n_layers);
     for (int i = 0; i < sp.n_layers; ++i) {
-        SslLayer& L = h->layers[i];
+        SslLayer& Lw = h->layers[i];
         const std::string pre = "encoder.layers." + std::to_string(i) + ".";
         {  // q, k, v projections concatenated -> one [3d, d] GEMM
             std::vector<float> w((size_t)3 * d * d), b((size_t)3 * d);
             const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
             for (int j = 0; j < 3; ++j) {
-                const float* ws_ = tab.get(pre + "attention." + nm[j] + ".weight", (int64_t)d * d);
-                const float* bs_ = tab.get(pre + "attention." + nm[j] + ".bias", d);
-                if (!ws_ || !bs_) {
-                    ok = false;
-                    break;
-                }
+                const float* ws_ = L.need(pre + "attention." + nm[j] + ".weight", (int64_t)d * d);
+                const float* bs_ = L.need(pre + "attention." + nm[j] + ".bias", d);
+                if (!ws_ || !bs_) break;
                 std::memcpy(w.data() + (size_t)j * d * d, ws_, sizeof(float) * (size_t)d * d);
                 std::memcpy(b.data() + (size_t)j * d, bs_, sizeof(float) * d);
             }
-            L.qkv.N = 3 * d; L.qkv.C_in = d; L.qkv.ksize = 1;
-            pend.push_back({&L.qkv.w, st.add(w)});
-            pend.push_back({&L.qkv.b, st.add(b)});
+            Lw.qkv.N = 3 * d; Lw.qkv.C_in = d; Lw.qkv.ksize = 1;
+            L.raw(&Lw.qkv.w, w);
+            L.raw(&Lw.qkv.b, b);
         }
-        linw(&L.o, pre + "attention.out_proj", d, d);
-        vec(&L.ln1w, pre + "layer_norm.weight", d);
-        vec(&L.ln1b, pre + "layer_norm.bias", d);
-        linw(&L.ff1, pre + "feed_forward.intermediate_dense", I, d);
-        linw(&L.ff2, pre + "feed_forward.output_dense", d, I);
-        vec(&L.ln2w, pre + "final_layer_norm.weight", d);
-        vec(&L.ln2b, pre + "final_layer_norm.bias", d);
+        L.conv(&Lw.o, pre + "attention.out_proj", d, d, 1);
+        L.vec(&Lw.ln1w, pre + "layer_norm.weight", d);
+        L.vec(&Lw.ln1b, pre + "layer_norm.bias", d);
+        L.conv(&Lw.ff1, pre + "feed_forward.intermediate_dense", I, d, 1);
+        L.conv(&Lw.ff2, pre + "feed_forward.output_dense", d, I, 1);
+        L.vec(&Lw.ln2w, pre + "final_layer_norm.weight", d);
+        L.vec(&Lw.ln2b, pre + "final_layer_norm.bias", d);
         if (sp.rel_pos_buckets > 0) {  // gate = f(sum of 4 outputs): fold rows 0..3 and 4..7 of the 8 x hd projection
             const int hd = d / H;
-            const float* gw = tab.get(pre + "attention.gru_rel_pos_linear.weight", (int64_t)8 * hd);
-            const float* gb = tab.get(pre + "attention.gru_rel_pos_linear.bias", 8);
-            if (!gw || !gb) {
-                ok = false;
-            } else {
+            const float* gw = L.need(pre + "attention.gru_rel_pos_linear.weight", (int64_t)8 * hd);
+            const float* gb = L.need(pre + "attention.gru_rel_pos_linear.bias", 8);
+            if (gw && gb) {
                 std::vector<float> w2((size_t)2 * hd, 0.f), b2(2, 0.f);
                 for (int r = 0; r < 8; ++r) {
                     for (int e = 0; e < hd; ++e) w2[(size_t)(r / 4) * hd + e] += gw[(size_t)r * hd + e];
                     b2[r / 4] += gb[r];
                 }
-                pend.push_back({&L.gate_w, st.add(w2)});
-                pend.push_back({&L.gate_b, st.add(b2)});
+                L.raw(&Lw.gate_w, w2);
+                L.raw(&Lw.gate_b, b2);
             }
-            vec(&L.gate_c, pre + "attention.gru_rel_pos_const", H);
+            L.vec(&Lw.gate_c, pre + "attention.gru_rel_pos_const", H);
         }
     }
     if (sp.rel_pos_buckets > 0) {
         // WavLMAttention.compute_bias / _relative_positions_bucket, tabulated by relative distance r = key - query (float32
         // arithmetic like the reference).  For |r| >= max_distance the bucket is saturated, so clamping r is exact.
         QA_REQUIRE(sp.rel_pos_buckets % 4 == 0 && sp.rel_pos_max_distance > sp.rel_pos_buckets / 4, "ssl spec: relative position buckets");
-        const float* emb = tab.get("encoder.layers.0.attention.rel_attn_embed.weight", (int64_t)sp.rel_pos_buckets * H);
-        if (!emb) {
-            ok = false;
-        } else {
+        const float* emb = L.need("encoder.layers.0.attention.rel_attn_embed.weight", (int64_t)sp.rel_pos_buckets * H);
+        if (emb) {
             const int R = sp.rel_pos_max_distance, nb = sp.rel_pos_buckets / 2, max_exact = nb / 2;
             std::vector<float> t((size_t)H * (2 * R + 1));
             const float denom = (float)std::log((double)sp.rel_pos_max_distance / max_exact);
@@ -289,13 +225,10 @@ int build(qa_ssl* h, const HostTable& tab) {
                 }
                 for (int hh = 0; hh < H; ++hh) t[(size_t)hh * (2 * R + 1) + (r + R)] = emb[(size_t)bucket * H + hh];
             }
-            pend.push_back({&h->relbias, st.add(t)});
+            L.raw(&h->relbias, t);
         }
     }
-    if (!ok) return QA_ERR_INVALID;
-    QA_TRY(st.upload());
-    for (auto& pv : pend) *pv.first = st.ptr(pv.second);
-    return QA_OK;
+    return L.upload();
 }
 
 int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feats) {
@@ -325,7 +258,9 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         const int Lo = (L - w.ksize) / sp.conv_stride[i] + 1;
         QA_REQUIRE(Lo >= 1, "ssl: input too short at conv layer %d", i);
         float* y = c.arena.alloc<float>((size_t)B * Lo * w.N);
-        QA_TRY(conv(c, x, C, B, L, w, y, w.N, Lo, sp.conv_stride[i], 0, 0, sp.feat_norm_layer ? ACT_NONE : ACT_GELU));
+        ConvOpt o = conv_geom(sp.conv_stride[i], 0, 0);
+        o.act = sp.feat_norm_layer ? ACT_NONE : ACT_GELU;
+        QA_TRY(conv_op(c, x, C, B, L, w, y, w.N, Lo, o));
         if (sp.feat_norm_layer) {
             QA_TRY(layernorm(c, y, h->cln_w[i], h->cln_b[i], y, (int64_t)B * Lo, w.N, 1e-5f));
             if (!c.dry) QA_TRY(launch_ssl_act(y, (long long)B * Lo * w.N, ACT_GELU, c.stream));
@@ -349,14 +284,18 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     const bool rel = sp.rel_pos_buckets > 0;
     float* gate = rel ? c.arena.alloc<float>((size_t)rows * H) : nullptr;
     QA_TRY(layernorm(c, x, h->fp_ln_w, h->fp_ln_b, t0, rows, C, eps));
-    QA_TRY(linear(c, t0, rows, h->fp, hcur));
+    QA_TRY(linear_op(c, t0, rows, h->fp, hcur));
     // ---- encoder front: h = h + GELU(pos_conv(h))  (HubertPositionalConvEmbedding; the even kernel's extra output frame is
     // never computed), then LayerNorm for the post-LN flavour
     {
         const int G = sp.pos_groups, cg = d / G, k = sp.pos_kernel;
-        for (int g = 0; g < G; ++g)
-            QA_TRY(conv(c, hcur + (size_t)g * cg, d, B, N, h->pos[g], hnext + (size_t)g * cg, d, N, 1, k / 2, k - 1 - k / 2, ACT_GELU,
-                        hcur + (size_t)g * cg, d));
+        ConvOpt o = conv_geom(1, k / 2, k - 1 - k / 2);
+        o.act = ACT_GELU;
+        o.ldr = d;
+        for (int g = 0; g < G; ++g) {
+            o.res = hcur + (size_t)g * cg;
+            QA_TRY(conv_op(c, hcur + (size_t)g * cg, d, B, N, h->pos[g], hnext + (size_t)g * cg, d, N, o));
+        }
         if (!sp.stable_layer_norm) {
             QA_TRY(layernorm(c, hnext, h->enc_ln_w, h->enc_ln_b, hcur, rows, d, eps));
         } else {
@@ -378,30 +317,30 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     for (int i = 0; i < sp.n_layers; ++i) {
         const SslLayer& Lw = h->layers[i];
         if (!sp.stable_layer_norm) {  // HubertEncoderLayer: x = LN(x + Attn(x)); x = LN(x + FFN(x))
-            QA_TRY(linear(c, hcur, rows, Lw.qkv, qkv));
+            QA_TRY(linear_op(c, hcur, rows, Lw.qkv, qkv));
             if (!c.dry) {
                 if (rel) QA_TRY(launch_ssl_gate(hcur, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
                 QA_TRY(launch_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0,
                                         c.stream, gate, rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
             }
-            QA_TRY(linear(c, att, rows, Lw.o, tmp, ACT_NONE, hcur));
+            QA_TRY(linear_op(c, att, rows, Lw.o, tmp, epi(ACT_NONE, hcur)));
             QA_TRY(layernorm(c, tmp, Lw.ln1w, Lw.ln1b, hnext, rows, d, eps));
-            QA_TRY(linear(c, hnext, rows, Lw.ff1, ffu, ACT_GELU));
-            QA_TRY(linear(c, ffu, rows, Lw.ff2, tmp, ACT_NONE, hnext));
+            QA_TRY(linear_op(c, hnext, rows, Lw.ff1, ffu, epi(ACT_GELU)));
+            QA_TRY(linear_op(c, ffu, rows, Lw.ff2, tmp, epi(ACT_NONE, hnext)));
             QA_TRY(layernorm(c, tmp, Lw.ln2w, Lw.ln2b, hcur, rows, d, eps));
             QA_TRY(maybe_accumulate(i + 1, hcur));
         } else {  // HubertEncoderLayerStableLayerNorm: x = x + Attn(LN(x)); x = x + FFN(LN(x)); final LN after the last layer
             QA_TRY(layernorm(c, hcur, Lw.ln1w, Lw.ln1b, tmp, rows, d, eps));
-            QA_TRY(linear(c, tmp, rows, Lw.qkv, qkv));
+            QA_TRY(linear_op(c, tmp, rows, Lw.qkv, qkv));
             if (!c.dry) {
                 if (rel) QA_TRY(launch_ssl_gate(tmp, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
                 QA_TRY(launch_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0,
                                         c.stream, gate, rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
             }
-            QA_TRY(linear(c, att, rows, Lw.o, hcur, ACT_NONE, hcur));
+            QA_TRY(linear_op(c, att, rows, Lw.o, hcur, epi(ACT_NONE, hcur)));
             QA_TRY(layernorm(c, hcur, Lw.ln2w, Lw.ln2b, tmp, rows, d, eps));
-            QA_TRY(linear(c, tmp, rows, Lw.ff1, ffu, ACT_GELU));
-            QA_TRY(linear(c, ffu, rows, Lw.ff2, hcur, ACT_NONE, hcur));
+            QA_TRY(linear_op(c, tmp, rows, Lw.ff1, ffu, epi(ACT_GELU)));
+            QA_TRY(linear_op(c, ffu, rows, Lw.ff2, hcur, epi(ACT_NONE, hcur)));
             if (i == sp.n_layers - 1) {
                 QA_TRY(layernorm(c, hcur, h->enc_ln_w, h->enc_ln_b, tmp, rows, d, eps));
                 QA_TRY(maybe_accumulate(i + 1, tmp));
@@ -412,17 +351,6 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     }
     QA_REQUIRE(n_acc > 0, "ssl: no hidden state selected");
     if (!c.dry) QA_TRY(launch_ssl_compress(acc, feats, (long long)rows * d, 1.0f / (float)n_acc, sp.compress_exponent, c.stream));
-    return QA_OK;
-}
-
-int ensure_ws(qa_ssl* h, size_t bytes) {
-    if (bytes <= h->ws_cap) return QA_OK;
-    if (h->ws) QA_HIP(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_cap = 0;
-    const size_t cap = bytes + bytes / 16;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), cap));
-    h->ws_cap = cap;
     return QA_OK;
 }
 
@@ -440,24 +368,12 @@ int qa_ssl_create(qa_ssl** out, const qa_ssl_spec* spec, const qa_tensor* tensor
     std::unique_ptr<qa_ssl> h(new qa_ssl());
     h->spec = *spec;
     h->device = device;
-    HostTable tab(tensors, n_tensors);
-    const int st = build(h.get(), tab);
-    if (st != QA_OK) {
-        h->store.release();
-        return st;
-    }
+    QA_TRY(build(h.get(), HostTable(tensors, n_tensors)));
     *out = h.release();
     return QA_OK;
 }
 
-void qa_ssl_destroy(qa_ssl* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    h->store.release();
-    if (h->ws) (void)hipFree(h->ws);
-    delete h;
-}
+void qa_ssl_destroy(qa_ssl* h) { destroy_handle(h); }
 
 int64_t qa_ssl_frames(const qa_ssl* h, int64_t T) {
     if (!h) {
@@ -482,17 +398,7 @@ int qa_ssl_forward(qa_ssl* h, const float* wav, int64_t B, int64_t T, float* fea
     const int64_t L0 = (T + 2 * (int64_t)h->spec.pad - h->spec.conv_kernel[0]) / h->spec.conv_stride[0] + 1;
     QA_REQUIRE(B * L0 < (1LL << 31) && L0 * h->spec.conv_dim[0] < (1LL << 31), "qa_ssl_forward: batch of %lld x %lld samples is too large",
                (long long)B, (long long)T);
-    QA_HIP(hipSetDevice(h->device));
-    Ctx& c = h->ctx;
-    c.stream = static_cast<hipStream_t>(stream);
-    c.dry = true;
-    c.arena.begin(nullptr, 0);
-    QA_TRY(forward_graph(h, c, wav, (int)B, (int)T, feats));
-    QA_TRY(ensure_ws(h, c.arena.peak()));
-    c.dry = false;
-    c.taps.clear();
-    c.arena.begin(h->ws, h->ws_cap);
-    return forward_graph(h, c, wav, (int)B, (int)T, feats);
+    return run_planned(*h, stream, [&] { return forward_graph(h, h->ctx, wav, (int)B, (int)T, feats); });
 }
 
 }  // extern "C"
