@@ -13,6 +13,8 @@
  *   qa_lm_create       <-> LLM_SFT(...) + load_state_dict   QuarkAudio-UniSE/model/llm/llm_sft.py:13-33, model/model.py:82-91
  *   qa_lm_generate     <-> LLM_SFT.generate(...)            QuarkAudio-UniSE/model/llm/llm_sft.py:93-195
  *   qa_bicodec_detokenize <-> BiCodec.detokenize(...)       QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199
+ *   qa_bicodec_tokenize   <-> BiCodec.tokenize(batch)       QuarkAudio-UniSE/model/bicodec/bicodec.py:151-180
+ *   qa_bicodec_forward    <-> BiCodec.forward(batch)        QuarkAudio-UniSE/model/bicodec/bicodec.py:113-149
  *
  * Conventions
  *   - every function returns 0 on success or a negative qa_status; nothing throws across the ABI;
@@ -458,6 +460,41 @@ int64_t qa_bicodec_enc_tap(qa_bicodec_enc* h, const char* name, float* dst, int6
 /* Wav2Vec2FeatureExtractor(do_normalize=True) on equal-length rows (audio_tokenizer.py:74-90, nothing padded):
  * out[b, :] = (wav[b, :] - mean) / sqrt(var + eps) with the population variance; eps = 1e-7 in the reference.  out may alias wav. */
 int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float eps, void* stream);
+
+/* ---- BiCodec.forward (QuarkAudio-UniSE/model/bicodec/bicodec.py:113-149, eval mode) ----------------------------------------------
+ * Needs both handles: the tokenizer (qa_bicodec_enc, which owns the ECAPA latent the x-vector head pools) and the detokenizer
+ * (qa_bicodec, which owns the prenet output the postnet reads).  The forward-only weights are optional: tokenize / detokenize never
+ * read them.  x-vector head: ASTP attentive statistics pooling with global context
+ * (speaker/pooling_layers.py:92-148, [frames; mean; std] 4608 -> 128 -> 1536), BatchNorm1d(3072),
+ * Linear(3072 -> xvector_dim) (speaker/ecapa_tdnn.py:195-212).  postnet: feat_decoder.Decoder without condition (Linear, two ratio-1
+ * SamplingBlocks each with a 2-layer VocosBackbone, a VocosBackbone with plain LayerNorm, Linear, optional tanh). */
+typedef struct qa_bicodec_forward_spec {
+    int32_t postnet_input_channels; /* 1024  = latent_dim (the prenet output) */
+    int32_t postnet_vocos_dim;      /* 384 */
+    int32_t postnet_vocos_inter;    /* 2048 */
+    int32_t postnet_vocos_layers;   /* 6 */
+    int32_t postnet_out_channels;   /* 1024  (the XLSR-53 feature width) */
+    int32_t postnet_tanh;           /* 0     use_tanh_at_final */
+    int32_t xvector_dim;            /* 1024  speaker_encoder.out_dim */
+} qa_bicodec_forward_spec;
+/* Attach the forward-only weights (host memory, the reference's keys speaker_encoder.speaker_encoder.{pool.linear1, pool.linear2, bn,
+ * linear}.* and postnet.*).  The two handles must describe the same model (latent width, codebook, global tokens) on one device.  On
+ * failure (the first missing or mis-shaped key in the error message) both handles keep what they had. */
+int qa_bicodec_load_forward(qa_bicodec* dec, qa_bicodec_enc* enc, const qa_bicodec_forward_spec* spec, const qa_tensor* tensors,
+                            int64_t n_tensors);
+/* 1 if the forward-only weights are attached, 0 if not, negative on a null handle */
+int qa_bicodec_has_forward(const qa_bicodec* dec, const qa_bicodec_enc* enc);
+/* feat fp32 [B, N, input_channels], ref_wav fp32 [B, T_ref] (the whole rows: get_global_tokens with ref_len = 0).  Outputs (device):
+ * semantic_out int64 [B, N], global_out int64 [B, token_num] (the tokens detokenize is run on), recons fp32 [B, N * hop]
+ * (= qa_bicodec_detokenize of those tokens, bit for bit), pred_feat fp32 [B, postnet_out_channels, N] (channel-first), x_vector
+ * fp32 [B, xvector_dim], d_vector fp32 [B, latent_dim], perplexity and cluster_size fp32 scalars: the code statistics over all B * N
+ * semantic tokens (factorized_vector_quantize.py:98-103; active_num is cluster_size), summed in a fixed order. */
+int qa_bicodec_forward(qa_bicodec* dec, qa_bicodec_enc* enc, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref,
+                       int64_t* semantic_out, int64_t* global_out, float* recons, float* pred_feat, float* x_vector, float* d_vector,
+                       float* perplexity, float* cluster_size, void* stream);
+/* Kernel-level entry point of forward's code statistics (tests): indices int64 [n] (device, 0 < n < 2^24, entries outside
+ * [0, codebook_size) are not counted), codebook_size <= 16384 -> perplexity, cluster_size (device fp32 scalars). */
+int qa_code_usage(const int64_t* indices, int64_t n, int32_t codebook_size, float* perplexity, float* cluster_size, void* stream);
 
 /* ---- UniSE AR-LM ------------------------------------------------------------------------------------ */
 

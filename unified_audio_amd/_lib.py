@@ -89,6 +89,13 @@ class qa_bicodec_enc_spec(C.Structure):
     ]
 
 
+class qa_bicodec_forward_spec(C.Structure):
+    _fields_ = [
+        ("postnet_input_channels", C.c_int32), ("postnet_vocos_dim", C.c_int32), ("postnet_vocos_inter", C.c_int32),
+        ("postnet_vocos_layers", C.c_int32), ("postnet_out_channels", C.c_int32), ("postnet_tanh", C.c_int32), ("xvector_dim", C.c_int32),
+    ]
+
+
 class qa_ssl_spec(C.Structure):
     _fields_ = [
         ("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8),
@@ -175,6 +182,11 @@ SYMBOLS = {
     "qa_bicodec_enc_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "qa_bicodec_enc_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "qa_wav_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_void_p]),
+    "qa_bicodec_load_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(qa_bicodec_forward_spec), C.POINTER(qa_tensor), C.c_int64]),
+    "qa_bicodec_has_forward": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "qa_code_usage": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_bicodec_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_lm_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_lm_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
     "qa_lm_destroy": (None, [C.c_void_p]),
     "qa_lm_generate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,

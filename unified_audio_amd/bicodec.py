@@ -61,8 +61,9 @@ class BiCodecSpec:
         `speaker_encoder` -> SpeakerEncoder (speaker_encoder.py:48-56), `prenet` -> Decoder (feat_decoder.py:37-47), `decoder` ->
         WaveGenerator (wave_generator.py:60-67).  A missing required key is a TypeError and an unknown key in a block whose constructor
         takes no **kwargs is a TypeError, as in the reference; a value the detokenizer kernels have no path for is refused by name
-        (QuarkAudioError -4) instead of being ignored.  `mel_params`, `encoder` and `postnet` configure the encoder / training side
-        (tokenize, forward) and are not read."""
+        (QuarkAudioError -4) instead of being ignored.  `mel_params` and `encoder` configure the encoder side (tokenize) and are not
+        read; the keys of `postnet` are checked as Decoder(**postnet) checks them (BiCodecForwardSpec.from_config), its values only
+        when the forward head is built."""
         def block(name, required, optional=(), open_kwargs=False):
             if name not in audio_tokenizer:
                 raise KeyError(f"config.yaml: audio_tokenizer.{name} is missing (bicodec.py:80-87 reads it)")
@@ -83,6 +84,7 @@ class BiCodecSpec:
         pre = block("prenet", ("input_channels", "vocos_dim", "vocos_intermediate_dim", "vocos_num_layers", "out_channels"),
                     ("condition_dim", "sample_ratios", "use_tanh_at_final"))
         dec = block("decoder", ("input_channel", "channels", "rates", "kernel_sizes"), ("d_out",))
+        BiCodecForwardSpec.from_config(audio_tokenizer)
         latent = int(q["input_dim"])
         if int(q["codebook_dim"]) == latent:
             refuse("quantizer.input_dim == codebook_dim (Identity projections, factorized_vector_quantize.py:59-65)")
@@ -219,6 +221,7 @@ class BiCodecEncoderSpec:
                    "frames the signal as 2 hops of a multiple of 32 samples)")
         if int(spk.get("fsq_num_quantizers", 1)) != 1:
             refuse(f"speaker_encoder.fsq_num_quantizers = {spk['fsq_num_quantizers']} (one FSQ stage is built)")
+        BiCodecForwardSpec.from_config(audio_tokenizer)  # the postnet's keys; its values matter only to forward
         if int(spk.get("input_dim", mkw["mel_dim"])) != mkw["mel_dim"]:
             raise ValueError(f"BiCodec config.yaml: speaker_encoder.input_dim = {spk['input_dim']} and mel_params.num_mels = "
                              f"{mkw['mel_dim']} must agree (get_global_tokens feeds one into the other)")
@@ -244,6 +247,76 @@ class BiCodecEncoderSpec:
 
 
 SPEC_BICODEC_ENCODER = BiCodecEncoderSpec()
+
+POSTNET_REQUIRED = ("input_channels", "vocos_dim", "vocos_intermediate_dim", "vocos_num_layers", "out_channels")
+POSTNET_OPTIONAL = ("condition_dim", "sample_ratios", "use_tanh_at_final")
+
+
+@dataclass(frozen=True)
+class BiCodecForwardSpec:
+    """What `BiCodec.forward` needs beyond tokenize and detokenize (bicodec.py:113-149): the `postnet` block of the `config.yaml`
+    (feat_decoder.Decoder, feat_decoder.py:37-47, called without a condition) and `speaker_encoder.out_dim`, the width of the x-vector
+    (ECAPA_TDNN's Linear(3072 -> out_dim), ecapa_tdnn.py:188).  The published values are the defaults."""
+
+    input_channels: int = 1024  # = latent_dim: the postnet reads the prenet output
+    vocos_dim: int = 384
+    vocos_inter: int = 2048
+    vocos_layers: int = 6
+    out_channels: int = 1024    # the XLSR-53 feature width pred_feat predicts
+    use_tanh_at_final: bool = False
+    sample_ratios: Tuple[int, ...] = (1, 1)
+    condition_dim: Any = None
+    xvector_dim: int = 1024     # speaker_encoder.out_dim
+
+    @classmethod
+    def from_spec(cls, spec: BiCodecSpec, encoder_spec: BiCodecEncoderSpec) -> "BiCodecForwardSpec":
+        """The published postnet (6 ConvNeXt layers at the prenet's widths, latent -> XLSR-53 width) of a model of `spec`."""
+        return cls(input_channels=spec.latent_dim, vocos_dim=spec.vocos_dim, vocos_inter=spec.vocos_inter,
+                   out_channels=encoder_spec.input_channels, xvector_dim=spec.latent_dim)
+
+    @classmethod
+    def from_config(cls, audio_tokenizer: Mapping[str, Any]) -> "BiCodecForwardSpec | None":
+        """The `postnet` block as `Decoder(**config["postnet"])` takes it (bicodec.py:86) and `speaker_encoder.out_dim`; None without a
+        `postnet` block.  A missing required key or an unknown key is a TypeError, as in the reference.  A value the forward kernels have
+        no path for is NOT refused here (tokenize and detokenize never read the postnet): `unsupported()` names it, and forward refuses."""
+        if "postnet" not in audio_tokenizer:
+            return None
+        b = dict(audio_tokenizer["postnet"])
+        missing = [k for k in POSTNET_REQUIRED if k not in b]
+        if missing:
+            raise TypeError(f"audio_tokenizer.postnet: missing required argument(s) {missing}")
+        unknown = [k for k in b if k not in POSTNET_REQUIRED and k not in POSTNET_OPTIONAL]
+        if unknown:
+            raise TypeError(f"audio_tokenizer.postnet: unexpected keyword argument(s) {unknown}")
+        spk = dict(audio_tokenizer.get("speaker_encoder") or {})
+        return cls(input_channels=int(b["input_channels"]), vocos_dim=int(b["vocos_dim"]), vocos_inter=int(b["vocos_intermediate_dim"]),
+                   vocos_layers=int(b["vocos_num_layers"]), out_channels=int(b["out_channels"]),
+                   use_tanh_at_final=bool(b.get("use_tanh_at_final", False)),
+                   sample_ratios=tuple(int(r) for r in b.get("sample_ratios", (1, 1))), condition_dim=b.get("condition_dim"),
+                   xvector_dim=int(spk.get("out_dim", 512)))
+
+    def unsupported(self, latent_dim: int) -> "str | None":
+        """Why the forward kernels cannot run this postnet, or None."""
+        if list(self.sample_ratios) != [1, 1]:
+            return f"postnet.sample_ratios = {list(self.sample_ratios)} (the two ratio-1 SamplingBlocks of the published model are built)"
+        if self.condition_dim is not None:
+            return f"postnet.condition_dim = {self.condition_dim} (BiCodec.forward calls the postnet without a condition, bicodec.py:135)"
+        if self.input_channels != latent_dim:
+            return f"postnet.input_channels = {self.input_channels} (it reads the prenet output of width {latent_dim})"
+        for name, v in (("postnet.vocos_dim", self.vocos_dim), ("postnet.vocos_intermediate_dim", self.vocos_inter),
+                        ("postnet.out_channels", self.out_channels), ("speaker_encoder.out_dim", self.xvector_dim)):
+            if v <= 0 or v % 32:
+                return f"{name} = {v} (a positive multiple of 32)"
+        if self.vocos_layers < 1:
+            return f"postnet.vocos_num_layers = {self.vocos_layers}"
+        return None
+
+    def to_c(self) -> "_lib.qa_bicodec_forward_spec":
+        s = _lib.qa_bicodec_forward_spec()
+        s.postnet_input_channels, s.postnet_vocos_dim, s.postnet_vocos_inter = self.input_channels, self.vocos_dim, self.vocos_inter
+        s.postnet_vocos_layers, s.postnet_out_channels = self.vocos_layers, self.out_channels
+        s.postnet_tanh, s.xvector_dim = int(self.use_tanh_at_final), self.xvector_dim
+        return s
 # the entry whose presence makes load_state_dict build the tokenizer (then every encoder.*, quantizer.in_project.*, speaker_encoder.*
 # tensor it reads must be there); stray encoder-side entries without it are ignored, as they always were
 ENCODER_KEY = "encoder.encoder.embed.weight"
@@ -304,19 +377,23 @@ class BiCodec(torch.nn.Module):
     """`detokenize(semantic_tokens, global_tokens)` and `tokenize(batch)` / `get_semantic_tokens` / `get_global_tokens` of the reference's
     BiCodec.  Weights in the reference's key layout (`BiCodec.state_dict()` / the `model.safetensors` of the checkpoint).  The tokenizer
     is built when the state dict holds encoder.encoder.embed.weight (then it needs encoder.*, quantizer.in_project.* and the
-    speaker_encoder's ECAPA / perceiver / project_in entries); a detokenize-only state dict loads as before.  The x-vector head and
-    postnet entries are ignored."""
+    speaker_encoder's ECAPA / perceiver / project_in entries); a detokenize-only state dict loads as before.  `forward(batch)` (bicodec.py:
+    113-149) additionally needs the x-vector head (speaker_encoder.speaker_encoder.{pool, bn, linear}.*) and postnet.*: they are
+    attached when the tokenizer is built and they are present; without them everything else loads and runs as before and only forward
+    refuses, naming the first missing or mis-shaped key."""
 
     def __init__(self, spec: BiCodecSpec = SPEC_BICODEC, *, device: str | torch.device = "cuda:0", check_tokens: bool = True,
-                 encoder_spec: BiCodecEncoderSpec | None = None):
+                 encoder_spec: BiCodecEncoderSpec | None = None, forward_spec: BiCodecForwardSpec | None = None):
         super().__init__()
         self.spec = spec
         self.encoder_spec = encoder_spec or BiCodecEncoderSpec.from_spec(spec)
+        self.forward_spec = forward_spec or BiCodecForwardSpec.from_spec(spec, self.encoder_spec)
         self.device = torch.device(device)
         self.check_tokens = check_tokens
         self._lib = _lib.load_library()
         self._handle = C.c_void_p()
         self._enc = C.c_void_p()
+        self._forward_error = None  # (status, message): why forward cannot run
 
     @classmethod
     def load_from_checkpoint(cls, model_dir, device="cuda:0", spec: BiCodecSpec | None = None, **kwargs) -> "BiCodec":
@@ -326,13 +403,14 @@ class BiCodec(torch.nn.Module):
         from safetensors.torch import load_file
 
         sd = load_file(f"{model_dir}/model.safetensors")
-        encoder_spec = None
+        encoder_spec = forward_spec = None
         if spec is None:
             cfg = load_config(f"{model_dir}/config.yaml")["audio_tokenizer"]
             spec = BiCodecSpec.from_config(cfg)
             if ENCODER_KEY in sd:  # the tokenizer's config blocks are read only when the tokenizer is built
                 encoder_spec = BiCodecEncoderSpec.from_config(cfg)
-        return cls(spec, device=device, encoder_spec=encoder_spec).load_state_dict(sd)
+                forward_spec = BiCodecForwardSpec.from_config(cfg)
+        return cls(spec, device=device, encoder_spec=encoder_spec, forward_spec=forward_spec).load_state_dict(sd)
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = False, assign: bool = False):
         _lib.require_device()
@@ -347,8 +425,60 @@ class BiCodec(torch.nn.Module):
             espec = self.encoder_spec.to_c()
             _lib.check(self._lib.qa_bicodec_enc_create(C.byref(enc), C.byref(espec), table, n, self.device.index or 0))
             self._enc = enc
+            # the forward head is optional: nothing else reads it, and a state dict without (all of) it still loads
+            why = self.forward_spec.unsupported(self.spec.latent_dim)
+            if why is not None:
+                self._forward_error = (-4, f"BiCodec config.yaml: {why} - the MI355X forward has no path for it")
+            else:
+                fspec = self.forward_spec.to_c()
+                st = self._lib.qa_bicodec_load_forward(self._handle, self._enc, C.byref(fspec), table, n)
+                self._forward_error = None if st == 0 else (st, self._lib.qa_last_error().decode("utf-8", "replace"))
+        else:
+            self._forward_error = (-3, f"BiCodec has no tokenizer: the state dict held no {ENCODER_KEY} (a detokenize-only checkpoint)")
         del keep
         return self
+
+    @property
+    def has_forward(self) -> bool:
+        return bool(self._handle.value and self._enc.value) and self._lib.qa_bicodec_has_forward(self._handle, self._enc) == 1
+
+    @torch.no_grad()
+    def forward(self, batch: Mapping[str, torch.Tensor]) -> Dict[str, Any]:
+        """BiCodec.forward in eval mode (bicodec.py:113-149) -> the reference's dict: vq_loss (0-dim NaN: the mean of the two empty eval
+        losses, factorized_vector_quantize.py:121-131), perplexity and cluster_size (0-dim fp32, the code statistics over all B * N
+        semantic tokens of the batch), recons [B, 1, N * hop] (= detokenize(*tokenize(batch)) bit for bit), pred_feat [B, out_channels, N]
+        (the postnet on the prenet output before the d-vector add), x_vector / d_vector [B, out_dim], audios = batch["wav"].unsqueeze(1)
+        and with_speaker_loss = False.  batch: "feat" [B, N, input_channels], "ref_wav" [B, T] (the whole rows, as get_global_tokens with
+        ref_len = 0; the mel is the library's, not torchaudio's), "wav"."""
+        if not self._handle.value:
+            raise _lib.QuarkAudioError(-3, "BiCodec has no weights: call load_state_dict first")
+        feat, ref, wav = batch["feat"], batch["ref_wav"], batch["wav"]
+        self._require_tokenizer()
+        if self._forward_error is not None:
+            st, msg = self._forward_error
+            raise _lib.QuarkAudioError(st, f"BiCodec.forward needs the x-vector head and postnet weights: {msg}")
+        if feat.dim() != 3 or feat.shape[2] != self.encoder_spec.input_channels or feat.shape[1] == 0:
+            raise _lib.QuarkAudioError(-1, f"feat must be [B, N, {self.encoder_spec.input_channels}] with N > 0, got {tuple(feat.shape)}")
+        if ref.dim() != 2 or ref.shape[0] != feat.shape[0] or ref.shape[1] == 0:
+            raise _lib.QuarkAudioError(-1, f"ref_wav must be [B, T] with B = {feat.shape[0]}, got {tuple(ref.shape)}")
+        feat = feat.to(device=self.device, dtype=torch.float32).contiguous()
+        ref = ref.to(device=self.device, dtype=torch.float32).contiguous()
+        B, N, _ = feat.shape
+        fs, dev = self.forward_spec, self.device
+        sem = torch.empty((B, N), dtype=torch.int64, device=dev)
+        glob = torch.empty((B, self.spec.token_num), dtype=torch.int64, device=dev)
+        recons = torch.empty((B, 1, N * self.spec.hop), dtype=torch.float32, device=dev)
+        pred = torch.empty((B, fs.out_channels, N), dtype=torch.float32, device=dev)
+        x_vector = torch.empty((B, fs.xvector_dim), dtype=torch.float32, device=dev)
+        d_vector = torch.empty((B, self.spec.latent_dim), dtype=torch.float32, device=dev)
+        stats = torch.empty(2, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._lib.qa_bicodec_forward(self._handle, self._enc, feat.data_ptr(), B, N, ref.data_ptr(), ref.shape[1], sem.data_ptr(),
+                                                glob.data_ptr(), recons.data_ptr(), pred.data_ptr(), x_vector.data_ptr(), d_vector.data_ptr(),
+                                                stats[0:1].data_ptr(), stats[1:2].data_ptr(), stream))
+        return {"vq_loss": torch.full((), float("nan"), dtype=torch.float32, device=dev), "perplexity": stats[0], "cluster_size": stats[1],
+                "recons": recons, "pred_feat": pred, "x_vector": x_vector, "d_vector": d_vector,
+                "audios": wav.to(dev).unsqueeze(1), "with_speaker_loss": False}
 
     def train(self, mode: bool = True):
         if mode:
@@ -436,8 +566,9 @@ class BiCodec(torch.nn.Module):
 
     def tap(self, name: str) -> torch.Tensor:
         """Intermediates of the last call: detokenize's (z_q, prenet.*, gen.block{i}, ...), get_semantic_tokens' (enc.*, vq.latent) and
-        get_global_tokens' (mel, ecapa.*, perceiver.out, fsq.bounded)."""
-        encoder_side = name.startswith(("enc.", "vq.", "mel", "ecapa.", "perceiver.", "fsq."))
+        get_global_tokens' (mel, ecapa.*, perceiver.out, fsq.bounded); forward adds ecapa.pool [B, 3072], x_vector and postnet.out
+        [B, N, out_channels]."""
+        encoder_side = name.startswith(("enc.", "vq.", "mel", "ecapa.", "perceiver.", "fsq.", "x_vector"))
         h, fn = (self._enc, self._lib.qa_bicodec_enc_tap) if encoder_side else (self._handle, self._lib.qa_bicodec_tap)
         n = fn(h, name.encode(), None, 0, None)
         if n < 0:

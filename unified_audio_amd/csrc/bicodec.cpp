@@ -40,6 +40,11 @@ int launch_fsq(const float* x, const float* w, const float* bias, const int* lev
 int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate, long long ldg,
                        const float* res, long long ldr, float* y, long long ldy, int M, int N, int K, int act, hipStream_t s,
                        float rms_eps, int dual);
+int launch_astp_pool(const float* logit, const float* x, int B, int T, int C, const float* bn_s, const float* bn_t, float* pool, float* bn,
+                     hipStream_t s);
+int launch_frame_stats(const float* x, int B, int T, int C, float* ctx, hipStream_t s);
+int launch_code_usage(const long long* idx, long long n, int K, float* perplexity, float* active, hipStream_t s);
+int launch_widen_i32(const int* src, long long* dst, long long n, hipStream_t s);
 }  // namespace qa
 
 using namespace qa;
@@ -78,6 +83,14 @@ struct qa_bicodec : Handle {
     VocosW down[2], backbone;
     std::vector<GenBlockW> blocks;
     const float* a_final = nullptr;
+    // postnet (feat_decoder.Decoder without condition): attached by qa_bicodec_load_forward, read by qa_bicodec_forward only
+    struct Postnet {
+        WeightStore store;
+        qa_bicodec_forward_spec spec{};
+        ConvW linear_pre, linear_out;
+        VocosW down[2], backbone;
+    };
+    std::unique_ptr<Postnet> post;
 };
 
 // Conv1dReluBn (ecapa_tdnn.py): the convolution with BN(ReLU(.)) as the epilogue  relu(acc + b) * s + t
@@ -109,6 +122,14 @@ struct qa_bicodec_enc : Handle {
     SeRes2W blocks[3];
     std::vector<PerceiverLayerW> perceiver;
     const float *latents = nullptr, *norm_gamma = nullptr;
+    // the ECAPA x-vector head (ASTP pooling, BatchNorm1d, Linear): attached by qa_bicodec_load_forward, read by qa_bicodec_forward only
+    struct XvecHead {
+        WeightStore store;
+        // pool.linear1 [128, 3 x 1536] split by its input: the frames (lin1x) and the global context [mean; std] (lin1c, with the bias)
+        ConvW lin1x, lin1c, lin2, linear;
+        const float *bn_s = nullptr, *bn_t = nullptr;  // BatchNorm1d(3072) in eval as y = v * s + t
+    };
+    std::unique_ptr<XvecHead> xvec;
 };
 
 namespace {
@@ -313,7 +334,30 @@ int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, 
     return QA_OK;
 }
 
-int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long long* glob, int B, int T, float* wav_out) {
+// BiCodec.postnet (feat_decoder.py:79-96 without condition) on the prenet output px [B, T, latent] -> pred [B, out_channels, T],
+// channel-first like the reference (bicodec.py:135)
+int postnet_op(const qa_bicodec::Postnet& p, Ctx& c, const float* px, int B, int T, float* pred) {
+    const qa_bicodec_forward_spec& sp = p.spec;
+    const int C = sp.postnet_vocos_dim, I = sp.postnet_vocos_inter, O = sp.postnet_out_channels;
+    const int64_t rows = (int64_t)B * T;
+    float* x = c.arena.alloc<float>(rows * C);
+    float* t1 = c.arena.alloc<float>(rows * C);
+    float* u = c.arena.alloc<float>(rows * I);
+    float* o = c.arena.alloc<float>(rows * O);
+    QA_TRY(linear_op(c, px, rows, p.linear_pre, x));
+    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, p.down[i], x, t1, u, B, T, C, nullptr, 0));
+    QA_TRY(vocos(c, p.backbone, x, t1, u, B, T, C, nullptr, 0));
+    QA_TRY(linear_op(c, x, rows, p.linear_out, o, epi(sp.postnet_tanh ? ACT_TANH : ACT_NONE)));
+    c.tap("postnet.out", o, rows * O);
+    // [B, T, O] read as a [B, C' = T, T' = O] tensor with strides (T O, O, 1): its channel-last form is [B, O, T]
+    if (!c.dry) QA_TRY(launch_to_channel_last(o, (long long)T * O, O, 1, pred, B, T, O, c.stream));
+    return QA_OK;
+}
+
+// pred / dvec_out (forward only, else nullptr): the postnet's output from the prenet output BEFORE the d-vector add (bicodec.py:135-136),
+// and a copy of the d-vector
+int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long long* glob, int B, int T, float* wav_out, float* pred = nullptr,
+                     float* dvec_out = nullptr) {
     const qa_bicodec_spec& sp = h->spec;
     const int Ld = sp.latent_dim, C = sp.vocos_dim, I = sp.vocos_inter;
     const int64_t rows = (int64_t)B * T;
@@ -341,6 +385,12 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     c.tap("prenet.backbone", x, rows * C);
     float* px = zq;  // z_q is dead: reuse it for the prenet output [B, T, latent]
     QA_TRY(linear_op(c, x, rows, h->linear_out, px));
+    if (pred) {
+        const size_t m = c.arena.mark();  // the postnet's buffers are dead once pred is written
+        QA_TRY(postnet_op(*h->post, c, px, B, T, pred));
+        c.arena.release(m);
+    }
+    if (dvec_out && !c.dry) QA_HIP(hipMemcpyAsync(dvec_out, dvec, sizeof(float) * (size_t)B * Ld, hipMemcpyDeviceToDevice, c.stream));
     if (!c.dry) QA_TRY(launch_add_rowvec(px, dvec, B, T, Ld, c.stream));
     c.tap("prenet.out", px, rows * Ld);
     // ---- wave generator
@@ -621,7 +671,9 @@ int conv_bn_relu(Ctx& c, const float* x, int64_t ldx, int B, int T, const ConvBn
     return conv_op(c, x, ldx, B, T, w.conv, y, ldy, T, o);
 }
 
-int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, int64_t ref_len, int* tokens) {
+// latent_out (forward only): the ECAPA latent [B, frames, 1536] stays in the arena for the x-vector head
+int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, int64_t ref_len, int* tokens,
+                 const float** latent_out = nullptr) {
     const qa_bicodec_enc_spec& sp = h->spec;
     const int hop = sp.hop_length, C = sp.ecapa_channels, D = sp.spk_latent_dim, nl = sp.token_num;
     const int nf = (int)(ref_len / hop) + 1;  // torch.stft(center=True) frames
@@ -664,6 +716,7 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
         QA_TRY(conv_op(c, cat, 3 * C, B, nf, h->ecapa_out, latent, 1536, nf, o));
     }
     c.tap("ecapa.latent", latent, rows * 1536);
+    if (latent_out) *latent_out = latent;
     // ---- PerceiverResampler [B, token_num, D]
     const int inner = sp.perceiver_heads * sp.perceiver_dim_head, nk = nl + nf;
     const int64_t lrows = (int64_t)B * nl;
@@ -709,6 +762,141 @@ int check_global_shape(const qa_bicodec_enc* h, int64_t B, int64_t T, int64_t re
                "STFT's reflect padding (n_fft / 2 = %d)", (long long)ref_len, h->spec.n_fft / 2);
     QA_REQUIRE(B * (ref_len / h->spec.hop_length + 2) * 3 * h->spec.ecapa_channels < (1LL << 31) && B * T < (1LL << 40),
                "qa_bicodec_get_global_tokens: batch too large (split it)");
+    return QA_OK;
+}
+
+// ---------------------------------------------------------------- BiCodec.forward (bicodec.py:113-149)
+
+void vocos_keys(std::vector<std::pair<std::string, int64_t>>* k, const std::string& p, int C, int I, int n_layers) {
+    k->push_back({p + ".embed.weight", (int64_t)C * C * 7});
+    k->push_back({p + ".embed.bias", C});
+    k->push_back({p + ".norm.weight", C});
+    k->push_back({p + ".norm.bias", C});
+    for (int i = 0; i < n_layers; ++i) {
+        const std::string q = p + ".convnext." + std::to_string(i);
+        k->push_back({q + ".dwconv.weight", (int64_t)C * 7});
+        k->push_back({q + ".dwconv.bias", C});
+        k->push_back({q + ".norm.weight", C});
+        k->push_back({q + ".norm.bias", C});
+        k->push_back({q + ".pwconv1.weight", (int64_t)I * C});
+        k->push_back({q + ".pwconv1.bias", I});
+        k->push_back({q + ".pwconv2.weight", (int64_t)C * I});
+        k->push_back({q + ".pwconv2.bias", C});
+        k->push_back({q + ".gamma", C});
+    }
+    k->push_back({p + ".final_layer_norm.weight", C});
+    k->push_back({p + ".final_layer_norm.bias", C});
+}
+
+// The forward-only weights: the x-vector head speaker_encoder.speaker_encoder.{pool.linear1, pool.linear2, bn, linear}.* (into the
+// tokenizer handle, which owns the ECAPA latent) and postnet.* (into the detokenizer handle, which owns the prenet output).  Every key is
+// checked in module order before anything is folded, so the error names the first missing or mis-shaped one.
+int build_forward(const qa_bicodec* dec, const qa_bicodec_enc* enc, const qa_bicodec_forward_spec& sp, const HostTable& tab,
+                  std::unique_ptr<qa_bicodec::Postnet>* post_out, std::unique_ptr<qa_bicodec_enc::XvecHead>* xvec_out) {
+    const qa_bicodec_spec& ds = dec->spec;
+    const qa_bicodec_enc_spec& es = enc->spec;
+    const int Ld = ds.latent_dim, C = sp.postnet_vocos_dim, I = sp.postnet_vocos_inter, O = sp.postnet_out_channels, X = sp.xvector_dim;
+    QA_REQUIRE(dec->device == enc->device, "bicodec forward: the detokenizer (device %d) and the tokenizer (device %d) must share a device",
+               dec->device, enc->device);
+    QA_REQUIRE(sp.postnet_input_channels == Ld, "bicodec forward: postnet.input_channels %d != the prenet output width %d",
+               sp.postnet_input_channels, Ld);
+    QA_REQUIRE(C > 0 && C % 32 == 0 && I > 0 && I % 32 == 0 && O > 0 && O % 32 == 0 && sp.postnet_vocos_layers >= 1,
+               "bicodec forward: postnet vocos_dim %d, vocos_intermediate_dim %d, out_channels %d must be positive multiples of 32 and "
+               "vocos_num_layers %d >= 1", C, I, O, sp.postnet_vocos_layers);
+    QA_REQUIRE(X > 0 && X % 32 == 0, "bicodec forward: speaker_encoder.out_dim %d must be a positive multiple of 32", X);
+    QA_REQUIRE(es.ecapa_channels * 3 == 1536, "bicodec forward: the pooling head reads the 1536-wide ECAPA latent (channels %d)",
+               es.ecapa_channels);
+    bool same = es.latent_dim == Ld && es.codebook_size == ds.codebook_size && es.token_num == ds.token_num && es.n_levels == ds.n_levels;
+    for (int i = 0; same && i < ds.n_levels; ++i) same = es.levels[i] == ds.levels[i];
+    QA_REQUIRE(same, "bicodec forward: the tokenizer (latent %d, codebook %d, %d global tokens of %d levels) and the detokenizer (latent %d, "
+               "codebook %d, %d global tokens of %d levels) disagree", es.latent_dim, es.codebook_size, es.token_num, es.n_levels, Ld,
+               ds.codebook_size, ds.token_num, ds.n_levels);
+    const std::string e = "speaker_encoder.speaker_encoder";
+    std::vector<std::pair<std::string, int64_t>> keys = {
+        {e + ".pool.linear1.weight", (int64_t)128 * 4608}, {e + ".pool.linear1.bias", 128},
+        {e + ".pool.linear2.weight", (int64_t)1536 * 128}, {e + ".pool.linear2.bias", 1536},
+        {e + ".bn.weight", 3072}, {e + ".bn.bias", 3072}, {e + ".bn.running_mean", 3072}, {e + ".bn.running_var", 3072},
+        {e + ".linear.weight", (int64_t)X * 3072}, {e + ".linear.bias", X},
+        {"postnet.linear_pre.weight", (int64_t)C * Ld}, {"postnet.linear_pre.bias", C}};
+    for (int i = 0; i < 2; ++i) vocos_keys(&keys, "postnet.downsample." + std::to_string(i) + ".1", C, I, 2);
+    vocos_keys(&keys, "postnet.vocos_backbone", C, I, sp.postnet_vocos_layers);
+    keys.push_back({"postnet.linear.weight", (int64_t)O * C});
+    keys.push_back({"postnet.linear.bias", O});
+    for (const auto& k : keys)
+        if (!tab.get(k.first, k.second)) return QA_ERR_MISSING;  // HostTable::get has set the error message
+    std::unique_ptr<qa_bicodec_enc::XvecHead> xv(new qa_bicodec_enc::XvecHead());
+    {
+        Loader L(tab, xv->store);
+        std::vector<float> w1;  // [128][4608]: columns 0 .. 1535 the frames, 1536 .. 4607 the context (pooling_layers.py:133)
+        if (L.weight(e + ".pool.linear1", 128, 4608, &w1)) {
+            std::vector<float> wx((size_t)128 * 1536), wc((size_t)128 * 3072);
+            for (int n = 0; n < 128; ++n) {
+                std::memcpy(&wx[(size_t)n * 1536], &w1[(size_t)n * 4608], sizeof(float) * 1536);
+                std::memcpy(&wc[(size_t)n * 3072], &w1[(size_t)n * 4608 + 1536], sizeof(float) * 3072);
+            }
+            xv->lin1x.N = 128; xv->lin1x.C_in = 1536; xv->lin1x.ksize = 1;
+            xv->lin1c.N = 128; xv->lin1c.C_in = 3072; xv->lin1c.ksize = 1;
+            L.raw(&xv->lin1x.w, wx);
+            L.raw(&xv->lin1c.w, wc);
+            L.vec(&xv->lin1c.b, e + ".pool.linear1.bias", 128);
+        }
+        L.conv(&xv->lin2, e + ".pool.linear2", 1536, 128, 1);
+        std::vector<float> s, t;
+        batchnorm(L, e + ".bn", 3072, &s, &t);
+        L.raw(&xv->bn_s, s);
+        L.raw(&xv->bn_t, t);
+        L.conv(&xv->linear, e + ".linear", X, 3072, 1);
+        QA_TRY(L.upload());
+    }
+    std::unique_ptr<qa_bicodec::Postnet> pn(new qa_bicodec::Postnet());
+    pn->spec = sp;
+    {
+        Loader L(tab, pn->store);
+        L.conv(&pn->linear_pre, "postnet.linear_pre", C, Ld, 1);
+        for (int i = 0; i < 2; ++i) build_vocos(L, &pn->down[i], "postnet.downsample." + std::to_string(i) + ".1", C, I, 2, false, 3.0f);
+        build_vocos(L, &pn->backbone, "postnet.vocos_backbone", C, I, sp.postnet_vocos_layers, false, 1.0f);
+        L.conv(&pn->linear_out, "postnet.linear", O, C, 1);
+        QA_TRY(L.upload());
+    }
+    *post_out = std::move(pn);
+    *xvec_out = std::move(xv);
+    return QA_OK;
+}
+
+// the tokenizer half of forward: semantic tokens and their statistics, global tokens of the whole rows (ref_len = T) as int64, and the
+// x-vector from the ECAPA latent global_graph leaves in the arena (it is not recomputed)
+int forward_enc_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, const float* wav, int64_t T, long long* sem,
+                      long long* glob, float* xvec, float* perplexity, float* active) {
+    const qa_bicodec_enc_spec& sp = h->spec;
+    const qa_bicodec_enc::XvecHead& xv = *h->xvec;
+    QA_TRY(semantic_graph(h, c, feat, B, N, sem));
+    if (!c.dry) QA_TRY(launch_code_usage(sem, (long long)B * N, sp.codebook_size, perplexity, active, c.stream));
+    int* g32 = c.arena.alloc<int>((size_t)B * sp.token_num);
+    const float* latent = nullptr;
+    QA_TRY(global_graph(h, c, wav, B, T, T, g32, &latent));
+    if (!c.dry) QA_TRY(launch_widen_i32(g32, glob, (long long)B * sp.token_num, c.stream));
+    // ---- x-vector (ecapa_tdnn.py:204-206): ASTP with the global context of ECAPA_TDNN_GLOB_c512 (pooling_layers.py:129-144), BN, Linear.
+    // linear1(cat(x, mean, std)) = W_x x + (W_c [mean; std] + b): the context half is one row per item, folded into that item's bias
+    const int nf = (int)(T / sp.hop_length) + 1;
+    const int64_t rows = (int64_t)B * nf;
+    float* ctx = c.arena.alloc<float>((size_t)B * 3072);
+    float* cb = c.arena.alloc<float>((size_t)B * 128);
+    float* a1 = c.arena.alloc<float>((size_t)rows * 128);
+    float* logit = c.arena.alloc<float>((size_t)rows * 1536);
+    float* pool = c.arena.alloc<float>((size_t)B * 3072);
+    float* bn = c.arena.alloc<float>((size_t)B * 3072);
+    if (!c.dry) QA_TRY(launch_frame_stats(latent, B, nf, 1536, ctx, c.stream));
+    QA_TRY(linear_per_item(c, ctx, B, xv.lin1c, cb));
+    for (int b = 0; b < B; ++b) {  // tanh(W_x x + cb[b]) over the item's frames
+        ConvW w = xv.lin1x;
+        w.b = cb + (size_t)b * 128;
+        QA_TRY(conv_op(c, latent + (size_t)b * nf * 1536, 1536, 1, nf, w, a1 + (size_t)b * nf * 128, 128, nf, epi(ACT_TANH)));
+    }
+    QA_TRY(linear_op(c, a1, rows, xv.lin2, logit));
+    if (!c.dry) QA_TRY(launch_astp_pool(logit, latent, B, nf, 1536, xv.bn_s, xv.bn_t, pool, bn, c.stream));
+    c.tap("ecapa.pool", pool, (int64_t)B * 3072);
+    QA_TRY(linear_per_item(c, bn, B, xv.linear, xvec));
+    c.tap("x_vector", xvec, (int64_t)B * xv.linear.N);
     return QA_OK;
 }
 
@@ -816,6 +1004,64 @@ int qa_bicodec_enable_taps(qa_bicodec* h, int on) { return taps_enable(h ? &h->c
 
 int64_t qa_bicodec_tap(qa_bicodec* h, const char* name, float* dst, int64_t cap, void* stream) {
     return tap_read(h ? &h->ctx : nullptr, "qa_bicodec_tap", name, dst, cap, stream);
+}
+
+int qa_code_usage(const int64_t* indices, int64_t n, int32_t codebook_size, float* perplexity, float* cluster_size, void* stream) {
+    if (!indices || !perplexity || !cluster_size) {
+        set_error("qa_code_usage: null argument");
+        return QA_ERR_INVALID;
+    }
+    return launch_code_usage((const long long*)indices, n, codebook_size, perplexity, cluster_size, static_cast<hipStream_t>(stream));
+}
+
+int qa_bicodec_load_forward(qa_bicodec* dec, qa_bicodec_enc* enc, const qa_bicodec_forward_spec* spec, const qa_tensor* tensors,
+                            int64_t n_tensors) {
+    if (!dec || !enc || !spec || !tensors) {
+        set_error("qa_bicodec_load_forward: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_HIP(hipSetDevice(dec->device));
+    std::unique_ptr<qa_bicodec::Postnet> post;
+    std::unique_ptr<qa_bicodec_enc::XvecHead> xvec;
+    QA_TRY(build_forward(dec, enc, *spec, HostTable(tensors, n_tensors), &post, &xvec));
+    if (dec->post || enc->xvec) QA_HIP(hipDeviceSynchronize());  // the old weights may still be read by an earlier forward
+    dec->post = std::move(post);
+    enc->xvec = std::move(xvec);
+    return QA_OK;
+}
+
+int qa_bicodec_has_forward(const qa_bicodec* dec, const qa_bicodec_enc* enc) {
+    if (!dec || !enc) {
+        set_error("qa_bicodec_has_forward: null handle");
+        return QA_ERR_INVALID;
+    }
+    return dec->post && enc->xvec ? 1 : 0;
+}
+
+int qa_bicodec_forward(qa_bicodec* dec, qa_bicodec_enc* enc, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref,
+                       int64_t* semantic_out, int64_t* global_out, float* recons, float* pred_feat, float* x_vector, float* d_vector,
+                       float* perplexity, float* cluster_size, void* stream) {
+    if (!dec || !enc || !feat || !ref_wav || !semantic_out || !global_out || !recons || !pred_feat || !x_vector || !d_vector || !perplexity ||
+        !cluster_size) {
+        set_error("qa_bicodec_forward: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(dec->post && enc->xvec, "qa_bicodec_forward: no forward head is attached (qa_bicodec_load_forward: the checkpoint's "
+               "postnet.* and speaker_encoder.speaker_encoder.{pool, bn, linear}.* weights)");
+    QA_REQUIRE(B > 0 && N > 0, "qa_bicodec_forward: feat is [%lld, %lld, C]", (long long)B, (long long)N);
+    const qa_bicodec_forward_spec& ps = dec->post->spec;
+    const int64_t wide = std::max({(int64_t)enc->spec.vocos_inter, (int64_t)enc->spec.input_channels, (int64_t)ps.postnet_vocos_inter,
+                                   (int64_t)ps.postnet_out_channels, (int64_t)dec->hop * 32});
+    QA_REQUIRE(B * N * wide < (1LL << 31) && B * N < (1LL << 24), "qa_bicodec_forward: batch too large (split it)");
+    QA_TRY(check_global_shape(enc, B, T_ref, T_ref));
+    QA_TRY(run_planned(*enc, stream, [&] {
+        return forward_enc_graph(enc, enc->ctx, feat, (int)B, (int)N, ref_wav, T_ref, (long long*)semantic_out, (long long*)global_out,
+                                 x_vector, perplexity, cluster_size);
+    }));
+    return run_planned(*dec, stream, [&] {
+        return detokenize_graph(dec, dec->ctx, (const long long*)semantic_out, (const long long*)global_out, (int)B, (int)N, recons, pred_feat,
+                                d_vector);
+    });
 }
 
 }  // extern "C"

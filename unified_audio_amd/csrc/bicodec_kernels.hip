@@ -480,4 +480,173 @@ int launch_fsq(const float* x, const float* w, const float* bias, const int* lev
     return QA_OK;
 }
 
+// ---------------------------------------------------------------- BiCodec.forward (bicodec.py:113-149): x-vector head, code statistics
+
+// ASTP (speaker/pooling_layers.py:119-144) after linear2: per (b, c) alpha = softmax_T(logit[b, :, c]),
+// mean = sum alpha x, var = sum alpha x^2 - mean^2, std = sqrt(max(var, 1e-7)) -> pool[b, c] / pool[b, C + c]; bn[b, :] = the same
+// through BatchNorm1d (eval) as y = v * s + t (ecapa_tdnn.py:205).  Time-major inputs [B, T, C]: a workgroup owns 64 contiguous
+// channels (one per lane, coalesced rows) and its four waves take every fourth frame with an online (running-maximum) softmax, so each
+// input is read once.  The exponentials are fp32; the three running sums are fp64, and the four partial states merge in wave order,
+// so the result does not depend on timing.
+constexpr int ASTP_SLICES = 4;
+__global__ __launch_bounds__(256) void astp_pool_kernel(const float* __restrict__ logit, const float* __restrict__ x, int T, int C,
+                                                        const float* __restrict__ bn_s, const float* __restrict__ bn_t,
+                                                        float* __restrict__ pool, float* __restrict__ bn) {
+    __shared__ double st[ASTP_SLICES][4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane, b = blockIdx.y;
+    float m = -INFINITY;
+    double l = 0.0, s1 = 0.0, s2 = 0.0;
+    if (c < C) {
+        const float* lr = logit + (long long)b * T * C + c;
+        const float* xr = x + (long long)b * T * C + c;
+        for (int t = w; t < T; t += ASTP_SLICES) {
+            const float v = lr[(long long)t * C];
+            const double xv = (double)xr[(long long)t * C];
+            if (v > m) {  // new maximum: rescale what was summed so far (exp(-inf) = 0 on the first frame)
+                const double r = (double)expf(m - v);
+                l = l * r + 1.0;
+                s1 = s1 * r + xv;
+                s2 = s2 * r + xv * xv;
+                m = v;
+            } else {
+                const double e = (double)expf(v - m);
+                l += e;
+                s1 += e * xv;
+                s2 += e * xv * xv;
+            }
+        }
+    }
+    st[w][0][lane] = (double)m;
+    st[w][1][lane] = l;
+    st[w][2][lane] = s1;
+    st[w][3][lane] = s2;
+    __syncthreads();
+    if (w != 0 || c >= C) return;
+    double M = st[0][0][lane], L = st[0][1][lane], S1 = st[0][2][lane], S2 = st[0][3][lane];  // slice 0 holds frame 0: M is finite
+    for (int k = 1; k < ASTP_SLICES; ++k) {
+        const double mk = st[k][0][lane];
+        if (!(mk > -INFINITY)) continue;  // a slice without frames (T < 4)
+        const double nm = fmax(M, mk), ra = exp(M - nm), rb = exp(mk - nm);
+        L = L * ra + st[k][1][lane] * rb;
+        S1 = S1 * ra + st[k][2][lane] * rb;
+        S2 = S2 * ra + st[k][3][lane] * rb;
+        M = nm;
+    }
+    const double mean = S1 / L, var = S2 / L - mean * mean;
+    const float mf = (float)mean, sf = (float)sqrt(fmax(var, 1e-7));
+    float* pr = pool + (long long)b * 2 * C;
+    float* br = bn + (long long)b * 2 * C;
+    pr[c] = mf;
+    pr[C + c] = sf;
+    br[c] = fmaf(mf, bn_s[c], bn_t[c]);
+    br[C + c] = fmaf(sf, bn_s[C + c], bn_t[C + c]);
+}
+int launch_astp_pool(const float* logit, const float* x, int B, int T, int C, const float* bn_s, const float* bn_t, float* pool, float* bn,
+                     hipStream_t s) {
+    QA_REQUIRE(B > 0 && T > 0 && C > 0 && B < 65536, "astp_pool: [%d, %d, %d]", B, T, C);
+    hipLaunchKernelGGL(astp_pool_kernel, dim3((unsigned)ceil_div(C, 64), (unsigned)B), dim3(256), 0, s, logit, x, T, C, bn_s, bn_t, pool, bn);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ASTP's global context (pooling_layers.py:129-133, global_context_att=True as ECAPA_TDNN_GLOB_c512 builds it): per (b, c) the plain
+// mean over frames and sqrt(var + 1e-7) with torch.var's unbiased variance (T = 1 gives NaN, as torch does) -> ctx[b, c] / ctx[b, C + c].
+// Layout and parallel split as astp_pool_kernel; the sums are fp64.
+__global__ __launch_bounds__(256) void frame_stats_kernel(const float* __restrict__ x, int T, int C, float* __restrict__ ctx) {
+    __shared__ double st[ASTP_SLICES][2][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane, b = blockIdx.y;
+    double s1 = 0.0, s2 = 0.0;
+    if (c < C) {
+        const float* xr = x + (long long)b * T * C + c;
+        for (int t = w; t < T; t += ASTP_SLICES) {
+            const double v = (double)xr[(long long)t * C];
+            s1 += v;
+            s2 += v * v;
+        }
+    }
+    st[w][0][lane] = s1;
+    st[w][1][lane] = s2;
+    __syncthreads();
+    if (w != 0 || c >= C) return;
+    double S1 = st[0][0][lane], S2 = st[0][1][lane];
+    for (int k = 1; k < ASTP_SLICES; ++k) {
+        S1 += st[k][0][lane];
+        S2 += st[k][1][lane];
+    }
+    const double mean = S1 / T, var = (S2 - S1 * mean) / (double)(T - 1);
+    ctx[(long long)b * 2 * C + c] = (float)mean;
+    ctx[(long long)b * 2 * C + C + c] = (float)sqrt(var + 1e-7);
+}
+int launch_frame_stats(const float* x, int B, int T, int C, float* ctx, hipStream_t s) {
+    QA_REQUIRE(B > 0 && T > 0 && C > 0 && B < 65536, "frame_stats: [%d, %d, %d]", B, T, C);
+    hipLaunchKernelGGL(frame_stats_kernel, dim3((unsigned)ceil_div(C, 64), (unsigned)B), dim3(256), 0, s, x, T, C, ctx);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// FactorizedVectorQuantize.forward's code statistics (vq/factorized_vector_quantize.py:98-103) over ALL n = B * N indices of a call:
+// p_k = count_k / n (fp32, as torch.mean of the one-hot), perplexity = exp(-sum_k p_k log(p_k + 1e-10)), active = #{k : count_k > 0}.
+// One workgroup: an integer histogram of K bins in LDS, then every thread sums its bins k = tid, tid + 1024, ... in fp64 and the
+// partial sums meet in a fixed butterfly / wave order - bitwise reproducible from run to run.
+__global__ __launch_bounds__(1024) void code_usage_kernel(const long long* __restrict__ idx, long long n, int K, float* __restrict__ perplexity,
+                                                          float* __restrict__ active) {
+    extern __shared__ int hist[];
+    __shared__ double red[16];
+    __shared__ int redi[16];
+    for (int k = threadIdx.x; k < K; k += 1024) hist[k] = 0;
+    __syncthreads();
+    for (long long i = threadIdx.x; i < n; i += 1024) {
+        const long long v = idx[i];
+        if (v >= 0 && v < K) atomicAdd(&hist[v], 1);
+    }
+    __syncthreads();
+    const float nf = (float)n;
+    double h = 0.0;
+    int used = 0;
+    for (int k = threadIdx.x; k < K; k += 1024) {
+        const int cnt = hist[k];
+        const float p = (float)cnt / nf;
+        h += (double)p * log((double)(p + 1e-10f));
+        used += cnt > 0;
+    }
+    h = wave_sum_d(h);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) used += __shfl_xor(used, o, 64);
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = h;
+        redi[threadIdx.x >> 6] = used;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double H = 0.0;
+        int U = 0;
+        for (int i = 0; i < 16; ++i) {
+            H += red[i];
+            U += redi[i];
+        }
+        perplexity[0] = (float)exp(-H);
+        active[0] = (float)U;
+    }
+}
+int launch_code_usage(const long long* idx, long long n, int K, float* perplexity, float* active, hipStream_t s) {
+    QA_REQUIRE(n > 0 && n < (1LL << 24) && K >= 1 && K <= 16384, "code_usage: %lld indices, codebook %d (n < 2^24, K <= 16384)", n, K);
+    hipLaunchKernelGGL(code_usage_kernel, dim3(1), dim3(1024), (size_t)K * sizeof(int), s, idx, n, K, perplexity, active);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// int32 -> int64 (the FSQ indices of get_global_tokens as the detokenizer's global tokens)
+__global__ __launch_bounds__(256) void widen_i32_kernel(const int* __restrict__ src, long long* __restrict__ dst, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+int launch_widen_i32(const int* src, long long* dst, long long n, hipStream_t s) {
+    if (n <= 0) return QA_OK;
+    hipLaunchKernelGGL(widen_i32_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, src, dst, n);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
 }  // namespace qa

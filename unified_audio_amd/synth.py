@@ -586,6 +586,48 @@ def bicodec_speaker_state_dict(seed: int, spec=None) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def bicodec_forward_state_dict(seed: int, spec=None) -> Dict[str, torch.Tensor]:
+    """Seeded weights with the key names / shapes of the parts of `BiCodec.state_dict()` that only `forward` reads (bicodec.py:113-149):
+    the x-vector head speaker_encoder.speaker_encoder.{pool.linear1, pool.linear2, bn, linear} (ASTP with its global context +
+    BatchNorm1d + Linear,
+    ecapa_tdnn.py:179-188) and postnet.* (feat_decoder.Decoder without condition).  `spec` is a BiCodecForwardSpec.  pool.linear2 is
+    scaled so that the attention over frames is peaked but not one-hot; the BatchNorm statistics are of the pooled ReLU latent's scale."""
+    from .bicodec import BiCodecForwardSpec
+
+    spec = spec or BiCodecForwardSpec()
+    g = _Gen(seed)
+    rng, sd = g.rng, g.sd
+    C, I = spec.vocos_dim, spec.vocos_inter
+    p = "speaker_encoder.speaker_encoder"
+    g.conv(p + ".pool.linear1", 128, 3 * 1536, 1, gain=8.0)  # global_context_att: cat(frames, mean, std)
+    g.conv(p + ".pool.linear2", 1536, 128, 1, gain=16.0)
+    sd[p + ".bn.weight"] = _t(1.0 + 0.1 * rng.standard_normal(3072))
+    sd[p + ".bn.bias"] = _t(0.1 * rng.standard_normal(3072))
+    sd[p + ".bn.running_mean"] = _t(rng.uniform(0.0, 0.05, size=3072))
+    sd[p + ".bn.running_var"] = _t(rng.uniform(0.001, 0.01, size=3072))
+    sd[p + ".bn.num_batches_tracked"] = torch.tensor(100, dtype=torch.int64)
+    g.linear(p + ".linear", spec.xvector_dim, 3072)
+
+    def vocos(q, n_layers):
+        g.conv(q + ".embed", C, C, 7)
+        g.norm(q + ".norm", C)
+        for i in range(n_layers):
+            r = f"{q}.convnext.{i}"
+            g.conv(r + ".dwconv", C, 1, 7)
+            g.norm(r + ".norm", C)
+            g.linear(r + ".pwconv1", I, C)
+            g.linear(r + ".pwconv2", C, I)
+            sd[r + ".gamma"] = _t(rng.uniform(0.5, 1.5, size=C) / n_layers)
+        g.norm(q + ".final_layer_norm", C)
+
+    g.linear("postnet.linear_pre", C, spec.input_channels)
+    for i in range(2):
+        vocos(f"postnet.downsample.{i}.1", 2)
+    vocos("postnet.vocos_backbone", spec.vocos_layers)
+    g.linear("postnet.linear", spec.out_channels, C)
+    return sd
+
+
 def ssl_state_dict(spec, seed: int = 21) -> Dict[str, torch.Tensor]:
     """Seeded random weights in the transformers HubertModel / Wav2Vec2Model key layout (shapes only depend on the spec)."""
     g = torch.Generator().manual_seed(seed)
