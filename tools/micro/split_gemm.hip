@@ -5,6 +5,8 @@
 //   part 1 (numerics): error of the 9-product form against an fp64 reference, beside the error of the fp32 fmaf chain the product kernel
 //                      computes today, on uniform and on wide-dynamic-range operands; a probe of the MFMA's internal adder.
 //   part 2 (speed):    one 128 x 128 x 16 tile kernel (LINEAR shapes only) on the shapes that carry H-Codec 1.5's FLOPs.
+// r06 adds the six-product form (hl, lh, mm, hm, mh, hh: ml, lm and ll dropped) and a round-to-nearest-even split beside the truncation
+// split; SG_MODES=9t,6t,6r picks the forms that parts 1 and 2 run (version 3, the pipelined kernel, only).
 // build: hipcc --offload-arch=gfx950 -O3 tools/micro/split_gemm.hip -o tools/micro/split_gemm
 #include <hip/hip_runtime.h>
 
@@ -13,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <string>
 #include <vector>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -50,9 +53,38 @@ __device__ __host__ inline void split3(float x, unsigned& h, unsigned& m, unsign
     l = lb >> 16;
 }
 
-// 8 consecutive fp32 -> three u32x4 of 8 bf16 each.  v_perm_b32 packs the two high halves of a pair in one instruction.
+// 8 consecutive fp32 -> three u32x4 of 8 bf16 each.
+//   RNE = false: truncation, twice; v_perm_b32 packs the two high halves of a pair in one instruction.  Same-sign residuals:
+//                |m| < 2^-7 |x|, |l| < 2^-15 |x|.
+//   RNE = true:  round-to-nearest-even, twice (v_cvt_pk_bf16_f32, gfx950): h = rne(x), m = rne(x - h), l = x - h - m; every
+//                subtraction is exact and l has <= 8 significant bits (sign borrowing), so x == h + m + l exactly, with
+//                |m| <= 2^-8 |x| and |l| <= 2^-16 |x|.  Non-finite x: h = x, m = l = 0 (the residual is forced to 0 when it is not
+//                finite), so inf stays inf and NaN stays NaN through every product that contains h.
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned rne_pk(float a, float b) {  // low half bf16(a), high half bf16(b): one v_cvt_pk_bf16_f32
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+template <bool RNE>
 __device__ __forceinline__ void split8(const f32x4 lo, const f32x4 hi, u32x4& ph, u32x4& pm, u32x4& pl) {
     float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    if constexpr (RNE) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float a = x[2 * i], b = x[2 * i + 1];
+            const unsigned h = rne_pk(a, b);
+            float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
+            ra = __builtin_isfinite(ra) ? ra : 0.f;
+            rb = __builtin_isfinite(rb) ? rb : 0.f;
+            const unsigned m = rne_pk(ra, rb);
+            const float la = ra - __builtin_bit_cast(float, m << 16), lb = rb - __builtin_bit_cast(float, m & 0xffff0000u);
+            ph[i] = h;
+            pm[i] = m;
+            pl[i] = rne_pk(la, lb);  // exact
+        }
+        return;
+    }
     unsigned xb[8], rb[8], r2b[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -71,12 +103,13 @@ __device__ __forceinline__ void split8(const f32x4 lo, const f32x4 hi, u32x4& ph
 }
 
 // weights, once: W [N, K] fp32 -> Wp [N][K/8][3 planes][8] bf16 (48 contiguous bytes per (row, k-group))
+template <bool RNE>
 __global__ void prepack_kernel(const float* w, u32x4* wp, long long n_groups) {
     const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (g >= n_groups) return;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(w + g * 8), hi = *reinterpret_cast<const f32x4*>(w + g * 8 + 4);
     u32x4 ph, pm, pl;
-    split8(lo, hi, ph, pm, pl);
+    split8<RNE>(lo, hi, ph, pm, pl);
     wp[g * 3 + 0] = ph;
     wp[g * 3 + 1] = pm;
     wp[g * 3 + 2] = pl;
@@ -177,7 +210,7 @@ __global__ __launch_bounds__(256, 3) void split_gemm_kernel(const float* __restr
             if (SG_VARIANT & 2) {                                                          \
                 ph_ = __builtin_bit_cast(u32x4, a_lo[i]); pm_ = __builtin_bit_cast(u32x4, a_hi[i]); pl_ = ph_; \
             } else                                                                         \
-                split8(a_lo[i], a_hi[i], ph_, pm_, pl_);                                   \
+                split8<false>(a_lo[i], a_hi[i], ph_, pm_, pl_);                                   \
             sa_[0 * A_SLOTS + ld_slot + 256 * i] = ph_;                                    \
             sa_[1 * A_SLOTS + ld_slot + 256 * i] = pm_;                                    \
             sa_[2 * A_SLOTS + ld_slot + 256 * i] = pl_;                                    \
@@ -389,7 +422,7 @@ __global__ __launch_bounds__(256, 3) void split_gemm_dma_kernel(const float* __r
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             u32x4 ph, pm, pl;
-            split8(__builtin_bit_cast(f32x4, araw[i][0]), __builtin_bit_cast(f32x4, araw[i][1]), ph, pm, pl);
+            split8<false>(__builtin_bit_cast(f32x4, araw[i][0]), __builtin_bit_cast(f32x4, araw[i][1]), ph, pm, pl);
             af[0][i] = __builtin_bit_cast(bf16x8, ph);
             af[1][i] = __builtin_bit_cast(bf16x8, pm);
             af[2][i] = __builtin_bit_cast(bf16x8, pl);
@@ -443,14 +476,25 @@ __global__ __launch_bounds__(256, 3) void split_gemm_dma_kernel(const float* __r
 // Here the tail is taken out of the chunk: three LDS stages, the DMA of chunk kc+2 and the fragment reads + activation split of chunk
 // kc+1 are issued underneath the MFMAs of chunk kc (two register sets of fragments, loop unrolled by two), so a chunk ends with a bare
 // vmcnt(0) + barrier and the next chunk's first MFMA has its operands in registers.
+// (activation plane, weight plane) of each product, smallest first; 0 = h, 1 = m, 2 = l
+struct Planes { int a[9], b[9]; };
+constexpr Planes plane_order(int np) {
+    return np == 9 ? Planes{{2, 2, 1, 1, 2, 0, 1, 0, 0}, {2, 1, 2, 1, 0, 2, 0, 1, 0}}
+                   : Planes{{0, 2, 1, 0, 1, 0, 0, 0, 0}, {2, 0, 1, 1, 0, 0, 0, 0, 0}};  // hl, lh, mm, hm, mh, hh
+}
 #ifndef SG_LEAD
 #define SG_LEAD 8   // MFMAs issued before the first split instruction (covers the LDS latency of the raw activation fragments)
 #endif
 #ifndef SG_VPM
-#define SG_VPM 4    // split VALU instructions per MFMA slot after that
+#define SG_VPM 4    // split VALU instructions per MFMA slot after that (9 products)
+#endif
+#ifndef SG_VPM6
+#define SG_VPM6 7   // the same for 6 products: a third fewer MFMA slots carry the same split (RNE: about 2 x 60 VALU per wave and chunk)
 #endif
 __device__ unsigned long long g_clk[2];  // [0] shader cycles, [1] 100 MHz ticks, summed over workgroups (main loop of wave 0)
-template <int BM, int BN>
+// NP = 9: every plane product.  NP = 6: hl, lh, mm, hm, mh, hh (the three dropped terms ml, lm, ll are each <= 2^-24 |ab| under the RNE
+// split, one fp32 rounding, of random sign).  RNE selects the split of split8 for the activations (the weights are pre-split to match).
+template <int BM, int BN, int NP, bool RNE>
 __global__ __launch_bounds__(256, 2) void split_gemm_pipe_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
                                                                  float* __restrict__ y, int M, int N, int K, int panel) {
     constexpr int WM = 2, WN = 2;
@@ -528,7 +572,7 @@ __global__ __launch_bounds__(256, 2) void split_gemm_pipe_kernel(const float* __
     {                                                                                                                   \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                \
             u32x4 ph_, pm_, pl_;                                                                                        \
-            split8(__builtin_bit_cast(f32x4, ARAW[i][0]), __builtin_bit_cast(f32x4, ARAW[i][1]), ph_, pm_, pl_);        \
+            split8<RNE>(__builtin_bit_cast(f32x4, ARAW[i][0]), __builtin_bit_cast(f32x4, ARAW[i][1]), ph_, pm_, pl_);   \
             AF[0][i] = __builtin_bit_cast(bf16x8, ph_);                                                                 \
             AF[1][i] = __builtin_bit_cast(bf16x8, pm_);                                                                 \
             AF[2][i] = __builtin_bit_cast(bf16x8, pl_);                                                                 \
@@ -536,18 +580,18 @@ __global__ __launch_bounds__(256, 2) void split_gemm_pipe_kernel(const float* __
     }
 #define SG_MFMA(AF, BFR)                                                                                                \
     {                                                                                                                   \
-        _Pragma("unroll") for (int g = 0; g < 9; ++g) {                                                                 \
+        _Pragma("unroll") for (int g = 0; g < NP; ++g) {                                                                \
             _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                            \
                 _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                          \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BFR[PB[g]][j], AF[PA[g]][i], acc[i][j], 0, 0, 0); \
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BFR[PL.b[g]][j], AF[PL.a[g]][i], acc[i][j], 0, 0, 0); \
             }                                                                                                           \
         }                                                                                                               \
     }
 #define SG_PATTERN()                                                                                                    \
     {                                                                                                                   \
         __builtin_amdgcn_sched_group_barrier(0x008, SG_LEAD, 0);                                                        \
-        _Pragma("unroll") for (int q_ = 0; q_ < 9 * TM * TN - SG_LEAD; ++q_) {                                          \
-            __builtin_amdgcn_sched_group_barrier(0x002, SG_VPM, 0);                                                     \
+        _Pragma("unroll") for (int q_ = 0; q_ < NP * TM * TN - SG_LEAD; ++q_) {                                         \
+            __builtin_amdgcn_sched_group_barrier(0x002, NP == 9 ? SG_VPM : SG_VPM6, 0);                                 \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                          \
         }                                                                                                               \
     }
@@ -559,8 +603,8 @@ __global__ __launch_bounds__(256, 2) void split_gemm_pipe_kernel(const float* __
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    constexpr int PA[9] = {2, 2, 1, 1, 2, 0, 1, 0, 0};
-    constexpr int PB[9] = {2, 1, 2, 1, 0, 2, 0, 1, 0};
+    static_assert(NP == 9 || NP == 6, "9 or 6 plane products");
+    constexpr Planes PL = plane_order(NP);
 
     SG_DMA(0, 0)
     SG_DMA(1, 1)
@@ -663,12 +707,29 @@ static double now_ms(hipEvent_t e0, hipEvent_t e1) {
     return ms;
 }
 
-static void host_split(float x, float& h, float& m, float& l) {
+static float host_rne_bf16(float x) {  // round to nearest even at 8 significand bits (finite x)
+    unsigned u;
+    memcpy(&u, &x, 4);
+    u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+    float r;
+    memcpy(&r, &u, 4);
+    return r;
+}
+static void host_split(float x, float& h, float& m, float& l, bool rne) {
+    if (rne) {
+        h = host_rne_bf16(x);
+        const float r = x - h;
+        m = host_rne_bf16(r);
+        l = r - m;
+        return;
+    }
     unsigned a, b, c;
     split3(x, a, b, c);
     a <<= 16; b <<= 16; c <<= 16;
     memcpy(&h, &a, 4); memcpy(&m, &b, 4); memcpy(&l, &c, 4);
 }
+
+struct Mode { int np; bool rne; const char* name; };
 
 int main(int argc, char** argv) {
     const bool speed_only = argc > 1 && !strcmp(argv[1], "speed");
@@ -694,8 +755,8 @@ int main(int argc, char** argv) {
             CK(hipEventSynchronize(e1));
             const double ms = now_ms(e0, e1);
             const double flop = (double)blocks * 4 * iters * 36 * 32768.0;
-            printf("== bf16 32x32x16 MFMA register loop, %d workgroup(s) per CU: %.1f ms, %.0f TFLOP/s bf16 = %.1f fp32-equivalent (9 products)\n", wg_per_cu, ms, flop / ms / 1e9,
-                   flop / ms / 1e9 / 9.0);
+            printf("== bf16 32x32x16 MFMA register loop, %d workgroup(s) per CU: %.1f ms, %.0f TFLOP/s bf16 = %.1f fp32-equivalent (9 products), %.1f (6 products)\n", wg_per_cu, ms,
+                   flop / ms / 1e9, flop / ms / 1e9 / 9.0, flop / ms / 1e9 / 6.0);
         }
     }
     if (!speed_only) {
@@ -739,16 +800,23 @@ int main(int argc, char** argv) {
 
     struct Shape { const char* name; int M, N, K; };
     std::vector<Shape> acc_shapes = {{"acc.uniform", 256, 512, 1024}, {"acc.k4096", 256, 512, 4096}};
-    std::vector<Shape> speed_shapes = {{"stride test 16000x4096x1056", 16000, 4096, 1056}, {"stride test 16000x4096x992", 16000, 4096, 992},
-                                       {"stride test 8000x3072x1056", 8000, 3072, 1056}, {"stride test 9056x2048x544", 9056, 2048, 544},
-                                       {"dec.ffn1 16000x4096x1024", 16000, 4096, 1024}, {"bt.in_proj 8000x3072x1024", 8000, 3072, 1024},
+    std::vector<Shape> speed_shapes = {{"dec.ffn1 16000x4096x1024", 16000, 4096, 1024}, {"bt.in_proj 8000x3072x1024", 8000, 3072, 1024},
                                        {"dec.qkv 16000x2304x1024", 16000, 2304, 1024},  {"dec.w2 16000x1024x4096", 16000, 1024, 4096},
                                        {"bt.lin2 8000x1024x2048", 8000, 1024, 2048},     {"bt.o 8000x1024x1024", 8000, 1024, 1024},
                                        {"mimi.lin1 9056x2048x512", 9056, 2048, 512},     {"mimi.lin2 9056x512x2048", 9056, 512, 2048},
                                        {"mimi.in 9056x1536x512", 9056, 1536, 512},       {"mimi.out 9056x512x512", 9056, 512, 512},
                                        {"cal 8192x4096x4096", 8192, 4096, 4096}};
 
-    auto run = [&](const Shape& s, int dist, bool check, int reps) {
+    // SG_MODES: comma-separated subset of 9t (9 products, truncation split: r05), 6t (6 products, truncation), 6r (6 products, RNE split)
+    std::vector<Mode> modes;
+    {
+        const char* env = getenv("SG_MODES");
+        const std::string want = env ? env : "9t,6t,6r";
+        if (want.find("9t") != std::string::npos) modes.push_back({9, false, "split9 trunc"});
+        if (want.find("6t") != std::string::npos) modes.push_back({6, false, "split6 trunc"});
+        if (want.find("6r") != std::string::npos) modes.push_back({6, true, "split6 RNE"});
+    }
+    auto run = [&](const Shape& s, int dist, bool check, int reps, const Mode& mode) {
         const long long M = s.M, N = s.N, K = s.K;
         std::vector<float> hx(M * K), hw(N * K), hb(N);
         std::mt19937_64 rng(1234 + M + N + K + dist);
@@ -769,13 +837,16 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dw, hw.data(), N * K * 4, hipMemcpyHostToDevice));
         CK(hipMemcpy(db, hb.data(), N * 4, hipMemcpyHostToDevice));
         const long long ng = N * K / 8;
-        prepack_kernel<<<(unsigned)((ng + 255) / 256), 256>>>(dw, dwp, ng);
+        if (mode.rne) prepack_kernel<true><<<(unsigned)((ng + 255) / 256), 256>>>(dw, dwp, ng);
+        else prepack_kernel<false><<<(unsigned)((ng + 255) / 256), 256>>>(dw, dwp, ng);
         CK(hipGetLastError());
         const unsigned tiles = (unsigned)(((M + 127) / 128) * ((N + 127) / 128));
         const bool dma = !getenv("SG_V1");
         const bool pipe = !getenv("SG_V1") && !getenv("SG_V2");
         auto launch = [&]() {
-            if (pipe) split_gemm_pipe_kernel<128, 128><<<tiles, 256>>>(dx, dwp, db, dy, (int)M, (int)N, (int)K, 8);
+            if (pipe && mode.np == 6 && mode.rne) split_gemm_pipe_kernel<128, 128, 6, true><<<tiles, 256>>>(dx, dwp, db, dy, (int)M, (int)N, (int)K, 8);
+            else if (pipe && mode.np == 6) split_gemm_pipe_kernel<128, 128, 6, false><<<tiles, 256>>>(dx, dwp, db, dy, (int)M, (int)N, (int)K, 8);
+            else if (pipe) split_gemm_pipe_kernel<128, 128, 9, false><<<tiles, 256>>>(dx, dwp, db, dy, (int)M, (int)N, (int)K, 8);
             else if (dma) split_gemm_dma_kernel<128, 128><<<tiles, 256>>>(dx, dwp, db, dy, (int)M, (int)N, (int)K, 8);
             else split_gemm_kernel<128, 128><<<tiles, 256>>>(dx, dwp, db, dy, (int)M, (int)N, (int)K, 8);
         };
@@ -785,7 +856,8 @@ int main(int argc, char** argv) {
             std::vector<float> hy(M * N);
             CK(hipMemcpy(hy.data(), dy, M * N * 4, hipMemcpyDeviceToHost));
             // references on sampled rows: fp64, the fp32 fmaf chain in k order (what v_mfma_f32_32x32x2_f32 computes, bitwise), and the
-            // 9-product sum evaluated in fp64 (must equal the fp64 reference: the split is exact)
+            // kept plane products evaluated in fp64 (9 products: must equal the fp64 reference, the split is exact; 6 products: the dropped
+            // ml + lm + ll, printed relative to sum |a b|)
             double e_split = 0, e_chain = 0, e_split_max = 0, e_chain_max = 0, den = 0, split_exact_dev = 0;
             double rel_rms_s = 0, rel_rms_c = 0, ref_rms = 0;
             long long cnt = 0;
@@ -800,12 +872,14 @@ int main(int argc, char** argv) {
                         c = fmaf(a, b, c);
                         if (n < 8) {
                             float ah, am, al, bh, bm, bl;
-                            host_split(a, ah, am, al); host_split(b, bh, bm, bl);
-                            r9 += ((double)ah + am + al) * ((double)bh + bm + bl);
+                            host_split(a, ah, am, al, mode.rne); host_split(b, bh, bm, bl, mode.rne);
+                            if ((double)ah + am + al != (double)a || (double)bh + bm + bl != (double)b) split_exact_dev = INFINITY;
+                            if (mode.np == 9) r9 += ((double)ah + am + al) * ((double)bh + bm + bl);
+                            else r9 += (double)ah * bl + (double)al * bh + (double)am * bm + (double)ah * bm + (double)am * bh + (double)ah * bh;
                         }
                     }
                     c += hb[n];
-                    if (n < 8) split_exact_dev = fmax(split_exact_dev, fabs(r9 - r));
+                    if (n < 8) split_exact_dev = fmax(split_exact_dev, fabs(r9 - r) / sabs);
                     const double es = fabs((double)hy[m * N + n] - r) / sabs, ec = fabs((double)c - r) / sabs;
                     e_split += es; e_chain += ec;
                     e_split_max = fmax(e_split_max, es); e_chain_max = fmax(e_chain_max, ec);
@@ -816,9 +890,10 @@ int main(int argc, char** argv) {
                 }
             }
             (void)den;
-            printf("  %-14s dist=%d M=%lld N=%lld K=%lld : |err| / sum|a b|  split9 mean %.3e max %.3e | fp32 chain mean %.3e max %.3e | rel RMS split9 %.3e chain %.3e | "
-                   "fp64(9 products) - fp64 = %.1e\n",
-                   s.name, dist, M, N, K, e_split / cnt, e_split_max, e_chain / cnt, e_chain_max, sqrt(rel_rms_s / ref_rms), sqrt(rel_rms_c / ref_rms), split_exact_dev);
+            printf("  %-14s %s dist=%d M=%lld N=%lld K=%lld : |err| / sum|a b|  split mean %.3e max %.3e | fp32 chain mean %.3e max %.3e | rel RMS split %.3e chain %.3e | "
+                   "|fp64(kept products) - fp64| / sum|a b| max = %.1e\n",
+                   s.name, mode.name, dist, M, N, K, e_split / cnt, e_split_max, e_chain / cnt, e_chain_max, sqrt(rel_rms_s / ref_rms), sqrt(rel_rms_c / ref_rms),
+                   split_exact_dev);
             // determinism: three launches, same bits
             std::vector<float> hy2(M * N);
             bool same = true;
@@ -827,7 +902,7 @@ int main(int argc, char** argv) {
                 CK(hipMemcpy(hy2.data(), dy, M * N * 4, hipMemcpyDeviceToHost));
                 same = same && !memcmp(hy.data(), hy2.data(), M * N * 4);
             }
-            printf("  %-14s three launches bit-identical: %s\n", s.name, same ? "yes" : "NO");
+            printf("  %-14s %s three launches bit-identical: %s\n", s.name, mode.name, same ? "yes" : "NO");
         } else {
             for (int i = 0; i < 2; ++i) launch();
             CK(hipEventRecord(e0));
@@ -844,11 +919,15 @@ int main(int argc, char** argv) {
         CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(db)); CK(hipFree(dy)); CK(hipFree(dwp));
     };
     if (!speed_only) {
-        printf("== numerics: 9 bf16 plane products vs the fp32 fma chain, both against fp64 (rows sampled every 4th)\n");
-        for (auto& s : acc_shapes)
-            for (int dist = 0; dist < 2; ++dist) run(s, dist, true, 0);
+        printf("== numerics: bf16 plane products vs the fp32 fma chain, both against fp64 (rows sampled every 4th)\n");
+        for (const Mode& md : modes)
+            for (auto& s : acc_shapes)
+                for (int dist = 0; dist < 2; ++dist) run(s, dist, true, 0, md);
     }
-    printf("== speed: %s<128,128>, SG_STORE_AT=%d SG_VARIANT=%d\n", getenv("SG_V1") ? "split_gemm_kernel (register staging)" : getenv("SG_V2") ? "split_gemm_dma_kernel" : "split_gemm_pipe_kernel", SG_STORE_AT, SG_VARIANT);
-    for (auto& s : speed_shapes) run(s, 0, false, 10);
+    for (const Mode& md : modes) {
+        printf("== speed: %s<128,128>, %s, SG_STORE_AT=%d SG_VARIANT=%d\n", getenv("SG_V1") ? "split_gemm_kernel (register staging)" : getenv("SG_V2") ? "split_gemm_dma_kernel" : "split_gemm_pipe_kernel",
+               md.name, SG_STORE_AT, SG_VARIANT);
+        for (auto& s : speed_shapes) run(s, 0, false, 10, md);
+    }
     return 0;
 }

@@ -132,6 +132,9 @@ struct ConvParams {
     float* am_dist;
     int* am_idx;
     int am_ld;
+    // 1: this launch keeps the fp32 chain whatever QA_GEMM_MATH says.  The UniSE LM's projections: its decode-step GEMVs sum every row
+    // in fp32 order, and a sequence's logits must not depend on which rows of its batch went through which kernel.
+    int math_fp32;
 };
 
 // Live measurement hook (bench.py): when enabled every conv_gemm launch is bracketed by HIP events on its own stream.

@@ -12,6 +12,8 @@
 // the current tile's MFMAs).  LDS rows are padded to 36 floats so that the ds_read_b128 fragment loads are
 // bank-conflict free; each lane fetches 4 consecutive k per read and the (lane>>5) halves take k-groups
 // {0..3},{4..7}: the K order inside a step is permuted identically for A and B, which leaves the sum unchanged.
+// That is the fp32 chain (QA_GEMM_MATH = 0).  The default, split-6 (QA_GEMM_MATH = 1, split4_rne below), runs the same tiles on the
+// bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.
 #include <cstdlib>
 #include <type_traits>
 
@@ -46,6 +48,48 @@ namespace qa {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (float4 arrays were left as scratch allocas)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// Split-6 math (QA_GEMM_MATH = 1).  Each operand is split, exactly, into three bf16 planes x = h + m + l by round-to-nearest-even:
+// h = rne(x), m = rne(x - h), l = x - h - m.  Both subtractions are exact and l keeps <= 8 significant bits (sign borrowing), so
+// |m| <= 2^-8 |x| and |l| <= 2^-16 |x|.  A 16-wide k group then takes six v_mfma_f32_32x32x16_bf16 (every bf16 x bf16 product is exact
+// in fp32), smallest terms first: hl, lh, mm, hm, mh, hh (activation plane first).  The dropped ml, lm and ll are each <= 2^-24 |ab|,
+// the size of one fp32 rounding, of random sign.  Non-finite x: h = x and m = l = 0 (the residual is zeroed when it is not finite),
+// so inf and NaN reach the sum through hh exactly as through the fp32 chain.  A finite |x| that rounds past the largest bf16
+// (>= 2^128 (1 - 2^-9)) becomes h = inf.
+__device__ __forceinline__ unsigned rne_bf16x2(float a, float b) {  // low half bf16(a), high half bf16(b): one v_cvt_pk_bf16_f32
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ void split4_rne(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float a = x[2 * i], b = x[2 * i + 1];
+        const unsigned h = rne_bf16x2(a, b);
+        float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
+        ra = __builtin_isfinite(ra) ? ra : 0.f;
+        rb = __builtin_isfinite(rb) ? rb : 0.f;
+        const unsigned m = rne_bf16x2(ra, rb);
+        ph[i] = h;
+        pm[i] = m;
+        pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
+    }
+}
+
+// LDS bytes of one conv_gemm configuration (fp32 image with 4-float row padding, or three bf16 planes) and the workgroups per CU that
+// the register budget is tuned for
+__host__ __device__ constexpr int conv_gemm_lds_bytes(int BM, int BN, int BK, bool split) {
+    return (split ? 2 * (BM + BN) * 3 * BK * 2 : 2 * (BM + BN) * (BK + 4) * 4) + BM * 8 * 4;
+}
+__host__ __device__ constexpr int conv_gemm_min_wg(int BM, int BN, int BK, bool split) {
+    const int regs = BM == 256 ? (BK == 16 ? 2 : 1) : (BM == 64 && (BK == 16 || BN == 64) ? 4 : (BK == 16 ? 3 : 2));
+    const int lds = 160 * 1024 / conv_gemm_lds_bytes(BM, BN, BK, split);
+    return regs < lds ? regs : (lds < 1 ? 1 : lds);
+}
 
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -101,8 +145,13 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const ConvParams& p, long lo
 // x + m * ldx, so the per-chunk source-frame lookup (LDS read, clamp, select, 64-bit address build) and the padding multiply
 // disappear from the main loop - about 20 of its ~50 non-MFMA instructions, each of which costs ~30 cycles beside the co-resident
 // workgroup's MFMAs.
-template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false>
-__global__ __launch_bounds__(256, (BM == 256 ? (BK == 16 ? 2 : 1) : (BM == 64 && (BK == 16 || BN == 64) ? 4 : (BK == 16 ? 3 : 2)))) void conv_gemm_kernel(const ConvParams p_in) {
+//
+// SPLIT: split-6 math (above).  The staging threads split their activation / weight float4 after the zero-padding mask and the ELU
+// prologue and store three bf16 planes; a plane row is BK bf16 = BK / 8 16-byte slots, slot s of row r sits at s ^ swz(r) so that the
+// 16 lanes one ds_read_b128 group serves cover all 64 banks.  Per output element the order is fixed: 16-wide k groups ascending, six
+// MFMAs per group in the order above, one fp32 accumulator - independent of BM, BN, BK and the tile order, like the fp32 chain.
+template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false, bool SPLIT = false>
+__global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv_gemm_kernel(const ConvParams p_in) {
     ConvParams p = p_in;
     constexpr int LDS = BK + 4;
     constexpr int RPP = 256 / (BK / 4);  // rows staged per pass: 8 (BK=32) or 4 (BK=16) threads cover one row chunk
@@ -112,10 +161,16 @@ __global__ __launch_bounds__(256, (BM == 256 ? (BK == 16 ? 2 : 1) : (BM == 64 &&
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(TM >= 1 && TN >= 1, "wave tile must hold at least one 32x32 MFMA tile");
 
-    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + BN) * LDS];
+    constexpr int SMEM_FLOATS = SPLIT ? 2 * (BM + BN) * 3 * BK / 2 : 2 * (BM + BN) * LDS;
+    __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
     __shared__ int s_tap[BM * TAP_WIN];  // source-frame offset (floats, relative to the clip) of (row, tap); -1 = zero padding
     float* sA = smem;
     float* sB = smem + 2 * BM * LDS;
+    // SPLIT image: [buffer][operand A rows, then B rows][plane h, m, l] rows of BK bf16
+    constexpr int PLANE_A = BM * BK * 2, PLANE_B = BN * BK * 2;       // bytes of one plane of one buffer
+    constexpr int BUF_BYTES = 3 * (PLANE_A + PLANE_B);
+    char* const sbytes = reinterpret_cast<char*>(smem);
+    auto swz = [](int row, int slot) { return BK == 16 ? slot ^ ((row >> 3) & 1) : slot ^ ((row >> 2) & 3); };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -225,7 +280,31 @@ __global__ __launch_bounds__(256, (BM == 256 ? (BK == 16 ? 2 : 1) : (BM == 64 &&
         _Pragma("unroll") for (int i = 0; i < B_IT; ++i) b_reg[i] = *reinterpret_cast<const f32x4*>(b_ptr[i] + k0_); \
     }
 #define QA_STORE_LDS(BUF)                                                                                      \
-    {                                                                                                          \
+    { if constexpr (SPLIT) {                                                                                   \
+        char* a_ = sbytes + (BUF) * BUF_BYTES;                                                                 \
+        char* b_ = a_ + 3 * PLANE_A;                                                                           \
+        const int sl_ = ld_c4 >> 3, in_ = (ld_c4 & 7) * 2;                                                     \
+        _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                     \
+            f32x4 v = LINEAR ? a_reg[i] : a_reg[i] * a_keep[i];                                                \
+            if (PRO_ELU) {                                                                                     \
+                v.x = elu_f(v.x); v.y = elu_f(v.y); v.z = elu_f(v.z); v.w = elu_f(v.w);                        \
+            }                                                                                                  \
+            u32x2 h_, m_, l_;                                                                                  \
+            split4_rne(v, h_, m_, l_);                                                                         \
+            const int r_ = ld_row + RPP * i, o_ = r_ * BK * 2 + swz(r_, sl_) * 16 + in_;                       \
+            *reinterpret_cast<u32x2*>(a_ + o_) = h_;                                                           \
+            *reinterpret_cast<u32x2*>(a_ + PLANE_A + o_) = m_;                                                 \
+            *reinterpret_cast<u32x2*>(a_ + 2 * PLANE_A + o_) = l_;                                             \
+        }                                                                                                      \
+        _Pragma("unroll") for (int i = 0; i < B_IT; ++i) {                                                     \
+            u32x2 h_, m_, l_;                                                                                  \
+            split4_rne(b_reg[i], h_, m_, l_);                                                                  \
+            const int r_ = ld_row + RPP * i, o_ = r_ * BK * 2 + swz(r_, sl_) * 16 + in_;                       \
+            *reinterpret_cast<u32x2*>(b_ + o_) = h_;                                                           \
+            *reinterpret_cast<u32x2*>(b_ + PLANE_B + o_) = m_;                                                 \
+            *reinterpret_cast<u32x2*>(b_ + 2 * PLANE_B + o_) = l_;                                             \
+        }                                                                                                      \
+    } else {                                                                                                   \
         float* a_ = sA + (BUF) * BM * LDS;                                                                     \
         float* b_ = sB + (BUF) * BN * LDS;                                                                     \
         _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                     \
@@ -237,7 +316,7 @@ __global__ __launch_bounds__(256, (BM == 256 ? (BK == 16 ? 2 : 1) : (BM == 64 &&
         }                                                                                                      \
         _Pragma("unroll") for (int i = 0; i < B_IT; ++i)                                                       \
             *reinterpret_cast<f32x4*>(b_ + (ld_row + RPP * i) * LDS + ld_c4) = b_reg[i];                       \
-    }
+    } }
 
     __syncthreads();  // tap table visible
     QA_LOAD_GLOBAL(0)
@@ -258,6 +337,56 @@ __global__ __launch_bounds__(256, (BM == 256 ? (BK == 16 ? 2 : 1) : (BM == 64 &&
     // SIMD with back-to-back 64-cycle MFMAs, and then get roughly one issue slot per MFMA (measured: ~55 cycles per
     // instruction, the "address phase" lasted as long as the whole MFMA phase).
     constexpr int NKK = BK / 8;
+    if constexpr (SPLIT) {
+        // one K chunk = BK / 16 groups of 6 * TM * TN MFMAs; the next chunk's global loads ride in front of group 0 and its split + LDS
+        // stores behind the last group's MFMAs (VALU that depends on nothing the MFMAs write issues underneath them)
+        constexpr int NG = BK / 16;
+        const int sl_h = lane >> 5;
+        int a_off[TM], b_off[TN];  // byte offsets of this lane's fragments (plane h of buffer 0, group 0)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int r = wm * WTM + i * 32 + frag_row;
+            a_off[i] = r * BK * 2 + swz(r, sl_h) * 16;
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int r = wn * WTN + j * 32 + frag_row;
+            b_off[j] = 3 * PLANE_A + r * BK * 2 + swz(r, sl_h) * 16;
+        }
+        for (int kc = 0; kc < nk; ++kc) {
+            const int cur = kc & 1;
+            const int nxt = min(kc + 1, nk - 1);
+            const char* base = sbytes + cur * BUF_BYTES;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                // group g of a row is slots 2g (k 0..7) and 2g + 1 (k 8..15); swz XORs the slot with row bits, so the swizzled slot of
+                // 2g + h is (h ^ x) ^ 2g: the byte offset of group 0, XOR 32 g
+                bf16x8 af[3][TM], bf[3][TN];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+                        af[pl][i] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_A + (a_off[i] ^ (32 * g)));
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        bf[pl][j] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_B + (b_off[j] ^ (32 * g)));
+                }
+                if (g == 0) QA_LOAD_GLOBAL(nxt)
+                if (g == NG - 1) QA_STORE_LDS(cur ^ 1)
+                // operands swapped as in the fp32 loop below; planes 0 = h, 1 = m, 2 = l; order hl, lh, mm, hm, mh, hh
+                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PW[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PW[q]][j], af[PA[q]][i], acc[i][j], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();
+        }
+    } else
     for (int kc = 0; kc < nk; ++kc) {
         const int cur = kc & 1;
         const int nxt = min(kc + 1, nk - 1);
@@ -436,23 +565,33 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
         const double elems = (double)p.B * p.T_in * p.C_in + n * k + out_elems;
         profile_record_begin(cfg, 2.0 * (double)p.M * n * k, 4.0 * elems, stream, &p);
     }
+    // QA_GEMM_MATH: 1 = split-6 (bf16 planes, default), 0 = the fp32 chain; the same for every launch whatever its M
+    const bool split = knob(K_GEMM_MATH) != 0 && !p.math_fp32;
+#define QA_GEMM_GO(BM_, BN_, WM_, WN_, ELU_, BK_, LIN_)                                                                              \
+    {                                                                                                                               \
+        if (split)                                                                                                                  \
+            hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
+        else                                                                                                                        \
+            hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
+    }
     if constexpr (BM == 256) {  // r06 experiment (QA_GEMM_256): LINEAR layers only, BK = 16 (61 KB of LDS: two workgroups per CU)
         QA_REQUIRE(linear && p.prologue != ACT_ELU, "conv_gemm: the 256 x 128 tile exists for LINEAR layers only");
-        hipLaunchKernelGGL((conv_gemm_kernel<256, 128, 2, 2, false, 16, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        QA_GEMM_GO(256, 128, 2, 2, false, 16, true)
         if (prof) profile_record_end(stream);
         QA_LAUNCH_CHECK();
         return QA_OK;
     } else
     if (bk16 && linear)
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, (BN >= 64 ? 16 : 32), true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        QA_GEMM_GO(BM, BN, WM, WN, false, (BN >= 64 ? 16 : 32), true)
     else if (bk16)
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, (BN >= 64 ? 16 : 32)>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        QA_GEMM_GO(BM, BN, WM, WN, false, (BN >= 64 ? 16 : 32), false)
     else if (p.prologue == ACT_ELU)
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        QA_GEMM_GO(BM, BN, WM, WN, true, 32, false)
     else if (linear)
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false, 32, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        QA_GEMM_GO(BM, BN, WM, WN, false, 32, true)
     else
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        QA_GEMM_GO(BM, BN, WM, WN, false, 32, false)
+#undef QA_GEMM_GO
     if (prof) profile_record_end(stream);
     QA_LAUNCH_CHECK();
     return QA_OK;

@@ -135,6 +135,7 @@ struct Ctx {
     Arena arena;
     hipStream_t stream = nullptr;
     bool dry = false;      // planning pass: allocate, do not launch
+    bool gemm_fp32 = false;  // conv_op launches keep conv_gemm's fp32 chain (ConvParams::math_fp32)
     bool capture = false;  // test hook: snapshot named intermediates (buffers are reused / updated in place later)
     std::unordered_map<std::string, Tap> taps;
     void tap(const std::string& name, const float* p, int64_t n) {
@@ -306,6 +307,7 @@ inline int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const C
     p.algo_k = w.algo_cin ? w.algo_cin * w.ksize : 0;
     p.rope = o.rope; p.rope_n = o.rope_n; p.rope_hd = o.rope_hd; p.rope_T = o.rope_T; p.rope_pos0 = o.rope_pos0;
     p.alpha = o.alpha; p.y2 = o.y2; p.alpha2 = o.alpha2; p.ldy2 = o.ldy2;
+    p.math_fp32 = c.gemm_fp32 ? 1 : 0;
     if (o.shift) {
         p.res = o.shift;
         p.ldr = 0;

@@ -15,6 +15,7 @@ namespace qa {
     X(GEMM_256, "QA_GEMM_256", 0, "r06 experiment: 256x128 block tile (4 waves, 4x2 accumulators each) for LINEAR layers with M >= 8000 and N >= 1024; value = its efficiency relative to 128x128 in 1/1000 for the cost model (0: never chosen; QA_GEMM_CFG=5 forces it)") \
     X(GEMM_BK16, "QA_GEMM_BK16", 1 << 30, "largest K that takes the BK = 16 K-chunk variant")                                     \
     X(GEMM_BK16_MIN_TILES, "QA_GEMM_BK16_MIN_TILES", 384, "fewest tiles of a launch that take BK = 16")                          \
+    X(GEMM_MATH, "QA_GEMM_MATH", 1, "conv_gemm arithmetic: 1 = split-6 (operands split into three bf16 planes, six v_mfma_f32_32x32x16_bf16 per 16-wide k group, fp32 accumulation), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32)") \
     X(GEMM_LINEAR, "QA_GEMM_LINEAR", 1, "table-free K loop for ksize-1 layers")                                                  \
     X(GEMM_XCD, "QA_GEMM_XCD", 1, "XCD-aware tile order")                                                                        \
     X(GEMM_PANEL, "QA_GEMM_PANEL", 8, "conv_gemm tile order: column panels of this many tiles, row tiles fastest inside a panel (0: column tiles fastest over the whole row; 8: +4 % on N >= 4096 shapes, +1.2 % on H-Codec 2.0)") \
