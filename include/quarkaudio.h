@@ -244,6 +244,23 @@ typedef struct qa_conv_args {
 } qa_conv_args;
 int qa_conv1d_cl(const qa_conv_args* args, void* stream);
 
+/* ---- pre-split weight images (knob QA_GEMM_PRESPLIT) ---------------------------------------------------------
+ * conv_gemm's default arithmetic splits both operands into three bf16 planes.  Weights do not change between calls, so every model
+ * handle builds the planes of all its weights once, at load, and its launches that take a 128-column tile read them instead of
+ * splitting in the K loop (narrower tiles keep the in-loop split) - the same bits either way.  These entry points give a caller-owned weight (qa_conv1d_cl) the same route, and tests a way to read an image:
+ *   qa_weight_planes         writes the image of the device array w[0 .. n), n % 8 == 0, into `planes` (6 n bytes of device memory,
+ *                            16-byte aligned): per group of 8 floats three 16-byte units, the group's h, m and l planes as 8 bf16 each;
+ *   qa_weight_planes_attach  from now on a qa_conv1d_cl whose weight (all N rows) lies inside w[0 .. n), on an 8-float boundary,
+ *                            reads `planes` when it takes a 128-column tile; w must not change while attached, and ranges must not overlap;
+ *   qa_weight_planes_detach  undoes it (before either buffer is freed);
+ *   qa_weight_planes_bytes   bytes of all images attached in this process, the handles' included;
+ *   qa_weight_plane_offset   host logic, no device: byte offset inside the image of element `index`, plane 0 (h), 1 (m) or 2 (l). */
+int qa_weight_planes(const float* w, int64_t n, void* planes, void* stream);
+int qa_weight_planes_attach(const float* w, int64_t n, const void* planes);
+int qa_weight_planes_detach(const float* w);
+int64_t qa_weight_planes_bytes(void);
+int64_t qa_weight_plane_offset(int64_t index, int32_t plane);
+
 /* ---- host logic exposed for CPU tests (no device needed) ------------------------------------------------
  * SConv1d geometry of the reference (encoder_modules/conv.py:54-61,195-211, non-causal): for an input of L frames,
  * kernel k (dilation 1) and stride s it yields T_out = ceil(L/s) and the (left, right + extra) reflect paddings. */

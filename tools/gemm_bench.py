@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the implicit-GEMM kernel on the shapes H-Codec 1.0 (B=32 x 10 s) actually launches.
-usage: [QA_GEMM_CFG=0|1|2] [QA_GEMM_XCD=0|1] python tools/gemm_bench.py"""
+usage: [QA_GEMM_CFG=0|1|2] [QA_GEMM_XCD=0|1] [QA_BENCH_PLANES=1] python tools/gemm_bench.py
+QA_BENCH_PLANES=1 gives every weight a pre-split image (qa_weight_planes / qa_weight_planes_attach), the route a loaded model takes."""
 import os
 import sys
 
@@ -35,6 +36,20 @@ def bench_shape(lib, dev, M, N, C, k, s, reps=5):
     x = torch.randn(1, T + k, C, device=dev, generator=g)
     w = torch.randn(N, k, C, device=dev, generator=g) * 0.05
     b = torch.randn(N, device=dev, generator=g)
+    planes = None
+    if os.environ.get("QA_BENCH_PLANES") == "1":
+        planes = torch.empty(w.numel() * 6, dtype=torch.uint8, device=dev)
+        assert lib.qa_weight_planes(w.data_ptr(), w.numel(), planes.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
+        assert lib.qa_weight_planes_attach(w.data_ptr(), w.numel(), planes.data_ptr()) == 0
+    try:
+        return _timed(lib, x, w, b, s, M, reps)
+    finally:
+        if planes is not None:
+            torch.cuda.synchronize()
+            lib.qa_weight_planes_detach(w.data_ptr())
+
+
+def _timed(lib, x, w, b, s, M, reps):
     for _ in range(2):
         y = conv1d_cl(lib, x, w, b, stride=s, T_out=M)
     e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)

@@ -141,6 +141,11 @@ SYMBOLS = {
     "qa_rvq_lookup": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_void_p]),
     "qa_conv1d_cl": (C.c_int, [C.POINTER(qa_conv_args), C.c_void_p]),
+    "qa_weight_planes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_weight_planes_attach": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "qa_weight_planes_detach": (C.c_int, [C.c_void_p]),
+    "qa_weight_planes_bytes": (C.c_int64, []),
+    "qa_weight_plane_offset": (C.c_int64, [C.c_int64, C.c_int32]),
     "qa_sconv_geometry": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "qa_resolve_frame": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "qa_profile_begin": (C.c_int, []),

@@ -12,6 +12,7 @@
 
 #include "kernels.h"
 #include "knobs.h"
+#include "split_planes.h"
 
 namespace qa {
 // ---- the knob table (knobs.h): values start from the environment, qa_set_knob() overrides at run time
@@ -306,6 +307,20 @@ int qa_conv1d_cl(const qa_conv_args* args, void* stream) {
     ConvParams p;
     QA_TRY(conv_params_from_args(*args, &p));
     return launch_conv_gemm(p, static_cast<hipStream_t>(stream));
+}
+
+int qa_weight_planes(const float* w, int64_t n, void* planes, void* stream) {
+    return launch_weight_planes(w, n, planes, static_cast<hipStream_t>(stream));
+}
+int qa_weight_planes_attach(const float* w, int64_t n, const void* planes) { return weight_planes_attach(w, n, planes); }
+int qa_weight_planes_detach(const float* w) {
+    weight_planes_detach(w);
+    return QA_OK;
+}
+int64_t qa_weight_planes_bytes(void) { return weight_planes_bytes(); }
+int64_t qa_weight_plane_offset(int64_t index, int32_t plane) {
+    if (index < 0 || plane < 0 || plane > 2) return QA_ERR_INVALID;
+    return plane_byte_offset(index, plane);
 }
 
 int qa_codes_check_async(const int64_t* codes, int64_t n, int64_t lo, int64_t limit, int64_t* bad_count_dev, void* stream) {

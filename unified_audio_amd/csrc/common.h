@@ -135,6 +135,9 @@ struct ConvParams {
     // 1: this launch keeps the fp32 chain whatever QA_GEMM_MATH says.  The UniSE LM's projections: its decode-step GEMVs sum every row
     // in fp32 order, and a sequence's logits must not depend on which rows of its batch went through which kernel.
     int math_fp32;
+    // Pre-split image of w (split_planes.h), or null: set by launch_conv_gemm from the attached images (QA_GEMM_PRESPLIT).  The
+    // split-6 instances then copy plane units into LDS instead of splitting the weight tile in the K loop; same bits either way.
+    const void* wp;
 };
 
 // Live measurement hook (bench.py): when enabled every conv_gemm launch is bracketed by HIP events on its own stream.
@@ -156,6 +159,13 @@ void profile_record_begin(int cfg, double flops, double bytes, hipStream_t s, co
 void profile_record_end(hipStream_t s);
 
 int launch_conv_gemm(const ConvParams& p, hipStream_t stream);
+// Pre-split weight images (conv_gemm.hip, split_planes.h): build the image of w[0 .. n) (6 n bytes, n % 8 == 0) on `stream`; attach it,
+// so that conv_gemm launches whose weight lies inside w[0 .. n) read it; detach it again (before either buffer is freed); bytes of
+// all attached images of the process
+int launch_weight_planes(const float* w, long long n, void* planes, hipStream_t stream);
+int weight_planes_attach(const float* w, long long n, const void* planes);
+void weight_planes_detach(const float* w);
+long long weight_planes_bytes();
 int conv_params_from_args(const qa_conv_args& a, ConvParams* p);
 
 }  // namespace qa

@@ -14,10 +14,14 @@
 // {0..3},{4..7}: the K order inside a step is permuted identically for A and B, which leaves the sum unchanged.
 // That is the fp32 chain (QA_GEMM_MATH = 0).  The default, split-6 (QA_GEMM_MATH = 1, split4_rne below), runs the same tiles on the
 // bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.
+#include <algorithm>
 #include <cstdlib>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
+#include "split_planes.h"
 
 // tuning knobs of tools/variants.py
 #ifndef QA_LOAD_AT  // MFMA group of a K chunk that carries the next chunk's global loads
@@ -47,37 +51,78 @@ extern "C" int qa_debug_timing(unsigned long long* out, int reset) {
 namespace qa {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (float4 arrays were left as scratch allocas)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// Split-6 math (QA_GEMM_MATH = 1).  Each operand is split, exactly, into three bf16 planes x = h + m + l by round-to-nearest-even:
-// h = rne(x), m = rne(x - h), l = x - h - m.  Both subtractions are exact and l keeps <= 8 significant bits (sign borrowing), so
-// |m| <= 2^-8 |x| and |l| <= 2^-16 |x|.  A 16-wide k group then takes six v_mfma_f32_32x32x16_bf16 (every bf16 x bf16 product is exact
-// in fp32), smallest terms first: hl, lh, mm, hm, mh, hh (activation plane first).  The dropped ml, lm and ll are each <= 2^-24 |ab|,
-// the size of one fp32 rounding, of random sign.  Non-finite x: h = x and m = l = 0 (the residual is zeroed when it is not finite),
-// so inf and NaN reach the sum through hh exactly as through the fp32 chain.  A finite |x| that rounds past the largest bf16
-// (>= 2^128 (1 - 2^-9)) becomes h = inf.
-__device__ __forceinline__ unsigned rne_bf16x2(float a, float b) {  // low half bf16(a), high half bf16(b): one v_cvt_pk_bf16_f32
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split4_rne(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float a = x[2 * i], b = x[2 * i + 1];
-        const unsigned h = rne_bf16x2(a, b);
-        float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
-        ra = __builtin_isfinite(ra) ? ra : 0.f;
-        rb = __builtin_isfinite(rb) ? rb : 0.f;
-        const unsigned m = rne_bf16x2(ra, rb);
-        ph[i] = h;
-        pm[i] = m;
-        pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
+// ---- pre-split weight images (QA_GEMM_PRESPLIT; layout and split in split_planes.h) ----
+// The weights of a model never change after load, yet the K loop splits a weight tile again for every row tile of every launch.
+// A WeightStore therefore builds the plane image of its whole blob once, at load, and attaches it here; launch_conv_gemm looks the
+// launch's weight pointer up and, when an image covers it, takes the kernel instance whose B staging copies 16-byte plane units
+// instead of splitting.  The lookup is by address, so row slices and hand-built views of a stored weight find their planes too.
+__global__ __launch_bounds__(256) void weight_planes_kernel(const float* __restrict__ w, long long groups, char* __restrict__ planes) {
+    for (long long g = blockIdx.x * 256LL + threadIdx.x; g < groups; g += gridDim.x * 256LL) {
+        u32x2 h0, m0, l0, h1, m1, l1;
+        split4_rne(*reinterpret_cast<const f32x4*>(w + g * 8), h0, m0, l0);
+        split4_rne(*reinterpret_cast<const f32x4*>(w + g * 8 + 4), h1, m1, l1);
+        u32x4* out = reinterpret_cast<u32x4*>(planes + g * PLANE_GROUP_BYTES);
+        out[0] = u32x4{h0[0], h0[1], h1[0], h1[1]};
+        out[1] = u32x4{m0[0], m0[1], m1[0], m1[1]};
+        out[2] = u32x4{l0[0], l0[1], l1[0], l1[1]};
     }
+}
+
+int launch_weight_planes(const float* w, long long n, void* planes, hipStream_t stream) {
+    QA_REQUIRE(w && planes && n >= 0 && n % 8 == 0, "weight_planes: null pointer or n=%lld not a multiple of 8", n);
+    QA_REQUIRE(((uintptr_t)w % 16) == 0 && ((uintptr_t)planes % 16) == 0, "weight_planes: w / planes must be 16-byte aligned");
+    if (n == 0) return QA_OK;
+    const long long groups = n / 8;
+    const unsigned grid = (unsigned)std::min<long long>(ceil_div(groups, 256), 256 * 64);
+    hipLaunchKernelGGL(weight_planes_kernel, dim3(grid), dim3(256), 0, stream, w, groups, static_cast<char*>(planes));
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+namespace {
+struct PlaneImage {
+    const float* w;
+    long long n;
+    const char* planes;
+};
+std::mutex g_planes_mu;
+std::vector<PlaneImage> g_planes;  // a handful of entries: one per loaded weight store
+}  // namespace
+
+int weight_planes_attach(const float* w, long long n, const void* planes) {
+    QA_REQUIRE(w && planes && n > 0 && n % 8 == 0, "weight_planes_attach: null pointer or n=%lld not a positive multiple of 8", n);
+    QA_REQUIRE(((uintptr_t)w % 32) == 0 && ((uintptr_t)planes % 16) == 0, "weight_planes_attach: w must be 32-byte, planes 16-byte aligned");
+    std::lock_guard<std::mutex> lock(g_planes_mu);
+    for (const PlaneImage& im : g_planes)
+        QA_REQUIRE(w + n <= im.w || im.w + im.n <= w, "weight_planes_attach: the range overlaps an attached image");
+    g_planes.push_back(PlaneImage{w, n, static_cast<const char*>(planes)});
+    return QA_OK;
+}
+
+void weight_planes_detach(const float* w) {
+    std::lock_guard<std::mutex> lock(g_planes_mu);
+    for (size_t i = 0; i < g_planes.size(); ++i)
+        if (g_planes[i].w == w) {
+            g_planes.erase(g_planes.begin() + (long)i);
+            return;
+        }
+}
+
+long long weight_planes_bytes() {
+    std::lock_guard<std::mutex> lock(g_planes_mu);
+    long long total = 0;
+    for (const PlaneImage& im : g_planes) total += im.n / 8 * PLANE_GROUP_BYTES;
+    return total;
+}
+
+// the planes of w[0 .. n) when one attached image covers them and w sits on an 8-float group of it; else nullptr (split in the loop)
+static const char* weight_planes_find(const float* w, long long n) {
+    std::lock_guard<std::mutex> lock(g_planes_mu);
+    for (const PlaneImage& im : g_planes)
+        if (w >= im.w && w + n <= im.w + im.n && ((w - im.w) & 7) == 0) return im.planes + plane_byte_offset(w - im.w, 0);
+    return nullptr;
 }
 
 // LDS bytes of one conv_gemm configuration (fp32 image with 4-float row padding, or three bf16 planes) and the workgroups per CU that
@@ -150,8 +195,15 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const ConvParams& p, long lo
 // prologue and store three bf16 planes; a plane row is BK bf16 = BK / 8 16-byte slots, slot s of row r sits at s ^ swz(r) so that the
 // 16 lanes one ds_read_b128 group serves cover all 64 banks.  Per output element the order is fixed: 16-wide k groups ascending, six
 // MFMAs per group in the order above, one fp32 accumulator - independent of BM, BN, BK and the tile order, like the fp32 chain.
-template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false, bool SPLIT = false>
+//
+// PRE (SPLIT only): the weight comes from a pre-split image (p.wp, split_planes.h).  The B tile of a chunk is BN * BK / 128 blocks of
+// 48 image units: 128 / BK rows x BK / 8 slots x 3 planes.  A staging thread owns the same unit of every chunk - one 16-byte global
+// load, one ds_write_b128, both addresses fixed before the loop - and 16 consecutive lanes write the 256 contiguous (XOR-permuted)
+// bytes that one plane of a block occupies in LDS.  The LDS image is byte for byte the one the in-loop split builds.  Instantiated
+// for the 128-column tiles only (launch_cfg).
+template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false, bool SPLIT = false, bool PRE = false>
 __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv_gemm_kernel(const ConvParams p_in) {
+    static_assert(SPLIT || !PRE, "a pre-split weight image feeds the split-6 instances only");
     ConvParams p = p_in;
     constexpr int LDS = BK + 4;
     constexpr int RPP = 256 / (BK / 4);  // rows staged per pass: 8 (BK=32) or 4 (BK=16) threads cover one row chunk
@@ -238,10 +290,28 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
         a_tab[i] = (ld_row + RPP * i) * TAP_WIN;
     }
     const float* b_ptr[B_IT];
+    if constexpr (!PRE) {
 #pragma unroll
-    for (int i = 0; i < B_IT; ++i) {
-        const int n = min(n0 + ld_row + RPP * i, p.N - 1);
-        b_ptr[i] = p.w + (long long)n * p.K + ld_c4;
+        for (int i = 0; i < B_IT; ++i) {
+            const int n = min(n0 + ld_row + RPP * i, p.N - 1);
+            b_ptr[i] = p.w + (long long)n * p.K + ld_c4;
+        }
+    }
+    // PRE: unit u = tid + 256 i of the B tile -> (block of 128 / BK rows, plane, row in block, slot)
+    constexpr int BP_UNITS = BN * BK / 128 * 48, BP_IT = PRE ? BP_UNITS / 256 : 1;
+    static_assert(!PRE || (BN == 128 && BP_UNITS % 256 == 0), "the image path exists for the 128-column tiles: every thread moves BP_IT whole units");
+    const char* bp_ptr[BP_IT];  // this thread's unit of chunk 0 in the image
+    int bp_lds[BP_IT];          // ... and its byte offset in an LDS buffer
+    if constexpr (PRE) {
+#pragma unroll
+        for (int i = 0; i < BP_IT; ++i) {
+            const int u = tid + 256 * i, v = u % 48;
+            const int pl = v >> 4, slot = v % (BK / 8);
+            const int row = u / 48 * (128 / BK) + (v & 15) / (BK / 8);
+            const int n = min(n0 + row, p.N - 1);
+            bp_ptr[i] = static_cast<const char*>(p.wp) + plane_byte_offset((long long)n * p.K + slot * 8, pl);
+            bp_lds[i] = 3 * PLANE_A + pl * PLANE_B + row * BK * 2 + swz(row, slot) * 16;
+        }
     }
     const int nk = p.K / BK;
 
@@ -256,6 +326,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
     // Staging registers of the NEXT K chunk (native vector type: float4 arrays were left as scratch allocas).  Every
     // iteration loads (the last one re-loads chunk nk-1, harmlessly).
     f32x4 a_reg[A_IT], b_reg[B_IT];
+    u32x4 bp_reg[BP_IT];  // PRE: plane units instead of b_reg
     float a_keep[A_IT];  // 0 for frames that fall into zero padding (select on the data at LDS-store time, not on the load)
 
 #define QA_LOAD_GLOBAL(KC)                                                                                     \
@@ -277,12 +348,16 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
                 a_reg[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + (unsigned)(max(off_, 0) + c_));          \
             }                                                                                                  \
         }                                                                                                      \
-        _Pragma("unroll") for (int i = 0; i < B_IT; ++i) b_reg[i] = *reinterpret_cast<const f32x4*>(b_ptr[i] + k0_); \
+        if constexpr (PRE) {                                                                                   \
+            _Pragma("unroll") for (int i = 0; i < BP_IT; ++i)                                                  \
+                bp_reg[i] = *reinterpret_cast<const u32x4*>(bp_ptr[i] + (long long)(KC) * (BK * 6)); \
+        } else {                                                                                               \
+            _Pragma("unroll") for (int i = 0; i < B_IT; ++i) b_reg[i] = *reinterpret_cast<const f32x4*>(b_ptr[i] + k0_); \
+        }                                                                                                      \
     }
 #define QA_STORE_LDS(BUF)                                                                                      \
     { if constexpr (SPLIT) {                                                                                   \
         char* a_ = sbytes + (BUF) * BUF_BYTES;                                                                 \
-        char* b_ = a_ + 3 * PLANE_A;                                                                           \
         const int sl_ = ld_c4 >> 3, in_ = (ld_c4 & 7) * 2;                                                     \
         _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                     \
             f32x4 v = LINEAR ? a_reg[i] : a_reg[i] * a_keep[i];                                                \
@@ -296,6 +371,11 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
             *reinterpret_cast<u32x2*>(a_ + PLANE_A + o_) = m_;                                                 \
             *reinterpret_cast<u32x2*>(a_ + 2 * PLANE_A + o_) = l_;                                             \
         }                                                                                                      \
+        if constexpr (PRE) {                                                                                   \
+            _Pragma("unroll") for (int i = 0; i < BP_IT; ++i)                                                  \
+                *reinterpret_cast<u32x4*>(a_ + bp_lds[i]) = bp_reg[i];                                         \
+        } else {                                                                                               \
+        char* b_ = a_ + 3 * PLANE_A;                                                                           \
         _Pragma("unroll") for (int i = 0; i < B_IT; ++i) {                                                     \
             u32x2 h_, m_, l_;                                                                                  \
             split4_rne(b_reg[i], h_, m_, l_);                                                                  \
@@ -303,7 +383,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
             *reinterpret_cast<u32x2*>(b_ + o_) = h_;                                                           \
             *reinterpret_cast<u32x2*>(b_ + PLANE_B + o_) = m_;                                                 \
             *reinterpret_cast<u32x2*>(b_ + 2 * PLANE_B + o_) = l_;                                             \
-        }                                                                                                      \
+        } }                                                                                                    \
     } else {                                                                                                   \
         float* a_ = sA + (BUF) * BM * LDS;                                                                     \
         float* b_ = sB + (BUF) * BN * LDS;                                                                     \
@@ -569,7 +649,9 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     const bool split = knob(K_GEMM_MATH) != 0 && !p.math_fp32;
 #define QA_GEMM_GO(BM_, BN_, WM_, WN_, ELU_, BK_, LIN_)                                                                              \
     {                                                                                                                               \
-        if (split)                                                                                                                  \
+        if (split && p.wp && BN_ == 128) /* narrower tiles keep the in-loop split: measured slower from an image */ \
+            hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, true, BN_ == 128>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
+        else if (split)                                                                                                             \
             hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
         else                                                                                                                        \
             hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
@@ -614,6 +696,9 @@ int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
     ConvParams q = p;
     q.xcd_swizzle = swz;
     q.panel = (int)knob(K_GEMM_PANEL);
+    // QA_GEMM_PRESPLIT: the weight's pre-split image, when a loaded store (or a caller) attached one that covers all N rows; only the
+    // split-6 instances read it
+    q.wp = knob(K_GEMM_PRESPLIT) != 0 ? weight_planes_find(p.w, (long long)p.N * p.K) : nullptr;
     // frame / in_rep by multiply-high: exact for frame * in_rep < 2^32 (frames of one clip are < 2^31 / ldx)
     auto al16 = [](const void* ptr) { return ((uintptr_t)ptr % 16) == 0; };
     q.vec_epi = p.N % 4 == 0 && p.ldy % 4 == 0 && al16(p.y) && (!p.bias || al16(p.bias)) && (!p.gamma || al16(p.gamma)) &&

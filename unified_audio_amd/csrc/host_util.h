@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "split_planes.h"
 
 namespace qa {
 
@@ -41,15 +42,22 @@ class HostTable {
     std::unordered_map<std::string, const qa_tensor*> map_;
 };
 
-// Folded weights are appended to one host blob (64-float aligned) and uploaded with a single copy.
+// Folded weights are appended to one host blob (64-float aligned) and uploaded with a single copy.  upload() also builds the
+// pre-split image of the whole blob (split_planes.h: 6 bytes per weight beside the 4 of the fp32 blob, padding, biases and raw()
+// vectors included, so that the planes of any stored weight follow from its address) and attaches it for conv_gemm's split-6
+// launches - unless `planes` is off (a handle whose conv_gemm launches all keep the fp32 chain) or QA_GEMM_PRESPLIT is 0 at load time.
+// The fp32 blob stays: the fp32 chain and every kernel that is not conv_gemm read it.
 class WeightStore {
    public:
     WeightStore() = default;
     WeightStore(const WeightStore&) = delete;
     WeightStore& operator=(const WeightStore&) = delete;
     ~WeightStore() {
+        if (planes_attached_) weight_planes_detach(dev_);
+        if (planes_) (void)hipFree(planes_);
         if (dev_) (void)hipFree(dev_);
     }
+    bool planes = true;
     size_t add(const std::vector<float>& v) { return add(v.data(), v.size()); }
     size_t add(const float* p, size_t n) {
         const size_t off = blob_.size();
@@ -58,10 +66,23 @@ class WeightStore {
         return off;
     }
     int upload() {
-        QA_HIP(hipMalloc(&dev_, blob_.size() * sizeof(float)));
-        QA_HIP(hipMemcpy(dev_, blob_.data(), blob_.size() * sizeof(float), hipMemcpyHostToDevice));
-        bytes_ = blob_.size() * sizeof(float);
+        const size_t n = blob_.size();
+        QA_HIP(hipMalloc(&dev_, n * sizeof(float)));
+        QA_HIP(hipMemcpy(dev_, blob_.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        bytes_ = n * sizeof(float);
         std::vector<float>().swap(blob_);
+        if (planes && n > 0 && knob(K_GEMM_PRESPLIT) != 0) {
+            if (hipMalloc(&planes_, n / 8 * PLANE_GROUP_BYTES) != hipSuccess) {
+                // no room for the image: the model still loads and every launch splits in the loop - same kernels, same bits
+                (void)hipGetLastError();
+                planes_ = nullptr;
+                return QA_OK;
+            }
+            QA_TRY(launch_weight_planes(dev_, (long long)n, planes_, nullptr));
+            QA_HIP(hipStreamSynchronize(nullptr));  // the handle's calls run on the caller's streams
+            QA_TRY(weight_planes_attach(dev_, (long long)n, planes_));
+            planes_attached_ = true;
+        }
         return QA_OK;
     }
     const float* ptr(size_t off) const { return dev_ + off; }
@@ -70,6 +91,8 @@ class WeightStore {
    private:
     std::vector<float> blob_;
     float* dev_ = nullptr;
+    void* planes_ = nullptr;
+    bool planes_attached_ = false;
     size_t bytes_ = 0;
 };
 

@@ -16,6 +16,7 @@ namespace qa {
     X(GEMM_BK16, "QA_GEMM_BK16", 1 << 30, "largest K that takes the BK = 16 K-chunk variant")                                     \
     X(GEMM_BK16_MIN_TILES, "QA_GEMM_BK16_MIN_TILES", 384, "fewest tiles of a launch that take BK = 16")                          \
     X(GEMM_MATH, "QA_GEMM_MATH", 1, "conv_gemm arithmetic: 1 = split-6 (operands split into three bf16 planes, six v_mfma_f32_32x32x16_bf16 per 16-wide k group, fp32 accumulation), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32)") \
+    X(GEMM_PRESPLIT, "QA_GEMM_PRESPLIT", 1, "split-6 weights from a pre-split image: a weight store builds the three bf16 planes of all its weights once, at load (6 bytes per weight beside the fp32 blob; not built when 0 at load time), and conv_gemm's 128-column tiles copy them into LDS instead of splitting the weight tile in the K loop (narrower tiles keep the in-loop split); 0 at launch = ignore the image and split in the loop; same bits either way") \
     X(GEMM_LINEAR, "QA_GEMM_LINEAR", 1, "table-free K loop for ksize-1 layers")                                                  \
     X(GEMM_XCD, "QA_GEMM_XCD", 1, "XCD-aware tile order")                                                                        \
     X(GEMM_PANEL, "QA_GEMM_PANEL", 8, "conv_gemm tile order: column panels of this many tiles, row tiles fastest inside a panel (0: column tiles fastest over the whole row; 8: +4 % on N >= 4096 shapes, +1.2 % on H-Codec 2.0)") \

@@ -127,6 +127,7 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
     // fused step did not tile it) is gone - a spec the fused step cannot tile is refused here, with the reason
     QA_REQUIRE(lm->fused_ok, "lm spec: the decode step needs hidden %% 256 == 0 (got %d), intermediate %% 256 == 0 (got %d), head_dim %% 8 == 0 and "
                "global / semantic vocabulary sizes that are multiples of 4 (got %d / %d)", d, I, sp.global_size, sp.semantic_size);
+    lm->store.planes = false;  // every conv_gemm launch of the LM keeps the fp32 chain (Ctx::gemm_fp32): no pre-split image
     Loader L(tab, lm->store);
     L.vec(&lm->task_emb, "task_embedding.weight", (int64_t)sp.num_tasks * d);
     L.vec(&lm->enroll_sos, "enroll_sos_embedding.weight", d);

@@ -1,0 +1,54 @@
+// split_planes.h - the operand split of conv_gemm's split-6 arithmetic and the memory layout of a pre-split weight image.
+//
+// The K loop (activations, and weights without an image) and the load-time image builder run the SAME device function, so an image
+// holds bit for bit what the loop would have produced.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace qa {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (float4 arrays were left as scratch allocas)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// Split-6 math (QA_GEMM_MATH = 1).  Each operand is split, exactly, into three bf16 planes x = h + m + l by round-to-nearest-even:
+// h = rne(x), m = rne(x - h), l = x - h - m.  Both subtractions are exact and l keeps <= 8 significant bits (sign borrowing), so
+// |m| <= 2^-8 |x| and |l| <= 2^-16 |x|.  A 16-wide k group then takes six v_mfma_f32_32x32x16_bf16 (every bf16 x bf16 product is exact
+// in fp32), smallest terms first: hl, lh, mm, hm, mh, hh (activation plane first).  The dropped ml, lm and ll are each <= 2^-24 |ab|,
+// the size of one fp32 rounding, of random sign.  Non-finite x: h = x and m = l = 0 (the residual is zeroed when it is not finite),
+// so inf and NaN reach the sum through hh exactly as through the fp32 chain.  A finite |x| that rounds past the largest bf16
+// (>= 2^128 (1 - 2^-9)) becomes h = inf.
+__device__ __forceinline__ unsigned rne_bf16x2(float a, float b) {  // low half bf16(a), high half bf16(b): one v_cvt_pk_bf16_f32
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ void split4_rne(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float a = x[2 * i], b = x[2 * i + 1];
+        const unsigned h = rne_bf16x2(a, b);
+        float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
+        ra = __builtin_isfinite(ra) ? ra : 0.f;
+        rb = __builtin_isfinite(rb) ? rb : 0.f;
+        const unsigned m = rne_bf16x2(ra, rb);
+        ph[i] = h;
+        pm[i] = m;
+        pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
+    }
+}
+
+// Pre-split weight image (QA_GEMM_PRESPLIT).  The image of a float array w[0 .. n), n % 8 == 0, holds 6 bytes per weight: every
+// aligned group of 8 floats becomes three consecutive 16-byte units - its h, m and l planes, 8 bf16 each, in the order of the floats.
+// A unit is exactly one 16-byte slot of one plane row of the K loop's LDS image, so a staging thread moves it with one 16-byte global
+// load and one ds_write_b128, and the 16-wide chunk of a weight row is 96 contiguous bytes.  The address depends on the float's index
+// alone: the image of a row slice w + r * K (K % 8 == 0) is the image of w advanced by plane_byte_offset(r * K, 0).
+constexpr int PLANE_GROUP_BYTES = 48;  // image bytes per 8 floats
+__host__ __device__ constexpr long long plane_byte_offset(long long index, int plane) {
+    return (index >> 3) * PLANE_GROUP_BYTES + plane * 16 + (index & 7) * 2;
+}
+
+}  // namespace qa
