@@ -585,6 +585,68 @@ int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* st
 int qa_sample_logits(const float* logits, int64_t B, int64_t width, int64_t ld, int32_t top_k, float top_p, float temperature,
                      int32_t do_sample, uint64_t seed, int64_t* out_index, void* stream);
 
+/* ---- UniSE condition encoder and the pre-training-stage entry points of the LM --------------------------------------------------
+ * CustomLlamaModel's condition path (QuarkAudio-UniSE/model/llm/llm.py:52-54,130-132,304-306): cond_input_layer (Linear cond_dim -> dim),
+ * cond_encoder (ConformerEncoder, model/llm/conformer.py:384-484) and cond_output_layer (Linear dim -> hidden_out), eval mode, fp32.
+ * One ConformerLayer: x = 0.5 FF1(x) + x; x = Attn(LN(x)) + x; x = Conv(x) + x; x = 0.5 FF2(x) + x; x = LN(x), with FF = LN -> Linear ->
+ * SiLU -> Linear, Attn = biased q / k / v / out projections around softmax(Q K^T / sqrt(dim_head)) V with rotary embedding on the first
+ * pe_attn_head heads, Conv = LN -> 1x1 (d -> 2d) -> GLU -> depthwise k "same" -> BatchNorm1d (running statistics) -> SiLU -> 1x1.
+ * Weights: the reference's keys `cond_input_layer.*`, `cond_encoder.layers.N.*`, `cond_output_layer.*`; with cond_dim = hidden_out = 0 the
+ * handle is a bare ConformerEncoder and the keys are `layers.N.*`.  A missing key, or a key under those prefixes the model does not
+ * have, fails the create (num_batches_tracked and rotary_embedding.inv_freq are accepted and ignored). */
+typedef struct qa_cond_encoder_spec {
+    int32_t cond_dim;         /* 80    log-mel bins; 0 = bare ConformerEncoder */
+    int32_t dim;              /* 512   conf/config.yaml:148-157 */
+    int32_t n_layers;         /* 6 */
+    int32_t heads;            /* 8 */
+    int32_t dim_head;         /* 64 */
+    int32_t dw_kernel;        /* 31    odd, <= 31 */
+    int32_t ff_mult;          /* 4 */
+    int32_t pe_attn_head;     /* 1     heads 0 .. p-1 of q and k are rotated; -1 = all (None) */
+    int32_t rope_interleaved; /* 1     1: adjacent channel pairs (2i, 2i+1); 0: rotate-half pairs (i, i + dim_head/2) */
+    int32_t hidden_out;       /* 512   the LM's hidden size; 0 = bare ConformerEncoder */
+    int32_t qk_norm;          /* 0     1 ("rms_norm") is refused: not in the shipped configuration */
+} qa_cond_encoder_spec;
+typedef struct qa_cond_encoder qa_cond_encoder;
+int qa_cond_encoder_create(qa_cond_encoder** out, const qa_cond_encoder_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device);
+void qa_cond_encoder_destroy(qa_cond_encoder* h);
+/* mel fp32 [B, T, cond_dim] -> out fp32 [B, T, hidden_out] (device).  mask: NULL or bytes [B, T] on the device, non-zero = valid
+ * (ConformerEncoder.forward(x, mask), conformer.py:165-187): masked keys are invisible to every query and the attention module's output
+ * rows of masked positions are zero before the residual; nothing else reads the mask.  A batch item without a valid position is an
+ * error (a masked call copies B counters to the host and waits for them; an unmasked call is asynchronous on `stream`). */
+int qa_cond_encoder_forward(qa_cond_encoder* h, const float* mel, const uint8_t* mask, int64_t B, int64_t T, float* out, void* stream);
+/* the bare ConformerEncoder: x fp32 [B, T, dim] -> out [B, T, dim] (out may alias x) */
+int qa_conformer_forward(qa_cond_encoder* h, const float* x, const uint8_t* mask, int64_t B, int64_t T, float* out, void* stream);
+/* test hooks, as qa_hcodec_enable_taps / qa_hcodec_tap: conformer.N.ff1 (x after the first half-step), conformer.N.attn (the attention
+ * module's output, masked rows zero, before the residual), conformer.N.conv (x after the convolution module), conformer.N.out; [B, T, dim] */
+int qa_cond_encoder_enable_taps(qa_cond_encoder* h, int on);
+int64_t qa_cond_encoder_tap(qa_cond_encoder* h, const char* name, float* dst, int64_t cap, void* stream);
+
+/* Model.stft_logmel (QuarkAudio-UniSE/model/model.py:53-79): wav fp32 [B, n] is zero-padded by (win - hop) / 2 in front and to a multiple
+ * of the hop plus (win - hop) / 2 behind, STFT (periodic Hann, center = False), magnitude, HTK mel filter bank f_min .. f_max without
+ * normalisation, log(mel + 1e-10) -> out fp32 [B, qa_logmel_frames(n, hop), n_mels].  Needs win_length = 2 * hop_length, hop a multiple
+ * of 16 and n_fft >= win_length; other configurations are refused.  The function has no handle: the DFT basis, the filter bank and a
+ * workspace of each (device, parameter set) are built on first use and kept for the life of the process (1.7 MB + workspace for the
+ * UniSE configuration), and calls with the same parameters are serialised on the host while they queue their work. */
+int64_t qa_logmel_frames(int64_t n, int32_t hop_length);
+int qa_logmel(const float* wav, int64_t B, int64_t n, int32_t n_fft, int32_t win_length, int32_t hop_length, int32_t n_mels, int32_t sample_rate,
+              float f_min, float f_max, float* out, void* stream);
+
+/* CustomLlamaModel.generate (llm.py:291-374) on a qa_lm handle: prompt [mix_sos, cond_embeds] (cond_embeds fp32 [B, T, hidden] on the
+ * device, the condition encoder's output) or NO prompt (cond_embeds NULL and T = 0: the first step runs at position 0 over an empty
+ * cache).  Exactly `global_length` global steps, then semantic_sos and `semantic_length` semantic steps.  Other arguments as
+ * qa_lm_generate / qa_lm_generate_sampled.  Taps: "logits.global" is [B, global_length, global_size] after these calls. */
+int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
+                        float temperature, int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream);
+int qa_lm_generate_cond_sampled(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
+                                float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
+                                void* stream);
+/* CustomLlamaModel.forward (llm.py:107-147): as qa_lm_score with the prompt above, and with the LAST input / target position dropped
+ * (llm.py:126-127): Lt = global_length + semantic_length + 1, no semantic_eos target.  "logits.forced" is [B, Lt, V]. */
+int qa_lm_score_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, const int64_t* global_ids, int32_t global_length,
+                     const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing, float* loss_per_seq,
+                     int64_t* correct_per_seq, float* loss, float* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

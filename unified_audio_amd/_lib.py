@@ -96,6 +96,12 @@ class qa_bicodec_forward_spec(C.Structure):
     ]
 
 
+class qa_cond_encoder_spec(C.Structure):
+    _fields_ = [("cond_dim", C.c_int32), ("dim", C.c_int32), ("n_layers", C.c_int32), ("heads", C.c_int32), ("dim_head", C.c_int32),
+                ("dw_kernel", C.c_int32), ("ff_mult", C.c_int32), ("pe_attn_head", C.c_int32), ("rope_interleaved", C.c_int32),
+                ("hidden_out", C.c_int32), ("qk_norm", C.c_int32)]
+
+
 class qa_ssl_spec(C.Structure):
     _fields_ = [
         ("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8),
@@ -206,6 +212,21 @@ SYMBOLS = {
     "qa_lm_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "qa_sample_logits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                    C.c_uint64, C.c_void_p, C.c_void_p]),
+    "qa_cond_encoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_cond_encoder_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
+    "qa_cond_encoder_destroy": (None, [C.c_void_p]),
+    "qa_cond_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_conformer_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_cond_encoder_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
+    "qa_cond_encoder_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "qa_logmel_frames": (C.c_int64, [C.c_int64, C.c_int32]),
+    "qa_logmel": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                            C.c_void_p, C.c_void_p]),
+    "qa_lm_generate_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_generate_cond_sampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                              C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_score_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -83,7 +83,8 @@ static bool g_prof_on = false;   // conv_gemm launches
 static bool g_prof_hbm = false;  // byte-bound kernels (HbmKind): recorded as cfg = PROF_NCFG + kind
 static const char* const g_hbm_names[HK_NKINDS] = {"rownorm_kernel (RMSNorm / LayerNorm)", "dwconv_kernel (+ LayerNorm)", "gn_partial + gn_apply (GroupNorm)",
                                                    "rope_kernel", "istft_spec_kernel", "istft_ola_kernel", "stft_post_kernel", "rvq_lookup_kernel",
-                                                   "rvq_pick_kernel", "seanet_block_kernel<32> (fused conv0 + block)", "conv_in_kernel"};
+                                                   "rvq_pick_kernel", "seanet_block_kernel<32> (fused conv0 + block)", "conv_in_kernel",
+                                                   "glu_dwconv_bn_silu_kernel (GLU + depthwise + BatchNorm + SiLU)"};
 static std::vector<ProfRec> g_prof;
 static std::vector<hipEvent_t> g_pool;
 static hipEvent_t prof_event() {

@@ -48,13 +48,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // BIAS: WavLM's gated relative position bias (transformers WavLMAttention.forward): score(i, j) += gate[b, head, i] *
 // relbias[head][clamp(j - i, -R, R) + R]; the bucket function saturates below R, so the clamp is exact.
-template <int HD, bool BIAS>
+// KMASK: key-padding mask (Conformer condition encoder, conformer.py:165-174): kvalid [B, n_keys] bytes, 0 = the key is invisible to
+// every query of its batch item.  A tile's validity bytes travel with its K rows (register-staged, unconditional loads) and sit in
+// the four padding floats behind each K row in LDS, so the other instantiations keep their code and their LDS size.
+template <int HD, bool BIAS, bool KMASK = false>
 __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ q, long long ldq,
                                                         const float* __restrict__ k, const float* __restrict__ v,
                                                         long long ldkv, long long kv_bstride, float* __restrict__ out,
                                                         long long ldo, int n_q, int n_keys, float scale, int causal,
                                                         const float* __restrict__ gate, const float* __restrict__ relbias, int R,
-                                                        int context, int q_pos0, int ring_end, int dbg_arg) {
+                                                        int context, int q_pos0, int ring_end, int dbg_arg,
+                                                        const unsigned char* __restrict__ kvalid) {
 #if defined(QA_ATT_DBG) && QA_ATT_DBG == 0
     constexpr int dbg = 0;
     (void)dbg_arg;
@@ -136,7 +140,10 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     // quad into AGPRs for HD >= 96 (global_load; s_waitcnt vmcnt(0); v_accvgpr_write - eight serialized round trips per tile: 110 -> 177 us
     // per launch at HD = 128); ext_vector_type values stay in VGPRs and the loads stay in flight
     f32x4 kreg[NLD], vreg[NLD];
+    float mreg = 1.f;
+    const unsigned char* kvb = KMASK ? kvalid + (long long)b * n_keys : nullptr;
     auto fetch = [&](int kt) {
+        if (KMASK) mreg = kvb[min(kt * 32 + (tid & 31), n_keys - 1)] ? 1.f : 0.f;
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int i = tid + 256 * j;
@@ -163,6 +170,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
             *reinterpret_cast<f32x4*>(sK + row * LD + c4) = kreg[j];
             *reinterpret_cast<f32x4*>(sV + row * LD + c4) = vreg[j];
         }
+        if (KMASK && tid < 32) sK[tid * LD + HD] = mreg;
         __syncthreads();
         if (kt + 1 < n_tiles) fetch(kt + 1);
         if (dbg & 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -191,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
         // online softmax in base 2 (per lane = per query; the two halves of the wave hold interleaved key groups).  Masks are
         // evaluated only on tiles that can contain a hidden key for some query of this wave (wave-uniform test).
         const int q_first = q_blk0 + wave * 32, q_last = q_first + 31;
-        const bool need_mask = (dbg & 16) || ring || kt * 32 + 31 >= n_keys ||
+        const bool need_mask = KMASK || (dbg & 16) || ring || kt * 32 + 31 >= n_keys ||
                                (lin_causal && (kt * 32 + 31 > q_first + off || (context > 0 && kt * 32 < q_last + off - context + 1)));
         float tmax = -INFINITY;
         if (BIAS || need_mask) {
@@ -199,6 +207,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
                 bool ok = key < n_keys;
+                if (KMASK) ok = ok && sK[((r & 3) + 8 * (r >> 2) + 4 * hh) * LD + HD] != 0.f;
                 if (ring) {
                     const int delta = key - ring_idx;
                     const int pos = key >= ring_end ? -1 : (delta <= 0 ? ring_end + delta : ring_end + delta - n_keys);
@@ -278,22 +287,26 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
 int launch_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
                      long long ldo, int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale,
                      int causal, hipStream_t s, const float* gate, const float* relbias, int R, int context, int q_pos0,
-                     int ring_end) {
+                     int ring_end, const unsigned char* kvalid) {
     QA_REQUIRE(n_q > 0 && n_keys > 0 && (!causal || ring_end > 0 || n_keys >= n_q), "attention: n_q=%d n_keys=%d", n_q, n_keys);
     QA_REQUIRE(context >= 0 && (context == 0 || causal) && (ring_end <= 0 || (causal && context > 0 && !gate)),
                "attention: a context window needs causal=1; the ring mode needs causal=1 and context > 0");
     QA_REQUIRE((ldq % 4) == 0 && (ldkv % 4) == 0 && (ldo % 4) == 0, "attention: strides must be multiples of 4");
     QA_REQUIRE((gate == nullptr) == (relbias == nullptr) && (!gate || (R >= 0 && !causal && n_q == n_keys)),
                "attention: gate and relbias come together, for non-causal self-attention");
+    QA_REQUIRE(!kvalid || (!gate && !causal && n_q == n_keys), "attention: the key-padding mask is for non-causal self-attention without bias");
     dim3 grid((unsigned)ceil_div(n_q, 128), H, B);
     const int dbg = (int)knob(K_ATT_DEBUG);
 #define QA_ATT(HD)                                                                                                          \
-    if (gate)                                                                                                                \
+    if (kvalid)                                                                                                              \
+        hipLaunchKernelGGL((attention_kernel<HD, false, true>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q, \
+                           n_keys, scale, causal, nullptr, nullptr, 0, context, q_pos0, ring_end, dbg, kvalid);                 \
+    else if (gate)                                                                                                                \
         hipLaunchKernelGGL((attention_kernel<HD, true>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q, \
-                           n_keys, scale, causal, gate, relbias, R, context, q_pos0, ring_end, dbg);                             \
+                           n_keys, scale, causal, gate, relbias, R, context, q_pos0, ring_end, dbg, nullptr);                           \
     else                                                                                                                     \
         hipLaunchKernelGGL((attention_kernel<HD, false>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q, \
-                           n_keys, scale, causal, nullptr, nullptr, 0, context, q_pos0, ring_end, dbg)
+                           n_keys, scale, causal, nullptr, nullptr, 0, context, q_pos0, ring_end, dbg, nullptr)
     switch (hd) {
         case 32: QA_ATT(32); break;
         case 64: QA_ATT(64); break;

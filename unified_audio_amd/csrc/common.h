@@ -146,7 +146,7 @@ bool profile_enabled();
 // Byte-bound kernels (north_star: "rocprof HBM GB/s"): with qa_profile_begin_ex(2 | ...) their launches are bracketed by HIP events too,
 // each with its ALGORITHMIC bytes (every input and output element once), reduced per kind by qa_profile_end_hbm.
 enum HbmKind { HK_ROWNORM = 0, HK_DWCONV_LN, HK_GROUPNORM, HK_ROPE, HK_ISTFT_SPEC, HK_ISTFT_OLA, HK_STFT_POST, HK_RVQ_LOOKUP, HK_RVQ_PICK,
-               HK_SEANET_FRONT, HK_CONV_IN, HK_NKINDS };
+               HK_SEANET_FRONT, HK_CONV_IN, HK_GLU_DWCONV, HK_NKINDS };
 bool profile_hbm_enabled();
 struct HbmProf {  // scope guard around ONE launch (or the launches of one logical pass) on stream s
     hipStream_t s;

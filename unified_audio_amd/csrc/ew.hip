@@ -312,15 +312,15 @@ int launch_groupnorm(const float* x, const float* w, const float* bias, float* y
 // Rotate-half RoPE applied in place to the q and k parts of a fused [rows, 3*d] QKV buffer
 // (transformer.py:182-215: q*cos + rotate_half(q)*sin, positions 0..N-1, tables as RotaryEmbedding.forward).
 __global__ __launch_bounds__(256) void rope_kernel(float* __restrict__ qkv, const float* __restrict__ cs, int B, int N,
-                                                   int H, int hd, long long ld, int pos0, int interleaved) {
-    // one thread: one (row, head, pair i < hd/2) for q and for k
+                                                   int H, int hd, long long ld, int pos0, int interleaved, int Hr) {
+    // one thread: one (row, head < Hr, pair i < hd/2) for q and for k
     const int half = hd >> 1;
-    const long long total = (long long)B * N * H * half;
+    const long long total = (long long)B * N * Hr * half;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
     const int i = (int)(gid % half);
-    const int h = (int)((gid / half) % H);
-    const long long row = gid / ((long long)half * H);
+    const int h = (int)((gid / half) % Hr);
+    const long long row = gid / ((long long)half * Hr);
     const int t = (int)(row % N) + pos0;
     const float c = cs[((long long)t * half + i) * 2], s = cs[((long long)t * half + i) * 2 + 1];
     const int d = H * hd;
@@ -337,11 +337,12 @@ __global__ __launch_bounds__(256) void rope_kernel(float* __restrict__ qkv, cons
 }
 
 int launch_rope(float* qkv, const float* cos_sin, int B, int N, int H, int hd, long long ld, int pos0, hipStream_t s,
-                int interleaved) {
-    const long long total = (long long)B * N * H * (hd / 2);
-    HbmProf prof_(HK_ROPE, 16.0 * (double)B * N * H * hd, s);  // q and k parts: read + write
+                int interleaved, int rot_heads) {
+    const int Hr = rot_heads > 0 ? std::min(rot_heads, H) : H;
+    const long long total = (long long)B * N * Hr * (hd / 2);
+    HbmProf prof_(HK_ROPE, 16.0 * (double)B * N * Hr * hd, s);  // q and k parts: read + write
     hipLaunchKernelGGL(rope_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, qkv, cos_sin, B, N, H, hd, ld,
-                       pos0, interleaved);
+                       pos0, interleaved, Hr);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

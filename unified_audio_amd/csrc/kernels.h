@@ -24,8 +24,9 @@ int launch_dwconv(const float* x, const float* w_kc, const float* bias, const fl
 size_t groupnorm_scratch_bytes(int B, int T, int G);
 int launch_groupnorm(const float* x, const float* w, const float* bias, float* y, double* scratch, int B, int T, int C,
                      int G, float eps, int swish, hipStream_t s);
+// rot_heads > 0: only heads 0 .. rot_heads - 1 of q and k are rotated (Conformer `pe_attn_head`, conformer.py:157-160)
 int launch_rope(float* qkv, const float* cos_sin, int B, int N, int H, int hd, long long ld, int pos0, hipStream_t s,
-                int interleaved = 0);
+                int interleaved = 0, int rot_heads = 0);
 int launch_align(const float* sem, int B, int T, int D, float thr, int max_tokens, int* seg, int* start, int* len,
                  int* nseg, int* gmax, hipStream_t s);
 int launch_agg_build(const float* feats, const int* seg, const int* start, const int* len, const int* nseg, const float* qemb,
@@ -56,10 +57,11 @@ int launch_resample(const float* wav, const float* taps, float* out, int B, long
 //   causal = 1: key j visible to query i iff j <= i + (n_keys - n_q) (LM prefill / decode over a KV cache)
 //   gate [B, H, n_q] + relbias [H, 2R+1] (optional): score(i, j) += gate[b,h,i] * relbias[h][clamp(j - i, -R, R) + R]
 //   (WavLM gated relative position bias)
+//   kvalid [B, n_keys] bytes (optional, non-causal self-attention only): key j of item b is visible iff kvalid[b, j] != 0
 int launch_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
                      long long ldo, int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale,
                      int causal, hipStream_t s, const float* gate = nullptr, const float* relbias = nullptr, int R = 0,
-                     int context = 0, int q_pos0 = 0, int ring_end = 0);
+                     int context = 0, int q_pos0 = 0, int ring_end = 0, const unsigned char* kvalid = nullptr);
 // RingKVCache.complete() write (mimi/transformer.py:243-250): rows t = 0..T-1 of k / v (row stride ld, batch stride T * ld) go to
 // slot (pos0 + t) % cap of the caches [B, cap, d]
 int launch_ring_append(const float* k, const float* v, long long ld, float* kc, float* vc, int B, int T, int d, int cap, int pos0,

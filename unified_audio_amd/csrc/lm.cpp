@@ -24,7 +24,8 @@ int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_
 int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
                    hipStream_t s);
 int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
-                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s);
+                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s, int drop = 0);
+int launch_cond_prompt(float* x, const float* sos, const float* cond, int B, int T, int d, hipStream_t s);
 int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, const long long* tgt, float c, float sm, float* row_kl,
                        int* row_ok, hipStream_t s);
 int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
@@ -400,7 +401,7 @@ struct Chain {
 int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int Nm, int Ne, bool enroll) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads, B = ch.B;
-    const int64_t prow = (int64_t)B * L;
+    const int64_t prow = (int64_t)B * std::max(L, 1);  // L = 0: the empty prompt of CustomLlamaModel.generate(cond=None); a step still needs its row
     LMBuffers& b = ch.b;
     b.cap = cap;
     // the attention's key split, from the capacity alone (never from the batch or the step): att_split keys per split, more once
@@ -439,12 +440,16 @@ int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int 
 // (DESIGN.md section 11), so chains overlap nearly for free - tokens/s scales with the number of chains until the CUs fill.  Every
 // chain replays ONE captured step per token (hipGraph), round-robin over the chains, so the host issues two graph launches per
 // step instead of 124 kernel launches (eager launches go host-bound below ~3 us per kernel).  QA_LM_CHAINS forces a chain count.
+// cond_mode: CustomLlamaModel.generate (llm.py:291-374) - the prompt is [mix_sos, cond] (cond [B, Tc, d], already in the LM's width) or
+// empty (Tc = 0), and the global phase runs exactly G steps: its last token is returned but never fed (llm.py:318,345)
 int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, const float* mix, int Nm, int B, int G,
-                   int S, long long* gids, long long* sids, const SampleCfg& sc) {
+                   int S, long long* gids, long long* sids, const SampleCfg& sc, bool cond_mode = false, const float* cond = nullptr,
+                   int Tc = 0) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden;
-    const int L = 1 + (enroll ? 1 + Ne : 0) + 1 + Nm;
-    const int max_len = L + G + 1 + S;
+    const int L = cond_mode ? (Tc > 0 ? Tc + 1 : 0) : 1 + (enroll ? 1 + Ne : 0) + 1 + Nm;
+    const int Gs = cond_mode ? G : G + 1;  // steps of the global phase
+    const int max_len = L + Gs + S;
     QA_REQUIRE(max_len <= LM_MAX_POS, "generate: %d positions exceed max_position_embeddings %d", max_len, LM_MAX_POS);
     const int cap = (int)round_up(max_len, 64);  // cache row stride: shapes that round alike share their captured step graphs
     // A caller that is CAPTURING its stream into a hipGraph gets the plain single-chain launches on that stream only: no
@@ -494,6 +499,16 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     // ---- prompt (llm_sft.py:110-128) and prefill (llm_sft.py:130-135), chain by chain (these launches fill the device by themselves)
     for (Chain& ch : chains) {
         c.stream = ch.s;
+        if (cond_mode) {
+            int st = QA_OK;
+            if (L > 0) {
+                st = launch_cond_prompt(ch.b.x, lm->mix_sos, cond + (size_t)ch.b0 * Tc * d, ch.B, Tc, d, ch.s);
+                if (st == QA_OK) st = lm_body(lm, c, ch.b, ch.B, L, 0, cap, true);
+            }
+            c.stream = caller;
+            QA_TRY(st);
+            continue;
+        }
         const float* mix_c = mix + (size_t)ch.b0 * Nm * sp.feats_dim;
         const float* enr_c = enroll ? enroll + (size_t)ch.b0 * Ne * sp.feats_dim : nullptr;
         int st = linear_op(c, mix_c, (int64_t)ch.B * Nm, lm->adapter, ch.emix);
@@ -513,7 +528,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     float* const tap_base = lm->taps && !c.dry ? reinterpret_cast<float*>(lm->tap_buf.ptr) : nullptr;
     auto phase = [&](int which, long long first_id, int steps, int lo, int width, int keep) -> int {
         const int ids_ld = keep;
-        float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * (G + 1) * sp.global_size) : nullptr;
+        float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * Gs * sp.global_size) : nullptr;
         auto chain_tap = [&](const Chain& ch) { return tap ? tap + (size_t)ch.b0 * steps * width : nullptr; };
         for (Chain& ch : chains)
             QA_TRY(launch_lm_phase_init(ch.b.tok, first_id, ch.B, ch.b.state, pos, which == 0, sc.seed, ch.b0, ch.s));
@@ -527,7 +542,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
                 for (uint64_t v : {(uint64_t)(uintptr_t)lm->ws.ptr, (uint64_t)B, (uint64_t)nc, (uint64_t)ch.b0, (uint64_t)ch.B, (uint64_t)cap, (uint64_t)L,
                                    (uint64_t)G, (uint64_t)S, (uint64_t)Ne, (uint64_t)Nm, (uint64_t)(enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
                                    (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF),
-                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch)})
+                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch), (uint64_t)cond_mode})
                     key = mix_key(key, v);
                 if (!g.exec || g.key != key) {
                     g.reset();
@@ -558,7 +573,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
         pos += steps;
         return QA_OK;
     };
-    QA_TRY(phase(0, 0, G + 1, 3, sp.global_size, G));                            // llm_sft.py:137-164
+    QA_TRY(phase(0, 0, Gs, 3, sp.global_size, G));                               // llm_sft.py:137-164 / llm.py:316-343
     QA_TRY(phase(1, 1, S, 3 + sp.global_size, sp.semantic_size, S));            // llm_sft.py:166-193
     for (int i = 0; i < nc; ++i) {
         Chain& ch = chains[i];
@@ -579,6 +594,9 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
 // rows of input_ids behind it, the body over all Lp + Lt positions from position 0 with every layer, the final RMSNorm on the Lt target
 // rows, then output_head over the full vocabulary in chunks of QA_LM_SCORE_ROWS rows, each reduced by the row-loss kernel right behind it.
 struct ScoreArgs {
+    bool cond_mode;  // CustomLlamaModel.forward (llm.py:107-147): prompt [mix_sos, cond] or none, the last position dropped
+    const float* cond;
+    int Tc;
     int task, Ne, Nm, B, G, T;
     const float *enroll, *mix;
     const long long *gids, *sids;
@@ -591,7 +609,8 @@ struct ScoreArgs {
 int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, I = sp.intermediate, V = vocab_of(sp);
-    const int Lp = 1 + (a.enroll ? 1 + a.Ne : 0) + 1 + a.Nm, Lt = a.G + a.T + 2, n = Lp + Lt;
+    const int Lp = a.cond_mode ? (a.Tc > 0 ? a.Tc + 1 : 0) : 1 + (a.enroll ? 1 + a.Ne : 0) + 1 + a.Nm;
+    const int Lt = a.G + a.T + 2 - (a.cond_mode ? 1 : 0), n = Lp + Lt;
     QA_REQUIRE(n <= LM_MAX_POS, "qa_lm_score: %d positions (prompt %d + targets %d) exceed max_position_embeddings %d", n, Lp, Lt, LM_MAX_POS);
     const int GB = std::min(a.B, LM_MAX_ROWS);
     const int64_t prow = (int64_t)GB * n, trow = (int64_t)GB * Lt;
@@ -617,14 +636,19 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const float conf = (float)(1.0 - a.eps), smooth = (float)(a.eps / (V - 1));
     for (int b0 = 0; b0 < a.B; b0 += GB) {
         const int gb = std::min(GB, a.B - b0);
-        QA_TRY(linear_op(c, a.mix + (size_t)b0 * a.Nm * sp.feats_dim, (int64_t)gb * a.Nm, lm->adapter, emix));
-        if (a.enroll) QA_TRY(linear_op(c, a.enroll + (size_t)b0 * a.Ne * sp.feats_dim, (int64_t)gb * a.Ne, lm->adapter, eenr));
-        QA_TRY(launch_assemble_prompt(b.hn, lm->task_emb + (size_t)a.task * d, a.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
-                                      a.Ne, a.Nm, d, c.stream));
-        QA_HIP(hipMemcpy2DAsync(b.x, sizeof(float) * n * d, b.hn, sizeof(float) * Lp * d, sizeof(float) * Lp * d, gb, hipMemcpyDeviceToDevice,
-                                c.stream));
+        if (a.cond_mode) {
+            if (Lp > 0) QA_TRY(launch_cond_prompt(b.hn, lm->mix_sos, a.cond + (size_t)b0 * a.Tc * d, gb, a.Tc, d, c.stream));
+        } else {
+            QA_TRY(linear_op(c, a.mix + (size_t)b0 * a.Nm * sp.feats_dim, (int64_t)gb * a.Nm, lm->adapter, emix));
+            if (a.enroll) QA_TRY(linear_op(c, a.enroll + (size_t)b0 * a.Ne * sp.feats_dim, (int64_t)gb * a.Ne, lm->adapter, eenr));
+            QA_TRY(launch_assemble_prompt(b.hn, lm->task_emb + (size_t)a.task * d, a.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
+                                          a.Ne, a.Nm, d, c.stream));
+        }
+        if (Lp > 0)
+            QA_HIP(hipMemcpy2DAsync(b.x, sizeof(float) * n * d, b.hn, sizeof(float) * Lp * d, sizeof(float) * Lp * d, gb, hipMemcpyDeviceToDevice,
+                                    c.stream));
         QA_TRY(launch_lm_targets(b.x + (size_t)Lp * d, (long long)n * d, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T,
-                                 a.T, V, 3, 3 + sp.global_size, tgt, gb, d, c.stream));
+                                 a.T, V, 3, 3 + sp.global_size, tgt, gb, d, c.stream, a.cond_mode ? 1 : 0));
         QA_TRY(lm_body(lm, c, b, gb, n, 0, n, false, true));
         // final RMSNorm (its weight is folded into output_head) on the last Lt rows of every sequence (llm_sft.py:82)
         QA_HIP(hipMemcpy2DAsync(b.att, sizeof(float) * Lt * d, b.x + (size_t)Lp * d, sizeof(float) * n * d, sizeof(float) * Lt * d, gb,
@@ -685,16 +709,20 @@ void qa_lm_destroy(qa_lm* lm) { destroy_handle(lm); }
 
 static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                             int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc,
-                            int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    if (!lm || !mix_feats || !global_ids || !semantic_ids) {
-        set_error("qa_lm_generate: null argument");
+                            int64_t* global_ids, int64_t* semantic_ids, void* stream, bool cond_mode = false, const float* cond = nullptr,
+                            int64_t Tc = 0) {
+    const char* fn = cond_mode ? "qa_lm_generate_cond" : "qa_lm_generate";
+    if (!lm || (!cond_mode && !mix_feats) || !global_ids || !semantic_ids) {
+        set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_generate: task %d out of range (KeyError in the reference)", task);
-    QA_REQUIRE(B > 0 && n_mix > 0 && global_length >= 0 && semantic_length >= 0, "qa_lm_generate: bad shape");
-    QA_REQUIRE(!enroll_feats || n_enroll > 0, "qa_lm_generate: enrollment given with no frames");
-    QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "qa_lm_generate: temperature must be in (0, 1] (llm.py:278)");
-    QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "qa_lm_generate: bad top_k / top_p");
+    QA_REQUIRE(cond_mode || (task >= 0 && task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, task);
+    QA_REQUIRE(B > 0 && (cond_mode || n_mix > 0) && global_length >= 0 && semantic_length >= 0, "%s: bad shape", fn);
+    QA_REQUIRE(!cond_mode || (Tc >= 0 && Tc < LM_MAX_POS && (cond != nullptr) == (Tc > 0) && global_length + semantic_length > 0),
+               "qa_lm_generate_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %lld); at least one step", (long long)Tc);
+    QA_REQUIRE(!enroll_feats || n_enroll > 0, "%s: enrollment given with no frames", fn);
+    QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "%s: temperature must be in (0, 1] (llm.py:278)", fn);
+    QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "%s: bad top_k / top_p", fn);
     QA_HIP(hipSetDevice(lm->device));
     if (sc.do_sample) QA_TRY(lm_sample_prepare());
     lm->tap_n[0] = lm->tap_n[1] = -1;
@@ -703,7 +731,7 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     c.gemm_fp32 = true;  // ConvParams::math_fp32
     auto graph = [&] {
         return generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
-                              (long long*)global_ids, (long long*)semantic_ids, sc);
+                              (long long*)global_ids, (long long*)semantic_ids, sc, cond_mode, cond, (int)Tc);
     };
     QA_TRY(plan(lm->device, static_cast<hipStream_t>(stream), c, lm->ws, graph, [&](size_t bytes) -> int {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -720,7 +748,7 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
         c.stream = static_cast<hipStream_t>(stream);  // workspace the next call re-uses - quiesce them (error path only)
         for (hipStream_t cs : lm->chain_streams) (void)hipStreamSynchronize(cs);
     } else if (lm->taps) {
-        lm->tap_n[0] = B * (int64_t)(global_length + 1) * lm->spec.global_size;
+        lm->tap_n[0] = B * (int64_t)(global_length + (cond_mode ? 0 : 1)) * lm->spec.global_size;
         lm->tap_n[1] = B * (int64_t)semantic_length * lm->spec.semantic_size;
     }
     return st;
@@ -742,28 +770,32 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
                             semantic_ids, stream);
 }
 
-int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
-                const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
-                float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
-    if (!lm || !mix_feats || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
+static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                         const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length,
+                         double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream,
+                         bool cond_mode, const float* cond, int64_t Tc) {
+    const char* fn = cond_mode ? "qa_lm_score_cond" : "qa_lm_score";
+    if (!lm || (!cond_mode && !mix_feats) || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
         (semantic_length > 0 && !semantic_ids)) {
-        set_error("qa_lm_score: null argument");
+        set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_score: task %d out of range (KeyError in the reference)", task);
-    QA_REQUIRE(B > 0 && n_mix > 0 && global_length >= 0 && semantic_length >= 0, "qa_lm_score: bad shape");
-    QA_REQUIRE(!enroll_feats || n_enroll > 0, "qa_lm_score: enrollment given with no frames");
-    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "qa_lm_score: label_smoothing %g outside [0, 1]", label_smoothing);
-    QA_REQUIRE(n_mix <= LM_MAX_POS && n_enroll <= LM_MAX_POS && B <= (1 << 24), "qa_lm_score: bad shape");
+    QA_REQUIRE(cond_mode || (task >= 0 && task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, task);
+    QA_REQUIRE(B > 0 && (cond_mode || n_mix > 0) && global_length >= 0 && semantic_length >= 0, "%s: bad shape", fn);
+    QA_REQUIRE(!cond_mode || (Tc >= 0 && Tc < LM_MAX_POS && (cond != nullptr) == (Tc > 0)),
+               "qa_lm_score_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %lld)", (long long)Tc);
+    QA_REQUIRE(!enroll_feats || n_enroll > 0, "%s: enrollment given with no frames", fn);
+    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, label_smoothing);
+    QA_REQUIRE(n_mix <= LM_MAX_POS && n_enroll <= LM_MAX_POS && B <= (1 << 24), "%s: bad shape", fn);
     QA_HIP(hipSetDevice(lm->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
     const bool capturing = cs == hipStreamCaptureStatusActive;
-    ScoreArgs a{task, enroll_feats ? (int)n_enroll : 0, (int)n_mix, (int)B, global_length, semantic_length, enroll_feats, mix_feats,
+    ScoreArgs a{cond_mode, cond, (int)Tc, task, enroll_feats ? (int)n_enroll : 0, (int)n_mix, (int)B, global_length, semantic_length, enroll_feats, mix_feats,
                 reinterpret_cast<const long long*>(global_ids), reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq,
                 reinterpret_cast<long long*>(correct_per_seq), loss, acc};
-    const int Lt = global_length + semantic_length + 2;
+    const int Lt = global_length + semantic_length + 2 - (cond_mode ? 1 : 0);
     lm->score_tap_n = -1;
     float* tap = nullptr;
     if (lm->taps) {
@@ -785,6 +817,35 @@ int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_en
     QA_TRY(graph());
     if (tap) lm->score_tap_n = (int64_t)B * Lt * vocab_of(lm->spec);
     return QA_OK;
+}
+
+int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
+                float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
+    return lm_score_impl(lm, task, enroll_feats, n_enroll, mix_feats, n_mix, B, global_ids, global_length, semantic_ids, semantic_length,
+                         label_smoothing, loss_per_seq, correct_per_seq, loss, acc, stream, false, nullptr, 0);
+}
+
+int qa_lm_score_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, const int64_t* global_ids, int32_t global_length,
+                     const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing, float* loss_per_seq,
+                     int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
+    return lm_score_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_ids, global_length, semantic_ids, semantic_length, label_smoothing,
+                         loss_per_seq, correct_per_seq, loss, acc, stream, true, cond_embeds, T);
+}
+
+int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
+                        float temperature, int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    const SampleCfg sc{0, top_k, top_p, temperature, 0ull};
+    return lm_generate_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_length, semantic_length, sc, global_ids, semantic_ids, stream, true,
+                            cond_embeds, T);
+}
+
+int qa_lm_generate_cond_sampled(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
+                                float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
+                                void* stream) {
+    const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
+    return lm_generate_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_length, semantic_length, sc, global_ids, semantic_ids, stream, true,
+                            cond_embeds, T);
 }
 
 int qa_lm_enable_taps(qa_lm* lm, int on) {

@@ -224,8 +224,8 @@ __device__ __forceinline__ long long clamp_id(long long v, int V) { return v < 0
 
 __global__ __launch_bounds__(256) void lm_targets_kernel(float* __restrict__ x, long long ldx_seq, const float* __restrict__ table,
                                                          const long long* __restrict__ gids, int G, const long long* __restrict__ sids,
-                                                         int T, int V, int goff, int soff, long long* __restrict__ tgt, int B, int d) {
-    const int Lt = G + T + 2, d4 = d >> 2;
+                                                         int T, int V, int goff, int soff, long long* __restrict__ tgt, int B, int d, int drop) {
+    const int Lt = G + T + 2 - drop, d4 = d >> 2;  // drop = 1: CustomLlamaModel.forward leaves the last position out (llm.py:126-127)
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * Lt * d4) return;
     const int c = (int)(gid % d4) * 4;
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void lm_targets_kernel(float* __restrict__ x, 
     else in_id = sids[(long long)b * T + t - G - 2] + soff;
     if (t < G) tg = gids[(long long)b * G + t] + goff;
     else if (t == G) tg = 1;
-    else if (t < Lt - 1) tg = sids[(long long)b * T + t - G - 1] + soff;
+    else if (t < G + T + 1) tg = sids[(long long)b * T + t - G - 1] + soff;
     else tg = 2;
     in_id = clamp_id(in_id, V);
     *reinterpret_cast<float4*>(x + b * ldx_seq + (long long)t * d + c) = *reinterpret_cast<const float4*>(table + in_id * d + c);
@@ -246,11 +246,11 @@ __global__ __launch_bounds__(256) void lm_targets_kernel(float* __restrict__ x, 
 }
 
 int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
-                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s) {
-    QA_REQUIRE(d % 4 == 0 && ldx_seq % 4 == 0, "lm_targets: d %d / row stride must be multiples of 4", d);
-    const long long total = (long long)B * (G + T + 2) * (d / 4);
+                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s, int drop) {
+    QA_REQUIRE(d % 4 == 0 && ldx_seq % 4 == 0 && (drop == 0 || drop == 1), "lm_targets: d %d / row stride must be multiples of 4", d);
+    const long long total = (long long)B * (G + T + 2 - drop) * (d / 4);
     hipLaunchKernelGGL(lm_targets_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, ldx_seq, table, gids, G, sids, T, V,
-                       goff, soff, tgt, B, d);
+                       goff, soff, tgt, B, d, drop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

@@ -2,6 +2,7 @@
 
     LLM_SFT.generate  <->  QuarkAudio-UniSE/model/llm/llm_sft.py:93-195   (greedy path: model/model.py:173)
     LLM_SFT.forward   <->  QuarkAudio-UniSE/model/llm/llm_sft.py:37-90    (teacher-forced loss / accuracy: Model.validation_step)
+    CustomLlamaModel  <->  QuarkAudio-UniSE/model/llm/llm.py:13-374       (the pre-training-stage model: condition encoder prompt or none)
 
 Weights come in the reference's key layout (the Lightning checkpoint's `dnn.*` entries, prefix optional).
 """
@@ -166,6 +167,148 @@ class LLM_SFT:
         if n2 < 0:
             _lib.check(int(n2))
         return out
+
+
+DEFAULT_CONFORMER_PARAMS = dict(num_layers=2, dim=256, heads=8, dim_head=32, depthwise_conv_kernel_size=31, ff_mult=4, dropout=0.1,
+                                qk_norm=None, pe_attn_head=None)  # llm.py:25-35
+
+
+class CustomLlamaModel:
+    """llm.py:13-374: the Llama body with the Conformer condition encoder in front.  `forward` and `generate` take the log-mel
+    condition `cond` [B, T, cond_dim] (prompt [mix_sos, cond_output_layer(cond_encoder(cond_input_layer(cond)))]) or None (no prompt).
+    The reference's generate is written for one sequence (llm.py:316); here B = cond.size(0), or `batch_size` without a condition, and
+    every row equals its one-sequence result under greedy decoding.  `rope_interleaved`: see unified_audio_amd.conformer."""
+
+    def __init__(self, cond_dim: int = 80, global_size: int = 4096, semantic_size: int = 8192, hidden_size: int = 256, num_layers: int = 2,
+                 num_attention_heads: int = 8, dropout_p: float = 0.1, max_position_embeddings: int = 4096, label_smoothing: float = 0.1,
+                 conformer_params: Optional[dict] = None, *, rope_interleaved: bool = True, device: str | torch.device = "cuda:0"):
+        from .conformer import ConditionEncoder
+
+        if max_position_embeddings != 4096:
+            raise ValueError("max_position_embeddings is 4096 in this library (conf/config.yaml:146)")
+        self.device = torch.device(device)
+        self.cond_dim, self.hidden_size = int(cond_dim), int(hidden_size)
+        # the LM handle is LLM_SFT's: its task / enrollment / adapter tensors do not exist in this model and are filled with zeros
+        self._lm = LLM_SFT(num_tasks=1, feats_dim=32, device=device,
+                           llm_base_config=dict(global_size=global_size, semantic_size=semantic_size, hidden_size=hidden_size,
+                                                num_layers=num_layers, num_attention_heads=num_attention_heads,
+                                                label_smoothing=label_smoothing))
+        self._cond = ConditionEncoder(cond_dim, hidden_size, dict(conformer_params or DEFAULT_CONFORMER_PARAMS),
+                                      rope_interleaved=rope_interleaved, device=device)
+        self._has_cond = False
+        self.label_smoothing = float(label_smoothing)
+        self.vocab_size, self.global_offset, self.semantic_offset = self._lm.vocab_size, self._lm.global_offset, self._lm.semantic_offset
+
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
+        """The reference's keys (`dnn.` prefix optional).  Without `cond_*` keys the body still loads (strict=False) and the condition
+        path raises when called."""
+        sd = {(k[4:] if k.startswith("dnn.") else k): v for k, v in state_dict.items()}
+        d = self.hidden_size
+        body = {k: v for k, v in sd.items() if not k.startswith("cond_")}
+        body.setdefault("task_embedding.weight", torch.zeros(1, d))
+        body.setdefault("enroll_sos_embedding.weight", torch.zeros(1, d))
+        body.setdefault("adapter.weight", torch.zeros(d, 32))
+        body.setdefault("adapter.bias", torch.zeros(d))
+        self._lm.load_state_dict(body)
+        self._has_cond = any(k.startswith("cond_") for k in sd)
+        if self._has_cond:
+            self._cond.load_state_dict(sd)
+        elif strict:
+            raise _lib.QuarkAudioError(-3, "CustomLlamaModel.load_state_dict: no cond_input_layer / cond_encoder / cond_output_layer keys "
+                                           "(strict=False loads the body alone)")
+        return self
+
+    def eval(self):
+        return self
+
+    @property
+    def lm(self) -> "LLM_SFT":
+        """The LLM_SFT facade of the SAME qa_lm handle (num_tasks = 1, feats_dim = 32 unless the checkpoint carried LLM_SFT's task /
+        enrollment / adapter tensors in those shapes): its generate / forward share weights, workspace and captured steps with this model."""
+        return self._lm
+
+    def encode_condition(self, cond: torch.Tensor) -> torch.Tensor:
+        """cond [B, T, cond_dim] -> the prompt embeddings [B, T, hidden_size] (llm.py:130-132)"""
+        if not self._has_cond:
+            raise _lib.QuarkAudioError(-3, "CustomLlamaModel: the checkpoint had no cond_* weights, the condition path cannot run")
+        return self._cond(cond)
+
+    @torch.no_grad()
+    def generate(self, cond: Optional[torch.Tensor] = None, global_length: int = 32, semantic_length: int = 150, temperature: float = 0.8,
+                 top_k: int = 50, top_p: float = 0.95, do_sample: bool = True, *, batch_size: int = 1):
+        """llm.py:291-374 -> (global_ids [B, global_length], semantic_ids [B, semantic_length]) int64, offsets subtracted.  Sampling as
+        LLM_SFT.generate: Philox draws seeded from torch's global generator."""
+        lm = self._lm
+        if not lm._handle.value:
+            raise _lib.QuarkAudioError(-3, "CustomLlamaModel has no weights: call load_state_dict first")
+        emb, T, B = None, 0, int(batch_size)
+        if cond is not None:
+            emb = self.encode_condition(cond)
+            B, T = emb.shape[0], emb.shape[1]
+        gids = torch.empty((B, global_length), dtype=torch.int64, device=self.device)
+        sids = torch.empty((B, semantic_length), dtype=torch.int64, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        ptr = emb.data_ptr() if emb is not None else None
+        if do_sample:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+            _lib.check(lm._lib.qa_lm_generate_cond_sampled(lm._handle, ptr, T, B, global_length, semantic_length, temperature, top_k, top_p,
+                                                           seed, gids.data_ptr(), sids.data_ptr(), stream))
+        else:
+            _lib.check(lm._lib.qa_lm_generate_cond(lm._handle, ptr, T, B, global_length, semantic_length, temperature, top_k, top_p,
+                                                   gids.data_ptr(), sids.data_ptr(), stream))
+        return gids, sids
+
+    def _score(self, global_ids, semantic_ids, cond):
+        lm = self._lm
+        if not lm._handle.value:
+            raise _lib.QuarkAudioError(-3, "CustomLlamaModel has no weights: call load_state_dict first")
+        B = int(global_ids.shape[0])
+        g = global_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()
+        sids = semantic_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()
+        G, T = g.shape[1], sids.shape[1]
+        emb, Tc = None, 0
+        if cond is not None:
+            emb = self.encode_condition(cond)
+            if emb.shape[0] != B:
+                raise _lib.QuarkAudioError(-1, f"cond must be [B={B}, T, {self.cond_dim}], got {tuple(cond.shape)}")
+            Tc = emb.shape[1]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        shifted = torch.cat([g.reshape(-1) + self.global_offset, sids.reshape(-1) + self.semantic_offset])
+        if shifted.numel():
+            bad = C.c_int64(0)
+            _lib.check(lm._lib.qa_codes_check(shifted.data_ptr(), shifted.numel(), self.vocab_size, C.byref(bad), stream))
+            if bad.value:
+                raise IndexError(f"{bad.value} input ids out of range [0, {self.vocab_size}) after the offsets")
+        loss_seq = torch.empty(B, dtype=torch.float32, device=self.device)
+        correct = torch.empty(B, dtype=torch.int64, device=self.device)
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        _lib.check(lm._lib.qa_lm_score_cond(lm._handle, emb.data_ptr() if emb is not None else None, Tc, B, g.data_ptr(), G, sids.data_ptr(), T,
+                                            self.label_smoothing, loss_seq.data_ptr(), correct.data_ptr(), out.data_ptr(),
+                                            out[1:].data_ptr(), stream))
+        return loss_seq, correct, out[0], out[1], G + T + 1
+
+    @torch.no_grad()
+    def forward(self, global_ids, semantic_ids, cond: Optional[torch.Tensor] = None):
+        """llm.py:107-147 -> (loss, acc), 0-dim float32 device tensors over the B * (G + T + 1) target rows (no semantic_eos target)."""
+        _, _, loss, acc, _ = self._score(global_ids, semantic_ids, cond)
+        return loss, acc
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    @torch.no_grad()
+    def score(self, global_ids, semantic_ids, cond: Optional[torch.Tensor] = None):
+        """forward per sequence: (loss [B], acc [B])"""
+        loss_seq, correct, _, _, Lt = self._score(global_ids, semantic_ids, cond)
+        return loss_seq, correct.to(torch.float32) / Lt
+
+    def enable_taps(self, on: bool = True):
+        self._lm.enable_taps(on)
+        return self
+
+    def tap(self, name: str) -> torch.Tensor:
+        """"logits.global" [B, global_length, global_size], "logits.semantic", "logits.forced" [B, G + T + 1, vocab]"""
+        return self._lm.tap(name)
 
 
 def sample_logits(logits: torch.Tensor, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,

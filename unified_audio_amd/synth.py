@@ -664,3 +664,57 @@ def ssl_state_dict(spec, seed: int = 21) -> Dict[str, torch.Tensor]:
             if i == 0:
                 sd[pre + "attention.rel_attn_embed.weight"] = rn(spec.num_buckets, spec.num_attention_heads, scale=0.5)
     return sd
+
+
+# ---- UniSE condition encoder (QuarkAudio-UniSE/model/llm/llm.py:52-54, model/llm/conformer.py) ----
+
+CONFORMER_PARAMS_UNISE = dict(num_layers=6, dim=512, heads=8, dim_head=64, depthwise_conv_kernel_size=31, ff_mult=4, dropout=0.1,
+                              qk_norm=None, pe_attn_head=1)  # conf/config.yaml:148-157
+
+
+def conformer_state_dict(seed: int, conformer_params: dict, prefix: str = "", gain: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Seeded weights of one ConformerEncoder in the reference's key layout (`<prefix>layers.N.*`).  The BatchNorm running statistics
+    are non-trivial (mean != 0, var != 1) so that folding them is really exercised; `gain` scales the projections."""
+    p = conformer_params
+    d, inner, k, ffd = p["dim"], p["heads"] * p["dim_head"], p.get("depthwise_conv_kernel_size", 31), p["dim"] * p.get("ff_mult", 4)
+    g = _Gen(seed)
+    for i in range(p["num_layers"]):
+        lp = f"{prefix}layers.{i}"
+        for ff in ("ff1", "ff2"):
+            g.norm(f"{lp}.{ff}.sequential.0", d)
+            g.linear(f"{lp}.{ff}.sequential.1", ffd, d, gain=gain)
+            g.linear(f"{lp}.{ff}.sequential.4", d, ffd, gain=gain)
+        g.norm(f"{lp}.attn_norm", d)
+        for nm in ("to_q", "to_k", "to_v"):
+            g.linear(f"{lp}.attn.{nm}", inner, d, gain=2.0 * gain)
+        g.linear(f"{lp}.attn.to_out.0", d, inner, gain=gain)
+        cp = f"{lp}.conv_module"
+        g.norm(f"{cp}.layer_norm", d)
+        g.conv(f"{cp}.sequential.0", 2 * d, d, 1, gain=gain)
+        g.conv(f"{cp}.sequential.2", d, 1, k, gain=gain)
+        g.norm(f"{cp}.sequential.3", d)
+        g.sd[f"{cp}.sequential.3.running_mean"] = _t(0.2 * g.rng.standard_normal(d))
+        g.sd[f"{cp}.sequential.3.running_var"] = _t(g.rng.uniform(0.3, 1.8, size=d))
+        g.sd[f"{cp}.sequential.3.num_batches_tracked"] = torch.tensor(100, dtype=torch.int64)
+        g.conv(f"{cp}.sequential.5", d, d, 1, gain=gain)
+        g.norm(f"{lp}.final_norm", d)
+    return g.sd
+
+
+def cond_encoder_state_dict(seed: int, cond_dim: int, hidden_size: int, conformer_params: dict, gain: float = 1.0) -> Dict[str, torch.Tensor]:
+    """`cond_input_layer.*`, `cond_encoder.*`, `cond_output_layer.*` of CustomLlamaModel.  `gain` > 1 makes the prompt move the LM's
+    logits visibly (with default-initialised weights conditional and unconditional greedy streams coincide)."""
+    sd = conformer_state_dict(seed, conformer_params, "cond_encoder.", gain)
+    g = _Gen(seed + 1)
+    g.linear("cond_input_layer", conformer_params["dim"], cond_dim)
+    g.linear("cond_output_layer", hidden_size, conformer_params["dim"], gain=4.0 * gain)
+    sd.update(g.sd)
+    return sd
+
+
+def synth_logmel(seed: int, batch: int, frames: int, n_mels: int = 80) -> torch.Tensor:
+    """Log-mel-like condition [B, frames, n_mels]: smoothed noise around -4 with a few units of spread."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((batch, frames + 2, n_mels))
+    x = (x[:, :-2] + x[:, 1:-1] + x[:, 2:]) / math.sqrt(3.0)
+    return torch.from_numpy((2.5 * x - 4.0).astype(np.float32))

@@ -51,6 +51,12 @@ def mel_frames(n_samples: int) -> int:
     return (padded - WIN_LENGTH) // HOP_LENGTH + 1
 
 
+def mel_frames_for(n_samples: int, hop_length: int, win_length: int) -> int:
+    """`mel_frames` for any hop / window"""
+    padded = math.ceil(n_samples / hop_length) * hop_length + (win_length - hop_length)
+    return (padded - win_length) // hop_length + 1
+
+
 class _Frames:
     """Stand-in for a mel tensor: LLM_SFT.generate only calls `.size(1)` on it, LLM_SFT.forward only `.size(0)`."""
 
@@ -63,9 +69,23 @@ class _Frames:
 
 def stft_logmel(x: torch.Tensor, hop_length: int = HOP_LENGTH, win_length: int = WIN_LENGTH, n_fft: int = 640, n_mels: int = 80) -> torch.Tensor:
     """Model.stft_logmel (model.py:53-79), restated with the filter bank of torchaudio.functional.melscale_fbanks (HTK scale, no
-    normalisation, 0-8000 Hz).  NOT on the hot path: LLM_SFT.generate consumes only `mel.size(1)` (llm_sft.py:108), which
-    `mel_frames()` gives without computing anything; this function exists for callers that want the reference's tensor."""
+    normalisation, 0-8000 Hz).  LLM_SFT.generate consumes only `mel.size(1)` (llm_sft.py:108), which `mel_frames()` gives without
+    computing anything; CustomLlamaModel's condition encoder consumes the values.  A CUDA input runs on the device (qa_logmel: the
+    framed-signal DFT GEMM); a CPU input keeps this torch restatement."""
     assert x.ndim == 2
+    # the condition encoder's input (CustomLlamaModel): computed on the device by qa_logmel where its framed-signal DFT serves the
+    # configuration (win = 2 hop, hop a multiple of 16, n_mels a multiple of 4); any other configuration keeps the torch path below
+    if x.is_cuda and win_length == 2 * hop_length and hop_length % 16 == 0 and n_fft >= win_length and (n_fft - win_length) % 2 == 0 \
+            and n_mels % 4 == 0:
+        from . import _lib
+
+        lib = _lib.load_library()
+        xc = x.to(torch.float32).contiguous()
+        out = torch.empty((xc.shape[0], mel_frames_for(xc.shape[1], hop_length, win_length), n_mels), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.qa_logmel(xc.data_ptr(), xc.shape[0], xc.shape[1], n_fft, win_length, hop_length, n_mels, 16000, 0.0, 8000.0,
+                                     out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+        return out
     pad_length = math.ceil(x.size(-1) / hop_length) * hop_length - x.size(-1)
     x = torch.nn.functional.pad(x, ((win_length - hop_length) // 2, pad_length + (win_length - hop_length) // 2))
     spec = torch.stft(x, n_fft, hop_length, win_length=win_length, window=torch.hann_window(win_length, device=x.device), onesided=True,
