@@ -19,34 +19,6 @@
 
 #include "host_util.h"
 
-namespace qa {
-int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s);
-int launch_gather_global(const long long* tok, const float* table, float* out, int B, int N, int V, int L, hipStream_t s);
-int launch_adaln(const float* x, const float* scale, const float* shift, long long ld_cond, float* y, int B, int T, int C, float eps,
-                 hipStream_t s);
-int launch_add_rowvec(float* x, const float* v, int B, int T, int C, hipStream_t s);
-int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s);
-int launch_l2norm_rows(const float* x, float* y, long long rows, int D, hipStream_t s);
-int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s);
-int launch_spec_mag(const float* ri, int nbp, int nb, float* mag, int ldm, long long rows, hipStream_t s);
-int launch_res2_chain(const float* x, float* y, const float* wt, const float* bst, int B, int T, int C, int d, hipStream_t s);
-int launch_se_residual(const float* x, long long ldx, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
-                       float* gate, float* out, long long ldo, int B, int T, int C, int Hd, hipStream_t s);
-int launch_perceiver_ctx(const float* lat, long long lat_b, const float* x, float* ctx, int B, int n_lat, int T, int D, hipStream_t s);
-int launch_geglu(const float* h, int F, float* out, int ldo, long long rows, hipStream_t s);
-int launch_l2norm_scale(const float* x, const float* gamma, float* y, long long rows, int D, float scale, hipStream_t s);
-int launch_fsq(const float* x, const float* w, const float* bias, const int* levels, int nl, int D, long long rows, int* tokens,
-               float* bounded, hipStream_t s);
-int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate, long long ldg,
-                       const float* res, long long ldr, float* y, long long ldy, int M, int N, int K, int act, hipStream_t s,
-                       float rms_eps, int dual);
-int launch_astp_pool(const float* logit, const float* x, int B, int T, int C, const float* bn_s, const float* bn_t, float* pool, float* bn,
-                     hipStream_t s);
-int launch_frame_stats(const float* x, int B, int T, int C, float* ctx, hipStream_t s);
-int launch_code_usage(const long long* idx, long long n, int K, float* perplexity, float* active, hipStream_t s);
-int launch_widen_i32(const int* src, long long* dst, long long n, hipStream_t s);
-}  // namespace qa
-
 using namespace qa;
 
 namespace {
@@ -290,7 +262,7 @@ int build(qa_bicodec* h, const HostTable& tab) {
 // item's arithmetic does not depend on how many items share the call (a row-count rule - skinny up to 32 rows, implicit GEMM above -
 // made batches of more than 32 segments differ from smaller ones by 1e-5: found by the pipelined UniSE driver at 64 segments per batch)
 int linear_per_item(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y) {
-    if (c.dry) return QA_OK;
+    if (c.dry) return QA_OK;  // real-pass-only function: it allocates nothing
     if (w.C_in % 256 != 0) return linear_op(c, x, rows, w, y);
     for (int64_t r0 = 0; r0 < rows; r0 += 32) {
         const int n = (int)std::min<int64_t>(32, rows - r0);
@@ -309,28 +281,23 @@ int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, 
     ConvOpt same7;
     same7.pad_left = 3; same7.pad_right = 3;
     QA_TRY(conv_op(c, in ? in : x, in ? v.embed.C_in : C, B, T, v.embed, t1, C, T, same7));
-    if (!c.dry) {
-        if (cond) QA_TRY(launch_adaln(t1, cond, cond + C, ld_cond, x, B, T, C, 1e-6f, c.stream));
-        else QA_TRY(launch_layernorm(t1, v.nw, v.nb, x, rows, C, 1e-6f, c.stream));
-    }
+    if (cond) QA_RUN(c, launch_adaln(t1, cond, cond + C, ld_cond, x, B, T, C, 1e-6f, c.stream));
+    else QA_TRY(layernorm_op(c, t1, v.nw, v.nb, x, rows, C, 1e-6f));
     for (size_t i = 0; i < v.layers.size(); ++i) {
         const VocosLayerW& w = v.layers[i];
-        if (!c.dry) {
-            if (cond) {
-                const float* sc = cond + (int64_t)(i + 1) * 2 * C;
-                QA_TRY(launch_dwconv(x, w.dw, w.dwb, nullptr, nullptr, u, B, T, C, 7, 0.f, c.stream));  // u doubles as [rows, C] scratch
-                QA_TRY(launch_adaln(u, sc, sc + C, ld_cond, t1, B, T, C, 1e-6f, c.stream));
-            } else {
-                QA_TRY(launch_dwconv(x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, C, 7, 1e-6f, c.stream));
-            }
+        if (cond) {
+            const float* sc = cond + (int64_t)(i + 1) * 2 * C;
+            QA_TRY(dwconv_op(c, x, w.dw, w.dwb, nullptr, nullptr, u, B, T, C, 7, 0.f));  // u doubles as [rows, C] scratch
+            QA_RUN(c, launch_adaln(u, sc, sc + C, ld_cond, t1, B, T, C, 1e-6f, c.stream));
+        } else {
+            QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, C, 7, 1e-6f));
         }
         QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
         QA_TRY(linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma)));
     }
-    if (!c.dry) {
-        QA_TRY(launch_layernorm(x, v.fw, v.fb, t1, rows, C, 1e-6f, c.stream));
-        QA_HIP(hipMemcpyAsync(x, t1, sizeof(float) * (size_t)rows * C, hipMemcpyDeviceToDevice, c.stream));
-    }
+    QA_TRY(layernorm_op(c, x, v.fw, v.fb, t1, rows, C, 1e-6f));
+    // real pass only, more than a launch: the normalised rows go back into x
+    if (!c.dry) QA_HIP(hipMemcpyAsync(x, t1, sizeof(float) * (size_t)rows * C, hipMemcpyDeviceToDevice, c.stream));
     return QA_OK;
 }
 
@@ -350,8 +317,7 @@ int postnet_op(const qa_bicodec::Postnet& p, Ctx& c, const float* px, int B, int
     QA_TRY(linear_op(c, x, rows, p.linear_out, o, epi(sp.postnet_tanh ? ACT_TANH : ACT_NONE)));
     c.tap("postnet.out", o, rows * O);
     // [B, T, O] read as a [B, C' = T, T' = O] tensor with strides (T O, O, 1): its channel-last form is [B, O, T]
-    if (!c.dry) QA_TRY(launch_to_channel_last(o, (long long)T * O, O, 1, pred, B, T, O, c.stream));
-    return QA_OK;
+    return to_channel_last_op(c, o, (long long)T * O, O, 1, pred, B, T, O);
 }
 
 // pred / dvec_out (forward only, else nullptr): the postnet's output from the prenet output BEFORE the d-vector add (bicodec.py:135-136),
@@ -366,10 +332,8 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     float* gflat = c.arena.alloc<float>((size_t)B * sp.spk_latent_dim * sp.token_num);
     float* dvec = c.arena.alloc<float>((size_t)B * Ld);
     float* cond = c.arena.alloc<float>((size_t)B * h->ada.N);
-    if (!c.dry) {
-        QA_TRY(launch_gather_rows(sem, h->sem_table, zq, rows, sp.codebook_size, Ld, c.stream));
-        QA_TRY(launch_gather_global(glob, h->glob_table, gflat, B, sp.token_num, h->n_glob, sp.spk_latent_dim, c.stream));
-    }
+    QA_RUN(c, launch_gather_rows(sem, h->sem_table, zq, rows, sp.codebook_size, Ld, c.stream));
+    QA_RUN(c, launch_gather_global(glob, h->glob_table, gflat, B, sp.token_num, h->n_glob, sp.spk_latent_dim, c.stream));
     QA_TRY(linear_per_item(c, gflat, B, h->project, dvec));
     QA_TRY(linear_per_item(c, dvec, B, h->ada, cond));
     c.tap("z_q", zq, rows * Ld);
@@ -390,8 +354,9 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
         QA_TRY(postnet_op(*h->post, c, px, B, T, pred));
         c.arena.release(m);
     }
+    // real pass only, more than a launch: forward's copy of the d-vector
     if (dvec_out && !c.dry) QA_HIP(hipMemcpyAsync(dvec_out, dvec, sizeof(float) * (size_t)B * Ld, hipMemcpyDeviceToDevice, c.stream));
-    if (!c.dry) QA_TRY(launch_add_rowvec(px, dvec, B, T, Ld, c.stream));
+    QA_RUN(c, launch_add_rowvec(px, dvec, B, T, Ld, c.stream));
     c.tap("prenet.out", px, rows * Ld);
     // ---- wave generator
     int ch = sp.gen_channels, Tc = T;
@@ -656,11 +621,9 @@ int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, l
     c.tap("enc.out", z, rows * Ld);
     float* ze = c.arena.alloc<float>(rows * D);
     QA_TRY(linear_op(c, z, rows, h->in_project, ze));
-    if (!c.dry) {
-        QA_TRY(launch_l2norm_rows(ze, ze, rows, D, c.stream));
-        // one stage, no residual kept: the codebook search of rvq.hip (dist = (|e|^2 - 2 e.c) + |c|^2, lowest index on a tie)
-        QA_TRY(launch_rvq_search(ze, rows, h->codebook, h->e2, 1, sp.codebook_size, D, tokens, nullptr, 0, nullptr, c.stream));
-    }
+    QA_RUN(c, launch_l2norm_rows(ze, ze, rows, D, c.stream));
+    // one stage, no residual kept: the codebook search of rvq.hip (dist = (|e|^2 - 2 e.c) + |c|^2, lowest index on a tie)
+    QA_RUN(c, launch_rvq_search(ze, rows, h->codebook, h->e2, 1, sp.codebook_size, D, tokens, nullptr, 0, nullptr, c.stream));
     c.tap("vq.latent", ze, rows * D);
     return QA_OK;
 }
@@ -683,9 +646,9 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     float* ri = c.arena.alloc<float>((size_t)rows * 2 * h->nbp);
     float* mag = c.arena.alloc<float>((size_t)rows * h->kp);
     float* mel = c.arena.alloc<float>((size_t)rows * sp.mel_dim);
-    if (!c.dry) QA_TRY(launch_mel_frames(wav, B, T, ref_len, hop, nf, P, c.stream));
+    QA_RUN(c, launch_mel_frames(wav, B, T, ref_len, hop, nf, P, c.stream));
     QA_TRY(conv_op(c, P, hop, B, nf + 1, h->dft, ri, 2 * h->nbp, nf, ConvOpt()));
-    if (!c.dry) QA_TRY(launch_spec_mag(ri, h->nbp, h->nb, mag, h->kp, rows, c.stream));
+    QA_RUN(c, launch_spec_mag(ri, h->nbp, h->nb, mag, h->kp, rows, c.stream));
     QA_TRY(linear_op(c, mag, rows, h->fbank, mel));
     c.tap("mel", mel, rows * sp.mel_dim);
     // ---- ECAPA-TDNN latent [B, nf, 1536]
@@ -701,10 +664,10 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     for (int bi = 0; bi < 3; ++bi) {
         const SeRes2W& b = h->blocks[bi];
         QA_TRY(conv_bn_relu(c, xin, ldin, B, nf, b.c0, y1, C, 0));
-        if (!c.dry) QA_TRY(launch_res2_chain(y1, y2, b.res2_w, b.res2_bst, B, nf, C, b.dilation, c.stream));
+        QA_RUN(c, launch_res2_chain(y1, y2, b.res2_w, b.res2_bst, B, nf, C, b.dilation, c.stream));
         QA_TRY(conv_bn_relu(c, y2, C, B, nf, b.c2, y1, C, 0));
-        if (!c.dry) QA_TRY(launch_se_residual(xin, ldin, y1, b.se_w1, b.se_b1, b.se_w2, b.se_b2, gate, cat + (size_t)bi * C, 3 * C, B, nf, C,
-                                              128, c.stream));
+        QA_RUN(c, launch_se_residual(xin, ldin, y1, b.se_w1, b.se_b1, b.se_w2, b.se_b2, gate, cat + (size_t)bi * C, 3 * C, B, nf, C, 128,
+                                     c.stream));
         xin = cat + (size_t)bi * C;
         ldin = 3 * C;
     }
@@ -730,28 +693,25 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     float* gg = c.arena.alloc<float>((size_t)lrows * h->ffp);
     float* pout = c.arena.alloc<float>((size_t)lrows * D);
     QA_TRY(linear_op(c, latent, rows, h->proj_context, xc));
-    if (!c.dry) {
-        QA_TRY(launch_perceiver_ctx(h->latents, 0, xc, ctx, B, nl, nf, D, c.stream));        // cat(latents, x)
-        QA_TRY(launch_perceiver_ctx(h->latents, 0, nullptr, lat, B, nl, 0, D, c.stream));    // latents, broadcast over the batch
-    }
+    QA_RUN(c, launch_perceiver_ctx(h->latents, 0, xc, ctx, B, nl, nf, D, c.stream));      // cat(latents, x)
+    QA_RUN(c, launch_perceiver_ctx(h->latents, 0, nullptr, lat, B, nl, 0, D, c.stream));  // latents, broadcast over the batch
     for (size_t li = 0; li < h->perceiver.size(); ++li) {
         const PerceiverLayerW& lw = h->perceiver[li];
-        if (li > 0 && !c.dry) QA_TRY(launch_perceiver_ctx(lat, (int64_t)nl * D, nullptr, ctx, B, nl, nf, D, c.stream));
+        if (li > 0) QA_RUN(c, launch_perceiver_ctx(lat, (int64_t)nl * D, nullptr, ctx, B, nl, nf, D, c.stream));
         QA_TRY(linear_op(c, lat, lrows, lw.to_q, q));
         QA_TRY(linear_op(c, ctx, (int64_t)B * nk, lw.to_kv, kv));
-        if (!c.dry)
-            QA_TRY(launch_attention(q, inner, kv, kv + inner, 2 * inner, att, inner, B, nl, nk, (int64_t)nk * 2 * inner, sp.perceiver_heads,
-                                    sp.perceiver_dim_head, 1.f / std::sqrt((float)sp.perceiver_dim_head), 0, c.stream));
+        QA_TRY(attention_op(c, q, inner, kv, kv + inner, 2 * inner, att, inner, B, nl, nk, (int64_t)nk * 2 * inner, sp.perceiver_heads,
+                            sp.perceiver_dim_head, 1.f / std::sqrt((float)sp.perceiver_dim_head), 0));
         QA_TRY(linear_op(c, att, lrows, lw.to_out, lat, epi(ACT_NONE, lat)));
         QA_TRY(linear_op(c, lat, lrows, lw.ff1, hh));
-        if (!c.dry) QA_TRY(launch_geglu(hh, h->ff, gg, h->ffp, lrows, c.stream));
+        QA_RUN(c, launch_geglu(hh, h->ff, gg, h->ffp, lrows, c.stream));
         QA_TRY(linear_op(c, gg, lrows, lw.ff2, lat, epi(ACT_NONE, lat)));
     }
-    if (!c.dry) QA_TRY(launch_l2norm_scale(lat, h->norm_gamma, pout, lrows, D, std::sqrt((float)D), c.stream));
+    QA_RUN(c, launch_l2norm_scale(lat, h->norm_gamma, pout, lrows, D, std::sqrt((float)D), c.stream));
     c.tap("perceiver.out", pout, lrows * D);
     // ---- ResidualFSQ indices
     float* bounded = c.capture ? c.arena.alloc<float>((size_t)lrows * sp.n_levels) : nullptr;
-    if (!c.dry) QA_TRY(launch_fsq(pout, h->fsq_in.w, h->fsq_in.b, sp.levels, sp.n_levels, D, lrows, tokens, bounded, c.stream));
+    QA_RUN(c, launch_fsq(pout, h->fsq_in.w, h->fsq_in.b, sp.levels, sp.n_levels, D, lrows, tokens, bounded, c.stream));
     if (bounded) c.tap("fsq.bounded", bounded, lrows * sp.n_levels);
     return QA_OK;
 }
@@ -870,11 +830,11 @@ int forward_enc_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N
     const qa_bicodec_enc_spec& sp = h->spec;
     const qa_bicodec_enc::XvecHead& xv = *h->xvec;
     QA_TRY(semantic_graph(h, c, feat, B, N, sem));
-    if (!c.dry) QA_TRY(launch_code_usage(sem, (long long)B * N, sp.codebook_size, perplexity, active, c.stream));
+    QA_RUN(c, launch_code_usage(sem, (long long)B * N, sp.codebook_size, perplexity, active, c.stream));
     int* g32 = c.arena.alloc<int>((size_t)B * sp.token_num);
     const float* latent = nullptr;
     QA_TRY(global_graph(h, c, wav, B, T, T, g32, &latent));
-    if (!c.dry) QA_TRY(launch_widen_i32(g32, glob, (long long)B * sp.token_num, c.stream));
+    QA_RUN(c, launch_widen_i32(g32, glob, (long long)B * sp.token_num, c.stream));
     // ---- x-vector (ecapa_tdnn.py:204-206): ASTP with the global context of ECAPA_TDNN_GLOB_c512 (pooling_layers.py:129-144), BN, Linear.
     // linear1(cat(x, mean, std)) = W_x x + (W_c [mean; std] + b): the context half is one row per item, folded into that item's bias
     const int nf = (int)(T / sp.hop_length) + 1;
@@ -885,7 +845,7 @@ int forward_enc_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N
     float* logit = c.arena.alloc<float>((size_t)rows * 1536);
     float* pool = c.arena.alloc<float>((size_t)B * 3072);
     float* bn = c.arena.alloc<float>((size_t)B * 3072);
-    if (!c.dry) QA_TRY(launch_frame_stats(latent, B, nf, 1536, ctx, c.stream));
+    QA_RUN(c, launch_frame_stats(latent, B, nf, 1536, ctx, c.stream));
     QA_TRY(linear_per_item(c, ctx, B, xv.lin1c, cb));
     for (int b = 0; b < B; ++b) {  // tanh(W_x x + cb[b]) over the item's frames
         ConvW w = xv.lin1x;
@@ -893,7 +853,7 @@ int forward_enc_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N
         QA_TRY(conv_op(c, latent + (size_t)b * nf * 1536, 1536, 1, nf, w, a1 + (size_t)b * nf * 128, 128, nf, epi(ACT_TANH)));
     }
     QA_TRY(linear_op(c, a1, rows, xv.lin2, logit));
-    if (!c.dry) QA_TRY(launch_astp_pool(logit, latent, B, nf, 1536, xv.bn_s, xv.bn_t, pool, bn, c.stream));
+    QA_RUN(c, launch_astp_pool(logit, latent, B, nf, 1536, xv.bn_s, xv.bn_t, pool, bn, c.stream));
     c.tap("ecapa.pool", pool, (int64_t)B * 3072);
     QA_TRY(linear_per_item(c, bn, B, xv.linear, xvec));
     c.tap("x_vector", xvec, (int64_t)B * xv.linear.N);

@@ -14,16 +14,6 @@
 
 #include "host_util.h"
 
-namespace qa {
-int launch_glu_dwconv_bn_silu(const float* u, const float* w31, const float* bias, const float* scale, const float* shift, float* y, int B,
-                              int T, int C, hipStream_t s);
-int launch_masked_add(float* x, float* y, const unsigned char* valid, long long rows, int C, hipStream_t s);
-int launch_mask_count(const unsigned char* valid, int B, int T, int* counts, hipStream_t s);
-int launch_logmel_frames(const float* wav, int B, long long n, int pad, long long n_out, float* P, hipStream_t s);
-int launch_log_eps(float* x, long long n, float eps, hipStream_t s);
-int launch_spec_mag(const float* ri, int nbp, int nb, float* mag, int ldm, long long rows, hipStream_t s);
-}  // namespace qa
-
 using namespace qa;
 
 namespace {
@@ -183,12 +173,12 @@ struct CfTemps {
 };
 
 int feed_forward_op(Ctx& c, const FeedForwardW& f, float* x, const CfTemps& t, int64_t rows, int d) {
-    QA_TRY(launch_layernorm(x, f.lnw, f.lnb, t.hn, rows, d, 1e-5f, c.stream));
+    QA_TRY(layernorm_op(c, x, f.lnw, f.lnb, t.hn, rows, d, 1e-5f));
     QA_TRY(linear_op(c, t.hn, rows, f.l1, t.u, epi(ACT_SILU)));
     return linear_op(c, t.u, rows, f.l2h, x, epi(ACT_NONE, x));
 }
 
-// the ConformerEncoder in place on x [B, T, dim]; taps are issued in the planning pass too (they allocate)
+// the ConformerEncoder in place on x [B, T, dim]
 int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mask, int B, int T) {
     const qa_cond_encoder_spec& sp = h->spec;
     const int d = sp.dim, H = sp.heads, hd = sp.dim_head, inner = H * hd;
@@ -199,30 +189,28 @@ int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mas
     t.u = c.arena.alloc<float>(rows * std::max(std::max(d * sp.ff_mult, 2 * d), 3 * inner));
     t.v = c.arena.alloc<float>(rows * std::max(inner, d));
     const float scale = 1.0f / std::sqrt((float)hd);
-#define RUN(expr) do { if (!c.dry) QA_TRY(expr); } while (0)
     for (int l = 0; l < sp.n_layers; ++l) {
         const ConformerLayerW& W = h->layers[l];
         const std::string lp = "conformer." + std::to_string(l);
-        RUN(feed_forward_op(c, W.ff1, x, t, rows, d));
+        QA_TRY(feed_forward_op(c, W.ff1, x, t, rows, d));
         c.tap(lp + ".ff1", x, rows * d);
-        RUN(launch_layernorm(x, W.anw, W.anb, t.hn, rows, d, 1e-5f, c.stream));
-        RUN(linear_op(c, t.hn, rows, W.qkv, t.u));
-        RUN(launch_rope(t.u, h->rope, B, T, H, hd, 3 * inner, 0, c.stream, sp.rope_interleaved, sp.pe_attn_head < 0 ? 0 : sp.pe_attn_head));
-        RUN(launch_attention(t.u, 3 * inner, t.u + inner, t.u + 2 * inner, 3 * inner, t.v, inner, B, T, T, (long long)T * 3 * inner, H, hd, scale,
-                             0, c.stream, nullptr, nullptr, 0, 0, 0, 0, mask));
-        RUN(linear_op(c, t.v, rows, W.out, t.hn));
-        RUN(launch_masked_add(x, t.hn, mask, rows, d, c.stream));
+        QA_TRY(layernorm_op(c, x, W.anw, W.anb, t.hn, rows, d, 1e-5f));
+        QA_TRY(linear_op(c, t.hn, rows, W.qkv, t.u));
+        QA_TRY(rope_op(c, t.u, h->rope, B, T, H, hd, 3 * inner, 0, sp.rope_interleaved, sp.pe_attn_head < 0 ? 0 : sp.pe_attn_head));
+        QA_TRY(attention_op(c, t.u, 3 * inner, t.u + inner, t.u + 2 * inner, 3 * inner, t.v, inner, B, T, T, (long long)T * 3 * inner, H, hd,
+                            scale, 0, nullptr, nullptr, 0, 0, 0, 0, mask));
+        QA_TRY(linear_op(c, t.v, rows, W.out, t.hn));
+        QA_RUN(c, launch_masked_add(x, t.hn, mask, rows, d, c.stream));
         c.tap(lp + ".attn", t.hn, rows * d);
-        RUN(launch_layernorm(x, W.cnw, W.cnb, t.hn, rows, d, 1e-5f, c.stream));
-        RUN(linear_op(c, t.hn, rows, W.pw1, t.u));
-        RUN(launch_glu_dwconv_bn_silu(t.u, W.dw, W.dwb, W.bns, W.bnt, t.v, B, T, d, c.stream));
-        RUN(linear_op(c, t.v, rows, W.pw2, x, epi(ACT_NONE, x)));
+        QA_TRY(layernorm_op(c, x, W.cnw, W.cnb, t.hn, rows, d, 1e-5f));
+        QA_TRY(linear_op(c, t.hn, rows, W.pw1, t.u));
+        QA_RUN(c, launch_glu_dwconv_bn_silu(t.u, W.dw, W.dwb, W.bns, W.bnt, t.v, B, T, d, c.stream));
+        QA_TRY(linear_op(c, t.v, rows, W.pw2, x, epi(ACT_NONE, x)));
         c.tap(lp + ".conv", x, rows * d);
-        RUN(feed_forward_op(c, W.ff2, x, t, rows, d));
-        RUN(launch_layernorm(x, W.fnw, W.fnb, x, rows, d, 1e-5f, c.stream));
+        QA_TRY(feed_forward_op(c, W.ff2, x, t, rows, d));
+        QA_TRY(layernorm_op(c, x, W.fnw, W.fnb, x, rows, d, 1e-5f));
         c.tap(lp + ".out", x, rows * d);
     }
-#undef RUN
     c.arena.release(mark);
     return QA_OK;
 }
@@ -364,6 +352,7 @@ int qa_conformer_forward(qa_cond_encoder* h, const float* x, const uint8_t* mask
     if (mask) QA_TRY(check_mask(h, mask, (int)B, (int)T, s));
     const int64_t n = B * T * h->spec.dim;
     return run_planned(*h, stream, [&]() -> int {
+        // real pass only, more than a launch: the copy of the input the encoder then updates in place
         if (!h->ctx.dry && out != x) QA_HIP(hipMemcpyAsync(out, x, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
         return encoder_graph(h, h->ctx, out, mask, (int)B, (int)T);
     });
@@ -427,12 +416,12 @@ int qa_logmel(const float* wav, int64_t B, int64_t n, int32_t n_fft, int32_t win
         float* P = c.arena.alloc<float>((size_t)B * (nf + 1) * m->hop);
         float* ri = c.arena.alloc<float>((size_t)rows * 2 * m->nbp);
         float* mag = c.arena.alloc<float>((size_t)rows * m->kp);
-        if (c.dry) return QA_OK;
-        QA_TRY(launch_logmel_frames(wav, (int)B, n, (m->win - m->hop) / 2, (nf + 1) * m->hop, P, c.stream));
+        QA_RUN(c, launch_logmel_frames(wav, (int)B, n, (m->win - m->hop) / 2, (nf + 1) * m->hop, P, c.stream));
         QA_TRY(conv_op(c, P, m->hop, (int)B, (int)nf + 1, m->dft, ri, 2 * m->nbp, (int)nf, ConvOpt()));
-        QA_TRY(launch_spec_mag(ri, m->nbp, m->nb, mag, m->kp, rows, c.stream));
+        QA_RUN(c, launch_spec_mag(ri, m->nbp, m->nb, mag, m->kp, rows, c.stream));
         QA_TRY(linear_op(c, mag, rows, m->fbank, out));
-        return launch_log_eps(out, rows * m->n_mels, 1e-10f, c.stream);
+        QA_RUN(c, launch_log_eps(out, rows * m->n_mels, 1e-10f, c.stream));
+        return QA_OK;
     };
     QA_TRY(plan(device, static_cast<hipStream_t>(stream), c, m->ws, graph));
     return graph();

@@ -306,29 +306,26 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const
     float* qkv = c.arena.alloc<float>(rows * 3 * d);
     float* att = c.arena.alloc<float>(rows * d);
     float* cst = c.arena.alloc<float>((size_t)B * d);
-    // taps allocate from the arena: they are issued in the planning pass too (RUN skips only the launches there)
-#define RUN(expr) do { if (!c.dry) QA_TRY(expr); } while (0)
     for (size_t l = 0; l < tw.layers.size(); ++l) {
         const TransformerLayerW& L = tw.layers[l];
         const std::string lp = tap_prefix + ".layers." + std::to_string(l);
-        RUN(launch_rmsnorm(x, L.ln1, hn, rows, d, 1e-6f, c.stream));
-        RUN(linear_op(c, hn, rows, L.ih, big));
-        RUN(launch_lstm(big, L.w_hh, hl, cst, B, N, d, c.stream));
+        QA_TRY(rmsnorm_op(c, x, L.ln1, hn, rows, d, 1e-6f));
+        QA_TRY(linear_op(c, hn, rows, L.ih, big));
+        QA_RUN(c, launch_lstm(big, L.w_hh, hl, cst, B, N, d, c.stream));
         c.tap(lp + ".self_attn.rnn", hl, rows * d);
-        RUN(linear_op(c, hl, rows, L.qkv, qkv));
-        RUN(launch_rope(qkv, tw.rope, B, N, H, hd, 3 * d, 0, c.stream));
-        RUN(launch_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd,
-                             1.0f / std::sqrt((float)hd), causal ? 1 : 0, c.stream));
+        QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
+        QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
+        QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd,
+                            1.0f / std::sqrt((float)hd), causal ? 1 : 0));
         c.tap(lp + ".att", att, rows * d);
-        RUN(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
+        QA_TRY(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_attn", x, rows * d);
-        RUN(launch_rmsnorm(x, L.ln2, hn, rows, d, 1e-6f, c.stream));
-        RUN(linear_op(c, hn, rows, L.w1, big));
-        RUN(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
-        RUN(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
+        QA_TRY(rmsnorm_op(c, x, L.ln2, hn, rows, d, 1e-6f));
+        QA_TRY(linear_op(c, hn, rows, L.w1, big));
+        QA_TRY(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
+        QA_TRY(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_mlp", x, rows * d);
     }
-#undef RUN
     c.arena.release(mark);
     return QA_OK;
 }
@@ -355,22 +352,22 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
     const float* rope = win ? st->rope_win : mw.rope;
     const int rope_pos0 = win ? pos0 - st->rope_base : pos0;
     const float scale = 1.0f / std::sqrt((float)hd);
-    QA_TRY(launch_layernorm(x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f, c.stream));
+    QA_TRY(layernorm_op(c, x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f));
     // fused QKV projection with the interleaved-pair RoPE of q and k applied in the GEMM epilogue (one launch less per layer)
     ConvOpt qo;
     qo.rope = rope; qo.rope_n = 2 * d; qo.rope_hd = hd; qo.rope_T = N; qo.rope_pos0 = rope_pos0;
     QA_TRY(linear_op(c, t.hn, rows, L.in_proj, t.qkv, qo));
     if (st) {
         // RingKVCache.complete(): the chunk's keys / values are written first, then every query attends over the ring
-        QA_TRY(launch_ring_append(t.qkv + d, t.qkv + 2 * d, 3 * d, st->kc[li], st->vc[li], B, N, d, st->cap, pos0, c.stream));
-        QA_TRY(launch_attention(t.qkv, 3 * d, st->kc[li], st->vc[li], d, t.att, d, B, N, st->cap, (long long)st->cap * d, H, hd, scale, 1,
-                                c.stream, nullptr, nullptr, 0, mw.context, pos0, pos0 + N));
+        QA_RUN(c, launch_ring_append(t.qkv + d, t.qkv + 2 * d, 3 * d, st->kc[li], st->vc[li], B, N, d, st->cap, pos0, c.stream));
+        QA_TRY(attention_op(c, t.qkv, 3 * d, st->kc[li], st->vc[li], d, t.att, d, B, N, st->cap, (long long)st->cap * d, H, hd, scale, 1,
+                            nullptr, nullptr, 0, mw.context, pos0, pos0 + N));
     } else {
-        QA_TRY(launch_attention(t.qkv, 3 * d, t.qkv + d, t.qkv + 2 * d, 3 * d, t.att, d, B, N, N, (long long)N * 3 * d, H, hd, scale,
-                                mw.causal, c.stream, nullptr, nullptr, 0, mw.causal ? mw.context : 0));
+        QA_TRY(attention_op(c, t.qkv, 3 * d, t.qkv + d, t.qkv + 2 * d, 3 * d, t.att, d, B, N, N, (long long)N * 3 * d, H, hd, scale,
+                            mw.causal, nullptr, nullptr, 0, mw.causal ? mw.context : 0));
     }
     QA_TRY(linear_op(c, t.att, rows, L.out_proj, x, epi(ACT_NONE, x, L.ls1)));
-    QA_TRY(launch_layernorm(x, L.n2w, L.n2b, t.hn, rows, d, 1e-5f, c.stream));
+    QA_TRY(layernorm_op(c, x, L.n2w, L.n2b, t.hn, rows, d, 1e-5f));
     QA_TRY(linear_op(c, t.hn, rows, L.lin1, t.u, epi(ACT_GELU)));
     return linear_op(c, t.u, rows, L.lin2, x, epi(ACT_NONE, x, L.ls2));
 }
@@ -378,8 +375,7 @@ int mimi_op(Ctx& c, const MimiW& mw, float* x, int B, int N) {
     QA_REQUIRE(N <= MAX_POS, "mimi transformer: sequence of %d tokens exceeds %d", N, MAX_POS);
     const size_t mark = c.arena.mark();
     const MimiTemps t = mimi_temps(c, mw, (int64_t)B * N);
-    if (!c.dry)
-        for (const MimiLayerW& L : mw.layers) QA_TRY(mimi_layer(c, mw, L, x, t, B, N));
+    for (const MimiLayerW& L : mw.layers) QA_TRY(mimi_layer(c, mw, L, x, t, B, N));
     c.arena.release(mark);
     return QA_OK;
 }
@@ -389,7 +385,7 @@ int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const Mim
     const size_t mark = c.arena.mark();
     const MimiTemps ta = mimi_temps(c, wa, (int64_t)B * N);
     const MimiTemps tb = mimi_temps(c, wb, (int64_t)B * N);
-    if (!c.dry) {
+    if (!c.dry) {  // real pass only, more than launches: c.stream alternates between the two streams
         hipStream_t main = c.stream;
         for (size_t l = 0; l < wa.layers.size(); ++l) {
             c.stream = main;
@@ -408,10 +404,9 @@ int groupnorm_op(Ctx& c, const float* x, const float* w, const float* b, float* 
                  int swish) {
     const size_t mark = c.arena.mark();
     double* scratch = c.arena.alloc<double>(groupnorm_scratch_bytes(B, T, G) / sizeof(double));
-    int st = QA_OK;
-    if (!c.dry) st = launch_groupnorm(x, w, b, y, scratch, B, T, C, G, 1e-6f, swish, c.stream);
+    QA_RUN(c, launch_groupnorm(x, w, b, y, scratch, B, T, C, G, 1e-6f, swish, c.stream));
     c.arena.release(mark);
-    return st;
+    return QA_OK;
 }
 
 int dec_resblock_op(Ctx& c, const DecResW& w, float* x, int B, int T, int C, int G, bool causal = false) {
@@ -430,8 +425,7 @@ int dec_resblock_op(Ctx& c, const DecResW& w, float* x, int B, int T, int C, int
 
 int convnext_op(Ctx& c, const ConvNeXtW& w, float* x, float* t1, float* u, int B, int T, int d, bool causal = false) {
     const int64_t rows = (int64_t)B * T;
-    if (c.dry) return QA_OK;
-    QA_TRY(launch_dwconv(x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, d, 7, 1e-6f, c.stream, zpad_left(7, causal)));
+    QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, d, 7, 1e-6f, zpad_left(7, causal)));
     QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
     return linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma));
 }
@@ -447,7 +441,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     float* ri = c.arena.alloc<float>(rows * 2 * nb);
     QA_TRY(conv_op(c, wav, blk, B, T / blk, h->stft_basis, ri, 2 * nb, N50, conv_geom(2, 1, 1)));
     float* feat = c.arena.alloc<float>(rows * h->stft_ld);
-    if (!c.dry) QA_TRY(launch_stft_post(ri, feat, rows, nb, 2 * nb, h->stft_ld, c.stream));
+    QA_RUN(c, launch_stft_post(ri, feat, rows, nb, 2 * nb, h->stft_ld, c.stream));
     c.tap("enc.stft", feat, rows * h->stft_ld);
     float* x = c.arena.alloc<float>(rows * d);
     float* t1 = c.arena.alloc<float>(rows * d);
@@ -455,11 +449,11 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     // vq/conv.py Conv1d (:39-47): zero padding (k - stride, 0) in the causal variant, (k / 2, k / 2) otherwise
     const bool cz = sp.causal != 0;
     QA_TRY(conv_op(c, feat, h->stft_ld, B, N50, h->enc_embed, t1, d, N50, conv_geom(1, cz ? 2 : 1, cz ? 0 : 1)));
-    if (!c.dry) QA_TRY(launch_layernorm(t1, h->enc_norm_w, h->enc_norm_b, x, rows, d, 1e-6f, c.stream));
+    QA_TRY(layernorm_op(c, t1, h->enc_norm_w, h->enc_norm_b, x, rows, d, 1e-6f));
     for (const ConvNeXtW& w : h->enc_cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz));
     c.tap("enc.prior", x, rows * d);
     QA_TRY(transformer_op(c, h->enc_tr, x, B, N50, "encoder.post_net.1", cz));
-    if (!c.dry) QA_TRY(launch_layernorm(x, h->enc_fnorm_w, h->enc_fnorm_b, t1, rows, d, 1e-6f, c.stream));
+    QA_TRY(layernorm_op(c, x, h->enc_fnorm_w, h->enc_fnorm_b, t1, rows, d, 1e-6f));
     const int k = h->enc_out20.ksize, st = sp.frame_stride;
     const int pl = cz ? k - st : k / 2, pr = cz ? 0 : k / 2;
     const int Nf = (N50 + pl + pr - k) / st + 1;
@@ -486,7 +480,7 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
         const int SC = sp.sem_ch;
         if (!(fsc == 1 && fst == sp.sem_in && fsb == (int64_t)n_feat * sp.sem_in)) {
             float* fcl = c.arena.alloc<float>((size_t)B * n_feat * sp.sem_in);
-            if (!c.dry) QA_TRY(launch_to_channel_last(feat, fsb, fsc, fst, fcl, B, sp.sem_in, n_feat, c.stream));
+            QA_TRY(to_channel_last_op(c, feat, fsb, fsc, fst, fcl, B, sp.sem_in, n_feat));
             f = fcl;
         }
         Ls = n_feat;
@@ -518,7 +512,7 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
     // stage 0 at C = 32: conv0 + residual block + ELU in ONE launch (seanet_front.hip): the [B L, 32] conv0 output never exists in HBM
     const bool front = seanet_front_supported(C, C / 2, L);
     float* x = (front && !c.capture) ? nullptr : c.arena.alloc<float>((size_t)B * L * C);
-    if (!c.dry && x) QA_TRY(launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, L, C, 7, c.stream, cz ? 6 : -1));
+    if (x) QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, L, C, 7, c.stream, cz ? 6 : -1));
     if (x) c.tap("enc.conv0", x, (int64_t)B * L * C);
     for (int i = 0; i < sp.n_ratios; ++i) {
         const int r = sp.ratios[i];
@@ -526,9 +520,8 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
         const size_t mark = c.arena.mark();
         float* sc = c.arena.alloc<float>((size_t)B * L * C);
         if (i == 0 && front) {
-            if (!c.dry)
-                QA_TRY(launch_seanet_front(wav, h->conv0_w, h->conv0_b, rb.k3.w, rb.k3.b, rb.sc.w, rb.sc.b, rb.pw.w, rb.pw.b, sc,
-                                           B, L, C, C / 2, cz ? 1 : 0, c.stream));
+            QA_RUN(c, launch_seanet_front(wav, h->conv0_w, h->conv0_b, rb.k3.w, rb.k3.b, rb.sc.w, rb.sc.b, rb.pw.w, rb.pw.b, sc, B, L, C,
+                                          C / 2, cz ? 1 : 0, c.stream));
         } else {
         float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
         // shortcut_1x1(x)
@@ -589,14 +582,10 @@ int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
     long long* ia = c.arena.alloc<long long>((size_t)B * N25 * Q);
     long long* is = c.arena.alloc<long long>((size_t)B * N25 * Q);
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * N25, sp.codebook_size, sp.code_dim));
-    if (!c.dry) {
-        QA_TRY(launch_rvq_search(emb, (long long)B * N25, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0,
-                                 rvq_ws, c.stream));
-        QA_TRY(launch_rvq_search(sem, (long long)B * N25, h->cb_s, h->e2_s, Q, sp.codebook_size, sp.code_dim, is, nullptr, 0,
-                                 rvq_ws, c.stream));
-        QA_TRY(launch_codes_to_bqn(ia, ac_out, B, N25, Q, c.stream));
-        QA_TRY(launch_codes_to_bqn(is, sc_out, B, N25, Q, c.stream));
-    }
+    QA_RUN(c, launch_rvq_search(emb, (long long)B * N25, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0, rvq_ws, c.stream));
+    QA_RUN(c, launch_rvq_search(sem, (long long)B * N25, h->cb_s, h->e2_s, Q, sp.codebook_size, sp.code_dim, is, nullptr, 0, rvq_ws, c.stream));
+    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, N25, Q, c.stream));
+    QA_RUN(c, launch_codes_to_bqn(is, sc_out, B, N25, Q, c.stream));
     return QA_OK;
 }
 
@@ -609,12 +598,10 @@ int decode_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* sco
     long long* ia = c.arena.alloc<long long>(rows25 * Q);
     long long* is = c.arena.alloc<long long>(rows25 * Q);
     float* cat = c.arena.alloc<float>(rows25 * 2 * D);
-    if (!c.dry) {
-        QA_TRY(launch_codes_from_bqn(ac, ia, B, N, Q, c.stream));
-        QA_TRY(launch_codes_from_bqn(scodes, is, B, N, Q, c.stream));
-        QA_TRY(launch_rvq_lookup(ia, rows25, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
-        QA_TRY(launch_rvq_lookup(is, rows25, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
-    }
+    QA_RUN(c, launch_codes_from_bqn(ac, ia, B, N, Q, c.stream));
+    QA_RUN(c, launch_codes_from_bqn(scodes, is, B, N, Q, c.stream));
+    QA_RUN(c, launch_rvq_lookup(ia, rows25, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
+    QA_RUN(c, launch_rvq_lookup(is, rows25, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
     return decode_tail(h, c, cat, B, N, wav_out);
 }
 
@@ -640,7 +627,7 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     } else {
         float* up = c.arena.alloc<float>(rows25 * 2 * d);
         QA_TRY(linear_op(c, cat, rows25, h->up, up));
-        if (!c.dry) QA_TRY(launch_dwconv(up, h->up_dw, h->up_dwb, nullptr, nullptr, x, B, N50, d, 5, 0.f, c.stream, zpad_left(5, cz)));
+        QA_TRY(dwconv_op(c, up, h->up_dw, h->up_dwb, nullptr, nullptr, x, B, N50, d, 5, 0.f, zpad_left(5, cz)));
     }
     c.tap("dec.embed", x, rows * d);
     QA_TRY(dec_resblock_op(c, h->dres[0], x, B, N50, d, sp.gn_groups, cz));
@@ -653,10 +640,10 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     float* t1 = c.arena.alloc<float>(rows * d);
     float* u = c.arena.alloc<float>(rows * sp.dec_inter);
     QA_TRY(groupnorm_op(c, x, h->gn_w, h->gn_b, t1, B, N50, d, sp.gn_groups, 0));
-    if (!c.dry) QA_TRY(launch_layernorm(t1, h->norm_w, h->norm_b, x, rows, d, 1e-6f, c.stream));
+    QA_TRY(layernorm_op(c, t1, h->norm_w, h->norm_b, x, rows, d, 1e-6f));
     c.tap("dec.prior", x, rows * d);
     for (const ConvNeXtW& w : h->cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz));
-    if (!c.dry) QA_TRY(launch_layernorm(x, h->fnorm_w, h->fnorm_b, t1, rows, d, 1e-6f, c.stream));
+    QA_TRY(layernorm_op(c, x, h->fnorm_w, h->fnorm_b, t1, rows, d, 1e-6f));
     c.tap("dec.backbone", t1, rows * d);
     // ISTFT head
     const int nb = sp.n_fft / 2 + 1;
@@ -664,10 +651,10 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     float* S = c.arena.alloc<float>(rows * h->spec_ld);
     float* frames = c.arena.alloc<float>(rows * sp.n_fft);
     QA_TRY(linear_op(c, t1, rows, h->head, y));
-    if (!c.dry) QA_TRY(launch_istft_spec(y, S, rows, nb, 2 * nb, h->spec_ld, c.stream));
+    QA_RUN(c, launch_istft_spec(y, S, rows, nb, 2 * nb, h->spec_ld, c.stream));
     c.tap("dec.spec", S, rows * h->spec_ld);
     QA_TRY(linear_op(c, S, rows, h->basis, frames));
-    if (!c.dry) QA_TRY(launch_istft_ola(frames, h->window, wav_out, B, N50, sp.n_fft, sp.hop, c.stream));
+    QA_RUN(c, launch_istft_ola(frames, h->window, wav_out, B, N50, sp.n_fft, sp.hop, c.stream));
     return QA_OK;
 }
 
@@ -694,7 +681,7 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, 
     int* nseg = c.arena.alloc<int>(B);
     int* gmax = c.arena.alloc<int>(1);
     int G = N;  // planning pass: worst case, every frame its own group
-    if (!c.dry) {
+    if (!c.dry) {  // real pass only, more than launches: the group count is read back and checked
         QA_TRY(launch_align(sem, B, N, D, threshold, sp.max_tokens_per_group, seg, start, len, nseg, gmax, c.stream));
         QA_TRY(read_scalar(c, h, gmax, &G));
         QA_REQUIRE(G >= 1 && G <= N, "encode: alignment produced %d groups for %d frames", G, N);
@@ -708,31 +695,28 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, 
     // semantic_aggregator(sem), acoustic_aggregator(emb): both use the alignment of the semantic stream and are otherwise
     // independent, so the two 32-layer stacks run concurrently on two streams (fork / join with events; no host sync)
     hipStream_t side = serial_mode() ? c.stream : h->side;  // qa_set_serial(1): one stream
-    if (!c.dry) {
-        QA_TRY(launch_agg_build(sem, seg, start, len, nseg, h->qemb_sem, inter_s, B, N, G, D, c.stream));
-        QA_TRY(launch_agg_build(emb, seg, start, len, nseg, h->qemb_ac, inter_a, B, N, G, D, c.stream));
+    QA_RUN(c, launch_agg_build(sem, seg, start, len, nseg, h->qemb_sem, inter_s, B, N, G, D, c.stream));
+    QA_RUN(c, launch_agg_build(emb, seg, start, len, nseg, h->qemb_ac, inter_a, B, N, G, D, c.stream));
+    if (!c.dry) {  // real pass only: the event fork
         QA_HIP(hipEventRecord(h->ev_fork, c.stream));
         QA_HIP(hipStreamWaitEvent(side, h->ev_fork, 0));
     }
     QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S));
-    if (!c.dry) {
-        hipStream_t main = c.stream;
-        QA_TRY(launch_agg_gather(inter_s, start, len, nseg, agg_s, B, N, G, D, main));
-        QA_TRY(launch_agg_gather(inter_a, start, len, nseg, agg_a, B, N, G, D, side));
+    QA_RUN(c, launch_agg_gather(inter_s, start, len, nseg, agg_s, B, N, G, D, c.stream));
+    QA_RUN(c, launch_agg_gather(inter_a, start, len, nseg, agg_a, B, N, G, D, side));
+    if (!c.dry) {  // real pass only: the event join
         QA_HIP(hipEventRecord(h->ev_join, side));
-        QA_HIP(hipStreamWaitEvent(main, h->ev_join, 0));
+        QA_HIP(hipStreamWaitEvent(c.stream, h->ev_join, 0));
     }
     c.tap("enc.emb_agg", agg_a, (int64_t)B * G * D);
     c.tap("enc.sem_agg", agg_s, (int64_t)B * G * D);
     long long* ia = c.arena.alloc<long long>((size_t)B * G * Q);
     long long* is = c.arena.alloc<long long>((size_t)B * G * Q);
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * G, sp.codebook_size, D));
-    if (!c.dry) {
-        QA_TRY(launch_rvq_search(agg_a, (long long)B * G, h->cb_a, h->e2_a, Q, sp.codebook_size, D, ia, nullptr, 0, rvq_ws, c.stream));
-        QA_TRY(launch_rvq_search(agg_s, (long long)B * G, h->cb_s, h->e2_s, Q, sp.codebook_size, D, is, nullptr, 0, rvq_ws, c.stream));
-        QA_TRY(launch_codes_inject(ia, len, ac_out, B, N, G, Q, sp.codebook_size, c.stream));
-        QA_TRY(launch_codes_inject(is, len, sc_out, B, N, G, Q, sp.codebook_size, c.stream));
-    }
+    QA_RUN(c, launch_rvq_search(agg_a, (long long)B * G, h->cb_a, h->e2_a, Q, sp.codebook_size, D, ia, nullptr, 0, rvq_ws, c.stream));
+    QA_RUN(c, launch_rvq_search(agg_s, (long long)B * G, h->cb_s, h->e2_s, Q, sp.codebook_size, D, is, nullptr, 0, rvq_ws, c.stream));
+    QA_RUN(c, launch_codes_inject(ia, len, ac_out, B, N, G, Q, sp.codebook_size, c.stream));
+    QA_RUN(c, launch_codes_inject(is, len, sc_out, B, N, G, Q, sp.codebook_size, c.stream));
     return QA_OK;
 }
 
@@ -744,13 +728,11 @@ int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long 
     long long* ia = c.arena.alloc<long long>(rows * Q);
     long long* is = c.arena.alloc<long long>(rows * Q);
     float* cat = c.arena.alloc<float>(rows * 2 * D);
-    if (!c.dry) {
-        // token lengths: the reference keeps the ones extracted from the SEMANTIC codes for both streams (codec_adaptive.py:185-186)
-        QA_TRY(launch_deaggregate(ac, scodes, ia, B, Q, G, N, sp.codebook_size, c.stream));
-        QA_TRY(launch_deaggregate(scodes, scodes, is, B, Q, G, N, sp.codebook_size, c.stream));
-        QA_TRY(launch_rvq_lookup(ia, rows, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
-        QA_TRY(launch_rvq_lookup(is, rows, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
-    }
+    // token lengths: the reference keeps the ones extracted from the SEMANTIC codes for both streams (codec_adaptive.py:185-186)
+    QA_RUN(c, launch_deaggregate(ac, scodes, ia, B, Q, G, N, sp.codebook_size, c.stream));
+    QA_RUN(c, launch_deaggregate(scodes, scodes, is, B, Q, G, N, sp.codebook_size, c.stream));
+    QA_RUN(c, launch_rvq_lookup(ia, rows, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
+    QA_RUN(c, launch_rvq_lookup(is, rows, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
     QA_TRY(mimi_op(c, h->bottleneck, cat, B, N));
     c.tap("dec.bottleneck", cat, rows * 2 * D);
     return decode_tail(h, c, cat, B, N, wav_out);
@@ -792,8 +774,7 @@ int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int
     QA_TRY(conv_same(c, x, B, L, sd.conv2, o));
     c.tap("sem_dec.out", o, (int64_t)B * L * O);
     // [B, L, O] read as a [B, C' = L, T' = O] tensor with strides (L O, O, 1): its channel-last form is [B, O, L]
-    if (!c.dry) QA_TRY(launch_to_channel_last(o, (long long)L * O, O, 1, pred, B, L, O, c.stream));
-    return QA_OK;
+    return to_channel_last_op(c, o, (long long)L * O, O, 1, pred, B, L, O);
 }
 
 // the semantic decoder from device-resident semantic indices [B*N, Q]: the look-up decode makes, then semantic_decoder_op.  It runs on
@@ -802,7 +783,7 @@ int semantic_decoder_from_codes(qa_hcodec* h, Ctx& c, const long long* is_rows, 
     const qa_hcodec_spec& sp = h->spec;
     const int64_t rows = (int64_t)B * N;
     float* z = c.arena.alloc<float>(rows * sp.code_dim);
-    if (!c.dry) QA_TRY(launch_rvq_lookup(is_rows, rows, h->cb_s, sp.num_quantizers, sp.codebook_size, sp.code_dim, z, sp.code_dim, c.stream));
+    QA_RUN(c, launch_rvq_lookup(is_rows, rows, h->cb_s, sp.num_quantizers, sp.codebook_size, sp.code_dim, z, sp.code_dim, c.stream));
     return semantic_decoder_op(*h->sdec, c, z, sp.code_dim, B, N, pred);
 }
 
@@ -814,7 +795,7 @@ int forward_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const fl
     QA_TRY(encode_graph(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc));
     // the decoder's own path from the codes (decode_graph), so recon is decode(encode()) bit for bit
     long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
-    if (!c.dry) QA_TRY(launch_codes_from_bqn(sc, is, B, N, Q, c.stream));
+    QA_RUN(c, launch_codes_from_bqn(sc, is, B, N, Q, c.stream));
     QA_TRY(decode_graph(h, c, ac, sc, B, N, recon));
     return semantic_decoder_from_codes(h, c, is, B, N, pred);
 }
@@ -830,10 +811,8 @@ int forward_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T,
     *G_out = G;
     // every item's groups cover all N frames (x_lens = T for the whole batch, codec_adaptive.py:106-107): decode at N frames
     long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
-    if (!c.dry) {
-        QA_TRY(launch_token_lengths(sc, token_lengths, B, Q, G, K, c.stream));
-        QA_TRY(launch_deaggregate(sc, sc, is, B, Q, G, N, K, c.stream));  // codec_adaptive.py:134-135
-    }
+    QA_RUN(c, launch_token_lengths(sc, token_lengths, B, Q, G, K, c.stream));
+    QA_RUN(c, launch_deaggregate(sc, sc, is, B, Q, G, N, K, c.stream));  // codec_adaptive.py:134-135
     QA_TRY(decode_adaptive_graph(h, c, ac, sc, B, G, N, recon));
     return semantic_decoder_from_codes(h, c, is, B, N, pred);
 }
@@ -1365,7 +1344,7 @@ static int mimi_run(qa_mimi* m, const float* x, int B, int T, float* y, hipStrea
     const int64_t rows = (int64_t)B * T;
     auto graph = [&]() -> int {
         const MimiTemps t = mimi_temps(c, m->w, rows);
-        if (c.dry) return QA_OK;
+        if (c.dry) return QA_OK;  // real-pass-only remainder (the copy and the layers), below the graph's only allocations
         if (y != x) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * rows * m->w.d, hipMemcpyDeviceToDevice, stream));
         for (size_t l = 0; l < m->w.layers.size(); ++l)
             QA_TRY(mimi_layer(c, m->w, m->w.layers[l], y, t, B, T, streaming ? &m->st : nullptr, l));

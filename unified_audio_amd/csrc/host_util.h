@@ -1,6 +1,6 @@
 // host_util.h - host-side plumbing shared by the model graphs: weight-table lookup, the folded-weight store and its loader,
-// the per-call bump arena, the workspace and the planning / execution context, the convolution launcher, test taps and the
-// resources every model handle owns.
+// the per-call bump arena, the workspace and the planning / execution context, the convolution launcher, the planning-pass gate of
+// every other launch (QA_RUN and the shared ops), test taps and the resources every model handle owns.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -341,6 +341,39 @@ inline int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const C
 // plain linear over `rows` rows
 inline int linear_op(Ctx& c, const float* x, int64_t rows, const ConvW& w, float* y, const ConvOpt& o = ConvOpt()) {
     return conv_op(c, x, w.C_in, 1, (int)rows, w, y, w.N, (int)rows, o);
+}
+
+// The gate of every other launch of a model graph: QA_RUN(c, launch_...(..., c.stream)) launches in the real pass and does nothing
+// (its arguments are not even evaluated) in the planning pass, whose arena addresses are made up.  Taps and allocations still happen
+// in both passes - they size the arena - only the launch is skipped.  A graph function touches the device through conv_op /
+// linear_op, the ops below and QA_RUN alone, or inside a commented real-pass block.
+#define QA_RUN(c, call) do { if (!(c).dry) QA_TRY(call); } while (0)
+
+// The launchers that more than one model file issues, on c.stream and gated like conv_op (arguments as in kernels.h).
+inline int layernorm_op(Ctx& c, const float* x, const float* w, const float* b, float* y, int64_t rows, int C, float eps) {
+    return c.dry ? QA_OK : launch_layernorm(x, w, b, y, rows, C, eps, c.stream);
+}
+inline int rmsnorm_op(Ctx& c, const float* x, const float* w, float* y, int64_t rows, int C, float eps) {
+    return c.dry ? QA_OK : launch_rmsnorm(x, w, y, rows, C, eps, c.stream);
+}
+inline int dwconv_op(Ctx& c, const float* x, const float* w_kc, const float* bias, const float* lnw, const float* lnb, float* y, int B,
+                     int T, int C, int ksize, float eps, int pad_left = -1) {
+    return c.dry ? QA_OK : launch_dwconv(x, w_kc, bias, lnw, lnb, y, B, T, C, ksize, eps, c.stream, pad_left);
+}
+inline int to_channel_last_op(Ctx& c, const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T) {
+    return c.dry ? QA_OK : launch_to_channel_last(x, sb, sc, st, y, B, C, T, c.stream);
+}
+inline int rope_op(Ctx& c, float* qkv, const float* cos_sin, int B, int N, int H, int hd, long long ld, int pos0, int interleaved = 0,
+                   int rot_heads = 0) {
+    return c.dry ? QA_OK : launch_rope(qkv, cos_sin, B, N, H, hd, ld, pos0, c.stream, interleaved, rot_heads);
+}
+inline int attention_op(Ctx& c, const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out, long long ldo,
+                        int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale, int causal,
+                        const float* gate = nullptr, const float* relbias = nullptr, int R = 0, int context = 0, int q_pos0 = 0,
+                        int ring_end = 0, const unsigned char* kvalid = nullptr) {
+    if (c.dry) return QA_OK;
+    return launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_batch_stride, H, hd, scale, causal, c.stream, gate, relbias, R,
+                            context, q_pos0, ring_end, kvalid);
 }
 
 // ---------------------------------------------------------------- planning a call

@@ -1,4 +1,7 @@
-// kernels.h - host-side launchers of every HIP kernel in libquarkaudio_hip.
+// kernels.h - host-side launchers of every HIP kernel in libquarkaudio_hip, grouped by the .hip file that defines them.  Every launcher
+// is declared once: here, in lm_decode.h (the fused decode step, next to its argument structs) or in common.h (launch_conv_gemm,
+// launch_weight_planes).  A .hip file includes the header that declares its launchers, so the compiler checks each definition against
+// the declaration its callers see; a model file declares none of its own.
 #pragma once
 #include <algorithm>
 
@@ -89,5 +92,65 @@ int launch_rvq_search(const float* x, long long n_vec, const float* codebooks, c
 int launch_rvq_norms(const float* codebooks, float* e2, int QK, int D, hipStream_t s);
 int launch_rvq_lookup(const long long* indices, long long n_vec, const float* codebooks, int Q, int K, int D, float* out,
                       long long ldo, hipStream_t s);
+
+// lm_kernels.hip
+int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_sos, const float* enroll_emb,
+                           const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s);
+int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate, long long ldg,
+                       const float* res, long long ldr, float* y, long long ldy, int M, int N, int K, int act, hipStream_t s,
+                       float rms_eps, int dual);
+int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
+                   hipStream_t s);
+int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
+                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s, int drop = 0);
+int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, const long long* tgt, float c, float sm, float* row_kl,
+                       int* row_ok, hipStream_t s);
+int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
+                         hipStream_t s);
+int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
+
+// ssl_kernels.hip
+size_t ssl_conv0_scratch_bytes(int B, int T1, int C0);
+int launch_ssl_conv0(const float* wav, const float* w_kc, const float* bias, const float* gamma, const float* beta, float* y,
+                     void* scratch, int B, int T, int T1, int C0, int ksize, int stride, int pad, int norm_group, float eps, int act,
+                     hipStream_t s);
+int launch_ssl_gate(const float* hidden, const float* wab, const float* bab, const float* cst, float* gate, int B, int N, int H, int hd,
+                    hipStream_t s);
+int launch_ssl_accumulate(float* dst, const float* src, long long n, int first, hipStream_t s);
+int launch_ssl_act(float* x, long long n, int act, hipStream_t s);
+int launch_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, hipStream_t s);
+
+// bicodec_kernels.hip
+int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s);
+int launch_gather_global(const long long* tok, const float* table, float* out, int B, int N, int V, int L, hipStream_t s);
+int launch_adaln(const float* x, const float* scale, const float* shift, long long ld_cond, float* y, int B, int T, int C, float eps,
+                 hipStream_t s);
+int launch_add_rowvec(float* x, const float* v, int B, int T, int C, hipStream_t s);
+int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s);
+int launch_l2norm_rows(const float* x, float* y, long long rows, int D, hipStream_t s);
+int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s);
+int launch_spec_mag(const float* ri, int nbp, int nb, float* mag, int ldm, long long rows, hipStream_t s);
+int launch_res2_chain(const float* x, float* y, const float* wt, const float* bst, int B, int T, int C, int d, hipStream_t s);
+int launch_se_residual(const float* x, long long ldx, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
+                       float* gate, float* out, long long ldo, int B, int T, int C, int Hd, hipStream_t s);
+int launch_perceiver_ctx(const float* lat, long long lat_b, const float* x, float* ctx, int B, int n_lat, int T, int D, hipStream_t s);
+int launch_geglu(const float* h, int F, float* out, int ldo, long long rows, hipStream_t s);
+int launch_l2norm_scale(const float* x, const float* gamma, float* y, long long rows, int D, float scale, hipStream_t s);
+int launch_fsq(const float* x, const float* w, const float* bias, const int* levels, int nl, int D, long long rows, int* tokens,
+               float* bounded, hipStream_t s);
+int launch_astp_pool(const float* logit, const float* x, int B, int T, int C, const float* bn_s, const float* bn_t, float* pool, float* bn,
+                     hipStream_t s);
+int launch_frame_stats(const float* x, int B, int T, int C, float* ctx, hipStream_t s);
+int launch_code_usage(const long long* idx, long long n, int K, float* perplexity, float* active, hipStream_t s);
+int launch_widen_i32(const int* src, long long* dst, long long n, hipStream_t s);
+
+// conformer_kernels.hip
+int launch_glu_dwconv_bn_silu(const float* u, const float* w31, const float* bias, const float* scale, const float* shift, float* y, int B,
+                              int T, int C, hipStream_t s);
+int launch_masked_add(float* x, float* y, const unsigned char* valid, long long rows, int C, hipStream_t s);
+int launch_mask_count(const unsigned char* valid, int B, int T, int* counts, hipStream_t s);
+int launch_logmel_frames(const float* wav, int B, long long n, int pad, long long n_out, float* P, hipStream_t s);
+int launch_log_eps(float* x, long long n, float eps, hipStream_t s);
+int launch_cond_prompt(float* x, const float* sos, const float* cond, int B, int T, int d, hipStream_t s);
 
 }  // namespace qa

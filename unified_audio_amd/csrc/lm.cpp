@@ -18,22 +18,6 @@
 #include "host_util.h"
 #include "lm_decode.h"
 
-namespace qa {
-int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_sos, const float* enroll_emb,
-                           const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s);
-int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
-                   hipStream_t s);
-int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
-                      int goff, int soff, long long* tgt, int B, int d, hipStream_t s, int drop = 0);
-int launch_cond_prompt(float* x, const float* sos, const float* cond, int B, int T, int d, hipStream_t s);
-int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, const long long* tgt, float c, float sm, float* row_kl,
-                       int* row_ok, hipStream_t s);
-int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
-                         hipStream_t s);
-int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
-
-}  // namespace qa
-
 using namespace qa;
 
 namespace {
@@ -260,19 +244,17 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
         const LMLayer& L = lm->layers[i];
         float* kc = b.kc + i * cache_stride;
         float* vc = b.vc + i * cache_stride;
-        if (!c.dry) {
-            const bool last = skip_last_mlp && i == sp.n_layers - 1;  // prefill: only the KV cache of the last layer is consumed
-            QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
-            QA_TRY(linear_op(c, b.hn, rows, L.qkv, b.qkv));
-            QA_TRY(launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream));
-            if (last) break;
-            QA_TRY(launch_attention(b.qkv, 3 * d, kc, vc, d, b.att, d, B, n, pos0 + n, (long long)max_len * d, H, hd, scale, 1, c.stream));
-            QA_TRY(linear_op(c, b.att, rows, L.o, b.x, epi(ACT_NONE, b.x)));
-            QA_TRY(launch_rmsnorm(b.x, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
-            QA_TRY(linear_op(c, b.hn, rows, L.gate, b.g));
-            QA_TRY(linear_op(c, b.hn, rows, L.up, b.u, epi(ACT_NONE, nullptr, nullptr, b.g)));
-            QA_TRY(linear_op(c, b.u, rows, L.down, b.x, epi(ACT_NONE, b.x)));
-        }
+        const bool last = skip_last_mlp && i == sp.n_layers - 1;  // prefill: only the KV cache of the last layer is consumed
+        QA_TRY(rmsnorm_op(c, b.x, lm->ones, b.hn, rows, d, sp.rms_eps));
+        QA_TRY(linear_op(c, b.hn, rows, L.qkv, b.qkv));
+        QA_RUN(c, launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream));
+        if (last) break;
+        QA_TRY(attention_op(c, b.qkv, 3 * d, kc, vc, d, b.att, d, B, n, pos0 + n, (long long)max_len * d, H, hd, scale, 1));
+        QA_TRY(linear_op(c, b.att, rows, L.o, b.x, epi(ACT_NONE, b.x)));
+        QA_TRY(rmsnorm_op(c, b.x, lm->ones, b.hn, rows, d, sp.rms_eps));
+        QA_TRY(linear_op(c, b.hn, rows, L.gate, b.g));
+        QA_TRY(linear_op(c, b.hn, rows, L.up, b.u, epi(ACT_NONE, nullptr, nullptr, b.g)));
+        QA_TRY(linear_op(c, b.u, rows, L.down, b.x, epi(ACT_NONE, b.x)));
     }
     return QA_OK;
 }
@@ -474,7 +456,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
         chains[i].B = std::min(cb, B - i * cb);
         QA_TRY(chain_alloc(lm, c, chains[i], L, cap, G, S, Nm, Ne, enroll != nullptr));
     }
-    if (c.dry) return QA_OK;
+    if (c.dry) return QA_OK;  // real-pass-only remainder: chain_alloc above made the function's last arena allocations
     const bool multi = nc > 1;
     if (multi) {  // fork: the chains' streams start behind everything already queued on the caller's stream
         while ((int)lm->chain_streams.size() < nc) {
@@ -525,7 +507,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     int pos = L;
     const bool graphs = !capturing && (multi || use_graphs());
     // taps: logits.global [B][G + 1][global_size], then logits.semantic [B][S][semantic_size]
-    float* const tap_base = lm->taps && !c.dry ? reinterpret_cast<float*>(lm->tap_buf.ptr) : nullptr;
+    float* const tap_base = lm->taps ? reinterpret_cast<float*>(lm->tap_buf.ptr) : nullptr;
     auto phase = [&](int which, long long first_id, int steps, int lo, int width, int keep) -> int {
         const int ids_ld = keep;
         float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * Gs * sp.global_size) : nullptr;
@@ -631,7 +613,7 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     int* row_ok = c.arena.alloc<int>(trow);
     float* logits = c.arena.alloc<float>((size_t)chunk * V);
     double* seq_sum = c.arena.alloc<double>(a.B);
-    if (c.dry) return QA_OK;
+    if (c.dry) return QA_OK;  // real-pass-only remainder: seq_sum above is the function's last arena allocation
     // the reference's true_dist is fp32: confidence 1 - eps and eps / (V - 1) filled into a float tensor (llm.py:95-98)
     const float conf = (float)(1.0 - a.eps), smooth = (float)(a.eps / (V - 1));
     for (int b0 = 0; b0 < a.B; b0 += GB) {

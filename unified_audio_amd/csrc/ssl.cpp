@@ -11,18 +11,6 @@
 
 #include "host_util.h"
 
-namespace qa {
-size_t ssl_conv0_scratch_bytes(int B, int T1, int C0);
-int launch_ssl_conv0(const float* wav, const float* w_kc, const float* bias, const float* gamma, const float* beta, float* y,
-                     void* scratch, int B, int T, int T1, int C0, int ksize, int stride, int pad, int norm_group, float eps, int act,
-                     hipStream_t s);
-int launch_ssl_gate(const float* hidden, const float* wab, const float* bab, const float* cst, float* gate, int B, int N, int H, int hd,
-                    hipStream_t s);
-int launch_ssl_accumulate(float* dst, const float* src, long long n, int first, hipStream_t s);
-int launch_ssl_act(float* x, long long n, int act, hipStream_t s);
-int launch_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, hipStream_t s);
-}  // namespace qa
-
 using namespace qa;
 
 namespace {
@@ -49,11 +37,6 @@ struct qa_ssl : Handle {
 };
 
 namespace {
-
-int layernorm(Ctx& c, const float* x, const float* w, const float* b, float* y, int64_t rows, int C, float eps) {
-    if (c.dry) return QA_OK;
-    return launch_layernorm(x, w, b, y, rows, C, eps, c.stream);
-}
 
 int64_t frames_of(const qa_ssl_spec& sp, int64_t T) {
     int64_t L = T + 2 * (int64_t)sp.pad;
@@ -242,14 +225,12 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     {
         const size_t mark = c.arena.mark();
         char* scratch = c.arena.alloc<char>(ssl_conv0_scratch_bytes(B, L, C));
-        if (!c.dry)
-            QA_TRY(launch_ssl_conv0(wav, h->conv0_w, h->conv0_b, h->gn_w, h->gn_b, x, scratch, B, T, L, C, sp.conv_kernel[0],
-                                    sp.conv_stride[0], sp.pad, sp.feat_norm_layer ? 0 : 1, 1e-5f, sp.feat_norm_layer ? ACT_NONE : ACT_GELU,
-                                    c.stream));
+        QA_RUN(c, launch_ssl_conv0(wav, h->conv0_w, h->conv0_b, h->gn_w, h->gn_b, x, scratch, B, T, L, C, sp.conv_kernel[0], sp.conv_stride[0],
+                                   sp.pad, sp.feat_norm_layer ? 0 : 1, 1e-5f, sp.feat_norm_layer ? ACT_NONE : ACT_GELU, c.stream));
         c.arena.release(mark);
         if (sp.feat_norm_layer) {
-            QA_TRY(layernorm(c, x, h->cln_w[0], h->cln_b[0], x, (int64_t)B * L, C, 1e-5f));
-            if (!c.dry) QA_TRY(launch_ssl_act(x, (long long)B * L * C, ACT_GELU, c.stream));
+            QA_TRY(layernorm_op(c, x, h->cln_w[0], h->cln_b[0], x, (int64_t)B * L, C, 1e-5f));
+            QA_RUN(c, launch_ssl_act(x, (long long)B * L * C, ACT_GELU, c.stream));
         }
     }
     c.tap("ssl.conv0", x, (int64_t)B * L * C);
@@ -262,8 +243,8 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         o.act = sp.feat_norm_layer ? ACT_NONE : ACT_GELU;
         QA_TRY(conv_op(c, x, C, B, L, w, y, w.N, Lo, o));
         if (sp.feat_norm_layer) {
-            QA_TRY(layernorm(c, y, h->cln_w[i], h->cln_b[i], y, (int64_t)B * Lo, w.N, 1e-5f));
-            if (!c.dry) QA_TRY(launch_ssl_act(y, (long long)B * Lo * w.N, ACT_GELU, c.stream));
+            QA_TRY(layernorm_op(c, y, h->cln_w[i], h->cln_b[i], y, (int64_t)B * Lo, w.N, 1e-5f));
+            QA_RUN(c, launch_ssl_act(y, (long long)B * Lo * w.N, ACT_GELU, c.stream));
         }
         x = y;
         L = Lo;
@@ -283,7 +264,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     float* acc = c.arena.alloc<float>((size_t)rows * d);
     const bool rel = sp.rel_pos_buckets > 0;
     float* gate = rel ? c.arena.alloc<float>((size_t)rows * H) : nullptr;
-    QA_TRY(layernorm(c, x, h->fp_ln_w, h->fp_ln_b, t0, rows, C, eps));
+    QA_TRY(layernorm_op(c, x, h->fp_ln_w, h->fp_ln_b, t0, rows, C, eps));
     QA_TRY(linear_op(c, t0, rows, h->fp, hcur));
     // ---- encoder front: h = h + GELU(pos_conv(h))  (HubertPositionalConvEmbedding; the even kernel's extra output frame is
     // never computed), then LayerNorm for the post-LN flavour
@@ -297,7 +278,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
             QA_TRY(conv_op(c, hcur + (size_t)g * cg, d, B, N, h->pos[g], hnext + (size_t)g * cg, d, N, o));
         }
         if (!sp.stable_layer_norm) {
-            QA_TRY(layernorm(c, hnext, h->enc_ln_w, h->enc_ln_b, hcur, rows, d, eps));
+            QA_TRY(layernorm_op(c, hnext, h->enc_ln_w, h->enc_ln_b, hcur, rows, d, eps));
         } else {
             std::swap(hcur, hnext);
         }
@@ -307,7 +288,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     auto maybe_accumulate = [&](int index, const float* hs) -> int {
         for (int sidx : h->select)
             if (sidx == index) {
-                if (!c.dry) QA_TRY(launch_ssl_accumulate(acc, hs, (long long)rows * d, n_acc == 0, c.stream));
+                QA_RUN(c, launch_ssl_accumulate(acc, hs, (long long)rows * d, n_acc == 0, c.stream));
                 ++n_acc;
             }
         return QA_OK;
@@ -318,31 +299,27 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         const SslLayer& Lw = h->layers[i];
         if (!sp.stable_layer_norm) {  // HubertEncoderLayer: x = LN(x + Attn(x)); x = LN(x + FFN(x))
             QA_TRY(linear_op(c, hcur, rows, Lw.qkv, qkv));
-            if (!c.dry) {
-                if (rel) QA_TRY(launch_ssl_gate(hcur, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
-                QA_TRY(launch_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0,
-                                        c.stream, gate, rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
-            }
+            if (rel) QA_RUN(c, launch_ssl_gate(hcur, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
+            QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0, gate,
+                                rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
             QA_TRY(linear_op(c, att, rows, Lw.o, tmp, epi(ACT_NONE, hcur)));
-            QA_TRY(layernorm(c, tmp, Lw.ln1w, Lw.ln1b, hnext, rows, d, eps));
+            QA_TRY(layernorm_op(c, tmp, Lw.ln1w, Lw.ln1b, hnext, rows, d, eps));
             QA_TRY(linear_op(c, hnext, rows, Lw.ff1, ffu, epi(ACT_GELU)));
             QA_TRY(linear_op(c, ffu, rows, Lw.ff2, tmp, epi(ACT_NONE, hnext)));
-            QA_TRY(layernorm(c, tmp, Lw.ln2w, Lw.ln2b, hcur, rows, d, eps));
+            QA_TRY(layernorm_op(c, tmp, Lw.ln2w, Lw.ln2b, hcur, rows, d, eps));
             QA_TRY(maybe_accumulate(i + 1, hcur));
         } else {  // HubertEncoderLayerStableLayerNorm: x = x + Attn(LN(x)); x = x + FFN(LN(x)); final LN after the last layer
-            QA_TRY(layernorm(c, hcur, Lw.ln1w, Lw.ln1b, tmp, rows, d, eps));
+            QA_TRY(layernorm_op(c, hcur, Lw.ln1w, Lw.ln1b, tmp, rows, d, eps));
             QA_TRY(linear_op(c, tmp, rows, Lw.qkv, qkv));
-            if (!c.dry) {
-                if (rel) QA_TRY(launch_ssl_gate(tmp, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
-                QA_TRY(launch_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0,
-                                        c.stream, gate, rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
-            }
+            if (rel) QA_RUN(c, launch_ssl_gate(tmp, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
+            QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0, gate,
+                                rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
             QA_TRY(linear_op(c, att, rows, Lw.o, hcur, epi(ACT_NONE, hcur)));
-            QA_TRY(layernorm(c, hcur, Lw.ln2w, Lw.ln2b, tmp, rows, d, eps));
+            QA_TRY(layernorm_op(c, hcur, Lw.ln2w, Lw.ln2b, tmp, rows, d, eps));
             QA_TRY(linear_op(c, tmp, rows, Lw.ff1, ffu, epi(ACT_GELU)));
             QA_TRY(linear_op(c, ffu, rows, Lw.ff2, hcur, epi(ACT_NONE, hcur)));
             if (i == sp.n_layers - 1) {
-                QA_TRY(layernorm(c, hcur, h->enc_ln_w, h->enc_ln_b, tmp, rows, d, eps));
+                QA_TRY(layernorm_op(c, hcur, h->enc_ln_w, h->enc_ln_b, tmp, rows, d, eps));
                 QA_TRY(maybe_accumulate(i + 1, tmp));
             } else {
                 QA_TRY(maybe_accumulate(i + 1, hcur));
@@ -350,7 +327,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         }
     }
     QA_REQUIRE(n_acc > 0, "ssl: no hidden state selected");
-    if (!c.dry) QA_TRY(launch_ssl_compress(acc, feats, (long long)rows * d, 1.0f / (float)n_acc, sp.compress_exponent, c.stream));
+    QA_RUN(c, launch_ssl_compress(acc, feats, (long long)rows * d, 1.0f / (float)n_acc, sp.compress_exponent, c.stream));
     return QA_OK;
 }
 
