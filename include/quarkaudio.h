@@ -295,6 +295,10 @@ int qa_set_serial(int32_t on);
  * call's recurrence was in flight (the co-residency ticket: two handles driving one device never starve each other's grid barrier),
  * out[3] 1 once a barrier time-out has degraded the device to the per-step kernels. */
 int qa_debug_lstm_stats(int32_t device, int64_t* out4);
+/* Attention launches the host has issued in this process so far, by arithmetic (tests): out2[0] the fp32 chain (QA_ATT_MATH = 0, and
+ * every launch of a UniSE LM handle), out2[1] split-6.  Counted where the host launches: a launch recorded into a captured graph counts
+ * once, at capture, and its replays do not count. */
+int qa_debug_att_stats(int64_t* out2);
 
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Every A/B switch of the library is one row of a table (csrc/knobs.h; INTEGRATION.md lists them): an integer whose initial

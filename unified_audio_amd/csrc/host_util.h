@@ -159,6 +159,7 @@ struct Ctx {
     hipStream_t stream = nullptr;
     bool dry = false;      // planning pass: allocate, do not launch
     bool gemm_fp32 = false;  // conv_op launches keep conv_gemm's fp32 chain (ConvParams::math_fp32)
+    bool att_fp32 = false;   // attention_op launches keep attention_kernel's fp32 chain (set wherever gemm_fp32 is)
     bool capture = false;  // test hook: snapshot named intermediates (buffers are reused / updated in place later)
     std::unordered_map<std::string, Tap> taps;
     void tap(const std::string& name, const float* p, int64_t n) {
@@ -373,7 +374,7 @@ inline int attention_op(Ctx& c, const float* q, long long ldq, const float* k, c
                         int ring_end = 0, const unsigned char* kvalid = nullptr) {
     if (c.dry) return QA_OK;
     return launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_batch_stride, H, hd, scale, causal, c.stream, gate, relbias, R,
-                            context, q_pos0, ring_end, kvalid);
+                            context, q_pos0, ring_end, kvalid, c.att_fp32);
 }
 
 // ---------------------------------------------------------------- planning a call

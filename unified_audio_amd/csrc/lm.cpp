@@ -711,6 +711,7 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     if (lm->taps) QA_TRY(ensure_taps(lm, B, global_length, semantic_length, stream));
     Ctx& c = lm->ctx;
     c.gemm_fp32 = true;  // ConvParams::math_fp32
+    c.att_fp32 = true;   // the prefill attention stays consistent with the fp32 decode kernels
     auto graph = [&] {
         return generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
                               (long long*)global_ids, (long long*)semantic_ids, sc, cond_mode, cond, (int)Tc);
@@ -789,6 +790,7 @@ static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int
     }
     Ctx c;
     c.gemm_fp32 = true;  // ConvParams::math_fp32
+    c.att_fp32 = true;   // the prefill attention stays consistent with the fp32 decode kernels
     auto graph = [&] { return score_graph(lm, c, a, tap); };
     QA_TRY(plan(lm->device, s, c, lm->score_ws, graph, [&](size_t bytes) -> int {
         QA_REQUIRE(!capturing, "qa_lm_score under a stream capture needs %zu bytes of workspace, the handle holds %zu: make one call of the "
