@@ -1,5 +1,6 @@
-"""attention_kernel (csrc/attention.hip) in every mode its callers use, through the test hook qa_debug_attention_ex, against a
-float64 truth built from the reference's semantics (not from the kernel's formulas).
+"""attention_kernel (csrc/attention.hip) in every mode its callers use and in both arithmetic forms (QA_ATT_MATH = 0: the fp32 chain,
+1: split-6; (a), (b) and (d) run once per form), through the test hook qa_debug_attention_ex, against a float64 truth built from the
+reference's semantics (not from the kernel's formulas).
 
     mode     layout (the caller's)                                          mask / bias
     self     fused QKV [B, N, 3d] (H-Codec transformers, HuBERT / XLSR)     none
@@ -48,6 +49,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import functools
 import zlib
 
 import pytest
@@ -56,7 +58,7 @@ import torch.nn.functional as F
 
 from oracle.hcodec15_ref import MimiStreamState
 from oracle.ssl_ref import relative_position_bucket
-from tests.util import SENTINEL_BITS, check_guarded_out, guarded_out
+from tests.util import SENTINEL_BITS, check_guarded_out, guarded_out, with_knob
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +68,8 @@ S_ULP = 2.0 ** -24  # floor per unit of the largest visible |score|: one fp32 ro
 HEAD_ROWS, TAIL_ROWS = 2, 32  # NaN rows around every input buffer: a clamped or unclamped row read past either end finds NaN
 OUT_HEAD = 4                  # output offset into its guarded buffer (floats; stores are 16-byte aligned)
 HDS = (32, 64, 96, 128)
-REPORT = []                   # (mode, hd, regime, geometry, e_hip, e_cpu32, bound), printed by test_parity_report
+MATHS = (0, 1)                # QA_ATT_MATH: the fp32 chain, split-6
+REPORT = []                   # (math, mode, hd, regime, geometry, e_hip, e_cpu32, bound), printed by test_parity_report
 
 
 @dataclasses.dataclass(frozen=True)
@@ -267,29 +270,42 @@ def _seed(c: Case, regime: str) -> int:
     return zlib.crc32(f"{c}{regime}".encode())
 
 
+def _truth(c: Case, regime: str, rows, x):
+    """-> (t64, e_cpu32, s_max, blind) of inputs x: the fp64 truth, the host's own fp32 error, the largest visible |score| and the
+    queries with no visible key."""
+    t64 = attention_truth(c, x, torch.float64, rows)
+    t32 = attention_truth(c, x, torch.float32, rows)
+    e_cpu = float((t32.double() - t64).abs().max()) / max(float(t64.abs().max()), 1e-300)
+    qi = torch.arange(c.n_q) if rows is None else torch.as_tensor(rows)
+    s64 = scores(c, x, torch.float64, qi)
+    s_max = float(s64[torch.isfinite(s64)].abs().max()) if torch.isfinite(s64).any() else 0.0
+    return t64, e_cpu, s_max, ~reference_mask(c, qi).any(-1)
+
+
+@functools.lru_cache(maxsize=64)  # the two forms of one (mode, hd) run back to back and share the truth of the seeded inputs
+def _seeded_truth(c: Case, regime: str, rows):
+    return _truth(c, regime, rows, make_inputs(c, regime, _seed(c, regime)))
+
+
 def check_parity(lib, c: Case, regime: str, rows=None, x=None):
-    """-> (e_hip, e_cpu32, bound, message or None)."""
+    """The form QA_ATT_MATH selects at the time of the call -> (e_hip, e_cpu32, bound, message or None)."""
+    from unified_audio_amd import _lib
+
+    math = int(_lib.get_knob("QA_ATT_MATH"))
+    t64, e_cpu, s_max, blind = _seeded_truth(c, regime, rows and tuple(rows)) if x is None else _truth(c, regime, rows, x)
     x = make_inputs(c, regime, _seed(c, regime)) if x is None else x
     out = launch(lib, c, pack(c, x, torch.device("cuda"))).cpu()
     if rows is not None:
         out = out[:, torch.as_tensor(rows)]
-    t64 = attention_truth(c, x, torch.float64, rows)
-    t32 = attention_truth(c, x, torch.float32, rows)
-    scale = float(t64.abs().max())
-    e_hip = float((out.double() - t64).abs().max()) / max(scale, 1e-300)
-    e_cpu = float((t32.double() - t64).abs().max()) / max(scale, 1e-300)
-    qi = torch.arange(c.n_q) if rows is None else torch.as_tensor(rows)
-    s64 = scores(c, x, torch.float64, qi)
-    s_max = float(s64[torch.isfinite(s64)].abs().max()) if torch.isfinite(s64).any() else 0.0
+    e_hip = float((out.double() - t64).abs().max()) / max(float(t64.abs().max()), 1e-300)
     bound = C_PARITY * max(e_cpu, E_FLOOR, S_ULP * s_max)
-    blind = ~reference_mask(c, qi).any(-1)  # queries with no visible key: exactly 0
     msg = None
     if blind.any() and not torch.equal(out[:, blind], torch.zeros_like(out[:, blind])):
         msg = f"{c.tag()} {regime}: a query with no visible key is not exactly 0"
     elif not e_hip <= bound:
         msg = f"{c.tag()} {regime}: e_hip {e_hip:.3e} > bound {bound:.3e} (e_cpu32 {e_cpu:.3e})"
-    REPORT.append((c.mode, c.hd, regime, c.tag(), e_hip, e_cpu, bound))
-    print(f"ATTN {c.mode} hd{c.hd} {regime} {c.tag()} e_hip {e_hip:.3e} e_cpu32 {e_cpu:.3e} bound {bound:.3e} frac {e_hip / bound:.3f}")
+    REPORT.append((math, c.mode, c.hd, regime, c.tag(), e_hip, e_cpu, bound))
+    print(f"ATTN math{math} {c.mode} hd{c.hd} {regime} {c.tag()} e_hip {e_hip:.3e} e_cpu32 {e_cpu:.3e} bound {bound:.3e} frac {e_hip / bound:.3f}")
     return e_hip, e_cpu, bound, msg
 
 
@@ -329,15 +345,22 @@ def matrix_cases(mode: str, hd: int):
 MODES = ("self", "cross", "cache", "window", "ring", "bias")
 
 
-@pytest.mark.parametrize("hd", HDS)
-@pytest.mark.parametrize("mode", MODES)
-def test_attention_fp64_parity_matrix(qa_lib, gpu_device, mode, hd):
+def per_form(cases):
+    """pytest params of every case (a tuple of arguments) in both forms, the two side by side (they share _seeded_truth).  The split-6
+    case keeps the id the case had when this file ran the default form alone; the fp32 case adds "-fp32"."""
+    return [pytest.param(*c, math, id="-".join(map(str, c)) + ("" if math else "-fp32")) for c in cases for math in MATHS]
+
+
+
+@pytest.mark.parametrize("mode,hd,math", per_form([(mode, hd) for mode in MODES for hd in HDS]))
+def test_attention_fp64_parity_matrix(qa_lib, gpu_device, mode, hd, math):
     bad = []
-    for c in matrix_cases(mode, hd):
-        for regime in ("randn", "peaked"):
-            msg = check_parity(qa_lib, c, regime)[3]
-            if msg:
-                bad.append(msg)
+    with with_knob("QA_ATT_MATH", math):
+        for c in matrix_cases(mode, hd):
+            for regime in ("randn", "peaked"):
+                msg = check_parity(qa_lib, c, regime)[3]
+                if msg:
+                    bad.append(msg)
     assert not bad, "\n".join(bad)
 
 
@@ -357,13 +380,14 @@ AT_SIZE = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(AT_SIZE))
-def test_attention_at_caller_size(qa_lib, gpu_device, name):
+@pytest.mark.parametrize("name,math", per_form([(name,) for name in sorted(AT_SIZE)]))
+def test_attention_at_caller_size(qa_lib, gpu_device, name, math):
     c = AT_SIZE[name]
     g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
     edges = {0, 1, 31, 32, 33, 127, 128, 129, c.n_q - 1}
     rows = sorted({r for r in edges if r < c.n_q} | set(torch.randint(0, c.n_q, (24,), generator=g).tolist()))
-    msg = check_parity(qa_lib, c, "randn", rows=rows)[3]
+    with with_knob("QA_ATT_MATH", math):
+        msg = check_parity(qa_lib, c, "randn", rows=rows)[3]
     assert msg is None, msg
 
 
@@ -379,37 +403,31 @@ INVARIANCE = {
 SPLITS = [(0, 1), (1, 31), (31, 64), (64, 129), (129, 130), (130, 283), (250, 283), (0, 283)]
 
 
-@pytest.mark.parametrize("hd", HDS)
-@pytest.mark.parametrize("mode", MODES)
-def test_attention_bit_exact_invariance(qa_lib, gpu_device, mode, hd):
-    from unified_audio_amd import _lib
-
+@pytest.mark.parametrize("mode,hd,math", per_form([(mode, hd) for mode in MODES for hd in HDS]))
+def test_attention_bit_exact_invariance(qa_lib, gpu_device, mode, hd, math):
     c = dataclasses.replace(INVARIANCE[mode], hd=hd)
     p = pack(c, make_inputs(c, "randn", _seed(c, "inv")), gpu_device)
-    ref = launch(qa_lib, c, p)
-    for _ in range(2):  # three identical runs
-        assert torch.equal(launch(qa_lib, c, p), ref), "run-to-run"
-    old = _lib.set_knob("QA_ATT_DEBUG", 0)
-    try:
+    with with_knob("QA_ATT_MATH", math):
+        ref = launch(qa_lib, c, p)
+        for _ in range(2):  # three identical runs
+            assert torch.equal(launch(qa_lib, c, p), ref), "run-to-run"
         for dbg in (1, 2, 4, 8, 16, 31):
-            _lib.set_knob("QA_ATT_DEBUG", dbg)
-            assert torch.equal(launch(qa_lib, c, p), ref), f"QA_ATT_DEBUG={dbg}"
-    finally:
-        _lib.set_knob("QA_ATT_DEBUG", old)
-    for b in range(c.B):  # a batch item alone
-        assert torch.equal(launch(qa_lib, c, p, B=1, boff=b)[0], ref[b]), f"batch item {b} alone"
-    if mode in ("cache", "window", "cross"):
-        subsets = [torch.arange(a, b) for a, b in SPLITS]
-        if mode == "cross":  # any subset of the queries, in any order
-            subsets.append(torch.randperm(c.n_q, generator=torch.Generator().manual_seed(hd))[:150])
-        off = c.n_keys - c.n_q
-        for idx in subsets:
-            qbuf, qrows = _poisoned(c.B * len(idx), p.ldq, gpu_device)
-            qrows.view(c.B, len(idx), p.ldq).copy_(p.qrows[:, idx.to(gpu_device)])
-            # causal: queries [a, b) over keys [0, b + off) - a chunk of a chunked prefill; cross: every key
-            nk = c.n_keys if mode == "cross" else int(idx[-1]) + 1 + off
-            got = launch(qa_lib, c, p, q=qrows.data_ptr(), n_q=len(idx), n_keys=nk)
-            assert torch.equal(got, ref[:, idx.to(gpu_device)]), f"queries {int(idx[0])} .. {int(idx[-1])} ({len(idx)})"
+            with with_knob("QA_ATT_DEBUG", dbg):
+                assert torch.equal(launch(qa_lib, c, p), ref), f"QA_ATT_DEBUG={dbg}"
+        for b in range(c.B):  # a batch item alone
+            assert torch.equal(launch(qa_lib, c, p, B=1, boff=b)[0], ref[b]), f"batch item {b} alone"
+        if mode in ("cache", "window", "cross"):
+            subsets = [torch.arange(a, b) for a, b in SPLITS]
+            if mode == "cross":  # any subset of the queries, in any order
+                subsets.append(torch.randperm(c.n_q, generator=torch.Generator().manual_seed(hd))[:150])
+            off = c.n_keys - c.n_q
+            for idx in subsets:
+                qbuf, qrows = _poisoned(c.B * len(idx), p.ldq, gpu_device)
+                qrows.view(c.B, len(idx), p.ldq).copy_(p.qrows[:, idx.to(gpu_device)])
+                # causal: queries [a, b) over keys [0, b + off) - a chunk of a chunked prefill; cross: every key
+                nk = c.n_keys if mode == "cross" else int(idx[-1]) + 1 + off
+                got = launch(qa_lib, c, p, q=qrows.data_ptr(), n_q=len(idx), n_keys=nk)
+                assert torch.equal(got, ref[:, idx.to(gpu_device)]), f"queries {int(idx[0])} .. {int(idx[-1])} ({len(idx)})"
 
 
 # ------------------------------------------------------------------------------------------------ (e) contract errors
@@ -475,11 +493,11 @@ def test_attention_contract_errors(qa_lib, gpu_device, name):
 
 # ------------------------------------------------------------------------------------------------ report
 def test_parity_report():
-    """Per mode: the range of e_hip and e_cpu32 and the largest fraction of the bound used by the cases of this session."""
+    """Per form and mode: the range of e_hip and e_cpu32 and the largest fraction of the bound used by the cases of this session."""
     by = {}
-    for mode, hd, regime, tag, e_hip, e_cpu, bound in REPORT:
-        by.setdefault(mode, []).append((e_hip, e_cpu, bound))
-    for mode, v in sorted(by.items()):
+    for math, mode, hd, regime, tag, e_hip, e_cpu, bound in REPORT:
+        by.setdefault((math, mode), []).append((e_hip, e_cpu, bound))
+    for (math, mode), v in sorted(by.items()):
         eh, ec, bd = zip(*v)
-        print(f"ATTN-SUMMARY {mode}: {len(v)} cases, e_hip {min(eh):.2e} .. {max(eh):.2e}, e_cpu32 {min(ec):.2e} .. {max(ec):.2e}, "
+        print(f"ATTN-SUMMARY math{math} {mode}: {len(v)} cases, e_hip {min(eh):.2e} .. {max(eh):.2e}, e_cpu32 {min(ec):.2e} .. {max(ec):.2e}, "
               f"bound {min(bd):.2e} .. {max(bd):.2e}, largest fraction {max(a / b for a, _, b in v):.3f}")

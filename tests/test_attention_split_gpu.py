@@ -1,5 +1,6 @@
-"""The two arithmetic forms of the attention kernel (csrc/attention.hip, knob QA_ATT_MATH): 1 = split-6 (three bf16 planes per operand,
-six v_mfma_f32_32x32x16_bf16 per 16-wide k group), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32).
+"""The two arithmetic forms of attention_kernel (csrc/attention.hip: one kernel body, the SPLIT template parameter selects the AttForm;
+knob QA_ATT_MATH): 1 = split-6 (three bf16 planes per operand, six v_mfma_f32_32x32x16_bf16 per 16-wide k group), 0 = the fp32 chain
+(v_mfma_f32_32x32x2_f32).  The parity matrix, the memory contract and the invariances of both forms are in tests/test_attention_gpu.py.
 
 (a) both forms on the callers' geometries against the float64 truth of tests/test_attention_gpu.py, under that file's bound
     C_PARITY * max(e_cpu32, E_FLOOR, S_ULP * s_max) - the bound comes from the host's own fp32 evaluation and the number format, and both
@@ -28,7 +29,7 @@ import torch
 
 from tests.test_attention_gpu import (AT_SIZE, C_PARITY, E_FLOOR, OUT_HEAD, S_ULP, Case, _seed, check_parity, launch, make_inputs, pack,
                                       reference_mask)
-from tests.util import check_guarded_out, guarded_out
+from tests.util import check_guarded_out, guarded_out, with_knob
 
 pytestmark = pytest.mark.gpu
 
@@ -41,19 +42,6 @@ GEOMETRIES.update({
     "window_hd96": Case("window", B=3, H=5, hd=96, n_q=283, n_keys=283, context=34),
 })
 RATIOS = []  # (mode, name, e_chain, e_split)
-
-
-def _with_knob(name, value):
-    from unified_audio_amd import _lib
-
-    class Guard:
-        def __enter__(self):
-            self.old = _lib.set_knob(name, value)
-
-        def __exit__(self, *a):
-            _lib.set_knob(name, self.old)
-
-    return Guard()
 
 
 def _stats(lib):
@@ -71,7 +59,7 @@ def test_both_forms_meet_the_fp64_bound(qa_lib, gpu_device, name):
     x = make_inputs(c, "randn", _seed(c, "randn"))
     e, bad = {}, []
     for math in (0, 1):
-        with _with_knob("QA_ATT_MATH", math):
+        with with_knob("QA_ATT_MATH", math):
             before = _stats(qa_lib)
             e_hip, e_cpu, bound, msg = check_parity(qa_lib, c, "randn", rows=rows, x=x)
             after = _stats(qa_lib)
@@ -107,7 +95,7 @@ def test_lm_takes_the_fp32_chain_and_the_codec_follows_the_knob(qa_lib, gpu_devi
     mel = torch.zeros(3, 12, 80)
 
     for math in (1, 0):
-        with _with_knob("QA_ATT_MATH", math):
+        with with_knob("QA_ATT_MATH", math):
             s0 = _stats(qa_lib)
             lm.generate("se", None, None, mel, mix, global_length=5, do_sample=False)
             torch.cuda.synchronize()
@@ -134,7 +122,7 @@ def test_every_plane_of_every_operand_is_read(qa_lib, gpu_device, hd):
     # (averaging over keys and d shrinks the change); the lower ends sit above the 2^-24 of an fp32 rounding only for h and m, so the
     # l plane is required to change the bits at all and to stay below 2^-13.
     windows = {32: (0.05, 4.0), 64: (2.0 ** -16, 2.0 ** -5), 128: (0.0, 2.0 ** -13)}
-    with _with_knob("QA_ATT_MATH", 1), _with_knob("QA_ATT_DEBUG", 0):
+    with with_knob("QA_ATT_MATH", 1), with_knob("QA_ATT_DEBUG", 0):
         ref = launch(qa_lib, c, p)
         scale = float(ref.abs().max())
         for op, sel in list(OPERANDS.items()) + [("all", 0)]:
@@ -147,7 +135,7 @@ def test_every_plane_of_every_operand_is_read(qa_lib, gpu_device, hd):
                 assert lo <= d < hi, f"{op} plane bit {bit}: change {d:.3e} outside [{lo:.1e}, {hi:.1e})"
         _lib.set_knob("QA_ATT_DEBUG", 0)
         assert torch.equal(launch(qa_lib, c, p), ref)
-    with _with_knob("QA_ATT_MATH", 0), _with_knob("QA_ATT_DEBUG", 0):
+    with with_knob("QA_ATT_MATH", 0), with_knob("QA_ATT_DEBUG", 0):
         ref0 = launch(qa_lib, c, p)
         _lib.set_knob("QA_ATT_DEBUG", 32 | 64 | 128)
         assert torch.equal(launch(qa_lib, c, p), ref0), "the fp32 chain has no planes"
@@ -223,7 +211,7 @@ def test_key_padding_mask_both_forms_meet_the_fp64_bound(qa_lib, gpu_device, hd,
     bound = C_PARITY * max(e_cpu, E_FLOOR, S_ULP * s_max)
     e, bad = {}, []
     for math in (0, 1):
-        with _with_knob("QA_ATT_MATH", math):
+        with with_knob("QA_ATT_MATH", math):
             before = _stats(qa_lib)
             out = _kmask_launch(qa_lib, c, qkv, vbytes).cpu()
             after = _stats(qa_lib)
@@ -245,7 +233,7 @@ def test_all_masked_rows_are_exactly_zero(qa_lib, gpu_device, hd, math):
     blind = ~reference_mask(c, torch.arange(c.n_q)).any(-1)
     assert blind.any() and not blind.all()
     p = pack(c, make_inputs(c, "randn", _seed(c, "blind")), gpu_device)
-    with _with_knob("QA_ATT_MATH", math):
+    with with_knob("QA_ATT_MATH", math):
         out = launch(qa_lib, c, p).cpu()
     assert torch.equal(out[:, blind], torch.zeros_like(out[:, blind]))
     assert bool(torch.isfinite(out).all()) and float(out[:, ~blind].abs().max()) > 0

@@ -1,6 +1,7 @@
 """Shared helpers of the test-suite (oracle side on CPU, product side through the C-ABI)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -110,6 +111,18 @@ def check_guarded_out(buf, y, head):
     assert bad == 0, f"{bad} elements outside the [{M}, {N}] output (ldy {ldy}, offset {head}) were overwritten"
     unwritten = int(torch.isnan(y).sum())
     assert unwritten == 0, f"{unwritten} of the {M * N} output elements were never written"
+
+
+@contextlib.contextmanager
+def with_knob(name, value):
+    """Set a library knob (unified_audio_amd._lib.set_knob) for the duration of a with block."""
+    from unified_audio_amd import _lib
+
+    old = _lib.set_knob(name, value)
+    try:
+        yield
+    finally:
+        _lib.set_knob(name, old)
 
 
 def conv_ref(x, w, bias, case, dtype=torch.float64, *, gamma=None, residual=None, gate=None, rows=None):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""attention_kernel alone (qa_debug_attention) on the shapes the codecs launch: microseconds per launch."""
+"""attention_kernel alone, in the form QA_ATT_MATH selects (qa_debug_attention), on the shapes the codecs launch: microseconds per launch."""
 import ctypes as C
 import os
 import sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-phase shader cycles of attention_kernel's key-tile loop (needs the -DQA_ATT_TIMING=1 build):
+"""Per-phase shader cycles of attention_kernel's key-tile loop, in the form QA_ATT_MATH selects (needs the -DQA_ATT_TIMING=1 build):
     QA_VARIANT_SOURCES=attention.hip python tools/variants.py att_timing "-DQA_ATT_TIMING=1"
     QA_LIBRARY=tools/_variants/att_timing/libquarkaudio_hip.so python tools/att_timing.py
 Phases per 32-key tile and wave: [0] top barrier + LDS stores of the prefetched tile + second barrier (includes the wait for the tile's global

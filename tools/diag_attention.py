@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Diagnostic: run-to-run determinism of attention_kernel alone over a sweep of shapes and debug bits."""
+"""Diagnostic: run-to-run determinism of attention_kernel alone (the form QA_ATT_MATH selects) over a sweep of shapes and debug bits."""
 import ctypes as C
 import os
 import sys

@@ -1,4 +1,5 @@
-// attention.hip - fp32 flash-style attention on the f32 matrix cores.
+// attention.hip - flash-style attention with fp32-class results: one kernel body, attention_kernel, in two
+// arithmetic forms (AttForm) - the fp32 chain on the f32 matrix cores and split-6 bf16 planes on the bf16 ones.
 //
 // Reference semantics: softmax(Q K^T * head_dim^-0.5, fp32) V, no mask for the codec transformers
 // (QuarkAudio-HCodec/HCodec-1.0/vq/encoder_modules/transformer.py:158-180) and a causal mask over a KV cache for the
@@ -13,8 +14,8 @@
 //                         0 <= pos_q - p < context.  Slots overwritten by later tokens of the same chunk are gone, as in the
 //                         reference (it writes the whole chunk before it attends).
 //
-// One wave64 owns 32 queries and walks the keys 32 at a time; both products run TRANSPOSED on
-// v_mfma_f32_32x32x2_f32 so that every softmax statistic is per lane (no cross-lane row reductions):
+// One wave64 owns 32 queries and walks the keys 32 at a time; both products run TRANSPOSED (written here for the fp32 form's
+// v_mfma_f32_32x32x2_f32; the split-6 form's operand maps are at AttForm<HD, true>) so that every softmax statistic is per lane (no cross-lane row reductions):
 //   S^T[key, q] = sum_d K[key, d] Q[q, d]     A = K tile (LDS, ds_read_b128), B = Q (registers)
 //   O^T[d,  q] += sum_key V[key, d] P[q, key] A = V tile (LDS),               B = P = exp(S - m) (registers)
 // The 32x32 accumulator layout gives lane (q = lane & 31, h = lane >> 5) the keys (r&3) + 8*(r>>2) + 4*h for r = 0..15,
@@ -46,16 +47,210 @@ extern "C" int qa_debug_att_timing(unsigned long long* out, int reset) {
 
 namespace qa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
 
+// The two arithmetic forms.  An AttForm owns everything that depends on the number format: the LDS image of a key tile, the Q fragment,
+// the staging store of a fetched tile, and the two products.  attention_kernel below owns the rest and is the same text for both.
+// The kernel declares the K and the V image as two __shared__ arrays of K_BYTES / V_BYTES and hands them over: carved out of one array
+// the split HD 64 instances spill (profiles/r09_attention_resource_usage.md).
+template <int HD, bool SPLIT>
+struct AttForm;
+
+// fp32 chain (QA_ATT_MATH = 0, and every UniSE LM launch): v_mfma_f32_32x32x2_f32 on two [32 keys][HD + 4] float tiles.  A tile's
+// KMASK validity floats sit in the four padding floats behind each K row, so the other instantiations keep their code and their LDS size.
+template <int HD>
+struct AttForm<HD, false> {
+    static constexpr int MIN_WG = 2;
+    static constexpr int LD = HD + 4, DT = HD / 32, NG = HD / 8, NLD = HD / 32;
+    static constexpr int K_BYTES = 32 * LD * 4, V_BYTES = 32 * LD * 4;
+    float *sK, *sV;
+    int ql, hh;
+    float qreg[HD / 2];
+
+    __device__ __forceinline__ AttForm(char* k_tile, char* v_tile, int lane, int) : sK((float*)k_tile), sV((float*)v_tile), ql(lane & 31), hh(lane >> 5) {}
+    // Q fragment: lane (q, h) keeps d = 8g + 4h + e  ->  qreg[4g + e], scaled by qs
+    __device__ __forceinline__ void load_q(const float* qrow, float qs) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const float4 t = *reinterpret_cast<const float4*>(qrow + 4 * hh + 8 * g);
+            qreg[4 * g + 0] = t.x * qs; qreg[4 * g + 1] = t.y * qs; qreg[4 * g + 2] = t.z * qs; qreg[4 * g + 3] = t.w * qs;
+        }
+    }
+    __device__ __forceinline__ void stage(const f32x4 (&kreg)[NLD], const f32x4 (&vreg)[NLD], int tid) {
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + 256 * j;
+            const int row = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
+            *reinterpret_cast<f32x4*>(sK + row * LD + c4) = kreg[j];
+            *reinterpret_cast<f32x4*>(sV + row * LD + c4) = vreg[j];
+        }
+    }
+    __device__ __forceinline__ float& key_valid(int row) { return sK[row * LD + HD]; }
+    // S^T = K Q^T
+    __device__ __forceinline__ void scores(f32x16& s) const {
+        const float* kp = sK + ql * LD + 4 * hh;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const float4 a = *reinterpret_cast<const float4*>(kp + 8 * g);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qreg[4 * g + 0], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qreg[4 * g + 1], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qreg[4 * g + 2], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qreg[4 * g + 3], s, 0, 0, 0);
+        }
+    }
+    // O^T += V^T P^T ; k-slot (step st, half h) <-> key (st&3) + 8*(st>>2) + 4*h
+    __device__ __forceinline__ void accumulate(f32x16 (&o)[DT], const f32x16& p) const {
+#pragma unroll
+        for (int st = 0; st < 16; ++st) {
+            const int key = (st & 3) + 8 * (st >> 2) + 4 * hh;
+            const float* vp = sV + key * LD + ql;
+#pragma unroll
+            for (int t = 0; t < DT; ++t) o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * t], p[st], o[t], 0, 0, 0);
+        }
+    }
+};
+
+// Split-6 form (QA_ATT_MATH = 1): the same decomposition with every matrix operand as three exact bf16 planes x = h + m + l
+// (split_planes.h) and six v_mfma_f32_32x32x16_bf16 per 16-wide k group, smallest terms first (PAIR_A / PAIR_B, the LDS operand's plane
+// first), into one fp32 accumulator: 48 MFMAs of 32 cycles per tile at head dim 64 where the fp32 chain issues 64 of 64 cycles.
+//   Q   split once per wave after scale * log2(e) is folded in; lane (q, h) holds d = 16g + 8h + j of k group g (the B operand map).
+//   K/V the staging threads split each f32x4 right before the LDS store: per operand three planes of [32 keys][HD] bf16.
+//       K rows are HD * 2 + 16 bytes apart (an odd number of 16-byte slots: the ds_read_b128 of a 16-lane group covers all 64 banks);
+//       the KMASK validity float sits in the pad of the h plane's row.
+//       V rows are 64 bytes (mod 256) apart, so the four rows x 64 bytes a 32-lane half takes with one ds_read_b64_tr_b16 tile the 64
+//       banks; V stays row-major [key][d], the transposed read delivers the column-wise A operand (8-byte aligned addresses, EXEC full:
+//       the tile skip is a scalar branch).
+//   P   accumulator registers 8s .. 8s+7 of S^T are, for lane (q, h), the keys 16s + 8(j >> 2) + 4h + (j & 3), j = 0..7: used as the
+//       B fragment of k step s they never leave the registers; the V reads take the same key order (two 4-key blocks per fragment).
+//       p lies in [0, 1] (or is NaN): the residuals are finite without split4_rne's tests.
+// The summation order is fixed by (tile, k group, plane pair) alone.  dbg bits 32 / 64 / 128 (tests) zero the h / m / l plane of the
+// operands selected by bits 256 (Q), 512 (K), 1024 (V), 2048 (P); with none of those four set, of every operand.
+template <int HD>
+struct AttForm<HD, true> {
+    // three workgroups per CU up to HD 64, as the fp32 form gets there (168 VGPRs, no scratch; 768 workgroups of the 32 x 283 x 8 launch
+    // are one round of 256 CUs), two above
+    static constexpr int MIN_WG = HD <= 64 ? 3 : 2;
+    static constexpr int DT = HD / 32, NLD = HD / 32;
+    static constexpr int NKG = HD / 16;                                    // 16-wide k groups of S^T = K Q^T
+    static constexpr int KS = HD * 2 + 16;                                 // bytes per K row of one plane
+    static constexpr int VS = (HD % 64 == 0) ? HD * 2 + 64 : HD * 2;       // bytes per V row of one plane: 64 (mod 256)
+    static constexpr int KPLANE = 32 * KS, VPLANE = 32 * VS;
+    static constexpr int K_BYTES = 3 * KPLANE, V_BYTES = 3 * VPLANE;
+    static_assert(VS % 256 == 64 || VS % 256 == 192, "V rows must be 16 banks apart (mod 64)");
+    char *sK, *sV;
+    // read addresses.  K fragment of k group g, plane pl: 16 bytes at kread + pl * KPLANE + 32 g.  V fragment of k step s, d tile t:
+    // lane 4r + p of a 16-lane group supplies row r, columns 4p .. 4p + 3 of the group's 4-key x 16-d block; blocks at keys
+    // 16 s + 8 jh + 4 hh (jh = 0, 1: elements 0..3 and 4..7), d = 32 t + 16 * (group & 1)
+    const char *kread, *vread;
+    int hh;
+    int zq, zk, zv, zp;  // planes to zero (tests), per operand
+    bf16x8 qf[3][NKG];
+
+    __device__ __forceinline__ AttForm(char* k_tile, char* v_tile, int lane, int dbg) : sK(k_tile), sV(v_tile), hh(lane >> 5) {
+        kread = sK + (lane & 31) * KS + 16 * hh;
+        vread = sV + (4 * hh + ((lane & 15) >> 2)) * VS + 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+        const int zpl = (dbg >> 5) & 7, zsel = (dbg >> 8) & 15;  // planes to zero, and of which operands (0: all)
+        zq = (zsel == 0 || (zsel & 1)) ? zpl : 0, zk = (zsel == 0 || (zsel & 2)) ? zpl : 0;
+        zv = (zsel == 0 || (zsel & 4)) ? zpl : 0, zp = (zsel == 0 || (zsel & 8)) ? zpl : 0;
+    }
+    __device__ __forceinline__ void load_q(const float* qrow, float qs) {
+        const float* qp = qrow + 8 * hh;
+#pragma unroll
+        for (int g = 0; g < NKG; ++g) {
+            u32x2 p0[3], p1[3];
+            split4_rne(*reinterpret_cast<const f32x4*>(qp + 16 * g) * qs, p0[0], p0[1], p0[2]);
+            split4_rne(*reinterpret_cast<const f32x4*>(qp + 16 * g + 4) * qs, p1[0], p1[1], p1[2]);
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                if (zq & (1 << pl)) p0[pl] = p1[pl] = u32x2{0u, 0u};
+                qf[pl][g] = frag8(p0[pl], p1[pl]);
+            }
+        }
+    }
+    __device__ __forceinline__ void stage(const f32x4 (&kreg)[NLD], const f32x4 (&vreg)[NLD], int tid) {
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + 256 * j;
+            const int row = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
+            u32x2 pk[3], pv[3];
+            split4_rne(kreg[j], pk[0], pk[1], pk[2]);
+            split4_rne(vreg[j], pv[0], pv[1], pv[2]);
+            if (zk | zv) {
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+                    if (zk & (1 << pl)) pk[pl] = u32x2{0u, 0u};
+                    if (zv & (1 << pl)) pv[pl] = u32x2{0u, 0u};
+                }
+            }
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                *reinterpret_cast<u32x2*>(sK + pl * KPLANE + row * KS + c4 * 2) = pk[pl];
+                *reinterpret_cast<u32x2*>(sV + pl * VPLANE + row * VS + c4 * 2) = pv[pl];
+            }
+            if (HD >= 96) __builtin_amdgcn_sched_barrier(0);  // one split's temporaries at a time (HD 96: 253 -> 233 VGPRs; HD 128 still spills, DESIGN 21)
+        }
+    }
+    __device__ __forceinline__ float& key_valid(int row) { return *reinterpret_cast<float*>(sK + row * KS + HD * 2); }
+    // S^T = K Q^T
+    __device__ __forceinline__ void scores(f32x16& s) const {
+#pragma unroll
+        for (int g = 0; g < NKG; ++g) {
+            bf16x8 kf[3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) kf[pl] = *reinterpret_cast<const bf16x8*>(kread + pl * KPLANE + 32 * g);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[PAIR_A[i]], qf[PAIR_B[i]][g], s, 0, 0, 0);
+            if (HD >= 96) __builtin_amdgcn_sched_barrier(0);  // one group's fragments live at a time (register pressure, as above)
+        }
+    }
+    // O^T += V^T P^T, the P planes of each 16-key step split in registers right before its MFMAs
+    __device__ __forceinline__ void accumulate(f32x16 (&o)[DT], const f32x16& p) const {
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            bf16x8 pf[3];
+            {
+                u32x2 p0[3], p1[3];
+                const f32x4 x0 = {p[8 * st + 0], p[8 * st + 1], p[8 * st + 2], p[8 * st + 3]};
+                const f32x4 x1 = {p[8 * st + 4], p[8 * st + 5], p[8 * st + 6], p[8 * st + 7]};
+                split4_unit(x0, p0[0], p0[1], p0[2]);
+                split4_unit(x1, p1[0], p1[1], p1[2]);
+                if (zp) {
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl)
+                        if (zp & (1 << pl)) p0[pl] = p1[pl] = u32x2{0u, 0u};
+                }
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) pf[pl] = frag8(p0[pl], p1[pl]);
+            }
+#pragma unroll
+            for (int t = 0; t < DT; ++t) {
+                bf16x8 vf[3];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+                    const char* a = vread + pl * VPLANE + 16 * st * VS + 64 * t;
+                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
+                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 8 * VS));
+                    const s16x8 w = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    vf[pl] = __builtin_bit_cast(bf16x8, w);
+                }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[PAIR_A[i]], pf[PAIR_B[i]], o[t], 0, 0, 0);
+                if (HD >= 96) __builtin_amdgcn_sched_barrier(0);  // as above
+            }
+        }
+    }
+};
+
+// One wave per 32 queries, 32-key tiles, both products transposed, base-2 online softmax (file header); SPLIT selects the AttForm.
 // BIAS: WavLM's gated relative position bias (transformers WavLMAttention.forward): score(i, j) += gate[b, head, i] *
 // relbias[head][clamp(j - i, -R, R) + R]; the bucket function saturates below R, so the clamp is exact.
 // KMASK: key-padding mask (Conformer condition encoder, conformer.py:165-174): kvalid [B, n_keys] bytes, 0 = the key is invisible to
 // every query of its batch item.  A tile's validity bytes travel with its K rows (register-staged, unconditional loads) and sit in
-// the four padding floats behind each K row in LDS, so the other instantiations keep their code and their LDS size.
-template <int HD, bool BIAS, bool KMASK = false>
-__global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ q, long long ldq,
+// the padding behind each K row in LDS (AttForm::key_valid).
+// gate / relbias / R are read only with BIAS, kvalid only with KMASK.
+template <int HD, bool BIAS, bool KMASK, bool SPLIT>
+__global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_kernel(const float* __restrict__ q, long long ldq,
                                                         const float* __restrict__ k, const float* __restrict__ v,
                                                         long long ldkv, long long kv_bstride, float* __restrict__ out,
                                                         long long ldo, int n_q, int n_keys, float scale, int causal,
@@ -68,11 +263,10 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
 #else
     const int dbg = dbg_arg;
 #endif
-    constexpr int LD = HD + 4;
+    using Form = AttForm<HD, SPLIT>;
     constexpr int DT = HD / 32;
-    constexpr int NG = HD / 8;
-    __shared__ __attribute__((aligned(16))) float sK[32 * LD];
-    __shared__ __attribute__((aligned(16))) float sV[32 * LD];
+    __shared__ __attribute__((aligned(16))) char sK[Form::K_BYTES];
+    __shared__ __attribute__((aligned(16))) char sV[Form::V_BYTES];
 
     // `wave` through readfirstlane: every wave-level test below (tile skips, mask tests) is then a SCALAR branch.  As a VGPR value
     // hipcc lowers them to exec-masked regions, and exec-masked VMEM next to register-staged prefetches is where ROCm 7.2 mis-tracks
@@ -84,21 +278,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     const int qi = q_blk0 + wave * 32 + ql;
     const int off = n_keys - n_q;  // causal: key j visible iff j <= qi + off
 
-    // Q fragment: lane (q, h) keeps d = 8g + 4h + e  ->  qreg[4g + e].  The softmax runs in base 2: scale * log2(e) is folded into
-    // Q once, so that a score needs no multiply and an exponential is the single v_exp_f32 instruction (ocml's expf is ~10
-    // instructions, and a vector instruction issued beside the other waves' MFMAs costs ~30 cycles, conv_gemm.hip)
+    // The softmax runs in base 2: scale * log2(e) is folded into Q once, so that a score needs no multiply and an exponential is the
+    // single v_exp_f32 instruction (ocml's expf is ~10 instructions, and a vector instruction issued beside the other waves' MFMAs
+    // costs ~30 cycles, conv_gemm.hip)
     constexpr float LOG2E = 1.4426950408889634f;
-    const float qs = scale * LOG2E;
-    float qreg[HD / 2];
-    {
-        const int qrow = qi < n_q ? qi : n_q - 1;
-        const float* qp = q + ((long long)b * n_q + qrow) * ldq + head * HD + 4 * hh;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float4 t = *reinterpret_cast<const float4*>(qp + 8 * g);
-            qreg[4 * g + 0] = t.x * qs; qreg[4 * g + 1] = t.y * qs; qreg[4 * g + 2] = t.z * qs; qreg[4 * g + 3] = t.w * qs;
-        }
-    }
+    Form form(sK, sV, lane, dbg);
+    form.load_q(q + ((long long)b * n_q + (qi < n_q ? qi : n_q - 1)) * ldq + head * HD, scale * LOG2E);
 
     float gate_q = 0.f;
     const float* rb = nullptr;
@@ -130,8 +315,8 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     const int wave_first_key = (lin_causal && context > 0) ? max(0, q_blk0 + wave * 32 + off - context + 1) : 0;
     const int ring_idx = ring ? ring_end % n_keys : 0;  // RingKVCache.complete(): end_index
 
-    // K / V tiles go global -> registers -> LDS; the loads of tile kt + 1 are issued right after tile kt is in LDS and stay in
-    // flight under its 64 MFMAs (the first version loaded synchronously: one exposed L2 / HBM round trip per 32 keys)
+    // K / V tiles go global -> registers -> (split ->) LDS; the loads of tile kt + 1 are issued right after tile kt is in LDS and stay
+    // in flight under its MFMAs (the first version loaded synchronously: one exposed L2 / HBM round trip per 32 keys)
     // Rows past n_keys re-read the last valid row instead of being predicated off: their scores are masked to -inf below (need_mask
     // is set on any tile that reaches n_keys) and their probability is exactly 0, so a finite stand-in row changes nothing - and
     // every load of the kernel is UNCONDITIONAL.  The round-2 form (`if (key < n_keys) load; else zeros`) put the prefetch into an
@@ -166,14 +351,8 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     for (int kt = kt0; kt < n_tiles; ++kt) {
         QA_ATT_TICK(3)  // (the tail of the previous tile's PV phase; the first time: the Q prologue, negligible)
         __syncthreads();  // the previous tile is no longer read
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + 256 * j;
-            const int row = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
-            *reinterpret_cast<f32x4*>(sK + row * LD + c4) = kreg[j];
-            *reinterpret_cast<f32x4*>(sV + row * LD + c4) = vreg[j];
-        }
-        if (KMASK && tid < 32) sK[tid * LD + HD] = mreg;
+        form.stage(kreg, vreg, tid);
+        if (KMASK && tid < 32) form.key_valid(tid) = mreg;
         __syncthreads();
         if (kt + 1 < n_tiles) fetch(kt + 1);
         if (dbg & 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -185,19 +364,10 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
         // sequence that is not a multiple of 128: at N = 283 three of the four waves of block 3 would multiply clamped rows)
         if (!(dbg & 8) && (kt * 32 > wave_last_key || kt * 32 + 31 < wave_first_key || q_blk0 + wave * 32 >= n_q)) continue;
 
-        // S^T = K Q^T
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        const float* kp = sK + ql * LD + 4 * hh;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float4 a = *reinterpret_cast<const float4*>(kp + 8 * g);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qreg[4 * g + 0], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qreg[4 * g + 1], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qreg[4 * g + 2], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qreg[4 * g + 3], s, 0, 0, 0);
-        }
+        form.scores(s);
         QA_ATT_TICK(1)
         // online softmax in base 2 (per lane = per query; the two halves of the wave hold interleaved key groups).  Masks are
         // evaluated only on tiles that can contain a hidden key for some query of this wave (wave-uniform test).
@@ -210,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
                 bool ok = key < n_keys;
-                if (KMASK) ok = ok && sK[((r & 3) + 8 * (r >> 2) + 4 * hh) * LD + HD] != 0.f;
+                if (KMASK) ok = ok && form.key_valid((r & 3) + 8 * (r >> 2) + 4 * hh) != 0.f;
                 if (ring) {
                     const int delta = key - ring_idx;
                     const int pos = key >= ring_end ? -1 : (delta <= 0 ? ring_end + delta : ring_end + delta - n_keys);
@@ -246,14 +416,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
                 for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
         }
         QA_ATT_TICK(2)
-        // O^T += V^T P^T ; k-slot (step st, half h) <-> key (st&3) + 8*(st>>2) + 4*h
-#pragma unroll
-        for (int st = 0; st < 16; ++st) {
-            const int key = (st & 3) + 8 * (st >> 2) + 4 * hh;
-            const float* vp = sV + key * LD + ql;
-#pragma unroll
-            for (int t = 0; t < DT; ++t) o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * t], s[st], o[t], 0, 0, 0);
-        }
+        form.accumulate(o, s);
 #ifdef QA_ATT_TIMING
         ++n_done;
 #endif
@@ -286,319 +449,16 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Split-6 form (QA_ATT_MATH = 1): the same decomposition - one wave per 32 queries, 32-key tiles, both products transposed, base-2
-// online softmax, the same masks, skips and clamped unconditional loads - with every matrix operand as three exact bf16 planes
-// x = h + m + l (split_planes.h) and six v_mfma_f32_32x32x16_bf16 per 16-wide k group, smallest terms first (hl, lh, mm, hm, mh, hh,
-// the LDS operand's plane first), into one fp32 accumulator: 48 MFMAs of 32 cycles per tile at head dim 64 where the fp32 chain
-// issues 64 of 64 cycles.
-//   Q   split once per wave after scale * log2(e) is folded in; lane (q, h) holds d = 16g + 8h + j of k group g (the B operand map).
-//   K/V the staging threads split each f32x4 right before the LDS store: per operand three planes of [32 keys][HD] bf16.
-//       K rows are HD * 2 + 16 bytes apart (an odd number of 16-byte slots: the ds_read_b128 of a 16-lane group covers all 64 banks);
-//       the KMASK validity float sits in the pad of the h plane's row.
-//       V rows are 64 bytes (mod 256) apart, so the four rows x 64 bytes a 32-lane half takes with one ds_read_b64_tr_b16 tile the 64
-//       banks; V stays row-major [key][d], the transposed read delivers the column-wise A operand (8-byte aligned addresses, EXEC full:
-//       the tile skip is a scalar branch).
-//   P   accumulator registers 8s .. 8s+7 of S^T are, for lane (q, h), the keys 16s + 8(j >> 2) + 4h + (j & 3), j = 0..7: used as the
-//       B fragment of k step s they never leave the registers; the V reads take the same key order (two 4-key blocks per fragment).
-//       p lies in [0, 1] (or is NaN): the residuals are finite without split4_rne's tests.
-// The summation order is fixed by (tile, k group, plane pair) alone.  dbg bits 32 / 64 / 128 (tests) zero the h / m / l plane of the
-// operands selected by bits 256 (Q), 512 (K), 1024 (V), 2048 (P); with none of those four set, of every operand.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split4_unit(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {  // split4_rne for x in [0, 1]
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float a = x[2 * i], b = x[2 * i + 1];
-        const unsigned h = rne_bf16x2(a, b);
-        const float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
-        const unsigned m = rne_bf16x2(ra, rb);
-        ph[i] = h;
-        pm[i] = m;
-        pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
-    }
-}
-__device__ __forceinline__ bf16x8 frag8(const u32x2 lo, const u32x2 hi) {
-    const u32x4 t = {lo[0], lo[1], hi[0], hi[1]};
-    return __builtin_bit_cast(bf16x8, t);
-}
-
-template <int HD, bool BIAS, bool KMASK = false>
-// three workgroups per CU up to HD 64, as attention_kernel gets there (168 VGPRs, no scratch; 768 workgroups of the 32 x 283 x 8 launch are
-// one round of 256 CUs), two above
-__global__ __launch_bounds__(256, (HD <= 64 ? 3 : 2)) void attention_split_kernel(const float* __restrict__ q, long long ldq,
-                                                              const float* __restrict__ k, const float* __restrict__ v,
-                                                              long long ldkv, long long kv_bstride, float* __restrict__ out,
-                                                              long long ldo, int n_q, int n_keys, float scale, int causal,
-                                                              const float* __restrict__ gate, const float* __restrict__ relbias, int R,
-                                                              int context, int q_pos0, int ring_end, int dbg_arg,
-                                                              const unsigned char* __restrict__ kvalid) {
-#if defined(QA_ATT_DBG) && QA_ATT_DBG == 0
-    constexpr int dbg = 0;
-    (void)dbg_arg;
-#else
-    const int dbg = dbg_arg;
-#endif
-    constexpr int DT = HD / 32;
-    constexpr int NKG = HD / 16;                                    // 16-wide k groups of S^T = K Q^T
-    constexpr int KS = HD * 2 + 16;                                 // bytes per K row of one plane
-    constexpr int VS = (HD % 64 == 0) ? HD * 2 + 64 : HD * 2;       // bytes per V row of one plane: 64 (mod 256)
-    constexpr int KPLANE = 32 * KS, VPLANE = 32 * VS;
-    static_assert(VS % 256 == 64 || VS % 256 == 192, "V rows must be 16 banks apart (mod 64)");
-    __shared__ __attribute__((aligned(16))) char sK[3 * KPLANE];
-    __shared__ __attribute__((aligned(16))) char sV[3 * VPLANE];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar wave tests: attention_kernel
-    const int ql = lane & 31, hh = lane >> 5;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int q_blk0 = blockIdx.x * 128;
-    const int qi = q_blk0 + wave * 32 + ql;
-    const int off = n_keys - n_q;  // causal: key j visible iff j <= qi + off
-    const int zpl = (dbg >> 5) & 7, zsel = (dbg >> 8) & 15;  // planes to zero (tests), and of which operands (0: all)
-    const int zq = (zsel == 0 || (zsel & 1)) ? zpl : 0, zk = (zsel == 0 || (zsel & 2)) ? zpl : 0;
-    const int zv = (zsel == 0 || (zsel & 4)) ? zpl : 0, zp = (zsel == 0 || (zsel & 8)) ? zpl : 0;
-
-    constexpr float LOG2E = 1.4426950408889634f;
-    const float qs = scale * LOG2E;
-    bf16x8 qf[3][NKG];
-    {
-        const int qrow = qi < n_q ? qi : n_q - 1;
-        const float* qp = q + ((long long)b * n_q + qrow) * ldq + head * HD + 8 * hh;
-#pragma unroll
-        for (int g = 0; g < NKG; ++g) {
-            u32x2 p0[3], p1[3];
-            split4_rne(*reinterpret_cast<const f32x4*>(qp + 16 * g) * qs, p0[0], p0[1], p0[2]);
-            split4_rne(*reinterpret_cast<const f32x4*>(qp + 16 * g + 4) * qs, p1[0], p1[1], p1[2]);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                if (zq & (1 << pl)) p0[pl] = p1[pl] = u32x2{0u, 0u};
-                qf[pl][g] = frag8(p0[pl], p1[pl]);
-            }
-        }
-    }
-
-    float gate_q = 0.f;
-    const float* rb = nullptr;
-    if (BIAS) {
-        gate_q = LOG2E * gate[((long long)b * gridDim.y + head) * n_q + (qi < n_q ? qi : n_q - 1)];
-        rb = relbias + (long long)head * (2 * R + 1) + R;
-    }
-
-    f32x16 o[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    const float* kb = k + (long long)b * kv_bstride + head * HD;
-    const float* vb = v + (long long)b * kv_bstride + head * HD;
-
-    const bool ring = ring_end > 0;
-    const bool lin_causal = causal && !ring;
-    int last_key = n_keys - 1, first_key = 0;
-    if (lin_causal) {
-        const int q_last = min(q_blk0 + 127, n_q - 1);
-        last_key = min(last_key, q_last + off);
-        if (context > 0) first_key = max(0, q_blk0 + off - context + 1);
-    }
-    const int n_tiles = last_key / 32 + 1, kt0 = first_key / 32;
-    const int wave_last_key = lin_causal ? min(n_keys - 1, min(q_blk0 + wave * 32 + 31, n_q - 1) + off) : n_keys - 1;
-    const int wave_first_key = (lin_causal && context > 0) ? max(0, q_blk0 + wave * 32 + off - context + 1) : 0;
-    const int ring_idx = ring ? ring_end % n_keys : 0;  // RingKVCache.complete(): end_index
-
-    // global -> registers (fp32, in flight under the previous tile's MFMAs) -> split -> LDS; clamped unconditional loads as in
-    // attention_kernel
-    constexpr int NLD = HD / 32;
-    f32x4 kreg[NLD], vreg[NLD];
-    float mreg = 1.f;
-    const unsigned char* kvb = KMASK ? kvalid + (long long)b * n_keys : nullptr;
-    auto fetch = [&](int kt) {
-        if (KMASK) mreg = kvb[min(kt * 32 + (tid & 31), n_keys - 1)] ? 1.f : 0.f;
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + 256 * j;
-            const int row = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
-            const int key = min(kt * 32 + row, n_keys - 1);
-            kreg[j] = *reinterpret_cast<const f32x4*>(kb + (long long)key * ldkv + c4);
-            vreg[j] = *reinterpret_cast<const f32x4*>(vb + (long long)key * ldkv + c4);
-        }
-    };
-    // read addresses.  K fragment of k group g, plane pl: 16 bytes at kread + pl * KPLANE + 32 g.  V fragment of k step s, d tile t:
-    // lane 4r + p of a 16-lane group supplies row r, columns 4p .. 4p + 3 of the group's 4-key x 16-d block; blocks at keys
-    // 16 s + 8 jh + 4 hh (jh = 0, 1: elements 0..3 and 4..7), d = 32 t + 16 * (group & 1)
-    const char* kread = sK + ql * KS + 16 * hh;
-    const char* vread = sV + (4 * hh + ((lane & 15) >> 2)) * VS + 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
-#ifdef QA_ATT_TIMING
-    long long tacc[4] = {0, 0, 0, 0};
-    long long tlast = __builtin_readcyclecounter();
-    const long long tbegin = tlast;
-    long long n_done = 0;
-#endif
-    fetch(kt0);
-    for (int kt = kt0; kt < n_tiles; ++kt) {
-        QA_ATT_TICK(3)
-        __syncthreads();  // the previous tile is no longer read
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + 256 * j;
-            const int row = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
-            u32x2 pk[3], pv[3];
-            split4_rne(kreg[j], pk[0], pk[1], pk[2]);
-            split4_rne(vreg[j], pv[0], pv[1], pv[2]);
-            if (zk | zv) {
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    if (zk & (1 << pl)) pk[pl] = u32x2{0u, 0u};
-                    if (zv & (1 << pl)) pv[pl] = u32x2{0u, 0u};
-                }
-            }
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                *reinterpret_cast<u32x2*>(sK + pl * KPLANE + row * KS + c4 * 2) = pk[pl];
-                *reinterpret_cast<u32x2*>(sV + pl * VPLANE + row * VS + c4 * 2) = pv[pl];
-            }
-            if (HD >= 96) __builtin_amdgcn_sched_barrier(0);  // one split's temporaries at a time (HD 96: 253 -> 233 VGPRs; HD 128 still spills, DESIGN 21)
-        }
-        if (KMASK && tid < 32) *reinterpret_cast<float*>(sK + tid * KS + HD * 2) = mreg;
-        __syncthreads();
-        if (kt + 1 < n_tiles) fetch(kt + 1);
-        if (dbg & 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (dbg & 2) __syncthreads();  // before the tile skip: see attention_kernel
-        QA_ATT_TICK(0)
-        if (!(dbg & 8) && (kt * 32 > wave_last_key || kt * 32 + 31 < wave_first_key || q_blk0 + wave * 32 >= n_q)) continue;
-
-        // S^T = K Q^T; planes 0 = h, 1 = m, 2 = l; order hl, lh, mm, hm, mh, hh (LDS operand's plane first)
-        constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int g = 0; g < NKG; ++g) {
-            bf16x8 kf[3];
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) kf[pl] = *reinterpret_cast<const bf16x8*>(kread + pl * KPLANE + 32 * g);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[PA[i]], qf[PB[i]][g], s, 0, 0, 0);
-            if (HD >= 96) __builtin_amdgcn_sched_barrier(0);  // one group's fragments live at a time (register pressure, as above)
-        }
-        QA_ATT_TICK(1)
-        // online softmax in base 2, as in attention_kernel
-        const int q_first = q_blk0 + wave * 32, q_last = q_first + 31;
-        const bool need_mask = KMASK || (dbg & 16) || ring || kt * 32 + 31 >= n_keys ||
-                               (lin_causal && (kt * 32 + 31 > q_first + off || (context > 0 && kt * 32 < q_last + off - context + 1)));
-        float tmax = -INFINITY;
-        if (BIAS || need_mask) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                bool ok = key < n_keys;
-                if (KMASK) ok = ok && *reinterpret_cast<const float*>(sK + ((r & 3) + 8 * (r >> 2) + 4 * hh) * KS + HD * 2) != 0.f;
-                if (ring) {
-                    const int delta = key - ring_idx;
-                    const int pos = key >= ring_end ? -1 : (delta <= 0 ? ring_end + delta : ring_end + delta - n_keys);
-                    const int dq = q_pos0 + qi - pos;
-                    ok = ok && pos >= 0 && dq >= 0 && dq < context;
-                } else if (causal) {
-                    ok = ok && key <= qi + off && (context <= 0 || qi + off - key < context);
-                }
-                float sc = s[r];
-                if (BIAS) sc += gate_q * rb[max(-R, min(R, key - qi))];
-                s[r] = ok ? sc : -INFINITY;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);  // m_run = -inf -> 0
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = __builtin_amdgcn_exp2f(s[r] - m_use);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-        if ((dbg & 1) || __any(alpha != 1.f)) {
-#pragma unroll
-            for (int t = 0; t < DT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-        }
-        QA_ATT_TICK(2)
-        // O^T += V^T P^T, the P planes of each 16-key step split in registers right before its MFMAs
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            bf16x8 pf[3];
-            {
-                u32x2 p0[3], p1[3];
-                const f32x4 x0 = {s[8 * st + 0], s[8 * st + 1], s[8 * st + 2], s[8 * st + 3]};
-                const f32x4 x1 = {s[8 * st + 4], s[8 * st + 5], s[8 * st + 6], s[8 * st + 7]};
-                split4_unit(x0, p0[0], p0[1], p0[2]);
-                split4_unit(x1, p1[0], p1[1], p1[2]);
-                if (zp) {
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl)
-                        if (zp & (1 << pl)) p0[pl] = p1[pl] = u32x2{0u, 0u};
-                }
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) pf[pl] = frag8(p0[pl], p1[pl]);
-            }
-#pragma unroll
-            for (int t = 0; t < DT; ++t) {
-                bf16x8 vf[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    const char* a = vread + pl * VPLANE + 16 * st * VS + 64 * t;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 8 * VS));
-                    const s16x8 w = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    vf[pl] = __builtin_bit_cast(bf16x8, w);
-                }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[PA[i]], pf[PB[i]], o[t], 0, 0, 0);
-                if (HD >= 96) __builtin_amdgcn_sched_barrier(0);  // as above
-            }
-        }
-#ifdef QA_ATT_TIMING
-        ++n_done;
-#endif
-    }
-#ifdef QA_ATT_TIMING
-    QA_ATT_TICK(3)
-    if (lane == 0) {
-        for (int i = 0; i < 4; ++i) atomicAdd(&g_qa_att_timing[i], (unsigned long long)tacc[i]);
-        atomicAdd(&g_qa_att_timing[4], (unsigned long long)(tlast - tbegin));
-        atomicAdd(&g_qa_att_timing[5], 1ULL);
-        atomicAdd(&g_qa_att_timing[6], (unsigned long long)n_done);
-    }
-#endif
-
-    if (qi < n_q) {
-        const float inv = l_run > 0.f ? 1.f / l_run : 0.f;  // no visible key: 0 (attention_kernel)
-        float* op = out + ((long long)b * n_q + qi) * ldo + head * HD + 4 * hh;
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float4 w;
-                w.x = o[t][4 * c + 0] * inv; w.y = o[t][4 * c + 1] * inv;
-                w.z = o[t][4 * c + 2] * inv; w.w = o[t][4 * c + 3] * inv;
-                *reinterpret_cast<float4*>(op + 32 * t + 8 * c) = w;
-            }
-    }
+template <int HD, bool SPLIT>
+static auto attention_instance(bool bias, bool kmask) {
+    return kmask ? attention_kernel<HD, false, true, SPLIT> : bias ? attention_kernel<HD, true, false, SPLIT> : attention_kernel<HD, false, false, SPLIT>;
 }
 
 static std::atomic<long long> g_att_launches[2];  // by kernel form: [0] fp32 chain, [1] split-6 (qa_debug_att_stats)
 
 // gate [B, H, n_q] and relbias [H, 2R+1] (both optional, together): gated relative position bias, see attention_kernel.
-// Arithmetic: split-6 (attention_split_kernel) unless QA_ATT_MATH = 0 or the caller asks for the fp32 chain (math_fp32: the UniSE LM,
-// whose prefill stays consistent with its fp32 decode kernels)
+// Arithmetic: split-6 (SPLIT) unless QA_ATT_MATH = 0 or the caller asks for the fp32 chain (math_fp32: the UniSE LM, whose prefill
+// stays consistent with its fp32 decode kernels)
 int launch_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
                      long long ldo, int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale,
                      int causal, hipStream_t s, const float* gate, const float* relbias, int R, int context, int q_pos0,
@@ -610,34 +470,18 @@ int launch_attention(const float* q, long long ldq, const float* k, const float*
     QA_REQUIRE((gate == nullptr) == (relbias == nullptr) && (!gate || (R >= 0 && !causal && n_q == n_keys)),
                "attention: gate and relbias come together, for non-causal self-attention");
     QA_REQUIRE(!kvalid || (!gate && !causal && n_q == n_keys), "attention: the key-padding mask is for non-causal self-attention without bias");
-    dim3 grid((unsigned)ceil_div(n_q, 128), H, B);
-    const int dbg = (int)knob(K_ATT_DEBUG);
     const bool split = knob(K_ATT_MATH) != 0 && !math_fp32;
-#define QA_ATT_FORM(KERNEL, HD)                                                                                              \
-    if (kvalid)                                                                                                              \
-        hipLaunchKernelGGL((KERNEL<HD, false, true>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q, \
-                           n_keys, scale, causal, nullptr, nullptr, 0, context, q_pos0, ring_end, dbg, kvalid);                 \
-    else if (gate)                                                                                                                \
-        hipLaunchKernelGGL((KERNEL<HD, true>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q, \
-                           n_keys, scale, causal, gate, relbias, R, context, q_pos0, ring_end, dbg, nullptr);                           \
-    else                                                                                                                     \
-        hipLaunchKernelGGL((KERNEL<HD, false>), grid, dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q, \
-                           n_keys, scale, causal, nullptr, nullptr, 0, context, q_pos0, ring_end, dbg, nullptr)
-#define QA_ATT(HD)                                   \
-    if (split) {                                     \
-        QA_ATT_FORM(attention_split_kernel, HD);     \
-    } else {                                         \
-        QA_ATT_FORM(attention_kernel, HD);           \
-    }
+    const bool bias = gate != nullptr, kmask = kvalid != nullptr;
+    decltype(attention_instance<32, false>(bias, kmask)) kernel;
     switch (hd) {
-        case 32: QA_ATT(32); break;
-        case 64: QA_ATT(64); break;
-        case 96: QA_ATT(96); break;
-        case 128: QA_ATT(128); break;
+        case 32: kernel = split ? attention_instance<32, true>(bias, kmask) : attention_instance<32, false>(bias, kmask); break;
+        case 64: kernel = split ? attention_instance<64, true>(bias, kmask) : attention_instance<64, false>(bias, kmask); break;
+        case 96: kernel = split ? attention_instance<96, true>(bias, kmask) : attention_instance<96, false>(bias, kmask); break;
+        case 128: kernel = split ? attention_instance<128, true>(bias, kmask) : attention_instance<128, false>(bias, kmask); break;
         default: qa::set_error("attention: head_dim=%d unsupported (32/64/96/128)", hd); return QA_ERR_UNSUPPORTED;
     }
-#undef QA_ATT_FORM
-#undef QA_ATT
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(n_q, 128), H, B), dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q,
+                       n_keys, scale, causal, gate, relbias, R, context, q_pos0, ring_end, (int)knob(K_ATT_DEBUG), kvalid);
     QA_LAUNCH_CHECK();
     g_att_launches[split ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
     return QA_OK;

@@ -50,9 +50,6 @@ extern "C" int qa_debug_timing(unsigned long long* out, int reset) {
 
 namespace qa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // ---- pre-split weight images (QA_GEMM_PRESPLIT; layout and split in split_planes.h) ----
 // The weights of a model never change after load, yet the K loop splits a weight tile again for every row tile of every launch.
 // A WeightStore therefore builds the plane image of its whole blob once, at load, and attaches it here; launch_conv_gemm looks the
@@ -453,15 +450,14 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
                 }
                 if (g == 0) QA_LOAD_GLOBAL(nxt)
                 if (g == NG - 1) QA_STORE_LDS(cur ^ 1)
-                // operands swapped as in the fp32 loop below; planes 0 = h, 1 = m, 2 = l; order hl, lh, mm, hm, mh, hh
-                constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PW[6] = {2, 0, 1, 1, 0, 0};
+                // operands swapped as in the fp32 loop below; plane pairs in the order of split_planes.h (PAIR_A: activation, PAIR_B: weight)
 #pragma unroll
                 for (int q = 0; q < 6; ++q)
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PW[q]][j], af[PA[q]][i], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PAIR_B[q]][j], af[PAIR_A[q]][i], acc[i][j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             __syncthreads();

@@ -159,7 +159,7 @@ struct Ctx {
     hipStream_t stream = nullptr;
     bool dry = false;      // planning pass: allocate, do not launch
     bool gemm_fp32 = false;  // conv_op launches keep conv_gemm's fp32 chain (ConvParams::math_fp32)
-    bool att_fp32 = false;   // attention_op launches keep attention_kernel's fp32 chain (set wherever gemm_fp32 is)
+    bool att_fp32 = false;   // attention_op launches keep the fp32 form of attention_kernel (SPLIT = false) (set wherever gemm_fp32 is)
     bool capture = false;  // test hook: snapshot named intermediates (buffers are reused / updated in place later)
     std::unordered_map<std::string, Tap> taps;
     void tap(const std::string& name, const float* p, int64_t n) {

@@ -61,7 +61,8 @@ int launch_resample(const float* wav, const float* taps, float* out, int B, long
 //   gate [B, H, n_q] + relbias [H, 2R+1] (optional): score(i, j) += gate[b,h,i] * relbias[h][clamp(j - i, -R, R) + R]
 //   (WavLM gated relative position bias)
 //   kvalid [B, n_keys] bytes (optional, non-causal self-attention only): key j of item b is visible iff kvalid[b, j] != 0
-//   math_fp32: keep the fp32 chain (v_mfma_f32_32x32x2_f32) whatever QA_ATT_MATH says (Ctx::att_fp32)
+//   one kernel body in two arithmetic forms (attention_kernel<HD, BIAS, KMASK, SPLIT>): split-6 on the bf16 MFMA where QA_ATT_MATH = 1
+//   math_fp32: keep the fp32 form (SPLIT = false, v_mfma_f32_32x32x2_f32) whatever QA_ATT_MATH says (Ctx::att_fp32)
 int launch_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
                      long long ldo, int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale,
                      int causal, hipStream_t s, const float* gate = nullptr, const float* relbias = nullptr, int R = 0,

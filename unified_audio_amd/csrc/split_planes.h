@@ -1,4 +1,4 @@
-// split_planes.h - the operand split of conv_gemm's split-6 arithmetic and the memory layout of a pre-split weight image.
+// split_planes.h - the operand split of the split-6 arithmetic (conv_gemm, attention) and the memory layout of a pre-split weight image.
 //
 // The K loop (activations, and weights without an image) and the load-time image builder run the SAME device function, so an image
 // holds bit for bit what the loop would have produced.
@@ -14,6 +14,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // one operand fragment of v_mfma_f32_32x32x16_bf16
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // one 32x32 accumulator
 
 // Split-6 math (QA_GEMM_MATH = 1).  Each operand is split, exactly, into three bf16 planes x = h + m + l by round-to-nearest-even:
 // h = rne(x), m = rne(x - h), l = x - h - m.  Both subtractions are exact and l keeps <= 8 significant bits (sign borrowing), so
@@ -22,6 +24,11 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // the size of one fp32 rounding, of random sign.  Non-finite x: h = x and m = l = 0 (the residual is zeroed when it is not finite),
 // so inf and NaN reach the sum through hh exactly as through the fp32 chain.  A finite |x| that rounds past the largest bf16
 // (>= 2^128 (1 - 2^-9)) becomes h = inf.
+// The plane pairs of a k group in issue order (planes 0 = h, 1 = m, 2 = l).  Smallest terms first: the accumulator takes the 2^-16-sized
+// hl and lh and the mm before the 2^-8-sized hm and mh and the full-sized hh, so the small terms are summed among themselves before a
+// large partial sum can round them away.  PAIR_A is the plane of the first-named operand (conv_gemm: the activation; attention: the LDS
+// operand, K or V), PAIR_B that of the second (conv_gemm: the weight; attention: the register operand, Q or P).
+constexpr int PAIR_A[6] = {0, 2, 1, 0, 1, 0}, PAIR_B[6] = {2, 0, 1, 1, 0, 0};
 __device__ __forceinline__ unsigned rne_bf16x2(float a, float b) {  // low half bf16(a), high half bf16(b): one v_cvt_pk_bf16_f32
     const f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
@@ -39,6 +46,22 @@ __device__ __forceinline__ void split4_rne(const f32x4 x, u32x2& ph, u32x2& pm, 
         pm[i] = m;
         pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
     }
+}
+__device__ __forceinline__ void split4_unit(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {  // split4_rne for x in [0, 1]
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float a = x[2 * i], b = x[2 * i + 1];
+        const unsigned h = rne_bf16x2(a, b);
+        const float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
+        const unsigned m = rne_bf16x2(ra, rb);
+        ph[i] = h;
+        pm[i] = m;
+        pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
+    }
+}
+__device__ __forceinline__ bf16x8 frag8(const u32x2 lo, const u32x2 hi) {  // two split4 halves of one plane -> an MFMA fragment
+    const u32x4 t = {lo[0], lo[1], hi[0], hi[1]};
+    return __builtin_bit_cast(bf16x8, t);
 }
 
 // Pre-split weight image (QA_GEMM_PRESPLIT).  The image of a float array w[0 .. n), n % 8 == 0, holds 6 bytes per weight: every
