@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-phase shader-cycle breakdown of the implicit-GEMM main loop (needs a -DQA_TIMING build: tools/variants.py timing "-DQA_TIMING";
+"""Shader cycles per wave of the implicit-GEMM kernel: epilogue, whole kernel, K chunks and the shader clock (needs a -DQA_TIMING build: tools/variants.py timing "-DQA_TIMING";
 run with QA_LIBRARY=tools/_variants/timing/libquarkaudio_hip.so)."""
 import ctypes as C
 import os
@@ -36,9 +36,7 @@ def main():
         t = (C.c_ulonglong * 10)()
         lib.qa_debug_timing(t, 0)
         waves, chunks = t[6], t[7]
-        per = [t[i] / max(chunks, 1) for i in range(4)]
-        print(f"{name:18s} {e0.elapsed_time(e1) * 1e3:8.1f} us | per chunk per wave (cycles): addr+issue {per[0]:7.0f}  mfma {per[1]:7.0f}  "
-              f"wait+lds-store {per[2]:7.0f}  barrier {per[3]:7.0f} | per wave: epilogue {t[4] / waves:8.0f}  total {t[5] / waves:9.0f}  chunks {chunks / waves:.0f}  shader clock {t[5] / max(t[8], 1) * 100:.0f} MHz")
+        print(f"{name:18s} {e0.elapsed_time(e1) * 1e3:8.1f} us | per wave: epilogue {t[4] / waves:8.0f}  total {t[5] / waves:9.0f}  chunks {chunks / waves:.0f}  shader clock {t[5] / max(t[8], 1) * 100:.0f} MHz")
 
 
 if __name__ == "__main__":

@@ -159,13 +159,15 @@ void profile_record_begin(int cfg, double flops, double bytes, hipStream_t s, co
 void profile_record_end(hipStream_t s);
 
 int launch_conv_gemm(const ConvParams& p, hipStream_t stream);
-// Pre-split weight images (conv_gemm.hip, split_planes.h): build the image of w[0 .. n) (6 n bytes, n % 8 == 0) on `stream`; attach it,
+// Pre-split weight images (weight_planes.hip, split_planes.h): build the image of w[0 .. n) (6 n bytes, n % 8 == 0) on `stream`; attach it,
 // so that conv_gemm launches whose weight lies inside w[0 .. n) read it; detach it again (before either buffer is freed); bytes of
-// all attached images of the process
+// all attached images of the process; the planes of w[0 .. n) when one attached image covers them and w sits on an 8-float group of
+// it, else nullptr (launch_conv_gemm: split in the loop)
 int launch_weight_planes(const float* w, long long n, void* planes, hipStream_t stream);
 int weight_planes_attach(const float* w, long long n, const void* planes);
 void weight_planes_detach(const float* w);
 long long weight_planes_bytes();
+const char* weight_planes_find(const float* w, long long n);
 int conv_params_from_args(const qa_conv_args& a, ConvParams* p);
 
 }  // namespace qa

@@ -12,13 +12,13 @@
 // the current tile's MFMAs).  LDS rows are padded to 36 floats so that the ds_read_b128 fragment loads are
 // bank-conflict free; each lane fetches 4 consecutive k per read and the (lane>>5) halves take k-groups
 // {0..3},{4..7}: the K order inside a step is permuted identically for A and B, which leaves the sum unchanged.
-// That is the fp32 chain (QA_GEMM_MATH = 0).  The default, split-6 (QA_GEMM_MATH = 1, split4_rne below), runs the same tiles on the
-// bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.
+// That is the fp32 chain (QA_GEMM_MATH = 0).  The default, split-6 (QA_GEMM_MATH = 1, split4_rne in split_planes.h), runs the same tiles
+// on the bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.
+// Host side: launch_conv_gemm validates and derives the kernel's parameters, choose_tile is the tile cost model, launch_cfg /
+// launch_instance map a tile to a kernel instance.  The pre-split weight images the PRE instances read live in weight_planes.hip.
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 
 #include "common.h"
 #include "split_planes.h"
@@ -28,14 +28,8 @@
 #define QA_LOAD_AT 0
 #endif
 
-#ifdef QA_TIMING  // tuning builds only (tools/variants.py): per-phase shader-cycle totals of the main loop, summed over waves
-__device__ unsigned long long g_qa_timing[10];
-#define QA_TICK(i)                                              \
-    {                                                           \
-        const long long now_ = __builtin_readcyclecounter();    \
-        tacc[i] += now_ - tlast;                                \
-        tlast = now_;                                           \
-    }
+#ifdef QA_TIMING  // tuning builds only (tools/variants.py, read by tools/gemm_timing.py): shader-cycle totals of the kernel, summed over waves
+__device__ unsigned long long g_qa_timing[10];  // [4] epilogue, [5] main loop + epilogue, [6] waves, [7] chunks, [8] the interval of [5] in 100 MHz ticks; the rest unused
 extern "C" int qa_debug_timing(unsigned long long* out, int reset) {
     if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_qa_timing), sizeof(g_qa_timing)) != hipSuccess) return -1;  // out[10]
     if (reset) {
@@ -44,83 +38,9 @@ extern "C" int qa_debug_timing(unsigned long long* out, int reset) {
     }
     return 0;
 }
-#else
-#define QA_TICK(i)
 #endif
 
 namespace qa {
-
-// ---- pre-split weight images (QA_GEMM_PRESPLIT; layout and split in split_planes.h) ----
-// The weights of a model never change after load, yet the K loop splits a weight tile again for every row tile of every launch.
-// A WeightStore therefore builds the plane image of its whole blob once, at load, and attaches it here; launch_conv_gemm looks the
-// launch's weight pointer up and, when an image covers it, takes the kernel instance whose B staging copies 16-byte plane units
-// instead of splitting.  The lookup is by address, so row slices and hand-built views of a stored weight find their planes too.
-__global__ __launch_bounds__(256) void weight_planes_kernel(const float* __restrict__ w, long long groups, char* __restrict__ planes) {
-    for (long long g = blockIdx.x * 256LL + threadIdx.x; g < groups; g += gridDim.x * 256LL) {
-        u32x2 h0, m0, l0, h1, m1, l1;
-        split4_rne(*reinterpret_cast<const f32x4*>(w + g * 8), h0, m0, l0);
-        split4_rne(*reinterpret_cast<const f32x4*>(w + g * 8 + 4), h1, m1, l1);
-        u32x4* out = reinterpret_cast<u32x4*>(planes + g * PLANE_GROUP_BYTES);
-        out[0] = u32x4{h0[0], h0[1], h1[0], h1[1]};
-        out[1] = u32x4{m0[0], m0[1], m1[0], m1[1]};
-        out[2] = u32x4{l0[0], l0[1], l1[0], l1[1]};
-    }
-}
-
-int launch_weight_planes(const float* w, long long n, void* planes, hipStream_t stream) {
-    QA_REQUIRE(w && planes && n >= 0 && n % 8 == 0, "weight_planes: null pointer or n=%lld not a multiple of 8", n);
-    QA_REQUIRE(((uintptr_t)w % 16) == 0 && ((uintptr_t)planes % 16) == 0, "weight_planes: w / planes must be 16-byte aligned");
-    if (n == 0) return QA_OK;
-    const long long groups = n / 8;
-    const unsigned grid = (unsigned)std::min<long long>(ceil_div(groups, 256), 256 * 64);
-    hipLaunchKernelGGL(weight_planes_kernel, dim3(grid), dim3(256), 0, stream, w, groups, static_cast<char*>(planes));
-    QA_LAUNCH_CHECK();
-    return QA_OK;
-}
-
-namespace {
-struct PlaneImage {
-    const float* w;
-    long long n;
-    const char* planes;
-};
-std::mutex g_planes_mu;
-std::vector<PlaneImage> g_planes;  // a handful of entries: one per loaded weight store
-}  // namespace
-
-int weight_planes_attach(const float* w, long long n, const void* planes) {
-    QA_REQUIRE(w && planes && n > 0 && n % 8 == 0, "weight_planes_attach: null pointer or n=%lld not a positive multiple of 8", n);
-    QA_REQUIRE(((uintptr_t)w % 32) == 0 && ((uintptr_t)planes % 16) == 0, "weight_planes_attach: w must be 32-byte, planes 16-byte aligned");
-    std::lock_guard<std::mutex> lock(g_planes_mu);
-    for (const PlaneImage& im : g_planes)
-        QA_REQUIRE(w + n <= im.w || im.w + im.n <= w, "weight_planes_attach: the range overlaps an attached image");
-    g_planes.push_back(PlaneImage{w, n, static_cast<const char*>(planes)});
-    return QA_OK;
-}
-
-void weight_planes_detach(const float* w) {
-    std::lock_guard<std::mutex> lock(g_planes_mu);
-    for (size_t i = 0; i < g_planes.size(); ++i)
-        if (g_planes[i].w == w) {
-            g_planes.erase(g_planes.begin() + (long)i);
-            return;
-        }
-}
-
-long long weight_planes_bytes() {
-    std::lock_guard<std::mutex> lock(g_planes_mu);
-    long long total = 0;
-    for (const PlaneImage& im : g_planes) total += im.n / 8 * PLANE_GROUP_BYTES;
-    return total;
-}
-
-// the planes of w[0 .. n) when one attached image covers them and w sits on an 8-float group of it; else nullptr (split in the loop)
-static const char* weight_planes_find(const float* w, long long n) {
-    std::lock_guard<std::mutex> lock(g_planes_mu);
-    for (const PlaneImage& im : g_planes)
-        if (w >= im.w && w + n <= im.w + im.n && ((w - im.w) & 7) == 0) return im.planes + plane_byte_offset(w - im.w, 0);
-    return nullptr;
-}
 
 // LDS bytes of one conv_gemm configuration (fp32 image with 4-float row padding, or three bf16 planes) and the workgroups per CU that
 // the register budget is tuned for
@@ -197,7 +117,7 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const ConvParams& p, long lo
 // 48 image units: 128 / BK rows x BK / 8 slots x 3 planes.  A staging thread owns the same unit of every chunk - one 16-byte global
 // load, one ds_write_b128, both addresses fixed before the loop - and 16 consecutive lanes write the 256 contiguous (XOR-permuted)
 // bytes that one plane of a block occupies in LDS.  The LDS image is byte for byte the one the in-loop split builds.  Instantiated
-// for the 128-column tiles only (launch_cfg).
+// for the 128-column tiles only (launch_instance).
 template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false, bool SPLIT = false, bool PRE = false>
 __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv_gemm_kernel(const ConvParams p_in) {
     static_assert(SPLIT || !PRE, "a pre-split weight image feeds the split-6 instances only");
@@ -403,9 +323,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
     const int frag_row = lane & 31;
     const int frag_k = (lane >> 5) * 4;
 #ifdef QA_TIMING
-    long long tacc[5] = {0, 0, 0, 0, 0};
-    long long tlast = __builtin_readcyclecounter();
-    const long long tbegin = tlast;
+    const long long tbegin = __builtin_readcyclecounter();
     const unsigned long long rbegin = __builtin_amdgcn_s_memrealtime();  // constant 100 MHz
 #endif
     // One K chunk = BK/8 groups of 4*TM*TN MFMAs.  The next chunk's address arithmetic + global loads ride in group 0 and
@@ -598,7 +516,6 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
 #ifdef QA_TIMING
     if (lane == 0) {
         const long long tend = __builtin_readcyclecounter();
-        for (int i = 0; i < 4; ++i) atomicAdd(&g_qa_timing[i], (unsigned long long)tacc[i]);
         atomicAdd(&g_qa_timing[4], (unsigned long long)(tend - tloop));   // epilogue
         atomicAdd(&g_qa_timing[5], (unsigned long long)(tend - tbegin));  // main loop + epilogue
         atomicAdd(&g_qa_timing[6], 1ULL);                                 // waves
@@ -608,76 +525,121 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
 #endif
 }
 
+// the geometry of a Linear / 1x1 layer (the LINEAR instances), QA_GEMM_LINEAR on; the ELU prologue term stays with each user
+static bool is_linear(const ConvParams& p) {
+    return knob(K_GEMM_LINEAR) != 0 && p.ksize == 1 && p.stride == 1 && p.pad_left == 0 && p.in_rep <= 1 && p.T_in == p.T_out && p.dilation <= 1;
+}
+
+constexpr int prof_cfg(int bm, int bn) {  // PROF_CFG_* of a tile
+    return bm == 256 ? PROF_CFG_256x128 : bm == 64 ? (bn == 64 ? PROF_CFG_64x64 : PROF_CFG_64x128) : bn == 32 ? PROF_CFG_128x32 : bn == 64 ? PROF_CFG_128x64 : PROF_CFG_128x128;
+}
+
+// one (tile, prologue, chunk, addressing) choice in its three arithmetic instances
+template <int BM, int BN, int WM, int WN, bool ELU, int BK, bool LIN>
+static void launch_instance(const ConvParams& p, long long tiles, hipStream_t stream) {
+    // QA_GEMM_MATH: 1 = split-6 (bf16 planes, default), 0 = the fp32 chain; the same for every launch whatever its M
+    const bool split = knob(K_GEMM_MATH) != 0 && !p.math_fp32;
+    constexpr bool IMAGE = BN == 128;  // narrower tiles keep the in-loop split: measured slower from an image
+    const auto kernel = !split            ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, false, false>
+                        : IMAGE && p.wp ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, true, IMAGE>
+                                        : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, true, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+}
+
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     QA_REQUIRE(p.prologue == ACT_NONE || p.prologue == ACT_ELU, "conv_gemm: prologue %d unsupported", p.prologue);
     const long long tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    // BK = 16 chunks need 45 KB / 35 KB of LDS, so 3-4 workgroups are co-resident per CU (BK = 32: 2) and cover each
-    // other's barriers, prologues and epilogues: +10..25 % on the K = 512 layers of the aggregator stacks, +3..5 % on
-    // K = 768..3072 (per-shape sweep, tools/gemm_bench.py with QA_GEMM_BK16=0 / default).  QA_GEMM_BK16 = largest K that
-    // takes the BK = 16 variant.
+    // BK = 16 chunks need 45 KB / 35 KB of LDS, so 3-4 workgroups are co-resident per CU (BK = 32: 2) and cover each other's barriers, prologues and
+    // epilogues: +10..25 % on the K = 512 layers of the aggregator stacks, +3..5 % on K = 768..3072 (per-shape sweep, tools/gemm_bench.py with
+    // QA_GEMM_BK16=0 / default).  QA_GEMM_BK16 = largest K that takes the BK = 16 variant.
     const long long bk16_max_k = knob(K_GEMM_BK16);
-    // ... but only when the launch has enough tiles for that co-residency: with about one workgroup per CU nobody covers the
-    // exposed latency of the next chunk's global loads, which a BK = 16 chunk's 0.45 us of MFMAs is too short to hide (measured: the
-    // 144-tile RVQ distance GEMM 1056 x 1024 x 512 ran 37 us, 2.5 x its MFMA time).  QA_GEMM_BK16_MIN_TILES = fewest tiles that take BK = 16.
+    // ... but only when the launch has enough tiles for that co-residency: with about one workgroup per CU nobody covers the exposed latency of the
+    // next chunk's global loads, which a BK = 16 chunk's 0.45 us of MFMAs is too short to hide (measured: the 144-tile RVQ distance GEMM 1056 x 1024
+    // x 512 ran 37 us, 2.5 x its MFMA time).  QA_GEMM_BK16_MIN_TILES = fewest tiles that take BK = 16.
     const long long bk16_min_tiles = knob(K_GEMM_BK16_MIN_TILES);
-    const bool linear_on = knob(K_GEMM_LINEAR) != 0;
-    const bool linear = linear_on && p.ksize == 1 && p.stride == 1 && p.pad_left == 0 && p.in_rep <= 1 && p.T_in == p.T_out &&
-                        (p.dilation <= 1);
-    const bool bk16 = BN >= 64 && p.prologue != ACT_ELU && ((p.K <= bk16_max_k && tiles >= bk16_min_tiles) || p.C_in % 32 != 0);
+    const bool linear = is_linear(p), elu = p.prologue == ACT_ELU;
+    // the 256-row tile (r06 experiment, QA_GEMM_256) exists with BK = 16 only: 61 KB of LDS, two workgroups per CU
+    const bool bk16 = BM == 256 || (BN >= 64 && !elu && ((p.K <= bk16_max_k && tiles >= bk16_min_tiles) || p.C_in % 32 != 0));
     // the K loop runs K / BK whole chunks and the table form reads each chunk from ONE tap: a BK that does not divide K (and, with the
     // table, C_in) would drop the tail of K or read past a tap's C_in channels - into the next frame or the next channel group
-    const int bk = BM == 256 || bk16 ? 16 : 32;
-    const bool table = BM != 256 && (!linear || p.prologue == ACT_ELU);  // the ELU prologue exists in the table form only
+    const int bk = bk16 ? 16 : 32;
+    const bool table = BM != 256 && (!linear || elu);  // the ELU prologue exists in the table form only
     QA_REQUIRE(p.K % bk == 0 && (!table || p.C_in % bk == 0),
                "conv_gemm: the %dx%d tile's BK = %d K chunk does not divide K=%d / C_in=%d", BM, BN, bk, p.K, p.C_in);
     const bool prof = profile_enabled();
     if (prof) {
-        const int cfg = BM == 256 ? PROF_CFG_256x128 : BM == 64 ? (BN == 64 ? PROF_CFG_64x64 : PROF_CFG_64x128) : (BN == 32 ? PROF_CFG_128x32 : (BN == 64 ? PROF_CFG_128x64 : PROF_CFG_128x128));
         const double n = p.algo_n ? p.algo_n : p.N, k = p.algo_k ? p.algo_k : p.K;
         // algorithmic bytes: every input frame, weight and output element once (+ fused residual / gate reads)
         const double out_elems = p.am_dist ? 2.0 * (double)p.M * p.am_ld + p.M + n  // arg-min epilogue: (dist, idx) per 32 columns + |r|^2 + |e|^2
                                             : (double)p.M * n * (1.0 + (p.res ? 1.0 : 0.0) + (p.gate ? 1.0 : 0.0));
         const double elems = (double)p.B * p.T_in * p.C_in + n * k + out_elems;
-        profile_record_begin(cfg, 2.0 * (double)p.M * n * k, 4.0 * elems, stream, &p);
+        profile_record_begin(prof_cfg(BM, BN), 2.0 * (double)p.M * n * k, 4.0 * elems, stream, &p);
     }
-    // QA_GEMM_MATH: 1 = split-6 (bf16 planes, default), 0 = the fp32 chain; the same for every launch whatever its M
-    const bool split = knob(K_GEMM_MATH) != 0 && !p.math_fp32;
-#define QA_GEMM_GO(BM_, BN_, WM_, WN_, ELU_, BK_, LIN_)                                                                              \
-    {                                                                                                                               \
-        if (split && p.wp && BN_ == 128) /* narrower tiles keep the in-loop split: measured slower from an image */ \
-            hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, true, BN_ == 128>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
-        else if (split)                                                                                                             \
-            hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((conv_gemm_kernel<BM_, BN_, WM_, WN_, ELU_, BK_, LIN_, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p); \
+    if constexpr (BM == 256) QA_REQUIRE(linear && !elu, "conv_gemm: the 256 x 128 tile exists for LINEAR layers only");
+    constexpr int BK16 = BN >= 64 ? 16 : 32;  // the 32-column tile has no BK = 16 instance (bk16 is false for it)
+    if (bk16 && linear) launch_instance<BM, BN, WM, WN, false, BK16, true>(p, tiles, stream);
+    else if constexpr (BM != 256) {  // the 256-row tile has the instance above only
+        if (bk16) launch_instance<BM, BN, WM, WN, false, BK16, false>(p, tiles, stream);
+        else if (elu) launch_instance<BM, BN, WM, WN, true, 32, false>(p, tiles, stream);
+        else if (linear) launch_instance<BM, BN, WM, WN, false, 32, true>(p, tiles, stream);
+        else launch_instance<BM, BN, WM, WN, false, 32, false>(p, tiles, stream);
     }
-    if constexpr (BM == 256) {  // r06 experiment (QA_GEMM_256): LINEAR layers only, BK = 16 (61 KB of LDS: two workgroups per CU)
-        QA_REQUIRE(linear && p.prologue != ACT_ELU, "conv_gemm: the 256 x 128 tile exists for LINEAR layers only");
-        QA_GEMM_GO(256, 128, 2, 2, false, 16, true)
-        if (prof) profile_record_end(stream);
-        QA_LAUNCH_CHECK();
-        return QA_OK;
-    } else
-    if (bk16 && linear)
-        QA_GEMM_GO(BM, BN, WM, WN, false, (BN >= 64 ? 16 : 32), true)
-    else if (bk16)
-        QA_GEMM_GO(BM, BN, WM, WN, false, (BN >= 64 ? 16 : 32), false)
-    else if (p.prologue == ACT_ELU)
-        QA_GEMM_GO(BM, BN, WM, WN, true, 32, false)
-    else if (linear)
-        QA_GEMM_GO(BM, BN, WM, WN, false, 32, true)
-    else
-        QA_GEMM_GO(BM, BN, WM, WN, false, 32, false)
-#undef QA_GEMM_GO
     if (prof) profile_record_end(stream);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
 
+// Tile choice of a launch (a PROF_CFG_* value that has a kernel for this launch).
+// Tiles of one launch are dealt round-robin over 256 CUs (the co-resident workgroups of a CU share its matrix pipes), so the makespan is (tiles on
+// the busiest CU) x (work per tile) / (sustained efficiency of the tile).  Round 4 adds the 64-row tiles: the aggregator stacks of H-Codec 1.5 (M =
+// 9056 = 70.75 x 128) and the 4000-row SSL / BiCodec layers lose up to a third of the machine to tile quantisation with 128-row tiles (852 tiles of
+// 128 x 128 = 3.33 per CU: a fourth round for a third of the CUs).  Efficiencies from the square 8192 x 4096 x 4096 problem, where every tile divides
+// the grid evenly (profiles/r04_gemm_tile_sweep.txt: 133.1 / 121.5 / 121.6 / 115.9 TFLOP/s); ties go to the larger tile (less L2 traffic). Every
+// configuration accumulates an output element over k in the same order, so this choice - which depends on M, i.e. on the batch size - never changes a
+// bit (tests/test_kernels_gpu.py::test_conv_gemm_tile_configurations_are_bit_identical).
+static int choose_tile(const ConvParams& p) {
+    const bool lin = is_linear(p) && p.prologue != ACT_ELU;
+    int cfg = (int)knob(K_GEMM_CFG);  // >= 0: forced
+    if (cfg < 0) {
+        if (p.N <= 32) cfg = PROF_CFG_128x32;
+        else if (p.N <= 64) cfg = PROF_CFG_128x64;
+        else {
+            struct Cand { int cfg, bm, bn; double eff; };
+            static const Cand cands[] = {{PROF_CFG_128x128, 128, 128, 1.0}, {PROF_CFG_64x128, 64, 128, 0.914}, {PROF_CFG_128x64, 128, 64, 0.913},
+                                         {PROF_CFG_64x64, 64, 64, 0.871}};
+            // a launch that gives a CU at most ONE workgroup has nobody to cover that workgroup's barriers, prologue and epilogue: the
+            // 256-tile 4032 x 512 x 512 launch runs 8 % faster as 504 tiles of 64 x 64 although those need two rounds (same sweep)
+            auto cost_of = [&](int bm, int bn, double eff) {
+                const long long tiles = ceil_div(p.M, bm) * ceil_div(p.N, bn);
+                return (double)ceil_div(tiles, 256) * bm * bn / eff * (tiles <= 256 ? 1.25 : 1.0);
+            };
+            double best = 0.0;
+            cfg = PROF_CFG_128x128;
+            const long long eff256 = knob(K_GEMM_256);  // 0: never; else the tile's efficiency relative to 128 x 128, in 1/1000
+            if (eff256 > 0 && lin && p.M >= 8000 && p.N >= 1024) {  // try the 256 x 128 tile in front of the 128 x 128 one
+                best = cost_of(256, 128, eff256 / 1000.0);
+                cfg = PROF_CFG_256x128;
+            }
+            for (const Cand& c : cands) {
+                const double cost = cost_of(c.bm, c.bn, c.eff);
+                if (best == 0.0 || cost < best * 0.995) {
+                    best = cost;
+                    cfg = c.cfg;
+                }
+            }
+        }
+    }
+    // only BK = 32 exists for the 128 x 32 tile: C_in % 32 != 0 (possible only when forced, N > 32) takes 128 x 64
+    if (cfg == PROF_CFG_128x32 && p.C_in % 32 != 0) return PROF_CFG_128x64;
+    // a forced 256 x 128 on a layer it does not exist for, or a forced value that names no tile
+    if ((cfg == PROF_CFG_256x128 && !lin) || cfg >= PROF_NCFG) return PROF_CFG_128x128;
+    return cfg;
+}
+
 int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
-    // a K chunk never straddles two taps: C_in must be a multiple of the chunk width (16 for the BK = 16 variants, which
-    // exist for N > 32 without the ELU prologue - e.g. the 48-channel groups of the SSL positional convolution; 32 otherwise)
+    // a K chunk never straddles two taps: C_in must be a multiple of the chunk width (16 for the BK = 16 variants, which exist for N > 32 without the
+    // ELU prologue - e.g. the 48-channel groups of the SSL positional convolution; 32 otherwise)
     QA_REQUIRE(p.K % 16 == 0 && p.C_in % 16 == 0, "conv_gemm: K=%d / C_in=%d must be multiples of 16", p.K, p.C_in);
     QA_REQUIRE(p.C_in % 32 == 0 || (p.N > 32 && p.prologue != ACT_ELU),
                "conv_gemm: C_in=%d is not a multiple of 32 (only supported for N > 32 without the ELU prologue)", p.C_in);
@@ -687,82 +649,36 @@ int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
     QA_REQUIRE(((uintptr_t)p.x % 16) == 0 && ((uintptr_t)p.w % 16) == 0, "conv_gemm: x / w must be 16-byte aligned");
     if (p.M <= 0 || p.N <= 0) return QA_OK;
     QA_REQUIRE(ceil_div(p.M, 64) * ceil_div(p.N, 32) < (1LL << 31), "conv_gemm: grid too large");
-    const int forced = (int)knob(K_GEMM_CFG);
-    const int swz = (int)knob(K_GEMM_XCD);
+    auto al16 = [](const void* ptr) { return ((uintptr_t)ptr % 16) == 0; };
+    const bool vec_epi = p.N % 4 == 0 && p.ldy % 4 == 0 && al16(p.y) && (!p.bias || al16(p.bias)) && (!p.gamma || al16(p.gamma)) &&
+                         (!p.res || (p.ldr % 4 == 0 && al16(p.res))) && (!p.gate || (p.ldg % 4 == 0 && al16(p.gate)));
+    QA_REQUIRE(p.in_rep <= 1 || p.pad_mode == PAD_ZERO, "conv_gemm: in_rep needs zero padding");
+    const bool snake = p.act == ACT_SNAKE || p.post_act == ACT_SNAKE;
+    QA_REQUIRE((!snake && !p.y2) || (vec_epi && (!snake || (p.alpha && al16(p.alpha))) &&
+                                     (!p.y2 || (p.alpha2 && al16(p.alpha2) && al16(p.y2) && p.ldy2 % 4 == 0))),
+               "conv_gemm: Snake activation / second output need the float4 epilogue and 16-byte aligned alpha vectors");
+    QA_REQUIRE(p.dilation <= 1 || (p.pad_mode == PAD_ZERO && p.in_rep <= 1), "conv_gemm: dilation needs zero padding");
+    QA_REQUIRE(!p.am_dist || (vec_epi && p.am_idx && p.am_x2 && p.am_e2 && al16(p.am_e2) && p.am_ld >= (p.N + 31) / 32 && !p.y2),
+               "conv_gemm: the arg-min epilogue needs N %% 4 == 0, x2 / e2 / dist / idx and am_ld >= ceil(N / 32)");
+    QA_REQUIRE(!p.rope || (vec_epi && p.rope_hd % 4 == 0 && p.rope_n % 4 == 0 && p.rope_T > 0 && al16(p.rope)),
+               "conv_gemm: fused RoPE needs the float4 epilogue (N, strides, pointers multiples of 4 / 16 B)");
     ConvParams q = p;
-    q.xcd_swizzle = swz;
+    q.xcd_swizzle = (int)knob(K_GEMM_XCD);
     q.panel = (int)knob(K_GEMM_PANEL);
     // QA_GEMM_PRESPLIT: the weight's pre-split image, when a loaded store (or a caller) attached one that covers all N rows; only the
     // split-6 instances read it
     q.wp = knob(K_GEMM_PRESPLIT) != 0 ? weight_planes_find(p.w, (long long)p.N * p.K) : nullptr;
+    q.vec_epi = vec_epi;
     // frame / in_rep by multiply-high: exact for frame * in_rep < 2^32 (frames of one clip are < 2^31 / ldx)
-    auto al16 = [](const void* ptr) { return ((uintptr_t)ptr % 16) == 0; };
-    q.vec_epi = p.N % 4 == 0 && p.ldy % 4 == 0 && al16(p.y) && (!p.bias || al16(p.bias)) && (!p.gamma || al16(p.gamma)) &&
-                (!p.res || (p.ldr % 4 == 0 && al16(p.res))) && (!p.gate || (p.ldg % 4 == 0 && al16(p.gate)));
     q.rep_one = p.in_rep > 1 ? 0u : 1u;
     q.rep_magic = p.in_rep > 1 ? (unsigned)(((1ULL << 32) + p.in_rep - 1) / p.in_rep) : 0u;
-    QA_REQUIRE(p.in_rep <= 1 || p.pad_mode == PAD_ZERO, "conv_gemm: in_rep needs zero padding");
-    const bool snake = p.act == ACT_SNAKE || p.post_act == ACT_SNAKE;
-    QA_REQUIRE((!snake && !p.y2) || (q.vec_epi && (!snake || (p.alpha && al16(p.alpha))) &&
-                                     (!p.y2 || (p.alpha2 && al16(p.alpha2) && al16(p.y2) && p.ldy2 % 4 == 0))),
-               "conv_gemm: Snake activation / second output need the float4 epilogue and 16-byte aligned alpha vectors");
-    QA_REQUIRE(p.dilation <= 1 || (p.pad_mode == PAD_ZERO && p.in_rep <= 1), "conv_gemm: dilation needs zero padding");
-    QA_REQUIRE(!p.am_dist || (q.vec_epi && p.am_idx && p.am_x2 && p.am_e2 && al16(p.am_e2) && p.am_ld >= (p.N + 31) / 32 && !p.y2),
-               "conv_gemm: the arg-min epilogue needs N %% 4 == 0, x2 / e2 / dist / idx and am_ld >= ceil(N / 32)");
-    QA_REQUIRE(!p.rope || (q.vec_epi && p.rope_hd % 4 == 0 && p.rope_n % 4 == 0 && p.rope_T > 0 && al16(p.rope)),
-               "conv_gemm: fused RoPE needs the float4 epilogue (N, strides, pointers multiples of 4 / 16 B)");
-    int cfg;
-    if (forced >= 0) cfg = forced;
-    else if (p.N <= 32) cfg = PROF_CFG_128x32;
-    else if (p.N <= 64) cfg = PROF_CFG_128x64;
-    else {
-        // Tiles of one launch are dealt round-robin over 256 CUs (the co-resident workgroups of a CU share its matrix pipes), so the
-        // makespan is (tiles on the busiest CU) x (work per tile) / (sustained efficiency of the tile).  Round 4 adds the 64-row
-        // tiles: the aggregator stacks of H-Codec 1.5 (M = 9056 = 70.75 x 128) and the 4000-row SSL / BiCodec layers lose up to a
-        // third of the machine to tile quantisation with 128-row tiles (852 tiles of 128 x 128 = 3.33 per CU: a fourth round for a
-        // third of the CUs).  Efficiencies from the square 8192 x 4096 x 4096 problem, where every tile divides the grid evenly
-        // (profiles/r04_gemm_tile_sweep.txt: 133.1 / 121.5 / 121.6 / 115.9 TFLOP/s); ties go to the larger tile (less L2 traffic).
-        // Every configuration accumulates an output element over k in the same order, so this choice - which depends on M, i.e.
-        // on the batch size - never changes a bit (tests/test_kernels_gpu.py::test_conv_gemm_tile_configurations_are_bit_identical).
-        struct Cand { int cfg, bm, bn; double eff; };
-        static const Cand cands[] = {{PROF_CFG_128x128, 128, 128, 1.0}, {PROF_CFG_64x128, 64, 128, 0.914}, {PROF_CFG_128x64, 128, 64, 0.913},
-                                     {PROF_CFG_64x64, 64, 64, 0.871}};
-        double best = 0.0;
-        cfg = PROF_CFG_128x128;
-        const bool lin = knob(K_GEMM_LINEAR) != 0 && p.ksize == 1 && p.stride == 1 && p.pad_left == 0 && p.in_rep <= 1 && p.T_in == p.T_out &&
-                         p.dilation <= 1 && p.prologue != ACT_ELU;
-        const long long eff256 = knob(K_GEMM_256);  // 0: never; else the tile's efficiency relative to 128 x 128, in 1/1000
-        for (const Cand& c0 : cands) {
-            Cand c = c0;
-            if (&c0 == &cands[0] && eff256 > 0 && lin && p.M >= 8000 && p.N >= 1024) {  // try the 256 x 128 tile in front of the 128 x 128 one
-                const long long t256 = ceil_div(p.M, 256) * ceil_div(p.N, 128);
-                const double cost = (double)ceil_div(t256, 256) * 256 * 128 / (eff256 / 1000.0) * (t256 <= 256 ? 1.25 : 1.0);
-                best = cost;
-                cfg = PROF_CFG_256x128;
-            }
-            const long long tiles = ceil_div(p.M, c.bm) * ceil_div(p.N, c.bn);
-            // a launch that gives a CU at most ONE workgroup has nobody to cover that workgroup's barriers, prologue and epilogue: the
-            // 256-tile 4032 x 512 x 512 launch runs 8 % faster as 504 tiles of 64 x 64 although those need two rounds (same sweep)
-            const double cost = (double)ceil_div(tiles, 256) * c.bm * c.bn / c.eff * (tiles <= 256 ? 1.25 : 1.0);
-            if (best == 0.0 || cost < best * 0.995) {
-                best = cost;
-                cfg = c.cfg;
-            }
-        }
-    }
-    switch (cfg) {
-        case PROF_CFG_128x32:  // only BK = 32 exists for this tile: C_in % 32 != 0 (possible only when forced, N > 32) takes 128 x 64
-            if (p.C_in % 32 != 0) return launch_cfg<128, 64, 2, 2>(q, stream);
-            return launch_cfg<128, 32, 4, 1>(q, stream);
+
+    switch (choose_tile(p)) {
+        case PROF_CFG_128x32: return launch_cfg<128, 32, 4, 1>(q, stream);
         case PROF_CFG_128x64: return launch_cfg<128, 64, 2, 2>(q, stream);
         case PROF_CFG_64x128: return launch_cfg<64, 128, 1, 4>(q, stream);
         case PROF_CFG_64x64: return launch_cfg<64, 64, 2, 2>(q, stream);
-        case PROF_CFG_256x128: {
-            const bool lin = knob(K_GEMM_LINEAR) != 0 && p.ksize == 1 && p.stride == 1 && p.pad_left == 0 && p.in_rep <= 1 && p.T_in == p.T_out &&
-                             p.dilation <= 1 && p.prologue != ACT_ELU;
-            if (lin) return launch_cfg<256, 128, 2, 2>(q, stream);
-            return launch_cfg<128, 128, 2, 2>(q, stream);  // a forced 256 x 128 on a layer it does not exist for
-        }
+        case PROF_CFG_256x128: return launch_cfg<256, 128, 2, 2>(q, stream);
         default: return launch_cfg<128, 128, 2, 2>(q, stream);
     }
 }
