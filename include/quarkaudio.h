@@ -583,6 +583,50 @@ int qa_lm_enable_taps(qa_lm* lm, int on);
  * "logits.forced" [B, Lt, V] (the full-vocabulary teacher-forced logits). */
 int64_t qa_lm_tap(qa_lm* lm, const char* name, float* dst, int64_t cap, void* stream);
 
+/* ---- sessions: the Llama body over a cache the CALLER holds (CustomLlamaModel.llm_forward, llm.py:150-227) --------------------------
+ * A qa_lm_cache is device memory of its own - K and V as [layer][max_batch][max_len][hidden] fp32 plus the small buffers of the
+ * one-position step - so qa_lm_generate / qa_lm_score calls between two session calls on the same handle disturb nothing, and the
+ * reverse.  Several caches per handle are allowed; max_len <= 4096 (max_position_embeddings).  Its length and batch are HOST state:
+ * every call below that reads or changes them is refused under a caller's stream capture (a replay would repeat the captured
+ * positions).  One handle serves one stream at a time, as everywhere in this header.  qa_lm_destroy frees the caches the caller
+ * left; their pointers are invalid afterwards. */
+typedef struct qa_lm_cache qa_lm_cache;
+int qa_lm_cache_create(qa_lm* lm, int64_t max_batch, int64_t max_len, qa_lm_cache** out);
+void qa_lm_cache_destroy(qa_lm_cache* cache);
+int64_t qa_lm_cache_length(const qa_lm_cache* cache); /* positions held (DynamicCache.get_seq_length) */
+int64_t qa_lm_cache_batch(const qa_lm_cache* cache);  /* sequences held; 0 until the first forward call (and after a reset) */
+int qa_lm_cache_reset(qa_lm_cache* cache);            /* length 0, batch free again */
+/* DynamicCache.crop: keep the first `len` positions (0 <= len <= length).  Host state only: the rows behind are stale and invisible. */
+int qa_lm_cache_crop(qa_lm_cache* cache, int64_t len);
+/* Batch row j becomes old row idx[j] (idx: HOST int64 [n], 0 <= idx[j] < batch, n <= max_batch): DynamicCache.batch_select_indices,
+ * reorder_cache and batch_repeat_interleave in one entry, e.g. one TSE prefix run at B = 1 and repeated for the S segments of a file.
+ * Correct in place for any idx (permutations, repeats, growing and shrinking n); copies the first `length` positions of a row only.
+ * Asynchronous on `stream`, no allocation. */
+int qa_lm_cache_select(qa_lm_cache* cache, const int64_t* idx, int64_t n, void* stream);
+/* inputs_embeds fp32 [B, n, hidden] (device) run at positions length .. length + n - 1, causal over length + n keys; then length += n.
+ * last_hidden [B, n, hidden]: the final RMSNorm's output (last_hidden_state).  all_hidden: NULL, or [(n_layers + 1), B, n, hidden] =
+ * the input of every layer, then last_hidden (output_hidden_states, llm.py:192-220).  cache NULL is use_cache = False: positions
+ * 0 .. n - 1, nothing kept.  The first call on a cache fixes its batch B.  B above max_batch or length + n above max_len is an error
+ * that names the limit and leaves the cache as it was.
+ * n >= 2 runs the prefill kernels (implicit GEMM, flash attention with a query offset): a sequence's rows do not depend on the batch
+ * it sits in.  n = 1 runs the fused decode-step launches of qa_lm_generate on the caller's rows (more than 64 sequences: in groups of
+ * 64); there too a row does not depend on its batch.  The two paths sum in different orders, so one position fed as n = 1 and the
+ * same position inside a longer chunk agree to fp32 rounding, not bit for bit.
+ * Asynchronous on `stream`.  n = 1 with a cache allocates nothing; other shapes use a session workspace of the handle that grows to
+ * the largest B * n seen (growing waits for the device). */
+int qa_lm_forward(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int64_t B, int64_t n, float* last_hidden, float* all_hidden,
+                  void* stream);
+/* The submodules of LLM_SFT as device calls, so that a caller's decode loop never leaves the library.
+ * qa_lm_embed: out [n, hidden] = codec_embedding[ids[i]] (ids device int64, raw vocabulary ids).  The kernel clamps for memory safety;
+ *   check the ids with qa_codes_check first (the reference's nn.Embedding raises IndexError).
+ * qa_lm_head: logits [rows, width] = hidden [rows, hidden] x output_head[lo .. lo + width - 1]^T; `hidden` is last_hidden (norm applied).
+ * qa_lm_prompt: out [B, L, hidden] = [task, (enroll_sos, adapter(enroll_feats)), mix_sos, adapter(mix_feats)] (llm_sft.py:110-128),
+ *   L = 1 + (enroll_feats ? 1 + n_enroll : 0) + 1 + n_mix; arguments as qa_lm_generate. */
+int qa_lm_embed(qa_lm* lm, const int64_t* ids, int64_t n, float* out, void* stream);
+int qa_lm_head(qa_lm* lm, const float* hidden, int64_t rows, int32_t lo, int32_t width, float* logits, void* stream);
+int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                 float* out, void* stream);
+
 /* Kernel-level entry point of the sampler (parity / distribution tests): CustomLlamaModel.sample_logits (llm.py:253-288) on
  * logits [B, width] (row stride ld, device).  out_index int64 [B] (device).  do_sample = 0: arg-max (first maximum).
  * Synchronises `stream`. */

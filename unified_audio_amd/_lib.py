@@ -226,6 +226,17 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_lm_generate_cond_sampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                               C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_cache_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "qa_lm_cache_destroy": (None, [C.c_void_p]),
+    "qa_lm_cache_length": (C.c_int64, [C.c_void_p]),
+    "qa_lm_cache_batch": (C.c_int64, [C.c_void_p]),
+    "qa_lm_cache_reset": (C.c_int, [C.c_void_p]),
+    "qa_lm_cache_crop": (C.c_int, [C.c_void_p, C.c_int64]),
+    "qa_lm_cache_select": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p]),
+    "qa_lm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_lm_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "qa_lm_prompt": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "qa_lm_score_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }

@@ -110,6 +110,14 @@ int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, con
 int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
                          hipStream_t s);
 int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
+// one wave of independent row moves of a KV cache (qa_lm_cache_select), passed by value: row src[i] -> row dst[i], -1 = the spare row
+constexpr int KV_MOVES_MAX = 32;
+struct KvMoves {
+    int n;
+    int dst[KV_MOVES_MAX], src[KV_MOVES_MAX];
+};
+int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, int length, const KvMoves& mv,
+                        hipStream_t s);
 
 // ssl_kernels.hip
 size_t ssl_conv0_scratch_bytes(int B, int T1, int C0);

@@ -47,6 +47,23 @@ struct StepGraph {  // one captured decode step of a phase, replayable because e
     }
 };
 
+// A KV cache a caller holds across qa_lm_forward calls.  One device allocation of its own: K and V as
+// [layer][max_batch][max_len][hidden] fp32 (the row layout lm_body and the fused step use, with the layer stride fixed by max_batch so
+// that a batch select never moves a layer), one spare row per (layer, K / V) for the select's cycles, and the buffers of the n = 1 step.
+// Length and batch are HOST state.
+struct qa_lm_cache {
+    qa_lm* lm = nullptr;
+    int max_batch = 0, max_len = 0;
+    int B = 0;    // 0: not fixed yet (fresh or reset)
+    int len = 0;  // positions every row holds
+    char* mem = nullptr;
+    float *kc = nullptr, *vc = nullptr, *spare = nullptr;
+    float *x = nullptr, *q = nullptr, *u = nullptr, *att_part = nullptr, *mlp_part = nullptr;  // n = 1 step, min(max_batch, 64) rows
+    int* state = nullptr;
+    int att_tps = 0, S_att = 0;
+};
+void cache_free(qa_lm_cache* c);
+
 struct qa_lm : Handle {
     qa_lm_spec spec{};
     bool fused_ok = false;   // the shapes fit the fused decode step (required since r05: build_lm refuses a spec that does not tile)
@@ -63,6 +80,10 @@ struct qa_lm : Handle {
     const float *task_emb = nullptr, *enroll_sos = nullptr, *mix_sos = nullptr, *codec_emb = nullptr, *ones = nullptr,
                 *rope = nullptr;  // `ones`: unit RMSNorm weight (the learned ones are folded into the projections)
     ConvW adapter, head;
+    // the session entry points (qa_lm_forward / qa_lm_head) return and consume the final norm's OUTPUT, so they need the norm weight and the
+    // un-folded output_head that generate's fused head never reads
+    const float* norm_w = nullptr;
+    ConvW head_raw;
     std::vector<LMLayer> layers;
     // test hook (qa_lm_enable_taps): the slice logits of every decode step, in an allocation of their own (never the workspace, so
     // turning taps on cannot move a buffer of the step); tap_n: elements of logits.global / logits.semantic of the last call (-1: none)
@@ -73,7 +94,13 @@ struct qa_lm : Handle {
     Workspace score_ws;
     Workspace score_tap;  // logits.forced [B][Lt][V] of the last score call (taps on)
     int64_t score_tap_n = -1;
+    // qa_lm_forward (n >= 2 chunks, cache-less calls), qa_lm_prompt: a third workspace, so that a session never moves a buffer of generate
+    // or score; the KV caches themselves are allocations of their own (qa_lm_cache)
+    Workspace sess_ws;
+    Ctx sess_ctx;
+    std::vector<qa_lm_cache*> caches;  // live caches of this handle (qa_lm_destroy frees the ones the caller left)
     ~qa_lm() {
+        while (!caches.empty()) cache_free(caches.back());  // unregisters itself
         for (StepGraph& g : graphs) g.reset();  // before the buffers they point into
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
         for (hipStream_t st : chain_streams) (void)hipStreamDestroy(st);
@@ -205,6 +232,9 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
         }
     }
     L.raw(&lm->rope, cs);
+    // behind everything generate and score read: their weights keep the offsets they had
+    L.vec(&lm->norm_w, "norm.weight", d);
+    L.conv(&lm->head_raw, "output_head", V, d, 1, false);
     return L.upload();
 }
 
@@ -217,6 +247,14 @@ struct LMBuffers {
     int *pidx, *state;
     long long *ids_g, *ids_s;
     int cap, S_att, att_tps;  // cache capacity, the attention's split count of a replayed step and 16-key tiles per split
+    size_t layer_stride;      // floats between two layers of kc / vc; 0: B * cap * d (generate's arena); a qa_lm_cache: max_batch * max_len * d
+};
+
+// what a session step (qa_lm_forward, n = 1) hooks onto the layer loop of the fused step; generate passes none
+struct StepIO {
+    const float* x_in = nullptr;  // layer 0 reads these rows [B, d] (and adds them as its residual) instead of gathering codec_embedding[tok]
+    float* hidden = nullptr;      // entry i <- the input of layer i, B rows each, entries `hidden_stride` floats apart (nullptr: no copies)
+    size_t hidden_stride = 0;
 };
 
 struct SampleCfg {
@@ -234,16 +272,20 @@ struct SampleCfg {
 // one pass of the Llama body over `n` new positions per sequence, positions pos0..pos0+n-1 (the prefill)
 // one_cache: every layer writes its keys / values into the same [B, max_len, d] pair (scoring: nothing reads a layer's cache after the
 // layer's own attention)
-int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len, bool skip_last_mlp, bool one_cache = false) {
+// hidden (qa_lm_forward with all_hidden): entry i [B, n, d] <- the input of layer i
+int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len, bool skip_last_mlp, bool one_cache = false,
+            float* hidden = nullptr) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H;
     const int64_t rows = (int64_t)B * n;
     const float scale = 1.0f / std::sqrt((float)hd);
-    const size_t cache_stride = one_cache ? 0 : (size_t)B * max_len * d;
+    const size_t cache_stride = one_cache ? 0 : b.layer_stride ? b.layer_stride : (size_t)B * max_len * d;
     for (int i = 0; i < sp.n_layers; ++i) {
         const LMLayer& L = lm->layers[i];
         float* kc = b.kc + i * cache_stride;
         float* vc = b.vc + i * cache_stride;
+        if (hidden && !c.dry)
+            QA_HIP(hipMemcpyAsync(hidden + (size_t)i * rows * d, b.x, sizeof(float) * rows * d, hipMemcpyDeviceToDevice, c.stream));
         const bool last = skip_last_mlp && i == sp.n_layers - 1;  // prefill: only the KV cache of the last layer is consumed
         QA_TRY(rmsnorm_op(c, b.x, lm->ones, b.hn, rows, d, sp.rms_eps));
         QA_TRY(linear_op(c, b.hn, rows, L.qkv, b.qkv));
@@ -262,15 +304,14 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
 // ONE decode step as 5 launches per layer + 2 (lm_decode.hip).  Everything step-dependent (position, ids column, RNG step) is read
 // from b.state on the device, so the launch arguments are identical for every step of a phase: the sequence can be captured once
 // into a hipGraph and replayed.
-// tap (taps on): [B][tap_cols][width] logits of the phase's steps for these B rows, column = the step's col
-int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long long* ids, int ids_ld, int keep, const SampleCfg& sc,
-               hipStream_t s, int pos, int col,  // pos / col >= 0: host-driven loop; -1: read from the device state (captured step)
-               float* tap, int tap_cols) {
+// fused_layers: the layers of the step (launches 1 - 5); [lo, lo + width): the head slice the last layer's prefetch plane warms
+// (width 0: no head follows - a session step, which ends in the final RMSNorm instead)
+int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStream_t s, int pos, const StepIO& io) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H, I = sp.intermediate;
     const float scale = 1.0f / std::sqrt((float)hd);
     const long long kv_bstride = (long long)b.cap * d;
-    const size_t cache_stride = (size_t)B * b.cap * d;
+    const size_t cache_stride = b.layer_stride ? b.layer_stride : (size_t)B * b.cap * d;
     // key split of the attention launch: split sp owns the fixed tile range [sp, sp + 1) * b.att_tps (lm_attn_kernel); a host-driven
     // step launches the splits that hold keys, a replayed one all of them (the others write identity records): same bits either way
     const int S_att = pos >= 0 ? std::max(1, (int)ceil_div(ceil_div(pos + 1, 16), b.att_tps)) : b.S_att;
@@ -291,6 +332,8 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         const LMLayer& L = lm->layers[i];
         float* kc = b.kc + i * cache_stride;
         float* vc = b.vc + i * cache_stride;
+        if (io.hidden)
+            QA_HIP(hipMemcpyAsync(io.hidden + i * io.hidden_stride, i == 0 ? io.x_in : b.x, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
         GemvArgs a{};
         a.M = B; a.rms_eps = sp.rms_eps; a.state = b.state; a.pos = pos; a.H = H; a.hd = hd; a.d = d;
         // o_proj's tile width (computed here: the qkv launch may prefetch its weights)
@@ -302,7 +345,8 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         // 1. RMSNorm + QKV + RoPE + cache append; layer 0 gathers its input rows from codec_embedding (llm_sft.py:140,169)
         GemvArgs q = a;
         q.x = b.x; q.ldx = d;
-        if (i == 0) { q.tok = b.tok; q.table = lm->codec_emb; }
+        if (i == 0 && io.x_in) q.x = io.x_in;
+        else if (i == 0) { q.tok = b.tok; q.table = lm->codec_emb; }
         q.w = L.qkv_dec; q.N = 3 * d; q.K = d;
         q.rope = lm->rope; q.q = b.q; q.kc = kc; q.vc = vc; q.kv_bstride = kv_bstride;
         PfArgs qpf{};
@@ -314,7 +358,8 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         GemvArgs o = a;
         o.att_part = b.att_part; o.S = S_att;
         o.w = L.o.w; o.N = d; o.K = d; o.ldx = d;
-        if (i == 0) { o.res_tok = b.tok; o.res_table = lm->codec_emb; } else { o.res = b.x; }
+        if (i == 0 && io.x_in) { o.res = io.x_in; }
+        else if (i == 0) { o.res_tok = b.tok; o.res_table = lm->codec_emb; } else { o.res = b.x; }
         o.ldr = d; o.y = b.x; o.ldy = d;
         // tile width by the batch: the 8-row groups (lm_gemv4_kernel R8) hold a workgroup's pull of attention partials at 52 KB whatever the
         // batch, but every column tile re-reads and re-merges the partials of its rows - so the launch keeps ~256 workgroups: 4 columns x 2
@@ -330,7 +375,7 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
             PfArgs gpf{};
             if (pfk & 4) {
                 if (i + 1 < sp.n_layers) pf_region(gpf, 0, lm->layers[i + 1].qkv_dec, (long long)lm->nt_qkv * d * 4, 3 * d / lm->nt_qkv);
-                else pf_region(gpf, 0, lm->head.w + (size_t)lo * d, (long long)head_nt(width) * d * 4, width / head_nt(width));
+                else if (width > 0) pf_region(gpf, 0, lm->head.w + (size_t)lo * d, (long long)head_nt(width) * d * 4, width / head_nt(width));
             }
             QA_TRY(launch_lm_mlp(g, I, lm->mlp_ac, L.down_dec, b.mlp_part, b.x, d, b.x, d, s, &gpf));
             continue;
@@ -341,6 +386,17 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         dn.x = b.u; dn.ldx = I; dn.w = L.down.w; dn.N = d; dn.K = I; dn.res = b.x; dn.ldr = d; dn.y = b.x; dn.ldy = d;
         QA_TRY(launch_lm_gemv(dn, GM_RESID, lm->nt_down, s));
     }
+    return QA_OK;
+}
+
+// the whole step of generate: the layers, then head and pick / sample (launches 6 - 7)
+// tap (taps on): [B][tap_cols][width] logits of the phase's steps for these B rows, column = the step's col
+int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long long* ids, int ids_ld, int keep, const SampleCfg& sc,
+               hipStream_t s, int pos, int col,  // pos / col >= 0: host-driven loop; -1: read from the device state (captured step)
+               float* tap, int tap_cols) {
+    const qa_lm_spec& sp = lm->spec;
+    const int d = sp.hidden, H = sp.n_heads, hd = d / H;
+    QA_TRY(fused_layers(lm, b, B, lo, width, s, pos, StepIO()));
     // 6. final RMSNorm (weight folded into output_head) + the rows of output_head inside the active vocabulary slice (the range
     //    mask of llm_sft.py:150-153 / :180-182 sets everything else to -inf) + per-tile arg-max
     const int nt = head_nt(width);
@@ -349,7 +405,11 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
     hg.x = b.x; hg.ldx = d; hg.w = lm->head.w + (size_t)lo * d; hg.N = width; hg.K = d;
     hg.pmax = b.pmax; hg.pidx = b.pidx; hg.logits = (sc.do_sample || tap) ? b.logits : nullptr; hg.ldl = width;
     PfArgs hpf{};
-    if (pfk & 8) pf_region(hpf, 0, lm->layers[0].qkv_dec, (long long)lm->nt_qkv * d * 4, 3 * d / lm->nt_qkv);
+    if (knob(K_LM_PF) & 8) {  // the next step's first weights (QA_LM_PF, as in fused_layers)
+        hpf.p[0] = reinterpret_cast<const char*>(lm->layers[0].qkv_dec);
+        hpf.tile_bytes[0] = (long long)lm->nt_qkv * d * 4;
+        hpf.n_tiles[0] = 3 * d / lm->nt_qkv;
+    }
     QA_TRY(launch_lm_gemv(hg, GM_HEAD, nt, s, &hpf));
     if (tap) QA_TRY(launch_lm_tap(b.logits, width, B, tap, tap_cols, b.state, col, s));
     // 7. next token
@@ -668,9 +728,374 @@ int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
     return grow_step_buffer(lm, lm->tap_buf, sizeof(float) * n);
 }
 
+
+// ---- sessions: qa_lm_forward over a caller-held qa_lm_cache (CustomLlamaModel.llm_forward, llm.py:150-227)
+
+// Length and batch of a cache are host state, so a session call cannot be recorded into a caller's graph: a replay would run with the
+// positions of the capture.  Refused, with the reason.
+int refuse_capture(const char* fn, hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+    QA_REQUIRE(cs != hipStreamCaptureStatusActive,
+               "%s: refused under a stream capture - the cache length is host state, a replayed graph would repeat the captured positions", fn);
+    return QA_OK;
+}
+
+// the attention's key split of the n = 1 step, from the capacity alone (as chain_alloc)
+void att_split_of(const qa_lm* lm, int cap, int* tps, int* S) {
+    const int cap_tiles = (int)ceil_div(cap, 16);
+    *tps = std::max(lm->att_split / 16, (int)ceil_div(cap_tiles, 4));
+    *S = (int)ceil_div(cap_tiles, *tps);
+}
+
+struct ForwardArgs {
+    qa_lm_cache* cache;  // nullptr: use_cache = False, the keys live in the call's workspace
+    const float* x;      // [B, n, d]
+    int B, n;
+    float *last_hidden, *all_hidden;
+};
+
+int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
+    const qa_lm_spec& sp = lm->spec;
+    const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads, B = a.B, n = a.n;
+    const int pos0 = a.cache ? a.cache->len : 0;
+    const int64_t rows = (int64_t)B * n;
+    const bool step = n == 1 && lm->fused_ok;
+    LMBuffers b{};
+    if (a.cache) {
+        b.kc = a.cache->kc;
+        b.vc = a.cache->vc;
+        b.cap = a.cache->max_len;
+        b.layer_stride = (size_t)a.cache->max_batch * a.cache->max_len * d;
+        b.att_tps = a.cache->att_tps;
+        b.S_att = a.cache->S_att;
+    } else {  // every layer keeps its own keys here too: the n = 1 step appends to layer i's cache before layer i's attention reads it
+        b.cap = (int)round_up(n, 16);
+        b.kc = c.arena.alloc<float>((size_t)sp.n_layers * B * b.cap * d);
+        b.vc = c.arena.alloc<float>((size_t)sp.n_layers * B * b.cap * d);
+        att_split_of(lm, b.cap, &b.att_tps, &b.S_att);
+    }
+    const size_t hs = (size_t)rows * d;  // one entry of all_hidden
+    if (!step) {
+        b.x = c.arena.alloc<float>(rows * d);
+        b.hn = c.arena.alloc<float>(rows * d);
+        b.qkv = c.arena.alloc<float>(rows * 3 * d);
+        b.att = c.arena.alloc<float>(rows * d);
+        b.g = c.arena.alloc<float>(rows * I);
+        b.u = c.arena.alloc<float>(rows * I);
+        if (c.dry) return QA_OK;  // real-pass-only remainder
+        QA_HIP(hipMemcpyAsync(b.x, a.x, sizeof(float) * hs, hipMemcpyDeviceToDevice, c.stream));
+        QA_TRY(lm_body(lm, c, b, B, n, pos0, b.cap, false, false, a.all_hidden));
+        QA_TRY(launch_rmsnorm(b.x, lm->norm_w, a.last_hidden, rows, d, sp.rms_eps, c.stream));
+    } else {
+        // the fused step's launches on the caller's rows, at most LM_MAX_ROWS of them per pass (a row's arithmetic does not know its group)
+        const int GB = std::min(B, LM_MAX_ROWS);
+        if (a.cache) {
+            b.x = a.cache->x; b.q = a.cache->q; b.u = a.cache->u; b.att_part = a.cache->att_part; b.mlp_part = a.cache->mlp_part;
+            b.state = a.cache->state;
+        } else {
+            b.x = c.arena.alloc<float>((size_t)GB * d);
+            b.q = c.arena.alloc<float>((size_t)GB * d);
+            b.u = c.arena.alloc<float>((size_t)GB * I);
+            b.att_part = c.arena.alloc<float>((size_t)GB * H * b.S_att * (d / H + 4));
+            b.mlp_part = c.arena.alloc<float>(lm->mlp_fused ? (size_t)(I / lm->mlp_ac) * 32 * ceil_div(GB, 32) * d : 0);
+            b.state = c.arena.alloc<int>(ST_WORDS);  // never read: the position is a launch argument
+        }
+        if (c.dry) return QA_OK;  // real-pass-only remainder
+        const size_t row_stride = (size_t)b.cap * d;
+        for (int b0 = 0; b0 < B; b0 += GB) {
+            const int gb = std::min(GB, B - b0);
+            LMBuffers g = b;
+            g.kc = b.kc + b0 * row_stride;
+            g.vc = b.vc + b0 * row_stride;
+            if (!g.layer_stride) g.layer_stride = (size_t)B * b.cap * d;  // the whole call's layer, not the group's
+            StepIO io;
+            io.x_in = a.x + (size_t)b0 * d;
+            if (a.all_hidden) {
+                io.hidden = a.all_hidden + (size_t)b0 * d;
+                io.hidden_stride = hs;
+            }
+            QA_TRY(fused_layers(lm, g, gb, 0, 0, c.stream, pos0, io));
+            QA_TRY(launch_rmsnorm(b.x, lm->norm_w, a.last_hidden + (size_t)b0 * d, gb, d, sp.rms_eps, c.stream));
+        }
+    }
+    if (a.all_hidden)  // llm.py:216-220: the last entry is the final norm's output
+        QA_HIP(hipMemcpyAsync(a.all_hidden + (size_t)sp.n_layers * hs, a.last_hidden, sizeof(float) * hs, hipMemcpyDeviceToDevice, c.stream));
+    return QA_OK;
+}
+
+// plan + run on the session workspace; growing it waits for the device (earlier session calls may still read the old buffer)
+template <typename G>
+int run_session(qa_lm* lm, hipStream_t s, G&& graph) {
+    Ctx& c = lm->sess_ctx;
+    c.gemm_fp32 = true;  // as generate and score: the fp32 chain everywhere
+    c.att_fp32 = true;
+    QA_TRY(plan(lm->device, s, c, lm->sess_ws, graph, [&](size_t) -> int {
+        QA_HIP(hipDeviceSynchronize());
+        return QA_OK;
+    }));
+    return graph();
+}
+
+// qa_lm_cache_select as waves of row moves.  Row j must become old row idx[j].  A move may run once nothing still pending reads its
+// destination, so the moves are emitted leaves first; what is left then is disjoint cycles, each opened by parking one row in the
+// cache's spare row (-1).  Consecutive moves that neither read nor overwrite one another's rows share a launch.
+void plan_cache_moves(const int64_t* idx, int n, int rows, std::vector<KvMoves>* waves) {
+    std::vector<int> src(n), readers(rows + 1, 0);  // readers[r + 1]: pending moves that read row r (r = -1: the spare row)
+    std::vector<char> pending(n, 0);
+    int left = 0;
+    for (int j = 0; j < n; ++j) {
+        src[j] = (int)idx[j];
+        if (src[j] != j) {
+            pending[j] = 1;
+            ++readers[src[j] + 1];
+            ++left;
+        }
+    }
+    std::vector<std::pair<int, int>> order;  // (dst, src)
+    auto emit_free = [&] {
+        for (bool progress = true; progress;) {
+            progress = false;
+            for (int j = 0; j < n; ++j)
+                if (pending[j] && readers[j + 1] == 0) {
+                    order.push_back({j, src[j]});
+                    --readers[src[j] + 1];
+                    pending[j] = 0;
+                    --left;
+                    progress = true;
+                }
+        }
+    };
+    emit_free();
+    while (left > 0) {  // only cycles are left: park one row of a cycle, let its reader take the spare row instead
+        int j = 0;
+        while (!pending[j]) ++j;
+        order.push_back({-1, j});
+        for (int k = 0; k < n; ++k)
+            if (pending[k] && src[k] == j) {
+                src[k] = -1;
+                ++readers[0];
+            }
+        readers[j + 1] = 0;
+        emit_free();
+    }
+    KvMoves w{};
+    std::vector<char> rd(rows + 1, 0), wr(rows + 1, 0);
+    auto flush = [&] {
+        if (w.n) waves->push_back(w);
+        w = KvMoves{};
+        std::fill(rd.begin(), rd.end(), 0);
+        std::fill(wr.begin(), wr.end(), 0);
+    };
+    for (const auto& m : order) {
+        if (w.n == KV_MOVES_MAX || wr[m.second + 1] || rd[m.first + 1] || wr[m.first + 1]) flush();
+        w.dst[w.n] = m.first;
+        w.src[w.n] = m.second;
+        ++w.n;
+        wr[m.first + 1] = 1;
+        rd[m.second + 1] = 1;
+    }
+    flush();
+}
+
 }  // namespace
 
+void cache_free(qa_lm_cache* c) {
+    if (!c) return;
+    if (c->lm) {
+        auto& v = c->lm->caches;
+        v.erase(std::remove(v.begin(), v.end(), c), v.end());
+    }
+    if (c->mem) (void)hipFree(c->mem);  // waits for the work that still reads it
+    delete c;
+}
+
 extern "C" {
+
+int qa_lm_cache_create(qa_lm* lm, int64_t max_batch, int64_t max_len, qa_lm_cache** out) {
+    if (!lm || !out) {
+        set_error("qa_lm_cache_create: null argument");
+        return QA_ERR_INVALID;
+    }
+    *out = nullptr;
+    QA_REQUIRE(max_batch >= 1 && max_batch <= (1 << 16), "qa_lm_cache_create: max_batch %lld outside [1, 65536]", (long long)max_batch);
+    QA_REQUIRE(max_len >= 1 && max_len <= LM_MAX_POS, "qa_lm_cache_create: max_len %lld outside [1, %d] (max_position_embeddings)",
+               (long long)max_len, LM_MAX_POS);
+    QA_HIP(hipSetDevice(lm->device));
+    const qa_lm_spec& sp = lm->spec;
+    const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads;
+    std::unique_ptr<qa_lm_cache> c(new qa_lm_cache());
+    c->max_batch = (int)max_batch;
+    c->max_len = (int)max_len;
+    att_split_of(lm, c->max_len, &c->att_tps, &c->S_att);
+    const int GB = (int)std::min<int64_t>(max_batch, LM_MAX_ROWS);
+    Arena layout;  // sizes the one allocation, then places the buffers in it
+    auto place = [&] {
+        const size_t plane = (size_t)sp.n_layers * max_batch * max_len * d;
+        c->kc = layout.alloc<float>(plane);
+        c->vc = layout.alloc<float>(plane);
+        c->spare = layout.alloc<float>((size_t)sp.n_layers * 2 * max_len * d);
+        c->x = layout.alloc<float>((size_t)GB * d);
+        c->q = layout.alloc<float>((size_t)GB * d);
+        c->u = layout.alloc<float>((size_t)GB * I);
+        c->att_part = layout.alloc<float>((size_t)GB * H * c->S_att * (d / H + 4));
+        c->mlp_part = layout.alloc<float>(lm->mlp_fused ? (size_t)(I / lm->mlp_ac) * 32 * ceil_div(GB, 32) * d : 0);
+        c->state = layout.alloc<int>(ST_WORDS);
+    };
+    layout.begin(nullptr, 0);
+    place();
+    const size_t bytes = layout.peak();
+    if (hipMalloc(reinterpret_cast<void**>(&c->mem), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->mem = nullptr;
+        set_error("qa_lm_cache_create: no device memory for a cache of %lld rows x %lld positions (%zu bytes)", (long long)max_batch,
+                  (long long)max_len, bytes);
+        return QA_ERR_HIP;
+    }
+    layout.begin(c->mem, bytes);
+    place();
+    c->lm = lm;
+    lm->caches.push_back(c.get());
+    *out = c.release();
+    return QA_OK;
+}
+
+void qa_lm_cache_destroy(qa_lm_cache* cache) {
+    if (!cache) return;
+    if (cache->lm) (void)hipSetDevice(cache->lm->device);
+    cache_free(cache);
+}
+
+int64_t qa_lm_cache_length(const qa_lm_cache* cache) { return cache ? cache->len : 0; }
+int64_t qa_lm_cache_batch(const qa_lm_cache* cache) { return cache ? cache->B : 0; }
+
+int qa_lm_cache_reset(qa_lm_cache* cache) {
+    if (!cache) {
+        set_error("qa_lm_cache_reset: null cache");
+        return QA_ERR_INVALID;
+    }
+    cache->len = 0;
+    cache->B = 0;
+    return QA_OK;
+}
+
+int qa_lm_cache_crop(qa_lm_cache* cache, int64_t len) {
+    if (!cache) {
+        set_error("qa_lm_cache_crop: null cache");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(len >= 0 && len <= cache->len, "qa_lm_cache_crop: length %lld outside [0, %d] (the cache's current length)", (long long)len,
+               cache->len);
+    cache->len = (int)len;  // the rows behind it are stale and invisible: every reader stops at the length
+    return QA_OK;
+}
+
+int qa_lm_cache_select(qa_lm_cache* cache, const int64_t* idx, int64_t n, void* stream) {
+    if (!cache || !idx) {
+        set_error("qa_lm_cache_select: null argument");
+        return QA_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture("qa_lm_cache_select", s));
+    QA_REQUIRE(cache->B > 0, "qa_lm_cache_select: the cache has no batch yet (no qa_lm_forward call since create / reset)");
+    QA_REQUIRE(n >= 1 && n <= cache->max_batch, "qa_lm_cache_select: %lld rows requested, the cache was created with max_batch %d", (long long)n,
+               cache->max_batch);
+    for (int64_t j = 0; j < n; ++j)
+        QA_REQUIRE(idx[j] >= 0 && idx[j] < cache->B, "qa_lm_cache_select: idx[%lld] = %lld outside the cache's %d rows (IndexError in the reference)",
+                   (long long)j, (long long)idx[j], cache->B);
+    qa_lm* lm = cache->lm;
+    QA_HIP(hipSetDevice(lm->device));
+    if (cache->len > 0) {
+        std::vector<KvMoves> waves;
+        plan_cache_moves(idx, (int)n, std::max(cache->B, (int)n), &waves);
+        for (const KvMoves& w : waves)
+            QA_TRY(launch_kv_row_moves(cache->kc, cache->vc, cache->spare, lm->spec.n_layers, cache->max_batch, cache->max_len, lm->spec.hidden,
+                                       cache->len, w, s));
+    }
+    cache->B = (int)n;
+    return QA_OK;
+}
+
+int qa_lm_forward(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int64_t B, int64_t n, float* last_hidden, float* all_hidden,
+                  void* stream) {
+    if (!lm || !inputs_embeds || !last_hidden) {
+        set_error("qa_lm_forward: null argument");
+        return QA_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture("qa_lm_forward", s));
+    QA_REQUIRE(B >= 1 && n >= 1 && B <= (1 << 16), "qa_lm_forward: bad shape B = %lld, n = %lld", (long long)B, (long long)n);
+    if (cache) {
+        QA_REQUIRE(cache->lm == lm, "qa_lm_forward: the cache belongs to another qa_lm handle");
+        QA_REQUIRE(B <= cache->max_batch, "qa_lm_forward: B = %lld exceeds the cache's max_batch %d", (long long)B, cache->max_batch);
+        QA_REQUIRE(cache->B == 0 || B == cache->B, "qa_lm_forward: B = %lld, but the cache holds %d sequences (the first call fixes the batch; "
+                   "qa_lm_cache_select changes it, qa_lm_cache_reset frees it)", (long long)B, cache->B);
+        QA_REQUIRE(cache->len + n <= cache->max_len, "qa_lm_forward: %d cached + %lld new positions exceed the cache's max_len %d", cache->len,
+                   (long long)n, cache->max_len);
+    } else {
+        QA_REQUIRE(n <= LM_MAX_POS, "qa_lm_forward: %lld positions exceed max_position_embeddings %d", (long long)n, LM_MAX_POS);
+    }
+    const ForwardArgs a{cache, inputs_embeds, (int)B, (int)n, last_hidden, all_hidden};
+    QA_TRY(run_session(lm, s, [&] { return forward_graph(lm, lm->sess_ctx, a); }));
+    if (cache) {
+        cache->B = (int)B;
+        cache->len += (int)n;
+    }
+    return QA_OK;
+}
+
+int qa_lm_embed(qa_lm* lm, const int64_t* ids, int64_t n, float* out, void* stream) {
+    if (!lm || !ids || !out) {
+        set_error("qa_lm_embed: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(n >= 0, "qa_lm_embed: bad count %lld", (long long)n);
+    QA_HIP(hipSetDevice(lm->device));
+    return launch_gather_rows(reinterpret_cast<const long long*>(ids), lm->codec_emb, out, n, vocab_of(lm->spec), lm->spec.hidden,
+                              static_cast<hipStream_t>(stream));
+}
+
+int qa_lm_head(qa_lm* lm, const float* hidden, int64_t rows, int32_t lo, int32_t width, float* logits, void* stream) {
+    if (!lm || !hidden || !logits) {
+        set_error("qa_lm_head: null argument");
+        return QA_ERR_INVALID;
+    }
+    const int V = vocab_of(lm->spec);
+    QA_REQUIRE(rows >= 1 && rows <= (1 << 24), "qa_lm_head: bad row count %lld", (long long)rows);
+    QA_REQUIRE(lo >= 0 && width >= 1 && (int64_t)lo + width <= V, "qa_lm_head: slice [%d, %d + %d) outside the vocabulary of %d", lo, lo, width, V);
+    QA_HIP(hipSetDevice(lm->device));
+    ConvW w = lm->head_raw;  // rows lo .. lo + width - 1 of output_head
+    w.w += (size_t)lo * w.C_in;
+    w.N = w.algo_n = width;
+    Ctx c;
+    c.stream = static_cast<hipStream_t>(stream);
+    c.gemm_fp32 = true;
+    return linear_op(c, hidden, rows, w, logits);
+}
+
+int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                 float* out, void* stream) {
+    if (!lm || !mix_feats || !out) {
+        set_error("qa_lm_prompt: null argument");
+        return QA_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture("qa_lm_prompt", s));  // the adapters' scratch lives in the session workspace, which may have to grow
+    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_prompt: task %d out of range (KeyError in the reference)", task);
+    QA_REQUIRE(B >= 1 && n_mix >= 1 && n_mix <= LM_MAX_POS && B <= (1 << 16), "qa_lm_prompt: bad shape");
+    QA_REQUIRE(!enroll_feats || (n_enroll >= 1 && n_enroll <= LM_MAX_POS), "qa_lm_prompt: enrollment given with no frames");
+    const int d = lm->spec.hidden, Ne = enroll_feats ? (int)n_enroll : 0, Nm = (int)n_mix;
+    Ctx& c = lm->sess_ctx;
+    return run_session(lm, s, [&]() -> int {
+        float* emix = c.arena.alloc<float>((size_t)B * Nm * d);
+        float* eenr = enroll_feats ? c.arena.alloc<float>((size_t)B * Ne * d) : nullptr;
+        QA_TRY(linear_op(c, mix_feats, B * Nm, lm->adapter, emix));
+        if (enroll_feats) QA_TRY(linear_op(c, enroll_feats, B * Ne, lm->adapter, eenr));
+        QA_RUN(c, launch_assemble_prompt(out, lm->task_emb + (size_t)task * d, enroll_feats ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix,
+                                         (int)B, Ne, Nm, d, c.stream));
+        return QA_OK;
+    });
+}
 
 int qa_lm_create(qa_lm** out, const qa_lm_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
     if (!out || !spec || !tensors) {

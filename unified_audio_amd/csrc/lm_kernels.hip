@@ -394,5 +394,35 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
     return QA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// qa_lm_cache_select: one WAVE of row moves of a KV cache [layer][max_batch][max_len][d] (K and V), the first `n4` float4 of a row each
+// (length * d floats: stale positions behind the cache length are never copied).  Grid: x covers a row, y = move, z = layer * 2 + {K, V}.
+// Row -1 is the cache's spare row [layer][K / V][max_len][d] (lm.cpp plan_cache_moves: it breaks a permutation cycle).  The moves of one
+// launch never read a row another move of the launch writes, so the launch is in-place safe; the host orders the waves on the stream.
+// Rows are whole 16-byte multiples (d % 32 == 0) and 16-byte aligned.
+__global__ __launch_bounds__(256) void kv_row_moves_kernel(float4* __restrict__ kc, float4* __restrict__ vc, float4* __restrict__ spare,
+                                                           long long layer4, long long row4, long long n4, const KvMoves mv) {
+    const int layer = blockIdx.z >> 1, kv = blockIdx.z & 1;
+    const int dst = mv.dst[blockIdx.y], src = mv.src[blockIdx.y];
+    float4* base = (kv ? vc : kc) + layer * layer4;
+    float4* sp = spare + (long long)blockIdx.z * row4;
+    const float4* from = src < 0 ? sp : base + src * row4;
+    float4* to = dst < 0 ? sp : base + dst * row4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) to[i] = from[i];
+}
+int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, int length, const KvMoves& mv,
+                        hipStream_t s) {
+    QA_REQUIRE(mv.n >= 1 && mv.n <= KV_MOVES_MAX && d % 4 == 0 && length >= 1 && length <= max_len, "kv_row_moves: bad launch");
+    for (int i = 0; i < mv.n; ++i)
+        QA_REQUIRE(mv.dst[i] >= -1 && mv.dst[i] < max_batch && mv.src[i] >= -1 && mv.src[i] < max_batch && mv.dst[i] != mv.src[i],
+                   "kv_row_moves: move %d -> %d outside the cache's %d rows", mv.src[i], mv.dst[i], max_batch);
+    const long long row4 = (long long)max_len * d / 4, n4 = (long long)length * d / 4;
+    // ~8 float4 per thread: enough workgroups to fill the device at one move, few enough that the tail is short
+    const unsigned gx = (unsigned)std::min<long long>(ceil_div(n4, 256 * 8), 1024);
+    hipLaunchKernelGGL(kv_row_moves_kernel, dim3(gx, (unsigned)mv.n, (unsigned)(2 * n_layers)), dim3(256), 0, s, reinterpret_cast<float4*>(kc),
+                       reinterpret_cast<float4*>(vc), reinterpret_cast<float4*>(spare), (long long)max_batch * row4, row4, n4, mv);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
 
 }  // namespace qa

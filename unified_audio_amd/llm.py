@@ -9,13 +9,89 @@ Weights come in the reference's key layout (the Lightning checkpoint's `dnn.*` e
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+import weakref
+from types import SimpleNamespace
+from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import _lib
 
 DEFAULT_TASK_MAP = {"se": 0, "tse": 1, "rtse": 2}  # conf/config.yaml:132-136
+
+
+MAX_POSITION_EMBEDDINGS = 4096  # conf/config.yaml:146
+
+
+class KVCache:
+    """A key / value cache held across llm_forward calls (qa_lm_cache): what transformers' DynamicCache is to the reference's
+    llm_forward, with a fixed capacity.  Device memory of its own; its length and batch are host state.  Freed with this object, or
+    with the model's handle, whichever goes first."""
+
+    def __init__(self, lm, max_batch: int, max_len: int = MAX_POSITION_EMBEDDINGS):
+        self._lm = lm._lm if isinstance(lm, CustomLlamaModel) else lm
+        if not self._lm._handle.value:
+            raise _lib.QuarkAudioError(-3, "KVCache: the model has no weights: call load_state_dict first")
+        self._lib = self._lm._lib
+        self._handle = C.c_void_p()
+        _lib.check(self._lib.qa_lm_cache_create(self._lm._handle, int(max_batch), int(max_len), C.byref(self._handle)))
+        self.max_batch, self.max_len = int(max_batch), int(max_len)
+        self._lm._caches.add(self)
+
+    def _ptr(self):
+        if self._handle is None or not self._handle.value:
+            raise _lib.QuarkAudioError(-1, "KVCache: the cache was freed (with its model's handle, or by free())")
+        return self._handle
+
+    def free(self):
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.qa_lm_cache_destroy(self._handle)
+        self._handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return torch.cuda.current_stream(self._lm.device).cuda_stream
+
+    def get_seq_length(self) -> int:
+        return int(self._lib.qa_lm_cache_length(self._ptr()))
+
+    @property
+    def batch_size(self) -> int:
+        return int(self._lib.qa_lm_cache_batch(self._ptr()))
+
+    def reset(self):
+        _lib.check(self._lib.qa_lm_cache_reset(self._ptr()))
+
+    def crop(self, max_length: int):
+        """DynamicCache.crop: keep the first `max_length` positions (negative: drop that many from the end)."""
+        n = int(max_length)
+        if n < 0:
+            n = self.get_seq_length() + n
+        _lib.check(self._lib.qa_lm_cache_crop(self._ptr(), n))
+
+    def batch_select_indices(self, indices: Sequence[int]):
+        """Row j becomes old row indices[j]; the batch becomes len(indices) (at most max_batch)."""
+        idx = [int(i) for i in (indices.tolist() if torch.is_tensor(indices) else indices)]
+        arr = (C.c_int64 * len(idx))(*idx)
+        _lib.check(self._lib.qa_lm_cache_select(self._ptr(), arr, len(idx), self._stream()))
+
+    def reorder_cache(self, beam_idx):
+        self.batch_select_indices(beam_idx)
+
+    def batch_repeat_interleave(self, repeats: int):
+        self.batch_select_indices([b for b in range(self.batch_size) for _ in range(int(repeats))])
+
+
+def _unsupported(**kw):
+    for name, (value, default) in kw.items():
+        if value is not default and value != default:
+            raise _lib.QuarkAudioError(-4, f"llm_forward: {name} is not supported (attention is causal over the cache, positions follow "
+                                           f"the cache length, attention weights are never materialised)")
 
 
 class LLM_SFT:
@@ -38,6 +114,9 @@ class LLM_SFT:
         self.semantic_offset = 3 + cfg["global_size"]
         self._lib = _lib.load_library()
         self._handle = C.c_void_p()
+        self._caches = weakref.WeakSet()  # live KVCache objects of the handle
+        self.hidden_size = cfg["hidden_size"]
+        self.num_layers = cfg["num_layers"]
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         _lib.require_device()
@@ -55,6 +134,8 @@ class LLM_SFT:
 
     def _free(self):
         if getattr(self, "_handle", None) is not None and self._handle.value:
+            for cache in list(self._caches):  # qa_lm_destroy frees the handle's caches: do it first, so no KVCache keeps a dead pointer
+                cache.free()
             self._lib.qa_lm_destroy(self._handle)
             self._handle = C.c_void_p()
 
@@ -63,6 +144,103 @@ class LLM_SFT:
             self._free()
         except Exception:
             pass
+
+    # ---- sessions: the body over a cache the caller holds, and LLM_SFT's submodules as device calls
+
+    def _ready(self):
+        if not self._handle.value:
+            raise _lib.QuarkAudioError(-3, "LLM_SFT has no weights: call load_state_dict first")
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    @torch.no_grad()
+    def llm_forward(self, inputs_embeds: torch.Tensor, attention_mask=None, past_key_values: Optional[KVCache] = None,
+                    use_cache: bool = False, output_attentions: bool = False, output_hidden_states: bool = False, position_ids=None,
+                    cache_position=None):
+        """CustomLlamaModel.llm_forward (llm.py:150-227): inputs_embeds [B, n, hidden] at positions len .. len + n - 1 of
+        `past_key_values` (a KVCache; use_cache=True with none creates one of B rows x max_position_embeddings), causal.  Returns an
+        object with .last_hidden_state [B, n, hidden], .past_key_values (None unless use_cache) and .hidden_states (None, or the
+        n_layers + 1 tensors of output_hidden_states).  A sequence's rows do not depend on the batch it is in."""
+        self._ready()
+        _unsupported(attention_mask=(attention_mask, None), position_ids=(position_ids, None), cache_position=(cache_position, None),
+                     output_attentions=(bool(output_attentions), False))
+        x = inputs_embeds.to(device=self.device, dtype=torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[2] != self.hidden_size:
+            raise _lib.QuarkAudioError(-1, f"llm_forward: inputs_embeds must be [B, n, hidden = {self.hidden_size}], got {tuple(x.shape)}")
+        B, n, d = x.shape
+        cache = past_key_values
+        if cache is not None and not isinstance(cache, KVCache):
+            raise _lib.QuarkAudioError(-1, "llm_forward: past_key_values must be a unified_audio_amd.KVCache")
+        if cache is not None and cache._lm is not self:
+            raise _lib.QuarkAudioError(-1, "llm_forward: past_key_values belongs to another model")
+        if use_cache and cache is None:
+            cache = KVCache(self, B, MAX_POSITION_EMBEDDINGS)  # llm.py:170-171
+        out = torch.empty_like(x)
+        hs = torch.empty((self.num_layers + 1, B, n, d), dtype=torch.float32, device=self.device) if output_hidden_states else None
+        _lib.check(self._lib.qa_lm_forward(self._handle, cache._ptr() if cache is not None else None, x.data_ptr(), B, n, out.data_ptr(),
+                                           hs.data_ptr() if hs is not None else None, self._stream()))
+        return SimpleNamespace(last_hidden_state=out, past_key_values=cache if use_cache else None,
+                               hidden_states=tuple(hs.unbind(0)) if hs is not None else None, attentions=None)
+
+    @torch.no_grad()
+    def test_generate(self, inputs_embeds: torch.Tensor, top_k: int = 50, top_p: float = 0.95, temperature: float = 0.8):
+        """llm.py:229-250: inputs_embeds one position at a time over a fresh cache; the concatenated last hidden states."""
+        cache = KVCache(self, inputs_embeds.shape[0], max(int(inputs_embeds.shape[1]), 1))
+        outs = [self.llm_forward(inputs_embeds[:, i:i + 1], past_key_values=cache, use_cache=True).last_hidden_state
+                for i in range(inputs_embeds.shape[1])]
+        cache.free()
+        return torch.cat(outs, dim=1)
+
+    @torch.no_grad()
+    def codec_embedding(self, ids: torch.Tensor) -> torch.Tensor:
+        """LLM_SFT.codec_embedding: raw vocabulary ids [...] -> [..., hidden]; IndexError for an id outside the vocabulary."""
+        self._ready()
+        t = ids.to(device=self.device, dtype=torch.int64).contiguous()
+        out = torch.empty(tuple(t.shape) + (self.hidden_size,), dtype=torch.float32, device=self.device)
+        if t.numel():
+            bad = C.c_int64(0)
+            _lib.check(self._lib.qa_codes_check(t.data_ptr(), t.numel(), self.vocab_size, C.byref(bad), self._stream()))
+            if bad.value:
+                raise IndexError(f"{bad.value} ids out of range [0, {self.vocab_size})")
+            _lib.check(self._lib.qa_lm_embed(self._handle, t.data_ptr(), t.numel(), out.data_ptr(), self._stream()))
+        return out
+
+    @torch.no_grad()
+    def output_head(self, hidden: torch.Tensor, lo: int = 0, width: Optional[int] = None) -> torch.Tensor:
+        """LLM_SFT.output_head on last_hidden_state rows [..., hidden] -> logits [..., width] of the vocabulary slice [lo, lo + width)
+        (default: the whole vocabulary)."""
+        self._ready()
+        h = hidden.to(device=self.device, dtype=torch.float32).contiguous()
+        if h.shape[-1] != self.hidden_size:
+            raise _lib.QuarkAudioError(-1, f"output_head: hidden must be [..., {self.hidden_size}], got {tuple(h.shape)}")
+        width = self.vocab_size - int(lo) if width is None else int(width)
+        out = torch.empty(tuple(h.shape[:-1]) + (width,), dtype=torch.float32, device=self.device)
+        rows = h.numel() // self.hidden_size
+        if rows:
+            _lib.check(self._lib.qa_lm_head(self._handle, h.data_ptr(), rows, int(lo), width, out.data_ptr(), self._stream()))
+        return out
+
+    @torch.no_grad()
+    def build_prompt(self, task_name: str, enroll_feats: Optional[torch.Tensor], mix_feats: torch.Tensor) -> torch.Tensor:
+        """llm_sft.py:110-128: [task, (enroll_sos, adapter(enroll_feats)), mix_sos, adapter(mix_feats)] -> [B, L, hidden]."""
+        self._ready()
+        task = self.task_map[task_name]  # KeyError like the reference
+        mix = mix_feats.to(device=self.device, dtype=torch.float32).contiguous()
+        if mix.dim() != 3 or mix.shape[2] != self._spec.feats_dim:
+            raise _lib.QuarkAudioError(-1, f"build_prompt: mix_feats must be [B, N, {self._spec.feats_dim}], got {tuple(mix.shape)}")
+        B, n_mix, _ = mix.shape
+        enr, n_enr = None, 0
+        if enroll_feats is not None:
+            enr = enroll_feats.to(device=self.device, dtype=torch.float32).contiguous()
+            if enr.dim() != 3 or enr.shape[0] != B or enr.shape[2] != self._spec.feats_dim:
+                raise _lib.QuarkAudioError(-1, f"build_prompt: enroll_feats must be [{B}, N, {self._spec.feats_dim}], got {tuple(enr.shape)}")
+            n_enr = enr.shape[1]
+        L = 1 + (1 + n_enr if enr is not None else 0) + 1 + n_mix
+        out = torch.empty((B, L, self.hidden_size), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.qa_lm_prompt(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, mix.data_ptr(), n_mix, B,
+                                          out.data_ptr(), self._stream()))
+        return out
 
     @torch.no_grad()
     def generate(self, task_name: str, enroll_mel, enroll_feats, mix_mel: torch.Tensor, mix_feats: torch.Tensor,
@@ -257,6 +435,25 @@ class CustomLlamaModel:
             _lib.check(lm._lib.qa_lm_generate_cond(lm._handle, ptr, T, B, global_length, semantic_length, temperature, top_k, top_p,
                                                    gids.data_ptr(), sids.data_ptr(), stream))
         return gids, sids
+
+    def llm_forward(self, inputs_embeds, attention_mask=None, past_key_values=None, use_cache=False, output_attentions=False,
+                    output_hidden_states=False, position_ids=None, cache_position=None):
+        """llm.py:150-227 over a KVCache: see LLM_SFT.llm_forward (the same code on the same handle)."""
+        return self._lm.llm_forward(inputs_embeds, attention_mask, past_key_values, use_cache, output_attentions, output_hidden_states,
+                                    position_ids, cache_position)
+
+    def test_generate(self, inputs_embeds, top_k: int = 50, top_p: float = 0.95, temperature: float = 0.8):
+        """llm.py:229-250"""
+        return self._lm.test_generate(inputs_embeds, top_k, top_p, temperature)
+
+    def codec_embedding(self, ids):
+        return self._lm.codec_embedding(ids)
+
+    def output_head(self, hidden, lo: int = 0, width: Optional[int] = None):
+        return self._lm.output_head(hidden, lo, width)
+
+    def build_prompt(self, task_name, enroll_feats, mix_feats):
+        return self._lm.build_prompt(task_name, enroll_feats, mix_feats)
 
     def _score(self, global_ids, semantic_ids, cond):
         lm = self._lm
