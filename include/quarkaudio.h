@@ -557,6 +557,25 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
                            int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                            int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream);
 
+/* qa_lm_generate / qa_lm_generate_sampled over a batch whose enrollments differ in length (TSE / rTSE: the enrollment is a recording of
+ * the user's choosing).  Row b behaves as LLM_SFT.generate would for that sequence ALONE with its first n_enroll[b] frames: prompt
+ * [task, enroll_sos, adapter(enroll_feats[b, :n_enroll[b]]), mix_sos, adapter(mix_feats[b])] at positions 0 .. L_b - 1 with
+ * L_b = 3 + n_enroll[b] + n_mix, decode step t at position L_b + t over L_b + t + 1 keys.  n_mix, global_length and semantic_length
+ * are common to the batch.
+ *   enroll_feats [B, n_enroll_max, feats_dim] (device), required; frames at or behind n_enroll[b] are padding and never enter a row's
+ *                arithmetic (they may hold anything, NaN included)
+ *   n_enroll     HOST int64 [B], each in 1 .. n_enroll_max; read during the call, may be freed on return
+ * Refused, before anything is launched, when enroll_feats or n_enroll is NULL, when a length is out of range (the message names the row
+ * and its value) or when 3 + n_enroll_max + n_mix + global_length + 1 + semantic_length exceeds 4096.  A vector whose entries all equal
+ * n_enroll_max gives, bit for bit, the logits and tokens of qa_lm_generate(_sampled) with n_enroll = n_enroll_max.  Taps as there. */
+int qa_lm_generate_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                          const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
+                          int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream);
+int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                                  const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length,
+                                  float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
+                                  void* stream);
+
 /* LLM_SFT.forward (llm_sft.py:37-90): teacher-forced scoring of given token streams.  With Lt = global_length + semantic_length + 2,
  * input_ids = [0, global_ids + 3, 1, semantic_ids + 3 + global_size] and target_ids = [global_ids + 3, 1, semantic_ids + 3 + global_size, 2];
  * the prompt is generate's, the body runs causally over all prompt + Lt positions from position 0, and output_head covers the FULL

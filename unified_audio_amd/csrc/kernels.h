@@ -97,7 +97,8 @@ int launch_rvq_lookup(const long long* indices, long long n_vec, const float* co
 
 // lm_kernels.hip
 int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_sos, const float* enroll_emb,
-                           const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s);
+                           const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s,
+                           const int* off = nullptr);  // off [B] (device): row b holds Ne + off[b] enrollment frames, zeros behind its prompt
 int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate, long long ldg,
                        const float* res, long long ldr, float* y, long long ldy, int M, int N, int K, int act, hipStream_t s,
                        float rms_eps, int dual);

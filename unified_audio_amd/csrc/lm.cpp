@@ -245,6 +245,7 @@ struct LMBuffers {
     // fused decode step
     float *q, *att_part, *pmax, *mlp_part;
     int *pidx, *state;
+    int* off;  // ragged generate: per-row position offsets L_b - L_max <= 0 (lm_decode.h GemvArgs::off); nullptr everywhere else
     long long *ids_g, *ids_s;
     int cap, S_att, att_tps;  // cache capacity, the attention's split count of a replayed step and 16-key tiles per split
     size_t layer_stride;      // floats between two layers of kc / vc; 0: B * cap * d (generate's arena); a qa_lm_cache: max_batch * max_len * d
@@ -313,7 +314,8 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
     const long long kv_bstride = (long long)b.cap * d;
     const size_t cache_stride = b.layer_stride ? b.layer_stride : (size_t)B * b.cap * d;
     // key split of the attention launch: split sp owns the fixed tile range [sp, sp + 1) * b.att_tps (lm_attn_kernel); a host-driven
-    // step launches the splits that hold keys, a replayed one all of them (the others write identity records): same bits either way
+    // step launches the splits that hold keys, a replayed one all of them (the others write identity records): same bits either way.
+    // Ragged batch: `pos` is the LONGEST row's position, so the count covers every row; a shorter row's surplus splits are identity records
     const int S_att = pos >= 0 ? std::max(1, (int)ceil_div(ceil_div(pos + 1, 16), b.att_tps)) : b.S_att;
     // cross-launch prefetch (QA_LM_PF, lm_decode.h PfArgs): which launch carries the prefetch plane for which consumer
     const long long pfk = knob(K_LM_PF);
@@ -335,7 +337,7 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
         if (io.hidden)
             QA_HIP(hipMemcpyAsync(io.hidden + i * io.hidden_stride, i == 0 ? io.x_in : b.x, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
         GemvArgs a{};
-        a.M = B; a.rms_eps = sp.rms_eps; a.state = b.state; a.pos = pos; a.H = H; a.hd = hd; a.d = d;
+        a.M = B; a.rms_eps = sp.rms_eps; a.state = b.state; a.pos = pos; a.off = b.off; a.H = H; a.hd = hd; a.d = d;
         // o_proj's tile width (computed here: the qkv launch may prefetch its weights)
         int nt_o = lm->nt_o;
         if (gemv_r8_ok(d)) {
@@ -353,7 +355,7 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
         if (pfk & 1) pf_region(qpf, 0, L.o.w, (long long)nt_o * d * 4, d / nt_o);
         QA_TRY(launch_lm_gemv(q, GM_QKV, lm->nt_qkv, s, &qpf));
         // 2. attention over the cache (pos + 1 keys), split over S_att workgroups per (sequence, head)
-        QA_TRY(launch_lm_attn(b.q, d, kc, vc, kv_bstride, d, b.att_part, B, H, hd, S_att, b.att_tps, b.state, scale, pos, s));
+        QA_TRY(launch_lm_attn(b.q, d, kc, vc, kv_bstride, d, b.att_part, B, H, hd, S_att, b.att_tps, b.state, scale, pos, s, b.off));
         // 3. merge of the partials + o_proj + residual
         GemvArgs o = a;
         o.att_part = b.att_part; o.S = S_att;
@@ -440,7 +442,7 @@ struct Chain {
     hipStream_t s = nullptr;
 };
 
-int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int Nm, int Ne, bool enroll) {
+int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int Nm, int Ne, bool enroll, bool ragged) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads, B = ch.B;
     const int64_t prow = (int64_t)B * std::max(L, 1);  // L = 0: the empty prompt of CustomLlamaModel.generate(cond=None); a step still needs its row
@@ -472,6 +474,7 @@ int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int 
     b.ids_s = c.arena.alloc<long long>((size_t)B * std::max(S, 1));
     ch.emix = c.arena.alloc<float>((size_t)B * Nm * d);
     ch.eenr = enroll ? c.arena.alloc<float>((size_t)B * Ne * d) : nullptr;
+    b.off = ragged ? c.arena.alloc<int>(B) : nullptr;  // last, and only then: a rectangular call keeps the layout it had
     return QA_OK;
 }
 
@@ -486,7 +489,9 @@ int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int 
 // empty (Tc = 0), and the global phase runs exactly G steps: its last token is returned but never fed (llm.py:318,345)
 int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, const float* mix, int Nm, int B, int G,
                    int S, long long* gids, long long* sids, const SampleCfg& sc, bool cond_mode = false, const float* cond = nullptr,
-                   int Tc = 0) {
+                   int Tc = 0, const int* ne_rows = nullptr) {
+    // ne_rows (HOST, [B]; qa_lm_generate_ragged): row b's enrollment frames, 1 .. Ne.  L, pos and the capacity below
+    // are then the LONGEST possible row's (Ne frames); the rows' own positions follow from the per-chain offset array b.off
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden;
     const int L = cond_mode ? (Tc > 0 ? Tc + 1 : 0) : 1 + (enroll ? 1 + Ne : 0) + 1 + Nm;
@@ -514,7 +519,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     for (int i = 0; i < nc; ++i) {
         chains[i].b0 = i * cb;
         chains[i].B = std::min(cb, B - i * cb);
-        QA_TRY(chain_alloc(lm, c, chains[i], L, cap, G, S, Nm, Ne, enroll != nullptr));
+        QA_TRY(chain_alloc(lm, c, chains[i], L, cap, G, S, Nm, Ne, enroll != nullptr, ne_rows != nullptr));
     }
     if (c.dry) return QA_OK;  // real-pass-only remainder: chain_alloc above made the function's last arena allocations
     const bool multi = nc > 1;
@@ -554,10 +559,17 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
         const float* mix_c = mix + (size_t)ch.b0 * Nm * sp.feats_dim;
         const float* enr_c = enroll ? enroll + (size_t)ch.b0 * Ne * sp.feats_dim : nullptr;
         int st = linear_op(c, mix_c, (int64_t)ch.B * Nm, lm->adapter, ch.emix);
+        // ragged: the adapter also runs over the padding frames (a GEMM row depends on its own input row alone) and assemble_prompt
+        // never copies their outputs
         if (st == QA_OK && enroll) st = linear_op(c, enr_c, (int64_t)ch.B * Ne, lm->adapter, ch.eenr);
+        if (st == QA_OK && ne_rows) st = launch_lm_offsets(ch.b.off, ne_rows + ch.b0, Ne, ch.B, ch.s);
         if (st == QA_OK)
             st = launch_assemble_prompt(ch.b.x, lm->task_emb + (size_t)task * d, enroll ? lm->enroll_sos : nullptr, ch.eenr, lm->mix_sos,
-                                        ch.emix, ch.B, Ne, Nm, d, ch.s);
+                                        ch.emix, ch.B, Ne, Nm, d, ch.s, ch.b.off);
+        // Ragged: the prefill runs unchanged over L = L_max positions and needs NO mask.  It is causal, so a valid query (position < L_b)
+        // never sees a key behind itself, least of all the zero rows at L_b .. L - 1.  The queries of those zero rows are finite garbage
+        // that nothing consumes (the prefill's last hidden state is not used, only its K / V), and the K / V rows they leave at L_b + t
+        // are overwritten by decode step t before that step - the first to count them among its L_b + t + 1 keys - reads them.
         if (st == QA_OK) st = lm_body(lm, c, ch.b, ch.B, L, 0, cap, true);
         c.stream = caller;
         QA_TRY(st);
@@ -584,7 +596,8 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
                 for (uint64_t v : {(uint64_t)(uintptr_t)lm->ws.ptr, (uint64_t)B, (uint64_t)nc, (uint64_t)ch.b0, (uint64_t)ch.B, (uint64_t)cap, (uint64_t)L,
                                    (uint64_t)G, (uint64_t)S, (uint64_t)Ne, (uint64_t)Nm, (uint64_t)(enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
                                    (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF),
-                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch), (uint64_t)cond_mode})
+                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch), (uint64_t)cond_mode,
+                                   (uint64_t)(ne_rows != nullptr)})  // ragged or not - never the lengths: they live in device memory (b.off)
                     key = mix_key(key, v);
                 if (!g.exec || g.key != key) {
                     g.reset();
@@ -1117,8 +1130,9 @@ void qa_lm_destroy(qa_lm* lm) { destroy_handle(lm); }
 static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                             int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc,
                             int64_t* global_ids, int64_t* semantic_ids, void* stream, bool cond_mode = false, const float* cond = nullptr,
-                            int64_t Tc = 0) {
-    const char* fn = cond_mode ? "qa_lm_generate_cond" : "qa_lm_generate";
+                            int64_t Tc = 0, const int64_t* ne_rows = nullptr, bool ragged = false) {
+    // ragged (qa_lm_generate_ragged*): n_enroll is n_enroll_max and ne_rows the HOST vector of the rows' own frame counts
+    const char* fn = cond_mode ? "qa_lm_generate_cond" : ragged ? "qa_lm_generate_ragged" : "qa_lm_generate";
     if (!lm || (!cond_mode && !mix_feats) || !global_ids || !semantic_ids) {
         set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
@@ -1130,6 +1144,19 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     QA_REQUIRE(!enroll_feats || n_enroll > 0, "%s: enrollment given with no frames", fn);
     QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "%s: temperature must be in (0, 1] (llm.py:278)", fn);
     QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "%s: bad top_k / top_p", fn);
+    std::vector<int> ne_host;  // every check of a ragged call comes before the first launch: a refused call has launched nothing
+    if (ragged) {
+        QA_REQUIRE(enroll_feats && ne_rows, "%s: per-row enrollment lengths need enroll_feats [B, n_enroll_max, feats_dim] and n_enroll [B]", fn);
+        const long long total = 3 + (long long)n_enroll + n_mix + global_length + 1 + semantic_length;
+        QA_REQUIRE(total <= LM_MAX_POS, "%s: %lld positions (3 + n_enroll_max %lld + n_mix %lld + %d + 1 + %d) exceed max_position_embeddings %d",
+                   fn, total, (long long)n_enroll, (long long)n_mix, global_length, semantic_length, LM_MAX_POS);
+        ne_host.resize((size_t)B);
+        for (int64_t i = 0; i < B; ++i) {
+            QA_REQUIRE(ne_rows[i] >= 1 && ne_rows[i] <= n_enroll, "%s: n_enroll[%lld] = %lld is outside 1 .. n_enroll_max = %lld", fn,
+                       (long long)i, (long long)ne_rows[i], (long long)n_enroll);
+            ne_host[(size_t)i] = (int)ne_rows[i];
+        }
+    }
     QA_HIP(hipSetDevice(lm->device));
     if (sc.do_sample) QA_TRY(lm_sample_prepare());
     lm->tap_n[0] = lm->tap_n[1] = -1;
@@ -1139,7 +1166,7 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
     c.att_fp32 = true;   // the prefill attention stays consistent with the fp32 decode kernels
     auto graph = [&] {
         return generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
-                              (long long*)global_ids, (long long*)semantic_ids, sc, cond_mode, cond, (int)Tc);
+                              (long long*)global_ids, (long long*)semantic_ids, sc, cond_mode, cond, (int)Tc, ragged ? ne_host.data() : nullptr);
     };
     QA_TRY(plan(lm->device, static_cast<hipStream_t>(stream), c, lm->ws, graph, [&](size_t bytes) -> int {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1176,6 +1203,23 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
     const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
     return lm_generate_impl(lm, task, enroll_feats, n_enroll, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
                             semantic_ids, stream);
+}
+
+int qa_lm_generate_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                          const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
+                          int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    const SampleCfg sc{0, top_k, top_p, temperature, 0ull};
+    return lm_generate_impl(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
+                            semantic_ids, stream, false, nullptr, 0, n_enroll, true);
+}
+
+int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                                  const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length,
+                                  float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
+                                  void* stream) {
+    const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
+    return lm_generate_impl(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
+                            semantic_ids, stream, false, nullptr, 0, n_enroll, true);
 }
 
 static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,

@@ -41,6 +41,9 @@ struct GemvArgs {
     float rms_eps;
     const int* state;
     int pos;  // >= 0: position of the step (host-driven loop); < 0: read it from state (captured step)
+    // ragged batches: off[row] = L_row - L_max <= 0, the row's position is the step's plus off[row].  Device memory,
+    // written once per call, so a captured step serves every length vector.  nullptr: every row sits at the step's position
+    const int* off;
     // GM_QKV
     const float* rope;  // [pos][hd/2][2] cos, sin
     float* q;           // [M, d]
@@ -70,7 +73,11 @@ bool lm_mlp_fused_supported(int d, int I, int nt_gu);
 int launch_lm_mlp(const GemvArgs& a, int I, int ac, const float* wd, float* partial, const float* res, long long ldr, float* y, long long ldy,
                   hipStream_t s, const PfArgs* pf = nullptr);
 int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* vc, long long kv_bstride, long long ldkv,
-                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s);
+                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s,
+                   const int* off = nullptr);  // off: per-row position offsets as GemvArgs::off
+// off[i] = n_rows[i] - n_max for the B <= LM_MAX_ROWS rows of a chain (the values travel as kernel arguments: the host vector may be
+// freed on return, and the write is ordered on the stream like every other launch of the call)
+int launch_lm_offsets(int* off, const int* n_rows, int n_max, int B, hipStream_t s);
 int launch_lm_pick(const float* pmax, const int* pidx, int n_tiles, int B, int lo, long long* tok, long long* ids, long long ids_ld,
                    int keep, int* state, int col, hipStream_t s);
 int launch_lm_phase_init(long long* tok, long long first_id, int B, int* state, int pos, int reset_step, unsigned long long seed,

@@ -144,7 +144,7 @@ __device__ __forceinline__ void att_merge(const GemvArgs& a, int row, int k, flo
 // entry: a dependent load of data another kernel just wrote costs ~2 us on this chip, so a kernel must not chain them.
 struct EpiPre {
     float res[4];   // GM_RESID: residual values of this thread's outputs
-    int pos;        // GM_QKV: position
+    int pos[4];     // GM_QKV: position of the row of each of this thread's rotary pairs (one value unless the batch is ragged)
     float c[4], s[4];  // GM_QKV: cos / sin of this thread's rotary pairs
 };
 
@@ -166,6 +166,7 @@ __device__ __forceinline__ void row_group(GemvArgs& a, int rg, int n_tiles, int 
     if (a.tok) a.tok += r0;
     if (a.att_part) a.att_part += r0 * a.H * a.S * (a.hd + 4);
     if (a.q) a.q += r0 * a.d;
+    if (a.off) a.off += r0;
     if (a.kc) a.kc += r0 * a.kv_bstride;
     if (a.vc) a.vc += r0 * a.kv_bstride;
     if (a.res) a.res += r0 * a.ldr;
@@ -191,7 +192,7 @@ __device__ __forceinline__ void epi_prefetch(const GemvArgs& a, int tile, int ti
         }
     } else if (MODE == GM_QKV) {
         constexpr int HP = NT / 2;
-        e.pos = a.pos >= 0 ? a.pos : a.state[ST_POS];
+        const int pos = a.pos >= 0 ? a.pos : a.state[ST_POS];
         const int hd = a.hd, half = hd >> 1, tps = a.d / NT;
         const int sec = tile / tps, c0 = (tile - sec * tps) * NT, h = c0 / hd;
 #pragma unroll
@@ -199,12 +200,16 @@ __device__ __forceinline__ void epi_prefetch(const GemvArgs& a, int tile, int ti
             const int i = tid + u * 512;
             e.c[u] = 1.f;
             e.s[u] = 0.f;
-            if (i < MT * 16 * HP && sec != 2) {
+            e.pos[u] = pos;
+            if (i < MT * 16 * HP) {
                 const int row = i / HP, j = i - row * HP;
-                const int ri = ((c0 - h * hd) / NT) * HP + j;
-                e.c[u] = a.rope[((long long)e.pos * half + ri) * 2];
-                e.s[u] = a.rope[((long long)e.pos * half + ri) * 2 + 1];
-                (void)row;
+                // ragged batch: the row's own position (a wave-uniform branch; rows past M re-read the last row and are never stored)
+                if (a.off) e.pos[u] = pos + a.off[min(row, a.M - 1)];
+                if (sec != 2) {
+                    const int ri = ((c0 - h * hd) / NT) * HP + j;
+                    e.c[u] = a.rope[((long long)e.pos[u] * half + ri) * 2];
+                    e.s[u] = a.rope[((long long)e.pos[u] * half + ri) * 2 + 1];
+                }
             }
         }
     }
@@ -243,7 +248,7 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, const float (*p
                 const int d = a.d, hd = a.hd, half = hd >> 1, tps = d / NT;
                 const int sec = tile / tps, c0 = (tile - sec * tps) * NT;
                 const int h = c0 / hd, ri = ((c0 - h * hd) / NT) * HP + j;  // rotary index in [0, hd/2)
-                const int pos = e.pos;
+                const int pos = e.pos[u];
                 if (sec == 2) {  // V: no rotation
                     float* dst = a.vc + (long long)row * a.kv_bstride + (long long)pos * d + h * hd;
                     dst[ri] = v1;
@@ -843,7 +848,8 @@ template <int HD, int NW>
 __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restrict__ q, long long ldq,
                                                           const float* __restrict__ kc, const float* __restrict__ vc,
                                                           long long kv_bstride, long long ldkv, float* __restrict__ part,
-                                                          const int* __restrict__ state, float scale, int pos, int tps) {
+                                                          const int* __restrict__ state, float scale, int pos, int tps,
+                                                          const int* __restrict__ off) {
     constexpr int LPK = HD / 4;    // lanes per key row
     constexpr int KPI = 64 / LPK;  // key rows per load instruction
     constexpr int NI = 16 / KPI;   // load instructions per 16-key tile (per operand)
@@ -852,7 +858,8 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y, h = blockIdx.x, sp = blockIdx.z, S = gridDim.z, H = gridDim.x;
     const int kq = lane / LPK, c4 = (lane % LPK) * 4;
-    const int n_keys = (pos >= 0 ? pos : state[ST_POS]) + 1;
+    // ragged batch (off != nullptr): sequence b sits off[b] <= 0 positions behind the step's position and owns that many keys fewer
+    const int n_keys = (pos >= 0 ? pos : state[ST_POS]) + 1 + (off ? off[b] : 0);
     const int n_tiles = (n_keys + 15) >> 4;
     const int t0 = sp * tps, t_end = min(t0 + tps, n_tiles);  // this split's tiles (empty past the last key)
     const float* kb = kc + (long long)b * kv_bstride + h * HD + c4;
@@ -945,21 +952,43 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
 }
 
 int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* vc, long long kv_bstride, long long ldkv,
-                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s) {
+                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s, const int* off) {
     QA_REQUIRE(S >= 1 && S <= 4 && tps >= 1, "lm_attn: bad split count %d (%d tiles each)", S, tps);
     const dim3 grid(H, B, S);
     switch (hd) {
         case 64:
-            hipLaunchKernelGGL((lm_attn_kernel<64, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps);
+            hipLaunchKernelGGL((lm_attn_kernel<64, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off);
             break;
         case 128:
-            hipLaunchKernelGGL((lm_attn_kernel<128, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps);
+            hipLaunchKernelGGL((lm_attn_kernel<128, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off);
             break;
         case 32:
-            hipLaunchKernelGGL((lm_attn_kernel<32, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps);
+            hipLaunchKernelGGL((lm_attn_kernel<32, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off);
             break;
         default: set_error("lm_attn: head_dim=%d unsupported", hd); return QA_ERR_UNSUPPORTED;
     }
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Row offsets of a ragged batch: off[i] = n_rows[i] - n_max <= 0, one launch per chain and call.  The lengths are
+// host data, so they ride in the kernel arguments (one struct of LM_MAX_ROWS ints) and land in device memory in stream order.
+struct RowLens {
+    int n[LM_MAX_ROWS];
+};
+__global__ __launch_bounds__(LM_MAX_ROWS) void lm_offsets_kernel(int* __restrict__ off, const RowLens len, int n_max, int B) {
+    const int i = threadIdx.x;
+    if (i < B) off[i] = len.n[i] - n_max;
+}
+int launch_lm_offsets(int* off, const int* n_rows, int n_max, int B, hipStream_t s) {
+    QA_REQUIRE(B >= 1 && B <= LM_MAX_ROWS, "lm_offsets: %d rows (a chain holds 1 .. %d)", B, LM_MAX_ROWS);
+    RowLens len{};
+    for (int i = 0; i < B; ++i) {
+        QA_REQUIRE(n_rows[i] >= 1 && n_rows[i] <= n_max, "lm_offsets: row %d has %d frames, outside 1 .. %d", i, n_rows[i], n_max);
+        len.n[i] = n_rows[i];
+    }
+    hipLaunchKernelGGL(lm_offsets_kernel, dim3(1), dim3(LM_MAX_ROWS), 0, s, off, len, n_max, B);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

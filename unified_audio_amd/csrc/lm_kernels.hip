@@ -11,12 +11,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------
 // llm_sft.py:110-128: prompt = [task, (enroll_sos, adapter(enroll)), mix_sos, adapter(mix)]  -> x [B, L, d]
+// Ragged batches (off != nullptr): row b uses the first Ne + off[b] of its Ne enrollment rows and is laid out
+// left-aligned over L + off[b] positions; the positions behind are written as zeros and the enrollment rows behind are never read.
 __global__ __launch_bounds__(256) void assemble_prompt_kernel(float* __restrict__ x, const float* __restrict__ task_vec,
                                                               const float* __restrict__ enroll_sos,
                                                               const float* __restrict__ enroll_emb,
                                                               const float* __restrict__ mix_sos,
                                                               const float* __restrict__ mix_emb, int B, int Ne, int Nm,
-                                                              int d) {
+                                                              int d, const int* __restrict__ off) {
     const int L = 1 + (enroll_emb ? 1 + Ne : 0) + 1 + Nm;
     const int d4 = d >> 2;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -24,6 +26,7 @@ __global__ __launch_bounds__(256) void assemble_prompt_kernel(float* __restrict_
     const int c = (int)(gid % d4) * 4;
     const int pos = (int)((gid / d4) % L);
     const int b = (int)(gid / ((long long)d4 * L));
+    const int ne = off ? Ne + off[b] : Ne;  // this row's enrollment frames
     const float* src;
     int p = pos;
     if (p == 0) {
@@ -34,23 +37,25 @@ __global__ __launch_bounds__(256) void assemble_prompt_kernel(float* __restrict_
             src = enroll_sos;
         } else {
             if (enroll_emb) p -= 1;
-            if (enroll_emb && p < Ne) {
+            if (enroll_emb && p < ne) {
                 src = enroll_emb + ((long long)b * Ne + p) * d;
             } else {
-                if (enroll_emb) p -= Ne;
-                src = (p == 0) ? mix_sos : mix_emb + ((long long)b * Nm + (p - 1)) * d;
+                if (enroll_emb) p -= ne;
+                src = (p == 0) ? mix_sos : (p <= Nm) ? mix_emb + ((long long)b * Nm + (p - 1)) * d : nullptr;
             }
         }
     }
-    *reinterpret_cast<float4*>(x + ((long long)b * L + pos) * d + c) = *reinterpret_cast<const float4*>(src + c);
+    *reinterpret_cast<float4*>(x + ((long long)b * L + pos) * d + c) =
+        src ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_sos, const float* enroll_emb,
-                           const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s) {
+                           const float* mix_sos, const float* mix_emb, int B, int Ne, int Nm, int d, hipStream_t s, const int* off) {
+    QA_REQUIRE(!off || enroll_emb, "assemble_prompt: per-row lengths need an enrollment");
     const int L = 1 + (enroll_emb ? 1 + Ne : 0) + 1 + Nm;
     const long long total = (long long)B * L * (d / 4);
     hipLaunchKernelGGL(assemble_prompt_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, task_vec,
-                       enroll_sos, enroll_emb, mix_sos, mix_emb, B, Ne, Nm, d);
+                       enroll_sos, enroll_emb, mix_sos, mix_emb, B, Ne, Nm, d, off);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

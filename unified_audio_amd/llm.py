@@ -245,8 +245,12 @@ class LLM_SFT:
     @torch.no_grad()
     def generate(self, task_name: str, enroll_mel, enroll_feats, mix_mel: torch.Tensor, mix_feats: torch.Tensor,
                  global_length: int = 32, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
-                 do_sample: bool = True):
+                 do_sample: bool = True, *, enroll_lengths=None):
         """Returns (global_ids [B, global_length], semantic_ids [B, mix_mel.size(1)]) int64, offsets subtracted.
+        enroll_lengths (keyword only; None: the reference's rectangular call): a sequence or tensor of B frame counts for a batch whose
+        enrollments differ in length.  enroll_feats is then [B, max(enroll_lengths), feats_dim], row b's frames at or behind
+        enroll_lengths[b] are padding that is never read, and row b's tokens are what the reference returns for that sequence alone
+        with its own enroll_feats[b:b+1, :enroll_lengths[b]] (qa_lm_generate_ragged).
         Only `mix_mel.size(1)` is consumed from the mel inputs, exactly like the reference (llm_sft.py:108).
         do_sample=True (the reference's signature default, llm_sft.py:106) samples every token on the device with
         CustomLlamaModel.sample_logits' filters (llm.py:253-288); the draws come from a Philox stream seeded from torch's
@@ -266,6 +270,22 @@ class LLM_SFT:
         sids = torch.empty((B, S), dtype=torch.int64, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         enr_ptr = enr.data_ptr() if enr is not None else None
+        if enroll_lengths is not None:
+            lens = [int(v) for v in (enroll_lengths.tolist() if isinstance(enroll_lengths, torch.Tensor) else enroll_lengths)]
+            if len(lens) != B:
+                raise _lib.QuarkAudioError(-1, f"generate: enroll_lengths has {len(lens)} entries for a batch of {B}")
+            if enr is not None and (enr.dim() != 3 or enr.shape[0] != B):
+                raise _lib.QuarkAudioError(-1, f"generate: enroll_feats must be [{B}, max(enroll_lengths), feats_dim], got {tuple(enr.shape)}")
+            arr = (C.c_int64 * B)(*lens)  # host vector: the library reads it during the call
+            if do_sample:
+                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+                _lib.check(self._lib.qa_lm_generate_ragged_sampled(self._handle, task, enr_ptr, n_enr, arr, mix.data_ptr(), n_mix, B,
+                                                                   global_length, S, temperature, top_k, top_p, seed, gids.data_ptr(),
+                                                                   sids.data_ptr(), stream))
+            else:
+                _lib.check(self._lib.qa_lm_generate_ragged(self._handle, task, enr_ptr, n_enr, arr, mix.data_ptr(), n_mix, B, global_length,
+                                                           S, temperature, top_k, top_p, gids.data_ptr(), sids.data_ptr(), stream))
+            return gids, sids
         if do_sample:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())  # advances torch's CPU generator: new draws per call
             _lib.check(self._lib.qa_lm_generate_sampled(self._handle, task, enr_ptr, n_enr, mix.data_ptr(), n_mix, B, global_length,

@@ -13,6 +13,7 @@ independent), and the results are handed back per utterance.  The last stage of 
 """
 from __future__ import annotations
 
+import inspect
 import math
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -115,9 +116,19 @@ class UniSE:
         self.semantic_model = semantic_model
         self.detokenize = detokenize if detokenize is not None else (tokenizer.detokenize if tokenizer is not None else None)
         self.max_segments = max(1, int(max_segments))
+        # per-row enrollment lengths (LLM_SFT.generate's `enroll_lengths`) are this package's extension: an LM with
+        # the reference's own signature (the reference's LLM_SFT module behind the same driver, tests/test_file_boundary_cpu.py) cannot
+        # take them and keeps one pass per enrollment length
+        try:
+            params = inspect.signature(dnn.generate).parameters.values()
+            self._ragged_ok = any(p.name == "enroll_lengths" or p.kind is inspect.Parameter.VAR_KEYWORD for p in params)
+        except (AttributeError, TypeError, ValueError):
+            self._ragged_ok = False
 
     def _generate(self, mode: str, seg_src: torch.Tensor, counts: Sequence[int], enroll_feats_per_utt: Optional[torch.Tensor],
-                  enroll_samples: int):
+                  enroll_samples: int, enroll_frames: Optional[Sequence[int]] = None):
+        """enroll_frames (enrollments of different lengths): the valid feature frames of every row of enroll_feats_per_utt, which is
+        then zero-padded to the longest; None: every row is valid throughout."""
         m = self.max_segments
         if seg_src.size(0) > m:  # micro-batches of <= max_segments segments; a segment's utterance is looked up through `owner`
             owner = torch.repeat_interleave(torch.arange(len(counts)), torch.tensor(list(counts)))
@@ -126,19 +137,47 @@ class UniSE:
                 own = owner[a:a + m]
                 utts, sub_counts = torch.unique_consecutive(own, return_counts=True)
                 ef = enroll_feats_per_utt[utts.to(enroll_feats_per_utt.device)] if enroll_feats_per_utt is not None else None
-                g, sids = self._generate(mode, seg_src[a:a + m], sub_counts.tolist(), ef, enroll_samples)
+                frames = [enroll_frames[i] for i in utts.tolist()] if enroll_frames is not None else None
+                g, sids = self._generate(mode, seg_src[a:a + m], sub_counts.tolist(), ef, enroll_samples, frames)
                 gs.append(g)
                 ss.append(sids)
             return torch.cat(gs, dim=0), torch.cat(ss, dim=0)
         mix_feats = self.semantic_model(seg_src)                                   # extract_semantic_features, model.py:38-51
         mix_mel = _Frames(seg_src.size(0), mel_frames(SEG_LEN))
         enroll_mel = enroll_feats = None
+        ragged = {}
         if enroll_feats_per_utt is not None:
+            if enroll_frames is not None:  # this micro-batch's longest enrollment bounds its prompt, not the call's
+                enroll_feats_per_utt = enroll_feats_per_utt[:, :max(enroll_frames)]
+                if len(set(enroll_frames)) > 1:
+                    # one generate call over rows of different prompt lengths (LLM_SFT.generate enroll_lengths):
+                    # every segment carries its utterance's frame count, and the padding behind it is never read
+                    ragged["enroll_lengths"] = [n for n, c in zip(enroll_frames, counts) for _ in range(c)]
             # model.py:207-210: the utterance's enrollment is tiled over its segments
             enroll_feats = torch.cat([enroll_feats_per_utt[i:i + 1].expand(c, -1, -1) for i, c in enumerate(counts)], dim=0).contiguous()
             enroll_mel = _Frames(seg_src.size(0), mel_frames(enroll_samples))
         return self.dnn.generate(task_name=mode, enroll_mel=enroll_mel, enroll_feats=enroll_feats, mix_mel=mix_mel, mix_feats=mix_feats,
-                                 do_sample=False)
+                                 do_sample=False, **ragged)
+
+    def _enroll_features(self, enrolls: Sequence[torch.Tensor]):
+        """The SSL features of one enrollment per utterance -> ([U, N_e, d], samples, frames).  Equal lengths: one front-end pass, frames
+        None.  Different lengths: the front-end is not causal, so zero-padding a waveform would change its features - it runs once per
+        DISTINCT length (every utterance keeps its own enrollment length, as in the reference's one-file-per-step loop, model.py:197-219),
+        the features are zero-padded to the longest, and `frames` holds every utterance's own count for the LM's ragged call."""
+        lens = [int(e.size(-1)) for e in enrolls]
+        if len(set(lens)) == 1:
+            return self.semantic_model(torch.cat(list(enrolls), dim=0)), lens[0], None
+        feats: List[Optional[torch.Tensor]] = [None] * len(enrolls)
+        for n in sorted(set(lens)):
+            idx = [i for i, v in enumerate(lens) if v == n]
+            f = self.semantic_model(torch.cat([enrolls[i] for i in idx], dim=0))
+            for j, i in enumerate(idx):
+                feats[i] = f[j]
+        frames = [int(f.size(0)) for f in feats]
+        ef = feats[0].new_zeros((len(feats), max(frames), feats[0].size(-1)))
+        for i, f in enumerate(feats):
+            ef[i, :frames[i]] = f
+        return ef, max(lens), frames
 
     @staticmethod
     def _split(counts, *tensors):
@@ -159,10 +198,9 @@ class UniSE:
             if enrolls is None or len(enrolls) != len(srcs):
                 raise ValueError(f"{mode} needs one enrollment per utterance")
             lens = [int(e.size(-1)) for e in enrolls]
-            if len(set(lens)) > 1:
-                # every utterance keeps ITS enrollment length (the reference feeds one file per step, model.py:197-219, and never trims
-                # an enrollment to another file's): the prompt length of a generate call is common to its batch, so utterances are grouped
-                # by enrollment length, one pass per group, and handed back in the caller's order
+            if len(set(lens)) > 1 and not self._ragged_ok:
+                # an LM without `enroll_lengths`: the prompt length of its generate call is common to the batch, so utterances are grouped
+                # by enrollment length (each keeps ITS length, model.py:197-219), one pass per group, handed back in the caller's order
                 out: List[Optional[Tuple[torch.Tensor, torch.Tensor]]] = [None] * len(srcs)
                 for n in sorted(set(lens)):
                     idx = [i for i, v in enumerate(lens) if v == n]
@@ -172,11 +210,12 @@ class UniSE:
         segs = [segment(s, normalise=(mode == "se")) for s in srcs]
         counts = [s.size(0) for s in segs]
         seg_src = torch.cat(segs, dim=0)
-        ef, n_enr = None, 0
+        ef, n_enr, frames = None, 0, None
         if mode != "se":
-            ef = self.semantic_model(torch.cat(list(enrolls), dim=0))             # [U, N_e, d]
-            n_enr = enrolls[0].size(-1)
-        global_ids, semantic_ids = self._generate(mode, seg_src, counts, ef, n_enr)
+            # enrollments of different lengths no longer split the LM pass into one group per length: the features are padded to the
+            # longest and the segments of ALL utterances go through one ragged generate per micro-batch
+            ef, n_enr, frames = self._enroll_features(enrolls)                    # [U, N_e, d]
+        global_ids, semantic_ids = self._generate(mode, seg_src, counts, ef, n_enr, frames)
         return self._split(counts, global_ids, semantic_ids)
 
     def _wave(self, src: torch.Tensor, gids: torch.Tensor, sids: torch.Tensor) -> torch.Tensor:
@@ -241,15 +280,14 @@ class UniSE:
         s_feat, s_lm, s_dec = (torch.cuda.Stream(dev) for _ in range(3))
         for st in (s_feat, s_lm, s_dec):
             st.wait_stream(cur)
-        ef, n_enr = None, 0
+        ef, n_enr, frames = None, 0, None
         if mode != "se":
             if enrolls is None or len(enrolls) != len(srcs):
                 raise ValueError(f"{mode} needs one enrollment per utterance")
-            if len({e.size(-1) for e in enrolls}) != 1:
-                raise ValueError("enrollments of one call must have the same length")
+            if len({e.size(-1) for e in enrolls}) != 1 and not self._ragged_ok:
+                raise ValueError("enrollments of one call must have the same length (the LM's generate takes no enroll_lengths)")
             with torch.cuda.stream(s_feat):
-                ef = self.semantic_model(torch.cat(list(enrolls), dim=0))
-            n_enr = enrolls[0].size(-1)
+                ef, n_enr, frames = self._enroll_features(enrolls)  # different lengths: padded features + per-utterance frame counts
         nb = (n_seg + m - 1) // m
         feats, toks, wavs = [None] * nb, [None] * nb, [None] * nb  # alive until the final join: nothing is freed under a stream
         ev_f = [torch.cuda.Event() for _ in range(nb)]
@@ -267,12 +305,19 @@ class UniSE:
                     with torch.cuda.stream(s_feat):
                         x = seg_src[k * m:(k + 1) * m]
                         f = self.semantic_model(x)
-                        e = None
+                        e, rag = None, {}
                         if ef is not None:
-                            e = ef[torch.tensor(owner[k * m:(k + 1) * m], device=dev)].contiguous()
+                            own = owner[k * m:(k + 1) * m]
+                            e = ef[torch.tensor(own, device=dev)]
+                            if frames is not None:  # as _generate: trimmed to the micro-batch's longest, ragged only if the lengths differ
+                                fr = [frames[u] for u in own]
+                                e = e[:, :max(fr)]
+                                if len(set(fr)) > 1:
+                                    rag["enroll_lengths"] = fr
+                            e = e.contiguous()
                             e.record_stream(s_lm)
                         f.record_stream(s_lm)
-                        feats[k] = (f, e, x.size(0))
+                        feats[k] = (f, e, x.size(0), rag)
                         ev_f[k].record(s_feat)
                 j = k - 2
                 if 0 <= j < nb:  # stage 3: waveform of micro-batch k - 2 (enqueued BEFORE the long LM enqueue of this turn)
@@ -286,9 +331,9 @@ class UniSE:
                 if 0 <= j < nb:  # stage 2: tokens of micro-batch k - 1
                     with torch.cuda.stream(s_lm):
                         s_lm.wait_event(ev_f[j])
-                        f, e, b = feats[j]
+                        f, e, b, rag = feats[j]
                         g, s = self.dnn.generate(task_name=mode, enroll_mel=None if e is None else _Frames(b, mel_frames(n_enr)), enroll_feats=e,
-                                                 mix_mel=_Frames(b, mel_frames(SEG_LEN)), mix_feats=f, do_sample=False)
+                                                 mix_mel=_Frames(b, mel_frames(SEG_LEN)), mix_feats=f, do_sample=False, **rag)
                         g.record_stream(s_dec)
                         s.record_stream(s_dec)
                         toks[j] = (g, s)
