@@ -192,6 +192,24 @@ def test_invariances_are_bit_exact(qa_lib, gpu_device):
     assert torch.equal(g0[0], g1[0]) and torch.equal(g0[1], g1[1])
 
 
+@pytest.mark.parametrize("B", [3, 65])
+def test_a_cacheless_step_equals_the_step_over_a_fresh_cache(qa_lib, gpu_device, B):
+    """The n = 1 step with its buffers and keys in the call's workspace (use_cache=False, capacity 16) against the same step over a
+    fresh KVCache of 16 positions, which brings its own: every hidden state bit for bit.  65 rows: the smallest batch that crosses
+    one group of 64, where the layer stride of the workspace's keys must be the whole call's and not the group's."""
+    import unified_audio_amd as qa
+
+    spec, dev = SMALL, gpu_device
+    sd, lm = _model(spec, 21, dev)
+    x = _embeds(sd, spec, 7, B, 1).to(dev)
+    plain = lm.llm_forward(x, use_cache=False, output_hidden_states=True)
+    cached = lm.llm_forward(x, past_key_values=qa.KVCache(lm, B, 16), use_cache=True, output_hidden_states=True)
+    assert torch.equal(plain.last_hidden_state, cached.last_hidden_state)
+    assert len(plain.hidden_states) == len(cached.hidden_states) == spec.n_layers + 1
+    for i, (a, b) in enumerate(zip(plain.hidden_states, cached.hidden_states)):
+        assert torch.equal(a, b), i
+
+
 @pytest.mark.parametrize("idx", [[3, 1, 0, 2], [1, 1, 1, 1], [2, 0], [0, 0, 1, 1, 2, 2, 3, 3]])
 def test_cache_select_equals_running_the_selected_sequences(qa_lib, gpu_device, idx):
     import unified_audio_amd as qa

@@ -217,9 +217,7 @@ int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mas
 
 // a batch item without a valid key has no attention output (the reference yields NaN): refused.  One small copy and one wait, masked calls only.
 int check_mask(qa_cond_encoder* h, const unsigned char* mask, int B, int T, hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-    QA_REQUIRE(cs != hipStreamCaptureStatusActive, "condition encoder: a masked call waits for its mask check on the host and cannot run under a "
+    QA_REQUIRE(!stream_capturing(s), "condition encoder: a masked call waits for its mask check on the host and cannot run under a "
                "stream capture (check the mask beforehand and pass the valid items unmasked, or call outside the capture)");
     if (B > h->host_cap) {
         if (h->host_counts) QA_HIP(hipHostFree(h->host_counts));

@@ -405,6 +405,14 @@ int plan(int device, hipStream_t stream, Ctx& c, Workspace& ws, G&& graph, P&& p
     return QA_OK;
 }
 
+// whether `s` is being captured into a hipGraph by its owner (a failed query clears the sticky error and counts as "no")
+inline bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess) return cs == hipStreamCaptureStatusActive;
+    (void)hipGetLastError();
+    return false;
+}
+
 // ---------------------------------------------------------------- test taps (the qa_*_tap / qa_*_enable_taps entry points)
 
 inline int taps_enable(Ctx* c, const char* fn, int on) {

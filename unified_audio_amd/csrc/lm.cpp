@@ -32,6 +32,13 @@ struct LMLayer {
 };
 constexpr int LM_MAX_POS = 4096;  // max_position_embeddings (conf/config.yaml:146)
 constexpr int LM_MAX_CHAINS = 16;
+
+// the buffers of the fused n = 1 step (lm_decode.hip) and the key split of its attention launch, placed by alloc_step
+struct StepBufs {
+    float *x = nullptr, *q = nullptr, *u = nullptr, *att_part = nullptr, *mlp_part = nullptr;
+    int* state = nullptr;
+    int att_tps = 0, S_att = 0;  // 16-key tiles per split, and the split count of a replayed step
+};
 }  // namespace
 
 struct StepGraph {  // one captured decode step of a phase, replayable because every loop-carried scalar lives in device state
@@ -58,9 +65,7 @@ struct qa_lm_cache {
     int len = 0;  // positions every row holds
     char* mem = nullptr;
     float *kc = nullptr, *vc = nullptr, *spare = nullptr;
-    float *x = nullptr, *q = nullptr, *u = nullptr, *att_part = nullptr, *mlp_part = nullptr;  // n = 1 step, min(max_batch, 64) rows
-    int* state = nullptr;
-    int att_tps = 0, S_att = 0;
+    StepBufs step;  // n = 1 step, min(max_batch, 64) rows
 };
 void cache_free(qa_lm_cache* c);
 
@@ -73,7 +78,7 @@ struct qa_lm : Handle {
     int nt_qkv = 0, nt_o = 0, nt_gu = 0, nt_down = 0;
     hipStream_t cap_stream = nullptr;
     std::vector<StepGraph> graphs;  // [2 * chain + phase]: phase 0 global, 1 semantic
-    std::vector<hipStream_t> chain_streams;  // internal streams of the chains of a B > 32 call
+    std::vector<hipStream_t> chain_streams;  // internal streams of the chains of a B > 64 call
     std::vector<hipEvent_t> chain_join;
     hipEvent_t ev_fork = nullptr;
     unsigned long long calls = 0;
@@ -90,12 +95,16 @@ struct qa_lm : Handle {
     bool taps = false;
     Workspace tap_buf;
     int64_t tap_n[2] = {-1, -1};
-    // qa_lm_score: a workspace and a tap buffer of its own, so that scoring never moves a buffer a captured decode step points into
+    // Three workspaces, one per family of entry points, because a call that grows its workspace frees the old buffer:
+    //   ws (Handle)  qa_lm_generate*: the captured decode steps point into it (they are keyed by its address)
+    //   score_ws     qa_lm_score*: scoring never moves a buffer a captured step points into
+    //   sess_ws      qa_lm_forward (n >= 2 chunks, cache-less calls) and qa_lm_prompt: a session never moves a buffer of generate or score
+    //                (the KV caches themselves are allocations of their own, qa_lm_cache)
+    // generate plans on Handle::ctx and the sessions on sess_ctx, which run_session and its callers' graph lambdas must both name.  Score
+    // plans on a Ctx on its stack: a Ctx carries nothing from one call to the next (plan re-arms it) and nothing else has to reach it.
     Workspace score_ws;
-    Workspace score_tap;  // logits.forced [B][Lt][V] of the last score call (taps on)
+    Workspace score_tap;  // logits.forced [B][Lt][V] of the last score call (taps on), an allocation of its own like tap_buf
     int64_t score_tap_n = -1;
-    // qa_lm_forward (n >= 2 chunks, cache-less calls), qa_lm_prompt: a third workspace, so that a session never moves a buffer of generate
-    // or score; the KV caches themselves are allocations of their own (qa_lm_cache)
     Workspace sess_ws;
     Ctx sess_ctx;
     std::vector<qa_lm_cache*> caches;  // live caches of this handle (qa_lm_destroy frees the ones the caller left)
@@ -239,17 +248,43 @@ int build_lm(qa_lm* lm, const HostTable& tab) {
 }
 
 struct LMBuffers {
-    float *x, *hn, *qkv, *att, *g, *u, *logits;
+    float *x, *hn, *qkv, *att, *g, *u;  // the prefill body (alloc_body)
+    StepBufs step;                       // the fused decode step (alloc_step)
     float *kc, *vc;
     long long* tok;
-    // fused decode step
-    float *q, *att_part, *pmax, *mlp_part;
-    int *pidx, *state;
+    float *logits, *pmax;  // head, pick / sample of generate's step
+    int* pidx;
     int* off;  // ragged generate: per-row position offsets L_b - L_max <= 0 (lm_decode.h GemvArgs::off); nullptr everywhere else
     long long *ids_g, *ids_s;
-    int cap, S_att, att_tps;  // cache capacity, the attention's split count of a replayed step and 16-key tiles per split
-    size_t layer_stride;      // floats between two layers of kc / vc; 0: B * cap * d (generate's arena); a qa_lm_cache: max_batch * max_len * d
+    int cap;              // cache capacity
+    size_t layer_stride;  // floats between two layers of kc / vc; 0: B * cap * d (generate's arena); a qa_lm_cache: max_batch * max_len * d
 };
+
+void alloc_body(Arena& a, LMBuffers& b, int64_t rows, int d, int I) {
+    b.x = a.alloc<float>(rows * d);
+    b.hn = a.alloc<float>(rows * d);
+    b.qkv = a.alloc<float>(rows * 3 * d);
+    b.att = a.alloc<float>(rows * d);
+    b.g = a.alloc<float>(rows * I);
+    b.u = a.alloc<float>(rows * I);
+}
+
+// The fused step's buffers for `rows` <= LM_MAX_ROWS rows over a cache of `cap` positions per row.  The attention's key split comes from
+// the capacity alone (never from the batch or the step): att_split keys per split, more once four splits would not cover the cache.
+// body == nullptr: x and u are allocated here like the rest.  body given (generate's chains only): s.x and s.u ALIAS body->x and body->u -
+// the step runs on the first rows of the prefill buffers it follows, so a chain plans no second x / u.
+void alloc_step(const qa_lm* lm, Arena& a, StepBufs& s, int rows, int cap, const LMBuffers* body = nullptr) {
+    const int d = lm->spec.hidden, I = lm->spec.intermediate, H = lm->spec.n_heads;
+    const int cap_tiles = (int)ceil_div(cap, 16);
+    s.att_tps = std::max(lm->att_split / 16, (int)ceil_div(cap_tiles, 4));
+    s.S_att = (int)ceil_div(cap_tiles, s.att_tps);
+    s.x = body ? body->x : a.alloc<float>((size_t)rows * d);
+    s.q = a.alloc<float>((size_t)rows * d);
+    s.u = body ? body->u : a.alloc<float>((size_t)rows * I);
+    s.att_part = a.alloc<float>((size_t)rows * H * s.S_att * (d / H + 4));
+    s.mlp_part = a.alloc<float>(lm->mlp_fused ? (size_t)(I / lm->mlp_ac) * 32 * ceil_div(rows, 32) * d : 0);  // [row group][I / ac][32][d]
+    s.state = a.alloc<int>(ST_WORDS);
+}
 
 // what a session step (qa_lm_forward, n = 1) hooks onto the layer loop of the fused step; generate passes none
 struct StepIO {
@@ -311,12 +346,13 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H, I = sp.intermediate;
     const float scale = 1.0f / std::sqrt((float)hd);
+    const StepBufs& sb = b.step;
     const long long kv_bstride = (long long)b.cap * d;
     const size_t cache_stride = b.layer_stride ? b.layer_stride : (size_t)B * b.cap * d;
-    // key split of the attention launch: split sp owns the fixed tile range [sp, sp + 1) * b.att_tps (lm_attn_kernel); a host-driven
+    // key split of the attention launch: split sp owns the fixed tile range [sp, sp + 1) * sb.att_tps (lm_attn_kernel); a host-driven
     // step launches the splits that hold keys, a replayed one all of them (the others write identity records): same bits either way.
     // Ragged batch: `pos` is the LONGEST row's position, so the count covers every row; a shorter row's surplus splits are identity records
-    const int S_att = pos >= 0 ? std::max(1, (int)ceil_div(ceil_div(pos + 1, 16), b.att_tps)) : b.S_att;
+    const int S_att = pos >= 0 ? std::max(1, (int)ceil_div(ceil_div(pos + 1, 16), sb.att_tps)) : sb.S_att;
     // cross-launch prefetch (QA_LM_PF, lm_decode.h PfArgs): which launch carries the prefetch plane for which consumer
     const long long pfk = knob(K_LM_PF);
     const bool fused_mlp = lm->mlp_fused;
@@ -335,9 +371,9 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
         float* kc = b.kc + i * cache_stride;
         float* vc = b.vc + i * cache_stride;
         if (io.hidden)
-            QA_HIP(hipMemcpyAsync(io.hidden + i * io.hidden_stride, i == 0 ? io.x_in : b.x, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
+            QA_HIP(hipMemcpyAsync(io.hidden + i * io.hidden_stride, i == 0 ? io.x_in : sb.x, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
         GemvArgs a{};
-        a.M = B; a.rms_eps = sp.rms_eps; a.state = b.state; a.pos = pos; a.off = b.off; a.H = H; a.hd = hd; a.d = d;
+        a.M = B; a.rms_eps = sp.rms_eps; a.state = sb.state; a.pos = pos; a.off = b.off; a.H = H; a.hd = hd; a.d = d;
         // o_proj's tile width (computed here: the qkv launch may prefetch its weights)
         int nt_o = lm->nt_o;
         if (gemv_r8_ok(d)) {
@@ -346,23 +382,23 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
         }
         // 1. RMSNorm + QKV + RoPE + cache append; layer 0 gathers its input rows from codec_embedding (llm_sft.py:140,169)
         GemvArgs q = a;
-        q.x = b.x; q.ldx = d;
+        q.x = sb.x; q.ldx = d;
         if (i == 0 && io.x_in) q.x = io.x_in;
         else if (i == 0) { q.tok = b.tok; q.table = lm->codec_emb; }
         q.w = L.qkv_dec; q.N = 3 * d; q.K = d;
-        q.rope = lm->rope; q.q = b.q; q.kc = kc; q.vc = vc; q.kv_bstride = kv_bstride;
+        q.rope = lm->rope; q.q = sb.q; q.kc = kc; q.vc = vc; q.kv_bstride = kv_bstride;
         PfArgs qpf{};
         if (pfk & 1) pf_region(qpf, 0, L.o.w, (long long)nt_o * d * 4, d / nt_o);
         QA_TRY(launch_lm_gemv(q, GM_QKV, lm->nt_qkv, s, &qpf));
         // 2. attention over the cache (pos + 1 keys), split over S_att workgroups per (sequence, head)
-        QA_TRY(launch_lm_attn(b.q, d, kc, vc, kv_bstride, d, b.att_part, B, H, hd, S_att, b.att_tps, b.state, scale, pos, s, b.off));
+        QA_TRY(launch_lm_attn(sb.q, d, kc, vc, kv_bstride, d, sb.att_part, B, H, hd, S_att, sb.att_tps, sb.state, scale, pos, s, b.off));
         // 3. merge of the partials + o_proj + residual
         GemvArgs o = a;
-        o.att_part = b.att_part; o.S = S_att;
+        o.att_part = sb.att_part; o.S = S_att;
         o.w = L.o.w; o.N = d; o.K = d; o.ldx = d;
         if (i == 0 && io.x_in) { o.res = io.x_in; }
-        else if (i == 0) { o.res_tok = b.tok; o.res_table = lm->codec_emb; } else { o.res = b.x; }
-        o.ldr = d; o.y = b.x; o.ldy = d;
+        else if (i == 0) { o.res_tok = b.tok; o.res_table = lm->codec_emb; } else { o.res = sb.x; }
+        o.ldr = d; o.y = sb.x; o.ldy = d;
         // tile width by the batch: the 8-row groups (lm_gemv4_kernel R8) hold a workgroup's pull of attention partials at 52 KB whatever the
         // batch, but every column tile re-reads and re-merges the partials of its rows - so the launch keeps ~256 workgroups: 4 columns x 2
         // row groups at 16 sequences, 8 x 4 at 32, 16 x 8 at 64 (r05 A/B, generate ms at 16 / 32 / 64 sequences: width 4 110.4 / 147.4 / 206.5,
@@ -372,20 +408,20 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
         QA_TRY(launch_lm_gemv(o, GM_RESID, nt_o, s, &opf));
         // 4. RMSNorm + gate / up + SwiGLU
         GemvArgs g = a;
-        g.x = b.x; g.ldx = d; g.w = L.gu_dec; g.N = 2 * I; g.K = d; g.y = b.u; g.ldy = I;
+        g.x = sb.x; g.ldx = d; g.w = L.gu_dec; g.N = 2 * I; g.K = d; g.y = sb.u; g.ldy = I;
         if (lm->mlp_fused && L.down_dec) {  // 4 + 5 as the fused MLP launch + the reduce launch (lm_decode.hip)
             PfArgs gpf{};
             if (pfk & 4) {
                 if (i + 1 < sp.n_layers) pf_region(gpf, 0, lm->layers[i + 1].qkv_dec, (long long)lm->nt_qkv * d * 4, 3 * d / lm->nt_qkv);
                 else if (width > 0) pf_region(gpf, 0, lm->head.w + (size_t)lo * d, (long long)head_nt(width) * d * 4, width / head_nt(width));
             }
-            QA_TRY(launch_lm_mlp(g, I, lm->mlp_ac, L.down_dec, b.mlp_part, b.x, d, b.x, d, s, &gpf));
+            QA_TRY(launch_lm_mlp(g, I, lm->mlp_ac, L.down_dec, sb.mlp_part, sb.x, d, sb.x, d, s, &gpf));
             continue;
         }
         QA_TRY(launch_lm_gemv(g, GM_GATEUP, lm->nt_gu, s));
         // 5. down_proj + residual
         GemvArgs dn = a;
-        dn.x = b.u; dn.ldx = I; dn.w = L.down.w; dn.N = d; dn.K = I; dn.res = b.x; dn.ldr = d; dn.y = b.x; dn.ldy = d;
+        dn.x = sb.u; dn.ldx = I; dn.w = L.down.w; dn.N = d; dn.K = I; dn.res = sb.x; dn.ldr = d; dn.y = sb.x; dn.ldy = d;
         QA_TRY(launch_lm_gemv(dn, GM_RESID, lm->nt_down, s));
     }
     return QA_OK;
@@ -403,8 +439,8 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
     //    mask of llm_sft.py:150-153 / :180-182 sets everything else to -inf) + per-tile arg-max
     const int nt = head_nt(width);
     GemvArgs hg{};
-    hg.M = B; hg.rms_eps = sp.rms_eps; hg.state = b.state; hg.pos = pos; hg.H = H; hg.hd = hd; hg.d = d;
-    hg.x = b.x; hg.ldx = d; hg.w = lm->head.w + (size_t)lo * d; hg.N = width; hg.K = d;
+    hg.M = B; hg.rms_eps = sp.rms_eps; hg.state = b.step.state; hg.pos = pos; hg.H = H; hg.hd = hd; hg.d = d;
+    hg.x = b.step.x; hg.ldx = d; hg.w = lm->head.w + (size_t)lo * d; hg.N = width; hg.K = d;
     hg.pmax = b.pmax; hg.pidx = b.pidx; hg.logits = (sc.do_sample || tap) ? b.logits : nullptr; hg.ldl = width;
     PfArgs hpf{};
     if (knob(K_LM_PF) & 8) {  // the next step's first weights (QA_LM_PF, as in fused_layers)
@@ -413,13 +449,13 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         hpf.n_tiles[0] = 3 * d / lm->nt_qkv;
     }
     QA_TRY(launch_lm_gemv(hg, GM_HEAD, nt, s, &hpf));
-    if (tap) QA_TRY(launch_lm_tap(b.logits, width, B, tap, tap_cols, b.state, col, s));
+    if (tap) QA_TRY(launch_lm_tap(b.logits, width, B, tap, tap_cols, b.step.state, col, s));
     // 7. next token
     if (!sc.do_sample) {
-        QA_TRY(launch_lm_pick(b.pmax, b.pidx, width / nt, B, lo, b.tok, ids, ids_ld, keep, b.state, col, s));
+        QA_TRY(launch_lm_pick(b.pmax, b.pidx, width / nt, B, lo, b.tok, ids, ids_ld, keep, b.step.state, col, s));
     } else {
-        QA_TRY(launch_lm_sample(b.logits, width, width, B, lo, sc.top_k, sc.top_p, sc.temperature, 1, b.tok, ids, ids_ld, keep, b.state, s));
-        QA_TRY(launch_lm_advance(b.state, s));
+        QA_TRY(launch_lm_sample(b.logits, width, width, B, lo, sc.top_k, sc.top_p, sc.temperature, 1, b.tok, ids, ids_ld, keep, b.step.state, s));
+        QA_TRY(launch_lm_advance(b.step.state, s));
     }
     return QA_OK;
 }
@@ -442,40 +478,70 @@ struct Chain {
     hipStream_t s = nullptr;
 };
 
-int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int Nm, int Ne, bool enroll, bool ragged) {
+// The prompt of a call, as every entry point that builds one describes it.  cond_mode: CustomLlamaModel's [mix_sos, cond] (cond
+// [B, Tc, d], already in the LM's width) or nothing (Tc = 0); otherwise LLM_SFT's [task, (enroll_sos, enroll)?, mix_sos, mix] from
+// features the adapter still has to project.  ne_rows (HOST, [B]; ragged generate): row b's enrollment frames,
+// 1 .. Ne - the prompt is then laid out for the LONGEST possible row (Ne frames)
+struct Prompt {
+    bool cond_mode;
+    const float* cond; int Tc;
+    int task;
+    const float* enroll; int Ne;  // nullptr and 0: no enrollment
+    const float* mix; int Nm;
+    const int* ne_rows;
+};
+
+Prompt speech_prompt(int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix) {
+    return Prompt{false, nullptr, 0, task, enroll_feats, enroll_feats ? (int)n_enroll : 0, mix_feats, (int)n_mix, nullptr};
+}
+Prompt cond_prompt(const float* cond_embeds, int64_t T) { return Prompt{true, cond_embeds, (int)T, 0, nullptr, 0, nullptr, 0, nullptr}; }
+
+int prompt_len(const Prompt& p) { return p.cond_mode ? (p.Tc > 0 ? p.Tc + 1 : 0) : 1 + (p.enroll ? 1 + p.Ne : 0) + 1 + p.Nm; }
+
+// The prompt rows (llm_sft.py:110-128 / llm.py:301-306) of sequences [b0, b0 + gb) into out [gb, prompt_len, d], on c.stream.  emix /
+// eenr: the adapter's output for these rows; off (ragged only, [gb], device) receives their position offsets.  Ragged: the adapter also
+// runs over the padding frames (a GEMM row depends on its own input row alone) and assemble_prompt never copies their outputs.
+int build_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix, float* eenr, float* out, int* off) {
+    const int d = lm->spec.hidden, F = lm->spec.feats_dim;
+    if (p.cond_mode) {
+        if (p.Tc > 0) QA_RUN(c, launch_cond_prompt(out, lm->mix_sos, p.cond + (size_t)b0 * p.Tc * d, gb, p.Tc, d, c.stream));
+        return QA_OK;
+    }
+    QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
+    if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
+    if (p.ne_rows) QA_RUN(c, launch_lm_offsets(off, p.ne_rows + b0, p.Ne, gb, c.stream));
+    QA_RUN(c, launch_assemble_prompt(out, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
+                                     p.Ne, p.Nm, d, c.stream, off));
+    return QA_OK;
+}
+
+struct GenArgs {
+    Prompt p;
+    int B, G, S;
+    SampleCfg sc;
+    int64_t *gids, *sids;
+};
+
+void chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, const GenArgs& a, int L, int cap) {
     const qa_lm_spec& sp = lm->spec;
-    const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads, B = ch.B;
+    const int d = sp.hidden, B = ch.B;
     const int64_t prow = (int64_t)B * std::max(L, 1);  // L = 0: the empty prompt of CustomLlamaModel.generate(cond=None); a step still needs its row
     LMBuffers& b = ch.b;
     b.cap = cap;
-    // the attention's key split, from the capacity alone (never from the batch or the step): att_split keys per split, more once
-    // four splits would not cover the cache
-    const int cap_tiles = (int)ceil_div(cap, 16);
-    b.att_tps = std::max(lm->att_split / 16, (int)ceil_div(cap_tiles, 4));
-    b.S_att = (int)ceil_div(cap_tiles, b.att_tps);
-    b.x = c.arena.alloc<float>(prow * d);
-    b.hn = c.arena.alloc<float>(prow * d);
-    b.qkv = c.arena.alloc<float>(prow * 3 * d);
-    b.att = c.arena.alloc<float>(prow * d);
-    b.g = c.arena.alloc<float>(prow * I);
-    b.u = c.arena.alloc<float>(prow * I);
+    alloc_body(c.arena, b, prow, d, sp.intermediate);
     const int wmax = std::max(sp.global_size, sp.semantic_size);
     b.logits = c.arena.alloc<float>((size_t)B * wmax);
     b.kc = c.arena.alloc<float>((size_t)sp.n_layers * B * cap * d);
     b.vc = c.arena.alloc<float>((size_t)sp.n_layers * B * cap * d);
     b.tok = c.arena.alloc<long long>(B);
-    b.q = c.arena.alloc<float>((size_t)B * d);
-    b.att_part = c.arena.alloc<float>((size_t)B * H * b.S_att * (d / H + 4));
-    b.mlp_part = c.arena.alloc<float>(lm->mlp_fused ? (size_t)(I / lm->mlp_ac) * 32 * ceil_div(B, 32) * d : 0);  // [row group][I / ac][32][d]
+    alloc_step(lm, c.arena, b.step, B, cap, &b);  // b.step.x and b.step.u are b.x and b.u, not allocations of their own
     b.pmax = c.arena.alloc<float>((size_t)B * (wmax / 4 + 1));
     b.pidx = c.arena.alloc<int>((size_t)B * (wmax / 4 + 1));
-    b.state = c.arena.alloc<int>(ST_WORDS);
-    b.ids_g = c.arena.alloc<long long>((size_t)B * std::max(G, 1));
-    b.ids_s = c.arena.alloc<long long>((size_t)B * std::max(S, 1));
-    ch.emix = c.arena.alloc<float>((size_t)B * Nm * d);
-    ch.eenr = enroll ? c.arena.alloc<float>((size_t)B * Ne * d) : nullptr;
-    b.off = ragged ? c.arena.alloc<int>(B) : nullptr;  // last, and only then: a rectangular call keeps the layout it had
-    return QA_OK;
+    b.ids_g = c.arena.alloc<long long>((size_t)B * std::max(a.G, 1));
+    b.ids_s = c.arena.alloc<long long>((size_t)B * std::max(a.S, 1));
+    ch.emix = c.arena.alloc<float>((size_t)B * a.p.Nm * d);
+    ch.eenr = a.p.enroll ? c.arena.alloc<float>((size_t)B * a.p.Ne * d) : nullptr;
+    b.off = a.p.ne_rows ? c.arena.alloc<int>(B) : nullptr;  // last, and only then: a rectangular call keeps the layout it had
 }
 
 // r05: up to 64 sequences are ONE chain - every GEMV / fused-MLP launch of the step carries two row groups of 32 (gridDim.y, lm_decode.hip
@@ -485,28 +551,22 @@ int chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, int L, int cap, int G, int S, int 
 // (DESIGN.md section 11), so chains overlap nearly for free - tokens/s scales with the number of chains until the CUs fill.  Every
 // chain replays ONE captured step per token (hipGraph), round-robin over the chains, so the host issues two graph launches per
 // step instead of 124 kernel launches (eager launches go host-bound below ~3 us per kernel).  QA_LM_CHAINS forces a chain count.
-// cond_mode: CustomLlamaModel.generate (llm.py:291-374) - the prompt is [mix_sos, cond] (cond [B, Tc, d], already in the LM's width) or
-// empty (Tc = 0), and the global phase runs exactly G steps: its last token is returned but never fed (llm.py:318,345)
-int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, const float* mix, int Nm, int B, int G,
-                   int S, long long* gids, long long* sids, const SampleCfg& sc, bool cond_mode = false, const float* cond = nullptr,
-                   int Tc = 0, const int* ne_rows = nullptr) {
-    // ne_rows (HOST, [B]; qa_lm_generate_ragged): row b's enrollment frames, 1 .. Ne.  L, pos and the capacity below
-    // are then the LONGEST possible row's (Ne frames); the rows' own positions follow from the per-chain offset array b.off
+// cond_mode: CustomLlamaModel.generate (llm.py:291-374) - the global phase runs exactly G steps: its last token is returned but never
+// fed (llm.py:318,345)
+int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
+    // ragged: L, pos and the capacity below are the LONGEST possible row's; the rows' own positions follow from the per-chain offsets b.off
     const qa_lm_spec& sp = lm->spec;
-    const int d = sp.hidden;
-    const int L = cond_mode ? (Tc > 0 ? Tc + 1 : 0) : 1 + (enroll ? 1 + Ne : 0) + 1 + Nm;
-    const int Gs = cond_mode ? G : G + 1;  // steps of the global phase
+    const Prompt& p = a.p;
+    const SampleCfg& sc = a.sc;
+    const int B = a.B, G = a.G, S = a.S;
+    const int L = prompt_len(p);
+    const int Gs = p.cond_mode ? G : G + 1;  // steps of the global phase
     const int max_len = L + Gs + S;
     QA_REQUIRE(max_len <= LM_MAX_POS, "generate: %d positions exceed max_position_embeddings %d", max_len, LM_MAX_POS);
     const int cap = (int)round_up(max_len, 64);  // cache row stride: shapes that round alike share their captured step graphs
     // A caller that is CAPTURING its stream into a hipGraph gets the plain single-chain launches on that stream only: no
     // internal streams, no capture of our own inside theirs (the multi-chain replay path would fail there where the eager path works).
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c.stream, &cap_status) != hipSuccess) {
-        (void)hipGetLastError();
-        cap_status = hipStreamCaptureStatusNone;
-    }
-    const bool capturing = cap_status == hipStreamCaptureStatusActive;
+    const bool capturing = stream_capturing(c.stream);
     int nc = (int)knob(K_LM_CHAINS);
     if (nc <= 0) nc = (int)ceil_div(B, LM_MAX_ROWS);  // r05: one chain serves up to 64 sequences (two row groups per launch)
     if (capturing) nc = 1;
@@ -519,7 +579,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     for (int i = 0; i < nc; ++i) {
         chains[i].b0 = i * cb;
         chains[i].B = std::min(cb, B - i * cb);
-        QA_TRY(chain_alloc(lm, c, chains[i], L, cap, G, S, Nm, Ne, enroll != nullptr, ne_rows != nullptr));
+        chain_alloc(lm, c, chains[i], a, L, cap);
     }
     if (c.dry) return QA_OK;  // real-pass-only remainder: chain_alloc above made the function's last arena allocations
     const bool multi = nc > 1;
@@ -546,31 +606,12 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     // ---- prompt (llm_sft.py:110-128) and prefill (llm_sft.py:130-135), chain by chain (these launches fill the device by themselves)
     for (Chain& ch : chains) {
         c.stream = ch.s;
-        if (cond_mode) {
-            int st = QA_OK;
-            if (L > 0) {
-                st = launch_cond_prompt(ch.b.x, lm->mix_sos, cond + (size_t)ch.b0 * Tc * d, ch.B, Tc, d, ch.s);
-                if (st == QA_OK) st = lm_body(lm, c, ch.b, ch.B, L, 0, cap, true);
-            }
-            c.stream = caller;
-            QA_TRY(st);
-            continue;
-        }
-        const float* mix_c = mix + (size_t)ch.b0 * Nm * sp.feats_dim;
-        const float* enr_c = enroll ? enroll + (size_t)ch.b0 * Ne * sp.feats_dim : nullptr;
-        int st = linear_op(c, mix_c, (int64_t)ch.B * Nm, lm->adapter, ch.emix);
-        // ragged: the adapter also runs over the padding frames (a GEMM row depends on its own input row alone) and assemble_prompt
-        // never copies their outputs
-        if (st == QA_OK && enroll) st = linear_op(c, enr_c, (int64_t)ch.B * Ne, lm->adapter, ch.eenr);
-        if (st == QA_OK && ne_rows) st = launch_lm_offsets(ch.b.off, ne_rows + ch.b0, Ne, ch.B, ch.s);
-        if (st == QA_OK)
-            st = launch_assemble_prompt(ch.b.x, lm->task_emb + (size_t)task * d, enroll ? lm->enroll_sos : nullptr, ch.eenr, lm->mix_sos,
-                                        ch.emix, ch.B, Ne, Nm, d, ch.s, ch.b.off);
+        int st = build_prompt(lm, c, p, ch.b0, ch.B, ch.emix, ch.eenr, ch.b.x, ch.b.off);
         // Ragged: the prefill runs unchanged over L = L_max positions and needs NO mask.  It is causal, so a valid query (position < L_b)
         // never sees a key behind itself, least of all the zero rows at L_b .. L - 1.  The queries of those zero rows are finite garbage
         // that nothing consumes (the prefill's last hidden state is not used, only its K / V), and the K / V rows they leave at L_b + t
         // are overwritten by decode step t before that step - the first to count them among its L_b + t + 1 keys - reads them.
-        if (st == QA_OK) st = lm_body(lm, c, ch.b, ch.B, L, 0, cap, true);
+        if (st == QA_OK && L > 0) st = lm_body(lm, c, ch.b, ch.B, L, 0, cap, true);
         c.stream = caller;
         QA_TRY(st);
     }
@@ -585,7 +626,7 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
         float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * Gs * sp.global_size) : nullptr;
         auto chain_tap = [&](const Chain& ch) { return tap ? tap + (size_t)ch.b0 * steps * width : nullptr; };
         for (Chain& ch : chains)
-            QA_TRY(launch_lm_phase_init(ch.b.tok, first_id, ch.B, ch.b.state, pos, which == 0, sc.seed, ch.b0, ch.s));
+            QA_TRY(launch_lm_phase_init(ch.b.tok, first_id, ch.B, ch.b.step.state, pos, which == 0, sc.seed, ch.b0, ch.s));
         if (graphs && steps > 0) {
             if ((int)lm->graphs.size() < 2 * nc) lm->graphs.resize(2 * nc);
             for (int i = 0; i < nc; ++i) {
@@ -594,10 +635,10 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
                 StepGraph& g = lm->graphs[2 * i + which];
                 uint64_t key = 0x51ull;
                 for (uint64_t v : {(uint64_t)(uintptr_t)lm->ws.ptr, (uint64_t)B, (uint64_t)nc, (uint64_t)ch.b0, (uint64_t)ch.B, (uint64_t)cap, (uint64_t)L,
-                                   (uint64_t)G, (uint64_t)S, (uint64_t)Ne, (uint64_t)Nm, (uint64_t)(enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
+                                   (uint64_t)G, (uint64_t)S, (uint64_t)p.Ne, (uint64_t)p.Nm, (uint64_t)(p.enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
                                    (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF),
-                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch), (uint64_t)cond_mode,
-                                   (uint64_t)(ne_rows != nullptr)})  // ragged or not - never the lengths: they live in device memory (b.off)
+                                   (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch), (uint64_t)p.cond_mode,
+                                   (uint64_t)(p.ne_rows != nullptr)})  // ragged or not - never the lengths: they live in device memory (b.off)
                     key = mix_key(key, v);
                 if (!g.exec || g.key != key) {
                     g.reset();
@@ -633,9 +674,9 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
     for (int i = 0; i < nc; ++i) {
         Chain& ch = chains[i];
         if (G > 0)
-            QA_HIP(hipMemcpyAsync(gids + (size_t)ch.b0 * G, ch.b.ids_g, sizeof(long long) * (size_t)ch.B * G, hipMemcpyDeviceToDevice, ch.s));
+            QA_HIP(hipMemcpyAsync(a.gids + (size_t)ch.b0 * G, ch.b.ids_g, sizeof(long long) * (size_t)ch.B * G, hipMemcpyDeviceToDevice, ch.s));
         if (S > 0)
-            QA_HIP(hipMemcpyAsync(sids + (size_t)ch.b0 * S, ch.b.ids_s, sizeof(long long) * (size_t)ch.B * S, hipMemcpyDeviceToDevice, ch.s));
+            QA_HIP(hipMemcpyAsync(a.sids + (size_t)ch.b0 * S, ch.b.ids_s, sizeof(long long) * (size_t)ch.B * S, hipMemcpyDeviceToDevice, ch.s));
         if (multi) {  // join: the caller's stream continues behind every chain
             QA_HIP(hipEventRecord(lm->chain_join[i], ch.s));
             QA_HIP(hipStreamWaitEvent(caller, lm->chain_join[i], 0));
@@ -649,11 +690,8 @@ int generate_graph(qa_lm* lm, Ctx& c, int task, const float* enroll, int Ne, con
 // rows of input_ids behind it, the body over all Lp + Lt positions from position 0 with every layer, the final RMSNorm on the Lt target
 // rows, then output_head over the full vocabulary in chunks of QA_LM_SCORE_ROWS rows, each reduced by the row-loss kernel right behind it.
 struct ScoreArgs {
-    bool cond_mode;  // CustomLlamaModel.forward (llm.py:107-147): prompt [mix_sos, cond] or none, the last position dropped
-    const float* cond;
-    int Tc;
-    int task, Ne, Nm, B, G, T;
-    const float *enroll, *mix;
+    Prompt p;  // cond_mode: CustomLlamaModel.forward (llm.py:107-147), prompt [mix_sos, cond] or none, the last position dropped
+    int B, G, T;
     const long long *gids, *sids;
     double eps;
     float* loss_seq;
@@ -663,24 +701,21 @@ struct ScoreArgs {
 
 int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const qa_lm_spec& sp = lm->spec;
-    const int d = sp.hidden, I = sp.intermediate, V = vocab_of(sp);
-    const int Lp = a.cond_mode ? (a.Tc > 0 ? a.Tc + 1 : 0) : 1 + (a.enroll ? 1 + a.Ne : 0) + 1 + a.Nm;
-    const int Lt = a.G + a.T + 2 - (a.cond_mode ? 1 : 0), n = Lp + Lt;
+    const int d = sp.hidden, V = vocab_of(sp);
+    const Prompt& p = a.p;
+    const int Lp = prompt_len(p);
+    const int Lt = a.G + a.T + 2 - (p.cond_mode ? 1 : 0), n = Lp + Lt;
     QA_REQUIRE(n <= LM_MAX_POS, "qa_lm_score: %d positions (prompt %d + targets %d) exceed max_position_embeddings %d", n, Lp, Lt, LM_MAX_POS);
     const int GB = std::min(a.B, LM_MAX_ROWS);
     const int64_t prow = (int64_t)GB * n, trow = (int64_t)GB * Lt;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(knob(K_LM_SCORE_ROWS), trow));
     LMBuffers b{};
-    b.x = c.arena.alloc<float>(prow * d);
-    b.hn = c.arena.alloc<float>(prow * d);   // also the assembled prompt (before the body) and the normalised target rows (after it)
-    b.qkv = c.arena.alloc<float>(prow * 3 * d);
-    b.att = c.arena.alloc<float>(prow * d);  // also the compacted target rows (after the body)
-    b.g = c.arena.alloc<float>(prow * I);
-    b.u = c.arena.alloc<float>(prow * I);
+    // b.hn is also the assembled prompt (before the body) and the normalised target rows (after it), b.att the compacted target rows
+    alloc_body(c.arena, b, prow, d, sp.intermediate);
     b.kc = c.arena.alloc<float>(prow * d);   // one layer's cache, shared by all layers (lm_body one_cache)
     b.vc = c.arena.alloc<float>(prow * d);
-    float* emix = c.arena.alloc<float>((size_t)GB * a.Nm * d);
-    float* eenr = a.enroll ? c.arena.alloc<float>((size_t)GB * a.Ne * d) : nullptr;
+    float* emix = c.arena.alloc<float>((size_t)GB * p.Nm * d);
+    float* eenr = p.enroll ? c.arena.alloc<float>((size_t)GB * p.Ne * d) : nullptr;
     long long* tgt = c.arena.alloc<long long>(trow);
     float* row_kl = c.arena.alloc<float>(trow);
     int* row_ok = c.arena.alloc<int>(trow);
@@ -691,19 +726,12 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const float conf = (float)(1.0 - a.eps), smooth = (float)(a.eps / (V - 1));
     for (int b0 = 0; b0 < a.B; b0 += GB) {
         const int gb = std::min(GB, a.B - b0);
-        if (a.cond_mode) {
-            if (Lp > 0) QA_TRY(launch_cond_prompt(b.hn, lm->mix_sos, a.cond + (size_t)b0 * a.Tc * d, gb, a.Tc, d, c.stream));
-        } else {
-            QA_TRY(linear_op(c, a.mix + (size_t)b0 * a.Nm * sp.feats_dim, (int64_t)gb * a.Nm, lm->adapter, emix));
-            if (a.enroll) QA_TRY(linear_op(c, a.enroll + (size_t)b0 * a.Ne * sp.feats_dim, (int64_t)gb * a.Ne, lm->adapter, eenr));
-            QA_TRY(launch_assemble_prompt(b.hn, lm->task_emb + (size_t)a.task * d, a.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
-                                          a.Ne, a.Nm, d, c.stream));
-        }
+        QA_TRY(build_prompt(lm, c, p, b0, gb, emix, eenr, b.hn, nullptr));
         if (Lp > 0)
             QA_HIP(hipMemcpy2DAsync(b.x, sizeof(float) * n * d, b.hn, sizeof(float) * Lp * d, sizeof(float) * Lp * d, gb, hipMemcpyDeviceToDevice,
                                     c.stream));
         QA_TRY(launch_lm_targets(b.x + (size_t)Lp * d, (long long)n * d, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T,
-                                 a.T, V, 3, 3 + sp.global_size, tgt, gb, d, c.stream, a.cond_mode ? 1 : 0));
+                                 a.T, V, 3, 3 + sp.global_size, tgt, gb, d, c.stream, p.cond_mode ? 1 : 0));
         QA_TRY(lm_body(lm, c, b, gb, n, 0, n, false, true));
         // final RMSNorm (its weight is folded into output_head) on the last Lt rows of every sequence (llm_sft.py:82)
         QA_HIP(hipMemcpy2DAsync(b.att, sizeof(float) * Lt * d, b.x + (size_t)Lp * d, sizeof(float) * n * d, sizeof(float) * Lt * d, gb,
@@ -734,31 +762,19 @@ int grow_step_buffer(qa_lm* lm, Workspace& w, size_t bytes) {
 
 // the tap storage of a B x (G + 1, S) call: its own allocation, grown like the workspace
 int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) != hipSuccess) (void)hipGetLastError();
-    QA_REQUIRE(cs != hipStreamCaptureStatusActive, "qa_lm_generate: taps (a test hook) are not supported under a stream capture");
+    QA_REQUIRE(!stream_capturing(static_cast<hipStream_t>(stream)), "qa_lm_generate: taps (a test hook) are not supported under a stream capture");
     const size_t n = (size_t)B * ((size_t)(G + 1) * lm->spec.global_size + (size_t)S * lm->spec.semantic_size);
     return grow_step_buffer(lm, lm->tap_buf, sizeof(float) * n);
 }
-
 
 // ---- sessions: qa_lm_forward over a caller-held qa_lm_cache (CustomLlamaModel.llm_forward, llm.py:150-227)
 
 // Length and batch of a cache are host state, so a session call cannot be recorded into a caller's graph: a replay would run with the
 // positions of the capture.  Refused, with the reason.
 int refuse_capture(const char* fn, hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-    QA_REQUIRE(cs != hipStreamCaptureStatusActive,
+    QA_REQUIRE(!stream_capturing(s),
                "%s: refused under a stream capture - the cache length is host state, a replayed graph would repeat the captured positions", fn);
     return QA_OK;
-}
-
-// the attention's key split of the n = 1 step, from the capacity alone (as chain_alloc)
-void att_split_of(const qa_lm* lm, int cap, int* tps, int* S) {
-    const int cap_tiles = (int)ceil_div(cap, 16);
-    *tps = std::max(lm->att_split / 16, (int)ceil_div(cap_tiles, 4));
-    *S = (int)ceil_div(cap_tiles, *tps);
 }
 
 struct ForwardArgs {
@@ -770,7 +786,7 @@ struct ForwardArgs {
 
 int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
     const qa_lm_spec& sp = lm->spec;
-    const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads, B = a.B, n = a.n;
+    const int d = sp.hidden, B = a.B, n = a.n;
     const int pos0 = a.cache ? a.cache->len : 0;
     const int64_t rows = (int64_t)B * n;
     const bool step = n == 1 && lm->fused_ok;
@@ -780,22 +796,14 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
         b.vc = a.cache->vc;
         b.cap = a.cache->max_len;
         b.layer_stride = (size_t)a.cache->max_batch * a.cache->max_len * d;
-        b.att_tps = a.cache->att_tps;
-        b.S_att = a.cache->S_att;
     } else {  // every layer keeps its own keys here too: the n = 1 step appends to layer i's cache before layer i's attention reads it
         b.cap = (int)round_up(n, 16);
         b.kc = c.arena.alloc<float>((size_t)sp.n_layers * B * b.cap * d);
         b.vc = c.arena.alloc<float>((size_t)sp.n_layers * B * b.cap * d);
-        att_split_of(lm, b.cap, &b.att_tps, &b.S_att);
     }
     const size_t hs = (size_t)rows * d;  // one entry of all_hidden
     if (!step) {
-        b.x = c.arena.alloc<float>(rows * d);
-        b.hn = c.arena.alloc<float>(rows * d);
-        b.qkv = c.arena.alloc<float>(rows * 3 * d);
-        b.att = c.arena.alloc<float>(rows * d);
-        b.g = c.arena.alloc<float>(rows * I);
-        b.u = c.arena.alloc<float>(rows * I);
+        alloc_body(c.arena, b, rows, d, sp.intermediate);
         if (c.dry) return QA_OK;  // real-pass-only remainder
         QA_HIP(hipMemcpyAsync(b.x, a.x, sizeof(float) * hs, hipMemcpyDeviceToDevice, c.stream));
         QA_TRY(lm_body(lm, c, b, B, n, pos0, b.cap, false, false, a.all_hidden));
@@ -803,17 +811,8 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
     } else {
         // the fused step's launches on the caller's rows, at most LM_MAX_ROWS of them per pass (a row's arithmetic does not know its group)
         const int GB = std::min(B, LM_MAX_ROWS);
-        if (a.cache) {
-            b.x = a.cache->x; b.q = a.cache->q; b.u = a.cache->u; b.att_part = a.cache->att_part; b.mlp_part = a.cache->mlp_part;
-            b.state = a.cache->state;
-        } else {
-            b.x = c.arena.alloc<float>((size_t)GB * d);
-            b.q = c.arena.alloc<float>((size_t)GB * d);
-            b.u = c.arena.alloc<float>((size_t)GB * I);
-            b.att_part = c.arena.alloc<float>((size_t)GB * H * b.S_att * (d / H + 4));
-            b.mlp_part = c.arena.alloc<float>(lm->mlp_fused ? (size_t)(I / lm->mlp_ac) * 32 * ceil_div(GB, 32) * d : 0);
-            b.state = c.arena.alloc<int>(ST_WORDS);  // never read: the position is a launch argument
-        }
+        if (a.cache) b.step = a.cache->step;
+        else alloc_step(lm, c.arena, b.step, GB, b.cap);  // its state words are never read: the position is a launch argument
         if (c.dry) return QA_OK;  // real-pass-only remainder
         const size_t row_stride = (size_t)b.cap * d;
         for (int b0 = 0; b0 < B; b0 += GB) {
@@ -829,7 +828,7 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
                 io.hidden_stride = hs;
             }
             QA_TRY(fused_layers(lm, g, gb, 0, 0, c.stream, pos0, io));
-            QA_TRY(launch_rmsnorm(b.x, lm->norm_w, a.last_hidden + (size_t)b0 * d, gb, d, sp.rms_eps, c.stream));
+            QA_TRY(launch_rmsnorm(b.step.x, lm->norm_w, a.last_hidden + (size_t)b0 * d, gb, d, sp.rms_eps, c.stream));
         }
     }
     if (a.all_hidden)  // llm.py:216-220: the last entry is the final norm's output
@@ -936,24 +935,17 @@ int qa_lm_cache_create(qa_lm* lm, int64_t max_batch, int64_t max_len, qa_lm_cach
                (long long)max_len, LM_MAX_POS);
     QA_HIP(hipSetDevice(lm->device));
     const qa_lm_spec& sp = lm->spec;
-    const int d = sp.hidden, I = sp.intermediate, H = sp.n_heads;
     std::unique_ptr<qa_lm_cache> c(new qa_lm_cache());
     c->max_batch = (int)max_batch;
     c->max_len = (int)max_len;
-    att_split_of(lm, c->max_len, &c->att_tps, &c->S_att);
     const int GB = (int)std::min<int64_t>(max_batch, LM_MAX_ROWS);
     Arena layout;  // sizes the one allocation, then places the buffers in it
     auto place = [&] {
-        const size_t plane = (size_t)sp.n_layers * max_batch * max_len * d;
+        const size_t plane = (size_t)sp.n_layers * max_batch * max_len * sp.hidden;
         c->kc = layout.alloc<float>(plane);
         c->vc = layout.alloc<float>(plane);
-        c->spare = layout.alloc<float>((size_t)sp.n_layers * 2 * max_len * d);
-        c->x = layout.alloc<float>((size_t)GB * d);
-        c->q = layout.alloc<float>((size_t)GB * d);
-        c->u = layout.alloc<float>((size_t)GB * I);
-        c->att_part = layout.alloc<float>((size_t)GB * H * c->S_att * (d / H + 4));
-        c->mlp_part = layout.alloc<float>(lm->mlp_fused ? (size_t)(I / lm->mlp_ac) * 32 * ceil_div(GB, 32) * d : 0);
-        c->state = layout.alloc<int>(ST_WORDS);
+        c->spare = layout.alloc<float>((size_t)sp.n_layers * 2 * max_len * sp.hidden);
+        alloc_step(lm, layout, c->step, GB, c->max_len);
     };
     layout.begin(nullptr, 0);
     place();
@@ -1097,16 +1089,13 @@ int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_e
     QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_prompt: task %d out of range (KeyError in the reference)", task);
     QA_REQUIRE(B >= 1 && n_mix >= 1 && n_mix <= LM_MAX_POS && B <= (1 << 16), "qa_lm_prompt: bad shape");
     QA_REQUIRE(!enroll_feats || (n_enroll >= 1 && n_enroll <= LM_MAX_POS), "qa_lm_prompt: enrollment given with no frames");
-    const int d = lm->spec.hidden, Ne = enroll_feats ? (int)n_enroll : 0, Nm = (int)n_mix;
+    const Prompt p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
+    const int d = lm->spec.hidden;
     Ctx& c = lm->sess_ctx;
     return run_session(lm, s, [&]() -> int {
-        float* emix = c.arena.alloc<float>((size_t)B * Nm * d);
-        float* eenr = enroll_feats ? c.arena.alloc<float>((size_t)B * Ne * d) : nullptr;
-        QA_TRY(linear_op(c, mix_feats, B * Nm, lm->adapter, emix));
-        if (enroll_feats) QA_TRY(linear_op(c, enroll_feats, B * Ne, lm->adapter, eenr));
-        QA_RUN(c, launch_assemble_prompt(out, lm->task_emb + (size_t)task * d, enroll_feats ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix,
-                                         (int)B, Ne, Nm, d, c.stream));
-        return QA_OK;
+        float* emix = c.arena.alloc<float>((size_t)B * p.Nm * d);
+        float* eenr = p.enroll ? c.arena.alloc<float>((size_t)B * p.Ne * d) : nullptr;
+        return build_prompt(lm, c, p, 0, (int)B, emix, eenr, out, nullptr);
     });
 }
 
@@ -1127,54 +1116,58 @@ int qa_lm_create(qa_lm** out, const qa_lm_spec* spec, const qa_tensor* tensors, 
 
 void qa_lm_destroy(qa_lm* lm) { destroy_handle(lm); }
 
-static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
-                            int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc,
-                            int64_t* global_ids, int64_t* semantic_ids, void* stream, bool cond_mode = false, const float* cond = nullptr,
-                            int64_t Tc = 0, const int64_t* ne_rows = nullptr, bool ragged = false) {
-    // ragged (qa_lm_generate_ragged*): n_enroll is n_enroll_max and ne_rows the HOST vector of the rows' own frame counts
-    const char* fn = cond_mode ? "qa_lm_generate_cond" : ragged ? "qa_lm_generate_ragged" : "qa_lm_generate";
-    if (!lm || (!cond_mode && !mix_feats) || !global_ids || !semantic_ids) {
+// what the six generate entry points share; each then sets its prompt
+static GenArgs gen_args(int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc, int64_t* global_ids, int64_t* semantic_ids) {
+    GenArgs a{};
+    a.B = (int)B; a.G = global_length; a.S = semantic_length; a.sc = sc; a.gids = global_ids; a.sids = semantic_ids;
+    return a;
+}
+
+// ragged (qa_lm_generate_ragged*): a.p.Ne is n_enroll_max and ne_rows64 the caller's HOST vector [B] of the rows' own frame counts, which is
+// checked here and handed on as a.p.ne_rows
+static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = false, const int64_t* ne_rows64 = nullptr) {
+    Prompt& p = a.p;
+    const char* fn = p.cond_mode ? "qa_lm_generate_cond" : ragged ? "qa_lm_generate_ragged" : "qa_lm_generate";
+    if (!lm || (!p.cond_mode && !p.mix) || !a.gids || !a.sids) {
         set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(cond_mode || (task >= 0 && task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, task);
-    QA_REQUIRE(B > 0 && (cond_mode || n_mix > 0) && global_length >= 0 && semantic_length >= 0, "%s: bad shape", fn);
-    QA_REQUIRE(!cond_mode || (Tc >= 0 && Tc < LM_MAX_POS && (cond != nullptr) == (Tc > 0) && global_length + semantic_length > 0),
-               "qa_lm_generate_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %lld); at least one step", (long long)Tc);
-    QA_REQUIRE(!enroll_feats || n_enroll > 0, "%s: enrollment given with no frames", fn);
+    const SampleCfg& sc = a.sc;
+    QA_REQUIRE(p.cond_mode || (p.task >= 0 && p.task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, p.task);
+    QA_REQUIRE(a.B > 0 && (p.cond_mode || p.Nm > 0) && a.G >= 0 && a.S >= 0, "%s: bad shape", fn);
+    QA_REQUIRE(!p.cond_mode || (p.Tc >= 0 && p.Tc < LM_MAX_POS && (p.cond != nullptr) == (p.Tc > 0) && a.G + a.S > 0),
+               "qa_lm_generate_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %d); at least one step", p.Tc);
+    QA_REQUIRE(!p.enroll || p.Ne > 0, "%s: enrollment given with no frames", fn);
     QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "%s: temperature must be in (0, 1] (llm.py:278)", fn);
     QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "%s: bad top_k / top_p", fn);
     std::vector<int> ne_host;  // every check of a ragged call comes before the first launch: a refused call has launched nothing
     if (ragged) {
-        QA_REQUIRE(enroll_feats && ne_rows, "%s: per-row enrollment lengths need enroll_feats [B, n_enroll_max, feats_dim] and n_enroll [B]", fn);
-        const long long total = 3 + (long long)n_enroll + n_mix + global_length + 1 + semantic_length;
-        QA_REQUIRE(total <= LM_MAX_POS, "%s: %lld positions (3 + n_enroll_max %lld + n_mix %lld + %d + 1 + %d) exceed max_position_embeddings %d",
-                   fn, total, (long long)n_enroll, (long long)n_mix, global_length, semantic_length, LM_MAX_POS);
-        ne_host.resize((size_t)B);
-        for (int64_t i = 0; i < B; ++i) {
-            QA_REQUIRE(ne_rows[i] >= 1 && ne_rows[i] <= n_enroll, "%s: n_enroll[%lld] = %lld is outside 1 .. n_enroll_max = %lld", fn,
-                       (long long)i, (long long)ne_rows[i], (long long)n_enroll);
-            ne_host[(size_t)i] = (int)ne_rows[i];
+        QA_REQUIRE(p.enroll && ne_rows64, "%s: per-row enrollment lengths need enroll_feats [B, n_enroll_max, feats_dim] and n_enroll [B]", fn);
+        const long long total = (long long)prompt_len(p) + a.G + 1 + a.S;
+        QA_REQUIRE(total <= LM_MAX_POS,
+                   "%s: %lld positions (prompt %d with n_enroll_max %d and n_mix %d, + %d + 1 + %d) exceed max_position_embeddings %d", fn,
+                   total, prompt_len(p), p.Ne, p.Nm, a.G, a.S, LM_MAX_POS);
+        ne_host.resize((size_t)a.B);
+        for (int i = 0; i < a.B; ++i) {
+            QA_REQUIRE(ne_rows64[i] >= 1 && ne_rows64[i] <= p.Ne, "%s: n_enroll[%d] = %lld is outside 1 .. n_enroll_max = %d", fn, i,
+                       (long long)ne_rows64[i], p.Ne);
+            ne_host[(size_t)i] = (int)ne_rows64[i];
         }
+        p.ne_rows = ne_host.data();
     }
     QA_HIP(hipSetDevice(lm->device));
     if (sc.do_sample) QA_TRY(lm_sample_prepare());
     lm->tap_n[0] = lm->tap_n[1] = -1;
-    if (lm->taps) QA_TRY(ensure_taps(lm, B, global_length, semantic_length, stream));
+    if (lm->taps) QA_TRY(ensure_taps(lm, a.B, a.G, a.S, stream));
     Ctx& c = lm->ctx;
     c.gemm_fp32 = true;  // ConvParams::math_fp32
     c.att_fp32 = true;   // the prefill attention stays consistent with the fp32 decode kernels
-    auto graph = [&] {
-        return generate_graph(lm, c, task, enroll_feats, (int)n_enroll, mix_feats, (int)n_mix, (int)B, global_length, semantic_length,
-                              (long long*)global_ids, (long long*)semantic_ids, sc, cond_mode, cond, (int)Tc, ragged ? ne_host.data() : nullptr);
-    };
+    auto graph = [&] { return generate_graph(lm, c, a); };
     QA_TRY(plan(lm->device, static_cast<hipStream_t>(stream), c, lm->ws, graph, [&](size_t bytes) -> int {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(c.stream, &cs) != hipSuccess) (void)hipGetLastError();
         // growing the workspace synchronises the device and allocates: neither is possible inside a caller's stream capture
-        QA_REQUIRE(cs != hipStreamCaptureStatusActive,
+        QA_REQUIRE(!stream_capturing(c.stream),
                    "qa_lm_generate under a stream capture needs %zu bytes of workspace, the handle holds %zu: make one call of the same shape outside "
-                   "the capture first (with QA_LM_CHAINS=1 for batches above 32: a capturing caller gets the single-chain launches)",
+                   "the capture first (with QA_LM_CHAINS=1 for batches above 64: a capturing caller gets the single-chain launches)",
                    bytes, lm->ws.cap);
         return grow_step_buffer(lm, lm->ws, bytes);
     }));
@@ -1183,8 +1176,8 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
         c.stream = static_cast<hipStream_t>(stream);  // workspace the next call re-uses - quiesce them (error path only)
         for (hipStream_t cs : lm->chain_streams) (void)hipStreamSynchronize(cs);
     } else if (lm->taps) {
-        lm->tap_n[0] = B * (int64_t)(global_length + (cond_mode ? 0 : 1)) * lm->spec.global_size;
-        lm->tap_n[1] = B * (int64_t)semantic_length * lm->spec.semantic_size;
+        lm->tap_n[0] = (int64_t)a.B * (a.G + (p.cond_mode ? 0 : 1)) * lm->spec.global_size;
+        lm->tap_n[1] = (int64_t)a.B * a.S * lm->spec.semantic_size;
     }
     return st;
 }
@@ -1192,34 +1185,34 @@ static int lm_generate_impl(qa_lm* lm, int32_t task, const float* enroll_feats, 
 int qa_lm_generate(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                    int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                    int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    const SampleCfg sc{0, top_k, top_p, temperature, 0ull};
-    return lm_generate_impl(lm, task, enroll_feats, n_enroll, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
-                            semantic_ids, stream);
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
+    a.p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
+    return lm_generate_impl(lm, a, stream);
 }
 
 int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                            int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                            int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
-    return lm_generate_impl(lm, task, enroll_feats, n_enroll, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
-                            semantic_ids, stream);
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
+    a.p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
+    return lm_generate_impl(lm, a, stream);
 }
 
 int qa_lm_generate_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
                           const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                           int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    const SampleCfg sc{0, top_k, top_p, temperature, 0ull};
-    return lm_generate_impl(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
-                            semantic_ids, stream, false, nullptr, 0, n_enroll, true);
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
+    a.p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix);
+    return lm_generate_impl(lm, a, stream, true, n_enroll);
 }
 
 int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
                                   const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length,
                                   float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
                                   void* stream) {
-    const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
-    return lm_generate_impl(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix, B, global_length, semantic_length, sc, global_ids,
-                            semantic_ids, stream, false, nullptr, 0, n_enroll, true);
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
+    a.p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix);
+    return lm_generate_impl(lm, a, stream, true, n_enroll);
 }
 
 static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
@@ -1241,12 +1234,10 @@ static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int
     QA_REQUIRE(n_mix <= LM_MAX_POS && n_enroll <= LM_MAX_POS && B <= (1 << 24), "%s: bad shape", fn);
     QA_HIP(hipSetDevice(lm->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-    const bool capturing = cs == hipStreamCaptureStatusActive;
-    ScoreArgs a{cond_mode, cond, (int)Tc, task, enroll_feats ? (int)n_enroll : 0, (int)n_mix, (int)B, global_length, semantic_length, enroll_feats, mix_feats,
-                reinterpret_cast<const long long*>(global_ids), reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq,
-                reinterpret_cast<long long*>(correct_per_seq), loss, acc};
+    const bool capturing = stream_capturing(s);
+    const Prompt p = cond_mode ? cond_prompt(cond, Tc) : speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
+    ScoreArgs a{p, (int)B, global_length, semantic_length, reinterpret_cast<const long long*>(global_ids),
+                reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq, reinterpret_cast<long long*>(correct_per_seq), loss, acc};
     const int Lt = global_length + semantic_length + 2 - (cond_mode ? 1 : 0);
     lm->score_tap_n = -1;
     float* tap = nullptr;
@@ -1288,17 +1279,17 @@ int qa_lm_score_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, 
 
 int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
                         float temperature, int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    const SampleCfg sc{0, top_k, top_p, temperature, 0ull};
-    return lm_generate_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_length, semantic_length, sc, global_ids, semantic_ids, stream, true,
-                            cond_embeds, T);
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
+    a.p = cond_prompt(cond_embeds, T);
+    return lm_generate_impl(lm, a, stream);
 }
 
 int qa_lm_generate_cond_sampled(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
                                 float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
                                 void* stream) {
-    const SampleCfg sc{1, top_k, top_p, temperature, (unsigned long long)seed};
-    return lm_generate_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_length, semantic_length, sc, global_ids, semantic_ids, stream, true,
-                            cond_embeds, T);
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
+    a.p = cond_prompt(cond_embeds, T);
+    return lm_generate_impl(lm, a, stream);
 }
 
 int qa_lm_enable_taps(qa_lm* lm, int on) {
