@@ -546,21 +546,24 @@ static void launch_instance(const ConvParams& p, long long tiles, hipStream_t st
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
 }
 
+// The K-chunk width of a launch (launch_cfg; choose_tile prices the instance this picks).
+// BK = 16 chunks need 45 KB / 35 KB of LDS, so 3-4 workgroups are co-resident per CU (BK = 32: 2) and cover each other's barriers, prologues and
+// epilogues: +10..25 % on the K = 512 layers of the aggregator stacks, +3..5 % on K = 768..3072 (per-shape sweep, tools/gemm_bench.py with
+// QA_GEMM_BK16=0 / default).  QA_GEMM_BK16 = largest K that takes the BK = 16 variant.
+// ... but only when the launch has enough tiles for that co-residency: with about one workgroup per CU nobody covers the exposed latency of the
+// next chunk's global loads, which a BK = 16 chunk's 0.45 us of MFMAs is too short to hide (measured: the 144-tile RVQ distance GEMM 1056 x 1024
+// x 512 ran 37 us, 2.5 x its MFMA time).  QA_GEMM_BK16_MIN_TILES = fewest tiles that take BK = 16.
+// The 256-row tile (r06 experiment, QA_GEMM_256) exists with BK = 16 only: 61 KB of LDS, two workgroups per CU.
+static bool takes_bk16(int bm, int bn, long long tiles, int K, int C_in, bool elu) {
+    return bm == 256 || (bn >= 64 && !elu && ((K <= knob(K_GEMM_BK16) && tiles >= knob(K_GEMM_BK16_MIN_TILES)) || C_in % 32 != 0));
+}
+
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     QA_REQUIRE(p.prologue == ACT_NONE || p.prologue == ACT_ELU, "conv_gemm: prologue %d unsupported", p.prologue);
     const long long tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    // BK = 16 chunks need 45 KB / 35 KB of LDS, so 3-4 workgroups are co-resident per CU (BK = 32: 2) and cover each other's barriers, prologues and
-    // epilogues: +10..25 % on the K = 512 layers of the aggregator stacks, +3..5 % on K = 768..3072 (per-shape sweep, tools/gemm_bench.py with
-    // QA_GEMM_BK16=0 / default).  QA_GEMM_BK16 = largest K that takes the BK = 16 variant.
-    const long long bk16_max_k = knob(K_GEMM_BK16);
-    // ... but only when the launch has enough tiles for that co-residency: with about one workgroup per CU nobody covers the exposed latency of the
-    // next chunk's global loads, which a BK = 16 chunk's 0.45 us of MFMAs is too short to hide (measured: the 144-tile RVQ distance GEMM 1056 x 1024
-    // x 512 ran 37 us, 2.5 x its MFMA time).  QA_GEMM_BK16_MIN_TILES = fewest tiles that take BK = 16.
-    const long long bk16_min_tiles = knob(K_GEMM_BK16_MIN_TILES);
     const bool linear = is_linear(p), elu = p.prologue == ACT_ELU;
-    // the 256-row tile (r06 experiment, QA_GEMM_256) exists with BK = 16 only: 61 KB of LDS, two workgroups per CU
-    const bool bk16 = BM == 256 || (BN >= 64 && !elu && ((p.K <= bk16_max_k && tiles >= bk16_min_tiles) || p.C_in % 32 != 0));
+    const bool bk16 = takes_bk16(BM, BN, tiles, p.K, p.C_in, elu);
     // the K loop runs K / BK whole chunks and the table form reads each chunk from ONE tap: a BK that does not divide K (and, with the
     // table, C_in) would drop the tail of K or read past a tap's C_in channels - into the next frame or the next channel group
     const int bk = bk16 ? 16 : 32;
@@ -590,39 +593,79 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     return QA_OK;
 }
 
-// Tile choice of a launch (a PROF_CFG_* value that has a kernel for this launch).
-// Tiles of one launch are dealt round-robin over 256 CUs (the co-resident workgroups of a CU share its matrix pipes), so the makespan is (tiles on
-// the busiest CU) x (work per tile) / (sustained efficiency of the tile).  Round 4 adds the 64-row tiles: the aggregator stacks of H-Codec 1.5 (M =
-// 9056 = 70.75 x 128) and the 4000-row SSL / BiCodec layers lose up to a third of the machine to tile quantisation with 128-row tiles (852 tiles of
-// 128 x 128 = 3.33 per CU: a fourth round for a third of the CUs).  Efficiencies from the square 8192 x 4096 x 4096 problem, where every tile divides
-// the grid evenly (profiles/r04_gemm_tile_sweep.txt: 133.1 / 121.5 / 121.6 / 115.9 TFLOP/s); ties go to the larger tile (less L2 traffic). Every
+// Tile choice of a launch (a PROF_CFG_* value that has a kernel for this launch): the cheapest of 128 x 128, 64 x 128, 128 x 64 and 64 x 64 under
+// a makespan model of the instance launch_cfg would actually launch (DESIGN.md section 24 has the measurements it is fitted to and checked on).
+//   - A CU holds w workgroups of an instance (registers and LDS: profiles/r10_conv_gemm_resource_usage.md; 1 .. 5, by tile, BK and arithmetic
+//     form), so a round of the machine is 256 w tiles.  `share` launches of this shape run side by side and fill rounds together.
+//   - A full round costs w tiles of work, (rows x columns x K) / efficiency each: co-resident workgroups share the CU's matrix pipe.
+//   - The last round holds m <= 256 w tiles, ceil(m / 256) on the busiest CU and m / 256 on the average one.  It costs the mean of the two: the
+//     busiest CU sets the end, but CUs that run dry early hand their part of the power budget - the bound of these GEMMs - to the others.  Never
+//     less than one tile: a lone workgroup still walks its whole K loop.
+//   - Every round adds one exposed ramp - first loads, prologue and epilogue that no co-resident workgroup covers - of 0.22 of a 128 x 128
+//     tile's time, whatever the tile; and a launch costs about a quarter of a 128 x 128 x 512 tile before its first workgroup runs.
+// Efficiencies relative to 128 x 128 at saturation.  Split-6: 0.85 / 0.80 / 0.69 for 64 x 128 / 128 x 64 / 64 x 64, from the M = 16000 layers
+// (K = 512 .. 3072, no row padding) of profiles/r07_gemm_tile_sweep.txt, final build: the 64-column tiles split their weights in the K loop and fall
+// behind 64 x 128, which reads the image; 8192 x 4096 x 4096 (0.86 / 0.91 / 0.81) ranks them the other way round and misleads on every layer a model
+// has.  fp32 chain: round 4's 0.914 / 0.913 / 0.871 (profiles/r04_gemm_tile_sweep.txt).  Ties go to the larger tile (less L2 traffic).  Every
 // configuration accumulates an output element over k in the same order, so this choice - which depends on M, i.e. on the batch size - never changes a
 // bit (tests/test_kernels_gpu.py::test_conv_gemm_tile_configurations_are_bit_identical).
-static int choose_tile(const ConvParams& p) {
-    const bool lin = is_linear(p) && p.prologue != ACT_ELU;
+struct TileQuery {
+    long long M, N, K;
+    int C_in;
+    bool lin, elu, split;  // LINEAR instance without the ELU prologue; ELU prologue; split-6 arithmetic (else the fp32 chain)
+    bool image;            // split-6 only: the weight has a pre-split image (QA_GEMM_PRESPLIT), which the 128-column tiles read
+    int share;             // launches of this shape that share the device (>= 1)
+};
+// co-resident workgroups per CU of the instance (tile, K chunk, arithmetic form): the occupancy column of the resource table, which is the same for
+// the LINEAR and the table form of an instance
+static int workgroups_per_cu(int cfg, bool bk16, bool split) {
+    switch (cfg) {
+        case PROF_CFG_128x128: return bk16 ? 3 : split ? 1 : 2;
+        case PROF_CFG_64x128: return bk16 ? 4 : 2;
+        case PROF_CFG_128x64: return bk16 ? 4 : 2;
+        case PROF_CFG_64x64: return bk16 ? 5 : split ? 3 : 4;
+        case PROF_CFG_256x128: return 2;
+        default: return split ? 2 : 3;  // 128 x 32
+    }
+}
+static double tile_cost(const TileQuery& t, int cfg, int bm, int bn, double eff) {
+    constexpr double kTile = 128.0 * 128.0, kRamp = 0.22, kLaunch = 0.27 * 512.0;
+    const long long tiles = ceil_div(t.M, bm) * ceil_div(t.N, bn);
+    const long long w = workgroups_per_cu(cfg, takes_bk16(bm, bn, tiles, (int)t.K, t.C_in, t.elu), t.split);
+    const long long n = tiles * (t.share > 1 ? t.share : 1), cap = 256 * w;
+    const long long rounds = ceil_div(n, cap), m = n - (rounds - 1) * cap;
+    double last = 0.5 * ((double)ceil_div(m, 256) + (double)m / 256.0);
+    if (last < 1.0) last = 1.0;
+    return kTile * kLaunch + (double)t.K * ((double)bm * bn / eff * ((double)(w * (rounds - 1)) + last) + kRamp * kTile * (double)rounds);
+}
+// The round-4 model, kept for split-6 launches WITHOUT a pre-split image: tiles dealt round-robin over 256 CUs, (tiles on the busiest CU) x (work per
+// tile) / (round 4's efficiency), a quarter more for a launch that gives a CU at most one workgroup.  The split-6 efficiencies above are those of
+// 64 x 128 reading the image; without one it drops to 128 x 64's level (profiles/r07_gemm_tile_sweep.txt, "no image attached"), and with the image
+// figures the 4000-row layers lost 4 - 6 % there (profiles/r11_gemm_tile_sweep.txt).  No model loads weights without an image at the default knobs,
+// so these launches were not re-fitted and keep the parent's choice.
+static double tile_cost_r4(const TileQuery& t, int bm, int bn, double eff) {
+    const long long tiles = ceil_div(t.M, bm) * ceil_div(t.N, bn);
+    return (double)ceil_div(tiles, 256) * bm * bn / eff * (tiles <= 256 ? 1.25 : 1.0);
+}
+static int choose_tile(const TileQuery& t) {
     int cfg = (int)knob(K_GEMM_CFG);  // >= 0: forced
     if (cfg < 0) {
-        if (p.N <= 32) cfg = PROF_CFG_128x32;
-        else if (p.N <= 64) cfg = PROF_CFG_128x64;
+        if (t.N <= 32) cfg = PROF_CFG_128x32;
+        else if (t.N <= 64) cfg = PROF_CFG_128x64;
         else {
-            struct Cand { int cfg, bm, bn; double eff; };
-            static const Cand cands[] = {{PROF_CFG_128x128, 128, 128, 1.0}, {PROF_CFG_64x128, 64, 128, 0.914}, {PROF_CFG_128x64, 128, 64, 0.913},
-                                         {PROF_CFG_64x64, 64, 64, 0.871}};
-            // a launch that gives a CU at most ONE workgroup has nobody to cover that workgroup's barriers, prologue and epilogue: the
-            // 256-tile 4032 x 512 x 512 launch runs 8 % faster as 504 tiles of 64 x 64 although those need two rounds (same sweep)
-            auto cost_of = [&](int bm, int bn, double eff) {
-                const long long tiles = ceil_div(p.M, bm) * ceil_div(p.N, bn);
-                return (double)ceil_div(tiles, 256) * bm * bn / eff * (tiles <= 256 ? 1.25 : 1.0);
-            };
+            struct Cand { int cfg, bm, bn; double eff6, eff32; };
+            static const Cand cands[] = {{PROF_CFG_128x128, 128, 128, 1.0, 1.0}, {PROF_CFG_64x128, 64, 128, 0.85, 0.914},
+                                         {PROF_CFG_128x64, 128, 64, 0.80, 0.913}, {PROF_CFG_64x64, 64, 64, 0.69, 0.871}};
             double best = 0.0;
             cfg = PROF_CFG_128x128;
             const long long eff256 = knob(K_GEMM_256);  // 0: never; else the tile's efficiency relative to 128 x 128, in 1/1000
-            if (eff256 > 0 && lin && p.M >= 8000 && p.N >= 1024) {  // try the 256 x 128 tile in front of the 128 x 128 one
-                best = cost_of(256, 128, eff256 / 1000.0);
+            const bool r4 = t.split && !t.image;
+            if (eff256 > 0 && t.lin && t.M >= 8000 && t.N >= 1024) {  // try the 256 x 128 tile in front of the 128 x 128 one
+                best = r4 ? tile_cost_r4(t, 256, 128, eff256 / 1000.0) : tile_cost(t, PROF_CFG_256x128, 256, 128, eff256 / 1000.0);
                 cfg = PROF_CFG_256x128;
             }
             for (const Cand& c : cands) {
-                const double cost = cost_of(c.bm, c.bn, c.eff);
+                const double cost = r4 ? tile_cost_r4(t, c.bm, c.bn, c.eff32) : tile_cost(t, c.cfg, c.bm, c.bn, t.split ? c.eff6 : c.eff32);
                 if (best == 0.0 || cost < best * 0.995) {
                     best = cost;
                     cfg = c.cfg;
@@ -631,10 +674,14 @@ static int choose_tile(const ConvParams& p) {
         }
     }
     // only BK = 32 exists for the 128 x 32 tile: C_in % 32 != 0 (possible only when forced, N > 32) takes 128 x 64
-    if (cfg == PROF_CFG_128x32 && p.C_in % 32 != 0) return PROF_CFG_128x64;
+    if (cfg == PROF_CFG_128x32 && t.C_in % 32 != 0) return PROF_CFG_128x64;
     // a forced 256 x 128 on a layer it does not exist for, or a forced value that names no tile
-    if ((cfg == PROF_CFG_256x128 && !lin) || cfg >= PROF_NCFG) return PROF_CFG_128x128;
+    if ((cfg == PROF_CFG_256x128 && !t.lin) || cfg >= PROF_NCFG) return PROF_CFG_128x128;
     return cfg;
+}
+static int choose_tile(const ConvParams& p) {
+    const bool elu = p.prologue == ACT_ELU;
+    return choose_tile(TileQuery{p.M, p.N, p.K, p.C_in, is_linear(p) && !elu, elu, knob(K_GEMM_MATH) != 0 && !p.math_fp32, p.wp != nullptr, 1});
 }
 
 int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
@@ -673,7 +720,7 @@ int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
     q.rep_one = p.in_rep > 1 ? 0u : 1u;
     q.rep_magic = p.in_rep > 1 ? (unsigned)(((1ULL << 32) + p.in_rep - 1) / p.in_rep) : 0u;
 
-    switch (choose_tile(p)) {
+    switch (choose_tile(q)) {
         case PROF_CFG_128x32: return launch_cfg<128, 32, 4, 1>(q, stream);
         case PROF_CFG_128x64: return launch_cfg<128, 64, 2, 2>(q, stream);
         case PROF_CFG_64x128: return launch_cfg<64, 128, 1, 4>(q, stream);
@@ -711,3 +758,15 @@ int conv_params_from_args(const qa_conv_args& a, ConvParams* out) {
 }
 
 }  // namespace qa
+
+// test hook (not in the public header): the tile (a QA_GEMM_CFG value) launch_conv_gemm would take for an M x N x K layer of kernel size
+// `ksize` - `linear`: a LINEAR-form layer without prologue; `share`: launches of this shape running side by side; the weight is taken to have a pre-split
+// image, as every loaded model's has - under the current knobs, without launching anything; negative for a bad argument
+extern "C" int qa_debug_conv_gemm_tile(long long M, long long N, long long K, int ksize, int linear, int math_fp32, int share) {
+    if (M <= 0 || N <= 0 || K <= 0 || ksize < 1 || K % ksize != 0 || M >= (1LL << 31) || N >= (1LL << 31) || K >= (1LL << 31)) {
+        qa::set_error("qa_debug_conv_gemm_tile: bad argument");
+        return -1;
+    }
+    const bool lin = linear != 0 && ksize == 1 && qa::knob(qa::K_GEMM_LINEAR) != 0;
+    return qa::choose_tile(qa::TileQuery{M, N, K, (int)(K / ksize), lin, false, qa::knob(qa::K_GEMM_MATH) != 0 && !math_fp32, true, share});
+}

@@ -634,6 +634,41 @@ int launch_agg_gather(const float* x, const int* start, const int* len, const in
     return QA_OK;
 }
 
+// The last aggregator layer needs only the query rows past its key / value projection (QA_AGG_LAST_ROWS): the query rows of x
+// [B, T + G, D] and the q columns of their qkv rows [B, T + G, 3 D] -> compact xq, qq [B, G, D], with agg_gather's indexing.  A padded
+// group (g >= nseg[b]) reads row 0 of its clip, a valid row whose result agg_zero_padded overwrites.
+__global__ __launch_bounds__(128) void agg_query_rows_kernel(const float* __restrict__ x, const float* __restrict__ qkv,
+                                                             const int* __restrict__ start, const int* __restrict__ len,
+                                                             const int* __restrict__ nseg, float* __restrict__ xq,
+                                                             float* __restrict__ qq, int T, int G, int D) {
+    const int b = blockIdx.y, g = blockIdx.x;
+    const int src = g < nseg[b] ? start[(long long)b * T + g] + len[(long long)b * T + g] + g : 0;
+    const long long row = (long long)b * (T + G) + src, dst = ((long long)b * G + g) * D;
+    for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4) {
+        *reinterpret_cast<float4*>(xq + dst + c) = *reinterpret_cast<const float4*>(x + row * D + c);
+        *reinterpret_cast<float4*>(qq + dst + c) = *reinterpret_cast<const float4*>(qkv + row * 3 * D + c);
+    }
+}
+int launch_agg_query_rows(const float* x, const float* qkv, const int* start, const int* len, const int* nseg, float* xq, float* qq,
+                          int B, int T, int G, int D, hipStream_t s) {
+    QA_REQUIRE(D % 4 == 0, "agg_query_rows: D=%d must be a multiple of 4", D);
+    hipLaunchKernelGGL(agg_query_rows_kernel, dim3(G, B), dim3(128), 0, s, x, qkv, start, len, nseg, xq, qq, T, G, D);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+// out [B, G, D]: zero the padded groups, as agg_gather writes them
+__global__ __launch_bounds__(128) void agg_zero_padded_kernel(const int* __restrict__ nseg, float* __restrict__ out, int G, int D) {
+    const int b = blockIdx.y, g = blockIdx.x;
+    if (g < nseg[b]) return;
+    for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4)
+        *reinterpret_cast<float4*>(out + ((long long)b * G + g) * D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+int launch_agg_zero_padded(const int* nseg, float* out, int B, int G, int D, hipStream_t s) {
+    hipLaunchKernelGGL(agg_zero_padded_kernel, dim3(G, B), dim3(128), 0, s, nseg, out, G, D);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
 // library indices [B*G, Q] -> reference layout [B, Q, G] with the group length injected:
 // code' = (len - 1) * K + code (codec_adaptive.py:68-73; len = 0 for padded groups gives code - K, as in the reference)
 __global__ void codes_inject_kernel(const long long* __restrict__ idx, const int* __restrict__ len, long long* __restrict__ dst,

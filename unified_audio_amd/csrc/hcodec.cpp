@@ -379,19 +379,56 @@ int mimi_op(Ctx& c, const MimiW& mw, float* x, int B, int N) {
     c.arena.release(mark);
     return QA_OK;
 }
-// two independent stacks of equal depth, layer-interleaved on two streams (xa on the caller's stream, xb on `side`)
-int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const MimiW& wb, float* xb, int B, int N) {
+// The read-out of a QueryTokenAggregator stack over x [B, T + G, d]: the output rows at the G query positions per clip -> out [B, G, d],
+// zeros for padded groups (start / len / nseg as in agg_build / agg_gather).
+struct AggReadout {
+    const int *start, *len, *nseg;
+    int T, G;
+    float* out;
+};
+// Last layer of an aggregator stack, read-out included (QA_AGG_LAST_ROWS): the keys and values need every row, so LayerNorm 1 and in_proj run
+// as in mimi_layer; everything after them is row-wise and runs on the B G query rows alone, gathered into xq / qq [B, G, d].  Every op gives
+// a row the bits it gives it in the full layer (conv_gemm does not depend on M or the tile, attention not on n_q), so out equals
+// agg_gather(mimi_layer(x)).  Non-causal stacks only: a compact query has lost its position.
+int mimi_readout_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, const float* x, const MimiTemps& t, float* xq, float* qq, int B,
+                       const AggReadout& ro) {
+    const int d = mw.d, H = mw.heads, hd = d / H, N = ro.T + ro.G;
+    const int64_t rows = (int64_t)B * N, qrows = (int64_t)B * ro.G;
+    QA_TRY(layernorm_op(c, x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f));
+    ConvOpt qo;
+    qo.rope = mw.rope; qo.rope_n = 2 * d; qo.rope_hd = hd; qo.rope_T = N; qo.rope_pos0 = 0;
+    QA_TRY(linear_op(c, t.hn, rows, L.in_proj, t.qkv, qo));
+    QA_RUN(c, launch_agg_query_rows(x, t.qkv, ro.start, ro.len, ro.nseg, xq, qq, B, ro.T, ro.G, d, c.stream));
+    QA_TRY(attention_op(c, qq, d, t.qkv + d, t.qkv + 2 * d, 3 * d, t.att, d, B, ro.G, N, (long long)N * 3 * d, H, hd,
+                        1.0f / std::sqrt((float)hd), 0));
+    QA_TRY(linear_op(c, t.att, qrows, L.out_proj, xq, epi(ACT_NONE, xq, L.ls1)));
+    QA_TRY(layernorm_op(c, xq, L.n2w, L.n2b, t.hn, qrows, d, 1e-5f));
+    QA_TRY(linear_op(c, t.hn, qrows, L.lin1, t.u, epi(ACT_GELU)));
+    QA_TRY(linear_op(c, t.u, qrows, L.lin2, ro.out, epi(ACT_NONE, xq, L.ls2)));
+    QA_RUN(c, launch_agg_zero_padded(ro.nseg, ro.out, B, ro.G, d, c.stream));
+    return QA_OK;
+}
+// two independent stacks of equal depth, layer-interleaved on two streams (xa on the caller's stream, xb on `side`); with read-outs (both
+// or neither) the last layer of each stack is mimi_readout_layer, which leaves xa / xb at the input of that layer
+int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const MimiW& wb, float* xb, int B, int N,
+                 const AggReadout* ra = nullptr, const AggReadout* rb = nullptr) {
     QA_REQUIRE(N <= MAX_POS && wa.layers.size() == wb.layers.size(), "mimi pair: mismatched stacks");
+    QA_REQUIRE(!ra == !rb && (!ra || (!wa.causal && !wb.causal && wa.d == wb.d && !wa.layers.empty())), "mimi pair: bad read-out");
     const size_t mark = c.arena.mark();
     const MimiTemps ta = mimi_temps(c, wa, (int64_t)B * N);
     const MimiTemps tb = mimi_temps(c, wb, (int64_t)B * N);
+    float* cq[4] = {nullptr, nullptr, nullptr, nullptr};  // xq, qq of either stack
+    if (ra)
+        for (float*& p : cq) p = c.arena.alloc<float>((size_t)B * ra->G * wa.d);
     if (!c.dry) {  // real pass only, more than launches: c.stream alternates between the two streams
         hipStream_t main = c.stream;
         for (size_t l = 0; l < wa.layers.size(); ++l) {
+            const bool last = ra && l + 1 == wa.layers.size();
             c.stream = main;
-            int st = mimi_layer(c, wa, wa.layers[l], xa, ta, B, N);
+            int st = last ? mimi_readout_layer(c, wa, wa.layers[l], xa, ta, cq[0], cq[1], B, *ra) : mimi_layer(c, wa, wa.layers[l], xa, ta, B, N);
             c.stream = side;
-            if (st == QA_OK) st = mimi_layer(c, wb, wb.layers[l], xb, tb, B, N);
+            if (st == QA_OK)
+                st = last ? mimi_readout_layer(c, wb, wb.layers[l], xb, tb, cq[2], cq[3], B, *rb) : mimi_layer(c, wb, wb.layers[l], xb, tb, B, N);
             c.stream = main;
             QA_TRY(st);
         }
@@ -701,9 +738,15 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, 
         QA_HIP(hipEventRecord(h->ev_fork, c.stream));
         QA_HIP(hipStreamWaitEvent(side, h->ev_fork, 0));
     }
-    QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S));
-    QA_RUN(c, launch_agg_gather(inter_s, start, len, nseg, agg_s, B, N, G, D, c.stream));
-    QA_RUN(c, launch_agg_gather(inter_a, start, len, nseg, agg_a, B, N, G, D, side));
+    // QA_AGG_LAST_ROWS: the last layer of each stack on the query rows only, read-out included (non-causal aggregators)
+    if (knob(K_AGG_LAST_ROWS) != 0 && !h->agg_sem.causal && !h->agg_ac.causal && !h->agg_sem.layers.empty()) {
+        const AggReadout rs{start, len, nseg, N, G, agg_s}, ra{start, len, nseg, N, G, agg_a};
+        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S, &rs, &ra));
+    } else {
+        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S));
+        QA_RUN(c, launch_agg_gather(inter_s, start, len, nseg, agg_s, B, N, G, D, c.stream));
+        QA_RUN(c, launch_agg_gather(inter_a, start, len, nseg, agg_a, B, N, G, D, side));
+    }
     if (!c.dry) {  // real pass only: the event join
         QA_HIP(hipEventRecord(h->ev_join, side));
         QA_HIP(hipStreamWaitEvent(c.stream, h->ev_join, 0));

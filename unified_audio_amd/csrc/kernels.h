@@ -36,6 +36,9 @@ int launch_agg_build(const float* feats, const int* seg, const int* start, const
                      float* out, int B, int T, int G, int D, hipStream_t s);
 int launch_agg_gather(const float* x, const int* start, const int* len, const int* nseg, float* out, int B, int T, int G,
                       int D, hipStream_t s);
+int launch_agg_query_rows(const float* x, const float* qkv, const int* start, const int* len, const int* nseg, float* xq, float* qq,
+                          int B, int T, int G, int D, hipStream_t s);
+int launch_agg_zero_padded(const int* nseg, float* out, int B, int G, int D, hipStream_t s);
 int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K,
                         hipStream_t s);
 int launch_adaptive_frames(const long long* codes, int B, int Q, int G, int K, int* totals, int* tmax, hipStream_t s);

@@ -22,6 +22,7 @@ namespace qa {
     X(GEMM_PANEL, "QA_GEMM_PANEL", 8, "conv_gemm tile order: column panels of this many tiles, row tiles fastest inside a panel (0: column tiles fastest over the whole row; 8: +4 % on N >= 4096 shapes, +1.2 % on H-Codec 2.0)") \
     X(ATT_MATH, "QA_ATT_MATH", 1, "attention arithmetic: 1 = split-6 (Q, K, V and the probabilities as three bf16 planes, six v_mfma_f32_32x32x16_bf16 per 16-wide k group, fp32 accumulation), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32); the UniSE LM keeps the fp32 chain either way") \
     X(ATT_DEBUG, "QA_ATT_DEBUG", 0, "attention_kernel debug bits, both forms: 1 always rescale, 2 extra barrier per tile, 4 wait for the prefetch at once, 8 no wave-uniform tile skip, 16 mask every tile; the split-6 form (SPLIT) only (tests): 32 / 64 / 128 zero the h / m / l plane of the operands selected by 256 Q, 512 K, 1024 V, 2048 P (none of the four: all)") \
+    X(AGG_LAST_ROWS, "QA_AGG_LAST_ROWS", 1, "H-Codec 1.5 encode: the last layer of each aggregator stack runs attention, out_proj, LayerNorm 2, lin1 and lin2 on the G query rows per clip only (the rows the read-out keeps); 0 = the full last layer; same bits either way") \
     X(SEANET_FUSED, "QA_SEANET_FUSED", 1, "fused conv0 + first SEANet residual block")                                           \
     X(MIMI_ROPE_WINDOW, "QA_MIMI_ROPE_WINDOW", 8192, "mimi streaming: positions covered by the RoPE table before the rolling window takes over (tests shrink it)") \
     X(LSTM_GRAPH, "QA_LSTM_GRAPH", 1, "replay the T step launches of an LSTM call from a cached hipGraph")                       \
