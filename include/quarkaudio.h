@@ -138,6 +138,21 @@ int qa_hcodec_encode(qa_hcodec* h, const float* wav, int64_t B, int64_t T,
 int qa_hcodec_decode(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B,
                      int64_t N, float* wav_out, void* stream);
 
+/* Per-clip lengths in one call (non-causal H-Codec 1.0): clip b behaves as qa_hcodec_encode / _decode would for it
+ * alone at its own length.  frames: HOST memory, int64 [B], the clips' lengths in CODE frames, 1 .. N each (N = T / encoder hop), read
+ * during the call and checked before anything is launched (QA_ERR_INVALID names the row).  H-Codec 1.5, 2.0 and causal handles are
+ * refused with QA_ERR_UNSUPPORTED.  A call whose lengths all equal N is the rectangular call, through the same launches.
+ *   encode: samples of wav from frames[b] * hop on and feature frames from frames[b] * (n_feat_frames / N) on are padding that is never
+ *           read (NaN there changes nothing); codes at frames >= frames[b] are written as -1, the dropped code, so the output is also a
+ *           legal input of qa_hcodec_decode.
+ *   decode: code entries at frames >= frames[b] are ignored, whatever they hold; wav_out[b] is exactly 0 from sample
+ *           frames[b] * 2 * hop on. */
+int qa_hcodec_encode_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const int64_t* frames,
+                            const float* feat, int64_t feat_stride_b, int64_t feat_stride_c, int64_t feat_stride_t,
+                            int64_t n_feat_frames, int64_t* acoustic_codes, int64_t* semantic_codes, void* stream);
+int qa_hcodec_decode_ragged(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B, int64_t N,
+                            const int64_t* frames, float* wav_out, void* stream);
+
 /* H-Codec 1.5 (spec.adaptive != 0): Codec.encode / Codec.decode of QuarkAudio-HCodec/HCodec-1.5/vq/codec_adaptive.py:150-199.
  * The number of groups G is data dependent (the reference syncs the host too: modeling_flexicodec_new.py:910), so
  *   - encode writes int64 [B, nq, G] length-injected codes (code' = (len-1)*codebook_size + code) compactly into buffers of

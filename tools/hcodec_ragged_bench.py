@@ -1,0 +1,93 @@
+#!/usr/bin/env python
+"""H-Codec 1.0 ragged-batch micro-benchmark at the SPEC_10 size: N clips (seeded) whose lengths are spread over 2 - 10 s
+(50 - 250 code frames), resident on the device, features given.
+
+  ragged    ONE Codec.encode(..., lengths=...) + ONE Codec.decode(..., lengths=...) over all N clips
+  grouped   one encode + decode per DISTINCT length (what a caller did before per-clip lengths existed)
+
+Argument 1: N (default 32).  Each figure is the median (min - max) of REPS runs (argument 2, default 5) after one warm-up run, wall clock
+around a device synchronisation; the two forms are compared on the valid part of every clip (codes_equal, wav_equal: the grouped calls
+take the fused stage 0, so equality of the codes is expected but not guaranteed, and the waveforms are decoded from each form's own
+codes).  One JSON line per figure is appended to profiles/hcodec_ragged_bench.jsonl (argument 3: another path)."""
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import unified_audio_amd as qa  # noqa: E402
+from unified_audio_amd import synth  # noqa: E402  (seeded weights / inputs: data generation only)
+
+N_CLIPS = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "hcodec_ragged_bench.jsonl")
+FRAMES = (50, 250)  # 2 s .. 10 s at 25 code frames per second
+dev = torch.device("cuda:0")
+spec = qa.SPEC_10
+hop = spec.enc_hop
+codec = qa.Codec(None, None, None, spec=spec, device=dev, check_codes=False).load_state_dict(synth.hcodec10_state_dict(1234))
+lens = [round(FRAMES[0] + (FRAMES[1] - FRAMES[0]) * i / max(N_CLIPS - 1, 1)) for i in range(N_CLIPS)]
+lens = [lens[i] for i in torch.randperm(N_CLIPS, generator=torch.Generator().manual_seed(7)).tolist()]  # a file list is not sorted
+distinct = sorted(set(lens))
+n_max = max(lens)
+wav = synth.synth_wav(11, N_CLIPS, hop * n_max).to(dev)
+feat = synth.synth_feat(12, N_CLIPS, 2 * n_max).to(dev)
+rows = []
+
+
+def timed(fn):
+    ts, out = [], None
+    for _ in range(REPS + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return (statistics.median(ts[1:]), min(ts[1:]), max(ts[1:])), out
+
+
+def report(name, ms, **kw):
+    row = dict(bench="hcodec_ragged", name=name, clips=N_CLIPS, ms_median=round(ms[0], 3), ms_min=round(ms[1], 3), ms_max=round(ms[2], 3),
+               reps=REPS, **kw)
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+
+
+def ragged():
+    ac, sc = codec.encode(wav.unsqueeze(1), feat, lengths=lens)
+    return ac, sc, codec.decode(ac, sc, lengths=lens)
+
+
+def grouped():
+    q = spec.num_quantizers
+    ac = torch.full((N_CLIPS, q, n_max), -1, dtype=torch.int64, device=dev)
+    sc = torch.full((N_CLIPS, q, n_max), -1, dtype=torch.int64, device=dev)
+    w = torch.zeros((N_CLIPS, hop * n_max), device=dev)
+    for f in distinct:
+        idx = torch.tensor([b for b, x in enumerate(lens) if x == f], device=dev)
+        a, s = codec.encode(wav[idx, :hop * f].unsqueeze(1), feat[idx, :, :2 * f])
+        ac[idx, :, :f], sc[idx, :, :f] = a, s
+        w[idx, :hop * f] = codec.decode(a, s)
+    return ac, sc, w
+
+
+ms_r, (ar, sr, wr) = timed(ragged)
+ms_g, (ag, sg, wg) = timed(grouped)
+audio_s = sum(lens) * hop / 16000.0
+report("ragged", ms_r, distinct_lengths=len(distinct), frames_min=min(lens), frames_max=max(lens), audio_s_per_s=round(audio_s / ms_r[0] * 1e3, 1))
+report("grouped", ms_g, distinct_lengths=len(distinct), calls=len(distinct), audio_s_per_s=round(audio_s / ms_g[0] * 1e3, 1))
+codes_equal = bool(torch.equal(ar, ag) and torch.equal(sr, sg))
+row = dict(bench="hcodec_ragged", name="grouped_over_ragged", clips=N_CLIPS, ratio_of_medians=round(ms_g[0] / ms_r[0], 2),
+           ratio_min=round(ms_g[1] / ms_r[2], 2), ratio_max=round(ms_g[2] / ms_r[1], 2), distinct_lengths=len(distinct),
+           codes_equal=codes_equal, wav_equal=bool(torch.equal(wr, wg)),
+           wav_rel_rms=float(((wr - wg).double().pow(2).mean() / wg.double().pow(2).mean()).sqrt()))
+rows.append(row)
+print(json.dumps(row), flush=True)
+with open(OUT, "a") as f:
+    f.write("== python tools/hcodec_ragged_bench.py " + " ".join(sys.argv[1:]) + "\n")
+    for r in rows:
+        f.write(json.dumps(r) + "\n")

@@ -455,6 +455,7 @@ static auto attention_instance(bool bias, bool kmask) {
 }
 
 static std::atomic<long long> g_att_launches[2];  // by kernel form: [0] fp32 chain, [1] split-6 (qa_debug_att_stats)
+static std::atomic<long long> g_att_kmask_launches;  // launches of a KMASK instantiation (qa_debug_att_kmask_launches)
 
 // gate [B, H, n_q] and relbias [H, 2R+1] (both optional, together): gated relative position bias, see attention_kernel.
 // Arithmetic: split-6 (SPLIT) unless QA_ATT_MATH = 0 or the caller asks for the fp32 chain (math_fp32: the UniSE LM, whose prefill
@@ -484,6 +485,7 @@ int launch_attention(const float* q, long long ldq, const float* k, const float*
                        n_keys, scale, causal, gate, relbias, R, context, q_pos0, ring_end, (int)knob(K_ATT_DEBUG), kvalid);
     QA_LAUNCH_CHECK();
     g_att_launches[split ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+    if (kmask) g_att_kmask_launches.fetch_add(1, std::memory_order_relaxed);
     return QA_OK;
 }
 
@@ -499,6 +501,10 @@ extern "C" int qa_debug_att_stats(int64_t* out2) {
     for (int i = 0; i < 2; ++i) out2[i] = qa::g_att_launches[i].load(std::memory_order_relaxed);
     return QA_OK;
 }
+
+// test hook (not part of the public header): of those launches, the ones that took a key-padding-mask (KMASK) instantiation - the Conformer
+// condition encoder's, and the transformers of a ragged H-Codec call
+extern "C" long long qa_debug_att_kmask_launches(void) { return qa::g_att_kmask_launches.load(std::memory_order_relaxed); }
 
 namespace qa {
 // split4_unit against split4_rne on caller-provided values: counts the floats whose three planes differ

@@ -138,6 +138,12 @@ struct ConvParams {
     // Pre-split image of w (split_planes.h), or null: set by launch_conv_gemm from the attached images (QA_GEMM_PRESPLIT).  The
     // split-6 instances then copy plane units into LDS instead of splitting the weight tile in the K loop; same bits either way.
     const void* wp;
+    // Per-clip lengths (ragged H-Codec calls), or null: clip b holds lens[b] * len_mul input frames of the T_in its
+    // rows are laid out for.  The source-frame table of the non-LINEAR instances then pads at the clip's own end - reflect with the
+    // short-input rule against max_pad (= max(pad_left, pad_right), what Lp is derived from), zeros from frame lens[b] * len_mul on.
+    // lens is DEVICE memory [B]; in_rep must be 1.  Null: every clip has T_in frames, and the kernel loads nothing.
+    const int* lens;
+    int len_mul, max_pad;
 };
 
 // Live measurement hook (bench.py): when enabled every conv_gemm launch is bracketed by HIP events on its own stream.

@@ -186,10 +186,15 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
             const int row = e / TAP_WIN, j = jbase + (e % TAP_WIN);
             const int m = min(m0 + row, p.M - 1);
             const int t = m % p.T_out;
+            int len = t_virtual, lp = p.Lp;
+            if (p.lens) {  // launch-uniform: a ragged call, the clip ends at its own length (never past the T_in its rows are laid out for)
+                len = min(p.lens[m / p.T_out] * p.len_mul, t_virtual);
+                lp = len <= p.max_pad ? p.max_pad + 1 : len;
+            }
             int r = t * p.stride - p.pad_left + j * dil;
-            const int rr = r < 0 ? -r : (r >= p.Lp ? 2 * (p.Lp - 1) - r : r);  // = resolve_frame()
+            const int rr = r < 0 ? -r : (r >= lp ? 2 * (lp - 1) - r : r);  // = resolve_frame()
             r = reflect ? rr : r;
-            const bool ok = r >= 0 && r < t_virtual && j < p.ksize;
+            const bool ok = r >= 0 && r < len && j < p.ksize;
             const unsigned ru = ok ? (unsigned)r : 0u;
             const unsigned src = __umulhi(ru, p.rep_magic) + ru * p.rep_one;  // = r / in_rep
             s_tap[e] = ok ? (int)(src * (unsigned)ldx_i) : -1;
@@ -705,6 +710,7 @@ int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
                                      (!p.y2 || (p.alpha2 && al16(p.alpha2) && al16(p.y2) && p.ldy2 % 4 == 0))),
                "conv_gemm: Snake activation / second output need the float4 epilogue and 16-byte aligned alpha vectors");
     QA_REQUIRE(p.dilation <= 1 || (p.pad_mode == PAD_ZERO && p.in_rep <= 1), "conv_gemm: dilation needs zero padding");
+    QA_REQUIRE(!p.lens || (p.len_mul >= 1 && p.in_rep <= 1 && p.max_pad >= 0), "conv_gemm: per-clip lengths need len_mul >= 1 and in_rep = 1");
     QA_REQUIRE(!p.am_dist || (vec_epi && p.am_idx && p.am_x2 && p.am_e2 && al16(p.am_e2) && p.am_ld >= (p.N + 31) / 32 && !p.y2),
                "conv_gemm: the arg-min epilogue needs N %% 4 == 0, x2 / e2 / dist / idx and am_ld >= ceil(N / 32)");
     QA_REQUIRE(!p.rope || (vec_epi && p.rope_hd % 4 == 0 && p.rope_n % 4 == 0 && p.rope_T > 0 && al16(p.rope)),

@@ -12,7 +12,8 @@ namespace qa {
 // one thread = one output frame x 4 channels -> float4 stores, consecutive threads write consecutive 16 B.
 __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, float* __restrict__ y, int B,
-                                                      int T, int Cout, int ksize, int pad_left, int Lp) {
+                                                      int T, int Cout, int ksize, int pad_left, int Lp,
+                                                      const int* __restrict__ lens, int len_mul, int max_pad) {
     const int c4n = Cout >> 2;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = (long long)B * T * c4n;
@@ -21,9 +22,14 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
     const long long m = gid / c4n;
     const int b = (int)(m / T), t = (int)(m - (long long)b * T);
     const float* xb = x + (long long)b * T;
+    int len = T;
+    if (lens) {  // launch-uniform: a ragged call reflects at the clip's own end (short-input rule included)
+        len = min(lens[b] * len_mul, T);
+        Lp = len <= max_pad ? max_pad + 1 : len;
+    }
     float4 acc = bias ? *reinterpret_cast<const float4*>(bias + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j = 0; j < ksize; ++j) {
-        const int src = resolve_frame(t - pad_left + j, T, Lp, PAD_REFLECT);
+        const int src = resolve_frame(t - pad_left + j, len, Lp, PAD_REFLECT);
         const float xv = src >= 0 ? xb[src] : 0.f;
         const float* wj = w + (long long)j * Cout + c4 * 4;  // library layout [ksize][Cout]
         acc.x = fmaf(xv, wj[0], acc.x);
@@ -35,7 +41,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
 }
 
 int launch_conv_in(const float* x, const float* w_kc, const float* bias, float* y, int B, int T, int Cout, int ksize,
-                   hipStream_t s, int pad_left) {
+                   hipStream_t s, int pad_left, ClipLens rl) {
     QA_REQUIRE(Cout % 4 == 0 && pad_left < ksize, "conv_in: Cout=%d must be a multiple of 4 (pad_left %d, ksize %d)", Cout, pad_left, ksize);
     const int pad_total = ksize - 1;
     const int left = pad_left >= 0 ? pad_left : pad_total - pad_total / 2, right = pad_total - left;
@@ -44,7 +50,7 @@ int launch_conv_in(const float* x, const float* w_kc, const float* bias, float* 
     const long long total = (long long)B * T * (Cout / 4);
     HbmProf prof_(HK_CONV_IN, 4.0 * ((double)B * T + (double)B * T * Cout), s);
     hipLaunchKernelGGL(conv_in_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, w_kc, bias, y, B, T,
-                       Cout, ksize, left, Lp);
+                       Cout, ksize, left, Lp, rl.n, rl.mul, max_pad);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -135,12 +141,13 @@ template <bool LN>
 __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ bias, const float* __restrict__ lnw,
                                                      const float* __restrict__ lnb, float* __restrict__ y, int B, int T,
-                                                     int C, int ksize, float eps, int pad) {
+                                                     int C, int ksize, float eps, int pad, const int* __restrict__ lens, int len_mul) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long long)B * T) return;
     const int b = (int)(row / T), t = (int)(row - (long long)b * T);
     const float* xb = x + (long long)b * T * C;
+    const int len = lens ? min(lens[b] * len_mul, T) : T;  // launch-uniform test; ragged: zero padding starts at the clip's own end
     float4 v[MAX_V4];
     float s = 0.f;
 #pragma unroll
@@ -150,7 +157,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x
         float4 acc = *reinterpret_cast<const float4*>(bias + c);
         for (int j = 0; j < ksize; ++j) {
             const int src = t + j - pad;
-            if (src < 0 || src >= T) continue;
+            if (src < 0 || src >= len) continue;
             const float4 xv = *reinterpret_cast<const float4*>(xb + (long long)src * C + c);
             const float4 wv = *reinterpret_cast<const float4*>(w + (long long)j * C + c);
             acc.x = fmaf(xv.x, wv.x, acc.x);
@@ -193,7 +200,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x
 }
 
 int launch_dwconv(const float* x, const float* w_kc, const float* bias, const float* lnw, const float* lnb, float* y,
-                  int B, int T, int C, int ksize, float eps, hipStream_t s, int pad_left) {
+                  int B, int T, int C, int ksize, float eps, hipStream_t s, int pad_left, ClipLens rl) {
     QA_REQUIRE(C % 4 == 0 && C <= 256 * MAX_V4 && (ksize & 1) && pad_left < ksize, "dwconv: C=%d ksize=%d pad_left=%d unsupported", C,
                ksize, pad_left);
     const unsigned grid = (unsigned)ceil_div((long long)B * T, 4);
@@ -201,10 +208,10 @@ int launch_dwconv(const float* x, const float* w_kc, const float* bias, const fl
     HbmProf prof_(HK_DWCONV_LN, 8.0 * (double)B * T * C, s);
     if (lnw)
         hipLaunchKernelGGL(dwconv_kernel<true>, dim3(grid), dim3(256), 0, s, x, w_kc, bias, lnw, lnb, y, B, T, C, ksize,
-                           eps, pad);
+                           eps, pad, rl.n, rl.mul);
     else
         hipLaunchKernelGGL(dwconv_kernel<false>, dim3(grid), dim3(256), 0, s, x, w_kc, bias, lnw, lnb, y, B, T, C,
-                           ksize, eps, pad);
+                           ksize, eps, pad, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -218,10 +225,11 @@ int launch_dwconv(const float* x, const float* w_kc, const float* bias, const fl
 constexpr int GN_ROWS = 64;
 
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x, double* __restrict__ partial,
-                                                         int T, int C, int G) {
+                                                         int T, int C, int G, const int* __restrict__ lens, int len_mul) {
     extern __shared__ float sh[];  // [2][C]
     const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
-    const int t0 = chunk * GN_ROWS, t1 = min(T, t0 + GN_ROWS);
+    const int len = lens ? min(lens[b] * len_mul, T) : T;  // ragged: a chunk behind the clip's end sums nothing and stores exact zeros
+    const int t0 = chunk * GN_ROWS, t1 = min(len, t0 + GN_ROWS);
     const float* xb = x + (long long)b * T * C;
     for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
         float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
@@ -250,7 +258,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, const double* __restrict__ partial,
                                                        const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ y, int T, int C, int G, int nchunk, float eps,
-                                                       int swish) {
+                                                       int swish, const int* __restrict__ lens, int len_mul) {
     extern __shared__ float sh[];  // [2][G]: mean, rstd
     const int b = blockIdx.y;
     const int cpg = C / G;
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
             s += pp[0];
             q += pp[1];
         }
-        const double n = (double)T * cpg;
+        const double n = (double)(lens ? min(lens[b] * len_mul, T) : T) * cpg;  // ragged: statistics over the clip's own frames
         const double mean = s / n;
         double var = q / n - mean * mean;
         if (var < 0.0) var = 0.0;
@@ -294,16 +302,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 size_t groupnorm_scratch_bytes(int B, int T, int G) { return (size_t)B * ceil_div(T, GN_ROWS) * G * 2 * sizeof(double); }
 
 int launch_groupnorm(const float* x, const float* w, const float* bias, float* y, double* scratch, int B, int T, int C,
-                     int G, float eps, int swish, hipStream_t s) {
+                     int G, float eps, int swish, hipStream_t s, ClipLens rl) {
     QA_REQUIRE(C % 4 == 0 && C % G == 0, "groupnorm: C=%d G=%d unsupported", C, G);
     const int nchunk = (int)ceil_div(T, GN_ROWS);
     HbmProf prof_(HK_GROUPNORM, 8.0 * (double)B * T * C, s);  // algorithmic: x once in, y once out (the two-pass form reads x twice)
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 2 * C * sizeof(float), s, x, scratch, T, C, G);
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 2 * C * sizeof(float), s, x, scratch, T, C, G, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     const long long n4 = (long long)T * (C / 4);
     const unsigned gx = (unsigned)std::min<long long>(ceil_div(n4, 256), 64);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(gx, B), dim3(256), 2 * G * sizeof(float), s, x, scratch, w, bias, y, T, C,
-                       G, nchunk, eps, swish);
+                       G, nchunk, eps, swish, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -376,34 +384,71 @@ int launch_to_channel_last(const float* x, long long sb, long long sc, long long
 }
 
 // codes: library [n_vec = B*N, Q] -> reference [B, Q, N] (codec.py:173-174) and back (codec.py:179-180)
-__global__ void codes_to_bqn_kernel(const long long* __restrict__ src, long long* __restrict__ dst, int B, int N, int Q) {
+// lens (ragged calls, else null): entries at frames n >= lens[b] become -1, the dropped code, whatever the source holds there
+__global__ void codes_to_bqn_kernel(const long long* __restrict__ src, long long* __restrict__ dst, int B, int N, int Q,
+                                    const int* __restrict__ lens) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * N * Q) return;
     const int n = (int)(gid % N);
     const int q = (int)((gid / N) % Q);
     const int b = (int)(gid / ((long long)N * Q));
-    dst[gid] = src[((long long)b * N + n) * Q + q];
+    const long long v = src[((long long)b * N + n) * Q + q];
+    dst[gid] = (lens && n >= lens[b]) ? -1 : v;
 }
 __global__ void codes_from_bqn_kernel(const long long* __restrict__ src, long long* __restrict__ dst, int B, int N,
-                                      int Q) {
+                                      int Q, const int* __restrict__ lens) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * N * Q) return;
     const int q = (int)(gid % Q);
     const int n = (int)((gid / Q) % N);
     const int b = (int)(gid / ((long long)N * Q));
-    dst[gid] = src[((long long)b * Q + q) * N + n];
+    const long long v = src[((long long)b * Q + q) * N + n];
+    dst[gid] = (lens && n >= lens[b]) ? -1 : v;
 }
-int launch_codes_to_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s) {
+int launch_codes_to_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s, const int* lens) {
     const long long total = (long long)B * N * Q;
     if (total == 0) return QA_OK;
-    hipLaunchKernelGGL(codes_to_bqn_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, src, dst, B, N, Q);
+    hipLaunchKernelGGL(codes_to_bqn_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, src, dst, B, N, Q, lens);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
-int launch_codes_from_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s) {
+int launch_codes_from_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s, const int* lens) {
     const long long total = (long long)B * N * Q;
     if (total == 0) return QA_OK;
-    hipLaunchKernelGGL(codes_from_bqn_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, src, dst, B, N, Q);
+    hipLaunchKernelGGL(codes_from_bqn_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, src, dst, B, N, Q, lens);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// Per-clip lengths of a ragged call.  The host vector travels BY VALUE in the launch (as the LM's row lengths do, lm_decode.hip): written
+// on the call's stream in stream order, no staging buffer whose lifetime a later call could cut short.
+constexpr int ROW_LENS_CHUNK = 256;
+struct RowLensArg {
+    int n[ROW_LENS_CHUNK];
+};
+__global__ void row_lens_kernel(int* __restrict__ dst, const RowLensArg a, int n) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = a.n[threadIdx.x];
+}
+int launch_row_lens(int* dst, const int* src, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += ROW_LENS_CHUNK) {
+        RowLensArg a{};
+        const int m = std::min(ROW_LENS_CHUNK, n - i0);
+        for (int i = 0; i < m; ++i) a.n[i] = src[i0 + i];
+        hipLaunchKernelGGL(row_lens_kernel, dim3(1), dim3(ROW_LENS_CHUNK), 0, s, dst + i0, a, m);
+        QA_LAUNCH_CHECK();
+    }
+    return QA_OK;
+}
+// key-padding mask of a ragged transformer call: valid[b, n] = n < lens[b] * mul
+__global__ void len_mask_kernel(unsigned char* __restrict__ valid, int B, int N, const int* __restrict__ lens, int len_mul) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * N) return;
+    const int b = (int)(gid / N), n = (int)(gid - (long long)b * N);
+    valid[gid] = n < lens[b] * len_mul ? 1 : 0;
+}
+int launch_len_mask(unsigned char* valid, int B, int N, ClipLens rl, hipStream_t s) {
+    QA_REQUIRE(rl.n && rl.mul >= 1, "len_mask: no lengths");
+    hipLaunchKernelGGL(len_mask_kernel, dim3((unsigned)ceil_div((long long)B * N, 256)), dim3(256), 0, s, valid, B, N, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -471,15 +516,23 @@ int launch_stft_post(const float* ri, float* out, long long rows, int nb, int ld
 // divide by the folded hann^2 envelope.  frames [B, T, n_fft] (already multiplied by the window inside the
 // inverse-DFT basis), out [B, T*hop].
 __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ win,
-                                                        float* __restrict__ out, int B, int T, int n_fft, int hop) {
+                                                        float* __restrict__ out, int B, int T, int n_fft, int hop,
+                                                        const int* __restrict__ lens, int len_mul) {
     const long long L = (long long)T * hop;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * L) return;
     const int b = (int)(gid / L);
     const long long n = gid - (long long)b * L;
+    // ragged (launch-uniform test): the clip has Tb frames - later frames contribute nothing, the trim and the envelope are those of a
+    // Tb-frame clip, and the samples behind Tb * hop are exactly zero
+    const int Tb = lens ? min(lens[b] * len_mul, T) : T;
+    if (n >= (long long)Tb * hop) {
+        out[gid] = 0.f;
+        return;
+    }
     const long long p = n + (n_fft - hop) / 2;
     int t_hi = (int)(p / hop);
-    if (t_hi > T - 1) t_hi = T - 1;
+    if (t_hi > Tb - 1) t_hi = Tb - 1;
     long long lo = p - n_fft + 1;
     int t_lo = lo <= 0 ? 0 : (int)((lo + hop - 1) / hop);
     float acc = 0.f, env = 0.f;
@@ -492,12 +545,12 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
     out[gid] = acc / env;
 }
 
-int launch_istft_ola(const float* frames, const float* win, float* out, int B, int T, int n_fft, int hop, hipStream_t s) {
+int launch_istft_ola(const float* frames, const float* win, float* out, int B, int T, int n_fft, int hop, hipStream_t s, ClipLens rl) {
     const long long total = (long long)B * T * hop;
     if (total == 0) return QA_OK;
     HbmProf prof_(HK_ISTFT_OLA, 4.0 * ((double)B * T * n_fft + (double)B * T * hop), s);
     hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, frames, win, out, B, T,
-                       n_fft, hop);
+                       n_fft, hop, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

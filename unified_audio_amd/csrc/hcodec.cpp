@@ -122,7 +122,11 @@ struct qa_hcodec : Handle {
         std::vector<SemDecBlock> blocks;
     };
     std::unique_ptr<SemDec> sdec;
+    // ragged calls (qa_hcodec_encode_ragged / _decode_ragged): the clips' code-frame counts [lens_cap], written on the call's stream
+    int* lens_dev = nullptr;
+    int lens_cap = 0;
     ~qa_hcodec() {
+        if (lens_dev) (void)hipFree(lens_dev);
         if (e2_dev) (void)hipFree(e2_dev);
         if (host_sync) (void)hipHostFree(host_sync);
         if (side) (void)hipStreamDestroy(side);
@@ -265,10 +269,16 @@ void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers,
 // ---------------------------------------------------------------- graph helpers
 
 // "same" zero-padded stride-1 conv (vq/conv.py:33-56, semantic_module.py:28-31)
+// ragged calls pass the clips' lengths in frames of x to the layers with a temporal footprint: ConvOpt with rl
+inline ConvOpt with_lens(ConvOpt o, ClipLens rl) {
+    o.lens = rl.n;
+    o.len_mul = rl.mul;
+    return o;
+}
 int conv_same(Ctx& c, const float* x, int B, int T, const ConvW& w, float* y, int prologue = ACT_NONE,
-              int act = ACT_NONE, const float* res = nullptr, bool causal = false) {
+              int act = ACT_NONE, const float* res = nullptr, bool causal = false, ClipLens rl = ClipLens()) {
     const int pad = (w.ksize - 1) / 2;
-    ConvOpt o = conv_geom(1, causal ? w.ksize - 1 : pad, causal ? 0 : pad);
+    ConvOpt o = with_lens(conv_geom(1, causal ? w.ksize - 1 : pad, causal ? 0 : pad), rl);
     o.prologue = prologue;
     o.act = act;
     o.res = res;
@@ -293,7 +303,10 @@ SGeom sconv_geom(int L, int k, int stride, bool causal = false) {
 inline int zpad_left(int k, bool causal) { return causal ? k - 1 : k / 2; }
 inline int zpad_right(int k, bool causal) { return causal ? 0 : k / 2; }
 
-int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const std::string& tap_prefix, bool causal = false) {
+// rl (ragged calls, non-causal): clip b has rl.n[b] * rl.mul of the N frames.  Only the attention looks past a clip's end - the LSTM runs
+// forward, everything else is row-wise - so the lengths become one [B, N] key-padding mask, built once per call, for the KMASK form.
+int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const std::string& tap_prefix, bool causal = false,
+                   ClipLens rl = ClipLens()) {
     const int d = tw.d, H = tw.heads, hd = d / H;
     const int64_t rows = (int64_t)B * N;
     QA_REQUIRE(N <= MAX_POS, "transformer: sequence of %d frames exceeds %d", N, MAX_POS);
@@ -306,6 +319,12 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const
     float* qkv = c.arena.alloc<float>(rows * 3 * d);
     float* att = c.arena.alloc<float>(rows * d);
     float* cst = c.arena.alloc<float>((size_t)B * d);
+    unsigned char* kvalid = nullptr;
+    if (rl.n) {
+        QA_REQUIRE(!causal, "transformer: per-clip lengths exist for the non-causal graph only");
+        kvalid = c.arena.alloc<unsigned char>(rows);
+        QA_RUN(c, launch_len_mask(kvalid, B, N, rl, c.stream));
+    }
     for (size_t l = 0; l < tw.layers.size(); ++l) {
         const TransformerLayerW& L = tw.layers[l];
         const std::string lp = tap_prefix + ".layers." + std::to_string(l);
@@ -316,7 +335,7 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const
         QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
         QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
         QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd,
-                            1.0f / std::sqrt((float)hd), causal ? 1 : 0));
+                            1.0f / std::sqrt((float)hd), causal ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, kvalid));
         c.tap(lp + ".att", att, rows * d);
         QA_TRY(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_attn", x, rows * d);
@@ -438,31 +457,31 @@ int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const Mim
 }
 
 int groupnorm_op(Ctx& c, const float* x, const float* w, const float* b, float* y, int B, int T, int C, int G,
-                 int swish) {
+                 int swish, ClipLens rl = ClipLens()) {
     const size_t mark = c.arena.mark();
     double* scratch = c.arena.alloc<double>(groupnorm_scratch_bytes(B, T, G) / sizeof(double));
-    QA_RUN(c, launch_groupnorm(x, w, b, y, scratch, B, T, C, G, 1e-6f, swish, c.stream));
+    QA_RUN(c, launch_groupnorm(x, w, b, y, scratch, B, T, C, G, 1e-6f, swish, c.stream, rl));
     c.arena.release(mark);
     return QA_OK;
 }
 
-int dec_resblock_op(Ctx& c, const DecResW& w, float* x, int B, int T, int C, int G, bool causal = false) {
+int dec_resblock_op(Ctx& c, const DecResW& w, float* x, int B, int T, int C, int G, bool causal = false, ClipLens rl = ClipLens()) {
     const size_t mark = c.arena.mark();
     float* t1 = c.arena.alloc<float>((size_t)B * T * C);
     float* t2 = c.arena.alloc<float>((size_t)B * T * C);
-    QA_TRY(groupnorm_op(c, x, w.n1w, w.n1b, t1, B, T, C, G, 1));
-    QA_TRY(conv_same(c, t1, B, T, w.c1, t2, ACT_NONE, ACT_NONE, nullptr, causal));
-    QA_TRY(groupnorm_op(c, t2, w.n2w, w.n2b, t1, B, T, C, G, 1));
-    QA_TRY(conv_same(c, t1, B, T, w.c2, x, ACT_NONE, ACT_NONE, x, causal));
+    QA_TRY(groupnorm_op(c, x, w.n1w, w.n1b, t1, B, T, C, G, 1, rl));
+    QA_TRY(conv_same(c, t1, B, T, w.c1, t2, ACT_NONE, ACT_NONE, nullptr, causal, rl));
+    QA_TRY(groupnorm_op(c, t2, w.n2w, w.n2b, t1, B, T, C, G, 1, rl));
+    QA_TRY(conv_same(c, t1, B, T, w.c2, x, ACT_NONE, ACT_NONE, x, causal, rl));
     c.arena.release(mark);
     return QA_OK;
 }
 
 // ---------------------------------------------------------------- encode / decode graphs
 
-int convnext_op(Ctx& c, const ConvNeXtW& w, float* x, float* t1, float* u, int B, int T, int d, bool causal = false) {
+int convnext_op(Ctx& c, const ConvNeXtW& w, float* x, float* t1, float* u, int B, int T, int d, bool causal = false, ClipLens rl = ClipLens()) {
     const int64_t rows = (int64_t)B * T;
-    QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, d, 7, 1e-6f, zpad_left(7, causal)));
+    QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, d, 7, 1e-6f, zpad_left(7, causal), rl));
     QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
     return linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma));
 }
@@ -503,8 +522,11 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
 }
 
 // SEANet encoder + semantic encoder: wav, feat -> emb, sem  [B, N25, code_dim] each (codec.py:169-170)
+// rl (ragged calls; H-Codec 1.0, non-causal): clip b has rl.n[b] code frames.  Every stage's length is that count times the stage's
+// frames per code frame, which is what each layer with a temporal footprint receives; samples and feature frames behind a clip's end are
+// never read, and the rows behind it that the rectangular launches still compute stay finite (they are built from valid rows and zeros).
 int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
-                 int64_t fst, int n_feat, float** emb_out, float** sem_out, int* n25_out) {
+                 int64_t fst, int n_feat, float** emb_out, float** sem_out, int* n25_out, ClipLens rl = ClipLens()) {
     const qa_hcodec_spec& sp = h->spec;
     float* emb = nullptr;
     int N50 = 0, N25 = 0;
@@ -521,24 +543,27 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
             f = fcl;
         }
         Ls = n_feat;
+        int fpc = 1;  // feature frames per code frame at the current stage (ragged calls)
+        for (const auto& blk : h->sem_blocks) fpc *= blk.stride;
         float* s = c.arena.alloc<float>((size_t)B * Ls * SC);
         float* tmp = c.arena.alloc<float>((size_t)B * Ls * SC);
-        QA_TRY(conv_same(c, f, B, Ls, h->sem_in, s));
+        QA_TRY(conv_same(c, f, B, Ls, h->sem_in, s, ACT_NONE, ACT_NONE, nullptr, false, rl.times(fpc)));
         for (size_t bi = 0; bi < h->sem_blocks.size(); ++bi) {
             const auto& blk = h->sem_blocks[bi];
             for (int u = 0; u < 2; ++u) {
-                QA_TRY(conv_same(c, s, B, Ls, blk.u1[u], tmp, ACT_ELU, ACT_ELU));       // ELU(conv1(ELU(s)))
-                QA_TRY(conv_same(c, tmp, B, Ls, blk.u2[u], s, ACT_NONE, ACT_NONE, s));  // s + conv2(.)
+                QA_TRY(conv_same(c, s, B, Ls, blk.u1[u], tmp, ACT_ELU, ACT_ELU, nullptr, false, rl.times(fpc)));  // ELU(conv1(ELU(s)))
+                QA_TRY(conv_same(c, tmp, B, Ls, blk.u2[u], s, ACT_NONE, ACT_NONE, s));  // s + conv2(.): 1x1, row-wise
             }
             const int k = blk.conv.ksize, pad = (k - 1) / 2;
             const int To = (Ls + 2 * pad - k) / blk.stride + 1;
             float* y = c.arena.alloc<float>((size_t)B * To * SC);
-            QA_TRY(conv_op(c, s, SC, B, Ls, blk.conv, y, SC, To, conv_geom(blk.stride, pad, pad)));
+            QA_TRY(conv_op(c, s, SC, B, Ls, blk.conv, y, SC, To, with_lens(conv_geom(blk.stride, pad, pad), rl.times(fpc))));
             s = y;
             Ls = To;
+            fpc /= blk.stride;
         }
         sem = c.arena.alloc<float>((size_t)B * Ls * sp.code_dim);
-        return conv_same(c, s, B, Ls, h->sem_out, sem);
+        return conv_same(c, s, B, Ls, h->sem_out, sem, ACT_NONE, ACT_NONE, nullptr, false, rl.times(fpc));
     };
     if (sp.version == 20) {
         QA_TRY(encoder20(h, c, wav, B, T, &emb, &N50, &N25));
@@ -547,9 +572,13 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
     int C = sp.n_filters, L = T;
     const bool cz = sp.causal != 0;
     // stage 0 at C = 32: conv0 + residual block + ELU in ONE launch (seanet_front.hip): the [B L, 32] conv0 output never exists in HBM
-    const bool front = seanet_front_supported(C, C / 2, L);
+    // ... except in a ragged call, which takes the unfused launches as a capture does: they already resolve padding per (row, tap) and take
+    // the clips' lengths there, where the fused kernel stages whole halo tiles of one shared length
+    const bool front = seanet_front_supported(C, C / 2, L) && !rl.n;
+    int spc = 2;  // samples (then frames) per code frame at the current stage
+    for (int i = 0; i < sp.n_ratios; ++i) spc *= sp.ratios[i];
     float* x = (front && !c.capture) ? nullptr : c.arena.alloc<float>((size_t)B * L * C);
-    if (x) QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, L, C, 7, c.stream, cz ? 6 : -1));
+    if (x) QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, L, C, 7, c.stream, cz ? 6 : -1, rl.times(spc)));
     if (x) c.tap("enc.conv0", x, (int64_t)B * L * C);
     for (int i = 0; i < sp.n_ratios; ++i) {
         const int r = sp.ratios[i];
@@ -564,7 +593,7 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
         // shortcut_1x1(x)
         QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));
         // ELU(k3(ELU(x)))  (reflect pad 1,1)
-        ConvOpt k3 = conv_geom(1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT);
+        ConvOpt k3 = with_lens(conv_geom(1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT), rl.times(spc));
         k3.prologue = ACT_ELU;
         k3.act = ACT_ELU;
         QA_TRY(conv_op(c, x, C, B, L, rb.k3, hh, rb.k3.N, L, k3));
@@ -579,21 +608,22 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
         // the strided conv writes below the mark: allocate its output after releasing the block temporaries is not
         // possible (sc is its input), so the output is carved above them and compacted by pointer swap.
         float* y = c.arena.alloc<float>((size_t)B * g.T_out * 2 * C);
-        QA_TRY(conv_op(c, sc, C, B, L, h->down[i], y, 2 * C, g.T_out, conv_geom(r, g.left, g.right, PAD_REFLECT)));
+        QA_TRY(conv_op(c, sc, C, B, L, h->down[i], y, 2 * C, g.T_out, with_lens(conv_geom(r, g.left, g.right, PAD_REFLECT), rl.times(spc))));
         (void)mark;
         x = y;
         L = g.T_out;
+        spc /= r;
         C *= 2;
         c.tap("enc.stage" + std::to_string(i), x, (int64_t)B * L * C);
     }
     QA_REQUIRE(C == sp.dimension, "encoder: channel ladder ends at %d, spec.dimension is %d", C, sp.dimension);
     N50 = L;
-    QA_TRY(transformer_op(c, h->enc_tr, x, B, N50, "encoder.model." + std::to_string(3 * sp.n_ratios + 2), cz));
+    QA_TRY(transformer_op(c, h->enc_tr, x, B, N50, "encoder.model." + std::to_string(3 * sp.n_ratios + 2), cz, rl.times(spc)));
     c.tap("enc.transformer", x, (int64_t)B * N50 * C);
     const SGeom g = sconv_geom(N50, 4, 2, cz);
     N25 = g.T_out;
     emb = c.arena.alloc<float>((size_t)B * N25 * sp.code_dim);
-    ConvOpt eo = conv_geom(2, g.left, g.right, PAD_REFLECT);
+    ConvOpt eo = with_lens(conv_geom(2, g.left, g.right, PAD_REFLECT), rl.times(spc));
     eo.prologue = ACT_ELU;
     QA_TRY(conv_op(c, x, C, B, N50, h->enc_out, emb, sp.code_dim, N25, eo));
     }
@@ -609,11 +639,11 @@ int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
 }
 
 int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
-                 int64_t fst, int n_feat, long long* ac_out, long long* sc_out) {
+                 int64_t fst, int n_feat, long long* ac_out, long long* sc_out, ClipLens rl = ClipLens()) {
     const qa_hcodec_spec& sp = h->spec;
     float *emb = nullptr, *sem = nullptr;
     int N25 = 0;
-    QA_TRY(encode_front(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, &emb, &sem, &N25));
+    QA_TRY(encode_front(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, &emb, &sem, &N25, rl));
     // ---- RVQ (both streams)
     const int Q = sp.num_quantizers;
     long long* ia = c.arena.alloc<long long>((size_t)B * N25 * Q);
@@ -621,29 +651,30 @@ int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * N25, sp.codebook_size, sp.code_dim));
     QA_RUN(c, launch_rvq_search(emb, (long long)B * N25, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0, rvq_ws, c.stream));
     QA_RUN(c, launch_rvq_search(sem, (long long)B * N25, h->cb_s, h->e2_s, Q, sp.codebook_size, sp.code_dim, is, nullptr, 0, rvq_ws, c.stream));
-    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, N25, Q, c.stream));
-    QA_RUN(c, launch_codes_to_bqn(is, sc_out, B, N25, Q, c.stream));
+    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, N25, Q, c.stream, rl.n));  // ragged: -1 behind a clip's last code frame
+    QA_RUN(c, launch_codes_to_bqn(is, sc_out, B, N25, Q, c.stream, rl.n));
     return QA_OK;
 }
 
-int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav_out);
+int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav_out, ClipLens rl = ClipLens());
 
-int decode_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, int B, int N, float* wav_out) {
+int decode_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, int B, int N, float* wav_out, ClipLens rl = ClipLens()) {
     const qa_hcodec_spec& sp = h->spec;
     const int Q = sp.num_quantizers, D = sp.code_dim;
     const int64_t rows25 = (int64_t)B * N;
     long long* ia = c.arena.alloc<long long>(rows25 * Q);
     long long* is = c.arena.alloc<long long>(rows25 * Q);
     float* cat = c.arena.alloc<float>(rows25 * 2 * D);
-    QA_RUN(c, launch_codes_from_bqn(ac, ia, B, N, Q, c.stream));
-    QA_RUN(c, launch_codes_from_bqn(scodes, is, B, N, Q, c.stream));
+    QA_RUN(c, launch_codes_from_bqn(ac, ia, B, N, Q, c.stream, rl.n));  // ragged: entries behind a clip's end are read as dropped codes
+    QA_RUN(c, launch_codes_from_bqn(scodes, is, B, N, Q, c.stream, rl.n));
     QA_RUN(c, launch_rvq_lookup(ia, rows25, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
     QA_RUN(c, launch_rvq_lookup(is, rows25, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
-    return decode_tail(h, c, cat, B, N, wav_out);
+    return decode_tail(h, c, cat, B, N, wav_out, rl);
 }
 
 // CodecDecoder.forward (codec_decoder.py:58-67) from the concatenated [acoustic | semantic] embeddings [B, N, 2*code_dim]
-int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav_out) {
+// rl (ragged calls; H-Codec 1.0, non-causal): clip b has rl.n[b] of the N code frames, 2 rl.n[b] decoder frames
+int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav_out, ClipLens rl) {
     const qa_hcodec_spec& sp = h->spec;
     const int d = sp.dec_dim;
     const int64_t rows25 = (int64_t)B * N;
@@ -653,6 +684,7 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     const bool cz = sp.causal != 0;
     const int N50 = (v20 ? sp.frame_stride : 2) * N;
     const int64_t rows = (int64_t)B * N50;
+    const ClipLens rl50 = rl.times(2);
     float* x = c.arena.alloc<float>(rows * d);
     if (v20) {
         // H-Codec 2.0 (codec_decoder.py:30-31,64-65): x.repeat_interleave(s) -> Conv1d k = s + 1, "same" zero padding.  The
@@ -664,22 +696,22 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     } else {
         float* up = c.arena.alloc<float>(rows25 * 2 * d);
         QA_TRY(linear_op(c, cat, rows25, h->up, up));
-        QA_TRY(dwconv_op(c, up, h->up_dw, h->up_dwb, nullptr, nullptr, x, B, N50, d, 5, 0.f, zpad_left(5, cz)));
+        QA_TRY(dwconv_op(c, up, h->up_dw, h->up_dwb, nullptr, nullptr, x, B, N50, d, 5, 0.f, zpad_left(5, cz), rl50));
     }
     c.tap("dec.embed", x, rows * d);
-    QA_TRY(dec_resblock_op(c, h->dres[0], x, B, N50, d, sp.gn_groups, cz));
-    QA_TRY(dec_resblock_op(c, h->dres[1], x, B, N50, d, sp.gn_groups, cz));
+    QA_TRY(dec_resblock_op(c, h->dres[0], x, B, N50, d, sp.gn_groups, cz, rl50));
+    QA_TRY(dec_resblock_op(c, h->dres[1], x, B, N50, d, sp.gn_groups, cz, rl50));
     c.tap("dec.prior_res1", x, rows * d);
-    QA_TRY(transformer_op(c, h->dec_tr, x, B, N50, "decoder.prior_net.3", cz));
+    QA_TRY(transformer_op(c, h->dec_tr, x, B, N50, "decoder.prior_net.3", cz, rl50));
     c.tap("dec.transformer", x, rows * d);
-    QA_TRY(dec_resblock_op(c, h->dres[2], x, B, N50, d, sp.gn_groups, cz));
-    QA_TRY(dec_resblock_op(c, h->dres[3], x, B, N50, d, sp.gn_groups, cz));
+    QA_TRY(dec_resblock_op(c, h->dres[2], x, B, N50, d, sp.gn_groups, cz, rl50));
+    QA_TRY(dec_resblock_op(c, h->dres[3], x, B, N50, d, sp.gn_groups, cz, rl50));
     float* t1 = c.arena.alloc<float>(rows * d);
     float* u = c.arena.alloc<float>(rows * sp.dec_inter);
-    QA_TRY(groupnorm_op(c, x, h->gn_w, h->gn_b, t1, B, N50, d, sp.gn_groups, 0));
+    QA_TRY(groupnorm_op(c, x, h->gn_w, h->gn_b, t1, B, N50, d, sp.gn_groups, 0, rl50));
     QA_TRY(layernorm_op(c, t1, h->norm_w, h->norm_b, x, rows, d, 1e-6f));
     c.tap("dec.prior", x, rows * d);
-    for (const ConvNeXtW& w : h->cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz));
+    for (const ConvNeXtW& w : h->cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz, rl50));
     QA_TRY(layernorm_op(c, x, h->fnorm_w, h->fnorm_b, t1, rows, d, 1e-6f));
     c.tap("dec.backbone", t1, rows * d);
     // ISTFT head
@@ -691,7 +723,7 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     QA_RUN(c, launch_istft_spec(y, S, rows, nb, 2 * nb, h->spec_ld, c.stream));
     c.tap("dec.spec", S, rows * h->spec_ld);
     QA_TRY(linear_op(c, S, rows, h->basis, frames));
-    QA_RUN(c, launch_istft_ola(frames, h->window, wav_out, B, N50, sp.n_fft, sp.hop, c.stream));
+    QA_RUN(c, launch_istft_ola(frames, h->window, wav_out, B, N50, sp.n_fft, sp.hop, c.stream, rl50));
     return QA_OK;
 }
 
@@ -1223,6 +1255,87 @@ int qa_hcodec_decode(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t
     QA_REQUIRE(B * N * (h->spec.version == 20 ? h->spec.frame_stride : 2) * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode: output too large");
     QA_REQUIRE(!h->spec.adaptive, "qa_hcodec_decode: this handle is an H-Codec 1.5 model, use qa_hcodec_decode_adaptive");
     return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out); });
+}
+
+// Shared front of the two ragged entry points, all of it before anything is launched.  ragged_refuse: the models that have no per-clip
+// lengths.  ragged_lengths: the lengths themselves (HOST memory, code frames, 1 .. N each; the error names the row).  *ragged = false when
+// every clip has N frames: the caller then takes the rectangular path as it is.  Otherwise the lengths are on their way to h->lens_dev,
+// in stream order in front of the call's kernels.
+static int ragged_refuse(qa_hcodec* h, const char* fn) {
+    const qa_hcodec_spec& sp = h->spec;
+    const char* why = sp.adaptive ? "an H-Codec 1.5 model (spec.adaptive): its alignment and aggregators need per-row sequence lengths of their own"
+                      : sp.version == 20 ? "an H-Codec 2.0 model (spec.version == 20)"
+                      : sp.causal        ? "a causal model (spec.causal)"
+                                         : nullptr;
+    if (why) {
+        set_error("%s: per-clip lengths are implemented for non-causal H-Codec 1.0; this handle is %s", fn, why);
+        return QA_ERR_UNSUPPORTED;
+    }
+    return QA_OK;
+}
+static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, const int64_t* frames, void* stream, bool* ragged) {
+    QA_REQUIRE(B > 0 && N > 0 && B < (1 << 20), "%s: %lld clips of %lld code frames", fn, (long long)B, (long long)N);
+    std::vector<int> len((size_t)B);
+    bool full = true;
+    for (int64_t b = 0; b < B; ++b) {
+        QA_REQUIRE(frames[b] >= 1 && frames[b] <= N, "%s: frames[%lld] = %lld is outside 1 .. N = %lld", fn, (long long)b, (long long)frames[b],
+                   (long long)N);
+        len[(size_t)b] = (int)frames[b];
+        full = full && frames[b] == N;
+    }
+    *ragged = !full;
+    if (full) return QA_OK;
+    QA_HIP(hipSetDevice(h->device));
+    if (B > h->lens_cap) {
+        if (h->lens_dev) QA_HIP(hipFree(h->lens_dev));  // waits for the work that still reads it
+        h->lens_dev = nullptr;
+        h->lens_cap = 0;
+        const int cap = (int)round_up(B, 256);
+        QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->lens_dev), sizeof(int) * (size_t)cap));
+        h->lens_cap = cap;
+    }
+    return launch_row_lens(h->lens_dev, len.data(), (int)B, static_cast<hipStream_t>(stream));
+}
+
+int qa_hcodec_encode_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const int64_t* frames, const float* feat, int64_t fsb,
+                            int64_t fsc, int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, void* stream) {
+    if (!h || !wav || !frames || !feat || !ac || !sc) {
+        set_error("qa_hcodec_encode_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    int hop = 2, fpc = 1;
+    for (int i = 0; i < h->spec.n_ratios; ++i) hop *= h->spec.ratios[i];
+    for (int i = 0; i < h->spec.n_sem_strides; ++i) fpc *= h->spec.sem_strides[i];
+    QA_TRY(ragged_refuse(h, "qa_hcodec_encode_ragged"));
+    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "qa_hcodec_encode_ragged: wav is [%lld, %lld]; T must be a positive multiple of %d",
+               (long long)B, (long long)T, hop);
+    const int64_t N = T / hop;
+    QA_REQUIRE(B * T < (1LL << 31), "qa_hcodec_encode_ragged: batch of %lld x %lld samples is too large", (long long)B, (long long)T);
+    QA_REQUIRE(n_feat == N * fpc, "qa_hcodec_encode_ragged: feat has %lld frames, %lld code frames need %lld", (long long)n_feat, (long long)N,
+               (long long)(N * fpc));
+    bool ragged = false;
+    QA_TRY(ragged_lengths(h, "qa_hcodec_encode_ragged", B, N, frames, stream, &ragged));
+    if (!ragged) return qa_hcodec_encode(h, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc, stream);
+    const ClipLens rl{h->lens_dev, 1};
+    return run(h, stream, [&] {
+        return encode_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc, rl);
+    });
+}
+
+int qa_hcodec_decode_ragged(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t N, const int64_t* frames, float* wav_out,
+                            void* stream) {
+    if (!h || !ac || !sc || !frames || !wav_out) {
+        set_error("qa_hcodec_decode_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_TRY(ragged_refuse(h, "qa_hcodec_decode_ragged"));
+    QA_REQUIRE(B > 0 && N > 0 && B * N * 2 * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode_ragged: codes are [%lld, Q, %lld]",
+               (long long)B, (long long)N);
+    bool ragged = false;
+    QA_TRY(ragged_lengths(h, "qa_hcodec_decode_ragged", B, N, frames, stream, &ragged));
+    if (!ragged) return qa_hcodec_decode(h, ac, sc, B, N, wav_out, stream);
+    const ClipLens rl{h->lens_dev, 1};
+    return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out, rl); });
 }
 
 int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,

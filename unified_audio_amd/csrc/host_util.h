@@ -283,6 +283,9 @@ struct ConvOpt {
     // fused interleaved-pair RoPE on the first rope_n output channels (ConvParams::rope)
     const float* rope = nullptr;
     int rope_n = 0, rope_hd = 0, rope_T = 0, rope_pos0 = 0;
+    // per-clip lengths of a ragged call (ConvParams::lens): clip b holds lens[b] * len_mul input frames
+    const int* lens = nullptr;
+    int len_mul = 0;
 };
 
 // geometry only
@@ -332,6 +335,7 @@ inline int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const C
     p.rope = o.rope; p.rope_n = o.rope_n; p.rope_hd = o.rope_hd; p.rope_T = o.rope_T; p.rope_pos0 = o.rope_pos0;
     p.alpha = o.alpha; p.y2 = o.y2; p.alpha2 = o.alpha2; p.ldy2 = o.ldy2;
     p.math_fp32 = c.gemm_fp32 ? 1 : 0;
+    p.lens = o.lens; p.len_mul = o.len_mul; p.max_pad = std::max(o.pad_left, o.pad_right);
     if (o.shift) {
         p.res = o.shift;
         p.ldr = 0;
@@ -358,8 +362,8 @@ inline int rmsnorm_op(Ctx& c, const float* x, const float* w, float* y, int64_t 
     return c.dry ? QA_OK : launch_rmsnorm(x, w, y, rows, C, eps, c.stream);
 }
 inline int dwconv_op(Ctx& c, const float* x, const float* w_kc, const float* bias, const float* lnw, const float* lnb, float* y, int B,
-                     int T, int C, int ksize, float eps, int pad_left = -1) {
-    return c.dry ? QA_OK : launch_dwconv(x, w_kc, bias, lnw, lnb, y, B, T, C, ksize, eps, c.stream, pad_left);
+                     int T, int C, int ksize, float eps, int pad_left = -1, ClipLens rl = ClipLens()) {
+    return c.dry ? QA_OK : launch_dwconv(x, w_kc, bias, lnw, lnb, y, B, T, C, ksize, eps, c.stream, pad_left, rl);
 }
 inline int to_channel_last_op(Ctx& c, const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T) {
     return c.dry ? QA_OK : launch_to_channel_last(x, sb, sc, st, y, B, C, T, c.stream);

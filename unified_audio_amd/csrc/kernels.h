@@ -9,10 +9,19 @@
 
 namespace qa {
 
+// Per-clip lengths of a ragged H-Codec call: clip b of a [B, T, ...] launch holds n[b] * mul frames (at most T);
+// n is DEVICE memory [B].  n == nullptr (the default everywhere): every clip has T frames, and the kernel takes today's path through one
+// uniform branch, without a load.
+struct ClipLens {
+    const int* n = nullptr;
+    int mul = 0;
+    ClipLens times(int k) const { return ClipLens{n, mul * k}; }
+};
+
 // ew.hip
 // pad_left < 0: the non-causal split of SConv1d (left = pad_total - pad_total / 2); causal SConv1d passes ksize - 1
 int launch_conv_in(const float* x, const float* w_kc, const float* bias, float* y, int B, int T, int Cout, int ksize,
-                   hipStream_t s, int pad_left = -1);
+                   hipStream_t s, int pad_left = -1, ClipLens rl = ClipLens());
 // seanet_front.hip: conv0 + SEANetResnetBlock + the ELU in front of the strided conv, one launch, `a` written once
 bool seanet_front_supported(int C, int hid, int L);
 int launch_seanet_front(const float* wav, const float* w0, const float* b0, const float* w3, const float* b3, const float* wsc,
@@ -23,10 +32,10 @@ int launch_layernorm(const float* x, const float* w, const float* b, float* y, l
                      hipStream_t s);
 // pad_left < 0: "same" (ksize / 2 each side); the causal Conv1d of vq/conv.py:44-47 passes ksize - 1
 int launch_dwconv(const float* x, const float* w_kc, const float* bias, const float* lnw, const float* lnb, float* y,
-                  int B, int T, int C, int ksize, float eps, hipStream_t s, int pad_left = -1);
+                  int B, int T, int C, int ksize, float eps, hipStream_t s, int pad_left = -1, ClipLens rl = ClipLens());
 size_t groupnorm_scratch_bytes(int B, int T, int G);
 int launch_groupnorm(const float* x, const float* w, const float* bias, float* y, double* scratch, int B, int T, int C,
-                     int G, float eps, int swish, hipStream_t s);
+                     int G, float eps, int swish, hipStream_t s, ClipLens rl = ClipLens());
 // rot_heads > 0: only heads 0 .. rot_heads - 1 of q and k are rotated (Conformer `pe_attn_head`, conformer.py:157-160)
 int launch_rope(float* qkv, const float* cos_sin, int B, int N, int H, int hd, long long ld, int pos0, hipStream_t s,
                 int interleaved = 0, int rot_heads = 0);
@@ -47,11 +56,17 @@ int launch_deaggregate(const long long* codes, const long long* len_codes, long 
                        hipStream_t s);
 int launch_to_channel_last(const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T,
                            hipStream_t s);
-int launch_codes_to_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s);
-int launch_codes_from_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s);
+// lens [B] (device) or null: entries n >= lens[b] are written as -1 (the dropped code) whatever the source holds
+int launch_codes_to_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s, const int* lens = nullptr);
+int launch_codes_from_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s, const int* lens = nullptr);
+// dst[0 .. n) (device) = the n host integers src, by value through the launch: no staging buffer, stream-ordered like any kernel
+int launch_row_lens(int* dst, const int* src, int n, hipStream_t s);
+// valid [B, N] bytes: 1 where n < rl.n[b] * rl.mul (the key-padding mask of launch_attention)
+int launch_len_mask(unsigned char* valid, int B, int N, ClipLens rl, hipStream_t s);
 int launch_stft_post(const float* ri, float* out, long long rows, int nb, int ldi, int ldo, hipStream_t s);
 int launch_istft_spec(const float* y, float* S, long long rows, int nb, int ldy, int ldS, hipStream_t s);
-int launch_istft_ola(const float* frames, const float* win, float* out, int B, int T, int n_fft, int hop, hipStream_t s);
+int launch_istft_ola(const float* frames, const float* win, float* out, int B, int T, int n_fft, int hop, hipStream_t s,
+                     ClipLens rl = ClipLens());
 
 int launch_codes_check(const long long* codes, long long n, long long limit, unsigned long long* bad, hipStream_t s);
 int launch_codes_count(const long long* codes, long long n, long long lo, long long limit, unsigned long long* bad, hipStream_t s);

@@ -150,6 +150,40 @@ class SemanticDecoderSpec:
         return s
 
 
+def code_frames(sample_lengths, hop: int):
+    """Code frames of clips of `sample_lengths` samples: ceil(len / hop) each, as `HCodecTokenizer.pad_wav` pads a clip alone.  A list of
+    ints; every length must be positive."""
+    out = []
+    for i, n in enumerate(_int_list(sample_lengths, "lengths")):
+        if n < 1:
+            raise _lib.QuarkAudioError(-1, f"lengths[{i}] = {n}: a clip needs at least one sample")
+        out.append(-(-n // hop))
+    return out
+
+
+def _int_list(values, what: str):
+    """A 1-D sequence / tensor of integers as a list of Python ints (host side: the lengths of a ragged call are host memory)."""
+    if torch.is_tensor(values):
+        if values.dim() != 1 or values.is_floating_point() or values.is_complex():
+            raise _lib.QuarkAudioError(-1, f"{what} must be a 1-D integer tensor, got {values.dtype} {tuple(values.shape)}")
+        values = values.tolist()
+    out = []
+    for i, v in enumerate(values):
+        if isinstance(v, bool) or int(v) != v:
+            raise _lib.QuarkAudioError(-1, f"{what}[{i}] = {v!r} is not an integer")
+        out.append(int(v))
+    return out
+
+
+def _frames_arg(lengths, B: int, what: str = "lengths"):
+    """The `frames` argument of qa_hcodec_encode_ragged / _decode_ragged: a host int64[B] from a list or tensor of code-frame counts.  The
+    range check (1 .. N, naming the row) is the library's; this only refuses what cannot be passed on."""
+    vals = _int_list(lengths, what)
+    if len(vals) != B:
+        raise _lib.QuarkAudioError(-1, f"{what} has {len(vals)} entries for a batch of {B}")
+    return (C.c_int64 * B)(*vals)
+
+
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -394,8 +428,12 @@ class Codec(torch.nn.Module):
 
     # -- hot path ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def encode(self, x: torch.Tensor, feat: torch.Tensor, use_mask=False, domain_split=None, threshold: float = 0.0):
-        """codec.py:166-175.  x [B,1,T] fp32, feat [B, sem_in, N50] fp32 (any strides) -> two int64 [B, nq, N25]."""
+    def encode(self, x: torch.Tensor, feat: torch.Tensor, use_mask=False, domain_split=None, threshold: float = 0.0, lengths=None):
+        """codec.py:166-175.  x [B,1,T] fp32, feat [B, sem_in, N50] fp32 (any strides) -> two int64 [B, nq, N25].
+
+        lengths (non-causal H-Codec 1.0): the clips' lengths in CODE frames, a host list / tensor of B values in 1 .. N25.  Row b then
+        equals encode of that clip alone at its own length; samples and feature frames behind it are never read, codes behind it are
+        -1 (the dropped code).  None: the rectangular call, exactly as before."""
         self._require_loaded()
         if self.spec.version == 20 and x.dim() == 2:  # H-Codec 2.0 passes wav without the channel dim (audio_tokenizer.py:73)
             x = x.unsqueeze(1)
@@ -411,6 +449,11 @@ class Codec(torch.nn.Module):
         ac = torch.empty((B, q, n25), dtype=torch.int64, device=self.device)
         sc = torch.empty((B, q, n25), dtype=torch.int64, device=self.device)
         sb, sch, st = feat.stride()
+        if lengths is not None:
+            frames = _frames_arg(lengths, B)
+            _lib.check(self._lib.qa_hcodec_encode_ragged(self._handle, x.data_ptr(), B, T, frames, feat.data_ptr(), sb, sch, st,
+                                                         feat.shape[2], ac.data_ptr(), sc.data_ptr(), _stream_ptr(self.device)))
+            return ac, sc
         if self.spec.adaptive:
             # codec_adaptive.py:150-178: dict of length-injected codes [B, nq, G]; G is data dependent (host sync, as in the
             # reference: modeling_flexicodec_new.py:910)
@@ -426,15 +469,20 @@ class Codec(torch.nn.Module):
         return ac, sc
 
     @torch.no_grad()
-    def decode(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths: Optional[torch.Tensor] = None):
+    def decode(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths: Optional[torch.Tensor] = None, *,
+               lengths=None):
         """codec.py:178-187.  int64 [B, nq, N25] x2 -> wav [B, N25 * 2 * hop].  H-Codec 1.5 (codec_adaptive.py:181-199):
         length-injected codes [B, nq, G] (or plain codes + token_lengths [B, G]).
         Codes: -1 = dropped (zero vector, as upstream's ResidualVQ masks it; 1.0 / 2.0 only - in the 1.5 wire format negative values carry
         the group lengths).  Any other value outside [0, codebook_size) raises IndexError like F.embedding - AFTER the decode has run on
         clamped indices (r04: the counter is read behind the decode's own host synchronisation, so the failing path costs a full decode;
-        `check_codes=False` skips the check)."""
+        `check_codes=False` skips the check).
+
+        lengths (keyword only; non-causal H-Codec 1.0): the clips' lengths in code frames, a host list / tensor of B values in 1 .. N.
+        Row b then equals decode of its first lengths[b] frames alone; entries behind them are ignored whatever they hold (the range
+        check does not count them), and the waveform is exactly zero from sample lengths[b] * 2 * hop on."""
         self._require_loaded()
-        if self.spec.adaptive:
+        if self.spec.adaptive and lengths is None:
             return self._decode_adaptive(acoustic_codes, semantic_codes, token_lengths)
         q = self.spec.num_quantizers
         if acoustic_codes.shape != semantic_codes.shape or acoustic_codes.dim() != 3 or acoustic_codes.shape[1] != q:
@@ -442,10 +490,21 @@ class Codec(torch.nn.Module):
                                            f"{tuple(acoustic_codes.shape)} / {tuple(semantic_codes.shape)}")
         ac = acoustic_codes.to(device=self.device, dtype=torch.int64).contiguous()
         sc = semantic_codes.to(device=self.device, dtype=torch.int64).contiguous()
-        # -1 is legal: a dropped code, masked to a zero vector by the third-party get_output_from_indices (INTEGRATION.md "Edge semantics")
-        pending = self._check_range_begin((ac, sc), self.spec.codebook_size, lo=-1)
         B, _, N = ac.shape
         wav = torch.empty((B, N * self.spec.dec_upsample * self.spec.hop), dtype=torch.float32, device=self.device)
+        if lengths is not None:
+            frames = _frames_arg(lengths, B)
+            pending = None
+            if self.check_codes:  # the entries behind a clip's end are not codes: the check sees them as dropped
+                fr = torch.tensor(list(frames), dtype=torch.int64, device=self.device)
+                live = (torch.arange(N, device=self.device)[None, :] < fr[:, None])[:, None, :]
+                pending = self._check_range_begin((torch.where(live, ac, -1), torch.where(live, sc, -1)), self.spec.codebook_size, lo=-1)
+            _lib.check(self._lib.qa_hcodec_decode_ragged(self._handle, ac.data_ptr(), sc.data_ptr(), B, N, frames, wav.data_ptr(),
+                                                         _stream_ptr(self.device)))
+            self._check_range_end(pending)
+            return wav
+        # -1 is legal: a dropped code, masked to a zero vector by the third-party get_output_from_indices (INTEGRATION.md "Edge semantics")
+        pending = self._check_range_begin((ac, sc), self.spec.codebook_size, lo=-1)
         _lib.check(self._lib.qa_hcodec_decode(self._handle, ac.data_ptr(), sc.data_ptr(), B, N, wav.data_ptr(),
                                               _stream_ptr(self.device)))
         self._check_range_end(pending)  # IndexError like the reference's F.embedding, raised behind the decode's own synchronisation
@@ -616,8 +675,52 @@ class HCodecTokenizer(torch.nn.Module):
         pad = math.ceil(wav.size(-1) / self.hop_length) * self.hop_length - wav.size(-1)
         return torch.nn.functional.pad(wav, (0, pad))
 
+    def code_frames(self, lengths):
+        """Code frames per clip for clip lengths in SAMPLES: ceil(len / hop) - what `tokenize(wav, lengths=...)` encodes and what
+        `detokenize(..., lengths=...)` takes."""
+        return code_frames(lengths, self.hop_length)
+
     @torch.no_grad()
-    def tokenize(self, wav: torch.Tensor, feats: Optional[torch.Tensor] = None, threshold: float = 0.0):
+    def _tokenize_ragged(self, wav: torch.Tensor, feats: Optional[torch.Tensor], lengths):
+        """tokenize with per-clip lengths in samples: wav [B, Tmax] holds clip b in wav[b, :lengths[b]].  Every clip is zero-padded to its
+        own multiple of the hop, as pad_wav pads a clip alone; what lies behind that is never read."""
+        hop = self.hop_length
+        frames = self.code_frames(lengths)
+        wav = wav.to(self.device)
+        if wav.dim() != 2 or wav.shape[0] != len(frames):
+            raise _lib.QuarkAudioError(-1, f"tokenize(lengths=...) expects wav [B, T] with B = {len(frames)}, got {tuple(wav.shape)}")
+        lens = _int_list(lengths, "lengths")
+        if max(lens) > wav.shape[1]:
+            raise _lib.QuarkAudioError(-1, f"lengths: a clip of {max(lens)} samples does not fit wav [B, {wav.shape[1]}]")
+        wav = self.pad_wav(wav)
+        n = wav.shape[1] // hop
+        pos = torch.arange(wav.shape[1], device=self.device)[None, :]
+        ln = torch.tensor(lens, device=self.device)[:, None]
+        end = torch.tensor(frames, device=self.device)[:, None] * hop
+        wav = wav.masked_fill((pos >= ln) & (pos < end), 0.0)  # pad_wav of each clip alone: zeros up to its own hop multiple
+        if feats is None:
+            # the SSL front-end is not causal and takes no lengths: one pass per distinct padded length, scattered into one batch
+            fpc = int(math.prod(self.model.spec.sem_strides))
+            out = None
+            for f in sorted(set(frames)):
+                rows = [b for b, fb in enumerate(frames) if fb == f]
+                part = self.extract_wav2vec2_features(wav[rows, : f * hop].contiguous())  # (b, t, d)
+                if part.shape[1] < fpc * f:
+                    raise _lib.QuarkAudioError(-1, f"the feature extractor returned {part.shape[1]} frames for {f} code frames, need {fpc * f}")
+                if out is None:
+                    out = torch.zeros((len(frames), fpc * n, part.shape[2]), dtype=torch.float32, device=self.device)
+                out[rows, : fpc * f] = part[:, : fpc * f].to(device=self.device, dtype=torch.float32)
+            feats = out
+        feats = feats.to(self.device).transpose(-2, -1)
+        return self.model.encode(wav.unsqueeze(1), feats, lengths=frames)
+
+    @torch.no_grad()
+    def tokenize(self, wav: torch.Tensor, feats: Optional[torch.Tensor] = None, threshold: float = 0.0, lengths=None):
+        """lengths (non-causal H-Codec 1.0): the clips' lengths in SAMPLES (host list / tensor), wav [B, Tmax] with clip b in its first
+        lengths[b] samples.  Codes of clip b then equal tokenize of that clip alone; `code_frames(lengths)` gives the frames per clip,
+        entries behind them are -1.  feats, when given, are [B, t, d] with clip b's frames first."""
+        if lengths is not None:
+            return self._tokenize_ragged(wav, feats, lengths)
         wav = self.pad_wav(wav.to(self.device))
         if feats is None:
             feats = self.extract_wav2vec2_features(wav)  # (b, t, d)
@@ -627,8 +730,11 @@ class HCodecTokenizer(torch.nn.Module):
         return self.model.encode(wav.unsqueeze(1), feats)
 
     @torch.no_grad()
-    def detokenize(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths=None):
-        """1.0: audio_tokenizer.py:64-66; 1.5: HCodec-1.5/audio_tokenizer.py:83-86 (call as detokenize(**codes))."""
+    def detokenize(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths=None, lengths=None):
+        """1.0: audio_tokenizer.py:64-66; 1.5: HCodec-1.5/audio_tokenizer.py:83-86 (call as detokenize(**codes)).  lengths: the clips'
+        lengths in CODE frames (`code_frames`), passed on to `Codec.decode`."""
+        if lengths is not None:
+            return self.model.decode(acoustic_codes, semantic_codes, lengths=lengths)
         if self.model.spec.adaptive:
             return self.model.decode(acoustic_codes, semantic_codes, token_lengths)
         return self.model.decode(acoustic_codes, semantic_codes)
