@@ -460,29 +460,28 @@ static std::atomic<long long> g_att_kmask_launches;  // launches of a KMASK inst
 // gate [B, H, n_q] and relbias [H, 2R+1] (both optional, together): gated relative position bias, see attention_kernel.
 // Arithmetic: split-6 (SPLIT) unless QA_ATT_MATH = 0 or the caller asks for the fp32 chain (math_fp32: the UniSE LM, whose prefill
 // stays consistent with its fp32 decode kernels)
-int launch_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
-                     long long ldo, int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale,
-                     int causal, hipStream_t s, const float* gate, const float* relbias, int R, int context, int q_pos0,
-                     int ring_end, const unsigned char* kvalid, bool math_fp32) {
-    QA_REQUIRE(n_q > 0 && n_keys > 0 && (!causal || ring_end > 0 || n_keys >= n_q), "attention: n_q=%d n_keys=%d", n_q, n_keys);
-    QA_REQUIRE(context >= 0 && (context == 0 || causal) && (ring_end <= 0 || (causal && context > 0 && !gate)),
+int launch_attention(const AttnArgs& a, hipStream_t s) {
+    QA_REQUIRE(a.n_q > 0 && a.n_keys > 0 && (!a.causal || a.ring_end > 0 || a.n_keys >= a.n_q), "attention: n_q=%d n_keys=%d", a.n_q, a.n_keys);
+    QA_REQUIRE(a.context >= 0 && (a.context == 0 || a.causal) && (a.ring_end <= 0 || (a.causal && a.context > 0 && !a.gate)),
                "attention: a context window needs causal=1; the ring mode needs causal=1 and context > 0");
-    QA_REQUIRE((ldq % 4) == 0 && (ldkv % 4) == 0 && (ldo % 4) == 0, "attention: strides must be multiples of 4");
-    QA_REQUIRE((gate == nullptr) == (relbias == nullptr) && (!gate || (R >= 0 && !causal && n_q == n_keys)),
+    QA_REQUIRE((a.ldq % 4) == 0 && (a.ldkv % 4) == 0 && (a.ldo % 4) == 0, "attention: strides must be multiples of 4");
+    QA_REQUIRE((a.gate == nullptr) == (a.relbias == nullptr) && (!a.gate || (a.R >= 0 && !a.causal && a.n_q == a.n_keys)),
                "attention: gate and relbias come together, for non-causal self-attention");
-    QA_REQUIRE(!kvalid || (!gate && !causal && n_q == n_keys), "attention: the key-padding mask is for non-causal self-attention without bias");
-    const bool split = knob(K_ATT_MATH) != 0 && !math_fp32;
-    const bool bias = gate != nullptr, kmask = kvalid != nullptr;
+    QA_REQUIRE(!a.kvalid || (!a.gate && !a.causal && a.n_q == a.n_keys),
+               "attention: the key-padding mask is for non-causal self-attention without bias");
+    const bool split = knob(K_ATT_MATH) != 0 && !a.math_fp32;
+    const bool bias = a.gate != nullptr, kmask = a.kvalid != nullptr;
     decltype(attention_instance<32, false>(bias, kmask)) kernel;
-    switch (hd) {
+    switch (a.hd) {
         case 32: kernel = split ? attention_instance<32, true>(bias, kmask) : attention_instance<32, false>(bias, kmask); break;
         case 64: kernel = split ? attention_instance<64, true>(bias, kmask) : attention_instance<64, false>(bias, kmask); break;
         case 96: kernel = split ? attention_instance<96, true>(bias, kmask) : attention_instance<96, false>(bias, kmask); break;
         case 128: kernel = split ? attention_instance<128, true>(bias, kmask) : attention_instance<128, false>(bias, kmask); break;
-        default: qa::set_error("attention: head_dim=%d unsupported (32/64/96/128)", hd); return QA_ERR_UNSUPPORTED;
+        default: qa::set_error("attention: head_dim=%d unsupported (32/64/96/128)", a.hd); return QA_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(n_q, 128), H, B), dim3(256), 0, s, q, ldq, k, v, ldkv, kv_batch_stride, out, ldo, n_q,
-                       n_keys, scale, causal, gate, relbias, R, context, q_pos0, ring_end, (int)knob(K_ATT_DEBUG), kvalid);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(a.n_q, 128), a.H, a.B), dim3(256), 0, s, a.q, a.ldq, a.k, a.v, a.ldkv, a.kv_batch_stride,
+                       a.out, a.ldo, a.n_q, a.n_keys, a.scale, a.causal, a.gate, a.relbias, a.R, a.context, a.q_pos0, a.ring_end,
+                       (int)knob(K_ATT_DEBUG), a.kvalid);
     QA_LAUNCH_CHECK();
     g_att_launches[split ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
     if (kmask) g_att_kmask_launches.fetch_add(1, std::memory_order_relaxed);
@@ -535,19 +534,31 @@ extern "C" int qa_debug_att_split_unit(const float* x, long long n, unsigned lon
     return QA_OK;
 }
 
+// what the three hooks below share: the operands, the shape, the scale and the mask mode, as the C ABI spells them
+static qa::AttnArgs debug_attn_args(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out, long long ldo,
+                                    int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale, int causal) {
+    qa::AttnArgs a;
+    a.q = q; a.ldq = ldq; a.out = out; a.ldo = ldo;
+    a.k = k; a.v = v; a.ldkv = ldkv; a.kv_batch_stride = kv_bstride;
+    a.B = B; a.n_q = n_q; a.n_keys = n_keys; a.H = H; a.hd = hd;
+    a.scale = scale; a.causal = causal;
+    return a;
+}
+
 // test hook (not part of the public header): non-causal self-attention under a key-padding mask, kvalid [B, n_keys] bytes (the KMASK
 // instantiations the Conformer condition encoder launches)
 extern "C" int qa_debug_attention_kmask(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out, long long ldo,
                                         int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale,
                                         const unsigned char* kvalid, void* stream) {
-    return qa::launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, 0, static_cast<hipStream_t>(stream),
-                                nullptr, nullptr, 0, 0, 0, 0, kvalid);
+    qa::AttnArgs a = debug_attn_args(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, 0);
+    a.kvalid = kvalid;
+    return qa::launch_attention(a, static_cast<hipStream_t>(stream));
 }
 
 // test / diagnostic hook (not part of the public header): the attention kernel alone on caller-provided buffers
 extern "C" int qa_debug_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out, long long ldo,
                                   int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale, int causal, void* stream) {
-    return qa::launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, causal,
+    return qa::launch_attention(debug_attn_args(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, causal),
                                 static_cast<hipStream_t>(stream));
 }
 
@@ -557,6 +568,8 @@ extern "C" int qa_debug_attention_ex(const float* q, long long ldq, const float*
                                      long long ldo, int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale,
                                      int causal, const float* gate, const float* relbias, int R, int context, int q_pos0, int ring_end,
                                      void* stream) {
-    return qa::launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, causal,
-                                static_cast<hipStream_t>(stream), gate, relbias, R, context, q_pos0, ring_end);
+    qa::AttnArgs a = debug_attn_args(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, causal);
+    a.gate = gate; a.relbias = relbias; a.R = R;
+    a.context = context; a.q_pos0 = q_pos0; a.ring_end = ring_end;
+    return qa::launch_attention(a, static_cast<hipStream_t>(stream));
 }

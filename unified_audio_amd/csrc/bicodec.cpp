@@ -111,8 +111,7 @@ namespace {
 void build_vocos(Loader& L, VocosW* v, const std::string& p, int C, int I, int n_layers, bool ada, float embed_gain, int C_in = 0) {
     L.conv(&v->embed, p + ".embed", C, C_in > 0 ? C_in : C, 7, true, embed_gain);
     if (!ada) {
-        L.vec(&v->nw, p + ".norm.weight", C);
-        L.vec(&v->nb, p + ".norm.bias", C);
+        L.norm(&v->nw, &v->nb, p + ".norm", C);
     }
     v->layers.resize(n_layers);
     for (int i = 0; i < n_layers; ++i) {
@@ -126,16 +125,12 @@ void build_vocos(Loader& L, VocosW* v, const std::string& p, int C, int I, int n
                 for (int j = 0; j < 7; ++j) kc[(size_t)j * C + c] = dw[(size_t)c * 7 + j];
         L.raw(&w.dw, kc);
         L.vec(&w.dwb, q + ".dwconv.bias", C);
-        if (!ada) {
-            L.vec(&w.lnw, q + ".norm.weight", C);
-            L.vec(&w.lnb, q + ".norm.bias", C);
-        }
+        if (!ada) L.norm(&w.lnw, &w.lnb, q + ".norm", C);
         L.vec(&w.gamma, q + ".gamma", C);
         L.conv(&w.pw1, q + ".pwconv1", I, C, 1);
         L.conv(&w.pw2, q + ".pwconv2", C, I, 1);
     }
-    L.vec(&v->fw, p + ".final_layer_norm.weight", C);
-    L.vec(&v->fb, p + ".final_layer_norm.bias", C);
+    L.norm(&v->fw, &v->fb, p + ".final_layer_norm", C);
 }
 
 int build(qa_bicodec* h, const HostTable& tab) {
@@ -700,8 +695,12 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
         if (li > 0) QA_RUN(c, launch_perceiver_ctx(lat, (int64_t)nl * D, nullptr, ctx, B, nl, nf, D, c.stream));
         QA_TRY(linear_op(c, lat, lrows, lw.to_q, q));
         QA_TRY(linear_op(c, ctx, (int64_t)B * nk, lw.to_kv, kv));
-        QA_TRY(attention_op(c, q, inner, kv, kv + inner, 2 * inner, att, inner, B, nl, nk, (int64_t)nk * 2 * inner, sp.perceiver_heads,
-                            sp.perceiver_dim_head, 1.f / std::sqrt((float)sp.perceiver_dim_head), 0));
+        AttnArgs at;  // the latents over the packed keys / values [B nk, 2 inner] of cat(latents, x)
+        at.q = q; at.ldq = inner; at.out = att; at.ldo = inner;
+        at.k = kv; at.v = kv + inner; at.ldkv = 2 * inner; at.kv_batch_stride = (int64_t)nk * 2 * inner;
+        at.B = B; at.n_q = nl; at.n_keys = nk; at.H = sp.perceiver_heads; at.hd = sp.perceiver_dim_head;
+        at.scale = 1.f / std::sqrt((float)sp.perceiver_dim_head);
+        QA_TRY(attention_op(c, at));
         QA_TRY(linear_op(c, att, lrows, lw.to_out, lat, epi(ACT_NONE, lat)));
         QA_TRY(linear_op(c, lat, lrows, lw.ff1, hh));
         QA_RUN(c, launch_geglu(hh, h->ff, gg, h->ffp, lrows, c.stream));

@@ -65,8 +65,7 @@ void lin(Loader& L, Keys& K, ConvW* dst, const std::string& p, int N, int C, flo
 void norm(Loader& L, Keys& K, const float** w, const float** b, const std::string& p, int d) {
     K.seen.insert(p + ".weight");
     K.seen.insert(p + ".bias");
-    L.vec(w, p + ".weight", d);
-    L.vec(b, p + ".bias", d);
+    L.norm(w, b, p, d);
 }
 void feed_forward(Loader& L, Keys& K, FeedForwardW* f, const std::string& p, int d, int inner) {
     norm(L, K, &f->lnw, &f->lnb, p + ".sequential.0", d);
@@ -188,7 +187,8 @@ int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mas
     t.hn = c.arena.alloc<float>(rows * d);
     t.u = c.arena.alloc<float>(rows * std::max(std::max(d * sp.ff_mult, 2 * d), 3 * inner));
     t.v = c.arena.alloc<float>(rows * std::max(inner, d));
-    const float scale = 1.0f / std::sqrt((float)hd);
+    AttnArgs at = attn_packed_qkv(t.u, t.v, B, T, H, hd);
+    at.kvalid = mask;
     for (int l = 0; l < sp.n_layers; ++l) {
         const ConformerLayerW& W = h->layers[l];
         const std::string lp = "conformer." + std::to_string(l);
@@ -197,8 +197,7 @@ int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mas
         QA_TRY(layernorm_op(c, x, W.anw, W.anb, t.hn, rows, d, 1e-5f));
         QA_TRY(linear_op(c, t.hn, rows, W.qkv, t.u));
         QA_TRY(rope_op(c, t.u, h->rope, B, T, H, hd, 3 * inner, 0, sp.rope_interleaved, sp.pe_attn_head < 0 ? 0 : sp.pe_attn_head));
-        QA_TRY(attention_op(c, t.u, 3 * inner, t.u + inner, t.u + 2 * inner, 3 * inner, t.v, inner, B, T, T, (long long)T * 3 * inner, H, hd,
-                            scale, 0, nullptr, nullptr, 0, 0, 0, 0, mask));
+        QA_TRY(attention_op(c, at));
         QA_TRY(linear_op(c, t.v, rows, W.out, t.hn));
         QA_RUN(c, launch_masked_add(x, t.hn, mask, rows, d, c.stream));
         c.tap(lp + ".attn", t.hn, rows * d);

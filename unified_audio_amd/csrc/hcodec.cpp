@@ -122,6 +122,14 @@ struct qa_hcodec : Handle {
         std::vector<SemDecBlock> blocks;
     };
     std::unique_ptr<SemDec> sdec;
+    // frame geometry, set once by build(): frames per CODE frame wherever the graphs or the entry points need a rate
+    struct Geom {
+        int samples = 0;        // waveform samples: 2 * prod(ratios); H-Codec 2.0: hop * frame_stride
+        int feat = 0;           // SSL feature frames: prod(sem_strides)
+        int dec = 0;            // decoder (ISTFT) frames: 2; H-Codec 2.0: frame_stride
+        std::vector<int> enc;   // SEANet: at the input of stage i; enc[n_ratios] = 2, the rate of its transformer (empty for 2.0)
+        std::vector<int> sem;   // semantic encoder: at the input of block i; sem[n_sem_strides] = 1, the rate of its output
+    } geom;
     // ragged calls (qa_hcodec_encode_ragged / _decode_ragged): the clips' code-frame counts [lens_cap], written on the call's stream
     int* lens_dev = nullptr;
     int lens_cap = 0;
@@ -168,7 +176,6 @@ void mimi_rope_table(int hd, int pos0, int n, std::vector<float>* cs) {
     }
 }
 
-// rows of an LSTM matrix / bias go from PyTorch's gate-major order (i,f,g,o blocks of d) to (unit, gate)
 void build_transformer(Loader& b, TransformerW* tw, const std::string& p, int d, int n_layers, int heads, int inter = 0) {
     if (inter <= 0) inter = 4 * d;
     tw->d = d;
@@ -185,6 +192,7 @@ void build_transformer(Loader& b, TransformerW* tw, const std::string& p, int d,
         const float* whh = b.need(ap + ".rnn.weight_hh_l0", (int64_t)4 * d * d);
         const float* bih = b.need(ap + ".rnn.bias_ih_l0", 4 * d);
         const float* bhh = b.need(ap + ".rnn.bias_hh_l0", 4 * d);
+        // rows of an LSTM matrix / bias go from PyTorch's gate-major order (i,f,g,o blocks of d) to (unit, gate)
         std::vector<float> wi((size_t)4 * d * d, 0.f), wh((size_t)4 * d * d, 0.f), bb((size_t)4 * d, 0.f);
         if (wih && whh && bih && bhh) {
             for (int u = 0; u < d; ++u)
@@ -211,14 +219,10 @@ void build_transformer(Loader& b, TransformerW* tw, const std::string& p, int d,
         L.qkv.N = 3 * d; L.qkv.C_in = d; L.qkv.ksize = 1;
         b.raw(&L.qkv.w, wq);
         b.raw(&L.qkv.b, bq);
-        L.o.N = d; L.o.C_in = d; L.o.ksize = 1;
-        b.vec(&L.o.w, ap + ".o_proj.weight", (int64_t)d * d);
-        L.w1.N = inter; L.w1.C_in = d; L.w1.ksize = 1;
-        b.vec(&L.w1.w, lp + ".mlp.w1.weight", (int64_t)inter * d);
-        L.w3.N = inter; L.w3.C_in = d; L.w3.ksize = 1;
-        b.vec(&L.w3.w, lp + ".mlp.w3.weight", (int64_t)inter * d);
-        L.w2.N = d; L.w2.C_in = inter; L.w2.ksize = 1;
-        b.vec(&L.w2.w, lp + ".mlp.w2.weight", (int64_t)inter * d);
+        b.linear(&L.o, ap + ".o_proj.weight", "", d, d);
+        b.linear(&L.w1, lp + ".mlp.w1.weight", "", inter, d);
+        b.linear(&L.w3, lp + ".mlp.w3.weight", "", inter, d);
+        b.linear(&L.w2, lp + ".mlp.w2.weight", "", d, inter);
     }
     // RoPE table, RotaryEmbedding of transformer.py:8-74 evaluated in fp32 like the reference
     const int hd = d / heads, half = hd / 2;
@@ -235,8 +239,7 @@ void build_transformer(Loader& b, TransformerW* tw, const std::string& p, int d,
     b.raw(&tw->rope, cs);
 }
 
-void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers, int heads, int ff, int causal = 0,
-                int context = 0) {
+void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers, int heads, int ff, int causal, int context) {
     mw->d = d;
     mw->heads = heads;
     mw->ff = ff;
@@ -246,20 +249,14 @@ void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers,
     for (int l = 0; l < n_layers; ++l) {
         MimiLayerW& L = mw->layers[l];
         const std::string lp = p + ".layers." + std::to_string(l);
-        b.vec(&L.n1w, lp + ".norm1.weight", d);
-        b.vec(&L.n1b, lp + ".norm1.bias", d);
-        b.vec(&L.n2w, lp + ".norm2.weight", d);
-        b.vec(&L.n2b, lp + ".norm2.bias", d);
+        b.norm(&L.n1w, &L.n1b, lp + ".norm1", d);
+        b.norm(&L.n2w, &L.n2b, lp + ".norm2", d);
         b.vec(&L.ls1, lp + ".layer_scale_1.scale", d);
         b.vec(&L.ls2, lp + ".layer_scale_2.scale", d);
-        L.in_proj.N = 3 * d; L.in_proj.C_in = d;
-        b.vec(&L.in_proj.w, lp + ".self_attn.in_proj_weight", (int64_t)3 * d * d);
-        L.out_proj.N = d; L.out_proj.C_in = d;
-        b.vec(&L.out_proj.w, lp + ".self_attn.out_proj.weight", (int64_t)d * d);
-        L.lin1.N = ff; L.lin1.C_in = d;
-        b.vec(&L.lin1.w, lp + ".linear1.weight", (int64_t)ff * d);
-        L.lin2.N = d; L.lin2.C_in = ff;
-        b.vec(&L.lin2.w, lp + ".linear2.weight", (int64_t)ff * d);
+        b.linear(&L.in_proj, lp + ".self_attn.in_proj_weight", "", 3 * d, d);
+        b.linear(&L.out_proj, lp + ".self_attn.out_proj.weight", "", d, d);
+        b.linear(&L.lin1, lp + ".linear1.weight", "", ff, d);
+        b.linear(&L.lin2, lp + ".linear2.weight", "", d, ff);
     }
     std::vector<float> cs;
     mimi_rope_table(d / heads, 0, MAX_POS, &cs);
@@ -268,28 +265,39 @@ void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers,
 
 // ---------------------------------------------------------------- graph helpers
 
-// "same" zero-padded stride-1 conv (vq/conv.py:33-56, semantic_module.py:28-31)
-// ragged calls pass the clips' lengths in frames of x to the layers with a temporal footprint: ConvOpt with rl
-inline ConvOpt with_lens(ConvOpt o, ClipLens rl) {
-    o.lens = rl.n;
-    o.len_mul = rl.mul;
+// The caller's SSL features [B, sem_in, n] as element strides: any layout
+struct FeatView {
+    const float* p;
+    int64_t sb, sc, st;
+    int n;
+};
+
+// y [t.B, T_out, w.N] = conv(x [t.B, t.T, w.C_in], w) with o's geometry, prologue and epilogue.  In a ragged call the clips' lengths at
+// t's rate go to every filter with a temporal footprint; a 1x1 is row-wise and takes none.
+int conv_at(Ctx& c, const float* x, const TimeAxis& t, const ConvW& w, float* y, int T_out, ConvOpt o) {
+    if (w.ksize > 1) o.rl = t.rl;
+    return conv_op(c, x, w.C_in, t.B, t.T, w, y, w.N, T_out, o);
+}
+// "same" zero-padded stride-1 conv (vq/conv.py:33-56, semantic_module.py:28-31); o: prologue and epilogue
+int conv_same(Ctx& c, const float* x, const TimeAxis& t, const ConvW& w, float* y, ConvOpt o = ConvOpt()) {
+    const int pad = (w.ksize - 1) / 2;
+    o.stride = 1;
+    o.pad_left = t.causal ? w.ksize - 1 : pad;
+    o.pad_right = t.causal ? 0 : pad;
+    return conv_at(c, x, t, w, y, t.T, o);
+}
+// ELU(conv(ELU(x))): the first convolution of a residual unit
+inline ConvOpt elu_conv_elu() {
+    ConvOpt o = epi(ACT_ELU);
+    o.prologue = ACT_ELU;
     return o;
 }
-int conv_same(Ctx& c, const float* x, int B, int T, const ConvW& w, float* y, int prologue = ACT_NONE,
-              int act = ACT_NONE, const float* res = nullptr, bool causal = false, ClipLens rl = ClipLens()) {
-    const int pad = (w.ksize - 1) / 2;
-    ConvOpt o = with_lens(conv_geom(1, causal ? w.ksize - 1 : pad, causal ? 0 : pad), rl);
-    o.prologue = prologue;
-    o.act = act;
-    o.res = res;
-    return conv_op(c, x, w.C_in, B, T, w, y, w.N, T, o);
-}
 
-// SConv1d geometry (encoder_modules/conv.py:195-211, non-causal): returns T_out and the paddings
+// SConv1d geometry (encoder_modules/conv.py:195-211): returns T_out and the paddings
 struct SGeom {
     int T_out, left, right;
 };
-SGeom sconv_geom(int L, int k, int stride, bool causal = false) {
+SGeom sconv_geom(int L, int k, int stride, bool causal) {
     int64_t t = 0;
     int32_t left = 0, right = 0;
     (void)qa_sconv_geometry(L, k, stride, &t, &left, &right);
@@ -303,12 +311,11 @@ SGeom sconv_geom(int L, int k, int stride, bool causal = false) {
 inline int zpad_left(int k, bool causal) { return causal ? k - 1 : k / 2; }
 inline int zpad_right(int k, bool causal) { return causal ? 0 : k / 2; }
 
-// rl (ragged calls, non-causal): clip b has rl.n[b] * rl.mul of the N frames.  Only the attention looks past a clip's end - the LSTM runs
-// forward, everything else is row-wise - so the lengths become one [B, N] key-padding mask, built once per call, for the KMASK form.
-int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const std::string& tap_prefix, bool causal = false,
-                   ClipLens rl = ClipLens()) {
-    const int d = tw.d, H = tw.heads, hd = d / H;
-    const int64_t rows = (int64_t)B * N;
+// In place on x [t.B, t.T, d].  Ragged calls (non-causal): only the attention looks past a clip's end - the LSTM runs forward, everything
+// else is row-wise - so the lengths become one [B, N] key-padding mask, built once per call, for the KMASK form.
+int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, const std::string& tap_prefix) {
+    const int d = tw.d, H = tw.heads, hd = d / H, B = t.B, N = t.T;
+    const int64_t rows = t.rows();
     QA_REQUIRE(N <= MAX_POS, "transformer: sequence of %d frames exceeds %d", N, MAX_POS);
     const size_t mark = c.arena.mark();
     float* hn = c.arena.alloc<float>(rows * d);
@@ -319,11 +326,13 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const
     float* qkv = c.arena.alloc<float>(rows * 3 * d);
     float* att = c.arena.alloc<float>(rows * d);
     float* cst = c.arena.alloc<float>((size_t)B * d);
-    unsigned char* kvalid = nullptr;
-    if (rl.n) {
-        QA_REQUIRE(!causal, "transformer: per-clip lengths exist for the non-causal graph only");
-        kvalid = c.arena.alloc<unsigned char>(rows);
-        QA_RUN(c, launch_len_mask(kvalid, B, N, rl, c.stream));
+    AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
+    at.causal = t.causal ? 1 : 0;
+    if (t.rl.n) {
+        QA_REQUIRE(!t.causal, "transformer: per-clip lengths exist for the non-causal graph only");
+        unsigned char* kvalid = c.arena.alloc<unsigned char>(rows);
+        QA_RUN(c, launch_len_mask(kvalid, B, N, t.rl, c.stream));
+        at.kvalid = kvalid;
     }
     for (size_t l = 0; l < tw.layers.size(); ++l) {
         const TransformerLayerW& L = tw.layers[l];
@@ -334,8 +343,7 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const
         c.tap(lp + ".self_attn.rnn", hl, rows * d);
         QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
         QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
-        QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd,
-                            1.0f / std::sqrt((float)hd), causal ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, kvalid));
+        QA_TRY(attention_op(c, at));
         c.tap(lp + ".att", att, rows * d);
         QA_TRY(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_attn", x, rows * d);
@@ -370,21 +378,25 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
     const bool win = st && st->rope_len > 0;  // RoPE angles from the rolling window (positions beyond the static table)
     const float* rope = win ? st->rope_win : mw.rope;
     const int rope_pos0 = win ? pos0 - st->rope_base : pos0;
-    const float scale = 1.0f / std::sqrt((float)hd);
     QA_TRY(layernorm_op(c, x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f));
     // fused QKV projection with the interleaved-pair RoPE of q and k applied in the GEMM epilogue (one launch less per layer)
     ConvOpt qo;
     qo.rope = rope; qo.rope_n = 2 * d; qo.rope_hd = hd; qo.rope_T = N; qo.rope_pos0 = rope_pos0;
     QA_TRY(linear_op(c, t.hn, rows, L.in_proj, t.qkv, qo));
+    AttnArgs at = attn_packed_qkv(t.qkv, t.att, B, N, H, hd);
     if (st) {
         // RingKVCache.complete(): the chunk's keys / values are written first, then every query attends over the ring
         QA_RUN(c, launch_ring_append(t.qkv + d, t.qkv + 2 * d, 3 * d, st->kc[li], st->vc[li], B, N, d, st->cap, pos0, c.stream));
-        QA_TRY(attention_op(c, t.qkv, 3 * d, st->kc[li], st->vc[li], d, t.att, d, B, N, st->cap, (long long)st->cap * d, H, hd, scale, 1,
-                            nullptr, nullptr, 0, mw.context, pos0, pos0 + N));
+        at.k = st->kc[li]; at.v = st->vc[li]; at.ldkv = d;
+        at.n_keys = st->cap;
+        at.kv_batch_stride = (long long)st->cap * d;
+        at.causal = 1;
+        at.context = mw.context; at.q_pos0 = pos0; at.ring_end = pos0 + N;
     } else {
-        QA_TRY(attention_op(c, t.qkv, 3 * d, t.qkv + d, t.qkv + 2 * d, 3 * d, t.att, d, B, N, N, (long long)N * 3 * d, H, hd, scale,
-                            mw.causal, nullptr, nullptr, 0, mw.causal ? mw.context : 0));
+        at.causal = mw.causal;
+        at.context = mw.causal ? mw.context : 0;
     }
+    QA_TRY(attention_op(c, at));
     QA_TRY(linear_op(c, t.att, rows, L.out_proj, x, epi(ACT_NONE, x, L.ls1)));
     QA_TRY(layernorm_op(c, x, L.n2w, L.n2b, t.hn, rows, d, 1e-5f));
     QA_TRY(linear_op(c, t.hn, rows, L.lin1, t.u, epi(ACT_GELU)));
@@ -418,8 +430,9 @@ int mimi_readout_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, const float
     qo.rope = mw.rope; qo.rope_n = 2 * d; qo.rope_hd = hd; qo.rope_T = N; qo.rope_pos0 = 0;
     QA_TRY(linear_op(c, t.hn, rows, L.in_proj, t.qkv, qo));
     QA_RUN(c, launch_agg_query_rows(x, t.qkv, ro.start, ro.len, ro.nseg, xq, qq, B, ro.T, ro.G, d, c.stream));
-    QA_TRY(attention_op(c, qq, d, t.qkv + d, t.qkv + 2 * d, 3 * d, t.att, d, B, ro.G, N, (long long)N * 3 * d, H, hd,
-                        1.0f / std::sqrt((float)hd), 0));
+    AttnArgs at = attn_packed_qkv(t.qkv, t.att, B, N, H, hd);  // keys and values of all N rows ...
+    at.q = qq; at.ldq = d; at.n_q = ro.G;                      // ... under the G compact queries
+    QA_TRY(attention_op(c, at));
     QA_TRY(linear_op(c, t.att, qrows, L.out_proj, xq, epi(ACT_NONE, xq, L.ls1)));
     QA_TRY(layernorm_op(c, xq, L.n2w, L.n2b, t.hn, qrows, d, 1e-5f));
     QA_TRY(linear_op(c, t.hn, qrows, L.lin1, t.u, epi(ACT_GELU)));
@@ -456,42 +469,42 @@ int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const Mim
     return QA_OK;
 }
 
-int groupnorm_op(Ctx& c, const float* x, const float* w, const float* b, float* y, int B, int T, int C, int G,
-                 int swish, ClipLens rl = ClipLens()) {
+int groupnorm_op(Ctx& c, const float* x, const float* w, const float* b, float* y, const TimeAxis& t, int C, int G, int swish) {
     const size_t mark = c.arena.mark();
-    double* scratch = c.arena.alloc<double>(groupnorm_scratch_bytes(B, T, G) / sizeof(double));
-    QA_RUN(c, launch_groupnorm(x, w, b, y, scratch, B, T, C, G, 1e-6f, swish, c.stream, rl));
+    double* scratch = c.arena.alloc<double>(groupnorm_scratch_bytes(t.B, t.T, G) / sizeof(double));
+    QA_RUN(c, launch_groupnorm(x, w, b, y, scratch, t.B, t.T, C, G, 1e-6f, swish, c.stream, t.rl));
     c.arena.release(mark);
     return QA_OK;
 }
 
-int dec_resblock_op(Ctx& c, const DecResW& w, float* x, int B, int T, int C, int G, bool causal = false, ClipLens rl = ClipLens()) {
+int dec_resblock_op(Ctx& c, const DecResW& w, float* x, const TimeAxis& t, int C, int G) {
     const size_t mark = c.arena.mark();
-    float* t1 = c.arena.alloc<float>((size_t)B * T * C);
-    float* t2 = c.arena.alloc<float>((size_t)B * T * C);
-    QA_TRY(groupnorm_op(c, x, w.n1w, w.n1b, t1, B, T, C, G, 1, rl));
-    QA_TRY(conv_same(c, t1, B, T, w.c1, t2, ACT_NONE, ACT_NONE, nullptr, causal, rl));
-    QA_TRY(groupnorm_op(c, t2, w.n2w, w.n2b, t1, B, T, C, G, 1, rl));
-    QA_TRY(conv_same(c, t1, B, T, w.c2, x, ACT_NONE, ACT_NONE, x, causal, rl));
+    float* t1 = c.arena.alloc<float>((size_t)t.rows() * C);
+    float* t2 = c.arena.alloc<float>((size_t)t.rows() * C);
+    QA_TRY(groupnorm_op(c, x, w.n1w, w.n1b, t1, t, C, G, 1));
+    QA_TRY(conv_same(c, t1, t, w.c1, t2));
+    QA_TRY(groupnorm_op(c, t2, w.n2w, w.n2b, t1, t, C, G, 1));
+    QA_TRY(conv_same(c, t1, t, w.c2, x, epi(ACT_NONE, x)));
     c.arena.release(mark);
     return QA_OK;
 }
 
 // ---------------------------------------------------------------- encode / decode graphs
 
-int convnext_op(Ctx& c, const ConvNeXtW& w, float* x, float* t1, float* u, int B, int T, int d, bool causal = false, ClipLens rl = ClipLens()) {
-    const int64_t rows = (int64_t)B * T;
-    QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, d, 7, 1e-6f, zpad_left(7, causal), rl));
-    QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
-    return linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma));
+int convnext_op(Ctx& c, const ConvNeXtW& w, float* x, float* t1, float* u, const TimeAxis& t, int d) {
+    QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, t.B, t.T, d, 7, 1e-6f, zpad_left(7, t.causal), t.rl));
+    QA_TRY(linear_op(c, t1, t.rows(), w.pw1, u, epi(ACT_GELU)));
+    return linear_op(c, u, t.rows(), w.pw2, x, epi(ACT_NONE, x, w.gamma));
 }
 
 // H-Codec 2.0 CodecEncoder.forward (HCodec-2.0/vq/codec_encoder.py:62-79): wav [B, T] -> emb [B, T / (hop*stride), code_dim]
-int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_out, int* n50_out, int* nf_out) {
+int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float** emb_out, int* n50_out, int* nf_out) {
     const qa_hcodec_spec& sp = h->spec;
+    const int B = tw.B, T = tw.T;
     const int blk = (sp.n_fft - sp.hop) / 2;  // 480: pad = (n_fft - hop) / 2 and hop = 2 * blk, n_fft = 4 * blk
     const int N50 = T / sp.hop, d = sp.enc_dim, nb = sp.n_fft / 2 + 1;
-    const int64_t rows = (int64_t)B * N50;
+    const TimeAxis t{B, N50, tw.causal, ClipLens()};
+    const int64_t rows = t.rows();
     // STFT as an implicit GEMM: the signal is a [B, T / blk, blk] "channel-last" tensor, a frame is 4 consecutive blocks
     // starting one block before 2 t (zero padded), the filter bank is the windowed DFT basis (re | im)
     float* ri = c.arena.alloc<float>(rows * 2 * nb);
@@ -503,12 +516,12 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     float* t1 = c.arena.alloc<float>(rows * d);
     float* u = c.arena.alloc<float>(rows * sp.enc_inter);
     // vq/conv.py Conv1d (:39-47): zero padding (k - stride, 0) in the causal variant, (k / 2, k / 2) otherwise
-    const bool cz = sp.causal != 0;
+    const bool cz = t.causal;
     QA_TRY(conv_op(c, feat, h->stft_ld, B, N50, h->enc_embed, t1, d, N50, conv_geom(1, cz ? 2 : 1, cz ? 0 : 1)));
     QA_TRY(layernorm_op(c, t1, h->enc_norm_w, h->enc_norm_b, x, rows, d, 1e-6f));
-    for (const ConvNeXtW& w : h->enc_cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz));
+    for (const ConvNeXtW& w : h->enc_cnx) QA_TRY(convnext_op(c, w, x, t1, u, t, d));
     c.tap("enc.prior", x, rows * d);
-    QA_TRY(transformer_op(c, h->enc_tr, x, B, N50, "encoder.post_net.1", cz));
+    QA_TRY(transformer_op(c, h->enc_tr, x, t, "encoder.post_net.1"));
     QA_TRY(layernorm_op(c, x, h->enc_fnorm_w, h->enc_fnorm_b, t1, rows, d, 1e-6f));
     const int k = h->enc_out20.ksize, st = sp.frame_stride;
     const int pl = cz ? k - st : k / 2, pr = cz ? 0 : k / 2;
@@ -521,129 +534,132 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, float** emb_
     return QA_OK;
 }
 
-// SEANet encoder + semantic encoder: wav, feat -> emb, sem  [B, N25, code_dim] each (codec.py:169-170)
-// rl (ragged calls; H-Codec 1.0, non-causal): clip b has rl.n[b] code frames.  Every stage's length is that count times the stage's
-// frames per code frame, which is what each layer with a temporal footprint receives; samples and feature frames behind a clip's end are
-// never read, and the rows behind it that the rectangular launches still compute stay finite (they are built from valid rows and zeros).
-int encode_front(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
-                 int64_t fst, int n_feat, float** emb_out, float** sem_out, int* n25_out, ClipLens rl = ClipLens()) {
+// SEANet encoder (seanet.py:121-187): wav [B, T] -> emb [B, N25, code_dim]; *n50_out: the frames of its transformer.
+// Ragged calls (H-Codec 1.0, non-causal): clip b has tw.rl.n[b] code frames.  Every stage's length is that count times the stage's frames
+// per code frame (h->geom.enc), which is what each layer with a temporal footprint receives; samples behind a clip's end are never read,
+// and the rows behind it that the rectangular launches still compute stay finite (they are built from valid rows and zeros).
+int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float** emb_out, int* n50_out, int* n25_out) {
     const qa_hcodec_spec& sp = h->spec;
-    float* emb = nullptr;
-    int N50 = 0, N25 = 0;
-    // ---- semantic encoder (independent of the acoustic branch until the RVQ / alignment)
-    float* sem = nullptr;
-    int Ls = 0;
-    auto semantic_branch = [&]() -> int {
-        QA_REQUIRE(n_feat > 0, "encode: feat has no frames");
-        const float* f = feat;
-        const int SC = sp.sem_ch;
-        if (!(fsc == 1 && fst == sp.sem_in && fsb == (int64_t)n_feat * sp.sem_in)) {
-            float* fcl = c.arena.alloc<float>((size_t)B * n_feat * sp.sem_in);
-            QA_TRY(to_channel_last_op(c, feat, fsb, fsc, fst, fcl, B, sp.sem_in, n_feat));
-            f = fcl;
-        }
-        Ls = n_feat;
-        int fpc = 1;  // feature frames per code frame at the current stage (ragged calls)
-        for (const auto& blk : h->sem_blocks) fpc *= blk.stride;
-        float* s = c.arena.alloc<float>((size_t)B * Ls * SC);
-        float* tmp = c.arena.alloc<float>((size_t)B * Ls * SC);
-        QA_TRY(conv_same(c, f, B, Ls, h->sem_in, s, ACT_NONE, ACT_NONE, nullptr, false, rl.times(fpc)));
-        for (size_t bi = 0; bi < h->sem_blocks.size(); ++bi) {
-            const auto& blk = h->sem_blocks[bi];
-            for (int u = 0; u < 2; ++u) {
-                QA_TRY(conv_same(c, s, B, Ls, blk.u1[u], tmp, ACT_ELU, ACT_ELU, nullptr, false, rl.times(fpc)));  // ELU(conv1(ELU(s)))
-                QA_TRY(conv_same(c, tmp, B, Ls, blk.u2[u], s, ACT_NONE, ACT_NONE, s));  // s + conv2(.): 1x1, row-wise
-            }
-            const int k = blk.conv.ksize, pad = (k - 1) / 2;
-            const int To = (Ls + 2 * pad - k) / blk.stride + 1;
-            float* y = c.arena.alloc<float>((size_t)B * To * SC);
-            QA_TRY(conv_op(c, s, SC, B, Ls, blk.conv, y, SC, To, with_lens(conv_geom(blk.stride, pad, pad), rl.times(fpc))));
-            s = y;
-            Ls = To;
-            fpc /= blk.stride;
-        }
-        sem = c.arena.alloc<float>((size_t)B * Ls * sp.code_dim);
-        return conv_same(c, s, B, Ls, h->sem_out, sem, ACT_NONE, ACT_NONE, nullptr, false, rl.times(fpc));
-    };
-    if (sp.version == 20) {
-        QA_TRY(encoder20(h, c, wav, B, T, &emb, &N50, &N25));
-    } else {
-    // ---- SEANet encoder
-    int C = sp.n_filters, L = T;
-    const bool cz = sp.causal != 0;
+    const int B = tw.B;
+    const bool cz = tw.causal;
+    int C = sp.n_filters;
+    TimeAxis t = tw;
     // stage 0 at C = 32: conv0 + residual block + ELU in ONE launch (seanet_front.hip): the [B L, 32] conv0 output never exists in HBM
     // ... except in a ragged call, which takes the unfused launches as a capture does: they already resolve padding per (row, tap) and take
     // the clips' lengths there, where the fused kernel stages whole halo tiles of one shared length
-    const bool front = seanet_front_supported(C, C / 2, L) && !rl.n;
-    int spc = 2;  // samples (then frames) per code frame at the current stage
-    for (int i = 0; i < sp.n_ratios; ++i) spc *= sp.ratios[i];
-    float* x = (front && !c.capture) ? nullptr : c.arena.alloc<float>((size_t)B * L * C);
-    if (x) QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, L, C, 7, c.stream, cz ? 6 : -1, rl.times(spc)));
-    if (x) c.tap("enc.conv0", x, (int64_t)B * L * C);
+    const bool front = seanet_front_supported(C, C / 2, t.T) && !t.rl.n;
+    float* x = (front && !c.capture) ? nullptr : c.arena.alloc<float>((size_t)t.rows() * C);
+    if (x) QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, t.T, C, 7, c.stream, cz ? 6 : -1, t.rl));
+    if (x) c.tap("enc.conv0", x, t.rows() * C);
     for (int i = 0; i < sp.n_ratios; ++i) {
-        const int r = sp.ratios[i];
+        const int r = sp.ratios[i], L = t.T;
         const ResBlockW& rb = h->res[i];
-        const size_t mark = c.arena.mark();
+        // the block's temporaries stay allocated to the end of the call
         float* sc = c.arena.alloc<float>((size_t)B * L * C);
         if (i == 0 && front) {
             QA_RUN(c, launch_seanet_front(wav, h->conv0_w, h->conv0_b, rb.k3.w, rb.k3.b, rb.sc.w, rb.sc.b, rb.pw.w, rb.pw.b, sc, B, L, C,
                                           C / 2, cz ? 1 : 0, c.stream));
         } else {
-        float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
-        // shortcut_1x1(x)
-        QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));
-        // ELU(k3(ELU(x)))  (reflect pad 1,1)
-        ConvOpt k3 = with_lens(conv_geom(1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT), rl.times(spc));
-        k3.prologue = ACT_ELU;
-        k3.act = ACT_ELU;
-        QA_TRY(conv_op(c, x, C, B, L, rb.k3, hh, rb.k3.N, L, k3));
-        // ELU(shortcut + 1x1(.))  -> the activation in front of the down-sampling conv is fused here
-        ConvOpt pw;
-        pw.res = sc;
-        pw.ldr = C;
-        pw.post_act = ACT_ELU;
-        QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, pw));
+            float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
+            // shortcut_1x1(x)
+            QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));
+            // ELU(k3(ELU(x)))  (reflect pad 1,1)
+            ConvOpt k3 = conv_geom(1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT);
+            k3.prologue = ACT_ELU;
+            k3.act = ACT_ELU;
+            QA_TRY(conv_at(c, x, t, rb.k3, hh, L, k3));
+            // ELU(shortcut + 1x1(.))  -> the activation in front of the down-sampling conv is fused here
+            ConvOpt pw;
+            pw.res = sc;
+            pw.ldr = C;
+            pw.post_act = ACT_ELU;
+            QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, pw));
         }
         const SGeom g = sconv_geom(L, 2 * r, r, cz);
-        // the strided conv writes below the mark: allocate its output after releasing the block temporaries is not
-        // possible (sc is its input), so the output is carved above them and compacted by pointer swap.
         float* y = c.arena.alloc<float>((size_t)B * g.T_out * 2 * C);
-        QA_TRY(conv_op(c, sc, C, B, L, h->down[i], y, 2 * C, g.T_out, with_lens(conv_geom(r, g.left, g.right, PAD_REFLECT), rl.times(spc))));
-        (void)mark;
+        QA_TRY(conv_at(c, sc, t, h->down[i], y, g.T_out, conv_geom(r, g.left, g.right, PAD_REFLECT)));
         x = y;
-        L = g.T_out;
-        spc /= r;
+        t = t.at(g.T_out, h->geom.enc[i + 1]);
         C *= 2;
-        c.tap("enc.stage" + std::to_string(i), x, (int64_t)B * L * C);
+        c.tap("enc.stage" + std::to_string(i), x, t.rows() * C);
     }
     QA_REQUIRE(C == sp.dimension, "encoder: channel ladder ends at %d, spec.dimension is %d", C, sp.dimension);
-    N50 = L;
-    QA_TRY(transformer_op(c, h->enc_tr, x, B, N50, "encoder.model." + std::to_string(3 * sp.n_ratios + 2), cz, rl.times(spc)));
-    c.tap("enc.transformer", x, (int64_t)B * N50 * C);
-    const SGeom g = sconv_geom(N50, 4, 2, cz);
-    N25 = g.T_out;
-    emb = c.arena.alloc<float>((size_t)B * N25 * sp.code_dim);
-    ConvOpt eo = with_lens(conv_geom(2, g.left, g.right, PAD_REFLECT), rl.times(spc));
+    QA_TRY(transformer_op(c, h->enc_tr, x, t, "encoder.model." + std::to_string(3 * sp.n_ratios + 2)));
+    c.tap("enc.transformer", x, t.rows() * C);
+    const SGeom g = sconv_geom(t.T, 4, 2, cz);
+    float* emb = c.arena.alloc<float>((size_t)B * g.T_out * sp.code_dim);
+    ConvOpt eo = conv_geom(2, g.left, g.right, PAD_REFLECT);
     eo.prologue = ACT_ELU;
-    QA_TRY(conv_op(c, x, C, B, N50, h->enc_out, emb, sp.code_dim, N25, eo));
-    }
-    c.tap("enc.emb", emb, (int64_t)B * N25 * sp.code_dim);
-    QA_TRY(semantic_branch());
-    QA_REQUIRE(Ls == N25, "encode: semantic stream has %d frames, acoustic stream %d (feat must have T/%d frames)", Ls,
-               N25, T / std::max(1, N50));
-    c.tap("enc.sem", sem, (int64_t)B * Ls * sp.code_dim);
+    QA_TRY(conv_at(c, x, t, h->enc_out, emb, g.T_out, eo));
     *emb_out = emb;
+    *n50_out = t.T;
+    *n25_out = g.T_out;
+    return QA_OK;
+}
+
+// Semantic encoder (semantic_module.py:157-201): feat [B, sem_in, f.n] -> sem [B, *ls_out, code_dim].  tf: the feature frames' axis; in a
+// ragged call feature frames behind a clip's end are never read (the rates of the stages are h->geom.sem).
+int semantic_encoder(qa_hcodec* h, Ctx& c, const FeatView& f, const TimeAxis& tf, float** sem_out, int* ls_out) {
+    const qa_hcodec_spec& sp = h->spec;
+    QA_REQUIRE(f.n > 0, "encode: feat has no frames");
+    const int B = tf.B, SC = sp.sem_ch;
+    const float* fcl = f.p;
+    if (!(f.sc == 1 && f.st == sp.sem_in && f.sb == (int64_t)f.n * sp.sem_in)) {
+        float* buf = c.arena.alloc<float>((size_t)B * f.n * sp.sem_in);
+        QA_TRY(to_channel_last_op(c, f.p, f.sb, f.sc, f.st, buf, B, sp.sem_in, f.n));
+        fcl = buf;
+    }
+    TimeAxis t = tf;
+    float* s = c.arena.alloc<float>((size_t)t.rows() * SC);
+    float* tmp = c.arena.alloc<float>((size_t)t.rows() * SC);
+    QA_TRY(conv_same(c, fcl, t, h->sem_in, s));
+    for (size_t bi = 0; bi < h->sem_blocks.size(); ++bi) {
+        const auto& blk = h->sem_blocks[bi];
+        for (int u = 0; u < 2; ++u) {
+            QA_TRY(conv_same(c, s, t, blk.u1[u], tmp, elu_conv_elu()));      // ELU(conv1(ELU(s)))
+            QA_TRY(conv_same(c, tmp, t, blk.u2[u], s, epi(ACT_NONE, s)));  // s + conv2(.): 1x1, row-wise
+        }
+        const int k = blk.conv.ksize, pad = (k - 1) / 2;
+        const int To = (t.T + 2 * pad - k) / blk.stride + 1;
+        float* y = c.arena.alloc<float>((size_t)B * To * SC);
+        QA_TRY(conv_at(c, s, t, blk.conv, y, To, conv_geom(blk.stride, pad, pad)));
+        s = y;
+        t = t.at(To, h->geom.sem[bi + 1]);
+    }
+    float* sem = c.arena.alloc<float>((size_t)t.rows() * sp.code_dim);
+    QA_TRY(conv_same(c, s, t, h->sem_out, sem));
     *sem_out = sem;
+    *ls_out = t.T;
+    return QA_OK;
+}
+
+// acoustic encoder + semantic encoder: wav, feat -> emb, sem  [B, N25, code_dim] each (codec.py:169-170); independent of each other
+// until the RVQ / alignment.  tw: the waveform's axis (in a ragged call its lengths are samples, h->geom.samples per code frame).
+int encode_front(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, const FeatView& f, float** emb_out, float** sem_out,
+                 int* n25_out) {
+    int N50 = 0, N25 = 0, Ls = 0;
+    if (h->spec.version == 20) {
+        QA_TRY(encoder20(h, c, wav, tw, emb_out, &N50, &N25));
+    } else {
+        QA_TRY(seanet_encoder(h, c, wav, tw, emb_out, &N50, &N25));
+    }
+    c.tap("enc.emb", *emb_out, (int64_t)tw.B * N25 * h->spec.code_dim);
+    TimeAxis tf = tw.at(f.n, h->geom.feat);
+    tf.causal = false;  // the semantic encoder has no causal variant
+    QA_TRY(semantic_encoder(h, c, f, tf, sem_out, &Ls));
+    QA_REQUIRE(Ls == N25, "encode: semantic stream has %d frames, acoustic stream %d (feat must have T/%d frames)", Ls, N25,
+               tw.T / std::max(1, N50));
+    c.tap("enc.sem", *sem_out, (int64_t)tw.B * Ls * h->spec.code_dim);
     *n25_out = N25;
     return QA_OK;
 }
 
-int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
-                 int64_t fst, int n_feat, long long* ac_out, long long* sc_out, ClipLens rl = ClipLens()) {
+int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, const FeatView& f, long long* ac_out, long long* sc_out) {
     const qa_hcodec_spec& sp = h->spec;
+    const int B = tw.B;
     float *emb = nullptr, *sem = nullptr;
     int N25 = 0;
-    QA_TRY(encode_front(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, &emb, &sem, &N25, rl));
+    QA_TRY(encode_front(h, c, wav, tw, f, &emb, &sem, &N25));
     // ---- RVQ (both streams)
     const int Q = sp.num_quantizers;
     long long* ia = c.arena.alloc<long long>((size_t)B * N25 * Q);
@@ -651,67 +667,48 @@ int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const flo
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * N25, sp.codebook_size, sp.code_dim));
     QA_RUN(c, launch_rvq_search(emb, (long long)B * N25, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0, rvq_ws, c.stream));
     QA_RUN(c, launch_rvq_search(sem, (long long)B * N25, h->cb_s, h->e2_s, Q, sp.codebook_size, sp.code_dim, is, nullptr, 0, rvq_ws, c.stream));
-    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, N25, Q, c.stream, rl.n));  // ragged: -1 behind a clip's last code frame
-    QA_RUN(c, launch_codes_to_bqn(is, sc_out, B, N25, Q, c.stream, rl.n));
+    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, N25, Q, c.stream, tw.rl.n));  // ragged: -1 behind a clip's last code frame
+    QA_RUN(c, launch_codes_to_bqn(is, sc_out, B, N25, Q, c.stream, tw.rl.n));
     return QA_OK;
 }
 
-int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav_out, ClipLens rl = ClipLens());
-
-int decode_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, int B, int N, float* wav_out, ClipLens rl = ClipLens()) {
+// CodecDecoder.forward (codec_decoder.py:58-67) from the concatenated [acoustic | semantic] embeddings [B, N, 2*code_dim]; tc: the code
+// frames' axis.  Ragged calls (H-Codec 1.0, non-causal): clip b has tc.rl.n[b] of the N code frames, 2 tc.rl.n[b] decoder frames.
+int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, const TimeAxis& tc, float* wav_out) {
     const qa_hcodec_spec& sp = h->spec;
-    const int Q = sp.num_quantizers, D = sp.code_dim;
-    const int64_t rows25 = (int64_t)B * N;
-    long long* ia = c.arena.alloc<long long>(rows25 * Q);
-    long long* is = c.arena.alloc<long long>(rows25 * Q);
-    float* cat = c.arena.alloc<float>(rows25 * 2 * D);
-    QA_RUN(c, launch_codes_from_bqn(ac, ia, B, N, Q, c.stream, rl.n));  // ragged: entries behind a clip's end are read as dropped codes
-    QA_RUN(c, launch_codes_from_bqn(scodes, is, B, N, Q, c.stream, rl.n));
-    QA_RUN(c, launch_rvq_lookup(ia, rows25, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
-    QA_RUN(c, launch_rvq_lookup(is, rows25, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
-    return decode_tail(h, c, cat, B, N, wav_out, rl);
-}
-
-// CodecDecoder.forward (codec_decoder.py:58-67) from the concatenated [acoustic | semantic] embeddings [B, N, 2*code_dim]
-// rl (ragged calls; H-Codec 1.0, non-causal): clip b has rl.n[b] of the N code frames, 2 rl.n[b] decoder frames
-int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav_out, ClipLens rl) {
-    const qa_hcodec_spec& sp = h->spec;
-    const int d = sp.dec_dim;
-    const int64_t rows25 = (int64_t)B * N;
-    // sub-pixel upsampler: 1x1 conv to 2*d channels; in channel-last layout the pixel shuffle (vq/conv.py:86-88) is a
-    // pure reinterpretation [B, N, 2, d] -> [B, 2N, d]
-    const bool v20 = sp.version == 20;
-    const bool cz = sp.causal != 0;
-    const int N50 = (v20 ? sp.frame_stride : 2) * N;
-    const int64_t rows = (int64_t)B * N50;
-    const ClipLens rl50 = rl.times(2);
+    const int d = sp.dec_dim, B = tc.B, N = tc.T;
+    const int64_t rows25 = tc.rows();
+    const TimeAxis t = tc.at(h->geom.dec * N, h->geom.dec);  // the decoder's frames
+    const int64_t rows = t.rows();
     float* x = c.arena.alloc<float>(rows * d);
-    if (v20) {
+    if (sp.version == 20) {
         // H-Codec 2.0 (codec_decoder.py:30-31,64-65): x.repeat_interleave(s) -> Conv1d k = s + 1, "same" zero padding.  The
         // repetition is folded into the implicit-GEMM gather (frame r reads row r / s), nothing is materialised.
         const int k = h->dec_embed20.ksize;
-        ConvOpt o = conv_geom(1, cz ? k - 1 : k / 2, cz ? 0 : k / 2);
+        ConvOpt o = conv_geom(1, zpad_left(k, t.causal), zpad_right(k, t.causal));
         o.in_rep = sp.frame_stride;
-        QA_TRY(conv_op(c, cat, 2 * sp.code_dim, B, N, h->dec_embed20, x, d, N50, o));
+        QA_TRY(conv_op(c, cat, 2 * sp.code_dim, B, N, h->dec_embed20, x, d, t.T, o));
     } else {
+        // sub-pixel upsampler: 1x1 conv to 2*d channels; in channel-last layout the pixel shuffle (vq/conv.py:86-88) is a
+        // pure reinterpretation [B, N, 2, d] -> [B, 2N, d]
         float* up = c.arena.alloc<float>(rows25 * 2 * d);
         QA_TRY(linear_op(c, cat, rows25, h->up, up));
-        QA_TRY(dwconv_op(c, up, h->up_dw, h->up_dwb, nullptr, nullptr, x, B, N50, d, 5, 0.f, zpad_left(5, cz), rl50));
+        QA_TRY(dwconv_op(c, up, h->up_dw, h->up_dwb, nullptr, nullptr, x, B, t.T, d, 5, 0.f, zpad_left(5, t.causal), t.rl));
     }
     c.tap("dec.embed", x, rows * d);
-    QA_TRY(dec_resblock_op(c, h->dres[0], x, B, N50, d, sp.gn_groups, cz, rl50));
-    QA_TRY(dec_resblock_op(c, h->dres[1], x, B, N50, d, sp.gn_groups, cz, rl50));
+    QA_TRY(dec_resblock_op(c, h->dres[0], x, t, d, sp.gn_groups));
+    QA_TRY(dec_resblock_op(c, h->dres[1], x, t, d, sp.gn_groups));
     c.tap("dec.prior_res1", x, rows * d);
-    QA_TRY(transformer_op(c, h->dec_tr, x, B, N50, "decoder.prior_net.3", cz, rl50));
+    QA_TRY(transformer_op(c, h->dec_tr, x, t, "decoder.prior_net.3"));
     c.tap("dec.transformer", x, rows * d);
-    QA_TRY(dec_resblock_op(c, h->dres[2], x, B, N50, d, sp.gn_groups, cz, rl50));
-    QA_TRY(dec_resblock_op(c, h->dres[3], x, B, N50, d, sp.gn_groups, cz, rl50));
+    QA_TRY(dec_resblock_op(c, h->dres[2], x, t, d, sp.gn_groups));
+    QA_TRY(dec_resblock_op(c, h->dres[3], x, t, d, sp.gn_groups));
     float* t1 = c.arena.alloc<float>(rows * d);
     float* u = c.arena.alloc<float>(rows * sp.dec_inter);
-    QA_TRY(groupnorm_op(c, x, h->gn_w, h->gn_b, t1, B, N50, d, sp.gn_groups, 0, rl50));
+    QA_TRY(groupnorm_op(c, x, h->gn_w, h->gn_b, t1, t, d, sp.gn_groups, 0));
     QA_TRY(layernorm_op(c, t1, h->norm_w, h->norm_b, x, rows, d, 1e-6f));
     c.tap("dec.prior", x, rows * d);
-    for (const ConvNeXtW& w : h->cnx) QA_TRY(convnext_op(c, w, x, t1, u, B, N50, d, cz, rl50));
+    for (const ConvNeXtW& w : h->cnx) QA_TRY(convnext_op(c, w, x, t1, u, t, d));
     QA_TRY(layernorm_op(c, x, h->fnorm_w, h->fnorm_b, t1, rows, d, 1e-6f));
     c.tap("dec.backbone", t1, rows * d);
     // ISTFT head
@@ -723,8 +720,22 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, int B, int N, float* wav
     QA_RUN(c, launch_istft_spec(y, S, rows, nb, 2 * nb, h->spec_ld, c.stream));
     c.tap("dec.spec", S, rows * h->spec_ld);
     QA_TRY(linear_op(c, S, rows, h->basis, frames));
-    QA_RUN(c, launch_istft_ola(frames, h->window, wav_out, B, N50, sp.n_fft, sp.hop, c.stream, rl50));
+    QA_RUN(c, launch_istft_ola(frames, h->window, wav_out, B, t.T, sp.n_fft, sp.hop, c.stream, t.rl));
     return QA_OK;
+}
+
+int decode_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, const TimeAxis& tc, float* wav_out) {
+    const qa_hcodec_spec& sp = h->spec;
+    const int Q = sp.num_quantizers, D = sp.code_dim, B = tc.B, N = tc.T;
+    const int64_t rows25 = tc.rows();
+    long long* ia = c.arena.alloc<long long>(rows25 * Q);
+    long long* is = c.arena.alloc<long long>(rows25 * Q);
+    float* cat = c.arena.alloc<float>(rows25 * 2 * D);
+    QA_RUN(c, launch_codes_from_bqn(ac, ia, B, N, Q, c.stream, tc.rl.n));  // ragged: entries behind a clip's end are read as dropped codes
+    QA_RUN(c, launch_codes_from_bqn(scodes, is, B, N, Q, c.stream, tc.rl.n));
+    QA_RUN(c, launch_rvq_lookup(ia, rows25, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
+    QA_RUN(c, launch_rvq_lookup(is, rows25, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
+    return decode_tail(h, c, cat, tc, wav_out);
 }
 
 // ---- H-Codec 1.5 (codec_adaptive.py:150-199)
@@ -737,13 +748,13 @@ int read_scalar(Ctx& c, qa_hcodec* h, const int* dev, int* out) {
     return QA_OK;
 }
 
-int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
-                          int64_t fst, int n_feat, long long* ac_out, long long* sc_out, int* G_out, float threshold) {
+int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, const FeatView& f, long long* ac_out,
+                          long long* sc_out, int* G_out, float threshold) {
     const qa_hcodec_spec& sp = h->spec;
-    const int D = sp.code_dim, Q = sp.num_quantizers;
+    const int D = sp.code_dim, Q = sp.num_quantizers, B = tw.B;
     float *emb = nullptr, *sem = nullptr;
     int N = 0;
-    QA_TRY(encode_front(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, &emb, &sem, &N));
+    QA_TRY(encode_front(h, c, wav, tw, f, &emb, &sem, &N));
     int* seg = c.arena.alloc<int>((size_t)B * N);
     int* start = c.arena.alloc<int>((size_t)B * N);
     int* len = c.arena.alloc<int>((size_t)B * N);
@@ -795,11 +806,11 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, 
     return QA_OK;
 }
 
-int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, int B, int G, int N,
-                          float* wav_out) {
+// tc: the axis of the N de-aggregated code frames; G groups per clip in the codes
+int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, const TimeAxis& tc, int G, float* wav_out) {
     const qa_hcodec_spec& sp = h->spec;
-    const int Q = sp.num_quantizers, D = sp.code_dim;
-    const int64_t rows = (int64_t)B * N;
+    const int Q = sp.num_quantizers, D = sp.code_dim, B = tc.B, N = tc.T;
+    const int64_t rows = tc.rows();
     long long* ia = c.arena.alloc<long long>(rows * Q);
     long long* is = c.arena.alloc<long long>(rows * Q);
     float* cat = c.arena.alloc<float>(rows * 2 * D);
@@ -810,7 +821,7 @@ int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long 
     QA_RUN(c, launch_rvq_lookup(is, rows, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
     QA_TRY(mimi_op(c, h->bottleneck, cat, B, N));
     c.tap("dec.bottleneck", cat, rows * 2 * D);
-    return decode_tail(h, c, cat, B, N, wav_out);
+    return decode_tail(h, c, cat, tc, wav_out);
 }
 
 // ---- Codec.forward (codec.py:138-162, codec_adaptive.py:100-148): encode -> RVQ -> decode with the codes kept on the device, and the
@@ -825,9 +836,10 @@ int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int
     QA_TRY(conv_op(c, z, ldz, B, L, sd.conv1, x, C, L, conv_geom(1, 1, 1)));
     for (const auto& blk : sd.blocks) {
         const int s = blk.stride, co = blk.c_out, To = L * s;
+        const TimeAxis to{B, To, false, ClipLens()};
         float* y = c.arena.alloc<float>((size_t)B * To * co);
         if (s == 1) {
-            QA_TRY(conv_same(c, x, B, L, blk.conv, y));
+            QA_TRY(conv_same(c, x, to, blk.conv, y));
         } else {  // ConvTranspose1d: phase phi writes rows q * s + phi (row stride s * co)
             for (int phi = 0; phi < s; ++phi) {
                 const ConvW& w = blk.phase[phi];
@@ -837,8 +849,8 @@ int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int
         }
         float* t = c.arena.alloc<float>((size_t)B * To * co);
         for (int u = 0; u < 2; ++u) {
-            QA_TRY(conv_same(c, y, B, To, blk.u1[u], t, ACT_ELU, ACT_ELU));       // ELU(conv1(ELU(y)))
-            QA_TRY(conv_same(c, t, B, To, blk.u2[u], y, ACT_NONE, ACT_NONE, y));  // y + conv2(.)
+            QA_TRY(conv_same(c, y, to, blk.u1[u], t, elu_conv_elu()));      // ELU(conv1(ELU(y)))
+            QA_TRY(conv_same(c, t, to, blk.u2[u], y, epi(ACT_NONE, y)));  // y + conv2(.)
         }
         x = y;
         L = To;
@@ -846,7 +858,7 @@ int semantic_decoder_op(const qa_hcodec::SemDec& sd, Ctx& c, const float* z, int
     }
     const int O = sp.output_channels;
     float* o = c.arena.alloc<float>((size_t)B * L * O);
-    QA_TRY(conv_same(c, x, B, L, sd.conv2, o));
+    QA_TRY(conv_same(c, x, TimeAxis{B, L, false, ClipLens()}, sd.conv2, o));
     c.tap("sem_dec.out", o, (int64_t)B * L * O);
     // [B, L, O] read as a [B, C' = L, T' = O] tensor with strides (L O, O, 1): its channel-last form is [B, O, L]
     return to_channel_last_op(c, o, (long long)L * O, O, 1, pred, B, L, O);
@@ -862,33 +874,34 @@ int semantic_decoder_from_codes(qa_hcodec* h, Ctx& c, const long long* is_rows, 
     return semantic_decoder_op(*h->sdec, c, z, sp.code_dim, B, N, pred);
 }
 
-int forward_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc, int64_t fst,
-                  int n_feat, int N, float* recon, float* pred) {
-    const int Q = h->spec.num_quantizers;
+// tw: the waveform's axis; N = tw.T / h->geom.samples code frames
+int forward_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, const FeatView& f, int N, float* recon, float* pred) {
+    const int Q = h->spec.num_quantizers, B = tw.B;
+    const TimeAxis tc = tw.at(N, 1);
     long long* ac = c.arena.alloc<long long>((size_t)B * Q * N);
     long long* sc = c.arena.alloc<long long>((size_t)B * Q * N);
-    QA_TRY(encode_graph(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc));
+    QA_TRY(encode_graph(h, c, wav, tw, f, ac, sc));
     // the decoder's own path from the codes (decode_graph), so recon is decode(encode()) bit for bit
     long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
     QA_RUN(c, launch_codes_from_bqn(sc, is, B, N, Q, c.stream));
-    QA_TRY(decode_graph(h, c, ac, sc, B, N, recon));
+    QA_TRY(decode_graph(h, c, ac, sc, tc, recon));
     return semantic_decoder_from_codes(h, c, is, B, N, pred);
 }
 
-int forward_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, int B, int T, const float* feat, int64_t fsb, int64_t fsc,
-                           int64_t fst, int n_feat, int N, float* recon, float* pred, long long* token_lengths, int* G_out) {
+int forward_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, const FeatView& f, int N, float* recon, float* pred,
+                           long long* token_lengths, int* G_out) {
     const qa_hcodec_spec& sp = h->spec;
-    const int Q = sp.num_quantizers, K = sp.codebook_size;
+    const int Q = sp.num_quantizers, K = sp.codebook_size, B = tw.B;
     long long* ac = c.arena.alloc<long long>((size_t)B * Q * N);
     long long* sc = c.arena.alloc<long long>((size_t)B * Q * N);
     int G = 0;
-    QA_TRY(encode_adaptive_graph(h, c, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc, &G, sp.threshold));
+    QA_TRY(encode_adaptive_graph(h, c, wav, tw, f, ac, sc, &G, sp.threshold));
     *G_out = G;
     // every item's groups cover all N frames (x_lens = T for the whole batch, codec_adaptive.py:106-107): decode at N frames
     long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
     QA_RUN(c, launch_token_lengths(sc, token_lengths, B, Q, G, K, c.stream));
     QA_RUN(c, launch_deaggregate(sc, sc, is, B, Q, G, N, K, c.stream));  // codec_adaptive.py:134-135
-    QA_TRY(decode_adaptive_graph(h, c, ac, sc, B, G, N, recon));
+    QA_TRY(decode_adaptive_graph(h, c, ac, sc, tw.at(N, 1), G, recon));
     return semantic_decoder_from_codes(h, c, is, B, N, pred);
 }
 
@@ -976,6 +989,14 @@ int build(qa_hcodec* h, const HostTable& tab) {
                "spec: channel counts must be multiples of 32");
     QA_REQUIRE(sp.n_fft % 2 == 0 && sp.hop > 0 && sp.n_fft > sp.hop && (sp.n_fft - sp.hop) % 2 == 0, "spec: bad STFT geometry");
     QA_REQUIRE(sp.dec_dim % sp.gn_groups == 0, "spec: dec_dim %% gn_groups != 0");
+    qa_hcodec::Geom& geom = h->geom;
+    geom.sem.assign(sp.n_sem_strides + 1, 1);
+    for (int i = sp.n_sem_strides - 1; i >= 0; --i) geom.sem[i] = geom.sem[i + 1] * sp.sem_strides[i];
+    geom.feat = geom.sem[0];
+    geom.dec = v20 ? sp.frame_stride : 2;
+    if (!v20) geom.enc.assign(sp.n_ratios + 1, 2);
+    for (int i = sp.n_ratios - 1; i >= 0 && !v20; --i) geom.enc[i] = geom.enc[i + 1] * sp.ratios[i];
+    geom.samples = v20 ? sp.hop * sp.frame_stride : geom.enc[0];
     Loader b(tab, h->store);
     auto dw_fold_c = [&](const float** dst, const std::string& name, int k, int ch) {
         std::vector<float> w((size_t)k * ch, 0.f);
@@ -988,15 +1009,10 @@ int build(qa_hcodec* h, const HostTable& tab) {
     auto fold_convnext = [&](ConvNeXtW& w, const std::string& cp, int ch, int inter) {
         dw_fold_c(&w.dw, cp + ".dwconv.conv.weight", 7, ch);
         b.vec(&w.dwb, cp + ".dwconv.conv.bias", ch);
-        b.vec(&w.lnw, cp + ".norm.weight", ch);
-        b.vec(&w.lnb, cp + ".norm.bias", ch);
+        b.norm(&w.lnw, &w.lnb, cp + ".norm", ch);
         b.vec(&w.gamma, cp + ".gamma", ch);
-        w.pw1.N = inter; w.pw1.C_in = ch; w.pw1.ksize = 1;
-        b.vec(&w.pw1.w, cp + ".pwconv1.linear.weight", (int64_t)inter * ch);
-        b.vec(&w.pw1.b, cp + ".pwconv1.linear.bias", inter);
-        w.pw2.N = ch; w.pw2.C_in = inter; w.pw2.ksize = 1;
-        b.vec(&w.pw2.w, cp + ".pwconv2.linear.weight", (int64_t)inter * ch);
-        b.vec(&w.pw2.b, cp + ".pwconv2.linear.bias", ch);
+        b.linear(&w.pw1, cp + ".pwconv1.linear.weight", cp + ".pwconv1.linear.bias", inter, ch);
+        b.linear(&w.pw2, cp + ".pwconv2.linear.weight", cp + ".pwconv2.linear.bias", ch, inter);
     };
     if (v20) {
         // --- H-Codec 2.0 encoder (HCodec-2.0/vq/codec_encoder.py:12-79)
@@ -1019,43 +1035,41 @@ int build(qa_hcodec* h, const HostTable& tab) {
         }
         h->stft_ld = pad32(2 * nbins);
         b.conv(&h->enc_embed, "encoder.embed.conv", de, 2 * nbins, 3, true, 1.f, de, h->stft_ld);
-        b.vec(&h->enc_norm_w, "encoder.norm.weight", de);
-        b.vec(&h->enc_norm_b, "encoder.norm.bias", de);
+        b.norm(&h->enc_norm_w, &h->enc_norm_b, "encoder.norm", de);
         h->enc_cnx.resize(sp.enc_convnext_layers);
         for (int i = 0; i < sp.enc_convnext_layers; ++i) fold_convnext(h->enc_cnx[i], "encoder.prior_net." + std::to_string(i), de, sp.enc_inter);
         build_transformer(b, &h->enc_tr, "encoder.post_net.1", de, sp.enc_layers, de / 64, tr_inter(de));
-        b.vec(&h->enc_fnorm_w, "encoder.final_layer_norm.weight", de);
-        b.vec(&h->enc_fnorm_b, "encoder.final_layer_norm.bias", de);
+        b.norm(&h->enc_fnorm_w, &h->enc_fnorm_b, "encoder.final_layer_norm", de);
         b.conv(&h->enc_out20, "encoder.out.conv", sp.code_dim, de, 2 * sp.frame_stride + 1);
     } else {
-    // --- SEANet encoder (seanet.py:121-187)
-    const std::string em = "encoder.model.";
-    b.wn = WN_FOLD;  // every SEANet convolution is weight-normed (seanet.py)
-    {   // conv0 (C_in = 1) as [7][n_filters] for launch_conv_in / launch_seanet_front
-        std::vector<float> w, w0((size_t)7 * sp.n_filters, 0.f);
-        if (b.weight(em + "0.conv.conv", sp.n_filters, 7, &w))
-            for (int n = 0; n < sp.n_filters; ++n)
-                for (int j = 0; j < 7; ++j) w0[(size_t)j * sp.n_filters + n] = w[n * 7 + j];
-        b.raw(&h->conv0_w, w0);
-        b.vec(&h->conv0_b, em + "0.conv.conv.bias", sp.n_filters);
-    }
-    h->res.resize(sp.n_ratios);
-    h->down.resize(sp.n_ratios);
-    int C = sp.n_filters;
-    for (int i = 0; i < sp.n_ratios; ++i) {
-        const std::string rp = em + std::to_string(1 + 3 * i);
-        const int hid = C / 2, hp = pad32(hid);
-        b.conv(&h->res[i].k3, rp + ".block.1.conv.conv", hid, C, 3, true, 1.f, hp, C);
-        b.conv(&h->res[i].pw, rp + ".block.3.conv.conv", C, hid, 1, true, 1.f, C, hp);
-        b.conv(&h->res[i].sc, rp + ".shortcut.conv.conv", C, C, 1);
-        b.conv(&h->down[i], em + std::to_string(3 + 3 * i) + ".conv.conv", 2 * C, C, 2 * sp.ratios[i]);
-        C *= 2;
-    }
-    QA_REQUIRE(C == sp.dimension, "spec: n_filters * 2^n_ratios = %d != dimension %d", C, sp.dimension);
-    build_transformer(b, &h->enc_tr, em + std::to_string(3 * sp.n_ratios + 2), sp.dimension, sp.enc_layers, sp.enc_heads);
-    b.conv(&h->enc_out, em + std::to_string(3 * sp.n_ratios + 5) + ".conv.conv", sp.dimension, sp.dimension, 4);
-    b.wn = WN_NONE;
-    QA_REQUIRE(sp.code_dim == sp.dimension, "spec: code_dim must equal dimension");
+        // --- SEANet encoder (seanet.py:121-187)
+        const std::string em = "encoder.model.";
+        b.wn = WN_FOLD;  // every SEANet convolution is weight-normed (seanet.py)
+        {   // conv0 (C_in = 1) as [7][n_filters] for launch_conv_in / launch_seanet_front
+            std::vector<float> w, w0((size_t)7 * sp.n_filters, 0.f);
+            if (b.weight(em + "0.conv.conv", sp.n_filters, 7, &w))
+                for (int n = 0; n < sp.n_filters; ++n)
+                    for (int j = 0; j < 7; ++j) w0[(size_t)j * sp.n_filters + n] = w[n * 7 + j];
+            b.raw(&h->conv0_w, w0);
+            b.vec(&h->conv0_b, em + "0.conv.conv.bias", sp.n_filters);
+        }
+        h->res.resize(sp.n_ratios);
+        h->down.resize(sp.n_ratios);
+        int C = sp.n_filters;
+        for (int i = 0; i < sp.n_ratios; ++i) {
+            const std::string rp = em + std::to_string(1 + 3 * i);
+            const int hid = C / 2, hp = pad32(hid);
+            b.conv(&h->res[i].k3, rp + ".block.1.conv.conv", hid, C, 3, true, 1.f, hp, C);
+            b.conv(&h->res[i].pw, rp + ".block.3.conv.conv", C, hid, 1, true, 1.f, C, hp);
+            b.conv(&h->res[i].sc, rp + ".shortcut.conv.conv", C, C, 1);
+            b.conv(&h->down[i], em + std::to_string(3 + 3 * i) + ".conv.conv", 2 * C, C, 2 * sp.ratios[i]);
+            C *= 2;
+        }
+        QA_REQUIRE(C == sp.dimension, "spec: n_filters * 2^n_ratios = %d != dimension %d", C, sp.dimension);
+        build_transformer(b, &h->enc_tr, em + std::to_string(3 * sp.n_ratios + 2), sp.dimension, sp.enc_layers, sp.enc_heads);
+        b.conv(&h->enc_out, em + std::to_string(3 * sp.n_ratios + 5) + ".conv.conv", sp.dimension, sp.dimension, 4);
+        b.wn = WN_NONE;
+        QA_REQUIRE(sp.code_dim == sp.dimension, "spec: code_dim must equal dimension");
     }
     // --- semantic encoder (semantic_module.py:157-201)
     const std::string se = "semantic_encoder.";
@@ -1097,26 +1111,19 @@ int build(qa_hcodec* h, const HostTable& tab) {
     const int ridx[4] = {0, 1, 5, 6};
     for (int i = 0; i < 4; ++i) {
         const std::string rp = "decoder.prior_net." + std::to_string(ridx[i]);
-        b.vec(&h->dres[i].n1w, rp + ".norm1.weight", d);
-        b.vec(&h->dres[i].n1b, rp + ".norm1.bias", d);
-        b.vec(&h->dres[i].n2w, rp + ".norm2.weight", d);
-        b.vec(&h->dres[i].n2b, rp + ".norm2.bias", d);
+        b.norm(&h->dres[i].n1w, &h->dres[i].n1b, rp + ".norm1", d);
+        b.norm(&h->dres[i].n2w, &h->dres[i].n2b, rp + ".norm2", d);
         b.conv(&h->dres[i].c1, rp + ".conv1.conv", d, d, 3);
         b.conv(&h->dres[i].c2, rp + ".conv2.conv", d, d, 3);
     }
     build_transformer(b, &h->dec_tr, "decoder.prior_net.3", d, sp.dec_layers, sp.dec_heads, tr_inter(d));
-    b.vec(&h->gn_w, "decoder.prior_net.7.weight", d);
-    b.vec(&h->gn_b, "decoder.prior_net.7.bias", d);
-    b.vec(&h->norm_w, "decoder.norm.weight", d);
-    b.vec(&h->norm_b, "decoder.norm.bias", d);
-    b.vec(&h->fnorm_w, "decoder.final_layer_norm.weight", d);
-    b.vec(&h->fnorm_b, "decoder.final_layer_norm.bias", d);
+    b.norm(&h->gn_w, &h->gn_b, "decoder.prior_net.7", d);
+    b.norm(&h->norm_w, &h->norm_b, "decoder.norm", d);
+    b.norm(&h->fnorm_w, &h->fnorm_b, "decoder.final_layer_norm", d);
     h->cnx.resize(sp.convnext_layers);
     for (int i = 0; i < sp.convnext_layers; ++i) fold_convnext(h->cnx[i], "decoder.post_net." + std::to_string(i), d, sp.dec_inter);
     const int nb = sp.n_fft / 2 + 1;
-    h->head.N = 2 * nb; h->head.C_in = d; h->head.ksize = 1;
-    b.vec(&h->head.w, "decoder.head.out.weight", (int64_t)2 * nb * d);
-    b.vec(&h->head.b, "decoder.head.out.bias", 2 * nb);
+    b.linear(&h->head, "decoder.head.out.weight", "decoder.head.out.bias", 2 * nb, d);
     // inverse real DFT (norm="backward") with the synthesis window folded in (spectral_ops.py:55-56):
     //   frame[n] = w[n]/N * sum_k c_k (Re_k cos(2 pi k n / N) - Im_k sin(2 pi k n / N)),  c_0 = c_{N/2} = 1, else 2
     {
@@ -1214,10 +1221,7 @@ static int run(qa_hcodec* h, void* stream, F&& graph) {
 extern "C" {
 
 int qa_hcodec_create(qa_hcodec** out, const qa_hcodec_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
-    if (!out || !spec || !tensors) {
-        set_error("qa_hcodec_create: null argument");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(out && spec && tensors, "qa_hcodec_create: null argument");
     *out = nullptr;
     QA_HIP(hipSetDevice(device));
     std::unique_ptr<qa_hcodec> h(new qa_hcodec());
@@ -1230,37 +1234,35 @@ int qa_hcodec_create(qa_hcodec** out, const qa_hcodec_spec* spec, const qa_tenso
 
 void qa_hcodec_destroy(qa_hcodec* h) { destroy_handle(h); }
 
-int qa_hcodec_encode(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
-                     int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, void* stream) {
-    if (!h || !wav || !feat || !ac || !sc) {
-        set_error("qa_hcodec_encode: null argument");
-        return QA_ERR_INVALID;
-    }
-    int hop = 2;
-    for (int i = 0; i < h->spec.n_ratios; ++i) hop *= h->spec.ratios[i];
-    if (h->spec.version == 20) hop = h->spec.hop * h->spec.frame_stride;
-    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "qa_hcodec_encode: wav is [%lld, %lld]; T must be a positive multiple of %d "
-               "(HCodecTokenizer.pad_wav)", (long long)B, (long long)T, hop);
-    QA_REQUIRE(B * T < (1LL << 31), "qa_hcodec_encode: batch of %lld x %lld samples is too large", (long long)B, (long long)T);
-    QA_REQUIRE(!h->spec.adaptive, "qa_hcodec_encode: this handle is an H-Codec 1.5 model, use qa_hcodec_encode_adaptive");
-    return run(h, stream, [&] { return encode_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc); });
+// ---- what the entry points share, all of it before anything is launched.  `fn` is the entry point the caller called; every message
+// names it and the offending values.
+
+// The front of every entry point that takes a waveform [B, T]: a whole number of code frames, few enough samples for 32-bit row indices.
+// Returns the code-frame count, or the (negative) status.
+static int64_t wav_code_frames(const qa_hcodec* h, const char* fn, int64_t B, int64_t T) {
+    const int hop = h->geom.samples;
+    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "%s: wav is [%lld, %lld]; T must be a positive multiple of %d (HCodecTokenizer.pad_wav)", fn,
+               (long long)B, (long long)T, hop);
+    QA_REQUIRE(B * T < (1LL << 31), "%s: batch of %lld x %lld samples is too large", fn, (long long)B, (long long)T);
+    return T / hop;
 }
 
-int qa_hcodec_decode(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t N, float* wav_out, void* stream) {
-    if (!h || !ac || !sc || !wav_out) {
-        set_error("qa_hcodec_decode: null argument");
-        return QA_ERR_INVALID;
-    }
-    QA_REQUIRE(B > 0 && N > 0, "qa_hcodec_decode: codes are [%lld, Q, %lld]", (long long)B, (long long)N);
-    QA_REQUIRE(B * N * (h->spec.version == 20 ? h->spec.frame_stride : 2) * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode: output too large");
-    QA_REQUIRE(!h->spec.adaptive, "qa_hcodec_decode: this handle is an H-Codec 1.5 model, use qa_hcodec_decode_adaptive");
-    return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out); });
+// the plain entry points serve H-Codec 1.0 / 2.0, their _adaptive twins H-Codec 1.5
+static int family_check(const qa_hcodec* h, const char* fn, bool adaptive) {
+    QA_REQUIRE(!adaptive || h->spec.adaptive, "%s: this handle is not an H-Codec 1.5 model", fn);
+    QA_REQUIRE(adaptive || !h->spec.adaptive, "%s: this handle is an H-Codec 1.5 model, use %s_adaptive", fn, fn);
+    return QA_OK;
 }
 
-// Shared front of the two ragged entry points, all of it before anything is launched.  ragged_refuse: the models that have no per-clip
-// lengths.  ragged_lengths: the lengths themselves (HOST memory, code frames, 1 .. N each; the error names the row).  *ragged = false when
-// every clip has N frames: the caller then takes the rectangular path as it is.  Otherwise the lengths are on their way to h->lens_dev,
-// in stream order in front of the call's kernels.
+// the axis of B clips of T frames at `rate` frames per code frame; lens: the clips' code-frame counts (device) of a ragged call, or null
+static TimeAxis clip_axis(const qa_hcodec* h, int64_t B, int64_t T, int rate, const int* lens) {
+    return TimeAxis{(int)B, (int)T, h->spec.causal != 0, ClipLens{lens, lens ? rate : 0}};
+}
+
+// ragged_refuse: the models that have no per-clip lengths.  ragged_lengths: the lengths themselves (HOST memory, code frames, 1 .. N each;
+// the error names the row).  *lens = nullptr when every clip has N frames: the call is then the rectangular one as it is - fused stage 0,
+// no key mask, nothing uploaded.  Otherwise *lens = h->lens_dev, the lengths on their way to it in stream order in front of the call's
+// kernels.
 static int ragged_refuse(qa_hcodec* h, const char* fn) {
     const qa_hcodec_spec& sp = h->spec;
     const char* why = sp.adaptive ? "an H-Codec 1.5 model (spec.adaptive): its alignment and aggregators need per-row sequence lengths of their own"
@@ -1273,7 +1275,7 @@ static int ragged_refuse(qa_hcodec* h, const char* fn) {
     }
     return QA_OK;
 }
-static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, const int64_t* frames, void* stream, bool* ragged) {
+static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, const int64_t* frames, void* stream, const int** lens) {
     QA_REQUIRE(B > 0 && N > 0 && B < (1 << 20), "%s: %lld clips of %lld code frames", fn, (long long)B, (long long)N);
     std::vector<int> len((size_t)B);
     bool full = true;
@@ -1283,7 +1285,7 @@ static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, co
         len[(size_t)b] = (int)frames[b];
         full = full && frames[b] == N;
     }
-    *ragged = !full;
+    *lens = nullptr;
     if (full) return QA_OK;
     QA_HIP(hipSetDevice(h->device));
     if (B > h->lens_cap) {
@@ -1294,77 +1296,84 @@ static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, co
         QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->lens_dev), sizeof(int) * (size_t)cap));
         h->lens_cap = cap;
     }
-    return launch_row_lens(h->lens_dev, len.data(), (int)B, static_cast<hipStream_t>(stream));
+    QA_TRY(launch_row_lens(h->lens_dev, len.data(), (int)B, static_cast<hipStream_t>(stream)));
+    *lens = h->lens_dev;
+    return QA_OK;
+}
+
+// qa_hcodec_encode (frames == nullptr) and qa_hcodec_encode_ragged
+static int encode_call(qa_hcodec* h, const char* fn, const float* wav, int64_t B, int64_t T, const int64_t* frames, const FeatView& f,
+                       int64_t* ac, int64_t* sc, void* stream) {
+    if (frames) QA_TRY(ragged_refuse(h, fn));
+    const int64_t N = wav_code_frames(h, fn, B, T);
+    if (N < 0) return (int)N;
+    QA_TRY(family_check(h, fn, false));
+    const int* lens = nullptr;
+    if (frames) {
+        QA_REQUIRE(f.n == N * h->geom.feat, "%s: feat has %lld frames, %lld code frames need %lld", fn, (long long)f.n, (long long)N,
+                   (long long)(N * h->geom.feat));
+        QA_TRY(ragged_lengths(h, fn, B, N, frames, stream, &lens));
+    }
+    const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, lens);
+    return run(h, stream, [&] { return encode_graph(h, h->ctx, wav, tw, f, (long long*)ac, (long long*)sc); });
+}
+
+// qa_hcodec_decode (frames == nullptr) and qa_hcodec_decode_ragged
+static int decode_call(qa_hcodec* h, const char* fn, const int64_t* ac, const int64_t* sc, int64_t B, int64_t N, const int64_t* frames,
+                       float* wav_out, void* stream) {
+    if (frames) QA_TRY(ragged_refuse(h, fn));
+    QA_REQUIRE(B > 0 && N > 0, "%s: codes are [%lld, Q, %lld]", fn, (long long)B, (long long)N);
+    QA_REQUIRE(B * N * h->geom.dec * (int64_t)h->spec.hop < (1LL << 31), "%s: output too large for codes [%lld, Q, %lld]", fn, (long long)B,
+               (long long)N);
+    QA_TRY(family_check(h, fn, false));
+    const int* lens = nullptr;
+    if (frames) QA_TRY(ragged_lengths(h, fn, B, N, frames, stream, &lens));
+    const TimeAxis tc = clip_axis(h, B, N, 1, lens);
+    return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, tc, wav_out); });
+}
+
+int qa_hcodec_encode(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
+                     int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, void* stream) {
+    QA_REQUIRE(h && wav && feat && ac && sc, "qa_hcodec_encode: null argument");
+    return encode_call(h, "qa_hcodec_encode", wav, B, T, nullptr, FeatView{feat, fsb, fsc, fst, (int)n_feat}, ac, sc, stream);
 }
 
 int qa_hcodec_encode_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const int64_t* frames, const float* feat, int64_t fsb,
                             int64_t fsc, int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, void* stream) {
-    if (!h || !wav || !frames || !feat || !ac || !sc) {
-        set_error("qa_hcodec_encode_ragged: null argument");
-        return QA_ERR_INVALID;
-    }
-    int hop = 2, fpc = 1;
-    for (int i = 0; i < h->spec.n_ratios; ++i) hop *= h->spec.ratios[i];
-    for (int i = 0; i < h->spec.n_sem_strides; ++i) fpc *= h->spec.sem_strides[i];
-    QA_TRY(ragged_refuse(h, "qa_hcodec_encode_ragged"));
-    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "qa_hcodec_encode_ragged: wav is [%lld, %lld]; T must be a positive multiple of %d",
-               (long long)B, (long long)T, hop);
-    const int64_t N = T / hop;
-    QA_REQUIRE(B * T < (1LL << 31), "qa_hcodec_encode_ragged: batch of %lld x %lld samples is too large", (long long)B, (long long)T);
-    QA_REQUIRE(n_feat == N * fpc, "qa_hcodec_encode_ragged: feat has %lld frames, %lld code frames need %lld", (long long)n_feat, (long long)N,
-               (long long)(N * fpc));
-    bool ragged = false;
-    QA_TRY(ragged_lengths(h, "qa_hcodec_encode_ragged", B, N, frames, stream, &ragged));
-    if (!ragged) return qa_hcodec_encode(h, wav, B, T, feat, fsb, fsc, fst, n_feat, ac, sc, stream);
-    const ClipLens rl{h->lens_dev, 1};
-    return run(h, stream, [&] {
-        return encode_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc, rl);
-    });
+    QA_REQUIRE(h && wav && frames && feat && ac && sc, "qa_hcodec_encode_ragged: null argument");
+    return encode_call(h, "qa_hcodec_encode_ragged", wav, B, T, frames, FeatView{feat, fsb, fsc, fst, (int)n_feat}, ac, sc, stream);
+}
+
+int qa_hcodec_decode(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t N, float* wav_out, void* stream) {
+    QA_REQUIRE(h && ac && sc && wav_out, "qa_hcodec_decode: null argument");
+    return decode_call(h, "qa_hcodec_decode", ac, sc, B, N, nullptr, wav_out, stream);
 }
 
 int qa_hcodec_decode_ragged(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t N, const int64_t* frames, float* wav_out,
                             void* stream) {
-    if (!h || !ac || !sc || !frames || !wav_out) {
-        set_error("qa_hcodec_decode_ragged: null argument");
-        return QA_ERR_INVALID;
-    }
-    QA_TRY(ragged_refuse(h, "qa_hcodec_decode_ragged"));
-    QA_REQUIRE(B > 0 && N > 0 && B * N * 2 * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode_ragged: codes are [%lld, Q, %lld]",
-               (long long)B, (long long)N);
-    bool ragged = false;
-    QA_TRY(ragged_lengths(h, "qa_hcodec_decode_ragged", B, N, frames, stream, &ragged));
-    if (!ragged) return qa_hcodec_decode(h, ac, sc, B, N, wav_out, stream);
-    const ClipLens rl{h->lens_dev, 1};
-    return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)N, wav_out, rl); });
+    QA_REQUIRE(h && ac && sc && frames && wav_out, "qa_hcodec_decode_ragged: null argument");
+    return decode_call(h, "qa_hcodec_decode_ragged", ac, sc, B, N, frames, wav_out, stream);
 }
 
 int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
                               int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, int64_t* n_groups, float threshold, void* stream) {
-    if (!h || !wav || !feat || !ac || !sc || !n_groups) {
-        set_error("qa_hcodec_encode_adaptive: null argument");
-        return QA_ERR_INVALID;
-    }
-    QA_REQUIRE(h->spec.adaptive, "qa_hcodec_encode_adaptive: this handle is not an H-Codec 1.5 model");
-    int hop = 2;
-    for (int i = 0; i < h->spec.n_ratios; ++i) hop *= h->spec.ratios[i];
-    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "qa_hcodec_encode_adaptive: wav is [%lld, %lld]; T must be a positive multiple of %d",
-               (long long)B, (long long)T, hop);
-    QA_REQUIRE(B * T < (1LL << 31), "qa_hcodec_encode_adaptive: batch too large");
-    QA_REQUIRE(threshold >= 0.f && threshold <= 1.f, "qa_hcodec_encode_adaptive: threshold %g outside [0, 1] (codec_adaptive.py:151)", threshold);
+    const char* fn = "qa_hcodec_encode_adaptive";
+    QA_REQUIRE(h && wav && feat && ac && sc && n_groups, "%s: null argument", fn);
+    QA_TRY(family_check(h, fn, true));
+    const int64_t N = wav_code_frames(h, fn, B, T);
+    if (N < 0) return (int)N;
+    QA_REQUIRE(threshold >= 0.f && threshold <= 1.f, "%s: threshold %g outside [0, 1] (codec_adaptive.py:151)", fn, threshold);
     const float thr = threshold <= 0.f ? h->spec.threshold : threshold;  // codec_adaptive.py:158
+    const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, nullptr);
+    const FeatView f{feat, fsb, fsc, fst, (int)n_feat};
     int G = 0;
-    QA_TRY(run(h, stream, [&] {
-        return encode_adaptive_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, (long long*)ac, (long long*)sc, &G, thr);
-    }));
+    QA_TRY(run(h, stream, [&] { return encode_adaptive_graph(h, h->ctx, wav, tw, f, (long long*)ac, (long long*)sc, &G, thr); }));
     *n_groups = G;
     return QA_OK;
 }
 
 int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* frames, void* stream) {
-    if (!h || !semantic_codes || !frames) {
-        set_error("qa_hcodec_adaptive_frames: null argument");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(h && semantic_codes && frames, "qa_hcodec_adaptive_frames: null argument");
     QA_REQUIRE(h->spec.adaptive && B > 0 && G > 0, "qa_hcodec_adaptive_frames: bad argument");
     QA_HIP(hipSetDevice(h->device));
     QA_TRY(h->ws.ensure((size_t)(B + 64) * sizeof(int)));
@@ -1382,20 +1391,16 @@ int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64
 
 int qa_hcodec_decode_adaptive(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t G, int64_t frames,
                               float* wav_out, void* stream) {
-    if (!h || !ac || !sc || !wav_out) {
-        set_error("qa_hcodec_decode_adaptive: null argument");
-        return QA_ERR_INVALID;
-    }
-    QA_REQUIRE(h->spec.adaptive, "qa_hcodec_decode_adaptive: this handle is not an H-Codec 1.5 model");
-    QA_REQUIRE(B > 0 && G > 0 && frames > 0 && B * frames * 2 * (int64_t)h->spec.hop < (1LL << 31), "qa_hcodec_decode_adaptive: bad shape");
-    return run(h, stream, [&] { return decode_adaptive_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, (int)B, (int)G, (int)frames, wav_out); });
+    QA_REQUIRE(h && ac && sc && wav_out, "qa_hcodec_decode_adaptive: null argument");
+    QA_TRY(family_check(h, "qa_hcodec_decode_adaptive", true));
+    QA_REQUIRE(B > 0 && G > 0 && frames > 0 && B * frames * h->geom.dec * (int64_t)h->spec.hop < (1LL << 31),
+               "qa_hcodec_decode_adaptive: bad shape: %lld clips, %lld groups, %lld frames", (long long)B, (long long)G, (long long)frames);
+    const TimeAxis tc = clip_axis(h, B, frames, 1, nullptr);
+    return run(h, stream, [&] { return decode_adaptive_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, tc, (int)G, wav_out); });
 }
 
 int qa_hcodec_load_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec* spec, const qa_tensor* tensors, int64_t n_tensors) {
-    if (!h || !spec || !tensors) {
-        set_error("qa_hcodec_load_semantic_decoder: null argument");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(h && spec && tensors, "qa_hcodec_load_semantic_decoder: null argument");
     QA_HIP(hipSetDevice(h->device));
     HostTable tab(tensors, n_tensors);
     std::unique_ptr<qa_hcodec::SemDec> sd;
@@ -1413,27 +1418,20 @@ int qa_hcodec_has_semantic_decoder(const qa_hcodec* h) {
     return h->sdec ? 1 : 0;
 }
 
-// shared argument checks of the two forward entry points; returns N25 through *n25
+// the front of the two forward entry points: forward's own checks (the semantic decoder is attached, pred_feat is small enough for 32-bit
+// row indices) around the shared ones; the code-frame count through *n25
 static int forward_checks(qa_hcodec* h, const char* fn, const float* wav, int64_t B, int64_t T, const float* feat, const float* recon,
                           const float* pred, bool adaptive, int* n25) {
-    if (!h || !wav || !feat || !recon || !pred) {
-        set_error("%s: null argument", fn);
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(h && wav && feat && recon && pred, "%s: null argument", fn);
     QA_REQUIRE(h->sdec, "%s: no semantic decoder is attached (qa_hcodec_load_semantic_decoder: the checkpoint's semantic_decoder.* "
                "weights)", fn);
-    QA_REQUIRE(!adaptive || h->spec.adaptive, "%s: this handle is not an H-Codec 1.5 model", fn);
-    QA_REQUIRE(adaptive || !h->spec.adaptive, "%s: this handle is an H-Codec 1.5 model, use qa_hcodec_forward_adaptive", fn);
-    int hop = 2;
-    for (int i = 0; i < h->spec.n_ratios; ++i) hop *= h->spec.ratios[i];
-    if (h->spec.version == 20) hop = h->spec.hop * h->spec.frame_stride;
-    QA_REQUIRE(B > 0 && T > 0 && T % hop == 0, "%s: wav is [%lld, %lld]; T must be a positive multiple of %d (HCodecTokenizer.pad_wav)",
-               fn, (long long)B, (long long)T, hop);
-    QA_REQUIRE(B * T < (1LL << 31), "%s: batch of %lld x %lld samples is too large", fn, (long long)B, (long long)T);
+    QA_TRY(family_check(h, fn, adaptive));
+    const int64_t N = wav_code_frames(h, fn, B, T);
+    if (N < 0) return (int)N;
     int64_t up = 1;
     for (int i = 0; i < h->sdec->spec.n_blocks; ++i) up *= h->sdec->spec.strides[i];
-    QA_REQUIRE(B * (T / hop) * up * std::max(h->sdec->spec.output_channels, h->sdec->spec.widths[0]) < (1LL << 31), "%s: pred_feat too large", fn);
-    *n25 = (int)(T / hop);
+    QA_REQUIRE(B * N * up * std::max(h->sdec->spec.output_channels, h->sdec->spec.widths[0]) < (1LL << 31), "%s: pred_feat too large", fn);
+    *n25 = (int)N;
     return QA_OK;
 }
 
@@ -1441,7 +1439,9 @@ int qa_hcodec_forward(qa_hcodec* h, const float* wav, int64_t B, int64_t T, cons
                       int64_t n_feat, float* recon, float* pred_feat, void* stream) {
     int N = 0;
     QA_TRY(forward_checks(h, "qa_hcodec_forward", wav, B, T, feat, recon, pred_feat, false, &N));
-    return run(h, stream, [&] { return forward_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat); });
+    const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, nullptr);
+    const FeatView f{feat, fsb, fsc, fst, (int)n_feat};
+    return run(h, stream, [&] { return forward_graph(h, h->ctx, wav, tw, f, N, recon, pred_feat); });
 }
 
 int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
@@ -1450,11 +1450,10 @@ int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_
     int N = 0;
     QA_TRY(forward_checks(h, "qa_hcodec_forward_adaptive", wav, B, T, feat, recon, pred_feat, true, &N));
     QA_REQUIRE(token_lengths && n_groups, "qa_hcodec_forward_adaptive: null argument");
+    const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, nullptr);
+    const FeatView f{feat, fsb, fsc, fst, (int)n_feat};
     int G = 0;
-    QA_TRY(run(h, stream, [&] {
-        return forward_adaptive_graph(h, h->ctx, wav, (int)B, (int)T, feat, fsb, fsc, fst, (int)n_feat, N, recon, pred_feat,
-                                      (long long*)token_lengths, &G);
-    }));
+    QA_TRY(run(h, stream, [&] { return forward_adaptive_graph(h, h->ctx, wav, tw, f, N, recon, pred_feat, (long long*)token_lengths, &G); }));
     *n_groups = G;
     return QA_OK;
 }
@@ -1469,10 +1468,7 @@ int64_t qa_hcodec_tap(qa_hcodec* h, const char* name, float* dst, int64_t cap, v
 
 int qa_mimi_create(qa_mimi** out, const qa_mimi_spec* spec, const qa_tensor* tensors, int64_t n_tensors, const char* prefix,
                    int device) {
-    if (!out || !spec || !tensors || !prefix) {
-        set_error("qa_mimi_create: null argument");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(out && spec && tensors && prefix, "qa_mimi_create: null argument");
     *out = nullptr;
     const qa_mimi_spec& sp = *spec;
     QA_REQUIRE(sp.d_model > 0 && sp.num_heads > 0 && sp.d_model % sp.num_heads == 0 && sp.num_layers > 0 && sp.dim_feedforward > 0,
@@ -1510,10 +1506,7 @@ static int mimi_run(qa_mimi* m, const float* x, int B, int T, float* y, hipStrea
 }
 
 int qa_mimi_forward(qa_mimi* m, const float* x, int64_t B, int64_t T, float* y, void* stream) {
-    if (!m || !x || !y) {
-        set_error("qa_mimi_forward: null argument");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(m && x && y, "qa_mimi_forward: null argument");
     QA_REQUIRE(B > 0 && T > 0 && T <= MAX_POS && B * T < (1LL << 31), "qa_mimi_forward: x is [%lld, %lld, d] (T <= %d)", (long long)B,
                (long long)T, MAX_POS);
     QA_REQUIRE(m->st.B == 0, "qa_mimi_forward: the handle is in streaming mode, use qa_mimi_stream_step");
@@ -1521,10 +1514,7 @@ int qa_mimi_forward(qa_mimi* m, const float* x, int64_t B, int64_t T, float* y, 
 }
 
 int qa_mimi_stream_begin(qa_mimi* m, int64_t B) {
-    if (!m) {
-        set_error("qa_mimi_stream_begin: null handle");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(m, "qa_mimi_stream_begin: null handle");
     QA_REQUIRE(m->spec.causal, "qa_mimi_stream_begin: Streaming only available for causal (mimi/transformer.py:382)");
     QA_REQUIRE(m->spec.context > 0, "qa_mimi_stream_begin: Cannot create a streaming KVCache without a context to estimate capacity "
                "(mimi/transformer.py:349-353)");
@@ -1549,10 +1539,7 @@ int qa_mimi_stream_begin(qa_mimi* m, int64_t B) {
 }
 
 int qa_mimi_stream_step(qa_mimi* m, const float* x, int64_t T, float* y, void* stream) {
-    if (!m || !x || !y) {
-        set_error("qa_mimi_stream_step: null argument");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(m && x && y, "qa_mimi_stream_step: null argument");
     QA_REQUIRE(m->st.B > 0, "qa_mimi_stream_step: not streaming (call qa_mimi_stream_begin)");
     QA_REQUIRE(T >= 1 && T <= m->st.cap, "qa_mimi_stream_step: a chunk of %lld frames does not fit the ring of %d (RingKVCache.complete "
                "would write one slot twice)", (long long)T, m->st.cap);
@@ -1581,10 +1568,7 @@ int qa_mimi_stream_step(qa_mimi* m, const float* x, int64_t T, float* y, void* s
 }
 
 int qa_mimi_stream_reset(qa_mimi* m) {
-    if (!m) {
-        set_error("qa_mimi_stream_reset: null handle");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(m, "qa_mimi_stream_reset: null handle");
     QA_REQUIRE(m->st.B > 0, "qa_mimi_stream_reset: Trying to reset streaming, but the transformer wasn't streaming (streaming.py:118-121)");
     m->st.offset = 0;  // RingKVCache.reset(): the caches keep their contents, end_offset = 0 alone invalidates them
     m->st.rope_len = 0;
@@ -1592,10 +1576,7 @@ int qa_mimi_stream_reset(qa_mimi* m) {
 }
 
 int qa_mimi_stream_end(qa_mimi* m) {
-    if (!m) {
-        set_error("qa_mimi_stream_end: null handle");
-        return QA_ERR_INVALID;
-    }
+    QA_REQUIRE(m, "qa_mimi_stream_end: null handle");
     (void)hipSetDevice(m->device);
     if (m->ring) {
         (void)hipDeviceSynchronize();

@@ -208,6 +208,19 @@ class Loader {
         if (p) pend_.push_back({dst, store_.add(p, (size_t)n)});
     }
     void raw(const float** dst, const std::vector<float>& v) { pend_.push_back({dst, store_.add(v)}); }
+    // nn.Linear [N][C_in] as it is stored (never weight-normed: `wn` does not apply); bias_key empty: no bias
+    void linear(ConvW* dst, const std::string& weight_key, const std::string& bias_key, int N, int C_in) {
+        dst->N = N;
+        dst->C_in = C_in;
+        dst->ksize = 1;
+        vec(&dst->w, weight_key, (int64_t)N * C_in);
+        if (!bias_key.empty()) vec(&dst->b, bias_key, N);
+    }
+    // the `.weight` / `.bias` pair of a normalisation over d channels
+    void norm(const float** w, const float** b, const std::string& prefix, int d) {
+        vec(w, prefix + ".weight", d);
+        vec(b, prefix + ".bias", d);
+    }
     // the [d0][rest] weight of prefix p; weight norm over dim 0 is folded as torch._weight_norm does it: w = v * (g / ||v||_2), the
     // sum of squares in double, the scale in fp32
     bool weight(const std::string& p, int64_t d0, int64_t rest, std::vector<float>* out) {
@@ -283,9 +296,7 @@ struct ConvOpt {
     // fused interleaved-pair RoPE on the first rope_n output channels (ConvParams::rope)
     const float* rope = nullptr;
     int rope_n = 0, rope_hd = 0, rope_T = 0, rope_pos0 = 0;
-    // per-clip lengths of a ragged call (ConvParams::lens): clip b holds lens[b] * len_mul input frames
-    const int* lens = nullptr;
-    int len_mul = 0;
+    ClipLens rl;  // per-clip lengths of a ragged call (ConvParams::lens / len_mul): clip b holds rl.n[b] * rl.mul input frames
 };
 
 // geometry only
@@ -306,6 +317,17 @@ inline ConvOpt epi(int act, const float* res = nullptr, const float* gamma = nul
     o.gate = gate;
     return o;
 }
+
+// The time axis of a [B, T, C] activation in a model graph and what rides along with it: whether the model's convolutions are causal and,
+// in a ragged call, the clips' lengths at this stage's rate (clip b holds rl.n[b] * rl.mul of the T frames; rl.n null: all T).
+struct TimeAxis {
+    int B = 0, T = 0;
+    bool causal = false;
+    ClipLens rl;
+    int64_t rows() const { return (int64_t)B * T; }
+    // the same clips at another stage of the graph: T_new frames, `rate` frames per unit of rl.n
+    TimeAxis at(int T_new, int rate) const { return TimeAxis{B, T_new, causal, ClipLens{rl.n, rl.n ? rate : 0}}; }
+};
 
 // y [B, T_out, w.N] (row stride ldy) = conv(x [B, T_in, w.C_in] (row stride ldx), w) on the implicit GEMM; nothing in a dry pass
 inline int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const ConvW& w, float* y, int64_t ldy, int T_out,
@@ -335,7 +357,7 @@ inline int conv_op(Ctx& c, const float* x, int64_t ldx, int B, int T_in, const C
     p.rope = o.rope; p.rope_n = o.rope_n; p.rope_hd = o.rope_hd; p.rope_T = o.rope_T; p.rope_pos0 = o.rope_pos0;
     p.alpha = o.alpha; p.y2 = o.y2; p.alpha2 = o.alpha2; p.ldy2 = o.ldy2;
     p.math_fp32 = c.gemm_fp32 ? 1 : 0;
-    p.lens = o.lens; p.len_mul = o.len_mul; p.max_pad = std::max(o.pad_left, o.pad_right);
+    p.lens = o.rl.n; p.len_mul = o.rl.mul; p.max_pad = std::max(o.pad_left, o.pad_right);
     if (o.shift) {
         p.res = o.shift;
         p.ldr = 0;
@@ -372,13 +394,10 @@ inline int rope_op(Ctx& c, float* qkv, const float* cos_sin, int B, int N, int H
                    int rot_heads = 0) {
     return c.dry ? QA_OK : launch_rope(qkv, cos_sin, B, N, H, hd, ld, pos0, c.stream, interleaved, rot_heads);
 }
-inline int attention_op(Ctx& c, const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out, long long ldo,
-                        int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale, int causal,
-                        const float* gate = nullptr, const float* relbias = nullptr, int R = 0, int context = 0, int q_pos0 = 0,
-                        int ring_end = 0, const unsigned char* kvalid = nullptr) {
+inline int attention_op(Ctx& c, AttnArgs a) {
     if (c.dry) return QA_OK;
-    return launch_attention(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_batch_stride, H, hd, scale, causal, c.stream, gate, relbias, R,
-                            context, q_pos0, ring_end, kvalid, c.att_fp32);
+    a.math_fp32 = c.att_fp32;
+    return launch_attention(a, c.stream);
 }
 
 // ---------------------------------------------------------------- planning a call

@@ -4,6 +4,7 @@
 // the declaration its callers see; a model file declares none of its own.
 #pragma once
 #include <algorithm>
+#include <cmath>
 
 #include "common.h"
 
@@ -81,10 +82,31 @@ int launch_resample(const float* wav, const float* taps, float* out, int B, long
 //   kvalid [B, n_keys] bytes (optional, non-causal self-attention only): key j of item b is visible iff kvalid[b, j] != 0
 //   one kernel body in two arithmetic forms (attention_kernel<HD, BIAS, KMASK, SPLIT>): split-6 on the bf16 MFMA where QA_ATT_MATH = 1
 //   math_fp32: keep the fp32 form (SPLIT = false, v_mfma_f32_32x32x2_f32) whatever QA_ATT_MATH says (Ctx::att_fp32)
-int launch_attention(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
-                     long long ldo, int B, int n_q, int n_keys, long long kv_batch_stride, int H, int hd, float scale,
-                     int causal, hipStream_t s, const float* gate = nullptr, const float* relbias = nullptr, int R = 0,
-                     int context = 0, int q_pos0 = 0, int ring_end = 0, const unsigned char* kvalid = nullptr, bool math_fp32 = false);
+struct AttnArgs {
+    const float *q = nullptr, *k = nullptr, *v = nullptr;  // q [B, n_q, H hd]; k, v [B, n_keys, H hd], item stride kv_batch_stride
+    float* out = nullptr;                                  // [B, n_q, H hd]
+    long long ldq = 0, ldkv = 0, ldo = 0, kv_batch_stride = 0;  // row strides of q, of k and v, of out
+    int B = 0, n_q = 0, n_keys = 0, H = 0, hd = 0;
+    float scale = 0.f;
+    int causal = 0;
+    const float *gate = nullptr, *relbias = nullptr;
+    int R = 0;
+    int context = 0, q_pos0 = 0, ring_end = 0;  // causal window; ring mode (RingKVCache): position of query 0, end of the ring
+    const unsigned char* kvalid = nullptr;
+    bool math_fp32 = false;
+};
+int launch_attention(const AttnArgs& a, hipStream_t s);
+// self-attention over a packed projection qkv [B N, 3 d] (q | k | v, d = H hd) -> att [B N, d], scale 1 / sqrt(hd), non-causal; the
+// caller sets what differs (causal, context, kvalid, gate / relbias / R)
+inline AttnArgs attn_packed_qkv(const float* qkv, float* att, int B, int N, int H, int hd) {
+    const long long d = (long long)H * hd;
+    AttnArgs a;
+    a.q = qkv; a.ldq = 3 * d; a.out = att; a.ldo = d;
+    a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.kv_batch_stride = (long long)N * 3 * d;
+    a.B = B; a.n_q = N; a.n_keys = N; a.H = H; a.hd = hd;
+    a.scale = 1.0f / std::sqrt((float)hd);
+    return a;
+}
 // RingKVCache.complete() write (mimi/transformer.py:243-250): rows t = 0..T-1 of k / v (row stride ld, batch stride T * ld) go to
 // slot (pos0 + t) % cap of the caches [B, cap, d]
 int launch_ring_append(const float* k, const float* v, long long ld, float* kc, float* vc, int B, int T, int d, int cap, int pos0,

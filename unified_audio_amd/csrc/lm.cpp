@@ -327,7 +327,12 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
         QA_TRY(linear_op(c, b.hn, rows, L.qkv, b.qkv));
         QA_RUN(c, launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream));
         if (last) break;
-        QA_TRY(attention_op(c, b.qkv, 3 * d, kc, vc, d, b.att, d, B, n, pos0 + n, (long long)max_len * d, H, hd, scale, 1));
+        AttnArgs at;  // the n new queries over the layer's KV cache, causal
+        at.q = b.qkv; at.ldq = 3 * d; at.out = b.att; at.ldo = d;
+        at.k = kc; at.v = vc; at.ldkv = d; at.kv_batch_stride = (long long)max_len * d;
+        at.B = B; at.n_q = n; at.n_keys = pos0 + n; at.H = H; at.hd = hd;
+        at.scale = scale; at.causal = 1;
+        QA_TRY(attention_op(c, at));
         QA_TRY(linear_op(c, b.att, rows, L.o, b.x, epi(ACT_NONE, b.x)));
         QA_TRY(rmsnorm_op(c, b.x, lm->ones, b.hn, rows, d, sp.rms_eps));
         QA_TRY(linear_op(c, b.hn, rows, L.gate, b.g));

@@ -83,13 +83,10 @@ int build(qa_ssl* h, const HostTable& tab) {
     h->cln_b.assign(sp.n_conv, nullptr);
     if (sp.feat_norm_layer) {
         for (int i = 0; i < sp.n_conv; ++i) {
-            const std::string pre = "feature_extractor.conv_layers." + std::to_string(i) + ".layer_norm.";
-            L.vec(&h->cln_w[i], pre + "weight", sp.conv_dim[i]);
-            L.vec(&h->cln_b[i], pre + "bias", sp.conv_dim[i]);
+            L.norm(&h->cln_w[i], &h->cln_b[i], "feature_extractor.conv_layers." + std::to_string(i) + ".layer_norm", sp.conv_dim[i]);
         }
     } else {
-        L.vec(&h->gn_w, "feature_extractor.conv_layers.0.layer_norm.weight", C0);
-        L.vec(&h->gn_b, "feature_extractor.conv_layers.0.layer_norm.bias", C0);
+        L.norm(&h->gn_w, &h->gn_b, "feature_extractor.conv_layers.0.layer_norm", C0);
     }
     h->convs.resize(sp.n_conv - 1);
     for (int i = 1; i < sp.n_conv; ++i)
@@ -97,8 +94,7 @@ int build(qa_ssl* h, const HostTable& tab) {
                sp.conv_kernel[i], sp.conv_bias != 0);
     const int CL = sp.conv_dim[sp.n_conv - 1];
     // ---- feature projection
-    L.vec(&h->fp_ln_w, "feature_projection.layer_norm.weight", CL);
-    L.vec(&h->fp_ln_b, "feature_projection.layer_norm.bias", CL);
+    L.norm(&h->fp_ln_w, &h->fp_ln_b, "feature_projection.layer_norm", CL);
     L.conv(&h->fp, "feature_projection.projection", d, CL, 1);
     // ---- positional convolution: weight_norm(dim = 2) folded, then one [cg][k][cg] filter bank per group
     {
@@ -140,8 +136,7 @@ int build(qa_ssl* h, const HostTable& tab) {
             }
         }
     }
-    L.vec(&h->enc_ln_w, "encoder.layer_norm.weight", d);
-    L.vec(&h->enc_ln_b, "encoder.layer_norm.bias", d);
+    L.norm(&h->enc_ln_w, &h->enc_ln_b, "encoder.layer_norm", d);
     // ---- encoder layers
     h->layers.resize(sp.n_layers);
     for (int i = 0; i < sp.n_layers; ++i) {
@@ -162,12 +157,10 @@ int build(qa_ssl* h, const HostTable& tab) {
             L.raw(&Lw.qkv.b, b);
         }
         L.conv(&Lw.o, pre + "attention.out_proj", d, d, 1);
-        L.vec(&Lw.ln1w, pre + "layer_norm.weight", d);
-        L.vec(&Lw.ln1b, pre + "layer_norm.bias", d);
+        L.norm(&Lw.ln1w, &Lw.ln1b, pre + "layer_norm", d);
         L.conv(&Lw.ff1, pre + "feed_forward.intermediate_dense", I, d, 1);
         L.conv(&Lw.ff2, pre + "feed_forward.output_dense", d, I, 1);
-        L.vec(&Lw.ln2w, pre + "final_layer_norm.weight", d);
-        L.vec(&Lw.ln2b, pre + "final_layer_norm.bias", d);
+        L.norm(&Lw.ln2w, &Lw.ln2b, pre + "final_layer_norm", d);
         if (sp.rel_pos_buckets > 0) {  // gate = f(sum of 4 outputs): fold rows 0..3 and 4..7 of the 8 x hd projection
             const int hd = d / H;
             const float* gw = L.need(pre + "attention.gru_rel_pos_linear.weight", (int64_t)8 * hd);
@@ -294,14 +287,16 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         return QA_OK;
     };
     QA_TRY(maybe_accumulate(0, hcur));
-    const float scale = 1.0f / std::sqrt((float)hd);
+    AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
+    at.gate = gate;  // WavLM's gated relative position bias (gate is null without it)
+    at.relbias = rel ? h->relbias : nullptr;
+    at.R = sp.rel_pos_max_distance;
     for (int i = 0; i < sp.n_layers; ++i) {
         const SslLayer& Lw = h->layers[i];
         if (!sp.stable_layer_norm) {  // HubertEncoderLayer: x = LN(x + Attn(x)); x = LN(x + FFN(x))
             QA_TRY(linear_op(c, hcur, rows, Lw.qkv, qkv));
             if (rel) QA_RUN(c, launch_ssl_gate(hcur, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
-            QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0, gate,
-                                rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
+            QA_TRY(attention_op(c, at));
             QA_TRY(linear_op(c, att, rows, Lw.o, tmp, epi(ACT_NONE, hcur)));
             QA_TRY(layernorm_op(c, tmp, Lw.ln1w, Lw.ln1b, hnext, rows, d, eps));
             QA_TRY(linear_op(c, hnext, rows, Lw.ff1, ffu, epi(ACT_GELU)));
@@ -312,8 +307,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
             QA_TRY(layernorm_op(c, hcur, Lw.ln1w, Lw.ln1b, tmp, rows, d, eps));
             QA_TRY(linear_op(c, tmp, rows, Lw.qkv, qkv));
             if (rel) QA_RUN(c, launch_ssl_gate(tmp, Lw.gate_w, Lw.gate_b, Lw.gate_c, gate, B, N, H, hd, c.stream));
-            QA_TRY(attention_op(c, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, N, N, (long long)N * 3 * d, H, hd, scale, 0, gate,
-                                rel ? h->relbias : nullptr, sp.rel_pos_max_distance));
+            QA_TRY(attention_op(c, at));
             QA_TRY(linear_op(c, att, rows, Lw.o, hcur, epi(ACT_NONE, hcur)));
             QA_TRY(layernorm_op(c, hcur, Lw.ln2w, Lw.ln2b, tmp, rows, d, eps));
             QA_TRY(linear_op(c, tmp, rows, Lw.ff1, ffu, epi(ACT_GELU)));
