@@ -362,6 +362,14 @@ int64_t qa_ssl_frames(const qa_ssl* h, int64_t T);
 /* wav float32 [B, T] (device) -> feats float32 [B, frames, hidden] (device, channel-last: what qa_hcodec_encode takes as `feat`
  * with strides (frames*hidden, 1, hidden)) */
 int qa_ssl_forward(qa_ssl* h, const float* wav, int64_t B, int64_t T, float* feats, void* stream);
+/* The same for a batch of clips of different lengths: row b of wav [B, T] holds a clip in its first lengths[b]
+ * samples, and behaves as qa_ssl_forward would for those samples alone - `pad` zeros on each side of ITS samples, its GroupNorm over its
+ * own frames, the positional convolution zero-padded at its own end, attention over its own keys.  feats is [B, qa_ssl_frames(T), hidden]:
+ * n_b = qa_ssl_frames(lengths[b]) frames in feats[b, :n_b], exactly 0.0f in feats[b, n_b:].  What wav holds behind a clip's end is never
+ * read.  lengths: HOST memory, int64 [B], in SAMPLES, each from the shortest input that yields one frame up to T; read during the call
+ * (the caller may free it on return) and checked before anything is launched - QA_ERR_INVALID names the row and its value
+ * ("lengths[1] = 79 ...").  lengths == NULL, or every entry equal to T, is qa_ssl_forward: the same launches, bit-identical output. */
+int qa_ssl_forward_ragged(qa_ssl* h, const float* wav, int64_t B, int64_t T, const int64_t* lengths, float* feats, void* stream);
 
 /* ---- mimi StreamingTransformer: causal / context windows and the streaming state --------------------------
  * Replaces StreamingTransformer (QuarkAudio-HCodec/HCodec-1.5/adaptive/model_blocks/mimi/transformer.py:605-698) in the

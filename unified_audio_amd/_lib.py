@@ -183,6 +183,7 @@ SYMBOLS = {
     "qa_ssl_destroy": (None, [C.c_void_p]),
     "qa_ssl_frames": (C.c_int64, [C.c_void_p, C.c_int64]),
     "qa_ssl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_ssl_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "qa_bicodec_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_bicodec_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
     "qa_bicodec_destroy": (None, [C.c_void_p]),
     "qa_bicodec_hop": (C.c_int64, [C.c_void_p]),

@@ -451,7 +451,9 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
 
 template <int HD, bool SPLIT>
 static auto attention_instance(bool bias, bool kmask) {
-    return kmask ? attention_kernel<HD, false, true, SPLIT> : bias ? attention_kernel<HD, true, false, SPLIT> : attention_kernel<HD, false, false, SPLIT>;
+    // BIAS and KMASK together: WavLM under a key-padding mask (a ragged qa_ssl_forward_ragged call)
+    return kmask ? (bias ? attention_kernel<HD, true, true, SPLIT> : attention_kernel<HD, false, true, SPLIT>)
+                 : bias ? attention_kernel<HD, true, false, SPLIT> : attention_kernel<HD, false, false, SPLIT>;
 }
 
 static std::atomic<long long> g_att_launches[2];  // by kernel form: [0] fp32 chain, [1] split-6 (qa_debug_att_stats)
@@ -467,8 +469,7 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
     QA_REQUIRE((a.ldq % 4) == 0 && (a.ldkv % 4) == 0 && (a.ldo % 4) == 0, "attention: strides must be multiples of 4");
     QA_REQUIRE((a.gate == nullptr) == (a.relbias == nullptr) && (!a.gate || (a.R >= 0 && !a.causal && a.n_q == a.n_keys)),
                "attention: gate and relbias come together, for non-causal self-attention");
-    QA_REQUIRE(!a.kvalid || (!a.gate && !a.causal && a.n_q == a.n_keys),
-               "attention: the key-padding mask is for non-causal self-attention without bias");
+    QA_REQUIRE(!a.kvalid || (!a.causal && a.n_q == a.n_keys), "attention: the key-padding mask is for non-causal self-attention");
     const bool split = knob(K_ATT_MATH) != 0 && !a.math_fp32;
     const bool bias = a.gate != nullptr, kmask = a.kvalid != nullptr;
     decltype(attention_instance<32, false>(bias, kmask)) kernel;
@@ -502,7 +503,7 @@ extern "C" int qa_debug_att_stats(int64_t* out2) {
 }
 
 // test hook (not part of the public header): of those launches, the ones that took a key-padding-mask (KMASK) instantiation - the Conformer
-// condition encoder's, and the transformers of a ragged H-Codec call
+// condition encoder's, and the transformers of a ragged H-Codec or SSL front-end call
 extern "C" long long qa_debug_att_kmask_launches(void) { return qa::g_att_kmask_launches.load(std::memory_order_relaxed); }
 
 namespace qa {
@@ -534,7 +535,7 @@ extern "C" int qa_debug_att_split_unit(const float* x, long long n, unsigned lon
     return QA_OK;
 }
 
-// what the three hooks below share: the operands, the shape, the scale and the mask mode, as the C ABI spells them
+// what the four hooks below share: the operands, the shape, the scale and the mask mode, as the C ABI spells them
 static qa::AttnArgs debug_attn_args(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out, long long ldo,
                                     int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale, int causal) {
     qa::AttnArgs a;
@@ -551,6 +552,17 @@ extern "C" int qa_debug_attention_kmask(const float* q, long long ldq, const flo
                                         int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale,
                                         const unsigned char* kvalid, void* stream) {
     qa::AttnArgs a = debug_attn_args(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, 0);
+    a.kvalid = kvalid;
+    return qa::launch_attention(a, static_cast<hipStream_t>(stream));
+}
+
+// test hook (not part of the public header): the gated relative position bias (gate [B, H, n_q], relbias [H, 2R + 1]) under a key-padding
+// mask - the BIAS + KMASK instantiations a ragged WavLM call launches
+extern "C" int qa_debug_attention_bias_kmask(const float* q, long long ldq, const float* k, const float* v, long long ldkv, float* out,
+                                             long long ldo, int B, int n_q, int n_keys, long long kv_bstride, int H, int hd, float scale,
+                                             const float* gate, const float* relbias, int R, const unsigned char* kvalid, void* stream) {
+    qa::AttnArgs a = debug_attn_args(q, ldq, k, v, ldkv, out, ldo, B, n_q, n_keys, kv_bstride, H, hd, scale, 0);
+    a.gate = gate; a.relbias = relbias; a.R = R;
     a.kvalid = kvalid;
     return qa::launch_attention(a, static_cast<hipStream_t>(stream));
 }

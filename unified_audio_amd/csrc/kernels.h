@@ -161,15 +161,18 @@ int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int ma
                         hipStream_t s);
 
 // ssl_kernels.hip
+// wav_len / l0_len [B] (device, both or neither): clip b holds wav_len[b] of the T samples and l0_len[b] of the T1 layer-0 frames
 size_t ssl_conv0_scratch_bytes(int B, int T1, int C0);
 int launch_ssl_conv0(const float* wav, const float* w_kc, const float* bias, const float* gamma, const float* beta, float* y,
                      void* scratch, int B, int T, int T1, int C0, int ksize, int stride, int pad, int norm_group, float eps, int act,
-                     hipStream_t s);
+                     hipStream_t s, const int* wav_len = nullptr, const int* l0_len = nullptr);
 int launch_ssl_gate(const float* hidden, const float* wab, const float* bab, const float* cst, float* gate, int B, int N, int H, int hd,
                     hipStream_t s);
 int launch_ssl_accumulate(float* dst, const float* src, long long n, int first, hipStream_t s);
 int launch_ssl_act(float* x, long long n, int act, hipStream_t s);
-int launch_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, hipStream_t s);
+// n_len [B] (device) or null: out is [B, N, d] and the rows n >= n_len[b] of clip b are written as 0
+int launch_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, hipStream_t s, const int* n_len = nullptr,
+                        int N = 0, int d = 0);
 
 // bicodec_kernels.hip
 int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s);

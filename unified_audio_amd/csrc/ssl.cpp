@@ -6,6 +6,13 @@
 // same buffer: ldx = ldy = hidden) is a conv_gemm launch with bias / GELU / residual fused; only layer 0 (C_in = 1) and the
 // per-channel GroupNorm over time have their own kernel (ssl_kernels.hip).  Attention = the codec's flash kernel over a
 // fused QKV buffer (q, k, v projections concatenated at load time).
+//
+// Per-clip lengths (qa_ssl_forward_ragged): row b of a [B, T] batch behaves as its first lengths[b] samples alone.
+// Three layers of the graph see past a clip's end and take its length: layer 0 (the zero padding behind the clip's own last sample, and
+// the GroupNorm over time), the "same"-padded positional convolution and the attention (a key-padding mask).  The extractor layers
+// 1 .. n_conv-1 are valid convolutions - an output frame below the clip's count reads only input frames below the clip's count - and
+// everything else is row-wise.  Frames behind a clip's end are computed from valid samples and zeros, stay finite, and are read by no
+// valid frame; the output rows behind the end are written as 0.
 #include <cmath>
 #include <memory>
 
@@ -34,9 +41,20 @@ struct qa_ssl : Handle {
     const float* relbias = nullptr;  // WavLM: [H][2R+1] relative position bias by clamped distance, R = rel_pos_max_distance
     std::vector<SslLayer> layers;
     std::vector<int> select;
+    // ragged calls: the clips' lengths [3][lens_cap] - in samples, in layer-0 frames, in output frames - written on the call's stream
+    int* lens_dev = nullptr;
+    int lens_cap = 0;
+    ~qa_ssl() {
+        if (lens_dev) (void)hipFree(lens_dev);
+    }
 };
 
 namespace {
+
+// the lengths of a ragged call at the three stages that read them (device, [B] each); all null: every clip fills its row
+struct SslLens {
+    const int *samples = nullptr, *l0 = nullptr, *n = nullptr;
+};
 
 int64_t frames_of(const qa_ssl_spec& sp, int64_t T) {
     int64_t L = T + 2 * (int64_t)sp.pad;
@@ -207,7 +225,7 @@ int build(qa_ssl* h, const HostTable& tab) {
     return L.upload();
 }
 
-int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feats) {
+int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, const SslLens& lens, float* feats) {
     const qa_ssl_spec& sp = h->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H, I = sp.intermediate;
     const float eps = sp.layer_norm_eps;
@@ -219,7 +237,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         const size_t mark = c.arena.mark();
         char* scratch = c.arena.alloc<char>(ssl_conv0_scratch_bytes(B, L, C));
         QA_RUN(c, launch_ssl_conv0(wav, h->conv0_w, h->conv0_b, h->gn_w, h->gn_b, x, scratch, B, T, L, C, sp.conv_kernel[0], sp.conv_stride[0],
-                                   sp.pad, sp.feat_norm_layer ? 0 : 1, 1e-5f, sp.feat_norm_layer ? ACT_NONE : ACT_GELU, c.stream));
+                                   sp.pad, sp.feat_norm_layer ? 0 : 1, 1e-5f, sp.feat_norm_layer ? ACT_NONE : ACT_GELU, c.stream, lens.samples, lens.l0));
         c.arena.release(mark);
         if (sp.feat_norm_layer) {
             QA_TRY(layernorm_op(c, x, h->cln_w[0], h->cln_b[0], x, (int64_t)B * L, C, 1e-5f));
@@ -266,6 +284,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         ConvOpt o = conv_geom(1, k / 2, k - 1 - k / 2);
         o.act = ACT_GELU;
         o.ldr = d;
+        if (lens.n) o.rl = ClipLens{lens.n, 1};  // zeros behind the clip's own last frame, as the "same" padding of the clip alone
         for (int g = 0; g < G; ++g) {
             o.res = hcur + (size_t)g * cg;
             QA_TRY(conv_op(c, hcur + (size_t)g * cg, d, B, N, h->pos[g], hnext + (size_t)g * cg, d, N, o));
@@ -291,6 +310,11 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
     at.gate = gate;  // WavLM's gated relative position bias (gate is null without it)
     at.relbias = rel ? h->relbias : nullptr;
     at.R = sp.rel_pos_max_distance;
+    if (lens.n) {  // the keys behind a clip's end are invisible to its queries
+        unsigned char* kvalid = c.arena.alloc<unsigned char>((size_t)rows);
+        QA_RUN(c, launch_len_mask(kvalid, B, N, ClipLens{lens.n, 1}, c.stream));
+        at.kvalid = kvalid;
+    }
     for (int i = 0; i < sp.n_layers; ++i) {
         const SslLayer& Lw = h->layers[i];
         if (!sp.stable_layer_norm) {  // HubertEncoderLayer: x = LN(x + Attn(x)); x = LN(x + FFN(x))
@@ -321,7 +345,7 @@ int forward_graph(qa_ssl* h, Ctx& c, const float* wav, int B, int T, float* feat
         }
     }
     QA_REQUIRE(n_acc > 0, "ssl: no hidden state selected");
-    QA_RUN(c, launch_ssl_compress(acc, feats, (long long)rows * d, 1.0f / (float)n_acc, sp.compress_exponent, c.stream));
+    QA_RUN(c, launch_ssl_compress(acc, feats, (long long)rows * d, 1.0f / (float)n_acc, sp.compress_exponent, c.stream, lens.n, N, d));
     return QA_OK;
 }
 
@@ -359,17 +383,61 @@ int64_t qa_ssl_frames(const qa_ssl* h, int64_t T) {
     return n;
 }
 
+// qa_ssl_forward (lengths == nullptr) and qa_ssl_forward_ragged.  Everything is checked before the first launch; a call whose clips all
+// fill their rows is the rectangular call as it is: nothing uploaded, no mask, the same launches.
+static int forward_call(qa_ssl* h, const char* fn, const float* wav, int64_t B, int64_t T, const int64_t* lengths, float* feats, void* stream) {
+    const qa_ssl_spec& sp = h->spec;
+    const int64_t N = frames_of(sp, T);
+    QA_REQUIRE(B > 0 && N >= 1, "%s: wav is [%lld, %lld]: too short for the feature extractor", fn, (long long)B, (long long)T);
+    const int64_t L0 = (T + 2 * (int64_t)sp.pad - sp.conv_kernel[0]) / sp.conv_stride[0] + 1;
+    QA_REQUIRE(B * L0 < (1LL << 31) && L0 * sp.conv_dim[0] < (1LL << 31), "%s: batch of %lld x %lld samples is too large", fn, (long long)B,
+               (long long)T);
+    SslLens lens;
+    bool full = true;
+    for (int64_t b = 0; lengths && b < B; ++b) full = full && lengths[b] == T;
+    if (!full) {
+        QA_REQUIRE(B < (1 << 20) && T < (1LL << 31), "%s: %lld clips of %lld samples", fn, (long long)B, (long long)T);
+        int64_t min_len = 1;  // the shortest input that yields one frame
+        for (int i = sp.n_conv - 1; i >= 0; --i) min_len = (min_len - 1) * sp.conv_stride[i] + sp.conv_kernel[i];
+        min_len = std::max<int64_t>(1, min_len - 2 * (int64_t)sp.pad);
+        // host vectors [3][B]: samples, layer-0 frames (the valid-conv floor rule of the graph), output frames
+        std::vector<int> v((size_t)3 * B);
+        for (int64_t b = 0; b < B; ++b) {
+            QA_REQUIRE(lengths[b] >= min_len && lengths[b] <= T, "%s: lengths[%lld] = %lld is outside %lld .. T = %lld samples", fn, (long long)b,
+                       (long long)lengths[b], (long long)min_len, (long long)T);
+            v[(size_t)b] = (int)lengths[b];
+            v[(size_t)(B + b)] = (int)((lengths[b] + 2 * (int64_t)sp.pad - sp.conv_kernel[0]) / sp.conv_stride[0] + 1);
+            v[(size_t)(2 * B + b)] = (int)frames_of(sp, lengths[b]);
+        }
+        QA_HIP(hipSetDevice(h->device));
+        if (B > h->lens_cap) {
+            if (h->lens_dev) QA_HIP(hipFree(h->lens_dev));  // waits for the work that still reads it
+            h->lens_dev = nullptr;
+            h->lens_cap = 0;
+            const int cap = (int)round_up(B, 256);
+            QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->lens_dev), sizeof(int) * 3 * (size_t)cap));
+            h->lens_cap = cap;
+        }
+        QA_TRY(launch_row_lens(h->lens_dev, v.data(), (int)(3 * B), static_cast<hipStream_t>(stream)));
+        lens = SslLens{h->lens_dev, h->lens_dev + B, h->lens_dev + 2 * B};
+    }
+    return run_planned(*h, stream, [&] { return forward_graph(h, h->ctx, wav, (int)B, (int)T, lens, feats); });
+}
+
 int qa_ssl_forward(qa_ssl* h, const float* wav, int64_t B, int64_t T, float* feats, void* stream) {
     if (!h || !wav || !feats) {
         set_error("qa_ssl_forward: null argument");
         return QA_ERR_INVALID;
     }
-    const int64_t N = frames_of(h->spec, T);
-    QA_REQUIRE(B > 0 && N >= 1, "qa_ssl_forward: wav is [%lld, %lld]: too short for the feature extractor", (long long)B, (long long)T);
-    const int64_t L0 = (T + 2 * (int64_t)h->spec.pad - h->spec.conv_kernel[0]) / h->spec.conv_stride[0] + 1;
-    QA_REQUIRE(B * L0 < (1LL << 31) && L0 * h->spec.conv_dim[0] < (1LL << 31), "qa_ssl_forward: batch of %lld x %lld samples is too large",
-               (long long)B, (long long)T);
-    return run_planned(*h, stream, [&] { return forward_graph(h, h->ctx, wav, (int)B, (int)T, feats); });
+    return forward_call(h, "qa_ssl_forward", wav, B, T, nullptr, feats, stream);
+}
+
+int qa_ssl_forward_ragged(qa_ssl* h, const float* wav, int64_t B, int64_t T, const int64_t* lengths, float* feats, void* stream) {
+    if (!h || !wav || !feats) {
+        set_error("qa_ssl_forward_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    return forward_call(h, "qa_ssl_forward_ragged", wav, B, T, lengths, feats, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,10 @@ namespace qa {
 // GELU.  The [B, T1, C0] activation is 2 GB at 32 x 10 s, so the conv output is never stored un-normalised: pass 1 computes
 // it for the statistics only, pass 2 recomputes it (10 FMAs per element) and writes the normalised, activated result once.
 // One workgroup = TCH consecutive frames x all channels; the input samples of the chunk and the filters sit in LDS.
+// Ragged call (wav_len / l0_len [B] device arrays, both null otherwise - one uniform branch, no load): clip b ends
+// at wav_len[b] samples - a sample behind it reads as 0 and is never loaded - and its statistics cover its own l0_len[b] frames: a
+// chunk counts clamp(l0_len[b] - t0, 0, TCH) of them, so a chunk behind the end contributes exact zeros to the fixed-order fold.  Pass
+// 2 still writes every frame of the chunk (from valid samples and zeros: finite); nothing valid reads the ones behind the clip's end.
 constexpr int SSL_TCH = 64;
 constexpr int SSL_KMAX = 16;
 
@@ -22,7 +26,8 @@ __global__ __launch_bounds__(256) void ssl_conv0_kernel(const float* __restrict_
                                                         const float* __restrict__ bias, const float* __restrict__ stats,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         float* __restrict__ y, double* __restrict__ partial, int T, int T1,
-                                                        int C0, int ksize, int stride, int pad, int act) {
+                                                        int C0, int ksize, int stride, int pad, int act,
+                                                        const int* __restrict__ wav_len, const int* __restrict__ l0_len) {
     extern __shared__ float smem[];
     float* xs = smem;                                   // SSL_TCH * stride + ksize samples
     float* ws = smem + SSL_TCH * stride + SSL_KMAX;     // [ksize][C0]
@@ -30,10 +35,12 @@ __global__ __launch_bounds__(256) void ssl_conv0_kernel(const float* __restrict_
     const int t0 = chunk * SSL_TCH;
     const int nt = min(SSL_TCH, T1 - t0);
     const int span = (nt - 1) * stride + ksize;
+    const int len = wav_len ? wav_len[b] : T;                              // at most T (checked by the host)
+    const int nstat = l0_len ? max(0, min(nt, l0_len[b] - t0)) : nt;       // frames of the chunk the statistics cover
     const long long s0 = (long long)t0 * stride - pad;  // first sample of the chunk in un-padded coordinates
     for (int i = tid; i < span; i += 256) {
         const long long s = s0 + i;
-        xs[i] = (s >= 0 && s < T) ? wav[(long long)b * T + s] : 0.f;
+        xs[i] = (s >= 0 && s < len) ? wav[(long long)b * T + s] : 0.f;
     }
     for (int i = tid; i < ksize * C0; i += 256) ws[i] = w_kc[i];
     __syncthreads();
@@ -50,7 +57,7 @@ __global__ __launch_bounds__(256) void ssl_conv0_kernel(const float* __restrict_
             be = beta[c];
         }
         double s1 = 0.0, s2 = 0.0;
-        for (int t = 0; t < nt; ++t) {
+        for (int t = 0; t < (STATS ? nstat : nt); ++t) {
             const float* xp = xs + t * stride;
             float v = bc;
 #pragma unroll
@@ -74,9 +81,10 @@ __global__ __launch_bounds__(256) void ssl_conv0_kernel(const float* __restrict_
 
 // per (clip, channel): fold the chunk partials in chunk order (deterministic) -> {mean, 1/sqrt(biased var + eps)}
 __global__ void ssl_gn_finalize_kernel(const double* __restrict__ partial, float* __restrict__ stats, int nchunks, int C0, int T1,
-                                       float eps) {
+                                       float eps, const int* __restrict__ l0_len) {
     const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C0) return;
+    if (l0_len) T1 = l0_len[b];  // ragged call: the clip's own frame count (>= 1)
     double s1 = 0.0, s2 = 0.0;
     for (int k = 0; k < nchunks; ++k) {
         const double* p = partial + (((long long)b * nchunks + k) * C0 + c) * 2;
@@ -95,9 +103,11 @@ size_t ssl_conv0_scratch_bytes(int B, int T1, int C0) {
 }
 
 // norm_group != 0: GroupNorm(C0 groups) + act fused (two passes over the waveform); else plain conv (+bias) + act
+// wav_len / l0_len (device [B], together or not at all): the clips' lengths in samples and in layer-0 frames of a ragged call
 int launch_ssl_conv0(const float* wav, const float* w_kc, const float* bias, const float* gamma, const float* beta, float* y,
                      void* scratch, int B, int T, int T1, int C0, int ksize, int stride, int pad, int norm_group, float eps, int act,
-                     hipStream_t s) {
+                     hipStream_t s, const int* wav_len, const int* l0_len) {
+    QA_REQUIRE((wav_len == nullptr) == (l0_len == nullptr), "ssl conv0: per-clip lengths come in samples and in frames, together");
     QA_REQUIRE(ksize <= SSL_KMAX && C0 % 4 == 0, "ssl conv0: ksize %d / C0 %d unsupported", ksize, C0);
     const int nchunks = (int)ceil_div(T1, SSL_TCH);
     const size_t lds = (size_t)(SSL_TCH * stride + SSL_KMAX + ksize * C0) * sizeof(float);
@@ -106,12 +116,12 @@ int launch_ssl_conv0(const float* wav, const float* w_kc, const float* bias, con
     float* stats = reinterpret_cast<float*>(partial + (size_t)B * nchunks * C0 * 2);
     if (norm_group) {
         hipLaunchKernelGGL(ssl_conv0_kernel<true>, dim3(nchunks, B), dim3(256), lds, s, wav, w_kc, bias, nullptr, nullptr, nullptr,
-                           nullptr, partial, T, T1, C0, ksize, stride, pad, ACT_NONE);
+                           nullptr, partial, T, T1, C0, ksize, stride, pad, ACT_NONE, wav_len, l0_len);
         hipLaunchKernelGGL(ssl_gn_finalize_kernel, dim3((unsigned)ceil_div(C0, 256), B), dim3(256), 0, s, partial, stats, nchunks, C0,
-                           T1, eps);
+                           T1, eps, l0_len);
     }
     hipLaunchKernelGGL(ssl_conv0_kernel<false>, dim3(nchunks, B), dim3(256), lds, s, wav, w_kc, bias, norm_group ? stats : nullptr,
-                       gamma, beta, y, nullptr, T, T1, C0, ksize, stride, pad, act);
+                       gamma, beta, y, nullptr, T, T1, C0, ksize, stride, pad, act, wav_len, l0_len);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -186,15 +196,26 @@ int launch_ssl_act(float* x, long long n, int act, hipStream_t s) {
 }
 
 // out = sign * |m|^e with m = sum * scale and sign = +1 for m > 0, -1 otherwise (audio_tokenizer.py:43-46: "(x > 0) * 2 - 1");
-// expo <= 0: out = m
-__global__ void ssl_compress_kernel(const float* __restrict__ sum, float* __restrict__ out, long long n, float scale, float expo) {
+// expo <= 0: out = m.  n_len (device [B], ragged call; null otherwise): clip b = elements [b * per_clip, (b + 1) * per_clip) of rows of d
+// floats holds n_len[b] frames; the rows behind them are written as exactly 0 whatever `sum` holds there.
+__global__ void ssl_compress_kernel(const float* __restrict__ sum, float* __restrict__ out, long long n, float scale, float expo,
+                                    const int* __restrict__ n_len, long long per_clip, int d) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (n_len) {
+        const long long b = i / per_clip;
+        if ((i - b * per_clip) / d >= n_len[b]) {
+            out[i] = 0.f;
+            return;
+        }
+    }
     const float m = sum[i] * scale;
     out[i] = expo > 0.f ? (m > 0.f ? 1.f : -1.f) * powf(fabsf(m), expo) : m;
 }
-int launch_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, hipStream_t s) {
-    hipLaunchKernelGGL(ssl_compress_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, sum, out, n, scale, expo);
+int launch_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, hipStream_t s, const int* n_len, int N, int d) {
+    QA_REQUIRE(!n_len || (N > 0 && d > 0 && n % ((long long)N * d) == 0), "ssl compress: per-clip lengths need the [B, N, d] shape");
+    hipLaunchKernelGGL(ssl_compress_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, sum, out, n, scale, expo, n_len,
+                       (long long)N * d, d);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

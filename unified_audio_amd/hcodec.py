@@ -643,9 +643,12 @@ class HCodecTokenizer(torch.nn.Module):
         return out
 
     @torch.no_grad()
-    def extract_wav2vec2_features(self, wavs: torch.Tensor) -> torch.Tensor:
+    def extract_wav2vec2_features(self, wavs: torch.Tensor, lengths=None) -> torch.Tensor:
         """1.0: audio_tokenizer.py:35-48 (pad (160,160), mean of all hidden states, sign*|x|^0.3); 1.5: hidden states 11 / 14 / 16
-        (HCodec-1.5/audio_tokenizer.py:53-67); 2.0 (`extract_ssl_features`): Resample first (HCodec-2.0/audio_tokenizer.py:48-64)."""
+        (HCodec-1.5/audio_tokenizer.py:53-67); 2.0 (`extract_ssl_features`): Resample first (HCodec-2.0/audio_tokenizer.py:48-64).
+        lengths (an SSLFeatureExtractor without resampling only, `_ragged_front_end`): the clips' lengths in samples, passed on to it."""
+        if lengths is not None and not self._ragged_front_end():
+            raise _lib.QuarkAudioError(-3, "per-clip lengths need an SSLFeatureExtractor as feature_extractor and no resampling")
         if self.feature_extractor is None:
             raise _lib.QuarkAudioError(-3, "no feature_extractor was given; pass feats= to tokenize()")
         from .ssl import SSLFeatureExtractor
@@ -658,7 +661,7 @@ class HCodecTokenizer(torch.nn.Module):
             if want != have:
                 raise _lib.QuarkAudioError(-1, f"this tokenizer averages hidden states {want or 'all'} but the SSLFeatureExtractor was built "
                                                f"with select={have or 'all'} (H-Codec 1.5 needs SPEC_XLSR53, 1.0 / 2.0 SPEC_HUBERT_BASE)")
-            return fx(wavs)
+            return fx(wavs) if lengths is None else fx(wavs, lengths=lengths)
         wavs = torch.nn.functional.pad(wavs, (160, 160))
         feats = self.feature_extractor(wavs, output_hidden_states=True)
         hs = feats.hidden_states
@@ -670,6 +673,13 @@ class HCodecTokenizer(torch.nn.Module):
         return symbol * feats_mix.abs() ** 0.3
 
     extract_ssl_features = extract_wav2vec2_features  # the 2.0 tokenizer's name for it
+
+    def _ragged_front_end(self) -> bool:
+        """Whether the front-end takes per-clip lengths in one call (SSLFeatureExtractor.__call__(lengths=...)):
+        the library's own extractor, fed the codec's waveform as it is (the 2.0 tokenizer's resampler has no lengths)."""
+        from .ssl import SSLFeatureExtractor
+
+        return isinstance(self.feature_extractor, SSLFeatureExtractor) and self.sampling_rate == 16000
 
     def pad_wav(self, wav: torch.Tensor) -> torch.Tensor:
         pad = math.ceil(wav.size(-1) / self.hop_length) * self.hop_length - wav.size(-1)
@@ -698,8 +708,16 @@ class HCodecTokenizer(torch.nn.Module):
         ln = torch.tensor(lens, device=self.device)[:, None]
         end = torch.tensor(frames, device=self.device)[:, None] * hop
         wav = wav.masked_fill((pos >= ln) & (pos < end), 0.0)  # pad_wav of each clip alone: zeros up to its own hop multiple
-        if feats is None:
-            # the SSL front-end is not causal and takes no lengths: one pass per distinct padded length, scattered into one batch
+        if feats is None and self._ragged_front_end():
+            # ONE front-end call: row b is the clip padded to its own hop multiple, alone (its own padding, normalisation and keys)
+            fpc = int(math.prod(self.model.spec.sem_strides))
+            part = self.extract_wav2vec2_features(wav, lengths=[f * hop for f in frames])  # (b, t, d), zeros behind every clip's frames
+            short = [f for f in set(frames) if self.feature_extractor.frames(f * hop) < fpc * f]
+            if part.shape[1] < fpc * n or short:
+                raise _lib.QuarkAudioError(-1, f"the feature extractor returned {part.shape[1]} frames for {n} code frames, need {fpc * n}")
+            feats = part[:, : fpc * n]
+        elif feats is None:
+            # a front-end that takes no lengths (it is not causal): one pass per distinct padded length, scattered into one batch
             fpc = int(math.prod(self.model.spec.sem_strides))
             out = None
             for f in sorted(set(frames)):

@@ -147,8 +147,12 @@ class SSLFeatureExtractor:
         return int(n)
 
     @torch.no_grad()
-    def __call__(self, wavs: torch.Tensor) -> torch.Tensor:
-        """wavs float32 [B, T] on the device -> feats_mix float32 [B, frames, hidden] (what the reference transposes to (b, d, t))."""
+    def __call__(self, wavs: torch.Tensor, lengths=None) -> torch.Tensor:
+        """wavs float32 [B, T] on the device -> feats_mix float32 [B, frames, hidden] (what the reference transposes to (b, d, t)).
+
+        lengths: the clips' lengths in SAMPLES (host list / tensor, B entries), clip b in wavs[b, :lengths[b]].
+        Row b then holds the features of that clip alone in its first `frames(lengths[b])` frames and exact zeros behind them; what
+        wavs holds behind a clip's end is never read.  None, or every entry equal to T: the rectangular call."""
         self._require_loaded()
         if wavs.dim() != 2:
             raise ValueError(f"wavs must be [B, T], got {tuple(wavs.shape)}")
@@ -156,8 +160,16 @@ class SSLFeatureExtractor:
         B, T = wavs.shape
         out = torch.empty(B, self.frames(T), self.spec.hidden_size, device=self.device, dtype=torch.float32)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.qa_ssl_forward(self._handle, C.c_void_p(wavs.data_ptr()), B, T, C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(stream)))
+        if lengths is None:
+            _lib.check(self._lib.qa_ssl_forward(self._handle, C.c_void_p(wavs.data_ptr()), B, T, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(stream)))
+            return out
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B:
+            raise _lib.QuarkAudioError(-1, f"SSLFeatureExtractor: lengths has {len(lens)} entries for wavs [B = {B}, {T}]")
+        arr = (C.c_int64 * B)(*lens)  # host memory, read during the call
+        _lib.check(self._lib.qa_ssl_forward_ragged(self._handle, C.c_void_p(wavs.data_ptr()), B, T, arr, C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(stream)))
         return out
 
     extract_wav2vec2_features = __call__

@@ -124,6 +124,14 @@ class UniSE:
             self._ragged_ok = any(p.name == "enroll_lengths" or p.kind is inspect.Parameter.VAR_KEYWORD for p in params)
         except (AttributeError, TypeError, ValueError):
             self._ragged_ok = False
+        # the same for the front-end: SSLFeatureExtractor.__call__(wavs, lengths=...) runs enrollments of different
+        # lengths in one call, every row as the clip alone; it also needs `frames(samples)` for the rows' frame counts.  Any other
+        # front-end keeps one pass per distinct length
+        try:
+            params = inspect.signature(semantic_model.__call__).parameters.values()
+            self._ssl_ragged_ok = any(p.name == "lengths" for p in params) and callable(getattr(semantic_model, "frames", None))
+        except (AttributeError, TypeError, ValueError):
+            self._ssl_ragged_ok = False
 
     def _generate(self, mode: str, seg_src: torch.Tensor, counts: Sequence[int], enroll_feats_per_utt: Optional[torch.Tensor],
                   enroll_samples: int, enroll_frames: Optional[Sequence[int]] = None):
@@ -161,12 +169,19 @@ class UniSE:
 
     def _enroll_features(self, enrolls: Sequence[torch.Tensor]):
         """The SSL features of one enrollment per utterance -> ([U, N_e, d], samples, frames).  Equal lengths: one front-end pass, frames
-        None.  Different lengths: the front-end is not causal, so zero-padding a waveform would change its features - it runs once per
-        DISTINCT length (every utterance keeps its own enrollment length, as in the reference's one-file-per-step loop, model.py:197-219),
-        the features are zero-padded to the longest, and `frames` holds every utterance's own count for the LM's ragged call."""
+        None.  Different lengths: the front-end is not causal, so zero-padding a waveform would change its features.  A front-end that
+        takes per-clip `lengths` runs them in ONE call, every row as the enrollment alone (bit for bit, tests/test_ssl_ragged_gpu.py) with
+        zeros behind its frames.  Any other runs once per DISTINCT length (every utterance keeps its own enrollment length, as in the
+        reference's one-file-per-step loop, model.py:197-219) and the features are zero-padded to the longest.  Either way `frames` holds
+        every utterance's own count for the LM's ragged call."""
         lens = [int(e.size(-1)) for e in enrolls]
         if len(set(lens)) == 1:
             return self.semantic_model(torch.cat(list(enrolls), dim=0)), lens[0], None
+        if self._ssl_ragged_ok:
+            wav = enrolls[0].new_zeros((len(enrolls), max(lens)))
+            for i, e in enumerate(enrolls):
+                wav[i, :lens[i]] = e[0]
+            return self.semantic_model(wav, lengths=lens), max(lens), [int(self.semantic_model.frames(n)) for n in lens]
         feats: List[Optional[torch.Tensor]] = [None] * len(enrolls)
         for n in sorted(set(lens)):
             idx = [i for i, v in enumerate(lens) if v == n]
