@@ -140,8 +140,8 @@ int qa_hcodec_decode(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t*
 
 /* Per-clip lengths in one call (non-causal H-Codec 1.0): clip b behaves as qa_hcodec_encode / _decode would for it
  * alone at its own length.  frames: HOST memory, int64 [B], the clips' lengths in CODE frames, 1 .. N each (N = T / encoder hop), read
- * during the call and checked before anything is launched (QA_ERR_INVALID names the row).  H-Codec 1.5, 2.0 and causal handles are
- * refused with QA_ERR_UNSUPPORTED.  A call whose lengths all equal N is the rectangular call, through the same launches.
+ * during the call and checked before anything is launched (QA_ERR_INVALID names the row).  H-Codec 1.5 (which has the _adaptive_ragged
+ * calls below), 2.0 and causal handles are refused with QA_ERR_UNSUPPORTED.  A call whose lengths all equal N is the rectangular call, through the same launches.
  *   encode: samples of wav from frames[b] * hop on and feature frames from frames[b] * (n_feat_frames / N) on are padding that is never
  *           read (NaN there changes nothing); codes at frames >= frames[b] are written as -1, the dropped code, so the output is also a
  *           legal input of qa_hcodec_decode.
@@ -168,6 +168,27 @@ int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t
 int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* frames, void* stream);
 int qa_hcodec_decode_adaptive(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B,
                               int64_t G, int64_t frames, float* wav_out, void* stream);
+
+/* Per-clip lengths in one H-Codec 1.5 call (non-causal models): row b equals qa_hcodec_encode_adaptive /
+ * _decode_adaptive on clip b alone (B = 1) at its own length, with its own group count and no padded query token among its keys - which the
+ * rectangular calls above do not give even for clips of equal length (they keep the reference's batch semantics).  frames: HOST memory,
+ * int64 [B], code frames 1 .. N each, checked before anything is launched (QA_ERR_INVALID names the row).  A call with lengths always
+ * takes the masked path, also when every length is N.  spec.causal, causal aggregators and a causal bottleneck are QA_ERR_UNSUPPORTED.
+ *   encode: N = T / encoder hop.  *n_groups is the largest group count G over the clips; codes are written compactly as [B, nq, G], and the
+ *           entries of clip b behind its own groups are -1: in this wire format a legal entry of length 0 (floor(-1 / K) + 1 = 0), and the
+ *           dropped code, so the output is valid input for qa_hcodec_decode_adaptive and for qa_hcodec_decode_adaptive_ragged.  Samples
+ *           and feature frames behind a clip's length are never read.
+ *   qa_hcodec_adaptive_clip_frames: sum_g len[b, g] of every row as host int64 [B] (qa_hcodec_adaptive_frames returns their maximum),
+ *           behind the same single synchronisation.
+ *   decode: codes [B, nq, G]; wav_out [B, 2 * N * hop].  Row b de-aggregates at most frames[b] frames, its bottleneck transformer and
+ *           decoder see frames[b] frames, and wav_out[b] is exactly 0 from sample frames[b] * 2 * hop on. */
+int qa_hcodec_encode_adaptive_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const int64_t* frames,
+                                     const float* feat, int64_t feat_stride_b, int64_t feat_stride_c, int64_t feat_stride_t,
+                                     int64_t n_feat_frames, int64_t* acoustic_codes, int64_t* semantic_codes, int64_t* n_groups,
+                                     float threshold, void* stream);
+int qa_hcodec_adaptive_clip_frames(qa_hcodec* h, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* frames_out, void* stream);
+int qa_hcodec_decode_adaptive_ragged(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B, int64_t G,
+                                     int64_t N, const int64_t* frames, float* wav_out, void* stream);
 
 /* Semantic decoder of H-Codec (semantic_module.Decoder, QuarkAudio-HCodec/HCodec-1.0/vq/semantic_module.py:205-300): it rebuilds
  * the SSL features from the summed semantic code vectors.  conv1 (k3, no bias) code_dim -> channels; block i: a Conv1d k3 (stride 1)

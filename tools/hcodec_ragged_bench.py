@@ -1,9 +1,14 @@
 #!/usr/bin/env python
-"""H-Codec 1.0 ragged-batch micro-benchmark at the SPEC_10 size: N clips (seeded) whose lengths are spread over 2 - 10 s
-(50 - 250 code frames), resident on the device, features given.
+"""H-Codec ragged-batch micro-benchmark at the SPEC_10 size (or, with --model 1.5, SPEC_15): N clips (seeded) whose lengths are spread
+over 2 - 10 s (50 - 250 code frames), resident on the device, features given.
 
-  ragged    ONE Codec.encode(..., lengths=...) + ONE Codec.decode(..., lengths=...) over all N clips
+  ragged    ONE Codec.encode(..., lengths=...) + ONE Codec.decode(..., lengths=...) over all N clips (1.5: encode_ragged + decode_ragged)
   grouped   one encode + decode per DISTINCT length (what a caller did before per-clip lengths existed)
+
+--model 1.5 (anywhere on the command line; the default is 1.0): the adaptive codec, appended to profiles/hcodec15_ragged_bench.jsonl.  A
+grouped 1.5 call holds the clips of ONE length; with every length distinct that is B = 1, the call a per-clip row is defined to equal, so
+the two forms must agree bit for bit on every clip's valid part once the grouped encode takes the unfused stage 0 (QA_SEANET_FUSED=0,
+set here for the grouped 1.5 encode): the run fails if they do not.
 
 Argument 1: N (default 32).  Each figure is the median (min - max) of REPS runs (argument 2, default 5) after one warm-up run, wall clock
 around a device synchronisation; the two forms are compared on the valid part of every clip (codes_equal, wav_equal: the grouped calls
@@ -22,20 +27,31 @@ sys.path.insert(0, ROOT)
 import unified_audio_amd as qa  # noqa: E402
 from unified_audio_amd import synth  # noqa: E402  (seeded weights / inputs: data generation only)
 
-N_CLIPS = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "hcodec_ragged_bench.jsonl")
+ARGV = sys.argv[1:]
+MODEL = "1.0"
+if "--model" in ARGV:
+    i = ARGV.index("--model")
+    MODEL = ARGV[i + 1]
+    del ARGV[i:i + 2]
+if MODEL not in ("1.0", "1.5"):
+    sys.exit(f"--model {MODEL}: 1.0 or 1.5")
+ADAPTIVE = MODEL == "1.5"
+N_CLIPS = int(ARGV[0]) if len(ARGV) > 0 else 32
+REPS = int(ARGV[1]) if len(ARGV) > 1 else 5
+OUT = ARGV[2] if len(ARGV) > 2 else os.path.join(ROOT, "profiles", "hcodec15_ragged_bench.jsonl" if ADAPTIVE else "hcodec_ragged_bench.jsonl")
+BENCH = "hcodec15_ragged" if ADAPTIVE else "hcodec_ragged"
 FRAMES = (50, 250)  # 2 s .. 10 s at 25 code frames per second
 dev = torch.device("cuda:0")
-spec = qa.SPEC_10
+spec = qa.SPEC_15 if ADAPTIVE else qa.SPEC_10
 hop = spec.enc_hop
-codec = qa.Codec(None, None, None, spec=spec, device=dev, check_codes=False).load_state_dict(synth.hcodec10_state_dict(1234))
+codec = qa.Codec(None, None, None, spec=spec, device=dev, check_codes=False).load_state_dict(
+    synth.hcodec10_state_dict(1234, spec) if ADAPTIVE else synth.hcodec10_state_dict(1234))
 lens = [round(FRAMES[0] + (FRAMES[1] - FRAMES[0]) * i / max(N_CLIPS - 1, 1)) for i in range(N_CLIPS)]
 lens = [lens[i] for i in torch.randperm(N_CLIPS, generator=torch.Generator().manual_seed(7)).tolist()]  # a file list is not sorted
 distinct = sorted(set(lens))
 n_max = max(lens)
 wav = synth.synth_wav(11, N_CLIPS, hop * n_max).to(dev)
-feat = synth.synth_feat(12, N_CLIPS, 2 * n_max).to(dev)
+feat = (synth.synth_feat(12, N_CLIPS, 2 * n_max, spec.sem_in) if ADAPTIVE else synth.synth_feat(12, N_CLIPS, 2 * n_max)).to(dev)
 rows = []
 
 
@@ -51,7 +67,7 @@ def timed(fn):
 
 
 def report(name, ms, **kw):
-    row = dict(bench="hcodec_ragged", name=name, clips=N_CLIPS, ms_median=round(ms[0], 3), ms_min=round(ms[1], 3), ms_max=round(ms[2], 3),
+    row = dict(bench=BENCH, name=name, clips=N_CLIPS, ms_median=round(ms[0], 3), ms_min=round(ms[1], 3), ms_max=round(ms[2], 3),
                reps=REPS, **kw)
     rows.append(row)
     print(json.dumps(row), flush=True)
@@ -74,6 +90,59 @@ def grouped():
         w[idx, :hop * f] = codec.decode(a, s)
     return ac, sc, w
 
+
+def ragged15():
+    c = codec.encode_ragged(wav.unsqueeze(1), feat, lens)
+    return c["acoustic_codes"], c["semantic_codes"], codec.decode_ragged(**c)
+
+
+def grouped15():
+    """codes as a list per clip (every call has a group count of its own); the waveforms in one zero-initialised batch"""
+    from unified_audio_amd import _lib
+
+    ac, sc = [None] * N_CLIPS, [None] * N_CLIPS
+    w = torch.zeros((N_CLIPS, hop * n_max), device=dev)
+    for f in distinct:
+        rows_f = [b for b, x in enumerate(lens) if x == f]
+        idx = torch.tensor(rows_f, device=dev)
+        old = _lib.set_knob("QA_SEANET_FUSED", 0)
+        try:
+            c = codec.encode(wav[idx, :hop * f].unsqueeze(1), feat[idx, :, :2 * f])
+        finally:
+            _lib.set_knob("QA_SEANET_FUSED", old)
+        w[idx, :hop * f] = codec.decode(**c)
+        for i, b in enumerate(rows_f):
+            ac[b], sc[b] = c["acoustic_codes"][i], c["semantic_codes"][i]
+    return ac, sc, w
+
+
+if ADAPTIVE:
+    ms_r, (ar, sr, wr) = timed(ragged15)
+    ms_g, (ag, sg, wg) = timed(grouped15)
+    audio_s = sum(lens) * hop / 16000.0
+    K = spec.codebook_size
+    nseg = (torch.div(sr[:, 0], K, rounding_mode="floor") + 1 > 0).sum(dim=1).tolist()
+    report("ragged", ms_r, distinct_lengths=len(distinct), frames_min=min(lens), frames_max=max(lens), groups_min=min(nseg), groups_max=max(nseg),
+           audio_s_per_s=round(audio_s / ms_r[0] * 1e3, 1))
+    report("grouped", ms_g, distinct_lengths=len(distinct), calls=len(distinct), audio_s_per_s=round(audio_s / ms_g[0] * 1e3, 1))
+    # a grouped call of more than one clip keeps the reference's batch semantics (padded queries are keys), so bit equality is defined
+    # against B = 1 calls only: rows whose length is shared are compared on their own group count
+    single = [b for b, x in enumerate(lens) if lens.count(x) == 1]
+    codes_equal = all(torch.equal(ar[b, :, :nseg[b]], ag[b]) and torch.equal(sr[b, :, :nseg[b]], sg[b]) and bool((ar[b, :, nseg[b]:] == -1).all())
+                      for b in single)
+    wav_equal = all(torch.equal(wr[b, :hop * lens[b]], wg[b, :hop * lens[b]]) and not bool(wr[b, hop * lens[b]:].any()) for b in single)
+    row = dict(bench=BENCH, name="grouped_over_ragged", clips=N_CLIPS, ratio_of_medians=round(ms_g[0] / ms_r[0], 2),
+               ratio_min=round(ms_g[1] / ms_r[2], 2), ratio_max=round(ms_g[2] / ms_r[1], 2), distinct_lengths=len(distinct),
+               rows_compared=len(single), codes_equal=codes_equal, wav_equal=wav_equal)
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+    with open(OUT, "a") as f:
+        f.write("== python tools/hcodec_ragged_bench.py " + " ".join(sys.argv[1:]) + "\n")
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    if not (codes_equal and wav_equal):
+        sys.exit("the per-clip call and the B = 1 calls differ on a clip's valid part")
+    sys.exit(0)
 
 ms_r, (ar, sr, wr) = timed(ragged)
 ms_g, (ag, sg, wg) = timed(grouped)

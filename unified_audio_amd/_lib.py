@@ -137,6 +137,12 @@ SYMBOLS = {
     "qa_hcodec_adaptive_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "qa_hcodec_decode_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                             C.c_void_p]),
+    "qa_hcodec_encode_adaptive_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                                   C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_float,
+                                                   C.c_void_p]),
+    "qa_hcodec_adaptive_clip_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    "qa_hcodec_decode_adaptive_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                                   C.c_void_p, C.c_void_p]),
     "qa_hcodec_load_semantic_decoder": (C.c_int, [C.c_void_p, C.POINTER(qa_semantic_decoder_spec), C.POINTER(qa_tensor), C.c_int64]),
     "qa_hcodec_has_semantic_decoder": (C.c_int, [C.c_void_p]),
     "qa_hcodec_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,

@@ -469,7 +469,9 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
     QA_REQUIRE((a.ldq % 4) == 0 && (a.ldkv % 4) == 0 && (a.ldo % 4) == 0, "attention: strides must be multiples of 4");
     QA_REQUIRE((a.gate == nullptr) == (a.relbias == nullptr) && (!a.gate || (a.R >= 0 && !a.causal && a.n_q == a.n_keys)),
                "attention: gate and relbias come together, for non-causal self-attention");
-    QA_REQUIRE(!a.kvalid || (!a.causal && a.n_q == a.n_keys), "attention: the key-padding mask is for non-causal self-attention");
+    // the kernel indexes the mask by (item, key) alone and a non-causal query carries no position, so compact queries (n_q != n_keys: the
+    // aggregators' read-out layer) take it as self-attention does
+    QA_REQUIRE(!a.kvalid || !a.causal, "attention: the key-padding mask is for non-causal attention");
     const bool split = knob(K_ATT_MATH) != 0 && !a.math_fp32;
     const bool bias = a.gate != nullptr, kmask = a.kvalid != nullptr;
     decltype(attention_instance<32, false>(bias, kmask)) kernel;

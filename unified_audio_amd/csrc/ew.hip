@@ -561,15 +561,18 @@ int launch_istft_ola(const float* frames, const float* win, float* out, int B, i
 // One workgroup per batch item; the scan over T (<= a few hundred frames) is sequential in thread 0.
 //   seg[b][t]   group index of frame t          start[b][g], len[b][g] (0 for g >= nseg[b])      nseg[b]
 //   gmax        max over b of nseg (atomicMax; zeroed by the launcher)
+// lens (per-clip calls, else null): clip b holds lens[b] of the T frames; norms, similarities and the scan stop there (the frames behind
+// are never read), start / len behind nseg[b] are T / 0 as ever, and seg behind lens[b] is left unwritten: nothing reads it.
 __global__ __launch_bounds__(256) void align_kernel(const float* __restrict__ sem, int T, int D, float thr, int max_tokens,
                                                     int* __restrict__ seg, int* __restrict__ start, int* __restrict__ len,
-                                                    int* __restrict__ nseg, int* __restrict__ gmax) {
+                                                    int* __restrict__ nseg, int* __restrict__ gmax, const int* __restrict__ lens) {
     extern __shared__ float sh[];  // [T] 1/max(norm, eps), then [T] sim
     float* inv = sh;
     float* sim = sh + T;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = sem + (long long)b * T * D;
-    for (int t = wave; t < T; t += 4) {
+    const int Tb = lens ? min(max(lens[b], 1), T) : T;  // the strides below stay T: the buffers are [B, T]
+    for (int t = wave; t < Tb; t += 4) {
         float s = 0.f;
         for (int c = lane * 4; c < D; c += 256) {
             const float4 v = *reinterpret_cast<const float4*>(x + (long long)t * D + c);
@@ -579,7 +582,7 @@ __global__ __launch_bounds__(256) void align_kernel(const float* __restrict__ se
         if (lane == 0) inv[t] = 1.f / fmaxf(sqrtf(s), 1e-8f);  // F.cosine_similarity: x / clamp_min(||x||, eps)
     }
     __syncthreads();
-    for (int t = wave; t < T - 1; t += 4) {
+    for (int t = wave; t < Tb - 1; t += 4) {
         const float ia = inv[t], ib = inv[t + 1];
         float s = 0.f;
         for (int c = lane * 4; c < D; c += 256) {
@@ -593,7 +596,7 @@ __global__ __launch_bounds__(256) void align_kernel(const float* __restrict__ se
     __syncthreads();
     if (tid == 0) {
         int g = -1, in_seg = 0;
-        for (int t = 0; t < T; ++t) {
+        for (int t = 0; t < Tb; ++t) {
             const bool new_group = (t == 0) || (sim[t - 1] <= thr);
             in_seg = new_group ? 0 : in_seg + 1;
             if (in_seg % max_tokens == 0) {
@@ -614,11 +617,11 @@ __global__ __launch_bounds__(256) void align_kernel(const float* __restrict__ se
 }
 
 int launch_align(const float* sem, int B, int T, int D, float thr, int max_tokens, int* seg, int* start, int* len,
-                 int* nseg, int* gmax, hipStream_t s) {
+                 int* nseg, int* gmax, const int* lens, hipStream_t s) {
     QA_REQUIRE(D % 4 == 0 && T >= 1 && max_tokens >= 1, "align: bad shape");
     QA_HIP(hipMemsetAsync(gmax, 0, sizeof(int), s));
     hipLaunchKernelGGL(align_kernel, dim3(B), dim3(256), 2 * T * sizeof(float), s, sem, T, D, thr, max_tokens, seg, start, len,
-                       nseg, gmax);
+                       nseg, gmax, lens);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -626,13 +629,28 @@ int launch_align(const float* sem, int B, int T, int D, float thr, int max_token
 // QueryTokenAggregator input (mimi/transformer.py:766-806): frames interleaved with one query token after each group;
 // query = mean of the group's frames + query_embedding; padded groups (g >= nseg[b]) sit at the end and carry the bare
 // query embedding.  out [B, T + G, D].
+// lens (per-clip calls, else null): clip b holds lens[b] frames.  Its interleaved row is lens[b] + nseg[b] positions long, as for the clip
+// alone; frames behind lens[b] are not scattered and padded groups carry no query.  The T - lens[b] + G - nseg[b] blocks that have nothing
+// to place write exact zeros to the positions behind it, one each: those keys are masked (agg_key_mask), and a masked key's value still
+// enters the attention as 0 * V, so it has to be finite.
 __global__ __launch_bounds__(256) void agg_build_kernel(const float* __restrict__ feats, const int* __restrict__ seg,
                                                         const int* __restrict__ start, const int* __restrict__ len,
                                                         const int* __restrict__ nseg, const float* __restrict__ qemb,
-                                                        float* __restrict__ out, int T, int G, int D) {
+                                                        float* __restrict__ out, int T, int G, int D, const int* __restrict__ lens) {
     const int b = blockIdx.y, p = blockIdx.x;  // p: source element, frames 0..T-1 then queries T..T+G-1
     const int S = T + G;
     float* ob = out + (long long)b * S * D;
+    if (lens) {
+        const int Tb = min(max(lens[b], 1), T), used = Tb + nseg[b];
+        int zero_at = -1;
+        if (p < T && p >= Tb) zero_at = used + (p - Tb);  // used .. used + T - Tb - 1
+        if (p >= T && p - T >= nseg[b]) zero_at = p;      // T + nseg[b] .. S - 1, which is where the first range ends
+        if (zero_at >= 0) {
+            for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4)
+                *reinterpret_cast<float4*>(ob + (long long)zero_at * D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+    }
     if (p < T) {
         const int dst = p + seg[(long long)b * T + p];
         for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4)
@@ -661,8 +679,24 @@ __global__ __launch_bounds__(256) void agg_build_kernel(const float* __restrict_
     }
 }
 int launch_agg_build(const float* feats, const int* seg, const int* start, const int* len, const int* nseg, const float* qemb,
-                     float* out, int B, int T, int G, int D, hipStream_t s) {
-    hipLaunchKernelGGL(agg_build_kernel, dim3(T + G, B), dim3(128), 0, s, feats, seg, start, len, nseg, qemb, out, T, G, D);
+                     float* out, int B, int T, int G, int D, const int* lens, hipStream_t s) {
+    hipLaunchKernelGGL(agg_build_kernel, dim3(T + G, B), dim3(128), 0, s, feats, seg, start, len, nseg, qemb, out, T, G, D, lens);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+// key-padding mask of the aggregators in a per-clip call: valid [B, T + G] bytes, 1 for the lens[b] + nseg[b] positions clip b's
+// interleaved row holds.  One launch per encode, shared by both stacks and all their layers.
+__global__ void agg_key_mask_kernel(unsigned char* __restrict__ valid, int B, int T, int G, const int* __restrict__ lens,
+                                    const int* __restrict__ nseg) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int S = T + G;
+    if (gid >= (long long)B * S) return;
+    const int b = (int)(gid / S), j = (int)(gid - (long long)b * S);
+    valid[gid] = j < min(max(lens[b], 1), T) + nseg[b] ? 1 : 0;
+}
+int launch_agg_key_mask(unsigned char* valid, int B, int T, int G, const int* lens, const int* nseg, hipStream_t s) {
+    QA_REQUIRE(lens && nseg, "agg_key_mask: no lengths");
+    hipLaunchKernelGGL(agg_key_mask_kernel, dim3((unsigned)ceil_div((long long)B * (T + G), 256)), dim3(256), 0, s, valid, B, T, G, lens, nseg);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -724,19 +758,23 @@ int launch_agg_zero_padded(const int* nseg, float* out, int B, int G, int D, hip
 
 // library indices [B*G, Q] -> reference layout [B, Q, G] with the group length injected:
 // code' = (len - 1) * K + code (codec_adaptive.py:68-73; len = 0 for padded groups gives code - K, as in the reference)
+// pad_minus1 (per-clip calls): a padded group is written as -1 instead, the length-0 entry that is also the library's dropped code
 __global__ void codes_inject_kernel(const long long* __restrict__ idx, const int* __restrict__ len, long long* __restrict__ dst,
-                                    int B, int T, int G, int Q, int K) {
+                                    int B, int T, int G, int Q, int K, int pad_minus1) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * Q * G) return;
     const int g = (int)(gid % G);
     const int q = (int)((gid / G) % Q);
     const int b = (int)(gid / ((long long)G * Q));
-    dst[gid] = (long long)(len[(long long)b * T + g] - 1) * K + idx[((long long)b * G + g) * Q + q];
+    const int n = len[(long long)b * T + g];
+    const long long v = (long long)(n - 1) * K + idx[((long long)b * G + g) * Q + q];
+    dst[gid] = (pad_minus1 && n == 0) ? -1 : v;
 }
-int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K,
+int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K, bool pad_minus1,
                         hipStream_t s) {
     const long long total = (long long)B * Q * G;
-    hipLaunchKernelGGL(codes_inject_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, idx, len, dst, B, T, G, Q, K);
+    hipLaunchKernelGGL(codes_inject_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, idx, len, dst, B, T, G, Q, K,
+                       pad_minus1 ? 1 : 0);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -786,9 +824,12 @@ int launch_token_lengths(const long long* codes, long long* out, int B, int Q, i
 // _deaggregate_features_from_token_lengths on index tensors (modeling_flexicodec_new.py:1007-1041, codec_adaptive.py:184-189):
 // codes [B, Q, G] (length-injected) -> plain indices [B*T, Q], each group repeated len times, rows past an item's total = 0.
 // Lengths come from `len_codes` (the reference ends up using the semantic stream's lengths for both streams).
+// cap (per-clip calls, else null): item b de-aggregates at most cap[b] frames; the rows behind hold index 0 like every row past a total.
 __global__ __launch_bounds__(64) void deaggregate_kernel(const long long* __restrict__ codes, const long long* __restrict__ len_codes,
-                                                          long long* __restrict__ out, int Q, int G, int T, int K) {
+                                                          long long* __restrict__ out, int Q, int G, int T, int K,
+                                                          const int* __restrict__ cap) {
     const int b = blockIdx.x;
+    const int Tb = cap ? min(max(cap[b], 0), T) : T;
     __shared__ int s_start[1024];
     __shared__ int s_n;
     if (threadIdx.x == 0) {
@@ -810,14 +851,14 @@ __global__ __launch_bounds__(64) void deaggregate_kernel(const long long* __rest
             const long long c = codes[((long long)b * Q + q) * G + g];
             long long plain = c % K;
             if (plain < 0) plain += K;  // python modulo
-            for (int t = st; t < en && t < T; ++t) out[((long long)b * T + t) * Q + q] = plain;
+            for (int t = st; t < en && t < Tb; ++t) out[((long long)b * T + t) * Q + q] = plain;
         }
     }
 }
 int launch_deaggregate(const long long* codes, const long long* len_codes, long long* out, int B, int Q, int G, int T, int K,
-                       hipStream_t s) {
+                       const int* cap, hipStream_t s) {
     QA_REQUIRE(G <= 1024, "deaggregate: %d groups per item exceed 1024", G);
-    hipLaunchKernelGGL(deaggregate_kernel, dim3(B), dim3(64), 0, s, codes, len_codes, out, Q, G, T, K);
+    hipLaunchKernelGGL(deaggregate_kernel, dim3(B), dim3(64), 0, s, codes, len_codes, out, Q, G, T, K, cap);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

@@ -130,7 +130,8 @@ struct qa_hcodec : Handle {
         std::vector<int> enc;   // SEANet: at the input of stage i; enc[n_ratios] = 2, the rate of its transformer (empty for 2.0)
         std::vector<int> sem;   // semantic encoder: at the input of block i; sem[n_sem_strides] = 1, the rate of its output
     } geom;
-    // ragged calls (qa_hcodec_encode_ragged / _decode_ragged): the clips' code-frame counts [lens_cap], written on the call's stream
+    // ragged calls (qa_hcodec_encode_ragged / _decode_ragged and their _adaptive_ twins): the clips' code-frame counts [lens_cap], written on
+    // the call's stream
     int* lens_dev = nullptr;
     int lens_cap = 0;
     ~qa_hcodec() {
@@ -369,9 +370,10 @@ MimiTemps mimi_temps(Ctx& c, const MimiW& mw, int64_t rows) {
     t.u = c.arena.alloc<float>(rows * mw.ff);
     return t;
 }
-// st != nullptr: streaming step of N frames at st->offset (layer index li selects the ring caches); the caller advances the offset
-int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const MimiTemps& t, int B, int N, MimiStream* st = nullptr,
-               size_t li = 0) {
+// st != nullptr: streaming step of N frames at st->offset (layer index li selects the ring caches); the caller advances the offset.
+// kvalid: the key-padding mask [B, N] of a per-clip call (non-causal, non-streaming), or null.
+int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const MimiTemps& t, int B, int N, const unsigned char* kvalid,
+               MimiStream* st = nullptr, size_t li = 0) {
     const int d = mw.d, H = mw.heads, hd = d / H;
     const int64_t rows = (int64_t)B * N;
     const int pos0 = st ? st->offset : 0;
@@ -395,6 +397,7 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
     } else {
         at.causal = mw.causal;
         at.context = mw.causal ? mw.context : 0;
+        at.kvalid = kvalid;
     }
     QA_TRY(attention_op(c, at));
     QA_TRY(linear_op(c, t.att, rows, L.out_proj, x, epi(ACT_NONE, x, L.ls1)));
@@ -402,11 +405,12 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
     QA_TRY(linear_op(c, t.hn, rows, L.lin1, t.u, epi(ACT_GELU)));
     return linear_op(c, t.u, rows, L.lin2, x, epi(ACT_NONE, x, L.ls2));
 }
-int mimi_op(Ctx& c, const MimiW& mw, float* x, int B, int N) {
+int mimi_op(Ctx& c, const MimiW& mw, float* x, int B, int N, const unsigned char* kvalid) {
     QA_REQUIRE(N <= MAX_POS, "mimi transformer: sequence of %d tokens exceeds %d", N, MAX_POS);
+    QA_REQUIRE(!kvalid || !mw.causal, "mimi transformer: a key-padding mask needs a non-causal stack");
     const size_t mark = c.arena.mark();
     const MimiTemps t = mimi_temps(c, mw, (int64_t)B * N);
-    for (const MimiLayerW& L : mw.layers) QA_TRY(mimi_layer(c, mw, L, x, t, B, N));
+    for (const MimiLayerW& L : mw.layers) QA_TRY(mimi_layer(c, mw, L, x, t, B, N, kvalid));
     c.arena.release(mark);
     return QA_OK;
 }
@@ -420,9 +424,10 @@ struct AggReadout {
 // Last layer of an aggregator stack, read-out included (QA_AGG_LAST_ROWS): the keys and values need every row, so LayerNorm 1 and in_proj run
 // as in mimi_layer; everything after them is row-wise and runs on the B G query rows alone, gathered into xq / qq [B, G, d].  Every op gives
 // a row the bits it gives it in the full layer (conv_gemm does not depend on M or the tile, attention not on n_q), so out equals
-// agg_gather(mimi_layer(x)).  Non-causal stacks only: a compact query has lost its position.
+// agg_gather(mimi_layer(x)).  Non-causal stacks only: a compact query has lost its position.  kvalid [B, T + G] or null, as in mimi_layer:
+// the mask is per key, so the G compact queries take it as the T + G queries of the full layer do.
 int mimi_readout_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, const float* x, const MimiTemps& t, float* xq, float* qq, int B,
-                       const AggReadout& ro) {
+                       const AggReadout& ro, const unsigned char* kvalid) {
     const int d = mw.d, H = mw.heads, hd = d / H, N = ro.T + ro.G;
     const int64_t rows = (int64_t)B * N, qrows = (int64_t)B * ro.G;
     QA_TRY(layernorm_op(c, x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f));
@@ -432,6 +437,7 @@ int mimi_readout_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, const float
     QA_RUN(c, launch_agg_query_rows(x, t.qkv, ro.start, ro.len, ro.nseg, xq, qq, B, ro.T, ro.G, d, c.stream));
     AttnArgs at = attn_packed_qkv(t.qkv, t.att, B, N, H, hd);  // keys and values of all N rows ...
     at.q = qq; at.ldq = d; at.n_q = ro.G;                      // ... under the G compact queries
+    at.kvalid = kvalid;
     QA_TRY(attention_op(c, at));
     QA_TRY(linear_op(c, t.att, qrows, L.out_proj, xq, epi(ACT_NONE, xq, L.ls1)));
     QA_TRY(layernorm_op(c, xq, L.n2w, L.n2b, t.hn, qrows, d, 1e-5f));
@@ -442,9 +448,11 @@ int mimi_readout_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, const float
 }
 // two independent stacks of equal depth, layer-interleaved on two streams (xa on the caller's stream, xb on `side`); with read-outs (both
 // or neither) the last layer of each stack is mimi_readout_layer, which leaves xa / xb at the input of that layer
+// kvalid [B, N] or null: one key-padding mask for both stacks (they share the alignment), written on the caller's stream before the fork
 int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const MimiW& wb, float* xb, int B, int N,
-                 const AggReadout* ra = nullptr, const AggReadout* rb = nullptr) {
+                 const unsigned char* kvalid, const AggReadout* ra = nullptr, const AggReadout* rb = nullptr) {
     QA_REQUIRE(N <= MAX_POS && wa.layers.size() == wb.layers.size(), "mimi pair: mismatched stacks");
+    QA_REQUIRE(!kvalid || (!wa.causal && !wb.causal), "mimi pair: a key-padding mask needs non-causal stacks");
     QA_REQUIRE(!ra == !rb && (!ra || (!wa.causal && !wb.causal && wa.d == wb.d && !wa.layers.empty())), "mimi pair: bad read-out");
     const size_t mark = c.arena.mark();
     const MimiTemps ta = mimi_temps(c, wa, (int64_t)B * N);
@@ -457,10 +465,12 @@ int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const Mim
         for (size_t l = 0; l < wa.layers.size(); ++l) {
             const bool last = ra && l + 1 == wa.layers.size();
             c.stream = main;
-            int st = last ? mimi_readout_layer(c, wa, wa.layers[l], xa, ta, cq[0], cq[1], B, *ra) : mimi_layer(c, wa, wa.layers[l], xa, ta, B, N);
+            int st = last ? mimi_readout_layer(c, wa, wa.layers[l], xa, ta, cq[0], cq[1], B, *ra, kvalid)
+                          : mimi_layer(c, wa, wa.layers[l], xa, ta, B, N, kvalid);
             c.stream = side;
             if (st == QA_OK)
-                st = last ? mimi_readout_layer(c, wb, wb.layers[l], xb, tb, cq[2], cq[3], B, *rb) : mimi_layer(c, wb, wb.layers[l], xb, tb, B, N);
+                st = last ? mimi_readout_layer(c, wb, wb.layers[l], xb, tb, cq[2], cq[3], B, *rb, kvalid)
+                          : mimi_layer(c, wb, wb.layers[l], xb, tb, B, N, kvalid);
             c.stream = main;
             QA_TRY(st);
         }
@@ -748,6 +758,8 @@ int read_scalar(Ctx& c, qa_hcodec* h, const int* dev, int* out) {
     return QA_OK;
 }
 
+// Per-clip calls (tw.rl.n: the clips' code-frame counts): clip b is aligned over its own frames, its interleaved row
+// holds its own frames and groups and nothing else is a visible key, so row b is the call on that clip alone; codes behind its groups are -1.
 int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, const FeatView& f, long long* ac_out,
                           long long* sc_out, int* G_out, float threshold) {
     const qa_hcodec_spec& sp = h->spec;
@@ -755,6 +767,7 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis
     float *emb = nullptr, *sem = nullptr;
     int N = 0;
     QA_TRY(encode_front(h, c, wav, tw, f, &emb, &sem, &N));
+    const int* lens = tw.rl.n;  // code frames per clip, or null
     int* seg = c.arena.alloc<int>((size_t)B * N);
     int* start = c.arena.alloc<int>((size_t)B * N);
     int* len = c.arena.alloc<int>((size_t)B * N);
@@ -762,7 +775,7 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis
     int* gmax = c.arena.alloc<int>(1);
     int G = N;  // planning pass: worst case, every frame its own group
     if (!c.dry) {  // real pass only, more than launches: the group count is read back and checked
-        QA_TRY(launch_align(sem, B, N, D, threshold, sp.max_tokens_per_group, seg, start, len, nseg, gmax, c.stream));
+        QA_TRY(launch_align(sem, B, N, D, threshold, sp.max_tokens_per_group, seg, start, len, nseg, gmax, lens, c.stream));
         QA_TRY(read_scalar(c, h, gmax, &G));
         QA_REQUIRE(G >= 1 && G <= N, "encode: alignment produced %d groups for %d frames", G, N);
     }
@@ -775,8 +788,13 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis
     // semantic_aggregator(sem), acoustic_aggregator(emb): both use the alignment of the semantic stream and are otherwise
     // independent, so the two 32-layer stacks run concurrently on two streams (fork / join with events; no host sync)
     hipStream_t side = serial_mode() ? c.stream : h->side;  // qa_set_serial(1): one stream
-    QA_RUN(c, launch_agg_build(sem, seg, start, len, nseg, h->qemb_sem, inter_s, B, N, G, D, c.stream));
-    QA_RUN(c, launch_agg_build(emb, seg, start, len, nseg, h->qemb_ac, inter_a, B, N, G, D, c.stream));
+    QA_RUN(c, launch_agg_build(sem, seg, start, len, nseg, h->qemb_sem, inter_s, B, N, G, D, lens, c.stream));
+    QA_RUN(c, launch_agg_build(emb, seg, start, len, nseg, h->qemb_ac, inter_a, B, N, G, D, lens, c.stream));
+    unsigned char* kvalid = nullptr;  // the aggregators' key mask: in front of the fork, so both streams see it
+    if (lens) {
+        kvalid = c.arena.alloc<unsigned char>((size_t)B * S);
+        QA_RUN(c, launch_agg_key_mask(kvalid, B, N, G, lens, nseg, c.stream));
+    }
     if (!c.dry) {  // real pass only: the event fork
         QA_HIP(hipEventRecord(h->ev_fork, c.stream));
         QA_HIP(hipStreamWaitEvent(side, h->ev_fork, 0));
@@ -784,9 +802,9 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis
     // QA_AGG_LAST_ROWS: the last layer of each stack on the query rows only, read-out included (non-causal aggregators)
     if (knob(K_AGG_LAST_ROWS) != 0 && !h->agg_sem.causal && !h->agg_ac.causal && !h->agg_sem.layers.empty()) {
         const AggReadout rs{start, len, nseg, N, G, agg_s}, ra{start, len, nseg, N, G, agg_a};
-        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S, &rs, &ra));
+        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S, kvalid, &rs, &ra));
     } else {
-        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S));
+        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S, kvalid));
         QA_RUN(c, launch_agg_gather(inter_s, start, len, nseg, agg_s, B, N, G, D, c.stream));
         QA_RUN(c, launch_agg_gather(inter_a, start, len, nseg, agg_a, B, N, G, D, side));
     }
@@ -801,12 +819,13 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * G, sp.codebook_size, D));
     QA_RUN(c, launch_rvq_search(agg_a, (long long)B * G, h->cb_a, h->e2_a, Q, sp.codebook_size, D, ia, nullptr, 0, rvq_ws, c.stream));
     QA_RUN(c, launch_rvq_search(agg_s, (long long)B * G, h->cb_s, h->e2_s, Q, sp.codebook_size, D, is, nullptr, 0, rvq_ws, c.stream));
-    QA_RUN(c, launch_codes_inject(ia, len, ac_out, B, N, G, Q, sp.codebook_size, c.stream));
-    QA_RUN(c, launch_codes_inject(is, len, sc_out, B, N, G, Q, sp.codebook_size, c.stream));
+    QA_RUN(c, launch_codes_inject(ia, len, ac_out, B, N, G, Q, sp.codebook_size, lens != nullptr, c.stream));
+    QA_RUN(c, launch_codes_inject(is, len, sc_out, B, N, G, Q, sp.codebook_size, lens != nullptr, c.stream));
     return QA_OK;
 }
 
-// tc: the axis of the N de-aggregated code frames; G groups per clip in the codes
+// tc: the axis of the N de-aggregated code frames; G groups per clip in the codes.  Per-clip calls (tc.rl.n): clip b de-aggregates at most
+// tc.rl.n[b] frames, and its bottleneck transformer and decoder see that many.
 int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long long* scodes, const TimeAxis& tc, int G, float* wav_out) {
     const qa_hcodec_spec& sp = h->spec;
     const int Q = sp.num_quantizers, D = sp.code_dim, B = tc.B, N = tc.T;
@@ -815,11 +834,16 @@ int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long 
     long long* is = c.arena.alloc<long long>(rows * Q);
     float* cat = c.arena.alloc<float>(rows * 2 * D);
     // token lengths: the reference keeps the ones extracted from the SEMANTIC codes for both streams (codec_adaptive.py:185-186)
-    QA_RUN(c, launch_deaggregate(ac, scodes, ia, B, Q, G, N, sp.codebook_size, c.stream));
-    QA_RUN(c, launch_deaggregate(scodes, scodes, is, B, Q, G, N, sp.codebook_size, c.stream));
+    QA_RUN(c, launch_deaggregate(ac, scodes, ia, B, Q, G, N, sp.codebook_size, tc.rl.n, c.stream));
+    QA_RUN(c, launch_deaggregate(scodes, scodes, is, B, Q, G, N, sp.codebook_size, tc.rl.n, c.stream));
     QA_RUN(c, launch_rvq_lookup(ia, rows, h->cb_a, Q, sp.codebook_size, D, cat, 2 * D, c.stream));
     QA_RUN(c, launch_rvq_lookup(is, rows, h->cb_s, Q, sp.codebook_size, D, cat + D, 2 * D, c.stream));
-    QA_TRY(mimi_op(c, h->bottleneck, cat, B, N));
+    unsigned char* kvalid = nullptr;
+    if (tc.rl.n) {
+        kvalid = c.arena.alloc<unsigned char>(rows);
+        QA_RUN(c, launch_len_mask(kvalid, B, N, ClipLens{tc.rl.n, 1}, c.stream));
+    }
+    QA_TRY(mimi_op(c, h->bottleneck, cat, B, N, kvalid));
     c.tap("dec.bottleneck", cat, rows * 2 * D);
     return decode_tail(h, c, cat, tc, wav_out);
 }
@@ -900,7 +924,7 @@ int forward_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxi
     // every item's groups cover all N frames (x_lens = T for the whole batch, codec_adaptive.py:106-107): decode at N frames
     long long* is = c.arena.alloc<long long>((size_t)B * N * Q);
     QA_RUN(c, launch_token_lengths(sc, token_lengths, B, Q, G, K, c.stream));
-    QA_RUN(c, launch_deaggregate(sc, sc, is, B, Q, G, N, K, c.stream));  // codec_adaptive.py:134-135
+    QA_RUN(c, launch_deaggregate(sc, sc, is, B, Q, G, N, K, nullptr, c.stream));  // codec_adaptive.py:134-135
     QA_TRY(decode_adaptive_graph(h, c, ac, sc, tw.at(N, 1), G, recon));
     return semantic_decoder_from_codes(h, c, is, B, N, pred);
 }
@@ -1259,13 +1283,16 @@ static TimeAxis clip_axis(const qa_hcodec* h, int64_t B, int64_t T, int rate, co
     return TimeAxis{(int)B, (int)T, h->spec.causal != 0, ClipLens{lens, lens ? rate : 0}};
 }
 
-// ragged_refuse: the models that have no per-clip lengths.  ragged_lengths: the lengths themselves (HOST memory, code frames, 1 .. N each;
-// the error names the row).  *lens = nullptr when every clip has N frames: the call is then the rectangular one as it is - fused stage 0,
-// no key mask, nothing uploaded.  Otherwise *lens = h->lens_dev, the lengths on their way to it in stream order in front of the call's
-// kernels.
+// ragged_refuse: the models that qa_hcodec_encode_ragged / _decode_ragged do not serve.  H-Codec 1.5 has per-clip entry points of its own
+// (qa_hcodec_encode_adaptive_ragged / _decode_adaptive_ragged): its codes are [B, Q, G] with a group count the call
+// reports, which the 1.0 signatures cannot carry.  ragged_lengths: the lengths themselves (HOST memory, code frames, 1 .. N each;
+// the error names the row).  *lens = nullptr when every clip has N frames and the caller does not ask for the masked path whatever the
+// lengths (always_masked): the call is then the rectangular one as it is - fused stage 0, no key mask, nothing uploaded.  Otherwise
+// *lens = h->lens_dev, the lengths on their way to it in stream order in front of the call's kernels.
 static int ragged_refuse(qa_hcodec* h, const char* fn) {
     const qa_hcodec_spec& sp = h->spec;
-    const char* why = sp.adaptive ? "an H-Codec 1.5 model (spec.adaptive): its alignment and aggregators need per-row sequence lengths of their own"
+    const char* why = sp.adaptive ? "an H-Codec 1.5 model (spec.adaptive): its per-clip calls are qa_hcodec_encode_adaptive_ragged / "
+                                    "qa_hcodec_decode_adaptive_ragged (Codec.encode_ragged / decode_ragged)"
                       : sp.version == 20 ? "an H-Codec 2.0 model (spec.version == 20)"
                       : sp.causal        ? "a causal model (spec.causal)"
                                          : nullptr;
@@ -1275,7 +1302,8 @@ static int ragged_refuse(qa_hcodec* h, const char* fn) {
     }
     return QA_OK;
 }
-static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, const int64_t* frames, void* stream, const int** lens) {
+static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, const int64_t* frames, bool always_masked, void* stream,
+                          const int** lens) {
     QA_REQUIRE(B > 0 && N > 0 && B < (1 << 20), "%s: %lld clips of %lld code frames", fn, (long long)B, (long long)N);
     std::vector<int> len((size_t)B);
     bool full = true;
@@ -1286,7 +1314,7 @@ static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, co
         full = full && frames[b] == N;
     }
     *lens = nullptr;
-    if (full) return QA_OK;
+    if (full && !always_masked) return QA_OK;
     QA_HIP(hipSetDevice(h->device));
     if (B > h->lens_cap) {
         if (h->lens_dev) QA_HIP(hipFree(h->lens_dev));  // waits for the work that still reads it
@@ -1312,7 +1340,7 @@ static int encode_call(qa_hcodec* h, const char* fn, const float* wav, int64_t B
     if (frames) {
         QA_REQUIRE(f.n == N * h->geom.feat, "%s: feat has %lld frames, %lld code frames need %lld", fn, (long long)f.n, (long long)N,
                    (long long)(N * h->geom.feat));
-        QA_TRY(ragged_lengths(h, fn, B, N, frames, stream, &lens));
+        QA_TRY(ragged_lengths(h, fn, B, N, frames, false, stream, &lens));
     }
     const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, lens);
     return run(h, stream, [&] { return encode_graph(h, h->ctx, wav, tw, f, (long long*)ac, (long long*)sc); });
@@ -1327,7 +1355,7 @@ static int decode_call(qa_hcodec* h, const char* fn, const int64_t* ac, const in
                (long long)N);
     QA_TRY(family_check(h, fn, false));
     const int* lens = nullptr;
-    if (frames) QA_TRY(ragged_lengths(h, fn, B, N, frames, stream, &lens));
+    if (frames) QA_TRY(ragged_lengths(h, fn, B, N, frames, false, stream, &lens));
     const TimeAxis tc = clip_axis(h, B, N, 1, lens);
     return run(h, stream, [&] { return decode_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, tc, wav_out); });
 }
@@ -1355,26 +1383,64 @@ int qa_hcodec_decode_ragged(qa_hcodec* h, const int64_t* ac, const int64_t* sc, 
     return decode_call(h, "qa_hcodec_decode_ragged", ac, sc, B, N, frames, wav_out, stream);
 }
 
-int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
-                              int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, int64_t* n_groups, float threshold, void* stream) {
-    const char* fn = "qa_hcodec_encode_adaptive";
-    QA_REQUIRE(h && wav && feat && ac && sc && n_groups, "%s: null argument", fn);
+// The per-clip H-Codec 1.5 calls serve the non-causal model only: a causal aggregator or bottleneck attends by position, and their
+// attention takes no key-padding mask.
+static int adaptive_ragged_refuse(qa_hcodec* h, const char* fn) {
+    const qa_hcodec_spec& sp = h->spec;
+    const char* why = sp.causal ? "a causal model (spec.causal)"
+                      : (h->agg_sem.causal || h->agg_ac.causal) ? "causal aggregators (spec.agg_causal)"
+                      : h->bottleneck.causal ? "a causal bottleneck transformer (spec.bt_causal)"
+                                             : nullptr;
+    if (why) {
+        set_error("%s: per-clip lengths are implemented for the non-causal H-Codec 1.5; this handle has %s", fn, why);
+        return QA_ERR_UNSUPPORTED;
+    }
+    return QA_OK;
+}
+
+// qa_hcodec_encode_adaptive (frames == nullptr) and qa_hcodec_encode_adaptive_ragged.  With lengths the call always takes the masked
+// path, also when every length is N: rows may still differ in group count, and a row that is the clip alone is what the caller asked for.
+static int encode_adaptive_call(qa_hcodec* h, const char* fn, const float* wav, int64_t B, int64_t T, const int64_t* frames, const FeatView& f,
+                                int64_t* ac, int64_t* sc, int64_t* n_groups, float threshold, void* stream) {
     QA_TRY(family_check(h, fn, true));
+    if (frames) QA_TRY(adaptive_ragged_refuse(h, fn));
     const int64_t N = wav_code_frames(h, fn, B, T);
     if (N < 0) return (int)N;
     QA_REQUIRE(threshold >= 0.f && threshold <= 1.f, "%s: threshold %g outside [0, 1] (codec_adaptive.py:151)", fn, threshold);
     const float thr = threshold <= 0.f ? h->spec.threshold : threshold;  // codec_adaptive.py:158
-    const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, nullptr);
-    const FeatView f{feat, fsb, fsc, fst, (int)n_feat};
+    const int* lens = nullptr;
+    if (frames) {
+        QA_REQUIRE(f.n == N * h->geom.feat, "%s: feat has %lld frames, %lld code frames need %lld", fn, (long long)f.n, (long long)N,
+                   (long long)(N * h->geom.feat));
+        QA_TRY(ragged_lengths(h, fn, B, N, frames, true, stream, &lens));
+    }
+    const TimeAxis tw = clip_axis(h, B, T, h->geom.samples, lens);
     int G = 0;
     QA_TRY(run(h, stream, [&] { return encode_adaptive_graph(h, h->ctx, wav, tw, f, (long long*)ac, (long long*)sc, &G, thr); }));
     *n_groups = G;
     return QA_OK;
 }
 
-int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* frames, void* stream) {
-    QA_REQUIRE(h && semantic_codes && frames, "qa_hcodec_adaptive_frames: null argument");
-    QA_REQUIRE(h->spec.adaptive && B > 0 && G > 0, "qa_hcodec_adaptive_frames: bad argument");
+int qa_hcodec_encode_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const float* feat, int64_t fsb, int64_t fsc,
+                              int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, int64_t* n_groups, float threshold, void* stream) {
+    const char* fn = "qa_hcodec_encode_adaptive";
+    QA_REQUIRE(h && wav && feat && ac && sc && n_groups, "%s: null argument", fn);
+    return encode_adaptive_call(h, fn, wav, B, T, nullptr, FeatView{feat, fsb, fsc, fst, (int)n_feat}, ac, sc, n_groups, threshold, stream);
+}
+
+int qa_hcodec_encode_adaptive_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const int64_t* frames, const float* feat,
+                                     int64_t fsb, int64_t fsc, int64_t fst, int64_t n_feat, int64_t* ac, int64_t* sc, int64_t* n_groups,
+                                     float threshold, void* stream) {
+    const char* fn = "qa_hcodec_encode_adaptive_ragged";
+    QA_REQUIRE(h && wav && frames && feat && ac && sc && n_groups, "%s: null argument", fn);
+    return encode_adaptive_call(h, fn, wav, B, T, frames, FeatView{feat, fsb, fsc, fst, (int)n_feat}, ac, sc, n_groups, threshold, stream);
+}
+
+// qa_hcodec_adaptive_frames (the maximum) and qa_hcodec_adaptive_clip_frames (every row's total): one launch, one synchronisation.  The
+// per-row totals come back in the same copy as the maximum, through a pageable host buffer (the pinned scalar holds one int).
+static int adaptive_frames_call(qa_hcodec* h, const char* fn, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* max_out,
+                                int64_t* rows_out, void* stream) {
+    QA_REQUIRE(h->spec.adaptive && B > 0 && G > 0 && B < (1 << 20), "%s: bad argument", fn);
     QA_HIP(hipSetDevice(h->device));
     QA_TRY(h->ws.ensure((size_t)(B + 64) * sizeof(int)));
     Ctx& c = h->ctx;
@@ -1383,20 +1449,53 @@ int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64
     int* tmax = totals + B;
     QA_TRY(launch_adaptive_frames((const long long*)semantic_codes, (int)B, h->spec.num_quantizers, (int)G, h->spec.codebook_size,
                                   totals, tmax, c.stream));
-    int n = 0;
-    QA_TRY(read_scalar(c, h, tmax, &n));
-    *frames = n;
+    if (!rows_out) {
+        int n = 0;
+        QA_TRY(read_scalar(c, h, tmax, &n));
+        *max_out = n;
+        return QA_OK;
+    }
+    std::vector<int> host((size_t)B);
+    QA_HIP(hipMemcpyAsync(host.data(), totals, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, c.stream));
+    QA_HIP(hipStreamSynchronize(c.stream));  // the one synchronisation qa_hcodec_adaptive_frames makes
+    lstm_call_note_sync();
+    for (int64_t b = 0; b < B; ++b) rows_out[b] = host[(size_t)b];
     return QA_OK;
+}
+
+int qa_hcodec_adaptive_frames(qa_hcodec* h, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* frames, void* stream) {
+    QA_REQUIRE(h && semantic_codes && frames, "qa_hcodec_adaptive_frames: null argument");
+    return adaptive_frames_call(h, "qa_hcodec_adaptive_frames", semantic_codes, B, G, frames, nullptr, stream);
+}
+
+int qa_hcodec_adaptive_clip_frames(qa_hcodec* h, const int64_t* semantic_codes, int64_t B, int64_t G, int64_t* frames_out, void* stream) {
+    QA_REQUIRE(h && semantic_codes && frames_out, "qa_hcodec_adaptive_clip_frames: null argument");
+    return adaptive_frames_call(h, "qa_hcodec_adaptive_clip_frames", semantic_codes, B, G, nullptr, frames_out, stream);
+}
+
+// qa_hcodec_decode_adaptive (frames == nullptr: every clip has N frames) and qa_hcodec_decode_adaptive_ragged
+static int decode_adaptive_call(qa_hcodec* h, const char* fn, const int64_t* ac, const int64_t* sc, int64_t B, int64_t G, int64_t N,
+                                const int64_t* frames, float* wav_out, void* stream) {
+    QA_TRY(family_check(h, fn, true));
+    if (frames) QA_TRY(adaptive_ragged_refuse(h, fn));
+    QA_REQUIRE(B > 0 && G > 0 && N > 0 && B * N * h->geom.dec * (int64_t)h->spec.hop < (1LL << 31),
+               "%s: bad shape: %lld clips, %lld groups, %lld frames", fn, (long long)B, (long long)G, (long long)N);
+    const int* lens = nullptr;
+    if (frames) QA_TRY(ragged_lengths(h, fn, B, N, frames, true, stream, &lens));
+    const TimeAxis tc = clip_axis(h, B, N, 1, lens);
+    return run(h, stream, [&] { return decode_adaptive_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, tc, (int)G, wav_out); });
 }
 
 int qa_hcodec_decode_adaptive(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t G, int64_t frames,
                               float* wav_out, void* stream) {
     QA_REQUIRE(h && ac && sc && wav_out, "qa_hcodec_decode_adaptive: null argument");
-    QA_TRY(family_check(h, "qa_hcodec_decode_adaptive", true));
-    QA_REQUIRE(B > 0 && G > 0 && frames > 0 && B * frames * h->geom.dec * (int64_t)h->spec.hop < (1LL << 31),
-               "qa_hcodec_decode_adaptive: bad shape: %lld clips, %lld groups, %lld frames", (long long)B, (long long)G, (long long)frames);
-    const TimeAxis tc = clip_axis(h, B, frames, 1, nullptr);
-    return run(h, stream, [&] { return decode_adaptive_graph(h, h->ctx, (const long long*)ac, (const long long*)sc, tc, (int)G, wav_out); });
+    return decode_adaptive_call(h, "qa_hcodec_decode_adaptive", ac, sc, B, G, frames, nullptr, wav_out, stream);
+}
+
+int qa_hcodec_decode_adaptive_ragged(qa_hcodec* h, const int64_t* ac, const int64_t* sc, int64_t B, int64_t G, int64_t N, const int64_t* frames,
+                                     float* wav_out, void* stream) {
+    QA_REQUIRE(h && ac && sc && frames && wav_out, "qa_hcodec_decode_adaptive_ragged: null argument");
+    return decode_adaptive_call(h, "qa_hcodec_decode_adaptive_ragged", ac, sc, B, G, N, frames, wav_out, stream);
 }
 
 int qa_hcodec_load_semantic_decoder(qa_hcodec* h, const qa_semantic_decoder_spec* spec, const qa_tensor* tensors, int64_t n_tensors) {
@@ -1499,7 +1598,7 @@ static int mimi_run(qa_mimi* m, const float* x, int B, int T, float* y, hipStrea
         if (c.dry) return QA_OK;  // real-pass-only remainder (the copy and the layers), below the graph's only allocations
         if (y != x) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * rows * m->w.d, hipMemcpyDeviceToDevice, stream));
         for (size_t l = 0; l < m->w.layers.size(); ++l)
-            QA_TRY(mimi_layer(c, m->w, m->w.layers[l], y, t, B, T, streaming ? &m->st : nullptr, l));
+            QA_TRY(mimi_layer(c, m->w, m->w.layers[l], y, t, B, T, nullptr, streaming ? &m->st : nullptr, l));
         return QA_OK;
     };
     return run_planned(*m, stream, graph);

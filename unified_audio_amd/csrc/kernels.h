@@ -40,21 +40,26 @@ int launch_groupnorm(const float* x, const float* w, const float* bias, float* y
 // rot_heads > 0: only heads 0 .. rot_heads - 1 of q and k are rotated (Conformer `pe_attn_head`, conformer.py:157-160)
 int launch_rope(float* qkv, const float* cos_sin, int B, int N, int H, int hd, long long ld, int pos0, hipStream_t s,
                 int interleaved = 0, int rot_heads = 0);
+// H-Codec 1.5 per-clip calls pass lens / cap [B] (device): the clips' code-frame counts.  Null everywhere else:
+// every clip has T frames and the kernels take the path they always took through one uniform branch, without a load.
 int launch_align(const float* sem, int B, int T, int D, float thr, int max_tokens, int* seg, int* start, int* len,
-                 int* nseg, int* gmax, hipStream_t s);
+                 int* nseg, int* gmax, const int* lens, hipStream_t s);
 int launch_agg_build(const float* feats, const int* seg, const int* start, const int* len, const int* nseg, const float* qemb,
-                     float* out, int B, int T, int G, int D, hipStream_t s);
+                     float* out, int B, int T, int G, int D, const int* lens, hipStream_t s);
+// valid [B, T + G] bytes: 1 where j < lens[b] + nseg[b] (the aggregators' key-padding mask in a per-clip call)
+int launch_agg_key_mask(unsigned char* valid, int B, int T, int G, const int* lens, const int* nseg, hipStream_t s);
 int launch_agg_gather(const float* x, const int* start, const int* len, const int* nseg, float* out, int B, int T, int G,
                       int D, hipStream_t s);
 int launch_agg_query_rows(const float* x, const float* qkv, const int* start, const int* len, const int* nseg, float* xq, float* qq,
                           int B, int T, int G, int D, hipStream_t s);
 int launch_agg_zero_padded(const int* nseg, float* out, int B, int G, int D, hipStream_t s);
-int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K,
+// pad_minus1: padded groups (len 0) are written as -1 instead of code - K
+int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K, bool pad_minus1,
                         hipStream_t s);
 int launch_adaptive_frames(const long long* codes, int B, int Q, int G, int K, int* totals, int* tmax, hipStream_t s);
 int launch_token_lengths(const long long* codes, long long* out, int B, int Q, int G, int K, hipStream_t s);
 int launch_deaggregate(const long long* codes, const long long* len_codes, long long* out, int B, int Q, int G, int T, int K,
-                       hipStream_t s);
+                       const int* cap, hipStream_t s);
 int launch_to_channel_last(const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T,
                            hipStream_t s);
 // lens [B] (device) or null: entries n >= lens[b] are written as -1 (the dropped code) whatever the source holds
@@ -79,7 +84,8 @@ int launch_resample(const float* wav, const float* taps, float* out, int B, long
 //   causal = 1: key j visible to query i iff j <= i + (n_keys - n_q) (LM prefill / decode over a KV cache)
 //   gate [B, H, n_q] + relbias [H, 2R+1] (optional): score(i, j) += gate[b,h,i] * relbias[h][clamp(j - i, -R, R) + R]
 //   (WavLM gated relative position bias)
-//   kvalid [B, n_keys] bytes (optional, non-causal self-attention only): key j of item b is visible iff kvalid[b, j] != 0
+//   kvalid [B, n_keys] bytes (optional, non-causal only; n_q need not equal n_keys: the mask is indexed by key alone): key j of item b
+//   is visible iff kvalid[b, j] != 0
 //   one kernel body in two arithmetic forms (attention_kernel<HD, BIAS, KMASK, SPLIT>): split-6 on the bf16 MFMA where QA_ATT_MATH = 1
 //   math_fp32: keep the fp32 form (SPLIT = false, v_mfma_f32_32x32x2_f32) whatever QA_ATT_MATH says (Ctx::att_fp32)
 struct AttnArgs {

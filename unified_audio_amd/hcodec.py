@@ -433,7 +433,8 @@ class Codec(torch.nn.Module):
 
         lengths (non-causal H-Codec 1.0): the clips' lengths in CODE frames, a host list / tensor of B values in 1 .. N25.  Row b then
         equals encode of that clip alone at its own length; samples and feature frames behind it are never read, codes behind it are
-        -1 (the dropped code).  None: the rectangular call, exactly as before."""
+        -1 (the dropped code).  None: the rectangular call, exactly as before.  H-Codec 1.5 refuses `lengths=` here (its codes are a
+        dict of [B, nq, G] tensors): `encode_ragged` / `decode_ragged` are its per-clip calls."""
         self._require_loaded()
         if self.spec.version == 20 and x.dim() == 2:  # H-Codec 2.0 passes wav without the channel dim (audio_tokenizer.py:73)
             x = x.unsqueeze(1)
@@ -451,6 +452,7 @@ class Codec(torch.nn.Module):
         sb, sch, st = feat.stride()
         if lengths is not None:
             frames = _frames_arg(lengths, B)
+            # (an H-Codec 1.5 handle is refused by the library with status -4, naming encode_ragged / decode_ragged)
             _lib.check(self._lib.qa_hcodec_encode_ragged(self._handle, x.data_ptr(), B, T, frames, feat.data_ptr(), sb, sch, st,
                                                          feat.shape[2], ac.data_ptr(), sc.data_ptr(), _stream_ptr(self.device)))
             return ac, sc
@@ -480,7 +482,8 @@ class Codec(torch.nn.Module):
 
         lengths (keyword only; non-causal H-Codec 1.0): the clips' lengths in code frames, a host list / tensor of B values in 1 .. N.
         Row b then equals decode of its first lengths[b] frames alone; entries behind them are ignored whatever they hold (the range
-        check does not count them), and the waveform is exactly zero from sample lengths[b] * 2 * hop on."""
+        check does not count them), and the waveform is exactly zero from sample lengths[b] * 2 * hop on.  H-Codec 1.5 refuses `lengths=`
+        here: its codes carry their lengths, and `decode_ragged` is its per-clip call."""
         self._require_loaded()
         if self.spec.adaptive and lengths is None:
             return self._decode_adaptive(acoustic_codes, semantic_codes, token_lengths)
@@ -510,6 +513,103 @@ class Codec(torch.nn.Module):
         self._check_range_end(pending)  # IndexError like the reference's F.embedding, raised behind the decode's own synchronisation
         return wav
 
+    # -- per-clip lengths, every model ---------------------------------------------------------------
+    @torch.no_grad()
+    def encode_ragged(self, x: torch.Tensor, feat: torch.Tensor, lengths, threshold: float = 0.0):
+        """One encode of clips of unequal length.  lengths: code frames per clip, a host list / tensor of B values in 1 .. N.
+
+        H-Codec 1.5: {'acoustic_codes', 'semantic_codes'} as int64 [B, nq, G], G the largest group count of the
+        batch.  Row b equals `encode` of clip b alone (B = 1) at its own length - its own alignment, its own group count, no padded query
+        token among its keys, which the rectangular `encode` does not give even for clips of equal length.  Entries behind a clip's own
+        groups are -1, a legal entry of length 0, so the dict is valid input for `decode` and `decode_ragged` alike.
+        H-Codec 1.0: `encode(x, feat, lengths=lengths)`."""
+        if not self.spec.adaptive:
+            return self.encode(x, feat, lengths=lengths)
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise _lib.QuarkAudioError(-1, f"encode_ragged expects x of shape [B,1,T], got {tuple(x.shape)}")
+        if feat.dim() != 3 or feat.shape[0] != x.shape[0] or feat.shape[1] != self.spec.sem_in:
+            raise _lib.QuarkAudioError(-1, f"encode_ragged expects feat of shape [B,{self.spec.sem_in},N], got {tuple(feat.shape)}")
+        if not 0 <= threshold <= 1.0:
+            raise _lib.QuarkAudioError(-1, f"encode_ragged: threshold {threshold} outside [0, 1]")
+        B, _, T = x.shape
+        frames = _frames_arg(lengths, B)
+        self._require_loaded()
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        feat = feat.to(device=self.device, dtype=torch.float32)
+        n25 = T // self.spec.enc_hop
+        q = self.spec.num_quantizers
+        ac = torch.empty((B, q, max(n25, 1)), dtype=torch.int64, device=self.device)
+        sc = torch.empty((B, q, max(n25, 1)), dtype=torch.int64, device=self.device)
+        sb, sch, st = feat.stride()
+        g = C.c_int64(0)
+        _lib.check(self._lib.qa_hcodec_encode_adaptive_ragged(self._handle, x.data_ptr(), B, T, frames, feat.data_ptr(), sb, sch, st,
+                                                              feat.shape[2], ac.data_ptr(), sc.data_ptr(), C.byref(g), float(threshold),
+                                                              _stream_ptr(self.device)))
+        G = int(g.value)
+        return {"acoustic_codes": ac.view(-1)[: B * q * G].view(B, q, G), "semantic_codes": sc.view(-1)[: B * q * G].view(B, q, G)}
+
+    def _adaptive_codes(self, acoustic_codes, semantic_codes, token_lengths, what: str):
+        """The two code tensors of an H-Codec 1.5 decode on the device, length-injected (codec_adaptive.py:68-73)."""
+        q, K = self.spec.num_quantizers, self.spec.codebook_size
+        if acoustic_codes.shape != semantic_codes.shape or acoustic_codes.dim() != 3 or acoustic_codes.shape[1] != q:
+            raise _lib.QuarkAudioError(-1, f"{what} expects two [B,{q},G] code tensors")
+        ac = acoustic_codes.to(device=self.device, dtype=torch.int64).contiguous()
+        sc = semantic_codes.to(device=self.device, dtype=torch.int64).contiguous()
+        if token_lengths is not None:  # plain codes + explicit lengths: inject, exactly what encode emits
+            tl = token_lengths.to(device=self.device, dtype=torch.int64).unsqueeze(1)
+            ac, sc = (tl - 1) * K + ac, (tl - 1) * K + sc
+        return ac, sc
+
+    @torch.no_grad()
+    def adaptive_frames(self, semantic_codes: torch.Tensor):
+        """Code frames per clip of length-injected H-Codec 1.5 codes [B, nq, G]: the sum of the group lengths of every row, a list of B
+        ints (one host synchronisation)."""
+        if not self.spec.adaptive:
+            raise _lib.QuarkAudioError(-4, "adaptive_frames: this is not an H-Codec 1.5 model")
+        if semantic_codes.dim() != 3 or semantic_codes.shape[1] != self.spec.num_quantizers or semantic_codes.shape[2] < 1:
+            raise _lib.QuarkAudioError(-1, f"adaptive_frames expects [B,{self.spec.num_quantizers},G] codes, got {tuple(semantic_codes.shape)}")
+        self._require_loaded()
+        sc = semantic_codes.to(device=self.device, dtype=torch.int64).contiguous()
+        B, _, G = sc.shape
+        out = (C.c_int64 * B)()
+        _lib.check(self._lib.qa_hcodec_adaptive_clip_frames(self._handle, sc.data_ptr(), B, G, out, _stream_ptr(self.device)))
+        return [int(v) for v in out]
+
+    @torch.no_grad()
+    def decode_ragged(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths: Optional[torch.Tensor] = None, *,
+                      lengths=None):
+        """One decode of clips of unequal length.
+
+        H-Codec 1.5: length-injected codes [B, nq, G] (or plain codes + token_lengths [B, G]); the lengths ride in the codes, so
+        `lengths` stays None.  Row b equals `decode` of clip b alone (B = 1): its bottleneck transformer and decoder see its own frames
+        only.  Returns wav [B, max(frames) * 2 * hop], exactly zero behind every clip; a row whose codes hold no frame is an error.
+        H-Codec 1.0: `decode(acoustic_codes, semantic_codes, lengths=lengths)`."""
+        if not self.spec.adaptive:
+            if token_lengths is not None:
+                raise _lib.QuarkAudioError(-1, "decode_ragged: token_lengths belong to H-Codec 1.5 codes")
+            return self.decode(acoustic_codes, semantic_codes, lengths=lengths)
+        if lengths is not None:
+            raise _lib.QuarkAudioError(-1, "decode_ragged: H-Codec 1.5 codes carry their lengths (adaptive_frames), pass none")
+        q = self.spec.num_quantizers
+        if acoustic_codes.shape != semantic_codes.shape or acoustic_codes.dim() != 3 or acoustic_codes.shape[1] != q:
+            raise _lib.QuarkAudioError(-1, f"decode_ragged expects two [B,{q},G] code tensors")
+        self._require_loaded()
+        ac, sc = self._adaptive_codes(acoustic_codes, semantic_codes, token_lengths, "decode_ragged")
+        B, _, G = ac.shape
+        K = self.spec.codebook_size
+        pending = self._check_range_begin((ac, sc), K * self.spec.max_tokens_per_group, lo=-K)
+        per_clip = self.adaptive_frames(sc)
+        self._check_range_end(pending)  # behind the frame counts' synchronisation, before any decode work
+        for b, n in enumerate(per_clip):
+            if n < 1:
+                raise _lib.QuarkAudioError(-1, f"decode_ragged: frames[{b}] = {n}: the codes of row {b} hold no frame")
+        n = max(per_clip)
+        frames = (C.c_int64 * B)(*per_clip)
+        wav = torch.empty((B, n * 2 * self.spec.hop), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.qa_hcodec_decode_adaptive_ragged(self._handle, ac.data_ptr(), sc.data_ptr(), B, G, n, frames, wav.data_ptr(),
+                                                              _stream_ptr(self.device)))
+        return wav
+
     def enable_taps(self, on: bool = True):
         """Test hook: make encode/decode snapshot their named intermediates (see DESIGN.md "taps")."""
         self._require_loaded()
@@ -517,14 +617,8 @@ class Codec(torch.nn.Module):
         return self
 
     def _decode_adaptive(self, acoustic_codes, semantic_codes, token_lengths):
-        q, K = self.spec.num_quantizers, self.spec.codebook_size
-        if acoustic_codes.shape != semantic_codes.shape or acoustic_codes.dim() != 3 or acoustic_codes.shape[1] != q:
-            raise _lib.QuarkAudioError(-1, f"decode expects two [B,{q},G] code tensors")
-        ac = acoustic_codes.to(device=self.device, dtype=torch.int64).contiguous()
-        sc = semantic_codes.to(device=self.device, dtype=torch.int64).contiguous()
-        if token_lengths is not None:  # plain codes + explicit lengths: inject, exactly what encode emits (codec_adaptive.py:68-73)
-            tl = token_lengths.to(device=self.device, dtype=torch.int64).unsqueeze(1)
-            ac, sc = (tl - 1) * K + ac, (tl - 1) * K + sc
+        K = self.spec.codebook_size
+        ac, sc = self._adaptive_codes(acoustic_codes, semantic_codes, token_lengths, "decode")
         B, _, G = ac.shape
         # length-injected: code + (len - 1) * K with len in 0..max_tokens (len 0 = the padding groups of shorter clips: [-K, 0))
         pending = self._check_range_begin((ac, sc), K * self.spec.max_tokens_per_group, lo=-K)
@@ -691,7 +785,7 @@ class HCodecTokenizer(torch.nn.Module):
         return code_frames(lengths, self.hop_length)
 
     @torch.no_grad()
-    def _tokenize_ragged(self, wav: torch.Tensor, feats: Optional[torch.Tensor], lengths):
+    def _tokenize_ragged(self, wav: torch.Tensor, feats: Optional[torch.Tensor], lengths, threshold: float = 0.0):
         """tokenize with per-clip lengths in samples: wav [B, Tmax] holds clip b in wav[b, :lengths[b]].  Every clip is zero-padded to its
         own multiple of the hop, as pad_wav pads a clip alone; what lies behind that is never read."""
         hop = self.hop_length
@@ -730,15 +824,18 @@ class HCodecTokenizer(torch.nn.Module):
                 out[rows, : fpc * f] = part[:, : fpc * f].to(device=self.device, dtype=torch.float32)
             feats = out
         feats = feats.to(self.device).transpose(-2, -1)
+        if self.model.spec.adaptive:  # H-Codec 1.5: the dict of [B, nq, G] codes, -1 behind every clip's own groups
+            return self.model.encode_ragged(wav.unsqueeze(1), feats, frames, threshold=threshold)
         return self.model.encode(wav.unsqueeze(1), feats, lengths=frames)
 
     @torch.no_grad()
     def tokenize(self, wav: torch.Tensor, feats: Optional[torch.Tensor] = None, threshold: float = 0.0, lengths=None):
-        """lengths (non-causal H-Codec 1.0): the clips' lengths in SAMPLES (host list / tensor), wav [B, Tmax] with clip b in its first
-        lengths[b] samples.  Codes of clip b then equal tokenize of that clip alone; `code_frames(lengths)` gives the frames per clip,
-        entries behind them are -1.  feats, when given, are [B, t, d] with clip b's frames first."""
+        """lengths (non-causal H-Codec 1.0 / 1.5): the clips' lengths in SAMPLES (host list / tensor), wav [B, Tmax] with clip b in its
+        first lengths[b] samples.  Codes of clip b then equal tokenize of that clip alone; `code_frames(lengths)` gives the frames per
+        clip.  1.0: entries behind them are -1.  1.5: the dict of `Codec.encode_ragged`.  feats, when given, are [B, t, d] with clip b's
+        frames first."""
         if lengths is not None:
-            return self._tokenize_ragged(wav, feats, lengths)
+            return self._tokenize_ragged(wav, feats, lengths, threshold)
         wav = self.pad_wav(wav.to(self.device))
         if feats is None:
             feats = self.extract_wav2vec2_features(wav)  # (b, t, d)
@@ -748,9 +845,12 @@ class HCodecTokenizer(torch.nn.Module):
         return self.model.encode(wav.unsqueeze(1), feats)
 
     @torch.no_grad()
-    def detokenize(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths=None, lengths=None):
+    def detokenize(self, acoustic_codes: torch.Tensor, semantic_codes: torch.Tensor, token_lengths=None, lengths=None, ragged: bool = False):
         """1.0: audio_tokenizer.py:64-66; 1.5: HCodec-1.5/audio_tokenizer.py:83-86 (call as detokenize(**codes)).  lengths: the clips'
-        lengths in CODE frames (`code_frames`), passed on to `Codec.decode`."""
+        lengths in CODE frames (`code_frames`), passed on to `Codec.decode`.  ragged=True: `Codec.decode_ragged` - for H-Codec 1.5 codes
+        of `tokenize(..., lengths=...)`, whose lengths ride in the codes."""
+        if ragged:
+            return self.model.decode_ragged(acoustic_codes, semantic_codes, token_lengths, lengths=lengths)
         if lengths is not None:
             return self.model.decode(acoustic_codes, semantic_codes, lengths=lengths)
         if self.model.spec.adaptive:
