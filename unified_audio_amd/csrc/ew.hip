@@ -218,36 +218,45 @@ int launch_dwconv(const float* x, const float* w_kc, const float* bias, const fl
 
 // ------------------------------------------------------------------------------------------------
 // GroupNorm(G, C, eps) over [B, T, C] channel-last (vq/conv.py:259-260 "Normalize"), optional swish after it
-// (ResnetBlock.nonlinearity, vq/conv.py:303-304).  Two deterministic passes:
+// (ResnetBlock.nonlinearity, vq/conv.py:303-304).  Two deterministic passes, no atomics, a fixed fold order:
 //   1. gn_partial: grid (chunks, B); each block reduces `rows_per_chunk` frames: thread = one float4 channel
-//      column, fp32 running sum / sum of squares, then a group reduction in LDS -> partial[b][chunk][g][2] (double)
-//   2. gn_apply: every block first folds the partials of its batch item in a fixed order (LDS), then streams.
-constexpr int GN_ROWS = 64;
+//      column, running sum / sum of squares in DOUBLE, as ssl_conv0_kernel keeps them (a float squared is exact in
+//      double, so var = E[x^2] - mean^2 keeps 29 more bits than the data has when the group's mean is large against its
+//      deviation, as behind a swish; with fp32 sums a group at 100 +- 0.5 came out wrong by 4e-3), then a group
+//      reduction in LDS -> partial[b][chunk][g][2] (double)
+//   2. gn_apply: every block first folds the partials of its batch item in a fixed order (LDS), then streams.  The
+//      mean is kept as a float pair (hi + lo): x - hi is exact for x near the mean, so the fp32 rounding of a large
+//      mean does not enter the output either.
+// 32 frames per chunk: twice the workgroups of the 64-frame chunks this kernel had with fp32 sums, which more than pays for the double
+// arithmetic (profiles/groupnorm_offset_fix.md)
+constexpr int GN_ROWS = 32;
+constexpr int GN_MAX_C = 4096;  // gn_partial's LDS: 2 * C doubles
 
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x, double* __restrict__ partial,
                                                          int T, int C, int G, const int* __restrict__ lens, int len_mul) {
-    extern __shared__ float sh[];  // [2][C]
+    extern __shared__ double shd[];  // [2][C]
     const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
     const int len = lens ? min(lens[b] * len_mul, T) : T;  // ragged: a chunk behind the clip's end sums nothing and stores exact zeros
     const int t0 = chunk * GN_ROWS, t1 = min(len, t0 + GN_ROWS);
     const float* xb = x + (long long)b * T * C;
     for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
         for (int t = t0; t < t1; ++t) {
             const float4 v = *reinterpret_cast<const float4*>(xb + (long long)t * C + c);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            q.x = fmaf(v.x, v.x, q.x); q.y = fmaf(v.y, v.y, q.y); q.z = fmaf(v.z, v.z, q.z); q.w = fmaf(v.w, v.w, q.w);
+            const double a0 = v.x, a1 = v.y, a2 = v.z, a3 = v.w;
+            s0 += a0; s1 += a1; s2 += a2; s3 += a3;
+            q0 = fma(a0, a0, q0); q1 = fma(a1, a1, q1); q2 = fma(a2, a2, q2); q3 = fma(a3, a3, q3);
         }
-        sh[c] = s.x; sh[c + 1] = s.y; sh[c + 2] = s.z; sh[c + 3] = s.w;
-        sh[C + c] = q.x; sh[C + c + 1] = q.y; sh[C + c + 2] = q.z; sh[C + c + 3] = q.w;
+        shd[c] = s0; shd[c + 1] = s1; shd[c + 2] = s2; shd[c + 3] = s3;
+        shd[C + c] = q0; shd[C + c + 1] = q1; shd[C + c + 2] = q2; shd[C + c + 3] = q3;
     }
     __syncthreads();
     const int cpg = C / G;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
         double s = 0.0, q = 0.0;
         for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-            s += (double)sh[c];
-            q += (double)sh[C + c];
+            s += shd[c];
+            q += shd[C + c];
         }
         double* out = partial + (((long long)b * nchunk + chunk) * G + g) * 2;
         out[0] = s;
@@ -259,7 +268,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
                                                        const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ y, int T, int C, int G, int nchunk, float eps,
                                                        int swish, const int* __restrict__ lens, int len_mul) {
-    extern __shared__ float sh[];  // [2][G]: mean, rstd
+    extern __shared__ float sh[];  // [3][G]: mean (hi), mean (lo), rstd
     const int b = blockIdx.y;
     const int cpg = C / G;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
@@ -273,8 +282,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
         const double mean = s / n;
         double var = q / n - mean * mean;
         if (var < 0.0) var = 0.0;
-        sh[g] = (float)mean;
-        sh[G + g] = (float)(1.0 / sqrt(var + (double)eps));
+        const float hi = (float)mean;
+        sh[g] = hi;
+        sh[G + g] = (float)(mean - (double)hi);
+        sh[2 * G + g] = (float)(1.0 / sqrt(var + (double)eps));
     }
     __syncthreads();
     const int c4n = C >> 2;
@@ -286,12 +297,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
         const float4 v = *reinterpret_cast<const float4*>(xb + i * 4);
         const float4 ww = *reinterpret_cast<const float4*>(w + c);
         const float4 bv = *reinterpret_cast<const float4*>(bias + c);
-        float4 o;
         // channels c..c+3 may straddle groups only if cpg % 4 != 0 -> resolve per element
-        o.x = (v.x - sh[(c + 0) / cpg]) * sh[G + (c + 0) / cpg] * ww.x + bv.x;
-        o.y = (v.y - sh[(c + 1) / cpg]) * sh[G + (c + 1) / cpg] * ww.y + bv.y;
-        o.z = (v.z - sh[(c + 2) / cpg]) * sh[G + (c + 2) / cpg] * ww.z + bv.z;
-        o.w = (v.w - sh[(c + 3) / cpg]) * sh[G + (c + 3) / cpg] * ww.w + bv.w;
+        const int g0 = (c + 0) / cpg, g1 = (c + 1) / cpg, g2 = (c + 2) / cpg, g3 = (c + 3) / cpg;
+        float4 o;
+        o.x = ((v.x - sh[g0]) - sh[G + g0]) * sh[2 * G + g0] * ww.x + bv.x;
+        o.y = ((v.y - sh[g1]) - sh[G + g1]) * sh[2 * G + g1] * ww.y + bv.y;
+        o.z = ((v.z - sh[g2]) - sh[G + g2]) * sh[2 * G + g2] * ww.z + bv.z;
+        o.w = ((v.w - sh[g3]) - sh[G + g3]) * sh[2 * G + g3] * ww.w + bv.w;
         if (swish) {
             o.x = silu_f(o.x); o.y = silu_f(o.y); o.z = silu_f(o.z); o.w = silu_f(o.w);
         }
@@ -303,14 +315,14 @@ size_t groupnorm_scratch_bytes(int B, int T, int G) { return (size_t)B * ceil_di
 
 int launch_groupnorm(const float* x, const float* w, const float* bias, float* y, double* scratch, int B, int T, int C,
                      int G, float eps, int swish, hipStream_t s, ClipLens rl) {
-    QA_REQUIRE(C % 4 == 0 && C % G == 0, "groupnorm: C=%d G=%d unsupported", C, G);
+    QA_REQUIRE(C % 4 == 0 && C <= GN_MAX_C && G >= 1 && C % G == 0, "groupnorm: C=%d G=%d unsupported", C, G);
     const int nchunk = (int)ceil_div(T, GN_ROWS);
     HbmProf prof_(HK_GROUPNORM, 8.0 * (double)B * T * C, s);  // algorithmic: x once in, y once out (the two-pass form reads x twice)
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 2 * C * sizeof(float), s, x, scratch, T, C, G, rl.n, rl.mul);
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 2 * C * sizeof(double), s, x, scratch, T, C, G, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     const long long n4 = (long long)T * (C / 4);
     const unsigned gx = (unsigned)std::min<long long>(ceil_div(n4, 256), 64);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(gx, B), dim3(256), 2 * G * sizeof(float), s, x, scratch, w, bias, y, T, C,
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(gx, B), dim3(256), 3 * G * sizeof(float), s, x, scratch, w, bias, y, T, C,
                        G, nchunk, eps, swish, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     return QA_OK;
@@ -957,3 +969,45 @@ int launch_ring_append(const float* k, const float* v, long long ld, float* kc, 
 }
 
 }  // namespace qa
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (not part of the public header): the float kernels above alone on caller-provided device buffers, one launcher call each
+// (tests/test_ew_kernels_gpu.py).  lens: device int32 [B] or null, with len_mul the ClipLens of the launchers.
+extern "C" int qa_debug_rownorm(int mode, const float* x, const float* w, const float* b, float* y, long long rows, int C, float eps,
+                                void* stream) {
+    return mode == 0 ? qa::launch_rmsnorm(x, w, y, rows, C, eps, static_cast<hipStream_t>(stream))
+                     : qa::launch_layernorm(x, w, b, y, rows, C, eps, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_dwconv(const float* x, const float* w_kc, const float* bias, const float* lnw, const float* lnb, float* y, int B,
+                               int T, int C, int ksize, float eps, int pad_left, const int* lens, int len_mul, void* stream) {
+    return qa::launch_dwconv(x, w_kc, bias, lnw, lnb, y, B, T, C, ksize, eps, static_cast<hipStream_t>(stream), pad_left,
+                             qa::ClipLens{lens, len_mul});
+}
+extern "C" long long qa_debug_groupnorm_scratch_bytes(int B, int T, int G) { return (long long)qa::groupnorm_scratch_bytes(B, T, G); }
+extern "C" int qa_debug_groupnorm(const float* x, const float* w, const float* bias, float* y, void* scratch, int B, int T, int C, int G,
+                                  float eps, int swish, const int* lens, int len_mul, void* stream) {
+    return qa::launch_groupnorm(x, w, bias, y, static_cast<double*>(scratch), B, T, C, G, eps, swish, static_cast<hipStream_t>(stream),
+                                qa::ClipLens{lens, len_mul});
+}
+extern "C" int qa_debug_conv_in(const float* x, const float* w_kc, const float* bias, float* y, int B, int T, int Cout, int ksize,
+                                int pad_left, const int* lens, int len_mul, void* stream) {
+    return qa::launch_conv_in(x, w_kc, bias, y, B, T, Cout, ksize, static_cast<hipStream_t>(stream), pad_left, qa::ClipLens{lens, len_mul});
+}
+extern "C" int qa_debug_rope(float* qkv, const float* cos_sin, int B, int N, int H, int hd, long long ld, int pos0, int interleaved,
+                             int rot_heads, void* stream) {
+    return qa::launch_rope(qkv, cos_sin, B, N, H, hd, ld, pos0, static_cast<hipStream_t>(stream), interleaved, rot_heads);
+}
+extern "C" int qa_debug_istft_spec(const float* y, float* S, long long rows, int nb, int ldy, int ldS, void* stream) {
+    return qa::launch_istft_spec(y, S, rows, nb, ldy, ldS, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_stft_post(const float* ri, float* out, long long rows, int nb, int ldi, int ldo, void* stream) {
+    return qa::launch_stft_post(ri, out, rows, nb, ldi, ldo, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_istft_ola(const float* frames, const float* win, float* out, int B, int T, int n_fft, int hop, const int* lens,
+                                  int len_mul, void* stream) {
+    return qa::launch_istft_ola(frames, win, out, B, T, n_fft, hop, static_cast<hipStream_t>(stream), qa::ClipLens{lens, len_mul});
+}
+extern "C" int qa_debug_to_channel_last(const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T,
+                                        void* stream) {
+    return qa::launch_to_channel_last(x, sb, sc, st, y, B, C, T, static_cast<hipStream_t>(stream));
+}
