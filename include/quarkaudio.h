@@ -461,6 +461,14 @@ int64_t qa_bicodec_hop(const qa_bicodec* h);
  * with qa_codes_check where the reference's F.embedding would raise. */
 int qa_bicodec_detokenize(qa_bicodec* h, const int64_t* semantic_tokens, const int64_t* global_tokens, int64_t B, int64_t T,
                           float* wav_out, void* stream);
+/* Per-clip lengths in one call: clip b behaves as qa_bicodec_detokenize would for it alone at its own length.
+ * lengths: HOST memory, int64 [B], the clips' lengths in TOKENS, 1 .. T each, read during the call (the caller may free it on return)
+ * and checked before anything is launched (QA_ERR_INVALID names the row and its value).  Entries of semantic_tokens at or behind
+ * lengths[b] are ignored, whatever they hold (-1 included): they are never read.  wav_out fp32 [B, T * hop]: wav_out[b] is exactly 0
+ * from sample lengths[b] * hop on.  global_tokens have no length.  A call whose lengths all equal T is the rectangular call, through the
+ * same launches. */
+int qa_bicodec_detokenize_ragged(qa_bicodec* h, const int64_t* semantic_tokens, const int64_t* global_tokens, int64_t B, int64_t T,
+                                 const int64_t* lengths, float* wav_out, void* stream);
 /* test hooks, as qa_hcodec_enable_taps / qa_hcodec_tap: z_q, d_vector, prenet.down, prenet.backbone, prenet.out, gen.block{i} */
 int qa_bicodec_enable_taps(qa_bicodec* h, int on);
 int64_t qa_bicodec_tap(qa_bicodec* h, const char* name, float* dst, int64_t cap, void* stream);
@@ -516,6 +524,24 @@ int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B,
 /* BiCodec.tokenize(batch) (bicodec.py:151-165): both of the above on one stream */
 int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref, int64_t ref_len,
                         int64_t* semantic_out, int32_t* global_out, void* stream);
+/* Per-clip lengths in one call: row b behaves as the rectangular call above would for that clip alone at its own
+ * length.  Every length vector is HOST memory, int64 [B], read during the call (the caller may free it on return) and checked before
+ * anything is launched (QA_ERR_INVALID names the entry point, the row and its value); a vector whose entries all equal the full extent
+ * makes the rectangular call, through the same launches.
+ *   get_semantic_tokens_ragged: frame_lengths in FEATURE FRAMES, 1 .. N each.  Rows of feat at or behind frame_lengths[b] are padding
+ *       that is never read (NaN there changes nothing); semantic_out[b, n] = -1 for n >= frame_lengths[b].
+ *   get_global_tokens_ragged: lengths in SAMPLES, 1 .. T each.  The reference clip of row b is wav[b, k % lengths[b]] for k < ref_len:
+ *       get_ref_clip on the clip alone; samples at or behind lengths[b] are never read.  ref_len must be positive unless every length is T.
+ *   tokenize_ragged: both of the above on one stream, every check of both in front of the first launch.  The two vectors count
+ *       different things: frame_lengths the rows of feat, lengths the samples of ref_wav (the front-end's frame rule relates them,
+ *       qa_ssl_frames). */
+int qa_bicodec_get_semantic_tokens_ragged(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const int64_t* frame_lengths,
+                                          int64_t* semantic_out, void* stream);
+int qa_bicodec_get_global_tokens_ragged(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, const int64_t* lengths, int64_t ref_len,
+                                        int32_t* global_out, void* stream);
+int qa_bicodec_tokenize_ragged(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const int64_t* frame_lengths, const float* ref_wav,
+                               int64_t T_ref, const int64_t* lengths, int64_t ref_len, int64_t* semantic_out, int32_t* global_out,
+                               void* stream);
 /* test hooks: enc.backbone (input backbone), enc.down (after the SamplingBlock stages), enc.out [B, N, latent_dim],
  * vq.latent [B * N, codebook_dim] (in_project output after F.normalize); mel [B, frames, mel_dim], ecapa.layer1 [B, frames, C],
  * ecapa.layers234 [B, frames, 3 C] (the concatenation of the three SE-Res2 block outputs), ecapa.latent [B, frames, 1536],
@@ -525,6 +551,11 @@ int64_t qa_bicodec_enc_tap(qa_bicodec_enc* h, const char* name, float* dst, int6
 /* Wav2Vec2FeatureExtractor(do_normalize=True) on equal-length rows (audio_tokenizer.py:74-90, nothing padded):
  * out[b, :] = (wav[b, :] - mean) / sqrt(var + eps) with the population variance; eps = 1e-7 in the reference.  out may alias wav. */
 int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float eps, void* stream);
+/* Rows of unequal length: lengths is HOST memory, int64 [B], in SAMPLES, 1 .. T each, read during the call and
+ * checked before anything is launched (QA_ERR_INVALID names the row and its value).  out[b, :lengths[b]] is the row above of
+ * wav[b, :lengths[b]] alone - mean and variance over the clip's own samples, summed in the order qa_wav_normalize sums a [1, lengths[b]]
+ * row - and out[b, lengths[b]:] is exactly 0; samples at or behind lengths[b] are never read.  out may alias wav. */
+int qa_wav_normalize_ragged(const float* wav, int64_t B, int64_t T, const int64_t* lengths, float* out, float eps, void* stream);
 
 /* ---- BiCodec.forward (QuarkAudio-UniSE/model/bicodec/bicodec.py:113-149, eval mode) ----------------------------------------------
  * Needs both handles: the tokenizer (qa_bicodec_enc, which owns the ECAPA latent the x-vector head pools) and the detokenizer

@@ -194,6 +194,8 @@ SYMBOLS = {
     "qa_bicodec_destroy": (None, [C.c_void_p]),
     "qa_bicodec_hop": (C.c_int64, [C.c_void_p]),
     "qa_bicodec_detokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_bicodec_detokenize_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
+                                               C.c_void_p]),
     "qa_bicodec_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "qa_bicodec_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "qa_bicodec_enc_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_bicodec_enc_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
@@ -202,9 +204,16 @@ SYMBOLS = {
     "qa_bicodec_get_global_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "qa_bicodec_tokenize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "qa_bicodec_get_semantic_tokens_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
+                                                        C.c_void_p]),
+    "qa_bicodec_get_global_tokens_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                                      C.c_void_p, C.c_void_p]),
+    "qa_bicodec_tokenize_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                             C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_bicodec_enc_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "qa_bicodec_enc_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "qa_wav_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_void_p]),
+    "qa_wav_normalize_ragged": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_float, C.c_void_p]),
     "qa_bicodec_load_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(qa_bicodec_forward_spec), C.POINTER(qa_tensor), C.c_int64]),
     "qa_bicodec_has_forward": (C.c_int, [C.c_void_p, C.c_void_p]),
     "qa_code_usage": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -322,19 +322,41 @@ class BiCodecForwardSpec:
 ENCODER_KEY = "encoder.encoder.embed.weight"
 
 
+def clip_lengths(lengths, B: int, lo: int, hi: int, what: str, hi_name: str = "T"):
+    """The length vector of a per-clip call as a host int64 array: B entries (list / tuple / tensor), each in
+    lo .. hi.  Checked here, before anything is launched, in the words of the library's own check (QuarkAudioError -1 names the row and
+    its value); the C entry points check again for callers of the C-ABI."""
+    lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lens) != B:
+        raise _lib.QuarkAudioError(-1, f"{what}: lengths has {len(lens)} entries for a batch of B = {B}")
+    for b, v in enumerate(lens):
+        if not lo <= v <= hi:
+            raise _lib.QuarkAudioError(-1, f"{what}: lengths[{b}] = {v} is outside {lo} .. {hi_name} = {hi}")
+    return lens, (C.c_int64 * B)(*lens)
+
+
 @torch.no_grad()
-def wav_normalize(wav: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
+def wav_normalize(wav: torch.Tensor, eps: float = 1e-7, lengths=None) -> torch.Tensor:
     """Wav2Vec2FeatureExtractor(do_normalize=True) on equal-length rows (audio_tokenizer.py:74-90, padding=True pads nothing):
-    wav [B, T] (or [T]) on the GPU -> (wav - mean) / sqrt(var + eps) per row, fp32, on the same device."""
+    wav [B, T] (or [T]) on the GPU -> (wav - mean) / sqrt(var + eps) per row, fp32, on the same device.
+
+    lengths: the rows' lengths in SAMPLES (host list / tensor, B entries, 1 .. T).  Row b is then normalised
+    over its own lengths[b] samples, exactly as the clip alone would be, and is exactly 0 behind them; what wav holds there is never
+    read.  None: every row has T samples."""
     if wav.dim() not in (1, 2) or wav.shape[-1] == 0:
         raise _lib.QuarkAudioError(-1, f"wav must be [B, T] or [T] with T > 0, got {tuple(wav.shape)}")
     if wav.device.type != "cuda":
         raise _lib.QuarkAudioError(-1, "wav_normalize runs on the GPU: move wav to a HIP device first")
     x = wav.to(torch.float32).contiguous()
-    out = torch.empty_like(x)
     B, T = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    arr = None if lengths is None else clip_lengths(lengths, B, 1, T, "wav_normalize")[1]
+    out = torch.empty_like(x)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    _lib.check(_lib.load_library().qa_wav_normalize(x.data_ptr(), B, T, out.data_ptr(), float(eps), stream))
+    lib = _lib.load_library()
+    if arr is None:
+        _lib.check(lib.qa_wav_normalize(x.data_ptr(), B, T, out.data_ptr(), float(eps), stream))
+    else:
+        _lib.check(lib.qa_wav_normalize_ragged(x.data_ptr(), B, T, arr, out.data_ptr(), float(eps), stream))
     return out
 
 
@@ -489,8 +511,13 @@ class BiCodec(torch.nn.Module):
         return self
 
     @torch.no_grad()
-    def detokenize(self, semantic_tokens: torch.Tensor, global_tokens: torch.Tensor) -> torch.Tensor:
-        """semantic_tokens [B, T] int64, global_tokens [B, 1, token_num] (or [B, token_num]) int64 -> wav [B, 1, T * hop] float32."""
+    def detokenize(self, semantic_tokens: torch.Tensor, global_tokens: torch.Tensor, lengths=None) -> torch.Tensor:
+        """semantic_tokens [B, T] int64, global_tokens [B, 1, token_num] (or [B, token_num]) int64 -> wav [B, 1, T * hop] float32.
+
+        lengths: the clips' lengths in TOKENS (host list / tensor, B entries, 1 .. T).  Row b is then the
+        waveform of semantic_tokens[b, :lengths[b]] alone in its first lengths[b] * hop samples and exactly 0 behind them; entries at
+        or behind lengths[b] are ignored, whatever they hold (-1 included), and the range check masks them.  None: the rectangular
+        call."""
         if not self._handle.value:
             raise _lib.QuarkAudioError(-3, "BiCodec has no weights: call load_state_dict first")
         sem = semantic_tokens.to(device=self.device, dtype=torch.int64).contiguous()
@@ -501,18 +528,28 @@ class BiCodec(torch.nn.Module):
         glob = glob.reshape(B, -1)
         if glob.shape[1] != self.spec.token_num:
             raise _lib.QuarkAudioError(-1, f"global_tokens must hold {self.spec.token_num} tokens per item, got {tuple(global_tokens.shape)}")
+        lens = arr = None
+        if lengths is not None:  # checked before anything is launched
+            lens, arr = clip_lengths(lengths, B, 1, T, "BiCodec.detokenize")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if self.check_tokens:  # F.embedding / the implicit FSQ codebook gather would refuse out-of-range ids: ONE check (one host
             # sync) for both tensors - the global ids are scaled onto the semantic range so that a single limit serves
             lim_s, lim_g = self.spec.codebook_size, self.spec.global_size
-            both = torch.cat([sem.reshape(-1), torch.where((glob >= 0) & (glob < lim_g), 0, lim_s).reshape(-1)])
+            live = sem
+            if lens is not None:  # entries behind a clip's end count as valid, as Codec.decode(lengths=...) masks them
+                keep = torch.arange(T, device=self.device).unsqueeze(0) < torch.tensor(lens, device=self.device).unsqueeze(1)
+                live = torch.where(keep, sem, 0)
+            both = torch.cat([live.reshape(-1), torch.where((glob >= 0) & (glob < lim_g), 0, lim_s).reshape(-1)])
             bad = C.c_int64(0)
             _lib.check(self._lib.qa_codes_check(both.data_ptr(), both.numel(), lim_s, C.byref(bad), stream))
             if bad.value:
                 n_g = int(((glob < 0) | (glob >= lim_g)).sum())
                 raise IndexError(f"{bad.value - n_g} semantic_tokens out of range [0, {lim_s}), {n_g} global_tokens out of range [0, {lim_g})")
         wav = torch.empty((B, 1, T * self.spec.hop), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.qa_bicodec_detokenize(self._handle, sem.data_ptr(), glob.data_ptr(), B, T, wav.data_ptr(), stream))
+        if arr is None:
+            _lib.check(self._lib.qa_bicodec_detokenize(self._handle, sem.data_ptr(), glob.data_ptr(), B, T, wav.data_ptr(), stream))
+        else:
+            _lib.check(self._lib.qa_bicodec_detokenize_ragged(self._handle, sem.data_ptr(), glob.data_ptr(), B, T, arr, wav.data_ptr(), stream))
         return wav
 
     @property
@@ -524,39 +561,82 @@ class BiCodec(torch.nn.Module):
             raise _lib.QuarkAudioError(-3, f"BiCodec has no tokenizer: the state dict held no {ENCODER_KEY} (a detokenize-only checkpoint); "
                                            "tokenize needs the encoder.*, quantizer.in_project.* and speaker_encoder.* weights")
 
-    @torch.no_grad()
-    def get_semantic_tokens(self, batch: Mapping[str, torch.Tensor]) -> torch.Tensor:
-        """bicodec.py:167-172: batch["feat"] [B, N, input_channels] (the XLSR-53 hidden-state mix) -> semantic tokens int64 [B, N]."""
+    def _feat(self, batch):
         self._require_tokenizer()
         feat = batch["feat"]
         if feat.dim() != 3 or feat.shape[2] != self.encoder_spec.input_channels or feat.shape[1] == 0:
             raise _lib.QuarkAudioError(-1, f"feat must be [B, N, {self.encoder_spec.input_channels}] with N > 0, got {tuple(feat.shape)}")
-        feat = feat.to(device=self.device, dtype=torch.float32).contiguous()
-        B, N, _ = feat.shape
-        out = torch.empty((B, N), dtype=torch.int64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.qa_bicodec_get_semantic_tokens(self._enc, feat.data_ptr(), B, N, out.data_ptr(), stream))
-        return out
+        return feat.to(device=self.device, dtype=torch.float32).contiguous()
 
-    @torch.no_grad()
-    def get_global_tokens(self, batch: Mapping[str, torch.Tensor], ref_len: int = 0) -> torch.Tensor:
-        """bicodec.py:174-178: batch["ref_wav"] [B, T] -> global tokens int32 [B, 1, token_num].  ref_len > 0 takes the mel spectrogram of
-        BiCodecTokenizer.get_ref_clip(ref_wav) of that length (tile a short row, truncate a long one) without materialising the clip."""
+    def _ref_wav(self, batch):
         self._require_tokenizer()
         wav = batch["ref_wav"]
         if wav.dim() != 2 or wav.shape[1] == 0:
             raise _lib.QuarkAudioError(-1, f"ref_wav must be [B, T], got {tuple(wav.shape)}")
-        wav = wav.to(device=self.device, dtype=torch.float32).contiguous()
-        B, T = wav.shape
-        out = torch.empty((B, 1, self.encoder_spec.token_num), dtype=torch.int32, device=self.device)
+        return wav.to(device=self.device, dtype=torch.float32).contiguous()
+
+    @torch.no_grad()
+    def get_semantic_tokens(self, batch: Mapping[str, torch.Tensor], lengths=None) -> torch.Tensor:
+        """bicodec.py:167-172: batch["feat"] [B, N, input_channels] (the XLSR-53 hidden-state mix) -> semantic tokens int64 [B, N].
+
+        lengths: the clips' lengths in FEATURE FRAMES (host list / tensor, B entries, 1 .. N).  Row b then holds
+        the tokens of feat[b, :lengths[b]] alone and -1 behind them; rows of feat behind a clip's end are never read."""
+        feat = self._feat(batch)
+        B, N, _ = feat.shape
+        arr = None if lengths is None else clip_lengths(lengths, B, 1, N, "BiCodec.get_semantic_tokens", "N")[1]
+        out = torch.empty((B, N), dtype=torch.int64, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.qa_bicodec_get_global_tokens(self._enc, wav.data_ptr(), B, T, int(ref_len), out.data_ptr(), stream))
+        if arr is None:
+            _lib.check(self._lib.qa_bicodec_get_semantic_tokens(self._enc, feat.data_ptr(), B, N, out.data_ptr(), stream))
+        else:
+            _lib.check(self._lib.qa_bicodec_get_semantic_tokens_ragged(self._enc, feat.data_ptr(), B, N, arr, out.data_ptr(), stream))
         return out
 
     @torch.no_grad()
-    def tokenize(self, batch: Mapping[str, torch.Tensor], ref_len: int = 0):
-        """bicodec.py:151-165: (semantic_tokens int64 [B, N], global_tokens int32 [B, 1, token_num])."""
-        return self.get_semantic_tokens(batch), self.get_global_tokens(batch, ref_len)
+    def get_global_tokens(self, batch: Mapping[str, torch.Tensor], ref_len: int = 0, lengths=None) -> torch.Tensor:
+        """bicodec.py:174-178: batch["ref_wav"] [B, T] -> global tokens int32 [B, 1, token_num].  ref_len > 0 takes the mel spectrogram of
+        BiCodecTokenizer.get_ref_clip(ref_wav) of that length (tile a short row, truncate a long one) without materialising the clip.
+
+        lengths: the clips' lengths in SAMPLES (host list / tensor, B entries, 1 .. T); needs ref_len > 0.  The
+        reference clip of row b is then get_ref_clip(ref_wav[b, :lengths[b]]): it tiles by its own length, and samples behind it are
+        never read."""
+        wav = self._ref_wav(batch)
+        B, T = wav.shape
+        arr = None if lengths is None else clip_lengths(lengths, B, 1, T, "BiCodec.get_global_tokens")[1]
+        out = torch.empty((B, 1, self.encoder_spec.token_num), dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if arr is None:
+            _lib.check(self._lib.qa_bicodec_get_global_tokens(self._enc, wav.data_ptr(), B, T, int(ref_len), out.data_ptr(), stream))
+        else:
+            _lib.check(self._lib.qa_bicodec_get_global_tokens_ragged(self._enc, wav.data_ptr(), B, T, arr, int(ref_len), out.data_ptr(), stream))
+        return out
+
+    @torch.no_grad()
+    def tokenize(self, batch: Mapping[str, torch.Tensor], ref_len: int = 0, lengths=None, frame_lengths=None):
+        """bicodec.py:151-165: (semantic_tokens int64 [B, N], global_tokens int32 [B, 1, token_num]).
+
+        Per-clip calls pass both vectors: `lengths`, the clips' samples in batch["ref_wav"] (as
+        get_global_tokens), and `frame_lengths`, their frames in batch["feat"] (as get_semantic_tokens) - the front-end's frame rule
+        relates the two (SSLFeatureExtractor.frames, BiCodecTokenizer.token_frames).  Both are checked before anything is launched,
+        and the call is ONE library call."""
+        if lengths is None and frame_lengths is None:
+            return self.get_semantic_tokens(batch), self.get_global_tokens(batch, ref_len)
+        if lengths is None or frame_lengths is None:
+            raise _lib.QuarkAudioError(-1, "BiCodec.tokenize: a per-clip call needs lengths (samples of ref_wav) and frame_lengths (frames of "
+                                           "feat) together")
+        feat, wav = self._feat(batch), self._ref_wav(batch)
+        B, N, _ = feat.shape
+        if wav.shape[0] != B:
+            raise _lib.QuarkAudioError(-1, f"ref_wav must be [B, T] with B = {B}, got {tuple(wav.shape)}")
+        T = wav.shape[1]
+        sarr = clip_lengths(lengths, B, 1, T, "BiCodec.tokenize")[1]
+        farr = clip_lengths(frame_lengths, B, 1, N, "BiCodec.tokenize: frame_lengths", "N")[1]
+        sem = torch.empty((B, N), dtype=torch.int64, device=self.device)
+        glob = torch.empty((B, 1, self.encoder_spec.token_num), dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.qa_bicodec_tokenize_ragged(self._enc, feat.data_ptr(), B, N, farr, wav.data_ptr(), T, sarr, int(ref_len),
+                                                        sem.data_ptr(), glob.data_ptr(), stream))
+        return sem, glob
 
     def enable_taps(self, on: bool = True):
         _lib.check(self._lib.qa_bicodec_enable_taps(self._handle, int(on)))
@@ -621,8 +701,15 @@ class BiCodecTokenizer(torch.nn.Module):
         self.device = model.device
 
     @torch.no_grad()
-    def detokenize(self, global_tokens: torch.Tensor, semantic_tokens: torch.Tensor) -> torch.Tensor:
-        return self.model.detokenize(semantic_tokens, global_tokens)
+    def detokenize(self, global_tokens: torch.Tensor, semantic_tokens: torch.Tensor, lengths=None) -> torch.Tensor:
+        """lengths: the clips' lengths in TOKENS (`token_frames(sample_lengths)` for the output of `tokenize(wav, lengths=...)`), as
+        BiCodec.detokenize takes them."""
+        return self.model.detokenize(semantic_tokens, global_tokens, lengths=lengths)
+
+    def token_frames(self, sample_lengths):
+        """Semantic tokens per clip for clips of these many samples: the XLSR-53 front-end's frame rule (floor), clip by clip."""
+        fx = self.feature_extractor
+        return [fx.frames(int(n)) for n in (sample_lengths.tolist() if torch.is_tensor(sample_lengths) else sample_lengths)]
 
     @staticmethod
     def _check_extractor(fx):
@@ -659,15 +746,19 @@ class BiCodecTokenizer(torch.nn.Module):
         return self._feature_extractor
 
     @torch.no_grad()
-    def extract_wav2vec2_features(self, wavs: torch.Tensor) -> torch.Tensor:
-        """audio_tokenizer.py:74-90: wavs [B, T] -> (hidden_states[11] + [14] + [16]) / 3 of the normalised rows, [B, N, 1024]."""
+    def extract_wav2vec2_features(self, wavs: torch.Tensor, lengths=None) -> torch.Tensor:
+        """audio_tokenizer.py:74-90: wavs [B, T] -> (hidden_states[11] + [14] + [16]) / 3 of the normalised rows, [B, N, 1024].
+        lengths (samples, 400 .. T each): every row normalised over, and its features taken of, its own samples; one front-end call."""
         wavs = wavs.to(device=self.device, dtype=torch.float32)
         if wavs.dim() == 1:
             wavs = wavs.unsqueeze(0)
         fx = self.feature_extractor
         if wavs.dim() != 2 or wavs.shape[-1] < 400:  # the 10-sample / stride-5 conv stack needs 400 samples for one frame
             raise _lib.QuarkAudioError(-1, f"wav must be [B, T] with T >= 400 samples (one XLSR-53 frame at 16 kHz), got {tuple(wavs.shape)}")
-        return fx(wav_normalize(wavs))
+        if lengths is None:
+            return fx(wav_normalize(wavs))
+        lens = clip_lengths(lengths, wavs.shape[0], 400, wavs.shape[1], "BiCodecTokenizer")[0]
+        return fx(wav_normalize(wavs, lengths=lens), lengths=lens)
 
     @property
     def ref_segment_length(self) -> int:
@@ -684,12 +775,23 @@ class BiCodecTokenizer(torch.nn.Module):
         return self.model.get_semantic_tokens({"feat": self.extract_wav2vec2_features(wavs)})
 
     @torch.no_grad()
-    def tokenize(self, wav: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def tokenize(self, wav: torch.Tensor, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """audio_tokenizer.py:93-103: wav [B, T] -> (global_tokens int32 [B, 1, token_num], semantic_tokens int64 [B, N]).  The reference
-        clip (get_ref_clip) is formed inside the mel kernel."""
+        clip (get_ref_clip) is formed inside the mel kernel.
+
+        lengths: the clips' lengths in SAMPLES (host list / tensor, B entries, 400 .. T), clip b in
+        wav[b, :lengths[b]].  Row b then holds what tokenize(wav[b:b+1, :lengths[b]]) returns - its own normalisation, its own
+        features, its own reference clip - in the first token_frames(lengths)[b] semantic tokens, and -1 behind them.  One
+        normalisation, one front-end call, one codec call; what wav holds behind a clip's end is never read."""
         wav = wav.to(device=self.device, dtype=torch.float32)
         if wav.dim() == 1:
             wav = wav.unsqueeze(0)
-        feat = self.extract_wav2vec2_features(wav)
-        semantic, global_tokens = self.model.tokenize({"feat": feat, "ref_wav": wav, "wav": wav}, ref_len=self.ref_segment_length)
+        if lengths is None:
+            feat = self.extract_wav2vec2_features(wav)
+            semantic, global_tokens = self.model.tokenize({"feat": feat, "ref_wav": wav, "wav": wav}, ref_len=self.ref_segment_length)
+            return global_tokens, semantic
+        feat = self.extract_wav2vec2_features(wav, lengths=lengths)  # checks the lengths before anything is launched
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        semantic, global_tokens = self.model.tokenize({"feat": feat, "ref_wav": wav, "wav": wav}, ref_len=self.ref_segment_length,
+                                                      lengths=lens, frame_lengths=self.token_frames(lens))
         return global_tokens, semantic

@@ -17,11 +17,40 @@
 // Layout: channel-last [B, frames, C] everywhere; weights arrive with the reference's state_dict keys (weight_g / weight_v folded here).
 #include <memory>
 
+#include "clip_lengths.h"
 #include "host_util.h"
 
 using namespace qa;
 
 namespace {
+
+// The lengths of a per-clip call on their way to the kernels: a handle-owned device array of `slots` vectors of
+// up to `cap` clips, written on the call's stream by row_lens_kernel with the values riding in its arguments.
+struct LensDev {
+    int* dev = nullptr;
+    int cap = 0;
+    LensDev() = default;
+    LensDev(const LensDev&) = delete;
+    LensDev& operator=(const LensDev&) = delete;
+    ~LensDev() {
+        if (dev) (void)hipFree(dev);
+    }
+    // *out = the device copy of len [B] in slot `slot` of `slots`
+    int upload(const std::vector<int>& len, int slot, int slots, hipStream_t stream, const int** out) {
+        const int B = (int)len.size();
+        if (B > cap) {
+            if (dev) QA_HIP(hipFree(dev));  // waits for the work that still reads it
+            dev = nullptr;
+            cap = 0;
+            const int grown = (int)round_up(B, 256);
+            QA_HIP(hipMalloc(reinterpret_cast<void**>(&dev), sizeof(int) * (size_t)grown * slots));
+            cap = grown;
+        }
+        QA_TRY(launch_row_lens(dev + (size_t)slot * cap, len.data(), B, stream));
+        *out = dev + (size_t)slot * cap;
+        return QA_OK;
+    }
+};
 
 struct VocosLayerW {
     const float *dw = nullptr, *dwb = nullptr, *lnw = nullptr, *lnb = nullptr, *gamma = nullptr;  // lnw == nullptr: AdaLN
@@ -63,6 +92,7 @@ struct qa_bicodec : Handle {
         VocosW down[2], backbone;
     };
     std::unique_ptr<Postnet> post;
+    LensDev lens;  // qa_bicodec_detokenize_ragged: the clips' token counts
 };
 
 // Conv1dReluBn (ecapa_tdnn.py): the convolution with BN(ReLU(.)) as the epilogue  relu(acc + b) * s + t
@@ -102,6 +132,7 @@ struct qa_bicodec_enc : Handle {
         const float *bn_s = nullptr, *bn_t = nullptr;  // BatchNorm1d(3072) in eval as y = v * s + t
     };
     std::unique_ptr<XvecHead> xvec;
+    LensDev lens;  // the _ragged entry points: slot 0 the clips' feature frames, slot 1 their samples
 };
 
 namespace {
@@ -270,11 +301,13 @@ int linear_per_item(Ctx& c, const float* x, int64_t rows, const ConvW& w, float*
 // VocosBackbone.forward (blocks/vocos.py:323-335) in place on x [B, T, C]; t1 [rows, C], u [rows, I] scratch.
 // cond: AdaLN scale / shift rows of this backbone ([B, n_ada * 2 * C], entry a at offset a * 2 * C), or nullptr for plain LayerNorm.
 // in: the embed convolution reads [B, T, embed.C_in] from here instead of x (the encoder's 1024 -> 384 input backbone)
-int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, int C, const float* cond, int64_t ld_cond,
+// rl: the clips' lengths in frames of a per-clip call - the k7 embed and the depthwise k7 of every layer pad with zeros from a clip's own
+// end; LayerNorm, AdaLN and the pointwise linears are row-wise
+int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, int C, const float* cond, int64_t ld_cond, ClipLens rl,
           const float* in = nullptr) {
     const int64_t rows = (int64_t)B * T;
     ConvOpt same7;
-    same7.pad_left = 3; same7.pad_right = 3;
+    same7.pad_left = 3; same7.pad_right = 3; same7.rl = rl;
     QA_TRY(conv_op(c, in ? in : x, in ? v.embed.C_in : C, B, T, v.embed, t1, C, T, same7));
     if (cond) QA_RUN(c, launch_adaln(t1, cond, cond + C, ld_cond, x, B, T, C, 1e-6f, c.stream));
     else QA_TRY(layernorm_op(c, t1, v.nw, v.nb, x, rows, C, 1e-6f));
@@ -282,10 +315,10 @@ int vocos(Ctx& c, const VocosW& v, float* x, float* t1, float* u, int B, int T, 
         const VocosLayerW& w = v.layers[i];
         if (cond) {
             const float* sc = cond + (int64_t)(i + 1) * 2 * C;
-            QA_TRY(dwconv_op(c, x, w.dw, w.dwb, nullptr, nullptr, u, B, T, C, 7, 0.f));  // u doubles as [rows, C] scratch
+            QA_TRY(dwconv_op(c, x, w.dw, w.dwb, nullptr, nullptr, u, B, T, C, 7, 0.f, -1, rl));  // u doubles as [rows, C] scratch
             QA_RUN(c, launch_adaln(u, sc, sc + C, ld_cond, t1, B, T, C, 1e-6f, c.stream));
         } else {
-            QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, C, 7, 1e-6f));
+            QA_TRY(dwconv_op(c, x, w.dw, w.dwb, w.lnw, w.lnb, t1, B, T, C, 7, 1e-6f, -1, rl));
         }
         QA_TRY(linear_op(c, t1, rows, w.pw1, u, epi(ACT_GELU)));
         QA_TRY(linear_op(c, u, rows, w.pw2, x, epi(ACT_NONE, x, w.gamma)));
@@ -307,8 +340,8 @@ int postnet_op(const qa_bicodec::Postnet& p, Ctx& c, const float* px, int B, int
     float* u = c.arena.alloc<float>(rows * I);
     float* o = c.arena.alloc<float>(rows * O);
     QA_TRY(linear_op(c, px, rows, p.linear_pre, x));
-    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, p.down[i], x, t1, u, B, T, C, nullptr, 0));
-    QA_TRY(vocos(c, p.backbone, x, t1, u, B, T, C, nullptr, 0));
+    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, p.down[i], x, t1, u, B, T, C, nullptr, 0, ClipLens()));
+    QA_TRY(vocos(c, p.backbone, x, t1, u, B, T, C, nullptr, 0, ClipLens()));
     QA_TRY(linear_op(c, x, rows, p.linear_out, o, epi(sp.postnet_tanh ? ACT_TANH : ACT_NONE)));
     c.tap("postnet.out", o, rows * O);
     // [B, T, O] read as a [B, C' = T, T' = O] tensor with strides (T O, O, 1): its channel-last form is [B, O, T]
@@ -316,9 +349,13 @@ int postnet_op(const qa_bicodec::Postnet& p, Ctx& c, const float* px, int B, int
 }
 
 // pred / dvec_out (forward only, else nullptr): the postnet's output from the prenet output BEFORE the d-vector add (bicodec.py:135-136),
-// and a copy of the d-vector
-int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long long* glob, int B, int T, float* wav_out, float* pred = nullptr,
-                     float* dvec_out = nullptr) {
+// and a copy of the d-vector.
+// rl (per-clip calls; rl.n null: the rectangular call): clip b holds rl.n[b] of the T tokens.  Every filter with a
+// temporal footprint sees the clip's length at its own rate - tokens in the prenet, tokens x the strides so far in the wave generator,
+// where a dilated k7 pads by up to 27 frames - and pads with zeros from the clip's own end; entries of `sem` behind it are never read
+// and wav_out[b] is exactly 0 from sample rl.n[b] * hop on.
+int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long long* glob, int B, int T, ClipLens rl, float* wav_out,
+                     float* pred = nullptr, float* dvec_out = nullptr) {
     const qa_bicodec_spec& sp = h->spec;
     const int Ld = sp.latent_dim, C = sp.vocos_dim, I = sp.vocos_inter;
     const int64_t rows = (int64_t)B * T;
@@ -327,7 +364,7 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     float* gflat = c.arena.alloc<float>((size_t)B * sp.spk_latent_dim * sp.token_num);
     float* dvec = c.arena.alloc<float>((size_t)B * Ld);
     float* cond = c.arena.alloc<float>((size_t)B * h->ada.N);
-    QA_RUN(c, launch_gather_rows(sem, h->sem_table, zq, rows, sp.codebook_size, Ld, c.stream));
+    QA_RUN(c, launch_gather_rows(sem, h->sem_table, zq, rows, sp.codebook_size, Ld, c.stream, T, rl.n));
     QA_RUN(c, launch_gather_global(glob, h->glob_table, gflat, B, sp.token_num, h->n_glob, sp.spk_latent_dim, c.stream));
     QA_TRY(linear_per_item(c, gflat, B, h->project, dvec));
     QA_TRY(linear_per_item(c, dvec, B, h->ada, cond));
@@ -338,9 +375,9 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     float* t1 = c.arena.alloc<float>(rows * C);
     float* u = c.arena.alloc<float>(rows * I);
     QA_TRY(linear_op(c, zq, rows, h->linear_pre, x));
-    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, T, C, nullptr, 0));
+    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, T, C, nullptr, 0, rl));
     c.tap("prenet.down", x, rows * C);
-    QA_TRY(vocos(c, h->backbone, x, t1, u, B, T, C, cond, h->ada.N));
+    QA_TRY(vocos(c, h->backbone, x, t1, u, B, T, C, cond, h->ada.N, rl));
     c.tap("prenet.backbone", x, rows * C);
     float* px = zq;  // z_q is dead: reuse it for the prenet output [B, T, latent]
     QA_TRY(linear_op(c, x, rows, h->linear_out, px));
@@ -358,12 +395,13 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     float* s_in = c.arena.alloc<float>((size_t)B * Tc * ch);  // snake(conv0(x)): the only form block 0 consumes
     {
         ConvOpt o;
-        o.pad_left = 3; o.pad_right = 3; o.act = ACT_SNAKE; o.alpha = h->blocks[0].a_in;
+        o.pad_left = 3; o.pad_right = 3; o.act = ACT_SNAKE; o.alpha = h->blocks[0].a_in; o.rl = rl;
         QA_TRY(conv_op(c, px, Ld, B, T, h->gen_in, s_in, ch, T, o));
     }
     for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
         const GenBlockW& g = h->blocks[bi];
         const int s = g.stride, co = g.c_out, To = Tc * s;
+        const ClipLens rl_in = rl.times(Tc / T), rl_out = rl.times(To / T);  // the clips at the block's input and output rates
         const size_t n = (size_t)B * To * co;
         float* raw0 = c.arena.alloc<float>(n);
         float* raw1 = c.arena.alloc<float>(n);
@@ -374,6 +412,7 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
             ConvOpt o;
             o.pad_left = g.pad_left[phi];
             o.pad_right = g.phase[phi].ksize - 1 - g.pad_left[phi];
+            o.rl = rl_in;
             o.y2 = snk + (size_t)phi * co; o.alpha2 = g.unit[0].a1; o.ldy2 = (int64_t)s * co;
             QA_TRY(conv_op(c, s_in, g.c_in, B, Tc, g.phase[phi], raw0 + (size_t)phi * co, (int64_t)s * co, Tc, o));
         }
@@ -384,7 +423,7 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
             const UnitW& un = g.unit[j];
             ConvOpt o7;  // Snake (input, already applied) -> dilated k7 -> Snake (epilogue)
             o7.pad_left = 3 * un.dilation; o7.pad_right = 3 * un.dilation; o7.dilation = un.dilation;
-            o7.act = ACT_SNAKE; o7.alpha = un.a2;
+            o7.act = ACT_SNAKE; o7.alpha = un.a2; o7.rl = rl_out;
             QA_TRY(conv_op(c, snk, co, B, To, un.c7, act, co, To, o7));
             ConvOpt o1;  // k1 + skip; the sum leaves raw (for the next skip) and activated (for the next convolution)
             o1.res = cur; o1.ldr = co;
@@ -404,9 +443,10 @@ int detokenize_graph(qa_bicodec* h, Ctx& c, const long long* sem, const long lon
     }
     {
         ConvOpt o;
-        o.pad_left = 3; o.pad_right = 3; o.act = ACT_TANH;
+        o.pad_left = 3; o.pad_right = 3; o.act = ACT_TANH; o.rl = rl.times(Tc / T);
         QA_TRY(conv_op(c, s_in, ch, B, Tc, h->gen_out, wav_out, 1, Tc, o));
     }
+    if (rl.n) QA_RUN(c, launch_zero_behind(wav_out, B, Tc, rl.times(Tc / T), c.stream));  // behind the last writer of the waveform
     return QA_OK;
 }
 
@@ -600,16 +640,18 @@ int build_speaker(qa_bicodec_enc* h, Loader& L) {
     return QA_OK;
 }
 
-int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, long long* tokens) {
+// rl (per-clip calls; rl.n null: the rectangular call): clip b holds rl.n[b] of the N feature frames; rows of `feat` behind them are
+// never read, and tokens[b, n] = -1 for n >= rl.n[b]
+int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, ClipLens rl, long long* tokens) {
     const qa_bicodec_enc_spec& sp = h->spec;
     const int C = sp.vocos_dim, I = sp.vocos_inter, Ld = sp.latent_dim, D = sp.codebook_dim;
     const int64_t rows = (int64_t)B * N;
     float* x = c.arena.alloc<float>(rows * C);
     float* t1 = c.arena.alloc<float>(rows * C);
     float* u = c.arena.alloc<float>(rows * std::max(I, Ld));
-    QA_TRY(vocos(c, h->backbone, x, t1, u, B, N, C, nullptr, 0, feat));
+    QA_TRY(vocos(c, h->backbone, x, t1, u, B, N, C, nullptr, 0, rl, feat));
     c.tap("enc.backbone", x, rows * C);
-    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, N, C, nullptr, 0));
+    for (int i = 0; i < 2; ++i) QA_TRY(vocos(c, h->down[i], x, t1, u, B, N, C, nullptr, 0, rl));
     c.tap("enc.down", x, rows * C);
     float* z = u;  // the ConvNeXt scratch is dead: z [rows, latent]
     QA_TRY(linear_op(c, x, rows, h->project, z));
@@ -619,6 +661,7 @@ int semantic_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N, l
     QA_RUN(c, launch_l2norm_rows(ze, ze, rows, D, c.stream));
     // one stage, no residual kept: the codebook search of rvq.hip (dist = (|e|^2 - 2 e.c) + |c|^2, lowest index on a tie)
     QA_RUN(c, launch_rvq_search(ze, rows, h->codebook, h->e2, 1, sp.codebook_size, D, tokens, nullptr, 0, nullptr, c.stream));
+    if (rl.n) QA_RUN(c, launch_tokens_fill_behind(tokens, B, N, rl.n, c.stream));
     c.tap("vq.latent", ze, rows * D);
     return QA_OK;
 }
@@ -629,8 +672,10 @@ int conv_bn_relu(Ctx& c, const float* x, int64_t ldx, int B, int T, const ConvBn
     return conv_op(c, x, ldx, B, T, w.conv, y, ldy, T, o);
 }
 
-// latent_out (forward only): the ECAPA latent [B, frames, 1536] stays in the arena for the x-vector head
-int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, int64_t ref_len, int* tokens,
+// latent_out (forward only): the ECAPA latent [B, frames, 1536] stays in the arena for the x-vector head.
+// samples (per-clip calls, device [B]; null: the rectangular call): the reference clip of row b is wav[b, k % samples[b]] - the framing
+// kernel is the only reader of wav, and everything behind it runs over the ref_len samples every row then has
+int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, int64_t ref_len, const int* samples, int* tokens,
                  const float** latent_out = nullptr) {
     const qa_bicodec_enc_spec& sp = h->spec;
     const int hop = sp.hop_length, C = sp.ecapa_channels, D = sp.spk_latent_dim, nl = sp.token_num;
@@ -641,7 +686,7 @@ int global_graph(qa_bicodec_enc* h, Ctx& c, const float* wav, int B, int64_t T, 
     float* ri = c.arena.alloc<float>((size_t)rows * 2 * h->nbp);
     float* mag = c.arena.alloc<float>((size_t)rows * h->kp);
     float* mel = c.arena.alloc<float>((size_t)rows * sp.mel_dim);
-    QA_RUN(c, launch_mel_frames(wav, B, T, ref_len, hop, nf, P, c.stream));
+    QA_RUN(c, launch_mel_frames(wav, B, T, ref_len, hop, nf, P, c.stream, samples));
     QA_TRY(conv_op(c, P, hop, B, nf + 1, h->dft, ri, 2 * h->nbp, nf, ConvOpt()));
     QA_RUN(c, launch_spec_mag(ri, h->nbp, h->nb, mag, h->kp, rows, c.stream));
     QA_TRY(linear_op(c, mag, rows, h->fbank, mel));
@@ -828,11 +873,11 @@ int forward_enc_graph(qa_bicodec_enc* h, Ctx& c, const float* feat, int B, int N
                       long long* glob, float* xvec, float* perplexity, float* active) {
     const qa_bicodec_enc_spec& sp = h->spec;
     const qa_bicodec_enc::XvecHead& xv = *h->xvec;
-    QA_TRY(semantic_graph(h, c, feat, B, N, sem));
+    QA_TRY(semantic_graph(h, c, feat, B, N, ClipLens(), sem));
     QA_RUN(c, launch_code_usage(sem, (long long)B * N, sp.codebook_size, perplexity, active, c.stream));
     int* g32 = c.arena.alloc<int>((size_t)B * sp.token_num);
     const float* latent = nullptr;
-    QA_TRY(global_graph(h, c, wav, B, T, T, g32, &latent));
+    QA_TRY(global_graph(h, c, wav, B, T, T, nullptr, g32, &latent));
     QA_RUN(c, launch_widen_i32(g32, glob, (long long)B * sp.token_num, c.stream));
     // ---- x-vector (ecapa_tdnn.py:204-206): ASTP with the global context of ECAPA_TDNN_GLOB_c512 (pooling_layers.py:129-144), BN, Linear.
     // linear1(cat(x, mean, std)) = W_x x + (W_c [mean; std] + b): the context half is one row per item, folded into that item's bias
@@ -882,17 +927,44 @@ void qa_bicodec_destroy(qa_bicodec* h) { destroy_handle(h); }
 
 int64_t qa_bicodec_hop(const qa_bicodec* h) { return h ? h->hop : QA_ERR_INVALID; }
 
+// qa_bicodec_detokenize (lengths == nullptr) and qa_bicodec_detokenize_ragged.  Every check runs before the first launch; a length vector
+// whose entries all equal T leaves the call without a device array: the rectangular call as it is
+static int detokenize_call(qa_bicodec* h, const char* fn, const int64_t* semantic_tokens, const int64_t* global_tokens, int64_t B, int64_t T,
+                           const int64_t* lengths, float* wav_out, void* stream) {
+    QA_REQUIRE(B > 0 && T > 0, "%s: tokens are [%lld, %lld]", fn, (long long)B, (long long)T);
+    QA_REQUIRE(B * T * (int64_t)h->hop * 32 < (1LL << 31), "%s: batch too large (split it)", fn);
+    const int* lens = nullptr;
+    if (lengths) {
+        std::vector<int> len;
+        bool full = true;
+        QA_TRY(check_clip_lengths(fn, B, lengths, 1, T, "tokens", "T", &len, &full));
+        if (!full) {
+            QA_HIP(hipSetDevice(h->device));
+            QA_TRY(h->lens.upload(len, 0, 1, static_cast<hipStream_t>(stream), &lens));
+        }
+    }
+    return run_planned(*h, stream, [&] {
+        return detokenize_graph(h, h->ctx, (const long long*)semantic_tokens, (const long long*)global_tokens, (int)B, (int)T,
+                                ClipLens{lens, lens ? 1 : 0}, wav_out);
+    });
+}
+
 int qa_bicodec_detokenize(qa_bicodec* h, const int64_t* semantic_tokens, const int64_t* global_tokens, int64_t B, int64_t T, float* wav_out,
                           void* stream) {
     if (!h || !semantic_tokens || !global_tokens || !wav_out) {
         set_error("qa_bicodec_detokenize: null argument");
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(B > 0 && T > 0, "qa_bicodec_detokenize: tokens are [%lld, %lld]", (long long)B, (long long)T);
-    QA_REQUIRE(B * T * (int64_t)h->hop * 32 < (1LL << 31), "qa_bicodec_detokenize: batch too large (split it)");
-    return run_planned(*h, stream, [&] {
-        return detokenize_graph(h, h->ctx, (const long long*)semantic_tokens, (const long long*)global_tokens, (int)B, (int)T, wav_out);
-    });
+    return detokenize_call(h, "qa_bicodec_detokenize", semantic_tokens, global_tokens, B, T, nullptr, wav_out, stream);
+}
+
+int qa_bicodec_detokenize_ragged(qa_bicodec* h, const int64_t* semantic_tokens, const int64_t* global_tokens, int64_t B, int64_t T,
+                                 const int64_t* lengths, float* wav_out, void* stream) {
+    if (!h || !semantic_tokens || !global_tokens || !lengths || !wav_out) {
+        set_error("qa_bicodec_detokenize_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    return detokenize_call(h, "qa_bicodec_detokenize_ragged", semantic_tokens, global_tokens, B, T, lengths, wav_out, stream);
 }
 
 int qa_bicodec_enc_create(qa_bicodec_enc** out, const qa_bicodec_enc_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
@@ -912,15 +984,76 @@ int qa_bicodec_enc_create(qa_bicodec_enc** out, const qa_bicodec_enc_spec* spec,
 
 void qa_bicodec_enc_destroy(qa_bicodec_enc* h) { destroy_handle(h); }
 
+// The tokenizer's entry points, rectangular (lengths == nullptr) and per-clip.  *_checks: every check of a call,
+// lengths included (frames: 1 .. N feature frames; samples: 1 .. T samples) - all of them run before the first launch, and for
+// qa_bicodec_tokenize_ragged both halves are checked before either runs.  A vector whose entries all equal the full extent leaves its
+// half without a device array: the rectangular call as it is.
+struct EncLens {
+    std::vector<int> len;
+    bool ragged = false;
+};
+static int semantic_checks(qa_bicodec_enc* h, const char* fn, int64_t B, int64_t N, const int64_t* frame_lengths, EncLens* out) {
+    QA_REQUIRE(B > 0 && N > 0, "%s: feat is [%lld, %lld, C]", fn, (long long)B, (long long)N);
+    QA_REQUIRE(B * N * (int64_t)std::max(h->spec.vocos_inter, h->spec.input_channels) < (1LL << 31), "%s: batch too large (split it)", fn);
+    if (frame_lengths) {
+        bool full = true;
+        QA_TRY(check_clip_lengths(fn, B, frame_lengths, 1, N, "feature frames", "N", &out->len, &full));
+        out->ragged = !full;
+    }
+    return QA_OK;
+}
+static int global_checks(qa_bicodec_enc* h, const char* fn, int64_t B, int64_t T, int64_t* ref_len, const int64_t* lengths, EncLens* out) {
+    if (lengths) {
+        QA_REQUIRE(B > 0 && T > 0, "%s: wav is [%lld, %lld]", fn, (long long)B, (long long)T);
+        bool full = true;
+        QA_TRY(check_clip_lengths(fn, B, lengths, 1, T, "samples", "T", &out->len, &full));
+        out->ragged = !full;
+        // without a reference length every clip would be its own row with its own frame count: not one rectangular mel
+        QA_REQUIRE(full || *ref_len > 0, "%s: clips of different lengths need ref_len > 0 (the reference clip every row is tiled or truncated to)",
+                   fn);
+    }
+    if (*ref_len <= 0) *ref_len = T;
+    return check_global_shape(h, B, T, *ref_len);
+}
+static int semantic_run(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const EncLens& fl, int64_t* semantic_out, void* stream) {
+    const int* lens = nullptr;
+    if (fl.ragged) {
+        QA_HIP(hipSetDevice(h->device));
+        QA_TRY(h->lens.upload(fl.len, 0, 2, static_cast<hipStream_t>(stream), &lens));
+    }
+    return run_planned(*h, stream, [&] {
+        return semantic_graph(h, h->ctx, feat, (int)B, (int)N, ClipLens{lens, lens ? 1 : 0}, (long long*)semantic_out);
+    });
+}
+static int global_run(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, int64_t ref_len, const EncLens& sl, int32_t* global_out,
+                      void* stream) {
+    const int* lens = nullptr;
+    if (sl.ragged) {
+        QA_HIP(hipSetDevice(h->device));
+        QA_TRY(h->lens.upload(sl.len, 1, 2, static_cast<hipStream_t>(stream), &lens));
+    }
+    return run_planned(*h, stream, [&] { return global_graph(h, h->ctx, wav, (int)B, T, ref_len, lens, (int*)global_out); });
+}
+
 int qa_bicodec_get_semantic_tokens(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, int64_t* semantic_out, void* stream) {
     if (!h || !feat || !semantic_out) {
         set_error("qa_bicodec_get_semantic_tokens: null argument");
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(B > 0 && N > 0, "qa_bicodec_get_semantic_tokens: feat is [%lld, %lld, C]", (long long)B, (long long)N);
-    QA_REQUIRE(B * N * (int64_t)std::max(h->spec.vocos_inter, h->spec.input_channels) < (1LL << 31),
-               "qa_bicodec_get_semantic_tokens: batch too large (split it)");
-    return run_planned(*h, stream, [&] { return semantic_graph(h, h->ctx, feat, (int)B, (int)N, (long long*)semantic_out); });
+    EncLens fl;
+    QA_TRY(semantic_checks(h, "qa_bicodec_get_semantic_tokens", B, N, nullptr, &fl));
+    return semantic_run(h, feat, B, N, fl, semantic_out, stream);
+}
+
+int qa_bicodec_get_semantic_tokens_ragged(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const int64_t* frame_lengths,
+                                          int64_t* semantic_out, void* stream) {
+    if (!h || !feat || !frame_lengths || !semantic_out) {
+        set_error("qa_bicodec_get_semantic_tokens_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    EncLens fl;
+    QA_TRY(semantic_checks(h, "qa_bicodec_get_semantic_tokens_ragged", B, N, frame_lengths, &fl));
+    return semantic_run(h, feat, B, N, fl, semantic_out, stream);
 }
 
 int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, int64_t ref_len, int32_t* global_out, void* stream) {
@@ -928,9 +1061,20 @@ int qa_bicodec_get_global_tokens(qa_bicodec_enc* h, const float* wav, int64_t B,
         set_error("qa_bicodec_get_global_tokens: null argument");
         return QA_ERR_INVALID;
     }
-    if (ref_len <= 0) ref_len = T;
-    QA_TRY(check_global_shape(h, B, T, ref_len));
-    return run_planned(*h, stream, [&] { return global_graph(h, h->ctx, wav, (int)B, T, ref_len, (int*)global_out); });
+    EncLens sl;
+    QA_TRY(global_checks(h, "qa_bicodec_get_global_tokens", B, T, &ref_len, nullptr, &sl));
+    return global_run(h, wav, B, T, ref_len, sl, global_out, stream);
+}
+
+int qa_bicodec_get_global_tokens_ragged(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, const int64_t* lengths, int64_t ref_len,
+                                        int32_t* global_out, void* stream) {
+    if (!h || !wav || !lengths || !global_out) {
+        set_error("qa_bicodec_get_global_tokens_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    EncLens sl;
+    QA_TRY(global_checks(h, "qa_bicodec_get_global_tokens_ragged", B, T, &ref_len, lengths, &sl));
+    return global_run(h, wav, B, T, ref_len, sl, global_out, stream);
 }
 
 int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const float* ref_wav, int64_t T_ref, int64_t ref_len,
@@ -941,6 +1085,20 @@ int qa_bicodec_tokenize(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t
     }
     QA_TRY(qa_bicodec_get_semantic_tokens(h, feat, B, N, semantic_out, stream));
     return qa_bicodec_get_global_tokens(h, ref_wav, B, T_ref, ref_len, global_out, stream);
+}
+
+int qa_bicodec_tokenize_ragged(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const int64_t* frame_lengths, const float* ref_wav,
+                               int64_t T_ref, const int64_t* lengths, int64_t ref_len, int64_t* semantic_out, int32_t* global_out,
+                               void* stream) {
+    if (!h || !feat || !frame_lengths || !ref_wav || !lengths || !semantic_out || !global_out) {
+        set_error("qa_bicodec_tokenize_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    EncLens fl, sl;
+    QA_TRY(semantic_checks(h, "qa_bicodec_tokenize_ragged", B, N, frame_lengths, &fl));
+    QA_TRY(global_checks(h, "qa_bicodec_tokenize_ragged", B, T_ref, &ref_len, lengths, &sl));
+    QA_TRY(semantic_run(h, feat, B, N, fl, semantic_out, stream));
+    return global_run(h, ref_wav, B, T_ref, ref_len, sl, global_out, stream);
 }
 
 int qa_bicodec_enc_enable_taps(qa_bicodec_enc* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_bicodec_enc_enable_taps", on); }
@@ -957,6 +1115,21 @@ int qa_wav_normalize(const float* wav, int64_t B, int64_t T, float* out, float e
     QA_REQUIRE(B > 0 && B < (1LL << 31) && T > 0, "qa_wav_normalize: wav is [%lld, %lld]", (long long)B, (long long)T);
     QA_REQUIRE(eps >= 0.f, "qa_wav_normalize: eps %g < 0", (double)eps);
     return launch_wav_normalize(wav, out, (int)B, (long long)T, eps, static_cast<hipStream_t>(stream));
+}
+
+int qa_wav_normalize_ragged(const float* wav, int64_t B, int64_t T, const int64_t* lengths, float* out, float eps, void* stream) {
+    if (!wav || !lengths || !out) {
+        set_error("qa_wav_normalize_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    QA_REQUIRE(B > 0 && B < (1LL << 31) && T > 0, "qa_wav_normalize_ragged: wav is [%lld, %lld]", (long long)B, (long long)T);
+    QA_REQUIRE(eps >= 0.f, "qa_wav_normalize_ragged: eps %g < 0", (double)eps);
+    std::vector<int> len;
+    bool full = true;
+    QA_TRY(check_clip_lengths("qa_wav_normalize_ragged", B, lengths, 1, T, "samples", "T", &len, &full));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the launcher reads the caller's int64 lengths as they are");
+    return launch_wav_normalize(wav, out, (int)B, (long long)T, eps, static_cast<hipStream_t>(stream),
+                                full ? nullptr : reinterpret_cast<const long long*>(lengths));
 }
 
 int qa_bicodec_enable_taps(qa_bicodec* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_bicodec_enable_taps", on); }
@@ -1018,8 +1191,8 @@ int qa_bicodec_forward(qa_bicodec* dec, qa_bicodec_enc* enc, const float* feat, 
                                  x_vector, perplexity, cluster_size);
     }));
     return run_planned(*dec, stream, [&] {
-        return detokenize_graph(dec, dec->ctx, (const long long*)semantic_out, (const long long*)global_out, (int)B, (int)N, recons, pred_feat,
-                                d_vector);
+        return detokenize_graph(dec, dec->ctx, (const long long*)semantic_out, (const long long*)global_out, (int)B, (int)N, ClipLens(), recons,
+                                pred_feat, d_vector);
     });
 }
 

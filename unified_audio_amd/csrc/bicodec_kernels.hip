@@ -2,6 +2,7 @@
 // (bicodec.py:151-180) that are not plain contractions: token look-ups into folded tables, AdaLayerNorm, the d-vector broadcast add;
 // the feature normalisation, the mel framing / magnitude, the Res2 chain, SE, perceiver glue, FSQ.  Everything with a large contraction
 // (linears, k7 / dilated k7 convolutions, the polyphase ConvTranspose1d, the DFT and the mel filterbank) runs on conv_gemm.hip.
+#include <algorithm>
 #include <cmath>
 
 #include "kernels.h"
@@ -9,21 +10,61 @@
 namespace qa {
 
 // out[i, :] = table[clamp(tok[i]), :]   (FactorizedVectorQuantize.detokenize with out_project folded into the table)
+// lens [n / T] (device) or null: row i = b * T + t of a per-clip call with t >= lens[b] is padding - its token is
+// not loaded, the table is not indexed, and the row is exact zeros (finite: the zero-padding taps of the convolutions multiply it by 0)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const long long* __restrict__ tok, const float* __restrict__ table, float* __restrict__ out,
-                                                          long long n, int V, int D) {
+                                                          long long n, int V, int D, int T, const int* __restrict__ lens) {
     const int d4 = D >> 2;
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= n * d4) return;
     const long long i = gid / d4;
     const int c = (int)(gid - i * d4) * 4;
+    if (lens) {  // launch-uniform
+        const long long b = i / T;
+        if ((int)(i - b * T) >= lens[b]) {
+            *reinterpret_cast<float4*>(out + i * D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+    }
     long long t = tok[i];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);  // memory safety only; callers validate (qa_codes_check)
     *reinterpret_cast<float4*>(out + i * D + c) = *reinterpret_cast<const float4*>(table + t * D + c);
 }
-int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s) {
+int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s, int T, const int* lens) {
     QA_REQUIRE(D % 4 == 0, "gather_rows: D=%d must be a multiple of 4", D);
+    QA_REQUIRE(!lens || (T >= 1 && n % T == 0), "gather_rows: per-clip lengths need rows = B * T (rows %lld, T %d)", n, T);
     if (n <= 0) return QA_OK;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)ceil_div(n * (D / 4), 256)), dim3(256), 0, s, tok, table, out, n, V, D);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)ceil_div(n * (D / 4), 256)), dim3(256), 0, s, tok, table, out, n, V, D, T, lens);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// The tails of a per-clip call, each behind the last writer of its output: tok[b, n] = -1 for n >= lens[b] (the
+// semantic tokens behind a clip's last frame) and x[b, t] = 0.0f for t >= lens[b] * mul (the waveform behind a clip's last sample).
+// Nothing in front of a clip's end is touched.
+__global__ __launch_bounds__(256) void tokens_fill_behind_kernel(long long* __restrict__ tok, long long total, int N, const int* __restrict__ lens) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long long b = gid / N;
+    if ((int)(gid - b * N) >= lens[b]) tok[gid] = -1;
+}
+int launch_tokens_fill_behind(long long* tok, int B, int N, const int* lens, hipStream_t s) {
+    QA_REQUIRE(lens && B > 0 && N > 0, "tokens_fill_behind: [%d, %d] without lengths", B, N);
+    const long long total = (long long)B * N;
+    hipLaunchKernelGGL(tokens_fill_behind_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, tok, total, N, lens);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+__global__ __launch_bounds__(256) void zero_behind_kernel(float* __restrict__ x, long long total, long long T, const int* __restrict__ lens, int mul) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long long b = gid / T;
+    if (gid - b * T >= (long long)lens[b] * mul) x[gid] = 0.f;
+}
+int launch_zero_behind(float* x, int B, long long T, ClipLens rl, hipStream_t s) {
+    QA_REQUIRE(rl.n && rl.mul >= 1 && B > 0 && T > 0, "zero_behind: [%d, %lld] without lengths", B, T);
+    const long long total = (long long)B * T;
+    hipLaunchKernelGGL(zero_behind_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, total, T, rl.n, rl.mul);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -127,26 +168,53 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {  // 256 t
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
-__global__ __launch_bounds__(256) void wav_normalize_kernel(const float* x, float* y, long long T, float eps) {
-    __shared__ double red[4];
-    const float* xr = x + (long long)blockIdx.x * T;
-    float* yr = y + (long long)blockIdx.x * T;
+// one row: the moments over its first `len` samples, (x - mean) / sqrt(var + eps) there and exact zeros from `len` to T
+__device__ __forceinline__ void wav_normalize_row(const float* xr, float* yr, long long len, long long T, float eps, double* red) {
     double s = 0.0;
-    for (long long t = threadIdx.x; t < T; t += 256) s += (double)xr[t];
-    const double mean = block_sum_d(s, red) / (double)T;
+    for (long long t = threadIdx.x; t < len; t += 256) s += (double)xr[t];
+    const double mean = block_sum_d(s, red) / (double)len;
     double ss = 0.0;
-    for (long long t = threadIdx.x; t < T; t += 256) {
+    for (long long t = threadIdx.x; t < len; t += 256) {
         const double d = (double)xr[t] - mean;
         ss += d * d;
     }
-    const double var = block_sum_d(ss, red) / (double)T;
+    const double var = block_sum_d(ss, red) / (double)len;
     const float m = (float)mean, inv = (float)(1.0 / sqrt(var + (double)eps));
-    for (long long t = threadIdx.x; t < T; t += 256) yr[t] = (xr[t] - m) * inv;
+    for (long long t = threadIdx.x; t < len; t += 256) yr[t] = (xr[t] - m) * inv;
+    for (long long t = len + threadIdx.x; t < T; t += 256) yr[t] = 0.f;
 }
-int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s) {
+__global__ __launch_bounds__(256) void wav_normalize_kernel(const float* x, float* y, long long T, float eps) {
+    __shared__ double red[4];
+    wav_normalize_row(x + (long long)blockIdx.x * T, y + (long long)blockIdx.x * T, T, T, eps, red);
+}
+// Per-clip lengths: row b is normalised over its own lens.n[b] samples - the same loops, so the same summation
+// order, as the kernel above on a [1, lens.n[b]] row - and nothing behind them is read.  The lengths ride BY VALUE in the launch, as
+// row_lens_kernel's do (ew.hip): this entry point has no handle that could own a device array.
+constexpr int WAV_LENS_CHUNK = 256;
+struct WavLensArg {
+    long long n[WAV_LENS_CHUNK];
+};
+__global__ __launch_bounds__(256) void wav_normalize_ragged_kernel(const float* x, float* y, long long T, float eps, const WavLensArg lens) {
+    __shared__ double red[4];
+    wav_normalize_row(x + (long long)blockIdx.x * T, y + (long long)blockIdx.x * T, lens.n[blockIdx.x], T, eps, red);
+}
+int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s, const long long* lens_host) {
     QA_REQUIRE(B > 0 && T > 0, "wav_normalize: [%d, %lld]", B, T);
-    hipLaunchKernelGGL(wav_normalize_kernel, dim3((unsigned)B), dim3(256), 0, s, x, y, T, eps);
-    QA_LAUNCH_CHECK();
+    if (!lens_host) {
+        hipLaunchKernelGGL(wav_normalize_kernel, dim3((unsigned)B), dim3(256), 0, s, x, y, T, eps);
+        QA_LAUNCH_CHECK();
+        return QA_OK;
+    }
+    for (int b0 = 0; b0 < B; b0 += WAV_LENS_CHUNK) {
+        WavLensArg a{};
+        const int m = std::min(WAV_LENS_CHUNK, B - b0);
+        for (int i = 0; i < m; ++i) {
+            QA_REQUIRE(lens_host[b0 + i] >= 1 && lens_host[b0 + i] <= T, "wav_normalize: row %d holds %lld of %lld samples", b0 + i, lens_host[b0 + i], T);
+            a.n[i] = lens_host[b0 + i];
+        }
+        hipLaunchKernelGGL(wav_normalize_ragged_kernel, dim3((unsigned)m), dim3(256), 0, s, x + (long long)b0 * T, y + (long long)b0 * T, T, eps, a);
+        QA_LAUNCH_CHECK();
+    }
     return QA_OK;
 }
 
@@ -174,19 +242,22 @@ int launch_l2norm_rows(const float* x, float* y, long long rows, int D, hipStrea
 // the reference clip of ref_len samples, reflect-padded by torch.stft(center=True) (k < 0 -> -k, k >= ref_len -> 2 (ref_len - 1) - k),
 // and clip[k] = wav[k % T] is BiCodecTokenizer.get_ref_clip's tile-then-truncate as index arithmetic.  Viewed as [B, n_frames + 1, hop],
 // frame t of a window of 2 hop samples centred on t * hop is rows t and t + 1: a k = 2 convolution over hop channels.
+// lens [B] (device) or null: the clip of row b is its first lens[b] samples (a per-clip call) - it tiles by its own
+// length, and nothing behind it is read.
 __global__ __launch_bounds__(256) void mel_frames_kernel(const float* __restrict__ wav, long long T, long long ref_len, int hop,
-                                                         long long n_out, float* __restrict__ P) {
+                                                         long long n_out, float* __restrict__ P, const int* __restrict__ lens) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_out) return;
     const int b = blockIdx.y;
     long long k = i - hop;
     k = k < 0 ? -k : (k >= ref_len ? 2 * (ref_len - 1) - k : k);
-    P[(long long)b * n_out + i] = wav[(long long)b * T + k % T];
+    const long long len = lens ? (long long)lens[b] : T;  // launch-uniform
+    P[(long long)b * n_out + i] = wav[(long long)b * T + k % len];
 }
-int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s) {
+int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s, const int* lens) {
     QA_REQUIRE(T > 0 && ref_len > hop && B > 0, "mel_frames: T=%lld ref_len=%lld hop=%d", T, ref_len, hop);
     const long long n_out = (long long)(n_frames + 1) * hop;
-    hipLaunchKernelGGL(mel_frames_kernel, dim3((unsigned)ceil_div(n_out, 256), (unsigned)B), dim3(256), 0, s, wav, T, ref_len, hop, n_out, P);
+    hipLaunchKernelGGL(mel_frames_kernel, dim3((unsigned)ceil_div(n_out, 256), (unsigned)B), dim3(256), 0, s, wav, T, ref_len, hop, n_out, P, lens);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

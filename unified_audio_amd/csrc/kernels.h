@@ -181,14 +181,24 @@ int launch_ssl_compress(const float* sum, float* out, long long n, float scale, 
                         int N = 0, int d = 0);
 
 // bicodec_kernels.hip
-int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s);
+// The per-clip calls of BiCodec pass the clips' lengths; null everywhere else: today's path through one
+// launch-uniform branch, without a load.
+// lens [n / T] (device): rows t >= lens[b] of clip b are written as zeros and their tokens are never read
+int launch_gather_rows(const long long* tok, const float* table, float* out, long long n, int V, int D, hipStream_t s, int T = 0,
+                       const int* lens = nullptr);
+// tok [B, N]: -1 at n >= lens[b];  x [B, T]: 0.0f at t >= rl.n[b] * rl.mul.  Per-clip calls only (lens not null)
+int launch_tokens_fill_behind(long long* tok, int B, int N, const int* lens, hipStream_t s);
+int launch_zero_behind(float* x, int B, long long T, ClipLens rl, hipStream_t s);
 int launch_gather_global(const long long* tok, const float* table, float* out, int B, int N, int V, int L, hipStream_t s);
 int launch_adaln(const float* x, const float* scale, const float* shift, long long ld_cond, float* y, int B, int T, int C, float eps,
                  hipStream_t s);
 int launch_add_rowvec(float* x, const float* v, int B, int T, int C, hipStream_t s);
-int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s);
+// lens_host [B] (HOST memory, 1 .. T each, travels by value in the launch) or null: row b is normalised over its own samples, zeros behind
+int launch_wav_normalize(const float* x, float* y, int B, long long T, float eps, hipStream_t s, const long long* lens_host = nullptr);
 int launch_l2norm_rows(const float* x, float* y, long long rows, int D, hipStream_t s);
-int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s);
+// lens [B] (device, samples) or null: the reference clip of row b tiles by lens[b] instead of T
+int launch_mel_frames(const float* wav, int B, long long T, long long ref_len, int hop, int n_frames, float* P, hipStream_t s,
+                      const int* lens = nullptr);
 int launch_spec_mag(const float* ri, int nbp, int nb, float* mag, int ldm, long long rows, hipStream_t s);
 int launch_res2_chain(const float* x, float* y, const float* wt, const float* bst, int B, int T, int C, int d, hipStream_t s);
 int launch_se_residual(const float* x, long long ldx, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
