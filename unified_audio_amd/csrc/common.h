@@ -165,6 +165,15 @@ void profile_record_begin(int cfg, double flops, double bytes, hipStream_t s, co
 void profile_record_end(hipStream_t s);
 
 int launch_conv_gemm(const ConvParams& p, hipStream_t stream);
+// Scope guard of a two-stream region: the conv_gemm launches this thread issues while it lives run beside n - 1 launches of the same shape on
+// sibling streams (conv_gemm.hip takes_bk16: QA_GEMM_BK16_MIN_TILES counts the tiles of all n).
+struct GemmLanes {
+    int prev;
+    explicit GemmLanes(int n);
+    ~GemmLanes();
+    GemmLanes(const GemmLanes&) = delete;
+    GemmLanes& operator=(const GemmLanes&) = delete;
+};
 // Pre-split weight images (weight_planes.hip, split_planes.h): build the image of w[0 .. n) (6 n bytes, n % 8 == 0) on `stream`; attach it,
 // so that conv_gemm launches whose weight lies inside w[0 .. n) read it; detach it again (before either buffer is freed); bytes of
 // all attached images of the process; the planes of w[0 .. n) when one attached image covers them and w sits on an 8-float group of

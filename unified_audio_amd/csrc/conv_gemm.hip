@@ -559,8 +559,16 @@ static void launch_instance(const ConvParams& p, long long tiles, hipStream_t st
 // next chunk's global loads, which a BK = 16 chunk's 0.45 us of MFMAs is too short to hide (measured: the 144-tile RVQ distance GEMM 1056 x 1024
 // x 512 ran 37 us, 2.5 x its MFMA time).  QA_GEMM_BK16_MIN_TILES = fewest tiles that take BK = 16.
 // The 256-row tile (r06 experiment, QA_GEMM_256) exists with BK = 16 only: 61 KB of LDS, two workgroups per CU.
+// Launches of a two-stream region (GemmLanes, common.h) run beside a sibling of the same shape on the other stream, so the workgroups of the
+// two cover each other's loads: the threshold counts the tiles of both.  A half-batch lane of the H-Codec 1.5 bottleneck at 32 x 10 s has 256
+// tiles in out_proj and lin2; on the BK = 32 instance (one workgroup per CU) the split gained 0.1 ms per step, on BK = 16 1.3 ms (DESIGN.md
+// section 30).  Same bits either way: every instance accumulates an output element over k in the same order.
+static thread_local int t_gemm_lanes = 1;
+GemmLanes::GemmLanes(int n) : prev(t_gemm_lanes) { t_gemm_lanes = n > 1 ? n : 1; }
+GemmLanes::~GemmLanes() { t_gemm_lanes = prev; }
 static bool takes_bk16(int bm, int bn, long long tiles, int K, int C_in, bool elu) {
-    return bm == 256 || (bn >= 64 && !elu && ((K <= knob(K_GEMM_BK16) && tiles >= knob(K_GEMM_BK16_MIN_TILES)) || C_in % 32 != 0));
+    return bm == 256 ||
+           (bn >= 64 && !elu && ((K <= knob(K_GEMM_BK16) && tiles * t_gemm_lanes >= knob(K_GEMM_BK16_MIN_TILES)) || C_in % 32 != 0));
 }
 
 template <int BM, int BN, int WM, int WN>

@@ -4,6 +4,7 @@
 // (QuarkAudio-HCodec/HCodec-1.0/vq/codec.py:166-187) with every activation kept time-major / channel-last
 // ([B, frames, C] rows) so that all convolutions and linears are one implicit-GEMM kernel (conv_gemm.hip).
 // Weights arrive in the reference's state_dict layout; weight-norm is folded and filters re-laid out here, once.
+#include <atomic>
 #include <memory>
 
 #include "host_util.h"
@@ -446,31 +447,61 @@ int mimi_readout_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, const float
     QA_RUN(c, launch_agg_zero_padded(ro.nseg, ro.out, B, ro.G, d, c.stream));
     return QA_OK;
 }
-// two independent stacks of equal depth, layer-interleaved on two streams (xa on the caller's stream, xb on `side`); with read-outs (both
-// or neither) the last layer of each stack is mimi_readout_layer, which leaves xa / xb at the input of that layer
-// kvalid [B, N] or null: one key-padding mask for both stacks (they share the alignment), written on the caller's stream before the fork
-int mimi_pair_op(Ctx& c, hipStream_t side, const MimiW& wa, float* xa, const MimiW& wb, float* xb, int B, int N,
-                 const unsigned char* kvalid, const AggReadout* ra = nullptr, const AggReadout* rb = nullptr) {
+std::atomic<long long> g_split_regions;  // regions that ran as two half-batch lanes so far (qa_debug_batch_split_regions)
+
+// One side of mimi_pair_op: a stack over x [B, N, d].  kvalid [B, N] or null: its key-padding mask, written on the caller's stream before
+// the fork.  ro: its read-out, or null.
+struct MimiStack {
+    const MimiW& w;
+    float* x;
+    int B;
+    const unsigned char* kvalid;
+    const AggReadout* ro;
+};
+// The workspace bytes [lo, hi) that one lane of a two-stream region was handed.  The arena is a bump allocator: what one lane releases the
+// other would receive while the first lane's kernels still run, so every region gives its lanes ranges of their own and checks them at the
+// join, in the planning and in the real pass.
+struct LaneSpan {
+    size_t lo, hi;
+};
+int lanes_disjoint(const LaneSpan& a, const LaneSpan& b) {
+    QA_REQUIRE(a.lo <= a.hi && b.lo <= b.hi && (a.hi <= b.lo || b.hi <= a.lo),
+               "two-stream region: the lanes' workspace ranges [%zu, %zu) and [%zu, %zu) overlap", a.lo, a.hi, b.lo, b.hi);
+    return QA_OK;
+}
+// two independent stacks of equal depth over N rows per clip, layer-interleaved on two streams (a on the caller's stream, b on `side`); with
+// read-outs (both or neither) the last layer of each stack is mimi_readout_layer, which leaves a.x / b.x at the input of that layer.  The
+// stacks may be the two aggregators over one batch, or ONE stack over the two halves of a batch (QA_BATCH_SPLIT): every op of a layer is
+// per clip, so a half batch is a row range of the same buffer and gets the bits the whole batch gives it.  The caller forks and joins.
+// gemm_lanes = 2: the two sides launch the same GEMM shapes side by side (GemmLanes, common.h) - the halves of a batch; the aggregators
+// measured no faster with it and keep 1.
+int mimi_pair_op(Ctx& c, hipStream_t side, const MimiStack& a, const MimiStack& b, int N, int gemm_lanes = 1) {
+    const MimiW &wa = a.w, &wb = b.w;
     QA_REQUIRE(N <= MAX_POS && wa.layers.size() == wb.layers.size(), "mimi pair: mismatched stacks");
-    QA_REQUIRE(!kvalid || (!wa.causal && !wb.causal), "mimi pair: a key-padding mask needs non-causal stacks");
-    QA_REQUIRE(!ra == !rb && (!ra || (!wa.causal && !wb.causal && wa.d == wb.d && !wa.layers.empty())), "mimi pair: bad read-out");
+    QA_REQUIRE((!a.kvalid && !b.kvalid) || (!wa.causal && !wb.causal), "mimi pair: a key-padding mask needs non-causal stacks");
+    QA_REQUIRE(!a.ro == !b.ro && (!a.ro || (!wa.causal && !wb.causal && wa.d == wb.d && !wa.layers.empty())), "mimi pair: bad read-out");
     const size_t mark = c.arena.mark();
-    const MimiTemps ta = mimi_temps(c, wa, (int64_t)B * N);
-    const MimiTemps tb = mimi_temps(c, wb, (int64_t)B * N);
     float* cq[4] = {nullptr, nullptr, nullptr, nullptr};  // xq, qq of either stack
-    if (ra)
-        for (float*& p : cq) p = c.arena.alloc<float>((size_t)B * ra->G * wa.d);
+    const MimiTemps ta = mimi_temps(c, wa, (int64_t)a.B * N);
+    if (a.ro)
+        for (int i = 0; i < 2; ++i) cq[i] = c.arena.alloc<float>((size_t)a.B * a.ro->G * wa.d);
+    const size_t mid = c.arena.mark();
+    const MimiTemps tb = mimi_temps(c, wb, (int64_t)b.B * N);
+    if (b.ro)
+        for (int i = 2; i < 4; ++i) cq[i] = c.arena.alloc<float>((size_t)b.B * b.ro->G * wb.d);
+    QA_TRY(lanes_disjoint(LaneSpan{mark, mid}, LaneSpan{mid, c.arena.mark()}));
     if (!c.dry) {  // real pass only, more than launches: c.stream alternates between the two streams
         hipStream_t main = c.stream;
+        const GemmLanes lanes(gemm_lanes);
         for (size_t l = 0; l < wa.layers.size(); ++l) {
-            const bool last = ra && l + 1 == wa.layers.size();
+            const bool last = a.ro && l + 1 == wa.layers.size();
             c.stream = main;
-            int st = last ? mimi_readout_layer(c, wa, wa.layers[l], xa, ta, cq[0], cq[1], B, *ra, kvalid)
-                          : mimi_layer(c, wa, wa.layers[l], xa, ta, B, N, kvalid);
+            int st = last ? mimi_readout_layer(c, wa, wa.layers[l], a.x, ta, cq[0], cq[1], a.B, *a.ro, a.kvalid)
+                          : mimi_layer(c, wa, wa.layers[l], a.x, ta, a.B, N, a.kvalid);
             c.stream = side;
             if (st == QA_OK)
-                st = last ? mimi_readout_layer(c, wb, wb.layers[l], xb, tb, cq[2], cq[3], B, *rb, kvalid)
-                          : mimi_layer(c, wb, wb.layers[l], xb, tb, B, N, kvalid);
+                st = last ? mimi_readout_layer(c, wb, wb.layers[l], b.x, tb, cq[2], cq[3], b.B, *b.ro, b.kvalid)
+                          : mimi_layer(c, wb, wb.layers[l], b.x, tb, b.B, N, b.kvalid);
             c.stream = main;
             QA_TRY(st);
         }
@@ -802,9 +833,9 @@ int encode_adaptive_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis
     // QA_AGG_LAST_ROWS: the last layer of each stack on the query rows only, read-out included (non-causal aggregators)
     if (knob(K_AGG_LAST_ROWS) != 0 && !h->agg_sem.causal && !h->agg_ac.causal && !h->agg_sem.layers.empty()) {
         const AggReadout rs{start, len, nseg, N, G, agg_s}, ra{start, len, nseg, N, G, agg_a};
-        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S, kvalid, &rs, &ra));
+        QA_TRY(mimi_pair_op(c, side, MimiStack{h->agg_sem, inter_s, B, kvalid, &rs}, MimiStack{h->agg_ac, inter_a, B, kvalid, &ra}, S));
     } else {
-        QA_TRY(mimi_pair_op(c, side, h->agg_sem, inter_s, h->agg_ac, inter_a, B, S, kvalid));
+        QA_TRY(mimi_pair_op(c, side, MimiStack{h->agg_sem, inter_s, B, kvalid, nullptr}, MimiStack{h->agg_ac, inter_a, B, kvalid, nullptr}, S));
         QA_RUN(c, launch_agg_gather(inter_s, start, len, nseg, agg_s, B, N, G, D, c.stream));
         QA_RUN(c, launch_agg_gather(inter_a, start, len, nseg, agg_a, B, N, G, D, side));
     }
@@ -843,7 +874,27 @@ int decode_adaptive_graph(qa_hcodec* h, Ctx& c, const long long* ac, const long 
         kvalid = c.arena.alloc<unsigned char>(rows);
         QA_RUN(c, launch_len_mask(kvalid, B, N, ClipLens{tc.rl.n, 1}, c.stream));
     }
-    QA_TRY(mimi_op(c, h->bottleneck, cat, B, N, kvalid));
+    // QA_BATCH_SPLIT bit 1: the stack over the two halves of the batch, clips [0, ceil(B / 2)) on the caller's stream and the rest on
+    // `side`, layer-interleaved like the aggregators - one half's LayerNorms and attention run beside the other half's GEMMs, and the
+    // partly filled last round of a GEMM's tiles is covered.  One lane, as before, for a single clip, under
+    // qa_set_serial(1), with taps on, or when the smaller half has fewer than QA_BATCH_SPLIT_MIN_ROWS rows.
+    const int B0 = (B + 1) / 2, B1 = B - B0;
+    if ((knob(K_BATCH_SPLIT) & 1) != 0 && B1 >= 1 && !serial_mode() && !c.capture && (int64_t)B1 * N >= knob(K_BATCH_SPLIT_MIN_ROWS)) {
+        const int64_t r0 = (int64_t)B0 * N;
+        if (!c.dry) {  // real pass only: the event fork
+            QA_HIP(hipEventRecord(h->ev_fork, c.stream));
+            QA_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+            g_split_regions.fetch_add(1, std::memory_order_relaxed);
+        }
+        QA_TRY(mimi_pair_op(c, h->side, MimiStack{h->bottleneck, cat, B0, kvalid, nullptr},
+                            MimiStack{h->bottleneck, cat + r0 * 2 * D, B1, kvalid ? kvalid + r0 : nullptr, nullptr}, N, 2));
+        if (!c.dry) {  // real pass only: the event join, in front of decode_tail - its recurrences find the device empty
+            QA_HIP(hipEventRecord(h->ev_join, h->side));
+            QA_HIP(hipStreamWaitEvent(c.stream, h->ev_join, 0));
+        }
+    } else {
+        QA_TRY(mimi_op(c, h->bottleneck, cat, B, N, kvalid));
+    }
     c.tap("dec.bottleneck", cat, rows * 2 * D);
     return decode_tail(h, c, cat, tc, wav_out);
 }
@@ -1556,6 +1607,9 @@ int qa_hcodec_forward_adaptive(qa_hcodec* h, const float* wav, int64_t B, int64_
     *n_groups = G;
     return QA_OK;
 }
+
+// diagnostics (tests): regions of all H-Codec calls of the process that ran as two half-batch lanes (QA_BATCH_SPLIT) so far
+long long qa_debug_batch_split_regions(void) { return qa::g_split_regions.load(std::memory_order_relaxed); }
 
 int qa_hcodec_enable_taps(qa_hcodec* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_hcodec_enable_taps", on); }
 

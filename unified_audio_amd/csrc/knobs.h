@@ -23,6 +23,8 @@ namespace qa {
     X(ATT_MATH, "QA_ATT_MATH", 1, "attention arithmetic: 1 = split-6 (Q, K, V and the probabilities as three bf16 planes, six v_mfma_f32_32x32x16_bf16 per 16-wide k group, fp32 accumulation), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32); the UniSE LM keeps the fp32 chain either way") \
     X(ATT_DEBUG, "QA_ATT_DEBUG", 0, "attention_kernel debug bits, both forms: 1 always rescale, 2 extra barrier per tile, 4 wait for the prefetch at once, 8 no wave-uniform tile skip, 16 mask every tile; the split-6 form (SPLIT) only (tests): 32 / 64 / 128 zero the h / m / l plane of the operands selected by 256 Q, 512 K, 1024 V, 2048 P (none of the four: all)") \
     X(AGG_LAST_ROWS, "QA_AGG_LAST_ROWS", 1, "H-Codec 1.5 encode: the last layer of each aggregator stack runs attention, out_proj, LayerNorm 2, lin1 and lin2 on the G query rows per clip only (the rows the read-out keeps); 0 = the full last layer; same bits either way") \
+    X(BATCH_SPLIT, "QA_BATCH_SPLIT", 1, "H-Codec: a one-stream phase as two half-batch lanes on two streams - clips [0, ceil(B / 2)) on the caller's stream, the rest on an internal one, enqueued layer by layer and joined before the next recurrence (bit mask): 1 = the H-Codec 1.5 bottleneck transformer (32 x 10 s: 97.5 -> 96.1 ms per step); 0 = one lane; one lane as well for B = 1, under QA_SERIAL and with taps on; same bits either way") \
+    X(BATCH_SPLIT_MIN_ROWS, "QA_BATCH_SPLIT_MIN_ROWS", 500, "QA_BATCH_SPLIT: fewest rows (clips x frames) of the smaller lane at which a region is split (10 s clips: lanes of 250 rows lose 0.5 ms, 500 rows gain 0.3 ms; tests: 0)") \
     X(SEANET_FUSED, "QA_SEANET_FUSED", 1, "fused conv0 + first SEANet residual block")                                           \
     X(MIMI_ROPE_WINDOW, "QA_MIMI_ROPE_WINDOW", 8192, "mimi streaming: positions covered by the RoPE table before the rolling window takes over (tests shrink it)") \
     X(LSTM_GRAPH, "QA_LSTM_GRAPH", 1, "replay the T step launches of an LSTM call from a cached hipGraph")                       \
