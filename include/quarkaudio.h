@@ -331,6 +331,11 @@ int qa_set_serial(int32_t on);
  * call's recurrence was in flight (the co-residency ticket: two handles driving one device never starve each other's grid barrier),
  * out[3] 1 once a barrier time-out has degraded the device to the per-step kernels. */
 int qa_debug_lstm_stats(int32_t device, int64_t* out4);
+/* One LSTM recurrence alone, as a model graph issues it (tests): xw [B, T, 4d] = x W_ih^T + b_ih + b_hh and w_hh [4d, d] with the 4d
+ * axis in (unit, gate) order, h_out [B, T, d], c_state [B, d] scratch; zero initial state.  The library chooses the kernel as it does
+ * inside a codec call (knobs QA_LSTM_XCD, QA_LSTM_TEAM, QA_LSTM_PERSISTENT).  Waits for an in-launch recurrence and returns an error,
+ * without re-running on the per-step kernels, if its step barrier timed out. */
+int qa_debug_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, void* stream);
 /* Attention launches the host has issued in this process so far, by arithmetic (tests): out2[0] the fp32 chain (QA_ATT_MATH = 0, and
  * every launch of a UniSE LM handle), out2[1] split-6.  Counted where the host launches: a launch recorded into a captured graph counts
  * once, at capture, and its replays do not count. */

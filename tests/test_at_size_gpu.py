@@ -164,7 +164,7 @@ def test_persistent_lstm_forced_on_matches_per_step_and_torch(qa_lib, gpu_device
 
 @pytest.mark.parametrize("d,B,T,mode", [(512, 32, 500, 1), (512, 32, 500, 2), (768, 20, 250, 2), (512, 5, 64, 2), (768, 33, 96, 1)])
 def test_xcd_local_lstm_matches_per_step_and_torch(qa_lib, gpu_device, knob, capfd, d, B, T, mode):
-    """QA_LSTM_XCD (lstm.hip lstm_xcd_kernel): W_hh resident in the registers of every XCD's 32 CUs, the sequences dealt to the XCDs,
+    """QA_LSTM_XCD (lstm.hip lstm_team_kernel, XCD = true): W_hh resident in the registers of every XCD's 32 CUs, the sequences dealt to the XCDs,
     the step barrier inside one XCD.  Inside a real transformer layer of the codec: rnn tap and waveform against the per-step
     kernels (another K-split order: close, not bit-identical) and against torch.nn.LSTM through the oracle's transformer; B = 33 takes
     two launches, B = 5 leaves three XCD teams without a sequence."""
@@ -208,7 +208,7 @@ def test_xcd_local_lstm_matches_per_step_and_torch(qa_lib, gpu_device, knob, cap
 
 @pytest.mark.parametrize("d,B,T", [(1024, 32, 500), (1024, 17, 64), (1024, 40, 32)])
 def test_team_lstm_matches_per_step_and_torch(qa_lib, gpu_device, knob, capfd, d, B, T):
-    """QA_LSTM_TEAM (lstm.hip lstm_team_kernel): the d = 1024 recurrence (H-Codec 1.5 decoder) on 4 teams of 64 workgroups, W_hh in
+    """QA_LSTM_TEAM (lstm.hip lstm_team_kernel, XCD = false): the d = 1024 recurrence (H-Codec 1.5 decoder) on 4 teams of 64 workgroups, W_hh in
     registers - same checks as the XCD-local kernel's test: against the per-step kernels (another summation order: close, not equal),
     torch.nn.LSTM through the oracle, rows alone == rows in the batch, more sequences than one launch holds (40 > 32), idle team slots
     (17).  (The d = 1536 instantiation - 2 teams of 128 x 12 waves - passed the same checks in r05 and was removed as slower than
@@ -253,7 +253,8 @@ def test_persistent_lstm_barrier_timeout_is_recovered_in_the_same_call(qa_lib, g
     starves it) used to return garbage with QA_OK and report the error one LSTM call later.  Now the call that hit it waits for
     its stream, sees ITS error word and re-runs on the per-step kernels.  QA_LSTM_FAULT makes the barrier wait for a workgroup that
     does not exist; QA_LSTM_SPIN_LIMIT shortens the bounded spin from seconds to milliseconds.  All three in-launch recurrences:
-    lstm_persistent_kernel, lstm_xcd_kernel (d = 512) and lstm_team_kernel (d = 1024, the default of the H-Codec 1.5 decoder)."""
+    lstm_persistent_kernel and lstm_team_kernel in both forms (one team per XCD at d = 512; 4 teams of 64 at d = 1024, the default of the
+    H-Codec 1.5 decoder)."""
     import dataclasses
 
     import unified_audio_amd as qa

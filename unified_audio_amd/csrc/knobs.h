@@ -29,10 +29,10 @@ namespace qa {
     X(MIMI_ROPE_WINDOW, "QA_MIMI_ROPE_WINDOW", 8192, "mimi streaming: positions covered by the RoPE table before the rolling window takes over (tests shrink it)") \
     X(LSTM_GRAPH, "QA_LSTM_GRAPH", 1, "replay the T step launches of an LSTM call from a cached hipGraph")                       \
     X(LSTM_PERSISTENT, "QA_LSTM_PERSISTENT", -1, "persistent recurrence kernel: -1 auto (d >= 1536), 0 off, 1 on for every supported width") \
-    X(LSTM_XCD, "QA_LSTM_XCD", 1, "XCD-local LSTM recurrence for d = 512 / 768 (one launch, W_hh in the registers of every XCD's 32 CUs, sequences dealt to the XCDs, 32-member step barrier per XCD): 0 off (the per-step kernels), 1 agent-scope hand-off forms, 2 XCD-local forms (h stores that stay in the XCD's L2; H-Codec 1.0: 42.7 against 43.3 ms)") \
-    X(LSTM_TEAM, "QA_LSTM_TEAM", 1, "team recurrence for d = 1024 (one launch: 4 teams of 64 workgroups, W_hh resident in registers, 8 sequences per team, agent-scope hand-offs; H-Codec 1.5 decoder: 134.1 -> 128.3 ms per step, profiles/r04_lstm_team_ab.txt): 0 = the per-step kernels") \
+    X(LSTM_XCD, "QA_LSTM_XCD", 1, "XCD-local LSTM recurrence for d = 512 / 768 (lstm_team_kernel with one team per XCD: one launch, W_hh in the registers of every XCD's 32 CUs, sequences dealt to the XCDs, 32-member step barrier per XCD): 0 off (the per-step kernels), 1 agent-scope hand-off forms, 2 XCD-local forms (h stores that stay in the XCD's L2; H-Codec 1.0: 42.7 against 43.3 ms)") \
+    X(LSTM_TEAM, "QA_LSTM_TEAM", 1, "team recurrence for d = 1024 (lstm_team_kernel, one launch: 4 teams of 64 workgroups, W_hh resident in registers, 8 sequences per team, agent-scope hand-offs; H-Codec 1.5 decoder: 134.1 -> 128.3 ms per step, profiles/r04_lstm_team_ab.txt): 0 = the per-step kernels") \
     X(LSTM_SPIN_LIMIT, "QA_LSTM_SPIN_LIMIT", 1 << 21, "persistent recurrence: polls of a barrier word before the barrier is declared broken") \
-    X(LSTM_FAULT, "QA_LSTM_FAULT", 0, "1 (tests): the persistent kernel's barrier waits for a workgroup that does not exist, like a starved launch") \
+    X(LSTM_FAULT, "QA_LSTM_FAULT", 0, "1 (tests): the step barrier of every in-launch recurrence (lstm_persistent_kernel, lstm_team_kernel) waits for one workgroup more than exists, like a starved launch") \
     X(LM_GRAPH, "QA_LM_GRAPH", 0, "1: replay one captured decode step per token")                                                \
     X(LM_MLP_FUSED, "QA_LM_MLP_FUSED", 1, "decode step: gate/up + SwiGLU + down of 16 activation columns per workgroup in one launch emitting K-slice partials, summed by a reduce launch (0: separate gate/up and down launches)") \
     X(LM_PF, "QA_LM_PF", 7, "decode step: cross-launch L2 weight prefetch planes (bit mask; lm_decode.h PfArgs): 1 qkv launch -> o_proj weights, 2 o_proj launch -> fused-MLP weights, 4 MLP launch -> next layer's qkv weights (last layer: the head slice), 8 head launch -> layer 0 qkv weights") \

@@ -13,8 +13,9 @@
 // v_mfma_f32_16x16x4_f32 with batch as the M dimension, reduces the 8 partial tiles through LDS and applies the
 // cell update in the same kernel, so gates never touch HBM.
 //
-// XCD-local variant (lstm_xcd_kernel, further down; default for d = 512 / 768, QA_LSTM_XCD): every XCD keeps a copy of W_hh in the
-// registers of its 32 CUs and runs its share of the batch rows alone - 2.3 / 2.8 us per step against 6.2 / 7.5 us.
+// Team variant (lstm_team_kernel, further down; ONE kernel body, three instances; default for d = 512 / 768 under QA_LSTM_XCD and for
+// d = 1024 under QA_LSTM_TEAM): one launch for all T steps, teams of 32 / 64 workgroups (one XCD / two XCDs' worth) that each keep a
+// copy of W_hh in registers and run their share of the batch rows alone - 2.3 / 2.8 / 5.4 us per step against 6.2 / 7.5 / 9.7 us.
 //
 // Persistent variant (lstm_persistent_kernel, measured in tools/micro/lstm_persistent.hip: 14.7 -> 8.7 us per step at d = 1536 / B = 16,
 // 10.05 -> 9.1 at d = 1024 / B = 32, equal at 768, slower at 512): ONE launch for all T steps, d / U workgroups (<= CU count, all
@@ -321,22 +322,34 @@ __global__ __launch_bounds__(512) void lstm_persistent_kernel(const float* __res
     if (epi) c_state[(long long)eb * d + unit] = c_reg;
 }
 
-// ------------------------------------------------------------------------------------------------ XCD-local recurrence (QA_LSTM_XCD)
-// The batch rows of an LSTM are independent recurrences and a d <= 768 W_hh (4.2 / 9.4 MB) fits the REGISTERS of the 32 CUs of ONE
-// XCD.  So: one launch for all T steps, one workgroup per CU, and the workgroups that land on XCD x (s_getreg HW_REG_XCC_ID - read
-// from the hardware, never assumed from blockIdx) form TEAM x.  Every team keeps its own copy of the whole W_hh in registers (a
-// workgroup: U = d / 32 hidden units = 4 U gate rows) and runs the sequences b = x, x + 8, x + 16, ... of the call all by itself: no
-// exchange between XCDs at all, a step's h_t travels through the team's own L2, and the per-step barrier has 32 participants on one
-// counter in that L2 (~1 us) instead of 256 over the fabric (~4 us).  Matrix work on v_mfma_f32_4x4x1_16b_f32: block = hidden unit
-// (A: lane & 3 = gate row of the unit, resident weights), B: lane & 3 = sequence of the team (h_{t-1} from LDS); lane (unit, q) ends
-// with the unit's 4 gate pre-activations of sequence q.  K is split over the waves; partials meet in LDS in a fixed order
-// (deterministic; a row's arithmetic does not depend on the batch).
-//   QA_LSTM_XCD = 1: agent-scope forms (sc1 write-through h stores, agent atomics) - valid wherever the workgroups sit;
-//   QA_LSTM_XCD = 2: XCD-local forms (plain h stores that stay in the team's L2, workgroup-scope atomic executed in that L2) -
-//                    relies on what defines a team: its members share one L2.  Loads of h / the counter bypass L1 (sc1) in both.
-// Needs 32 resident workgroups per XCD: a surplus or missing member trips the bounded spins -> error word -> the calling model
-// graph re-runs the call on the per-step kernels (run_graph_checked), exactly like lstm_persistent_kernel.
+// ------------------------------------------------------------------------------------------------ team recurrence (QA_LSTM_XCD, QA_LSTM_TEAM)
+// The batch rows of an LSTM are independent recurrences, so: one launch for all T steps, one workgroup per CU, and the workgroups form
+// TEAMS of PT members.  Every team keeps its own copy of the whole W_hh in registers (a workgroup: U = d / PT hidden units = 4 U gate
+// rows, in RG row groups of 64 where 4 U > 64) and runs the sequences b = team, team + n_teams, ... of the call all by itself, 4 SG
+// of them per launch: no exchange between teams at all, and the per-step barrier is ONE PT-member counter.  Matrix work on
+// v_mfma_f32_4x4x1_16b_f32: block = hidden unit (A: lane & 3 = gate row of the unit, resident weights), B: lane & 3 = sequence of the
+// team (h_{t-1} from LDS); lane (unit, q) ends with the unit's 4 gate pre-activations of sequence q + 4 g (SG chains per wave: the
+// resident A operand is used SG times).  K is split over the waves; partials meet in LDS in a fixed order (deterministic; a row's
+// arithmetic does not depend on the batch).  Every hand-off uses the agent-scope forms: sc1 write-through h stores, drained vmcnt,
+// agent atomic on the team's counter, sc1 loads of h and of the counter.
+//   XCD = true (d = 512 / 768: W_hh, 4.2 / 9.4 MB, fits the REGISTERS of the 32 CUs of ONE XCD; 2.3 / 2.8 us per step against 6.2 /
+//     7.5): the workgroups that land on XCD x (s_getreg HW_REG_XCC_ID - read from the hardware, never assumed from blockIdx) form
+//     team x and take their slot from a counter; a step's h_t travels through the team's own L2 and the counter lives there (~1 us
+//     against ~4 us over the fabric).  A surplus member on an XCD (so another team is short of one) sets the error words and leaves.
+//     QA_LSTM_XCD = 2 (`fast`) adds the XCD-local forms - plain h stores that stay in the team's L2, workgroup-scope atomic executed
+//     in that L2 - which rely on what defines such a team: its members share one L2.
+//   XCD = false (d = 1024: 64 members = two XCDs' worth of register files per copy of W_hh, four teams; 5.4 us per step against 9.7,
+//     profiles/r04_lstm_team_ab.txt; MFMA floor at B = 32: 2 us): team = blockIdx % n_teams, slot = blockIdx / n_teams - nothing
+//     depends on where a workgroup lands.  (The 128-member / two-team form for d = 1536 lost to lstm_persistent_kernel in r05,
+//     ~10 against 8.5 us per step - a 128-member arrival counter alone is ~1.5 us of serialised atomics,
+//     profiles/r05_lstm_team1536_ab.txt - and was removed.)
+// Needs every member resident at once: a missing one trips the bounded spins -> error word -> the calling model graph re-runs the call
+// on the per-step kernels (run_graph_checked), exactly like lstm_persistent_kernel.  QA_LSTM_FAULT (tests): the waiters wait for
+// PT + 1 arrivals per step.
 enum { SX_SLOT = 0, SX_CNT = 8 };  // sync lines: team slot counters [8], team arrive counters [8], SY_ERR
+// dynamic LDS of every instance: h_{t-1} of the team's sequences (static LDS stops at 64 KB) + padding nobody touches, so that ONE
+// workgroup fits a CU (more than half of its 160 KB) and the grid spreads one per CU, 32 per XCD
+constexpr int LSTM_TEAM_DYN_LDS = 96 * 1024;
 
 __device__ __forceinline__ unsigned xcc_id() {
     unsigned v;
@@ -344,36 +357,44 @@ __device__ __forceinline__ unsigned xcc_id() {
     return v & 15u;
 }
 
-template <int D, int NW>
-__global__ __launch_bounds__(NW * 64, 1) void lstm_xcd_kernel(const float* __restrict__ xw, const float* __restrict__ w_hh, float* h_out,
-                                                               float* __restrict__ c_state, int B, int T, unsigned* sy, int per_team,
-                                                               int n_teams, unsigned* err_host, unsigned spin_limit, int fast) {
-    constexpr int U = D / 32, R = 4 * U, RG = (R + 63) / 64, KS = NW / RG, KW = D / KS, NQ = 4, LDH = D + 4;
-    static_assert(NW % RG == 0 && D % KS == 0 && KW % 4 == 0 && NQ * D / 4 == NW * 64, "lstm_xcd: shape does not tile");
-    __shared__ __attribute__((aligned(16))) float s_h[NQ][LDH];           // h_{t-1} of the team's sequences (rows 16 B apart in bank phase)
-    __shared__ __attribute__((aligned(16))) float s_part[KS][RG * 64][4];  // [K slice][unit * 4 + q][gate]
-    __shared__ int s_ctl[3];
-    extern __shared__ float s_pad[];  // unused: sized by the host so that ONE workgroup fits a CU
+template <int D, int NW, int PT, int SG, bool XCD>
+__global__ __launch_bounds__(NW * 64, 1) void lstm_team_kernel(const float* __restrict__ xw, const float* __restrict__ w_hh, float* h_out,
+                                                                float* __restrict__ c_state, int B, int T, unsigned* sy, int n_teams, int fault,
+                                                                unsigned* err_host, unsigned spin_limit, int fast) {
+    constexpr int U = D / PT, R = 4 * U, RG = (R + 63) / 64, KS = NW / RG, KW = D / KS, NQ = 4 * SG, LDH = D + 4, F4 = NQ * D / 4 / (NW * 64);
+    static_assert(D % PT == 0 && NW % RG == 0 && D % KS == 0 && KW % 4 == 0 && (NQ * D / 4) % (NW * 64) == 0, "lstm_team: shape does not tile");
+    __shared__ __attribute__((aligned(16))) float s_part[KS][RG * 64][SG][4];  // [K slice][unit * 4 + q][sequence group][gate]
+    __shared__ int s_ctl[3];                                                   // team, slot (XCD), verdict of the step's wait
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+    float (*s_h)[LDH] = reinterpret_cast<float (*)[LDH]>(s_dyn);  // h_{t-1} of the team's sequences (rows 16 B apart in bank phase)
+    static_assert(NQ * LDH * 4 <= LSTM_TEAM_DYN_LDS, "lstm_team: h staging does not fit the dynamic segment");
+    static_assert(sizeof(s_part) + sizeof(s_ctl) + LSTM_TEAM_DYN_LDS > 80 * 1024, "lstm_team: two workgroups would fit one CU");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rg = wave % RG, ks = wave / RG;
-    if (tid == 0) {
-        const unsigned x = xcc_id();
-        s_ctl[0] = (int)x;
-        s_ctl[1] = x < 8u ? (int)__hip_atomic_fetch_add(sy + (SX_SLOT + x) * SY_STRIDE, 1u, QA_RLX) : per_team;
-    }
-    __syncthreads();
-    const int team = s_ctl[0], slot = s_ctl[1];
     unsigned* err = sy + SY_ERR * SY_STRIDE;
-    if (slot >= per_team || team >= n_teams) {  // a 33rd workgroup on this XCD (so another team is short of one): nobody can finish
+    int team, slot;
+    if constexpr (XCD) {
         if (tid == 0) {
-            __hip_atomic_store(err, 1u, QA_RLX);
-            __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const unsigned x = xcc_id();
+            s_ctl[0] = (int)x;
+            s_ctl[1] = x < 8u ? (int)__hip_atomic_fetch_add(sy + (SX_SLOT + x) * SY_STRIDE, 1u, QA_RLX) : PT;
         }
-        return;
+        __syncthreads();
+        team = s_ctl[0], slot = s_ctl[1];
+        if (slot >= PT || team >= n_teams) {  // a 33rd workgroup on this XCD (so another team is short of one): nobody can finish
+            if (tid == 0) {
+                __hip_atomic_store(err, 1u, QA_RLX);
+                __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            return;
+        }
+    } else {
+        team = blockIdx.x % n_teams, slot = blockIdx.x / n_teams;
     }
     const int nq = min(NQ, (B - team + n_teams - 1) / n_teams);  // this team's sequences: b = team + n_teams * q
     if (nq <= 0) return;
     unsigned* cnt = sy + (SX_CNT + team) * SY_STRIDE;
+    const unsigned members = (unsigned)(PT + fault);  // QA_LSTM_FAULT: wait for a member that does not exist
 
     // resident weights: lane = gate row (unit-major, gate-minor: the load-time permutation) of row group rg, K slice ks
     const int lrow = rg * 64 + lane;
@@ -386,132 +407,40 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_xcd_kernel(const float* __res
             wreg[4 * j] = v.x; wreg[4 * j + 1] = v.y; wreg[4 * j + 2] = v.z; wreg[4 * j + 3] = v.w;
         }
     }
-    // epilogue lane (waves of K slice 0): hidden unit of the team slot, sequence q
+    // epilogue lane (waves of K slice 0): hidden unit of the team slot, sequences q + 4 g
     const int q = lane & 3, ul = rg * 16 + (lane >> 2);
-    const bool epi = ks == 0 && ul < U && q < nq;
-    const int unit = slot * U + min(ul, U - 1);
-    const int eb = team + n_teams * min(q, nq - 1);
-    // staging share of this thread: one float4 of h_{t-1}
-    const int sq = tid / (D / 4), sc4 = tid % (D / 4);
-    const int sb = team + n_teams * min(sq, nq - 1);
-    float c_reg = 0.f;
-    for (int t = 0; t < T; ++t) {
-        float4 xg = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (epi) xg = *reinterpret_cast<const float4*>(xw + ((long long)eb * T + t) * 4 * D + (long long)unit * 4);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (t > 0) {
-            if (tid == 0) s_ctl[2] = lstm_spin_until(cnt, (unsigned)(per_team * t), err, err_host, spin_limit) ? 1 : 0;
-            __syncthreads();
-            if (!s_ctl[2]) break;  // uniform: a broken barrier ends the call for the whole workgroup (the error words are set)
-            asm volatile("" ::: "memory");
-            f32x4 hv = lstm_load_sc1_b128(h_out + ((long long)sb * T + (t - 1)) * D + 4 * sc4);
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(hv)::"memory");
-            *reinterpret_cast<f32x4*>(&s_h[sq][4 * sc4]) = hv;
-            __syncthreads();
-            const float* hq = &s_h[q][ks * KW];
-#pragma unroll
-            for (int j = 0; j < KW / 4; ++j) {
-                const float4 hb = *reinterpret_cast<const float4*>(hq + 4 * j);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * j], hb.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * j + 1], hb.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * j + 2], hb.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[4 * j + 3], hb.w, acc, 0, 0, 0);
-            }
-            *reinterpret_cast<f32x4*>(&s_part[ks][rg * 64 + lane][0]) = acc;
-            __syncthreads();
-        }
-        if (epi) {
-            f32x4 g = {xg.x, xg.y, xg.z, xg.w};
-            if (t > 0) {
-#pragma unroll
-                for (int k = 0; k < KS; ++k) g += *reinterpret_cast<const f32x4*>(&s_part[k][rg * 64 + lane][0]);
-            }
-            const float ig = sigmoid_f(g[0]), fg = sigmoid_f(g[1]), gg = tanhf(g[2]), og = sigmoid_f(g[3]);
-            c_reg = fg * c_reg + ig * gg;
-            unsigned* dst = reinterpret_cast<unsigned*>(h_out + ((long long)eb * T + t) * D + unit);
-            const unsigned hbits = __float_as_uint(og * tanhf(c_reg));
-            if (fast) __hip_atomic_store(dst, hbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // plain store: stays in this XCD's L2
-            else __hip_atomic_store(dst, hbits, QA_RLX);                                               // sc1: write-through
-        }
-        if (t + 1 < T) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the storing waves drain before the workgroup reports the step done
-            __syncthreads();
-            if (tid == 0) {
-                if (fast) (void)__hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                else (void)__hip_atomic_fetch_add(cnt, 1u, QA_RLX);
-            }
-        }
-    }
-    if (epi) c_state[(long long)eb * D + unit] = c_reg;
-}
-
-// ------------------------------------------------------------------------------------------------ team recurrence for wider layers
-// QA_LSTM_TEAM (default 1 since r04: parity green on MI355X, 5.4 us per step against 9.7 for the per-step kernel at d = 1024,
-// profiles/r04_lstm_team_ab.txt).  The XCD-local idea for widths whose W_hh does not fit ONE XCD's registers: a team is PT
-// workgroups (64 at d = 1024: two XCDs' worth of register files per copy of W_hh, four teams; the 128-workgroup / two-team form for d = 1536 lost to lstm_persistent_kernel in r05), team =
-// blockIdx % n_teams, slot = blockIdx / n_teams - nothing depends on where a workgroup lands, because every hand-off uses the
-// agent-scope forms (sc1 write-through stores, drained vmcnt, agent atomic on the team's counter, sc1 loads).  A team runs
-// 4 SG sequences (two MFMA chains per wave at SG = 2: the resident A operand is used twice), so B = 32 at d = 1024 is ONE launch.
-// Per step: one PT-member counter + 4 SG x d x 4 bytes of h per workgroup + KW x SG 4x4x1 MFMAs per wave (MFMA floor at
-// d = 1024 / B = 32: 2 us per step; the per-step kernel takes 9.7 us).
-template <int D, int NW, int PT, int SG>
-__global__ __launch_bounds__(NW * 64, 1) void lstm_team_kernel(const float* __restrict__ xw, const float* __restrict__ w_hh, float* h_out,
-                                                                float* __restrict__ c_state, int B, int T, unsigned* sy, int n_teams, int fault,
-                                                                unsigned* err_host, unsigned spin_limit) {
-    constexpr int U = D / PT, R = 4 * U, KS = NW, KW = D / KS, NQ = 4 * SG, LDH = D + 4, F4 = NQ * D / 4 / (NW * 64);
-    static_assert(R <= 64 && D % PT == 0 && D % KS == 0 && KW % 4 == 0 && (NQ * D / 4) % (NW * 64) == 0, "lstm_team: shape does not tile");
-    __shared__ __attribute__((aligned(16))) float s_part[KS][64][SG][4];  // [K slice][unit * 4 + q][sequence group][gate]
-    __shared__ int s_ok;
-    // h_{t-1} of the team's sequences lives in the DYNAMIC segment (49 KB at d = 1536: static LDS stops at 64 KB); the host sizes that
-    // segment beyond it so that ONE workgroup fits a CU
-    extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-    float (*s_h)[LDH] = reinterpret_cast<float (*)[LDH]>(s_dyn);
-    const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
-    const int team = blockIdx.x % n_teams, slot = blockIdx.x / n_teams;
-    unsigned* err = sy + SY_ERR * SY_STRIDE;
-    const int nq = min(NQ, (B - team + n_teams - 1) / n_teams);  // this team's sequences: b = team + n_teams * q
-    if (nq <= 0) return;
-    unsigned* cnt = sy + (SX_CNT + team) * SY_STRIDE;
-    const unsigned members = (unsigned)(PT + fault);  // QA_LSTM_FAULT: wait for a member that does not exist
-
-    float wreg[KW];
-    {
-        const float* wrow = w_hh + ((long long)slot * R + min(lane, R - 1)) * D + ks * KW;
-#pragma unroll
-        for (int j = 0; j < KW / 4; ++j) {
-            const float4 v = *reinterpret_cast<const float4*>(wrow + 4 * j);
-            wreg[4 * j] = v.x; wreg[4 * j + 1] = v.y; wreg[4 * j + 2] = v.z; wreg[4 * j + 3] = v.w;
-        }
-    }
-    const int q = lane & 3, ul = lane >> 2;
     const bool epi_wave = ks == 0 && ul < U;
     const int unit = slot * U + min(ul, U - 1);
     float c_reg[SG];
 #pragma unroll
     for (int g = 0; g < SG; ++g) c_reg[g] = 0.f;
+    // staging share of this thread: F4 float4 of h_{t-1}; an absent sequence stages the team's last one again
+    const float* hsrc[F4];
+#pragma unroll
+    for (int i = 0; i < F4; ++i) {
+        const int f = tid + i * NW * 64, sq = f / (D / 4), sc4 = f % (D / 4);
+        hsrc[i] = h_out + (long long)(team + n_teams * min(sq, nq - 1)) * T * D + 4 * sc4;
+    }
     for (int t = 0; t < T; ++t) {
         float4 xg[SG];
 #pragma unroll
         for (int g = 0; g < SG; ++g) {
             xg[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (epi_wave && q + 4 * g < nq)
-                xg[g] = *reinterpret_cast<const float4*>(xw + ((long long)(team + n_teams * (q + 4 * g)) * T + t) * 4 * D + (long long)unit * 4);
+            if (epi_wave && q + 4 * g < nq)  // (the clamp keeps the address arithmetic off the branch: two VGPRs at d = 768, which has none to spare)
+                xg[g] = *reinterpret_cast<const float4*>(xw + ((long long)(team + n_teams * min(q + 4 * g, nq - 1)) * T + t) * 4 * D + (long long)unit * 4);
         }
         f32x4 acc[SG];
 #pragma unroll
         for (int g = 0; g < SG; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (t > 0) {
-            if (tid == 0) s_ok = lstm_spin_until(cnt, members * (unsigned)t, err, err_host, spin_limit) ? 1 : 0;
+            if (tid == 0) s_ctl[2] = lstm_spin_until(cnt, members * (unsigned)t, err, err_host, spin_limit) ? 1 : 0;
             __syncthreads();
-            if (!s_ok) break;
+            if (!s_ctl[2]) break;  // uniform: a broken barrier ends the call for the whole workgroup (the error words are set)
             asm volatile("" ::: "memory");
-            {
+            {  // every load in flight at once
                 f32x4 hv[F4];
 #pragma unroll
-                for (int i = 0; i < F4; ++i) {
-                    const int f = tid + i * NW * 64, sq = f / (D / 4), sc4 = f % (D / 4);
-                    hv[i] = lstm_load_sc1_b128(h_out + ((long long)(team + n_teams * min(sq, nq - 1)) * T + (t - 1)) * D + 4 * sc4);
-                }
+                for (int i = 0; i < F4; ++i) hv[i] = lstm_load_sc1_b128(hsrc[i] + (long long)(t - 1) * D);
 #pragma unroll
                 for (int i = 0; i < F4; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(hv[i])::"memory");
 #pragma unroll
@@ -533,7 +462,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_team_kernel(const float* __re
                 }
             }
 #pragma unroll
-            for (int g = 0; g < SG; ++g) *reinterpret_cast<f32x4*>(&s_part[ks][lane][g][0]) = acc[g];
+            for (int g = 0; g < SG; ++g) *reinterpret_cast<f32x4*>(&s_part[ks][lrow][g][0]) = acc[g];
             __syncthreads();
         }
         if (epi_wave) {
@@ -543,18 +472,23 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_team_kernel(const float* __re
                 f32x4 gt = {xg[g].x, xg[g].y, xg[g].z, xg[g].w};
                 if (t > 0) {
 #pragma unroll
-                    for (int k = 0; k < KS; ++k) gt += *reinterpret_cast<const f32x4*>(&s_part[k][lane][g][0]);
+                    for (int k = 0; k < KS; ++k) gt += *reinterpret_cast<const f32x4*>(&s_part[k][lrow][g][0]);
                 }
                 const float ig = sigmoid_f(gt[0]), fg = sigmoid_f(gt[1]), gg = tanhf(gt[2]), og = sigmoid_f(gt[3]);
                 c_reg[g] = fg * c_reg[g] + ig * gg;
-                const int b = team + n_teams * (q + 4 * g);
-                __hip_atomic_store(reinterpret_cast<unsigned*>(h_out + ((long long)b * T + t) * D + unit), __float_as_uint(og * tanhf(c_reg[g])), QA_RLX);
+                unsigned* dst = reinterpret_cast<unsigned*>(h_out + ((long long)(team + n_teams * (q + 4 * g)) * T + t) * D + unit);
+                const unsigned hbits = __float_as_uint(og * tanhf(c_reg[g]));
+                if (XCD && fast) __hip_atomic_store(dst, hbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // plain store: stays in this XCD's L2
+                else __hip_atomic_store(dst, hbits, QA_RLX);                                                      // sc1: write-through
             }
         }
         if (t + 1 < T) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the storing waves drain before the workgroup reports the step done
             __syncthreads();
-            if (tid == 0) (void)__hip_atomic_fetch_add(cnt, 1u, QA_RLX);
+            if (tid == 0) {
+                if (XCD && fast) (void)__hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                else (void)__hip_atomic_fetch_add(cnt, 1u, QA_RLX);
+            }
         }
     }
     if (epi_wave) {
@@ -661,6 +595,17 @@ static int lstm_persistent_prepare(LstmPersistentDev& P, int dev) {
     return QA_OK;
 }
 
+// QA_LSTM_SPIN_LIMIT, clamped to what a poll counter can hold and a barrier needs
+static unsigned lstm_spin_limit() { return (unsigned)std::max<long long>(64, std::min<long long>(knob(K_LSTM_SPIN_LIMIT), 1LL << 30)); }
+
+// the sync block of the next in-launch recurrence: the ring's next one, with every polled word zeroed on `s` in front of EVERY launch
+static int lstm_arm_sync(LstmPersistentDev& P, hipStream_t s, unsigned** sy) {
+    *sy = P.sync + (size_t)P.next * SY_WORDS * SY_STRIDE;
+    P.next = (P.next + 1) % LSTM_SYNC_RING;
+    QA_HIP(hipMemsetAsync(*sy, 0, sizeof(unsigned) * SY_WORDS * SY_STRIDE, s));
+    return QA_OK;
+}
+
 // returns QA_OK and sets *done = true when the persistent kernel took the call; *done = false: shape / device not eligible
 static int launch_lstm_persistent(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, hipStream_t s,
                                   int dev, bool* done) {
@@ -677,16 +622,15 @@ static int launch_lstm_persistent(const float* xw, const float* w_hh_ug, float* 
     if (U > 8 || NT > 2 || (NT == 1 && d == 1536)) return QA_OK;
     // QA_LSTM_FAULT (tests): the barrier waits for one workgroup more than exists, i.e. what a starved launch looks like
     const int nwg = d / U, ngrp = 8, per_grp = nwg / ngrp + (knob(K_LSTM_FAULT) ? 1 : 0);
-    const unsigned spin_limit = (unsigned)std::max<long long>(64, std::min<long long>(knob(K_LSTM_SPIN_LIMIT), 1LL << 30));
+    const unsigned spin_limit = lstm_spin_limit();
     unsigned* const err_word = lstm_err_word(P, dev);
     for (int b0 = 0; b0 < B; b0 += 32) {
         const int bn = std::min(32, B - b0);
         const float* xw_b = xw + (long long)b0 * T * 4 * d;
         float* h_b = h_out + (long long)b0 * T * d;
         float* c_b = c_state + (long long)b0 * d;
-        unsigned* sy = P.sync + (size_t)P.next * SY_WORDS * SY_STRIDE;
-        P.next = (P.next + 1) % LSTM_SYNC_RING;
-        QA_HIP(hipMemsetAsync(sy, 0, sizeof(unsigned) * SY_WORDS * SY_STRIDE, s));  // every polled word, before EVERY launch
+        unsigned* sy = nullptr;
+        QA_TRY(lstm_arm_sync(P, s, &sy));
 #define QA_LP(MT, NT_, NI) \
     hipLaunchKernelGGL((lstm_persistent_kernel<MT, NT_, NI>), dim3(nwg), dim3(512), 0, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, U, sy, ngrp, per_grp, err_word, spin_limit)
         const bool two = bn > 16;
@@ -705,80 +649,42 @@ static int launch_lstm_persistent(const float* xw, const float* w_hh_ug, float* 
     return QA_OK;
 }
 
-// QA_LSTM_XCD: the XCD-local recurrence for the widths whose W_hh fits one XCD's registers (d = 512 / 768); *done as above
-static int launch_lstm_xcd(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, hipStream_t s, int dev,
-                           bool* done) {
-    *done = false;
-    const int mode = (int)knob(K_LSTM_XCD);
-    LstmPersistentDev& P = g_lstm_p[dev];
-    if (t_lstm_per_step || mode <= 0 || P.degraded || !(d == 512 || d == 768) || T < 2) return QA_OK;
-    QA_TRY(lstm_persistent_prepare(P, dev));
-    const int per_team = 32, n_teams = P.cus / per_team;
-    if (n_teams < 1 || n_teams > 8 || P.cus % per_team) return QA_OK;
-    const unsigned spin_limit = (unsigned)std::max<long long>(64, std::min<long long>(knob(K_LSTM_SPIN_LIMIT), 1LL << 30));
-    const int pad = 96 * 1024;  // dynamic LDS nobody touches: ONE workgroup per CU, so the grid spreads 32 per XCD
+// One instance of lstm_team_kernel over the whole device: 4 SG sequences per team and launch, further sequences in further launches
+template <int D, int NW, int PT, int SG, bool XCD>
+static int launch_lstm_team(LstmPersistentDev& P, int dev, const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T,
+                            hipStream_t s, int fast) {
+    const auto kernel = lstm_team_kernel<D, NW, PT, SG, XCD>;
+    QA_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(kernel), LSTM_TEAM_DYN_LDS));
+    const int n_teams = P.cus / PT, per_launch = 4 * SG * n_teams;
     const int fault = knob(K_LSTM_FAULT) ? 1 : 0;
-    if (d == 512) QA_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(lstm_xcd_kernel<512, 8>), pad));
-    else QA_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(lstm_xcd_kernel<768, 12>), pad));
-    for (int b0 = 0; b0 < B; b0 += 4 * n_teams) {
-        const int bn = std::min(4 * n_teams, B - b0);
-        const float* xw_b = xw + (long long)b0 * T * 4 * d;
-        float* h_b = h_out + (long long)b0 * T * d;
-        float* c_b = c_state + (long long)b0 * d;
-        unsigned* sy = P.sync + (size_t)P.next * SY_WORDS * SY_STRIDE;
-        P.next = (P.next + 1) % LSTM_SYNC_RING;
-        QA_HIP(hipMemsetAsync(sy, 0, sizeof(unsigned) * SY_WORDS * SY_STRIDE, s));
-        const dim3 grid((unsigned)(n_teams * per_team));
-        if (d == 512)
-            hipLaunchKernelGGL((lstm_xcd_kernel<512, 8>), grid, dim3(512), pad, s, xw_b, w_hh_ug, h_b, c_b, bn, T, sy, per_team + fault, n_teams,
-                               lstm_err_word(P, dev), spin_limit, mode >= 2 ? 1 : 0);
-        else
-            hipLaunchKernelGGL((lstm_xcd_kernel<768, 12>), grid, dim3(768), pad, s, xw_b, w_hh_ug, h_b, c_b, bn, T, sy, per_team + fault, n_teams,
-                               lstm_err_word(P, dev), spin_limit, mode >= 2 ? 1 : 0);
-        QA_LAUNCH_CHECK();
-        lstm_count_launch(P, dev);
-    }
-    *done = true;
-    return QA_OK;
-}
-
-// QA_LSTM_TEAM: d = 1024 on 4 teams of 64 workgroups - see lstm_team_kernel; *done as above
-template <int D, int PT, int NW>
-static int launch_lstm_team_t(LstmPersistentDev& P, int dev, const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T,
-                              hipStream_t s) {
-    constexpr int SG = 2;
-    const int n_teams = P.cus / PT;
-    const unsigned spin_limit = (unsigned)std::max<long long>(64, std::min<long long>(knob(K_LSTM_SPIN_LIMIT), 1LL << 30));
-    const int dyn = 96 * 1024;  // s_h (4 SG sequences x (D + 4) floats: 33 / 49 KB) + padding: with the static 16 KB one workgroup per CU
-    static_assert(4 * SG * (D + 4) * 4 <= 96 * 1024, "lstm_team: h staging does not fit the dynamic segment");
-    const int fault = knob(K_LSTM_FAULT) ? 1 : 0;
-    QA_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(lstm_team_kernel<D, NW, PT, SG>), dyn));
-    const int per_launch = 4 * SG * n_teams;
+    const unsigned spin_limit = lstm_spin_limit();
     for (int b0 = 0; b0 < B; b0 += per_launch) {
-        const int bn = std::min(per_launch, B - b0);
-        unsigned* sy = P.sync + (size_t)P.next * SY_WORDS * SY_STRIDE;
-        P.next = (P.next + 1) % LSTM_SYNC_RING;
-        QA_HIP(hipMemsetAsync(sy, 0, sizeof(unsigned) * SY_WORDS * SY_STRIDE, s));
-        hipLaunchKernelGGL((lstm_team_kernel<D, NW, PT, SG>), dim3((unsigned)(n_teams * PT)), dim3(NW * 64), dyn, s, xw + (long long)b0 * T * 4 * D, w_hh_ug,
-                           h_out + (long long)b0 * T * D, c_state + (long long)b0 * D, bn, T, sy, n_teams, fault, lstm_err_word(P, dev), spin_limit);
+        unsigned* sy = nullptr;
+        QA_TRY(lstm_arm_sync(P, s, &sy));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(n_teams * PT)), dim3(NW * 64), LSTM_TEAM_DYN_LDS, s, xw + (long long)b0 * T * 4 * D, w_hh_ug,
+                           h_out + (long long)b0 * T * D, c_state + (long long)b0 * D, std::min(per_launch, B - b0), T, sy, n_teams, fault,
+                           lstm_err_word(P, dev), spin_limit, fast);
         QA_LAUNCH_CHECK();
         lstm_count_launch(P, dev);
     }
     return QA_OK;
 }
 
-static int launch_lstm_team(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, hipStream_t s, int dev,
-                            bool* done) {
+// The team form of a width, if its knob and the device allow one; *done as above.
+//   QA_LSTM_XCD:  d = 512 / 768 on one 32-member team per XCD (8 / 12 waves; 1 .. 8 XCDs of 32 CUs), mode 2 = the XCD-local forms
+//   QA_LSTM_TEAM: d = 1024 on 4 teams of 64 workgroups x 8 waves, 16 hidden units per workgroup in 128 VGPRs per lane - laid out for 256 CUs
+static int launch_lstm_teams(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, hipStream_t s, int dev,
+                             bool* done) {
     *done = false;
     LstmPersistentDev& P = g_lstm_p[dev];
-    // d = 1024 (H-Codec 1.5 decoder): 4 teams of 64 workgroups x 8 waves, 16 hidden units per workgroup in 128 VGPRs per lane.
-    // d = 1536 (H-Codec 2.0) on 2 teams of 128 workgroups x 12 waves (again 128 resident weights per lane; h staged through registers or by
-    // LDS-DMA) was built and measured in r05: parity green, ~10 us per step against 8.5 for lstm_persistent_kernel (a 128-member arrival
-    // counter alone is ~1.5 us of serialised atomics; profiles/r05_lstm_team1536_ab.txt) - removed again, d = 1536 stays on that kernel
-    if (t_lstm_per_step || knob(K_LSTM_TEAM) <= 0 || d != 1024 || P.degraded || T < 2) return QA_OK;
+    const bool xcd = d == 512 || d == 768;
+    const int mode = xcd ? (int)knob(K_LSTM_XCD) : d == 1024 ? (int)knob(K_LSTM_TEAM) : 0;
+    if (t_lstm_per_step || mode <= 0 || P.degraded || T < 2) return QA_OK;
     QA_TRY(lstm_persistent_prepare(P, dev));
-    if (P.cus != 256) return QA_OK;  // the team size is laid out for 256 CUs
-    QA_TRY((launch_lstm_team_t<1024, 64, 8>(P, dev, xw, w_hh_ug, h_out, c_state, B, T, s)));
+    if (xcd ? (P.cus % 32 != 0 || P.cus < 32 || P.cus > 8 * 32) : P.cus != 256) return QA_OK;
+    if (d == 512) QA_TRY((launch_lstm_team<512, 8, 32, 1, true>(P, dev, xw, w_hh_ug, h_out, c_state, B, T, s, mode >= 2 ? 1 : 0)));
+    else if (d == 768) QA_TRY((launch_lstm_team<768, 12, 32, 1, true>(P, dev, xw, w_hh_ug, h_out, c_state, B, T, s, mode >= 2 ? 1 : 0)));
+    else QA_TRY((launch_lstm_team<1024, 8, 64, 2, false>(P, dev, xw, w_hh_ug, h_out, c_state, B, T, s, 0)));
     *done = true;
     return QA_OK;
 }
@@ -907,9 +813,7 @@ int launch_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_st
         ++g_lstm_p[dev].diverted;  // another handle's in-launch recurrence may be running: no second whole-device kernel beside it
     } else {
         bool done = false;
-        QA_TRY(launch_lstm_xcd(xw, w_hh_ug, h_out, c_state, B, T, d, s, dev, &done));
-        if (done) return QA_OK;
-        QA_TRY(launch_lstm_team(xw, w_hh_ug, h_out, c_state, B, T, d, s, dev, &done));
+        QA_TRY(launch_lstm_teams(xw, w_hh_ug, h_out, c_state, B, T, d, s, dev, &done));
         if (done) return QA_OK;
         QA_TRY(launch_lstm_persistent(xw, w_hh_ug, h_out, c_state, B, T, d, s, dev, &done));
         if (done) return QA_OK;
@@ -949,3 +853,24 @@ int launch_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_st
 }
 
 }  // namespace qa
+
+// test hook: one recurrence as a model graph issues it - inside a ticket, through launch_lstm's own choice of kernel.  An in-launch
+// recurrence is waited for when the ticket closes; a barrier time-out is an error here (no re-run on the per-step kernels)
+extern "C" int qa_debug_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, void* stream) {
+    QA_REQUIRE(xw && w_hh_ug && h_out && c_state && B >= 1 && T >= 1 && d >= 1, "qa_debug_lstm: bad argument");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    int dev = 0;
+    QA_HIP(hipGetDevice(&dev));
+    void* ticket = nullptr;
+    QA_TRY(qa::lstm_call_begin(dev, &ticket));
+    const int st = qa::launch_lstm(xw, w_hh_ug, h_out, c_state, B, T, d, s);
+    bool failed = false;
+    const int st_end = qa::lstm_call_end(ticket, s, &failed);
+    if (st != QA_OK) return st;
+    QA_TRY(st_end);
+    if (failed) {
+        qa::set_error("qa_debug_lstm: the step barrier of the in-launch recurrence timed out (h_out is invalid)");
+        return QA_ERR_HIP;
+    }
+    return QA_OK;
+}
