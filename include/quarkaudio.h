@@ -344,7 +344,7 @@ int qa_debug_att_stats(int64_t* out2);
 /* ---- tuning knobs -------------------------------------------------------------------------------------------
  * Every A/B switch of the library is one row of a table (csrc/knobs.h; INTEGRATION.md lists them): an integer whose initial
  * value is the environment variable of the same name (e.g. QA_LSTM_PERSISTENT, QA_LM_MLP_FUSED) and which qa_set_knob()
- * overrides at run time.  Knobs are read by the host-side launch code at launch (QA_LM_MLP_FUSED: at qa_lm_create) time.  No knob changes results beyond fp32 summation order; none selects a CPU path.  Process-wide. */
+ * overrides at run time.  Knobs are read by the host-side launch code at launch (QA_LM_MLP_FUSED: at qa_lm_create) time.  No knob changes results beyond fp32 summation order - except the opt-in reduced-precision values 2 / 3 of QA_GEMM_MATH; none selects a CPU path.  Process-wide. */
 int qa_knob_count(void);
 int qa_knob_info(int32_t index, const char** name, int64_t* value, int64_t* default_value, const char** doc);
 int qa_set_knob(const char* name, int64_t value);

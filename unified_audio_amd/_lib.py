@@ -323,6 +323,50 @@ def knobs() -> dict:
     return out
 
 
+GEMM_MATH_MODES = {"fp32": 0, "split6": 1, "split3": 2, "bf16": 3}  # QA_GEMM_MATH values (csrc/knobs.h)
+
+
+def _gemm_math_value(mode) -> int:
+    """"fp32" | "split6" | "split3" | "bf16" or the knob's integer -> the integer; ValueError for anything else."""
+    if isinstance(mode, str):
+        if mode not in GEMM_MATH_MODES:
+            raise ValueError(f"unknown GEMM arithmetic {mode!r}: one of {', '.join(GEMM_MATH_MODES)}")
+        return GEMM_MATH_MODES[mode]
+    if isinstance(mode, bool) or not isinstance(mode, int) or mode not in GEMM_MATH_MODES.values():
+        raise ValueError(f"unknown GEMM arithmetic {mode!r}: one of {', '.join(GEMM_MATH_MODES)} or 0 .. 3")
+    return mode
+
+
+def set_gemm_math(mode) -> int:
+    """Select the arithmetic of every conv_gemm launch of this process (QA_GEMM_MATH): "split6" (1, the default, fp32-class), "fp32" (0),
+    or the reduced-precision "split3" (2, operands exact to 2^-16) and "bf16" (3, bf16 operands); fp32 accumulation in all of them.  Returns
+    the previous value.  The UniSE LM's launches keep the fp32 chain, and attention has its own knob (QA_ATT_MATH)."""
+    return set_knob("QA_GEMM_MATH", _gemm_math_value(mode))
+
+
+def gemm_math_name() -> str:
+    """Name of the arithmetic conv_gemm currently runs (any value the library does not name runs split-6)."""
+    value = get_knob("QA_GEMM_MATH")
+    return next((n for n, v in GEMM_MATH_MODES.items() if v == value), "split6")
+
+
+class gemm_math:
+    """`with gemm_math("bf16"): ...` - set_gemm_math for the block, the previous value restored on exit (also when the block raises).
+    Process-wide like every knob, not per handle or per thread."""
+
+    def __init__(self, mode):
+        self._value = _gemm_math_value(mode)  # an unknown mode raises here, before the library is touched
+        self._prev = None
+
+    def __enter__(self):
+        self._prev = set_knob("QA_GEMM_MATH", self._value)
+        return self
+
+    def __exit__(self, *exc):
+        set_knob("QA_GEMM_MATH", self._prev)
+        return False
+
+
 def require_device() -> None:
     if load_library().qa_device_count() <= 0:
         raise QuarkAudioError(-2, "no HIP device visible: the quarkaudio hot path only runs on an MI355X (gfx950)")

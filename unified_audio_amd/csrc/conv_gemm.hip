@@ -13,7 +13,8 @@
 // bank-conflict free; each lane fetches 4 consecutive k per read and the (lane>>5) halves take k-groups
 // {0..3},{4..7}: the K order inside a step is permuted identically for A and B, which leaves the sum unchanged.
 // That is the fp32 chain (QA_GEMM_MATH = 0).  The default, split-6 (QA_GEMM_MATH = 1, split4_rne in split_planes.h), runs the same tiles
-// on the bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.
+// on the bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.  Two opt-in reduced
+// forms keep fewer planes of the same split: split-3 (QA_GEMM_MATH = 2, two planes, three MFMAs) and bf16 (3, one plane, one MFMA).
 // Host side: launch_conv_gemm validates and derives the kernel's parameters, choose_tile is the tile cost model, launch_cfg /
 // launch_instance map a tile to a kernel instance.  The pre-split weight images the PRE instances read live in weight_planes.hip.
 #include <algorithm>
@@ -118,9 +119,19 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const ConvParams& p, long lo
 // load, one ds_write_b128, both addresses fixed before the loop - and 16 consecutive lanes write the 256 contiguous (XOR-permuted)
 // bytes that one plane of a block occupies in LDS.  The LDS image is byte for byte the one the in-loop split builds.  Instantiated
 // for the 128-column tiles only (launch_instance).
-template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false, bool SPLIT = false, bool PRE = false>
-__global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv_gemm_kernel(const ConvParams p_in) {
-    static_assert(SPLIT || !PRE, "a pre-split weight image feeds the split-6 instances only");
+//
+// NPL: the arithmetic form as a plane count.  0 = the fp32 chain; 3 = split-6; 2 = split-3 and 1 = bf16 (QA_GEMM_MATH = 2 / 3,
+// split_planes.h): the staging threads compute and store the first NPL planes only, the fragment reads load those, and a k group issues
+// the table's pairs that pair_kept names (3: all six; 2: hm, mh, hh; 1: hh), in the table's order - so the per-element order, and with it the independence of
+// BM, BN, BK, LINEAR and the tile order, is the same in every form.  The LDS image keeps the three-plane stride in every form (the l, or
+// m and l, rows are simply never touched): the occupancy of these instances is set by registers, and one layout keeps the image path, the
+// epilogue staging and conv_gemm_min_wg as they are.  PRE instances read the same image and move only the units of the kept planes.
+template <int BM, int BN, int WM, int WN, bool PRO_ELU, int BK = 32, bool LINEAR = false, int NPL = 0, bool PRE = false>
+__global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void conv_gemm_kernel(const ConvParams p_in) {
+    constexpr bool SPLIT = NPL > 0;
+    constexpr int NP = SPLIT ? NPL : 3;  // planes moved and read
+    static_assert(NPL >= 0 && NPL <= 3, "0 = fp32 chain, else the number of bf16 planes");
+    static_assert(SPLIT || !PRE, "a pre-split weight image feeds the bf16-plane instances only");
     ConvParams p = p_in;
     constexpr int LDS = BK + 4;
     constexpr int RPP = 256 / (BK / 4);  // rows staged per pass: 8 (BK=32) or 4 (BK=16) threads cover one row chunk
@@ -220,16 +231,17 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
         }
     }
     // PRE: unit u = tid + 256 i of the B tile -> (block of 128 / BK rows, plane, row in block, slot)
-    constexpr int BP_UNITS = BN * BK / 128 * 48, BP_IT = PRE ? BP_UNITS / 256 : 1;
+    constexpr int BP_BLOCK = 16 * NP;  // units of one block that this form moves: its first NP planes
+    constexpr int BP_UNITS = BN * BK / 128 * BP_BLOCK, BP_IT = PRE ? BP_UNITS / 256 : 1;
     static_assert(!PRE || (BN == 128 && BP_UNITS % 256 == 0), "the image path exists for the 128-column tiles: every thread moves BP_IT whole units");
     const char* bp_ptr[BP_IT];  // this thread's unit of chunk 0 in the image
     int bp_lds[BP_IT];          // ... and its byte offset in an LDS buffer
     if constexpr (PRE) {
 #pragma unroll
         for (int i = 0; i < BP_IT; ++i) {
-            const int u = tid + 256 * i, v = u % 48;
+            const int u = tid + 256 * i, v = u % BP_BLOCK;
             const int pl = v >> 4, slot = v % (BK / 8);
-            const int row = u / 48 * (128 / BK) + (v & 15) / (BK / 8);
+            const int row = u / BP_BLOCK * (128 / BK) + (v & 15) / (BK / 8);
             const int n = min(n0 + row, p.N - 1);
             bp_ptr[i] = static_cast<const char*>(p.wp) + plane_byte_offset((long long)n * p.K + slot * 8, pl);
             bp_lds[i] = 3 * PLANE_A + pl * PLANE_B + row * BK * 2 + swz(row, slot) * 16;
@@ -287,11 +299,11 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
                 v.x = elu_f(v.x); v.y = elu_f(v.y); v.z = elu_f(v.z); v.w = elu_f(v.w);                        \
             }                                                                                                  \
             u32x2 h_, m_, l_;                                                                                  \
-            split4_rne(v, h_, m_, l_);                                                                         \
+            split4_planes<NP>(v, h_, m_, l_);                                                                  \
             const int r_ = ld_row + RPP * i, o_ = r_ * BK * 2 + swz(r_, sl_) * 16 + in_;                       \
             *reinterpret_cast<u32x2*>(a_ + o_) = h_;                                                           \
-            *reinterpret_cast<u32x2*>(a_ + PLANE_A + o_) = m_;                                                 \
-            *reinterpret_cast<u32x2*>(a_ + 2 * PLANE_A + o_) = l_;                                             \
+            if constexpr (NP >= 2) *reinterpret_cast<u32x2*>(a_ + PLANE_A + o_) = m_;                          \
+            if constexpr (NP == 3) *reinterpret_cast<u32x2*>(a_ + 2 * PLANE_A + o_) = l_;                      \
         }                                                                                                      \
         if constexpr (PRE) {                                                                                   \
             _Pragma("unroll") for (int i = 0; i < BP_IT; ++i)                                                  \
@@ -300,11 +312,11 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
         char* b_ = a_ + 3 * PLANE_A;                                                                           \
         _Pragma("unroll") for (int i = 0; i < B_IT; ++i) {                                                     \
             u32x2 h_, m_, l_;                                                                                  \
-            split4_rne(b_reg[i], h_, m_, l_);                                                                  \
+            split4_planes<NP>(b_reg[i], h_, m_, l_);                                                           \
             const int r_ = ld_row + RPP * i, o_ = r_ * BK * 2 + swz(r_, sl_) * 16 + in_;                       \
             *reinterpret_cast<u32x2*>(b_ + o_) = h_;                                                           \
-            *reinterpret_cast<u32x2*>(b_ + PLANE_B + o_) = m_;                                                 \
-            *reinterpret_cast<u32x2*>(b_ + 2 * PLANE_B + o_) = l_;                                             \
+            if constexpr (NP >= 2) *reinterpret_cast<u32x2*>(b_ + PLANE_B + o_) = m_;                          \
+            if constexpr (NP == 3) *reinterpret_cast<u32x2*>(b_ + 2 * PLANE_B + o_) = l_;                      \
         } }                                                                                                    \
     } else {                                                                                                   \
         float* a_ = sA + (BUF) * BM * LDS;                                                                     \
@@ -361,9 +373,9 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
             for (int g = 0; g < NG; ++g) {
                 // group g of a row is slots 2g (k 0..7) and 2g + 1 (k 8..15); swz XORs the slot with row bits, so the swizzled slot of
                 // 2g + h is (h ^ x) ^ 2g: the byte offset of group 0, XOR 32 g
-                bf16x8 af[3][TM], bf[3][TN];
+                bf16x8 af[NP][TM], bf[NP][TN];
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
+                for (int pl = 0; pl < NP; ++pl) {
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
                         af[pl][i] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_A + (a_off[i] ^ (32 * g)));
@@ -374,6 +386,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
                 if (g == 0) QA_LOAD_GLOBAL(nxt)
                 if (g == NG - 1) QA_STORE_LDS(cur ^ 1)
                 // operands swapped as in the fp32 loop below; plane pairs in the order of split_planes.h (PAIR_A: activation, PAIR_B: weight)
+                if constexpr (NP == 3) {
 #pragma unroll
                 for (int q = 0; q < 6; ++q)
 #pragma unroll
@@ -381,6 +394,18 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, SPLIT)) void conv
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PAIR_B[q]][j], af[PAIR_A[q]][i], acc[i][j], 0, 0, 0);
+                } else {  // split-3: hm, mh, hh; bf16: hh - the kept pairs, in the table's order
+                    static_for<6>([&](auto q_c) {
+                        constexpr int q = decltype(q_c)::value;
+                        if constexpr (pair_kept(q, NP)) {
+#pragma unroll
+                            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                                for (int j = 0; j < TN; ++j)
+                                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PAIR_B[q]][j], af[PAIR_A[q]][i], acc[i][j], 0, 0, 0);
+                        }
+                    });
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
             __syncthreads();
@@ -539,15 +564,25 @@ constexpr int prof_cfg(int bm, int bn) {  // PROF_CFG_* of a tile
     return bm == 256 ? PROF_CFG_256x128 : bm == 64 ? (bn == 64 ? PROF_CFG_64x64 : PROF_CFG_64x128) : bn == 32 ? PROF_CFG_128x32 : bn == 64 ? PROF_CFG_128x64 : PROF_CFG_128x128;
 }
 
-// one (tile, prologue, chunk, addressing) choice in its three arithmetic instances
+// QA_GEMM_MATH as the kernel's plane count: 0 = the fp32 chain (also every launch with math_fp32, whatever the knob says), 2 = split-3 (two
+// planes), 3 = bf16 (one plane), any other value = split-6 (three planes, the default); the same for every launch whatever its M
+static int gemm_planes(const ConvParams& p) {
+    const long long math = knob(K_GEMM_MATH);
+    return math == 0 || p.math_fp32 ? 0 : math == 2 ? 2 : math == 3 ? 1 : 3;
+}
+
+// one (tile, prologue, chunk, addressing) choice in its arithmetic instances
 template <int BM, int BN, int WM, int WN, bool ELU, int BK, bool LIN>
 static void launch_instance(const ConvParams& p, long long tiles, hipStream_t stream) {
-    // QA_GEMM_MATH: 1 = split-6 (bf16 planes, default), 0 = the fp32 chain; the same for every launch whatever its M
-    const bool split = knob(K_GEMM_MATH) != 0 && !p.math_fp32;
     constexpr bool IMAGE = BN == 128;  // narrower tiles keep the in-loop split: measured slower from an image
-    const auto kernel = !split            ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, false, false>
-                        : IMAGE && p.wp ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, true, IMAGE>
-                                        : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, true, false>;
+    const bool image = IMAGE && p.wp;
+    void (*kernel)(const ConvParams) = nullptr;
+    switch (gemm_planes(p)) {
+        case 0: kernel = conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 0, false>; break;
+        case 1: kernel = image ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 1, IMAGE> : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 1, false>; break;
+        case 2: kernel = image ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 2, IMAGE> : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 2, false>; break;
+        default: kernel = image ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 3, IMAGE> : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 3, false>; break;
+    }
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
 }
 

@@ -47,6 +47,37 @@ __device__ __forceinline__ void split4_rne(const f32x4 x, u32x2& ph, u32x2& pm, 
         pl[i] = rne_bf16x2(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));  // exact
     }
 }
+// The reduced arithmetics of conv_gemm keep the first NPL planes of the same split and, of the table above, the pairs of kept planes whose
+// product is at least as large as the operands' own truncation: plane p is 2^-8p of its operand, so pair (a, b) is 2^-8(a + b) of the product,
+// and a form with NPL planes issues the pairs with a + b < NPL, in the table's order.  NPL = 3 is split-6 (ml, lm, ll dropped).  Split-3
+// (QA_GEMM_MATH = 2, NPL = 2): x ~ h + m, exact to 2^-16 |x|, products hm, mh, hh; the dropped mm is <= 2^-16 |ab|.  bf16 (QA_GEMM_MATH = 3,
+// NPL = 1): x ~ h, exact to 2^-8 |x|, the one product hh.
+__host__ __device__ constexpr bool pair_kept(int q, int npl) { return PAIR_A[q] + PAIR_B[q] < npl; }
+// split4_rne's first two planes (the same bits) without the third
+__device__ __forceinline__ void split4_rne2(const f32x4 x, u32x2& ph, u32x2& pm) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float a = x[2 * i], b = x[2 * i + 1];
+        const unsigned h = rne_bf16x2(a, b);
+        float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
+        ra = __builtin_isfinite(ra) ? ra : 0.f;
+        rb = __builtin_isfinite(rb) ? rb : 0.f;
+        ph[i] = h;
+        pm[i] = rne_bf16x2(ra, rb);
+    }
+}
+// ... and its first plane alone
+__device__ __forceinline__ void split4_rne1(const f32x4 x, u32x2& ph) {
+    ph[0] = rne_bf16x2(x[0], x[1]);
+    ph[1] = rne_bf16x2(x[2], x[3]);
+}
+template <int NPL>  // the first NPL planes; the others are left untouched
+__device__ __forceinline__ void split4_planes(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {
+    static_assert(NPL >= 1 && NPL <= 3, "one to three planes");
+    if constexpr (NPL == 3) split4_rne(x, ph, pm, pl);
+    else if constexpr (NPL == 2) split4_rne2(x, ph, pm);
+    else split4_rne1(x, ph);
+}
 __device__ __forceinline__ void split4_unit(const f32x4 x, u32x2& ph, u32x2& pm, u32x2& pl) {  // split4_rne for x in [0, 1]
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
