@@ -138,15 +138,16 @@ int qa_hcodec_encode(qa_hcodec* h, const float* wav, int64_t B, int64_t T,
 int qa_hcodec_decode(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B,
                      int64_t N, float* wav_out, void* stream);
 
-/* Per-clip lengths in one call (non-causal H-Codec 1.0): clip b behaves as qa_hcodec_encode / _decode would for it
- * alone at its own length.  frames: HOST memory, int64 [B], the clips' lengths in CODE frames, 1 .. N each (N = T / encoder hop), read
- * during the call and checked before anything is launched (QA_ERR_INVALID names the row).  H-Codec 1.5 (which has the _adaptive_ragged
- * calls below), 2.0 and causal handles are refused with QA_ERR_UNSUPPORTED.  A call whose lengths all equal N is the rectangular call, through the same launches.
- *   encode: samples of wav from frames[b] * hop on and feature frames from frames[b] * (n_feat_frames / N) on are padding that is never
- *           read (NaN there changes nothing); codes at frames >= frames[b] are written as -1, the dropped code, so the output is also a
- *           legal input of qa_hcodec_decode.
+/* Per-clip lengths in one call (non-causal H-Codec 1.0; non-causal H-Codec 2.0, section 33): clip b behaves as
+ * qa_hcodec_encode / _decode would for it alone at its own length.  frames: HOST memory, int64 [B], the clips' lengths in CODE frames,
+ * 1 .. N each (N = T / encoder hop; H-Codec 2.0: hop * frame_stride = 3840 samples), read during the call and checked before anything is
+ * launched (QA_ERR_INVALID names the row).  H-Codec 1.5 (which has the _adaptive_ragged calls below) and causal handles, 1.0 or 2.0, are
+ * refused with QA_ERR_UNSUPPORTED.  A call whose lengths all equal N is the rectangular call, through the same launches.
+ *   encode: samples of wav from frames[b] * encoder hop on and feature frames from frames[b] * (n_feat_frames / N) on are padding that is
+ *           never read (NaN there changes nothing); codes at frames >= frames[b] are written as -1, the dropped code, so the output is
+ *           also a legal input of qa_hcodec_decode.
  *   decode: code entries at frames >= frames[b] are ignored, whatever they hold; wav_out[b] is exactly 0 from sample
- *           frames[b] * 2 * hop on. */
+ *           frames[b] * 2 * hop (H-Codec 2.0: frames[b] * frame_stride * hop) on. */
 int qa_hcodec_encode_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T, const int64_t* frames,
                             const float* feat, int64_t feat_stride_b, int64_t feat_stride_c, int64_t feat_stride_t,
                             int64_t n_feat_frames, int64_t* acoustic_codes, int64_t* semantic_codes, void* stream);
@@ -256,6 +257,13 @@ int qa_codes_check_async(const int64_t* codes, int64_t n, int64_t lo, int64_t li
  * qa_resample_length = ceil(new * T / orig) samples per clip; wav [B, T] -> out [B, qa_resample_length] (device). */
 int64_t qa_resample_length(int64_t T, int32_t orig_freq, int32_t new_freq);
 int qa_resample(const float* wav, int64_t B, int64_t T, int32_t orig_freq, int32_t new_freq, float* out, void* stream);
+/* Per-clip lengths in one resample call: row b equals qa_resample on wav[b, :lengths[b]] alone.  lengths: HOST
+ * memory, int64 [B], SAMPLES at orig_freq, 1 .. T each, checked before anything is launched (QA_ERR_INVALID names the row); the values
+ * travel in the launches' arguments, nothing is copied from the caller's memory after the call returns.  Samples t >= lengths[b] are
+ * never loaded (they read as zero); out[b, o] is written as exactly 0 for o >= qa_resample_length(lengths[b]), where a zero-filled
+ * row would carry the filter's ringing. */
+int qa_resample_ragged(const float* wav, int64_t B, int64_t T, const int64_t* lengths, int32_t orig_freq, int32_t new_freq, float* out,
+                       void* stream);
 
 /* Implicit-GEMM Conv1d over channel-last activations (covers nn.Linear with ksize = 1):
  *   y[b, t, n] = post( res[b,t,n] + gamma[n] * act( bias[n] + sum_{j,c} pro(x[b, src(t,j), c]) * w[n, j, c] ) )

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "clip_lengths.h"
 #include "kernels.h"
 #include "knobs.h"
 #include "split_planes.h"
@@ -385,32 +386,66 @@ int64_t qa_resample_length(int64_t T, int32_t orig_freq, int32_t new_freq) {
     return (n * T + o - 1) / o;
 }
 
-int qa_resample(const float* wav, int64_t B, int64_t T, int32_t orig_freq, int32_t new_freq, float* out, void* stream) {
-    if (!wav || !out) {
-        set_error("qa_resample: null argument");
-        return QA_ERR_INVALID;
+// qa_resample (lengths == nullptr) and qa_resample_ragged.  The lengths are checked before anything is launched and reach the kernel as a
+// device array that row_lens_kernel writes from its own arguments, in stream order: nothing reads the caller's vector after the call.
+static int resample_call(const char* fn, const float* wav, int64_t B, int64_t T, const int64_t* lengths, int32_t orig_freq, int32_t new_freq,
+                         float* out, void* stream) {
+    QA_REQUIRE(B > 0 && T > 0 && orig_freq > 0 && new_freq > 0, "%s: bad argument", fn);
+    std::vector<int> len;
+    if (lengths) {
+        bool full = false;
+        QA_TRY(check_clip_lengths(fn, B, lengths, 1, T, "samples", "T", &len, &full));
     }
-    QA_REQUIRE(B > 0 && T > 0 && orig_freq > 0 && new_freq > 0, "qa_resample: bad argument");
     const int g = gcd_i(orig_freq, new_freq);
     const int orig = orig_freq / g, nw = new_freq / g;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (orig == nw) {
-        QA_HIP(hipMemcpyAsync(out, wav, sizeof(float) * (size_t)B * T, hipMemcpyDeviceToDevice, s));
+        if (!lengths) {
+            QA_HIP(hipMemcpyAsync(out, wav, sizeof(float) * (size_t)B * T, hipMemcpyDeviceToDevice, s));
+            return QA_OK;
+        }
+        for (int64_t b = 0; b < B; ++b) {  // the clip's own samples, zeros behind them; the padding is not read
+            const size_t n = (size_t)len[(size_t)b];
+            QA_HIP(hipMemcpyAsync(out + b * T, wav + b * T, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+            if (n < (size_t)T) QA_HIP(hipMemsetAsync(out + b * T + n, 0, sizeof(float) * ((size_t)T - n), s));
+        }
         return QA_OK;
     }
     std::vector<float> taps;
     int width = 0;
     resample_taps(orig, nw, &taps, &width);
     float* dev = nullptr;
+    int* lens_dev = nullptr;
     QA_HIP(hipMallocAsync(reinterpret_cast<void**>(&dev), taps.size() * sizeof(float), s));
     hipError_t e = hipMemcpyAsync(dev, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, s);
     int st = QA_OK;
+    if (e == hipSuccess && lengths) e = hipMallocAsync(reinterpret_cast<void**>(&lens_dev), sizeof(int) * (size_t)B, s);
+    if (e == hipSuccess && lengths) st = launch_row_lens(lens_dev, len.data(), (int)B, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // `taps` is a stack-lifetime host buffer
-    if (e == hipSuccess)
-        st = launch_resample(wav, dev, out, (int)B, T, qa_resample_length(T, orig_freq, new_freq), orig, nw, width, 2 * width + orig, s);
+    if (e == hipSuccess && st == QA_OK)
+        st = launch_resample(wav, dev, out, (int)B, T, qa_resample_length(T, orig_freq, new_freq), orig, nw, width, 2 * width + orig, s,
+                             lens_dev);
+    if (lens_dev) (void)hipFreeAsync(lens_dev, s);
     (void)hipFreeAsync(dev, s);
     QA_HIP(e);
     return st;
+}
+
+int qa_resample(const float* wav, int64_t B, int64_t T, int32_t orig_freq, int32_t new_freq, float* out, void* stream) {
+    if (!wav || !out) {
+        set_error("qa_resample: null argument");
+        return QA_ERR_INVALID;
+    }
+    return resample_call("qa_resample", wav, B, T, nullptr, orig_freq, new_freq, out, stream);
+}
+
+int qa_resample_ragged(const float* wav, int64_t B, int64_t T, const int64_t* lengths, int32_t orig_freq, int32_t new_freq, float* out,
+                       void* stream) {
+    if (!wav || !lengths || !out) {
+        set_error("qa_resample_ragged: null argument");
+        return QA_ERR_INVALID;
+    }
+    return resample_call("qa_resample_ragged", wav, B, T, lengths, orig_freq, new_freq, out, stream);
 }
 
 }  // extern "C"

@@ -753,7 +753,8 @@ int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
                                      (!p.y2 || (p.alpha2 && al16(p.alpha2) && al16(p.y2) && p.ldy2 % 4 == 0))),
                "conv_gemm: Snake activation / second output need the float4 epilogue and 16-byte aligned alpha vectors");
     QA_REQUIRE(p.dilation <= 1 || (p.pad_mode == PAD_ZERO && p.in_rep <= 1), "conv_gemm: dilation needs zero padding");
-    QA_REQUIRE(!p.lens || (p.len_mul >= 1 && p.in_rep <= 1 && p.max_pad >= 0), "conv_gemm: per-clip lengths need len_mul >= 1 and in_rep = 1");
+    // with in_rep > 1 (zero padding only, above) len_mul counts VIRTUAL frames: build_taps cuts r at lens[b] * len_mul before r / in_rep
+    QA_REQUIRE(!p.lens || (p.len_mul >= 1 && p.max_pad >= 0), "conv_gemm: per-clip lengths need len_mul >= 1");
     QA_REQUIRE(!p.am_dist || (vec_epi && p.am_idx && p.am_x2 && p.am_e2 && al16(p.am_e2) && p.am_ld >= (p.N + 31) / 32 && !p.y2),
                "conv_gemm: the arg-min epilogue needs N %% 4 == 0, x2 / e2 / dist / idx and am_ld >= ceil(N / 32)");
     QA_REQUIRE(!p.rope || (vec_epi && p.rope_hd % 4 == 0 && p.rope_n % 4 == 0 && p.rope_T > 0 && al16(p.rope)),

@@ -909,9 +909,12 @@ int launch_codes_count(const long long* codes, long long n, long long lo, long l
 //   out[b, q * new + i] = sum_j kernel[i][j] * padded[b, q * orig + j],  padded = wav with `width` zeros in front and
 //   width + orig behind, kernel [new][2 * width + orig]; the output is cut to ceil(new * T / orig) samples.
 // HBM-bound (one read of the waveform, 1/3 of it written for 48 -> 16 kHz): one thread per output sample, taps from LDS.
+// lens [B] (device) or null: a per-clip call - row b holds lens[b] of its T samples.  Samples behind them read as
+// zero and are never loaded, so an output is the same fmaf chain as on the clip alone; outputs behind ceil(new * lens[b] / orig) are
+// written as exactly zero (a zero-filled row would carry the filter's ringing there).
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ wav, const float* __restrict__ taps, float* __restrict__ out,
                                                        long long T, long long T_out, int orig, int nw, int width, int ktaps,
-                                                       int use_lds) {
+                                                       int use_lds, const int* __restrict__ lens) {
     extern __shared__ float s_taps[];
     if (use_lds) {  // small filter banks (48 -> 16 kHz: 1 x 41 taps) live in LDS; large ones (44.1 -> 16 kHz: 160 x 475) stay in L2
         for (int i = threadIdx.x; i < nw * ktaps; i += 256) s_taps[i] = taps[i];
@@ -925,20 +928,28 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
     const float* x = wav + (long long)b * T;
     const float* k = (use_lds ? s_taps : taps) + ph * ktaps;
     const long long base = q * orig - width;
+    long long len = T;
+    if (lens) {  // launch-uniform
+        len = min((long long)lens[b], T);
+        if (o >= (len * nw + orig - 1) / orig) {
+            out[(long long)b * T_out + o] = 0.f;
+            return;
+        }
+    }
     float acc = 0.f;
     for (int j = 0; j < ktaps; ++j) {
         const long long t = base + j;
-        const float v = (t >= 0 && t < T) ? x[t] : 0.f;
+        const float v = (t >= 0 && t < len) ? x[t] : 0.f;
         acc = fmaf(k[j], v, acc);
     }
     out[(long long)b * T_out + o] = acc;
 }
 int launch_resample(const float* wav, const float* taps, float* out, int B, long long T, long long T_out, int orig, int nw, int width,
-                    int ktaps, hipStream_t s) {
+                    int ktaps, hipStream_t s, const int* lens) {
     const size_t bytes = (size_t)nw * ktaps * sizeof(float);
     const int use_lds = bytes <= 48 * 1024;
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)ceil_div(T_out, 256), (unsigned)B), dim3(256), use_lds ? bytes : 0, s, wav, taps, out, T,
-                       T_out, orig, nw, width, ktaps, use_lds);
+                       T_out, orig, nw, width, ktaps, use_lds, lens);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

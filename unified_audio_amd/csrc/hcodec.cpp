@@ -128,7 +128,8 @@ struct qa_hcodec : Handle {
         int samples = 0;        // waveform samples: 2 * prod(ratios); H-Codec 2.0: hop * frame_stride
         int feat = 0;           // SSL feature frames: prod(sem_strides)
         int dec = 0;            // decoder (ISTFT) frames: 2; H-Codec 2.0: frame_stride
-        std::vector<int> enc;   // SEANet: at the input of stage i; enc[n_ratios] = 2, the rate of its transformer (empty for 2.0)
+        std::vector<int> enc;   // SEANet: at the input of stage i; enc[n_ratios] = 2, the rate of its transformer.  H-Codec 2.0: enc[0] =
+                                // 2 * frame_stride, the STFT's input blocks of (n_fft - hop) / 2 samples; enc[1] = frame_stride, its frames
         std::vector<int> sem;   // semantic encoder: at the input of block i; sem[n_sem_strides] = 1, the rate of its output
     } geom;
     // ragged calls (qa_hcodec_encode_ragged / _decode_ragged and their _adaptive_ twins): the clips' code-frame counts [lens_cap], written on
@@ -544,12 +545,15 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float*
     const int B = tw.B, T = tw.T;
     const int blk = (sp.n_fft - sp.hop) / 2;  // 480: pad = (n_fft - hop) / 2 and hop = 2 * blk, n_fft = 4 * blk
     const int N50 = T / sp.hop, d = sp.enc_dim, nb = sp.n_fft / 2 + 1;
-    const TimeAxis t{B, N50, tw.causal, ClipLens()};
+    // Ragged calls (non-causal): clip b has tw.rl.n[b] code frames, geom.enc[0] of the STFT's input blocks and geom.enc[1] frames per code
+    // frame.  Every filter with a temporal footprint ends the clip there, so nothing behind a clip's last sample is read.
+    const TimeAxis tb = tw.at(T / blk, h->geom.enc[0]);
+    const TimeAxis t = tw.at(N50, h->geom.enc[1]);
     const int64_t rows = t.rows();
     // STFT as an implicit GEMM: the signal is a [B, T / blk, blk] "channel-last" tensor, a frame is 4 consecutive blocks
     // starting one block before 2 t (zero padded), the filter bank is the windowed DFT basis (re | im)
     float* ri = c.arena.alloc<float>(rows * 2 * nb);
-    QA_TRY(conv_op(c, wav, blk, B, T / blk, h->stft_basis, ri, 2 * nb, N50, conv_geom(2, 1, 1)));
+    QA_TRY(conv_at(c, wav, tb, h->stft_basis, ri, N50, conv_geom(2, 1, 1)));
     float* feat = c.arena.alloc<float>(rows * h->stft_ld);
     QA_RUN(c, launch_stft_post(ri, feat, rows, nb, 2 * nb, h->stft_ld, c.stream));
     c.tap("enc.stft", feat, rows * h->stft_ld);
@@ -558,7 +562,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float*
     float* u = c.arena.alloc<float>(rows * sp.enc_inter);
     // vq/conv.py Conv1d (:39-47): zero padding (k - stride, 0) in the causal variant, (k / 2, k / 2) otherwise
     const bool cz = t.causal;
-    QA_TRY(conv_op(c, feat, h->stft_ld, B, N50, h->enc_embed, t1, d, N50, conv_geom(1, cz ? 2 : 1, cz ? 0 : 1)));
+    QA_TRY(conv_at(c, feat, t, h->enc_embed, t1, N50, conv_geom(1, cz ? 2 : 1, cz ? 0 : 1)));
     QA_TRY(layernorm_op(c, t1, h->enc_norm_w, h->enc_norm_b, x, rows, d, 1e-6f));
     for (const ConvNeXtW& w : h->enc_cnx) QA_TRY(convnext_op(c, w, x, t1, u, t, d));
     c.tap("enc.prior", x, rows * d);
@@ -568,7 +572,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float*
     const int pl = cz ? k - st : k / 2, pr = cz ? 0 : k / 2;
     const int Nf = (N50 + pl + pr - k) / st + 1;
     float* emb = c.arena.alloc<float>((size_t)B * Nf * sp.code_dim);
-    QA_TRY(conv_op(c, t1, d, B, N50, h->enc_out20, emb, sp.code_dim, Nf, conv_geom(st, pl, pr)));
+    QA_TRY(conv_at(c, t1, t, h->enc_out20, emb, Nf, conv_geom(st, pl, pr)));
     *emb_out = emb;
     *n50_out = N50;
     *nf_out = Nf;
@@ -714,7 +718,8 @@ int encode_graph(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, con
 }
 
 // CodecDecoder.forward (codec_decoder.py:58-67) from the concatenated [acoustic | semantic] embeddings [B, N, 2*code_dim]; tc: the code
-// frames' axis.  Ragged calls (H-Codec 1.0, non-causal): clip b has tc.rl.n[b] of the N code frames, 2 tc.rl.n[b] decoder frames.
+// frames' axis.  Ragged calls (H-Codec 1.0 / 2.0, non-causal): clip b has tc.rl.n[b] of the N code frames, geom.dec times as many decoder
+// frames (2; H-Codec 2.0: frame_stride).
 int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, const TimeAxis& tc, float* wav_out) {
     const qa_hcodec_spec& sp = h->spec;
     const int d = sp.dec_dim, B = tc.B, N = tc.T;
@@ -728,6 +733,7 @@ int decode_tail(qa_hcodec* h, Ctx& c, const float* cat, const TimeAxis& tc, floa
         const int k = h->dec_embed20.ksize;
         ConvOpt o = conv_geom(1, zpad_left(k, t.causal), zpad_right(k, t.causal));
         o.in_rep = sp.frame_stride;
+        o.rl = t.rl;  // ragged: the clip ends at geom.dec * frames[b] VIRTUAL (repeated) frames, so a tap behind it reads the zero padding
         QA_TRY(conv_op(c, cat, 2 * sp.code_dim, B, N, h->dec_embed20, x, d, t.T, o));
     } else {
         // sub-pixel upsampler: 1x1 conv to 2*d channels; in channel-last layout the pixel shuffle (vq/conv.py:86-88) is a
@@ -1069,6 +1075,7 @@ int build(qa_hcodec* h, const HostTable& tab) {
     for (int i = sp.n_sem_strides - 1; i >= 0; --i) geom.sem[i] = geom.sem[i + 1] * sp.sem_strides[i];
     geom.feat = geom.sem[0];
     geom.dec = v20 ? sp.frame_stride : 2;
+    if (v20) geom.enc = {2 * sp.frame_stride, sp.frame_stride};  // hop = 2 blocks (checked below), frame_stride frames per code frame
     if (!v20) geom.enc.assign(sp.n_ratios + 1, 2);
     for (int i = sp.n_ratios - 1; i >= 0 && !v20; --i) geom.enc[i] = geom.enc[i + 1] * sp.ratios[i];
     geom.samples = v20 ? sp.hop * sp.frame_stride : geom.enc[0];
@@ -1344,11 +1351,10 @@ static int ragged_refuse(qa_hcodec* h, const char* fn) {
     const qa_hcodec_spec& sp = h->spec;
     const char* why = sp.adaptive ? "an H-Codec 1.5 model (spec.adaptive): its per-clip calls are qa_hcodec_encode_adaptive_ragged / "
                                     "qa_hcodec_decode_adaptive_ragged (Codec.encode_ragged / decode_ragged)"
-                      : sp.version == 20 ? "an H-Codec 2.0 model (spec.version == 20)"
-                      : sp.causal        ? "a causal model (spec.causal)"
-                                         : nullptr;
+                      : sp.causal ? (sp.version == 20 ? "a causal H-Codec 2.0 model (spec.causal)" : "a causal model (spec.causal)")
+                                  : nullptr;
     if (why) {
-        set_error("%s: per-clip lengths are implemented for non-causal H-Codec 1.0; this handle is %s", fn, why);
+        set_error("%s: per-clip lengths are implemented for non-causal H-Codec 1.0 / 2.0; this handle is %s", fn, why);
         return QA_ERR_UNSUPPORTED;
     }
     return QA_OK;

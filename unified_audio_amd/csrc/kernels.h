@@ -77,7 +77,7 @@ int launch_istft_ola(const float* frames, const float* win, float* out, int B, i
 int launch_codes_check(const long long* codes, long long n, long long limit, unsigned long long* bad, hipStream_t s);
 int launch_codes_count(const long long* codes, long long n, long long lo, long long limit, unsigned long long* bad, hipStream_t s);
 int launch_resample(const float* wav, const float* taps, float* out, int B, long long T, long long T_out, int orig, int nw, int width,
-                    int ktaps, hipStream_t s);
+                    int ktaps, hipStream_t s, const int* lens = nullptr);  // lens [B] (device): the rows' sample counts, or null
 
 // attention.hip : softmax(Q K^T * scale) V over a fused [B*N, 3*H*hd] QKV buffer (RoPE already applied)
 //   causal = 0: full attention over the N keys of the same batch item (codec transformers)

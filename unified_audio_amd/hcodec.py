@@ -434,7 +434,17 @@ class Codec(torch.nn.Module):
         lengths (non-causal H-Codec 1.0): the clips' lengths in CODE frames, a host list / tensor of B values in 1 .. N25.  Row b then
         equals encode of that clip alone at its own length; samples and feature frames behind it are never read, codes behind it are
         -1 (the dropped code).  None: the rectangular call, exactly as before.  H-Codec 1.5 refuses `lengths=` here (its codes are a
-        dict of [B, nq, G] tensors): `encode_ragged` / `decode_ragged` are its per-clip calls."""
+        dict of [B, nq, G] tensors): `encode_ragged` / `decode_ragged` are its per-clip calls.  H-Codec 2.0 refuses `lengths=` here too,
+        with status -4 and before any library call, although `encode_ragged` serves it through the very same entry point: that refusal
+        is pinned by tests/test_hcodec_ragged_gpu.py::test_refusals_and_checks_come_before_any_launch, and a change that may edit that
+        test can collapse the two doors."""
+        if lengths is not None and self.spec.version == 20:
+            raise _lib.QuarkAudioError(-4, "Codec.encode(lengths=...): on an H-Codec 2.0 model the per-clip calls are "
+                                           "Codec.encode_ragged / Codec.decode_ragged")
+        return self._encode(x, feat, threshold, lengths)
+
+    def _encode(self, x, feat, threshold, lengths):
+        """encode's body; lengths: code frames per clip (non-causal H-Codec 1.0 / 2.0: qa_hcodec_encode_ragged) or None."""
         self._require_loaded()
         if self.spec.version == 20 and x.dim() == 2:  # H-Codec 2.0 passes wav without the channel dim (audio_tokenizer.py:73)
             x = x.unsqueeze(1)
@@ -483,10 +493,18 @@ class Codec(torch.nn.Module):
         lengths (keyword only; non-causal H-Codec 1.0): the clips' lengths in code frames, a host list / tensor of B values in 1 .. N.
         Row b then equals decode of its first lengths[b] frames alone; entries behind them are ignored whatever they hold (the range
         check does not count them), and the waveform is exactly zero from sample lengths[b] * 2 * hop on.  H-Codec 1.5 refuses `lengths=`
-        here: its codes carry their lengths, and `decode_ragged` is its per-clip call."""
+        here: its codes carry their lengths, and `decode_ragged` is its per-clip call.  H-Codec 2.0 refuses `lengths=` here as `encode`
+        does (status -4, before any library call; pinned by the same test): `decode_ragged` is its per-clip call."""
+        if lengths is not None and self.spec.version == 20:
+            raise _lib.QuarkAudioError(-4, "Codec.decode(lengths=...): on an H-Codec 2.0 model the per-clip calls are "
+                                           "Codec.encode_ragged / Codec.decode_ragged")
         self._require_loaded()
         if self.spec.adaptive and lengths is None:
             return self._decode_adaptive(acoustic_codes, semantic_codes, token_lengths)
+        return self._decode(acoustic_codes, semantic_codes, lengths)
+
+    def _decode(self, acoustic_codes, semantic_codes, lengths):
+        """decode's body for H-Codec 1.0 / 2.0 codes; lengths: code frames per clip (qa_hcodec_decode_ragged) or None."""
         q = self.spec.num_quantizers
         if acoustic_codes.shape != semantic_codes.shape or acoustic_codes.dim() != 3 or acoustic_codes.shape[1] != q:
             raise _lib.QuarkAudioError(-1, f"decode expects two [B,{q},N] code tensors, got "
@@ -522,9 +540,12 @@ class Codec(torch.nn.Module):
         batch.  Row b equals `encode` of clip b alone (B = 1) at its own length - its own alignment, its own group count, no padded query
         token among its keys, which the rectangular `encode` does not give even for clips of equal length.  Entries behind a clip's own
         groups are -1, a legal entry of length 0, so the dict is valid input for `decode` and `decode_ragged` alike.
-        H-Codec 1.0: `encode(x, feat, lengths=lengths)`."""
+        H-Codec 1.0: `encode(x, feat, lengths=lengths)`.
+        H-Codec 2.0 (non-causal): two int64 [B, nq, N] tensors, row b the codes of clip b alone at its own length,
+        -1 behind them; x is [B, T] or [B, 1, T] with T = 3840 N, feat [B, sem_in, 4 N].  This is the 2.0 model's only per-clip encode:
+        `encode(lengths=...)` refuses it (see there)."""
         if not self.spec.adaptive:
-            return self.encode(x, feat, lengths=lengths)
+            return self._encode(x, feat, 0.0, lengths)
         if x.dim() != 3 or x.shape[1] != 1:
             raise _lib.QuarkAudioError(-1, f"encode_ragged expects x of shape [B,1,T], got {tuple(x.shape)}")
         if feat.dim() != 3 or feat.shape[0] != x.shape[0] or feat.shape[1] != self.spec.sem_in:
@@ -583,11 +604,15 @@ class Codec(torch.nn.Module):
         H-Codec 1.5: length-injected codes [B, nq, G] (or plain codes + token_lengths [B, G]); the lengths ride in the codes, so
         `lengths` stays None.  Row b equals `decode` of clip b alone (B = 1): its bottleneck transformer and decoder see its own frames
         only.  Returns wav [B, max(frames) * 2 * hop], exactly zero behind every clip; a row whose codes hold no frame is an error.
-        H-Codec 1.0: `decode(acoustic_codes, semantic_codes, lengths=lengths)`."""
+        H-Codec 1.0: `decode(acoustic_codes, semantic_codes, lengths=lengths)`.
+        H-Codec 2.0 (non-causal): codes [B, nq, N] and `lengths` in code frames -> wav [B, 3840 N]; row b is the
+        decode of its first lengths[b] frames alone, entries behind them are ignored whatever they hold (the range check does not count
+        them), and the waveform is exactly zero from sample 3840 * lengths[b] on.  `decode(lengths=...)` refuses a 2.0 model."""
         if not self.spec.adaptive:
             if token_lengths is not None:
                 raise _lib.QuarkAudioError(-1, "decode_ragged: token_lengths belong to H-Codec 1.5 codes")
-            return self.decode(acoustic_codes, semantic_codes, lengths=lengths)
+            self._require_loaded()
+            return self._decode(acoustic_codes, semantic_codes, lengths)
         if lengths is not None:
             raise _lib.QuarkAudioError(-1, "decode_ragged: H-Codec 1.5 codes carry their lengths (adaptive_frames), pass none")
         q = self.spec.num_quantizers
@@ -725,29 +750,47 @@ class HCodecTokenizer(torch.nn.Module):
         self.model.load_state_dict(state_dict)
         return self
 
-    def resample(self, wavs: torch.Tensor) -> torch.Tensor:
-        """torchaudio.transforms.Resample(sampling_rate, 16000) (HCodec-2.0/audio_tokenizer.py:44,51) on the device."""
+    def resample(self, wavs: torch.Tensor, lengths=None) -> torch.Tensor:
+        """torchaudio.transforms.Resample(sampling_rate, 16000) (HCodec-2.0/audio_tokenizer.py:44,51) on the device.
+        lengths: the clips' lengths in samples at `sampling_rate` (host list / tensor): row b is then the resampled clip alone -
+        `resampled_lengths(lengths)[b]` samples, exact zeros behind them, nothing behind wavs[b, :lengths[b]] read (qa_resample_ragged)."""
         if self.sampling_rate == 16000:
             return wavs
         x = wavs.to(device=self.device, dtype=torch.float32).contiguous()
         B, T = x.shape
-        n = int(self.model._lib.qa_resample_length(T, self.sampling_rate, 16000))
+        lib = self.model._lib
+        n = int(lib.qa_resample_length(T, self.sampling_rate, 16000))
         out = torch.empty((B, n), dtype=torch.float32, device=self.device)
-        _lib.check(self.model._lib.qa_resample(x.data_ptr(), B, T, self.sampling_rate, 16000, out.data_ptr(), _stream_ptr(self.device)))
+        if lengths is None:
+            _lib.check(lib.qa_resample(x.data_ptr(), B, T, self.sampling_rate, 16000, out.data_ptr(), _stream_ptr(self.device)))
+        else:
+            _lib.check(lib.qa_resample_ragged(x.data_ptr(), B, T, _frames_arg(lengths, B), self.sampling_rate, 16000, out.data_ptr(),
+                                              _stream_ptr(self.device)))
         return out
+
+    def resampled_lengths(self, lengths):
+        """Samples at 16 kHz of clips of `lengths` samples at `sampling_rate`: ceil(16000 * len / sampling_rate), as Resample cuts a
+        clip alone.  A clip padded to its own code frames, f * 3840 samples at 48 kHz, gives f * 1280 samples: 4 f SSL frames."""
+        g = math.gcd(self.sampling_rate, 16000)
+        o, n = self.sampling_rate // g, 16000 // g
+        return [-(-n * v // o) for v in _int_list(lengths, "lengths")]
 
     @torch.no_grad()
     def extract_wav2vec2_features(self, wavs: torch.Tensor, lengths=None) -> torch.Tensor:
         """1.0: audio_tokenizer.py:35-48 (pad (160,160), mean of all hidden states, sign*|x|^0.3); 1.5: hidden states 11 / 14 / 16
         (HCodec-1.5/audio_tokenizer.py:53-67); 2.0 (`extract_ssl_features`): Resample first (HCodec-2.0/audio_tokenizer.py:48-64).
-        lengths (an SSLFeatureExtractor without resampling only, `_ragged_front_end`): the clips' lengths in samples, passed on to it."""
-        if lengths is not None and not self._ragged_front_end():
-            raise _lib.QuarkAudioError(-3, "per-clip lengths need an SSLFeatureExtractor as feature_extractor and no resampling")
+        lengths (an SSLFeatureExtractor only, `_lengths_front_end`): the clips' lengths in samples at `sampling_rate`.  The 2.0 tokenizer
+        resamples with them (`resample(wavs, lengths)`) and passes the 16 kHz lengths on; the others pass them on as they are."""
+        if lengths is not None and not self._lengths_front_end():
+            raise _lib.QuarkAudioError(-3, "per-clip lengths need an SSLFeatureExtractor as feature_extractor")
         if self.feature_extractor is None:
             raise _lib.QuarkAudioError(-3, "no feature_extractor was given; pass feats= to tokenize()")
         from .ssl import SSLFeatureExtractor
 
-        wavs = self.resample(wavs)
+        if lengths is not None and not self._ragged_front_end():
+            wavs, lengths = self.resample(wavs, lengths), self.resampled_lengths(lengths)
+        else:
+            wavs = self.resample(wavs)
         if isinstance(self.feature_extractor, SSLFeatureExtractor):  # padding, averaging and compression happen in the library
             fx = self.feature_extractor
             want = tuple(self.select_layers or ())
@@ -770,10 +813,18 @@ class HCodecTokenizer(torch.nn.Module):
 
     def _ragged_front_end(self) -> bool:
         """Whether the front-end takes per-clip lengths in one call (SSLFeatureExtractor.__call__(lengths=...)):
-        the library's own extractor, fed the codec's waveform as it is (the 2.0 tokenizer's resampler has no lengths)."""
+        the library's own extractor, fed the codec's waveform as it is.  Behind the 2.0 tokenizer's resampler see `_lengths_front_end`."""
         from .ssl import SSLFeatureExtractor
 
         return isinstance(self.feature_extractor, SSLFeatureExtractor) and self.sampling_rate == 16000
+
+    def _lengths_front_end(self) -> bool:
+        """Whether `extract_wav2vec2_features(wav, lengths=...)` is one front-end call: the library's own extractor, fed the waveform as it
+        is (`_ragged_front_end`) or through the 2.0 tokenizer's resampler, which takes lengths too (qa_resample_ragged, DESIGN.md
+        section 33)."""
+        from .ssl import SSLFeatureExtractor
+
+        return isinstance(self.feature_extractor, SSLFeatureExtractor)
 
     def pad_wav(self, wav: torch.Tensor) -> torch.Tensor:
         pad = math.ceil(wav.size(-1) / self.hop_length) * self.hop_length - wav.size(-1)
@@ -802,11 +853,12 @@ class HCodecTokenizer(torch.nn.Module):
         ln = torch.tensor(lens, device=self.device)[:, None]
         end = torch.tensor(frames, device=self.device)[:, None] * hop
         wav = wav.masked_fill((pos >= ln) & (pos < end), 0.0)  # pad_wav of each clip alone: zeros up to its own hop multiple
-        if feats is None and self._ragged_front_end():
+        if feats is None and self._lengths_front_end():
             # ONE front-end call: row b is the clip padded to its own hop multiple, alone (its own padding, normalisation and keys)
             fpc = int(math.prod(self.model.spec.sem_strides))
             part = self.extract_wav2vec2_features(wav, lengths=[f * hop for f in frames])  # (b, t, d), zeros behind every clip's frames
-            short = [f for f in set(frames) if self.feature_extractor.frames(f * hop) < fpc * f]
+            hop16 = hop if self.sampling_rate == 16000 else self.resampled_lengths([hop])[0]  # the front-end's samples per code frame
+            short = [f for f in set(frames) if self.feature_extractor.frames(f * hop16) < fpc * f]
             if part.shape[1] < fpc * n or short:
                 raise _lib.QuarkAudioError(-1, f"the feature extractor returned {part.shape[1]} frames for {n} code frames, need {fpc * n}")
             feats = part[:, : fpc * n]
@@ -826,14 +878,17 @@ class HCodecTokenizer(torch.nn.Module):
         feats = feats.to(self.device).transpose(-2, -1)
         if self.model.spec.adaptive:  # H-Codec 1.5: the dict of [B, nq, G] codes, -1 behind every clip's own groups
             return self.model.encode_ragged(wav.unsqueeze(1), feats, frames, threshold=threshold)
+        if self.model.spec.version == 20:  # its per-clip door; 2.0 passes wav without the channel dim (audio_tokenizer.py:73)
+            return self.model.encode_ragged(wav, feats, frames)
         return self.model.encode(wav.unsqueeze(1), feats, lengths=frames)
 
     @torch.no_grad()
     def tokenize(self, wav: torch.Tensor, feats: Optional[torch.Tensor] = None, threshold: float = 0.0, lengths=None):
-        """lengths (non-causal H-Codec 1.0 / 1.5): the clips' lengths in SAMPLES (host list / tensor), wav [B, Tmax] with clip b in its
-        first lengths[b] samples.  Codes of clip b then equal tokenize of that clip alone; `code_frames(lengths)` gives the frames per
-        clip.  1.0: entries behind them are -1.  1.5: the dict of `Codec.encode_ragged`.  feats, when given, are [B, t, d] with clip b's
-        frames first."""
+        """lengths (non-causal H-Codec 1.0 / 1.5 / 2.0): the clips' lengths in SAMPLES (host list / tensor), wav [B, Tmax] with clip b in
+        its first lengths[b] samples.  Codes of clip b then equal tokenize of that clip alone; `code_frames(lengths)` gives the frames per
+        clip.  1.0 / 2.0: entries behind them are -1.  1.5: the dict of `Codec.encode_ragged`.  feats, when given, are [B, t, d] with clip
+        b's frames first, and no front-end is touched; without them the 2.0 tokenizer resamples with the lengths (`resample`) in front of
+        an SSLFeatureExtractor that takes the 16 kHz lengths: one front-end call."""
         if lengths is not None:
             return self._tokenize_ragged(wav, feats, lengths, threshold)
         wav = self.pad_wav(wav.to(self.device))
@@ -851,6 +906,8 @@ class HCodecTokenizer(torch.nn.Module):
         of `tokenize(..., lengths=...)`, whose lengths ride in the codes."""
         if ragged:
             return self.model.decode_ragged(acoustic_codes, semantic_codes, token_lengths, lengths=lengths)
+        if lengths is not None and self.model.spec.version == 20:  # the 2.0 model's per-clip door
+            return self.model.decode_ragged(acoustic_codes, semantic_codes, lengths=lengths)
         if lengths is not None:
             return self.model.decode(acoustic_codes, semantic_codes, lengths=lengths)
         if self.model.spec.adaptive:
