@@ -146,3 +146,26 @@ int launch_cond_prompt(float* x, const float* sos, const float* cond, int B, int
 }
 
 }  // namespace qa
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (not part of the public header): one launcher each on caller-provided device buffers, the launcher's arguments in its
+// order and the stream last (tests/test_front_kernels_gpu.py)
+extern "C" int qa_debug_glu_dwconv_bn_silu(const float* u, const float* w31, const float* bias, const float* scale, const float* shift,
+                                           float* y, int B, int T, int C, void* stream) {
+    return qa::launch_glu_dwconv_bn_silu(u, w31, bias, scale, shift, y, B, T, C, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_masked_add(float* x, float* y, const unsigned char* valid, long long rows, int C, void* stream) {
+    return qa::launch_masked_add(x, y, valid, rows, C, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_mask_count(const unsigned char* valid, int B, int T, int* counts, void* stream) {
+    return qa::launch_mask_count(valid, B, T, counts, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_logmel_frames(const float* wav, int B, long long n, int pad, long long n_out, float* P, void* stream) {
+    return qa::launch_logmel_frames(wav, B, n, pad, n_out, P, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_log_eps(float* x, long long n, float eps, void* stream) {
+    return qa::launch_log_eps(x, n, eps, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_cond_prompt(float* x, const float* sos, const float* cond, int B, int T, int d, void* stream) {
+    return qa::launch_cond_prompt(x, sos, cond, B, T, d, static_cast<hipStream_t>(stream));
+}

@@ -31,7 +31,7 @@ struct SeanetFrontParams {
     const float *wsc, *bsc;  // shortcut 1x1: [C][C], [C]
     const float *wpw, *bpw;  // 1x1 after the k3: [C][32] (columns >= hid are zero), [C]
     float* a;                // [B, L, C]
-    int B, L, hid8;          // hid8 = hidden width rounded up to 8 (K steps of the second contraction)
+    int B, L;
     int pl3, Lp3, pl0, Lp0;  // left paddings and short-input lengths of the k3 / k7 reflect pads
 };
 
@@ -210,7 +210,7 @@ int launch_seanet_front(const float* wav, const float* w0, const float* b0, cons
                "shape C=%d hid=%d L=%d", C, hid, L);
     SeanetFrontParams p{};
     p.wav = wav; p.w0 = w0; p.b0 = b0; p.w3 = w3; p.b3 = b3; p.wsc = wsc; p.bsc = bsc; p.wpw = wpw; p.bpw = bpw; p.a = a;
-    p.B = B; p.L = L; p.hid8 = (int)round_up(hid, 8);
+    p.B = B; p.L = L;
     p.pl3 = causal ? 2 : 1;
     p.pl0 = causal ? 6 : 3;
     const int mp3 = causal ? 2 : 1, mp0 = causal ? 6 : 3;
@@ -227,3 +227,13 @@ int launch_seanet_front(const float* wav, const float* w0, const float* b0, cons
 }
 
 }  // namespace qa
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (not part of the public header): the fused front alone on caller-provided device buffers, weights in the library layouts
+// of launch_seanet_front (tests/test_front_kernels_gpu.py)
+extern "C" int qa_debug_seanet_front_supported(int C, int hid, int L) { return qa::seanet_front_supported(C, hid, L) ? 1 : 0; }
+extern "C" int qa_debug_seanet_front(const float* wav, const float* w0, const float* b0, const float* w3, const float* b3, const float* wsc,
+                                     const float* bsc, const float* wpw, const float* bpw, float* a, int B, int L, int C, int hid,
+                                     int causal, void* stream) {
+    return qa::launch_seanet_front(wav, w0, b0, w3, b3, wsc, bsc, wpw, bpw, a, B, L, C, hid, causal, static_cast<hipStream_t>(stream));
+}

@@ -221,3 +221,28 @@ int launch_ssl_compress(const float* sum, float* out, long long n, float scale, 
 }
 
 }  // namespace qa
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (not part of the public header): one launcher each on caller-provided device buffers, the launcher's arguments in its
+// order with the per-clip length arrays (device int32 [B] or null) behind them and the stream last (tests/test_front_kernels_gpu.py)
+extern "C" long long qa_debug_ssl_conv0_scratch_bytes(int B, int T1, int C0) { return (long long)qa::ssl_conv0_scratch_bytes(B, T1, C0); }
+extern "C" int qa_debug_ssl_conv0(const float* wav, const float* w_kc, const float* bias, const float* gamma, const float* beta, float* y,
+                                  void* scratch, int B, int T, int T1, int C0, int ksize, int stride, int pad, int norm_group, float eps,
+                                  int act, const int* wav_len, const int* l0_len, void* stream) {
+    return qa::launch_ssl_conv0(wav, w_kc, bias, gamma, beta, y, scratch, B, T, T1, C0, ksize, stride, pad, norm_group, eps, act,
+                                static_cast<hipStream_t>(stream), wav_len, l0_len);
+}
+extern "C" int qa_debug_ssl_gate(const float* hidden, const float* wab, const float* bab, const float* cst, float* gate, int B, int N, int H,
+                                 int hd, void* stream) {
+    return qa::launch_ssl_gate(hidden, wab, bab, cst, gate, B, N, H, hd, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_ssl_accumulate(float* dst, const float* src, long long n, int first, void* stream) {
+    return qa::launch_ssl_accumulate(dst, src, n, first, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_ssl_act(float* x, long long n, int act, void* stream) {
+    return qa::launch_ssl_act(x, n, act, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_ssl_compress(const float* sum, float* out, long long n, float scale, float expo, const int* n_len, int N, int d,
+                                     void* stream) {
+    return qa::launch_ssl_compress(sum, out, n, scale, expo, static_cast<hipStream_t>(stream), n_len, N, d);
+}
