@@ -723,6 +723,31 @@ int qa_lm_cache_select(qa_lm_cache* cache, const int64_t* idx, int64_t n, void* 
  * the largest B * n seen (growing waits for the device). */
 int qa_lm_forward(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int64_t B, int64_t n, float* last_hidden, float* all_hidden,
                   void* stream);
+/* Per-row lengths (ragged sessions).  Every row of a cache has a length of its own; the calls above see a cache whose rows are all
+ * equally long exactly as before.  On a cache with unequal rows: qa_lm_cache_length is the LONGEST row; qa_lm_cache_crop(len) needs
+ * len <= the longest row and sets every row to min(its length, len); qa_lm_cache_select gives row j the contents AND the length of old
+ * row idx[j] (each move copies that row's own length); qa_lm_cache_reset clears every length; qa_lm_forward(n) feeds n positions to every
+ * row at the row's own position (the ragged call below with n[b] = n), so a greedy loop after a ragged prefill keeps calling it with
+ * n = 1.
+ *
+ * qa_lm_forward_ragged: inputs_embeds and last_hidden [B, n_max, hidden], all_hidden NULL or [(n_layers + 1), B, n_max, hidden]; n is
+ * a HOST int64 [B] with 0 <= n[b] <= n_max, read during the call only (the lengths reach the device as kernel arguments, into an array
+ * the cache owns).  Row b's first n[b] positions run at positions len[b] .. len[b] + n[b] - 1, causal over the row's own len[b] + n[b]
+ * keys; then len[b] += n[b].  The row's result is what qa_lm_forward gives that sequence alone, bit for bit.  Input entries t >= n[b]
+ * are never read; the same entries of last_hidden and all_hidden are written as exactly 0.  n[b] = 0 is an idle row: it does not
+ * advance and no K / V position is written for it.  No row writes a K / V position at or behind its new length, so a row may end at
+ * max_len with n[b] < n_max, and an idle row may already stand at max_len.  A call whose n is all zeros succeeds and launches nothing.
+ * `cache` is required.  Every check (NULL n, n[b] outside 0 .. n_max, len[b] + n[b] > max_len, B against max_batch and the fixed
+ * batch) runs before the first launch, names the row and its value, and leaves the cache as it was.  Refused under a stream capture.
+ * The path follows n_max alone: n_max >= 2 the chunk kernels, n_max = 1 the fused step in groups of 64.  With every row at one length
+ * and every n[b] = n_max the call IS qa_lm_forward: the same launches, the same bits.
+ * qa_lm_cache_lengths: out HOST int64 [batch] <- the rows' lengths.
+ * qa_lm_cache_crop_rows: lens HOST int64 [batch], 0 <= lens[b] <= length of row b; host state only, like qa_lm_cache_crop.  A row
+ * joins a running batch as: select (grow by one row), crop_rows (the new row to 0), forward_ragged with n = [0, .., 0, L]. */
+int qa_lm_forward_ragged(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int64_t B, int64_t n_max, const int64_t* n,
+                         float* last_hidden, float* all_hidden, void* stream);
+int qa_lm_cache_lengths(const qa_lm_cache* cache, int64_t* out);
+int qa_lm_cache_crop_rows(qa_lm_cache* cache, const int64_t* lens);
 /* The submodules of LLM_SFT as device calls, so that a caller's decode loop never leaves the library.
  * qa_lm_embed: out [n, hidden] = codec_embedding[ids[i]] (ids device int64, raw vocabulary ids).  The kernel clamps for memory safety;
  *   check the ids with qa_codes_check first (the reference's nn.Embedding raises IndexError).

@@ -261,6 +261,10 @@ SYMBOLS = {
     "qa_lm_cache_crop": (C.c_int, [C.c_void_p, C.c_int64]),
     "qa_lm_cache_select": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_void_p]),
     "qa_lm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "qa_lm_cache_lengths": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "qa_lm_cache_crop_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "qa_lm_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "qa_lm_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "qa_lm_prompt": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -249,14 +249,20 @@ struct AttForm<HD, true> {
 // every query of its batch item.  A tile's validity bytes travel with its K rows (register-staged, unconditional loads) and sit in
 // the padding behind each K row in LDS (AttForm::key_valid).
 // gate / relbias / R are read only with BIAS, kvalid only with KMASK.
-template <int HD, bool BIAS, bool KMASK, bool SPLIT>
+// RAGGED: a causal chunk over a KV cache whose items differ in length (a qa_lm_cache session).  Item b holds
+// row_pos0[b] cached keys and row_nq[b] <= n_q live query rows: its counts nq / nk replace the launch's in every test below, while n_q
+// stays the row count of the q / out layout.  A (sequence, head) belongs to one workgroup column that starts at key 0, so an item's walk
+// never depends on its neighbours; query rows behind nq are written as exact zeros, and a workgroup with no live query only does that.
+// row_pos0 / row_nq are read only with RAGGED: every other instantiation keeps its code.
+template <int HD, bool BIAS, bool KMASK, bool SPLIT, bool RAGGED = false>
 __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_kernel(const float* __restrict__ q, long long ldq,
                                                         const float* __restrict__ k, const float* __restrict__ v,
                                                         long long ldkv, long long kv_bstride, float* __restrict__ out,
                                                         long long ldo, int n_q, int n_keys, float scale, int causal,
                                                         const float* __restrict__ gate, const float* __restrict__ relbias, int R,
                                                         int context, int q_pos0, int ring_end, int dbg_arg,
-                                                        const unsigned char* __restrict__ kvalid) {
+                                                        const unsigned char* __restrict__ kvalid,
+                                                        const int* __restrict__ row_pos0, const int* __restrict__ row_nq) {
 #if defined(QA_ATT_DBG) && QA_ATT_DBG == 0
     constexpr int dbg = 0;
     (void)dbg_arg;
@@ -276,14 +282,26 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
     const int b = blockIdx.z, head = blockIdx.y;
     const int q_blk0 = blockIdx.x * 128;
     const int qi = q_blk0 + wave * 32 + ql;
-    const int off = n_keys - n_q;  // causal: key j visible iff j <= qi + off
+    const int nq = RAGGED ? row_nq[b] : n_q;              // live queries and keys of this item
+    const int nk = RAGGED ? row_pos0[b] + nq : n_keys;
+    if (RAGGED && q_blk0 >= nq) {  // workgroup-uniform, before the first barrier: no live query here (an idle item, or a block behind nq)
+        if (qi < n_q) {
+            float* op = out + ((long long)b * n_q + qi) * ldo + head * HD + 4 * hh;
+#pragma unroll
+            for (int t = 0; t < HD / 32; ++t)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) *reinterpret_cast<float4*>(op + 32 * t + 8 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
+    const int off = nk - nq;  // causal: key j visible iff j <= qi + off
 
     // The softmax runs in base 2: scale * log2(e) is folded into Q once, so that a score needs no multiply and an exponential is the
     // single v_exp_f32 instruction (ocml's expf is ~10 instructions, and a vector instruction issued beside the other waves' MFMAs
     // costs ~30 cycles, conv_gemm.hip)
     constexpr float LOG2E = 1.4426950408889634f;
     Form form(sK, sV, lane, dbg);
-    form.load_q(q + ((long long)b * n_q + (qi < n_q ? qi : n_q - 1)) * ldq + head * HD, scale * LOG2E);
+    form.load_q(q + ((long long)b * n_q + (qi < nq ? qi : nq - 1)) * ldq + head * HD, scale * LOG2E);
 
     float gate_q = 0.f;
     const float* rb = nullptr;
@@ -304,14 +322,14 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
 
     const bool ring = ring_end > 0;
     const bool lin_causal = causal && !ring;
-    int last_key = n_keys - 1, first_key = 0;
+    int last_key = nk - 1, first_key = 0;
     if (lin_causal) {
-        const int q_last = min(q_blk0 + 127, n_q - 1);
+        const int q_last = min(q_blk0 + 127, nq - 1);
         last_key = min(last_key, q_last + off);
         if (context > 0) first_key = max(0, q_blk0 + off - context + 1);
     }
     const int n_tiles = last_key / 32 + 1, kt0 = first_key / 32;
-    const int wave_last_key = lin_causal ? min(n_keys - 1, min(q_blk0 + wave * 32 + 31, n_q - 1) + off) : n_keys - 1;
+    const int wave_last_key = lin_causal ? min(nk - 1, min(q_blk0 + wave * 32 + 31, nq - 1) + off) : nk - 1;
     const int wave_first_key = (lin_causal && context > 0) ? max(0, q_blk0 + wave * 32 + off - context + 1) : 0;
     const int ring_idx = ring ? ring_end % n_keys : 0;  // RingKVCache.complete(): end_index
 
@@ -331,12 +349,12 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
     float mreg = 1.f;
     const unsigned char* kvb = KMASK ? kvalid + (long long)b * n_keys : nullptr;
     auto fetch = [&](int kt) {
-        if (KMASK) mreg = kvb[min(kt * 32 + (tid & 31), n_keys - 1)] ? 1.f : 0.f;
+        if (KMASK) mreg = kvb[min(kt * 32 + (tid & 31), nk - 1)] ? 1.f : 0.f;
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int i = tid + 256 * j;
             const int row = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
-            const int key = min(kt * 32 + row, n_keys - 1);
+            const int key = min(kt * 32 + row, nk - 1);
             kreg[j] = *reinterpret_cast<const f32x4*>(kb + (long long)key * ldkv + c4);
             vreg[j] = *reinterpret_cast<const f32x4*>(vb + (long long)key * ldkv + c4);
         }
@@ -362,7 +380,7 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
         QA_ATT_TICK(0)
         // wave-uniform skips: the whole tile is masked for this wave, or the wave owns no query at all (the last query block of a
         // sequence that is not a multiple of 128: at N = 283 three of the four waves of block 3 would multiply clamped rows)
-        if (!(dbg & 8) && (kt * 32 > wave_last_key || kt * 32 + 31 < wave_first_key || q_blk0 + wave * 32 >= n_q)) continue;
+        if (!(dbg & 8) && (kt * 32 > wave_last_key || kt * 32 + 31 < wave_first_key || q_blk0 + wave * 32 >= nq)) continue;
 
         f32x16 s;
 #pragma unroll
@@ -372,14 +390,14 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
         // online softmax in base 2 (per lane = per query; the two halves of the wave hold interleaved key groups).  Masks are
         // evaluated only on tiles that can contain a hidden key for some query of this wave (wave-uniform test).
         const int q_first = q_blk0 + wave * 32, q_last = q_first + 31;
-        const bool need_mask = KMASK || (dbg & 16) || ring || kt * 32 + 31 >= n_keys ||
+        const bool need_mask = KMASK || (dbg & 16) || ring || kt * 32 + 31 >= nk ||
                                (lin_causal && (kt * 32 + 31 > q_first + off || (context > 0 && kt * 32 < q_last + off - context + 1)));
         float tmax = -INFINITY;
         if (BIAS || need_mask) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                bool ok = key < n_keys;
+                bool ok = key < nk;
                 if (KMASK) ok = ok && form.key_valid((r & 3) + 8 * (r >> 2) + 4 * hh) != 0.f;
                 if (ring) {
                     const int delta = key - ring_idx;
@@ -444,6 +462,7 @@ __global__ __launch_bounds__(256, (AttForm<HD, SPLIT>::MIN_WG)) void attention_k
                 float4 w;
                 w.x = o[t][4 * c + 0] * inv; w.y = o[t][4 * c + 1] * inv;
                 w.z = o[t][4 * c + 2] * inv; w.w = o[t][4 * c + 3] * inv;
+                if (RAGGED && qi >= nq) w = make_float4(0.f, 0.f, 0.f, 0.f);  // a row of the layout behind the item's count
                 *reinterpret_cast<float4*>(op + 32 * t + 8 * c) = w;
             }
     }
@@ -463,7 +482,12 @@ static std::atomic<long long> g_att_kmask_launches;  // launches of a KMASK inst
 // Arithmetic: split-6 (SPLIT) unless QA_ATT_MATH = 0 or the caller asks for the fp32 chain (math_fp32: the UniSE LM, whose prefill
 // stays consistent with its fp32 decode kernels)
 int launch_attention(const AttnArgs& a, hipStream_t s) {
-    QA_REQUIRE(a.n_q > 0 && a.n_keys > 0 && (!a.causal || a.ring_end > 0 || a.n_keys >= a.n_q), "attention: n_q=%d n_keys=%d", a.n_q, a.n_keys);
+    const bool ragged = a.row_nq != nullptr;  // the items' own counts decide; n_keys is then only the longest item's
+    QA_REQUIRE(a.n_q > 0 && a.n_keys > 0 && (!a.causal || a.ring_end > 0 || ragged || a.n_keys >= a.n_q), "attention: n_q=%d n_keys=%d", a.n_q,
+               a.n_keys);
+    QA_REQUIRE((a.row_pos0 == nullptr) == (a.row_nq == nullptr) &&
+                   (!ragged || (a.causal && a.math_fp32 && !a.gate && !a.kvalid && a.context == 0 && a.ring_end <= 0)),
+               "attention: per-item lengths are for the plain causal fp32 form (no bias, key mask, window or ring)");
     QA_REQUIRE(a.context >= 0 && (a.context == 0 || a.causal) && (a.ring_end <= 0 || (a.causal && a.context > 0 && !a.gate)),
                "attention: a context window needs causal=1; the ring mode needs causal=1 and context > 0");
     QA_REQUIRE((a.ldq % 4) == 0 && (a.ldkv % 4) == 0 && (a.ldo % 4) == 0, "attention: strides must be multiples of 4");
@@ -482,9 +506,17 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
         case 128: kernel = split ? attention_instance<128, true>(bias, kmask) : attention_instance<128, false>(bias, kmask); break;
         default: qa::set_error("attention: head_dim=%d unsupported (32/64/96/128)", a.hd); return QA_ERR_UNSUPPORTED;
     }
+    if (ragged) {  // the fp32 form alone, one more flag on the same body
+        switch (a.hd) {
+            case 32: kernel = attention_kernel<32, false, false, false, true>; break;
+            case 64: kernel = attention_kernel<64, false, false, false, true>; break;
+            case 96: kernel = attention_kernel<96, false, false, false, true>; break;
+            default: kernel = attention_kernel<128, false, false, false, true>; break;
+        }
+    }
     hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(a.n_q, 128), a.H, a.B), dim3(256), 0, s, a.q, a.ldq, a.k, a.v, a.ldkv, a.kv_batch_stride,
                        a.out, a.ldo, a.n_q, a.n_keys, a.scale, a.causal, a.gate, a.relbias, a.R, a.context, a.q_pos0, a.ring_end,
-                       (int)knob(K_ATT_DEBUG), a.kvalid);
+                       (int)knob(K_ATT_DEBUG), a.kvalid, a.row_pos0, a.row_nq);
     QA_LAUNCH_CHECK();
     g_att_launches[split ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
     if (kmask) g_att_kmask_launches.fetch_add(1, std::memory_order_relaxed);

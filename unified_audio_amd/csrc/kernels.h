@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "lm_session_rows.h"
 
 namespace qa {
 
@@ -100,6 +101,10 @@ struct AttnArgs {
     int context = 0, q_pos0 = 0, ring_end = 0;  // causal window; ring mode (RingKVCache): position of query 0, end of the ring
     const unsigned char* kvalid = nullptr;
     bool math_fp32 = false;
+    // ragged causal chunk (fp32 form, no bias / mask / window): item b holds row_pos0[b] cached keys and row_nq[b] of
+    // the n_q query rows (device int [B] each, both or neither).  Query i < row_nq[b] sees key j iff j <= i + row_pos0[b], the key walk
+    // stops at row_pos0[b] + row_nq[b], query rows behind row_nq[b] are written as 0.  n_q stays the row count of the q / out layout
+    const int *row_pos0 = nullptr, *row_nq = nullptr;
 };
 int launch_attention(const AttnArgs& a, hipStream_t s);
 // self-attention over a packed projection qkv [B N, 3 d] (q | k | v, d = H hd) -> att [B N, d], scale 1 / sqrt(hd), non-causal; the
@@ -148,8 +153,18 @@ int launch_assemble_prompt(float* x, const float* task_vec, const float* enroll_
 int launch_skinny_gemm(const float* x, long long ldx, const float* w, const float* bias, const float* gate, long long ldg,
                        const float* res, long long ldr, float* y, long long ldy, int M, int N, int K, int act, hipStream_t s,
                        float rms_eps, int dual);
+// row_pos0 / row_n (device int [B], both or neither): item b's t-th row sits at position row_pos0[b] + t and only its first row_n[b]
+// rows are rotated and appended (a ragged chunk); nullptr: every item at pos0 with all n rows
 int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
-                   hipStream_t s);
+                   hipStream_t s, const int* row_pos0 = nullptr, const int* row_n = nullptr);
+// Host integers into device memory in stream order: dst[i] = vals[i], i < count.  The values ride in the kernel arguments (LM_ROW_INTS per
+// launch), so the host vector may be freed on return
+constexpr int LM_ROW_INTS = 256;
+int launch_lm_row_ints(int* dst, const int* vals, long long count, hipStream_t s);
+// y [B, n, d] <- x [B, n, d] for the rows t < row_n[b], exact zeros for the others, whose x rows are never read
+int launch_lm_rows_masked_copy(float* y, const float* x, int B, int n, int d, const int* row_n, hipStream_t s);
+// exact zeros into the rows t >= row_n[b] of every one of the `entries` tensors [B, n, d] that lie entry_stride floats apart
+int launch_lm_rows_zero_pad(float* y, long long entry_stride, int entries, int B, int n, int d, const int* row_n, hipStream_t s);
 int launch_lm_targets(float* x, long long ldx_seq, const float* table, const long long* gids, int G, const long long* sids, int T, int V,
                       int goff, int soff, long long* tgt, int B, int d, hipStream_t s, int drop = 0);
 int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, const long long* tgt, float c, float sm, float* row_kl,
@@ -157,14 +172,8 @@ int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, con
 int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
                          hipStream_t s);
 int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
-// one wave of independent row moves of a KV cache (qa_lm_cache_select), passed by value: row src[i] -> row dst[i], -1 = the spare row
-constexpr int KV_MOVES_MAX = 32;
-struct KvMoves {
-    int n;
-    int dst[KV_MOVES_MAX], src[KV_MOVES_MAX];
-};
-int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, int length, const KvMoves& mv,
-                        hipStream_t s);
+// one wave of independent row moves of a KV cache (qa_lm_cache_select; KvMoves: lm_session_rows.h), passed by value
+int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, const KvMoves& mv, hipStream_t s);
 
 // ssl_kernels.hip
 // wav_len / l0_len [B] (device, both or neither): clip b holds wav_len[b] of the T samples and l0_len[b] of the T1 layer-0 frames

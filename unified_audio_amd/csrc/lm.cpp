@@ -57,15 +57,21 @@ struct StepGraph {  // one captured decode step of a phase, replayable because e
 // A KV cache a caller holds across qa_lm_forward calls.  One device allocation of its own: K and V as
 // [layer][max_batch][max_len][hidden] fp32 (the row layout lm_body and the fused step use, with the layer stride fixed by max_batch so
 // that a batch select never moves a layer), one spare row per (layer, K / V) for the select's cycles, and the buffers of the n = 1 step.
-// Length and batch are HOST state.
+// Lengths and batch are HOST state.  Every row has a length of its own; a call that needs them on the device
+// writes them, in stream order, into `rows`.
 struct qa_lm_cache {
     qa_lm* lm = nullptr;
     int max_batch = 0, max_len = 0;
-    int B = 0;    // 0: not fixed yet (fresh or reset)
-    int len = 0;  // positions every row holds
+    int B = 0;             // 0: not fixed yet (fresh or reset)
+    std::vector<int> len;  // [max_batch] positions row b holds (rows behind B: 0)
     char* mem = nullptr;
     float *kc = nullptr, *vc = nullptr, *spare = nullptr;
+    // device ints [2][max_batch] of a ragged call: a chunk's (position of the first new row, new rows), a step's (offset to the step's
+    // position as GemvArgs::off, 1 or 0 new rows)
+    int* rows = nullptr;
     StepBufs step;  // n = 1 step, min(max_batch, 64) rows
+    int longest() const { return B > 0 ? *std::max_element(len.begin(), len.begin() + B) : 0; }
+    bool uniform() const { return B == 0 || std::all_of(len.begin(), len.begin() + B, [&](int v) { return v == len[0]; }); }
 };
 void cache_free(qa_lm_cache* c);
 
@@ -254,7 +260,7 @@ struct LMBuffers {
     long long* tok;
     float *logits, *pmax;  // head, pick / sample of generate's step
     int* pidx;
-    int* off;  // ragged generate: per-row position offsets L_b - L_max <= 0 (lm_decode.h GemvArgs::off); nullptr everywhere else
+    int* off;  // ragged generate, ragged session steps: per-row position offsets L_b - L_max <= 0 (lm_decode.h GemvArgs::off); nullptr everywhere else
     long long *ids_g, *ids_s;
     int cap;              // cache capacity
     size_t layer_stride;  // floats between two layers of kc / vc; 0: B * cap * d (generate's arena); a qa_lm_cache: max_batch * max_len * d
@@ -309,8 +315,10 @@ struct SampleCfg {
 // one_cache: every layer writes its keys / values into the same [B, max_len, d] pair (scoring: nothing reads a layer's cache after the
 // layer's own attention)
 // hidden (qa_lm_forward with all_hidden): entry i [B, n, d] <- the input of layer i
+// row_pos0 / row_n (device int [B], a ragged session chunk): sequence b's rows start at row_pos0[b] and only its first row_n[b] exist;
+// pos0 is then the LONGEST row's, so pos0 + n bounds every row's keys
 int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len, bool skip_last_mlp, bool one_cache = false,
-            float* hidden = nullptr) {
+            float* hidden = nullptr, const int* row_pos0 = nullptr, const int* row_n = nullptr) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H;
     const int64_t rows = (int64_t)B * n;
@@ -325,13 +333,14 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
         const bool last = skip_last_mlp && i == sp.n_layers - 1;  // prefill: only the KV cache of the last layer is consumed
         QA_TRY(rmsnorm_op(c, b.x, lm->ones, b.hn, rows, d, sp.rms_eps));
         QA_TRY(linear_op(c, b.hn, rows, L.qkv, b.qkv));
-        QA_RUN(c, launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream));
+        QA_RUN(c, launch_rope_kv(b.qkv, lm->rope, kc, vc, B, n, H, hd, pos0, max_len, c.stream, row_pos0, row_n));
         if (last) break;
         AttnArgs at;  // the n new queries over the layer's KV cache, causal
         at.q = b.qkv; at.ldq = 3 * d; at.out = b.att; at.ldo = d;
         at.k = kc; at.v = vc; at.ldkv = d; at.kv_batch_stride = (long long)max_len * d;
         at.B = B; at.n_q = n; at.n_keys = pos0 + n; at.H = H; at.hd = hd;
         at.scale = scale; at.causal = 1;
+        at.row_pos0 = row_pos0; at.row_nq = row_n;
         QA_TRY(attention_op(c, at));
         QA_TRY(linear_op(c, b.att, rows, L.o, b.x, epi(ACT_NONE, b.x)));
         QA_TRY(rmsnorm_op(c, b.x, lm->ones, b.hn, rows, d, sp.rms_eps));
@@ -787,12 +796,20 @@ struct ForwardArgs {
     const float* x;      // [B, n, d]
     int B, n;
     float *last_hidden, *all_hidden;
+    // ragged (needs a cache): row b feeds its first n_rows[b] <= n positions (HOST, checked); nullptr: rectangular
+    const int* n_rows = nullptr;
 };
 
 int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, B = a.B, n = a.n;
-    const int pos0 = a.cache ? a.cache->len : 0;
+    const bool ragged = a.n_rows != nullptr;
+    // ragged: the position of the LONGEST row that takes part - the step's position (the others sit off[b] <= 0 behind it), and with
+    // pos0 + n a bound on every row's keys in the chunk path
+    int pos0 = a.cache && !ragged ? a.cache->len[0] : 0;
+    if (ragged)
+        for (int i = 0; i < B; ++i)
+            if (a.n_rows[i] > 0) pos0 = std::max(pos0, a.cache->len[(size_t)i]);
     const int64_t rows = (int64_t)B * n;
     const bool step = n == 1 && lm->fused_ok;
     LMBuffers b{};
@@ -807,11 +824,25 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
         b.vc = c.arena.alloc<float>((size_t)sp.n_layers * B * b.cap * d);
     }
     const size_t hs = (size_t)rows * d;  // one entry of all_hidden
+    int idle = 0;                        // idle rows of a ragged n = 1 step
     if (!step) {
         alloc_body(c.arena, b, rows, d, sp.intermediate);
         if (c.dry) return QA_OK;  // real-pass-only remainder
-        QA_HIP(hipMemcpyAsync(b.x, a.x, sizeof(float) * hs, hipMemcpyDeviceToDevice, c.stream));
-        QA_TRY(lm_body(lm, c, b, B, n, pos0, b.cap, false, false, a.all_hidden));
+        if (ragged) {
+            // the rows' lengths travel as kernel arguments into the cache's device array; the padded input rows are replaced by zeros
+            // without being read, and a zero row stays zero through the body (lm_rows_masked_copy_kernel): every padded output row is 0
+            int* const row_pos0 = a.cache->rows;
+            int* const row_n = a.cache->rows + B;
+            std::vector<int> vals((size_t)2 * B);
+            std::copy(a.cache->len.begin(), a.cache->len.begin() + B, vals.begin());
+            std::copy(a.n_rows, a.n_rows + B, vals.begin() + B);
+            QA_TRY(launch_lm_row_ints(row_pos0, vals.data(), 2 * (long long)B, c.stream));
+            QA_TRY(launch_lm_rows_masked_copy(b.x, a.x, B, n, d, row_n, c.stream));
+            QA_TRY(lm_body(lm, c, b, B, n, pos0, b.cap, false, false, a.all_hidden, row_pos0, row_n));
+        } else {
+            QA_HIP(hipMemcpyAsync(b.x, a.x, sizeof(float) * hs, hipMemcpyDeviceToDevice, c.stream));
+            QA_TRY(lm_body(lm, c, b, B, n, pos0, b.cap, false, false, a.all_hidden));
+        }
         QA_TRY(launch_rmsnorm(b.x, lm->norm_w, a.last_hidden, rows, d, sp.rms_eps, c.stream));
     } else {
         // the fused step's launches on the caller's rows, at most LM_MAX_ROWS of them per pass (a row's arithmetic does not know its group)
@@ -820,12 +851,23 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
         else alloc_step(lm, c.arena, b.step, GB, b.cap);  // its state words are never read: the position is a launch argument
         if (c.dry) return QA_OK;  // real-pass-only remainder
         const size_t row_stride = (size_t)b.cap * d;
+        if (ragged) {  // off[b] as ragged generate passes it; an idle row's is -(pos0 + 1): position -1, no key, no append (lm_decode.hip)
+            std::vector<int> vals((size_t)2 * B);
+            for (int i = 0; i < B; ++i) {
+                const bool on = a.n_rows[i] > 0;
+                vals[(size_t)i] = on ? a.cache->len[(size_t)i] - pos0 : -(pos0 + 1);
+                vals[(size_t)B + i] = on ? 1 : 0;
+                idle += !on;
+            }
+            QA_TRY(launch_lm_row_ints(a.cache->rows, vals.data(), 2 * (long long)B, c.stream));
+        }
         for (int b0 = 0; b0 < B; b0 += GB) {
             const int gb = std::min(GB, B - b0);
             LMBuffers g = b;
             g.kc = b.kc + b0 * row_stride;
             g.vc = b.vc + b0 * row_stride;
             if (!g.layer_stride) g.layer_stride = (size_t)B * b.cap * d;  // the whole call's layer, not the group's
+            if (ragged) g.off = a.cache->rows + b0;
             StepIO io;
             io.x_in = a.x + (size_t)b0 * d;
             if (a.all_hidden) {
@@ -836,8 +878,14 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
             QA_TRY(launch_rmsnorm(b.step.x, lm->norm_w, a.last_hidden + (size_t)b0 * d, gb, d, sp.rms_eps, c.stream));
         }
     }
-    if (a.all_hidden)  // llm.py:216-220: the last entry is the final norm's output
+    // a ragged step computed its idle rows too (on whatever their input rows held): their outputs become exact zeros, one launch each for
+    // last_hidden and for the layer inputs of all_hidden
+    const int* const step_n = step && ragged && idle ? a.cache->rows + B : nullptr;
+    if (step_n) QA_TRY(launch_lm_rows_zero_pad(a.last_hidden, 0, 1, B, 1, d, step_n, c.stream));
+    if (a.all_hidden) {  // llm.py:216-220: the last entry is the final norm's output
+        if (step_n) QA_TRY(launch_lm_rows_zero_pad(a.all_hidden, (long long)hs, sp.n_layers, B, 1, d, step_n, c.stream));
         QA_HIP(hipMemcpyAsync(a.all_hidden + (size_t)sp.n_layers * hs, a.last_hidden, sizeof(float) * hs, hipMemcpyDeviceToDevice, c.stream));
+    }
     return QA_OK;
 }
 
@@ -852,67 +900,6 @@ int run_session(qa_lm* lm, hipStream_t s, G&& graph) {
         return QA_OK;
     }));
     return graph();
-}
-
-// qa_lm_cache_select as waves of row moves.  Row j must become old row idx[j].  A move may run once nothing still pending reads its
-// destination, so the moves are emitted leaves first; what is left then is disjoint cycles, each opened by parking one row in the
-// cache's spare row (-1).  Consecutive moves that neither read nor overwrite one another's rows share a launch.
-void plan_cache_moves(const int64_t* idx, int n, int rows, std::vector<KvMoves>* waves) {
-    std::vector<int> src(n), readers(rows + 1, 0);  // readers[r + 1]: pending moves that read row r (r = -1: the spare row)
-    std::vector<char> pending(n, 0);
-    int left = 0;
-    for (int j = 0; j < n; ++j) {
-        src[j] = (int)idx[j];
-        if (src[j] != j) {
-            pending[j] = 1;
-            ++readers[src[j] + 1];
-            ++left;
-        }
-    }
-    std::vector<std::pair<int, int>> order;  // (dst, src)
-    auto emit_free = [&] {
-        for (bool progress = true; progress;) {
-            progress = false;
-            for (int j = 0; j < n; ++j)
-                if (pending[j] && readers[j + 1] == 0) {
-                    order.push_back({j, src[j]});
-                    --readers[src[j] + 1];
-                    pending[j] = 0;
-                    --left;
-                    progress = true;
-                }
-        }
-    };
-    emit_free();
-    while (left > 0) {  // only cycles are left: park one row of a cycle, let its reader take the spare row instead
-        int j = 0;
-        while (!pending[j]) ++j;
-        order.push_back({-1, j});
-        for (int k = 0; k < n; ++k)
-            if (pending[k] && src[k] == j) {
-                src[k] = -1;
-                ++readers[0];
-            }
-        readers[j + 1] = 0;
-        emit_free();
-    }
-    KvMoves w{};
-    std::vector<char> rd(rows + 1, 0), wr(rows + 1, 0);
-    auto flush = [&] {
-        if (w.n) waves->push_back(w);
-        w = KvMoves{};
-        std::fill(rd.begin(), rd.end(), 0);
-        std::fill(wr.begin(), wr.end(), 0);
-    };
-    for (const auto& m : order) {
-        if (w.n == KV_MOVES_MAX || wr[m.second + 1] || rd[m.first + 1] || wr[m.first + 1]) flush();
-        w.dst[w.n] = m.first;
-        w.src[w.n] = m.second;
-        ++w.n;
-        wr[m.first + 1] = 1;
-        rd[m.second + 1] = 1;
-    }
-    flush();
 }
 
 }  // namespace
@@ -943,6 +930,7 @@ int qa_lm_cache_create(qa_lm* lm, int64_t max_batch, int64_t max_len, qa_lm_cach
     std::unique_ptr<qa_lm_cache> c(new qa_lm_cache());
     c->max_batch = (int)max_batch;
     c->max_len = (int)max_len;
+    c->len.assign((size_t)max_batch, 0);
     const int GB = (int)std::min<int64_t>(max_batch, LM_MAX_ROWS);
     Arena layout;  // sizes the one allocation, then places the buffers in it
     auto place = [&] {
@@ -951,6 +939,7 @@ int qa_lm_cache_create(qa_lm* lm, int64_t max_batch, int64_t max_len, qa_lm_cach
         c->vc = layout.alloc<float>(plane);
         c->spare = layout.alloc<float>((size_t)sp.n_layers * 2 * max_len * sp.hidden);
         alloc_step(lm, layout, c->step, GB, c->max_len);
+        c->rows = layout.alloc<int>((size_t)2 * max_batch);  // behind everything else: the other buffers keep their offsets
     };
     layout.begin(nullptr, 0);
     place();
@@ -976,7 +965,16 @@ void qa_lm_cache_destroy(qa_lm_cache* cache) {
     cache_free(cache);
 }
 
-int64_t qa_lm_cache_length(const qa_lm_cache* cache) { return cache ? cache->len : 0; }
+int64_t qa_lm_cache_length(const qa_lm_cache* cache) { return cache ? cache->longest() : 0; }
+
+int qa_lm_cache_lengths(const qa_lm_cache* cache, int64_t* out) {
+    if (!cache || !out) {
+        set_error("qa_lm_cache_lengths: null argument");
+        return QA_ERR_INVALID;
+    }
+    for (int b = 0; b < cache->B; ++b) out[b] = cache->len[(size_t)b];
+    return QA_OK;
+}
 int64_t qa_lm_cache_batch(const qa_lm_cache* cache) { return cache ? cache->B : 0; }
 
 int qa_lm_cache_reset(qa_lm_cache* cache) {
@@ -984,7 +982,7 @@ int qa_lm_cache_reset(qa_lm_cache* cache) {
         set_error("qa_lm_cache_reset: null cache");
         return QA_ERR_INVALID;
     }
-    cache->len = 0;
+    std::fill(cache->len.begin(), cache->len.end(), 0);
     cache->B = 0;
     return QA_OK;
 }
@@ -994,9 +992,22 @@ int qa_lm_cache_crop(qa_lm_cache* cache, int64_t len) {
         set_error("qa_lm_cache_crop: null cache");
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(len >= 0 && len <= cache->len, "qa_lm_cache_crop: length %lld outside [0, %d] (the cache's current length)", (long long)len,
-               cache->len);
-    cache->len = (int)len;  // the rows behind it are stale and invisible: every reader stops at the length
+    QA_REQUIRE(len >= 0 && len <= cache->longest(), "qa_lm_cache_crop: length %lld outside [0, %d] (the cache's current length)", (long long)len,
+               cache->longest());
+    for (int b = 0; b < cache->B; ++b)  // the rows behind it are stale and invisible: every reader stops at its row's length
+        cache->len[(size_t)b] = std::min(cache->len[(size_t)b], (int)len);
+    return QA_OK;
+}
+
+int qa_lm_cache_crop_rows(qa_lm_cache* cache, const int64_t* lens) {
+    if (!cache || !lens) {
+        set_error("qa_lm_cache_crop_rows: null argument");
+        return QA_ERR_INVALID;
+    }
+    const int64_t bad = check_crop_rows(lens, cache->len.data(), cache->B);
+    QA_REQUIRE(bad < 0, "qa_lm_cache_crop_rows: lens[%lld] = %lld outside [0, %d] (the length of row %lld)", (long long)bad, (long long)lens[bad],
+               cache->len[(size_t)bad], (long long)bad);
+    for (int b = 0; b < cache->B; ++b) cache->len[(size_t)b] = (int)lens[b];
     return QA_OK;
 }
 
@@ -1015,15 +1026,68 @@ int qa_lm_cache_select(qa_lm_cache* cache, const int64_t* idx, int64_t n, void* 
                    (long long)j, (long long)idx[j], cache->B);
     qa_lm* lm = cache->lm;
     QA_HIP(hipSetDevice(lm->device));
-    if (cache->len > 0) {
+    if (cache->longest() > 0) {  // every move carries the length of the row it moves
         std::vector<KvMoves> waves;
-        plan_cache_moves(idx, (int)n, std::max(cache->B, (int)n), &waves);
+        plan_cache_moves(idx, cache->len.data(), (int)n, std::max(cache->B, (int)n), &waves);
         for (const KvMoves& w : waves)
-            QA_TRY(launch_kv_row_moves(cache->kc, cache->vc, cache->spare, lm->spec.n_layers, cache->max_batch, cache->max_len, lm->spec.hidden,
-                                       cache->len, w, s));
+            QA_TRY(launch_kv_row_moves(cache->kc, cache->vc, cache->spare, lm->spec.n_layers, cache->max_batch, cache->max_len, lm->spec.hidden, w, s));
     }
+    std::vector<int> len_new((size_t)cache->max_batch, 0);
+    for (int64_t j = 0; j < n; ++j) len_new[(size_t)j] = cache->len[(size_t)idx[j]];
+    cache->len.swap(len_new);
     cache->B = (int)n;
     return QA_OK;
+}
+
+// what qa_lm_forward and qa_lm_forward_ragged share once their arguments are checked: run, then advance the rows
+static int lm_forward_run(qa_lm* lm, hipStream_t s, const ForwardArgs& a) {
+    QA_TRY(run_session(lm, s, [&] { return forward_graph(lm, lm->sess_ctx, a); }));
+    if (qa_lm_cache* cache = a.cache) {
+        cache->B = a.B;
+        for (int b = 0; b < a.B; ++b) cache->len[(size_t)b] += a.n_rows ? a.n_rows[b] : a.n;
+    }
+    return QA_OK;
+}
+
+static int lm_forward_cache_checks(const char* fn, qa_lm* lm, qa_lm_cache* cache, int64_t B) {
+    QA_REQUIRE(cache->lm == lm, "%s: the cache belongs to another qa_lm handle", fn);
+    QA_REQUIRE(B <= cache->max_batch, "%s: B = %lld exceeds the cache's max_batch %d", fn, (long long)B, cache->max_batch);
+    QA_REQUIRE(cache->B == 0 || B == cache->B, "%s: B = %lld, but the cache holds %d sequences (the first call fixes the batch; "
+               "qa_lm_cache_select changes it, qa_lm_cache_reset frees it)", fn, (long long)B, cache->B);
+    return QA_OK;
+}
+
+int qa_lm_forward_ragged(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int64_t B, int64_t n_max, const int64_t* n,
+                         float* last_hidden, float* all_hidden, void* stream) {
+    const char* fn = "qa_lm_forward_ragged";
+    if (!lm || !inputs_embeds || !last_hidden) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture(fn, s));
+    QA_REQUIRE(cache, "%s: a qa_lm_cache is required - without one every row starts at position 0 and a causal pass over left-aligned rows "
+               "is qa_lm_forward", fn);
+    QA_REQUIRE(n, "%s: null n (HOST int64 [B], the rows' position counts)", fn);
+    QA_REQUIRE(B >= 1 && n_max >= 1 && B <= (1 << 16) && n_max <= LM_MAX_POS, "%s: bad shape B = %lld, n_max = %lld", fn, (long long)B,
+               (long long)n_max);
+    QA_TRY(lm_forward_cache_checks(fn, lm, cache, B));
+    // every check comes before the first launch and leaves the cache as it was
+    std::vector<int> n_rows;
+    int64_t row = 0;
+    int active = 0;
+    bool uniform = false;
+    const SessionRowsFault f = check_session_rows(n, cache->len.data(), B, n_max, cache->max_len, &row, &n_rows, &active, &uniform);
+    QA_REQUIRE(f != SR_COUNT_RANGE, "%s: n[%lld] = %lld is outside 0 .. n_max = %lld", fn, (long long)row, (long long)n[row], (long long)n_max);
+    QA_REQUIRE(f != SR_OVER_CAPACITY, "%s: row %lld holds %d positions, + n[%lld] = %lld exceed the cache's max_len %d", fn, (long long)row,
+               cache->len[(size_t)row], (long long)row, (long long)n[row], cache->max_len);
+    if (active == 0) {  // nothing to do: no launch, no row advances (the batch is still fixed, as by any call)
+        cache->B = (int)B;
+        return QA_OK;
+    }
+    ForwardArgs a{cache, inputs_embeds, (int)B, (int)n_max, last_hidden, all_hidden};
+    if (!uniform) a.n_rows = n_rows.data();  // a rectangular call IS qa_lm_forward: its launches, its bits
+    return lm_forward_run(lm, s, a);
 }
 
 int qa_lm_forward(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int64_t B, int64_t n, float* last_hidden, float* all_hidden,
@@ -1035,23 +1099,18 @@ int qa_lm_forward(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     QA_TRY(refuse_capture("qa_lm_forward", s));
     QA_REQUIRE(B >= 1 && n >= 1 && B <= (1 << 16), "qa_lm_forward: bad shape B = %lld, n = %lld", (long long)B, (long long)n);
+    std::vector<int> n_rows;
     if (cache) {
-        QA_REQUIRE(cache->lm == lm, "qa_lm_forward: the cache belongs to another qa_lm handle");
-        QA_REQUIRE(B <= cache->max_batch, "qa_lm_forward: B = %lld exceeds the cache's max_batch %d", (long long)B, cache->max_batch);
-        QA_REQUIRE(cache->B == 0 || B == cache->B, "qa_lm_forward: B = %lld, but the cache holds %d sequences (the first call fixes the batch; "
-                   "qa_lm_cache_select changes it, qa_lm_cache_reset frees it)", (long long)B, cache->B);
-        QA_REQUIRE(cache->len + n <= cache->max_len, "qa_lm_forward: %d cached + %lld new positions exceed the cache's max_len %d", cache->len,
-                   (long long)n, cache->max_len);
+        QA_TRY(lm_forward_cache_checks("qa_lm_forward", lm, cache, B));
+        QA_REQUIRE(cache->longest() + n <= cache->max_len, "qa_lm_forward: %d cached + %lld new positions exceed the cache's max_len %d%s",
+                   cache->longest(), (long long)n, cache->max_len, cache->uniform() ? "" : " (the longest row)");
+        if (!cache->uniform()) n_rows.assign((size_t)B, (int)n);  // rows of unequal lengths: the ragged call with n[b] = n
     } else {
         QA_REQUIRE(n <= LM_MAX_POS, "qa_lm_forward: %lld positions exceed max_position_embeddings %d", (long long)n, LM_MAX_POS);
     }
-    const ForwardArgs a{cache, inputs_embeds, (int)B, (int)n, last_hidden, all_hidden};
-    QA_TRY(run_session(lm, s, [&] { return forward_graph(lm, lm->sess_ctx, a); }));
-    if (cache) {
-        cache->B = (int)B;
-        cache->len += (int)n;
-    }
-    return QA_OK;
+    ForwardArgs a{cache, inputs_embeds, (int)B, (int)n, last_hidden, all_hidden};
+    if (!n_rows.empty()) a.n_rows = n_rows.data();
+    return lm_forward_run(lm, s, a);
 }
 
 int qa_lm_embed(qa_lm* lm, const int64_t* ids, int64_t n, float* out, void* stream) {

@@ -43,6 +43,7 @@ struct GemvArgs {
     int pos;  // >= 0: position of the step (host-driven loop); < 0: read it from state (captured step)
     // ragged batches: off[row] = L_row - L_max <= 0, the row's position is the step's plus off[row].  Device memory,
     // written once per call, so a captured step serves every length vector.  nullptr: every row sits at the step's position
+    // A session step (lm.cpp forward_graph) marks an IDLE row with off[row] = -(pos + 1): position -1, no K / V append, no key
     const int* off;
     // GM_QKV
     const float* rope;  // [pos][hd/2][2] cos, sin

@@ -204,11 +204,14 @@ __device__ __forceinline__ void epi_prefetch(const GemvArgs& a, int tile, int ti
             if (i < MT * 16 * HP) {
                 const int row = i / HP, j = i - row * HP;
                 // ragged batch: the row's own position (a wave-uniform branch; rows past M re-read the last row and are never stored)
+                // An IDLE row of a session step (lm.cpp forward_graph) carries off = -(pos + 1): its position is -1,
+                // it reads RoPE row 0 and the epilogue appends nothing for it
                 if (a.off) e.pos[u] = pos + a.off[min(row, a.M - 1)];
                 if (sec != 2) {
                     const int ri = ((c0 - h * hd) / NT) * HP + j;
-                    e.c[u] = a.rope[((long long)e.pos[u] * half + ri) * 2];
-                    e.s[u] = a.rope[((long long)e.pos[u] * half + ri) * 2 + 1];
+                    const long long rp = a.off ? max(e.pos[u], 0) : e.pos[u];
+                    e.c[u] = a.rope[(rp * half + ri) * 2];
+                    e.s[u] = a.rope[(rp * half + ri) * 2 + 1];
                 }
             }
         }
@@ -249,6 +252,7 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, const float (*p
                 const int sec = tile / tps, c0 = (tile - sec * tps) * NT;
                 const int h = c0 / hd, ri = ((c0 - h * hd) / NT) * HP + j;  // rotary index in [0, hd/2)
                 const int pos = e.pos[u];
+                if (sec != 0 && pos < 0) continue;  // an idle row (epi_prefetch): no K / V write - the row may already stand at its capacity
                 if (sec == 2) {  // V: no rotation
                     float* dst = a.vc + (long long)row * a.kv_bstride + (long long)pos * d + h * hd;
                     dst[ri] = v1;
@@ -859,6 +863,7 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
     const int b = blockIdx.y, h = blockIdx.x, sp = blockIdx.z, S = gridDim.z, H = gridDim.x;
     const int kq = lane / LPK, c4 = (lane % LPK) * 4;
     // ragged batch (off != nullptr): sequence b sits off[b] <= 0 positions behind the step's position and owns that many keys fewer
+    // (an idle row of a session step owns none: no tile, no load, an identity record)
     const int n_keys = (pos >= 0 ? pos : state[ST_POS]) + 1 + (off ? off[b] : 0);
     const int n_tiles = (n_keys + 15) >> 4;
     const int t0 = sp * tps, t_end = min(t0 + tps, n_tiles);  // this split's tiles (empty past the last key)

@@ -5,6 +5,8 @@
 // single-query attention behind QA_LM_UNFUSED) were removed in round 5.
 #include "kernels.h"
 
+#include <cstring>
+
 namespace qa {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -185,9 +187,13 @@ int launch_skinny_gemm(const float* x, long long ldx, const float* w, const floa
 }
 
 // RoPE (rotate-half, position pos0 + t) on the q and k parts of a fused [B*n, 3d] buffer in place, and append k, v to the caches
+// RAGGED (a session chunk with per-row lengths): item b's rows start at position row_pos0[b] and only its first
+// row_n[b] rows exist - the others are neither rotated nor appended, so a row that ends at max_len writes nothing into its neighbour
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void rope_kv_kernel(float* __restrict__ qkv, const float* __restrict__ cs,
                                                       float* __restrict__ kc, float* __restrict__ vc, int B, int n, int H,
-                                                      int hd, int pos0, int max_len) {
+                                                      int hd, int pos0, int max_len, const int* __restrict__ row_pos0,
+                                                      const int* __restrict__ row_n) {
     const int half = hd >> 1, d = H * hd;
     const long long total = (long long)B * n * H * half;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -196,6 +202,10 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(float* __restrict__ qkv, c
     const int h = (int)((gid / half) % H);
     const long long row = gid / ((long long)half * H);
     const int b = (int)(row / n), t = (int)(row % n);
+    if (RAGGED) {
+        if (t >= row_n[b]) return;
+        pos0 = row_pos0[b];
+    }
     const int pos = pos0 + t;
     const float c = cs[((long long)pos * half + i) * 2], sn = cs[((long long)pos * half + i) * 2 + 1];
     float* q = qkv + row * 3 * d + h * hd;
@@ -212,10 +222,72 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(float* __restrict__ qkv, c
     vc[dst + i + half] = v[i + half];
 }
 int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
-                   hipStream_t s) {
+                   hipStream_t s, const int* row_pos0, const int* row_n) {
+    QA_REQUIRE((row_pos0 == nullptr) == (row_n == nullptr), "rope_kv: per-row positions and counts come together");
     const long long total = (long long)B * n * H * (hd / 2);
-    hipLaunchKernelGGL(rope_kv_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0,
-                       max_len);
+    const dim3 grid((unsigned)ceil_div(total, 256));
+    if (row_n) hipLaunchKernelGGL(rope_kv_kernel<true>, grid, dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0, max_len, row_pos0, row_n);
+    else hipLaunchKernelGGL(rope_kv_kernel<false>, grid, dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0, max_len, row_pos0, row_n);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-row lengths of a session call.  The lengths are host data: they ride in the kernel arguments and land in
+// a device array the cache owns, in stream order (as launch_lm_offsets does for ragged generate).
+struct RowInts {
+    int v[LM_ROW_INTS];
+};
+__global__ __launch_bounds__(LM_ROW_INTS) void lm_row_ints_kernel(int* __restrict__ dst, const RowInts vals, int count) {
+    const int i = threadIdx.x;
+    if (i < count) dst[i] = vals.v[i];
+}
+int launch_lm_row_ints(int* dst, const int* vals, long long count, hipStream_t s) {
+    for (long long i0 = 0; i0 < count; i0 += LM_ROW_INTS) {
+        const int c = (int)std::min<long long>(LM_ROW_INTS, count - i0);
+        RowInts r{};
+        std::memcpy(r.v, vals + i0, sizeof(int) * c);
+        hipLaunchKernelGGL(lm_row_ints_kernel, dim3(1), dim3(LM_ROW_INTS), 0, s, dst + i0, r, c);
+        QA_LAUNCH_CHECK();
+    }
+    return QA_OK;
+}
+
+// The input of a ragged chunk: rows t < row_n[b] are copied, the others become exact zeros WITHOUT being read.  A zero row stays a zero
+// row through the whole body (no projection of the Llama layers has a bias, RMSNorm and SwiGLU map 0 to 0, and the ragged attention
+// writes 0 for such a query), so the padded rows of every hidden state and of the final norm come out as 0 with no launch of their own.
+__global__ __launch_bounds__(256) void lm_rows_masked_copy_kernel(float4* __restrict__ y, const float4* __restrict__ x, int B, int n, int d4,
+                                                                  const int* __restrict__ row_n) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * n * d4) return;
+    const long long row = gid / d4;
+    const int b = (int)(row / n), t = (int)(row % n);
+    y[gid] = t < row_n[b] ? x[gid] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+int launch_lm_rows_masked_copy(float* y, const float* x, int B, int n, int d, const int* row_n, hipStream_t s) {
+    QA_REQUIRE(d % 4 == 0 && row_n, "lm_rows_masked_copy: bad launch");
+    const long long total = (long long)B * n * (d / 4);
+    hipLaunchKernelGGL(lm_rows_masked_copy_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, reinterpret_cast<float4*>(y),
+                       reinterpret_cast<const float4*>(x), B, n, d / 4, row_n);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// The outputs of a ragged n = 1 step: the fused step computes every row of its group, so the idle rows' outputs (and their copies in
+// all_hidden) are overwritten with exact zeros here, one launch for all entries.  Grid: x covers an entry, y = entry.
+__global__ __launch_bounds__(256) void lm_rows_zero_pad_kernel(float4* __restrict__ y, long long entry_stride4, int B, int n, int d4,
+                                                               const int* __restrict__ row_n) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * n * d4) return;
+    const long long row = gid / d4;
+    const int b = (int)(row / n), t = (int)(row % n);
+    if (t >= row_n[b]) y[(long long)blockIdx.y * entry_stride4 + gid] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+int launch_lm_rows_zero_pad(float* y, long long entry_stride, int entries, int B, int n, int d, const int* row_n, hipStream_t s) {
+    QA_REQUIRE(d % 4 == 0 && entry_stride % 4 == 0 && entries >= 1 && entries <= 65535 && row_n, "lm_rows_zero_pad: bad launch");
+    const long long total = (long long)B * n * (d / 4);
+    hipLaunchKernelGGL(lm_rows_zero_pad_kernel, dim3((unsigned)ceil_div(total, 256), (unsigned)entries), dim3(256), 0, s,
+                       reinterpret_cast<float4*>(y), entry_stride / 4, B, n, d / 4, row_n);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -400,32 +472,39 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// qa_lm_cache_select: one WAVE of row moves of a KV cache [layer][max_batch][max_len][d] (K and V), the first `n4` float4 of a row each
-// (length * d floats: stale positions behind the cache length are never copied).  Grid: x covers a row, y = move, z = layer * 2 + {K, V}.
+// qa_lm_cache_select: one WAVE of row moves of a KV cache [layer][max_batch][max_len][d] (K and V).  Move i copies the first mv.len[i]
+// positions of its row (the length of the row it carries rides with the move: stale positions behind it are never copied, and rows of
+// different lengths share a launch).  Grid: x covers the longest row of the wave, y = move, z = layer * 2 + {K, V}.
 // Row -1 is the cache's spare row [layer][K / V][max_len][d] (lm.cpp plan_cache_moves: it breaks a permutation cycle).  The moves of one
 // launch never read a row another move of the launch writes, so the launch is in-place safe; the host orders the waves on the stream.
 // Rows are whole 16-byte multiples (d % 32 == 0) and 16-byte aligned.
 __global__ __launch_bounds__(256) void kv_row_moves_kernel(float4* __restrict__ kc, float4* __restrict__ vc, float4* __restrict__ spare,
-                                                           long long layer4, long long row4, long long n4, const KvMoves mv) {
+                                                           long long layer4, long long row4, int d4, const KvMoves mv) {
     const int layer = blockIdx.z >> 1, kv = blockIdx.z & 1;
     const int dst = mv.dst[blockIdx.y], src = mv.src[blockIdx.y];
+    const long long n4 = (long long)mv.len[blockIdx.y] * d4;
     float4* base = (kv ? vc : kc) + layer * layer4;
     float4* sp = spare + (long long)blockIdx.z * row4;
     const float4* from = src < 0 ? sp : base + src * row4;
     float4* to = dst < 0 ? sp : base + dst * row4;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) to[i] = from[i];
 }
-int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, int length, const KvMoves& mv,
-                        hipStream_t s) {
-    QA_REQUIRE(mv.n >= 1 && mv.n <= KV_MOVES_MAX && d % 4 == 0 && length >= 1 && length <= max_len, "kv_row_moves: bad launch");
-    for (int i = 0; i < mv.n; ++i)
+int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, const KvMoves& mv, hipStream_t s) {
+    QA_REQUIRE(mv.n >= 1 && mv.n <= KV_MOVES_MAX && d % 4 == 0, "kv_row_moves: bad launch");
+    int longest = 0;
+    for (int i = 0; i < mv.n; ++i) {
         QA_REQUIRE(mv.dst[i] >= -1 && mv.dst[i] < max_batch && mv.src[i] >= -1 && mv.src[i] < max_batch && mv.dst[i] != mv.src[i],
                    "kv_row_moves: move %d -> %d outside the cache's %d rows", mv.src[i], mv.dst[i], max_batch);
-    const long long row4 = (long long)max_len * d / 4, n4 = (long long)length * d / 4;
+        QA_REQUIRE(mv.len[i] >= 0 && mv.len[i] <= max_len, "kv_row_moves: move %d -> %d of %d positions, the cache holds %d", mv.src[i], mv.dst[i],
+                   mv.len[i], max_len);
+        longest = std::max(longest, mv.len[i]);
+    }
+    if (longest == 0) return QA_OK;
+    const long long row4 = (long long)max_len * d / 4, n4 = (long long)longest * d / 4;
     // ~8 float4 per thread: enough workgroups to fill the device at one move, few enough that the tail is short
     const unsigned gx = (unsigned)std::min<long long>(ceil_div(n4, 256 * 8), 1024);
     hipLaunchKernelGGL(kv_row_moves_kernel, dim3(gx, (unsigned)mv.n, (unsigned)(2 * n_layers)), dim3(256), 0, s, reinterpret_cast<float4*>(kc),
-                       reinterpret_cast<float4*>(vc), reinterpret_cast<float4*>(spare), (long long)max_batch * row4, row4, n4, mv);
+                       reinterpret_cast<float4*>(vc), reinterpret_cast<float4*>(spare), (long long)max_batch * row4, row4, d / 4, mv);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

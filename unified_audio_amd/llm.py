@@ -25,8 +25,8 @@ MAX_POSITION_EMBEDDINGS = 4096  # conf/config.yaml:146
 
 class KVCache:
     """A key / value cache held across llm_forward calls (qa_lm_cache): what transformers' DynamicCache is to the reference's
-    llm_forward, with a fixed capacity.  Device memory of its own; its length and batch are host state.  Freed with this object, or
-    with the model's handle, whichever goes first."""
+    llm_forward, with a fixed capacity.  Device memory of its own; its batch and its rows' lengths are host state (every row has a
+    length of its own: llm_forward(..., chunk_lengths=)).  Freed with this object, or with the model's handle, whichever goes first."""
 
     def __init__(self, lm, max_batch: int, max_len: int = MAX_POSITION_EMBEDDINGS):
         self._lm = lm._lm if isinstance(lm, CustomLlamaModel) else lm
@@ -58,7 +58,21 @@ class KVCache:
         return torch.cuda.current_stream(self._lm.device).cuda_stream
 
     def get_seq_length(self) -> int:
+        """Positions held; on a cache whose rows differ in length, the longest row's."""
         return int(self._lib.qa_lm_cache_length(self._ptr()))
+
+    def get_seq_lengths(self) -> list:
+        """Positions held by every row: batch_size ints."""
+        arr = (C.c_int64 * max(self.batch_size, 1))()
+        _lib.check(self._lib.qa_lm_cache_lengths(self._ptr(), arr))
+        return [int(v) for v in arr[:self.batch_size]]
+
+    def crop_rows(self, lengths: Sequence[int]):
+        """Keep the first lengths[b] positions of row b (0 <= lengths[b] <= the row's length); batch_size ints."""
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != self.batch_size:
+            raise _lib.QuarkAudioError(-1, f"KVCache.crop_rows: {len(lens)} lengths for a cache of {self.batch_size} rows")
+        _lib.check(self._lib.qa_lm_cache_crop_rows(self._ptr(), (C.c_int64 * max(len(lens), 1))(*lens)))
 
     @property
     def batch_size(self) -> int:
@@ -68,7 +82,8 @@ class KVCache:
         _lib.check(self._lib.qa_lm_cache_reset(self._ptr()))
 
     def crop(self, max_length: int):
-        """DynamicCache.crop: keep the first `max_length` positions (negative: drop that many from the end)."""
+        """DynamicCache.crop: keep the first `max_length` positions (negative: drop that many from the end of the longest row); rows
+        that are shorter already keep their length."""
         n = int(max_length)
         if n < 0:
             n = self.get_seq_length() + n
@@ -157,11 +172,15 @@ class LLM_SFT:
     @torch.no_grad()
     def llm_forward(self, inputs_embeds: torch.Tensor, attention_mask=None, past_key_values: Optional[KVCache] = None,
                     use_cache: bool = False, output_attentions: bool = False, output_hidden_states: bool = False, position_ids=None,
-                    cache_position=None):
+                    cache_position=None, *, chunk_lengths: Optional[Sequence[int]] = None):
         """CustomLlamaModel.llm_forward (llm.py:150-227): inputs_embeds [B, n, hidden] at positions len .. len + n - 1 of
         `past_key_values` (a KVCache; use_cache=True with none creates one of B rows x max_position_embeddings), causal.  Returns an
         object with .last_hidden_state [B, n, hidden], .past_key_values (None unless use_cache) and .hidden_states (None, or the
-        n_layers + 1 tensors of output_hidden_states).  A sequence's rows do not depend on the batch it is in."""
+        n_layers + 1 tensors of output_hidden_states).  A sequence's rows do not depend on the batch it is in.
+
+        chunk_lengths (B ints, 0 .. n; needs a cache): row b feeds only its first chunk_lengths[b] positions, at the row's own position
+        in the cache (qa_lm_forward_ragged).  The input behind a row's count is never read and the outputs there are exactly 0; a count
+        of 0 leaves the row idle.  None is the plain call; on a cache whose rows differ in length it feeds n positions to every row."""
         self._ready()
         _unsupported(attention_mask=(attention_mask, None), position_ids=(position_ids, None), cache_position=(cache_position, None),
                      output_attentions=(bool(output_attentions), False))
@@ -176,10 +195,20 @@ class LLM_SFT:
             raise _lib.QuarkAudioError(-1, "llm_forward: past_key_values belongs to another model")
         if use_cache and cache is None:
             cache = KVCache(self, B, MAX_POSITION_EMBEDDINGS)  # llm.py:170-171
-        out = torch.empty_like(x)
-        hs = torch.empty((self.num_layers + 1, B, n, d), dtype=torch.float32, device=self.device) if output_hidden_states else None
-        _lib.check(self._lib.qa_lm_forward(self._handle, cache._ptr() if cache is not None else None, x.data_ptr(), B, n, out.data_ptr(),
-                                           hs.data_ptr() if hs is not None else None, self._stream()))
+        # chunk_lengths: zeros, so that a call whose counts are all 0 (which launches nothing) returns what every idle row returns
+        new = torch.empty if chunk_lengths is None else torch.zeros
+        out = new(x.shape, dtype=torch.float32, device=self.device)
+        hs = new((self.num_layers + 1, B, n, d), dtype=torch.float32, device=self.device) if output_hidden_states else None
+        hs_ptr = hs.data_ptr() if hs is not None else None
+        if chunk_lengths is not None:
+            lens = [int(v) for v in (chunk_lengths.tolist() if torch.is_tensor(chunk_lengths) else chunk_lengths)]
+            if len(lens) != B:
+                raise _lib.QuarkAudioError(-1, f"llm_forward: chunk_lengths has {len(lens)} entries for {B} sequences")
+            _lib.check(self._lib.qa_lm_forward_ragged(self._handle, cache._ptr() if cache is not None else None, x.data_ptr(), B, n,
+                                                      (C.c_int64 * B)(*lens), out.data_ptr(), hs_ptr, self._stream()))
+        else:
+            _lib.check(self._lib.qa_lm_forward(self._handle, cache._ptr() if cache is not None else None, x.data_ptr(), B, n, out.data_ptr(),
+                                               hs_ptr, self._stream()))
         return SimpleNamespace(last_hidden_state=out, past_key_values=cache if use_cache else None,
                                hidden_states=tuple(hs.unbind(0)) if hs is not None else None, attentions=None)
 
@@ -457,10 +486,10 @@ class CustomLlamaModel:
         return gids, sids
 
     def llm_forward(self, inputs_embeds, attention_mask=None, past_key_values=None, use_cache=False, output_attentions=False,
-                    output_hidden_states=False, position_ids=None, cache_position=None):
+                    output_hidden_states=False, position_ids=None, cache_position=None, *, chunk_lengths=None):
         """llm.py:150-227 over a KVCache: see LLM_SFT.llm_forward (the same code on the same handle)."""
         return self._lm.llm_forward(inputs_embeds, attention_mask, past_key_values, use_cache, output_attentions, output_hidden_states,
-                                    position_ids, cache_position)
+                                    position_ids, cache_position, chunk_lengths=chunk_lengths)
 
     def test_generate(self, inputs_embeds, top_k: int = 50, top_p: float = 0.95, temperature: float = 0.8):
         """llm.py:229-250"""
