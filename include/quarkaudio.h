@@ -680,6 +680,31 @@ int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_en
                 const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
                 float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream);
 
+/* qa_lm_score for a batch whose rows differ in length.  Layouts are qa_lm_score's with the maxima as the strides:
+ * enroll_feats [B, n_enroll_max, feats_dim], mix_feats [B, n_mix_max, feats_dim], semantic_ids [B, semantic_length_max]; global_length is
+ * common to the batch.  Three optional HOST int64 vectors [B], read during the call only (they may be freed on return):
+ *   n_enroll[b]   in 1 .. n_enroll_max (only with an enrollment)
+ *   n_mix[b]      in 1 .. n_mix_max
+ *   n_semantic[b] in 0 .. semantic_length_max
+ * NULL means "every row at full width".  Row b is scored as qa_lm_score scores that sequence alone on enroll_feats[b, :n_enroll[b]],
+ * mix_feats[b, :n_mix[b]] and semantic_ids[b, :n_semantic[b]]: a prompt of Lp_b = 1 + (1 + n_enroll[b]) + 1 + n_mix[b] positions
+ * (2 + n_mix[b] without an enrollment), Lt_b = global_length + n_semantic[b] + 2 target rows with the eos target right behind the row's
+ * own last semantic id, positions 0 .. Lp_b + Lt_b - 1.  Feature frames and ids at or behind a row's lengths never enter its
+ * arithmetic and are not range-checked (check ids[b, :n_semantic[b]] with qa_codes_check).
+ * Outputs: loss_per_seq[b] the mean KL over the row's own Lt_b rows, correct_per_seq[b] its correct rows; the scalars pool the rows:
+ * loss = (sum over all target rows of kl) / sum_b Lt_b, acc = sum_b correct_b / sum_b Lt_b.  No atomics: a row's values do not depend on
+ * its neighbours, its group of 64, the padded width, QA_LM_SCORE_ROWS or taps.  The tap "logits.forced" is then PACKED:
+ * [sum_b Lt_b, V], sequences in order, each with its own Lt_b rows.
+ * Every check runs before the first launch, names the row and its value, and leaves the handle usable: a length out of range, n_enroll
+ * without enroll_feats, a row above 4096 positions, a NULL pointer where data is needed.  Refused under a stream capture whenever a
+ * vector is given (a replayed graph would repeat the captured lengths).  With every given vector uniform at full width the call IS
+ * qa_lm_score: the same launches, the same bits.  Sequences go through in groups of 64, each laid out at its own longest row; inside a
+ * group the body still computes the padded layout (dead attention blocks exit at once), the head and the loss run on packed rows. */
+int qa_lm_score_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
+                       int64_t n_mix_max, const int64_t* n_mix, int64_t B, const int64_t* global_ids, int32_t global_length,
+                       const int64_t* semantic_ids, int32_t semantic_length_max, const int64_t* n_semantic, double label_smoothing,
+                       float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream);
+
 /* Test hook, as qa_hcodec_enable_taps: while on, qa_lm_generate / qa_lm_generate_sampled record the logits of the active vocabulary
  * slice at every decode step (what the head computes before the pick / sampler), in storage of their own: turning taps on changes no
  * token.  Not supported under a caller's stream capture (the call is refused). */
@@ -758,6 +783,14 @@ int qa_lm_embed(qa_lm* lm, const int64_t* ids, int64_t n, float* out, void* stre
 int qa_lm_head(qa_lm* lm, const float* hidden, int64_t rows, int32_t lo, int32_t width, float* logits, void* stream);
 int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
                  float* out, void* stream);
+/* qa_lm_prompt with per-row lengths (n_enroll / n_mix: HOST int64 [B] as in qa_lm_score_ragged, NULL = full width): out
+ * [B, Lp_max, hidden] with Lp_max = 1 + (enroll_feats ? 1 + n_enroll_max : 0) + 1 + n_mix_max; row b is left-aligned over its own
+ * Lp_b = 1 + (1 + n_enroll[b]) + 1 + n_mix[b] positions (2 + n_mix[b] without an enrollment) - what qa_lm_prompt gives the row alone on
+ * its trimmed features, bit for bit - with exact zeros behind.  Padding frames are never copied.  The result feeds
+ * qa_lm_forward_ragged with n[b] = Lp_b.  Checks and the stream-capture refusal as in qa_lm_score_ragged; uniform vectors at full width
+ * are qa_lm_prompt. */
+int qa_lm_prompt_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
+                        int64_t n_mix_max, const int64_t* n_mix, int64_t B, float* out, void* stream);
 
 /* Kernel-level entry point of the sampler (parity / distribution tests): CustomLlamaModel.sample_logits (llm.py:253-288) on
  * logits [B, width] (row stride ld, device).  out_index int64 [B] (device).  do_sample = 0: arg-max (first maximum).

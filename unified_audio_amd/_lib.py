@@ -236,6 +236,11 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_void_p]),
     "qa_lm_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
                               C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_score_ragged": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                     C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int64),
+                                     C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_prompt_ragged": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                      C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p]),
     "qa_lm_enable_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "qa_lm_tap": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "qa_sample_logits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_int32,

@@ -172,6 +172,20 @@ int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, con
 int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
                          hipStream_t s);
 int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
+// scoring with per-row lengths.  ne_r / nm_r / T_r / lp_r / off_r: device int [B] of one group (launch_lm_row_ints):
+// the row's enrollment frames, mixture frames, semantic ids, prompt positions and packed target-row offset
+// x [B, n, d] <- prompt + input embeddings left-aligned, zeros behind; tgt (packed) <- the targets.  table == nullptr: the prompt alone
+int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,
+                             const float* mix_emb, int Ne, int Nm, const float* table, const long long* gids, int G, const long long* sids,
+                             int T_max, int V, int goff, int soff, long long* tgt, const int* ne_r, const int* nm_r, const int* T_r,
+                             const int* off_r, int B, int d, hipStream_t s);
+// y (packed [sum Lt_b, d]) <- x[b, lp[b] .. lp[b] + Lt_b - 1, :], Lt_b = G + T[b] + 2 <= Lt_max
+int launch_lm_score_gather(float* y, const float* x, int B, int n, int d, int G, int Lt_max, const int* lp_r, const int* T_r, const int* off_r,
+                           hipStream_t s);
+int launch_lm_seq_reduce_rows(const float* row_kl, const int* row_ok, int B, int G, const int* T_r, const int* off_r, double* seq_sum,
+                              float* loss_seq, long long* correct_seq, hipStream_t s);
+int launch_lm_batch_reduce_rows(const double* seq_sum, const long long* correct_seq, int B, long long total, float* loss, float* acc,
+                                hipStream_t s);
 // one wave of independent row moves of a KV cache (qa_lm_cache_select; KvMoves: lm_session_rows.h), passed by value
 int launch_kv_row_moves(float* kc, float* vc, float* spare, int n_layers, int max_batch, int max_len, int d, const KvMoves& mv, hipStream_t s);
 

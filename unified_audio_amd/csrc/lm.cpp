@@ -11,12 +11,14 @@
 //
 // qa_lm_score is the other entry point, LLM_SFT.forward (llm_sft.py:37-90): the whole teacher-forced sequence through the same body
 // (every layer), output_head over the full vocabulary on the target rows, and the label-smoothed KL + accuracy (llm.py:87-104).
+// qa_lm_score_ragged / qa_lm_prompt_ragged are the same with per-row lengths (host logic in lm_score_rows.h).
 #include <memory>
 
 #include <cstdlib>
 
 #include "host_util.h"
 #include "lm_decode.h"
+#include "lm_score_rows.h"
 
 using namespace qa;
 
@@ -711,12 +713,17 @@ struct ScoreArgs {
     float* loss_seq;
     long long* correct_seq;
     float *loss, *acc;
+    // per-row lengths (qa_lm_score_ragged): p.Ne / p.Nm / T are then the tensors' widths.  nullptr: rectangular
+    const ScoreRows* rows = nullptr;
 };
+
+int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap);
 
 int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, V = vocab_of(sp);
     const Prompt& p = a.p;
+    if (a.rows) return score_rows_graph(lm, c, a, tap);
     const int Lp = prompt_len(p);
     const int Lt = a.G + a.T + 2 - (p.cond_mode ? 1 : 0), n = Lp + Lt;
     QA_REQUIRE(n <= LM_MAX_POS, "qa_lm_score: %d positions (prompt %d + targets %d) exceed max_position_embeddings %d", n, Lp, Lt, LM_MAX_POS);
@@ -765,6 +772,78 @@ int score_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     return launch_lm_batch_reduce(seq_sum, a.correct_seq, a.B, Lt, a.loss, a.acc, c.stream);
 }
 
+// The device ints of one group of a ragged score / prompt call, SR_COUNT arrays of `gb` entries each behind one another
+enum { SR_NE = 0, SR_NM, SR_T, SR_OFF, SR_LP, SR_L, SR_ZERO, SR_COUNT };
+
+int write_score_ints(int* dst, const ScoreRows& R, const ScoreGroup& g, hipStream_t s) {
+    std::vector<int> vals((size_t)SR_COUNT * g.gb, 0);
+    for (int i = 0; i < g.gb; ++i) {
+        const size_t b = (size_t)g.b0 + i;
+        vals[(size_t)SR_NE * g.gb + i] = R.ne[b];
+        vals[(size_t)SR_NM * g.gb + i] = R.nm[b];
+        vals[(size_t)SR_T * g.gb + i] = R.T[b];
+        vals[(size_t)SR_OFF * g.gb + i] = (int)(R.off[b] - g.row0);  // inside the group: at most gb * LM_MAX_POS
+        vals[(size_t)SR_LP * g.gb + i] = R.Lp[b];
+        vals[(size_t)SR_L * g.gb + i] = R.L[b];
+    }
+    return launch_lm_row_ints(dst, vals.data(), (long long)vals.size(), s);
+}
+
+// score_graph with per-row lengths.  The same structure - groups of at most LM_MAX_ROWS sequences in index order,
+// adapters, assembly, body, final norm, head in QA_LM_SCORE_ROWS chunks, row loss, fixed-order reduces - with these differences: a group is
+// laid out at its OWN longest row; one assembly pass writes prompt, input embeddings and the packed targets; the body runs with the rows'
+// counts (a query block wholly behind a row's length exits at once, K / V behind it are not written); and the tail - norm, head, row loss -
+// runs over the PACKED target rows alone, so no padded row reaches the full-vocabulary head.
+int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
+    const qa_lm_spec& sp = lm->spec;
+    const int d = sp.hidden, V = vocab_of(sp), F = sp.feats_dim;
+    const Prompt& p = a.p;
+    const ScoreRows& R = *a.rows;
+    const int GB = std::min(a.B, LM_MAX_ROWS);
+    const int64_t prow = R.body_rows_max, trow = R.packed_rows_max;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(knob(K_LM_SCORE_ROWS), trow));
+    LMBuffers b{};
+    // as score_graph: b.att holds the packed target rows, b.hn their normalised form (a group's packed rows are fewer than its body rows)
+    alloc_body(c.arena, b, prow, d, sp.intermediate);
+    b.kc = c.arena.alloc<float>(prow * d);
+    b.vc = c.arena.alloc<float>(prow * d);
+    float* emix = c.arena.alloc<float>((size_t)GB * p.Nm * d);
+    float* eenr = p.enroll ? c.arena.alloc<float>((size_t)GB * p.Ne * d) : nullptr;
+    long long* tgt = c.arena.alloc<long long>(trow);
+    float* row_kl = c.arena.alloc<float>(trow);
+    int* row_ok = c.arena.alloc<int>(trow);
+    float* logits = c.arena.alloc<float>((size_t)chunk * V);
+    double* seq_sum = c.arena.alloc<double>(a.B);
+    int* ints = c.arena.alloc<int>((size_t)SR_COUNT * GB);
+    if (c.dry) return QA_OK;  // real-pass-only remainder: ints above is the function's last arena allocation
+    const float conf = (float)(1.0 - a.eps), smooth = (float)(a.eps / (V - 1));
+    for (const ScoreGroup& g : R.groups) {
+        const int b0 = g.b0, gb = g.gb, n = g.n;
+        const int *ne_r = ints + SR_NE * gb, *nm_r = ints + SR_NM * gb, *T_r = ints + SR_T * gb, *off_r = ints + SR_OFF * gb,
+                  *lp_r = ints + SR_LP * gb, *L_r = ints + SR_L * gb, *zero_r = ints + SR_ZERO * gb;
+        QA_TRY(write_score_ints(ints, R, g, c.stream));
+        // the adapters run over the padding frames too: a GEMM row depends on its own input row alone, and those outputs are never copied
+        QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
+        if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
+        QA_TRY(launch_lm_score_assemble(b.x, n, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, p.Ne,
+                                        p.Nm, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T, a.T, V, 3,
+                                        3 + sp.global_size, tgt, ne_r, nm_r, T_r, off_r, gb, d, c.stream));
+        QA_TRY(lm_body(lm, c, b, gb, n, 0, n, false, true, nullptr, zero_r, L_r));
+        QA_TRY(launch_lm_score_gather(b.att, b.x, gb, n, d, a.G, g.Lt_max, lp_r, T_r, off_r, c.stream));
+        const int64_t rows = g.rows;
+        QA_TRY(launch_rmsnorm(b.att, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
+        for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+            const int64_t nr = std::min(chunk, rows - r0);
+            QA_TRY(linear_op(c, b.hn + (size_t)r0 * d, nr, lm->head, logits));
+            QA_TRY(launch_lm_row_loss(logits, V, V, nr, tgt + r0, conf, smooth, row_kl + r0, row_ok + r0, c.stream));
+            if (tap)
+                QA_HIP(hipMemcpyAsync(tap + ((size_t)g.row0 + r0) * V, logits, sizeof(float) * nr * V, hipMemcpyDeviceToDevice, c.stream));
+        }
+        QA_TRY(launch_lm_seq_reduce_rows(row_kl, row_ok, gb, a.G, T_r, off_r, seq_sum + b0, a.loss_seq + b0, a.correct_seq + b0, c.stream));
+    }
+    return launch_lm_batch_reduce_rows(seq_sum, a.correct_seq, a.B, R.total_rows, a.loss, a.acc, c.stream);
+}
+
 // grow the workspace or the tap buffer of generate: earlier calls may still be running out of the old buffer, and captured steps point
 // into it (they are keyed by its address and re-captured)
 int grow_step_buffer(qa_lm* lm, Workspace& w, size_t bytes) {
@@ -788,6 +867,27 @@ int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
 int refuse_capture(const char* fn, hipStream_t s) {
     QA_REQUIRE(!stream_capturing(s),
                "%s: refused under a stream capture - the cache length is host state, a replayed graph would repeat the captured positions", fn);
+    return QA_OK;
+}
+
+// The lengths of a ragged score / prompt call are read on the host during the call: a replayed graph would repeat the captured lengths.
+int refuse_score_capture(const char* fn, hipStream_t s) {
+    QA_REQUIRE(!stream_capturing(s), "%s: refused under a stream capture - the rows' lengths are host data read during the call, a replayed "
+               "graph would repeat the captured lengths", fn);
+    return QA_OK;
+}
+
+// The refusals of the length vectors of qa_lm_score_ragged / qa_lm_prompt_ragged as the library's messages (lm_score_rows.h)
+int score_rows_refusal(const char* fn, ScoreRowsFault f, const ScoreRowsShape& s, int64_t row, int64_t value) {
+    QA_REQUIRE(f != SCR_ENROLL_WITHOUT, "%s: n_enroll given (n_enroll[0] = %lld) without an enrollment (enroll_feats is NULL)", fn, (long long)value);
+    QA_REQUIRE(f != SCR_ENROLL_RANGE, "%s: n_enroll[%lld] = %lld is outside 1 .. n_enroll_max = %lld", fn, (long long)row, (long long)value,
+               (long long)s.ne_max);
+    QA_REQUIRE(f != SCR_MIX_RANGE, "%s: n_mix[%lld] = %lld is outside 1 .. n_mix_max = %lld", fn, (long long)row, (long long)value,
+               (long long)s.nm_max);
+    QA_REQUIRE(f != SCR_SEMANTIC_RANGE, "%s: n_semantic[%lld] = %lld is outside 0 .. semantic_length_max = %lld", fn, (long long)row,
+               (long long)value, (long long)s.T_max);
+    QA_REQUIRE(f != SCR_TOO_LONG, "%s: row %lld holds %lld positions (prompt + targets), which exceed max_position_embeddings %d", fn,
+               (long long)row, (long long)value, s.max_pos);
     return QA_OK;
 }
 
@@ -1163,6 +1263,48 @@ int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_e
     });
 }
 
+int qa_lm_prompt_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
+                        int64_t n_mix_max, const int64_t* n_mix, int64_t B, float* out, void* stream) {
+    const char* fn = "qa_lm_prompt_ragged";
+    if (!n_enroll && !n_mix) return qa_lm_prompt(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, out, stream);
+    if (!lm || !mix_feats || !out) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_score_capture(fn, s));
+    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, task);
+    QA_REQUIRE(B >= 1 && n_mix_max >= 1 && n_mix_max <= LM_MAX_POS && B <= (1 << 16), "%s: bad shape", fn);
+    QA_REQUIRE(!enroll_feats || (n_enroll_max >= 1 && n_enroll_max <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
+    ScoreRowsShape shape;
+    shape.B = B; shape.has_enroll = enroll_feats != nullptr; shape.ne_max = enroll_feats ? n_enroll_max : 0; shape.nm_max = n_mix_max;
+    shape.targets = false; shape.group_rows = LM_MAX_ROWS; shape.max_pos = 2 * LM_MAX_POS + 3;  // as qa_lm_prompt: the frame counts bound it
+    ScoreRows R;
+    int64_t row = 0, value = 0;
+    QA_TRY(score_rows_refusal(fn, plan_score_rows(n_enroll, n_mix, nullptr, shape, &R, &row, &value), shape, row, value));
+    if (R.uniform) return qa_lm_prompt(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, out, stream);
+    const Prompt p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix_max);
+    const int d = lm->spec.hidden, Fd = lm->spec.feats_dim;
+    Ctx& c = lm->sess_ctx;
+    return run_session(lm, s, [&]() -> int {
+        const int GB = (int)std::min<int64_t>(B, LM_MAX_ROWS);
+        float* emix = c.arena.alloc<float>((size_t)GB * p.Nm * d);
+        float* eenr = p.enroll ? c.arena.alloc<float>((size_t)GB * p.Ne * d) : nullptr;
+        int* ints = c.arena.alloc<int>((size_t)SR_COUNT * GB);
+        if (c.dry) return QA_OK;  // real-pass-only remainder
+        for (const ScoreGroup& g : R.groups) {  // groups bound the adapters' scratch; a row's prompt does not know its group
+            const int b0 = g.b0, gb = g.gb;
+            QA_TRY(write_score_ints(ints, R, g, c.stream));
+            QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * Fd, (int64_t)gb * p.Nm, lm->adapter, emix));
+            if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * Fd, (int64_t)gb * p.Ne, lm->adapter, eenr));
+            QA_TRY(launch_lm_score_assemble(out + (size_t)b0 * R.Lp_max * d, R.Lp_max, lm->task_emb + (size_t)p.task * d,
+                                            p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, p.Ne, p.Nm, nullptr, nullptr, 0, nullptr,
+                                            0, 0, 0, 0, nullptr, ints + SR_NE * gb, ints + SR_NM * gb, nullptr, nullptr, gb, d, c.stream));
+        }
+        return QA_OK;
+    });
+}
+
 int qa_lm_create(qa_lm** out, const qa_lm_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
     if (!out || !spec || !tensors) {
         set_error("qa_lm_create: null argument");
@@ -1282,8 +1424,8 @@ int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_f
 static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
                          const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length,
                          double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream,
-                         bool cond_mode, const float* cond, int64_t Tc) {
-    const char* fn = cond_mode ? "qa_lm_score_cond" : "qa_lm_score";
+                         bool cond_mode, const float* cond, int64_t Tc, const ScoreRows* rows = nullptr) {
+    const char* fn = cond_mode ? "qa_lm_score_cond" : rows ? "qa_lm_score_ragged" : "qa_lm_score";
     if (!lm || (!cond_mode && !mix_feats) || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
         (semantic_length > 0 && !semantic_ids)) {
         set_error("%s: null argument", fn);
@@ -1302,12 +1444,15 @@ static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int
     const Prompt p = cond_mode ? cond_prompt(cond, Tc) : speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
     ScoreArgs a{p, (int)B, global_length, semantic_length, reinterpret_cast<const long long*>(global_ids),
                 reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq, reinterpret_cast<long long*>(correct_per_seq), loss, acc};
+    a.rows = rows;
     const int Lt = global_length + semantic_length + 2 - (cond_mode ? 1 : 0);
+    // logits.forced: [B, Lt, V], or packed [sum Lt_b, V] after a call with per-row lengths
+    const size_t tap_rows = rows ? (size_t)rows->total_rows : (size_t)B * Lt;
     lm->score_tap_n = -1;
     float* tap = nullptr;
     if (lm->taps) {
         QA_REQUIRE(!capturing, "qa_lm_score: taps (a test hook) are not supported under a stream capture");
-        const size_t bytes = sizeof(float) * (size_t)B * Lt * vocab_of(lm->spec);
+        const size_t bytes = sizeof(float) * tap_rows * vocab_of(lm->spec);
         if (bytes > lm->score_tap.cap) QA_HIP(hipDeviceSynchronize());  // earlier calls may still be writing the old buffer
         QA_TRY(lm->score_tap.ensure(bytes));
         tap = reinterpret_cast<float*>(lm->score_tap.ptr);
@@ -1323,8 +1468,41 @@ static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int
         return QA_OK;
     }));
     QA_TRY(graph());
-    if (tap) lm->score_tap_n = (int64_t)B * Lt * vocab_of(lm->spec);
+    if (tap) lm->score_tap_n = (int64_t)tap_rows * vocab_of(lm->spec);
     return QA_OK;
+}
+
+int qa_lm_score_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
+                       int64_t n_mix_max, const int64_t* n_mix, int64_t B, const int64_t* global_ids, int32_t global_length,
+                       const int64_t* semantic_ids, int32_t semantic_length_max, const int64_t* n_semantic, double label_smoothing,
+                       float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
+    const char* fn = "qa_lm_score_ragged";
+    auto rectangular = [&] {
+        return qa_lm_score(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, global_ids, global_length, semantic_ids,
+                           semantic_length_max, label_smoothing, loss_per_seq, correct_per_seq, loss, acc, stream);
+    };
+    if (!n_enroll && !n_mix && !n_semantic) return rectangular();  // every row at full width
+    if (!lm || !mix_feats || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
+        (semantic_length_max > 0 && !semantic_ids)) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    // every check comes before the first launch: a refused call has launched nothing and leaves the handle as it was
+    QA_TRY(refuse_score_capture(fn, static_cast<hipStream_t>(stream)));
+    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, task);
+    QA_REQUIRE(B > 0 && B <= (1 << 24) && n_mix_max > 0 && n_mix_max <= LM_MAX_POS && global_length >= 0 && global_length <= LM_MAX_POS &&
+                   semantic_length_max >= 0 && semantic_length_max <= LM_MAX_POS, "%s: bad shape", fn);
+    QA_REQUIRE(!enroll_feats || (n_enroll_max > 0 && n_enroll_max <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
+    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, label_smoothing);
+    ScoreRowsShape shape;
+    shape.B = B; shape.has_enroll = enroll_feats != nullptr; shape.ne_max = enroll_feats ? n_enroll_max : 0; shape.nm_max = n_mix_max;
+    shape.T_max = semantic_length_max; shape.G = global_length; shape.group_rows = LM_MAX_ROWS; shape.max_pos = LM_MAX_POS;
+    ScoreRows R;
+    int64_t row = 0, value = 0;
+    QA_TRY(score_rows_refusal(fn, plan_score_rows(n_enroll, n_mix, n_semantic, shape, &R, &row, &value), shape, row, value));
+    if (R.uniform) return rectangular();  // the rectangular call: its launches, its bits
+    return lm_score_impl(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, global_ids, global_length, semantic_ids,
+                         semantic_length_max, label_smoothing, loss_per_seq, correct_per_seq, loss, acc, stream, false, nullptr, 0, &R);
 }
 
 int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,

@@ -472,6 +472,170 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Teacher-forced scoring with per-row lengths (qa_lm_score_ragged / qa_lm_prompt_ragged).  Row b of a group holds
+// ne[b] of the Ne enrollment frames, nm[b] of the Nm mixture frames and T[b] of the T_max semantic ids (device int [B] each, written by
+// launch_lm_row_ints).  The rectangular kernels above keep their code: these are launched by the ragged entry points alone.
+//
+// One assembly pass: x [B, n, d] row b <- [task, (enroll_sos, enroll_emb[b, :ne])?, mix_sos, mix_emb[b, :nm], codec_embedding(input_ids_b)]
+// left-aligned over L_b = Lp_b + Lt_b positions, exact zeros behind; target_ids_b -> tgt[off[b] ..] (PACKED: Lt_b = G + T[b] + 2 entries).
+// The eos target sits right behind the row's own last semantic id.  Frames and ids at or behind a row's counts are never read.
+// table == nullptr: a prompt-only pass (no target positions, gids / sids / tgt unused).
+__global__ __launch_bounds__(256) void lm_score_assemble_kernel(float* __restrict__ x, int n, const float* __restrict__ task_vec,
+                                                                const float* __restrict__ enroll_sos, const float* __restrict__ enroll_emb,
+                                                                const float* __restrict__ mix_sos, const float* __restrict__ mix_emb, int Ne,
+                                                                int Nm, const float* __restrict__ table, const long long* __restrict__ gids,
+                                                                int G, const long long* __restrict__ sids, int T_max, int V, int goff, int soff,
+                                                                long long* __restrict__ tgt, const int* __restrict__ ne_r,
+                                                                const int* __restrict__ nm_r, const int* __restrict__ T_r,
+                                                                const int* __restrict__ off_r, int B, int d) {
+    const int d4 = d >> 2;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * n * d4) return;
+    const int c = (int)(gid % d4) * 4;
+    const int pos = (int)((gid / d4) % n);
+    const int b = (int)(gid / ((long long)d4 * n));
+    const int ne = enroll_emb ? ne_r[b] : 0, nm = nm_r[b];
+    const int Lp = 1 + (enroll_emb ? 1 + ne : 0) + 1 + nm;
+    const float* src = nullptr;
+    if (pos < Lp) {
+        int p = pos;
+        if (p == 0) {
+            src = task_vec;
+        } else {
+            p -= 1;
+            if (enroll_emb && p == 0) {
+                src = enroll_sos;
+            } else {
+                if (enroll_emb) p -= 1;
+                if (enroll_emb && p < ne) {
+                    src = enroll_emb + ((long long)b * Ne + p) * d;
+                } else {
+                    if (enroll_emb) p -= ne;
+                    src = (p == 0) ? mix_sos : mix_emb + ((long long)b * Nm + (p - 1)) * d;  // p - 1 < nm: pos < Lp
+                }
+            }
+        }
+    } else if (table) {
+        const int T = T_r[b], t = pos - Lp;
+        if (t < G + T + 2) {
+            long long in_id, tg;
+            if (t == 0) in_id = 0;
+            else if (t <= G) in_id = gids[(long long)b * G + t - 1] + goff;
+            else if (t == G + 1) in_id = 1;
+            else in_id = sids[(long long)b * T_max + t - G - 2] + soff;
+            if (t < G) tg = gids[(long long)b * G + t] + goff;
+            else if (t == G) tg = 1;
+            else if (t < G + T + 1) tg = sids[(long long)b * T_max + t - G - 1] + soff;
+            else tg = 2;
+            src = table + clamp_id(in_id, V) * d;
+            if (c == 0) tgt[off_r[b] + t] = clamp_id(tg, V);
+        }
+    }
+    *reinterpret_cast<float4*>(x + ((long long)b * n + pos) * d + c) =
+        src ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,
+                             const float* mix_emb, int Ne, int Nm, const float* table, const long long* gids, int G, const long long* sids,
+                             int T_max, int V, int goff, int soff, long long* tgt, const int* ne_r, const int* nm_r, const int* T_r,
+                             const int* off_r, int B, int d, hipStream_t s) {
+    QA_REQUIRE(d % 4 == 0 && n >= 1 && B >= 1 && nm_r && (!enroll_emb || ne_r) && (!table || (tgt && T_r && off_r)), "lm_score_assemble: bad launch");
+    const long long total = (long long)B * n * (d / 4);
+    hipLaunchKernelGGL(lm_score_assemble_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, n, task_vec, enroll_sos, enroll_emb,
+                       mix_sos, mix_emb, Ne, Nm, table, gids, G, sids, T_max, V, goff, soff, tgt, ne_r, nm_r, T_r, off_r, B, d);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// The packed tail: y [sum Lt_b, d] <- each row's last Lt_b = G + T[b] + 2 live positions x[b, lp[b] + t, :], sequences in order.  Grid: x
+// covers Lt_max rows of one sequence, y = sequence.
+__global__ __launch_bounds__(256) void lm_score_gather_kernel(float4* __restrict__ y, const float4* __restrict__ x, int n, int d4, int G,
+                                                              int Lt_max, const int* __restrict__ lp_r, const int* __restrict__ T_r,
+                                                              const int* __restrict__ off_r) {
+    const int b = blockIdx.y;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)Lt_max * d4) return;
+    const int t = (int)(gid / d4), c = (int)(gid % d4);
+    if (t >= G + T_r[b] + 2) return;
+    y[((long long)off_r[b] + t) * d4 + c] = x[((long long)b * n + lp_r[b] + t) * d4 + c];
+}
+
+int launch_lm_score_gather(float* y, const float* x, int B, int n, int d, int G, int Lt_max, const int* lp_r, const int* T_r, const int* off_r,
+                           hipStream_t s) {
+    QA_REQUIRE(d % 4 == 0 && B >= 1 && B <= 65535 && Lt_max >= 1 && lp_r && T_r && off_r, "lm_score_gather: bad launch");
+    const long long total = (long long)Lt_max * (d / 4);
+    hipLaunchKernelGGL(lm_score_gather_kernel, dim3((unsigned)ceil_div(total, 256), (unsigned)B), dim3(256), 0, s, reinterpret_cast<float4*>(y),
+                       reinterpret_cast<const float4*>(x), n, d / 4, G, Lt_max, lp_r, T_r, off_r);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// lm_seq_reduce_kernel over packed rows: sequence b owns rows off[b] .. off[b] + Lt_b - 1, Lt_b = G + T[b] + 2.  The same thread
+// ownership and the same fixed LDS tree in double, so a sequence's values equal the rectangular kernel's on its own rows.
+__global__ __launch_bounds__(256) void lm_seq_reduce_rows_kernel(const float* __restrict__ row_kl, const int* __restrict__ row_ok, int G,
+                                                                 const int* __restrict__ T_r, const int* __restrict__ off_r,
+                                                                 double* __restrict__ seq_sum, float* __restrict__ loss_seq,
+                                                                 long long* __restrict__ correct_seq) {
+    __shared__ double s_kl[256];
+    __shared__ long long s_ok[256];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int Lt = G + T_r[b] + 2;
+    const long long base = off_r[b];
+    double kl = 0.0;
+    long long ok = 0;
+    for (int t = tid; t < Lt; t += 256) {
+        kl += (double)row_kl[base + t];
+        ok += row_ok[base + t];
+    }
+    s_kl[tid] = kl;
+    s_ok[tid] = ok;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) {
+            s_kl[tid] += s_kl[tid + h];
+            s_ok[tid] += s_ok[tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        seq_sum[b] = s_kl[0];
+        loss_seq[b] = (float)(s_kl[0] / Lt);
+        correct_seq[b] = s_ok[0];
+    }
+}
+
+int launch_lm_seq_reduce_rows(const float* row_kl, const int* row_ok, int B, int G, const int* T_r, const int* off_r, double* seq_sum,
+                              float* loss_seq, long long* correct_seq, hipStream_t s) {
+    QA_REQUIRE(B >= 1 && T_r && off_r, "lm_seq_reduce_rows: bad launch");
+    hipLaunchKernelGGL(lm_seq_reduce_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, row_kl, row_ok, G, T_r, off_r, seq_sum, loss_seq,
+                       correct_seq);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// The batch scalars over rows of different lengths: the pooled mean over all `total` = sum Lt_b target rows, sequences in index order.
+__global__ void lm_batch_reduce_rows_kernel(const double* __restrict__ seq_sum, const long long* __restrict__ correct_seq, int B,
+                                            long long total, float* __restrict__ loss, float* __restrict__ acc) {
+    double kl = 0.0;
+    long long ok = 0;
+    for (int b = 0; b < B; ++b) {
+        kl += seq_sum[b];
+        ok += correct_seq[b];
+    }
+    const double n = (double)total;
+    *loss = (float)(kl / n);
+    *acc = (float)((double)ok / n);
+}
+
+int launch_lm_batch_reduce_rows(const double* seq_sum, const long long* correct_seq, int B, long long total, float* loss, float* acc,
+                                hipStream_t s) {
+    QA_REQUIRE(B >= 1 && total >= 1, "lm_batch_reduce_rows: bad launch");
+    hipLaunchKernelGGL(lm_batch_reduce_rows_kernel, dim3(1), dim3(1), 0, s, seq_sum, correct_seq, B, total, loss, acc);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // qa_lm_cache_select: one WAVE of row moves of a KV cache [layer][max_batch][max_len][d] (K and V).  Move i copies the first mv.len[i]
 // positions of its row (the length of the row it carries rides with the move: stale positions behind it are never copied, and rows of
 // different lengths share a launch).  Grid: x covers the longest row of the wave, y = move, z = layer * 2 + {K, V}.

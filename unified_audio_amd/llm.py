@@ -250,9 +250,26 @@ class LLM_SFT:
             _lib.check(self._lib.qa_lm_head(self._handle, h.data_ptr(), rows, int(lo), width, out.data_ptr(), self._stream()))
         return out
 
+    @staticmethod
+    def _lengths(name: str, lengths, B: int):
+        """A per-row length argument (None, or B ints as a list / tensor) as (list or None, HOST int64 array or None)."""
+        if lengths is None:
+            return None, None
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B:
+            raise _lib.QuarkAudioError(-1, f"{name} has {len(lens)} entries for a batch of {B}")
+        return lens, (C.c_int64 * max(B, 1))(*lens)  # host vector: the library reads it during the call
+
     @torch.no_grad()
-    def build_prompt(self, task_name: str, enroll_feats: Optional[torch.Tensor], mix_feats: torch.Tensor) -> torch.Tensor:
-        """llm_sft.py:110-128: [task, (enroll_sos, adapter(enroll_feats)), mix_sos, adapter(mix_feats)] -> [B, L, hidden]."""
+    def build_prompt(self, task_name: str, enroll_feats: Optional[torch.Tensor], mix_feats: torch.Tensor, *, enroll_lengths=None,
+                     mix_lengths=None) -> torch.Tensor:
+        """llm_sft.py:110-128: [task, (enroll_sos, adapter(enroll_feats)), mix_sos, adapter(mix_feats)] -> [B, L, hidden].
+
+        enroll_lengths / mix_lengths (keyword only; B frame counts each, None: every row at full width): row b uses
+        enroll_feats[b, :enroll_lengths[b]] and mix_feats[b, :mix_lengths[b]].  The result is [B, Lp_max, hidden] with Lp_max the prompt
+        at the tensors' widths; row b is left-aligned over its own Lp_b = 1 + (1 + enroll_lengths[b]) + 1 + mix_lengths[b] positions
+        (2 + mix_lengths[b] without an enrollment) - build_prompt of the row alone, bit for bit - with exact zeros behind.  Padding frames
+        are never copied.  It feeds llm_forward(..., chunk_lengths=Lp) on a KVCache (qa_lm_prompt_ragged)."""
         self._ready()
         task = self.task_map[task_name]  # KeyError like the reference
         mix = mix_feats.to(device=self.device, dtype=torch.float32).contiguous()
@@ -267,6 +284,12 @@ class LLM_SFT:
             n_enr = enr.shape[1]
         L = 1 + (1 + n_enr if enr is not None else 0) + 1 + n_mix
         out = torch.empty((B, L, self.hidden_size), dtype=torch.float32, device=self.device)
+        if enroll_lengths is not None or mix_lengths is not None:
+            _, ne_arr = self._lengths("build_prompt: enroll_lengths", enroll_lengths, B)
+            _, nm_arr = self._lengths("build_prompt: mix_lengths", mix_lengths, B)
+            _lib.check(self._lib.qa_lm_prompt_ragged(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, ne_arr,
+                                                     mix.data_ptr(), n_mix, nm_arr, B, out.data_ptr(), self._stream()))
+            return out
         _lib.check(self._lib.qa_lm_prompt(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, mix.data_ptr(), n_mix, B,
                                           out.data_ptr(), self._stream()))
         return out
@@ -357,24 +380,85 @@ class LLM_SFT:
                                          out.data_ptr(), out[1:].data_ptr(), stream))
         return loss_seq, correct, out[0], out[1], G + T + 2
 
+    def _score_ragged(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths,
+                      semantic_lengths, enroll_lengths):
+        """qa_lm_score_ragged: _score with per-row lengths; the last entry is Lt_b = G + semantic_lengths[b] + 2 as an int64 [B] device
+        tensor.  Only the ids inside a row's length are range-checked."""
+        if not self._handle.value:
+            raise _lib.QuarkAudioError(-3, "LLM_SFT has no weights: call load_state_dict first")
+        task = self.task_map[task_name]  # KeyError like the reference
+        B = int(mix_mel.size(0))
+        mix = mix_feats.to(device=self.device, dtype=torch.float32).contiguous()
+        if mix.dim() != 3 or mix.shape[0] != B:
+            raise _lib.QuarkAudioError(-1, f"mix_feats must be [B={B}, N, feats_dim], got {tuple(mix.shape)}")
+        enr, n_enr = None, 0
+        if enroll_mel is not None:
+            enr = enroll_feats.to(device=self.device, dtype=torch.float32).contiguous()
+            if enr.dim() != 3 or enr.shape[0] != B:
+                raise _lib.QuarkAudioError(-1, f"enroll_feats must be [B={B}, N, feats_dim], got {tuple(enr.shape)}")
+            n_enr = enr.shape[1]
+        g = global_ids.to(device=self.device, dtype=torch.int64)
+        sids = semantic_ids.to(device=self.device, dtype=torch.int64)
+        g = g.reshape(B, g.numel() // B).contiguous()  # a width of 0 (no id at all) is a valid shape here
+        sids = sids.reshape(B, sids.numel() // B).contiguous()
+        G, T = g.shape[1], sids.shape[1]
+        _, ne_arr = self._lengths("enroll_lengths", enroll_lengths, B)
+        _, nm_arr = self._lengths("mix_lengths", mix_lengths, B)
+        t_lens, t_arr = self._lengths("semantic_lengths", semantic_lengths, B)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        # nn.Embedding's range check, over the ids a row really holds: what lies at or behind semantic_lengths[b] is padding
+        t_dev = torch.tensor(t_lens if t_lens is not None else [T] * B, dtype=torch.int64, device=self.device)
+        live = torch.arange(T, device=self.device)[None, :] < t_dev[:, None]
+        shifted = torch.cat([g.reshape(-1) + self.global_offset, sids[live] + self.semantic_offset]).contiguous()
+        if shifted.numel():
+            bad = C.c_int64(0)
+            _lib.check(self._lib.qa_codes_check(shifted.data_ptr(), shifted.numel(), self.vocab_size, C.byref(bad), stream))
+            if bad.value:
+                raise IndexError(f"{bad.value} input ids out of range [0, {self.vocab_size}) after the offsets (global + {self.global_offset}, "
+                                 f"semantic + {self.semantic_offset})")
+        loss_seq = torch.empty(B, dtype=torch.float32, device=self.device)
+        correct = torch.empty(B, dtype=torch.int64, device=self.device)
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.qa_lm_score_ragged(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, ne_arr, mix.data_ptr(),
+                                                mix.shape[1], nm_arr, B, g.data_ptr(), G, sids.data_ptr(), T, t_arr, self.label_smoothing,
+                                                loss_seq.data_ptr(), correct.data_ptr(), out.data_ptr(), out[1:].data_ptr(), stream))
+        return loss_seq, correct, out[0], out[1], t_dev + (G + 2)
+
     @torch.no_grad()
-    def forward(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids):
+    def forward(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, *, mix_lengths=None,
+                semantic_lengths=None, enroll_lengths=None):
         """llm_sft.py:37-90: teacher-forced (loss, acc), 0-dim float32 device tensors.  loss = F.kl_div(log_softmax(logits), true_dist,
         'batchmean') over the B * (G + T + 2) target rows with label smoothing `label_smoothing` (llm.py:87-104); acc = the fraction of
         rows whose first arg-max over the full vocabulary is the target.  global_ids [B, G] / semantic_ids [B, T], int32 or int64, offsets
-        subtracted (what BiCodecTokenizer.tokenize returns; any G).  Forward only: no graph, no gradient."""
-        _, _, loss, acc, _ = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
+        subtracted (what BiCodecTokenizer.tokenize returns; any G).  Forward only: no graph, no gradient.
+
+        mix_lengths / semantic_lengths / enroll_lengths (keyword only; a list or tensor of B ints each, None: every row at full width;
+        DESIGN.md section 35): row b is scored as that sequence alone on enroll_feats[b, :enroll_lengths[b]], mix_feats[b, :mix_lengths[b]]
+        and semantic_ids[b, :semantic_lengths[b]], with Lt_b = G + semantic_lengths[b] + 2 target rows.  What lies at or behind a row's
+        lengths is never read and never range-checked.  loss and acc then pool the rows: the sums over all target rows divided by
+        sum_b Lt_b.  With all three None the call is the reference's rectangular one."""
+        if mix_lengths is None and semantic_lengths is None and enroll_lengths is None:
+            _, _, loss, acc, _ = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
+            return loss, acc
+        _, _, loss, acc, _ = self._score_ragged(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths,
+                                                semantic_lengths, enroll_lengths)
         return loss, acc
 
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
 
     @torch.no_grad()
-    def score(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids):
+    def score(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, *, mix_lengths=None,
+              semantic_lengths=None, enroll_lengths=None):
         """forward per sequence: (loss [B], acc [B]) float32 - each sequence's mean label-smoothed KL and accuracy over its own G + T + 2
-        target rows (forward's scalars are their means).  A sequence's values do not depend on the batch it is scored in."""
-        loss_seq, correct, _, _, Lt = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
-        return loss_seq, correct.to(torch.float32) / Lt
+        target rows (forward's scalars are their means).  A sequence's values do not depend on the batch it is scored in.
+        With per-row lengths (see forward) row b's values are over its own Lt_b = G + semantic_lengths[b] + 2 rows."""
+        if mix_lengths is None and semantic_lengths is None and enroll_lengths is None:
+            loss_seq, correct, _, _, Lt = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
+            return loss_seq, correct.to(torch.float32) / Lt
+        loss_seq, correct, _, _, Lt = self._score_ragged(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids,
+                                                         mix_lengths, semantic_lengths, enroll_lengths)
+        return loss_seq, correct.to(torch.float32) / Lt.to(torch.float32)
 
     def enable_taps(self, on: bool = True):
         """Test hook: make generate record the slice logits of every decode step (qa_lm_enable_taps)."""
@@ -385,7 +469,8 @@ class LLM_SFT:
 
     def tap(self, name: str) -> torch.Tensor:
         """Test hook: flat fp32 copy of a snapshot of the last generate: "logits.global" ([B, global_length + 1, global_size]) or
-        "logits.semantic" ([B, semantic_length, semantic_size]); of the last forward / score: "logits.forced" ([B, G + T + 2, vocab])."""
+        "logits.semantic" ([B, semantic_length, semantic_size]); of the last forward / score: "logits.forced" ([B, G + T + 2, vocab]; after a call with per-row lengths packed,
+        [sum_b Lt_b, vocab], sequences in order)."""
         n = self._lib.qa_lm_tap(self._handle, name.encode(), None, 0, None)
         if n < 0:
             _lib.check(int(n))
@@ -501,8 +586,10 @@ class CustomLlamaModel:
     def output_head(self, hidden, lo: int = 0, width: Optional[int] = None):
         return self._lm.output_head(hidden, lo, width)
 
-    def build_prompt(self, task_name, enroll_feats, mix_feats):
-        return self._lm.build_prompt(task_name, enroll_feats, mix_feats)
+    def build_prompt(self, task_name, enroll_feats, mix_feats, *, enroll_lengths=None, mix_lengths=None):
+        """LLM_SFT.build_prompt on the same handle; with per-row lengths the result is [B, Lp_max, hidden], row b left-aligned over
+        Lp_b = 1 + (1 + enroll_lengths[b]) + 1 + mix_lengths[b] positions (2 + mix_lengths[b] without an enrollment), zeros behind."""
+        return self._lm.build_prompt(task_name, enroll_feats, mix_feats, enroll_lengths=enroll_lengths, mix_lengths=mix_lengths)
 
     def _score(self, global_ids, semantic_ids, cond):
         lm = self._lm

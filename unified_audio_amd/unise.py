@@ -529,12 +529,20 @@ class Model:
         return mode, enroll, src, int(fs[0]), names[0]
 
     @torch.no_grad()
-    def validation_step(self, batch, batch_idx: int = 0):
+    def validation_step(self, batch, batch_idx: int = 0, *, use_lengths: bool = False):
         """model.py:134-160: score the checkpoint on one held-out batch `(mode, enroll, mix, speech, interf, fs, lengths, names)` (B >= 1).
         The LM's targets are the BiCodec tokens of the interferer for 'rtse' and of the clean speech otherwise (tokenize needs the
         tokenizer's encoder weights); the prompt is the SSL features of the mixture (and of the enrollment when there is one).  There is
-        no Lightning here, so the values are returned instead of logged: {'valid_loss', 'valid_acc'}, 0-dim float32 device tensors."""
+        no Lightning here, so the values are returned instead of logged: {'valid_loss', 'valid_acc'}, 0-dim float32 device tensors.
+
+        use_lengths (keyword only; False: the reference's behaviour, which ignores `lengths` and scores the padding of a short clip like
+        any other frame): every clip is tokenized, featurised and scored over its own `lengths[b]` samples - tokenize(..., lengths=) with
+        token_frames(lengths) semantic tokens, semantic_model(mix, lengths=) with frames(lengths[b]) feature frames, the enrollment at
+        its one fixed duration as the loader gives it, then the LM's forward with per-row lengths.  The values pool
+        the clips' own target rows."""
         mode, enroll, mix, speech, interf, fs, lengths, names = batch
+        if use_lengths:
+            return self._validation_step_lengths(mode, enroll, mix, speech, interf, lengths)
         global_tokens, semantic_tokens = self.tokenizer.tokenize(interf if mode == "rtse" else speech)  # (B, 1, G) int32, (B, T) int64
         mix = mix.to(self.device, torch.float32)
         # the LM reads only mix_mel.size(0) and whether enroll_mel is None (llm_sft.py:63,72): the frame-count stand-in replaces the mel
@@ -547,6 +555,39 @@ class Model:
             enroll_feats = self.extract_semantic_features(enroll)
         loss, acc = self.dnn(task_name=mode, enroll_mel=enroll_mel, enroll_feats=enroll_feats, mix_mel=mix_mel, mix_feats=mix_feats,
                              global_ids=global_tokens.squeeze(1), semantic_ids=semantic_tokens)
+        return {"valid_loss": loss, "valid_acc": acc}
+
+    def _validation_step_lengths(self, mode, enroll, mix, speech, interf, lengths):
+        """validation_step(use_lengths=True): the batch's `lengths` (samples) through the tokenizer, the semantic model and the LM."""
+        import inspect
+
+        def takes_lengths(fn):
+            try:
+                return "lengths" in inspect.signature(fn).parameters
+            except (TypeError, ValueError):
+                return False
+
+        if lengths is None:
+            raise ValueError("validation_step(use_lengths=True): the batch carries no `lengths`")
+        if not takes_lengths(self.tokenizer.tokenize) or not hasattr(self.tokenizer, "token_frames"):
+            raise TypeError("validation_step(use_lengths=True): the tokenizer needs tokenize(wav, lengths=) and token_frames(lengths)")
+        if not takes_lengths(self.semantic_model.__call__) or not hasattr(self.semantic_model, "frames"):
+            raise TypeError("validation_step(use_lengths=True): the semantic model needs __call__(wavs, lengths=) and frames(n_samples)")
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        global_tokens, semantic_tokens = self.tokenizer.tokenize(interf if mode == "rtse" else speech, lengths=lens)
+        semantic_lengths = self.tokenizer.token_frames(lens)
+        mix = mix.to(self.device, torch.float32)
+        mix_mel = _Frames(mix.size(0), mel_frames(mix.size(-1)))
+        mix_feats = self.semantic_model(mix, lengths=lens)
+        mix_lengths = [self.semantic_model.frames(n) for n in lens]
+        enroll_mel = enroll_feats = None
+        if enroll is not None:  # one fixed duration for the whole batch (data_module.py: enroll_duration)
+            enroll = enroll.to(self.device, torch.float32)
+            enroll_mel = _Frames(enroll.size(0), mel_frames(enroll.size(-1)))
+            enroll_feats = self.extract_semantic_features(enroll)
+        loss, acc = self.dnn(task_name=mode, enroll_mel=enroll_mel, enroll_feats=enroll_feats, mix_mel=mix_mel, mix_feats=mix_feats,
+                             global_ids=global_tokens.squeeze(1), semantic_ids=semantic_tokens, mix_lengths=mix_lengths,
+                             semantic_lengths=semantic_lengths)
         return {"valid_loss": loss, "valid_acc": acc}
 
     @torch.no_grad()
