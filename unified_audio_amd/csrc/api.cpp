@@ -387,7 +387,7 @@ int64_t qa_resample_length(int64_t T, int32_t orig_freq, int32_t new_freq) {
 }
 
 // qa_resample (lengths == nullptr) and qa_resample_ragged.  The lengths are checked before anything is launched and reach the kernel as a
-// device array that row_lens_kernel writes from its own arguments, in stream order: nothing reads the caller's vector after the call.
+// device array that launch_row_ints writes from its own arguments, in stream order: nothing reads the caller's vector after the call.
 static int resample_call(const char* fn, const float* wav, int64_t B, int64_t T, const int64_t* lengths, int32_t orig_freq, int32_t new_freq,
                          float* out, void* stream) {
     QA_REQUIRE(B > 0 && T > 0 && orig_freq > 0 && new_freq > 0, "%s: bad argument", fn);
@@ -420,7 +420,7 @@ static int resample_call(const char* fn, const float* wav, int64_t B, int64_t T,
     hipError_t e = hipMemcpyAsync(dev, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, s);
     int st = QA_OK;
     if (e == hipSuccess && lengths) e = hipMallocAsync(reinterpret_cast<void**>(&lens_dev), sizeof(int) * (size_t)B, s);
-    if (e == hipSuccess && lengths) st = launch_row_lens(lens_dev, len.data(), (int)B, s);
+    if (e == hipSuccess && lengths) st = launch_row_ints(lens_dev, len.data(), B, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // `taps` is a stack-lifetime host buffer
     if (e == hipSuccess && st == QA_OK)
         st = launch_resample(wav, dev, out, (int)B, T, qa_resample_length(T, orig_freq, new_freq), orig, nw, width, 2 * width + orig, s,

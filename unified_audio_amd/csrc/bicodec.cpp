@@ -24,34 +24,6 @@ using namespace qa;
 
 namespace {
 
-// The lengths of a per-clip call on their way to the kernels: a handle-owned device array of `slots` vectors of
-// up to `cap` clips, written on the call's stream by row_lens_kernel with the values riding in its arguments.
-struct LensDev {
-    int* dev = nullptr;
-    int cap = 0;
-    LensDev() = default;
-    LensDev(const LensDev&) = delete;
-    LensDev& operator=(const LensDev&) = delete;
-    ~LensDev() {
-        if (dev) (void)hipFree(dev);
-    }
-    // *out = the device copy of len [B] in slot `slot` of `slots`
-    int upload(const std::vector<int>& len, int slot, int slots, hipStream_t stream, const int** out) {
-        const int B = (int)len.size();
-        if (B > cap) {
-            if (dev) QA_HIP(hipFree(dev));  // waits for the work that still reads it
-            dev = nullptr;
-            cap = 0;
-            const int grown = (int)round_up(B, 256);
-            QA_HIP(hipMalloc(reinterpret_cast<void**>(&dev), sizeof(int) * (size_t)grown * slots));
-            cap = grown;
-        }
-        QA_TRY(launch_row_lens(dev + (size_t)slot * cap, len.data(), B, stream));
-        *out = dev + (size_t)slot * cap;
-        return QA_OK;
-    }
-};
-
 struct VocosLayerW {
     const float *dw = nullptr, *dwb = nullptr, *lnw = nullptr, *lnb = nullptr, *gamma = nullptr;  // lnw == nullptr: AdaLN
     ConvW pw1, pw2;
@@ -92,7 +64,7 @@ struct qa_bicodec : Handle {
         VocosW down[2], backbone;
     };
     std::unique_ptr<Postnet> post;
-    LensDev lens;  // qa_bicodec_detokenize_ragged: the clips' token counts
+    DeviceInts lens;  // qa_bicodec_detokenize_ragged: the clips' token counts
 };
 
 // Conv1dReluBn (ecapa_tdnn.py): the convolution with BN(ReLU(.)) as the epilogue  relu(acc + b) * s + t
@@ -132,7 +104,7 @@ struct qa_bicodec_enc : Handle {
         const float *bn_s = nullptr, *bn_t = nullptr;  // BatchNorm1d(3072) in eval as y = v * s + t
     };
     std::unique_ptr<XvecHead> xvec;
-    LensDev lens;  // the _ragged entry points: slot 0 the clips' feature frames, slot 1 their samples
+    DeviceInts lens{2};  // the _ragged entry points: the clips' feature frames and their samples, whichever the call carries
 };
 
 namespace {
@@ -940,7 +912,7 @@ static int detokenize_call(qa_bicodec* h, const char* fn, const int64_t* semanti
         QA_TRY(check_clip_lengths(fn, B, lengths, 1, T, "tokens", "T", &len, &full));
         if (!full) {
             QA_HIP(hipSetDevice(h->device));
-            QA_TRY(h->lens.upload(len, 0, 1, static_cast<hipStream_t>(stream), &lens));
+            QA_TRY(h->lens.upload({&len}, static_cast<hipStream_t>(stream), &lens));
         }
     }
     return run_planned(*h, stream, [&] {
@@ -991,6 +963,7 @@ void qa_bicodec_enc_destroy(qa_bicodec_enc* h) { destroy_handle(h); }
 struct EncLens {
     std::vector<int> len;
     bool ragged = false;
+    const int* dev = nullptr;  // the device copy of a ragged half (upload_lens)
 };
 static int semantic_checks(qa_bicodec_enc* h, const char* fn, int64_t B, int64_t N, const int64_t* frame_lengths, EncLens* out) {
     QA_REQUIRE(B > 0 && N > 0, "%s: feat is [%lld, %lld, C]", fn, (long long)B, (long long)N);
@@ -1015,24 +988,28 @@ static int global_checks(qa_bicodec_enc* h, const char* fn, int64_t B, int64_t T
     if (*ref_len <= 0) *ref_len = T;
     return check_global_shape(h, B, T, *ref_len);
 }
+// The lengths of one call on their way to the kernels: every ragged half in ONE upload (a rectangular half carries none, dev stays null)
+static int upload_lens(qa_bicodec_enc* h, void* stream, EncLens* a, EncLens* b = nullptr) {
+    std::vector<EncLens*> ragged;
+    for (EncLens* l : {a, b})
+        if (l && l->ragged) ragged.push_back(l);
+    if (ragged.empty()) return QA_OK;
+    std::vector<const std::vector<int>*> src;
+    for (EncLens* l : ragged) src.push_back(&l->len);
+    const int* dev[2] = {nullptr, nullptr};
+    QA_HIP(hipSetDevice(h->device));
+    QA_TRY(h->lens.upload(src, static_cast<hipStream_t>(stream), dev));
+    for (size_t i = 0; i < ragged.size(); ++i) ragged[i]->dev = dev[i];
+    return QA_OK;
+}
 static int semantic_run(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, const EncLens& fl, int64_t* semantic_out, void* stream) {
-    const int* lens = nullptr;
-    if (fl.ragged) {
-        QA_HIP(hipSetDevice(h->device));
-        QA_TRY(h->lens.upload(fl.len, 0, 2, static_cast<hipStream_t>(stream), &lens));
-    }
     return run_planned(*h, stream, [&] {
-        return semantic_graph(h, h->ctx, feat, (int)B, (int)N, ClipLens{lens, lens ? 1 : 0}, (long long*)semantic_out);
+        return semantic_graph(h, h->ctx, feat, (int)B, (int)N, ClipLens{fl.dev, fl.dev ? 1 : 0}, (long long*)semantic_out);
     });
 }
 static int global_run(qa_bicodec_enc* h, const float* wav, int64_t B, int64_t T, int64_t ref_len, const EncLens& sl, int32_t* global_out,
                       void* stream) {
-    const int* lens = nullptr;
-    if (sl.ragged) {
-        QA_HIP(hipSetDevice(h->device));
-        QA_TRY(h->lens.upload(sl.len, 1, 2, static_cast<hipStream_t>(stream), &lens));
-    }
-    return run_planned(*h, stream, [&] { return global_graph(h, h->ctx, wav, (int)B, T, ref_len, lens, (int*)global_out); });
+    return run_planned(*h, stream, [&] { return global_graph(h, h->ctx, wav, (int)B, T, ref_len, sl.dev, (int*)global_out); });
 }
 
 int qa_bicodec_get_semantic_tokens(qa_bicodec_enc* h, const float* feat, int64_t B, int64_t N, int64_t* semantic_out, void* stream) {
@@ -1053,6 +1030,7 @@ int qa_bicodec_get_semantic_tokens_ragged(qa_bicodec_enc* h, const float* feat, 
     }
     EncLens fl;
     QA_TRY(semantic_checks(h, "qa_bicodec_get_semantic_tokens_ragged", B, N, frame_lengths, &fl));
+    QA_TRY(upload_lens(h, stream, &fl));
     return semantic_run(h, feat, B, N, fl, semantic_out, stream);
 }
 
@@ -1074,6 +1052,7 @@ int qa_bicodec_get_global_tokens_ragged(qa_bicodec_enc* h, const float* wav, int
     }
     EncLens sl;
     QA_TRY(global_checks(h, "qa_bicodec_get_global_tokens_ragged", B, T, &ref_len, lengths, &sl));
+    QA_TRY(upload_lens(h, stream, &sl));
     return global_run(h, wav, B, T, ref_len, sl, global_out, stream);
 }
 
@@ -1097,6 +1076,7 @@ int qa_bicodec_tokenize_ragged(qa_bicodec_enc* h, const float* feat, int64_t B, 
     EncLens fl, sl;
     QA_TRY(semantic_checks(h, "qa_bicodec_tokenize_ragged", B, N, frame_lengths, &fl));
     QA_TRY(global_checks(h, "qa_bicodec_tokenize_ragged", B, T_ref, &ref_len, lengths, &sl));
+    QA_TRY(upload_lens(h, stream, &fl, &sl));
     QA_TRY(semantic_run(h, feat, B, N, fl, semantic_out, stream));
     return global_run(h, ref_wav, B, T_ref, ref_len, sl, global_out, stream);
 }

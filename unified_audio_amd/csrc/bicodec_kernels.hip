@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void wav_normalize_kernel(const float* x, floa
 }
 // Per-clip lengths: row b is normalised over its own lens.n[b] samples - the same loops, so the same summation
 // order, as the kernel above on a [1, lens.n[b]] row - and nothing behind them is read.  The lengths ride BY VALUE in the launch, as
-// row_lens_kernel's do (ew.hip): this entry point has no handle that could own a device array.
+// row_ints_kernel's do (ew.hip): this entry point has no handle that could own a device array.
 constexpr int WAV_LENS_CHUNK = 256;
 struct WavLensArg {
     long long n[WAV_LENS_CHUNK];

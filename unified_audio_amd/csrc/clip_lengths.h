@@ -1,10 +1,12 @@
-// clip_lengths.h - the host-side check of the length vector of a per-clip BiCodec call.  Host code without a HIP
-// dependency, so that it also compiles into a stand-alone program under the host sanitizers (tools/clip_lengths_selftest.cpp).
+// clip_lengths.h - the length vector of a per-clip BiCodec / resample / wav_normalize call: check_row_lengths
+// (row_lengths.h) with the refusal worded.  Host code without a HIP dependency, so that it also compiles into a stand-alone program under
+// the host sanitizers (tools/clip_lengths_selftest.cpp).
 #pragma once
 #include <cstdint>
 #include <vector>
 
 #include "quarkaudio.h"
+#include "row_lengths.h"
 
 namespace qa {
 
@@ -24,17 +26,11 @@ inline int check_clip_lengths(const char* fn, int64_t B, const int64_t* lengths,
         set_error("%s: %lld clips of up to %lld %s", fn, (long long)B, (long long)hi, unit);
         return QA_ERR_INVALID;
     }
-    out->assign((size_t)B, 0);
-    *full = true;
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t v = lengths[b];
-        if (v < lo || v > hi) {
-            set_error("%s: lengths[%lld] = %lld is outside %lld .. %s = %lld (%s)", fn, (long long)b, (long long)v, (long long)lo, hi_name,
-                      (long long)hi, unit);
-            return QA_ERR_INVALID;
-        }
-        (*out)[(size_t)b] = (int)v;
-        *full = *full && v == hi;
+    const int64_t bad = check_row_lengths(lengths, B, lo, hi, out, full);
+    if (bad >= 0) {
+        set_error("%s: lengths[%lld] = %lld is outside %lld .. %s = %lld (%s)", fn, (long long)bad, (long long)lengths[bad], (long long)lo,
+                  hi_name, (long long)hi, unit);
+        return QA_ERR_INVALID;
     }
     return QA_OK;
 }

@@ -432,21 +432,21 @@ int launch_codes_from_bqn(const long long* src, long long* dst, int B, int N, in
     return QA_OK;
 }
 
-// Per-clip lengths of a ragged call.  The host vector travels BY VALUE in the launch (as the LM's row lengths do, lm_decode.hip): written
-// on the call's stream in stream order, no staging buffer whose lifetime a later call could cut short.
-constexpr int ROW_LENS_CHUNK = 256;
-struct RowLensArg {
-    int n[ROW_LENS_CHUNK];
+// The host integers of a call with per-row lengths: clip lengths, row counts, positions, offsets.  They travel BY
+// VALUE in the launch, ROW_INTS_CHUNK of them per launch: written on the call's stream in stream order, no staging buffer whose lifetime a
+// later call could cut short, and the host vector may be freed or overwritten on return.
+struct IntChunk {
+    int v[ROW_INTS_CHUNK];
 };
-__global__ void row_lens_kernel(int* __restrict__ dst, const RowLensArg a, int n) {
-    if ((int)threadIdx.x < n) dst[threadIdx.x] = a.n[threadIdx.x];
+__global__ __launch_bounds__(ROW_INTS_CHUNK) void row_ints_kernel(int* __restrict__ dst, const IntChunk a, int n) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = a.v[threadIdx.x];
 }
-int launch_row_lens(int* dst, const int* src, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += ROW_LENS_CHUNK) {
-        RowLensArg a{};
-        const int m = std::min(ROW_LENS_CHUNK, n - i0);
-        for (int i = 0; i < m; ++i) a.n[i] = src[i0 + i];
-        hipLaunchKernelGGL(row_lens_kernel, dim3(1), dim3(ROW_LENS_CHUNK), 0, s, dst + i0, a, m);
+int launch_row_ints(int* dst, const int* src, long long count, hipStream_t s) {
+    for (long long i0 = 0; i0 < count; i0 += ROW_INTS_CHUNK) {
+        IntChunk a{};
+        const int n = (int)std::min<long long>(ROW_INTS_CHUNK, count - i0);
+        std::copy(src + i0, src + i0 + n, a.v);
+        hipLaunchKernelGGL(row_ints_kernel, dim3(1), dim3(ROW_INTS_CHUNK), 0, s, dst + i0, a, n);
         QA_LAUNCH_CHECK();
     }
     return QA_OK;
@@ -1017,6 +1017,10 @@ extern "C" int qa_debug_stft_post(const float* ri, float* out, long long rows, i
 extern "C" int qa_debug_istft_ola(const float* frames, const float* win, float* out, int B, int T, int n_fft, int hop, const int* lens,
                                   int len_mul, void* stream) {
     return qa::launch_istft_ola(frames, win, out, B, T, n_fft, hop, static_cast<hipStream_t>(stream), qa::ClipLens{lens, len_mul});
+}
+// host_src: HOST int32 [count]; dst: device int32 [count] (tests/test_row_ints_gpu.py)
+extern "C" int qa_debug_row_ints(int* dst, const int* host_src, long long count, void* stream) {
+    return qa::launch_row_ints(dst, host_src, count, static_cast<hipStream_t>(stream));
 }
 extern "C" int qa_debug_to_channel_last(const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T,
                                         void* stream) {

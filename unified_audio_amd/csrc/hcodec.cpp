@@ -8,6 +8,7 @@
 #include <memory>
 
 #include "host_util.h"
+#include "row_lengths.h"
 
 namespace qa {
 
@@ -132,12 +133,10 @@ struct qa_hcodec : Handle {
                                 // 2 * frame_stride, the STFT's input blocks of (n_fft - hop) / 2 samples; enc[1] = frame_stride, its frames
         std::vector<int> sem;   // semantic encoder: at the input of block i; sem[n_sem_strides] = 1, the rate of its output
     } geom;
-    // ragged calls (qa_hcodec_encode_ragged / _decode_ragged and their _adaptive_ twins): the clips' code-frame counts [lens_cap], written on
-    // the call's stream
-    int* lens_dev = nullptr;
-    int lens_cap = 0;
+    // ragged calls (qa_hcodec_encode_ragged / _decode_ragged and their _adaptive_ twins): the clips' code-frame counts, written on the call's
+    // stream
+    DeviceInts lens;
     ~qa_hcodec() {
-        if (lens_dev) (void)hipFree(lens_dev);
         if (e2_dev) (void)hipFree(e2_dev);
         if (host_sync) (void)hipHostFree(host_sync);
         if (side) (void)hipStreamDestroy(side);
@@ -1346,7 +1345,7 @@ static TimeAxis clip_axis(const qa_hcodec* h, int64_t B, int64_t T, int rate, co
 // reports, which the 1.0 signatures cannot carry.  ragged_lengths: the lengths themselves (HOST memory, code frames, 1 .. N each;
 // the error names the row).  *lens = nullptr when every clip has N frames and the caller does not ask for the masked path whatever the
 // lengths (always_masked): the call is then the rectangular one as it is - fused stage 0, no key mask, nothing uploaded.  Otherwise
-// *lens = h->lens_dev, the lengths on their way to it in stream order in front of the call's kernels.
+// *lens = the handle's device array (h->lens), the lengths on their way to it in stream order in front of the call's kernels.
 static int ragged_refuse(qa_hcodec* h, const char* fn) {
     const qa_hcodec_spec& sp = h->spec;
     const char* why = sp.adaptive ? "an H-Codec 1.5 model (spec.adaptive): its per-clip calls are qa_hcodec_encode_adaptive_ragged / "
@@ -1362,28 +1361,14 @@ static int ragged_refuse(qa_hcodec* h, const char* fn) {
 static int ragged_lengths(qa_hcodec* h, const char* fn, int64_t B, int64_t N, const int64_t* frames, bool always_masked, void* stream,
                           const int** lens) {
     QA_REQUIRE(B > 0 && N > 0 && B < (1 << 20), "%s: %lld clips of %lld code frames", fn, (long long)B, (long long)N);
-    std::vector<int> len((size_t)B);
+    std::vector<int> len;
     bool full = true;
-    for (int64_t b = 0; b < B; ++b) {
-        QA_REQUIRE(frames[b] >= 1 && frames[b] <= N, "%s: frames[%lld] = %lld is outside 1 .. N = %lld", fn, (long long)b, (long long)frames[b],
-                   (long long)N);
-        len[(size_t)b] = (int)frames[b];
-        full = full && frames[b] == N;
-    }
+    const int64_t bad = check_row_lengths(frames, B, 1, N, &len, &full);
+    QA_REQUIRE(bad < 0, "%s: frames[%lld] = %lld is outside 1 .. N = %lld", fn, (long long)bad, (long long)frames[bad], (long long)N);
     *lens = nullptr;
     if (full && !always_masked) return QA_OK;
     QA_HIP(hipSetDevice(h->device));
-    if (B > h->lens_cap) {
-        if (h->lens_dev) QA_HIP(hipFree(h->lens_dev));  // waits for the work that still reads it
-        h->lens_dev = nullptr;
-        h->lens_cap = 0;
-        const int cap = (int)round_up(B, 256);
-        QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->lens_dev), sizeof(int) * (size_t)cap));
-        h->lens_cap = cap;
-    }
-    QA_TRY(launch_row_lens(h->lens_dev, len.data(), (int)B, static_cast<hipStream_t>(stream)));
-    *lens = h->lens_dev;
-    return QA_OK;
+    return h->lens.upload({&len}, static_cast<hipStream_t>(stream), lens);
 }
 
 // qa_hcodec_encode (frames == nullptr) and qa_hcodec_encode_ragged

@@ -149,6 +149,42 @@ struct Workspace {
     }
 };
 
+// The host integers of a call with per-row lengths on their way to the kernels: a handle-owned device array of
+// `slots` vectors of up to `cap` ints each, written on the call's stream by launch_row_ints.  It only grows, by whole multiples of
+// ROW_INTS_CHUNK rows; hipFree waits for the work that still reads the old array.
+struct DeviceInts {
+    int* dev = nullptr;
+    int cap = 0;
+    const int slots;
+    explicit DeviceInts(int slots = 1) : slots(slots) {}
+    DeviceInts(const DeviceInts&) = delete;
+    DeviceInts& operator=(const DeviceInts&) = delete;
+    ~DeviceInts() {
+        if (dev) (void)hipFree(dev);
+    }
+    // ALL the vectors of one call, each of the same B host ints: out[i] = the device copy of *src[i], i < src.size() <= slots.  The
+    // array grows at most once and before anything is written, so no vector of the call can land in an array that the same call frees.
+    int upload(const std::vector<const std::vector<int>*>& src, hipStream_t stream, const int** out) {
+        const size_t k = src.size(), B = k ? src[0]->size() : 0;
+        bool same = k >= 1 && k <= (size_t)slots && B >= 1 && B < ((size_t)1 << 30);
+        for (size_t i = 1; same && i < k; ++i) same = src[i]->size() == B;
+        QA_REQUIRE(same, "DeviceInts: %zu vectors of %zu ints into %d slots", k, B, slots);
+        if (B > (size_t)cap) {
+            if (dev) QA_HIP(hipFree(dev));
+            dev = nullptr;
+            cap = 0;
+            const int grown = (int)round_up((int64_t)B, ROW_INTS_CHUNK);
+            QA_HIP(hipMalloc(reinterpret_cast<void**>(&dev), sizeof(int) * (size_t)grown * slots));
+            cap = grown;
+        }
+        for (size_t i = 0; i < k; ++i) {
+            QA_TRY(launch_row_ints(dev + i * cap, src[i]->data(), (long long)B, stream));
+            out[i] = dev + i * cap;
+        }
+        return QA_OK;
+    }
+};
+
 struct Tap {
     const float* ptr;
     int64_t numel;

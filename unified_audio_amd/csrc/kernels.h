@@ -66,8 +66,10 @@ int launch_to_channel_last(const float* x, long long sb, long long sc, long long
 // lens [B] (device) or null: entries n >= lens[b] are written as -1 (the dropped code) whatever the source holds
 int launch_codes_to_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s, const int* lens = nullptr);
 int launch_codes_from_bqn(const long long* src, long long* dst, int B, int N, int Q, hipStream_t s, const int* lens = nullptr);
-// dst[0 .. n) (device) = the n host integers src, by value through the launch: no staging buffer, stream-ordered like any kernel
-int launch_row_lens(int* dst, const int* src, int n, hipStream_t s);
+// dst[0 .. count) (device) = the host integers src[0 .. count), in stream order like any kernel.  The values ride in the kernel arguments
+// (ROW_INTS_CHUNK per launch): no staging buffer, and the host vector may be freed on return
+constexpr int ROW_INTS_CHUNK = 256;
+int launch_row_ints(int* dst, const int* src, long long count, hipStream_t s);
 // valid [B, N] bytes: 1 where n < rl.n[b] * rl.mul (the key-padding mask of launch_attention)
 int launch_len_mask(unsigned char* valid, int B, int N, ClipLens rl, hipStream_t s);
 int launch_stft_post(const float* ri, float* out, long long rows, int nb, int ldi, int ldo, hipStream_t s);
@@ -157,10 +159,6 @@ int launch_skinny_gemm(const float* x, long long ldx, const float* w, const floa
 // rows are rotated and appended (a ragged chunk); nullptr: every item at pos0 with all n rows
 int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int max_len,
                    hipStream_t s, const int* row_pos0 = nullptr, const int* row_n = nullptr);
-// Host integers into device memory in stream order: dst[i] = vals[i], i < count.  The values ride in the kernel arguments (LM_ROW_INTS per
-// launch), so the host vector may be freed on return
-constexpr int LM_ROW_INTS = 256;
-int launch_lm_row_ints(int* dst, const int* vals, long long count, hipStream_t s);
 // y [B, n, d] <- x [B, n, d] for the rows t < row_n[b], exact zeros for the others, whose x rows are never read
 int launch_lm_rows_masked_copy(float* y, const float* x, int B, int n, int d, const int* row_n, hipStream_t s);
 // exact zeros into the rows t >= row_n[b] of every one of the `entries` tensors [B, n, d] that lie entry_stride floats apart
@@ -172,7 +170,7 @@ int launch_lm_row_loss(const float* z, long long ldl, int V, long long rows, con
 int launch_lm_seq_reduce(const float* row_kl, const int* row_ok, int B, int Lt, double* seq_sum, float* loss_seq, long long* correct_seq,
                          hipStream_t s);
 int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, int B, int Lt, float* loss, float* acc, hipStream_t s);
-// scoring with per-row lengths.  ne_r / nm_r / T_r / lp_r / off_r: device int [B] of one group (launch_lm_row_ints):
+// scoring with per-row lengths.  ne_r / nm_r / T_r / lp_r / off_r: device int [B] of one group (launch_row_ints):
 // the row's enrollment frames, mixture frames, semantic ids, prompt positions and packed target-row offset
 // x [B, n, d] <- prompt + input embeddings left-aligned, zeros behind; tgt (packed) <- the targets.  table == nullptr: the prompt alone
 int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,

@@ -19,6 +19,7 @@
 #include "host_util.h"
 #include "lm_decode.h"
 #include "lm_score_rows.h"
+#include "row_lengths.h"
 
 using namespace qa;
 
@@ -786,7 +787,7 @@ int write_score_ints(int* dst, const ScoreRows& R, const ScoreGroup& g, hipStrea
         vals[(size_t)SR_LP * g.gb + i] = R.Lp[b];
         vals[(size_t)SR_L * g.gb + i] = R.L[b];
     }
-    return launch_lm_row_ints(dst, vals.data(), (long long)vals.size(), s);
+    return launch_row_ints(dst, vals.data(), (long long)vals.size(), s);
 }
 
 // score_graph with per-row lengths.  The same structure - groups of at most LM_MAX_ROWS sequences in index order,
@@ -862,18 +863,14 @@ int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
 
 // ---- sessions: qa_lm_forward over a caller-held qa_lm_cache (CustomLlamaModel.llm_forward, llm.py:150-227)
 
-// Length and batch of a cache are host state, so a session call cannot be recorded into a caller's graph: a replay would run with the
-// positions of the capture.  Refused, with the reason.
-int refuse_capture(const char* fn, hipStream_t s) {
-    QA_REQUIRE(!stream_capturing(s),
-               "%s: refused under a stream capture - the cache length is host state, a replayed graph would repeat the captured positions", fn);
-    return QA_OK;
-}
-
-// The lengths of a ragged score / prompt call are read on the host during the call: a replayed graph would repeat the captured lengths.
-int refuse_score_capture(const char* fn, hipStream_t s) {
-    QA_REQUIRE(!stream_capturing(s), "%s: refused under a stream capture - the rows' lengths are host data read during the call, a replayed "
-               "graph would repeat the captured lengths", fn);
+// A call that reads host state cannot be recorded into a caller's graph: a replay would run with what the capture read.  Refused, with the
+// reason.  CACHE_IS_HOST_STATE: length and batch of a cache (the session calls); LENGTHS_ARE_HOST_DATA: the length vectors of a ragged
+// score / prompt call.
+const char* const CACHE_IS_HOST_STATE = "the cache length is host state, a replayed graph would repeat the captured positions";
+const char* const LENGTHS_ARE_HOST_DATA =
+    "the rows' lengths are host data read during the call, a replayed graph would repeat the captured lengths";
+int refuse_capture(const char* fn, hipStream_t s, const char* why) {
+    QA_REQUIRE(!stream_capturing(s), "%s: refused under a stream capture - %s", fn, why);
     return QA_OK;
 }
 
@@ -936,7 +933,7 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
             std::vector<int> vals((size_t)2 * B);
             std::copy(a.cache->len.begin(), a.cache->len.begin() + B, vals.begin());
             std::copy(a.n_rows, a.n_rows + B, vals.begin() + B);
-            QA_TRY(launch_lm_row_ints(row_pos0, vals.data(), 2 * (long long)B, c.stream));
+            QA_TRY(launch_row_ints(row_pos0, vals.data(), 2 * (long long)B, c.stream));
             QA_TRY(launch_lm_rows_masked_copy(b.x, a.x, B, n, d, row_n, c.stream));
             QA_TRY(lm_body(lm, c, b, B, n, pos0, b.cap, false, false, a.all_hidden, row_pos0, row_n));
         } else {
@@ -959,7 +956,7 @@ int forward_graph(qa_lm* lm, Ctx& c, const ForwardArgs& a) {
                 vals[(size_t)B + i] = on ? 1 : 0;
                 idle += !on;
             }
-            QA_TRY(launch_lm_row_ints(a.cache->rows, vals.data(), 2 * (long long)B, c.stream));
+            QA_TRY(launch_row_ints(a.cache->rows, vals.data(), 2 * (long long)B, c.stream));
         }
         for (int b0 = 0; b0 < B; b0 += GB) {
             const int gb = std::min(GB, B - b0);
@@ -1117,7 +1114,7 @@ int qa_lm_cache_select(qa_lm_cache* cache, const int64_t* idx, int64_t n, void* 
         return QA_ERR_INVALID;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_lm_cache_select", s));
+    QA_TRY(refuse_capture("qa_lm_cache_select", s, CACHE_IS_HOST_STATE));
     QA_REQUIRE(cache->B > 0, "qa_lm_cache_select: the cache has no batch yet (no qa_lm_forward call since create / reset)");
     QA_REQUIRE(n >= 1 && n <= cache->max_batch, "qa_lm_cache_select: %lld rows requested, the cache was created with max_batch %d", (long long)n,
                cache->max_batch);
@@ -1165,7 +1162,7 @@ int qa_lm_forward_ragged(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embe
         return QA_ERR_INVALID;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture(fn, s));
+    QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
     QA_REQUIRE(cache, "%s: a qa_lm_cache is required - without one every row starts at position 0 and a causal pass over left-aligned rows "
                "is qa_lm_forward", fn);
     QA_REQUIRE(n, "%s: null n (HOST int64 [B], the rows' position counts)", fn);
@@ -1197,7 +1194,7 @@ int qa_lm_forward(qa_lm* lm, qa_lm_cache* cache, const float* inputs_embeds, int
         return QA_ERR_INVALID;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_lm_forward", s));
+    QA_TRY(refuse_capture("qa_lm_forward", s, CACHE_IS_HOST_STATE));
     QA_REQUIRE(B >= 1 && n >= 1 && B <= (1 << 16), "qa_lm_forward: bad shape B = %lld, n = %lld", (long long)B, (long long)n);
     std::vector<int> n_rows;
     if (cache) {
@@ -1249,7 +1246,7 @@ int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_e
         return QA_ERR_INVALID;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_lm_prompt", s));  // the adapters' scratch lives in the session workspace, which may have to grow
+    QA_TRY(refuse_capture("qa_lm_prompt", s, CACHE_IS_HOST_STATE));  // the adapters' scratch lives in the session workspace, which may have to grow
     QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_prompt: task %d out of range (KeyError in the reference)", task);
     QA_REQUIRE(B >= 1 && n_mix >= 1 && n_mix <= LM_MAX_POS && B <= (1 << 16), "qa_lm_prompt: bad shape");
     QA_REQUIRE(!enroll_feats || (n_enroll >= 1 && n_enroll <= LM_MAX_POS), "qa_lm_prompt: enrollment given with no frames");
@@ -1272,7 +1269,7 @@ int qa_lm_prompt_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int6
         return QA_ERR_INVALID;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_score_capture(fn, s));
+    QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
     QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, task);
     QA_REQUIRE(B >= 1 && n_mix_max >= 1 && n_mix_max <= LM_MAX_POS && B <= (1 << 16), "%s: bad shape", fn);
     QA_REQUIRE(!enroll_feats || (n_enroll_max >= 1 && n_enroll_max <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
@@ -1353,12 +1350,9 @@ static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = fa
         QA_REQUIRE(total <= LM_MAX_POS,
                    "%s: %lld positions (prompt %d with n_enroll_max %d and n_mix %d, + %d + 1 + %d) exceed max_position_embeddings %d", fn,
                    total, prompt_len(p), p.Ne, p.Nm, a.G, a.S, LM_MAX_POS);
-        ne_host.resize((size_t)a.B);
-        for (int i = 0; i < a.B; ++i) {
-            QA_REQUIRE(ne_rows64[i] >= 1 && ne_rows64[i] <= p.Ne, "%s: n_enroll[%d] = %lld is outside 1 .. n_enroll_max = %d", fn, i,
-                       (long long)ne_rows64[i], p.Ne);
-            ne_host[(size_t)i] = (int)ne_rows64[i];
-        }
+        bool full = true;  // not used: a batch of full rows still runs as a ragged one
+        const int64_t bad = check_row_lengths(ne_rows64, a.B, 1, p.Ne, &ne_host, &full);
+        QA_REQUIRE(bad < 0, "%s: n_enroll[%d] = %lld is outside 1 .. n_enroll_max = %d", fn, (int)bad, (long long)ne_rows64[bad], p.Ne);
         p.ne_rows = ne_host.data();
     }
     QA_HIP(hipSetDevice(lm->device));
@@ -1488,7 +1482,7 @@ int qa_lm_score_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64
         return QA_ERR_INVALID;
     }
     // every check comes before the first launch: a refused call has launched nothing and leaves the handle as it was
-    QA_TRY(refuse_score_capture(fn, static_cast<hipStream_t>(stream)));
+    QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
     QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, task);
     QA_REQUIRE(B > 0 && B <= (1 << 24) && n_mix_max > 0 && n_mix_max <= LM_MAX_POS && global_length >= 0 && global_length <= LM_MAX_POS &&
                    semantic_length_max >= 0 && semantic_length_max <= LM_MAX_POS, "%s: bad shape", fn);

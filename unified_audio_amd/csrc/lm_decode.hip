@@ -978,24 +978,16 @@ int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* 
 
 // ------------------------------------------------------------------------------------------------
 // Row offsets of a ragged batch: off[i] = n_rows[i] - n_max <= 0, one launch per chain and call.  The lengths are
-// host data, so they ride in the kernel arguments (one struct of LM_MAX_ROWS ints) and land in device memory in stream order.
-struct RowLens {
-    int n[LM_MAX_ROWS];
-};
-__global__ __launch_bounds__(LM_MAX_ROWS) void lm_offsets_kernel(int* __restrict__ off, const RowLens len, int n_max, int B) {
-    const int i = threadIdx.x;
-    if (i < B) off[i] = len.n[i] - n_max;
-}
+// host data: the offsets are computed here and ride in the arguments of launch_row_ints (ew.hip) into device memory in stream order.
 int launch_lm_offsets(int* off, const int* n_rows, int n_max, int B, hipStream_t s) {
     QA_REQUIRE(B >= 1 && B <= LM_MAX_ROWS, "lm_offsets: %d rows (a chain holds 1 .. %d)", B, LM_MAX_ROWS);
-    RowLens len{};
+    static_assert(LM_MAX_ROWS <= ROW_INTS_CHUNK, "the offsets of a chain are one launch");
+    int host[LM_MAX_ROWS];
     for (int i = 0; i < B; ++i) {
         QA_REQUIRE(n_rows[i] >= 1 && n_rows[i] <= n_max, "lm_offsets: row %d has %d frames, outside 1 .. %d", i, n_rows[i], n_max);
-        len.n[i] = n_rows[i];
+        host[i] = n_rows[i] - n_max;
     }
-    hipLaunchKernelGGL(lm_offsets_kernel, dim3(1), dim3(LM_MAX_ROWS), 0, s, off, len, n_max, B);
-    QA_LAUNCH_CHECK();
-    return QA_OK;
+    return launch_row_ints(off, host, B, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -233,26 +233,9 @@ int launch_rope_kv(float* qkv, const float* cs, float* kc, float* vc, int B, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// Per-row lengths of a session call.  The lengths are host data: they ride in the kernel arguments and land in
-// a device array the cache owns, in stream order (as launch_lm_offsets does for ragged generate).
-struct RowInts {
-    int v[LM_ROW_INTS];
-};
-__global__ __launch_bounds__(LM_ROW_INTS) void lm_row_ints_kernel(int* __restrict__ dst, const RowInts vals, int count) {
-    const int i = threadIdx.x;
-    if (i < count) dst[i] = vals.v[i];
-}
-int launch_lm_row_ints(int* dst, const int* vals, long long count, hipStream_t s) {
-    for (long long i0 = 0; i0 < count; i0 += LM_ROW_INTS) {
-        const int c = (int)std::min<long long>(LM_ROW_INTS, count - i0);
-        RowInts r{};
-        std::memcpy(r.v, vals + i0, sizeof(int) * c);
-        hipLaunchKernelGGL(lm_row_ints_kernel, dim3(1), dim3(LM_ROW_INTS), 0, s, dst + i0, r, c);
-        QA_LAUNCH_CHECK();
-    }
-    return QA_OK;
-}
-
+// Per-row lengths of a session call.  The lengths are host data: launch_row_ints (ew.hip) writes them into a device
+// array the cache owns, in stream order.
+//
 // The input of a ragged chunk: rows t < row_n[b] are copied, the others become exact zeros WITHOUT being read.  A zero row stays a zero
 // row through the whole body (no projection of the Llama layers has a bias, RMSNorm and SwiGLU map 0 to 0, and the ragged attention
 // writes 0 for such a query), so the padded rows of every hidden state and of the final norm come out as 0 with no launch of their own.
@@ -474,7 +457,7 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
 // ------------------------------------------------------------------------------------------------
 // Teacher-forced scoring with per-row lengths (qa_lm_score_ragged / qa_lm_prompt_ragged).  Row b of a group holds
 // ne[b] of the Ne enrollment frames, nm[b] of the Nm mixture frames and T[b] of the T_max semantic ids (device int [B] each, written by
-// launch_lm_row_ints).  The rectangular kernels above keep their code: these are launched by the ragged entry points alone.
+// launch_row_ints).  The rectangular kernels above keep their code: these are launched by the ragged entry points alone.
 //
 // One assembly pass: x [B, n, d] row b <- [task, (enroll_sos, enroll_emb[b, :ne])?, mix_sos, mix_emb[b, :nm], codec_embedding(input_ids_b)]
 // left-aligned over L_b = Lp_b + Lt_b positions, exact zeros behind; target_ids_b -> tgt[off[b] ..] (PACKED: Lt_b = G + T[b] + 2 entries).

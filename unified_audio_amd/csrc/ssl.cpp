@@ -17,6 +17,7 @@
 #include <memory>
 
 #include "host_util.h"
+#include "row_lengths.h"
 
 using namespace qa;
 
@@ -41,12 +42,9 @@ struct qa_ssl : Handle {
     const float* relbias = nullptr;  // WavLM: [H][2R+1] relative position bias by clamped distance, R = rel_pos_max_distance
     std::vector<SslLayer> layers;
     std::vector<int> select;
-    // ragged calls: the clips' lengths [3][lens_cap] - in samples, in layer-0 frames, in output frames - written on the call's stream
-    int* lens_dev = nullptr;
-    int lens_cap = 0;
-    ~qa_ssl() {
-        if (lens_dev) (void)hipFree(lens_dev);
-    }
+    // ragged calls: the clips' lengths [3][B] - in samples, in layer-0 frames, in output frames - as ONE vector of 3 B ints (one upload, one
+    // launch up to B = 85), written on the call's stream
+    DeviceInts lens;
 };
 
 namespace {
@@ -393,33 +391,26 @@ static int forward_call(qa_ssl* h, const char* fn, const float* wav, int64_t B, 
     QA_REQUIRE(B * L0 < (1LL << 31) && L0 * sp.conv_dim[0] < (1LL << 31), "%s: batch of %lld x %lld samples is too large", fn, (long long)B,
                (long long)T);
     SslLens lens;
+    int64_t min_len = 1;  // the shortest input that yields one frame
+    for (int i = sp.n_conv - 1; i >= 0; --i) min_len = (min_len - 1) * sp.conv_stride[i] + sp.conv_kernel[i];
+    min_len = std::max<int64_t>(1, min_len - 2 * (int64_t)sp.pad);
+    std::vector<int> v;
     bool full = true;
-    for (int64_t b = 0; lengths && b < B; ++b) full = full && lengths[b] == T;
+    const int64_t bad = lengths ? check_row_lengths(lengths, B, min_len, T, &v, &full) : -1;
     if (!full) {
         QA_REQUIRE(B < (1 << 20) && T < (1LL << 31), "%s: %lld clips of %lld samples", fn, (long long)B, (long long)T);
-        int64_t min_len = 1;  // the shortest input that yields one frame
-        for (int i = sp.n_conv - 1; i >= 0; --i) min_len = (min_len - 1) * sp.conv_stride[i] + sp.conv_kernel[i];
-        min_len = std::max<int64_t>(1, min_len - 2 * (int64_t)sp.pad);
+        QA_REQUIRE(bad < 0, "%s: lengths[%lld] = %lld is outside %lld .. T = %lld samples", fn, (long long)bad, (long long)lengths[bad],
+                   (long long)min_len, (long long)T);
         // host vectors [3][B]: samples, layer-0 frames (the valid-conv floor rule of the graph), output frames
-        std::vector<int> v((size_t)3 * B);
+        v.resize((size_t)3 * B);
         for (int64_t b = 0; b < B; ++b) {
-            QA_REQUIRE(lengths[b] >= min_len && lengths[b] <= T, "%s: lengths[%lld] = %lld is outside %lld .. T = %lld samples", fn, (long long)b,
-                       (long long)lengths[b], (long long)min_len, (long long)T);
-            v[(size_t)b] = (int)lengths[b];
             v[(size_t)(B + b)] = (int)((lengths[b] + 2 * (int64_t)sp.pad - sp.conv_kernel[0]) / sp.conv_stride[0] + 1);
             v[(size_t)(2 * B + b)] = (int)frames_of(sp, lengths[b]);
         }
+        const int* dev = nullptr;
         QA_HIP(hipSetDevice(h->device));
-        if (B > h->lens_cap) {
-            if (h->lens_dev) QA_HIP(hipFree(h->lens_dev));  // waits for the work that still reads it
-            h->lens_dev = nullptr;
-            h->lens_cap = 0;
-            const int cap = (int)round_up(B, 256);
-            QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->lens_dev), sizeof(int) * 3 * (size_t)cap));
-            h->lens_cap = cap;
-        }
-        QA_TRY(launch_row_lens(h->lens_dev, v.data(), (int)(3 * B), static_cast<hipStream_t>(stream)));
-        lens = SslLens{h->lens_dev, h->lens_dev + B, h->lens_dev + 2 * B};
+        QA_TRY(h->lens.upload({&v}, static_cast<hipStream_t>(stream), &dev));
+        lens = SslLens{dev, dev + B, dev + 2 * B};
     }
     return run_planned(*h, stream, [&] { return forward_graph(h, h->ctx, wav, (int)B, (int)T, lens, feats); });
 }
