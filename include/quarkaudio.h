@@ -830,6 +830,16 @@ void qa_cond_encoder_destroy(qa_cond_encoder* h);
 int qa_cond_encoder_forward(qa_cond_encoder* h, const float* mel, const uint8_t* mask, int64_t B, int64_t T, float* out, void* stream);
 /* the bare ConformerEncoder: x fp32 [B, T, dim] -> out [B, T, dim] (out may alias x) */
 int qa_conformer_forward(qa_cond_encoder* h, const float* x, const uint8_t* mask, int64_t B, int64_t T, float* out, void* stream);
+/* The two calls above over a batch whose items differ in length.  lengths: HOST int64 [B], each in 1 .. T frames, read during the call
+ * (it may be freed on return).  Item b comes out as the call without a mask would give it ALONE at T = lengths[b]: keys at or behind
+ * lengths[b] are invisible, the convolution module's "same" zero padding starts at lengths[b] (the mask above never reaches that module),
+ * and out[b, lengths[b]:] is exactly 0.  What x / mel hold at or behind an item's length is never used (NaN included).  The vector is
+ * checked on the host before anything is launched - the message names the row and its value - so the call does not wait for the device;
+ * it is refused under a stream capture.  lengths NULL, or every entry equal to T: the call without a mask, same launches, same bits.
+ * Taps keep their shapes; rows behind an item's length are unspecified except in conformer.N.attn, where they are zero. */
+int qa_cond_encoder_forward_ragged(qa_cond_encoder* h, const float* mel, const int64_t* lengths, int64_t B, int64_t T, float* out,
+                                   void* stream);
+int qa_conformer_forward_ragged(qa_cond_encoder* h, const float* x, const int64_t* lengths, int64_t B, int64_t T, float* out, void* stream);
 /* test hooks, as qa_hcodec_enable_taps / qa_hcodec_tap: conformer.N.ff1 (x after the first half-step), conformer.N.attn (the attention
  * module's output, masked rows zero, before the residual), conformer.N.conv (x after the convolution module), conformer.N.out; [B, T, dim] */
 int qa_cond_encoder_enable_taps(qa_cond_encoder* h, int on);
@@ -844,6 +854,12 @@ int64_t qa_cond_encoder_tap(qa_cond_encoder* h, const char* name, float* dst, in
 int64_t qa_logmel_frames(int64_t n, int32_t hop_length);
 int qa_logmel(const float* wav, int64_t B, int64_t n, int32_t n_fft, int32_t win_length, int32_t hop_length, int32_t n_mels, int32_t sample_rate,
               float f_min, float f_max, float* out, void* stream);
+/* qa_logmel over clips of different lengths.  lengths: HOST int64 [B], each in 1 .. n samples, read during the call.  With
+ * F_b = qa_logmel_frames(lengths[b], hop): out[b, :F_b] is qa_logmel of wav[b, :lengths[b]] alone, out[b, F_b:] is exactly 0, and the
+ * samples at or behind lengths[b] are never used.  Checked before anything is launched (the message names the row and its value), refused
+ * under a stream capture.  lengths NULL, or every entry equal to n: qa_logmel, same launches, same bits. */
+int qa_logmel_ragged(const float* wav, const int64_t* lengths, int64_t B, int64_t n, int32_t n_fft, int32_t win_length, int32_t hop_length,
+                     int32_t n_mels, int32_t sample_rate, float f_min, float f_max, float* out, void* stream);
 
 /* CustomLlamaModel.generate (llm.py:291-374) on a qa_lm handle: prompt [mix_sos, cond_embeds] (cond_embeds fp32 [B, T, hidden] on the
  * device, the condition encoder's output) or NO prompt (cond_embeds NULL and T = 0: the first step runs at position 0 over an empty
@@ -854,11 +870,36 @@ int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t 
 int qa_lm_generate_cond_sampled(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
                                 float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
                                 void* stream);
+/* The two calls above over a batch whose conditions differ in length, by the mechanism of qa_lm_generate_ragged.  cond_embeds is
+ * [B, T_max, hidden]; n_cond: HOST int64 [B], each in 1 .. T_max, read during the call.  Row b behaves as qa_lm_generate_cond would for it
+ * ALONE with cond_embeds[b, :n_cond[b]]: prompt [mix_sos, cond] at positions 0 .. n_cond[b], decode step t at position 1 + n_cond[b] + t.
+ * Frames at or behind n_cond[b] are never used (NaN included).  global_length and semantic_length are common to the batch.  Refused,
+ * before anything is launched: a vector with cond_embeds NULL or T_max = 0; a length out of range (the message names the row and its
+ * value); 1 + T_max + global_length + 1 + semantic_length above 4096; a stream capture.  n_cond NULL, or every entry equal to T_max:
+ * qa_lm_generate_cond(_sampled), same launches, same bits.  Taps as there. */
+int qa_lm_generate_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, int32_t global_length,
+                               int32_t semantic_length, float temperature, int32_t top_k, float top_p, int64_t* global_ids,
+                               int64_t* semantic_ids, void* stream);
+int qa_lm_generate_cond_ragged_sampled(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B,
+                                       int32_t global_length, int32_t semantic_length, float temperature, int32_t top_k, float top_p,
+                                       uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream);
 /* CustomLlamaModel.forward (llm.py:107-147): as qa_lm_score with the prompt above, and with the LAST input / target position dropped
  * (llm.py:126-127): Lt = global_length + semantic_length + 1, no semantic_eos target.  "logits.forced" is [B, Lt, V]. */
 int qa_lm_score_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, const int64_t* global_ids, int32_t global_length,
                      const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing, float* loss_per_seq,
                      int64_t* correct_per_seq, float* loss, float* acc, void* stream);
+/* qa_lm_score_cond over rows that differ in their condition frames, their semantic ids, or both, by the plan and the kernels of
+ * qa_lm_score_ragged.  n_cond: HOST int64 [B], each in 1 .. T_max; n_semantic: HOST int64 [B], each in 0 .. semantic_length_max; either may
+ * be NULL (every row at full width); both are read during the call.  Row b is scored as qa_lm_score_cond scores it ALONE with
+ * cond_embeds[b, :n_cond[b]] and semantic_ids[b, :n_semantic[b]]: Lp_b = 1 + n_cond[b] prompt positions and
+ * Lt_b = global_length + n_semantic[b] + 1 target rows - the last position of ITS OWN stream is dropped, there is no eos target.  Frames
+ * and ids at or behind a row's counts are never used.  loss_per_seq[b] is the mean over the row's Lt_b targets; loss and acc pool all
+ * sum Lt_b target rows; "logits.forced" is packed [sum Lt_b, V], rows in order.  Refused, before anything is launched: n_cond with
+ * cond_embeds NULL or T_max = 0, a count out of range (the message names the row and its value), a row of more than 4096 positions, a
+ * stream capture.  Both vectors NULL or at full width: qa_lm_score_cond, same launches, same bits. */
+int qa_lm_score_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, const int64_t* global_ids,
+                            int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length_max, const int64_t* n_semantic,
+                            double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -258,6 +258,17 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_lm_generate_cond_sampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                               C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_cond_encoder_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_conformer_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_logmel_ragged": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "qa_lm_generate_cond_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32,
+                                             C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_generate_cond_ragged_sampled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32,
+                                                     C.c_float, C.c_int32, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_score_cond_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_int32, C.POINTER(C.c_int64), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "qa_lm_cache_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "qa_lm_cache_destroy": (None, [C.c_void_p]),
     "qa_lm_cache_length": (C.c_int64, [C.c_void_p]),
@@ -276,6 +287,17 @@ SYMBOLS = {
     "qa_lm_score_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+
+def host_lengths(name: str, lengths, B: int):
+    """A per-row length argument (None, or B ints as a list / tensor) as (list or None, HOST int64 array or None): the library reads the
+    array during the call."""
+    if lengths is None:
+        return None, None
+    lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) != B:
+        raise QuarkAudioError(-1, f"{name} has {len(lens)} entries for a batch of {B}")
+    return lens, (C.c_int64 * max(B, 1))(*lens)
 
 
 def lib_path() -> str:

@@ -55,13 +55,17 @@ class _CondHandle:
         except Exception:
             pass
 
-    def _run(self, fn, x: torch.Tensor, mask: Optional[torch.Tensor], width_in: int, width_out: int) -> torch.Tensor:
+    def _run(self, fn, fn_ragged, x: torch.Tensor, mask: Optional[torch.Tensor], lengths, width_in: int, width_out: int) -> torch.Tensor:
         if not self._handle.value:
             raise _lib.QuarkAudioError(-3, f"{type(self).__name__} has no weights: call load_state_dict first")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         if x.dim() != 3 or x.shape[-1] != width_in:
             raise _lib.QuarkAudioError(-1, f"input must be [B, T, {width_in}], got {tuple(x.shape)}")
         B, T, _ = x.shape
+        if mask is not None and lengths is not None:
+            raise _lib.QuarkAudioError(-1, "mask and lengths are two different functions (the mask never reaches the convolution module): "
+                                           "pass one of them")
+        _, lens = _lib.host_lengths("lengths", lengths, B)
         m = None
         if mask is not None:
             m = mask.to(device=self.device, dtype=torch.bool).contiguous()
@@ -69,6 +73,9 @@ class _CondHandle:
                 raise _lib.QuarkAudioError(-1, f"mask must be bool [B={B}, T={T}], got {tuple(m.shape)}")
         y = torch.empty((B, T, width_out), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if lens is not None:
+            _lib.check(fn_ragged(self._handle, x.data_ptr(), lens, B, T, y.data_ptr(), stream))
+            return y
         _lib.check(fn(self._handle, x.data_ptr(), m.data_ptr() if m is not None else None, B, T, y.data_ptr(), stream))
         return y
 
@@ -119,9 +126,13 @@ class ConformerEncoder(_CondHandle):
         return super().load_state_dict(sd, strict)
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B, T, dim], mask bool [B, T] (True = valid) or None -> [B, T, dim]"""
-        return self._run(self._lib.qa_conformer_forward, x, mask, self.dim, self.dim)
+    def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None, *, lengths=None) -> torch.Tensor:
+        """x [B, T, dim], mask bool [B, T] (True = valid) or None -> [B, T, dim].
+
+        lengths (keyword only; B frame counts in 1 .. T): row b comes out as forward(x[b:b+1, :lengths[b]]) alone, exact zeros behind, and
+        what x holds behind a row's length is never used.  This is NOT the mask: the reference's mask hides padded keys but never reaches
+        the convolution module, whose k = 31 window then pulls padded frames into a row's last 15 valid ones.  One of the two at most."""
+        return self._run(self._lib.qa_conformer_forward, self._lib.qa_conformer_forward_ragged, x, mask, lengths, self.dim, self.dim)
 
 
 class ConditionEncoder(_CondHandle):
@@ -138,6 +149,7 @@ class ConditionEncoder(_CondHandle):
                          rope_interleaved), device)
 
     @torch.no_grad()
-    def forward(self, cond: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """cond [B, T, cond_dim] (log-mel) -> [B, T, hidden_size]"""
-        return self._run(self._lib.qa_cond_encoder_forward, cond, mask, self.cond_dim, self.hidden_size)
+    def forward(self, cond: torch.Tensor, mask: Optional[torch.Tensor] = None, *, lengths=None) -> torch.Tensor:
+        """cond [B, T, cond_dim] (log-mel) -> [B, T, hidden_size]; `lengths` as ConformerEncoder.forward (zeros behind a row's length)"""
+        return self._run(self._lib.qa_cond_encoder_forward, self._lib.qa_cond_encoder_forward_ragged, cond, mask, lengths, self.cond_dim,
+                         self.hidden_size)

@@ -13,6 +13,7 @@
 #include <tuple>
 
 #include "host_util.h"
+#include "row_lengths.h"
 
 using namespace qa;
 
@@ -39,6 +40,7 @@ struct qa_cond_encoder : Handle {
     const float* rope = nullptr;
     int* host_counts = nullptr;  // pinned: valid keys per batch item of a masked call
     int host_cap = 0;
+    DeviceInts lens;  // the _ragged entry points: the items' frame counts
     ~qa_cond_encoder() {
         if (host_counts) (void)hipHostFree(host_counts);
     }
@@ -177,8 +179,13 @@ int feed_forward_op(Ctx& c, const FeedForwardW& f, float* x, const CfTemps& t, i
     return linear_op(c, t.u, rows, f.l2h, x, epi(ACT_NONE, x));
 }
 
-// the ConformerEncoder in place on x [B, T, dim]
-int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mask, int B, int T) {
+// the ConformerEncoder in place on x [B, T, dim].  mask: the reference's key-padding mask (bytes [B, T], device) or null.  lens (device int
+// [B], null in every call without lengths; never together with mask): item b holds lens[b] of the T frames and comes
+// out as it would alone at that length - the keys behind are invisible (the byte image of the lengths takes the mask's place in the
+// attention and in masked_add), the convolution module's zero padding starts at lens[b], and the rows behind are zeros on entry (so that
+// whatever the caller left there, NaN included, never reaches a product with an attention weight of 0) and zeros on return.  The per-frame
+// stages stay rectangular: a GEMM or LayerNorm row depends on its own input row alone.
+int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mask, const int* lens, int B, int T) {
     const qa_cond_encoder_spec& sp = h->spec;
     const int d = sp.dim, H = sp.heads, hd = sp.dim_head, inner = H * hd;
     const int64_t rows = (int64_t)B * T;
@@ -188,6 +195,12 @@ int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mas
     t.u = c.arena.alloc<float>(rows * std::max(std::max(d * sp.ff_mult, 2 * d), 3 * inner));
     t.v = c.arena.alloc<float>(rows * std::max(inner, d));
     AttnArgs at = attn_packed_qkv(t.u, t.v, B, T, H, hd);
+    if (lens) {
+        unsigned char* image = c.arena.alloc<unsigned char>((size_t)rows);
+        QA_RUN(c, launch_len_mask(image, B, T, ClipLens{lens, 1}, c.stream));
+        QA_RUN(c, launch_lm_rows_zero_pad(x, 0, 1, B, T, d, lens, c.stream));
+        mask = image;
+    }
     at.kvalid = mask;
     for (int l = 0; l < sp.n_layers; ++l) {
         const ConformerLayerW& W = h->layers[l];
@@ -203,13 +216,14 @@ int encoder_graph(qa_cond_encoder* h, Ctx& c, float* x, const unsigned char* mas
         c.tap(lp + ".attn", t.hn, rows * d);
         QA_TRY(layernorm_op(c, x, W.cnw, W.cnb, t.hn, rows, d, 1e-5f));
         QA_TRY(linear_op(c, t.hn, rows, W.pw1, t.u));
-        QA_RUN(c, launch_glu_dwconv_bn_silu(t.u, W.dw, W.dwb, W.bns, W.bnt, t.v, B, T, d, c.stream));
+        QA_RUN(c, launch_glu_dwconv_bn_silu(t.u, W.dw, W.dwb, W.bns, W.bnt, t.v, B, T, d, c.stream, lens));
         QA_TRY(linear_op(c, t.v, rows, W.pw2, x, epi(ACT_NONE, x)));
         c.tap(lp + ".conv", x, rows * d);
         QA_TRY(feed_forward_op(c, W.ff2, x, t, rows, d));
         QA_TRY(layernorm_op(c, x, W.fnw, W.fnb, x, rows, d, 1e-5f));
         c.tap(lp + ".out", x, rows * d);
     }
+    if (lens) QA_RUN(c, launch_lm_rows_zero_pad(x, 0, 1, B, T, d, lens, c.stream));  // the last LayerNorm made non-zero rows out of zeros
     c.arena.release(mark);
     return QA_OK;
 }
@@ -249,6 +263,58 @@ int forward_checks(qa_cond_encoder* h, const char* fn, const void* x, const void
     return QA_OK;
 }
 
+// The length vector of a _ragged call (HOST int64 [B], 1 .. T frames each; null: none) -> *dev, the device copy the graph reads, or null
+// when the call is the rectangular one (no vector, or every entry equal to T).  Everything is checked before the first launch, on the host
+// alone: where a masked call reads its counters back and waits, a call with lengths does not.
+int upload_lengths(qa_cond_encoder* h, const char* fn, const int64_t* lengths, int64_t B, int64_t T, hipStream_t s, const int** dev) {
+    *dev = nullptr;
+    if (!lengths) return QA_OK;
+    QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
+    std::vector<int> v;
+    bool full = true;
+    const int64_t bad = check_row_lengths(lengths, B, 1, T, &v, &full);
+    QA_REQUIRE(bad < 0, "%s: lengths[%lld] = %lld is outside 1 .. T = %lld frames", fn, (long long)bad, (long long)lengths[bad], (long long)T);
+    return full ? QA_OK : h->lens.upload({&v}, s, dev);
+}
+
+// qa_conformer_forward(_ragged): at most one of mask and lengths
+int conformer_call(qa_cond_encoder* h, const char* fn, const float* x, const uint8_t* mask, const int64_t* lengths, int64_t B, int64_t T,
+                   float* out, void* stream) {
+    QA_TRY(forward_checks(h, fn, x, out, B, T, false));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_HIP(hipSetDevice(h->device));
+    const int* lens = nullptr;
+    QA_TRY(upload_lengths(h, fn, lengths, B, T, s, &lens));
+    if (mask) QA_TRY(check_mask(h, mask, (int)B, (int)T, s));
+    const int64_t n = B * T * h->spec.dim;
+    return run_planned(*h, stream, [&]() -> int {
+        // real pass only, more than a launch: the copy of the input the encoder then updates in place
+        if (!h->ctx.dry && out != x) QA_HIP(hipMemcpyAsync(out, x, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+        return encoder_graph(h, h->ctx, out, mask, lens, (int)B, (int)T);
+    });
+}
+
+int cond_encoder_call(qa_cond_encoder* h, const char* fn, const float* mel, const uint8_t* mask, const int64_t* lengths, int64_t B, int64_t T,
+                      float* out, void* stream) {
+    QA_TRY(forward_checks(h, fn, mel, out, B, T, true));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_HIP(hipSetDevice(h->device));
+    const int* lens = nullptr;
+    QA_TRY(upload_lengths(h, fn, lengths, B, T, s, &lens));
+    if (mask) QA_TRY(check_mask(h, mask, (int)B, (int)T, s));
+    const int64_t rows = B * T;
+    return run_planned(*h, stream, [&]() -> int {
+        Ctx& c = h->ctx;
+        float* x = c.arena.alloc<float>(rows * h->spec.dim);
+        QA_TRY(linear_op(c, mel, rows, h->in_layer, x));
+        QA_TRY(encoder_graph(h, c, x, mask, lens, (int)B, (int)T));
+        QA_TRY(linear_op(c, x, rows, h->out_layer, out));
+        // the biased Linear made non-zero rows out of the zeros behind an item's frames
+        if (lens) QA_RUN(c, launch_lm_rows_zero_pad(out, 0, 1, (int)B, (int)T, h->spec.hidden_out, lens, c.stream));
+        return QA_OK;
+    });
+}
+
 // ---------------------------------------------------------------- log-mel front
 
 struct LogMel {
@@ -257,6 +323,7 @@ struct LogMel {
     Ctx ctx;
     ConvW dft, fbank;
     int nb = 0, nbp = 0, kp = 0, hop = 0, win = 0, n_mels = 0;
+    DeviceInts lens{2};  // qa_logmel_ragged: the rows' samples and frames
     std::mutex mu;
 };
 typedef std::tuple<int, int, int, int, int, int, float, float> LogMelKey;
@@ -343,31 +410,20 @@ int qa_cond_encoder_create(qa_cond_encoder** out, const qa_cond_encoder_spec* sp
 void qa_cond_encoder_destroy(qa_cond_encoder* h) { destroy_handle(h); }
 
 int qa_conformer_forward(qa_cond_encoder* h, const float* x, const uint8_t* mask, int64_t B, int64_t T, float* out, void* stream) {
-    QA_TRY(forward_checks(h, "qa_conformer_forward", x, out, B, T, false));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_HIP(hipSetDevice(h->device));
-    if (mask) QA_TRY(check_mask(h, mask, (int)B, (int)T, s));
-    const int64_t n = B * T * h->spec.dim;
-    return run_planned(*h, stream, [&]() -> int {
-        // real pass only, more than a launch: the copy of the input the encoder then updates in place
-        if (!h->ctx.dry && out != x) QA_HIP(hipMemcpyAsync(out, x, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-        return encoder_graph(h, h->ctx, out, mask, (int)B, (int)T);
-    });
+    return conformer_call(h, "qa_conformer_forward", x, mask, nullptr, B, T, out, stream);
+}
+
+int qa_conformer_forward_ragged(qa_cond_encoder* h, const float* x, const int64_t* lengths, int64_t B, int64_t T, float* out, void* stream) {
+    return conformer_call(h, "qa_conformer_forward_ragged", x, nullptr, lengths, B, T, out, stream);
 }
 
 int qa_cond_encoder_forward(qa_cond_encoder* h, const float* mel, const uint8_t* mask, int64_t B, int64_t T, float* out, void* stream) {
-    QA_TRY(forward_checks(h, "qa_cond_encoder_forward", mel, out, B, T, true));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_HIP(hipSetDevice(h->device));
-    if (mask) QA_TRY(check_mask(h, mask, (int)B, (int)T, s));
-    const int64_t rows = B * T;
-    return run_planned(*h, stream, [&]() -> int {
-        Ctx& c = h->ctx;
-        float* x = c.arena.alloc<float>(rows * h->spec.dim);
-        QA_TRY(linear_op(c, mel, rows, h->in_layer, x));
-        QA_TRY(encoder_graph(h, c, x, mask, (int)B, (int)T));
-        return linear_op(c, x, rows, h->out_layer, out);
-    });
+    return cond_encoder_call(h, "qa_cond_encoder_forward", mel, mask, nullptr, B, T, out, stream);
+}
+
+int qa_cond_encoder_forward_ragged(qa_cond_encoder* h, const float* mel, const int64_t* lengths, int64_t B, int64_t T, float* out,
+                                   void* stream) {
+    return cond_encoder_call(h, "qa_cond_encoder_forward_ragged", mel, nullptr, lengths, B, T, out, stream);
 }
 
 int qa_cond_encoder_enable_taps(qa_cond_encoder* h, int on) { return taps_enable(h ? &h->ctx : nullptr, "qa_cond_encoder_enable_taps", on); }
@@ -378,20 +434,30 @@ int64_t qa_cond_encoder_tap(qa_cond_encoder* h, const char* name, float* dst, in
 
 int64_t qa_logmel_frames(int64_t n, int32_t hop_length) { return (n <= 0 || hop_length <= 0) ? (int64_t)QA_ERR_INVALID : (n + hop_length - 1) / hop_length; }
 
-int qa_logmel(const float* wav, int64_t B, int64_t n, int32_t n_fft, int32_t win_length, int32_t hop_length, int32_t n_mels, int32_t sample_rate,
-              float f_min, float f_max, float* out, void* stream) {
+// qa_logmel (lengths == nullptr) and qa_logmel_ragged.  Everything is checked before the first launch; a call whose rows all hold n samples
+// is the rectangular call as it is: nothing uploaded, the same launches.
+static int logmel_call(const char* fn, const float* wav, const int64_t* lengths, int64_t B, int64_t n, int32_t n_fft, int32_t win_length,
+                       int32_t hop_length, int32_t n_mels, int32_t sample_rate, float f_min, float f_max, float* out, void* stream) {
     if (!wav || !out) {
-        set_error("qa_logmel: null argument");
+        set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
     }
     QA_REQUIRE(hop_length >= 16 && hop_length % 16 == 0 && win_length == 2 * hop_length && n_fft >= win_length && (n_fft - win_length) % 2 == 0,
-               "qa_logmel: the framed-signal DFT needs win_length = 2 * hop_length, hop a multiple of 16, n_fft >= win_length (got n_fft %d, "
-               "win %d, hop %d)", n_fft, win_length, hop_length);
+               "%s: the framed-signal DFT needs win_length = 2 * hop_length, hop a multiple of 16, n_fft >= win_length (got n_fft %d, "
+               "win %d, hop %d)", fn, n_fft, win_length, hop_length);
     QA_REQUIRE(n_mels > 0 && n_mels % 4 == 0 && sample_rate > 0 && f_min >= 0.f && f_max > f_min && f_max <= sample_rate / 2,
-               "qa_logmel: n_mels %d (a multiple of 4), band %g - %g Hz at %d Hz", n_mels, f_min, f_max, sample_rate);
+               "%s: n_mels %d (a multiple of 4), band %g - %g Hz at %d Hz", fn, n_mels, f_min, f_max, sample_rate);
     const int64_t nf = (n + hop_length - 1) / hop_length;
-    QA_REQUIRE(B > 0 && B < 65536 && n > 0 && B * (nf + 1) * (int64_t)std::max(hop_length, n_fft + 8) < (1LL << 31), "qa_logmel: wav is [%lld, %lld]",
+    QA_REQUIRE(B > 0 && B < 65536 && n > 0 && B * (nf + 1) * (int64_t)std::max(hop_length, n_fft + 8) < (1LL << 31), "%s: wav is [%lld, %lld]", fn,
                (long long)B, (long long)n);
+    std::vector<int> samples, frames;
+    bool full = true;
+    if (lengths) {
+        QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
+        const int64_t bad = check_row_lengths(lengths, B, 1, n, &samples, &full);
+        QA_REQUIRE(bad < 0, "%s: lengths[%lld] = %lld is outside 1 .. n = %lld samples", fn, (long long)bad, (long long)lengths[bad], (long long)n);
+        for (int v : samples) frames.push_back((v + hop_length - 1) / hop_length);
+    }
     int device = 0;
     QA_HIP(hipGetDevice(&device));
     LogMel* m = nullptr;
@@ -409,19 +475,31 @@ int qa_logmel(const float* wav, int64_t B, int64_t n, int32_t n_fft, int32_t win
     std::lock_guard<std::mutex> lock(m->mu);
     Ctx& c = m->ctx;
     const int64_t rows = B * nf;
+    const int* lens[2] = {nullptr, nullptr};  // device: the rows' samples, the rows' frames
+    if (!full) QA_TRY(m->lens.upload({&samples, &frames}, static_cast<hipStream_t>(stream), lens));
     auto graph = [&]() -> int {
         float* P = c.arena.alloc<float>((size_t)B * (nf + 1) * m->hop);
         float* ri = c.arena.alloc<float>((size_t)rows * 2 * m->nbp);
         float* mag = c.arena.alloc<float>((size_t)rows * m->kp);
-        QA_RUN(c, launch_logmel_frames(wav, (int)B, n, (m->win - m->hop) / 2, (nf + 1) * m->hop, P, c.stream));
+        QA_RUN(c, launch_logmel_frames(wav, (int)B, n, (m->win - m->hop) / 2, (nf + 1) * m->hop, P, c.stream, lens[0]));
         QA_TRY(conv_op(c, P, m->hop, (int)B, (int)nf + 1, m->dft, ri, 2 * m->nbp, (int)nf, ConvOpt()));
         QA_RUN(c, launch_spec_mag(ri, m->nbp, m->nb, mag, m->kp, rows, c.stream));
         QA_TRY(linear_op(c, mag, rows, m->fbank, out));
-        QA_RUN(c, launch_log_eps(out, rows * m->n_mels, 1e-10f, c.stream));
+        QA_RUN(c, launch_log_eps(out, rows * m->n_mels, 1e-10f, c.stream, lens[1], (int)nf, m->n_mels));  // and the zeros behind a row's frames
         return QA_OK;
     };
     QA_TRY(plan(device, static_cast<hipStream_t>(stream), c, m->ws, graph));
     return graph();
+}
+
+int qa_logmel(const float* wav, int64_t B, int64_t n, int32_t n_fft, int32_t win_length, int32_t hop_length, int32_t n_mels, int32_t sample_rate,
+              float f_min, float f_max, float* out, void* stream) {
+    return logmel_call("qa_logmel", wav, nullptr, B, n, n_fft, win_length, hop_length, n_mels, sample_rate, f_min, f_max, out, stream);
+}
+
+int qa_logmel_ragged(const float* wav, const int64_t* lengths, int64_t B, int64_t n, int32_t n_fft, int32_t win_length, int32_t hop_length,
+                     int32_t n_mels, int32_t sample_rate, float f_min, float f_max, float* out, void* stream) {
+    return logmel_call("qa_logmel_ragged", wav, lengths, B, n, n_fft, win_length, hop_length, n_mels, sample_rate, f_min, f_max, out, stream);
 }
 
 }  // extern "C"

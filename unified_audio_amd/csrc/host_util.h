@@ -472,6 +472,17 @@ inline bool stream_capturing(hipStream_t s) {
     return false;
 }
 
+// A call that reads host state cannot be recorded into a caller's graph: a replay would run with what the capture read.  Refused, with the
+// reason.  CACHE_IS_HOST_STATE: length and batch of a cache (the session calls); LENGTHS_ARE_HOST_DATA: the length vectors of a call with
+// per-row lengths.
+constexpr const char* CACHE_IS_HOST_STATE = "the cache length is host state, a replayed graph would repeat the captured positions";
+constexpr const char* LENGTHS_ARE_HOST_DATA =
+    "the rows' lengths are host data read during the call, a replayed graph would repeat the captured lengths";
+inline int refuse_capture(const char* fn, hipStream_t s, const char* why) {
+    QA_REQUIRE(!stream_capturing(s), "%s: refused under a stream capture - %s", fn, why);
+    return QA_OK;
+}
+
 // ---------------------------------------------------------------- test taps (the qa_*_tap / qa_*_enable_taps entry points)
 
 inline int taps_enable(Ctx* c, const char* fn, int on) {

@@ -173,15 +173,17 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
 // scoring with per-row lengths.  ne_r / nm_r / T_r / lp_r / off_r: device int [B] of one group (launch_row_ints):
 // the row's enrollment frames, mixture frames, semantic ids, prompt positions and packed target-row offset
 // x [B, n, d] <- prompt + input embeddings left-aligned, zeros behind; tgt (packed) <- the targets.  table == nullptr: the prompt alone
+// task_vec == nullptr: CustomLlamaModel's prompt [mix_sos, mix_emb[b, :nm]] (mix_emb [B, Nm, d]: the condition embeddings) or none (mix_emb
+// null).  drop = 1 in the three launchers: a row's own last position is left out, Lt_b = G + T[b] + 1
 int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,
                              const float* mix_emb, int Ne, int Nm, const float* table, const long long* gids, int G, const long long* sids,
                              int T_max, int V, int goff, int soff, long long* tgt, const int* ne_r, const int* nm_r, const int* T_r,
-                             const int* off_r, int B, int d, hipStream_t s);
-// y (packed [sum Lt_b, d]) <- x[b, lp[b] .. lp[b] + Lt_b - 1, :], Lt_b = G + T[b] + 2 <= Lt_max
+                             const int* off_r, int B, int d, hipStream_t s, int drop = 0);
+// y (packed [sum Lt_b, d]) <- x[b, lp[b] .. lp[b] + Lt_b - 1, :], Lt_b = G + T[b] + 2 - drop <= Lt_max
 int launch_lm_score_gather(float* y, const float* x, int B, int n, int d, int G, int Lt_max, const int* lp_r, const int* T_r, const int* off_r,
-                           hipStream_t s);
+                           hipStream_t s, int drop = 0);
 int launch_lm_seq_reduce_rows(const float* row_kl, const int* row_ok, int B, int G, const int* T_r, const int* off_r, double* seq_sum,
-                              float* loss_seq, long long* correct_seq, hipStream_t s);
+                              float* loss_seq, long long* correct_seq, hipStream_t s, int drop = 0);
 int launch_lm_batch_reduce_rows(const double* seq_sum, const long long* correct_seq, int B, long long total, float* loss, float* acc,
                                 hipStream_t s);
 // one wave of independent row moves of a KV cache (qa_lm_cache_select; KvMoves: lm_session_rows.h), passed by value
@@ -236,12 +238,14 @@ int launch_code_usage(const long long* idx, long long n, int K, float* perplexit
 int launch_widen_i32(const int* src, long long* dst, long long n, hipStream_t s);
 
 // conformer_kernels.hip
+// the nullable last arguments are device int [B] of a call with per-row lengths: the items' frame counts (rows, frames
+// of the [., F, C] tensor), sample counts, or prompt offsets n_cond[b] - T; null: today's launch
 int launch_glu_dwconv_bn_silu(const float* u, const float* w31, const float* bias, const float* scale, const float* shift, float* y, int B,
-                              int T, int C, hipStream_t s);
+                              int T, int C, hipStream_t s, const int* rows = nullptr);
 int launch_masked_add(float* x, float* y, const unsigned char* valid, long long rows, int C, hipStream_t s);
 int launch_mask_count(const unsigned char* valid, int B, int T, int* counts, hipStream_t s);
-int launch_logmel_frames(const float* wav, int B, long long n, int pad, long long n_out, float* P, hipStream_t s);
-int launch_log_eps(float* x, long long n, float eps, hipStream_t s);
-int launch_cond_prompt(float* x, const float* sos, const float* cond, int B, int T, int d, hipStream_t s);
+int launch_logmel_frames(const float* wav, int B, long long n, int pad, long long n_out, float* P, hipStream_t s, const int* rows = nullptr);
+int launch_log_eps(float* x, long long n, float eps, hipStream_t s, const int* frames = nullptr, int F = 0, int C = 0);
+int launch_cond_prompt(float* x, const float* sos, const float* cond, int B, int T, int d, hipStream_t s, const int* off = nullptr);
 
 }  // namespace qa

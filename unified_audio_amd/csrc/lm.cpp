@@ -497,8 +497,8 @@ struct Chain {
 
 // The prompt of a call, as every entry point that builds one describes it.  cond_mode: CustomLlamaModel's [mix_sos, cond] (cond
 // [B, Tc, d], already in the LM's width) or nothing (Tc = 0); otherwise LLM_SFT's [task, (enroll_sos, enroll)?, mix_sos, mix] from
-// features the adapter still has to project.  ne_rows (HOST, [B]; ragged generate): row b's enrollment frames,
-// 1 .. Ne - the prompt is then laid out for the LONGEST possible row (Ne frames)
+// features the adapter still has to project.  ne_rows (HOST, [B]; ragged generate, DESIGN.md sections 23 and 37): row b's enrollment frames,
+// 1 .. Ne - or, in cond_mode, its condition frames, 1 .. Tc - the prompt is then laid out for the LONGEST possible row (Ne / Tc frames)
 struct Prompt {
     bool cond_mode;
     const float* cond; int Tc;
@@ -521,7 +521,8 @@ int prompt_len(const Prompt& p) { return p.cond_mode ? (p.Tc > 0 ? p.Tc + 1 : 0)
 int build_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix, float* eenr, float* out, int* off) {
     const int d = lm->spec.hidden, F = lm->spec.feats_dim;
     if (p.cond_mode) {
-        if (p.Tc > 0) QA_RUN(c, launch_cond_prompt(out, lm->mix_sos, p.cond + (size_t)b0 * p.Tc * d, gb, p.Tc, d, c.stream));
+        if (p.ne_rows) QA_RUN(c, launch_lm_offsets(off, p.ne_rows + b0, p.Tc, gb, c.stream));
+        if (p.Tc > 0) QA_RUN(c, launch_cond_prompt(out, lm->mix_sos, p.cond + (size_t)b0 * p.Tc * d, gb, p.Tc, d, c.stream, off));
         return QA_OK;
     }
     QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
@@ -795,12 +796,14 @@ int write_score_ints(int* dst, const ScoreRows& R, const ScoreGroup& g, hipStrea
 // laid out at its OWN longest row; one assembly pass writes prompt, input embeddings and the packed targets; the body runs with the rows'
 // counts (a query block wholly behind a row's length exits at once, K / V behind it are not written); and the tail - norm, head, row loss -
 // runs over the PACKED target rows alone, so no padded row reaches the full-vocabulary head.
+// cond_mode (qa_lm_score_cond_ragged): no adapter - the condition embeddings are the prompt's frames as they are - and
+// a row's own last position dropped.
 int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, V = vocab_of(sp), F = sp.feats_dim;
     const Prompt& p = a.p;
     const ScoreRows& R = *a.rows;
-    const int GB = std::min(a.B, LM_MAX_ROWS);
+    const int GB = std::min(a.B, LM_MAX_ROWS), drop = p.cond_mode ? 1 : 0;
     const int64_t prow = R.body_rows_max, trow = R.packed_rows_max;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(knob(K_LM_SCORE_ROWS), trow));
     LMBuffers b{};
@@ -823,14 +826,20 @@ int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
         const int *ne_r = ints + SR_NE * gb, *nm_r = ints + SR_NM * gb, *T_r = ints + SR_T * gb, *off_r = ints + SR_OFF * gb,
                   *lp_r = ints + SR_LP * gb, *L_r = ints + SR_L * gb, *zero_r = ints + SR_ZERO * gb;
         QA_TRY(write_score_ints(ints, R, g, c.stream));
-        // the adapters run over the padding frames too: a GEMM row depends on its own input row alone, and those outputs are never copied
-        QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
-        if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
-        QA_TRY(launch_lm_score_assemble(b.x, n, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, p.Ne,
-                                        p.Nm, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T, a.T, V, 3,
-                                        3 + sp.global_size, tgt, ne_r, nm_r, T_r, off_r, gb, d, c.stream));
+        if (p.cond_mode) {
+            QA_TRY(launch_lm_score_assemble(b.x, n, nullptr, nullptr, nullptr, lm->mix_sos, p.cond ? p.cond + (size_t)b0 * p.Tc * d : nullptr, 0, p.Tc,
+                                            lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T, a.T, V, 3,
+                                            3 + sp.global_size, tgt, nullptr, nm_r, T_r, off_r, gb, d, c.stream, drop));
+        } else {
+            // the adapters run over the padding frames too: a GEMM row depends on its own input row alone, and those outputs are never copied
+            QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
+            if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
+            QA_TRY(launch_lm_score_assemble(b.x, n, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix,
+                                            p.Ne, p.Nm, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T, a.T, V, 3,
+                                            3 + sp.global_size, tgt, ne_r, nm_r, T_r, off_r, gb, d, c.stream));
+        }
         QA_TRY(lm_body(lm, c, b, gb, n, 0, n, false, true, nullptr, zero_r, L_r));
-        QA_TRY(launch_lm_score_gather(b.att, b.x, gb, n, d, a.G, g.Lt_max, lp_r, T_r, off_r, c.stream));
+        QA_TRY(launch_lm_score_gather(b.att, b.x, gb, n, d, a.G, g.Lt_max, lp_r, T_r, off_r, c.stream, drop));
         const int64_t rows = g.rows;
         QA_TRY(launch_rmsnorm(b.att, lm->ones, b.hn, rows, d, sp.rms_eps, c.stream));
         for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
@@ -840,7 +849,7 @@ int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
             if (tap)
                 QA_HIP(hipMemcpyAsync(tap + ((size_t)g.row0 + r0) * V, logits, sizeof(float) * nr * V, hipMemcpyDeviceToDevice, c.stream));
         }
-        QA_TRY(launch_lm_seq_reduce_rows(row_kl, row_ok, gb, a.G, T_r, off_r, seq_sum + b0, a.loss_seq + b0, a.correct_seq + b0, c.stream));
+        QA_TRY(launch_lm_seq_reduce_rows(row_kl, row_ok, gb, a.G, T_r, off_r, seq_sum + b0, a.loss_seq + b0, a.correct_seq + b0, c.stream, drop));
     }
     return launch_lm_batch_reduce_rows(seq_sum, a.correct_seq, a.B, R.total_rows, a.loss, a.acc, c.stream);
 }
@@ -863,22 +872,15 @@ int ensure_taps(qa_lm* lm, int64_t B, int G, int S, void* stream) {
 
 // ---- sessions: qa_lm_forward over a caller-held qa_lm_cache (CustomLlamaModel.llm_forward, llm.py:150-227)
 
-// A call that reads host state cannot be recorded into a caller's graph: a replay would run with what the capture read.  Refused, with the
-// reason.  CACHE_IS_HOST_STATE: length and batch of a cache (the session calls); LENGTHS_ARE_HOST_DATA: the length vectors of a ragged
-// score / prompt call.
-const char* const CACHE_IS_HOST_STATE = "the cache length is host state, a replayed graph would repeat the captured positions";
-const char* const LENGTHS_ARE_HOST_DATA =
-    "the rows' lengths are host data read during the call, a replayed graph would repeat the captured lengths";
-int refuse_capture(const char* fn, hipStream_t s, const char* why) {
-    QA_REQUIRE(!stream_capturing(s), "%s: refused under a stream capture - %s", fn, why);
-    return QA_OK;
-}
-
 // The refusals of the length vectors of qa_lm_score_ragged / qa_lm_prompt_ragged as the library's messages (lm_score_rows.h)
 int score_rows_refusal(const char* fn, ScoreRowsFault f, const ScoreRowsShape& s, int64_t row, int64_t value) {
     QA_REQUIRE(f != SCR_ENROLL_WITHOUT, "%s: n_enroll given (n_enroll[0] = %lld) without an enrollment (enroll_feats is NULL)", fn, (long long)value);
     QA_REQUIRE(f != SCR_ENROLL_RANGE, "%s: n_enroll[%lld] = %lld is outside 1 .. n_enroll_max = %lld", fn, (long long)row, (long long)value,
                (long long)s.ne_max);
+    QA_REQUIRE(f != SCR_COND_WITHOUT, "%s: n_cond given (n_cond[0] = %lld) without a condition (cond_embeds is NULL or T_max = 0)", fn,
+               (long long)value);
+    QA_REQUIRE(f != SCR_MIX_RANGE || !s.cond_form, "%s: n_cond[%lld] = %lld is outside 1 .. T_max = %lld", fn, (long long)row, (long long)value,
+               (long long)s.nm_max);
     QA_REQUIRE(f != SCR_MIX_RANGE, "%s: n_mix[%lld] = %lld is outside 1 .. n_mix_max = %lld", fn, (long long)row, (long long)value,
                (long long)s.nm_max);
     QA_REQUIRE(f != SCR_SEMANTIC_RANGE, "%s: n_semantic[%lld] = %lld is outside 0 .. semantic_length_max = %lld", fn, (long long)row,
@@ -1328,9 +1330,10 @@ static GenArgs gen_args(int64_t B, int32_t global_length, int32_t semantic_lengt
 
 // ragged (qa_lm_generate_ragged*): a.p.Ne is n_enroll_max and ne_rows64 the caller's HOST vector [B] of the rows' own frame counts, which is
 // checked here and handed on as a.p.ne_rows
+// ragged in cond_mode (qa_lm_generate_cond_ragged*): a.p.Tc is T_max and ne_rows64 the rows' condition frames, NULL allowed (the rectangular call)
 static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = false, const int64_t* ne_rows64 = nullptr) {
     Prompt& p = a.p;
-    const char* fn = p.cond_mode ? "qa_lm_generate_cond" : ragged ? "qa_lm_generate_ragged" : "qa_lm_generate";
+    const char* fn = p.cond_mode ? (ragged ? "qa_lm_generate_cond_ragged" : "qa_lm_generate_cond") : ragged ? "qa_lm_generate_ragged" : "qa_lm_generate";
     if (!lm || (!p.cond_mode && !p.mix) || !a.gids || !a.sids) {
         set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
@@ -1339,12 +1342,23 @@ static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = fa
     QA_REQUIRE(p.cond_mode || (p.task >= 0 && p.task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, p.task);
     QA_REQUIRE(a.B > 0 && (p.cond_mode || p.Nm > 0) && a.G >= 0 && a.S >= 0, "%s: bad shape", fn);
     QA_REQUIRE(!p.cond_mode || (p.Tc >= 0 && p.Tc < LM_MAX_POS && (p.cond != nullptr) == (p.Tc > 0) && a.G + a.S > 0),
-               "qa_lm_generate_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %d); at least one step", p.Tc);
+               "%s: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %d); at least one step", fn, p.Tc);
     QA_REQUIRE(!p.enroll || p.Ne > 0, "%s: enrollment given with no frames", fn);
     QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "%s: temperature must be in (0, 1] (llm.py:278)", fn);
     QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "%s: bad top_k / top_p", fn);
     std::vector<int> ne_host;  // every check of a ragged call comes before the first launch: a refused call has launched nothing
-    if (ragged) {
+    if (ragged && p.cond_mode && ne_rows64) {
+        QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
+        QA_REQUIRE(p.cond && p.Tc > 0, "%s: n_cond given (n_cond[0] = %lld) without a condition (cond_embeds is NULL or T_max = 0)", fn,
+                   (long long)ne_rows64[0]);
+        const long long total = (long long)prompt_len(p) + a.G + 1 + a.S;
+        QA_REQUIRE(total <= LM_MAX_POS, "%s: %lld positions (prompt 1 + T_max %d, + %d + 1 + %d) exceed max_position_embeddings %d", fn, total,
+                   p.Tc, a.G, a.S, LM_MAX_POS);
+        bool full = true;
+        const int64_t bad = check_row_lengths(ne_rows64, a.B, 1, p.Tc, &ne_host, &full);
+        QA_REQUIRE(bad < 0, "%s: n_cond[%d] = %lld is outside 1 .. T_max = %d", fn, (int)bad, (long long)ne_rows64[bad], p.Tc);
+        if (!full) p.ne_rows = ne_host.data();  // every row full: the rectangular call, the same launches
+    } else if (ragged && !p.cond_mode) {
         QA_REQUIRE(p.enroll && ne_rows64, "%s: per-row enrollment lengths need enroll_feats [B, n_enroll_max, feats_dim] and n_enroll [B]", fn);
         const long long total = (long long)prompt_len(p) + a.G + 1 + a.S;
         QA_REQUIRE(total <= LM_MAX_POS,
@@ -1398,6 +1412,22 @@ int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, i
     return lm_generate_impl(lm, a, stream);
 }
 
+int qa_lm_generate_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, int32_t global_length,
+                               int32_t semantic_length, float temperature, int32_t top_k, float top_p, int64_t* global_ids,
+                               int64_t* semantic_ids, void* stream) {
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
+    a.p = cond_prompt(cond_embeds, T_max);
+    return lm_generate_impl(lm, a, stream, true, n_cond);
+}
+
+int qa_lm_generate_cond_ragged_sampled(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B,
+                                       int32_t global_length, int32_t semantic_length, float temperature, int32_t top_k, float top_p,
+                                       uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
+    a.p = cond_prompt(cond_embeds, T_max);
+    return lm_generate_impl(lm, a, stream, true, n_cond);
+}
+
 int qa_lm_generate_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
                           const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                           int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
@@ -1419,7 +1449,7 @@ static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int
                          const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length,
                          double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream,
                          bool cond_mode, const float* cond, int64_t Tc, const ScoreRows* rows = nullptr) {
-    const char* fn = cond_mode ? "qa_lm_score_cond" : rows ? "qa_lm_score_ragged" : "qa_lm_score";
+    const char* fn = cond_mode ? (rows ? "qa_lm_score_cond_ragged" : "qa_lm_score_cond") : rows ? "qa_lm_score_ragged" : "qa_lm_score";
     if (!lm || (!cond_mode && !mix_feats) || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
         (semantic_length > 0 && !semantic_ids)) {
         set_error("%s: null argument", fn);
@@ -1511,6 +1541,38 @@ int qa_lm_score_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, 
                      int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
     return lm_score_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_ids, global_length, semantic_ids, semantic_length, label_smoothing,
                          loss_per_seq, correct_per_seq, loss, acc, stream, true, cond_embeds, T);
+}
+
+int qa_lm_score_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, const int64_t* global_ids,
+                            int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length_max, const int64_t* n_semantic,
+                            double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
+    const char* fn = "qa_lm_score_cond_ragged";
+    auto rectangular = [&] {
+        return qa_lm_score_cond(lm, cond_embeds, T_max, B, global_ids, global_length, semantic_ids, semantic_length_max, label_smoothing,
+                                loss_per_seq, correct_per_seq, loss, acc, stream);
+    };
+    if (!n_cond && !n_semantic) return rectangular();  // every row at full width
+    if (!lm || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
+        (semantic_length_max > 0 && !semantic_ids)) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    // every check comes before the first launch: a refused call has launched nothing and leaves the handle as it was
+    QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
+    QA_REQUIRE(B > 0 && B <= (1 << 24) && T_max >= 0 && T_max < LM_MAX_POS && (cond_embeds != nullptr) == (T_max > 0) && global_length >= 0 &&
+                   global_length <= LM_MAX_POS && semantic_length_max >= 0 && semantic_length_max <= LM_MAX_POS,
+               "%s: cond_embeds [B, T_max, hidden] with T_max > 0, or NULL with T_max = 0 (got T_max = %lld); bad shape otherwise", fn,
+               (long long)T_max);
+    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, label_smoothing);
+    ScoreRowsShape shape;
+    shape.B = B; shape.cond_form = true; shape.nm_max = T_max; shape.T_max = semantic_length_max; shape.G = global_length;
+    shape.group_rows = LM_MAX_ROWS; shape.max_pos = LM_MAX_POS;
+    ScoreRows R;
+    int64_t row = 0, value = 0;
+    QA_TRY(score_rows_refusal(fn, plan_score_rows(nullptr, n_cond, n_semantic, shape, &R, &row, &value), shape, row, value));
+    if (R.uniform) return rectangular();  // the rectangular call: its launches, its bits
+    return lm_score_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_ids, global_length, semantic_ids, semantic_length_max, label_smoothing,
+                         loss_per_seq, correct_per_seq, loss, acc, stream, true, cond_embeds, T_max, &R);
 }
 
 int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,

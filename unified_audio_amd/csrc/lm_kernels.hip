@@ -463,6 +463,9 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
 // left-aligned over L_b = Lp_b + Lt_b positions, exact zeros behind; target_ids_b -> tgt[off[b] ..] (PACKED: Lt_b = G + T[b] + 2 entries).
 // The eos target sits right behind the row's own last semantic id.  Frames and ids at or behind a row's counts are never read.
 // table == nullptr: a prompt-only pass (no target positions, gids / sids / tgt unused).
+// task_vec == nullptr: CustomLlamaModel's form - the prompt is [mix_sos, mix_emb[b, :nm]] with mix_emb the condition
+// embeddings, already in the LM's width, or nothing at all (mix_emb null too).  drop = 1 (that model's forward, llm.py:126-127): the last
+// position of the row's OWN stream is left out, Lt_b = G + T[b] + 1, and with it the eos target.
 __global__ __launch_bounds__(256) void lm_score_assemble_kernel(float* __restrict__ x, int n, const float* __restrict__ task_vec,
                                                                 const float* __restrict__ enroll_sos, const float* __restrict__ enroll_emb,
                                                                 const float* __restrict__ mix_sos, const float* __restrict__ mix_emb, int Ne,
@@ -470,19 +473,21 @@ __global__ __launch_bounds__(256) void lm_score_assemble_kernel(float* __restric
                                                                 int G, const long long* __restrict__ sids, int T_max, int V, int goff, int soff,
                                                                 long long* __restrict__ tgt, const int* __restrict__ ne_r,
                                                                 const int* __restrict__ nm_r, const int* __restrict__ T_r,
-                                                                const int* __restrict__ off_r, int B, int d) {
+                                                                const int* __restrict__ off_r, int B, int d, int drop) {
     const int d4 = d >> 2;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * n * d4) return;
     const int c = (int)(gid % d4) * 4;
     const int pos = (int)((gid / d4) % n);
     const int b = (int)(gid / ((long long)d4 * n));
-    const int ne = enroll_emb ? ne_r[b] : 0, nm = nm_r[b];
-    const int Lp = 1 + (enroll_emb ? 1 + ne : 0) + 1 + nm;
+    const int ne = enroll_emb ? ne_r[b] : 0, nm = mix_emb ? nm_r[b] : 0;
+    const int Lp = task_vec ? 1 + (enroll_emb ? 1 + ne : 0) + 1 + nm : (mix_emb ? 1 + nm : 0);
     const float* src = nullptr;
     if (pos < Lp) {
         int p = pos;
-        if (p == 0) {
+        if (!task_vec) {
+            src = (p == 0) ? mix_sos : mix_emb + ((long long)b * Nm + (p - 1)) * d;  // p - 1 < nm: pos < Lp
+        } else if (p == 0) {
             src = task_vec;
         } else {
             p -= 1;
@@ -500,7 +505,7 @@ __global__ __launch_bounds__(256) void lm_score_assemble_kernel(float* __restric
         }
     } else if (table) {
         const int T = T_r[b], t = pos - Lp;
-        if (t < G + T + 2) {
+        if (t < G + T + 2 - drop) {
             long long in_id, tg;
             if (t == 0) in_id = 0;
             else if (t <= G) in_id = gids[(long long)b * G + t - 1] + goff;
@@ -521,48 +526,49 @@ __global__ __launch_bounds__(256) void lm_score_assemble_kernel(float* __restric
 int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,
                              const float* mix_emb, int Ne, int Nm, const float* table, const long long* gids, int G, const long long* sids,
                              int T_max, int V, int goff, int soff, long long* tgt, const int* ne_r, const int* nm_r, const int* T_r,
-                             const int* off_r, int B, int d, hipStream_t s) {
-    QA_REQUIRE(d % 4 == 0 && n >= 1 && B >= 1 && nm_r && (!enroll_emb || ne_r) && (!table || (tgt && T_r && off_r)), "lm_score_assemble: bad launch");
+                             const int* off_r, int B, int d, hipStream_t s, int drop) {
+    QA_REQUIRE(d % 4 == 0 && n >= 1 && B >= 1 && (!mix_emb || nm_r) && (task_vec || !enroll_emb) && (task_vec || mix_emb || table) &&
+                   (!enroll_emb || ne_r) && (!table || (tgt && T_r && off_r)) && (drop == 0 || drop == 1), "lm_score_assemble: bad launch");
     const long long total = (long long)B * n * (d / 4);
     hipLaunchKernelGGL(lm_score_assemble_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, n, task_vec, enroll_sos, enroll_emb,
-                       mix_sos, mix_emb, Ne, Nm, table, gids, G, sids, T_max, V, goff, soff, tgt, ne_r, nm_r, T_r, off_r, B, d);
+                       mix_sos, mix_emb, Ne, Nm, table, gids, G, sids, T_max, V, goff, soff, tgt, ne_r, nm_r, T_r, off_r, B, d, drop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
 
-// The packed tail: y [sum Lt_b, d] <- each row's last Lt_b = G + T[b] + 2 live positions x[b, lp[b] + t, :], sequences in order.  Grid: x
+// The packed tail: y [sum Lt_b, d] <- each row's last Lt_b = G + T[b] + 2 - drop live positions x[b, lp[b] + t, :], sequences in order.  Grid: x
 // covers Lt_max rows of one sequence, y = sequence.
 __global__ __launch_bounds__(256) void lm_score_gather_kernel(float4* __restrict__ y, const float4* __restrict__ x, int n, int d4, int G,
                                                               int Lt_max, const int* __restrict__ lp_r, const int* __restrict__ T_r,
-                                                              const int* __restrict__ off_r) {
+                                                              const int* __restrict__ off_r, int drop) {
     const int b = blockIdx.y;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)Lt_max * d4) return;
     const int t = (int)(gid / d4), c = (int)(gid % d4);
-    if (t >= G + T_r[b] + 2) return;
+    if (t >= G + T_r[b] + 2 - drop) return;
     y[((long long)off_r[b] + t) * d4 + c] = x[((long long)b * n + lp_r[b] + t) * d4 + c];
 }
 
 int launch_lm_score_gather(float* y, const float* x, int B, int n, int d, int G, int Lt_max, const int* lp_r, const int* T_r, const int* off_r,
-                           hipStream_t s) {
+                           hipStream_t s, int drop) {
     QA_REQUIRE(d % 4 == 0 && B >= 1 && B <= 65535 && Lt_max >= 1 && lp_r && T_r && off_r, "lm_score_gather: bad launch");
     const long long total = (long long)Lt_max * (d / 4);
     hipLaunchKernelGGL(lm_score_gather_kernel, dim3((unsigned)ceil_div(total, 256), (unsigned)B), dim3(256), 0, s, reinterpret_cast<float4*>(y),
-                       reinterpret_cast<const float4*>(x), n, d / 4, G, Lt_max, lp_r, T_r, off_r);
+                       reinterpret_cast<const float4*>(x), n, d / 4, G, Lt_max, lp_r, T_r, off_r, drop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
 
-// lm_seq_reduce_kernel over packed rows: sequence b owns rows off[b] .. off[b] + Lt_b - 1, Lt_b = G + T[b] + 2.  The same thread
+// lm_seq_reduce_kernel over packed rows: sequence b owns rows off[b] .. off[b] + Lt_b - 1, Lt_b = G + T[b] + 2 - drop.  The same thread
 // ownership and the same fixed LDS tree in double, so a sequence's values equal the rectangular kernel's on its own rows.
 __global__ __launch_bounds__(256) void lm_seq_reduce_rows_kernel(const float* __restrict__ row_kl, const int* __restrict__ row_ok, int G,
                                                                  const int* __restrict__ T_r, const int* __restrict__ off_r,
                                                                  double* __restrict__ seq_sum, float* __restrict__ loss_seq,
-                                                                 long long* __restrict__ correct_seq) {
+                                                                 long long* __restrict__ correct_seq, int drop) {
     __shared__ double s_kl[256];
     __shared__ long long s_ok[256];
     const int tid = threadIdx.x, b = blockIdx.x;
-    const int Lt = G + T_r[b] + 2;
+    const int Lt = G + T_r[b] + 2 - drop;
     const long long base = off_r[b];
     double kl = 0.0;
     long long ok = 0;
@@ -588,10 +594,10 @@ __global__ __launch_bounds__(256) void lm_seq_reduce_rows_kernel(const float* __
 }
 
 int launch_lm_seq_reduce_rows(const float* row_kl, const int* row_ok, int B, int G, const int* T_r, const int* off_r, double* seq_sum,
-                              float* loss_seq, long long* correct_seq, hipStream_t s) {
+                              float* loss_seq, long long* correct_seq, hipStream_t s, int drop) {
     QA_REQUIRE(B >= 1 && T_r && off_r, "lm_seq_reduce_rows: bad launch");
     hipLaunchKernelGGL(lm_seq_reduce_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, row_kl, row_ok, G, T_r, off_r, seq_sum, loss_seq,
-                       correct_seq);
+                       correct_seq, drop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

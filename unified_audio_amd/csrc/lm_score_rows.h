@@ -18,6 +18,7 @@ enum ScoreRowsFault {
     SCR_MIX_RANGE = 3,       // n_mix[b] outside 1 .. n_mix_max
     SCR_SEMANTIC_RANGE = 4,  // n_semantic[b] outside 0 .. semantic_length_max
     SCR_TOO_LONG = 5,        // the row's prompt + target positions exceed max_pos
+    SCR_COND_WITHOUT = 6,    // condition form: n_cond given, but the call has no condition
 };
 
 // what a call looks like before its vectors are read: the maxima are the strides of the caller's tensors
@@ -29,6 +30,10 @@ struct ScoreRowsShape {
     bool targets = true;  // false: a prompt-only call (qa_lm_prompt_ragged) - no target rows, T is ignored
     int group_rows = 64;  // sequences per pass of the body (LM_MAX_ROWS)
     int max_pos = 4096;   // max_position_embeddings
+    // CustomLlamaModel.forward (qa_lm_score_cond_ragged): the prompt is [mix_sos, cond[b, :n]] - n_mix / nm_max carry the
+    // rows' condition frames and T_max their width - or NOTHING (nm_max = 0), there is no enrollment, and the last position of a row's OWN
+    // stream is dropped: Lt = G + T + 1, no eos target
+    bool cond_form = false;
 };
 
 // sequences [b0, b0 + gb) go through the body together, laid out at the group's OWN longest row
@@ -62,6 +67,11 @@ inline ScoreRowsFault plan_score_rows(const int64_t* n_enroll, const int64_t* n_
         *value = s.B > 0 ? n_enroll[0] : 0;
         return SCR_ENROLL_WITHOUT;
     }
+    const bool no_cond = s.cond_form && s.nm_max <= 0;
+    if (n_mix && no_cond) {
+        *value = s.B > 0 ? n_mix[0] : 0;
+        return SCR_COND_WITHOUT;
+    }
     const size_t B = (size_t)std::max<int64_t>(s.B, 0);
     ScoreRows r;
     r.ne.assign(B, 0);
@@ -71,17 +81,17 @@ inline ScoreRowsFault plan_score_rows(const int64_t* n_enroll, const int64_t* n_
     r.Lt.assign(B, 0);
     r.L.assign(B, 0);
     r.off.assign(B, 0);
-    r.Lp_max = (int)(1 + (s.has_enroll ? 1 + s.ne_max : 0) + 1 + s.nm_max);
+    r.Lp_max = s.cond_form ? (int)(no_cond ? 0 : 1 + s.nm_max) : (int)(1 + (s.has_enroll ? 1 + s.ne_max : 0) + 1 + s.nm_max);
     for (size_t b = 0; b < B; ++b) {
         *row = (int64_t)b;
         const int64_t ne = s.has_enroll ? (n_enroll ? n_enroll[b] : s.ne_max) : 0;
-        const int64_t nm = n_mix ? n_mix[b] : s.nm_max;
+        const int64_t nm = no_cond ? 0 : n_mix ? n_mix[b] : s.nm_max;
         const int64_t T = s.targets ? (n_semantic ? n_semantic[b] : s.T_max) : 0;
         if (s.has_enroll && (ne < 1 || ne > s.ne_max)) {
             *value = ne;
             return SCR_ENROLL_RANGE;
         }
-        if (nm < 1 || nm > s.nm_max) {
+        if (!no_cond && (nm < 1 || nm > s.nm_max)) {
             *value = nm;
             return SCR_MIX_RANGE;
         }
@@ -90,8 +100,8 @@ inline ScoreRowsFault plan_score_rows(const int64_t* n_enroll, const int64_t* n_
             return SCR_SEMANTIC_RANGE;
         }
         // every term is bounded by its checked maximum, so the sum cannot overflow once the maxima are sane (lm.cpp checks them)
-        const int64_t Lp = 1 + (s.has_enroll ? 1 + ne : 0) + 1 + nm;
-        const int64_t Lt = s.targets ? (int64_t)s.G + T + 2 : 0;
+        const int64_t Lp = s.cond_form ? (no_cond ? 0 : 1 + nm) : 1 + (s.has_enroll ? 1 + ne : 0) + 1 + nm;
+        const int64_t Lt = s.targets ? (int64_t)s.G + T + (s.cond_form ? 1 : 2) : 0;
         if (Lp + Lt > s.max_pos) {
             *value = Lp + Lt;
             return SCR_TOO_LONG;

@@ -253,12 +253,7 @@ class LLM_SFT:
     @staticmethod
     def _lengths(name: str, lengths, B: int):
         """A per-row length argument (None, or B ints as a list / tensor) as (list or None, HOST int64 array or None)."""
-        if lengths is None:
-            return None, None
-        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(lens) != B:
-            raise _lib.QuarkAudioError(-1, f"{name} has {len(lens)} entries for a batch of {B}")
-        return lens, (C.c_int64 * max(B, 1))(*lens)  # host vector: the library reads it during the call
+        return _lib.host_lengths(name, lengths, B)
 
     @torch.no_grad()
     def build_prompt(self, task_name: str, enroll_feats: Optional[torch.Tensor], mix_feats: torch.Tensor, *, enroll_lengths=None,
@@ -539,24 +534,44 @@ class CustomLlamaModel:
         enrollment / adapter tensors in those shapes): its generate / forward share weights, workspace and captured steps with this model."""
         return self._lm
 
-    def encode_condition(self, cond: torch.Tensor) -> torch.Tensor:
-        """cond [B, T, cond_dim] -> the prompt embeddings [B, T, hidden_size] (llm.py:130-132)"""
+    def encode_condition(self, cond: torch.Tensor, lengths=None) -> torch.Tensor:
+        """cond [B, T, cond_dim] -> the prompt embeddings [B, T, hidden_size] (llm.py:130-132).  lengths (B frame counts, None: every row
+        at T): row b is encoded as cond[b:b+1, :lengths[b]] alone would be, with exact zeros behind (ConditionEncoder.forward)."""
         if not self._has_cond:
             raise _lib.QuarkAudioError(-3, "CustomLlamaModel: the checkpoint had no cond_* weights, the condition path cannot run")
-        return self._cond(cond)
+        return self._cond(cond, lengths=lengths)
 
     @torch.no_grad()
     def generate(self, cond: Optional[torch.Tensor] = None, global_length: int = 32, semantic_length: int = 150, temperature: float = 0.8,
-                 top_k: int = 50, top_p: float = 0.95, do_sample: bool = True, *, batch_size: int = 1):
+                 top_k: int = 50, top_p: float = 0.95, do_sample: bool = True, *, batch_size: int = 1, cond_lengths=None):
         """llm.py:291-374 -> (global_ids [B, global_length], semantic_ids [B, semantic_length]) int64, offsets subtracted.  Sampling as
-        LLM_SFT.generate: Philox draws seeded from torch's global generator."""
+        LLM_SFT.generate: Philox draws seeded from torch's global generator.
+
+        cond_lengths (keyword only; B frame counts, None: every row at T): row b is generated as generate(cond[b:b+1, :cond_lengths[b]])
+        would generate it alone - the condition encoder and the LM both run with the rows' lengths, in one pass each
+        (qa_cond_encoder_forward_ragged, qa_lm_generate_cond_ragged).  global_length and semantic_length stay common
+        to the batch."""
         lm = self._lm
         if not lm._handle.value:
             raise _lib.QuarkAudioError(-3, "CustomLlamaModel has no weights: call load_state_dict first")
         emb, T, B = None, 0, int(batch_size)
         if cond is not None:
-            emb = self.encode_condition(cond)
+            emb = self.encode_condition(cond, cond_lengths)
             B, T = emb.shape[0], emb.shape[1]
+        if cond_lengths is not None:
+            _, nc_arr = _lib.host_lengths("generate: cond_lengths", cond_lengths, B)
+            gids = torch.empty((B, global_length), dtype=torch.int64, device=self.device)
+            sids = torch.empty((B, semantic_length), dtype=torch.int64, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            ptr = emb.data_ptr() if emb is not None else None
+            if do_sample:
+                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+                _lib.check(lm._lib.qa_lm_generate_cond_ragged_sampled(lm._handle, ptr, T, nc_arr, B, global_length, semantic_length, temperature,
+                                                                      top_k, top_p, seed, gids.data_ptr(), sids.data_ptr(), stream))
+            else:
+                _lib.check(lm._lib.qa_lm_generate_cond_ragged(lm._handle, ptr, T, nc_arr, B, global_length, semantic_length, temperature, top_k,
+                                                              top_p, gids.data_ptr(), sids.data_ptr(), stream))
+            return gids, sids
         gids = torch.empty((B, global_length), dtype=torch.int64, device=self.device)
         sids = torch.empty((B, semantic_length), dtype=torch.int64, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -591,22 +606,35 @@ class CustomLlamaModel:
         Lp_b = 1 + (1 + enroll_lengths[b]) + 1 + mix_lengths[b] positions (2 + mix_lengths[b] without an enrollment), zeros behind."""
         return self._lm.build_prompt(task_name, enroll_feats, mix_feats, enroll_lengths=enroll_lengths, mix_lengths=mix_lengths)
 
-    def _score(self, global_ids, semantic_ids, cond):
+    def _score(self, global_ids, semantic_ids, cond, cond_lengths=None, semantic_lengths=None):
+        """The last entry is Lt: G + T + 1, or with per-row lengths Lt_b = G + semantic_lengths[b] + 1 as an int64 [B] device tensor."""
         lm = self._lm
         if not lm._handle.value:
             raise _lib.QuarkAudioError(-3, "CustomLlamaModel has no weights: call load_state_dict first")
         B = int(global_ids.shape[0])
-        g = global_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()
-        sids = semantic_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()
+        ragged = cond_lengths is not None or semantic_lengths is not None
+        g = global_ids.to(device=self.device, dtype=torch.int64)
+        sids = semantic_ids.to(device=self.device, dtype=torch.int64)
+        if ragged:  # a width of 0 (no id at all) is a valid shape here
+            g, sids = g.reshape(B, g.numel() // B).contiguous(), sids.reshape(B, sids.numel() // B).contiguous()
+        else:
+            g, sids = g.reshape(B, -1).contiguous(), sids.reshape(B, -1).contiguous()
         G, T = g.shape[1], sids.shape[1]
         emb, Tc = None, 0
         if cond is not None:
-            emb = self.encode_condition(cond)
-            if emb.shape[0] != B:
+            if cond.shape[0] != B:
                 raise _lib.QuarkAudioError(-1, f"cond must be [B={B}, T, {self.cond_dim}], got {tuple(cond.shape)}")
+            emb = self.encode_condition(cond, cond_lengths)
             Tc = emb.shape[1]
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        _, nc_arr = _lib.host_lengths("cond_lengths", cond_lengths, B)
+        t_lens, t_arr = _lib.host_lengths("semantic_lengths", semantic_lengths, B)
         shifted = torch.cat([g.reshape(-1) + self.global_offset, sids.reshape(-1) + self.semantic_offset])
+        t_dev = None
+        if ragged:  # nn.Embedding's range check, over the ids a row really holds: what lies at or behind semantic_lengths[b] is padding
+            t_dev = torch.tensor(t_lens if t_lens is not None else [T] * B, dtype=torch.int64, device=self.device)
+            live = torch.arange(T, device=self.device)[None, :] < t_dev[:, None]
+            shifted = torch.cat([g.reshape(-1) + self.global_offset, sids[live] + self.semantic_offset]).contiguous()
         if shifted.numel():
             bad = C.c_int64(0)
             _lib.check(lm._lib.qa_codes_check(shifted.data_ptr(), shifted.numel(), self.vocab_size, C.byref(bad), stream))
@@ -615,32 +643,43 @@ class CustomLlamaModel:
         loss_seq = torch.empty(B, dtype=torch.float32, device=self.device)
         correct = torch.empty(B, dtype=torch.int64, device=self.device)
         out = torch.empty(2, dtype=torch.float32, device=self.device)
+        if ragged:
+            _lib.check(lm._lib.qa_lm_score_cond_ragged(lm._handle, emb.data_ptr() if emb is not None else None, Tc, nc_arr, B, g.data_ptr(), G,
+                                                       sids.data_ptr(), T, t_arr, self.label_smoothing, loss_seq.data_ptr(),
+                                                       correct.data_ptr(), out.data_ptr(), out[1:].data_ptr(), stream))
+            return loss_seq, correct, out[0], out[1], t_dev + (G + 1)
         _lib.check(lm._lib.qa_lm_score_cond(lm._handle, emb.data_ptr() if emb is not None else None, Tc, B, g.data_ptr(), G, sids.data_ptr(), T,
                                             self.label_smoothing, loss_seq.data_ptr(), correct.data_ptr(), out.data_ptr(),
                                             out[1:].data_ptr(), stream))
         return loss_seq, correct, out[0], out[1], G + T + 1
 
     @torch.no_grad()
-    def forward(self, global_ids, semantic_ids, cond: Optional[torch.Tensor] = None):
-        """llm.py:107-147 -> (loss, acc), 0-dim float32 device tensors over the B * (G + T + 1) target rows (no semantic_eos target)."""
-        _, _, loss, acc, _ = self._score(global_ids, semantic_ids, cond)
+    def forward(self, global_ids, semantic_ids, cond: Optional[torch.Tensor] = None, *, cond_lengths=None, semantic_lengths=None):
+        """llm.py:107-147 -> (loss, acc), 0-dim float32 device tensors over the B * (G + T + 1) target rows (no semantic_eos target).
+
+        cond_lengths / semantic_lengths (keyword only; B ints each, None: every row at full width): row b is scored
+        as forward(global_ids[b:b+1], semantic_ids[b:b+1, :semantic_lengths[b]], cond[b:b+1, :cond_lengths[b]]) scores it alone, with
+        Lt_b = G + semantic_lengths[b] + 1 target rows (the last position of its OWN stream is dropped).  loss and acc pool the rows: the
+        sums over all target rows divided by sum_b Lt_b.  What lies at or behind a row's lengths is never read and never range-checked."""
+        _, _, loss, acc, _ = self._score(global_ids, semantic_ids, cond, cond_lengths, semantic_lengths)
         return loss, acc
 
     def __call__(self, *args, **kwargs):
         return self.forward(*args, **kwargs)
 
     @torch.no_grad()
-    def score(self, global_ids, semantic_ids, cond: Optional[torch.Tensor] = None):
-        """forward per sequence: (loss [B], acc [B])"""
-        loss_seq, correct, _, _, Lt = self._score(global_ids, semantic_ids, cond)
-        return loss_seq, correct.to(torch.float32) / Lt
+    def score(self, global_ids, semantic_ids, cond: Optional[torch.Tensor] = None, *, cond_lengths=None, semantic_lengths=None):
+        """forward per sequence: (loss [B], acc [B]); with per-row lengths (see forward) over each row's own Lt_b target rows"""
+        loss_seq, correct, _, _, Lt = self._score(global_ids, semantic_ids, cond, cond_lengths, semantic_lengths)
+        return loss_seq, correct.to(torch.float32) / (Lt.to(torch.float32) if torch.is_tensor(Lt) else Lt)
 
     def enable_taps(self, on: bool = True):
         self._lm.enable_taps(on)
         return self
 
     def tap(self, name: str) -> torch.Tensor:
-        """"logits.global" [B, global_length, global_size], "logits.semantic", "logits.forced" [B, G + T + 1, vocab]"""
+        """"logits.global" [B, global_length, global_size], "logits.semantic", "logits.forced" [B, G + T + 1, vocab] (packed
+        [sum Lt_b, vocab] after a call with per-row lengths)"""
         return self._lm.tap(name)
 
 

@@ -68,11 +68,16 @@ class _Frames:
         return self._shape[dim]
 
 
-def stft_logmel(x: torch.Tensor, hop_length: int = HOP_LENGTH, win_length: int = WIN_LENGTH, n_fft: int = 640, n_mels: int = 80) -> torch.Tensor:
+def stft_logmel(x: torch.Tensor, hop_length: int = HOP_LENGTH, win_length: int = WIN_LENGTH, n_fft: int = 640, n_mels: int = 80,
+                lengths=None) -> torch.Tensor:
     """Model.stft_logmel (model.py:53-79), restated with the filter bank of torchaudio.functional.melscale_fbanks (HTK scale, no
     normalisation, 0-8000 Hz).  LLM_SFT.generate consumes only `mel.size(1)` (llm_sft.py:108), which `mel_frames()` gives without
     computing anything; CustomLlamaModel's condition encoder consumes the values.  A CUDA input runs on the device (qa_logmel: the
-    framed-signal DFT GEMM); a CPU input keeps this torch restatement."""
+    framed-signal DFT GEMM); a CPU input keeps this torch restatement.
+
+    lengths (B sample counts in 1 .. x.size(1), None: every row is full): out[b, :F_b], F_b = mel_frames_for(lengths[b], ...), is the
+    log-mel of x[b:b+1, :lengths[b]] alone and out[b, F_b:] is exactly 0; samples behind a row's length are never used.  Device inputs in
+    the configuration qa_logmel serves only (qa_logmel_ragged)."""
     assert x.ndim == 2
     # the condition encoder's input (CustomLlamaModel): computed on the device by qa_logmel where its framed-signal DFT serves the
     # configuration (win = 2 hop, hop a multiple of 16, n_mels a multiple of 4); any other configuration keeps the torch path below
@@ -83,10 +88,17 @@ def stft_logmel(x: torch.Tensor, hop_length: int = HOP_LENGTH, win_length: int =
         lib = _lib.load_library()
         xc = x.to(torch.float32).contiguous()
         out = torch.empty((xc.shape[0], mel_frames_for(xc.shape[1], hop_length, win_length), n_mels), dtype=torch.float32, device=x.device)
+        _, lens = _lib.host_lengths("stft_logmel: lengths", lengths, xc.shape[0])
         with torch.cuda.device(x.device):
+            if lens is not None:
+                _lib.check(lib.qa_logmel_ragged(xc.data_ptr(), lens, xc.shape[0], xc.shape[1], n_fft, win_length, hop_length, n_mels, 16000,
+                                                0.0, 8000.0, out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+                return out
             _lib.check(lib.qa_logmel(xc.data_ptr(), xc.shape[0], xc.shape[1], n_fft, win_length, hop_length, n_mels, 16000, 0.0, 8000.0,
                                      out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
         return out
+    if lengths is not None:
+        raise ValueError("stft_logmel: lengths need a device input in the configuration qa_logmel serves (win = 2 hop, hop % 16 == 0)")
     pad_length = math.ceil(x.size(-1) / hop_length) * hop_length - x.size(-1)
     x = torch.nn.functional.pad(x, ((win_length - hop_length) // 2, pad_length + (win_length - hop_length) // 2))
     spec = torch.stft(x, n_fft, hop_length, win_length=win_length, window=torch.hann_window(win_length, device=x.device), onesided=True,
@@ -508,9 +520,9 @@ class Model:
     def extract_semantic_features(self, wavs: torch.Tensor) -> torch.Tensor:  # model.py:38-51
         return self.semantic_model(wavs.to(self.device))
 
-    def stft_logmel(self, x: torch.Tensor) -> torch.Tensor:  # model.py:53-79
+    def stft_logmel(self, x: torch.Tensor, lengths=None) -> torch.Tensor:  # model.py:53-79; lengths: see stft_logmel
         c = self.stft_conf
-        return stft_logmel(x, c["hop_length"], c["win_length"], c["n_fft"], c["n_mels"])
+        return stft_logmel(x, c["hop_length"], c["win_length"], c["n_fft"], c["n_mels"], lengths=lengths)
 
     def _save(self, name: str, est: torch.Tensor, fs: int):
         import os
