@@ -175,10 +175,20 @@ int launch_lm_batch_reduce(const double* seq_sum, const long long* correct_seq, 
 // x [B, n, d] <- prompt + input embeddings left-aligned, zeros behind; tgt (packed) <- the targets.  table == nullptr: the prompt alone
 // task_vec == nullptr: CustomLlamaModel's prompt [mix_sos, mix_emb[b, :nm]] (mix_emb [B, Nm, d]: the condition embeddings) or none (mix_emb
 // null).  drop = 1 in the three launchers: a row's own last position is left out, Lt_b = G + T[b] + 1
-int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,
-                             const float* mix_emb, int Ne, int Nm, const float* table, const long long* gids, int G, const long long* sids,
-                             int T_max, int V, int goff, int soff, long long* tgt, const int* ne_r, const int* nm_r, const int* T_r,
-                             const int* off_r, int B, int d, hipStream_t s, int drop = 0);
+// Filled by name, like AttnArgs; every member defaults to "absent", so a prompt-only pass sets the prompt's members alone
+struct ScoreAssembleArgs {
+    float* x = nullptr;  // [B, n, d]
+    int n = 0, B = 0, d = 0;
+    const float *task_vec = nullptr, *enroll_sos = nullptr, *enroll_emb = nullptr, *mix_sos = nullptr, *mix_emb = nullptr;
+    int Ne = 0, Nm = 0;  // the frame strides of enroll_emb / mix_emb
+    const float* table = nullptr;  // codec_embedding [V, d]; with it gids [B, G] / sids [B, T_max] (offsets goff / soff) and tgt
+    const long long *gids = nullptr, *sids = nullptr;
+    int G = 0, T_max = 0, V = 0, goff = 0, soff = 0;
+    long long* tgt = nullptr;
+    const int *ne_r = nullptr, *nm_r = nullptr, *T_r = nullptr, *off_r = nullptr;
+    int drop = 0;
+};
+int launch_lm_score_assemble(const ScoreAssembleArgs& a, hipStream_t s);
 // y (packed [sum Lt_b, d]) <- x[b, lp[b] .. lp[b] + Lt_b - 1, :], Lt_b = G + T[b] + 2 - drop <= Lt_max
 int launch_lm_score_gather(float* y, const float* x, int B, int n, int d, int G, int Lt_max, const int* lp_r, const int* T_r, const int* off_r,
                            hipStream_t s, int drop = 0);

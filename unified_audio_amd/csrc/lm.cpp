@@ -14,6 +14,8 @@
 // qa_lm_score_ragged / qa_lm_prompt_ragged are the same with per-row lengths (host logic in lm_score_rows.h).
 #include <memory>
 
+#include <climits>
+#include <cstdio>
 #include <cstdlib>
 
 #include "host_util.h"
@@ -500,33 +502,57 @@ struct Chain {
 // features the adapter still has to project.  ne_rows (HOST, [B]; ragged generate, DESIGN.md sections 23 and 37): row b's enrollment frames,
 // 1 .. Ne - or, in cond_mode, its condition frames, 1 .. Tc - the prompt is then laid out for the LONGEST possible row (Ne / Tc frames)
 struct Prompt {
-    bool cond_mode;
-    const float* cond; int Tc;
-    int task;
-    const float* enroll; int Ne;  // nullptr and 0: no enrollment
-    const float* mix; int Nm;
-    const int* ne_rows;
+    bool cond_mode = false;
+    const float* cond = nullptr; int Tc = 0;
+    int task = 0;
+    const float* enroll = nullptr; int Ne = 0;  // nullptr and 0: no enrollment
+    const float* mix = nullptr; int Nm = 0;
+    const int* ne_rows = nullptr;
 };
 
 Prompt speech_prompt(int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix) {
-    return Prompt{false, nullptr, 0, task, enroll_feats, enroll_feats ? (int)n_enroll : 0, mix_feats, (int)n_mix, nullptr};
+    Prompt p;
+    p.task = task;
+    p.enroll = enroll_feats; p.Ne = enroll_feats ? (int)n_enroll : 0;
+    p.mix = mix_feats; p.Nm = (int)n_mix;
+    return p;
 }
-Prompt cond_prompt(const float* cond_embeds, int64_t T) { return Prompt{true, cond_embeds, (int)T, 0, nullptr, 0, nullptr, 0, nullptr}; }
+Prompt cond_prompt(const float* cond_embeds, int64_t T) {
+    Prompt p;
+    p.cond_mode = true;
+    p.cond = cond_embeds; p.Tc = (int)T;
+    return p;
+}
 
 int prompt_len(const Prompt& p) { return p.cond_mode ? (p.Tc > 0 ? p.Tc + 1 : 0) : 1 + (p.enroll ? 1 + p.Ne : 0) + 1 + p.Nm; }
 
 // The prompt rows (llm_sft.py:110-128 / llm.py:301-306) of sequences [b0, b0 + gb) into out [gb, prompt_len, d], on c.stream.  emix /
 // eenr: the adapter's output for these rows; off (ragged only, [gb], device) receives their position offsets.  Ragged: the adapter also
 // runs over the padding frames (a GEMM row depends on its own input row alone) and assemble_prompt never copies their outputs.
+// the adapter over the mixture and enrollment frames of sequences [b0, b0 + gb) of a speech prompt -> emix [gb, Nm, d], eenr [gb, Ne, d]
+int adapt_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix, float* eenr) {
+    const int F = lm->spec.feats_dim;
+    QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
+    if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
+    return QA_OK;
+}
+
+// the speech prompt's members of a per-row assembly pass (score_rows_graph, prompt_call): adapter outputs and the group's device counts
+void speech_assemble(ScoreAssembleArgs& as, const qa_lm* lm, const Prompt& p, const float* emix, const float* eenr, const int* ne_r,
+                     const int* nm_r) {
+    as.task_vec = lm->task_emb + (size_t)p.task * lm->spec.hidden;
+    as.enroll_sos = p.enroll ? lm->enroll_sos : nullptr; as.enroll_emb = eenr; as.Ne = p.Ne; as.ne_r = ne_r;
+    as.mix_sos = lm->mix_sos; as.mix_emb = emix; as.Nm = p.Nm; as.nm_r = nm_r;
+}
+
 int build_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix, float* eenr, float* out, int* off) {
-    const int d = lm->spec.hidden, F = lm->spec.feats_dim;
+    const int d = lm->spec.hidden;
     if (p.cond_mode) {
         if (p.ne_rows) QA_RUN(c, launch_lm_offsets(off, p.ne_rows + b0, p.Tc, gb, c.stream));
         if (p.Tc > 0) QA_RUN(c, launch_cond_prompt(out, lm->mix_sos, p.cond + (size_t)b0 * p.Tc * d, gb, p.Tc, d, c.stream, off));
         return QA_OK;
     }
-    QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
-    if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
+    QA_TRY(adapt_prompt(lm, c, p, b0, gb, emix, eenr));
     if (p.ne_rows) QA_RUN(c, launch_lm_offsets(off, p.ne_rows + b0, p.Ne, gb, c.stream));
     QA_RUN(c, launch_assemble_prompt(out, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
                                      p.Ne, p.Nm, d, c.stream, off));
@@ -800,7 +826,7 @@ int write_score_ints(int* dst, const ScoreRows& R, const ScoreGroup& g, hipStrea
 // a row's own last position dropped.
 int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
     const qa_lm_spec& sp = lm->spec;
-    const int d = sp.hidden, V = vocab_of(sp), F = sp.feats_dim;
+    const int d = sp.hidden, V = vocab_of(sp);
     const Prompt& p = a.p;
     const ScoreRows& R = *a.rows;
     const int GB = std::min(a.B, LM_MAX_ROWS), drop = p.cond_mode ? 1 : 0;
@@ -826,18 +852,19 @@ int score_rows_graph(qa_lm* lm, Ctx& c, const ScoreArgs& a, float* tap) {
         const int *ne_r = ints + SR_NE * gb, *nm_r = ints + SR_NM * gb, *T_r = ints + SR_T * gb, *off_r = ints + SR_OFF * gb,
                   *lp_r = ints + SR_LP * gb, *L_r = ints + SR_L * gb, *zero_r = ints + SR_ZERO * gb;
         QA_TRY(write_score_ints(ints, R, g, c.stream));
-        if (p.cond_mode) {
-            QA_TRY(launch_lm_score_assemble(b.x, n, nullptr, nullptr, nullptr, lm->mix_sos, p.cond ? p.cond + (size_t)b0 * p.Tc * d : nullptr, 0, p.Tc,
-                                            lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T, a.T, V, 3,
-                                            3 + sp.global_size, tgt, nullptr, nm_r, T_r, off_r, gb, d, c.stream, drop));
+        ScoreAssembleArgs as;
+        as.x = b.x; as.n = n; as.B = gb; as.d = d;
+        as.table = lm->codec_emb; as.V = V; as.goff = 3; as.soff = 3 + sp.global_size;
+        as.gids = a.gids + (size_t)b0 * a.G; as.G = a.G; as.sids = a.sids + (size_t)b0 * a.T; as.T_max = a.T;
+        as.tgt = tgt; as.T_r = T_r; as.off_r = off_r; as.drop = drop;
+        if (p.cond_mode) {  // the condition embeddings are the prompt's frames as they are; none at all without a condition
+            as.mix_sos = lm->mix_sos; as.mix_emb = p.cond ? p.cond + (size_t)b0 * p.Tc * d : nullptr; as.Nm = p.Tc; as.nm_r = nm_r;
         } else {
             // the adapters run over the padding frames too: a GEMM row depends on its own input row alone, and those outputs are never copied
-            QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * F, (int64_t)gb * p.Nm, lm->adapter, emix));
-            if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * F, (int64_t)gb * p.Ne, lm->adapter, eenr));
-            QA_TRY(launch_lm_score_assemble(b.x, n, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix,
-                                            p.Ne, p.Nm, lm->codec_emb, a.gids + (size_t)b0 * a.G, a.G, a.sids + (size_t)b0 * a.T, a.T, V, 3,
-                                            3 + sp.global_size, tgt, ne_r, nm_r, T_r, off_r, gb, d, c.stream));
+            QA_TRY(adapt_prompt(lm, c, p, b0, gb, emix, eenr));
+            speech_assemble(as, lm, p, emix, eenr, ne_r, nm_r);
         }
+        QA_TRY(launch_lm_score_assemble(as, c.stream));
         QA_TRY(lm_body(lm, c, b, gb, n, 0, n, false, true, nullptr, zero_r, L_r));
         QA_TRY(launch_lm_score_gather(b.att, b.x, gb, n, d, a.G, g.Lt_max, lp_r, T_r, off_r, c.stream, drop));
         const int64_t rows = g.rows;
@@ -1241,69 +1268,6 @@ int qa_lm_head(qa_lm* lm, const float* hidden, int64_t rows, int32_t lo, int32_t
     return linear_op(c, hidden, rows, w, logits);
 }
 
-int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
-                 float* out, void* stream) {
-    if (!lm || !mix_feats || !out) {
-        set_error("qa_lm_prompt: null argument");
-        return QA_ERR_INVALID;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_lm_prompt", s, CACHE_IS_HOST_STATE));  // the adapters' scratch lives in the session workspace, which may have to grow
-    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "qa_lm_prompt: task %d out of range (KeyError in the reference)", task);
-    QA_REQUIRE(B >= 1 && n_mix >= 1 && n_mix <= LM_MAX_POS && B <= (1 << 16), "qa_lm_prompt: bad shape");
-    QA_REQUIRE(!enroll_feats || (n_enroll >= 1 && n_enroll <= LM_MAX_POS), "qa_lm_prompt: enrollment given with no frames");
-    const Prompt p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
-    const int d = lm->spec.hidden;
-    Ctx& c = lm->sess_ctx;
-    return run_session(lm, s, [&]() -> int {
-        float* emix = c.arena.alloc<float>((size_t)B * p.Nm * d);
-        float* eenr = p.enroll ? c.arena.alloc<float>((size_t)B * p.Ne * d) : nullptr;
-        return build_prompt(lm, c, p, 0, (int)B, emix, eenr, out, nullptr);
-    });
-}
-
-int qa_lm_prompt_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
-                        int64_t n_mix_max, const int64_t* n_mix, int64_t B, float* out, void* stream) {
-    const char* fn = "qa_lm_prompt_ragged";
-    if (!n_enroll && !n_mix) return qa_lm_prompt(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, out, stream);
-    if (!lm || !mix_feats || !out) {
-        set_error("%s: null argument", fn);
-        return QA_ERR_INVALID;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
-    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, task);
-    QA_REQUIRE(B >= 1 && n_mix_max >= 1 && n_mix_max <= LM_MAX_POS && B <= (1 << 16), "%s: bad shape", fn);
-    QA_REQUIRE(!enroll_feats || (n_enroll_max >= 1 && n_enroll_max <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
-    ScoreRowsShape shape;
-    shape.B = B; shape.has_enroll = enroll_feats != nullptr; shape.ne_max = enroll_feats ? n_enroll_max : 0; shape.nm_max = n_mix_max;
-    shape.targets = false; shape.group_rows = LM_MAX_ROWS; shape.max_pos = 2 * LM_MAX_POS + 3;  // as qa_lm_prompt: the frame counts bound it
-    ScoreRows R;
-    int64_t row = 0, value = 0;
-    QA_TRY(score_rows_refusal(fn, plan_score_rows(n_enroll, n_mix, nullptr, shape, &R, &row, &value), shape, row, value));
-    if (R.uniform) return qa_lm_prompt(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, out, stream);
-    const Prompt p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix_max);
-    const int d = lm->spec.hidden, Fd = lm->spec.feats_dim;
-    Ctx& c = lm->sess_ctx;
-    return run_session(lm, s, [&]() -> int {
-        const int GB = (int)std::min<int64_t>(B, LM_MAX_ROWS);
-        float* emix = c.arena.alloc<float>((size_t)GB * p.Nm * d);
-        float* eenr = p.enroll ? c.arena.alloc<float>((size_t)GB * p.Ne * d) : nullptr;
-        int* ints = c.arena.alloc<int>((size_t)SR_COUNT * GB);
-        if (c.dry) return QA_OK;  // real-pass-only remainder
-        for (const ScoreGroup& g : R.groups) {  // groups bound the adapters' scratch; a row's prompt does not know its group
-            const int b0 = g.b0, gb = g.gb;
-            QA_TRY(write_score_ints(ints, R, g, c.stream));
-            QA_TRY(linear_op(c, p.mix + (size_t)b0 * p.Nm * Fd, (int64_t)gb * p.Nm, lm->adapter, emix));
-            if (p.enroll) QA_TRY(linear_op(c, p.enroll + (size_t)b0 * p.Ne * Fd, (int64_t)gb * p.Ne, lm->adapter, eenr));
-            QA_TRY(launch_lm_score_assemble(out + (size_t)b0 * R.Lp_max * d, R.Lp_max, lm->task_emb + (size_t)p.task * d,
-                                            p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, p.Ne, p.Nm, nullptr, nullptr, 0, nullptr,
-                                            0, 0, 0, 0, nullptr, ints + SR_NE * gb, ints + SR_NM * gb, nullptr, nullptr, gb, d, c.stream));
-        }
-        return QA_OK;
-    });
-}
-
 int qa_lm_create(qa_lm** out, const qa_lm_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
     if (!out || !spec || !tensors) {
         set_error("qa_lm_create: null argument");
@@ -1321,19 +1285,117 @@ int qa_lm_create(qa_lm** out, const qa_lm_spec* spec, const qa_tensor* tensors, 
 
 void qa_lm_destroy(qa_lm* lm) { destroy_handle(lm); }
 
-// what the six generate entry points share; each then sets its prompt
-static GenArgs gen_args(int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc, int64_t* global_ids, int64_t* semantic_ids) {
-    GenArgs a{};
-    a.B = (int)B; a.G = global_length; a.S = semantic_length; a.sc = sc; a.gids = global_ids; a.sids = semantic_ids;
-    return a;
+// ---- generate, score and prompt: one front per family.  An entry point builds its Prompt, fills the family's
+// argument struct and passes the name its messages carry; every check lives in the front, runs once, and comes before the first launch,
+// before any handle state is written and before any output is touched.  The order of the checks is part of the contract: it decides
+// which of two simultaneous faults a caller sees.
+
+// a count of the API as the int the graphs take.  Saturating: a value beyond int lands on the same side of every bound it is held to
+static int narrow(int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, INT_MIN), INT_MAX); }
+
+// the shape the length vectors of a prompt / score call are planned against (lm_score_rows.h): the Prompt's widths are the tensors' strides
+static ScoreRowsShape prompt_rows_shape(const Prompt& p, int64_t B) {
+    ScoreRowsShape s;
+    s.B = B; s.cond_form = p.cond_mode; s.has_enroll = p.enroll != nullptr; s.ne_max = p.Ne; s.nm_max = p.cond_mode ? p.Tc : p.Nm;
+    s.targets = false; s.group_rows = LM_MAX_ROWS; s.max_pos = 2 * LM_MAX_POS + 3;  // no target rows: the frame counts bound it
+    return s;
+}
+static ScoreRowsShape score_rows_shape(const ScoreArgs& a) {
+    ScoreRowsShape s = prompt_rows_shape(a.p, a.B);
+    s.targets = true; s.G = a.G; s.T_max = a.T; s.max_pos = LM_MAX_POS;
+    return s;
 }
 
-// ragged (qa_lm_generate_ragged*): a.p.Ne is n_enroll_max and ne_rows64 the caller's HOST vector [B] of the rows' own frame counts, which is
-// checked here and handed on as a.p.ne_rows
-// ragged in cond_mode (qa_lm_generate_cond_ragged*): a.p.Tc is T_max and ne_rows64 the rows' condition frames, NULL allowed (the rectangular call)
-static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = false, const int64_t* ne_rows64 = nullptr) {
+// the HOST length vectors [B] of a score / prompt call, each NULL for "every row at full width": the rows' enrollment frames, mixture - or, in
+// cond_mode, condition - frames and semantic ids
+struct ScoreLens {
+    const int64_t *enroll, *mix, *semantic;
+    bool any() const { return enroll || mix || semantic; }
+};
+static const ScoreLens NO_LENS{};
+
+// qa_lm_prompt / qa_lm_prompt_ragged.  No vector, or every row at full width: the rectangular launches
+static int prompt_call(const char* fn, qa_lm* lm, const Prompt& p, int64_t B, const ScoreLens& n, float* out, void* stream) {
+    if (!lm || !p.mix || !out) {
+        set_error("%s: null argument", fn);
+        return QA_ERR_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // without vectors: the adapters' scratch lives in the session workspace, which may have to grow
+    QA_TRY(refuse_capture(fn, s, n.any() ? LENGTHS_ARE_HOST_DATA : CACHE_IS_HOST_STATE));
+    QA_REQUIRE(p.task >= 0 && p.task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, p.task);
+    QA_REQUIRE(B >= 1 && p.Nm >= 1 && p.Nm <= LM_MAX_POS && B <= (1 << 16), "%s: bad shape", fn);
+    QA_REQUIRE(!p.enroll || (p.Ne >= 1 && p.Ne <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
+    ScoreRows R;
+    if (n.any()) {
+        const ScoreRowsShape shape = prompt_rows_shape(p, B);
+        int64_t row = 0, value = 0;
+        QA_TRY(score_rows_refusal(fn, plan_score_rows(n.enroll, n.mix, nullptr, shape, &R, &row, &value), shape, row, value));
+    }
+    const int d = lm->spec.hidden;
+    Ctx& c = lm->sess_ctx;
+    if (R.uniform)
+        return run_session(lm, s, [&]() -> int {
+            float* emix = c.arena.alloc<float>((size_t)B * p.Nm * d);
+            float* eenr = p.enroll ? c.arena.alloc<float>((size_t)B * p.Ne * d) : nullptr;
+            return build_prompt(lm, c, p, 0, (int)B, emix, eenr, out, nullptr);
+        });
+    return run_session(lm, s, [&]() -> int {
+        const int GB = (int)std::min<int64_t>(B, LM_MAX_ROWS);
+        float* emix = c.arena.alloc<float>((size_t)GB * p.Nm * d);
+        float* eenr = p.enroll ? c.arena.alloc<float>((size_t)GB * p.Ne * d) : nullptr;
+        int* ints = c.arena.alloc<int>((size_t)SR_COUNT * GB);
+        if (c.dry) return QA_OK;  // real-pass-only remainder
+        for (const ScoreGroup& g : R.groups) {  // groups bound the adapters' scratch; a row's prompt does not know its group
+            QA_TRY(write_score_ints(ints, R, g, c.stream));
+            QA_TRY(adapt_prompt(lm, c, p, g.b0, g.gb, emix, eenr));
+            ScoreAssembleArgs as;  // no table: the prompt alone
+            as.x = out + (size_t)g.b0 * R.Lp_max * d; as.n = R.Lp_max; as.B = g.gb; as.d = d;
+            speech_assemble(as, lm, p, emix, eenr, ints + SR_NE * g.gb, ints + SR_NM * g.gb);
+            QA_TRY(launch_lm_score_assemble(as, c.stream));
+        }
+        return QA_OK;
+    });
+}
+
+int qa_lm_prompt(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                 float* out, void* stream) {
+    return prompt_call("qa_lm_prompt", lm, speech_prompt(task, enroll_feats, narrow(n_enroll), mix_feats, narrow(n_mix)), B, NO_LENS, out, stream);
+}
+
+int qa_lm_prompt_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
+                        int64_t n_mix_max, const int64_t* n_mix, int64_t B, float* out, void* stream) {
+    return prompt_call(n_enroll || n_mix ? "qa_lm_prompt_ragged" : "qa_lm_prompt", lm,
+                       speech_prompt(task, enroll_feats, narrow(n_enroll_max), mix_feats, narrow(n_mix_max)), B,
+                       ScoreLens{n_enroll, n_mix, nullptr}, out, stream);
+}
+
+// What the per-row vector of a ragged generate entry point is held to.  The two families differ in every member
+struct GenRows {
+    bool ragged;              // false: a rectangular entry point, nothing below is read
+    const int64_t* n;         // HOST [B], 1 .. the prompt's Ne (speech) or Tc (condition)
+    const char *vec, *bound;  // as the messages name them
+    bool optional;            // a NULL vector is the rectangular call; false: refused
+    bool full_is_rect;        // every row at the bound: the rectangular launches; false: still a ragged call
+    bool host_only;           // refused under a stream capture
+};
+static const GenRows NO_ROWS{};
+static GenRows enroll_rows(const int64_t* n_enroll) { return GenRows{true, n_enroll, "n_enroll", "n_enroll_max", false, false, false}; }
+static GenRows cond_rows(const int64_t* n_cond) { return GenRows{true, n_cond, "n_cond", "T_max", true, true, true}; }
+
+static GenArgs gen_args(const Prompt& p, int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc, int64_t* global_ids,
+                        int64_t* semantic_ids) {
+    return GenArgs{p, (int)B, global_length, semantic_length, sc, global_ids, semantic_ids};
+}
+static SampleCfg greedy(float temperature, int32_t top_k, float top_p) { return SampleCfg{0, top_k, top_p, temperature, 0ull}; }
+static SampleCfg sampled(float temperature, int32_t top_k, float top_p, uint64_t seed) {
+    return SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed};
+}
+
+// the eight qa_lm_generate* entry points.  A ragged call lays its prompt out for the LONGEST possible row (a.p.Ne / a.p.Tc) and hands the
+// checked vector on as a.p.ne_rows
+static int generate_call(const char* fn, qa_lm* lm, GenArgs a, const GenRows& r, void* stream) {
     Prompt& p = a.p;
-    const char* fn = p.cond_mode ? (ragged ? "qa_lm_generate_cond_ragged" : "qa_lm_generate_cond") : ragged ? "qa_lm_generate_ragged" : "qa_lm_generate";
     if (!lm || (!p.cond_mode && !p.mix) || !a.gids || !a.sids) {
         set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
@@ -1346,28 +1408,27 @@ static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = fa
     QA_REQUIRE(!p.enroll || p.Ne > 0, "%s: enrollment given with no frames", fn);
     QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "%s: temperature must be in (0, 1] (llm.py:278)", fn);
     QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "%s: bad top_k / top_p", fn);
-    std::vector<int> ne_host;  // every check of a ragged call comes before the first launch: a refused call has launched nothing
-    if (ragged && p.cond_mode && ne_rows64) {
-        QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
-        QA_REQUIRE(p.cond && p.Tc > 0, "%s: n_cond given (n_cond[0] = %lld) without a condition (cond_embeds is NULL or T_max = 0)", fn,
-                   (long long)ne_rows64[0]);
+    std::vector<int> rows_host;
+    if (r.ragged && (r.n || !r.optional)) {
+        if (r.host_only) QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
+        // the tensor the vector indexes must be there, and the longest possible row must fit: the two families' own texts
+        char prompt_is[96];
+        if (p.cond_mode) {
+            QA_REQUIRE(p.cond && p.Tc > 0, "%s: n_cond given (n_cond[0] = %lld) without a condition (cond_embeds is NULL or T_max = 0)", fn,
+                       (long long)r.n[0]);
+            std::snprintf(prompt_is, sizeof(prompt_is), "prompt 1 + T_max %d", p.Tc);
+        } else {
+            QA_REQUIRE(p.enroll && r.n, "%s: per-row enrollment lengths need enroll_feats [B, n_enroll_max, feats_dim] and n_enroll [B]", fn);
+            std::snprintf(prompt_is, sizeof(prompt_is), "prompt %d with n_enroll_max %d and n_mix %d", prompt_len(p), p.Ne, p.Nm);
+        }
         const long long total = (long long)prompt_len(p) + a.G + 1 + a.S;
-        QA_REQUIRE(total <= LM_MAX_POS, "%s: %lld positions (prompt 1 + T_max %d, + %d + 1 + %d) exceed max_position_embeddings %d", fn, total,
-                   p.Tc, a.G, a.S, LM_MAX_POS);
+        QA_REQUIRE(total <= LM_MAX_POS, "%s: %lld positions (%s, + %d + 1 + %d) exceed max_position_embeddings %d", fn, total, prompt_is, a.G, a.S,
+                   LM_MAX_POS);
+        const int hi = p.cond_mode ? p.Tc : p.Ne;
         bool full = true;
-        const int64_t bad = check_row_lengths(ne_rows64, a.B, 1, p.Tc, &ne_host, &full);
-        QA_REQUIRE(bad < 0, "%s: n_cond[%d] = %lld is outside 1 .. T_max = %d", fn, (int)bad, (long long)ne_rows64[bad], p.Tc);
-        if (!full) p.ne_rows = ne_host.data();  // every row full: the rectangular call, the same launches
-    } else if (ragged && !p.cond_mode) {
-        QA_REQUIRE(p.enroll && ne_rows64, "%s: per-row enrollment lengths need enroll_feats [B, n_enroll_max, feats_dim] and n_enroll [B]", fn);
-        const long long total = (long long)prompt_len(p) + a.G + 1 + a.S;
-        QA_REQUIRE(total <= LM_MAX_POS,
-                   "%s: %lld positions (prompt %d with n_enroll_max %d and n_mix %d, + %d + 1 + %d) exceed max_position_embeddings %d", fn,
-                   total, prompt_len(p), p.Ne, p.Nm, a.G, a.S, LM_MAX_POS);
-        bool full = true;  // not used: a batch of full rows still runs as a ragged one
-        const int64_t bad = check_row_lengths(ne_rows64, a.B, 1, p.Ne, &ne_host, &full);
-        QA_REQUIRE(bad < 0, "%s: n_enroll[%d] = %lld is outside 1 .. n_enroll_max = %d", fn, (int)bad, (long long)ne_rows64[bad], p.Ne);
-        p.ne_rows = ne_host.data();
+        const int64_t bad = check_row_lengths(r.n, a.B, 1, hi, &rows_host, &full);
+        QA_REQUIRE(bad < 0, "%s: %s[%d] = %lld is outside 1 .. %s = %d", fn, r.vec, (int)bad, (long long)r.n[bad], r.bound, hi);
+        if (!full || !r.full_is_rect) p.ne_rows = rows_host.data();
     }
     QA_HIP(hipSetDevice(lm->device));
     if (sc.do_sample) QA_TRY(lm_sample_prepare());
@@ -1399,79 +1460,118 @@ static int lm_generate_impl(qa_lm* lm, GenArgs a, void* stream, bool ragged = fa
 int qa_lm_generate(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                    int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                    int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
-    a.p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
-    return lm_generate_impl(lm, a, stream);
+    const Prompt p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
+    const SampleCfg sc = greedy(temperature, top_k, top_p);
+    return generate_call("qa_lm_generate", lm, gen_args(p, B, global_length, semantic_length, sc, global_ids, semantic_ids), NO_ROWS, stream);
 }
 
 int qa_lm_generate_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats,
                            int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                            int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
-    a.p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
-    return lm_generate_impl(lm, a, stream);
-}
-
-int qa_lm_generate_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, int32_t global_length,
-                               int32_t semantic_length, float temperature, int32_t top_k, float top_p, int64_t* global_ids,
-                               int64_t* semantic_ids, void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
-    a.p = cond_prompt(cond_embeds, T_max);
-    return lm_generate_impl(lm, a, stream, true, n_cond);
-}
-
-int qa_lm_generate_cond_ragged_sampled(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B,
-                                       int32_t global_length, int32_t semantic_length, float temperature, int32_t top_k, float top_p,
-                                       uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
-    a.p = cond_prompt(cond_embeds, T_max);
-    return lm_generate_impl(lm, a, stream, true, n_cond);
+    const Prompt p = speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
+    const SampleCfg sc = sampled(temperature, top_k, top_p, seed);
+    return generate_call("qa_lm_generate", lm, gen_args(p, B, global_length, semantic_length, sc, global_ids, semantic_ids), NO_ROWS, stream);
 }
 
 int qa_lm_generate_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
                           const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length, float temperature,
                           int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
-    a.p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix);
-    return lm_generate_impl(lm, a, stream, true, n_enroll);
+    const Prompt p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix);
+    const SampleCfg sc = greedy(temperature, top_k, top_p);
+    return generate_call("qa_lm_generate_ragged", lm, gen_args(p, B, global_length, semantic_length, sc, global_ids, semantic_ids),
+                         enroll_rows(n_enroll), stream);
 }
 
 int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
                                   const float* mix_feats, int64_t n_mix, int64_t B, int32_t global_length, int32_t semantic_length,
                                   float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
                                   void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
-    a.p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix);
-    return lm_generate_impl(lm, a, stream, true, n_enroll);
+    const Prompt p = speech_prompt(task, enroll_feats, n_enroll_max, mix_feats, n_mix);
+    const SampleCfg sc = sampled(temperature, top_k, top_p, seed);
+    return generate_call("qa_lm_generate_ragged", lm, gen_args(p, B, global_length, semantic_length, sc, global_ids, semantic_ids),
+                         enroll_rows(n_enroll), stream);
 }
 
-static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
-                         const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length,
-                         double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream,
-                         bool cond_mode, const float* cond, int64_t Tc, const ScoreRows* rows = nullptr) {
-    const char* fn = cond_mode ? (rows ? "qa_lm_score_cond_ragged" : "qa_lm_score_cond") : rows ? "qa_lm_score_ragged" : "qa_lm_score";
-    if (!lm || (!cond_mode && !mix_feats) || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
-        (semantic_length > 0 && !semantic_ids)) {
+int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
+                        float temperature, int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    const SampleCfg sc = greedy(temperature, top_k, top_p);
+    return generate_call("qa_lm_generate_cond", lm, gen_args(cond_prompt(cond_embeds, T), B, global_length, semantic_length, sc, global_ids, semantic_ids),
+                         NO_ROWS, stream);
+}
+
+int qa_lm_generate_cond_sampled(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
+                                float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
+                                void* stream) {
+    const SampleCfg sc = sampled(temperature, top_k, top_p, seed);
+    return generate_call("qa_lm_generate_cond", lm, gen_args(cond_prompt(cond_embeds, T), B, global_length, semantic_length, sc, global_ids, semantic_ids),
+                         NO_ROWS, stream);
+}
+
+int qa_lm_generate_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, int32_t global_length,
+                               int32_t semantic_length, float temperature, int32_t top_k, float top_p, int64_t* global_ids,
+                               int64_t* semantic_ids, void* stream) {
+    const SampleCfg sc = greedy(temperature, top_k, top_p);
+    return generate_call("qa_lm_generate_cond_ragged", lm,
+                         gen_args(cond_prompt(cond_embeds, T_max), B, global_length, semantic_length, sc, global_ids, semantic_ids), cond_rows(n_cond),
+                         stream);
+}
+
+int qa_lm_generate_cond_ragged_sampled(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B,
+                                       int32_t global_length, int32_t semantic_length, float temperature, int32_t top_k, float top_p,
+                                       uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    const SampleCfg sc = sampled(temperature, top_k, top_p, seed);
+    return generate_call("qa_lm_generate_cond_ragged", lm,
+                         gen_args(cond_prompt(cond_embeds, T_max), B, global_length, semantic_length, sc, global_ids, semantic_ids), cond_rows(n_cond),
+                         stream);
+}
+
+static ScoreArgs score_args(const Prompt& p, int64_t B, const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids,
+                            int32_t semantic_length, double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc) {
+    return ScoreArgs{p, narrow(B), global_length, semantic_length, reinterpret_cast<const long long*>(global_ids),
+                     reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq, reinterpret_cast<long long*>(correct_per_seq),
+                     loss, acc};
+}
+
+// the four qa_lm_score* entry points.  With a vector a.p.Ne / a.p.Nm / a.p.Tc / a.T are the tensors' widths.  No vector is the rectangular
+// call, with the rectangular checks (fn is then the rectangular sibling's name); vectors that hold every row at full width pass the
+// per-row checks and then take the rectangular graph.
+static int score_call(const char* fn, qa_lm* lm, ScoreArgs a, const ScoreLens& n, void* stream) {
+    const Prompt& p = a.p;
+    const bool ragged = n.any(), cm = p.cond_mode;
+    if (!lm || (!cm && !p.mix) || !a.loss_seq || !a.correct_seq || !a.loss || !a.acc || (a.G > 0 && !a.gids) || (a.T > 0 && !a.sids)) {
         set_error("%s: null argument", fn);
         return QA_ERR_INVALID;
     }
-    QA_REQUIRE(cond_mode || (task >= 0 && task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, task);
-    QA_REQUIRE(B > 0 && (cond_mode || n_mix > 0) && global_length >= 0 && semantic_length >= 0, "%s: bad shape", fn);
-    QA_REQUIRE(!cond_mode || (Tc >= 0 && Tc < LM_MAX_POS && (cond != nullptr) == (Tc > 0)),
-               "qa_lm_score_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %lld)", (long long)Tc);
-    QA_REQUIRE(!enroll_feats || n_enroll > 0, "%s: enrollment given with no frames", fn);
-    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, label_smoothing);
-    QA_REQUIRE(n_mix <= LM_MAX_POS && n_enroll <= LM_MAX_POS && B <= (1 << 24), "%s: bad shape", fn);
-    QA_HIP(hipSetDevice(lm->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ragged) QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
+    QA_REQUIRE(cm || (p.task >= 0 && p.task < lm->spec.num_tasks), "%s: task %d out of range (KeyError in the reference)", fn, p.task);
+    const bool cond_ok = p.Tc >= 0 && p.Tc < LM_MAX_POS && (p.cond != nullptr) == (p.Tc > 0);
+    if (!ragged) {
+        QA_REQUIRE(a.B > 0 && (cm || p.Nm > 0) && a.G >= 0 && a.T >= 0, "%s: bad shape", fn);
+        QA_REQUIRE(!cm || cond_ok, "qa_lm_score_cond: cond_embeds [B, T, hidden] with T > 0, or NULL with T = 0 (got T = %lld)", (long long)p.Tc);
+        QA_REQUIRE(!p.enroll || p.Ne > 0, "%s: enrollment given with no frames", fn);
+    } else {  // the widths are bounded before the vectors are read against them
+        const bool sizes_ok = a.B > 0 && a.B <= (1 << 24) && a.G >= 0 && a.G <= LM_MAX_POS && a.T >= 0 && a.T <= LM_MAX_POS;
+        QA_REQUIRE(!cm || (sizes_ok && cond_ok),
+                   "%s: cond_embeds [B, T_max, hidden] with T_max > 0, or NULL with T_max = 0 (got T_max = %lld); bad shape otherwise", fn,
+                   (long long)p.Tc);
+        QA_REQUIRE(cm || (sizes_ok && p.Nm > 0 && p.Nm <= LM_MAX_POS), "%s: bad shape", fn);
+        QA_REQUIRE(!p.enroll || (p.Ne > 0 && p.Ne <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
+    }
+    QA_REQUIRE(a.eps >= 0.0 && a.eps <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, a.eps);
+    if (!ragged) QA_REQUIRE(p.Nm <= LM_MAX_POS && p.Ne <= LM_MAX_POS && a.B <= (1 << 24), "%s: bad shape", fn);
+    ScoreRows R;
+    if (ragged) {
+        const ScoreRowsShape shape = score_rows_shape(a);
+        int64_t row = 0, value = 0;
+        QA_TRY(score_rows_refusal(fn, plan_score_rows(n.enroll, n.mix, n.semantic, shape, &R, &row, &value), shape, row, value));
+        if (!R.uniform) a.rows = &R;  // else the rectangular call: its launches, its bits
+    }
+    QA_HIP(hipSetDevice(lm->device));
     const bool capturing = stream_capturing(s);
-    const Prompt p = cond_mode ? cond_prompt(cond, Tc) : speech_prompt(task, enroll_feats, n_enroll, mix_feats, n_mix);
-    ScoreArgs a{p, (int)B, global_length, semantic_length, reinterpret_cast<const long long*>(global_ids),
-                reinterpret_cast<const long long*>(semantic_ids), label_smoothing, loss_per_seq, reinterpret_cast<long long*>(correct_per_seq), loss, acc};
-    a.rows = rows;
-    const int Lt = global_length + semantic_length + 2 - (cond_mode ? 1 : 0);
+    const int Lt = a.G + a.T + 2 - (cm ? 1 : 0);
     // logits.forced: [B, Lt, V], or packed [sum Lt_b, V] after a call with per-row lengths
-    const size_t tap_rows = rows ? (size_t)rows->total_rows : (size_t)B * Lt;
+    const size_t tap_rows = a.rows ? (size_t)R.total_rows : (size_t)a.B * Lt;
     lm->score_tap_n = -1;
     float* tap = nullptr;
     if (lm->taps) {
@@ -1496,98 +1596,39 @@ static int lm_score_impl(qa_lm* lm, int32_t task, const float* enroll_feats, int
     return QA_OK;
 }
 
+int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
+                const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
+                float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
+    const Prompt p = speech_prompt(task, enroll_feats, narrow(n_enroll), mix_feats, narrow(n_mix));
+    const ScoreArgs a = score_args(p, B, global_ids, global_length, semantic_ids, semantic_length, label_smoothing, loss_per_seq, correct_per_seq, loss, acc);
+    return score_call("qa_lm_score", lm, a, NO_LENS, stream);
+}
+
 int qa_lm_score_ragged(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll, const float* mix_feats,
                        int64_t n_mix_max, const int64_t* n_mix, int64_t B, const int64_t* global_ids, int32_t global_length,
                        const int64_t* semantic_ids, int32_t semantic_length_max, const int64_t* n_semantic, double label_smoothing,
                        float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
-    const char* fn = "qa_lm_score_ragged";
-    auto rectangular = [&] {
-        return qa_lm_score(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, global_ids, global_length, semantic_ids,
-                           semantic_length_max, label_smoothing, loss_per_seq, correct_per_seq, loss, acc, stream);
-    };
-    if (!n_enroll && !n_mix && !n_semantic) return rectangular();  // every row at full width
-    if (!lm || !mix_feats || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
-        (semantic_length_max > 0 && !semantic_ids)) {
-        set_error("%s: null argument", fn);
-        return QA_ERR_INVALID;
-    }
-    // every check comes before the first launch: a refused call has launched nothing and leaves the handle as it was
-    QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
-    QA_REQUIRE(task >= 0 && task < lm->spec.num_tasks, "%s: task %d out of range (KeyError in the reference)", fn, task);
-    QA_REQUIRE(B > 0 && B <= (1 << 24) && n_mix_max > 0 && n_mix_max <= LM_MAX_POS && global_length >= 0 && global_length <= LM_MAX_POS &&
-                   semantic_length_max >= 0 && semantic_length_max <= LM_MAX_POS, "%s: bad shape", fn);
-    QA_REQUIRE(!enroll_feats || (n_enroll_max > 0 && n_enroll_max <= LM_MAX_POS), "%s: enrollment given with no frames", fn);
-    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, label_smoothing);
-    ScoreRowsShape shape;
-    shape.B = B; shape.has_enroll = enroll_feats != nullptr; shape.ne_max = enroll_feats ? n_enroll_max : 0; shape.nm_max = n_mix_max;
-    shape.T_max = semantic_length_max; shape.G = global_length; shape.group_rows = LM_MAX_ROWS; shape.max_pos = LM_MAX_POS;
-    ScoreRows R;
-    int64_t row = 0, value = 0;
-    QA_TRY(score_rows_refusal(fn, plan_score_rows(n_enroll, n_mix, n_semantic, shape, &R, &row, &value), shape, row, value));
-    if (R.uniform) return rectangular();  // the rectangular call: its launches, its bits
-    return lm_score_impl(lm, task, enroll_feats, n_enroll_max, mix_feats, n_mix_max, B, global_ids, global_length, semantic_ids,
-                         semantic_length_max, label_smoothing, loss_per_seq, correct_per_seq, loss, acc, stream, false, nullptr, 0, &R);
-}
-
-int qa_lm_score(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix, int64_t B,
-                const int64_t* global_ids, int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing,
-                float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
-    return lm_score_impl(lm, task, enroll_feats, n_enroll, mix_feats, n_mix, B, global_ids, global_length, semantic_ids, semantic_length,
-                         label_smoothing, loss_per_seq, correct_per_seq, loss, acc, stream, false, nullptr, 0);
+    const Prompt p = speech_prompt(task, enroll_feats, narrow(n_enroll_max), mix_feats, narrow(n_mix_max));
+    const ScoreArgs a = score_args(p, B, global_ids, global_length, semantic_ids, semantic_length_max, label_smoothing, loss_per_seq, correct_per_seq, loss, acc);
+    const ScoreLens n{n_enroll, n_mix, n_semantic};
+    return score_call(n.any() ? "qa_lm_score_ragged" : "qa_lm_score", lm, a, n, stream);
 }
 
 int qa_lm_score_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, const int64_t* global_ids, int32_t global_length,
                      const int64_t* semantic_ids, int32_t semantic_length, double label_smoothing, float* loss_per_seq,
                      int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
-    return lm_score_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_ids, global_length, semantic_ids, semantic_length, label_smoothing,
-                         loss_per_seq, correct_per_seq, loss, acc, stream, true, cond_embeds, T);
+    const Prompt p = cond_prompt(cond_embeds, narrow(T));
+    const ScoreArgs a = score_args(p, B, global_ids, global_length, semantic_ids, semantic_length, label_smoothing, loss_per_seq, correct_per_seq, loss, acc);
+    return score_call("qa_lm_score_cond", lm, a, NO_LENS, stream);
 }
 
 int qa_lm_score_cond_ragged(qa_lm* lm, const float* cond_embeds, int64_t T_max, const int64_t* n_cond, int64_t B, const int64_t* global_ids,
                             int32_t global_length, const int64_t* semantic_ids, int32_t semantic_length_max, const int64_t* n_semantic,
                             double label_smoothing, float* loss_per_seq, int64_t* correct_per_seq, float* loss, float* acc, void* stream) {
-    const char* fn = "qa_lm_score_cond_ragged";
-    auto rectangular = [&] {
-        return qa_lm_score_cond(lm, cond_embeds, T_max, B, global_ids, global_length, semantic_ids, semantic_length_max, label_smoothing,
-                                loss_per_seq, correct_per_seq, loss, acc, stream);
-    };
-    if (!n_cond && !n_semantic) return rectangular();  // every row at full width
-    if (!lm || !loss_per_seq || !correct_per_seq || !loss || !acc || (global_length > 0 && !global_ids) ||
-        (semantic_length_max > 0 && !semantic_ids)) {
-        set_error("%s: null argument", fn);
-        return QA_ERR_INVALID;
-    }
-    // every check comes before the first launch: a refused call has launched nothing and leaves the handle as it was
-    QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
-    QA_REQUIRE(B > 0 && B <= (1 << 24) && T_max >= 0 && T_max < LM_MAX_POS && (cond_embeds != nullptr) == (T_max > 0) && global_length >= 0 &&
-                   global_length <= LM_MAX_POS && semantic_length_max >= 0 && semantic_length_max <= LM_MAX_POS,
-               "%s: cond_embeds [B, T_max, hidden] with T_max > 0, or NULL with T_max = 0 (got T_max = %lld); bad shape otherwise", fn,
-               (long long)T_max);
-    QA_REQUIRE(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing %g outside [0, 1]", fn, label_smoothing);
-    ScoreRowsShape shape;
-    shape.B = B; shape.cond_form = true; shape.nm_max = T_max; shape.T_max = semantic_length_max; shape.G = global_length;
-    shape.group_rows = LM_MAX_ROWS; shape.max_pos = LM_MAX_POS;
-    ScoreRows R;
-    int64_t row = 0, value = 0;
-    QA_TRY(score_rows_refusal(fn, plan_score_rows(nullptr, n_cond, n_semantic, shape, &R, &row, &value), shape, row, value));
-    if (R.uniform) return rectangular();  // the rectangular call: its launches, its bits
-    return lm_score_impl(lm, 0, nullptr, 0, nullptr, 0, B, global_ids, global_length, semantic_ids, semantic_length_max, label_smoothing,
-                         loss_per_seq, correct_per_seq, loss, acc, stream, true, cond_embeds, T_max, &R);
-}
-
-int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
-                        float temperature, int32_t top_k, float top_p, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{0, top_k, top_p, temperature, 0ull}, global_ids, semantic_ids);
-    a.p = cond_prompt(cond_embeds, T);
-    return lm_generate_impl(lm, a, stream);
-}
-
-int qa_lm_generate_cond_sampled(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,
-                                float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
-                                void* stream) {
-    GenArgs a = gen_args(B, global_length, semantic_length, SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed}, global_ids, semantic_ids);
-    a.p = cond_prompt(cond_embeds, T);
-    return lm_generate_impl(lm, a, stream);
+    const Prompt p = cond_prompt(cond_embeds, narrow(T_max));
+    const ScoreArgs a = score_args(p, B, global_ids, global_length, semantic_ids, semantic_length_max, label_smoothing, loss_per_seq, correct_per_seq, loss, acc);
+    const ScoreLens n{nullptr, n_cond, n_semantic};
+    return score_call(n.any() ? "qa_lm_score_cond_ragged" : "qa_lm_score_cond", lm, a, n, stream);
 }
 
 int qa_lm_enable_taps(qa_lm* lm, int on) {

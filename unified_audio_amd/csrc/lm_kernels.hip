@@ -523,15 +523,14 @@ __global__ __launch_bounds__(256) void lm_score_assemble_kernel(float* __restric
         src ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-int launch_lm_score_assemble(float* x, int n, const float* task_vec, const float* enroll_sos, const float* enroll_emb, const float* mix_sos,
-                             const float* mix_emb, int Ne, int Nm, const float* table, const long long* gids, int G, const long long* sids,
-                             int T_max, int V, int goff, int soff, long long* tgt, const int* ne_r, const int* nm_r, const int* T_r,
-                             const int* off_r, int B, int d, hipStream_t s, int drop) {
-    QA_REQUIRE(d % 4 == 0 && n >= 1 && B >= 1 && (!mix_emb || nm_r) && (task_vec || !enroll_emb) && (task_vec || mix_emb || table) &&
-                   (!enroll_emb || ne_r) && (!table || (tgt && T_r && off_r)) && (drop == 0 || drop == 1), "lm_score_assemble: bad launch");
-    const long long total = (long long)B * n * (d / 4);
-    hipLaunchKernelGGL(lm_score_assemble_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, n, task_vec, enroll_sos, enroll_emb,
-                       mix_sos, mix_emb, Ne, Nm, table, gids, G, sids, T_max, V, goff, soff, tgt, ne_r, nm_r, T_r, off_r, B, d, drop);
+int launch_lm_score_assemble(const ScoreAssembleArgs& a, hipStream_t s) {
+    QA_REQUIRE(a.d % 4 == 0 && a.n >= 1 && a.B >= 1 && (!a.mix_emb || a.nm_r) && (a.task_vec || !a.enroll_emb) &&
+                   (a.task_vec || a.mix_emb || a.table) && (!a.enroll_emb || a.ne_r) && (!a.table || (a.tgt && a.T_r && a.off_r)) &&
+                   (a.drop == 0 || a.drop == 1), "lm_score_assemble: bad launch");
+    const long long total = (long long)a.B * a.n * (a.d / 4);
+    hipLaunchKernelGGL(lm_score_assemble_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, a.x, a.n, a.task_vec, a.enroll_sos,
+                       a.enroll_emb, a.mix_sos, a.mix_emb, a.Ne, a.Nm, a.table, a.gids, a.G, a.sids, a.T_max, a.V, a.goff, a.soff, a.tgt, a.ne_r,
+                       a.nm_r, a.T_r, a.off_r, a.B, a.d, a.drop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

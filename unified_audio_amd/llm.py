@@ -109,6 +109,15 @@ def _unsupported(**kw):
                                            f"the cache length, attention weights are never materialised)")
 
 
+def _generate_call(lib, family: str, lengths_arr, do_sample: bool):
+    """The C function of a generate call - `family` (qa_lm_generate / qa_lm_generate_cond), _ragged with a per-row length array, _sampled
+    when sampling - and what the variant adds to the family's arguments: (function, (lengths_arr,) or (), (seed,) or ()).  The seed of a
+    sampled call advances torch's CPU generator, once per call: new draws per call, torch.manual_seed controls reproducibility."""
+    fn = getattr(lib, family + ("_ragged" if lengths_arr is not None else "") + ("_sampled" if do_sample else ""))
+    seed = (int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()),) if do_sample else ()
+    return fn, (lengths_arr,) if lengths_arr is not None else (), seed
+
+
 class LLM_SFT:
     def __init__(self, num_tasks: int = 3, task_map: Optional[Dict[str, int]] = None, feats_dim: int = 768,
                  llm_base_config: Optional[dict] = None, *, device: str | torch.device = "cuda:0"):
@@ -316,34 +325,19 @@ class LLM_SFT:
         gids = torch.empty((B, global_length), dtype=torch.int64, device=self.device)
         sids = torch.empty((B, S), dtype=torch.int64, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        enr_ptr = enr.data_ptr() if enr is not None else None
-        if enroll_lengths is not None:
-            lens = [int(v) for v in (enroll_lengths.tolist() if isinstance(enroll_lengths, torch.Tensor) else enroll_lengths)]
-            if len(lens) != B:
-                raise _lib.QuarkAudioError(-1, f"generate: enroll_lengths has {len(lens)} entries for a batch of {B}")
-            if enr is not None and (enr.dim() != 3 or enr.shape[0] != B):
-                raise _lib.QuarkAudioError(-1, f"generate: enroll_feats must be [{B}, max(enroll_lengths), feats_dim], got {tuple(enr.shape)}")
-            arr = (C.c_int64 * B)(*lens)  # host vector: the library reads it during the call
-            if do_sample:
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-                _lib.check(self._lib.qa_lm_generate_ragged_sampled(self._handle, task, enr_ptr, n_enr, arr, mix.data_ptr(), n_mix, B,
-                                                                   global_length, S, temperature, top_k, top_p, seed, gids.data_ptr(),
-                                                                   sids.data_ptr(), stream))
-            else:
-                _lib.check(self._lib.qa_lm_generate_ragged(self._handle, task, enr_ptr, n_enr, arr, mix.data_ptr(), n_mix, B, global_length,
-                                                           S, temperature, top_k, top_p, gids.data_ptr(), sids.data_ptr(), stream))
-            return gids, sids
-        if do_sample:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())  # advances torch's CPU generator: new draws per call
-            _lib.check(self._lib.qa_lm_generate_sampled(self._handle, task, enr_ptr, n_enr, mix.data_ptr(), n_mix, B, global_length,
-                                                        S, temperature, top_k, top_p, seed, gids.data_ptr(), sids.data_ptr(), stream))
-        else:
-            _lib.check(self._lib.qa_lm_generate(self._handle, task, enr_ptr, n_enr, mix.data_ptr(), n_mix, B, global_length, S,
-                                                temperature, top_k, top_p, gids.data_ptr(), sids.data_ptr(), stream))
+        _, arr = _lib.host_lengths("generate: enroll_lengths", enroll_lengths, B)
+        if arr is not None and enr is not None and (enr.dim() != 3 or enr.shape[0] != B):
+            raise _lib.QuarkAudioError(-1, f"generate: enroll_feats must be [{B}, max(enroll_lengths), feats_dim], got {tuple(enr.shape)}")
+        fn, lens, seed = _generate_call(self._lib, "qa_lm_generate", arr, do_sample)
+        _lib.check(fn(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, *lens, mix.data_ptr(), n_mix, B, global_length, S,
+                      temperature, top_k, top_p, *seed, gids.data_ptr(), sids.data_ptr(), stream))
         return gids, sids
 
-    def _score(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids):
-        """qa_lm_score: (loss_per_seq float [B], correct_per_seq int64 [B], loss, acc 0-dim float, Lt) on the device."""
+    def _score(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths=None,
+               semantic_lengths=None, enroll_lengths=None):
+        """qa_lm_score, or qa_lm_score_ragged with any per-row length: (loss_per_seq float [B], correct_per_seq int64 [B], loss, acc 0-dim
+        float, Lt) on the device.  Lt is G + T + 2, or with per-row lengths Lt_b = G + semantic_lengths[b] + 2 as an int64 [B] device tensor;
+        only the ids inside a row's length are then range-checked."""
         if not self._handle.value:
             raise _lib.QuarkAudioError(-3, "LLM_SFT has no weights: call load_state_dict first")
         task = self.task_map[task_name]  # KeyError like the reference
@@ -354,57 +348,26 @@ class LLM_SFT:
         enr, n_enr = None, 0
         if enroll_mel is not None:  # llm_sft.py:72: only the None test reads enroll_mel
             enr = enroll_feats.to(device=self.device, dtype=torch.float32).contiguous()
-            n_enr = enr.shape[1]
-        g = global_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()  # .long() (llm_sft.py:48-49)
-        sids = semantic_ids.to(device=self.device, dtype=torch.int64).reshape(B, -1).contiguous()
-        G, T = g.shape[1], sids.shape[1]
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        # nn.Embedding's range check of the shifted input ids (the targets are the same ids): one count, one host synchronisation
-        shifted = torch.cat([g.reshape(-1) + self.global_offset, sids.reshape(-1) + self.semantic_offset])
-        if shifted.numel():
-            bad = C.c_int64(0)
-            _lib.check(self._lib.qa_codes_check(shifted.data_ptr(), shifted.numel(), self.vocab_size, C.byref(bad), stream))
-            if bad.value:
-                raise IndexError(f"{bad.value} input ids out of range [0, {self.vocab_size}) after the offsets (global + {self.global_offset}, "
-                                 f"semantic + {self.semantic_offset})")
-        loss_seq = torch.empty(B, dtype=torch.float32, device=self.device)
-        correct = torch.empty(B, dtype=torch.int64, device=self.device)
-        out = torch.empty(2, dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.qa_lm_score(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, mix.data_ptr(), mix.shape[1], B,
-                                         g.data_ptr(), G, sids.data_ptr(), T, self.label_smoothing, loss_seq.data_ptr(), correct.data_ptr(),
-                                         out.data_ptr(), out[1:].data_ptr(), stream))
-        return loss_seq, correct, out[0], out[1], G + T + 2
-
-    def _score_ragged(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths,
-                      semantic_lengths, enroll_lengths):
-        """qa_lm_score_ragged: _score with per-row lengths; the last entry is Lt_b = G + semantic_lengths[b] + 2 as an int64 [B] device
-        tensor.  Only the ids inside a row's length are range-checked."""
-        if not self._handle.value:
-            raise _lib.QuarkAudioError(-3, "LLM_SFT has no weights: call load_state_dict first")
-        task = self.task_map[task_name]  # KeyError like the reference
-        B = int(mix_mel.size(0))
-        mix = mix_feats.to(device=self.device, dtype=torch.float32).contiguous()
-        if mix.dim() != 3 or mix.shape[0] != B:
-            raise _lib.QuarkAudioError(-1, f"mix_feats must be [B={B}, N, feats_dim], got {tuple(mix.shape)}")
-        enr, n_enr = None, 0
-        if enroll_mel is not None:
-            enr = enroll_feats.to(device=self.device, dtype=torch.float32).contiguous()
             if enr.dim() != 3 or enr.shape[0] != B:
                 raise _lib.QuarkAudioError(-1, f"enroll_feats must be [B={B}, N, feats_dim], got {tuple(enr.shape)}")
             n_enr = enr.shape[1]
-        g = global_ids.to(device=self.device, dtype=torch.int64)
+        g = global_ids.to(device=self.device, dtype=torch.int64)  # .long() (llm_sft.py:48-49)
         sids = semantic_ids.to(device=self.device, dtype=torch.int64)
-        g = g.reshape(B, g.numel() // B).contiguous()  # a width of 0 (no id at all) is a valid shape here
+        g = g.reshape(B, g.numel() // B).contiguous()  # a width of 0 (no id at all) is a valid shape
         sids = sids.reshape(B, sids.numel() // B).contiguous()
         G, T = g.shape[1], sids.shape[1]
         _, ne_arr = self._lengths("enroll_lengths", enroll_lengths, B)
         _, nm_arr = self._lengths("mix_lengths", mix_lengths, B)
         t_lens, t_arr = self._lengths("semantic_lengths", semantic_lengths, B)
+        ragged = ne_arr is not None or nm_arr is not None or t_arr is not None
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        # nn.Embedding's range check, over the ids a row really holds: what lies at or behind semantic_lengths[b] is padding
-        t_dev = torch.tensor(t_lens if t_lens is not None else [T] * B, dtype=torch.int64, device=self.device)
-        live = torch.arange(T, device=self.device)[None, :] < t_dev[:, None]
-        shifted = torch.cat([g.reshape(-1) + self.global_offset, sids[live] + self.semantic_offset]).contiguous()
+        # nn.Embedding's range check of the shifted input ids (the targets are the same ids): one count, one host synchronisation.  With
+        # per-row lengths over the ids a row really holds: what lies at or behind semantic_lengths[b] is padding
+        Lt, live_sids = G + T + 2, sids.reshape(-1)
+        if ragged:
+            t_dev = torch.tensor(t_lens if t_lens is not None else [T] * B, dtype=torch.int64, device=self.device)
+            Lt, live_sids = t_dev + (G + 2), sids[torch.arange(T, device=self.device)[None, :] < t_dev[:, None]]
+        shifted = torch.cat([g.reshape(-1) + self.global_offset, live_sids + self.semantic_offset]).contiguous()
         if shifted.numel():
             bad = C.c_int64(0)
             _lib.check(self._lib.qa_codes_check(shifted.data_ptr(), shifted.numel(), self.vocab_size, C.byref(bad), stream))
@@ -414,10 +377,17 @@ class LLM_SFT:
         loss_seq = torch.empty(B, dtype=torch.float32, device=self.device)
         correct = torch.empty(B, dtype=torch.int64, device=self.device)
         out = torch.empty(2, dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.qa_lm_score_ragged(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, ne_arr, mix.data_ptr(),
-                                                mix.shape[1], nm_arr, B, g.data_ptr(), G, sids.data_ptr(), T, t_arr, self.label_smoothing,
-                                                loss_seq.data_ptr(), correct.data_ptr(), out.data_ptr(), out[1:].data_ptr(), stream))
-        return loss_seq, correct, out[0], out[1], t_dev + (G + 2)
+        enr_ptr = enr.data_ptr() if enr is not None else None
+        outs = (self.label_smoothing, loss_seq.data_ptr(), correct.data_ptr(), out.data_ptr(), out[1:].data_ptr(), stream)
+        if ragged:
+            _lib.check(self._lib.qa_lm_score_ragged(self._handle, task, enr_ptr, n_enr, ne_arr, mix.data_ptr(), mix.shape[1], nm_arr, B,
+                                                    g.data_ptr(), G, sids.data_ptr(), T, t_arr, *outs))
+        else:  # qa_lm_score itself, so that its messages keep their prefix
+            _lib.check(self._lib.qa_lm_score(self._handle, task, enr_ptr, n_enr, mix.data_ptr(), mix.shape[1], B, g.data_ptr(), G,
+                                             sids.data_ptr(), T, *outs))
+        return loss_seq, correct, out[0], out[1], Lt
+
+    _score_ragged = _score  # the name tests/test_lm_score_ragged_gpu.py calls it by: the same function, the lengths in the same order
 
     @torch.no_grad()
     def forward(self, task_name: str, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, *, mix_lengths=None,
@@ -432,11 +402,8 @@ class LLM_SFT:
         and semantic_ids[b, :semantic_lengths[b]], with Lt_b = G + semantic_lengths[b] + 2 target rows.  What lies at or behind a row's
         lengths is never read and never range-checked.  loss and acc then pool the rows: the sums over all target rows divided by
         sum_b Lt_b.  With all three None the call is the reference's rectangular one."""
-        if mix_lengths is None and semantic_lengths is None and enroll_lengths is None:
-            _, _, loss, acc, _ = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
-            return loss, acc
-        _, _, loss, acc, _ = self._score_ragged(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths,
-                                                semantic_lengths, enroll_lengths)
+        _, _, loss, acc, _ = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths,
+                                         semantic_lengths, enroll_lengths)
         return loss, acc
 
     def __call__(self, *args, **kwargs):
@@ -448,12 +415,9 @@ class LLM_SFT:
         """forward per sequence: (loss [B], acc [B]) float32 - each sequence's mean label-smoothed KL and accuracy over its own G + T + 2
         target rows (forward's scalars are their means).  A sequence's values do not depend on the batch it is scored in.
         With per-row lengths (see forward) row b's values are over its own Lt_b = G + semantic_lengths[b] + 2 rows."""
-        if mix_lengths is None and semantic_lengths is None and enroll_lengths is None:
-            loss_seq, correct, _, _, Lt = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids)
-            return loss_seq, correct.to(torch.float32) / Lt
-        loss_seq, correct, _, _, Lt = self._score_ragged(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids,
-                                                         mix_lengths, semantic_lengths, enroll_lengths)
-        return loss_seq, correct.to(torch.float32) / Lt.to(torch.float32)
+        loss_seq, correct, _, _, Lt = self._score(task_name, enroll_mel, enroll_feats, mix_mel, mix_feats, global_ids, semantic_ids, mix_lengths,
+                                                  semantic_lengths, enroll_lengths)
+        return loss_seq, correct.to(torch.float32) / (Lt.to(torch.float32) if torch.is_tensor(Lt) else Lt)
 
     def enable_taps(self, on: bool = True):
         """Test hook: make generate record the slice logits of every decode step (qa_lm_enable_taps)."""
@@ -558,31 +522,13 @@ class CustomLlamaModel:
         if cond is not None:
             emb = self.encode_condition(cond, cond_lengths)
             B, T = emb.shape[0], emb.shape[1]
-        if cond_lengths is not None:
-            _, nc_arr = _lib.host_lengths("generate: cond_lengths", cond_lengths, B)
-            gids = torch.empty((B, global_length), dtype=torch.int64, device=self.device)
-            sids = torch.empty((B, semantic_length), dtype=torch.int64, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            ptr = emb.data_ptr() if emb is not None else None
-            if do_sample:
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-                _lib.check(lm._lib.qa_lm_generate_cond_ragged_sampled(lm._handle, ptr, T, nc_arr, B, global_length, semantic_length, temperature,
-                                                                      top_k, top_p, seed, gids.data_ptr(), sids.data_ptr(), stream))
-            else:
-                _lib.check(lm._lib.qa_lm_generate_cond_ragged(lm._handle, ptr, T, nc_arr, B, global_length, semantic_length, temperature, top_k,
-                                                              top_p, gids.data_ptr(), sids.data_ptr(), stream))
-            return gids, sids
+        _, nc_arr = _lib.host_lengths("generate: cond_lengths", cond_lengths, B)
         gids = torch.empty((B, global_length), dtype=torch.int64, device=self.device)
         sids = torch.empty((B, semantic_length), dtype=torch.int64, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        ptr = emb.data_ptr() if emb is not None else None
-        if do_sample:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            _lib.check(lm._lib.qa_lm_generate_cond_sampled(lm._handle, ptr, T, B, global_length, semantic_length, temperature, top_k, top_p,
-                                                           seed, gids.data_ptr(), sids.data_ptr(), stream))
-        else:
-            _lib.check(lm._lib.qa_lm_generate_cond(lm._handle, ptr, T, B, global_length, semantic_length, temperature, top_k, top_p,
-                                                   gids.data_ptr(), sids.data_ptr(), stream))
+        fn, lens, seed = _generate_call(lm._lib, "qa_lm_generate_cond", nc_arr, do_sample)
+        _lib.check(fn(lm._handle, emb.data_ptr() if emb is not None else None, T, *lens, B, global_length, semantic_length, temperature, top_k,
+                      top_p, *seed, gids.data_ptr(), sids.data_ptr(), stream))
         return gids, sids
 
     def llm_forward(self, inputs_embeds, attention_mask=None, past_key_values=None, use_cache=False, output_attentions=False,
