@@ -13,7 +13,7 @@
 // bank-conflict free; each lane fetches 4 consecutive k per read and the (lane>>5) halves take k-groups
 // {0..3},{4..7}: the K order inside a step is permuted identically for A and B, which leaves the sum unchanged.
 // That is the fp32 chain (QA_GEMM_MATH = 0).  The default, split-6 (QA_GEMM_MATH = 1, split4_rne in split_planes.h), runs the same tiles
-// on the bf16 matrix pipe: three bf16 planes per operand in LDS and six v_mfma_f32_32x32x16_bf16 per 16-wide k group.  Two opt-in reduced
+// on the bf16 matrix pipe: three bf16 planes per operand in LDS and, per 16 x 16 output tile, six v_mfma_f32_16x16x32_bf16 per 32-wide k group.  Two opt-in reduced
 // forms keep fewer planes of the same split: split-3 (QA_GEMM_MATH = 2, two planes, three MFMAs) and bf16 (3, one plane, one MFMA).
 // Host side: launch_conv_gemm validates and derives the kernel's parameters, choose_tile is the tile cost model, launch_cfg /
 // launch_instance map a tile to a kernel instance.  The pre-split weight images the PRE instances read live in weight_planes.hip.
@@ -44,7 +44,8 @@ extern "C" int qa_debug_timing(unsigned long long* out, int reset) {
 namespace qa {
 
 // LDS bytes of one conv_gemm configuration (fp32 image with 4-float row padding, or three bf16 planes) and the workgroups per CU that
-// the register budget is tuned for
+// the register budget is tuned for.  Split forms: BK = 32 is two buffers of 32 k, BK = 16 one buffer of 32 k - the bytes of two 16-k buffers,
+// which is what the formula says
 __host__ __device__ constexpr int conv_gemm_lds_bytes(int BM, int BN, int BK, bool split) {
     return (split ? 2 * (BM + BN) * 3 * BK * 2 : 2 * (BM + BN) * (BK + 4) * 4) + BM * 8 * 4;
 }
@@ -110,12 +111,20 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const ConvParams& p, long lo
 // workgroup's MFMAs.
 //
 // SPLIT: split-6 math (above).  The staging threads split their activation / weight float4 after the zero-padding mask and the ELU
-// prologue and store three bf16 planes; a plane row is BK bf16 = BK / 8 16-byte slots, slot s of row r sits at s ^ swz(r) so that the
-// 16 lanes one ds_read_b128 group serves cover all 64 banks.  Per output element the order is fixed: 16-wide k groups ascending, six
-// MFMAs per group in the order above, one fp32 accumulator - independent of BM, BN, BK and the tile order, like the fp32 chain.
+// prologue and store three bf16 planes.  A staged chunk is always one 32-wide k group (CK = 32): a plane row is 32 bf16 = four 16-byte
+// slots, and slot s of row r sits at s ^ (-(r >> 2) & 3).  A fragment read is one ds_read_b128: lane l takes slot l >> 4 of row l & 15 of a
+// 16-row tile.  The instruction serves the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32; in each, the 16 lanes'
+// (row & 3, swizzled slot) pairs are all different - rows 0-3 and 12-15 at slot s, rows 4-11 at slot s ^ 1, XORed with 0, 1 and 3, 2 - so
+// they cover all 64 banks (with the 32x32x16 form's s ^ (r >> 2) the same read was 2-way).  Per output element the order is fixed: 32-wide
+// k groups ascending, the kept plane pairs of a group in the order above, one MFMA each into one fp32 accumulator - independent of BM, BN,
+// BK, LINEAR, PRE, M and the tile order, like the fp32 chain.  K = 16 mod 32: the last group's upper 16 k are stored as zeros in both
+// operands (the staging threads re-read the lower half, so no load leaves the operands), which keeps K % 16 == 0 as the contract; in the
+// table form the two halves of a group look up their own taps, so C_in % 16 == 0 is enough as well.
+// BK names the buffering of a split instance: 32 = two LDS buffers and one barrier per chunk, 16 = one buffer - the LDS bytes of the former
+// two 16-k buffers, so the occupancy stays - and two barriers per chunk, the split + stores of the next chunk between them.
 //
-// PRE (SPLIT only): the weight comes from a pre-split image (p.wp, split_planes.h).  The B tile of a chunk is BN * BK / 128 blocks of
-// 48 image units: 128 / BK rows x BK / 8 slots x 3 planes.  A staging thread owns the same unit of every chunk - one 16-byte global
+// PRE (SPLIT only): the weight comes from a pre-split image (p.wp, split_planes.h).  The B tile of a chunk is BN / 4 blocks of
+// 48 image units: 4 rows x 4 slots x 3 planes.  A staging thread owns the same unit of every chunk - one 16-byte global
 // load, one ds_write_b128, both addresses fixed before the loop - and 16 consecutive lanes write the 256 contiguous (XOR-permuted)
 // bytes that one plane of a block occupies in LDS.  The LDS image is byte for byte the one the in-loop split builds.  Instantiated
 // for the 128-column tiles only (launch_instance).
@@ -133,24 +142,29 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     static_assert(NPL >= 0 && NPL <= 3, "0 = fp32 chain, else the number of bf16 planes");
     static_assert(SPLIT || !PRE, "a pre-split weight image feeds the bf16-plane instances only");
     ConvParams p = p_in;
+    // Split forms stage and consume 32-wide k groups whatever BK says: CK is the k width of a staged chunk.  For them BK names the buffering:
+    // 32 = two LDS buffers of 32 k (one barrier per chunk), 16 = ONE buffer of 32 k (the LDS bytes of two 16-k buffers; two barriers per chunk,
+    // the co-resident workgroups cover the store phase).
+    constexpr int CK = SPLIT ? 32 : BK;
+    constexpr bool ONE_BUF = SPLIT && BK == 16;
     constexpr int LDS = BK + 4;
-    constexpr int RPP = 256 / (BK / 4);  // rows staged per pass: 8 (BK=32) or 4 (BK=16) threads cover one row chunk
+    constexpr int RPP = 256 / (CK / 4);  // rows staged per pass: 8 (32 k) or 4 (16 k) threads cover one row chunk
     constexpr int WTM = BM / WM, WTN = BN / WN;
     constexpr int TM = WTM / 32, TN = WTN / 32;
     constexpr int A_IT = BM / RPP, B_IT = BN / RPP;
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(TM >= 1 && TN >= 1, "wave tile must hold at least one 32x32 MFMA tile");
 
-    constexpr int SMEM_FLOATS = SPLIT ? 2 * (BM + BN) * 3 * BK / 2 : 2 * (BM + BN) * LDS;
+    constexpr int SMEM_FLOATS = SPLIT ? (ONE_BUF ? 1 : 2) * (BM + BN) * 3 * CK / 2 : 2 * (BM + BN) * LDS;
     __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
     __shared__ int s_tap[BM * TAP_WIN];  // source-frame offset (floats, relative to the clip) of (row, tap); -1 = zero padding
     float* sA = smem;
     float* sB = smem + 2 * BM * LDS;
-    // SPLIT image: [buffer][operand A rows, then B rows][plane h, m, l] rows of BK bf16
-    constexpr int PLANE_A = BM * BK * 2, PLANE_B = BN * BK * 2;       // bytes of one plane of one buffer
+    // SPLIT image: [buffer][operand A rows, then B rows][plane h, m, l] rows of CK = 32 bf16
+    constexpr int PLANE_A = BM * CK * 2, PLANE_B = BN * CK * 2;       // bytes of one plane of one buffer
     constexpr int BUF_BYTES = 3 * (PLANE_A + PLANE_B);
     char* const sbytes = reinterpret_cast<char*>(smem);
-    auto swz = [](int row, int slot) { return BK == 16 ? slot ^ ((row >> 3) & 1) : slot ^ ((row >> 2) & 3); };
+    auto swz = [](int row, int slot) { return slot ^ ((0 - (row >> 2)) & 3); };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -179,8 +193,12 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     const int m0 = tm_i * BM;
     const int n0 = tn_i * BN;
 
-    const int ld_row = tid / (BK / 4);          // 0..RPP-1
-    const int ld_c4 = (tid % (BK / 4)) * 4;     // float offset inside the BK-wide K chunk
+    const int ld_row = tid / (CK / 4);          // 0..RPP-1
+    const int ld_c4 = (tid % (CK / 4)) * 4;     // float offset inside the CK-wide K chunk
+    // K = 16 mod 32 (split forms): the last chunk's upper 16 k do not exist.  The threads that stage them (ld_hi; bp_hi for the image units,
+    // whose slot is tid & 3 in every unit) re-read the lower half instead - always inside the operand - and store zeros, in BOTH operands.
+    const bool ld_hi = SPLIT && ld_c4 >= 16, bp_hi = (tid & 2) != 0;
+    const bool k_tail = SPLIT && (p.K & 16) != 0;
 
     // Source-frame table.  The im2col row of output frame t is the ksize frames src(t, j); padding (reflect with the
     // short-input rule of pad1d, or zeros) and repeat_interleave are resolved HERE, once per (row, tap), so that the main
@@ -232,7 +250,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     }
     // PRE: unit u = tid + 256 i of the B tile -> (block of 128 / BK rows, plane, row in block, slot)
     constexpr int BP_BLOCK = 16 * NP;  // units of one block that this form moves: its first NP planes
-    constexpr int BP_UNITS = BN * BK / 128 * BP_BLOCK, BP_IT = PRE ? BP_UNITS / 256 : 1;
+    constexpr int BP_UNITS = BN * CK / 128 * BP_BLOCK, BP_IT = PRE ? BP_UNITS / 256 : 1;
     static_assert(!PRE || (BN == 128 && BP_UNITS % 256 == 0), "the image path exists for the 128-column tiles: every thread moves BP_IT whole units");
     const char* bp_ptr[BP_IT];  // this thread's unit of chunk 0 in the image
     int bp_lds[BP_IT];          // ... and its byte offset in an LDS buffer
@@ -240,14 +258,14 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
 #pragma unroll
         for (int i = 0; i < BP_IT; ++i) {
             const int u = tid + 256 * i, v = u % BP_BLOCK;
-            const int pl = v >> 4, slot = v % (BK / 8);
-            const int row = u / BP_BLOCK * (128 / BK) + (v & 15) / (BK / 8);
+            const int pl = v >> 4, slot = v % (CK / 8);
+            const int row = u / BP_BLOCK * (128 / CK) + (v & 15) / (CK / 8);
             const int n = min(n0 + row, p.N - 1);
             bp_ptr[i] = static_cast<const char*>(p.wp) + plane_byte_offset((long long)n * p.K + slot * 8, pl);
-            bp_lds[i] = 3 * PLANE_A + pl * PLANE_B + row * BK * 2 + swz(row, slot) * 16;
+            bp_lds[i] = 3 * PLANE_A + pl * PLANE_B + row * CK * 2 + swz(row, slot) * 16;
         }
     }
-    const int nk = p.K / BK;
+    const int nk = (p.K + CK - 1) / CK;
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -256,6 +274,15 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // 32-wide k groups: 16 x 16 accumulators of v_mfma_f32_16x16x32_bf16, the same 64 registers per wave tile
+    constexpr int TM16 = WTM / 16, TN16 = WTN / 16;
+    f32x4 acc4[SPLIT ? TM16 : 1][SPLIT ? TN16 : 1];
+    if constexpr (SPLIT) {
+#pragma unroll
+        for (int i = 0; i < TM16; ++i)
+#pragma unroll
+            for (int j = 0; j < TN16; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
     // Staging registers of the NEXT K chunk (native vector type: float4 arrays were left as scratch allocas).  Every
     // iteration loads (the last one re-loads chunk nk-1, harmlessly).
@@ -265,34 +292,54 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
 
 #define QA_LOAD_GLOBAL(KC)                                                                                     \
     {                                                                                                          \
-        const int k0_ = (KC) * BK;                                                                             \
+        const int k0_ = (KC) * CK;                                                                             \
+        const bool tl_ = k_tail && (KC) == nk - 1;            /* block-uniform: the half chunk of K = 16 mod 32 */ \
+        const int kt_ = k0_ - (tl_ && ld_hi ? 16 : 0);        /* its upper-half threads re-read the lower half */  \
         if (LINEAR) {                                                                                          \
-            _Pragma("unroll") for (int i = 0; i < A_IT; ++i) a_reg[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + k0_); \
+            _Pragma("unroll") for (int i = 0; i < A_IT; ++i) a_reg[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + kt_); \
         } else {                                                                                               \
-            const int j_ = k0_ / p.C_in;                                                                       \
-            const int c_ = k0_ - j_ * p.C_in;                                                                  \
-            if (j_ >= jbase + TAP_WIN) { /* block-uniform; only for ksize > TAP_WIN */                         \
-                jbase = j_;                                                                                    \
+            const int j0_ = k0_ / p.C_in;                                                                      \
+            const int c0_ = k0_ - j0_ * p.C_in;                                                                \
+            int j1_ = j0_, c1_ = c0_;                                                                          \
+            if (SPLIT && (p.C_in & 16)) { /* block-uniform: the upper 16 k may belong to the next tap */       \
+                const int kh_ = tl_ ? k0_ : k0_ + 16;                                                          \
+                j1_ = kh_ / p.C_in;                                                                            \
+                c1_ = kh_ - j1_ * p.C_in - 16;                                                                 \
+            }                                                                                                  \
+            if (j1_ >= jbase + TAP_WIN) { /* block-uniform; only for ksize > TAP_WIN */                        \
+                jbase = j0_;                                                                                   \
                 build_taps(jbase);                                                                             \
                 __syncthreads();                                                                               \
             }                                                                                                  \
+            const int j_ = ld_hi ? j1_ : j0_, c_ = ld_hi ? c1_ : c0_;                                          \
             _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                 \
                 const int off_ = s_tap[a_tab[i] + (j_ - jbase)];                                               \
                 a_keep[i] = off_ >= 0 ? 1.f : 0.f;                                                             \
-                a_reg[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + (unsigned)(max(off_, 0) + c_));          \
+                a_reg[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + (max(off_, 0) + c_));                    \
             }                                                                                                  \
         }                                                                                                      \
         if constexpr (PRE) {                                                                                   \
+            const long long bo_ = (long long)(KC) * (CK * 6) - (tl_ && bp_hi ? 2 * PLANE_GROUP_BYTES : 0);     \
             _Pragma("unroll") for (int i = 0; i < BP_IT; ++i)                                                  \
-                bp_reg[i] = *reinterpret_cast<const u32x4*>(bp_ptr[i] + (long long)(KC) * (BK * 6)); \
+                bp_reg[i] = *reinterpret_cast<const u32x4*>(bp_ptr[i] + bo_);                                  \
         } else {                                                                                               \
-            _Pragma("unroll") for (int i = 0; i < B_IT; ++i) b_reg[i] = *reinterpret_cast<const f32x4*>(b_ptr[i] + k0_); \
+            _Pragma("unroll") for (int i = 0; i < B_IT; ++i) b_reg[i] = *reinterpret_cast<const f32x4*>(b_ptr[i] + kt_); \
         }                                                                                                      \
     }
-#define QA_STORE_LDS(BUF)                                                                                      \
+#define QA_STORE_LDS(BUF, KC)                                                                                  \
     { if constexpr (SPLIT) {                                                                                   \
         char* a_ = sbytes + (BUF) * BUF_BYTES;                                                                 \
         const int sl_ = ld_c4 >> 3, in_ = (ld_c4 & 7) * 2;                                                     \
+        if (k_tail && (KC) == nk - 1) { /* block-uniform: zeros into the upper 16 k of the half chunk */       \
+            const f32x4 z4_ = {0.f, 0.f, 0.f, 0.f};                                                            \
+            const u32x4 zu_ = {0u, 0u, 0u, 0u};                                                                \
+            _Pragma("unroll") for (int i = 0; i < A_IT; ++i) a_reg[i] = ld_hi ? z4_ : a_reg[i];                \
+            if constexpr (PRE) {                                                                               \
+                _Pragma("unroll") for (int i = 0; i < BP_IT; ++i) bp_reg[i] = bp_hi ? zu_ : bp_reg[i];         \
+            } else {                                                                                           \
+                _Pragma("unroll") for (int i = 0; i < B_IT; ++i) b_reg[i] = ld_hi ? z4_ : b_reg[i];            \
+            }                                                                                                  \
+        }                                                                                                      \
         _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                     \
             f32x4 v = LINEAR ? a_reg[i] : a_reg[i] * a_keep[i];                                                \
             if (PRO_ELU) {                                                                                     \
@@ -300,7 +347,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
             }                                                                                                  \
             u32x2 h_, m_, l_;                                                                                  \
             split4_planes<NP>(v, h_, m_, l_);                                                                  \
-            const int r_ = ld_row + RPP * i, o_ = r_ * BK * 2 + swz(r_, sl_) * 16 + in_;                       \
+            const int r_ = ld_row + RPP * i, o_ = r_ * CK * 2 + swz(r_, sl_) * 16 + in_;                       \
             *reinterpret_cast<u32x2*>(a_ + o_) = h_;                                                           \
             if constexpr (NP >= 2) *reinterpret_cast<u32x2*>(a_ + PLANE_A + o_) = m_;                          \
             if constexpr (NP == 3) *reinterpret_cast<u32x2*>(a_ + 2 * PLANE_A + o_) = l_;                      \
@@ -313,7 +360,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
         _Pragma("unroll") for (int i = 0; i < B_IT; ++i) {                                                     \
             u32x2 h_, m_, l_;                                                                                  \
             split4_planes<NP>(b_reg[i], h_, m_, l_);                                                           \
-            const int r_ = ld_row + RPP * i, o_ = r_ * BK * 2 + swz(r_, sl_) * 16 + in_;                       \
+            const int r_ = ld_row + RPP * i, o_ = r_ * CK * 2 + swz(r_, sl_) * 16 + in_;                       \
             *reinterpret_cast<u32x2*>(b_ + o_) = h_;                                                           \
             if constexpr (NP >= 2) *reinterpret_cast<u32x2*>(b_ + PLANE_B + o_) = m_;                          \
             if constexpr (NP == 3) *reinterpret_cast<u32x2*>(b_ + 2 * PLANE_B + o_) = l_;                      \
@@ -334,7 +381,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
 
     __syncthreads();  // tap table visible
     QA_LOAD_GLOBAL(0)
-    QA_STORE_LDS(0)
+    QA_STORE_LDS(0, 0)
     __syncthreads();
 
     const int frag_row = lane & 31;
@@ -350,65 +397,70 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     // instruction, the "address phase" lasted as long as the whole MFMA phase).
     constexpr int NKK = BK / 8;
     if constexpr (SPLIT) {
-        // one K chunk = BK / 16 groups of 6 * TM * TN MFMAs; the next chunk's global loads ride in front of group 0 and its split + LDS
-        // stores behind the last group's MFMAs (VALU that depends on nothing the MFMAs write issues underneath them)
-        constexpr int NG = BK / 16;
-        const int sl_h = lane >> 5;
-        int a_off[TM], b_off[TN];  // byte offsets of this lane's fragments (plane h of buffer 0, group 0)
+        // one K chunk = one 32-wide k group: the fragment of a 16-row tile is one ds_read_b128 per plane - lane l reads slot l >> 4 (k 8 (l >> 4) ..
+        // + 7) of row l & 15 - and a 16 x 16 accumulator takes the kept plane pairs in the table's order, one v_mfma_f32_16x16x32_bf16 each.
+        // The activation fragments of the wave's rows stay for the whole group; the weight fragments come column tile by column tile.  The next
+        // chunk's global loads ride in front of the MFMAs.  Two buffers: its split + LDS stores go under the MFMAs from column tile STORE_J on, one barrier
+        // per chunk.  ONE_BUF: they wait behind a second barrier - everybody has read the buffer - and the co-resident workgroups cover them.
+        // the 256-row tile (8 row tiles per wave) reads its activation fragments in four blocks: all of them beside the staging registers would not
+        // fit two workgroups per CU
+        constexpr int RB = BM == 256 ? 4 : 1;
+        // two buffers: the column tile whose MFMAs carry the next chunk's split + LDS stores.  A 16-cycle MFMA leaves the VALU 8 cycles, so the
+        // ~500 issue cycles of a 128 x 128 chunk's split need most of the chunk's 96 MFMAs: under the last of four column tiles the instance ran
+        // 10 % behind the 32x32x16 form, from the second on 10 % ahead of it
+        constexpr int STORE_J = TN16 > 1 ? 1 : 0;
+        const int fr = lane & 15, sl = lane >> 4;
+        int a_off[TM16], b_off[TN16];  // byte offsets of this lane's fragments (plane h of buffer 0)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int r = wm * WTM + i * 32 + frag_row;
-            a_off[i] = r * BK * 2 + swz(r, sl_h) * 16;
+        for (int i = 0; i < TM16; ++i) {
+            const int r = wm * WTM + i * 16 + fr;
+            a_off[i] = r * CK * 2 + swz(r, sl) * 16;
         }
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int r = wn * WTN + j * 32 + frag_row;
-            b_off[j] = 3 * PLANE_A + r * BK * 2 + swz(r, sl_h) * 16;
+        for (int j = 0; j < TN16; ++j) {
+            const int r = wn * WTN + j * 16 + fr;
+            b_off[j] = 3 * PLANE_A + r * CK * 2 + swz(r, sl) * 16;
         }
         for (int kc = 0; kc < nk; ++kc) {
-            const int cur = kc & 1;
+            const int cur = ONE_BUF ? 0 : kc & 1;
             const int nxt = min(kc + 1, nk - 1);
             const char* base = sbytes + cur * BUF_BYTES;
+            QA_LOAD_GLOBAL(nxt)
+            // RB row blocks: the activation fragments of TM16 / RB row tiles at a time, the weight fragments read once per block
+            static_for<RB>([&](auto rb_c) {
+                constexpr int i0 = decltype(rb_c)::value * (TM16 / RB);
+                bf16x8 af[NP][TM16 / RB];
 #pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                // group g of a row is slots 2g (k 0..7) and 2g + 1 (k 8..15); swz XORs the slot with row bits, so the swizzled slot of
-                // 2g + h is (h ^ x) ^ 2g: the byte offset of group 0, XOR 32 g
-                bf16x8 af[NP][TM], bf[NP][TN];
+                for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {
+                    for (int i = 0; i < TM16 / RB; ++i) af[pl][i] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_A + a_off[i0 + i]);
 #pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        af[pl][i] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_A + (a_off[i] ^ (32 * g)));
+                for (int j = 0; j < TN16; ++j) {
+                    bf16x8 bf[NP];
 #pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        bf[pl][j] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_B + (b_off[j] ^ (32 * g)));
-                }
-                if (g == 0) QA_LOAD_GLOBAL(nxt)
-                if (g == NG - 1) QA_STORE_LDS(cur ^ 1)
-                // operands swapped as in the fp32 loop below; plane pairs in the order of split_planes.h (PAIR_A: activation, PAIR_B: weight)
-                if constexpr (NP == 3) {
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PAIR_B[q]][j], af[PAIR_A[q]][i], acc[i][j], 0, 0, 0);
-                } else {  // split-3: hm, mh, hh; bf16: hh - the kept pairs, in the table's order
+                    for (int pl = 0; pl < NP; ++pl) bf[pl] = *reinterpret_cast<const bf16x8*>(base + pl * PLANE_B + b_off[j]);
+                    if (!ONE_BUF && i0 + TM16 / RB == TM16 && j == STORE_J) QA_STORE_LDS(cur ^ 1, nxt)
+                    // operands swapped as in the fp32 loop below; plane pairs in the order of split_planes.h (PAIR_A: activation, PAIR_B: weight)
                     static_for<6>([&](auto q_c) {
                         constexpr int q = decltype(q_c)::value;
                         if constexpr (pair_kept(q, NP)) {
 #pragma unroll
-                            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                                for (int j = 0; j < TN; ++j)
-                                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[PAIR_B[q]][j], af[PAIR_A[q]][i], acc[i][j], 0, 0, 0);
+                            for (int i = 0; i < TM16 / RB; ++i)
+                                acc4[i0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[PAIR_B[q]], af[PAIR_A[q]][i], acc4[i0 + i][j], 0, 0, 0);
                         }
                     });
                 }
-                __builtin_amdgcn_sched_barrier(0);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ONE_BUF) {
+                if (kc + 1 < nk) {  // block-uniform
+                    __syncthreads();  // every wave has read chunk kc
+                    QA_STORE_LDS(0, nxt)
+                    __syncthreads();
+                }
+            } else {
+                __syncthreads();
             }
-            __syncthreads();
         }
     } else
     for (int kc = 0; kc < nk; ++kc) {
@@ -432,7 +484,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
                 for (int j = 0; j < TN; ++j) bf[nb][j] = *reinterpret_cast<const f32x4*>(b + j * 32 * LDS + (kk + 1) * 8);
             }
             if (kk == QA_LOAD_AT) QA_LOAD_GLOBAL(nxt)
-            if (kk == NKK - 1) QA_STORE_LDS(cur ^ 1)
+            if (kk == NKK - 1) QA_STORE_LDS(cur ^ 1, nxt)
             // operands swapped on purpose: the W fragment is the MFMA's row operand and the activation fragment its
             // column operand, so D = (A W^T)^T and every lane ends up with 4 CONSECUTIVE output channels of one output
             // row per register quad -> the epilogue moves float4, not scalars
@@ -482,6 +534,13 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     static_for<TM>([&](auto i_c) {
         constexpr int i = decltype(i_c)::value;
         __syncthreads();  // operand buffers (i = 0) / previous pass (i > 0) no longer read
+        if constexpr (SPLIT) {  // 16 x 16 accumulators: row <- lane & 15, channels 4 (lane >> 4) .. + 3
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int j = 0; j < TN16; ++j)
+                    *reinterpret_cast<f32x4*>(stage + (wm * 32 + h * 16 + (lane & 15)) * EP_LD + wn * WTN + j * 16 + 4 * (lane >> 4)) = acc4[2 * i + h][j];
+        } else {
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -489,6 +548,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
                 const f32x4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
                 *reinterpret_cast<f32x4*>(stage + (wm * 32 + row_l) * EP_LD + wn * WTN + j * 32 + 8 * g + col_h) = v;
             }
+        }
         __syncthreads();
 #pragma unroll 1
         for (int r = ep_r0; r < EP_ROWS; r += 256 / EP_C4) {
@@ -586,7 +646,8 @@ static void launch_instance(const ConvParams& p, long long tiles, hipStream_t st
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
 }
 
-// The K-chunk width of a launch (launch_cfg; choose_tile prices the instance this picks).
+// The K-chunk width of a launch (launch_cfg; choose_tile prices the instance this picks).  For the split forms "BK = 16" is the one-buffer
+// instance (32-wide chunks, two barriers each) and "BK = 32" the two-buffer one: same LDS bytes, occupancy and trade-off as the widths below.
 // BK = 16 chunks need 45 KB / 35 KB of LDS, so 3-4 workgroups are co-resident per CU (BK = 32: 2) and cover each other's barriers, prologues and
 // epilogues: +10..25 % on the K = 512 layers of the aggregator stacks, +3..5 % on K = 768..3072 (per-shape sweep, tools/gemm_bench.py with
 // QA_GEMM_BK16=0 / default).  QA_GEMM_BK16 = largest K that takes the BK = 16 variant.
@@ -612,12 +673,13 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     const long long tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
     const bool linear = is_linear(p), elu = p.prologue == ACT_ELU;
     const bool bk16 = takes_bk16(BM, BN, tiles, p.K, p.C_in, elu);
-    // the K loop runs K / BK whole chunks and the table form reads each chunk from ONE tap: a BK that does not divide K (and, with the
-    // table, C_in) would drop the tail of K or read past a tap's C_in channels - into the next frame or the next channel group
-    const int bk = bk16 ? 16 : 32;
+    // the fp32 chain's K loop runs K / BK whole chunks and its table form reads each chunk from ONE tap: a BK that does not divide K (and, with
+    // the table, C_in) would drop the tail of K or read past a tap's C_in channels - into the next frame or the next channel group.  The split
+    // forms stage 32-wide groups as two 16-wide halves, each from its own tap, and zero-fill the missing half of K = 16 mod 32: multiples of 16
+    const int bk = bk16 || gemm_planes(p) > 0 ? 16 : 32;
     const bool table = BM != 256 && (!linear || elu);  // the ELU prologue exists in the table form only
     QA_REQUIRE(p.K % bk == 0 && (!table || p.C_in % bk == 0),
-               "conv_gemm: the %dx%d tile's BK = %d K chunk does not divide K=%d / C_in=%d", BM, BN, bk, p.K, p.C_in);
+               "conv_gemm: the %dx%d tile's K chunk needs K=%d / C_in=%d to be multiples of %d", BM, BN, p.K, p.C_in, bk);
     const bool prof = profile_enabled();
     if (prof) {
         const double n = p.algo_n ? p.algo_n : p.N, k = p.algo_k ? p.algo_k : p.K;
@@ -733,11 +795,12 @@ static int choose_tile(const ConvParams& p) {
 }
 
 int launch_conv_gemm(const ConvParams& p, hipStream_t stream) {
-    // a K chunk never straddles two taps: C_in must be a multiple of the chunk width (16 for the BK = 16 variants, which exist for N > 32 without the
-    // ELU prologue - e.g. the 48-channel groups of the SSL positional convolution; 32 otherwise)
+    // fp32 chain: a K chunk never straddles two taps, so C_in must be a multiple of the chunk width (16 for the BK = 16 variants, which exist for
+    // N > 32 without the ELU prologue - e.g. the 48-channel groups of the SSL positional convolution; 32 otherwise).  The split forms take any
+    // multiple of 16 in every instance: the 16-wide halves of a k group look up their own taps, and a missing last half is zero-filled
     QA_REQUIRE(p.K % 16 == 0 && p.C_in % 16 == 0, "conv_gemm: K=%d / C_in=%d must be multiples of 16", p.K, p.C_in);
-    QA_REQUIRE(p.C_in % 32 == 0 || (p.N > 32 && p.prologue != ACT_ELU),
-               "conv_gemm: C_in=%d is not a multiple of 32 (only supported for N > 32 without the ELU prologue)", p.C_in);
+    QA_REQUIRE(p.C_in % 32 == 0 || gemm_planes(p) > 0 || (p.N > 32 && p.prologue != ACT_ELU),
+               "conv_gemm: C_in=%d is not a multiple of 32 (the fp32 chain supports that only for N > 32 without the ELU prologue)", p.C_in);
     QA_REQUIRE((p.ldx % 4) == 0, "conv_gemm: ldx=%lld must be a multiple of 4 floats", p.ldx);
     QA_REQUIRE((long long)p.T_in * p.ldx < (1LL << 31), "conv_gemm: one batch item spans %lld floats (limit 2^31)",
                (long long)p.T_in * p.ldx);

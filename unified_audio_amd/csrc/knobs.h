@@ -13,9 +13,9 @@ namespace qa {
     X(SERIAL, "QA_SERIAL", 0, "1: no internal stream concurrency (every kernel alone on the device; = qa_set_serial)")           \
     X(GEMM_CFG, "QA_GEMM_CFG", -1, "force the conv_gemm tile: 0 = 128x32, 1 = 128x64, 2 = 128x128, 3 = 64x128, 4 = 64x64, 5 = 256x128 (LINEAR layers; else 128x128) (-1: cost model)")             \
     X(GEMM_256, "QA_GEMM_256", 0, "r06 experiment: 256x128 block tile (4 waves, 4x2 accumulators each) for LINEAR layers with M >= 8000 and N >= 1024; value = its efficiency relative to 128x128 in 1/1000 for the cost model (0: never chosen; QA_GEMM_CFG=5 forces it)") \
-    X(GEMM_BK16, "QA_GEMM_BK16", 1 << 30, "largest K that takes the BK = 16 K-chunk variant")                                     \
+    X(GEMM_BK16, "QA_GEMM_BK16", 1 << 30, "largest K that takes the BK = 16 K-chunk variant (fp32 chain: 16-wide chunks; split forms: one LDS buffer of 32 k instead of two)")                                     \
     X(GEMM_BK16_MIN_TILES, "QA_GEMM_BK16_MIN_TILES", 384, "fewest tiles of a launch that take BK = 16")                          \
-    X(GEMM_MATH, "QA_GEMM_MATH", 1, "conv_gemm arithmetic: 1 = split-6 (operands split into three bf16 planes, six v_mfma_f32_32x32x16_bf16 per 16-wide k group, fp32 accumulation), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32); opt-in reduced precision: 2 = split-3 (two planes, products hm, mh, hh: operands exact to 2^-16), 3 = bf16 (one plane, one product: bf16 operands, fp32 accumulation); any other value = split-6; launches marked math_fp32 (the UniSE LM) keep the fp32 chain") \
+    X(GEMM_MATH, "QA_GEMM_MATH", 1, "conv_gemm arithmetic: 1 = split-6 (operands split into three bf16 planes, six v_mfma_f32_16x16x32_bf16 per 32-wide k group, fp32 accumulation), 0 = the fp32 chain (v_mfma_f32_32x32x2_f32); opt-in reduced precision: 2 = split-3 (two planes, products hm, mh, hh: operands exact to 2^-16), 3 = bf16 (one plane, one product: bf16 operands, fp32 accumulation); any other value = split-6; launches marked math_fp32 (the UniSE LM) keep the fp32 chain") \
     X(GEMM_PRESPLIT, "QA_GEMM_PRESPLIT", 1, "split-6 weights from a pre-split image: a weight store builds the three bf16 planes of all its weights once, at load (6 bytes per weight beside the fp32 blob; not built when 0 at load time), and conv_gemm's 128-column tiles copy them into LDS instead of splitting the weight tile in the K loop (narrower tiles keep the in-loop split); 0 at launch = ignore the image and split in the loop; same bits either way") \
     X(GEMM_LINEAR, "QA_GEMM_LINEAR", 1, "table-free K loop for ksize-1 layers")                                                  \
     X(GEMM_XCD, "QA_GEMM_XCD", 1, "XCD-aware tile order")                                                                        \

@@ -14,13 +14,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // one operand fragment of v_mfma_f32_32x32x16_bf16
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // one operand fragment of v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16
 typedef float f32x16 __attribute__((ext_vector_type(16)));  // one 32x32 accumulator
 
 // Split-6 math (QA_GEMM_MATH = 1).  Each operand is split, exactly, into three bf16 planes x = h + m + l by round-to-nearest-even:
 // h = rne(x), m = rne(x - h), l = x - h - m.  Both subtractions are exact and l keeps <= 8 significant bits (sign borrowing), so
-// |m| <= 2^-8 |x| and |l| <= 2^-16 |x|.  A 16-wide k group then takes six v_mfma_f32_32x32x16_bf16 (every bf16 x bf16 product is exact
-// in fp32), smallest terms first: hl, lh, mm, hm, mh, hh (activation plane first).  The dropped ml, lm and ll are each <= 2^-24 |ab|,
+// |m| <= 2^-8 |x| and |l| <= 2^-16 |x|.  A k group - 32 wide in conv_gemm (v_mfma_f32_16x16x32_bf16), 16 wide in attention
+// (v_mfma_f32_32x32x16_bf16) - then takes six MFMAs (every bf16 x bf16 product is exact in fp32), smallest terms first: hl, lh, mm, hm,
+// mh, hh (activation plane first).  The dropped ml, lm and ll are each <= 2^-24 |ab|,
 // the size of one fp32 rounding, of random sign.  Non-finite x: h = x and m = l = 0 (the residual is zeroed when it is not finite),
 // so inf and NaN reach the sum through hh exactly as through the fp32 chain.  A finite |x| that rounds past the largest bf16
 // (>= 2^128 (1 - 2^-9)) becomes h = inf.
@@ -98,7 +99,7 @@ __device__ __forceinline__ bf16x8 frag8(const u32x2 lo, const u32x2 hi) {  // tw
 // Pre-split weight image (QA_GEMM_PRESPLIT).  The image of a float array w[0 .. n), n % 8 == 0, holds 6 bytes per weight: every
 // aligned group of 8 floats becomes three consecutive 16-byte units - its h, m and l planes, 8 bf16 each, in the order of the floats.
 // A unit is exactly one 16-byte slot of one plane row of the K loop's LDS image, so a staging thread moves it with one 16-byte global
-// load and one ds_write_b128, and the 16-wide chunk of a weight row is 96 contiguous bytes.  The address depends on the float's index
+// load and one ds_write_b128, and the 32-wide chunk of a weight row is 192 contiguous bytes.  The address depends on the float's index
 // alone: the image of a row slice w + r * K (K % 8 == 0) is the image of w advanced by plane_byte_offset(r * K, 0).
 constexpr int PLANE_GROUP_BYTES = 48;  // image bytes per 8 floats
 __host__ __device__ constexpr long long plane_byte_offset(long long index, int plane) {
