@@ -664,6 +664,32 @@ int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_f
                                   float temperature, int32_t top_k, float top_p, uint64_t seed, int64_t* global_ids, int64_t* semantic_ids,
                                   void* stream);
 
+/* qa_lm_generate / qa_lm_generate_sampled over a batch whose rows differ in any of their three lengths.  The layouts are
+ * qa_lm_generate_ragged's with the maxima as strides: enroll_feats [B, n_enroll_max, feats_dim] or NULL, mix_feats [B, n_mix_max, feats_dim],
+ * semantic_ids [B, semantic_length_max].  Three optional HOST int64 [B] vectors, read during the call only, NULL for "every row at full width":
+ *   n_enroll[b]    1 .. n_enroll_max (only with an enrollment)
+ *   n_mix[b]       1 .. n_mix_max
+ *   n_semantic[b]  0 .. semantic_length_max (0: the row returns global ids only)
+ * Row b behaves as qa_lm_generate(_sampled) for that sequence ALONE on enroll_feats[b, :n_enroll[b]] and mix_feats[b, :n_mix[b]] with
+ * semantic_length = n_semantic[b]: prompt of L_b = 1 + (1 + n_enroll[b]) + 1 + n_mix[b] positions (2 + n_mix[b] without an enrollment), the
+ * global phase from position L_b, then n_semantic[b] semantic steps.  global_length is common to the batch.
+ *   semantic_ids[b, t] for t >= n_semantic[b] is exactly -1 (the value qa_bicodec_detokenize_ragged ignores); the tap logits.semantic[b, t, :]
+ *   is exactly 0 there.  Frames at or behind a row's counts never enter any row's arithmetic (they may hold anything, NaN included).
+ * A row that has taken its last step stops reading and writing its keys and values, and a chain of rows stops at its own longest row.
+ * With every given vector at full width the call is qa_lm_generate(_sampled), with n_enroll alone qa_lm_generate_ragged(_sampled): the same
+ * launches, the same bits.  Refused before anything is launched, the handle staying usable: a length out of range (the message names the row
+ * and its value), n_enroll without enroll_feats, a NULL mix_feats or output, the longest possible row - prompt at the maxima + global_length
+ * + 1 + semantic_length_max - beyond 4096 positions, and, with n_mix or n_semantic given, a stream that is being captured (the lengths are
+ * host data). */
+int qa_lm_generate_rows(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                        const float* mix_feats, int64_t n_mix_max, const int64_t* n_mix, int64_t B, int32_t global_length,
+                        int32_t semantic_length_max, const int64_t* n_semantic, float temperature, int32_t top_k, float top_p,
+                        int64_t* global_ids, int64_t* semantic_ids, void* stream);
+int qa_lm_generate_rows_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                                const float* mix_feats, int64_t n_mix_max, const int64_t* n_mix, int64_t B, int32_t global_length,
+                                int32_t semantic_length_max, const int64_t* n_semantic, float temperature, int32_t top_k, float top_p,
+                                uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream);
+
 /* LLM_SFT.forward (llm_sft.py:37-90): teacher-forced scoring of given token streams.  With Lt = global_length + semantic_length + 2,
  * input_ids = [0, global_ids + 3, 1, semantic_ids + 3 + global_size] and target_ids = [global_ids + 3, 1, semantic_ids + 3 + global_size, 2];
  * the prompt is generate's, the body runs causally over all prompt + Lt positions from position 0, and output_head covers the FULL

@@ -33,8 +33,8 @@ def build_model(a, config, dev):
         lm = qa.LLM_SFT(device=dev).load_state_dict(synth.lm_state_dict(4321))
         fx = qa.SSLFeatureExtractor(qa.SPEC_WAVLM_BASE_PLUS, device=dev).load_state_dict(synth.ssl_state_dict(qa.SPEC_WAVLM_BASE_PLUS))
         bic = qa.BiCodec(device=dev).load_state_dict(synth.bicodec_state_dict(77))
-        return Model(config, device=dev, semantic_model=fx, tokenizer=qa.BiCodecTokenizer(model=bic), dnn=lm)
-    return Model(config, device=dev)
+        return Model(config, device=dev, semantic_model=fx, tokenizer=qa.BiCodecTokenizer(model=bic), dnn=lm, tail=a.tail)
+    return Model(config, device=dev, tail=a.tail)
 
 
 def batches_from_files(a, dev):
@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--enroll_duration", type=float, default=5.0)
     ap.add_argument("--synthetic", action="store_true", help="seeded random weights at the published sizes instead of checkpoints")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--tail", choices=["wrap", "trim"], default="wrap",
+                    help="wrap: the reference's wrap-padding of every file to a multiple of 5 s; trim: the last segment at its own length "
+                         "(faster on short files, NOT the reference's tokens for that segment)")
     a = ap.parse_args()
     config = {}
     if a.config:

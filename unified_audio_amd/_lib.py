@@ -234,6 +234,12 @@ SYMBOLS = {
     "qa_lm_generate_ragged_sampled": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                                 C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_uint64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    "qa_lm_generate_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                      C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_float, C.c_int32,
+                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_lm_generate_rows_sampled": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                              C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_float,
+                                              C.c_int32, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_lm_score": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
                               C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_lm_score_ragged": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,

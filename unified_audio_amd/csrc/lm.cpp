@@ -266,6 +266,7 @@ struct LMBuffers {
     float *logits, *pmax;  // head, pick / sample of generate's step
     int* pidx;
     int* off;  // ragged generate, ragged session steps: per-row position offsets L_b - L_max <= 0 (lm_decode.h GemvArgs::off); nullptr everywhere else
+    int* stop;  // generate with per-row semantic lengths: the rows' semantic steps (lm_decode.h GemvArgs::stop); nullptr everywhere else
     long long *ids_g, *ids_s;
     int cap;              // cache capacity
     size_t layer_stride;  // floats between two layers of kc / vc; 0: B * cap * d (generate's arena); a qa_lm_cache: max_batch * max_len * d
@@ -361,7 +362,9 @@ int lm_body(qa_lm* lm, Ctx& c, LMBuffers& b, int B, int n, int pos0, int max_len
 // into a hipGraph and replayed.
 // fused_layers: the layers of the step (launches 1 - 5); [lo, lo + width): the head slice the last layer's prefetch plane warms
 // (width 0: no head follows - a session step, which ends in the final RMSNorm instead)
-int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStream_t s, int pos, const StepIO& io) {
+// stop / col (the semantic phase of a generate with per-row semantic lengths): the rows' step counts and the step's column
+int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStream_t s, int pos, const StepIO& io, const int* stop = nullptr,
+                 int col = -1) {
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H, I = sp.intermediate;
     const float scale = 1.0f / std::sqrt((float)hd);
@@ -406,11 +409,12 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
         else if (i == 0) { q.tok = b.tok; q.table = lm->codec_emb; }
         q.w = L.qkv_dec; q.N = 3 * d; q.K = d;
         q.rope = lm->rope; q.q = sb.q; q.kc = kc; q.vc = vc; q.kv_bstride = kv_bstride;
+        q.stop = stop; q.col = col;
         PfArgs qpf{};
         if (pfk & 1) pf_region(qpf, 0, L.o.w, (long long)nt_o * d * 4, d / nt_o);
         QA_TRY(launch_lm_gemv(q, GM_QKV, lm->nt_qkv, s, &qpf));
         // 2. attention over the cache (pos + 1 keys), split over S_att workgroups per (sequence, head)
-        QA_TRY(launch_lm_attn(sb.q, d, kc, vc, kv_bstride, d, sb.att_part, B, H, hd, S_att, sb.att_tps, sb.state, scale, pos, s, b.off));
+        QA_TRY(launch_lm_attn(sb.q, d, kc, vc, kv_bstride, d, sb.att_part, B, H, hd, S_att, sb.att_tps, sb.state, scale, pos, s, b.off, stop, col));
         // 3. merge of the partials + o_proj + residual
         GemvArgs o = a;
         o.att_part = sb.att_part; o.S = S_att;
@@ -450,10 +454,10 @@ int fused_layers(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, hipStr
 // tap (taps on): [B][tap_cols][width] logits of the phase's steps for these B rows, column = the step's col
 int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long long* ids, int ids_ld, int keep, const SampleCfg& sc,
                hipStream_t s, int pos, int col,  // pos / col >= 0: host-driven loop; -1: read from the device state (captured step)
-               float* tap, int tap_cols) {
+               float* tap, int tap_cols, const int* stop = nullptr) {  // stop: as fused_layers, read with this step's `col`
     const qa_lm_spec& sp = lm->spec;
     const int d = sp.hidden, H = sp.n_heads, hd = d / H;
-    QA_TRY(fused_layers(lm, b, B, lo, width, s, pos, StepIO()));
+    QA_TRY(fused_layers(lm, b, B, lo, width, s, pos, StepIO(), stop, col));
     // 6. final RMSNorm (weight folded into output_head) + the rows of output_head inside the active vocabulary slice (the range
     //    mask of llm_sft.py:150-153 / :180-182 sets everything else to -inf) + per-tile arg-max
     const int nt = head_nt(width);
@@ -468,12 +472,12 @@ int fused_step(qa_lm* lm, const LMBuffers& b, int B, int lo, int width, long lon
         hpf.n_tiles[0] = 3 * d / lm->nt_qkv;
     }
     QA_TRY(launch_lm_gemv(hg, GM_HEAD, nt, s, &hpf));
-    if (tap) QA_TRY(launch_lm_tap(b.logits, width, B, tap, tap_cols, b.step.state, col, s));
+    if (tap) QA_TRY(launch_lm_tap(b.logits, width, B, tap, tap_cols, b.step.state, col, s, stop));
     // 7. next token
     if (!sc.do_sample) {
-        QA_TRY(launch_lm_pick(b.pmax, b.pidx, width / nt, B, lo, b.tok, ids, ids_ld, keep, b.step.state, col, s));
+        QA_TRY(launch_lm_pick(b.pmax, b.pidx, width / nt, B, lo, b.tok, ids, ids_ld, keep, b.step.state, col, s, stop));
     } else {
-        QA_TRY(launch_lm_sample(b.logits, width, width, B, lo, sc.top_k, sc.top_p, sc.temperature, 1, b.tok, ids, ids_ld, keep, b.step.state, s));
+        QA_TRY(launch_lm_sample(b.logits, width, width, B, lo, sc.top_k, sc.top_p, sc.temperature, 1, b.tok, ids, ids_ld, keep, b.step.state, s, stop));
         QA_TRY(launch_lm_advance(b.step.state, s));
     }
     return QA_OK;
@@ -494,6 +498,8 @@ struct Chain {
     int b0 = 0, B = 0;  // sequences [b0, b0 + B) of the call
     LMBuffers b{};
     float *emix = nullptr, *eenr = nullptr;
+    int* ints = nullptr;  // per-row mixture / semantic lengths only: the chain's GR_* arrays (write_gen_ints)
+    int steps_s = 0;      // semantic steps of THIS chain: its longest row's
     hipStream_t s = nullptr;
 };
 
@@ -508,6 +514,9 @@ struct Prompt {
     const float* enroll = nullptr; int Ne = 0;  // nullptr and 0: no enrollment
     const float* mix = nullptr; int Nm = 0;
     const int* ne_rows = nullptr;
+    // generate with per-row mixture lengths (HOST, [B]): row b's mixture frames, 1 .. Nm.  ne_rows is then given too
+    // (every entry Ne where the caller passed no n_enroll), and the prompt is assembled per row the way the scoring calls assemble theirs
+    const int* nm_rows = nullptr;
 };
 
 Prompt speech_prompt(int32_t task, const float* enroll_feats, int64_t n_enroll, const float* mix_feats, int64_t n_mix) {
@@ -545,7 +554,9 @@ void speech_assemble(ScoreAssembleArgs& as, const qa_lm* lm, const Prompt& p, co
     as.mix_sos = lm->mix_sos; as.mix_emb = emix; as.Nm = p.Nm; as.nm_r = nm_r;
 }
 
-int build_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix, float* eenr, float* out, int* off) {
+// rows_r (p.nm_rows only; device, written by the caller): the group's [ne | nm] counts, gb entries each, beside the offsets already in `off`
+int build_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix, float* eenr, float* out, int* off,
+                 const int* rows_r = nullptr) {
     const int d = lm->spec.hidden;
     if (p.cond_mode) {
         if (p.ne_rows) QA_RUN(c, launch_lm_offsets(off, p.ne_rows + b0, p.Tc, gb, c.stream));
@@ -553,6 +564,13 @@ int build_prompt(qa_lm* lm, Ctx& c, const Prompt& p, int b0, int gb, float* emix
         return QA_OK;
     }
     QA_TRY(adapt_prompt(lm, c, p, b0, gb, emix, eenr));
+    if (p.nm_rows) {  // row b left-aligned over its own Lp_b positions, zeros behind: the scoring calls' assembly, without a table
+        ScoreAssembleArgs as;
+        as.x = out; as.n = prompt_len(p); as.B = gb; as.d = d;
+        speech_assemble(as, lm, p, emix, eenr, rows_r, rows_r + gb);
+        QA_RUN(c, launch_lm_score_assemble(as, c.stream));
+        return QA_OK;
+    }
     if (p.ne_rows) QA_RUN(c, launch_lm_offsets(off, p.ne_rows + b0, p.Ne, gb, c.stream));
     QA_RUN(c, launch_assemble_prompt(out, lm->task_emb + (size_t)p.task * d, p.enroll ? lm->enroll_sos : nullptr, eenr, lm->mix_sos, emix, gb,
                                      p.Ne, p.Nm, d, c.stream, off));
@@ -564,7 +582,13 @@ struct GenArgs {
     int B, G, S;
     SampleCfg sc;
     int64_t *gids, *sids;
+    // per-row semantic lengths (HOST, [B], 0 .. S): row b takes stop_rows[b] semantic steps, S is then the ids' stride
+    // and the longest possible row's count.  nullptr: every row takes S
+    const int* stop_rows = nullptr;
 };
+
+// The device ints of one chain of a generate with per-row mixture or semantic lengths, GR_COUNT arrays of `B` entries each behind one another
+enum { GR_OFF = 0, GR_NE, GR_NM, GR_STOP, GR_COUNT };
 
 void chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, const GenArgs& a, int L, int cap) {
     const qa_lm_spec& sp = lm->spec;
@@ -585,7 +609,33 @@ void chain_alloc(qa_lm* lm, Ctx& c, Chain& ch, const GenArgs& a, int L, int cap)
     b.ids_s = c.arena.alloc<long long>((size_t)B * std::max(a.S, 1));
     ch.emix = c.arena.alloc<float>((size_t)B * a.p.Nm * d);
     ch.eenr = a.p.enroll ? c.arena.alloc<float>((size_t)B * a.p.Ne * d) : nullptr;
-    b.off = a.p.ne_rows ? c.arena.alloc<int>(B) : nullptr;  // last, and only then: a rectangular call keeps the layout it had
+    // last, and only then: the buffers of THIS chain lie where a rectangular call has them.  A later chain's move with the ints in front
+    // of them (none, B or GR_COUNT * B), which is why the step-graph key holds the chain's addresses (generate_graph)
+    if (a.p.nm_rows || a.stop_rows) {
+        int* ints = c.arena.alloc<int>((size_t)GR_COUNT * B);
+        b.off = a.p.nm_rows ? ints + GR_OFF * B : nullptr;
+        b.stop = a.stop_rows ? ints + GR_STOP * B : nullptr;
+        ch.ints = ints;
+    } else {
+        b.off = a.p.ne_rows ? c.arena.alloc<int>(B) : nullptr;
+    }
+}
+
+// the chain's per-row ints (GR_*) in one upload: offsets Lp_b - Lp_max, the rows' frame counts for the assembly, the rows' semantic steps
+int write_gen_ints(const Chain& ch, const GenArgs& a) {
+    static_assert(GR_COUNT * LM_MAX_ROWS <= ROW_INTS_CHUNK, "the ints of a chain are one launch");
+    const Prompt& p = a.p;
+    std::vector<int> vals((size_t)GR_COUNT * ch.B, 0);
+    for (int i = 0; i < ch.B; ++i) {
+        const int b = ch.b0 + i;
+        if (p.nm_rows) {
+            vals[(size_t)GR_NE * ch.B + i] = p.enroll ? p.ne_rows[b] : 0;
+            vals[(size_t)GR_NM * ch.B + i] = p.nm_rows[b];
+            vals[(size_t)GR_OFF * ch.B + i] = (p.enroll ? p.ne_rows[b] - p.Ne : 0) + p.nm_rows[b] - p.Nm;
+        }
+        if (a.stop_rows) vals[(size_t)GR_STOP * ch.B + i] = a.stop_rows[b];
+    }
+    return launch_row_ints(ch.ints, vals.data(), (long long)vals.size(), ch.s);
 }
 
 // r05: up to 64 sequences are ONE chain - every GEMV / fused-MLP launch of the step carries two row groups of 32 (gridDim.y, lm_decode.hip
@@ -624,8 +674,14 @@ int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
         chains[i].b0 = i * cb;
         chains[i].B = std::min(cb, B - i * cb);
         chain_alloc(lm, c, chains[i], a, L, cap);
+        chains[i].steps_s = S;
+        if (a.stop_rows) chains[i].steps_s = *std::max_element(a.stop_rows + chains[i].b0, a.stop_rows + chains[i].b0 + chains[i].B);
     }
     if (c.dry) return QA_OK;  // real-pass-only remainder: chain_alloc above made the function's last arena allocations
+    // taps: logits.global [B][G + 1][global_size], then logits.semantic [B][S][semantic_size]
+    float* const tap_base = lm->taps ? reinterpret_cast<float*>(lm->tap_buf.ptr) : nullptr;
+    if (a.stop_rows && tap_base && S > 0)  // exact zeros behind every row's own steps (lm_tap_kernel skips a retired row); ahead of the fork
+        QA_HIP(hipMemsetAsync(tap_base + (size_t)B * Gs * sp.global_size, 0, sizeof(float) * (size_t)B * S * sp.semantic_size, c.stream));
     const bool multi = nc > 1;
     if (multi) {  // fork: the chains' streams start behind everything already queued on the caller's stream
         while ((int)lm->chain_streams.size() < nc) {
@@ -650,7 +706,14 @@ int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
     // ---- prompt (llm_sft.py:110-128) and prefill (llm_sft.py:130-135), chain by chain (these launches fill the device by themselves)
     for (Chain& ch : chains) {
         c.stream = ch.s;
-        int st = build_prompt(lm, c, p, ch.b0, ch.B, ch.emix, ch.eenr, ch.b.x, ch.b.off);
+        int st = ch.ints ? write_gen_ints(ch, a) : QA_OK;
+        // -1 behind every row's own steps: the fill stays wherever lm_pick_kernel / lm_sample_kernel store nothing
+        if (st == QA_OK && a.stop_rows && S > 0 && hipMemsetAsync(ch.b.ids_s, 0xff, sizeof(long long) * (size_t)ch.B * S, ch.s) != hipSuccess) {
+            set_error("generate: hipMemsetAsync of the semantic ids failed");
+            st = QA_ERR_HIP;
+        }
+        if (st == QA_OK)
+            st = build_prompt(lm, c, p, ch.b0, ch.B, ch.emix, ch.eenr, ch.b.x, ch.b.off, ch.ints ? ch.ints + GR_NE * ch.B : nullptr);
         // Ragged: the prefill runs unchanged over L = L_max positions and needs NO mask.  It is causal, so a valid query (position < L_b)
         // never sees a key behind itself, least of all the zero rows at L_b .. L - 1.  The queries of those zero rows are finite garbage
         // that nothing consumes (the prefill's last hidden state is not used, only its K / V), and the K / V rows they leave at L_b + t
@@ -663,10 +726,11 @@ int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
     // ---- decode: G+1 global tokens (the last is fed to the cache but discarded), then S semantic tokens
     int pos = L;
     const bool graphs = !capturing && (multi || use_graphs());
-    // taps: logits.global [B][G + 1][global_size], then logits.semantic [B][S][semantic_size]
-    float* const tap_base = lm->taps ? reinterpret_cast<float*>(lm->tap_buf.ptr) : nullptr;
     auto phase = [&](int which, long long first_id, int steps, int lo, int width, int keep) -> int {
         const int ids_ld = keep;
+        // the semantic phase alone reads the rows' stops, and drives each chain for its own longest row (steps: the tap's and the ids' stride)
+        auto chain_stop = [&](const Chain& ch) -> const int* { return which == 1 ? ch.b.stop : nullptr; };
+        auto chain_steps = [&](const Chain& ch) { return which == 1 ? ch.steps_s : steps; };
         float* const tap = tap_base ? tap_base + (which == 0 ? 0 : (size_t)B * Gs * sp.global_size) : nullptr;
         auto chain_tap = [&](const Chain& ch) { return tap ? tap + (size_t)ch.b0 * steps * width : nullptr; };
         for (Chain& ch : chains)
@@ -675,6 +739,7 @@ int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
             if ((int)lm->graphs.size() < 2 * nc) lm->graphs.resize(2 * nc);
             for (int i = 0; i < nc; ++i) {
                 Chain& ch = chains[i];
+                if (chain_steps(ch) == 0) continue;
                 long long* ids = which == 0 ? ch.b.ids_g : ch.b.ids_s;
                 StepGraph& g = lm->graphs[2 * i + which];
                 uint64_t key = 0x51ull;
@@ -682,13 +747,18 @@ int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
                                    (uint64_t)G, (uint64_t)S, (uint64_t)p.Ne, (uint64_t)p.Nm, (uint64_t)(p.enroll != nullptr), (uint64_t)lo, (uint64_t)width, (uint64_t)keep, (uint64_t)sc.do_sample,
                                    (uint64_t)sc.top_k, (uint64_t)(sc.top_p * 1e6f), (uint64_t)(sc.temperature * 1e6f), (uint64_t)knob(K_LM_PF),
                                    (uint64_t)knob(K_LM_ROWSPLIT), (uint64_t)(uintptr_t)chain_tap(ch), (uint64_t)p.cond_mode,
-                                   (uint64_t)(p.ne_rows != nullptr)})  // ragged or not - never the lengths: they live in device memory (b.off)
+                                   // ragged or not, stop or not - never the lengths: they live in device memory (b.off, b.stop).  The
+                                   // ADDRESSES, and the chain's first buffer with them: chain_alloc ends a chain with no ints, B ints or
+                                   // GR_COUNT * B ints, so the buffers of chain i >= 1 lie where the call kind of chain i - 1 put them,
+                                   // and a step captured at one layout must never be replayed at another
+                                   (uint64_t)(uintptr_t)ch.b.x, (uint64_t)(uintptr_t)ch.b.off, (uint64_t)(uintptr_t)chain_stop(ch)})
                     key = mix_key(key, v);
                 if (!g.exec || g.key != key) {
                     g.reset();
                     if (!lm->cap_stream) QA_HIP(hipStreamCreateWithFlags(&lm->cap_stream, hipStreamNonBlocking));
                     QA_HIP(hipStreamBeginCapture(lm->cap_stream, hipStreamCaptureModeThreadLocal));
-                    const int st = fused_step(lm, ch.b, ch.B, lo, width, ids, ids_ld, keep, sc, lm->cap_stream, -1, -1, chain_tap(ch), steps);
+                    const int st = fused_step(lm, ch.b, ch.B, lo, width, ids, ids_ld, keep, sc, lm->cap_stream, -1, -1, chain_tap(ch), steps,
+                                              chain_stop(ch));
                     hipGraph_t graph = nullptr;
                     const hipError_t e = hipStreamEndCapture(lm->cap_stream, &graph);
                     if (st != QA_OK) {
@@ -702,14 +772,16 @@ int generate_graph(qa_lm* lm, Ctx& c, const GenArgs& a) {
                 }
             }
             for (int st = 0; st < steps; ++st)  // round-robin: every chain advances one token per turn
-                for (int i = 0; i < nc; ++i) QA_HIP(hipGraphLaunch(lm->graphs[2 * i + which].exec, chains[i].s));
+                for (int i = 0; i < nc; ++i)
+                    if (st < chain_steps(chains[i])) QA_HIP(hipGraphLaunch(lm->graphs[2 * i + which].exec, chains[i].s));
             pos += steps;
             return QA_OK;
         }
         for (int st = 0; st < steps; ++st)
             for (Chain& ch : chains)
-                QA_TRY(fused_step(lm, ch.b, ch.B, lo, width, which == 0 ? ch.b.ids_g : ch.b.ids_s, ids_ld, keep, sc, ch.s, pos + st, st,
-                                  chain_tap(ch), steps));
+                if (st < chain_steps(ch))
+                    QA_TRY(fused_step(lm, ch.b, ch.B, lo, width, which == 0 ? ch.b.ids_g : ch.b.ids_s, ids_ld, keep, sc, ch.s, pos + st, st,
+                                      chain_tap(ch), steps, chain_stop(ch)));
         pos += steps;
         return QA_OK;
     };
@@ -1378,9 +1450,17 @@ struct GenRows {
     bool optional;            // a NULL vector is the rectangular call; false: refused
     bool full_is_rect;        // every row at the bound: the rectangular launches; false: still a ragged call
     bool host_only;           // refused under a stream capture
+    // qa_lm_generate_rows with one of these given: HOST [B], mixture frames 1 .. Nm and semantic steps 0 .. S, each NULL
+    // for "every row at full width"; `n` is then optional too, and every given vector at full width is the rectangular call
+    const int64_t *mix = nullptr, *semantic = nullptr;
 };
 static const GenRows NO_ROWS{};
 static GenRows enroll_rows(const int64_t* n_enroll) { return GenRows{true, n_enroll, "n_enroll", "n_enroll_max", false, false, false}; }
+// the three vectors of qa_lm_generate_rows: none is qa_lm_generate, n_enroll alone qa_lm_generate_ragged - the same launches, the same bits
+static GenRows speech_rows(const int64_t* n_enroll, const int64_t* n_mix, const int64_t* n_semantic) {
+    if (!n_mix && !n_semantic) return n_enroll ? enroll_rows(n_enroll) : NO_ROWS;
+    return GenRows{true, n_enroll, "n_enroll", "n_enroll_max", true, true, true, n_mix, n_semantic};
+}
 static GenRows cond_rows(const int64_t* n_cond) { return GenRows{true, n_cond, "n_cond", "T_max", true, true, true}; }
 
 static GenArgs gen_args(const Prompt& p, int64_t B, int32_t global_length, int32_t semantic_length, const SampleCfg& sc, int64_t* global_ids,
@@ -1392,7 +1472,7 @@ static SampleCfg sampled(float temperature, int32_t top_k, float top_p, uint64_t
     return SampleCfg{1, top_k, top_p, temperature, (unsigned long long)seed};
 }
 
-// the eight qa_lm_generate* entry points.  A ragged call lays its prompt out for the LONGEST possible row (a.p.Ne / a.p.Tc) and hands the
+// the ten qa_lm_generate* entry points.  A ragged call lays its prompt out for the LONGEST possible row (a.p.Ne / a.p.Tc) and hands the
 // checked vector on as a.p.ne_rows
 static int generate_call(const char* fn, qa_lm* lm, GenArgs a, const GenRows& r, void* stream) {
     Prompt& p = a.p;
@@ -1408,8 +1488,35 @@ static int generate_call(const char* fn, qa_lm* lm, GenArgs a, const GenRows& r,
     QA_REQUIRE(!p.enroll || p.Ne > 0, "%s: enrollment given with no frames", fn);
     QA_REQUIRE(sc.temperature > 0.f && sc.temperature <= 1.0f, "%s: temperature must be in (0, 1] (llm.py:278)", fn);
     QA_REQUIRE(sc.top_k >= 0 && sc.top_p > 0.f, "%s: bad top_k / top_p", fn);
-    std::vector<int> rows_host;
-    if (r.ragged && (r.n || !r.optional)) {
+    std::vector<int> rows_host, mix_host, stop_host;
+    if (r.mix || r.semantic) {  // per-row mixture / semantic lengths: every check before the first launch, each naming its row and value
+        QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
+        QA_REQUIRE(!r.n || p.enroll, "%s: n_enroll given (n_enroll[0] = %lld) without an enrollment (enroll_feats is NULL)", fn, (long long)r.n[0]);
+        const long long total = (long long)prompt_len(p) + a.G + 1 + a.S;  // the longest possible row, as section 23 checks it
+        QA_REQUIRE(total <= LM_MAX_POS,
+                   "%s: %lld positions (prompt %d with n_enroll_max %d and n_mix_max %d, + %d + 1 + semantic_length_max %d) exceed "
+                   "max_position_embeddings %d", fn, total, prompt_len(p), p.Ne, p.Nm, a.G, a.S, LM_MAX_POS);
+        bool full_e = true, full_m = true, full_s = true;
+        if (r.n) {
+            const int64_t bad = check_row_lengths(r.n, a.B, 1, p.Ne, &rows_host, &full_e);
+            QA_REQUIRE(bad < 0, "%s: n_enroll[%d] = %lld is outside 1 .. n_enroll_max = %d", fn, (int)bad, (long long)r.n[bad], p.Ne);
+        }
+        if (r.mix) {
+            const int64_t bad = check_row_lengths(r.mix, a.B, 1, p.Nm, &mix_host, &full_m);
+            QA_REQUIRE(bad < 0, "%s: n_mix[%d] = %lld is outside 1 .. n_mix_max = %d", fn, (int)bad, (long long)r.mix[bad], p.Nm);
+        }
+        if (r.semantic) {
+            const int64_t bad = check_row_lengths(r.semantic, a.B, 0, a.S, &stop_host, &full_s);
+            QA_REQUIRE(bad < 0, "%s: n_semantic[%d] = %lld is outside 0 .. semantic_length_max = %d", fn, (int)bad, (long long)r.semantic[bad], a.S);
+        }
+        if (!full_e || !full_m) {  // one per-row assembly for both sources: a vector the caller left out stands at full width
+            if (!r.n) rows_host.assign((size_t)a.B, p.Ne);
+            if (!r.mix) mix_host.assign((size_t)a.B, p.Nm);
+            p.ne_rows = p.enroll ? rows_host.data() : nullptr;
+            p.nm_rows = mix_host.data();
+        }
+        if (!full_s) a.stop_rows = stop_host.data();
+    } else if (r.ragged && (r.n || !r.optional)) {
         if (r.host_only) QA_TRY(refuse_capture(fn, static_cast<hipStream_t>(stream), LENGTHS_ARE_HOST_DATA));
         // the tensor the vector indexes must be there, and the longest possible row must fit: the two families' own texts
         char prompt_is[96];
@@ -1490,6 +1597,26 @@ int qa_lm_generate_ragged_sampled(qa_lm* lm, int32_t task, const float* enroll_f
     const SampleCfg sc = sampled(temperature, top_k, top_p, seed);
     return generate_call("qa_lm_generate_ragged", lm, gen_args(p, B, global_length, semantic_length, sc, global_ids, semantic_ids),
                          enroll_rows(n_enroll), stream);
+}
+
+int qa_lm_generate_rows(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                        const float* mix_feats, int64_t n_mix_max, const int64_t* n_mix, int64_t B, int32_t global_length,
+                        int32_t semantic_length_max, const int64_t* n_semantic, float temperature, int32_t top_k, float top_p,
+                        int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    const Prompt p = speech_prompt(task, enroll_feats, narrow(n_enroll_max), mix_feats, narrow(n_mix_max));
+    const SampleCfg sc = greedy(temperature, top_k, top_p);
+    return generate_call("qa_lm_generate_rows", lm, gen_args(p, B, global_length, semantic_length_max, sc, global_ids, semantic_ids),
+                         speech_rows(n_enroll, n_mix, n_semantic), stream);
+}
+
+int qa_lm_generate_rows_sampled(qa_lm* lm, int32_t task, const float* enroll_feats, int64_t n_enroll_max, const int64_t* n_enroll,
+                                const float* mix_feats, int64_t n_mix_max, const int64_t* n_mix, int64_t B, int32_t global_length,
+                                int32_t semantic_length_max, const int64_t* n_semantic, float temperature, int32_t top_k, float top_p,
+                                uint64_t seed, int64_t* global_ids, int64_t* semantic_ids, void* stream) {
+    const Prompt p = speech_prompt(task, enroll_feats, narrow(n_enroll_max), mix_feats, narrow(n_mix_max));
+    const SampleCfg sc = sampled(temperature, top_k, top_p, seed);
+    return generate_call("qa_lm_generate_rows", lm, gen_args(p, B, global_length, semantic_length_max, sc, global_ids, semantic_ids),
+                         speech_rows(n_enroll, n_mix, n_semantic), stream);
 }
 
 int qa_lm_generate_cond(qa_lm* lm, const float* cond_embeds, int64_t T, int64_t B, int32_t global_length, int32_t semantic_length,

@@ -64,6 +64,12 @@ struct GemvArgs {
     int* pidx;
     float* logits;  // nullable: [M, N] full slice logits for the sampling path
     long long ldl;
+    // GM_QKV, per-row stop: stop[row] = the row's semantic steps, device memory written once per call like `off`.  A row
+    // whose stop is at or below the step's column (`col` with a host-driven step, the state's column with a replayed one) is RETIRED: an idle
+    // row in the sense above, position -1, no K / V append.  nullptr (every launch outside the semantic phase of a call with per-row
+    // semantic lengths): no row ever retires
+    const int* stop;
+    int col;
 };
 
 int lm_pick_nt(int N);
@@ -75,19 +81,23 @@ int launch_lm_mlp(const GemvArgs& a, int I, int ac, const float* wd, float* part
                   hipStream_t s, const PfArgs* pf = nullptr);
 int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* vc, long long kv_bstride, long long ldkv,
                    float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s,
-                   const int* off = nullptr);  // off: per-row position offsets as GemvArgs::off
+                   const int* off = nullptr,  // off: per-row position offsets as GemvArgs::off
+                   const int* stop = nullptr, int col = -1);  // stop / col: as GemvArgs::stop - a retired row owns no key
 // off[i] = n_rows[i] - n_max for the B <= LM_MAX_ROWS rows of a chain (the values travel as kernel arguments: the host vector may be
 // freed on return, and the write is ordered on the stream like every other launch of the call)
 int launch_lm_offsets(int* off, const int* n_rows, int n_max, int B, hipStream_t s);
+// stop (pick, tap, sample; nullable): a row with stop[b] <= the step's column stores nothing - no id, no token, no tap row
 int launch_lm_pick(const float* pmax, const int* pidx, int n_tiles, int B, int lo, long long* tok, long long* ids, long long ids_ld,
-                   int keep, int* state, int col, hipStream_t s);
+                   int keep, int* state, int col, hipStream_t s, const int* stop = nullptr);
 int launch_lm_phase_init(long long* tok, long long first_id, int B, int* state, int pos, int reset_step, unsigned long long seed,
                          int seq0, hipStream_t s);
 int launch_lm_advance(int* state, hipStream_t s);
 // test hook: copy the step's slice logits [B, width] into column `col` of tap [B][n_cols][width] (col < 0: the state's column)
-int launch_lm_tap(const float* logits, int width, int B, float* tap, int n_cols, const int* state, int col, hipStream_t s);
+int launch_lm_tap(const float* logits, int width, int B, float* tap, int n_cols, const int* state, int col, hipStream_t s,
+                  const int* stop = nullptr);
 int lm_sample_prepare();
 int launch_lm_sample(const float* logits, long long ldl, int width, int B, int lo, int top_k, float top_p, float temperature,
-                     int do_sample, long long* tok, long long* ids, long long ids_ld, int keep, const int* state, hipStream_t s);
+                     int do_sample, long long* tok, long long* ids, long long ids_ld, int keep, const int* state, hipStream_t s,
+                     const int* stop = nullptr);
 
 }  // namespace qa

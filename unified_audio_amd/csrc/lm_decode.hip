@@ -167,6 +167,7 @@ __device__ __forceinline__ void row_group(GemvArgs& a, int rg, int n_tiles, int 
     if (a.att_part) a.att_part += r0 * a.H * a.S * (a.hd + 4);
     if (a.q) a.q += r0 * a.d;
     if (a.off) a.off += r0;
+    if (a.stop) a.stop += r0;
     if (a.kc) a.kc += r0 * a.kv_bstride;
     if (a.vc) a.vc += r0 * a.kv_bstride;
     if (a.res) a.res += r0 * a.ldr;
@@ -207,9 +208,11 @@ __device__ __forceinline__ void epi_prefetch(const GemvArgs& a, int tile, int ti
                 // An IDLE row of a session step (lm.cpp forward_graph) carries off = -(pos + 1): its position is -1,
                 // it reads RoPE row 0 and the epilogue appends nothing for it
                 if (a.off) e.pos[u] = pos + a.off[min(row, a.M - 1)];
+                // per-row stop (wave-uniform like `off`): a row behind its last semantic step is idle in the same sense
+                if (a.stop && (a.pos >= 0 ? a.col : a.state[ST_COL]) >= a.stop[min(row, a.M - 1)]) e.pos[u] = -1;
                 if (sec != 2) {
                     const int ri = ((c0 - h * hd) / NT) * HP + j;
-                    const long long rp = a.off ? max(e.pos[u], 0) : e.pos[u];
+                    const long long rp = (a.off || a.stop) ? max(e.pos[u], 0) : e.pos[u];
                     e.c[u] = a.rope[(rp * half + ri) * 2];
                     e.s[u] = a.rope[(rp * half + ri) * 2 + 1];
                 }
@@ -853,7 +856,7 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
                                                           const float* __restrict__ kc, const float* __restrict__ vc,
                                                           long long kv_bstride, long long ldkv, float* __restrict__ part,
                                                           const int* __restrict__ state, float scale, int pos, int tps,
-                                                          const int* __restrict__ off) {
+                                                          const int* __restrict__ off, const int* __restrict__ stop, int col) {
     constexpr int LPK = HD / 4;    // lanes per key row
     constexpr int KPI = 64 / LPK;  // key rows per load instruction
     constexpr int NI = 16 / KPI;   // load instructions per 16-key tile (per operand)
@@ -864,7 +867,9 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
     const int kq = lane / LPK, c4 = (lane % LPK) * 4;
     // ragged batch (off != nullptr): sequence b sits off[b] <= 0 positions behind the step's position and owns that many keys fewer
     // (an idle row of a session step owns none: no tile, no load, an identity record)
-    const int n_keys = (pos >= 0 ? pos : state[ST_POS]) + 1 + (off ? off[b] : 0);
+    // per-row stop: a retired row owns no key either
+    int n_keys = (pos >= 0 ? pos : state[ST_POS]) + 1 + (off ? off[b] : 0);
+    if (stop && (pos >= 0 ? col : state[ST_COL]) >= stop[b]) n_keys = 0;
     const int n_tiles = (n_keys + 15) >> 4;
     const int t0 = sp * tps, t_end = min(t0 + tps, n_tiles);  // this split's tiles (empty past the last key)
     const float* kb = kc + (long long)b * kv_bstride + h * HD + c4;
@@ -957,18 +962,19 @@ __global__ __launch_bounds__(NW * 64) void lm_attn_kernel(const float* __restric
 }
 
 int launch_lm_attn(const float* q, long long ldq, const float* kc, const float* vc, long long kv_bstride, long long ldkv,
-                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s, const int* off) {
+                   float* part, int B, int H, int hd, int S, int tps, const int* state, float scale, int pos, hipStream_t s, const int* off,
+                   const int* stop, int col) {
     QA_REQUIRE(S >= 1 && S <= 4 && tps >= 1, "lm_attn: bad split count %d (%d tiles each)", S, tps);
     const dim3 grid(H, B, S);
     switch (hd) {
         case 64:
-            hipLaunchKernelGGL((lm_attn_kernel<64, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off);
+            hipLaunchKernelGGL((lm_attn_kernel<64, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off, stop, col);
             break;
         case 128:
-            hipLaunchKernelGGL((lm_attn_kernel<128, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off);
+            hipLaunchKernelGGL((lm_attn_kernel<128, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off, stop, col);
             break;
         case 32:
-            hipLaunchKernelGGL((lm_attn_kernel<32, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off);
+            hipLaunchKernelGGL((lm_attn_kernel<32, 8>), grid, dim3(512), 0, s, q, ldq, kc, vc, kv_bstride, ldkv, part, state, scale, pos, tps, off, stop, col);
             break;
         default: set_error("lm_attn: head_dim=%d unsupported", hd); return QA_ERR_UNSUPPORTED;
     }
@@ -1000,11 +1006,13 @@ int launch_lm_offsets(int* off, const int* n_rows, int n_max, int B, hipStream_t
 constexpr int PICK_SEQS = 4;
 __global__ __launch_bounds__(64 * PICK_SEQS) void lm_pick_kernel(const float* __restrict__ pmax, const int* __restrict__ pidx, int n_tiles,
                                                                  int B, int lo, long long* __restrict__ tok, long long* __restrict__ ids,
-                                                                 long long ids_ld, int keep, int* __restrict__ state, int col_arg) {
+                                                                 long long ids_ld, int keep, int* __restrict__ state, int col_arg,
+                                                                 const int* __restrict__ stop) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = col_arg >= 0 ? col_arg : state[ST_COL];
     const int b = blockIdx.x * PICK_SEQS + wave;
-    if (b < B) {
+    // a retired row stores neither id nor token: its ids column keeps the call's -1 fill, its token stays a valid one
+    if (b < B && !(stop && col >= stop[b])) {
         float best = -INFINITY;
         int bi = 0x7fffffff;
         for (int t = lane; t < n_tiles; t += 64) {
@@ -1043,9 +1051,9 @@ __global__ __launch_bounds__(64 * PICK_SEQS) void lm_pick_kernel(const float* __
 }
 
 int launch_lm_pick(const float* pmax, const int* pidx, int n_tiles, int B, int lo, long long* tok, long long* ids, long long ids_ld,
-                   int keep, int* state, int col, hipStream_t s) {
+                   int keep, int* state, int col, hipStream_t s, const int* stop) {
     hipLaunchKernelGGL(lm_pick_kernel, dim3((unsigned)ceil_div(B, PICK_SEQS)), dim3(64 * PICK_SEQS), 0, s, pmax, pidx, n_tiles, B, lo, tok, ids,
-                       ids_ld, keep, state, col);
+                       ids_ld, keep, state, col, stop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -1053,14 +1061,16 @@ int launch_lm_pick(const float* pmax, const int* pidx, int n_tiles, int B, int l
 // Test hook (qa_lm_enable_taps): tap[b][col][j] = logits[b][j] for the step's column col (read from the loop state when col_arg < 0, so
 // the same launch is right inside a replayed step graph).  Runs between the head launch and the pick / sample launch, which advances col.
 __global__ void lm_tap_kernel(const float* __restrict__ logits, int width, float* __restrict__ tap, int n_cols, const int* __restrict__ state,
-                              int col_arg) {
+                              int col_arg, const int* __restrict__ stop) {
     const int col = col_arg >= 0 ? col_arg : state[ST_COL];
     const int b = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= n_cols || j >= width) return;
+    if (stop && col >= stop[b]) return;  // a retired row: its tap rows keep the call's zero fill
     tap[((long long)b * n_cols + col) * width + j] = logits[(long long)b * width + j];
 }
-int launch_lm_tap(const float* logits, int width, int B, float* tap, int n_cols, const int* state, int col, hipStream_t s) {
-    hipLaunchKernelGGL(lm_tap_kernel, dim3((unsigned)ceil_div(width, 256), (unsigned)B), dim3(256), 0, s, logits, width, tap, n_cols, state, col);
+int launch_lm_tap(const float* logits, int width, int B, float* tap, int n_cols, const int* state, int col, hipStream_t s, const int* stop) {
+    hipLaunchKernelGGL(lm_tap_kernel, dim3((unsigned)ceil_div(width, 256), (unsigned)B), dim3(256), 0, s, logits, width, tap, n_cols, state, col,
+                       stop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -1161,11 +1171,12 @@ __device__ __forceinline__ float block_scan_1024(float v, float* s_wave, float* 
 __global__ __launch_bounds__(1024) void lm_sample_kernel(const float* __restrict__ logits, long long ldl, int width, int n_pow2, int lo,
                                                          int top_k, float top_p, float temperature, int do_sample,
                                                          long long* __restrict__ tok, long long* __restrict__ ids, long long ids_ld,
-                                                         int keep, const int* __restrict__ state) {
+                                                         int keep, const int* __restrict__ state, const int* __restrict__ stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // n_pow2 entries
     __shared__ float s_wave[16];
     __shared__ int s_cnt, s_pick;
     const int tid = threadIdx.x, b = blockIdx.x;
+    if (stop && state[ST_COL] >= stop[b]) return;  // a retired row, the whole workgroup: nothing sorted, drawn or stored
     const float* row = logits + (long long)b * ldl;
     for (int i = tid; i < n_pow2; i += 1024)
         keys[i] = i < width ? (((unsigned long long)f2ord(row[i])) << 32) | (unsigned)(~(unsigned)i) : 0ull;
@@ -1268,13 +1279,14 @@ __global__ __launch_bounds__(1024) void lm_sample_kernel(const float* __restrict
 int lm_sample_prepare() { return raise_dynamic_lds(reinterpret_cast<const void*>(lm_sample_kernel), 16384 * 8); }
 
 int launch_lm_sample(const float* logits, long long ldl, int width, int B, int lo, int top_k, float top_p, float temperature,
-                     int do_sample, long long* tok, long long* ids, long long ids_ld, int keep, const int* state, hipStream_t s) {
+                     int do_sample, long long* tok, long long* ids, long long ids_ld, int keep, const int* state, hipStream_t s,
+                     const int* stop) {
     int n_pow2 = 1024;
     while (n_pow2 < width) n_pow2 <<= 1;
     QA_REQUIRE(n_pow2 <= 16384, "lm_sample: vocabulary slice of %d entries exceeds the 16384 the sampler sorts in LDS", width);
     const size_t lds = (size_t)n_pow2 * sizeof(unsigned long long);
     hipLaunchKernelGGL(lm_sample_kernel, dim3(B), dim3(1024), lds, s, logits, ldl, width, n_pow2, lo, top_k, top_p, temperature,
-                       do_sample, tok, ids, ids_ld, keep, state);
+                       do_sample, tok, ids, ids_ld, keep, state, stop);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

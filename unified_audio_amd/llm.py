@@ -109,13 +109,17 @@ def _unsupported(**kw):
                                            f"the cache length, attention weights are never materialised)")
 
 
+def _call_seed(do_sample: bool):
+    """(seed,) of a sampled call, () of a greedy one: the seed advances torch's CPU generator, once per call"""
+    return (int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()),) if do_sample else ()
+
+
 def _generate_call(lib, family: str, lengths_arr, do_sample: bool):
     """The C function of a generate call - `family` (qa_lm_generate / qa_lm_generate_cond), _ragged with a per-row length array, _sampled
     when sampling - and what the variant adds to the family's arguments: (function, (lengths_arr,) or (), (seed,) or ()).  The seed of a
     sampled call advances torch's CPU generator, once per call: new draws per call, torch.manual_seed controls reproducibility."""
     fn = getattr(lib, family + ("_ragged" if lengths_arr is not None else "") + ("_sampled" if do_sample else ""))
-    seed = (int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()),) if do_sample else ()
-    return fn, (lengths_arr,) if lengths_arr is not None else (), seed
+    return fn, (lengths_arr,) if lengths_arr is not None else (), _call_seed(do_sample)
 
 
 class LLM_SFT:
@@ -301,8 +305,13 @@ class LLM_SFT:
     @torch.no_grad()
     def generate(self, task_name: str, enroll_mel, enroll_feats, mix_mel: torch.Tensor, mix_feats: torch.Tensor,
                  global_length: int = 32, temperature: float = 0.8, top_k: int = 50, top_p: float = 0.95,
-                 do_sample: bool = True, *, enroll_lengths=None):
+                 do_sample: bool = True, *, enroll_lengths=None, mix_lengths=None, semantic_lengths=None):
         """Returns (global_ids [B, global_length], semantic_ids [B, mix_mel.size(1)]) int64, offsets subtracted.
+        mix_lengths / semantic_lengths (keyword only; B ints each, None: every row at full width): mix_feats is
+        [B, max(mix_lengths), feats_dim] and row b is what the reference returns for that sequence alone on mix_feats[b, :mix_lengths[b]]
+        with semantic_lengths[b] semantic steps (0 .. S_max = mix_mel.size(1), checked by the library).  semantic_ids comes back
+        [B, S_max] with -1 behind each row's length - what BiCodec.detokenize(..., lengths=semantic_lengths) ignores.  Padding frames
+        are never read, and a finished row stops costing key / value traffic (qa_lm_generate_rows).
         enroll_lengths (keyword only; None: the reference's rectangular call): a sequence or tensor of B frame counts for a batch whose
         enrollments differ in length.  enroll_feats is then [B, max(enroll_lengths), feats_dim], row b's frames at or behind
         enroll_lengths[b] are padding that is never read, and row b's tokens are what the reference returns for that sequence alone
@@ -328,6 +337,15 @@ class LLM_SFT:
         _, arr = _lib.host_lengths("generate: enroll_lengths", enroll_lengths, B)
         if arr is not None and enr is not None and (enr.dim() != 3 or enr.shape[0] != B):
             raise _lib.QuarkAudioError(-1, f"generate: enroll_feats must be [{B}, max(enroll_lengths), feats_dim], got {tuple(enr.shape)}")
+        _, nm_arr = _lib.host_lengths("generate: mix_lengths", mix_lengths, B)
+        _, ns_arr = _lib.host_lengths("generate: semantic_lengths", semantic_lengths, B)
+        if nm_arr is not None or ns_arr is not None:
+            fn = self._lib.qa_lm_generate_rows_sampled if do_sample else self._lib.qa_lm_generate_rows
+            seed = _call_seed(do_sample)
+            _lib.check(fn(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, arr, mix.data_ptr(), n_mix, nm_arr, B,
+                          global_length, S, ns_arr, temperature, top_k, top_p, *seed, gids.data_ptr(), sids.data_ptr(), stream))
+            return gids, sids
+        # without them: qa_lm_generate / qa_lm_generate_ragged themselves, so that their messages keep their prefix
         fn, lens, seed = _generate_call(self._lib, "qa_lm_generate", arr, do_sample)
         _lib.check(fn(self._handle, task, enr.data_ptr() if enr is not None else None, n_enr, *lens, mix.data_ptr(), n_mix, B, global_length, S,
                       temperature, top_k, top_p, *seed, gids.data_ptr(), sids.data_ptr(), stream))

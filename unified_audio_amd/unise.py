@@ -22,6 +22,7 @@ import torch
 SEG_LEN = 5 * 16000        # model.py:176
 HOP_LENGTH = 320           # conf/config.yaml:124-128 (stft_config)
 WIN_LENGTH = 640
+MIN_TAIL = 16000           # UniSE(tail="trim"): the shortest last segment, in samples
 
 
 def wrap_pad(src: torch.Tensor, multiple: int = SEG_LEN) -> torch.Tensor:
@@ -43,6 +44,30 @@ def segment(src: torch.Tensor, normalise: bool) -> torch.Tensor:
     if normalise:
         seg = seg / src.abs().max(dim=-1, keepdim=True)[0]
     return seg
+
+
+def trim_samples(T: int, min_tail: int = MIN_TAIL) -> List[int]:
+    """The sample counts of the segments UniSE(tail="trim") cuts an utterance of T samples into: its full 5 s segments, then one last
+    segment of T mod 80000 samples - at least `min_tail`, an utterance that ends sooner wraps around as far."""
+    full, rem = divmod(int(T), SEG_LEN)
+    return [SEG_LEN] * full + ([max(rem, min_tail)] if rem or not full else [])
+
+
+def segment_trim(src: torch.Tensor, normalise: bool, min_tail: int = MIN_TAIL) -> Tuple[torch.Tensor, List[int]]:
+    """`segment` without the wrap-padding to a multiple of 5 s: src [1, T] -> (seg_src [n, 80000], the n rows' sample counts
+    `trim_samples(T)`).  The last row holds its samples in front and zeros behind them.  A last segment shorter than `min_tail` is
+    wrap-padded up to it the way the reference wraps to 80000: the utterance repeats itself.  normalise as in `segment`: the peak of the
+    WHOLE utterance."""
+    if src.dim() != 2 or src.size(0) != 1:
+        raise ValueError(f"src must be [1, T] like the reference's batch, got {tuple(src.shape)}")
+    samples = trim_samples(src.size(-1), min_tail)
+    total = sum(samples)
+    x = torch.cat([src] * math.ceil(total / src.size(-1)), dim=-1)[..., :total]
+    seg = x.new_zeros((len(samples), SEG_LEN))
+    seg.reshape(-1)[:total] = x[0]
+    if normalise:
+        seg = seg / src.abs().max(dim=-1, keepdim=True)[0]
+    return seg, samples
 
 
 def mel_frames(n_samples: int) -> int:
@@ -116,14 +141,22 @@ def stft_logmel(x: torch.Tensor, hop_length: int = HOP_LENGTH, win_length: int =
 
 
 class UniSE:
-    def __init__(self, dnn, semantic_model, tokenizer=None, detokenize: Optional[Callable] = None, max_segments: int = 64):
+    def __init__(self, dnn, semantic_model, tokenizer=None, detokenize: Optional[Callable] = None, max_segments: int = 64,
+                 tail: str = "wrap", min_tail: int = MIN_TAIL):
         """dnn: unified_audio_amd.LLM_SFT; semantic_model: unified_audio_amd.SSLFeatureExtractor(SPEC_WAVLM_BASE_PLUS);
         tokenizer: unified_audio_amd.BiCodecTokenizer (or any object / callable with the reference's
         `detokenize(global_tokens [B, 1, 32], semantic_tokens [B, N]) -> wav [B, 1, t]`, model.py:193).
         max_segments: 5 s segments per pass through the three stages (the micro-batch).  The reference feeds one utterance per step
         (data_module.py:340); here all segments of a call are batched, 64 at a time: the LM's decode step costs about the same for 16
         and for 64 sequences (one chain, two row groups per launch: 92 k tok/s against 41 k at 16), memory stays
-        bounded for long file lists, and - every stage being batch-invariant - the result does not depend on the value."""
+        bounded for long file lists, and - every stage being batch-invariant - the result does not depend on the value.
+        tail: "wrap" (the default) is the reference's behaviour: every utterance is wrap-padded to a multiple of 5 s (model.py:177-178), so
+        a 2 s utterance pays for a 5 s prompt and 250 semantic steps.  "trim" is opt-in and DEVIATES from the reference: an utterance of
+        T samples gives its full 5 s segments plus one last segment of T mod 80000 samples that runs at its own length through all three
+        stages - semantic_model(seg, lengths=), generate(mix_lengths=, semantic_lengths=), detokenize(lengths=) -
+        so the last segment is modelled WITHOUT the repeated start of the utterance behind it and its tokens differ from the
+        reference's.  A last segment shorter than `min_tail` samples is wrap-padded up to `min_tail`; 'se' still divides by the whole
+        utterance's peak; the 'ss' mode keeps "wrap".  It needs an LM, a front-end and a detokenizer that take per-row lengths."""
         self.dnn = dnn
         self.semantic_model = semantic_model
         self.detokenize = detokenize if detokenize is not None else (tokenizer.detokenize if tokenizer is not None else None)
@@ -144,11 +177,36 @@ class UniSE:
             self._ssl_ragged_ok = any(p.name == "lengths" for p in params) and callable(getattr(semantic_model, "frames", None))
         except (AttributeError, TypeError, ValueError):
             self._ssl_ragged_ok = False
+        if tail not in ("wrap", "trim"):
+            raise ValueError(f"tail must be 'wrap' or 'trim', got {tail!r}")
+        self.tail, self.min_tail = tail, int(min_tail)
+        if tail == "trim":
+            if not 1 <= self.min_tail <= SEG_LEN:
+                raise ValueError(f"min_tail must be 1 .. {SEG_LEN} samples, got {min_tail}")
+
+            def takes(fn, *names):
+                try:
+                    params = list(inspect.signature(fn).parameters.values())
+                except (AttributeError, TypeError, ValueError):
+                    return False
+                return any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params) or all(any(p.name == n for p in params) for n in names)
+
+            missing = []
+            if not (self._ragged_ok and takes(getattr(dnn, "generate", None), "mix_lengths", "semantic_lengths")):
+                missing.append("dnn.generate(..., enroll_lengths=, mix_lengths=, semantic_lengths=)")
+            if not self._ssl_ragged_ok:
+                missing.append("semantic_model(wavs, lengths=) with frames(n_samples)")
+            if self.detokenize is not None and not takes(self.detokenize, "lengths"):
+                missing.append("detokenize(global_tokens, semantic_tokens, lengths=)")
+            if missing:
+                raise TypeError("UniSE(tail='trim') runs the last segment at its own length and needs " + "; ".join(missing))
 
     def _generate(self, mode: str, seg_src: torch.Tensor, counts: Sequence[int], enroll_feats_per_utt: Optional[torch.Tensor],
-                  enroll_samples: int, enroll_frames: Optional[Sequence[int]] = None):
+                  enroll_samples: int, enroll_frames: Optional[Sequence[int]] = None, samples: Optional[Sequence[int]] = None):
         """enroll_frames (enrollments of different lengths): the valid feature frames of every row of enroll_feats_per_utt, which is
-        then zero-padded to the longest; None: every row is valid throughout."""
+        then zero-padded to the longest; None: every row is valid throughout.
+        samples (tail="trim"): every segment's own sample count; the semantic ids then come back [n, 250] with -1 behind a row's
+        mel_frames(samples) tokens."""
         m = self.max_segments
         if seg_src.size(0) > m:  # micro-batches of <= max_segments segments; a segment's utterance is looked up through `owner`
             owner = torch.repeat_interleave(torch.arange(len(counts)), torch.tensor(list(counts)))
@@ -158,14 +216,19 @@ class UniSE:
                 utts, sub_counts = torch.unique_consecutive(own, return_counts=True)
                 ef = enroll_feats_per_utt[utts.to(enroll_feats_per_utt.device)] if enroll_feats_per_utt is not None else None
                 frames = [enroll_frames[i] for i in utts.tolist()] if enroll_frames is not None else None
-                g, sids = self._generate(mode, seg_src[a:a + m], sub_counts.tolist(), ef, enroll_samples, frames)
+                g, sids = self._generate(mode, seg_src[a:a + m], sub_counts.tolist(), ef, enroll_samples, frames,
+                                         samples[a:a + m] if samples is not None else None)
                 gs.append(g)
                 ss.append(sids)
             return torch.cat(gs, dim=0), torch.cat(ss, dim=0)
-        mix_feats = self.semantic_model(seg_src)                                   # extract_semantic_features, model.py:38-51
-        mix_mel = _Frames(seg_src.size(0), mel_frames(SEG_LEN))
-        enroll_mel = enroll_feats = None
         ragged = {}
+        if samples is not None and any(n != SEG_LEN for n in samples):
+            # a micro-batch with a trimmed last segment: every stage at the rows' own lengths, the tensors at the longest row's
+            seg_src, mix_feats, mix_mel, ragged = self._trimmed_inputs(seg_src, samples)
+        else:
+            mix_feats = self.semantic_model(seg_src)                               # extract_semantic_features, model.py:38-51
+            mix_mel = _Frames(seg_src.size(0), mel_frames(SEG_LEN))
+        enroll_mel = enroll_feats = None
         if enroll_feats_per_utt is not None:
             if enroll_frames is not None:  # this micro-batch's longest enrollment bounds its prompt, not the call's
                 enroll_feats_per_utt = enroll_feats_per_utt[:, :max(enroll_frames)]
@@ -176,8 +239,25 @@ class UniSE:
             # model.py:207-210: the utterance's enrollment is tiled over its segments
             enroll_feats = torch.cat([enroll_feats_per_utt[i:i + 1].expand(c, -1, -1) for i, c in enumerate(counts)], dim=0).contiguous()
             enroll_mel = _Frames(seg_src.size(0), mel_frames(enroll_samples))
-        return self.dnn.generate(task_name=mode, enroll_mel=enroll_mel, enroll_feats=enroll_feats, mix_mel=mix_mel, mix_feats=mix_feats,
-                                 do_sample=False, **ragged)
+        g, sids = self.dnn.generate(task_name=mode, enroll_mel=enroll_mel, enroll_feats=enroll_feats, mix_mel=mix_mel, mix_feats=mix_feats,
+                                    do_sample=False, **ragged)
+        return g, (self._full_width(sids) if samples is not None else sids)
+
+    def _trimmed_inputs(self, seg_src: torch.Tensor, samples: Sequence[int]):
+        """The front-end and the LM's length arguments for segments of `samples` samples each (tail="trim"): (the segments cut to the
+        longest row, its features [B, frames(longest), d], the mel stand-in at the longest row's step count, generate's keywords)."""
+        samples = [int(n) for n in samples]
+        seg_src = seg_src[:, :max(samples)].contiguous()
+        mix_feats = self.semantic_model(seg_src, lengths=samples)
+        steps = [mel_frames(n) for n in samples]
+        lens = dict(mix_lengths=[int(self.semantic_model.frames(n)) for n in samples], semantic_lengths=steps)
+        return seg_src, mix_feats, _Frames(seg_src.size(0), max(steps)), lens
+
+    @staticmethod
+    def _full_width(sids: torch.Tensor) -> torch.Tensor:
+        """semantic ids [B, S] of a micro-batch whose longest row is shorter than 5 s -> [B, 250], -1 behind"""
+        full = mel_frames(SEG_LEN)
+        return sids if sids.size(1) == full else torch.nn.functional.pad(sids, (0, full - sids.size(1)), value=-1)
 
     def _enroll_features(self, enrolls: Sequence[torch.Tensor]):
         """The SSL features of one enrollment per utterance -> ([U, N_e, d], samples, frames).  Equal lengths: one front-end pass, frames
@@ -218,7 +298,8 @@ class UniSE:
     def enhance_tokens(self, mode: str, srcs: Sequence[torch.Tensor], enrolls: Optional[Sequence[torch.Tensor]] = None
                        ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """srcs: utterances [1, T_i] (device tensors); enrolls (tse / rtse): one [1, T_e_i] per utterance (any lengths).
-        Returns per utterance (global_ids [n_seg_i, 32], semantic_ids [n_seg_i, 250])."""
+        Returns per utterance (global_ids [n_seg_i, 32], semantic_ids [n_seg_i, 250]); with tail="trim" the last row of an utterance
+        holds mel_frames(its samples) ids and -1 behind them."""
         if mode not in ("se", "tse", "rtse"):
             raise KeyError(mode)
         if mode != "se":
@@ -234,20 +315,36 @@ class UniSE:
                     for i, r in zip(idx, self.enhance_tokens(mode, [srcs[i] for i in idx], [enrolls[i] for i in idx])):
                         out[i] = r
                 return out  # type: ignore[return-value]
-        segs = [segment(s, normalise=(mode == "se")) for s in srcs]
-        counts = [s.size(0) for s in segs]
+        segs, counts, samples = self._segments(mode, srcs)
         seg_src = torch.cat(segs, dim=0)
         ef, n_enr, frames = None, 0, None
         if mode != "se":
             # enrollments of different lengths no longer split the LM pass into one group per length: the features are padded to the
             # longest and the segments of ALL utterances go through one ragged generate per micro-batch
             ef, n_enr, frames = self._enroll_features(enrolls)                    # [U, N_e, d]
-        global_ids, semantic_ids = self._generate(mode, seg_src, counts, ef, n_enr, frames)
+        global_ids, semantic_ids = self._generate(mode, seg_src, counts, ef, n_enr, frames, samples)
         return self._split(counts, global_ids, semantic_ids)
+
+    def _segments(self, mode: str, srcs: Sequence[torch.Tensor]):
+        """The utterances' segments, their counts and - tail="trim" only, else None - every segment's own sample count"""
+        if self.tail == "trim":
+            cut = [segment_trim(s, normalise=(mode == "se"), min_tail=self.min_tail) for s in srcs]
+            return [c[0] for c in cut], [len(c[1]) for c in cut], [n for c in cut for n in c[1]]
+        segs = [segment(s, normalise=(mode == "se")) for s in srcs]
+        return segs, [s.size(0) for s in segs], None
 
     def _wave(self, src: torch.Tensor, gids: torch.Tensor, sids: torch.Tensor) -> torch.Tensor:
         est = self.detokenize(gids.unsqueeze(1), sids).squeeze(1)                 # model.py:192
         return est.reshape(-1)[: src.size(-1)]
+
+    def _detokenize_rows(self, g: torch.Tensor, s: torch.Tensor, samples: Sequence[int]) -> List[torch.Tensor]:
+        """One detokenize call over a micro-batch of tail="trim": row i's waveform over its own samples[i] samples"""
+        steps = [mel_frames(int(n)) for n in samples]
+        if all(n == SEG_LEN for n in samples):
+            est = self.detokenize(g.unsqueeze(1), s).squeeze(1)
+        else:
+            est = self.detokenize(g.unsqueeze(1), s[:, :max(steps)].contiguous(), lengths=steps).squeeze(1)
+        return [est[i, :int(n)] for i, n in enumerate(samples)]
 
     @torch.no_grad()
     def enhance(self, mode: str, srcs: Sequence[torch.Tensor], enrolls: Optional[Sequence[torch.Tensor]] = None):
@@ -260,19 +357,32 @@ class UniSE:
         if mode == "ss":
             return self._separate(srcs)
         toks = self.enhance_tokens(mode, srcs, enrolls)
-        return self._waves(srcs, toks)
+        return self._waves(srcs, toks, trim=self.tail == "trim")
 
-    def _waves(self, srcs, toks):
+    def _waves(self, srcs, toks, trim: bool = False):
         """model.py:192 for every utterance, with ONE detokenize call over all segments (segments are independent and the detokenizer
-        is batch-invariant, so this equals the reference's per-utterance calls bit for bit)."""
+        is batch-invariant, so this equals the reference's per-utterance calls bit for bit).  trim (tail="trim"): every row over its own
+        samples, an utterance's rows concatenated and cut to its length."""
         g = torch.cat([t[0] for t in toks], dim=0)
         s = torch.cat([t[1] for t in toks], dim=0)
         m = self.max_segments
+        if trim:
+            samples = [n for src in srcs for n in trim_samples(src.size(-1), self.min_tail)]
+            rows = [w for a in range(0, g.size(0), m) for w in self._detokenize_rows(g[a:a + m], s[a:a + m], samples[a:a + m])]
+            return self._join_rows(srcs, [t[0].size(0) for t in toks], rows)
         est = torch.cat([self.detokenize(g[a:a + m].unsqueeze(1), s[a:a + m]).squeeze(1) for a in range(0, g.size(0), m)], dim=0)
         out, at = [], 0
         for src, (gi, _) in zip(srcs, toks):
             out.append(est[at:at + gi.size(0)].reshape(-1)[: src.size(-1)])
             at += gi.size(0)
+        return out
+
+    @staticmethod
+    def _join_rows(srcs, counts, rows: List[torch.Tensor]):
+        out, at = [], 0
+        for src, c in zip(srcs, counts):
+            out.append(torch.cat(rows[at:at + c])[: src.size(-1)])
+            at += c
         return out
 
     @torch.no_grad()
@@ -297,8 +407,7 @@ class UniSE:
             raise RuntimeError("UniSE.enhance_pipelined needs a tokenizer (unified_audio_amd.BiCodecTokenizer) or a detokenize callable")
         if mode not in ("se", "tse", "rtse"):
             raise KeyError(mode)
-        segs = [segment(s, normalise=(mode == "se")) for s in srcs]
-        counts = [s.size(0) for s in segs]
+        segs, counts, samples = self._segments(mode, srcs)
         seg_src = torch.cat(segs, dim=0)
         dev = seg_src.device
         n_seg, m = seg_src.size(0), max(1, int(segments_per_batch))
@@ -331,8 +440,14 @@ class UniSE:
                 if k < nb:  # stage 1: features of micro-batch k
                     with torch.cuda.stream(s_feat):
                         x = seg_src[k * m:(k + 1) * m]
-                        f = self.semantic_model(x)
-                        e, rag = None, {}
+                        sm = samples[k * m:(k + 1) * m] if samples is not None else None
+                        rag, steps = {}, mel_frames(SEG_LEN)
+                        if sm is not None and any(n != SEG_LEN for n in sm):  # as _generate: the rows' own lengths through every stage
+                            x, f, mel, rag = self._trimmed_inputs(x, sm)
+                            steps = mel.size(1)
+                        else:
+                            f = self.semantic_model(x)
+                        e = None
                         if ef is not None:
                             own = owner[k * m:(k + 1) * m]
                             e = ef[torch.tensor(own, device=dev)]
@@ -344,23 +459,28 @@ class UniSE:
                             e = e.contiguous()
                             e.record_stream(s_lm)
                         f.record_stream(s_lm)
-                        feats[k] = (f, e, x.size(0), rag)
+                        feats[k] = (f, e, x.size(0), rag, steps)
                         ev_f[k].record(s_feat)
                 j = k - 2
                 if 0 <= j < nb:  # stage 3: waveform of micro-batch k - 2 (enqueued BEFORE the long LM enqueue of this turn)
                     with torch.cuda.stream(s_dec):
                         s_dec.wait_event(ev_l[j])
                         g, s = toks[j]
-                        w = self.detokenize(g.unsqueeze(1), s).squeeze(1)
-                        w.record_stream(cur)
+                        if samples is not None:
+                            w = self._detokenize_rows(g, s, samples[j * m:(j + 1) * m])
+                            for row in w:
+                                row.record_stream(cur)
+                        else:
+                            w = self.detokenize(g.unsqueeze(1), s).squeeze(1)
+                            w.record_stream(cur)
                         wavs[j] = w
                 j = k - 1
                 if 0 <= j < nb:  # stage 2: tokens of micro-batch k - 1
                     with torch.cuda.stream(s_lm):
                         s_lm.wait_event(ev_f[j])
-                        f, e, b, rag = feats[j]
+                        f, e, b, rag, steps = feats[j]
                         g, s = self.dnn.generate(task_name=mode, enroll_mel=None if e is None else _Frames(b, mel_frames(n_enr)), enroll_feats=e,
-                                                 mix_mel=_Frames(b, mel_frames(SEG_LEN)), mix_feats=f, do_sample=False, **rag)
+                                                 mix_mel=_Frames(b, steps), mix_feats=f, do_sample=False, **rag)
                         g.record_stream(s_dec)
                         s.record_stream(s_dec)
                         toks[j] = (g, s)
@@ -373,6 +493,8 @@ class UniSE:
         cur.wait_stream(s_dec)
         cur.wait_stream(s_lm)
         cur.wait_stream(s_feat)
+        if samples is not None:
+            return self._join_rows(srcs, counts, [row for w in wavs for row in w])
         est = torch.cat(wavs, dim=0)
         out, at = [], 0
         for src, c in zip(srcs, counts):
@@ -467,7 +589,8 @@ class Model:
     `test_steps(batches)` is the batched form: any number of the same tuples in one pass (segments of all files share the launches).
     """
 
-    def __init__(self, config, *, device: str | torch.device = "cuda:0", semantic_model=None, tokenizer=None, dnn=None, max_segments: int = 64):
+    def __init__(self, config, *, device: str | torch.device = "cuda:0", semantic_model=None, tokenizer=None, dnn=None, max_segments: int = 64,
+                 tail: str = "wrap"):
         from .bicodec import BiCodecTokenizer
         from .llm import LLM_SFT
         from .ssl import SPEC_WAVLM_BASE_PLUS, SSLFeatureExtractor
@@ -491,7 +614,8 @@ class Model:
             has_config = os.path.isdir(str(path)) and os.path.isfile(os.path.join(str(path), "config.json"))
             semantic_model = SSLFeatureExtractor.from_pretrained(path, None if has_config else SPEC_WAVLM_BASE_PLUS, device=self.device)
         self.semantic_model = semantic_model
-        self.driver = UniSE(self.dnn, self.semantic_model, tokenizer=self.tokenizer, max_segments=max_segments)
+        # tail="trim" (not the reference's behaviour, see UniSE): the last segment of every file at its own length
+        self.driver = UniSE(self.dnn, self.semantic_model, tokenizer=self.tokenizer, max_segments=max_segments, tail=tail)
         if config.get("ckpt_path") and dnn is None:
             import os
 
