@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_offsets.h"
 #include "split_planes.h"
 
 // tuning knobs of tools/variants.py
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
 
     constexpr int SMEM_FLOATS = SPLIT ? (ONE_BUF ? 1 : 2) * (BM + BN) * 3 * CK / 2 : 2 * (BM + BN) * LDS;
     __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
-    __shared__ int s_tap[BM * TAP_WIN];  // source-frame offset (floats, relative to the clip) of (row, tap); -1 = zero padding
+    __shared__ int s_tap[BM * TAP_WIN];  // source-frame offset (floats, relative to the tile's first clip) of (row, tap); -1 = zero padding
     float* sA = smem;
     float* sB = smem + 2 * BM * LDS;
     // SPLIT image: [buffer][operand A rows, then B rows][plane h, m, l] rows of CK = 32 bf16
@@ -206,18 +207,22 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     // MFMAs cost ~30 cycles each (measured), and the per-chunk resolve used to take as long as the MFMA phase itself.
     // Rows past M are clamped to row M-1 and columns past N to column N-1 (their results are never stored), so every
     // load in the main loop is unconditional.
+    // An entry is relative to the FIRST clip of the tile (clip0): (clip - clip0) * T_in * ldx + frame * ldx, below 2^31 by the host's check
+    // (conv_offsets.h), so the main loop adds it to ONE base pointer per thread - no pointer per staged row.
     const bool reflect = p.pad_mode == PAD_REFLECT;
     const int ldx_i = (int)p.ldx;
     const int t_virtual = p.T_in * (p.in_rep > 1 ? p.in_rep : 1);
     const int dil = p.dilation > 1 ? p.dilation : 1;
+    const int clip0 = m0 / p.T_out;  // m0 < M: every tile has a row
+    const unsigned clip_stride = (unsigned)p.T_in * (unsigned)ldx_i;
     auto build_taps = [&](int jbase) {
         for (int e = tid; e < BM * TAP_WIN; e += 256) {
             const int row = e / TAP_WIN, j = jbase + (e % TAP_WIN);
             const int m = min(m0 + row, p.M - 1);
-            const int t = m % p.T_out;
+            const int clip = m / p.T_out, t = m - clip * p.T_out;
             int len = t_virtual, lp = p.Lp;
             if (p.lens) {  // launch-uniform: a ragged call, the clip ends at its own length (never past the T_in its rows are laid out for)
-                len = min(p.lens[m / p.T_out] * p.len_mul, t_virtual);
+                len = min(p.lens[clip] * p.len_mul, t_virtual);
                 lp = len <= p.max_pad ? p.max_pad + 1 : len;
             }
             int r = t * p.stride - p.pad_left + j * dil;
@@ -226,19 +231,21 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
             const bool ok = r >= 0 && r < len && j < p.ksize;
             const unsigned ru = ok ? (unsigned)r : 0u;
             const unsigned src = __umulhi(ru, p.rep_magic) + ru * p.rep_one;  // = r / in_rep
-            s_tap[e] = ok ? (int)(src * (unsigned)ldx_i) : -1;
+            s_tap[e] = ok ? (int)((unsigned)(clip - clip0) * clip_stride + src * (unsigned)ldx_i) : -1;
         }
     };
     if (!LINEAR) build_taps(0);
     int jbase = 0;
 
-    const float* a_ptr[A_IT];  // clip base + this thread's column offset inside a chunk
-    int a_tab[A_IT];           // byte offset of the row's table line
+    // LINEAR: row base + this thread's column offset inside a chunk, per staged row.  Table form: ONE pointer, the tile's first clip + the
+    // column offset; staged row i reads line a_tab0 + i * RPP * TAP_WIN of the table (a compile-time stride: the ds_read's immediate)
+    const float* a_ptr[LINEAR ? A_IT : 1];
+    const int a_tab0 = ld_row * TAP_WIN;
+    if constexpr (LINEAR) {
 #pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-        const int m = min(m0 + ld_row + RPP * i, p.M - 1);
-        a_ptr[i] = LINEAR ? p.x + (long long)m * p.ldx + ld_c4 : p.x + (long long)(m / p.T_out) * p.T_in * p.ldx + ld_c4;
-        a_tab[i] = (ld_row + RPP * i) * TAP_WIN;
+        for (int i = 0; i < A_IT; ++i) a_ptr[i] = p.x + (long long)min(m0 + ld_row + RPP * i, p.M - 1) * p.ldx + ld_c4;
+    } else {
+        a_ptr[0] = p.x + (long long)clip0 * p.T_in * p.ldx + ld_c4;
     }
     const float* b_ptr[B_IT];
     if constexpr (!PRE) {
@@ -288,7 +295,11 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
     // iteration loads (the last one re-loads chunk nk-1, harmlessly).
     f32x4 a_reg[A_IT], b_reg[B_IT];
     u32x4 bp_reg[BP_IT];  // PRE: plane units instead of b_reg
-    float a_keep[A_IT];  // 0 for frames that fall into zero padding (select on the data at LDS-store time, not on the load)
+    // table form: bit A_IT - 1 - i is set when staged row i falls into zero padding - the sign bits of its table entries, shifted in row by
+    // row.  The staged value is then SELECTED to +0 at LDS-store time (the load itself is unconditional, from frame 0 of clip0): no inf or
+    // NaN in that frame can reach a padded position
+    static_assert(A_IT <= 32, "one mask register for the staged rows");
+    unsigned a_pad = 0u;
 
 #define QA_LOAD_GLOBAL(KC)                                                                                     \
     {                                                                                                          \
@@ -312,10 +323,12 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
                 __syncthreads();                                                                               \
             }                                                                                                  \
             const int j_ = ld_hi ? j1_ : j0_, c_ = ld_hi ? c1_ : c0_;                                          \
+            const int* tab_ = s_tap + (a_tab0 + (j_ - jbase));                                                 \
+            const float* ac_ = a_ptr[0] + c_;                                                                  \
             _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                 \
-                const int off_ = s_tap[a_tab[i] + (j_ - jbase)];                                               \
-                a_keep[i] = off_ >= 0 ? 1.f : 0.f;                                                             \
-                a_reg[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + (max(off_, 0) + c_));                    \
+                const int off_ = tab_[i * RPP * TAP_WIN];                                                      \
+                a_pad = __builtin_amdgcn_alignbit(a_pad, (unsigned)off_, 31); /* (a_pad << 1) | sign */        \
+                a_reg[i] = *reinterpret_cast<const f32x4*>(ac_ + (unsigned)max(off_, 0));                      \
             }                                                                                                  \
         }                                                                                                      \
         if constexpr (PRE) {                                                                                   \
@@ -341,7 +354,8 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
             }                                                                                                  \
         }                                                                                                      \
         _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                     \
-            f32x4 v = LINEAR ? a_reg[i] : a_reg[i] * a_keep[i];                                                \
+            f32x4 v = a_reg[i];                                                                                \
+            if (!LINEAR && (a_pad >> (A_IT - 1 - i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};                      \
             if (PRO_ELU) {                                                                                     \
                 v.x = elu_f(v.x); v.y = elu_f(v.y); v.z = elu_f(v.z); v.w = elu_f(v.w);                        \
             }                                                                                                  \
@@ -369,7 +383,8 @@ __global__ __launch_bounds__(256, conv_gemm_min_wg(BM, BN, BK, NPL > 0)) void co
         float* a_ = sA + (BUF) * BM * LDS;                                                                     \
         float* b_ = sB + (BUF) * BN * LDS;                                                                     \
         _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                                     \
-            f32x4 v = LINEAR ? a_reg[i] : a_reg[i] * a_keep[i];                                                \
+            f32x4 v = a_reg[i];                                                                                \
+            if (!LINEAR && (a_pad >> (A_IT - 1 - i) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};                      \
             if (PRO_ELU) {                                                                                     \
                 v.x = elu_f(v.x); v.y = elu_f(v.y); v.z = elu_f(v.z); v.w = elu_f(v.w);                        \
             }                                                                                                  \
@@ -633,17 +648,21 @@ static int gemm_planes(const ConvParams& p) {
 
 // one (tile, prologue, chunk, addressing) choice in its arithmetic instances
 template <int BM, int BN, int WM, int WN, bool ELU, int BK, bool LIN>
-static void launch_instance(const ConvParams& p, long long tiles, hipStream_t stream) {
+static int launch_instance(const ConvParams& p, long long tiles, hipStream_t stream) {
     constexpr bool IMAGE = BN == 128;  // narrower tiles keep the in-loop split: measured slower from an image
     const bool image = IMAGE && p.wp;
     void (*kernel)(const ConvParams) = nullptr;
     switch (gemm_planes(p)) {
-        case 0: kernel = conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 0, false>; break;
+        case 0:  // the fp32 chain has no one-buffer ELU instance (takes_bk16 never sends it one)
+            if constexpr (!(ELU && BK == 16)) kernel = conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 0, false>;
+            break;
         case 1: kernel = image ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 1, IMAGE> : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 1, false>; break;
         case 2: kernel = image ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 2, IMAGE> : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 2, false>; break;
         default: kernel = image ? conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 3, IMAGE> : conv_gemm_kernel<BM, BN, WM, WN, ELU, BK, LIN, 3, false>; break;
     }
+    QA_REQUIRE(kernel != nullptr, "conv_gemm: no %dx%d kernel instance for this launch (ELU %d, BK %d)", BM, BN, (int)ELU, BK);
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    return QA_OK;
 }
 
 // The K-chunk width of a launch (launch_cfg; choose_tile prices the instance this picks).  For the split forms "BK = 16" is the one-buffer
@@ -662,9 +681,11 @@ static void launch_instance(const ConvParams& p, long long tiles, hipStream_t st
 static thread_local int t_gemm_lanes = 1;
 GemmLanes::GemmLanes(int n) : prev(t_gemm_lanes) { t_gemm_lanes = n > 1 ? n : 1; }
 GemmLanes::~GemmLanes() { t_gemm_lanes = prev; }
-static bool takes_bk16(int bm, int bn, long long tiles, int K, int C_in, bool elu) {
-    return bm == 256 ||
-           (bn >= 64 && !elu && ((K <= knob(K_GEMM_BK16) && tiles * t_gemm_lanes >= knob(K_GEMM_BK16_MIN_TILES)) || C_in % 32 != 0));
+// The ELU prologue has one-buffer instances for the split forms of the 128 x 128 tile only (the 64 x 128 one from the image
+// would need scratch); elsewhere it keeps BK = 32.
+static bool takes_bk16(int bm, int bn, long long tiles, int K, int C_in, bool elu, bool split) {
+    return bm == 256 || (bn >= 64 && (!elu || (bm == 128 && bn == 128 && split)) &&
+                         ((K <= knob(K_GEMM_BK16) && tiles * t_gemm_lanes >= knob(K_GEMM_BK16_MIN_TILES)) || C_in % 32 != 0));
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -672,7 +693,7 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     QA_REQUIRE(p.prologue == ACT_NONE || p.prologue == ACT_ELU, "conv_gemm: prologue %d unsupported", p.prologue);
     const long long tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
     const bool linear = is_linear(p), elu = p.prologue == ACT_ELU;
-    const bool bk16 = takes_bk16(BM, BN, tiles, p.K, p.C_in, elu);
+    const bool bk16 = takes_bk16(BM, BN, tiles, p.K, p.C_in, elu, gemm_planes(p) > 0);
     // the fp32 chain's K loop runs K / BK whole chunks and its table form reads each chunk from ONE tap: a BK that does not divide K (and, with
     // the table, C_in) would drop the tail of K or read past a tap's C_in channels - into the next frame or the next channel group.  The split
     // forms stage 32-wide groups as two 16-wide halves, each from its own tap, and zero-fill the missing half of K = 16 mod 32: multiples of 16
@@ -680,6 +701,11 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     const bool table = BM != 256 && (!linear || elu);  // the ELU prologue exists in the table form only
     QA_REQUIRE(p.K % bk == 0 && (!table || p.C_in % bk == 0),
                "conv_gemm: the %dx%d tile's K chunk needs K=%d / C_in=%d to be multiples of %d", BM, BN, p.K, p.C_in, bk);
+    // the table's entries are 32-bit offsets from the first clip of a row tile (conv_offsets.h)
+    int64_t span = 0;
+    QA_REQUIRE(!table || conv_tile_offsets_fit(BM, p.T_out, p.T_in, p.ldx, &span),
+               "conv_gemm: a %d-row tile spans %lld floats of x (%lld clips of T_in=%d x ldx=%lld; T_out=%d), limit 2^31", BM, (long long)span,
+               (long long)ceil_div(BM, p.T_out) + 1, p.T_in, (long long)p.ldx, p.T_out);
     const bool prof = profile_enabled();
     if (prof) {
         const double n = p.algo_n ? p.algo_n : p.N, k = p.algo_k ? p.algo_k : p.K;
@@ -691,14 +717,19 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
     }
     if constexpr (BM == 256) QA_REQUIRE(linear && !elu, "conv_gemm: the 256 x 128 tile exists for LINEAR layers only");
     constexpr int BK16 = BN >= 64 ? 16 : 32;  // the 32-column tile has no BK = 16 instance (bk16 is false for it)
-    if (bk16 && linear) launch_instance<BM, BN, WM, WN, false, BK16, true>(p, tiles, stream);
+    int rc = QA_OK;
+    if (bk16 && linear && !elu) rc = launch_instance<BM, BN, WM, WN, false, BK16, true>(p, tiles, stream);
     else if constexpr (BM != 256) {  // the 256-row tile has the instance above only
-        if (bk16) launch_instance<BM, BN, WM, WN, false, BK16, false>(p, tiles, stream);
-        else if (elu) launch_instance<BM, BN, WM, WN, true, 32, false>(p, tiles, stream);
-        else if (linear) launch_instance<BM, BN, WM, WN, false, 32, true>(p, tiles, stream);
-        else launch_instance<BM, BN, WM, WN, false, 32, false>(p, tiles, stream);
+        if (bk16 && elu) {
+            QA_REQUIRE(BM == 128 && BN == 128, "conv_gemm: the one-buffer ELU instances exist for the 128 x 128 tile only");  // takes_bk16 agrees
+            if constexpr (BM == 128 && BN == 128) rc = launch_instance<BM, BN, WM, WN, true, 16, false>(p, tiles, stream);
+        } else if (bk16) rc = launch_instance<BM, BN, WM, WN, false, BK16, false>(p, tiles, stream);
+        else if (elu) rc = launch_instance<BM, BN, WM, WN, true, 32, false>(p, tiles, stream);
+        else if (linear) rc = launch_instance<BM, BN, WM, WN, false, 32, true>(p, tiles, stream);
+        else rc = launch_instance<BM, BN, WM, WN, false, 32, false>(p, tiles, stream);
     }
     if (prof) profile_record_end(stream);
+    if (rc != QA_OK) return rc;
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -741,7 +772,7 @@ static int workgroups_per_cu(int cfg, bool bk16, bool split) {
 static double tile_cost(const TileQuery& t, int cfg, int bm, int bn, double eff) {
     constexpr double kTile = 128.0 * 128.0, kRamp = 0.22, kLaunch = 0.27 * 512.0;
     const long long tiles = ceil_div(t.M, bm) * ceil_div(t.N, bn);
-    const long long w = workgroups_per_cu(cfg, takes_bk16(bm, bn, tiles, (int)t.K, t.C_in, t.elu), t.split);
+    const long long w = workgroups_per_cu(cfg, takes_bk16(bm, bn, tiles, (int)t.K, t.C_in, t.elu, t.split), t.split);
     const long long n = tiles * (t.share > 1 ? t.share : 1), cap = 256 * w;
     const long long rounds = ceil_div(n, cap), m = n - (rounds - 1) * cap;
     double last = 0.5 * ((double)ceil_div(m, 256) + (double)m / 256.0);
@@ -871,6 +902,24 @@ int conv_params_from_args(const qa_conv_args& a, ConvParams* out) {
 }
 
 }  // namespace qa
+
+// test hook (not in the public header): qa_conv1d_cl with the two pieces of tap-table geometry that qa_conv_args does not carry - a dilation
+// (zero padding, in_rep 1) and per-clip lengths (lens: DEVICE int [B], or null; clip b holds lens[b] * len_mul frames, as ConvParams says)
+extern "C" int qa_debug_conv1d_cl_ex(const qa_conv_args* args, int dilation, const int* lens, int len_mul, void* stream) {
+    if (!args || dilation < 1) {
+        qa::set_error("qa_debug_conv1d_cl_ex: bad argument");
+        return QA_ERR_INVALID;
+    }
+    qa::ConvParams p;
+    QA_TRY(qa::conv_params_from_args(*args, &p));
+    p.dilation = dilation;
+    if (lens) {
+        p.lens = lens;
+        p.len_mul = len_mul;
+        p.max_pad = args->pad_left > args->pad_right ? args->pad_left : args->pad_right;
+    }
+    return qa::launch_conv_gemm(p, static_cast<hipStream_t>(stream));
+}
 
 // test hook (not in the public header): the tile (a QA_GEMM_CFG value) launch_conv_gemm would take for an M x N x K layer of kernel size
 // `ksize` - `linear`: a LINEAR-form layer without prologue; `share`: launches of this shape running side by side; the weight is taken to have a pre-split
