@@ -344,6 +344,10 @@ int qa_debug_lstm_stats(int32_t device, int64_t* out4);
  * inside a codec call (knobs QA_LSTM_XCD, QA_LSTM_TEAM, QA_LSTM_PERSISTENT).  Waits for an in-launch recurrence and returns an error,
  * without re-running on the per-step kernels, if its step barrier timed out. */
 int qa_debug_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d, void* stream);
+/* One chunk of a recurrence that continues (tests; the streaming Transformer's LSTM): as qa_debug_lstm on the per-step kernels, but step 0
+ * starts from h_state / c_state [B, d], and both hold the state behind step T - 1 when the chunk has run. */
+int qa_debug_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
+                        void* stream);
 /* Attention launches the host has issued in this process so far, by arithmetic (tests): out2[0] the fp32 chain (QA_ATT_MATH = 0, and
  * every launch of a UniSE LM handle), out2[1] split-6.  Counted where the host launches: a launch recorded into a captured graph counts
  * once, at capture, and its replays do not count. */
@@ -440,6 +444,53 @@ int qa_mimi_stream_reset(qa_mimi* m);
 int qa_mimi_stream_end(qa_mimi* m);
 /* tokens seen since begin / reset; -1 outside streaming */
 int64_t qa_mimi_stream_offset(const qa_mimi* m);
+
+/* ---- codec Transformer: offline, cache mode and a streaming state ------------------------------------
+ * The block every H-Codec version runs in its encoder and decoder (QuarkAudio-HCodec/HCodec-1.0/vq/encoder_modules/transformer.py:396-489:
+ * RMSNorm -> nn.LSTM -> QKV + rotate-half RoPE -> attention -> O, RMSNorm -> SwiGLU), on its own.  Weights: `<prefix>.layers.N.
+ * {self_attn.rnn.{weight,bias}_{ih,hh}_l0, self_attn.{q,k,v}_proj.{weight,bias}, self_attn.o_proj.weight, input_layernorm.weight,
+ * post_attention_layernorm.weight, mlp.w1/w2/w3.weight}`.  x and y are fp32 [B, frames, hidden_size] device buffers, x != y.
+ *   qa_transformer_forward         forward(x): no mask; causal: key j visible to query i iff j <= i and (left_context == 0 or
+ *                                  i - j < left_context)                                                      (transformer.py:436-475)
+ *   qa_transformer_cache_*         past_key_values: per layer the roped K and V rows [B, capacity, d], capacity <= 8192
+ *   qa_transformer_forward_cached  forward(x, past_key_values, use_cache=True) as the reference runs it: the LSTM starts from zero on
+ *                                  every call (:133), RoPE at positions len .. len + n - 1 (:459-467), keys = cache | chunk.  Non-causal:
+ *                                  every query sees every key, the later ones of its own chunk included.  Causal with an empty cache: the
+ *                                  offline causal call, which also fills the cache.  Causal with a non-empty cache is refused - the
+ *                                  reference's (T, T) mask cannot be combined with cached keys and raises there.
+ *   qa_transformer_stream_*        what the reference cannot do and the causal graph allows exactly: the concatenated outputs of any
+ *                                  chunking equal qa_transformer_forward of the concatenated input (up to fp32 summation order).  State
+ *                                  per layer: the LSTM's (h, c) and the K / V rows; one running offset.  A step of n frames carries the
+ *                                  recurrence on from (h, c), ropes at offset + t, writes its K / V rows, then attends: the query at
+ *                                  p = offset + i sees key j iff j <= p and (left_context == 0 or p - j < left_context).  Needs causal = 1.
+ *                                  offset + n > capacity is refused before anything is launched and leaves the state untouched.
+ *                                  _reset: offset and LSTM states to zero (cached rows stay and are invisible); _offset: frames since
+ *                                  begin / reset, -1 outside streaming. */
+typedef struct qa_transformer_spec {
+    int32_t hidden_size;          /* 512 / 768 / 1024 / 1536; a multiple of 128 */
+    int32_t intermediate_size;
+    int32_t num_attention_heads;  /* head_dim = hidden_size / heads in {64, 96, 128} */
+    int32_t num_hidden_layers;
+    int32_t causal;
+    int32_t left_context;         /* > 0: use_sliding_window with this left_context; needs causal */
+} qa_transformer_spec;
+typedef struct qa_transformer qa_transformer;
+typedef struct qa_transformer_cache qa_transformer_cache;
+int qa_transformer_create(qa_transformer** out, const qa_transformer_spec* spec, const qa_tensor* tensors, int64_t n_tensors,
+                          const char* prefix, int device);
+void qa_transformer_destroy(qa_transformer* h);
+int qa_transformer_forward(qa_transformer* h, const float* x, int64_t B, int64_t T, float* y, void* stream);
+int qa_transformer_cache_create(qa_transformer* h, int64_t B, int64_t capacity, qa_transformer_cache** out);
+void qa_transformer_cache_destroy(qa_transformer_cache* c);
+int64_t qa_transformer_cache_length(const qa_transformer_cache* c);
+int qa_transformer_cache_reset(qa_transformer_cache* c);
+int qa_transformer_forward_cached(qa_transformer* h, qa_transformer_cache* cache, const float* x, int64_t B, int64_t n, float* y,
+                                  void* stream);
+int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity);
+int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, float* y, void* stream);
+int qa_transformer_stream_reset(qa_transformer* h);
+int qa_transformer_stream_end(qa_transformer* h);
+int64_t qa_transformer_stream_offset(const qa_transformer* h);
 
 /* ---- BiCodec detokenizer ------------------------------------------------------------------------
  * BiCodec.detokenize(semantic_tokens, global_tokens) (QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199), the stage

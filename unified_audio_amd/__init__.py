@@ -12,7 +12,8 @@ from .llm import KVCache, LLM_SFT, CustomLlamaModel, sample_logits  # noqa: F401
 from .conformer import ConditionEncoder, ConformerEncoder  # noqa: F401
 from .bicodec import BiCodec, BiCodecEncoderSpec, BiCodecForwardSpec, BiCodecSpec, BiCodecTokenizer, SPEC_BICODEC, SPEC_BICODEC_ENCODER, wav_normalize  # noqa: F401
 from .mimi import StreamingTransformer  # noqa: F401
+from .transformer import Transformer, TransformerCache  # noqa: F401
 from .unise import UniSE  # noqa: F401
 from .ssl import SPEC_HUBERT_BASE, SPEC_WAVLM_BASE_PLUS, SPEC_XLSR53, SSLFeatureExtractor, SSLSpec  # noqa: F401
 
-__all__ = ["CustomLlamaModel", "KVCache", "ConformerEncoder", "ConditionEncoder", "StreamingTransformer", "BiCodecTokenizer", "BiCodec", "BiCodecSpec", "SPEC_BICODEC", "BiCodecEncoderSpec", "SPEC_BICODEC_ENCODER", "BiCodecForwardSpec", "wav_normalize", "sample_logits", "UniSE", "SSLFeatureExtractor", "SSLSpec", "SPEC_HUBERT_BASE", "SPEC_XLSR53", "SPEC_WAVLM_BASE_PLUS", "LLM_SFT", "Codec", "HCodecSpec", "HCodecTokenizer", "SPEC_10", "SPEC_15", "SPEC_20", "QuarkAudioError", "load_library", "lib_path", "gemm_math", "set_gemm_math", "gemm_math_name"]
+__all__ = ["CustomLlamaModel", "KVCache", "ConformerEncoder", "ConditionEncoder", "StreamingTransformer", "Transformer", "TransformerCache", "BiCodecTokenizer", "BiCodec", "BiCodecSpec", "SPEC_BICODEC", "BiCodecEncoderSpec", "SPEC_BICODEC_ENCODER", "BiCodecForwardSpec", "wav_normalize", "sample_logits", "UniSE", "SSLFeatureExtractor", "SSLSpec", "SPEC_HUBERT_BASE", "SPEC_XLSR53", "SPEC_WAVLM_BASE_PLUS", "LLM_SFT", "Codec", "HCodecSpec", "HCodecTokenizer", "SPEC_10", "SPEC_15", "SPEC_20", "QuarkAudioError", "load_library", "lib_path", "gemm_math", "set_gemm_math", "gemm_math_name"]

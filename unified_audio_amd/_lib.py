@@ -69,6 +69,11 @@ class qa_mimi_spec(C.Structure):
                 ("causal", C.c_int32), ("context", C.c_int32)]
 
 
+class qa_transformer_spec(C.Structure):
+    _fields_ = [("hidden_size", C.c_int32), ("intermediate_size", C.c_int32), ("num_attention_heads", C.c_int32),
+                ("num_hidden_layers", C.c_int32), ("causal", C.c_int32), ("left_context", C.c_int32)]
+
+
 class qa_bicodec_spec(C.Structure):
     _fields_ = [
         ("latent_dim", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32), ("spk_latent_dim", C.c_int32),
@@ -187,6 +192,21 @@ SYMBOLS = {
     "qa_mimi_stream_reset": (C.c_int, [C.c_void_p]),
     "qa_mimi_stream_end": (C.c_int, [C.c_void_p]),
     "qa_mimi_stream_offset": (C.c_int64, [C.c_void_p]),
+    "qa_transformer_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_transformer_spec), C.POINTER(qa_tensor), C.c_int64, C.c_char_p,
+                                        C.c_int]),
+    "qa_transformer_destroy": (None, [C.c_void_p]),
+    "qa_transformer_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_transformer_cache_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "qa_transformer_cache_destroy": (None, [C.c_void_p]),
+    "qa_transformer_cache_length": (C.c_int64, [C.c_void_p]),
+    "qa_transformer_cache_reset": (C.c_int, [C.c_void_p]),
+    "qa_transformer_forward_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_transformer_stream_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "qa_transformer_stream_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "qa_transformer_stream_reset": (C.c_int, [C.c_void_p]),
+    "qa_transformer_stream_end": (C.c_int, [C.c_void_p]),
+    "qa_transformer_stream_offset": (C.c_int64, [C.c_void_p]),
+    "qa_debug_lstm_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "qa_ssl_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_ssl_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
     "qa_ssl_destroy": (None, [C.c_void_p]),
     "qa_ssl_frames": (C.c_int64, [C.c_void_p, C.c_int64]),

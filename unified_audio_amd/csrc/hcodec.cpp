@@ -157,6 +157,29 @@ struct qa_mimi : Handle {
     }
 };
 
+// One codec Transformer (encoder_modules/transformer.py:396-489) on its own: offline forward, the reference's cache mode and a
+// streaming state
+struct qa_transformer : Handle {
+    qa_transformer_spec spec{};
+    TransformerW w;
+    // streaming state (stream_B > 0: between qa_transformer_stream_begin and _end): per layer the LSTM's (h, c) [B, d] and the roped
+    // K / V rows [B, cap, d], one allocation; `offset` frames seen since begin / reset
+    int stream_B = 0, stream_cap = 0, offset = 0;
+    bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
+    float* stream_mem = nullptr;
+    std::vector<float*> kc, vc, hs, cs;
+    ~qa_transformer() {
+        if (stream_mem) (void)hipFree(stream_mem);
+    }
+};
+// past_key_values of Transformer.forward(x, past_key_values, use_cache=True): per layer the roped K and V rows [B, cap, d] in fp32
+struct qa_transformer_cache {
+    const qa_transformer* owner = nullptr;
+    int device = 0, B = 0, cap = 0, len = 0;
+    float* mem = nullptr;
+    std::vector<float*> kc, vc;
+};
+
 namespace qa {
 namespace {
 
@@ -315,7 +338,8 @@ inline int zpad_right(int k, bool causal) { return causal ? 0 : k / 2; }
 
 // In place on x [t.B, t.T, d].  Ragged calls (non-causal): only the attention looks past a clip's end - the LSTM runs forward, everything
 // else is row-wise - so the lengths become one [B, N] key-padding mask, built once per call, for the KMASK form.
-int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, const std::string& tap_prefix) {
+// left_context > 0 (causal graphs only): the sliding window of Transformer(use_sliding_window=True) - query i sees key j iff i - j < left_context.
+int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, const std::string& tap_prefix, int left_context = 0) {
     const int d = tw.d, H = tw.heads, hd = d / H, B = t.B, N = t.T;
     const int64_t rows = t.rows();
     QA_REQUIRE(N <= MAX_POS, "transformer: sequence of %d frames exceeds %d", N, MAX_POS);
@@ -330,6 +354,7 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
     float* cst = c.arena.alloc<float>((size_t)B * d);
     AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
     at.causal = t.causal ? 1 : 0;
+    at.context = t.causal ? left_context : 0;
     if (t.rl.n) {
         QA_REQUIRE(!t.causal, "transformer: per-clip lengths exist for the non-causal graph only");
         unsigned char* kvalid = c.arena.alloc<unsigned char>(rows);
@@ -354,6 +379,68 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
         QA_TRY(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
         QA_TRY(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
         c.tap(lp + ".x_mlp", x, rows * d);
+    }
+    c.arena.release(mark);
+    return QA_OK;
+}
+
+// A chunk of N frames at positions pos0 .. pos0 + N - 1 over per-layer K / V caches [B, cap, d]: the cached forward and the streaming step
+// of qa_transformer, in place on x [B, N, d].  Per layer the chunk's roped K and V rows are written to cache rows
+// pos0 .. pos0 + N - 1 before its queries attend over rows 0 .. pos0 + N - 1.
+struct TrChunk {
+    float* const* kc = nullptr;  // [layer] -> [B, cap, d]
+    float* const* vc = nullptr;
+    int cap = 0, pos0 = 0;
+    int causal = 0, context = 0;  // causal = 0: every query sees every key, the later ones of its own chunk included (mask None)
+    // streaming: the carried LSTM state of every layer [B, d] (read at step 0, left at the chunk's last step); null: the LSTM starts from
+    // zero, as the reference's does on every call (transformer.py:133)
+    float* const* hs = nullptr;
+    float* const* cs = nullptr;
+};
+int transformer_chunk_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const TrChunk& ch) {
+    const int d = tw.d, H = tw.heads, hd = d / H;
+    const int64_t rows = (int64_t)B * N;
+    const size_t mark = c.arena.mark();
+    float* hn = c.arena.alloc<float>(rows * d);
+    const int wide = std::max(4 * d, tw.inter);
+    float* big = c.arena.alloc<float>(rows * wide);
+    float* big2 = c.arena.alloc<float>(rows * wide);
+    float* hl = c.arena.alloc<float>(rows * d);
+    float* qkv = c.arena.alloc<float>(rows * 3 * d);
+    float* att = c.arena.alloc<float>(rows * d);
+    float* cst = ch.hs ? nullptr : c.arena.alloc<float>((size_t)B * d);
+    // a stream step of a few frames over a long history: the split-key kernel (stream_attn.hip), 1.0 - 1.5 x the step through
+    // attention_kernel up to 256 query rows per head and 0.92 - 1.01 x at 512 (B = 32 x 16 frames: its partial records outweigh the
+    // parallelism it adds; profiles/transformer_stream_bench.jsonl).  QA_TR_SHORT_ATTN: 0 never, 2 every chunk of <= 16 frames
+    const long long short_mode = knob(K_TR_SHORT_ATTN);
+    const bool short_chunk = ch.hs && ch.causal && N <= ATTN_SHORT_MAX_Q && (short_mode == 2 || (short_mode == 1 && (long long)B * N <= 256));
+    float* part = short_chunk ? c.arena.alloc<float>(attn_short_part_floats(B, H, hd, N, ch.cap)) : nullptr;
+    AttnArgs at;
+    at.q = qkv; at.ldq = 3 * d; at.out = att; at.ldo = d;
+    at.ldkv = d; at.kv_batch_stride = (long long)ch.cap * d;
+    at.B = B; at.n_q = N; at.n_keys = ch.pos0 + N; at.H = H; at.hd = hd;
+    at.scale = 1.0f / std::sqrt((float)hd);
+    at.causal = ch.causal;
+    at.context = ch.causal ? ch.context : 0;
+    for (size_t l = 0; l < tw.layers.size(); ++l) {
+        const TransformerLayerW& L = tw.layers[l];
+        QA_TRY(rmsnorm_op(c, x, L.ln1, hn, rows, d, 1e-6f));
+        QA_TRY(linear_op(c, hn, rows, L.ih, big));
+        if (ch.hs) QA_RUN(c, launch_lstm_carry(big, L.w_hh, hl, ch.hs[l], ch.cs[l], B, N, d, c.stream));
+        else QA_RUN(c, launch_lstm(big, L.w_hh, hl, cst, B, N, d, c.stream));
+        QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
+        QA_RUN(c, launch_rope_append(qkv, tw.rope, ch.kc[l], ch.vc[l], B, N, H, hd, ch.pos0, ch.cap, c.stream));
+        if (short_chunk) {
+            QA_RUN(c, launch_attention_short(qkv, 3 * d, ch.kc[l], ch.vc[l], att, part, B, N, H, hd, ch.pos0, ch.cap, at.context, c.stream));
+        } else {
+            at.k = ch.kc[l]; at.v = ch.vc[l];
+            QA_TRY(attention_op(c, at));
+        }
+        QA_TRY(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
+        QA_TRY(rmsnorm_op(c, x, L.ln2, hn, rows, d, 1e-6f));
+        QA_TRY(linear_op(c, hn, rows, L.w1, big));
+        QA_TRY(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
+        QA_TRY(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
     }
     c.arena.release(mark);
     return QA_OK;
@@ -1267,7 +1354,7 @@ int build(qa_hcodec* h, const HostTable& tab) {
 // was shared with another such kernel), runs the graph again on the per-step kernels - the call that hit the failure returns
 // valid results, and the device stops choosing the persistent kernel by itself.
 template <typename F>
-static int run_graph_checked(qa_hcodec* h, F&& graph) {
+static int run_graph_checked(Handle* h, F&& graph) {
     Ctx& c = h->ctx;
     void* ticket = nullptr;
     QA_TRY(lstm_call_begin(h->device, &ticket));
@@ -1733,5 +1820,210 @@ int qa_mimi_stream_end(qa_mimi* m) {
 }
 
 int64_t qa_mimi_stream_offset(const qa_mimi* m) { return (m && m->st.B > 0) ? m->st.offset : -1; }
+
+/* ---- codec Transformer: offline, cache mode, streaming state ------------------------------------------ */
+
+int qa_transformer_create(qa_transformer** out, const qa_transformer_spec* spec, const qa_tensor* tensors, int64_t n_tensors,
+                          const char* prefix, int device) {
+    QA_REQUIRE(out && spec && tensors && prefix, "qa_transformer_create: null argument");
+    *out = nullptr;
+    const qa_transformer_spec& sp = *spec;
+    QA_REQUIRE(sp.hidden_size > 0 && sp.num_attention_heads > 0 && sp.hidden_size % sp.num_attention_heads == 0 && sp.num_hidden_layers > 0 &&
+                   sp.intermediate_size > 0,
+               "qa_transformer_create: bad sizes");
+    const int hd = sp.hidden_size / sp.num_attention_heads;
+    QA_REQUIRE(hd == 64 || hd == 96 || hd == 128, "qa_transformer_create: head_dim %d unsupported (64/96/128)", hd);
+    QA_REQUIRE(sp.hidden_size % 128 == 0, "qa_transformer_create: hidden_size %d must be a multiple of 128 (the LSTM recurrence)", sp.hidden_size);
+    QA_REQUIRE(sp.intermediate_size % 32 == 0, "qa_transformer_create: intermediate_size %d must be a multiple of 32", sp.intermediate_size);
+    QA_REQUIRE(sp.left_context >= 0 && sp.left_context <= MAX_POS, "qa_transformer_create: left_context %d outside [0, %d]", sp.left_context,
+               MAX_POS);
+    QA_REQUIRE(sp.left_context == 0 || sp.causal, "qa_transformer_create: left_context (use_sliding_window) needs causal");
+    QA_HIP(hipSetDevice(device));
+    std::unique_ptr<qa_transformer> h(new qa_transformer());
+    h->spec = sp;
+    h->device = device;
+    HostTable tab(tensors, n_tensors);
+    Loader b(tab, h->store);
+    build_transformer(b, &h->w, prefix, sp.hidden_size, sp.num_hidden_layers, sp.num_attention_heads, sp.intermediate_size);
+    QA_TRY(b.upload());
+    *out = h.release();
+    return QA_OK;
+}
+
+void qa_transformer_destroy(qa_transformer* h) { destroy_handle(h); }
+
+static int transformer_check_io(const char* fn, const qa_transformer* h, const float* x, const float* y, int64_t B, int64_t n) {
+    QA_REQUIRE(h && x && y, "%s: null argument", fn);
+    QA_REQUIRE(x != y, "%s: x and y must be different buffers", fn);
+    QA_REQUIRE(B > 0 && n > 0 && n <= MAX_POS && B * n < (1LL << 31), "%s: x is [%lld, %lld, d] (at most %d frames)", fn, (long long)B,
+               (long long)n, MAX_POS);
+    return QA_OK;
+}
+
+int qa_transformer_forward(qa_transformer* h, const float* x, int64_t B, int64_t T, float* y, void* stream) {
+    QA_TRY(transformer_check_io("qa_transformer_forward", h, x, y, B, T));
+    QA_REQUIRE(h->stream_B == 0, "qa_transformer_forward: the handle is in streaming mode, use qa_transformer_stream_step");
+    Ctx& c = h->ctx;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    auto graph = [&]() -> int {
+        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * T * h->w.d, hipMemcpyDeviceToDevice, s));
+        return transformer_op(c, h->w, y, TimeAxis{(int)B, (int)T, h->spec.causal != 0, ClipLens()}, "", h->spec.left_context);
+    };
+    QA_TRY(plan(h->device, s, c, h->ws, graph));
+    return run_graph_checked(h, graph);
+}
+
+// the per-layer views of `mem`: `lead` floats per layer in front of the two [B, cap, d] caches (the streaming state's h and c)
+static void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, std::vector<float*>* kc, std::vector<float*>* vc) {
+    kc->resize(layers);
+    vc->resize(layers);
+    for (size_t l = 0; l < layers; ++l) {
+        (*kc)[l] = mem + l * (lead + 2 * per) + lead;
+        (*vc)[l] = (*kc)[l] + per;
+    }
+}
+
+int qa_transformer_cache_create(qa_transformer* h, int64_t B, int64_t capacity, qa_transformer_cache** out) {
+    QA_REQUIRE(h && out, "qa_transformer_cache_create: null argument");
+    *out = nullptr;
+    QA_REQUIRE(B > 0 && B < (1 << 20) && capacity >= 1 && capacity <= MAX_POS, "qa_transformer_cache_create: batch %lld, capacity %lld (1 .. %d)",
+               (long long)B, (long long)capacity, MAX_POS);
+    QA_HIP(hipSetDevice(h->device));
+    std::unique_ptr<qa_transformer_cache> c(new qa_transformer_cache());
+    const size_t L = h->w.layers.size(), per = (size_t)B * capacity * h->w.d;
+    // never cleared: no kernel reads a cache row at or behind the key count of its call
+    QA_HIP(hipMalloc(reinterpret_cast<void**>(&c->mem), sizeof(float) * 2 * L * per));
+    transformer_kv_views(c->mem, L, 0, per, &c->kc, &c->vc);
+    c->owner = h;
+    c->device = h->device;
+    c->B = (int)B;
+    c->cap = (int)capacity;
+    *out = c.release();
+    return QA_OK;
+}
+
+void qa_transformer_cache_destroy(qa_transformer_cache* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    if (c->mem) (void)hipFree(c->mem);
+    delete c;
+}
+
+int64_t qa_transformer_cache_length(const qa_transformer_cache* c) { return c ? c->len : -1; }
+
+int qa_transformer_cache_reset(qa_transformer_cache* c) {
+    QA_REQUIRE(c, "qa_transformer_cache_reset: null cache");
+    c->len = 0;  // the rows stay and become invisible
+    return QA_OK;
+}
+
+int qa_transformer_forward_cached(qa_transformer* h, qa_transformer_cache* cache, const float* x, int64_t B, int64_t n, float* y,
+                                  void* stream) {
+    QA_TRY(transformer_check_io("qa_transformer_forward_cached", h, x, y, B, n));
+    QA_REQUIRE(cache, "qa_transformer_forward_cached: null cache");
+    QA_REQUIRE(cache->owner == h, "qa_transformer_forward_cached: the cache was created for another Transformer");
+    QA_REQUIRE(B == cache->B, "qa_transformer_forward_cached: the cache holds %d sequences, x has %lld", cache->B, (long long)B);
+    QA_REQUIRE(!(h->spec.causal && cache->len > 0),
+               "qa_transformer_forward_cached: a causal Transformer cannot extend a cache that already holds %d frames - the reference builds a "
+               "(T, T) mask for the chunk alone and raises against the cached keys (transformer.py:469-475); stream a causal Transformer with "
+               "qa_transformer_stream_begin / qa_transformer_stream_step", cache->len);
+    QA_REQUIRE((int64_t)cache->len + n <= cache->cap, "qa_transformer_forward_cached: %d cached + %lld new frames exceed the capacity %d",
+               cache->len, (long long)n, cache->cap);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture("qa_transformer_forward_cached", s, CACHE_IS_HOST_STATE));
+    Ctx& c = h->ctx;
+    TrChunk ch;
+    ch.kc = cache->kc.data(); ch.vc = cache->vc.data();
+    ch.cap = cache->cap; ch.pos0 = cache->len;
+    ch.causal = h->spec.causal; ch.context = h->spec.left_context;
+    auto graph = [&]() -> int {
+        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, s));
+        return transformer_chunk_op(c, h->w, y, (int)B, (int)n, ch);
+    };
+    QA_TRY(plan(h->device, s, c, h->ws, graph));
+    QA_TRY(run_graph_checked(h, graph));
+    cache->len += (int)n;
+    return QA_OK;
+}
+
+static void transformer_stream_free(qa_transformer* h) {
+    if (h->stream_mem) {
+        (void)hipDeviceSynchronize();
+        (void)hipFree(h->stream_mem);
+    }
+    h->stream_mem = nullptr;
+    h->stream_B = h->stream_cap = h->offset = 0;
+}
+
+int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) {
+    QA_REQUIRE(h, "qa_transformer_stream_begin: null handle");
+    QA_REQUIRE(h->spec.causal, "qa_transformer_stream_begin: streaming needs a causal Transformer (a non-causal query sees frames that have "
+               "not arrived yet)");
+    QA_REQUIRE(B > 0 && B < (1 << 20) && capacity >= 1 && capacity <= MAX_POS, "qa_transformer_stream_begin: batch %lld, capacity %lld (1 .. %d)",
+               (long long)B, (long long)capacity, MAX_POS);
+    QA_HIP(hipSetDevice(h->device));
+    transformer_stream_free(h);
+    const size_t L = h->w.layers.size(), st = (size_t)B * h->w.d, per = (size_t)B * capacity * h->w.d;
+    QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->stream_mem), sizeof(float) * L * (2 * st + 2 * per)));
+    transformer_kv_views(h->stream_mem, L, 2 * st, per, &h->kc, &h->vc);
+    h->hs.resize(L);
+    h->cs.resize(L);
+    for (size_t l = 0; l < L; ++l) {
+        h->hs[l] = h->kc[l] - 2 * st;
+        h->cs[l] = h->kc[l] - st;
+    }
+    h->stream_B = (int)B;
+    h->stream_cap = (int)capacity;
+    h->offset = 0;
+    h->zero_state = true;
+    return QA_OK;
+}
+
+int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, float* y, void* stream) {
+    QA_REQUIRE(h && h->stream_B > 0, "qa_transformer_stream_step: not streaming (call qa_transformer_stream_begin)");
+    QA_TRY(transformer_check_io("qa_transformer_stream_step", h, x, y, h->stream_B, n));
+    // refused before any launch: the state stays as it was
+    QA_REQUIRE((int64_t)h->offset + n <= h->stream_cap, "qa_transformer_stream_step: %d streamed + %lld new frames exceed the capacity %d of "
+               "this stream (max_frames)", h->offset, (long long)n, h->stream_cap);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture("qa_transformer_stream_step", s, CACHE_IS_HOST_STATE));
+    QA_HIP(hipSetDevice(h->device));
+    const int B = h->stream_B;
+    if (h->zero_state) {  // begin / reset: (h, c) = 0 of every layer, in stream order like the step itself
+        const size_t st = (size_t)B * h->w.d;
+        for (size_t l = 0; l < h->hs.size(); ++l) QA_HIP(hipMemsetAsync(h->hs[l], 0, sizeof(float) * 2 * st, s));
+        h->zero_state = false;
+    }
+    Ctx& c = h->ctx;
+    TrChunk ch;
+    ch.kc = h->kc.data(); ch.vc = h->vc.data();
+    ch.cap = h->stream_cap; ch.pos0 = h->offset;
+    ch.causal = 1; ch.context = h->spec.left_context;
+    ch.hs = h->hs.data(); ch.cs = h->cs.data();
+    auto graph = [&]() -> int {
+        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, s));
+        return transformer_chunk_op(c, h->w, y, B, (int)n, ch);
+    };
+    QA_TRY(run_planned(*h, stream, graph));
+    h->offset += (int)n;
+    return QA_OK;
+}
+
+int qa_transformer_stream_reset(qa_transformer* h) {
+    QA_REQUIRE(h && h->stream_B > 0, "qa_transformer_stream_reset: not streaming");
+    h->offset = 0;  // the cached rows stay and become invisible: no step reads a row at or behind offset + n
+    h->zero_state = true;
+    return QA_OK;
+}
+
+int qa_transformer_stream_end(qa_transformer* h) {
+    QA_REQUIRE(h, "qa_transformer_stream_end: null handle");
+    (void)hipSetDevice(h->device);
+    transformer_stream_free(h);
+    return QA_OK;
+}
+
+int64_t qa_transformer_stream_offset(const qa_transformer* h) { return (h && h->stream_B > 0) ? h->offset : -1; }
 
 }  // extern "C"

@@ -125,6 +125,20 @@ inline AttnArgs attn_packed_qkv(const float* qkv, float* att, int B, int N, int 
 int launch_ring_append(const float* k, const float* v, long long ld, float* kc, float* vc, int B, int T, int d, int cap, int pos0,
                        hipStream_t s);
 
+// stream_attn.hip : what a chunk of a linear (non-ring) K/V cache needs beside launch_attention
+// Rotate-half RoPE of q (in place) and k of a packed projection qkv [B n, 3 d] at positions pos0 + t (table cs [.][hd / 2][2]); the
+// roped k and v rows go to rows pos0 .. pos0 + n - 1 of the caches kc / vc [B, cap, d].  pos0 + n <= cap is the caller's check
+int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s);
+// Causal attention of a short chunk (n <= ATTN_SHORT_MAX_Q queries at positions pos0 + i) over such a cache, keys 0 .. pos0 + n - 1 under
+// the window `context` (0 = none), fp32 arithmetic.  A (row, head) is split over workgroups that own the FIXED key ranges
+// [s L, (s + 1) L), L = attn_short_split_keys(cap): a key lands in the same split, tile and lane whatever pos0 is.  Partial records
+// [n, hd | m | l] per split in `part` (attn_short_part_floats), merged in split order by a second launch.  q [B n, ldq], out [B n, d]
+constexpr int ATTN_SHORT_MAX_Q = 16;
+int attn_short_split_keys(int cap);
+size_t attn_short_part_floats(int B, int H, int hd, int n, int cap);
+int launch_attention_short(const float* q, long long ldq, const float* kc, const float* vc, float* out, float* part, int B, int n, int H,
+                           int hd, int pos0, int cap, int context, hipStream_t s);
+
 // lstm.hip : one nn.LSTM layer (batch_first, zero initial state) given the precomputed input projection
 //   xw [B, T, 4d] = x W_ih^T + b_ih + b_hh with the 4d axis permuted to (unit, gate) order,
 //   w_hh [4d, d] rows permuted the same way.  h_out [B, T, d].  c_state [B, d] scratch.
@@ -132,6 +146,10 @@ int launch_ring_append(const float* k, const float* v, long long ld, float* kc, 
 // whose mask a replayed graph is not known to inherit
 int launch_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_state, int B, int T, int d,
                 hipStream_t s, bool eager = false);
+// One chunk of a recurrence that continues (the streaming Transformer): step 0 starts from h_state / c_state [B, d], which hold the
+// state behind step T - 1 on return.  Per-step kernels only, launched eagerly on `s`; h_out [B, T, d] as in launch_lstm
+int launch_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
+                      hipStream_t s);
 // persistent-recurrence bookkeeping for the model graphs: launches so far on `dev`; wait for `s` and report (and clear) a barrier
 // time-out; make this thread's next launch_lstm calls take the per-step kernels
 int lstm_call_begin(int dev, void** ticket);                  // open a model-graph call: own error word + launch count (thread-local)

@@ -27,6 +27,7 @@ namespace qa {
     X(BATCH_SPLIT_MIN_ROWS, "QA_BATCH_SPLIT_MIN_ROWS", 500, "QA_BATCH_SPLIT: fewest rows (clips x frames) of the smaller lane at which a region is split (10 s clips: lanes of 250 rows lose 0.5 ms, 500 rows gain 0.3 ms; tests: 0)") \
     X(SEANET_FUSED, "QA_SEANET_FUSED", 1, "fused conv0 + first SEANet residual block")                                           \
     X(MIMI_ROPE_WINDOW, "QA_MIMI_ROPE_WINDOW", 8192, "mimi streaming: positions covered by the RoPE table before the rolling window takes over (tests shrink it)") \
+    X(TR_SHORT_ATTN, "QA_TR_SHORT_ATTN", 1, "codec Transformer streaming step of 1 .. 16 frames: 1 = the split-key short-chunk attention (stream_attn.hip: fixed key ranges per workgroup, fp32, partial records merged by a second launch) while batch x frames <= 256, attention_kernel above (where it is the faster one); 2 = the short-chunk kernel for every step of <= 16 frames; 0 = attention_kernel, which steps of more than 16 frames always take") \
     X(LSTM_GRAPH, "QA_LSTM_GRAPH", 1, "replay the T step launches of an LSTM call from a cached hipGraph")                       \
     X(LSTM_PERSISTENT, "QA_LSTM_PERSISTENT", -1, "persistent recurrence kernel: -1 auto (d >= 1536), 0 off, 1 on for every supported width") \
     X(LSTM_XCD, "QA_LSTM_XCD", 1, "XCD-local LSTM recurrence for d = 512 / 768 (lstm_team_kernel with one team per XCD: one launch, W_hh in the registers of every XCD's 32 CUs, sequences dealt to the XCDs, 32-member step barrier per XCD): 0 off (the per-step kernels), 1 agent-scope hand-off forms, 2 XCD-local forms (h stores that stay in the XCD's L2; H-Codec 1.0: 42.7 against 43.3 ms)") \

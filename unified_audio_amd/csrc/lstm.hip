@@ -40,10 +40,14 @@ namespace qa {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // MT = number of 16-row batch tiles (B <= 16*MT); NI = 16-wide K steps per wave (d / 128) when known at compile time, 0 = loop
-template <int MT, int NI>
+// CARRY (launch_lstm_carry, the streaming Transformer): the recurrence continues from a carried state - step t = 0 runs the matvec on
+// h_state [B, d] and reads c_state instead of starting from zero.  h_state is only READ here: every workgroup reads all of h_{t-1} but
+// writes 4 units of h_t, so a step must never update the buffer it reads (the launcher moves row T - 1 of h_out into h_state behind
+// the last step).  c_state is read and written by the same lane and stays in place.
+template <int MT, int NI, bool CARRY = false>
 __global__ __launch_bounds__(512) void lstm_step_kernel(const float* __restrict__ xw, const float* __restrict__ w_hh,
                                                         float* __restrict__ h_out, float* __restrict__ c_state, int B,
-                                                        int T, int d, int t) {
+                                                        int T, int d, int t, const float* __restrict__ h_state = nullptr) {
     __shared__ float part[8][MT][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.x * 16;  // first permuted gate row of this workgroup
@@ -60,10 +64,10 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const float* __restrict_
     float c_prev = 0.f;
     if (epi) {
         xg = *reinterpret_cast<const float4*>(xw + ((long long)eb * T + t) * 4 * d + (long long)unit * 4);
-        if (t > 0) c_prev = c_state[(long long)eb * d + unit];
+        if (CARRY || t > 0) c_prev = c_state[(long long)eb * d + unit];
     }
 
-    if (t > 0) {
+    if (CARRY || t > 0) {
         const int kw = d / 8;
         const int k0 = wave * kw;
         const float* wrow = w_hh + (long long)(n0 + li) * d + k0 + 4 * kq;
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const float* __restrict_
         for (int m = 0; m < MT; ++m) {
             int b = m * 16 + li;
             if (b >= B) b = B - 1;  // rows past B are computed on a valid row and discarded
-            hrow[m] = h_out + ((long long)b * T + (t - 1)) * d + k0 + 4 * kq;
+            hrow[m] = (CARRY && t == 0) ? h_state + (long long)b * d + k0 + 4 * kq : h_out + ((long long)b * T + (t - 1)) * d + k0 + 4 * kq;
         }
         if (NI > 0) {  // all of this wave's W_hh and h loads in flight before the first MFMA: one L2 round trip per step
             float4 wv[NI > 0 ? NI : 1], hv[MT][NI > 0 ? NI : 1];
@@ -131,9 +135,10 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const float* __restrict_
     }
 }
 
-template <int MT>
-static void launch_step(int ni, dim3 grid, hipStream_t s, const float* xw, const float* w, float* h, float* c, int bn, int T, int d, int t) {
-#define QA_LS(NI) hipLaunchKernelGGL((lstm_step_kernel<MT, NI>), grid, dim3(512), 0, s, xw, w, h, c, bn, T, d, t)
+template <int MT, bool CARRY = false>
+static void launch_step(int ni, dim3 grid, hipStream_t s, const float* xw, const float* w, float* h, float* c, int bn, int T, int d, int t,
+                        const float* h_state = nullptr) {
+#define QA_LS(NI) hipLaunchKernelGGL((lstm_step_kernel<MT, NI, CARRY>), grid, dim3(512), 0, s, xw, w, h, c, bn, T, d, t, h_state)
     switch (ni) {
         case 1: QA_LS(1); break;
         case 2: QA_LS(2); break;
@@ -146,17 +151,30 @@ static void launch_step(int ni, dim3 grid, hipStream_t s, const float* xw, const
 #undef QA_LS
 }
 
-// One chain of T dependent step launches for batch rows [0, bn) of the given buffers.
-static void lstm_chain(const float* xw_b, const float* w_hh_ug, float* h_b, float* c_b, int bn, int T, int d, int t, hipStream_t s) {
+// One chain of T dependent step launches for batch rows [0, bn) of the given buffers; CARRY: continuing from the carried state
+// (h_state_b, c_b) of those rows
+template <bool CARRY = false>
+static void lstm_chain(const float* xw_b, const float* w_hh_ug, float* h_b, float* c_b, int bn, int T, int d, int t, hipStream_t s,
+                       const float* h_state_b = nullptr) {
     const int ni = (d % 128 == 0) ? d / 128 : 0;
     const int mt = (int)ceil_div(bn, 16);
     const dim3 grid(d / 4);
     switch (mt) {
-        case 1: launch_step<1>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t); break;
-        case 2: launch_step<2>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t); break;
-        case 3: launch_step<3>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t); break;
-        default: launch_step<4>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t); break;
+        case 1: launch_step<1, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
+        case 2: launch_step<2, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
+        case 3: launch_step<3, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
+        default: launch_step<4, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
     }
+}
+
+// h_state [B, d] <- h_out [B, T, d] row T - 1: the carried hidden state moves behind the last step of a chunk, never under a step
+__global__ __launch_bounds__(256) void lstm_state_copy_kernel(const float* __restrict__ h_out, float* __restrict__ h_state, int B, int T, int d) {
+    const int d4 = d >> 2;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * d4) return;
+    const long long b = gid / d4;
+    const int c = (int)(gid - b * d4) * 4;
+    *reinterpret_cast<float4*>(h_state + b * d + c) = *reinterpret_cast<const float4*>(h_out + (b * T + (T - 1)) * d + c);
 }
 
 // The step chains of a call: batches above 64 rows as consecutive chains of 64 (MT <= 4).  (r02: two concurrent half-batch chains on two
@@ -765,6 +783,23 @@ int lstm_call_end(void* ticket, hipStream_t s, bool* failed) {
 
 void lstm_force_per_step(bool on) { t_lstm_per_step = on; }
 
+// The recurrence of one streaming chunk: T eager per-step launches from (h_state, c_state), then the state move.  The in-launch
+// recurrences have no carried form (they need the whole device resident and cannot amortise their register load over a few frames).
+int launch_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d, hipStream_t s) {
+    QA_REQUIRE(d % 128 == 0, "lstm: hidden size %d must be a multiple of 128", d);
+    QA_REQUIRE(B >= 1 && T >= 1, "lstm: a carried chunk of %d rows x %d steps", B, T);
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int bn = std::min(64, B - b0);
+        for (int t = 0; t < T; ++t)
+            lstm_chain<true>(xw + (long long)b0 * T * 4 * d, w_hh_ug, h_out + (long long)b0 * T * d, c_state + (long long)b0 * d, bn, T, d, t, s,
+                             h_state + (long long)b0 * d);
+        QA_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lstm_state_copy_kernel, dim3((unsigned)ceil_div((long long)B * (d / 4), 256)), dim3(256), 0, s, h_out, h_state, B, T, d);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
 }  // namespace qa
 // diagnostics (tests): out[0] in-launch recurrences launched so far on `device`, out[1] calls with one possibly still in flight,
 // out[2] launches diverted to the per-step kernels because another call's recurrence was in flight, out[3] degraded flag
@@ -873,4 +908,12 @@ extern "C" int qa_debug_lstm(const float* xw, const float* w_hh_ug, float* h_out
         return QA_ERR_HIP;
     }
     return QA_OK;
+}
+
+// test hook: one chunk of a carried recurrence (launch_lstm_carry) - h_state / c_state [B, d] are read as the state in front of the
+// chunk and hold the state behind it on return
+extern "C" int qa_debug_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
+                                   void* stream) {
+    QA_REQUIRE(xw && w_hh_ug && h_out && h_state && c_state && B >= 1 && T >= 1 && d >= 1, "qa_debug_lstm_carry: bad argument");
+    return qa::launch_lstm_carry(xw, w_hh_ug, h_out, h_state, c_state, B, T, d, static_cast<hipStream_t>(stream));
 }

@@ -1,0 +1,265 @@
+// stream_attn.hip - the two kernels a streaming step of the codec Transformer adds in front of / in place of attention.hip
+// (DESIGN.md section 42): RoPE fused with the K/V cache append, and a split-key attention for short chunks over a long key history.
+//
+// The cache is LINEAR (row = position, [B, cap, d] fp32 per layer), not mimi's ring: the codec Transformer has no bounded context
+// unless `left_context` is given, and a window is then a mask over the same rows.
+//
+// attn_short_kernel: a stream step has n = 1 .. 16 queries per (row, head) and up to `cap` keys.  attention_kernel gives such a step
+// ONE workgroup per (row, head) with one busy wave that walks every key tile in turn - tens of dependent L2 round trips.  Here the
+// keys of a (row, head) are split over workgroups that own FIXED ranges [s L, (s + 1) L), L = attn_short_split_keys(cap) derived
+// from the cache capacity and never from the key count (lm_attn_kernel's rule, lm_decode.hip): a key sits in the same split, the
+// same 32-key tile and the same lane whatever the offset of the step is, so a step's bits depend on the cache contents and the
+// offset alone, not on how the stream was chunked before.  Each split runs a base-2 online softmax over its tiles in fp32 (plain
+// FMAs: at M <= 16 the step is bound by launch and memory latency, not by arithmetic) and writes one partial record
+// [n][hd | m | l | pad] ; attn_short_merge_kernel combines the records in split order.  A split (or tile) that lies wholly outside
+// the window / causal range is skipped; such a split writes the identity record (m = -inf, l = 0, o = 0), which the merge adds as
+// exact zeros.
+#include "kernels.h"
+
+namespace qa {
+
+// ------------------------------------------------------------------------------------------------ RoPE + append
+// one thread: one (row, head, pair i < hd / 2) - the rotate-half pairs (i, i + hd / 2) of q and k, and the same two elements of v
+__global__ __launch_bounds__(256) void rope_append_kernel(float* __restrict__ qkv, const float* __restrict__ cs, float* __restrict__ kc,
+                                                          float* __restrict__ vc, int B, int n, int H, int hd, int pos0, int cap) {
+    const int half = hd >> 1;
+    const long long total = (long long)B * n * H * half;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int i = (int)(gid % half);
+    const int h = (int)((gid / half) % H);
+    const long long row = gid / ((long long)half * H);
+    const int b = (int)(row / n), pos = pos0 + (int)(row - (long long)b * n);
+    const float c = cs[((long long)pos * half + i) * 2], s = cs[((long long)pos * half + i) * 2 + 1];
+    const int d = H * hd;
+    float* q = qkv + row * 3 * d + h * hd;
+    const float* k = q + d;
+    const float* v = q + 2 * d;
+    const float q1 = q[i], q2 = q[i + half];
+    q[i] = q1 * c - q2 * s;
+    q[i + half] = q2 * c + q1 * s;
+    const float k1 = k[i], k2 = k[i + half];
+    const long long dst = ((long long)b * cap + pos) * d + h * hd;
+    kc[dst + i] = k1 * c - k2 * s;
+    kc[dst + i + half] = k2 * c + k1 * s;
+    vc[dst + i] = v[i];
+    vc[dst + i + half] = v[i + half];
+}
+
+int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s) {
+    QA_REQUIRE(B >= 1 && n >= 1 && H >= 1 && hd >= 2 && hd % 2 == 0 && pos0 >= 0 && (long long)pos0 + n <= cap,
+               "rope_append: rows %d .. %d of a cache of %d rows", pos0, pos0 + n - 1, cap);
+    const long long total = (long long)B * n * H * (hd / 2);
+    hipLaunchKernelGGL(rope_append_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0, cap);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ short-chunk attention
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int AS_Q = ATTN_SHORT_MAX_Q;  // query slots of a workgroup
+constexpr int AS_KT = 32;               // keys per tile
+__host__ __device__ constexpr int as_rec(int hd) { return hd + 4; }  // floats of one query's record: o [hd], m, l, 2 pad (16-byte rows)
+
+// Grid (splits, H, B), 256 threads.  Score phase: wave w owns queries 4 w .. 4 w + 3 - lane (key = lane & 31, half = lane >> 5) holds
+// key `key` of the tile for queries 4 w + half and 4 w + 2 + half; the softmax statistics are reduced over the 32 lanes of a half.
+// PV phase: thread (q = tid >> 4, ct = tid & 15) owns the float4 columns ct and ct + 16 of query q - the same four queries per wave,
+// so a wave without a live query (4 w >= n) skips both phases of every tile.
+template <int HD>
+__global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ kc,
+                                                         const float* __restrict__ vc, float* __restrict__ part, int n, int pos0, int cap,
+                                                         int context, int split_keys, float qscale) {
+    constexpr int LDK = HD + 4;   // K / V rows an odd number of 16-byte slots apart: the ds_read_b128 of 32 keys covers all banks
+    constexpr int C4 = HD / 4;    // float4 columns of a head
+    constexpr int NLD = HD / 32;  // float4 per thread per operand and tile: 32 keys x HD floats over 256 threads
+    constexpr int NC = (C4 + 15) / 16;
+    constexpr int RS = as_rec(HD);
+    __shared__ __attribute__((aligned(16))) float sK[AS_KT][LDK];
+    __shared__ __attribute__((aligned(16))) float sV[AS_KT][LDK];
+    __shared__ __attribute__((aligned(16))) float sQ[AS_Q][HD];
+    __shared__ float sP[AS_Q][AS_KT + 1];
+    __shared__ float sA[AS_Q];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int sp = blockIdx.x, ns = gridDim.x, head = blockIdx.y, H = gridDim.y, b = blockIdx.z;
+    const int d = H * HD;
+    const int n_keys = pos0 + n;
+    // keys some query of the chunk can see, cut to this split's range
+    const int lo = context > 0 ? max(0, pos0 - context + 1) : 0;
+    const int k_begin = max(sp * split_keys, lo), k_end = min((sp + 1) * split_keys, n_keys);
+    float* rec = part + (((long long)(b * H + head) * ns + sp) * n) * RS;
+    if (k_begin >= k_end) {  // workgroup-uniform, before the first barrier: the identity record
+        for (int i = tid; i < n * RS; i += 256) rec[i] = (i % RS == HD) ? -INFINITY : 0.f;
+        return;
+    }
+    const int kt0 = k_begin / AS_KT, kt1 = (k_end - 1) / AS_KT;  // tiles sit on multiples of 32 keys and never straddle a split
+
+    for (int f = tid; f < AS_Q * C4; f += 256) {
+        const int qi = f / C4, c4 = f - qi * C4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (qi < n) v = *reinterpret_cast<const f32x4*>(q + ((long long)b * n + qi) * ldq + head * HD + 4 * c4) * qscale;
+        *reinterpret_cast<f32x4*>(&sQ[qi][4 * c4]) = v;
+    }
+
+    const float* kb = kc + (long long)b * cap * d + head * HD;
+    const float* vb = vc + (long long)b * cap * d + head * HD;
+    // register-staged tiles, every load unconditional: rows past the last key re-read it (it is written and finite; whatever lies behind
+    // it in the cache is not) and are masked below
+    f32x4 kreg[NLD], vreg[NLD];
+    auto fetch = [&](int kt) {
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + 256 * j;
+            const int row = i / C4, c4 = i - row * C4;
+            const long long key = min(kt * AS_KT + row, n_keys - 1);
+            kreg[j] = *reinterpret_cast<const f32x4*>(kb + key * d + 4 * c4);
+            vreg[j] = *reinterpret_cast<const f32x4*>(vb + key * d + 4 * c4);
+        }
+    };
+
+    const bool live = 4 * wave < n;  // wave-uniform
+    const int key_l = lane & 31, hh = lane >> 5;
+    const int qs[2] = {4 * wave + hh, 4 * wave + 2 + hh};
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+    const int pq = tid >> 4, ct = tid & 15;
+    f32x4 o[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) o[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    fetch(kt0);
+    for (int kt = kt0; kt <= kt1; ++kt) {
+        __syncthreads();  // the previous tile (and, the first time, nothing) is no longer read
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + 256 * j;
+            const int row = i / C4, c4 = i - row * C4;
+            *reinterpret_cast<f32x4*>(&sK[row][4 * c4]) = kreg[j];
+            *reinterpret_cast<f32x4*>(&sV[row][4 * c4]) = vreg[j];
+        }
+        __syncthreads();
+        if (kt < kt1) fetch(kt + 1);
+        if (live) {
+            float s[2] = {0.f, 0.f};
+#pragma unroll 4  // (fully unrolled hipcc hoists every LDS read in front of the first FMA: 256 VGPRs, one workgroup per CU)
+            for (int c4 = 0; c4 < C4; ++c4) {
+                const f32x4 kv = *reinterpret_cast<const f32x4*>(&sK[key_l][4 * c4]);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const f32x4 qv = *reinterpret_cast<const f32x4*>(&sQ[qs[e]][4 * c4]);
+                    s[e] += kv.x * qv.x;
+                    s[e] += kv.y * qv.y;
+                    s[e] += kv.z * qv.z;
+                    s[e] += kv.w * qv.w;
+                }
+            }
+            const int key = kt * AS_KT + key_l;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int p = pos0 + qs[e];  // the query's position; key <= p implies key < n_keys
+                const bool ok = qs[e] < n && key <= p && (context <= 0 || p - key < context);
+                const float sc = ok ? s[e] : -INFINITY;
+                float tmax = sc;
+#pragma unroll
+                for (int x = 16; x > 0; x >>= 1) tmax = fmaxf(tmax, __shfl_xor(tmax, x, 64));
+                const float m_new = fmaxf(m_run[e], tmax);
+                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+                const float alpha = __builtin_amdgcn_exp2f(m_run[e] - m_use);  // m_run = -inf -> 0
+                const float pr = __builtin_amdgcn_exp2f(sc - m_use);
+                float psum = pr;
+#pragma unroll
+                for (int x = 16; x > 0; x >>= 1) psum += __shfl_xor(psum, x, 64);
+                l_run[e] = l_run[e] * alpha + psum;
+                m_run[e] = m_new;
+                sP[qs[e]][key_l] = pr;
+                if (key_l == 0) sA[qs[e]] = alpha;
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const float a = sA[pq];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) o[c] *= a;
+#pragma unroll 8
+            for (int key = 0; key < AS_KT; ++key) {
+                const float pr = sP[pq][key];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const int col = ct + 16 * c;
+                    if (col < C4) o[c] += pr * *reinterpret_cast<const f32x4*>(&sV[key][4 * col]);
+                }
+            }
+        }
+    }
+    if (live) {
+        if (pq < n) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int col = ct + 16 * c;
+                if (col < C4) *reinterpret_cast<f32x4*>(rec + (long long)pq * RS + 4 * col) = o[c];
+            }
+        }
+        if (key_l == 0) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                if (qs[e] < n) {
+                    rec[(long long)qs[e] * RS + HD] = m_run[e];
+                    rec[(long long)qs[e] * RS + HD + 1] = l_run[e];
+                }
+        }
+    }
+}
+
+// Grid (H, B), 256 threads: out[b, i, head, :] = sum_s o_s 2^(m_s - M) / sum_s l_s 2^(m_s - M), splits in order
+template <int HD>
+__global__ __launch_bounds__(256) void attn_short_merge_kernel(const float* __restrict__ part, float* __restrict__ out, int n, int ns) {
+    constexpr int RS = as_rec(HD);
+    const int head = blockIdx.x, H = gridDim.x, b = blockIdx.y;
+    const float* rec = part + ((long long)(b * H + head) * ns) * n * RS;
+    for (int e = threadIdx.x; e < n * HD; e += 256) {
+        const int i = e / HD, c = e - i * HD;
+        const float* r = rec + (long long)i * RS;
+        float M = -INFINITY;
+        for (int s = 0; s < ns; ++s) M = fmaxf(M, r[(long long)s * n * RS + HD]);
+        const float m_use = (M == -INFINITY) ? 0.f : M;
+        float L = 0.f, acc = 0.f;
+        for (int s = 0; s < ns; ++s) {
+            const float* rs = r + (long long)s * n * RS;
+            const float w = __builtin_amdgcn_exp2f(rs[HD] - m_use);
+            L += rs[HD + 1] * w;
+            acc += rs[c] * w;
+        }
+        out[((long long)b * n + i) * H * HD + head * HD + c] = L > 0.f ? acc / L : 0.f;
+    }
+}
+
+// 16 splits of a cache, in whole 64-key steps, between 64 and 256 keys each
+int attn_short_split_keys(int cap) { return (int)std::min<int64_t>(256, std::max<int64_t>(64, round_up(ceil_div(cap, 16), 64))); }
+
+size_t attn_short_part_floats(int B, int H, int hd, int n, int cap) {
+    return (size_t)B * H * (size_t)ceil_div(cap, attn_short_split_keys(cap)) * n * as_rec(hd);
+}
+
+int launch_attention_short(const float* q, long long ldq, const float* kc, const float* vc, float* out, float* part, int B, int n, int H,
+                           int hd, int pos0, int cap, int context, hipStream_t s) {
+    QA_REQUIRE(B >= 1 && H >= 1 && n >= 1 && n <= ATTN_SHORT_MAX_Q && pos0 >= 0 && (long long)pos0 + n <= cap && context >= 0 && ldq % 4 == 0,
+               "attention_short: %d queries at offset %d of a cache of %d rows (at most %d queries)", n, pos0, cap, ATTN_SHORT_MAX_Q);
+    const int L = attn_short_split_keys(cap), ns = (int)ceil_div(pos0 + n, L);
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float qscale = LOG2E / std::sqrt((float)hd);
+    const dim3 grid((unsigned)ns, (unsigned)H, (unsigned)B), mgrid((unsigned)H, (unsigned)B);
+#define QA_AS(HD_)                                                                                                                        \
+    hipLaunchKernelGGL(attn_short_kernel<HD_>, grid, dim3(256), 0, s, q, ldq, kc, vc, part, n, pos0, cap, context, L, qscale);           \
+    hipLaunchKernelGGL(attn_short_merge_kernel<HD_>, mgrid, dim3(256), 0, s, part, out, n, ns)
+    switch (hd) {
+        case 64: QA_AS(64); break;
+        case 96: QA_AS(96); break;
+        case 128: QA_AS(128); break;
+        default: set_error("attention_short: head_dim=%d unsupported (64/96/128)", hd); return QA_ERR_UNSUPPORTED;
+    }
+#undef QA_AS
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+}  // namespace qa
