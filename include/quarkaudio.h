@@ -154,6 +154,37 @@ int qa_hcodec_encode_ragged(qa_hcodec* h, const float* wav, int64_t B, int64_t T
 int qa_hcodec_decode_ragged(qa_hcodec* h, const int64_t* acoustic_codes, const int64_t* semantic_codes, int64_t B, int64_t N,
                             const int64_t* frames, float* wav_out, void* stream);
 
+/* The causal H-Codec 1.0 acoustic encoder as a stream: SEANetEncoder -> Transformer -> strided out conv ->
+ * ResidualVQ, chunk by chunk.  The embeddings and acoustic codes of a step equal what ONE qa_hcodec_encode of the concatenated waveform
+ * gives for the same code frames (spec.causal = 1 makes every frame a function of the past alone); the reference has no such call.
+ *   qa_hcodec_stream_begin   allocates the state for B rows and up to max_frames CODE frames (first-chunk minimum .. 4096: the
+ *                            Transformer holds 8192 positions at 2 per code frame): per stateful convolution its last ctx = k_eff -
+ *                            stride input rows, per Transformer layer the LSTM's (h, c) and the roped K / V rows.  The state is an allocation
+ *                            of its own, so offline encode / decode / forward calls on the same handle between two steps change nothing.
+ *                            On a handle that already streams it frees the old stream and starts a new one.
+ *   qa_hcodec_stream_encode  the next n_samples samples of every row, wav [B, n_samples] (device), n_samples a positive multiple of the
+ *                            samples of a code frame (640; a trailing partial frame is the caller's to zero-pad, as pad_wav does), n =
+ *                            n_samples / 640 code frames -> acoustic_codes int64 [B, nq, n] and / or emb fp32 [B, n, code_dim] (either
+ *                            may be NULL, not both; the outputs do not depend on which are asked for).  The FIRST chunk of a stream pads
+ *                            its left edge with the reflection of its own frames, which equals the offline padding only from
+ *                            first_min_frames code frames on (2 for the shipped geometry): a shorter first chunk is refused.
+ *   qa_hcodec_stream_reset   back to offset 0: the next step is a first step again.
+ *   qa_hcodec_stream_end     frees the state; harmless on a handle that does not stream.
+ *   qa_hcodec_stream_offset  code frames streamed since begin / reset, -1 when not streaming.
+ *   qa_hcodec_stream_geometry  host logic, no device: the samples of a code frame, the first-chunk minimum and the contexts of the stateful
+ *                            convolutions in graph order (conv0, per stage the residual k3 and the down conv, the out conv) written to
+ *                            ctx[0 .. *n_ctx) (ctx may be NULL; cap: its capacity).
+ * Refused, before anything is launched and with the state and the offset left as they were: a non-causal handle, H-Codec 1.5 / 2.0
+ * (QA_ERR_UNSUPPORTED), a step without begin, n_samples that is not a positive multiple of the hop, a first chunk below the minimum, a
+ * step beyond max_frames, a stream under capture (the offset is host state). */
+int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames);
+int qa_hcodec_stream_encode(qa_hcodec* h, const float* wav, int64_t n_samples, int64_t* acoustic_codes, float* emb, void* stream);
+int qa_hcodec_stream_reset(qa_hcodec* h);
+int qa_hcodec_stream_end(qa_hcodec* h);
+int64_t qa_hcodec_stream_offset(const qa_hcodec* h);
+int qa_hcodec_stream_geometry(const qa_hcodec_spec* spec, int64_t* samples_per_frame, int64_t* first_min_frames, int32_t* ctx, int32_t cap,
+                              int32_t* n_ctx);
+
 /* H-Codec 1.5 (spec.adaptive != 0): Codec.encode / Codec.decode of QuarkAudio-HCodec/HCodec-1.5/vq/codec_adaptive.py:150-199.
  * The number of groups G is data dependent (the reference syncs the host too: modeling_flexicodec_new.py:910), so
  *   - encode writes int64 [B, nq, G] length-injected codes (code' = (len-1)*codebook_size + code) compactly into buffers of
@@ -348,6 +379,12 @@ int qa_debug_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_
  * starts from h_state / c_state [B, d], and both hold the state behind step T - 1 when the chunk has run. */
 int qa_debug_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
                         void* stream);
+/* The window of one causal convolution in a stream and its next state, alone (tests; stream_conv.hip): win
+ * [B, ctx + n, C] = head | chunk [B, n, C], the head being state_in [B, ctx, C] or, with first != 0 (n > ctx), the reflection of the chunk
+ * (position -1 - j reads frame 1 + j; state_in may then be NULL); state_out [B, ctx, C] = the last ctx rows of the window.  state_in and
+ * state_out must be different buffers: for n < ctx the next state takes rows of the current one. */
+int qa_debug_stream_window(const float* state_in, const float* chunk, float* win, float* state_out, int B, int ctx, int n, int C, int first,
+                           void* stream);
 /* Attention launches the host has issued in this process so far, by arithmetic (tests): out2[0] the fp32 chain (QA_ATT_MATH = 0, and
  * every launch of a UniSE LM handle), out2[1] split-6.  Counted where the host launches: a launch recorded into a captured graph counts
  * once, at capture, and its replays do not count. */

@@ -132,6 +132,15 @@ SYMBOLS = {
                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qa_hcodec_decode_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
                                           C.c_void_p]),
+    "qa_hcodec_stream_begin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "qa_hcodec_stream_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_hcodec_stream_reset": (C.c_int, [C.c_void_p]),
+    "qa_hcodec_stream_end": (C.c_int, [C.c_void_p]),
+    "qa_hcodec_stream_offset": (C.c_int64, [C.c_void_p]),
+    "qa_hcodec_stream_geometry": (C.c_int, [C.POINTER(qa_hcodec_spec), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                            C.c_int32, C.POINTER(C.c_int32)]),
+    "qa_debug_stream_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p]),
     "qa_hcodec_encode_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                             C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_float,
                                             C.c_void_p]),

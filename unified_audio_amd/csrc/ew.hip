@@ -10,10 +10,11 @@ namespace qa {
 // conv_in: SConv1d with C_in = 1 (reference: encoder.model.0, encoder_modules/conv.py:195-211; seanet.py:121-124)
 // y[b, t, co] = bias[co] + sum_j w[co, j] * x[b, reflect(t - pad_left + j)]
 // one thread = one output frame x 4 channels -> float4 stores, consecutive threads write consecutive 16 B.
+// Tx: the frames of x per item (= T, or T + ksize - 1 in the window form, whose taps all land inside the window: pad_left = 0, Lp = Tx).
 __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, float* __restrict__ y, int B,
                                                       int T, int Cout, int ksize, int pad_left, int Lp,
-                                                      const int* __restrict__ lens, int len_mul, int max_pad) {
+                                                      const int* __restrict__ lens, int len_mul, int max_pad, int Tx) {
     const int c4n = Cout >> 2;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = (long long)B * T * c4n;
@@ -21,8 +22,8 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
     const int c4 = (int)(gid % c4n);
     const long long m = gid / c4n;
     const int b = (int)(m / T), t = (int)(m - (long long)b * T);
-    const float* xb = x + (long long)b * T;
-    int len = T;
+    const float* xb = x + (long long)b * Tx;
+    int len = Tx;
     if (lens) {  // launch-uniform: a ragged call reflects at the clip's own end (short-input rule included)
         len = min(lens[b] * len_mul, T);
         Lp = len <= max_pad ? max_pad + 1 : len;
@@ -50,7 +51,19 @@ int launch_conv_in(const float* x, const float* w_kc, const float* bias, float* 
     const long long total = (long long)B * T * (Cout / 4);
     HbmProf prof_(HK_CONV_IN, 4.0 * ((double)B * T + (double)B * T * Cout), s);
     hipLaunchKernelGGL(conv_in_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, w_kc, bias, y, B, T,
-                       Cout, ksize, left, Lp, rl.n, rl.mul, max_pad);
+                       Cout, ksize, left, Lp, rl.n, rl.mul, max_pad, T);
+    QA_LAUNCH_CHECK();
+    return QA_OK;
+}
+
+int launch_conv_in_window(const float* x, const float* w_kc, const float* bias, float* y, int B, int T_in, int Cout, int ksize, hipStream_t s) {
+    QA_REQUIRE(Cout % 4 == 0 && ksize >= 1 && T_in >= ksize, "conv_in (window): Cout=%d must be a multiple of 4, the window of %d frames "
+               "at least ksize = %d", Cout, T_in, ksize);
+    const int T = T_in - ksize + 1;  // tap j of output t reads window frame t + j <= T_in - 1: resolve_frame returns it as it is
+    const long long total = (long long)B * T * (Cout / 4);
+    HbmProf prof_(HK_CONV_IN, 4.0 * ((double)B * T_in + (double)B * T * Cout), s);
+    hipLaunchKernelGGL(conv_in_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, x, w_kc, bias, y, B, T, Cout, ksize, 0, T_in,
+                       static_cast<const int*>(nullptr), 0, 0, T_in);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }

@@ -62,6 +62,85 @@ struct MimiStream {
 
 constexpr int MAX_POS = 8192;
 
+// the per-layer views of `mem`: `lead` floats per layer in front of the two [B, cap, d] caches (the streaming state's h and c)
+void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, std::vector<float*>* kc, std::vector<float*>* vc) {
+    kc->resize(layers);
+    vc->resize(layers);
+    for (size_t l = 0; l < layers; ++l) {
+        (*kc)[l] = mem + l * (lead + 2 * per) + lead;
+        (*vc)[l] = (*kc)[l] + per;
+    }
+}
+
+// The streaming state of one codec Transformer: per layer the LSTM's (h, c) [B, d] and the roped K / V rows
+// [B, cap, d], one allocation of the handle's own (not arena memory).  B > 0: streaming.  qa_transformer and the streaming H-Codec encoder
+// (section 43) both carry one.
+struct TrStream {
+    int B = 0, cap = 0;
+    bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
+    float* mem = nullptr;
+    std::vector<float*> kc, vc, hs, cs;
+    TrStream() = default;
+    TrStream(const TrStream&) = delete;
+    TrStream& operator=(const TrStream&) = delete;
+    ~TrStream() {
+        if (mem) (void)hipFree(mem);
+    }
+    void release() {  // waits for the steps that still read the state (the caller has set the device)
+        if (mem) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(mem);
+        }
+        mem = nullptr;
+        B = cap = 0;
+    }
+    // a fresh state for B sequences of up to `capacity` frames; never cleared: no kernel reads a K / V row at or behind the key count of
+    // its step, and (h, c) are zeroed by the first step
+    int begin(const TransformerW& w, int64_t batch, int64_t capacity) {
+        release();
+        const size_t L = w.layers.size(), st = (size_t)batch * w.d, per = (size_t)batch * capacity * w.d;
+        QA_HIP(hipMalloc(reinterpret_cast<void**>(&mem), sizeof(float) * L * (2 * st + 2 * per)));
+        transformer_kv_views(mem, L, 2 * st, per, &kc, &vc);
+        hs.resize(L);
+        cs.resize(L);
+        for (size_t l = 0; l < L; ++l) {
+            hs[l] = kc[l] - 2 * st;
+            cs[l] = kc[l] - st;
+        }
+        B = (int)batch;
+        cap = (int)capacity;
+        zero_state = true;
+        return QA_OK;
+    }
+    // begin / reset: (h, c) = 0 of every layer, in stream order like the step itself
+    int zero_if_new(int d, hipStream_t s) {
+        if (!zero_state) return QA_OK;
+        for (size_t l = 0; l < hs.size(); ++l) QA_HIP(hipMemsetAsync(hs[l], 0, sizeof(float) * 2 * (size_t)B * d, s));
+        zero_state = false;
+        return QA_OK;
+    }
+};
+
+// One stateful convolution of the streaming SEANet encoder: its carried context, the last `ctx` rows [B, ctx, C]
+// of its own input buffer.  Two buffers, alternated by the host: a step reads st[cur] and writes st[cur ^ 1] (stream_conv.hip)
+struct StreamConv {
+    int ctx = 0, C = 0;
+    float* st[2] = {nullptr, nullptr};
+};
+// The streaming state of a causal H-Codec 1.0 encoder: B > 0 between qa_hcodec_stream_begin and _end
+struct CodecStream {
+    int B = 0, cap = 0, offset = 0;  // capacity and offset in CODE frames
+    bool first = true;               // the next step is a first step: reflect fill, LSTM state zeroed
+    int cur = 0;                     // which of the two state buffers of every convolution holds the current state
+    int first_min = 0;               // the fewest code frames a first chunk may have (stream_geometry)
+    float* conv_mem = nullptr;
+    std::vector<StreamConv> convs;   // conv0, then (k3, down) per stage, then the out conv
+    TrStream tr;
+    ~CodecStream() {
+        if (conv_mem) (void)hipFree(conv_mem);
+    }
+};
+
 }  // namespace
 
 }  // namespace qa
@@ -136,6 +215,8 @@ struct qa_hcodec : Handle {
     // ragged calls (qa_hcodec_encode_ragged / _decode_ragged and their _adaptive_ twins): the clips' code-frame counts, written on the call's
     // stream
     DeviceInts lens;
+    // the chunked encoder of a causal H-Codec 1.0 handle (qa_hcodec_stream_*); null: not streaming
+    std::unique_ptr<CodecStream> strm;
     ~qa_hcodec() {
         if (e2_dev) (void)hipFree(e2_dev);
         if (host_sync) (void)hipHostFree(host_sync);
@@ -162,15 +243,9 @@ struct qa_mimi : Handle {
 struct qa_transformer : Handle {
     qa_transformer_spec spec{};
     TransformerW w;
-    // streaming state (stream_B > 0: between qa_transformer_stream_begin and _end): per layer the LSTM's (h, c) [B, d] and the roped
-    // K / V rows [B, cap, d], one allocation; `offset` frames seen since begin / reset
-    int stream_B = 0, stream_cap = 0, offset = 0;
-    bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
-    float* stream_mem = nullptr;
-    std::vector<float*> kc, vc, hs, cs;
-    ~qa_transformer() {
-        if (stream_mem) (void)hipFree(stream_mem);
-    }
+    // streaming state (st.B > 0: between qa_transformer_stream_begin and _end); `offset` frames seen since begin / reset
+    TrStream st;
+    int offset = 0;
 };
 // past_key_values of Transformer.forward(x, past_key_values, use_cache=True): per layer the roped K and V rows [B, cap, d] in fp32
 struct qa_transformer_cache {
@@ -444,6 +519,16 @@ int transformer_chunk_op(Ctx& c, const TransformerW& tw, float* x, int B, int N,
     }
     c.arena.release(mark);
     return QA_OK;
+}
+
+// the step of a streaming state at `pos0` frames: causal, the K / V rows and the carried LSTM state of `st`
+TrChunk stream_chunk(const TrStream& st, int pos0, int left_context) {
+    TrChunk ch;
+    ch.kc = st.kc.data(); ch.vc = st.vc.data();
+    ch.cap = st.cap; ch.pos0 = pos0;
+    ch.causal = 1; ch.context = left_context;
+    ch.hs = st.hs.data(); ch.cs = st.cs.data();
+    return ch;
 }
 
 // StreamingTransformer.forward, non-causal / non-streaming (mimi/transformer.py:377-425,553-594,674-698), in place on x
@@ -725,6 +810,130 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
     *emb_out = emb;
     *n50_out = t.T;
     *n25_out = g.T_out;
+    return QA_OK;
+}
+
+// ---- the causal encoder as a stream
+
+// Which models stream, and why the others do not; `fn` names the entry point.
+int stream_refuse(const qa_hcodec_spec& sp, const char* fn) {
+    const char* why = sp.version == 20 ? "an H-Codec 2.0 model: its encoder has an STFT front and a d = 1536 recurrence with no carried form"
+                      : (sp.adaptive || sp.version == 15) ? "an H-Codec 1.5 model: its codes come from a whole-utterance alignment"
+                                                          : nullptr;
+    if (why) {
+        set_error("%s: the chunked encoder exists for the causal H-Codec 1.0 only; this is %s - encode the whole utterance with "
+                  "qa_hcodec_encode%s", fn, why, sp.adaptive ? "_adaptive" : "");
+        return QA_ERR_UNSUPPORTED;
+    }
+    if (!sp.causal) {
+        set_error("%s: streaming needs a causal model (spec.causal = 1): a non-causal frame depends on samples that have not arrived yet - "
+                  "encode the whole utterance with qa_hcodec_encode", fn);
+        return QA_ERR_UNSUPPORTED;
+    }
+    QA_REQUIRE(sp.n_ratios >= 1 && sp.n_ratios <= 8, "%s: spec.n_ratios = %d outside 1 .. 8", fn, sp.n_ratios);
+    for (int i = 0; i < sp.n_ratios; ++i) QA_REQUIRE(sp.ratios[i] >= 1 && sp.ratios[i] <= 64, "%s: spec.ratios[%d] = %d", fn, i, sp.ratios[i]);
+    return QA_OK;
+}
+
+// The stateful convolutions of the causal SEANet encoder in graph order - conv0 (k7), per stage the residual k3 and the down conv
+// (k = 2 r, stride r), the out conv (k4, stride 2) - each with ctx = k_eff - stride, the rows of left context a causal SConv1d pads
+// (conv.py:203-206).  A waveform of a whole number of code frames needs no right padding anywhere (extra = 0: a stride-1 conv keeps L, a
+// k = 2 r / s = r conv has L / r frames with r | L), so a chunk needs nothing from the future.  The first chunk's left padding is the
+// reflection of its own first ctx frames, which is what the offline pad1d does only while the input of that layer is LONGER than ctx
+// (conv.py:79-96: otherwise the short-input rule, another function): first_min is the fewest code frames for which that holds everywhere.
+struct StreamGeom {
+    int samples = 0, first_min = 1;
+    std::vector<int> ctx, rate;  // per stateful conv: context rows, input rows per code frame
+};
+StreamGeom stream_geometry(const qa_hcodec_spec& sp) {
+    StreamGeom g;
+    std::vector<int> enc(sp.n_ratios + 1, 2);  // qa_hcodec::Geom::enc: frames per code frame at the input of stage i
+    for (int i = sp.n_ratios - 1; i >= 0; --i) enc[i] = enc[i + 1] * sp.ratios[i];
+    g.samples = enc[0];
+    auto add = [&](int k, int stride, int rate) {
+        g.ctx.push_back(k - stride);
+        g.rate.push_back(rate);
+    };
+    add(7, 1, enc[0]);
+    for (int i = 0; i < sp.n_ratios; ++i) {
+        add(3, 1, enc[i]);
+        add(2 * sp.ratios[i], sp.ratios[i], enc[i]);
+    }
+    add(4, 2, 2);
+    for (size_t i = 0; i < g.ctx.size(); ++i) g.first_min = std::max(g.first_min, g.ctx[i] / g.rate[i] + 1);  // n rate > ctx
+    return g;
+}
+
+// SEANet encoder, one step of a stream: the next n code frames wav [B, n * samples] -> emb [B, n, code_dim].  Mirrors seanet_encoder layer
+// for layer.  Every convolution with a temporal footprint runs as a VALID convolution (pads 0 / 0) over a window [B, ctx + n_in, C] that
+// launch_stream_window assembles from the carried state (first step: the reflection of the chunk) and the chunk; conv_op has no batch stride
+// for x, so the window is a buffer of its own.  The state of a conv is the raw rows of its own input buffer, before any prologue ELU; for
+// the down convs those rows hold the fused post-ELU values, as in seanet_encoder.  Stage 0 takes the unfused launches, as ragged calls do:
+// the fused front stages whole halo tiles with a reflect rule of its own (a carried-halo form of it is not built).  The 1x1 shortcut and the
+// 1x1 behind the k3 are row-wise and carry nothing.  The Transformer continues over its carried (h, c) and K / V rows at 2 frames per code
+// frame.  Reads st.cur / st.first / st.offset, which the caller advances behind a successful step.
+int seanet_encoder_step(qa_hcodec* h, Ctx& c, const float* wav, int n, float* emb) {
+    const qa_hcodec_spec& sp = h->spec;
+    CodecStream& st = *h->strm;
+    const int B = st.B, first = st.first ? 1 : 0;
+    size_t ci = 0;
+    // the window of the next stateful conv over chunk [B, L, C]: [B, ctx + L, C]; *T_in = ctx + L
+    auto window = [&](const float* chunk, int L, int C, float** win, int* T_in) -> int {
+        QA_REQUIRE(ci < st.convs.size() && st.convs[ci].C == C, "stream: convolution %zu of the ladder has no state of %d channels", ci, C);
+        const StreamConv& sc = st.convs[ci++];
+        *T_in = sc.ctx + L;
+        *win = c.arena.alloc<float>((size_t)B * *T_in * C);
+        QA_RUN(c, launch_stream_window(sc.st[st.cur], chunk, *win, sc.st[st.cur ^ 1], B, sc.ctx, L, C, first, c.stream));
+        return QA_OK;
+    };
+    int C = sp.n_filters, L = n * h->geom.samples, Tw = 0;
+    float* win = nullptr;
+    QA_TRY(window(wav, L, 1, &win, &Tw));
+    float* x = c.arena.alloc<float>((size_t)B * L * C);
+    QA_RUN(c, launch_conv_in_window(win, h->conv0_w, h->conv0_b, x, B, Tw, C, 7, c.stream));
+    for (int i = 0; i < sp.n_ratios; ++i) {
+        const int r = sp.ratios[i];
+        const ResBlockW& rb = h->res[i];
+        float* sc = c.arena.alloc<float>((size_t)B * L * C);
+        float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
+        QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));  // shortcut_1x1(x)
+        QA_TRY(window(x, L, C, &win, &Tw));
+        ConvOpt k3 = conv_geom(1, 0, 0);  // ELU(k3(ELU(.))) over the window
+        k3.prologue = ACT_ELU;
+        k3.act = ACT_ELU;
+        QA_TRY(conv_op(c, win, C, B, Tw, rb.k3, hh, rb.k3.N, L, k3));
+        ConvOpt pw;  // ELU(shortcut + 1x1(.)): the activation in front of the down conv, fused as in seanet_encoder
+        pw.res = sc;
+        pw.ldr = C;
+        pw.post_act = ACT_ELU;
+        QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, pw));
+        QA_TRY(window(sc, L, C, &win, &Tw));
+        float* y = c.arena.alloc<float>((size_t)B * (L / r) * 2 * C);
+        QA_TRY(conv_op(c, win, C, B, Tw, h->down[i], y, 2 * C, L / r, conv_geom(r, 0, 0)));
+        x = y;
+        L /= r;
+        C *= 2;
+    }
+    QA_REQUIRE(C == sp.dimension && L == 2 * n, "stream: the ladder ends at %d channels, %d frames (dimension %d, %d frames)", C, L,
+               sp.dimension, 2 * n);
+    QA_TRY(transformer_chunk_op(c, h->enc_tr, x, B, L, stream_chunk(st.tr, 2 * st.offset, 0)));
+    QA_TRY(window(x, L, C, &win, &Tw));
+    ConvOpt eo = conv_geom(2, 0, 0);
+    eo.prologue = ACT_ELU;
+    return conv_op(c, win, C, B, Tw, h->enc_out, emb, sp.code_dim, n, eo);
+}
+
+// one step of Codec.encode's acoustic half: SEANet step -> emb [B, n, code_dim] -> ResidualVQ -> codes [B, nq, n]; either output may be null
+int stream_encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int n, long long* ac_out, float* emb_out) {
+    const qa_hcodec_spec& sp = h->spec;
+    const int B = h->strm->B, Q = sp.num_quantizers;
+    float* emb = emb_out ? emb_out : c.arena.alloc<float>((size_t)B * n * sp.code_dim);
+    QA_TRY(seanet_encoder_step(h, c, wav, n, emb));
+    if (!ac_out) return QA_OK;
+    long long* ia = c.arena.alloc<long long>((size_t)B * n * Q);
+    float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * n, sp.codebook_size, sp.code_dim));
+    QA_RUN(c, launch_rvq_search(emb, (long long)B * n, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0, rvq_ws, c.stream));
+    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, n, Q, c.stream));
     return QA_OK;
 }
 
@@ -1512,6 +1721,115 @@ int qa_hcodec_decode_ragged(qa_hcodec* h, const int64_t* ac, const int64_t* sc, 
     return decode_call(h, "qa_hcodec_decode_ragged", ac, sc, B, N, frames, wav_out, stream);
 }
 
+/* ---- the causal H-Codec 1.0 acoustic encoder as a stream ---------------------------------------------- */
+
+int qa_hcodec_stream_geometry(const qa_hcodec_spec* spec, int64_t* samples_per_frame, int64_t* first_min_frames, int32_t* ctx, int32_t cap,
+                              int32_t* n_ctx) {
+    QA_REQUIRE(spec, "qa_hcodec_stream_geometry: null spec");
+    QA_TRY(stream_refuse(*spec, "qa_hcodec_stream_geometry"));
+    const StreamGeom g = stream_geometry(*spec);
+    if (samples_per_frame) *samples_per_frame = g.samples;
+    if (first_min_frames) *first_min_frames = g.first_min;
+    if (n_ctx) *n_ctx = (int32_t)g.ctx.size();
+    if (ctx) {
+        QA_REQUIRE(cap >= (int32_t)g.ctx.size(), "qa_hcodec_stream_geometry: ctx holds %d entries, the encoder has %zu stateful convolutions",
+                   cap, g.ctx.size());
+        for (size_t i = 0; i < g.ctx.size(); ++i) ctx[i] = g.ctx[i];
+    }
+    return QA_OK;
+}
+
+static void hcodec_stream_free(qa_hcodec* h) {
+    if (!h->strm) return;
+    (void)hipDeviceSynchronize();  // the steps that still read the state
+    h->strm.reset();
+}
+
+int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
+    QA_REQUIRE(h, "qa_hcodec_stream_begin: null handle");
+    QA_TRY(stream_refuse(h->spec, "qa_hcodec_stream_begin"));
+    const StreamGeom g = stream_geometry(h->spec);
+    QA_REQUIRE(B > 0 && B < (1 << 20) && max_frames >= g.first_min && max_frames <= MAX_POS / 2,
+               "qa_hcodec_stream_begin: batch %lld, max_frames %lld (code frames, %d .. %d: the Transformer holds %d positions at 2 per code "
+               "frame, and the first chunk alone needs %d)", (long long)B, (long long)max_frames, g.first_min, MAX_POS / 2, MAX_POS, g.first_min);
+    QA_HIP(hipSetDevice(h->device));
+    hcodec_stream_free(h);
+    std::unique_ptr<CodecStream> st(new CodecStream());
+    // the convolutions' states: two buffers [B, ctx, C] each, 64-float aligned, one allocation
+    st->convs.resize(g.ctx.size());
+    size_t total = 0;
+    int C = h->spec.n_filters;
+    for (size_t i = 0; i < g.ctx.size(); ++i) {
+        StreamConv& sc = st->convs[i];
+        sc.ctx = g.ctx[i];
+        sc.C = i == 0 ? 1 : C;
+        if (i >= 2 && i % 2 == 0) C *= 2;  // behind a down conv (convs 2, 4, ...) the ladder doubles
+        if (i + 1 == g.ctx.size()) sc.C = h->spec.dimension;
+        total += 2 * (size_t)round_up((int64_t)B * sc.ctx * sc.C, 64);
+    }
+    QA_HIP(hipMalloc(reinterpret_cast<void**>(&st->conv_mem), sizeof(float) * total));
+    float* p = st->conv_mem;
+    for (StreamConv& sc : st->convs)
+        for (int k = 0; k < 2; ++k) {
+            sc.st[k] = p;
+            p += round_up((int64_t)B * sc.ctx * sc.C, 64);
+        }
+    QA_TRY(st->tr.begin(h->enc_tr, B, 2 * max_frames));
+    st->B = (int)B;
+    st->cap = (int)max_frames;
+    st->first_min = g.first_min;
+    h->strm = std::move(st);
+    return QA_OK;
+}
+
+int qa_hcodec_stream_encode(qa_hcodec* h, const float* wav, int64_t n_samples, int64_t* acoustic_codes, float* emb, void* stream) {
+    QA_REQUIRE(h, "qa_hcodec_stream_encode: null handle");
+    QA_REQUIRE(h->strm, "qa_hcodec_stream_encode: not streaming (call qa_hcodec_stream_begin first)");
+    QA_REQUIRE(wav && (acoustic_codes || emb), "qa_hcodec_stream_encode: null wav, or neither acoustic_codes nor emb asked for");
+    CodecStream& st = *h->strm;
+    const int hop = h->geom.samples;
+    // every refusal comes before any launch and leaves the state and the offset as they were
+    QA_REQUIRE(n_samples > 0 && n_samples % hop == 0, "qa_hcodec_stream_encode: a step of %lld samples; it must be a positive multiple of the "
+               "%d samples of a code frame (zero-pad a trailing partial frame, as HCodecTokenizer.pad_wav does)", (long long)n_samples, hop);
+    const int64_t n = n_samples / hop;
+    QA_REQUIRE(st.B * n_samples < (1LL << 31), "qa_hcodec_stream_encode: a step of %d x %lld samples is too large", st.B, (long long)n_samples);
+    QA_REQUIRE(!st.first || n >= st.first_min, "qa_hcodec_stream_encode: the first chunk of a stream has %lld code frames, it needs at least %d "
+               "(%d samples): its left padding is the reflection of its own frames, which a shorter chunk cannot fill the way the offline "
+               "encoder does - buffer %d frames before the first step", (long long)n, st.first_min, st.first_min * hop, st.first_min);
+    QA_REQUIRE((int64_t)st.offset + n <= st.cap, "qa_hcodec_stream_encode: %d streamed + %lld new code frames exceed the capacity %d of this "
+               "stream (max_frames of qa_hcodec_stream_begin, at most %d); begin a longer stream or reset this one", st.offset, (long long)n,
+               st.cap, MAX_POS / 2);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    QA_TRY(refuse_capture("qa_hcodec_stream_encode", s, CACHE_IS_HOST_STATE));
+    QA_HIP(hipSetDevice(h->device));
+    if (st.first) st.tr.zero_state = true;
+    QA_TRY(st.tr.zero_if_new(h->enc_tr.d, s));
+    Ctx& c = h->ctx;
+    QA_TRY(run_planned(*h, stream, [&] { return stream_encode_graph(h, c, wav, (int)n, (long long*)acoustic_codes, emb); }));
+    st.offset += (int)n;
+    st.first = false;
+    st.cur ^= 1;
+    return QA_OK;
+}
+
+int qa_hcodec_stream_reset(qa_hcodec* h) {
+    QA_REQUIRE(h && h->strm, "qa_hcodec_stream_reset: not streaming (call qa_hcodec_stream_begin first)");
+    // the next step is a first step again: reflect fill instead of the convolutions' states, (h, c) zeroed in stream order, and the K / V
+    // rows stay and become invisible (no step reads a row at or behind its own key count)
+    h->strm->offset = 0;
+    h->strm->first = true;
+    return QA_OK;
+}
+
+int qa_hcodec_stream_end(qa_hcodec* h) {
+    if (!h || !h->strm) return QA_OK;  // nothing to end: harmless, like free(NULL)
+    (void)hipSetDevice(h->device);
+    hcodec_stream_free(h);
+    return QA_OK;
+}
+
+int64_t qa_hcodec_stream_offset(const qa_hcodec* h) { return (h && h->strm) ? h->strm->offset : -1; }
+
 // The per-clip H-Codec 1.5 calls serve the non-causal model only: a causal aggregator or bottleneck attends by position, and their
 // attention takes no key-padding mask.
 static int adaptive_ragged_refuse(qa_hcodec* h, const char* fn) {
@@ -1862,7 +2180,7 @@ static int transformer_check_io(const char* fn, const qa_transformer* h, const f
 
 int qa_transformer_forward(qa_transformer* h, const float* x, int64_t B, int64_t T, float* y, void* stream) {
     QA_TRY(transformer_check_io("qa_transformer_forward", h, x, y, B, T));
-    QA_REQUIRE(h->stream_B == 0, "qa_transformer_forward: the handle is in streaming mode, use qa_transformer_stream_step");
+    QA_REQUIRE(h->st.B == 0, "qa_transformer_forward: the handle is in streaming mode, use qa_transformer_stream_step");
     Ctx& c = h->ctx;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     auto graph = [&]() -> int {
@@ -1871,16 +2189,6 @@ int qa_transformer_forward(qa_transformer* h, const float* x, int64_t B, int64_t
     };
     QA_TRY(plan(h->device, s, c, h->ws, graph));
     return run_graph_checked(h, graph);
-}
-
-// the per-layer views of `mem`: `lead` floats per layer in front of the two [B, cap, d] caches (the streaming state's h and c)
-static void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, std::vector<float*>* kc, std::vector<float*>* vc) {
-    kc->resize(layers);
-    vc->resize(layers);
-    for (size_t l = 0; l < layers; ++l) {
-        (*kc)[l] = mem + l * (lead + 2 * per) + lead;
-        (*vc)[l] = (*kc)[l] + per;
-    }
 }
 
 int qa_transformer_cache_create(qa_transformer* h, int64_t B, int64_t capacity, qa_transformer_cache** out) {
@@ -1948,12 +2256,8 @@ int qa_transformer_forward_cached(qa_transformer* h, qa_transformer_cache* cache
 }
 
 static void transformer_stream_free(qa_transformer* h) {
-    if (h->stream_mem) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(h->stream_mem);
-    }
-    h->stream_mem = nullptr;
-    h->stream_B = h->stream_cap = h->offset = 0;
+    h->st.release();
+    h->offset = 0;
 }
 
 int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) {
@@ -1964,43 +2268,22 @@ int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) 
                (long long)B, (long long)capacity, MAX_POS);
     QA_HIP(hipSetDevice(h->device));
     transformer_stream_free(h);
-    const size_t L = h->w.layers.size(), st = (size_t)B * h->w.d, per = (size_t)B * capacity * h->w.d;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->stream_mem), sizeof(float) * L * (2 * st + 2 * per)));
-    transformer_kv_views(h->stream_mem, L, 2 * st, per, &h->kc, &h->vc);
-    h->hs.resize(L);
-    h->cs.resize(L);
-    for (size_t l = 0; l < L; ++l) {
-        h->hs[l] = h->kc[l] - 2 * st;
-        h->cs[l] = h->kc[l] - st;
-    }
-    h->stream_B = (int)B;
-    h->stream_cap = (int)capacity;
-    h->offset = 0;
-    h->zero_state = true;
-    return QA_OK;
+    return h->st.begin(h->w, B, capacity);
 }
 
 int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, float* y, void* stream) {
-    QA_REQUIRE(h && h->stream_B > 0, "qa_transformer_stream_step: not streaming (call qa_transformer_stream_begin)");
-    QA_TRY(transformer_check_io("qa_transformer_stream_step", h, x, y, h->stream_B, n));
+    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_step: not streaming (call qa_transformer_stream_begin)");
+    QA_TRY(transformer_check_io("qa_transformer_stream_step", h, x, y, h->st.B, n));
     // refused before any launch: the state stays as it was
-    QA_REQUIRE((int64_t)h->offset + n <= h->stream_cap, "qa_transformer_stream_step: %d streamed + %lld new frames exceed the capacity %d of "
-               "this stream (max_frames)", h->offset, (long long)n, h->stream_cap);
+    QA_REQUIRE((int64_t)h->offset + n <= h->st.cap, "qa_transformer_stream_step: %d streamed + %lld new frames exceed the capacity %d of "
+               "this stream (max_frames)", h->offset, (long long)n, h->st.cap);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     QA_TRY(refuse_capture("qa_transformer_stream_step", s, CACHE_IS_HOST_STATE));
     QA_HIP(hipSetDevice(h->device));
-    const int B = h->stream_B;
-    if (h->zero_state) {  // begin / reset: (h, c) = 0 of every layer, in stream order like the step itself
-        const size_t st = (size_t)B * h->w.d;
-        for (size_t l = 0; l < h->hs.size(); ++l) QA_HIP(hipMemsetAsync(h->hs[l], 0, sizeof(float) * 2 * st, s));
-        h->zero_state = false;
-    }
+    const int B = h->st.B;
+    QA_TRY(h->st.zero_if_new(h->w.d, s));
     Ctx& c = h->ctx;
-    TrChunk ch;
-    ch.kc = h->kc.data(); ch.vc = h->vc.data();
-    ch.cap = h->stream_cap; ch.pos0 = h->offset;
-    ch.causal = 1; ch.context = h->spec.left_context;
-    ch.hs = h->hs.data(); ch.cs = h->cs.data();
+    const TrChunk ch = stream_chunk(h->st, h->offset, h->spec.left_context);
     auto graph = [&]() -> int {
         if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, s));
         return transformer_chunk_op(c, h->w, y, B, (int)n, ch);
@@ -2011,9 +2294,9 @@ int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, flo
 }
 
 int qa_transformer_stream_reset(qa_transformer* h) {
-    QA_REQUIRE(h && h->stream_B > 0, "qa_transformer_stream_reset: not streaming");
+    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_reset: not streaming");
     h->offset = 0;  // the cached rows stay and become invisible: no step reads a row at or behind offset + n
-    h->zero_state = true;
+    h->st.zero_state = true;
     return QA_OK;
 }
 
@@ -2024,6 +2307,6 @@ int qa_transformer_stream_end(qa_transformer* h) {
     return QA_OK;
 }
 
-int64_t qa_transformer_stream_offset(const qa_transformer* h) { return (h && h->stream_B > 0) ? h->offset : -1; }
+int64_t qa_transformer_stream_offset(const qa_transformer* h) { return (h && h->st.B > 0) ? h->offset : -1; }
 
 }  // extern "C"

@@ -24,6 +24,14 @@ struct ClipLens {
 // pad_left < 0: the non-causal split of SConv1d (left = pad_total - pad_total / 2); causal SConv1d passes ksize - 1
 int launch_conv_in(const float* x, const float* w_kc, const float* bias, float* y, int B, int T, int Cout, int ksize,
                    hipStream_t s, int pad_left = -1, ClipLens rl = ClipLens());
+// the same filter as a VALID convolution over a window x [B, T_in] that already holds its left context: no padding, y [B, T_out, Cout]
+// with T_out = T_in - ksize + 1 (the streaming encoder's conv0)
+int launch_conv_in_window(const float* x, const float* w_kc, const float* bias, float* y, int B, int T_in, int Cout, int ksize, hipStream_t s);
+// stream_conv.hip: the window of a causal convolution in a stream and its next state, one launch.  win [B, ctx + n, C] = head | chunk
+// [B, n, C], the head being state_in [B, ctx, C] or, on the first step (n > ctx), the reflection of the chunk (position -1 - j reads frame
+// 1 + j); state_out [B, ctx, C] = the window's last ctx rows.  state_in and state_out are different buffers (n < ctx: they overlap in time)
+int launch_stream_window(const float* state_in, const float* chunk, float* win, float* state_out, int B, int ctx, int n, int C, int first,
+                         hipStream_t s);
 // seanet_front.hip: conv0 + SEANetResnetBlock + the ELU in front of the strided conv, one launch, `a` written once
 bool seanet_front_supported(int C, int hid, int L);
 int launch_seanet_front(const float* wav, const float* w0, const float* b0, const float* w3, const float* b3, const float* wsc,

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional, Tuple
 
@@ -184,6 +185,9 @@ def _frames_arg(lengths, B: int, what: str = "lengths"):
     return (C.c_int64 * B)(*vals)
 
 
+MAX_STREAM_FRAMES = 4096  # code frames a stream can hold: the encoder Transformer's 8192 positions at two per code frame
+
+
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -268,6 +272,7 @@ class Codec(torch.nn.Module):
         self._lib = _lib.load_library()
         self._state = None
         self._semantic_decoder_error = None  # why forward cannot run (no / incomplete semantic_decoder.* weights)
+        self._streaming_batch = 0  # > 0: inside streaming() (encode_stream)
 
     # -- weights -------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True, assign: bool = False):
@@ -391,8 +396,9 @@ class Codec(torch.nn.Module):
 
     def _free(self):
         if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._lib.qa_hcodec_destroy(self._handle)
+            self._lib.qa_hcodec_destroy(self._handle)  # a stream of the handle goes with it
             self._handle = C.c_void_p()
+        self._streaming_batch = 0
 
     def __del__(self):
         try:
@@ -568,6 +574,81 @@ class Codec(torch.nn.Module):
                                                               _stream_ptr(self.device)))
         G = int(g.value)
         return {"acoustic_codes": ac.view(-1)[: B * q * G].view(B, q, G), "semantic_codes": sc.view(-1)[: B * q * G].view(B, q, G)}
+
+    # -- the causal acoustic encoder as a stream --------------------------------
+    @property
+    def is_streaming(self) -> bool:
+        return self._streaming_batch > 0
+
+    @property
+    def streaming_offset(self) -> int:
+        """Code frames streamed since `streaming()` / `reset_streaming()`; -1 when not streaming."""
+        return int(self._lib.qa_hcodec_stream_offset(self._handle)) if self._handle.value else -1
+
+    @property
+    def stream_first_min_frames(self) -> int:
+        """The fewest code frames the first chunk of a stream may have (2 for the shipped geometry): it pads its left edge with the
+        reflection of its own frames, which equals the offline padding only from this length on.  Raises for a model that cannot stream."""
+        spec_c = self.spec.to_c()
+        first = C.c_int64(0)
+        _lib.check(self._lib.qa_hcodec_stream_geometry(C.byref(spec_c), None, C.byref(first), None, 0, None))
+        return int(first.value)
+
+    def streaming_forever(self, batch_size: int, max_frames: int = MAX_STREAM_FRAMES):
+        """Enter streaming mode (causal H-Codec 1.0): `encode_stream(x)` is then one step on the next samples of `batch_size` rows.
+        `max_frames` is the capacity in CODE frames (at most 4096, 163.84 s: the encoder's Transformer holds 8192 positions at two per code
+        frame); a step that would pass it is refused and leaves the state as it was.  Offline `encode` / `decode` / `forward` stay
+        allowed meanwhile: the stream's state is its own allocation.  On a codec that already streams, the old stream is freed."""
+        self._require_loaded()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qa_hcodec_stream_begin(self._handle, int(batch_size), int(max_frames)))
+        self._streaming_batch = int(batch_size)
+
+    def _stop_streaming(self):
+        if self._handle.value:
+            _lib.check(self._lib.qa_hcodec_stream_end(self._handle))
+        self._streaming_batch = 0
+
+    @contextmanager
+    def streaming(self, batch_size: int, max_frames: int = MAX_STREAM_FRAMES):
+        self.streaming_forever(batch_size, max_frames)
+        try:
+            yield
+        finally:
+            self._stop_streaming()
+
+    def reset_streaming(self):
+        """Back to offset 0: the next `encode_stream` is a first step again (reflect fill, LSTM state zeroed, earlier K / V rows invisible)."""
+        self._require_loaded()
+        _lib.check(self._lib.qa_hcodec_stream_reset(self._handle))
+
+    @torch.no_grad()
+    def encode_stream(self, x: torch.Tensor, return_emb: bool = False):
+        """The next chunk of every row of a stream: x [B, 1, n] or [B, n] fp32 with n a positive multiple of the samples of a code frame
+        (`spec.enc_hop`, 640) -> acoustic codes int64 [B, nq, n / hop], in the layout of `encode`'s first output; with `return_emb` also the
+        embeddings in front of the quantizer, emb [B, n / hop, code_dim].  Concatenated over the steps, both equal what one offline causal
+        `encode` of the concatenated waveform gives.  The first chunk needs at least `stream_first_min_frames` code frames.  A trailing
+        partial frame is the caller's to zero-pad, as `HCodecTokenizer.pad_wav` does - and only at the END of a stream: zeros in the middle
+        are signal.  The semantic codes have no stream (their encoder is not causal and the SSL features are whole-utterance)."""
+        if not self.is_streaming:
+            raise _lib.QuarkAudioError(-1, "Codec.encode_stream: not streaming - call it inside `with codec.streaming(batch_size):` "
+                                           "(or use encode for a whole utterance)")
+        if x.dim() == 3 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 2:
+            raise _lib.QuarkAudioError(-1, f"encode_stream expects x of shape [B,1,n] or [B,n], got {tuple(x.shape)}")
+        if x.shape[0] != self._streaming_batch:
+            raise _lib.QuarkAudioError(-1, f"streaming state was created for batch {self._streaming_batch}, got {x.shape[0]}")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        B, n = x.shape
+        # the library refuses a partial frame before it writes anything; max(.., 1): a chunk below one frame still gets its message
+        frames = max(n // self.spec.enc_hop, 1)
+        ac = torch.empty((B, self.spec.num_quantizers, frames), dtype=torch.int64, device=self.device)
+        emb = torch.empty((B, frames, self.spec.code_dim), dtype=torch.float32, device=self.device) if return_emb else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qa_hcodec_stream_encode(self._handle, x.data_ptr(), n, ac.data_ptr(), emb.data_ptr() if return_emb else None,
+                                                         _stream_ptr(self.device)))
+        return (ac, emb) if return_emb else ac
 
     def _adaptive_codes(self, acoustic_codes, semantic_codes, token_lengths, what: str):
         """The two code tensors of an H-Codec 1.5 decode on the device, length-injected (codec_adaptive.py:68-73)."""
