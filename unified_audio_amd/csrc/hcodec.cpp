@@ -56,7 +56,7 @@ struct MimiStream {
     // streaming_forever(): past the static RoPE table the step reads a rolling window of it (positions rope_base .. rope_base + len)
     // rebuilt on the host whenever the stream leaves it, so the offset is unbounded like the reference's (module/rope.py computes
     // the angles from the running offset)
-    float* rope_win = nullptr;
+    DeviceFloats rope_win;  // allocated by the first step that leaves the static table
     int rope_base = 0, rope_len = 0;
 };
 
@@ -78,29 +78,19 @@ void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, st
 struct TrStream {
     int B = 0, cap = 0;
     bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
-    float* mem = nullptr;
+    DeviceFloats mem;
     std::vector<float*> kc, vc, hs, cs;
-    TrStream() = default;
-    TrStream(const TrStream&) = delete;
-    TrStream& operator=(const TrStream&) = delete;
-    ~TrStream() {
-        if (mem) (void)hipFree(mem);
-    }
-    void release() {  // waits for the steps that still read the state (the caller has set the device)
-        if (mem) {
-            (void)hipDeviceSynchronize();
-            (void)hipFree(mem);
-        }
-        mem = nullptr;
+    void release() {  // not streaming any more (the caller has set the device)
+        mem.release();
         B = cap = 0;
     }
-    // a fresh state for B sequences of up to `capacity` frames; never cleared: no kernel reads a K / V row at or behind the key count of
-    // its step, and (h, c) are zeroed by the first step
+    // a fresh state for B sequences of up to `capacity` frames, in place of the one it held; never cleared: no kernel reads a K / V row at
+    // or behind the key count of its step, and (h, c) are zeroed by the first step
     int begin(const TransformerW& w, int64_t batch, int64_t capacity) {
         release();
         const size_t L = w.layers.size(), st = (size_t)batch * w.d, per = (size_t)batch * capacity * w.d;
-        QA_HIP(hipMalloc(reinterpret_cast<void**>(&mem), sizeof(float) * L * (2 * st + 2 * per)));
-        transformer_kv_views(mem, L, 2 * st, per, &kc, &vc);
+        QA_TRY(mem.allocate(L * (2 * st + 2 * per)));
+        transformer_kv_views(mem.ptr, L, 2 * st, per, &kc, &vc);
         hs.resize(L);
         cs.resize(L);
         for (size_t l = 0; l < L; ++l) {
@@ -133,12 +123,9 @@ struct CodecStream {
     bool first = true;               // the next step is a first step: reflect fill, LSTM state zeroed
     int cur = 0;                     // which of the two state buffers of every convolution holds the current state
     int first_min = 0;               // the fewest code frames a first chunk may have (stream_geometry)
-    float* conv_mem = nullptr;
+    DeviceFloats conv_mem;
     std::vector<StreamConv> convs;   // conv0, then (k3, down) per stage, then the out conv
     TrStream tr;
-    ~CodecStream() {
-        if (conv_mem) (void)hipFree(conv_mem);
-    }
 };
 
 }  // namespace
@@ -165,7 +152,7 @@ struct qa_hcodec : Handle {
     ConvW sem_out;
     // rvq
     const float *cb_a = nullptr, *cb_s = nullptr, *e2_a = nullptr, *e2_s = nullptr;
-    float* e2_dev = nullptr;
+    DeviceFloats e2_dev;
     // decoder
     ConvW up;
     const float *up_dw = nullptr, *up_dwb = nullptr;
@@ -218,7 +205,6 @@ struct qa_hcodec : Handle {
     // the chunked encoder of a causal H-Codec 1.0 handle (qa_hcodec_stream_*); null: not streaming
     std::unique_ptr<CodecStream> strm;
     ~qa_hcodec() {
-        if (e2_dev) (void)hipFree(e2_dev);
         if (host_sync) (void)hipHostFree(host_sync);
         if (side) (void)hipStreamDestroy(side);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -231,11 +217,7 @@ struct qa_mimi : Handle {
     qa_mimi_spec spec{};
     MimiW w;
     MimiStream st;       // st.B > 0: inside `with model.streaming(B)`
-    float* ring = nullptr;  // backing store of the ring caches
-    ~qa_mimi() {
-        if (ring) (void)hipFree(ring);
-        if (st.rope_win) (void)hipFree(st.rope_win);
-    }
+    DeviceFloats ring;   // backing store of the ring caches
 };
 
 // One codec Transformer (encoder_modules/transformer.py:396-489) on its own: offline forward, the reference's cache mode and a
@@ -251,7 +233,7 @@ struct qa_transformer : Handle {
 struct qa_transformer_cache {
     const qa_transformer* owner = nullptr;
     int device = 0, B = 0, cap = 0, len = 0;
-    float* mem = nullptr;
+    DeviceFloats mem;
     std::vector<float*> kc, vc;
 };
 
@@ -407,16 +389,39 @@ SGeom sconv_geom(int L, int k, int stride, bool causal) {
     }
     return {(int)t, left, right};
 }
+// qa_hcodec::Geom::enc of a SEANet ladder: frames per code frame at the input of stage i, 2 at its transformer
+std::vector<int> seanet_rates(const qa_hcodec_spec& sp) {
+    std::vector<int> enc(sp.n_ratios + 1, 2);
+    for (int i = sp.n_ratios - 1; i >= 0; --i) enc[i] = enc[i + 1] * sp.ratios[i];
+    return enc;
+}
 // zero padding of vq/conv.py's Conv1d (stride 1, :44-47): (k - 1, 0) if causal else (k / 2, k / 2)
 inline int zpad_left(int k, bool causal) { return causal ? k - 1 : k / 2; }
 inline int zpad_right(int k, bool causal) { return causal ? 0 : k / 2; }
 
+// The K / V caches and carried state of a chunk of t.T frames at positions pos0 .. pos0 + t.T - 1: the cached forward and the streaming step of
+// a codec Transformer.  Per layer the chunk's roped K and V rows are written to cache rows pos0 .. pos0 + t.T - 1 before
+// its queries attend over rows 0 .. pos0 + t.T - 1.
+struct TrChunk {
+    float* const* kc = nullptr;  // [layer] -> [B, cap, d]
+    float* const* vc = nullptr;
+    int cap = 0, pos0 = 0;
+    // streaming: the carried LSTM state of every layer [B, d] (read at step 0, left at the chunk's last step); null: the LSTM starts from
+    // zero, as the reference's does on every call (transformer.py:133)
+    float* const* hs = nullptr;
+    float* const* cs = nullptr;
+};
+
 // In place on x [t.B, t.T, d].  Ragged calls (non-causal): only the attention looks past a clip's end - the LSTM runs forward, everything
 // else is row-wise - so the lengths become one [B, N] key-padding mask, built once per call, for the KMASK form.
 // left_context > 0 (causal graphs only): the sliding window of Transformer(use_sliding_window=True) - query i sees key j iff i - j < left_context.
-int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, const std::string& tap_prefix, int left_context = 0) {
+// t.causal = 0: every query sees every key, the later ones of its own chunk included (mask None).
+// ch: null for the offline form (RoPE in place, attention over the packed qkv); else the chunk over ch's caches, which takes no taps.
+int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, const std::string& tap_prefix, int left_context = 0,
+                   const TrChunk* ch = nullptr) {
     const int d = tw.d, H = tw.heads, hd = d / H, B = t.B, N = t.T;
     const int64_t rows = t.rows();
+    const bool carried = ch && ch->hs;
     QA_REQUIRE(N <= MAX_POS, "transformer: sequence of %d frames exceeds %d", N, MAX_POS);
     const size_t mark = c.arena.mark();
     float* hn = c.arena.alloc<float>(rows * d);
@@ -426,107 +431,70 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
     float* hl = c.arena.alloc<float>(rows * d);
     float* qkv = c.arena.alloc<float>(rows * 3 * d);
     float* att = c.arena.alloc<float>(rows * d);
-    float* cst = c.arena.alloc<float>((size_t)B * d);
-    AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
-    at.causal = t.causal ? 1 : 0;
-    at.context = t.causal ? left_context : 0;
-    if (t.rl.n) {
-        QA_REQUIRE(!t.causal, "transformer: per-clip lengths exist for the non-causal graph only");
-        unsigned char* kvalid = c.arena.alloc<unsigned char>(rows);
-        QA_RUN(c, launch_len_mask(kvalid, B, N, t.rl, c.stream));
-        at.kvalid = kvalid;
-    }
-    for (size_t l = 0; l < tw.layers.size(); ++l) {
-        const TransformerLayerW& L = tw.layers[l];
-        const std::string lp = tap_prefix + ".layers." + std::to_string(l);
-        QA_TRY(rmsnorm_op(c, x, L.ln1, hn, rows, d, 1e-6f));
-        QA_TRY(linear_op(c, hn, rows, L.ih, big));
-        QA_RUN(c, launch_lstm(big, L.w_hh, hl, cst, B, N, d, c.stream));
-        c.tap(lp + ".self_attn.rnn", hl, rows * d);
-        QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
-        QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
-        QA_TRY(attention_op(c, at));
-        c.tap(lp + ".att", att, rows * d);
-        QA_TRY(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
-        c.tap(lp + ".x_attn", x, rows * d);
-        QA_TRY(rmsnorm_op(c, x, L.ln2, hn, rows, d, 1e-6f));
-        QA_TRY(linear_op(c, hn, rows, L.w1, big));
-        QA_TRY(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
-        QA_TRY(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
-        c.tap(lp + ".x_mlp", x, rows * d);
-    }
-    c.arena.release(mark);
-    return QA_OK;
-}
-
-// A chunk of N frames at positions pos0 .. pos0 + N - 1 over per-layer K / V caches [B, cap, d]: the cached forward and the streaming step
-// of qa_transformer, in place on x [B, N, d].  Per layer the chunk's roped K and V rows are written to cache rows
-// pos0 .. pos0 + N - 1 before its queries attend over rows 0 .. pos0 + N - 1.
-struct TrChunk {
-    float* const* kc = nullptr;  // [layer] -> [B, cap, d]
-    float* const* vc = nullptr;
-    int cap = 0, pos0 = 0;
-    int causal = 0, context = 0;  // causal = 0: every query sees every key, the later ones of its own chunk included (mask None)
-    // streaming: the carried LSTM state of every layer [B, d] (read at step 0, left at the chunk's last step); null: the LSTM starts from
-    // zero, as the reference's does on every call (transformer.py:133)
-    float* const* hs = nullptr;
-    float* const* cs = nullptr;
-};
-int transformer_chunk_op(Ctx& c, const TransformerW& tw, float* x, int B, int N, const TrChunk& ch) {
-    const int d = tw.d, H = tw.heads, hd = d / H;
-    const int64_t rows = (int64_t)B * N;
-    const size_t mark = c.arena.mark();
-    float* hn = c.arena.alloc<float>(rows * d);
-    const int wide = std::max(4 * d, tw.inter);
-    float* big = c.arena.alloc<float>(rows * wide);
-    float* big2 = c.arena.alloc<float>(rows * wide);
-    float* hl = c.arena.alloc<float>(rows * d);
-    float* qkv = c.arena.alloc<float>(rows * 3 * d);
-    float* att = c.arena.alloc<float>(rows * d);
-    float* cst = ch.hs ? nullptr : c.arena.alloc<float>((size_t)B * d);
+    float* cst = carried ? nullptr : c.arena.alloc<float>((size_t)B * d);
     // a stream step of a few frames over a long history: the split-key kernel (stream_attn.hip), 1.0 - 1.5 x the step through
     // attention_kernel up to 256 query rows per head and 0.92 - 1.01 x at 512 (B = 32 x 16 frames: its partial records outweigh the
     // parallelism it adds; profiles/transformer_stream_bench.jsonl).  QA_TR_SHORT_ATTN: 0 never, 2 every chunk of <= 16 frames
     const long long short_mode = knob(K_TR_SHORT_ATTN);
-    const bool short_chunk = ch.hs && ch.causal && N <= ATTN_SHORT_MAX_Q && (short_mode == 2 || (short_mode == 1 && (long long)B * N <= 256));
-    float* part = short_chunk ? c.arena.alloc<float>(attn_short_part_floats(B, H, hd, N, ch.cap)) : nullptr;
-    AttnArgs at;
-    at.q = qkv; at.ldq = 3 * d; at.out = att; at.ldo = d;
-    at.ldkv = d; at.kv_batch_stride = (long long)ch.cap * d;
-    at.B = B; at.n_q = N; at.n_keys = ch.pos0 + N; at.H = H; at.hd = hd;
-    at.scale = 1.0f / std::sqrt((float)hd);
-    at.causal = ch.causal;
-    at.context = ch.causal ? ch.context : 0;
+    const bool short_chunk = carried && t.causal && N <= ATTN_SHORT_MAX_Q && (short_mode == 2 || (short_mode == 1 && rows <= 256));
+    float* part = short_chunk ? c.arena.alloc<float>(attn_short_part_floats(B, H, hd, N, ch->cap)) : nullptr;
+    AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
+    at.causal = t.causal ? 1 : 0;
+    at.context = t.causal ? left_context : 0;
+    if (ch) {  // keys and values: rows 0 .. pos0 + N - 1 of the layer's caches
+        at.ldkv = d; at.kv_batch_stride = (long long)ch->cap * d;
+        at.n_keys = ch->pos0 + N;
+    }
+    if (t.rl.n) {
+        QA_REQUIRE(!t.causal && !ch, "transformer: per-clip lengths exist for the non-causal offline graph only");
+        unsigned char* kvalid = c.arena.alloc<unsigned char>(rows);
+        QA_RUN(c, launch_len_mask(kvalid, B, N, t.rl, c.stream));
+        at.kvalid = kvalid;
+    }
+    // the names are built in a tapping call only: a single-frame stream step is launch-bound, and this is its per-layer host work
+    const bool taps = c.capture && !ch;
+    std::string lp;
+    auto tap = [&](const char* name, const float* p) {
+        if (taps) c.tap(lp + name, p, rows * d);
+    };
     for (size_t l = 0; l < tw.layers.size(); ++l) {
         const TransformerLayerW& L = tw.layers[l];
+        if (taps) lp = tap_prefix + ".layers." + std::to_string(l);
         QA_TRY(rmsnorm_op(c, x, L.ln1, hn, rows, d, 1e-6f));
         QA_TRY(linear_op(c, hn, rows, L.ih, big));
-        if (ch.hs) QA_RUN(c, launch_lstm_carry(big, L.w_hh, hl, ch.hs[l], ch.cs[l], B, N, d, c.stream));
+        if (carried) QA_RUN(c, launch_lstm_carry(big, L.w_hh, hl, ch->hs[l], ch->cs[l], B, N, d, c.stream));
         else QA_RUN(c, launch_lstm(big, L.w_hh, hl, cst, B, N, d, c.stream));
+        tap(".self_attn.rnn", hl);
         QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
-        QA_RUN(c, launch_rope_append(qkv, tw.rope, ch.kc[l], ch.vc[l], B, N, H, hd, ch.pos0, ch.cap, c.stream));
-        if (short_chunk) {
-            QA_RUN(c, launch_attention_short(qkv, 3 * d, ch.kc[l], ch.vc[l], att, part, B, N, H, hd, ch.pos0, ch.cap, at.context, c.stream));
+        if (ch) {
+            QA_RUN(c, launch_rope_append(qkv, tw.rope, ch->kc[l], ch->vc[l], B, N, H, hd, ch->pos0, ch->cap, c.stream));
+            at.k = ch->kc[l]; at.v = ch->vc[l];
         } else {
-            at.k = ch.kc[l]; at.v = ch.vc[l];
+            QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
+        }
+        if (short_chunk) {
+            QA_RUN(c, launch_attention_short(qkv, 3 * d, at.k, at.v, att, part, B, N, H, hd, ch->pos0, ch->cap, at.context, c.stream));
+        } else {
             QA_TRY(attention_op(c, at));
         }
+        tap(".att", att);
         QA_TRY(linear_op(c, att, rows, L.o, x, epi(ACT_NONE, x)));
+        tap(".x_attn", x);
         QA_TRY(rmsnorm_op(c, x, L.ln2, hn, rows, d, 1e-6f));
         QA_TRY(linear_op(c, hn, rows, L.w1, big));
         QA_TRY(linear_op(c, hn, rows, L.w3, big2, epi(ACT_NONE, nullptr, nullptr, big)));
         QA_TRY(linear_op(c, big2, rows, L.w2, x, epi(ACT_NONE, x)));
+        tap(".x_mlp", x);
     }
     c.arena.release(mark);
     return QA_OK;
 }
 
-// the step of a streaming state at `pos0` frames: causal, the K / V rows and the carried LSTM state of `st`
-TrChunk stream_chunk(const TrStream& st, int pos0, int left_context) {
+// the step of a streaming state at `pos0` frames: the K / V rows and the carried LSTM state of `st`
+TrChunk stream_chunk(const TrStream& st, int pos0) {
     TrChunk ch;
     ch.kc = st.kc.data(); ch.vc = st.vc.data();
     ch.cap = st.cap; ch.pos0 = pos0;
-    ch.causal = 1; ch.context = left_context;
     ch.hs = st.hs.data(); ch.cs = st.cs.data();
     return ch;
 }
@@ -551,7 +519,7 @@ int mimi_layer(Ctx& c, const MimiW& mw, const MimiLayerW& L, float* x, const Mim
     const int64_t rows = (int64_t)B * N;
     const int pos0 = st ? st->offset : 0;
     const bool win = st && st->rope_len > 0;  // RoPE angles from the rolling window (positions beyond the static table)
-    const float* rope = win ? st->rope_win : mw.rope;
+    const float* rope = win ? st->rope_win.ptr : mw.rope;
     const int rope_pos0 = win ? pos0 - st->rope_base : pos0;
     QA_TRY(layernorm_op(c, x, L.n1w, L.n1b, t.hn, rows, d, 1e-5f));
     // fused QKV projection with the interleaved-pair RoPE of q and k applied in the GEMM epilogue (one launch less per layer)
@@ -750,23 +718,73 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float*
     return QA_OK;
 }
 
-// SEANet encoder (seanet.py:121-187): wav [B, T] -> emb [B, N25, code_dim]; *n50_out: the frames of its transformer.
+// SEANet encoder (seanet.py:121-187): wav [B, T] -> emb [B, N25, code_dim] (*emb_out null: an arena buffer); *n50_out: the frames of its
+// transformer.
 // Ragged calls (H-Codec 1.0, non-causal): clip b has tw.rl.n[b] code frames.  Every stage's length is that count times the stage's frames
 // per code frame (h->geom.enc), which is what each layer with a temporal footprint receives; samples behind a clip's end are never read,
 // and the rows behind it that the rectangular launches still compute stay finite (they are built from valid rows and zeros).
-int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float** emb_out, int* n50_out, int* n25_out) {
+// st: null for a whole utterance, else one step of a stream - wav holds the next tw.T / geom.samples code frames of
+// a causal model.  The ladder is the same; what differs is where a convolution with a temporal footprint finds its left context (sconv
+// below) and the front: a step takes the unfused launches, as a ragged call does - the fused front stages whole halo tiles with a reflect
+// rule of its own (a carried-halo form of it is not built) - and has neither lengths nor taps.  The 1x1 shortcut and the 1x1 behind the k3
+// are row-wise and carry nothing.  The Transformer continues over its carried (h, c) and K / V rows at 2 frames per code frame.  A step
+// reads st->cur / first / offset, which the caller advances behind a successful step.
+int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float** emb_out, int* n50_out, int* n25_out,
+                   CodecStream* st = nullptr) {
     const qa_hcodec_spec& sp = h->spec;
     const int B = tw.B;
-    const bool cz = tw.causal;
+    const bool cz = tw.causal, taps = c.capture && !st;
     int C = sp.n_filters;
     TimeAxis t = tw;
+    size_t ci = 0;
+    // stream: the window [B, ctx + L, C] of the next stateful convolution over chunk [B, L, C], assembled from its carried state (first
+    // step: the reflection of the chunk) and the chunk; conv_op has no batch stride for x, so the window is a buffer of its own.  The state
+    // of a convolution is the raw rows of its own input buffer, before any prologue ELU; for the down convs those rows hold the fused
+    // post-ELU values.
+    auto window = [&](const float* chunk, int L, int Cw, float** win) -> int {
+        QA_REQUIRE(ci < st->convs.size() && st->convs[ci].C == Cw, "stream: convolution %zu of the ladder has no state of %d channels", ci, Cw);
+        const StreamConv& sc = st->convs[ci++];
+        *win = c.arena.alloc<float>((size_t)B * (sc.ctx + L) * Cw);
+        QA_RUN(c, launch_stream_window(sc.st[st->cur], chunk, *win, sc.st[st->cur ^ 1], B, sc.ctx, L, Cw, st->first ? 1 : 0, c.stream));
+        return QA_OK;
+    };
+    // SConv1d(k = w.ksize, stride) over x [B, ta.T, w.C_in] -> *y [B, *T_out, w.N] (*y null: an arena buffer); o: prologue and epilogue.
+    // Offline the paddings of sconv_geom, reflected.  In a stream a VALID convolution (pads 0 / 0) over the window: a waveform of a whole
+    // number of code frames needs no right padding anywhere, so ta.T / stride frames.
+    auto sconv = [&](const float* x, const TimeAxis& ta, const ConvW& w, int stride, ConvOpt o, float** y, int* T_out) -> int {
+        TimeAxis tx = ta;
+        o.stride = stride;
+        if (st) {
+            float* win = nullptr;
+            QA_TRY(window(x, ta.T, w.C_in, &win));
+            x = win;
+            tx.T += st->convs[ci - 1].ctx;
+            *T_out = ta.T / stride;
+        } else {
+            const SGeom g = sconv_geom(ta.T, w.ksize, stride, cz);
+            o.pad_left = g.left;
+            o.pad_right = g.right;
+            o.pad_mode = PAD_REFLECT;
+            *T_out = g.T_out;
+        }
+        if (!*y) *y = c.arena.alloc<float>((size_t)B * *T_out * w.N);
+        return conv_at(c, x, tx, w, *y, *T_out, o);
+    };
     // stage 0 at C = 32: conv0 + residual block + ELU in ONE launch (seanet_front.hip): the [B L, 32] conv0 output never exists in HBM
     // ... except in a ragged call, which takes the unfused launches as a capture does: they already resolve padding per (row, tap) and take
     // the clips' lengths there, where the fused kernel stages whole halo tiles of one shared length
-    const bool front = seanet_front_supported(C, C / 2, t.T) && !t.rl.n;
-    float* x = (front && !c.capture) ? nullptr : c.arena.alloc<float>((size_t)t.rows() * C);
-    if (x) QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, t.T, C, 7, c.stream, cz ? 6 : -1, t.rl));
-    if (x) c.tap("enc.conv0", x, t.rows() * C);
+    const bool front = seanet_front_supported(C, C / 2, t.T) && !t.rl.n && !st;
+    float* x = nullptr;
+    if (st) {
+        float* win = nullptr;
+        QA_TRY(window(wav, t.T, 1, &win));
+        x = c.arena.alloc<float>((size_t)t.rows() * C);
+        QA_RUN(c, launch_conv_in_window(win, h->conv0_w, h->conv0_b, x, B, st->convs[0].ctx + t.T, C, 7, c.stream));
+    } else if (!front || c.capture) {
+        x = c.arena.alloc<float>((size_t)t.rows() * C);
+        QA_RUN(c, launch_conv_in(wav, h->conv0_w, h->conv0_b, x, B, t.T, C, 7, c.stream, cz ? 6 : -1, t.rl));
+        c.tap("enc.conv0", x, t.rows() * C);
+    }
     for (int i = 0; i < sp.n_ratios; ++i) {
         const int r = sp.ratios[i], L = t.T;
         const ResBlockW& rb = h->res[i];
@@ -777,13 +795,11 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
                                           C / 2, cz ? 1 : 0, c.stream));
         } else {
             float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
+            int Lk = 0;
             // shortcut_1x1(x)
             QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));
-            // ELU(k3(ELU(x)))  (reflect pad 1,1)
-            ConvOpt k3 = conv_geom(1, cz ? 2 : 1, cz ? 0 : 1, PAD_REFLECT);
-            k3.prologue = ACT_ELU;
-            k3.act = ACT_ELU;
-            QA_TRY(conv_at(c, x, t, rb.k3, hh, L, k3));
+            // ELU(k3(ELU(x)))  (offline: reflect pad 1,1; causal 2,0 - sconv_geom(L, 3, 1))
+            QA_TRY(sconv(x, t, rb.k3, 1, elu_conv_elu(), &hh, &Lk));
             // ELU(shortcut + 1x1(.))  -> the activation in front of the down-sampling conv is fused here
             ConvOpt pw;
             pw.res = sc;
@@ -791,25 +807,23 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
             pw.post_act = ACT_ELU;
             QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, pw));
         }
-        const SGeom g = sconv_geom(L, 2 * r, r, cz);
-        float* y = c.arena.alloc<float>((size_t)B * g.T_out * 2 * C);
-        QA_TRY(conv_at(c, sc, t, h->down[i], y, g.T_out, conv_geom(r, g.left, g.right, PAD_REFLECT)));
+        float* y = nullptr;
+        int To = 0;
+        QA_TRY(sconv(sc, t, h->down[i], r, ConvOpt(), &y, &To));
         x = y;
-        t = t.at(g.T_out, h->geom.enc[i + 1]);
+        t = t.at(To, h->geom.enc[i + 1]);
         C *= 2;
-        c.tap("enc.stage" + std::to_string(i), x, t.rows() * C);
+        if (taps) c.tap("enc.stage" + std::to_string(i), x, t.rows() * C);
     }
     QA_REQUIRE(C == sp.dimension, "encoder: channel ladder ends at %d, spec.dimension is %d", C, sp.dimension);
-    QA_TRY(transformer_op(c, h->enc_tr, x, t, "encoder.model." + std::to_string(3 * sp.n_ratios + 2)));
-    c.tap("enc.transformer", x, t.rows() * C);
-    const SGeom g = sconv_geom(t.T, 4, 2, cz);
-    float* emb = c.arena.alloc<float>((size_t)B * g.T_out * sp.code_dim);
-    ConvOpt eo = conv_geom(2, g.left, g.right, PAD_REFLECT);
+    QA_REQUIRE(!st || t.T * h->geom.samples == 2 * tw.T, "stream: the ladder ends at %d frames for a step of %d samples", t.T, tw.T);
+    const TrChunk ch = st ? stream_chunk(st->tr, 2 * st->offset) : TrChunk();
+    QA_TRY(transformer_op(c, h->enc_tr, x, t, taps ? "encoder.model." + std::to_string(3 * sp.n_ratios + 2) : std::string(), 0, st ? &ch : nullptr));
+    if (taps) c.tap("enc.transformer", x, t.rows() * C);
+    ConvOpt eo;
     eo.prologue = ACT_ELU;
-    QA_TRY(conv_at(c, x, t, h->enc_out, emb, g.T_out, eo));
-    *emb_out = emb;
+    QA_TRY(sconv(x, t, h->enc_out, 2, eo, emb_out, n25_out));
     *n50_out = t.T;
-    *n25_out = g.T_out;
     return QA_OK;
 }
 
@@ -847,8 +861,7 @@ struct StreamGeom {
 };
 StreamGeom stream_geometry(const qa_hcodec_spec& sp) {
     StreamGeom g;
-    std::vector<int> enc(sp.n_ratios + 1, 2);  // qa_hcodec::Geom::enc: frames per code frame at the input of stage i
-    for (int i = sp.n_ratios - 1; i >= 0; --i) enc[i] = enc[i + 1] * sp.ratios[i];
+    const std::vector<int> enc = seanet_rates(sp);
     g.samples = enc[0];
     auto add = [&](int k, int stride, int rate) {
         g.ctx.push_back(k - stride);
@@ -864,71 +877,13 @@ StreamGeom stream_geometry(const qa_hcodec_spec& sp) {
     return g;
 }
 
-// SEANet encoder, one step of a stream: the next n code frames wav [B, n * samples] -> emb [B, n, code_dim].  Mirrors seanet_encoder layer
-// for layer.  Every convolution with a temporal footprint runs as a VALID convolution (pads 0 / 0) over a window [B, ctx + n_in, C] that
-// launch_stream_window assembles from the carried state (first step: the reflection of the chunk) and the chunk; conv_op has no batch stride
-// for x, so the window is a buffer of its own.  The state of a conv is the raw rows of its own input buffer, before any prologue ELU; for
-// the down convs those rows hold the fused post-ELU values, as in seanet_encoder.  Stage 0 takes the unfused launches, as ragged calls do:
-// the fused front stages whole halo tiles with a reflect rule of its own (a carried-halo form of it is not built).  The 1x1 shortcut and the
-// 1x1 behind the k3 are row-wise and carry nothing.  The Transformer continues over its carried (h, c) and K / V rows at 2 frames per code
-// frame.  Reads st.cur / st.first / st.offset, which the caller advances behind a successful step.
-int seanet_encoder_step(qa_hcodec* h, Ctx& c, const float* wav, int n, float* emb) {
-    const qa_hcodec_spec& sp = h->spec;
-    CodecStream& st = *h->strm;
-    const int B = st.B, first = st.first ? 1 : 0;
-    size_t ci = 0;
-    // the window of the next stateful conv over chunk [B, L, C]: [B, ctx + L, C]; *T_in = ctx + L
-    auto window = [&](const float* chunk, int L, int C, float** win, int* T_in) -> int {
-        QA_REQUIRE(ci < st.convs.size() && st.convs[ci].C == C, "stream: convolution %zu of the ladder has no state of %d channels", ci, C);
-        const StreamConv& sc = st.convs[ci++];
-        *T_in = sc.ctx + L;
-        *win = c.arena.alloc<float>((size_t)B * *T_in * C);
-        QA_RUN(c, launch_stream_window(sc.st[st.cur], chunk, *win, sc.st[st.cur ^ 1], B, sc.ctx, L, C, first, c.stream));
-        return QA_OK;
-    };
-    int C = sp.n_filters, L = n * h->geom.samples, Tw = 0;
-    float* win = nullptr;
-    QA_TRY(window(wav, L, 1, &win, &Tw));
-    float* x = c.arena.alloc<float>((size_t)B * L * C);
-    QA_RUN(c, launch_conv_in_window(win, h->conv0_w, h->conv0_b, x, B, Tw, C, 7, c.stream));
-    for (int i = 0; i < sp.n_ratios; ++i) {
-        const int r = sp.ratios[i];
-        const ResBlockW& rb = h->res[i];
-        float* sc = c.arena.alloc<float>((size_t)B * L * C);
-        float* hh = c.arena.alloc<float>((size_t)B * L * rb.k3.N);
-        QA_TRY(conv_op(c, x, C, B, L, rb.sc, sc, C, L, ConvOpt()));  // shortcut_1x1(x)
-        QA_TRY(window(x, L, C, &win, &Tw));
-        ConvOpt k3 = conv_geom(1, 0, 0);  // ELU(k3(ELU(.))) over the window
-        k3.prologue = ACT_ELU;
-        k3.act = ACT_ELU;
-        QA_TRY(conv_op(c, win, C, B, Tw, rb.k3, hh, rb.k3.N, L, k3));
-        ConvOpt pw;  // ELU(shortcut + 1x1(.)): the activation in front of the down conv, fused as in seanet_encoder
-        pw.res = sc;
-        pw.ldr = C;
-        pw.post_act = ACT_ELU;
-        QA_TRY(conv_op(c, hh, rb.pw.C_in, B, L, rb.pw, sc, C, L, pw));
-        QA_TRY(window(sc, L, C, &win, &Tw));
-        float* y = c.arena.alloc<float>((size_t)B * (L / r) * 2 * C);
-        QA_TRY(conv_op(c, win, C, B, Tw, h->down[i], y, 2 * C, L / r, conv_geom(r, 0, 0)));
-        x = y;
-        L /= r;
-        C *= 2;
-    }
-    QA_REQUIRE(C == sp.dimension && L == 2 * n, "stream: the ladder ends at %d channels, %d frames (dimension %d, %d frames)", C, L,
-               sp.dimension, 2 * n);
-    QA_TRY(transformer_chunk_op(c, h->enc_tr, x, B, L, stream_chunk(st.tr, 2 * st.offset, 0)));
-    QA_TRY(window(x, L, C, &win, &Tw));
-    ConvOpt eo = conv_geom(2, 0, 0);
-    eo.prologue = ACT_ELU;
-    return conv_op(c, win, C, B, Tw, h->enc_out, emb, sp.code_dim, n, eo);
-}
-
 // one step of Codec.encode's acoustic half: SEANet step -> emb [B, n, code_dim] -> ResidualVQ -> codes [B, nq, n]; either output may be null
 int stream_encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int n, long long* ac_out, float* emb_out) {
     const qa_hcodec_spec& sp = h->spec;
     const int B = h->strm->B, Q = sp.num_quantizers;
     float* emb = emb_out ? emb_out : c.arena.alloc<float>((size_t)B * n * sp.code_dim);
-    QA_TRY(seanet_encoder_step(h, c, wav, n, emb));
+    int n50 = 0, n25 = 0;
+    QA_TRY(seanet_encoder(h, c, wav, TimeAxis{B, n * h->geom.samples, true, ClipLens()}, &emb, &n50, &n25, h->strm.get()));
     if (!ac_out) return QA_OK;
     long long* ia = c.arena.alloc<long long>((size_t)B * n * Q);
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * n, sp.codebook_size, sp.code_dim));
@@ -1371,8 +1326,7 @@ int build(qa_hcodec* h, const HostTable& tab) {
     geom.feat = geom.sem[0];
     geom.dec = v20 ? sp.frame_stride : 2;
     if (v20) geom.enc = {2 * sp.frame_stride, sp.frame_stride};  // hop = 2 blocks (checked below), frame_stride frames per code frame
-    if (!v20) geom.enc.assign(sp.n_ratios + 1, 2);
-    for (int i = sp.n_ratios - 1; i >= 0 && !v20; --i) geom.enc[i] = geom.enc[i + 1] * sp.ratios[i];
+    if (!v20) geom.enc = seanet_rates(sp);
     geom.samples = v20 ? sp.hop * sp.frame_stride : geom.enc[0];
     Loader b(tab, h->store);
     auto dw_fold_c = [&](const float** dst, const std::string& name, int k, int ch) {
@@ -1546,51 +1500,21 @@ int build(qa_hcodec* h, const HostTable& tab) {
     QA_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     // |e|^2 tables
     const int QK = sp.num_quantizers * sp.codebook_size;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&h->e2_dev), sizeof(float) * 2 * QK));
-    QA_TRY(launch_rvq_norms(h->cb_a, h->e2_dev, QK, sp.code_dim, nullptr));
-    QA_TRY(launch_rvq_norms(h->cb_s, h->e2_dev + QK, QK, sp.code_dim, nullptr));
+    QA_TRY(h->e2_dev.allocate(2 * (size_t)QK));
+    QA_TRY(launch_rvq_norms(h->cb_a, h->e2_dev.ptr, QK, sp.code_dim, nullptr));
+    QA_TRY(launch_rvq_norms(h->cb_s, h->e2_dev.ptr + QK, QK, sp.code_dim, nullptr));
     QA_HIP(hipDeviceSynchronize());
-    h->e2_a = h->e2_dev;
-    h->e2_s = h->e2_dev + QK;
+    h->e2_a = h->e2_dev.ptr;
+    h->e2_s = h->e2_dev.ptr + QK;
     return QA_OK;
 }
 
 }  // namespace
 }  // namespace qa
 
-// The non-dry pass of a model graph.  A call that launched the persistent LSTM recurrence (lstm.hip) waits for its stream before
-// returning and, should one of that kernel's grid barriers have timed out (it needs every workgroup resident at once: the device
-// was shared with another such kernel), runs the graph again on the per-step kernels - the call that hit the failure returns
-// valid results, and the device stops choosing the persistent kernel by itself.
-template <typename F>
-static int run_graph_checked(Handle* h, F&& graph) {
-    Ctx& c = h->ctx;
-    void* ticket = nullptr;
-    QA_TRY(lstm_call_begin(h->device, &ticket));
-    {
-        const int st = graph();
-        if (st != QA_OK) {  // error path only: the aggregator side stream may still run out of the workspace
-            (void)hipDeviceSynchronize();
-            bool ignored = false;
-            (void)lstm_call_end(ticket, c.stream, &ignored);
-            return st;
-        }
-    }
-    bool failed = false;
-    QA_TRY(lstm_call_end(ticket, c.stream, &failed));  // host-synchronous only for a call that launched an in-launch recurrence
-    if (!failed) return QA_OK;
-    std::fprintf(stderr, "libquarkaudio_hip: the grid barrier of the persistent LSTM recurrence timed out on device %d (shared device?); "
-                         "re-running the call on the per-step kernels\n", h->device);
-    lstm_force_per_step(true);
-    arm(c, h->ws);
-    const int st = graph();
-    lstm_force_per_step(false);
-    return st;
-}
-
 // plan the call on the handle's workspace, then its real pass
 template <typename F>
-static int run(qa_hcodec* h, void* stream, F&& graph) {
+static int run(Handle* h, void* stream, F&& graph) {
     QA_TRY(plan(h->device, static_cast<hipStream_t>(stream), h->ctx, h->ws, graph));
     return run_graph_checked(h, graph);
 }
@@ -1739,12 +1663,6 @@ int qa_hcodec_stream_geometry(const qa_hcodec_spec* spec, int64_t* samples_per_f
     return QA_OK;
 }
 
-static void hcodec_stream_free(qa_hcodec* h) {
-    if (!h->strm) return;
-    (void)hipDeviceSynchronize();  // the steps that still read the state
-    h->strm.reset();
-}
-
 int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
     QA_REQUIRE(h, "qa_hcodec_stream_begin: null handle");
     QA_TRY(stream_refuse(h->spec, "qa_hcodec_stream_begin"));
@@ -1753,7 +1671,7 @@ int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
                "qa_hcodec_stream_begin: batch %lld, max_frames %lld (code frames, %d .. %d: the Transformer holds %d positions at 2 per code "
                "frame, and the first chunk alone needs %d)", (long long)B, (long long)max_frames, g.first_min, MAX_POS / 2, MAX_POS, g.first_min);
     QA_HIP(hipSetDevice(h->device));
-    hcodec_stream_free(h);
+    h->strm.reset();  // a handle that is already streaming: its buffers wait for the steps that still read them
     std::unique_ptr<CodecStream> st(new CodecStream());
     // the convolutions' states: two buffers [B, ctx, C] each, 64-float aligned, one allocation
     st->convs.resize(g.ctx.size());
@@ -1767,8 +1685,8 @@ int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
         if (i + 1 == g.ctx.size()) sc.C = h->spec.dimension;
         total += 2 * (size_t)round_up((int64_t)B * sc.ctx * sc.C, 64);
     }
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&st->conv_mem), sizeof(float) * total));
-    float* p = st->conv_mem;
+    QA_TRY(st->conv_mem.allocate(total));
+    float* p = st->conv_mem.ptr;
     for (StreamConv& sc : st->convs)
         for (int k = 0; k < 2; ++k) {
             sc.st[k] = p;
@@ -1824,7 +1742,7 @@ int qa_hcodec_stream_reset(qa_hcodec* h) {
 int qa_hcodec_stream_end(qa_hcodec* h) {
     if (!h || !h->strm) return QA_OK;  // nothing to end: harmless, like free(NULL)
     (void)hipSetDevice(h->device);
-    hcodec_stream_free(h);
+    h->strm.reset();
     return QA_OK;
 }
 
@@ -2069,16 +1987,14 @@ int qa_mimi_stream_begin(qa_mimi* m, int64_t B) {
                "(mimi/transformer.py:349-353)");
     QA_REQUIRE(B > 0 && B < (1 << 20), "qa_mimi_stream_begin: batch %lld", (long long)B);
     QA_HIP(hipSetDevice(m->device));
-    if (m->ring) QA_HIP(hipFree(m->ring));
-    m->ring = nullptr;
     const size_t L = m->w.layers.size(), per = (size_t)B * m->spec.context * m->w.d;
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&m->ring), sizeof(float) * 2 * L * per));
-    QA_HIP(hipMemset(m->ring, 0, sizeof(float) * 2 * L * per));  // RingKVCache.__init__: zeros
+    QA_TRY(m->ring.allocate(2 * L * per));  // in place of the ring of a handle that is already streaming
+    QA_HIP(hipMemset(m->ring.ptr, 0, sizeof(float) * 2 * L * per));  // RingKVCache.__init__: zeros
     m->st.kc.resize(L);
     m->st.vc.resize(L);
     for (size_t l = 0; l < L; ++l) {
-        m->st.kc[l] = m->ring + (2 * l) * per;
-        m->st.vc[l] = m->ring + (2 * l + 1) * per;
+        m->st.kc[l] = m->ring.ptr + (2 * l) * per;
+        m->st.vc[l] = m->ring.ptr + (2 * l + 1) * per;
     }
     m->st.B = (int)B;
     m->st.cap = m->spec.context;
@@ -2103,11 +2019,11 @@ int qa_mimi_stream_step(qa_mimi* m, const float* x, int64_t T, float* y, void* s
         st.rope_len = 0;
     } else if (st.rope_len == 0 || st.offset < st.rope_base || end > (long long)st.rope_base + st.rope_len) {
         const int hd = m->w.d / m->w.heads;
-        if (!st.rope_win) QA_HIP(hipMalloc(reinterpret_cast<void**>(&st.rope_win), sizeof(float) * (size_t)MAX_POS * hd));
+        if (!st.rope_win.ptr) QA_TRY(st.rope_win.allocate((size_t)MAX_POS * hd));
         std::vector<float> cs;
         mimi_rope_table(hd, st.offset, table, &cs);
         QA_HIP(hipStreamSynchronize(s));  // earlier steps may still read the old window; `cs` is a stack-lifetime host buffer
-        QA_HIP(hipMemcpy(st.rope_win, cs.data(), sizeof(float) * cs.size(), hipMemcpyHostToDevice));
+        QA_HIP(hipMemcpy(st.rope_win.ptr, cs.data(), sizeof(float) * cs.size(), hipMemcpyHostToDevice));
         st.rope_base = st.offset;
         st.rope_len = table;
     }
@@ -2127,13 +2043,11 @@ int qa_mimi_stream_reset(qa_mimi* m) {
 int qa_mimi_stream_end(qa_mimi* m) {
     QA_REQUIRE(m, "qa_mimi_stream_end: null handle");
     (void)hipSetDevice(m->device);
-    if (m->ring) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(m->ring);
-    }
-    m->ring = nullptr;
-    if (m->st.rope_win) (void)hipFree(m->st.rope_win);
-    m->st = MimiStream{};
+    m->ring.release();
+    m->st.rope_win.release();
+    m->st.kc.clear();
+    m->st.vc.clear();
+    m->st.B = m->st.cap = m->st.offset = m->st.rope_base = m->st.rope_len = 0;
     return QA_OK;
 }
 
@@ -2178,17 +2092,22 @@ static int transformer_check_io(const char* fn, const qa_transformer* h, const f
     return QA_OK;
 }
 
+// y = the Transformer over x [B, n, d]: the copy on the real pass, then transformer_op in place on y; ch as in transformer_op
+static int transformer_run(qa_transformer* h, const float* x, int B, int n, float* y, void* stream, const TrChunk* ch) {
+    Ctx& c = h->ctx;
+    auto graph = [&]() -> int {
+        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, c.stream));
+        return transformer_op(c, h->w, y, TimeAxis{B, n, h->spec.causal != 0, ClipLens()}, "", h->spec.left_context, ch);
+    };
+    // a stream step carries its LSTM state through the per-step kernels alone; every other call's launch_lstm may be the persistent kernel
+    // and needs the ticket of run_graph_checked
+    return ch && ch->hs ? run_planned(*h, stream, graph) : run(h, stream, graph);
+}
+
 int qa_transformer_forward(qa_transformer* h, const float* x, int64_t B, int64_t T, float* y, void* stream) {
     QA_TRY(transformer_check_io("qa_transformer_forward", h, x, y, B, T));
     QA_REQUIRE(h->st.B == 0, "qa_transformer_forward: the handle is in streaming mode, use qa_transformer_stream_step");
-    Ctx& c = h->ctx;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    auto graph = [&]() -> int {
-        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * T * h->w.d, hipMemcpyDeviceToDevice, s));
-        return transformer_op(c, h->w, y, TimeAxis{(int)B, (int)T, h->spec.causal != 0, ClipLens()}, "", h->spec.left_context);
-    };
-    QA_TRY(plan(h->device, s, c, h->ws, graph));
-    return run_graph_checked(h, graph);
+    return transformer_run(h, x, (int)B, (int)T, y, stream, nullptr);
 }
 
 int qa_transformer_cache_create(qa_transformer* h, int64_t B, int64_t capacity, qa_transformer_cache** out) {
@@ -2200,8 +2119,8 @@ int qa_transformer_cache_create(qa_transformer* h, int64_t B, int64_t capacity, 
     std::unique_ptr<qa_transformer_cache> c(new qa_transformer_cache());
     const size_t L = h->w.layers.size(), per = (size_t)B * capacity * h->w.d;
     // never cleared: no kernel reads a cache row at or behind the key count of its call
-    QA_HIP(hipMalloc(reinterpret_cast<void**>(&c->mem), sizeof(float) * 2 * L * per));
-    transformer_kv_views(c->mem, L, 0, per, &c->kc, &c->vc);
+    QA_TRY(c->mem.allocate(2 * L * per));
+    transformer_kv_views(c->mem.ptr, L, 0, per, &c->kc, &c->vc);
     c->owner = h;
     c->device = h->device;
     c->B = (int)B;
@@ -2213,9 +2132,7 @@ int qa_transformer_cache_create(qa_transformer* h, int64_t B, int64_t capacity, 
 void qa_transformer_cache_destroy(qa_transformer_cache* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    if (c->mem) (void)hipFree(c->mem);
-    delete c;
+    delete c;  // c->mem waits for the calls that still read it
 }
 
 int64_t qa_transformer_cache_length(const qa_transformer_cache* c) { return c ? c->len : -1; }
@@ -2238,26 +2155,13 @@ int qa_transformer_forward_cached(qa_transformer* h, qa_transformer_cache* cache
                "qa_transformer_stream_begin / qa_transformer_stream_step", cache->len);
     QA_REQUIRE((int64_t)cache->len + n <= cache->cap, "qa_transformer_forward_cached: %d cached + %lld new frames exceed the capacity %d",
                cache->len, (long long)n, cache->cap);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_transformer_forward_cached", s, CACHE_IS_HOST_STATE));
-    Ctx& c = h->ctx;
+    QA_TRY(refuse_capture("qa_transformer_forward_cached", static_cast<hipStream_t>(stream), CACHE_IS_HOST_STATE));
     TrChunk ch;
     ch.kc = cache->kc.data(); ch.vc = cache->vc.data();
     ch.cap = cache->cap; ch.pos0 = cache->len;
-    ch.causal = h->spec.causal; ch.context = h->spec.left_context;
-    auto graph = [&]() -> int {
-        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, s));
-        return transformer_chunk_op(c, h->w, y, (int)B, (int)n, ch);
-    };
-    QA_TRY(plan(h->device, s, c, h->ws, graph));
-    QA_TRY(run_graph_checked(h, graph));
+    QA_TRY(transformer_run(h, x, (int)B, (int)n, y, stream, &ch));
     cache->len += (int)n;
     return QA_OK;
-}
-
-static void transformer_stream_free(qa_transformer* h) {
-    h->st.release();
-    h->offset = 0;
 }
 
 int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) {
@@ -2267,8 +2171,8 @@ int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) 
     QA_REQUIRE(B > 0 && B < (1 << 20) && capacity >= 1 && capacity <= MAX_POS, "qa_transformer_stream_begin: batch %lld, capacity %lld (1 .. %d)",
                (long long)B, (long long)capacity, MAX_POS);
     QA_HIP(hipSetDevice(h->device));
-    transformer_stream_free(h);
-    return h->st.begin(h->w, B, capacity);
+    h->offset = 0;
+    return h->st.begin(h->w, B, capacity);  // in place of the state of a handle that is already streaming
 }
 
 int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, float* y, void* stream) {
@@ -2280,15 +2184,9 @@ int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, flo
     const hipStream_t s = static_cast<hipStream_t>(stream);
     QA_TRY(refuse_capture("qa_transformer_stream_step", s, CACHE_IS_HOST_STATE));
     QA_HIP(hipSetDevice(h->device));
-    const int B = h->st.B;
     QA_TRY(h->st.zero_if_new(h->w.d, s));
-    Ctx& c = h->ctx;
-    const TrChunk ch = stream_chunk(h->st, h->offset, h->spec.left_context);
-    auto graph = [&]() -> int {
-        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, s));
-        return transformer_chunk_op(c, h->w, y, B, (int)n, ch);
-    };
-    QA_TRY(run_planned(*h, stream, graph));
+    const TrChunk ch = stream_chunk(h->st, h->offset);
+    QA_TRY(transformer_run(h, x, h->st.B, (int)n, y, stream, &ch));
     h->offset += (int)n;
     return QA_OK;
 }
@@ -2303,7 +2201,8 @@ int qa_transformer_stream_reset(qa_transformer* h) {
 int qa_transformer_stream_end(qa_transformer* h) {
     QA_REQUIRE(h, "qa_transformer_stream_end: null handle");
     (void)hipSetDevice(h->device);
-    transformer_stream_free(h);
+    h->st.release();
+    h->offset = 0;
     return QA_OK;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -182,6 +183,28 @@ struct DeviceInts {
             out[i] = dev + i * cap;
         }
         return QA_OK;
+    }
+};
+
+// One float buffer of a handle's own that lives across calls, outside the arena: the streaming and cache states.  release() first waits for
+// the device - the steps that still read the buffer - and the caller has set the device, on every path that ends in it (the destructor too).
+struct DeviceFloats {
+    float* ptr = nullptr;
+    DeviceFloats() = default;
+    DeviceFloats(const DeviceFloats&) = delete;
+    DeviceFloats& operator=(const DeviceFloats&) = delete;
+    ~DeviceFloats() { release(); }
+    // n floats in place of what it held, not cleared
+    int allocate(size_t n) {
+        release();
+        QA_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(float) * n));
+        return QA_OK;
+    }
+    void release() {
+        if (!ptr) return;
+        (void)hipDeviceSynchronize();
+        (void)hipFree(ptr);
+        ptr = nullptr;
     }
 };
 
@@ -531,6 +554,37 @@ template <typename G>
 int run_planned(Handle& h, void* stream, G&& graph) {
     QA_TRY(plan(h.device, static_cast<hipStream_t>(stream), h.ctx, h.ws, graph));
     return graph();
+}
+
+// The real pass of a planned call whose graph may launch the persistent LSTM recurrence (lstm.hip): every launch_lstm of a model graph.  Such
+// a call waits for its stream before returning and, should one of that kernel's grid barriers have timed out (it needs every workgroup
+// resident at once: the device was shared with another such kernel), runs the graph again on the per-step kernels - the call that hit the
+// failure returns valid results, and the device stops choosing the persistent kernel by itself.  A graph whose recurrences are all
+// launch_lstm_carry (the stream steps) or that has none uses only per-step kernels and needs no ticket: run_planned.
+template <typename F>
+int run_graph_checked(Handle* h, F&& graph) {
+    Ctx& c = h->ctx;
+    void* ticket = nullptr;
+    QA_TRY(lstm_call_begin(h->device, &ticket));
+    {
+        const int st = graph();
+        if (st != QA_OK) {  // error path only: the aggregator side stream may still run out of the workspace
+            (void)hipDeviceSynchronize();
+            bool ignored = false;
+            (void)lstm_call_end(ticket, c.stream, &ignored);
+            return st;
+        }
+    }
+    bool failed = false;
+    QA_TRY(lstm_call_end(ticket, c.stream, &failed));  // host-synchronous only for a call that launched an in-launch recurrence
+    if (!failed) return QA_OK;
+    std::fprintf(stderr, "libquarkaudio_hip: the grid barrier of the persistent LSTM recurrence timed out on device %d (shared device?); "
+                         "re-running the call on the per-step kernels\n", h->device);
+    lstm_force_per_step(true);
+    arm(c, h->ws);
+    const int st = graph();
+    lstm_force_per_step(false);
+    return st;
 }
 
 // qa_*_destroy: wait for the handle's work on its device, then free it
