@@ -184,6 +184,28 @@ int qa_hcodec_stream_end(qa_hcodec* h);
 int64_t qa_hcodec_stream_offset(const qa_hcodec* h);
 int qa_hcodec_stream_geometry(const qa_hcodec_spec* spec, int64_t* samples_per_frame, int64_t* first_min_frames, int32_t* ctx, int32_t cap,
                               int32_t* n_ctx);
+/* Per-row lengths, offsets and resets in one step: the rows of a stream need not start, step or end together.
+ * Between two of its resets (or begin and its first reset) the concatenated outputs of a row over the steps in which it had frames equal
+ * what one offline causal qa_hcodec_encode of that row's own concatenated waveform gives, whatever the other rows did meanwhile.
+ *   qa_hcodec_stream_encode_rows  as qa_hcodec_stream_encode, row b consuming only its first frames[b] code frames of the rectangle wav
+ *                            [B, n_samples]; frames is HOST memory, int64 [B], 0 <= frames[b] <= n = n_samples / 640, 0: the row idles -
+ *                            its state and offset stay as they are, bit for bit.  Samples behind a row's frames are never read (they may be
+ *                            non-finite).  Outputs in the rectangular layouts: behind a row's frames acoustic_codes hold -1 (the dropped
+ *                            code, as qa_hcodec_encode_ragged writes it) and emb holds exact zeros; emb, where given, must be 16-byte
+ *                            aligned (those zeros are written as float4; checked, refused otherwise).  When every row sits at one offset and
+ *                            frames[b] == n for all b the step IS qa_hcodec_stream_encode: same launches, same bits.
+ *   qa_hcodec_stream_reset_rows  the named rows (HOST int64 [n_rows], distinct, 0 .. B - 1) back to offset 0: their next step with frames
+ *                            is a first step (reflect fill, LSTM state zeroed, earlier K / V rows invisible); all other rows continue.
+ *   qa_hcodec_stream_offsets out [B] (host): the code frames of every row since begin / its reset.  qa_hcodec_stream_offset returns the
+ *                            largest of them - the one offset of a stream that only uses the calls above.
+ * qa_hcodec_stream_encode on a stream whose rows sit at different offsets gives every row all n frames at its own offset.
+ * Refused before anything is launched, state and every offset untouched: frames[b] outside 0 .. n; a row at offset 0 with 0 < frames[b] <
+ * first_min_frames (let it idle until enough is buffered); offset[b] + frames[b] > max_frames for any row (the message names it); every
+ * row idle; a row index out of range or named twice; a stream under capture; a handle that does not stream. */
+int qa_hcodec_stream_encode_rows(qa_hcodec* h, const float* wav, int64_t n_samples, const int64_t* frames, int64_t* acoustic_codes, float* emb,
+                                 void* stream);
+int qa_hcodec_stream_reset_rows(qa_hcodec* h, const int64_t* rows, int64_t n_rows);
+int qa_hcodec_stream_offsets(const qa_hcodec* h, int64_t* out);
 
 /* H-Codec 1.5 (spec.adaptive != 0): Codec.encode / Codec.decode of QuarkAudio-HCodec/HCodec-1.5/vq/codec_adaptive.py:150-199.
  * The number of groups G is data dependent (the reference syncs the host too: modeling_flexicodec_new.py:910), so
@@ -385,6 +407,17 @@ int qa_debug_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, flo
  * state_out must be different buffers: for n < ctx the next state takes rows of the current one. */
 int qa_debug_stream_window(const float* state_in, const float* chunk, float* win, float* state_out, int B, int ctx, int n, int C, int first,
                            void* stream);
+/* The same with per-row lengths (tests): n_rows_dev / first_dev are DEVICE int [B].  Item b holds n_b = n_rows_dev[b]
+ * (0 .. n) live chunk rows and takes the reflected head iff first_dev[b] != 0 (which needs n_b > ctx), else state_in (not NULL here).  Its
+ * window is head | its n_b chunk rows | 0.0f - chunk rows behind n_b are never read - and state_out[b] is window rows n_b .. n_b + ctx - 1;
+ * n_b = 0 copies state_in[b].  state_in == state_out is refused. */
+int qa_debug_stream_window_rows(const float* state_in, const float* chunk, float* win, float* state_out, int B, int ctx, int n, int C,
+                                const int* n_rows_dev, const int* first_dev, void* stream);
+/* qa_debug_lstm_carry with per-row step counts (tests): nq_dev / zero_dev are DEVICE int [B].  Row b runs its first
+ * nq_dev[b] (0 .. T) steps, from a zero state where zero_dev[b] != 0, and carries the state behind its own last step; a row with
+ * nq_dev[b] = 0 and zero_dev[b] = 0 keeps its (h, c) bit for bit.  h_out rows behind a row's steps are unspecified (finite scratch). */
+int qa_debug_lstm_carry_rows(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
+                             const int* nq_dev, const int* zero_dev, void* stream);
 /* Attention launches the host has issued in this process so far, by arithmetic (tests): out2[0] the fp32 chain (QA_ATT_MATH = 0, and
  * every launch of a UniSE LM handle), out2[1] split-6.  Counted where the host launches: a launch recorded into a captured graph counts
  * once, at capture, and its replays do not count. */
@@ -528,6 +561,17 @@ int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, flo
 int qa_transformer_stream_reset(qa_transformer* h);
 int qa_transformer_stream_end(qa_transformer* h);
 int64_t qa_transformer_stream_offset(const qa_transformer* h);
+/* Per-row lengths, offsets and resets, the block-level twin of qa_hcodec_stream_encode_rows in Transformer frames:
+ * row b consumes its first frames[b] (HOST int64 [B], 0 .. n) rows of x [B, n, d] at its own offset; x behind them is never read, y there
+ * is exact zeros (x and y 16-byte aligned: checked); an idle row keeps its state and offset.  _reset_rows: the named rows (HOST, distinct) back to offset 0, their LSTM state
+ * zeroed by their next step; _offsets: out [B] (host); _offset returns the largest.  Rows that move together with frames[b] == n take the
+ * launches of qa_transformer_stream_step.  Refused before any launch, everything untouched: frames[b] outside 0 .. n, offset[b] + frames[b]
+ * > capacity (the row is named), every row idle, a row index out of range or repeated, a stream under capture, and - with left_context > 0 -
+ * a ragged step that does not fit the short-chunk attention (more than 16 frames, QA_TR_SHORT_ATTN = 0, or over 256 query rows under
+ * QA_TR_SHORT_ATTN = 1): the long-chunk attention has its per-item form without a window only. */
+int qa_transformer_stream_step_rows(qa_transformer* h, const float* x, int64_t n, const int64_t* frames, float* y, void* stream);
+int qa_transformer_stream_reset_rows(qa_transformer* h, const int64_t* rows, int64_t n_rows);
+int qa_transformer_stream_offsets(const qa_transformer* h, int64_t* out);
 
 /* ---- BiCodec detokenizer ------------------------------------------------------------------------
  * BiCodec.detokenize(semantic_tokens, global_tokens) (QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199), the stage

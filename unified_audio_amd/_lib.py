@@ -137,6 +137,9 @@ SYMBOLS = {
     "qa_hcodec_stream_reset": (C.c_int, [C.c_void_p]),
     "qa_hcodec_stream_end": (C.c_int, [C.c_void_p]),
     "qa_hcodec_stream_offset": (C.c_int64, [C.c_void_p]),
+    "qa_hcodec_stream_encode_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qa_hcodec_stream_reset_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]),
+    "qa_hcodec_stream_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "qa_hcodec_stream_geometry": (C.c_int, [C.POINTER(qa_hcodec_spec), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                             C.c_int32, C.POINTER(C.c_int32)]),
     "qa_debug_stream_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -215,6 +218,13 @@ SYMBOLS = {
     "qa_transformer_stream_reset": (C.c_int, [C.c_void_p]),
     "qa_transformer_stream_end": (C.c_int, [C.c_void_p]),
     "qa_transformer_stream_offset": (C.c_int64, [C.c_void_p]),
+    "qa_transformer_stream_step_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "qa_transformer_stream_reset_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]),
+    "qa_transformer_stream_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "qa_debug_stream_window_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "qa_debug_lstm_carry_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "qa_debug_lstm_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "qa_ssl_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(qa_ssl_spec), C.POINTER(qa_tensor), C.c_int64, C.c_int]),
     "qa_ssl_destroy": (None, [C.c_void_p]),

@@ -79,6 +79,7 @@ struct TrStream {
     int B = 0, cap = 0;
     bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
     DeviceFloats mem;
+    DeviceInts ints{4};       // a step with per-row lengths: RowStep's four vectors, written once per step
     std::vector<float*> kc, vc, hs, cs;
     void release() {  // not streaming any more (the caller has set the device)
         mem.release();
@@ -111,6 +112,28 @@ struct TrStream {
     }
 };
 
+// What a step with per-row lengths carries to its kernels: per row the count in the caller's unit (code frames of
+// the H-Codec stream, frames of a Transformer stream), whether the row starts a sequence in this step, and its Transformer position and
+// query count.  Host vectors checked before any launch; dev[] are their device copies in TrStream::ints (upload), in that order.
+struct RowStep {
+    std::vector<int> cnt, first, pos0, nq;
+    const int* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int max_keys = 0;  // max_b(pos0[b] + nq[b]): the split count of the short attention, the key walk of the long one
+    // off: the rows' offsets, cnt already set; tr_rate Transformer frames per unit of cnt
+    void fill(const std::vector<int>& off, int tr_rate) {
+        const size_t B = off.size();
+        first.resize(B); pos0.resize(B); nq.resize(B);
+        max_keys = 0;
+        for (size_t b = 0; b < B; ++b) {
+            first[b] = off[b] == 0 && cnt[b] > 0;
+            pos0[b] = tr_rate * off[b];
+            nq[b] = tr_rate * cnt[b];
+            max_keys = std::max(max_keys, pos0[b] + nq[b]);
+        }
+    }
+    int upload(DeviceInts& ints, hipStream_t s) { return ints.upload({&cnt, &first, &pos0, &nq}, s, dev); }
+};
+
 // One stateful convolution of the streaming SEANet encoder: its carried context, the last `ctx` rows [B, ctx, C]
 // of its own input buffer.  Two buffers, alternated by the host: a step reads st[cur] and writes st[cur ^ 1] (stream_conv.hip)
 struct StreamConv {
@@ -119,8 +142,12 @@ struct StreamConv {
 };
 // The streaming state of a causal H-Codec 1.0 encoder: B > 0 between qa_hcodec_stream_begin and _end
 struct CodecStream {
-    int B = 0, cap = 0, offset = 0;  // capacity and offset in CODE frames
-    bool first = true;               // the next step is a first step: reflect fill, LSTM state zeroed
+    int B = 0, cap = 0;              // capacity in CODE frames
+    std::vector<int> off;            // [B] code frames of every row since begin / its reset; a row at 0 takes a first step next: reflect
+                                     // fill, LSTM state zeroed, earlier K / V rows invisible
+    const RowStep* rows = nullptr;   // the running step has per-row lengths (set around its graph only); null: every row moves together
+    int offset() const { return off.empty() ? 0 : *std::max_element(off.begin(), off.end()); }
+    bool first() const { return offset() == 0; }  // of a step in which every row moves together
     int cur = 0;                     // which of the two state buffers of every convolution holds the current state
     int first_min = 0;               // the fewest code frames a first chunk may have (stream_geometry)
     DeviceFloats conv_mem;
@@ -225,9 +252,10 @@ struct qa_mimi : Handle {
 struct qa_transformer : Handle {
     qa_transformer_spec spec{};
     TransformerW w;
-    // streaming state (st.B > 0: between qa_transformer_stream_begin and _end); `offset` frames seen since begin / reset
+    // streaming state (st.B > 0: between qa_transformer_stream_begin and _end); off[b] frames of row b seen since begin / its reset
     TrStream st;
-    int offset = 0;
+    std::vector<int> off;
+    int offset() const { return off.empty() ? 0 : *std::max_element(off.begin(), off.end()); }
 };
 // past_key_values of Transformer.forward(x, past_key_values, use_cache=True): per layer the roped K and V rows [B, cap, d] in fp32
 struct qa_transformer_cache {
@@ -410,7 +438,19 @@ struct TrChunk {
     // zero, as the reference's does on every call (transformer.py:133)
     float* const* hs = nullptr;
     float* const* cs = nullptr;
+    // a streaming step with per-row lengths: device int [B] each, all or none - item b sits at row_pos0[b] with
+    // row_nq[b] of the t.T frames, and starts from a zero LSTM state where row_zero[b] != 0; max_keys = max_b(row_pos0[b] + row_nq[b]).
+    // pos0 is then unused.  Null: every item at pos0 with all t.T frames, today's launches
+    const int *row_pos0 = nullptr, *row_nq = nullptr, *row_zero = nullptr;
+    int max_keys = 0;
 };
+
+// Whether a carried causal chunk of N frames x B rows takes the split-key kernel (stream_attn.hip): QA_TR_SHORT_ATTN 0 never, 1 up to 256
+// query rows per head, 2 every chunk of <= ATTN_SHORT_MAX_Q frames.  One rule for transformer_op and for the checks in front of a step
+inline bool tr_short_chunk(int B, int N) {
+    const long long mode = knob(K_TR_SHORT_ATTN);
+    return N <= ATTN_SHORT_MAX_Q && (mode == 2 || (mode == 1 && (int64_t)B * N <= 256));
+}
 
 // In place on x [t.B, t.T, d].  Ragged calls (non-causal): only the attention looks past a clip's end - the LSTM runs forward, everything
 // else is row-wise - so the lengths become one [B, N] key-padding mask, built once per call, for the KMASK form.
@@ -435,15 +475,23 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
     // a stream step of a few frames over a long history: the split-key kernel (stream_attn.hip), 1.0 - 1.5 x the step through
     // attention_kernel up to 256 query rows per head and 0.92 - 1.01 x at 512 (B = 32 x 16 frames: its partial records outweigh the
     // parallelism it adds; profiles/transformer_stream_bench.jsonl).  QA_TR_SHORT_ATTN: 0 never, 2 every chunk of <= 16 frames
-    const long long short_mode = knob(K_TR_SHORT_ATTN);
-    const bool short_chunk = carried && t.causal && N <= ATTN_SHORT_MAX_Q && (short_mode == 2 || (short_mode == 1 && rows <= 256));
+    const bool short_chunk = carried && t.causal && tr_short_chunk(B, N);
     float* part = short_chunk ? c.arena.alloc<float>(attn_short_part_floats(B, H, hd, N, ch->cap)) : nullptr;
     AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
     at.causal = t.causal ? 1 : 0;
     at.context = t.causal ? left_context : 0;
+    const bool ragged = ch && ch->row_nq;
     if (ch) {  // keys and values: rows 0 .. pos0 + N - 1 of the layer's caches
         at.ldkv = d; at.kv_batch_stride = (long long)ch->cap * d;
-        at.n_keys = ch->pos0 + N;
+        at.n_keys = ragged ? ch->max_keys : ch->pos0 + N;
+    }
+    if (ragged) {
+        QA_REQUIRE(carried && t.causal && ch->row_pos0 && ch->row_zero && ch->max_keys >= 1 && ch->max_keys <= ch->cap,
+                   "transformer: per-row lengths exist for the streaming step of a causal Transformer");
+        // the chunk form of attention_kernel with per-item counts is its fp32 form without a window (section 34); attention_op keeps it
+        // (the entry point has refused this on the host, in front of its first launch, with the words a caller needs)
+        QA_REQUIRE(short_chunk || at.context == 0, "transformer: per-row lengths under a sliding window need the short-chunk attention");
+        at.row_pos0 = ch->row_pos0; at.row_nq = ch->row_nq;
     }
     if (t.rl.n) {
         QA_REQUIRE(!t.causal && !ch, "transformer: per-clip lengths exist for the non-causal offline graph only");
@@ -462,18 +510,19 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
         if (taps) lp = tap_prefix + ".layers." + std::to_string(l);
         QA_TRY(rmsnorm_op(c, x, L.ln1, hn, rows, d, 1e-6f));
         QA_TRY(linear_op(c, hn, rows, L.ih, big));
-        if (carried) QA_RUN(c, launch_lstm_carry(big, L.w_hh, hl, ch->hs[l], ch->cs[l], B, N, d, c.stream));
+        if (carried) QA_RUN(c, launch_lstm_carry(big, L.w_hh, hl, ch->hs[l], ch->cs[l], B, N, d, c.stream, ch->row_nq, ch->row_zero));
         else QA_RUN(c, launch_lstm(big, L.w_hh, hl, cst, B, N, d, c.stream));
         tap(".self_attn.rnn", hl);
         QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
         if (ch) {
-            QA_RUN(c, launch_rope_append(qkv, tw.rope, ch->kc[l], ch->vc[l], B, N, H, hd, ch->pos0, ch->cap, c.stream));
+            QA_RUN(c, launch_rope_append(qkv, tw.rope, ch->kc[l], ch->vc[l], B, N, H, hd, ch->pos0, ch->cap, c.stream, ch->row_pos0, ch->row_nq));
             at.k = ch->kc[l]; at.v = ch->vc[l];
         } else {
             QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
         }
         if (short_chunk) {
-            QA_RUN(c, launch_attention_short(qkv, 3 * d, at.k, at.v, att, part, B, N, H, hd, ch->pos0, ch->cap, at.context, c.stream));
+            QA_RUN(c, launch_attention_short(qkv, 3 * d, at.k, at.v, att, part, B, N, H, hd, ch->pos0, ch->cap, at.context, c.stream, ch->row_pos0,
+                                             ch->row_nq, ch->max_keys));
         } else {
             QA_TRY(attention_op(c, at));
         }
@@ -491,11 +540,17 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
 }
 
 // the step of a streaming state at `pos0` frames: the K / V rows and the carried LSTM state of `st`
-TrChunk stream_chunk(const TrStream& st, int pos0) {
+// rows: the step has per-row lengths (uploaded); pos0 is then unused
+TrChunk stream_chunk(const TrStream& st, int pos0, const RowStep* rows = nullptr) {
     TrChunk ch;
     ch.kc = st.kc.data(); ch.vc = st.vc.data();
     ch.cap = st.cap; ch.pos0 = pos0;
     ch.hs = st.hs.data(); ch.cs = st.cs.data();
+    if (rows) {
+        ch.pos0 = 0;
+        ch.row_zero = rows->dev[1]; ch.row_pos0 = rows->dev[2]; ch.row_nq = rows->dev[3];
+        ch.max_keys = rows->max_keys;
+    }
     return ch;
 }
 
@@ -728,7 +783,9 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float*
 // below) and the front: a step takes the unfused launches, as a ragged call does - the fused front stages whole halo tiles with a reflect
 // rule of its own (a carried-halo form of it is not built) - and has neither lengths nor taps.  The 1x1 shortcut and the 1x1 behind the k3
 // are row-wise and carry nothing.  The Transformer continues over its carried (h, c) and K / V rows at 2 frames per code frame.  A step
-// reads st->cur / first / offset, which the caller advances behind a successful step.
+// reads st->cur / off / rows, which the caller advances behind a successful step.  With st->rows (a step with per-row lengths, section 45)
+// every window holds zeros behind a row's own frames, so whatever the caller's waveform holds there never enters the ladder; the launches
+// between the windows run on the rectangle.
 int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float** emb_out, int* n50_out, int* n25_out,
                    CodecStream* st = nullptr) {
     const qa_hcodec_spec& sp = h->spec;
@@ -737,6 +794,7 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
     int C = sp.n_filters;
     TimeAxis t = tw;
     size_t ci = 0;
+    const int code_frames = st ? tw.T / h->geom.samples : 0;
     // stream: the window [B, ctx + L, C] of the next stateful convolution over chunk [B, L, C], assembled from its carried state (first
     // step: the reflection of the chunk) and the chunk; conv_op has no batch stride for x, so the window is a buffer of its own.  The state
     // of a convolution is the raw rows of its own input buffer, before any prologue ELU; for the down convs those rows hold the fused
@@ -745,7 +803,10 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
         QA_REQUIRE(ci < st->convs.size() && st->convs[ci].C == Cw, "stream: convolution %zu of the ladder has no state of %d channels", ci, Cw);
         const StreamConv& sc = st->convs[ci++];
         *win = c.arena.alloc<float>((size_t)B * (sc.ctx + L) * Cw);
-        QA_RUN(c, launch_stream_window(sc.st[st->cur], chunk, *win, sc.st[st->cur ^ 1], B, sc.ctx, L, Cw, st->first ? 1 : 0, c.stream));
+        // per-row lengths: the row's live rows of this buffer are its code frames times the buffer's rows per code frame
+        const RowStep* rs = st->rows;
+        QA_RUN(c, launch_stream_window(sc.st[st->cur], chunk, *win, sc.st[st->cur ^ 1], B, sc.ctx, L, Cw, st->first() ? 1 : 0, c.stream,
+                                       rs ? ClipLens{rs->dev[0], L / code_frames} : ClipLens(), rs ? rs->dev[1] : nullptr));
         return QA_OK;
     };
     // SConv1d(k = w.ksize, stride) over x [B, ta.T, w.C_in] -> *y [B, *T_out, w.N] (*y null: an arena buffer); o: prologue and epilogue.
@@ -817,7 +878,7 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
     }
     QA_REQUIRE(C == sp.dimension, "encoder: channel ladder ends at %d, spec.dimension is %d", C, sp.dimension);
     QA_REQUIRE(!st || t.T * h->geom.samples == 2 * tw.T, "stream: the ladder ends at %d frames for a step of %d samples", t.T, tw.T);
-    const TrChunk ch = st ? stream_chunk(st->tr, 2 * st->offset) : TrChunk();
+    const TrChunk ch = st ? stream_chunk(st->tr, 2 * st->offset(), st->rows) : TrChunk();
     QA_TRY(transformer_op(c, h->enc_tr, x, t, taps ? "encoder.model." + std::to_string(3 * sp.n_ratios + 2) : std::string(), 0, st ? &ch : nullptr));
     if (taps) c.tap("enc.transformer", x, t.rows() * C);
     ConvOpt eo;
@@ -884,11 +945,15 @@ int stream_encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int n, long long
     float* emb = emb_out ? emb_out : c.arena.alloc<float>((size_t)B * n * sp.code_dim);
     int n50 = 0, n25 = 0;
     QA_TRY(seanet_encoder(h, c, wav, TimeAxis{B, n * h->geom.samples, true, ClipLens()}, &emb, &n50, &n25, h->strm.get()));
+    // per-row lengths: exact zeros behind a row's frames in emb (in front of the search, which then sees finite rows it would see anyway),
+    // and the dropped code -1 there, as a ragged encode writes them
+    const RowStep* rs = h->strm->rows;
+    if (rs) QA_RUN(c, launch_lm_rows_zero_pad(emb, 0, 1, B, n, sp.code_dim, rs->dev[0], c.stream));
     if (!ac_out) return QA_OK;
     long long* ia = c.arena.alloc<long long>((size_t)B * n * Q);
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * n, sp.codebook_size, sp.code_dim));
     QA_RUN(c, launch_rvq_search(emb, (long long)B * n, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0, rvq_ws, c.stream));
-    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, n, Q, c.stream));
+    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, n, Q, c.stream, rs ? rs->dev[0] : nullptr));
     return QA_OK;
 }
 
@@ -1694,48 +1759,128 @@ int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
         }
     QA_TRY(st->tr.begin(h->enc_tr, B, 2 * max_frames));
     st->B = (int)B;
+    st->off.assign((size_t)B, 0);
     st->cap = (int)max_frames;
     st->first_min = g.first_min;
     h->strm = std::move(st);
     return QA_OK;
 }
 
-int qa_hcodec_stream_encode(qa_hcodec* h, const float* wav, int64_t n_samples, int64_t* acoustic_codes, float* emb, void* stream) {
-    QA_REQUIRE(h, "qa_hcodec_stream_encode: null handle");
-    QA_REQUIRE(h->strm, "qa_hcodec_stream_encode: not streaming (call qa_hcodec_stream_begin first)");
-    QA_REQUIRE(wav && (acoustic_codes || emb), "qa_hcodec_stream_encode: null wav, or neither acoustic_codes nor emb asked for");
+// One step of the stream; frames null: every row takes all n code frames (qa_hcodec_stream_encode).  Every refusal comes before any launch
+// and leaves the state and all offsets as they were.  When every row sits at one offset and takes all n frames the step is the
+// rectangular one - no row arrays, today's launches, today's bits - whichever entry point it came through.
+static int stream_encode_call(qa_hcodec* h, const char* fn, const float* wav, int64_t n_samples, const int64_t* frames, int64_t* acoustic_codes,
+                              float* emb, void* stream) {
+    QA_REQUIRE(h, "%s: null handle", fn);
+    QA_REQUIRE(h->strm, "%s: not streaming (call qa_hcodec_stream_begin first)", fn);
+    QA_REQUIRE(wav && (acoustic_codes || emb), "%s: null wav, or neither acoustic_codes nor emb asked for", fn);
     CodecStream& st = *h->strm;
     const int hop = h->geom.samples;
-    // every refusal comes before any launch and leaves the state and the offset as they were
-    QA_REQUIRE(n_samples > 0 && n_samples % hop == 0, "qa_hcodec_stream_encode: a step of %lld samples; it must be a positive multiple of the "
-               "%d samples of a code frame (zero-pad a trailing partial frame, as HCodecTokenizer.pad_wav does)", (long long)n_samples, hop);
+    QA_REQUIRE(n_samples > 0 && n_samples % hop == 0, "%s: a step of %lld samples; it must be a positive multiple of the "
+               "%d samples of a code frame (zero-pad a trailing partial frame, as HCodecTokenizer.pad_wav does)", fn, (long long)n_samples, hop);
     const int64_t n = n_samples / hop;
-    QA_REQUIRE(st.B * n_samples < (1LL << 31), "qa_hcodec_stream_encode: a step of %d x %lld samples is too large", st.B, (long long)n_samples);
-    QA_REQUIRE(!st.first || n >= st.first_min, "qa_hcodec_stream_encode: the first chunk of a stream has %lld code frames, it needs at least %d "
-               "(%d samples): its left padding is the reflection of its own frames, which a shorter chunk cannot fill the way the offline "
-               "encoder does - buffer %d frames before the first step", (long long)n, st.first_min, st.first_min * hop, st.first_min);
-    QA_REQUIRE((int64_t)st.offset + n <= st.cap, "qa_hcodec_stream_encode: %d streamed + %lld new code frames exceed the capacity %d of this "
-               "stream (max_frames of qa_hcodec_stream_begin, at most %d); begin a longer stream or reset this one", st.offset, (long long)n,
-               st.cap, MAX_POS / 2);
+    QA_REQUIRE(st.B * n_samples < (1LL << 31), "%s: a step of %d x %lld samples is too large", fn, st.B, (long long)n_samples);
+    RowStep rs;
+    bool full = true;
+    if (frames) {
+        const int64_t bad = check_row_lengths(frames, st.B, 0, n, &rs.cnt, &full);
+        QA_REQUIRE(bad < 0, "%s: frames[%lld] = %lld is outside 0 .. %lld, the code frames of this step's rectangle (0: the row idles) - pass a "
+                   "wider rectangle or fewer frames", fn, (long long)bad, (long long)frames[bad], (long long)n);
+    } else {
+        rs.cnt.assign((size_t)st.B, (int)n);
+    }
+    bool together = full;
+    for (int b = 1; b < st.B; ++b) together = together && st.off[b] == st.off[0];
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_hcodec_stream_encode", s, CACHE_IS_HOST_STATE));
-    QA_HIP(hipSetDevice(h->device));
-    if (st.first) st.tr.zero_state = true;
-    QA_TRY(st.tr.zero_if_new(h->enc_tr.d, s));
     Ctx& c = h->ctx;
-    QA_TRY(run_planned(*h, stream, [&] { return stream_encode_graph(h, c, wav, (int)n, (long long*)acoustic_codes, emb); }));
-    st.offset += (int)n;
-    st.first = false;
+    if (together) {
+        QA_REQUIRE(!st.first() || n >= st.first_min, "%s: the first chunk of a stream has %lld code frames, it needs at least %d "
+                   "(%d samples): its left padding is the reflection of its own frames, which a shorter chunk cannot fill the way the offline "
+                   "encoder does - buffer %d frames before the first step", fn, (long long)n, st.first_min, st.first_min * hop, st.first_min);
+        QA_REQUIRE((int64_t)st.offset() + n <= st.cap, "%s: %d streamed + %lld new code frames exceed the capacity %d of this "
+                   "stream (max_frames of qa_hcodec_stream_begin, at most %d); begin a longer stream or reset this one", fn, st.offset(),
+                   (long long)n, st.cap, MAX_POS / 2);
+        QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
+        QA_HIP(hipSetDevice(h->device));
+        if (st.first()) st.tr.zero_state = true;
+        QA_TRY(st.tr.zero_if_new(h->enc_tr.d, s));
+        QA_TRY(run_planned(*h, stream, [&] { return stream_encode_graph(h, c, wav, (int)n, (long long*)acoustic_codes, emb); }));
+    } else {
+        int live = 0;
+        for (int b = 0; b < st.B; ++b) {
+            const int f = rs.cnt[b];
+            live += f > 0;
+            QA_REQUIRE(!(st.off[b] == 0 && f > 0 && f < st.first_min), "%s: row %d starts its stream with %d code frames, a first chunk needs at "
+                       "least %d (%d samples): its left padding is the reflection of its own frames - let the row idle (frames = 0) until %d "
+                       "frames are buffered", fn, b, f, st.first_min, st.first_min * hop, st.first_min);
+            QA_REQUIRE((int64_t)st.off[b] + f <= st.cap, "%s: row %d has %d streamed + %d new code frames, beyond the capacity %d of this stream "
+                       "(max_frames of qa_hcodec_stream_begin, at most %d); reset that row (qa_hcodec_stream_reset_rows) or begin a longer stream",
+                       fn, b, st.off[b], f, st.cap, MAX_POS / 2);
+        }
+        QA_REQUIRE(live > 0, "%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
+        QA_REQUIRE(!emb || ((reinterpret_cast<uintptr_t>(emb) & 15) == 0 && h->spec.code_dim % 4 == 0),
+                   "%s: emb must be 16-byte aligned (and code_dim a multiple of 4) in a step with per-row lengths: the rows behind a "
+                   "length are written as float4", fn);
+        QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
+        QA_HIP(hipSetDevice(h->device));
+        rs.fill(st.off, 2);
+        QA_TRY(rs.upload(st.tr.ints, s));
+        st.rows = &rs;
+        const int rc = run_planned(*h, stream, [&] { return stream_encode_graph(h, c, wav, (int)n, (long long*)acoustic_codes, emb); });
+        st.rows = nullptr;
+        QA_TRY(rc);
+        st.tr.zero_state = false;  // the rows that started were zeroed by the step's own kernel
+    }
+    for (int b = 0; b < st.B; ++b) st.off[b] += rs.cnt[b];
     st.cur ^= 1;
     return QA_OK;
+}
+
+int qa_hcodec_stream_encode(qa_hcodec* h, const float* wav, int64_t n_samples, int64_t* acoustic_codes, float* emb, void* stream) {
+    return stream_encode_call(h, "qa_hcodec_stream_encode", wav, n_samples, nullptr, acoustic_codes, emb, stream);
+}
+
+int qa_hcodec_stream_encode_rows(qa_hcodec* h, const float* wav, int64_t n_samples, const int64_t* frames, int64_t* acoustic_codes, float* emb,
+                                 void* stream) {
+    QA_REQUIRE(h, "qa_hcodec_stream_encode_rows: null handle");
+    QA_REQUIRE(frames, "qa_hcodec_stream_encode_rows: null frames (qa_hcodec_stream_encode is the call without per-row lengths)");
+    return stream_encode_call(h, "qa_hcodec_stream_encode_rows", wav, n_samples, frames, acoustic_codes, emb, stream);
 }
 
 int qa_hcodec_stream_reset(qa_hcodec* h) {
     QA_REQUIRE(h && h->strm, "qa_hcodec_stream_reset: not streaming (call qa_hcodec_stream_begin first)");
     // the next step is a first step again: reflect fill instead of the convolutions' states, (h, c) zeroed in stream order, and the K / V
     // rows stay and become invisible (no step reads a row at or behind its own key count)
-    h->strm->offset = 0;
-    h->strm->first = true;
+    std::fill(h->strm->off.begin(), h->strm->off.end(), 0);
+    return QA_OK;
+}
+
+// the named rows of a stream of B rows back to offset 0; an index out of range or named twice is refused and nothing changes
+static int stream_reset_rows(const char* fn, const int64_t* rows, int64_t n_rows, std::vector<int>* off) {
+    const int64_t B = (int64_t)off->size();
+    QA_REQUIRE(rows && n_rows >= 1 && n_rows <= B, "%s: %lld rows to reset of a stream of %lld (1 .. %lld distinct row indices)", fn,
+               (long long)n_rows, (long long)B, (long long)B);
+    std::vector<char> seen((size_t)B, 0);
+    for (int64_t i = 0; i < n_rows; ++i) {
+        QA_REQUIRE(rows[i] >= 0 && rows[i] < B, "%s: rows[%lld] = %lld is outside 0 .. %lld, the rows of this stream", fn, (long long)i,
+                   (long long)rows[i], (long long)B - 1);
+        QA_REQUIRE(!seen[(size_t)rows[i]], "%s: row %lld is named twice - name every row to reset once", fn, (long long)rows[i]);
+        seen[(size_t)rows[i]] = 1;
+    }
+    for (int64_t i = 0; i < n_rows; ++i) (*off)[(size_t)rows[i]] = 0;
+    return QA_OK;
+}
+
+int qa_hcodec_stream_reset_rows(qa_hcodec* h, const int64_t* rows, int64_t n_rows) {
+    QA_REQUIRE(h && h->strm, "qa_hcodec_stream_reset_rows: not streaming (call qa_hcodec_stream_begin first)");
+    // host state alone: a row at offset 0 takes a first step next - reflect fill, (h, c) zeroed by that step, its K / V rows invisible
+    return stream_reset_rows("qa_hcodec_stream_reset_rows", rows, n_rows, &h->strm->off);
+}
+
+int qa_hcodec_stream_offsets(const qa_hcodec* h, int64_t* out) {
+    QA_REQUIRE(h && h->strm, "qa_hcodec_stream_offsets: not streaming (call qa_hcodec_stream_begin first)");
+    QA_REQUIRE(out, "qa_hcodec_stream_offsets: null out");
+    for (size_t b = 0; b < h->strm->off.size(); ++b) out[b] = h->strm->off[b];
     return QA_OK;
 }
 
@@ -1746,7 +1891,7 @@ int qa_hcodec_stream_end(qa_hcodec* h) {
     return QA_OK;
 }
 
-int64_t qa_hcodec_stream_offset(const qa_hcodec* h) { return (h && h->strm) ? h->strm->offset : -1; }
+int64_t qa_hcodec_stream_offset(const qa_hcodec* h) { return (h && h->strm) ? h->strm->offset() : -1; }
 
 // The per-clip H-Codec 1.5 calls serve the non-causal model only: a causal aggregator or bottleneck attends by position, and their
 // attention takes no key-padding mask.
@@ -2096,8 +2241,13 @@ static int transformer_check_io(const char* fn, const qa_transformer* h, const f
 static int transformer_run(qa_transformer* h, const float* x, int B, int n, float* y, void* stream, const TrChunk* ch) {
     Ctx& c = h->ctx;
     auto graph = [&]() -> int {
-        if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, c.stream));
-        return transformer_op(c, h->w, y, TimeAxis{B, n, h->spec.causal != 0, ClipLens()}, "", h->spec.left_context, ch);
+        // per-row lengths: x behind a row's frames is never read (zeros enter instead), and y there is written as exact zeros
+        const int* row_nq = ch ? ch->row_nq : nullptr;
+        if (row_nq) QA_RUN(c, launch_lm_rows_masked_copy(y, x, B, n, h->w.d, row_nq, c.stream));
+        else if (!c.dry) QA_HIP(hipMemcpyAsync(y, x, sizeof(float) * B * n * h->w.d, hipMemcpyDeviceToDevice, c.stream));
+        QA_TRY(transformer_op(c, h->w, y, TimeAxis{B, n, h->spec.causal != 0, ClipLens()}, "", h->spec.left_context, ch));
+        if (row_nq) QA_RUN(c, launch_lm_rows_zero_pad(y, 0, 1, B, n, h->w.d, row_nq, c.stream));
+        return QA_OK;
     };
     // a stream step carries its LSTM state through the per-step kernels alone; every other call's launch_lstm may be the persistent kernel
     // and needs the ticket of run_graph_checked
@@ -2171,30 +2321,98 @@ int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) 
     QA_REQUIRE(B > 0 && B < (1 << 20) && capacity >= 1 && capacity <= MAX_POS, "qa_transformer_stream_begin: batch %lld, capacity %lld (1 .. %d)",
                (long long)B, (long long)capacity, MAX_POS);
     QA_HIP(hipSetDevice(h->device));
-    h->offset = 0;
-    return h->st.begin(h->w, B, capacity);  // in place of the state of a handle that is already streaming
+    h->off.clear();
+    QA_TRY(h->st.begin(h->w, B, capacity));  // in place of the state of a handle that is already streaming
+    h->off.assign((size_t)B, 0);
+    return QA_OK;
+}
+
+// One step; frames null: every row takes all n frames (qa_transformer_stream_step).  Refusals come before any launch and leave the state
+// and all offsets as they were; rows that move together with all n frames take the rectangular step whichever entry point they came through
+static int transformer_stream_call(qa_transformer* h, const char* fn, const float* x, int64_t n, const int64_t* frames, float* y, void* stream) {
+    QA_REQUIRE(h && h->st.B > 0, "%s: not streaming (call qa_transformer_stream_begin)", fn);
+    QA_TRY(transformer_check_io(fn, h, x, y, h->st.B, n));
+    const int B = h->st.B;
+    RowStep rs;
+    bool full = true;
+    if (frames) {
+        const int64_t bad = check_row_lengths(frames, B, 0, n, &rs.cnt, &full);
+        QA_REQUIRE(bad < 0, "%s: frames[%lld] = %lld is outside 0 .. %lld, the frames of this step's rectangle (0: the row idles) - pass a wider "
+                   "rectangle or fewer frames", fn, (long long)bad, (long long)frames[bad], (long long)n);
+    } else {
+        rs.cnt.assign((size_t)B, (int)n);
+    }
+    bool together = full;
+    for (int b = 1; b < B; ++b) together = together && h->off[b] == h->off[0];
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (together) {
+        QA_REQUIRE((int64_t)h->offset() + n <= h->st.cap, "%s: %d streamed + %lld new frames exceed the capacity %d of "
+                   "this stream (max_frames)", fn, h->offset(), (long long)n, h->st.cap);
+        QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
+        QA_HIP(hipSetDevice(h->device));
+        if (h->offset() == 0) h->st.zero_state = true;
+        QA_TRY(h->st.zero_if_new(h->w.d, s));
+        const TrChunk ch = stream_chunk(h->st, h->offset());
+        QA_TRY(transformer_run(h, x, B, (int)n, y, stream, &ch));
+    } else {
+        int live = 0;
+        for (int b = 0; b < B; ++b) {
+            live += rs.cnt[b] > 0;
+            QA_REQUIRE((int64_t)h->off[b] + rs.cnt[b] <= h->st.cap, "%s: row %d has %d streamed + %d new frames, beyond the capacity %d of this "
+                       "stream (max_frames); reset that row (qa_transformer_stream_reset_rows) or begin a longer stream", fn, b, h->off[b],
+                       rs.cnt[b], h->st.cap);
+        }
+        QA_REQUIRE(live > 0, "%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
+        // the long-chunk attention has its per-item form without a window only (attention.hip, section 34): nothing else runs in its place
+        if (h->spec.left_context > 0 && !tr_short_chunk(B, (int)n)) {
+            const long long mode = knob(K_TR_SHORT_ATTN);
+            const char* why = n > ATTN_SHORT_MAX_Q ? "this step has more frames" : mode == 0 ? "QA_TR_SHORT_ATTN = 0 turns that kernel off"
+                                                                                            : "QA_TR_SHORT_ATTN = 1 stops at 256 query rows";
+            set_error("%s: a step with per-row lengths under a sliding window (left_context = %d) runs on the short-chunk attention alone (at "
+                      "most %d frames per step) and %s; this step has %lld frames x %d rows - step fewer frames, set QA_TR_SHORT_ATTN = 2, or "
+                      "move the rows together", fn, h->spec.left_context, ATTN_SHORT_MAX_Q, why, (long long)n, B);
+            return QA_ERR_UNSUPPORTED;
+        }
+        QA_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0,
+                   "%s: x and y must be 16-byte aligned in a step with per-row lengths (the rows behind a length are written as float4)", fn);
+        QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
+        QA_HIP(hipSetDevice(h->device));
+        rs.fill(h->off, 1);
+        QA_TRY(rs.upload(h->st.ints, s));
+        const TrChunk ch = stream_chunk(h->st, 0, &rs);
+        QA_TRY(transformer_run(h, x, B, (int)n, y, stream, &ch));
+        h->st.zero_state = false;  // the rows that started were zeroed by the step's own kernel
+    }
+    for (int b = 0; b < B; ++b) h->off[b] += rs.cnt[b];
+    return QA_OK;
 }
 
 int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, float* y, void* stream) {
-    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_step: not streaming (call qa_transformer_stream_begin)");
-    QA_TRY(transformer_check_io("qa_transformer_stream_step", h, x, y, h->st.B, n));
-    // refused before any launch: the state stays as it was
-    QA_REQUIRE((int64_t)h->offset + n <= h->st.cap, "qa_transformer_stream_step: %d streamed + %lld new frames exceed the capacity %d of "
-               "this stream (max_frames)", h->offset, (long long)n, h->st.cap);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    QA_TRY(refuse_capture("qa_transformer_stream_step", s, CACHE_IS_HOST_STATE));
-    QA_HIP(hipSetDevice(h->device));
-    QA_TRY(h->st.zero_if_new(h->w.d, s));
-    const TrChunk ch = stream_chunk(h->st, h->offset);
-    QA_TRY(transformer_run(h, x, h->st.B, (int)n, y, stream, &ch));
-    h->offset += (int)n;
-    return QA_OK;
+    return transformer_stream_call(h, "qa_transformer_stream_step", x, n, nullptr, y, stream);
+}
+
+int qa_transformer_stream_step_rows(qa_transformer* h, const float* x, int64_t n, const int64_t* frames, float* y, void* stream) {
+    QA_REQUIRE(h, "qa_transformer_stream_step_rows: null handle");
+    QA_REQUIRE(frames, "qa_transformer_stream_step_rows: null frames (qa_transformer_stream_step is the call without per-row lengths)");
+    return transformer_stream_call(h, "qa_transformer_stream_step_rows", x, n, frames, y, stream);
 }
 
 int qa_transformer_stream_reset(qa_transformer* h) {
     QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_reset: not streaming");
-    h->offset = 0;  // the cached rows stay and become invisible: no step reads a row at or behind offset + n
+    std::fill(h->off.begin(), h->off.end(), 0);  // the cached rows stay and become invisible: no step reads a row at or behind offset + n
     h->st.zero_state = true;
+    return QA_OK;
+}
+
+int qa_transformer_stream_reset_rows(qa_transformer* h, const int64_t* rows, int64_t n_rows) {
+    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_reset_rows: not streaming (call qa_transformer_stream_begin)");
+    return stream_reset_rows("qa_transformer_stream_reset_rows", rows, n_rows, &h->off);
+}
+
+int qa_transformer_stream_offsets(const qa_transformer* h, int64_t* out) {
+    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_offsets: not streaming (call qa_transformer_stream_begin)");
+    QA_REQUIRE(out, "qa_transformer_stream_offsets: null out");
+    for (size_t b = 0; b < h->off.size(); ++b) out[b] = h->off[b];
     return QA_OK;
 }
 
@@ -2202,10 +2420,10 @@ int qa_transformer_stream_end(qa_transformer* h) {
     QA_REQUIRE(h, "qa_transformer_stream_end: null handle");
     (void)hipSetDevice(h->device);
     h->st.release();
-    h->offset = 0;
+    h->off.clear();
     return QA_OK;
 }
 
-int64_t qa_transformer_stream_offset(const qa_transformer* h) { return (h && h->st.B > 0) ? h->offset : -1; }
+int64_t qa_transformer_stream_offset(const qa_transformer* h) { return (h && h->st.B > 0) ? h->offset() : -1; }
 
 }  // extern "C"

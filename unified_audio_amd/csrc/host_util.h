@@ -455,7 +455,7 @@ inline int rope_op(Ctx& c, float* qkv, const float* cos_sin, int B, int N, int H
 }
 inline int attention_op(Ctx& c, AttnArgs a) {
     if (c.dry) return QA_OK;
-    a.math_fp32 = c.att_fp32;
+    a.math_fp32 = c.att_fp32 || a.row_nq != nullptr;  // the chunk form with per-item counts exists in the fp32 form alone (section 34)
     return launch_attention(a, c.stream);
 }
 

@@ -30,8 +30,10 @@ int launch_conv_in_window(const float* x, const float* w_kc, const float* bias, 
 // stream_conv.hip: the window of a causal convolution in a stream and its next state, one launch.  win [B, ctx + n, C] = head | chunk
 // [B, n, C], the head being state_in [B, ctx, C] or, on the first step (n > ctx), the reflection of the chunk (position -1 - j reads frame
 // 1 + j); state_out [B, ctx, C] = the window's last ctx rows.  state_in and state_out are different buffers (n < ctx: they overlap in time)
+// rows.n / first_rows (device int [B], both or neither): item b holds rows.n[b] * rows.mul <= n live chunk rows and
+// is a first step iff first_rows[b] != 0; zeros behind its rows in the window, its next state ends at its own last row, `first` is unused
 int launch_stream_window(const float* state_in, const float* chunk, float* win, float* state_out, int B, int ctx, int n, int C, int first,
-                         hipStream_t s);
+                         hipStream_t s, ClipLens rows = ClipLens(), const int* first_rows = nullptr);
 // seanet_front.hip: conv0 + SEANetResnetBlock + the ELU in front of the strided conv, one launch, `a` written once
 bool seanet_front_supported(int C, int hid, int L);
 int launch_seanet_front(const float* wav, const float* w0, const float* b0, const float* w3, const float* b3, const float* wsc,
@@ -136,16 +138,22 @@ int launch_ring_append(const float* k, const float* v, long long ld, float* kc, 
 // stream_attn.hip : what a chunk of a linear (non-ring) K/V cache needs beside launch_attention
 // Rotate-half RoPE of q (in place) and k of a packed projection qkv [B n, 3 d] at positions pos0 + t (table cs [.][hd / 2][2]); the
 // roped k and v rows go to rows pos0 .. pos0 + n - 1 of the caches kc / vc [B, cap, d].  pos0 + n <= cap is the caller's check
-int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s);
+// row_pos0 / row_nq (device int [B], both or neither): item b's rows sit at row_pos0[b] + t and only its first
+// row_nq[b] are rotated and appended; the others write nothing.  row_pos0[b] + row_nq[b] <= cap is the caller's check
+int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s,
+                       const int* row_pos0 = nullptr, const int* row_nq = nullptr);
 // Causal attention of a short chunk (n <= ATTN_SHORT_MAX_Q queries at positions pos0 + i) over such a cache, keys 0 .. pos0 + n - 1 under
 // the window `context` (0 = none), fp32 arithmetic.  A (row, head) is split over workgroups that own the FIXED key ranges
 // [s L, (s + 1) L), L = attn_short_split_keys(cap): a key lands in the same split, tile and lane whatever pos0 is.  Partial records
 // [n, hd | m | l] per split in `part` (attn_short_part_floats), merged in split order by a second launch.  q [B n, ldq], out [B n, d]
+// row_pos0 / row_nq as in launch_rope_append, max_keys = max_b(row_pos0[b] + row_nq[b]) from the host: the split count of the grid.  Item
+// b attends over its own row_pos0[b] + row_nq[b] keys; its queries behind row_nq[b] are written as 0; pos0 is then unused
 constexpr int ATTN_SHORT_MAX_Q = 16;
 int attn_short_split_keys(int cap);
 size_t attn_short_part_floats(int B, int H, int hd, int n, int cap);
 int launch_attention_short(const float* q, long long ldq, const float* kc, const float* vc, float* out, float* part, int B, int n, int H,
-                           int hd, int pos0, int cap, int context, hipStream_t s);
+                           int hd, int pos0, int cap, int context, hipStream_t s, const int* row_pos0 = nullptr, const int* row_nq = nullptr,
+                           int max_keys = 0);
 
 // lstm.hip : one nn.LSTM layer (batch_first, zero initial state) given the precomputed input projection
 //   xw [B, T, 4d] = x W_ih^T + b_ih + b_hh with the 4d axis permuted to (unit, gate) order,
@@ -156,8 +164,10 @@ int launch_lstm(const float* xw, const float* w_hh_ug, float* h_out, float* c_st
                 hipStream_t s, bool eager = false);
 // One chunk of a recurrence that continues (the streaming Transformer): step 0 starts from h_state / c_state [B, d], which hold the
 // state behind step T - 1 on return.  Per-step kernels only, launched eagerly on `s`; h_out [B, T, d] as in launch_lstm
+// nq / zero (device int [B], both or neither): row b runs its first nq[b] <= T steps - from zero where zero[b] != 0 -
+// and carries the state behind step nq[b] - 1; nq[b] = 0 leaves the row's (h, c) untouched
 int launch_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
-                      hipStream_t s);
+                      hipStream_t s, const int* nq = nullptr, const int* zero = nullptr);
 // persistent-recurrence bookkeeping for the model graphs: launches so far on `dev`; wait for `s` and report (and clear) a barrier
 // time-out; make this thread's next launch_lstm calls take the per-step kernels
 int lstm_call_begin(int dev, void** ticket);                  // open a model-graph call: own error word + launch count (thread-local)

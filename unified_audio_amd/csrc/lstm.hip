@@ -44,10 +44,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // h_state [B, d] and reads c_state instead of starting from zero.  h_state is only READ here: every workgroup reads all of h_{t-1} but
 // writes 4 units of h_t, so a step must never update the buffer it reads (the launcher moves row T - 1 of h_out into h_state behind
 // the last step).  c_state is read and written by the same lane and stays in place.
-template <int MT, int NI, bool CARRY = false>
+// ROWS (CARRY only; a chunk with per-row lengths): batch row b has nq[b] <= T live steps.  At a step t >= nq[b] the
+// row keeps its c_state - the cell state of its own last live step, or the carried one for nq[b] = 0; its h_out row is still written
+// (the rectangle's scratch: finite, never read by a live row, never carried).  The other instances keep their code.
+template <int MT, int NI, bool CARRY = false, bool ROWS = false>
 __global__ __launch_bounds__(512) void lstm_step_kernel(const float* __restrict__ xw, const float* __restrict__ w_hh,
                                                         float* __restrict__ h_out, float* __restrict__ c_state, int B,
-                                                        int T, int d, int t, const float* __restrict__ h_state = nullptr) {
+                                                        int T, int d, int t, const float* __restrict__ h_state = nullptr,
+                                                        const int* __restrict__ nq = nullptr) {
     __shared__ float part[8][MT][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.x * 16;  // first permuted gate row of this workgroup
@@ -130,15 +134,15 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const float* __restrict_
         const float ig = sigmoid_f(g4[0]), fg = sigmoid_f(g4[1]), gg = tanhf(g4[2]), og = sigmoid_f(g4[3]);
         const long long ci = (long long)b * d + unit;
         const float c_new = fg * c_prev + ig * gg;
-        c_state[ci] = c_new;
+        if (!ROWS || t < nq[b]) c_state[ci] = c_new;
         h_out[((long long)b * T + t) * d + unit] = og * tanhf(c_new);
     }
 }
 
-template <int MT, bool CARRY = false>
+template <int MT, bool CARRY = false, bool ROWS = false>
 static void launch_step(int ni, dim3 grid, hipStream_t s, const float* xw, const float* w, float* h, float* c, int bn, int T, int d, int t,
-                        const float* h_state = nullptr) {
-#define QA_LS(NI) hipLaunchKernelGGL((lstm_step_kernel<MT, NI, CARRY>), grid, dim3(512), 0, s, xw, w, h, c, bn, T, d, t, h_state)
+                        const float* h_state = nullptr, const int* nq = nullptr) {
+#define QA_LS(NI) hipLaunchKernelGGL((lstm_step_kernel<MT, NI, CARRY, ROWS>), grid, dim3(512), 0, s, xw, w, h, c, bn, T, d, t, h_state, nq)
     switch (ni) {
         case 1: QA_LS(1); break;
         case 2: QA_LS(2); break;
@@ -153,28 +157,48 @@ static void launch_step(int ni, dim3 grid, hipStream_t s, const float* xw, const
 
 // One chain of T dependent step launches for batch rows [0, bn) of the given buffers; CARRY: continuing from the carried state
 // (h_state_b, c_b) of those rows
-template <bool CARRY = false>
+template <bool CARRY = false, bool ROWS = false>
 static void lstm_chain(const float* xw_b, const float* w_hh_ug, float* h_b, float* c_b, int bn, int T, int d, int t, hipStream_t s,
-                       const float* h_state_b = nullptr) {
+                       const float* h_state_b = nullptr, const int* nq_b = nullptr) {
     const int ni = (d % 128 == 0) ? d / 128 : 0;
     const int mt = (int)ceil_div(bn, 16);
     const dim3 grid(d / 4);
     switch (mt) {
-        case 1: launch_step<1, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
-        case 2: launch_step<2, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
-        case 3: launch_step<3, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
-        default: launch_step<4, CARRY>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b); break;
+        case 1: launch_step<1, CARRY, ROWS>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b, nq_b); break;
+        case 2: launch_step<2, CARRY, ROWS>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b, nq_b); break;
+        case 3: launch_step<3, CARRY, ROWS>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b, nq_b); break;
+        default: launch_step<4, CARRY, ROWS>(ni, grid, s, xw_b, w_hh_ug, h_b, c_b, bn, T, d, t, h_state_b, nq_b); break;
     }
 }
 
 // h_state [B, d] <- h_out [B, T, d] row T - 1: the carried hidden state moves behind the last step of a chunk, never under a step
-__global__ __launch_bounds__(256) void lstm_state_copy_kernel(const float* __restrict__ h_out, float* __restrict__ h_state, int B, int T, int d) {
+// nq (device int [B]) or null: row b moves its own last live row nq[b] - 1 and nothing for nq[b] = 0
+__global__ __launch_bounds__(256) void lstm_state_copy_kernel(const float* __restrict__ h_out, float* __restrict__ h_state, int B, int T, int d,
+                                                              const int* __restrict__ nq) {
     const int d4 = d >> 2;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * d4) return;
     const long long b = gid / d4;
     const int c = (int)(gid - b * d4) * 4;
-    *reinterpret_cast<float4*>(h_state + b * d + c) = *reinterpret_cast<const float4*>(h_out + (b * T + (T - 1)) * d + c);
+    int last = T - 1;
+    if (nq) {
+        last = min(nq[b], T) - 1;
+        if (last < 0) return;
+    }
+    *reinterpret_cast<float4*>(h_state + b * d + c) = *reinterpret_cast<const float4*>(h_out + (b * T + last) * d + c);
+}
+
+// (h, c) [B, d] <- 0 for the rows with zero[b] != 0, in stream order in front of step 0: the rows of a chunk that start a sequence
+__global__ __launch_bounds__(256) void lstm_state_zero_rows_kernel(float* __restrict__ h_state, float* __restrict__ c_state, int B, int d,
+                                                                   const int* __restrict__ zero) {
+    const int d4 = d >> 2;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * d4) return;
+    const long long b = gid / d4;
+    if (zero[b] == 0) return;
+    const int c = (int)(gid - b * d4) * 4;
+    *reinterpret_cast<float4*>(h_state + b * d + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(c_state + b * d + c) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // The step chains of a call: batches above 64 rows as consecutive chains of 64 (MT <= 4).  (r02: two concurrent half-batch chains on two
@@ -785,17 +809,31 @@ void lstm_force_per_step(bool on) { t_lstm_per_step = on; }
 
 // The recurrence of one streaming chunk: T eager per-step launches from (h_state, c_state), then the state move.  The in-launch
 // recurrences have no carried form (they need the whole device resident and cannot amortise their register load over a few frames).
-int launch_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d, hipStream_t s) {
+// nq / zero (device int [B], both or neither): row b runs its first nq[b] <= T steps from its carried state - from zero
+// where zero[b] != 0 - and carries the state behind its own last step; nq[b] = 0 leaves (h, c) of the row as they are.
+int launch_lstm_carry(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d, hipStream_t s,
+                      const int* nq, const int* zero) {
     QA_REQUIRE(d % 128 == 0, "lstm: hidden size %d must be a multiple of 128", d);
     QA_REQUIRE(B >= 1 && T >= 1, "lstm: a carried chunk of %d rows x %d steps", B, T);
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int bn = std::min(64, B - b0);
-        for (int t = 0; t < T; ++t)
-            lstm_chain<true>(xw + (long long)b0 * T * 4 * d, w_hh_ug, h_out + (long long)b0 * T * d, c_state + (long long)b0 * d, bn, T, d, t, s,
-                             h_state + (long long)b0 * d);
+    QA_REQUIRE((nq == nullptr) == (zero == nullptr), "lstm: the rows' step counts and zero flags come together");
+    const dim3 sgrid((unsigned)ceil_div((long long)B * (d / 4), 256));
+    if (nq) {
+        hipLaunchKernelGGL(lstm_state_zero_rows_kernel, sgrid, dim3(256), 0, s, h_state, c_state, B, d, zero);
         QA_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(lstm_state_copy_kernel, dim3((unsigned)ceil_div((long long)B * (d / 4), 256)), dim3(256), 0, s, h_out, h_state, B, T, d);
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int bn = std::min(64, B - b0);
+        for (int t = 0; t < T; ++t) {
+            if (nq)
+                lstm_chain<true, true>(xw + (long long)b0 * T * 4 * d, w_hh_ug, h_out + (long long)b0 * T * d, c_state + (long long)b0 * d, bn, T,
+                                       d, t, s, h_state + (long long)b0 * d, nq + b0);
+            else
+                lstm_chain<true>(xw + (long long)b0 * T * 4 * d, w_hh_ug, h_out + (long long)b0 * T * d, c_state + (long long)b0 * d, bn, T, d, t,
+                                 s, h_state + (long long)b0 * d);
+        }
+        QA_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lstm_state_copy_kernel, sgrid, dim3(256), 0, s, h_out, h_state, B, T, d, nq);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -916,4 +954,13 @@ extern "C" int qa_debug_lstm_carry(const float* xw, const float* w_hh_ug, float*
                                    void* stream) {
     QA_REQUIRE(xw && w_hh_ug && h_out && h_state && c_state && B >= 1 && T >= 1 && d >= 1, "qa_debug_lstm_carry: bad argument");
     return qa::launch_lstm_carry(xw, w_hh_ug, h_out, h_state, c_state, B, T, d, static_cast<hipStream_t>(stream));
+}
+
+// test hook: as qa_debug_lstm_carry with per-row step counts (launch_lstm_carry's nq / zero, device int [B]): row b runs its first
+// nq_dev[b] of the T steps, from zero where zero_dev[b] != 0; a row with nq_dev[b] = 0 keeps its (h, c)
+extern "C" int qa_debug_lstm_carry_rows(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T,
+                                        int d, const int* nq_dev, const int* zero_dev, void* stream) {
+    QA_REQUIRE(xw && w_hh_ug && h_out && h_state && c_state && nq_dev && zero_dev && B >= 1 && T >= 1 && d >= 1,
+               "qa_debug_lstm_carry_rows: bad argument");
+    return qa::launch_lstm_carry(xw, w_hh_ug, h_out, h_state, c_state, B, T, d, static_cast<hipStream_t>(stream), nq_dev, zero_dev);
 }

@@ -20,8 +20,13 @@ namespace qa {
 
 // ------------------------------------------------------------------------------------------------ RoPE + append
 // one thread: one (row, head, pair i < hd / 2) - the rotate-half pairs (i, i + hd / 2) of q and k, and the same two elements of v
+// ROWS: item b's t-th row sits at position row_pos0[b] + t and only its first row_nq[b] rows exist - the others
+// touch neither q nor the caches, so no row of a cache is written that a later step of that item has not yet replaced, and none at or
+// behind `cap` (the host has checked row_pos0[b] + row_nq[b] <= cap)
+template <bool ROWS>
 __global__ __launch_bounds__(256) void rope_append_kernel(float* __restrict__ qkv, const float* __restrict__ cs, float* __restrict__ kc,
-                                                          float* __restrict__ vc, int B, int n, int H, int hd, int pos0, int cap) {
+                                                          float* __restrict__ vc, int B, int n, int H, int hd, int pos0, int cap,
+                                                          const int* __restrict__ row_pos0, const int* __restrict__ row_nq) {
     const int half = hd >> 1;
     const long long total = (long long)B * n * H * half;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -29,7 +34,13 @@ __global__ __launch_bounds__(256) void rope_append_kernel(float* __restrict__ qk
     const int i = (int)(gid % half);
     const int h = (int)((gid / half) % H);
     const long long row = gid / ((long long)half * H);
-    const int b = (int)(row / n), pos = pos0 + (int)(row - (long long)b * n);
+    const int b = (int)(row / n);
+    const int ti = (int)(row - (long long)b * n);
+    if (ROWS) {
+        pos0 = row_pos0[b];
+        if (ti >= row_nq[b] || pos0 < 0 || pos0 + ti >= cap) return;
+    }
+    const int pos = pos0 + ti;
     const float c = cs[((long long)pos * half + i) * 2], s = cs[((long long)pos * half + i) * 2 + 1];
     const int d = H * hd;
     float* q = qkv + row * 3 * d + h * hd;
@@ -46,11 +57,15 @@ __global__ __launch_bounds__(256) void rope_append_kernel(float* __restrict__ qk
     vc[dst + i + half] = v[i + half];
 }
 
-int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s) {
-    QA_REQUIRE(B >= 1 && n >= 1 && H >= 1 && hd >= 2 && hd % 2 == 0 && pos0 >= 0 && (long long)pos0 + n <= cap,
+int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s,
+                       const int* row_pos0, const int* row_nq) {
+    QA_REQUIRE((row_pos0 == nullptr) == (row_nq == nullptr), "rope_append: per-row positions and counts come together");
+    QA_REQUIRE(B >= 1 && n >= 1 && H >= 1 && hd >= 2 && hd % 2 == 0 && pos0 >= 0 && (row_nq || (long long)pos0 + n <= cap),
                "rope_append: rows %d .. %d of a cache of %d rows", pos0, pos0 + n - 1, cap);
     const long long total = (long long)B * n * H * (hd / 2);
-    hipLaunchKernelGGL(rope_append_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0, cap);
+    const dim3 grid((unsigned)ceil_div(total, 256));
+    if (row_nq) hipLaunchKernelGGL(rope_append_kernel<true>, grid, dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, 0, cap, row_pos0, row_nq);
+    else hipLaunchKernelGGL(rope_append_kernel<false>, grid, dim3(256), 0, s, qkv, cs, kc, vc, B, n, H, hd, pos0, cap, row_pos0, row_nq);
     QA_LAUNCH_CHECK();
     return QA_OK;
 }
@@ -66,10 +81,15 @@ __host__ __device__ constexpr int as_rec(int hd) { return hd + 4; }  // floats o
 // key `key` of the tile for queries 4 w + half and 4 w + 2 + half; the softmax statistics are reduced over the 32 lanes of a half.
 // PV phase: thread (q = tid >> 4, ct = tid & 15) owns the float4 columns ct and ct + 16 of query q - the same four queries per wave,
 // so a wave without a live query (4 w >= n) skips both phases of every tile.
-template <int HD>
+// ROWS: item b = blockIdx.z - workgroup-uniform, two scalar loads - sits at pos0 = row_pos0[b] with nq = row_nq[b]
+// live queries of the n query slots of the layout; n_keys = pos0 + nq.  The grid's split count comes from the longest item, so a split
+// wholly behind THIS item's keys (every split when n_keys = 0) leaves through the identity-record exit in front of the first barrier.
+// Dead queries are never loaded (zeros in sQ) and the merge writes them as 0 without reading a record.
+template <int HD, bool ROWS>
 __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ kc,
                                                          const float* __restrict__ vc, float* __restrict__ part, int n, int pos0, int cap,
-                                                         int context, int split_keys, float qscale) {
+                                                         int context, int split_keys, float qscale, const int* __restrict__ row_pos0,
+                                                         const int* __restrict__ row_nq) {
     constexpr int LDK = HD + 4;   // K / V rows an odd number of 16-byte slots apart: the ds_read_b128 of 32 keys covers all banks
     constexpr int C4 = HD / 4;    // float4 columns of a head
     constexpr int NLD = HD / 32;  // float4 per thread per operand and tile: 32 keys x HD floats over 256 threads
@@ -84,12 +104,17 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int sp = blockIdx.x, ns = gridDim.x, head = blockIdx.y, H = gridDim.y, b = blockIdx.z;
     const int d = H * HD;
-    const int n_keys = pos0 + n;
+    int nq = n;  // live queries of this item; n stays the row count of the q / record / out layouts
+    if (ROWS) {
+        pos0 = max(row_pos0[b], 0);
+        nq = min(max(row_nq[b], 0), min(n, cap - pos0));
+    }
+    const int n_keys = pos0 + nq;
     // keys some query of the chunk can see, cut to this split's range
     const int lo = context > 0 ? max(0, pos0 - context + 1) : 0;
     const int k_begin = max(sp * split_keys, lo), k_end = min((sp + 1) * split_keys, n_keys);
     float* rec = part + (((long long)(b * H + head) * ns + sp) * n) * RS;
-    if (k_begin >= k_end) {  // workgroup-uniform, before the first barrier: the identity record
+    if (k_begin >= k_end || (ROWS && nq == 0)) {  // workgroup-uniform, before the first barrier: the identity record
         for (int i = tid; i < n * RS; i += 256) rec[i] = (i % RS == HD) ? -INFINITY : 0.f;
         return;
     }
@@ -98,7 +123,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
     for (int f = tid; f < AS_Q * C4; f += 256) {
         const int qi = f / C4, c4 = f - qi * C4;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (qi < n) v = *reinterpret_cast<const f32x4*>(q + ((long long)b * n + qi) * ldq + head * HD + 4 * c4) * qscale;
+        if (qi < nq) v = *reinterpret_cast<const f32x4*>(q + ((long long)b * n + qi) * ldq + head * HD + 4 * c4) * qscale;
         *reinterpret_cast<f32x4*>(&sQ[qi][4 * c4]) = v;
     }
 
@@ -118,7 +143,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
         }
     };
 
-    const bool live = 4 * wave < n;  // wave-uniform
+    const bool live = 4 * wave < nq;  // wave-uniform
     const int key_l = lane & 31, hh = lane >> 5;
     const int qs[2] = {4 * wave + hh, 4 * wave + 2 + hh};
     float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
@@ -157,7 +182,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int p = pos0 + qs[e];  // the query's position; key <= p implies key < n_keys
-                const bool ok = qs[e] < n && key <= p && (context <= 0 || p - key < context);
+                const bool ok = qs[e] < nq && key <= p && (context <= 0 || p - key < context);
                 const float sc = ok ? s[e] : -INFINITY;
                 float tmax = sc;
 #pragma unroll
@@ -192,7 +217,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
         }
     }
     if (live) {
-        if (pq < n) {
+        if (pq < nq) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const int col = ct + 16 * c;
@@ -202,7 +227,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
         if (key_l == 0) {
 #pragma unroll
             for (int e = 0; e < 2; ++e)
-                if (qs[e] < n) {
+                if (qs[e] < nq) {
                     rec[(long long)qs[e] * RS + HD] = m_run[e];
                     rec[(long long)qs[e] * RS + HD + 1] = l_run[e];
                 }
@@ -211,13 +236,20 @@ __global__ __launch_bounds__(256) void attn_short_kernel(const float* __restrict
 }
 
 // Grid (H, B), 256 threads: out[b, i, head, :] = sum_s o_s 2^(m_s - M) / sum_s l_s 2^(m_s - M), splits in order
-template <int HD>
-__global__ __launch_bounds__(256) void attn_short_merge_kernel(const float* __restrict__ part, float* __restrict__ out, int n, int ns) {
+// ROWS: the queries i >= row_nq[b] of item b are written as 0 and their records, which no split has written, are not read
+template <int HD, bool ROWS>
+__global__ __launch_bounds__(256) void attn_short_merge_kernel(const float* __restrict__ part, float* __restrict__ out, int n, int ns,
+                                                               const int* __restrict__ row_nq) {
     constexpr int RS = as_rec(HD);
     const int head = blockIdx.x, H = gridDim.x, b = blockIdx.y;
     const float* rec = part + ((long long)(b * H + head) * ns) * n * RS;
+    const int nq = ROWS ? row_nq[b] : n;
     for (int e = threadIdx.x; e < n * HD; e += 256) {
         const int i = e / HD, c = e - i * HD;
+        if (ROWS && i >= nq) {
+            out[((long long)b * n + i) * H * HD + head * HD + c] = 0.f;
+            continue;
+        }
         const float* r = rec + (long long)i * RS;
         float M = -INFINITY;
         for (int s = 0; s < ns; ++s) M = fmaxf(M, r[(long long)s * n * RS + HD]);
@@ -241,16 +273,27 @@ size_t attn_short_part_floats(int B, int H, int hd, int n, int cap) {
 }
 
 int launch_attention_short(const float* q, long long ldq, const float* kc, const float* vc, float* out, float* part, int B, int n, int H,
-                           int hd, int pos0, int cap, int context, hipStream_t s) {
-    QA_REQUIRE(B >= 1 && H >= 1 && n >= 1 && n <= ATTN_SHORT_MAX_Q && pos0 >= 0 && (long long)pos0 + n <= cap && context >= 0 && ldq % 4 == 0,
+                           int hd, int pos0, int cap, int context, hipStream_t s, const int* row_pos0, const int* row_nq, int max_keys) {
+    QA_REQUIRE((row_pos0 == nullptr) == (row_nq == nullptr) && (!row_nq || (max_keys >= 1 && max_keys <= cap)),
+               "attention_short: per-row positions and counts come together, with the key count of the longest row (1 .. %d)", cap);
+    if (row_nq) pos0 = max_keys - n;  // unused by the kernels; the split count below covers the longest row
+    QA_REQUIRE(B >= 1 && H >= 1 && n >= 1 && n <= ATTN_SHORT_MAX_Q && (row_nq || (pos0 >= 0 && (long long)pos0 + n <= cap)) && context >= 0 &&
+                   ldq % 4 == 0,
                "attention_short: %d queries at offset %d of a cache of %d rows (at most %d queries)", n, pos0, cap, ATTN_SHORT_MAX_Q);
     const int L = attn_short_split_keys(cap), ns = (int)ceil_div(pos0 + n, L);
     constexpr float LOG2E = 1.4426950408889634f;
     const float qscale = LOG2E / std::sqrt((float)hd);
     const dim3 grid((unsigned)ns, (unsigned)H, (unsigned)B), mgrid((unsigned)H, (unsigned)B);
 #define QA_AS(HD_)                                                                                                                        \
-    hipLaunchKernelGGL(attn_short_kernel<HD_>, grid, dim3(256), 0, s, q, ldq, kc, vc, part, n, pos0, cap, context, L, qscale);           \
-    hipLaunchKernelGGL(attn_short_merge_kernel<HD_>, mgrid, dim3(256), 0, s, part, out, n, ns)
+    if (row_nq) {                                                                                                                         \
+        hipLaunchKernelGGL((attn_short_kernel<HD_, true>), grid, dim3(256), 0, s, q, ldq, kc, vc, part, n, 0, cap, context, L, qscale,    \
+                           row_pos0, row_nq);                                                                                             \
+        hipLaunchKernelGGL((attn_short_merge_kernel<HD_, true>), mgrid, dim3(256), 0, s, part, out, n, ns, row_nq);                       \
+    } else {                                                                                                                              \
+        hipLaunchKernelGGL((attn_short_kernel<HD_, false>), grid, dim3(256), 0, s, q, ldq, kc, vc, part, n, pos0, cap, context, L,        \
+                           qscale, row_pos0, row_nq);                                                                                     \
+        hipLaunchKernelGGL((attn_short_merge_kernel<HD_, false>), mgrid, dim3(256), 0, s, part, out, n, ns, row_nq);                      \
+    }
     switch (hd) {
         case 64: QA_AS(64); break;
         case 96: QA_AS(96); break;

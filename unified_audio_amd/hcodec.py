@@ -617,19 +617,37 @@ class Codec(torch.nn.Module):
         finally:
             self._stop_streaming()
 
-    def reset_streaming(self):
-        """Back to offset 0: the next `encode_stream` is a first step again (reflect fill, LSTM state zeroed, earlier K / V rows invisible)."""
+    @property
+    def streaming_offsets(self):
+        """The code frames of every row since `streaming()` / its own reset, a list of B ints (`streaming_offset` is the largest)."""
+        if not self.is_streaming:
+            raise _lib.QuarkAudioError(-1, "Codec.streaming_offsets: not streaming - call it inside `with codec.streaming(batch_size):`")
+        out = (C.c_int64 * self._streaming_batch)()
+        _lib.check(self._lib.qa_hcodec_stream_offsets(self._handle, out))
+        return [int(v) for v in out]
+
+    def reset_streaming(self, rows=None):
+        """Back to offset 0: the next `encode_stream` is a first step again (reflect fill, LSTM state zeroed, earlier K / V rows invisible).
+        `rows` (a list / tensor of distinct row indices): only those rows go back, all others continue."""
         self._require_loaded()
-        _lib.check(self._lib.qa_hcodec_stream_reset(self._handle))
+        if rows is None:
+            _lib.check(self._lib.qa_hcodec_stream_reset(self._handle))
+            return
+        vals = _int_list(rows, "rows")
+        _lib.check(self._lib.qa_hcodec_stream_reset_rows(self._handle, (C.c_int64 * max(len(vals), 1))(*vals), len(vals)))
 
     @torch.no_grad()
-    def encode_stream(self, x: torch.Tensor, return_emb: bool = False):
+    def encode_stream(self, x: torch.Tensor, return_emb: bool = False, lengths=None):
         """The next chunk of every row of a stream: x [B, 1, n] or [B, n] fp32 with n a positive multiple of the samples of a code frame
         (`spec.enc_hop`, 640) -> acoustic codes int64 [B, nq, n / hop], in the layout of `encode`'s first output; with `return_emb` also the
         embeddings in front of the quantizer, emb [B, n / hop, code_dim].  Concatenated over the steps, both equal what one offline causal
         `encode` of the concatenated waveform gives.  The first chunk needs at least `stream_first_min_frames` code frames.  A trailing
         partial frame is the caller's to zero-pad, as `HCodecTokenizer.pad_wav` does - and only at the END of a stream: zeros in the middle
-        are signal.  The semantic codes have no stream (their encoder is not causal and the SSL features are whole-utterance)."""
+        are signal.  The semantic codes have no stream (their encoder is not causal and the SSL features are whole-utterance).
+        `lengths`: a host list / tensor of B code-frame counts, row b consuming only its first lengths[b] frames of
+        the rectangle at ITS OWN offset; 0 lets the row idle (state and offset untouched), a row at offset 0 needs at least
+        `stream_first_min_frames`.  Samples behind a row's frames are never read; there the codes are -1 and emb is 0.  Each row's
+        outputs, concatenated over its steps between two of its resets, equal the offline causal `encode` of its own waveform."""
         if not self.is_streaming:
             raise _lib.QuarkAudioError(-1, "Codec.encode_stream: not streaming - call it inside `with codec.streaming(batch_size):` "
                                            "(or use encode for a whole utterance)")
@@ -646,8 +664,12 @@ class Codec(torch.nn.Module):
         ac = torch.empty((B, self.spec.num_quantizers, frames), dtype=torch.int64, device=self.device)
         emb = torch.empty((B, frames, self.spec.code_dim), dtype=torch.float32, device=self.device) if return_emb else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.qa_hcodec_stream_encode(self._handle, x.data_ptr(), n, ac.data_ptr(), emb.data_ptr() if return_emb else None,
-                                                         _stream_ptr(self.device)))
+            if lengths is None:
+                _lib.check(self._lib.qa_hcodec_stream_encode(self._handle, x.data_ptr(), n, ac.data_ptr(),
+                                                             emb.data_ptr() if return_emb else None, _stream_ptr(self.device)))
+            else:
+                _lib.check(self._lib.qa_hcodec_stream_encode_rows(self._handle, x.data_ptr(), n, _frames_arg(lengths, B), ac.data_ptr(),
+                                                                  emb.data_ptr() if return_emb else None, _stream_ptr(self.device)))
         return (ac, emb) if return_emb else ac
 
     def _adaptive_codes(self, acoustic_codes, semantic_codes, token_lengths, what: str):

@@ -18,6 +18,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
+from .hcodec import _frames_arg, _int_list
 
 MAX_FRAMES = 8192  # the library's RoPE table: the most frames a cache or a stream can hold
 
@@ -140,9 +141,23 @@ class Transformer(torch.nn.Module):
         finally:
             self._stop_streaming()
 
-    def reset_streaming(self):
+    def reset_streaming(self, rows=None):
+        """Back to offset 0.  `rows` (a list / tensor of distinct row indices): only those rows, all others continue."""
         self._require()
-        _lib.check(self._lib.qa_transformer_stream_reset(self._handle))
+        if rows is None:
+            _lib.check(self._lib.qa_transformer_stream_reset(self._handle))
+            return
+        vals = _int_list(rows, "rows")
+        _lib.check(self._lib.qa_transformer_stream_reset_rows(self._handle, (C.c_int64 * max(len(vals), 1))(*vals), len(vals)))
+
+    @property
+    def streaming_offsets(self):
+        """The frames of every row since `streaming()` / its own reset, a list of B ints (`streaming_offset` is the largest)."""
+        if not self.is_streaming:
+            raise _lib.QuarkAudioError(-1, "Transformer.streaming_offsets: not streaming")
+        out = (C.c_int64 * self._streaming_batch)()
+        _lib.check(self._lib.qa_transformer_stream_offsets(self._handle, out))
+        return [int(v) for v in out]
 
     @property
     def streaming_offset(self) -> int:
@@ -155,8 +170,13 @@ class Transformer(torch.nn.Module):
         return TransformerCache(self, batch_size, min(self.max_position_embeddings, MAX_FRAMES) if capacity is None else capacity)
 
     @torch.no_grad()
-    def forward(self, inputs_embeds: torch.Tensor, past_key_values: Optional[TransformerCache] = None, use_cache: Optional[bool] = None):
+    def forward(self, inputs_embeds: torch.Tensor, past_key_values: Optional[TransformerCache] = None, use_cache: Optional[bool] = None,
+                lengths=None):
+        """`lengths` (streaming only): a host list / tensor of B frame counts - row b consumes its first lengths[b]
+        frames of the rectangle at its own offset (0: the row idles); the output behind them is 0."""
         self._require()
+        if lengths is not None and not self.is_streaming:
+            raise _lib.QuarkAudioError(-1, "Transformer: lengths= belongs to a streaming step (inside streaming())")
         x = inputs_embeds
         if x.dim() != 3 or x.shape[-1] != self.hidden_size:
             raise _lib.QuarkAudioError(-1, f"Transformer expects [B, T, {self.hidden_size}], got {tuple(x.shape)}")
@@ -171,7 +191,11 @@ class Transformer(torch.nn.Module):
                                                    "use_cache belong to the non-streaming forward")
                 if B != self._streaming_batch:
                     raise _lib.QuarkAudioError(-1, f"streaming state was created for batch {self._streaming_batch}, got {B}")
-                _lib.check(self._lib.qa_transformer_stream_step(self._handle, x.data_ptr(), T, y.data_ptr(), stream))
+                if lengths is None:
+                    _lib.check(self._lib.qa_transformer_stream_step(self._handle, x.data_ptr(), T, y.data_ptr(), stream))
+                else:
+                    _lib.check(self._lib.qa_transformer_stream_step_rows(self._handle, x.data_ptr(), T, _frames_arg(lengths, B), y.data_ptr(),
+                                                                         stream))
                 return y
             if use_cache and past_key_values is None:  # transformer.py:456-457
                 past_key_values = self.new_cache(B)
