@@ -206,6 +206,17 @@ int qa_hcodec_stream_encode_rows(qa_hcodec* h, const float* wav, int64_t n_sampl
                                  void* stream);
 int qa_hcodec_stream_reset_rows(qa_hcodec* h, const int64_t* rows, int64_t n_rows);
 int qa_hcodec_stream_offsets(const qa_hcodec* h, int64_t* out);
+/* The same stream without an end: the encoder's Transformer under a sliding window of left_context TRANSFORMER
+ * frames (two per code frame), its K / V rows a ring (qa_transformer_stream_begin_ring).  The window is a property of the stream, not of
+ * the spec.  This is NOT the shipped full-causal encoder: it is the SEANet encoder whose Transformer was built with
+ * use_sliding_window=True, left_context=W, a parameter of the reference's block that vq/codec.py never sets; its embeddings and codes
+ * differ from the full-causal ones.  max_chunk_frames (code frames, at least the first-chunk minimum) is the most one step may take per
+ * row.  _encode, _encode_rows, _reset, _reset_rows, _offset(s) and _end are the calls above.  Refused before any launch: left_context
+ * < 1, a ring above 8192 rows, a chunk above max_chunk_frames, a row past 2^24 Transformer positions (2^23 code frames, about 93 hours),
+ * per-row lengths on a step of more than 8 code frames.  _capacity: the code frames the K / V rows hold (ring or linear), -1 when not
+ * streaming. */
+int qa_hcodec_stream_begin_ring(qa_hcodec* h, int64_t B, int32_t left_context, int64_t max_chunk_frames);
+int64_t qa_hcodec_stream_capacity(const qa_hcodec* h);
 
 /* H-Codec 1.5 (spec.adaptive != 0): Codec.encode / Codec.decode of QuarkAudio-HCodec/HCodec-1.5/vq/codec_adaptive.py:150-199.
  * The number of groups G is data dependent (the reference syncs the host too: modeling_flexicodec_new.py:910), so
@@ -418,6 +429,14 @@ int qa_debug_stream_window_rows(const float* state_in, const float* chunk, float
  * nq_dev[b] = 0 and zero_dev[b] = 0 keeps its (h, c) bit for bit.  h_out rows behind a row's steps are unspecified (finite scratch). */
 int qa_debug_lstm_carry_rows(const float* xw, const float* w_hh_ug, float* h_out, float* h_state, float* c_state, int B, int T, int d,
                              const int* nq_dev, const int* zero_dev, void* stream);
+/* One rope-append plus attention of a stream step over K / V caches [B, cap, H hd] the caller owns (tests; DESIGN.md sections 42, 46):
+ * qkv [B n, 3 H hd] (q is roped in place), out [B n, H hd], hd 64 / 96 / 128, window `context` (0: none).  Every item sits at pos0, or -
+ * row_pos0_dev / row_nq_dev, DEVICE int [B], both or neither - item b at row_pos0_dev[b] with its first row_nq_dev[b] frames.  ring != 0:
+ * the caches are rings (context >= 1, cap >= context - 1 + n, positions below 2^24), else linear (pos0 + n <= cap).  long_form != 0:
+ * attention_kernel in place of the short kernel (n <= 16) - rows moving together only; its ring mode needs cap >= context + n and
+ * every row of the ring finite.  The RoPE table and the partial records are the call's own; synchronous. */
+int qa_debug_stream_attn(float* qkv, float* kc, float* vc, float* out, int B, int n, int H, int hd, int cap, int context, int ring, int pos0,
+                         const int* row_pos0_dev, const int* row_nq_dev, int long_form, void* stream);
 /* Attention launches the host has issued in this process so far, by arithmetic (tests): out2[0] the fp32 chain (QA_ATT_MATH = 0, and
  * every launch of a UniSE LM handle), out2[1] split-6.  Counted where the host launches: a launch recorded into a captured graph counts
  * once, at capture, and its replays do not count. */
@@ -572,6 +591,17 @@ int64_t qa_transformer_stream_offset(const qa_transformer* h);
 int qa_transformer_stream_step_rows(qa_transformer* h, const float* x, int64_t n, const int64_t* frames, float* y, void* stream);
 int qa_transformer_stream_reset_rows(qa_transformer* h, const int64_t* rows, int64_t n_rows);
 int qa_transformer_stream_offsets(const qa_transformer* h, int64_t* out);
+/* A stream without an end: under a sliding window (causal, left_context = W > 0) the K / V rows are RINGS of
+ * qa_transformer_stream_capacity rows - the smallest multiple of 32 that is at least W + max_chunk - and position p sits in row p mod
+ * capacity.  _begin_ring replaces _begin (on a handle that already streams it frees the old stream); _step, _step_rows, _reset,
+ * _reset_rows, _offset(s) and _end are the calls above, unchanged.  A step takes at most max_chunk frames per row at any offset below
+ * 2^24 positions (a float holds those exactly); until the ring wraps, a step on the short-chunk attention gives the bits of a linear
+ * stream of the same capacity.  Positions at or beyond the 8192 of the static RoPE table take their angle from the table's own formula.
+ * Refused before any launch, state untouched, the message naming the value: a handle without a window, a capacity above 8192 rows, a
+ * chunk above max_chunk (the row is named), a row that would pass 2^24 positions, a stream under capture, per-row lengths on a chunk that
+ * does not fit the short-chunk attention.  _capacity: the rows of the cache of a ring or linear stream, -1 when not streaming. */
+int qa_transformer_stream_begin_ring(qa_transformer* h, int64_t B, int64_t max_chunk);
+int64_t qa_transformer_stream_capacity(const qa_transformer* h);
 
 /* ---- BiCodec detokenizer ------------------------------------------------------------------------
  * BiCodec.detokenize(semantic_tokens, global_tokens) (QuarkAudio-UniSE/model/bicodec/bicodec.py:182-199), the stage

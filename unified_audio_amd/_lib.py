@@ -221,6 +221,12 @@ SYMBOLS = {
     "qa_transformer_stream_step_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "qa_transformer_stream_reset_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]),
     "qa_transformer_stream_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "qa_transformer_stream_begin_ring": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "qa_transformer_stream_capacity": (C.c_int64, [C.c_void_p]),
+    "qa_hcodec_stream_begin_ring": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64]),
+    "qa_hcodec_stream_capacity": (C.c_int64, [C.c_void_p]),
+    "qa_debug_stream_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "qa_debug_stream_window_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "qa_debug_lstm_carry_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -8,6 +8,7 @@
 #include <memory>
 
 #include "host_util.h"
+#include "ring_geometry.h"
 #include "row_lengths.h"
 
 namespace qa {
@@ -24,7 +25,8 @@ struct TransformerLayerW {
 struct TransformerW {
     std::vector<TransformerLayerW> layers;
     int d = 0, heads = 0, inter = 0;
-    const float* rope = nullptr;  // [MAX_POS][hd/2][2]
+    const float* rope = nullptr;      // [MAX_POS][hd/2][2]
+    const float* rope_inv = nullptr;  // [hd/2]: the table's inverse frequencies, for the positions of a ring stream beyond it
 };
 
 struct ResBlockW {  // SEANetResnetBlock
@@ -60,7 +62,7 @@ struct MimiStream {
     int rope_base = 0, rope_len = 0;
 };
 
-constexpr int MAX_POS = 8192;
+constexpr int MAX_POS = TR_ROPE_POSITIONS;
 
 // the per-layer views of `mem`: `lead` floats per layer in front of the two [B, cap, d] caches (the streaming state's h and c)
 void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, std::vector<float*>* kc, std::vector<float*>* vc) {
@@ -77,13 +79,17 @@ void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, st
 // (section 43) both carry one.
 struct TrStream {
     int B = 0, cap = 0;
+    // ring mode: the caches are rings of cap rows under the window `window` and the stream has no end; a step takes
+    // at most max_chunk frames.  window = 0: linear, a step ends at or before row cap
+    int window = 0, max_chunk = 0;
+    bool ring() const { return window > 0; }
     bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
     DeviceFloats mem;
     DeviceInts ints{4};       // a step with per-row lengths: RowStep's four vectors, written once per step
     std::vector<float*> kc, vc, hs, cs;
     void release() {  // not streaming any more (the caller has set the device)
         mem.release();
-        B = cap = 0;
+        B = cap = window = max_chunk = 0;
     }
     // a fresh state for B sequences of up to `capacity` frames, in place of the one it held; never cleared: no kernel reads a K / V row at
     // or behind the key count of its step, and (h, c) are zeroed by the first step
@@ -102,6 +108,28 @@ struct TrStream {
         cap = (int)capacity;
         zero_state = true;
         return QA_OK;
+    }
+    // the same as a ring for chunks of up to `chunk` frames under the window `left_context`.  The rings ARE cleared, once: the short
+    // kernel never loads a row its item has not written, but attention_kernel's ring mode (long chunks) loads every row and multiplies the
+    // hidden ones by a zero probability, which needs them finite
+    int begin_ring(const TransformerW& w, int64_t batch, int left_context, int64_t chunk) {
+        const int64_t rows = ring::capacity(left_context, chunk);
+        QA_TRY(begin(w, batch, rows));
+        QA_HIP(hipMemset(mem.ptr, 0, sizeof(float) * w.layers.size() * 2 * ((size_t)batch * w.d + (size_t)batch * rows * w.d)));
+        QA_HIP(hipDeviceSynchronize());  // the steps run on the caller's stream, which need not wait for the null stream
+        window = left_context;
+        max_chunk = (int)chunk;
+        return QA_OK;
+    }
+    // Host check of a ring step: row b at off[b] units takes cnt[b] more, `rate` Transformer frames per unit.  -1: fine; else the first row
+    // that does not fit: a chunk above max_chunk (*why = 0) or a position at or past 2^24 (*why = 1)
+    int64_t first_bad_row(const std::vector<int>& off, const std::vector<int>& cnt, int rate, int* why) const {
+        for (size_t b = 0; b < off.size(); ++b) {
+            const int64_t p = (int64_t)rate * off[b], n = (int64_t)rate * cnt[b];
+            *why = n > max_chunk ? 0 : 1;
+            if (n > max_chunk || !ring::positions_fit(p, n)) return (int64_t)b;
+        }
+        return -1;
     }
     // begin / reset: (h, c) = 0 of every layer, in stream order like the step itself
     int zero_if_new(int d, hipStream_t s) {
@@ -335,18 +363,10 @@ void build_transformer(Loader& b, TransformerW* tw, const std::string& p, int d,
         b.linear(&L.w2, lp + ".mlp.w2.weight", "", d, inter);
     }
     // RoPE table, RotaryEmbedding of transformer.py:8-74 evaluated in fp32 like the reference
-    const int hd = d / heads, half = hd / 2;
-    std::vector<float> cs((size_t)MAX_POS * half * 2);
-    for (int i = 0; i < half; ++i) {
-        const float expo = (float)(2 * i) / (float)hd;
-        const float inv = 1.0f / std::pow(10000.0f, expo);
-        for (int t = 0; t < MAX_POS; ++t) {
-            const float fr = (float)t * inv;
-            cs[((size_t)t * half + i) * 2] = (float)std::cos((double)fr);
-            cs[((size_t)t * half + i) * 2 + 1] = (float)std::sin((double)fr);
-        }
-    }
+    std::vector<float> cs, inv;
+    transformer_rope_table(d / heads, &cs, &inv);
     b.raw(&tw->rope, cs);
+    b.raw(&tw->rope_inv, inv);
 }
 
 void build_mimi(Loader& b, MimiW* mw, const std::string& p, int d, int n_layers, int heads, int ff, int causal, int context) {
@@ -443,6 +463,8 @@ struct TrChunk {
     // pos0 is then unused.  Null: every item at pos0 with all t.T frames, today's launches
     const int *row_pos0 = nullptr, *row_nq = nullptr, *row_zero = nullptr;
     int max_keys = 0;
+    // window > 0: the caches are rings of cap rows under this sliding window, which replaces the left_context of the call
+    int window = 0;
 };
 
 // Whether a carried causal chunk of N frames x B rows takes the split-key kernel (stream_attn.hip): QA_TR_SHORT_ATTN 0 never, 1 up to 256
@@ -479,14 +501,21 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
     float* part = short_chunk ? c.arena.alloc<float>(attn_short_part_floats(B, H, hd, N, ch->cap)) : nullptr;
     AttnArgs at = attn_packed_qkv(qkv, att, B, N, H, hd);
     at.causal = t.causal ? 1 : 0;
+    const bool ring = ch && ch->window > 0;
+    if (ring) left_context = ch->window;
     at.context = t.causal ? left_context : 0;
     const bool ragged = ch && ch->row_nq;
     if (ch) {  // keys and values: rows 0 .. pos0 + N - 1 of the layer's caches
         at.ldkv = d; at.kv_batch_stride = (long long)ch->cap * d;
         at.n_keys = ragged ? ch->max_keys : ch->pos0 + N;
     }
+    if (ring) {  // the long chunk of a ring, rows moving together: attention_kernel's ring mode over all cap rows, keys appended first
+        QA_REQUIRE(carried && t.causal && ch->cap > ring::min_rows(ch->window, N), "transformer: a ring of %d rows under a window of %d "
+                   "holds chunks of fewer than %d frames", ch->cap, ch->window, ch->cap - ch->window + 1);
+        at.n_keys = ch->cap; at.q_pos0 = ch->pos0; at.ring_end = ch->pos0 + N;
+    }
     if (ragged) {
-        QA_REQUIRE(carried && t.causal && ch->row_pos0 && ch->row_zero && ch->max_keys >= 1 && ch->max_keys <= ch->cap,
+        QA_REQUIRE(carried && t.causal && ch->row_pos0 && ch->row_zero && (ring || (ch->max_keys >= 1 && ch->max_keys <= ch->cap)),
                    "transformer: per-row lengths exist for the streaming step of a causal Transformer");
         // the chunk form of attention_kernel with per-item counts is its fp32 form without a window (section 34); attention_op keeps it
         // (the entry point has refused this on the host, in front of its first launch, with the words a caller needs)
@@ -515,14 +544,15 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
         tap(".self_attn.rnn", hl);
         QA_TRY(linear_op(c, hl, rows, L.qkv, qkv));
         if (ch) {
-            QA_RUN(c, launch_rope_append(qkv, tw.rope, ch->kc[l], ch->vc[l], B, N, H, hd, ch->pos0, ch->cap, c.stream, ch->row_pos0, ch->row_nq));
+            QA_RUN(c, launch_rope_append(qkv, tw.rope, ch->kc[l], ch->vc[l], B, N, H, hd, ch->pos0, ch->cap, c.stream, ch->row_pos0, ch->row_nq,
+                                         ring ? tw.rope_inv : nullptr));
             at.k = ch->kc[l]; at.v = ch->vc[l];
         } else {
             QA_TRY(rope_op(c, qkv, tw.rope, B, N, H, hd, 3 * d, 0));
         }
         if (short_chunk) {
             QA_RUN(c, launch_attention_short(qkv, 3 * d, at.k, at.v, att, part, B, N, H, hd, ch->pos0, ch->cap, at.context, c.stream, ch->row_pos0,
-                                             ch->row_nq, ch->max_keys));
+                                             ch->row_nq, ch->max_keys, ring));
         } else {
             QA_TRY(attention_op(c, at));
         }
@@ -546,6 +576,7 @@ TrChunk stream_chunk(const TrStream& st, int pos0, const RowStep* rows = nullptr
     ch.kc = st.kc.data(); ch.vc = st.vc.data();
     ch.cap = st.cap; ch.pos0 = pos0;
     ch.hs = st.hs.data(); ch.cs = st.cs.data();
+    ch.window = st.window;
     if (rows) {
         ch.pos0 = 0;
         ch.row_zero = rows->dev[1]; ch.row_pos0 = rows->dev[2]; ch.row_nq = rows->dev[3];
@@ -1728,13 +1759,9 @@ int qa_hcodec_stream_geometry(const qa_hcodec_spec* spec, int64_t* samples_per_f
     return QA_OK;
 }
 
-int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
-    QA_REQUIRE(h, "qa_hcodec_stream_begin: null handle");
-    QA_TRY(stream_refuse(h->spec, "qa_hcodec_stream_begin"));
-    const StreamGeom g = stream_geometry(h->spec);
-    QA_REQUIRE(B > 0 && B < (1 << 20) && max_frames >= g.first_min && max_frames <= MAX_POS / 2,
-               "qa_hcodec_stream_begin: batch %lld, max_frames %lld (code frames, %d .. %d: the Transformer holds %d positions at 2 per code "
-               "frame, and the first chunk alone needs %d)", (long long)B, (long long)max_frames, g.first_min, MAX_POS / 2, MAX_POS, g.first_min);
+// left_context > 0: a ring stream for chunks of up to max_frames code frames under that window; else a linear one
+// of max_frames code frames.  The arguments are checked by the two entry points
+static int hcodec_stream_begin(qa_hcodec* h, const StreamGeom& g, int64_t B, int64_t max_frames, int left_context) {
     QA_HIP(hipSetDevice(h->device));
     h->strm.reset();  // a handle that is already streaming: its buffers wait for the steps that still read them
     std::unique_ptr<CodecStream> st(new CodecStream());
@@ -1757,13 +1784,71 @@ int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
             sc.st[k] = p;
             p += round_up((int64_t)B * sc.ctx * sc.C, 64);
         }
-    QA_TRY(st->tr.begin(h->enc_tr, B, 2 * max_frames));
+    if (left_context > 0) QA_TRY(st->tr.begin_ring(h->enc_tr, B, left_context, 2 * max_frames));
+    else QA_TRY(st->tr.begin(h->enc_tr, B, 2 * max_frames));
     st->B = (int)B;
     st->off.assign((size_t)B, 0);
-    st->cap = (int)max_frames;
+    st->cap = st->tr.cap / 2;  // a linear stream: max_frames
     st->first_min = g.first_min;
     h->strm = std::move(st);
     return QA_OK;
+}
+
+int qa_hcodec_stream_begin(qa_hcodec* h, int64_t B, int64_t max_frames) {
+    QA_REQUIRE(h, "qa_hcodec_stream_begin: null handle");
+    QA_TRY(stream_refuse(h->spec, "qa_hcodec_stream_begin"));
+    const StreamGeom g = stream_geometry(h->spec);
+    QA_REQUIRE(B > 0 && B < (1 << 20) && max_frames >= g.first_min && max_frames <= MAX_POS / 2,
+               "qa_hcodec_stream_begin: batch %lld, max_frames %lld (code frames, %d .. %d: the Transformer holds %d positions at 2 per code "
+               "frame, and the first chunk alone needs %d)", (long long)B, (long long)max_frames, g.first_min, MAX_POS / 2, MAX_POS, g.first_min);
+    return hcodec_stream_begin(h, g, B, max_frames, 0);
+}
+
+// The stream under a sliding window of left_context Transformer frames (two per code frame), as a ring without an end.  This is NOT the
+// shipped full-causal encoder: it is the SEANet encoder whose Transformer was built with use_sliding_window=True, left_context=W
+int qa_hcodec_stream_begin_ring(qa_hcodec* h, int64_t B, int32_t left_context, int64_t max_chunk_frames) {
+    QA_REQUIRE(h, "qa_hcodec_stream_begin_ring: null handle");
+    QA_TRY(stream_refuse(h->spec, "qa_hcodec_stream_begin_ring"));
+    const StreamGeom g = stream_geometry(h->spec);
+    QA_REQUIRE(left_context > 0, "qa_hcodec_stream_begin_ring: left_context %d - a ring needs a sliding window of at least 1 Transformer frame "
+               "(without a window a query sees its whole history, which no ring holds; qa_hcodec_stream_begin is the full-causal stream)",
+               (int)left_context);
+    QA_REQUIRE(B > 0 && B < (1 << 20) && max_chunk_frames >= g.first_min && max_chunk_frames <= MAX_POS / 2,
+               "qa_hcodec_stream_begin_ring: batch %lld, max_chunk_frames %lld (code frames, %d .. %d: the first chunk alone needs %d)",
+               (long long)B, (long long)max_chunk_frames, g.first_min, MAX_POS / 2, g.first_min);
+    const int64_t rows = ring::capacity(left_context, 2 * max_chunk_frames);
+    QA_REQUIRE(rows <= MAX_POS, "qa_hcodec_stream_begin_ring: left_context %d with max_chunk_frames %lld needs a ring of %lld rows, above the "
+               "%d a cache may have", (int)left_context, (long long)max_chunk_frames, (long long)rows, MAX_POS);
+    return hcodec_stream_begin(h, g, B, max_chunk_frames, left_context);
+}
+
+int64_t qa_hcodec_stream_capacity(const qa_hcodec* h) { return (h && h->strm) ? h->strm->cap : -1; }
+
+// the long-chunk attention has its per-item form without a window only (attention.hip, section 34), and nothing else runs in its place: a
+// step of n Transformer frames x B rows with per-row lengths under a window is refused unless it takes the short kernel
+static int rows_under_window_check(const char* fn, int left_context, int B, int64_t n) {
+    if (n <= ATTN_SHORT_MAX_Q && tr_short_chunk(B, (int)n)) return QA_OK;
+    const long long mode = knob(K_TR_SHORT_ATTN);
+    const char* why = n > ATTN_SHORT_MAX_Q ? "this step has more frames" : mode == 0 ? "QA_TR_SHORT_ATTN = 0 turns that kernel off"
+                                                                                    : "QA_TR_SHORT_ATTN = 1 stops at 256 query rows";
+    set_error("%s: a step with per-row lengths under a sliding window (left_context = %d) runs on the short-chunk attention alone (at "
+              "most %d frames per step) and %s; this step has %lld frames x %d rows - step fewer frames, set QA_TR_SHORT_ATTN = 2, or "
+              "move the rows together", fn, left_context, ATTN_SHORT_MAX_Q, why, (long long)n, B);
+    return QA_ERR_UNSUPPORTED;
+}
+
+// the refusal of a ring step that first_bad_row has found: a chunk above max_chunk (why 0) or a row past 2^24 positions (1); offset and n
+// in the caller's unit, `rate` Transformer frames each
+static int ring_refuse(const char* fn, const TrStream& st, int64_t row, int why, int64_t offset, int64_t n, int rate) {
+    const char* unit = rate == 2 ? "code frames" : "frames";
+    if (why == 0)
+        set_error("%s: row %lld takes %lld %s in this step, above the max_chunk %d this ring stream was begun for (a ring of %d rows holds "
+                  "no longer chunk under its window of %d) - step fewer frames or begin the stream with a larger max_chunk", fn, (long long)row,
+                  (long long)n, unit, st.max_chunk / rate, st.cap, st.window);
+    else
+        set_error("%s: row %lld has %lld streamed + %lld new %s, which passes 2^24 = %lld Transformer positions, the last a float "
+                  "holds exactly - reset that row", fn, (long long)row, (long long)offset, (long long)n, unit, (long long)ring::MAX_POSITIONS);
+    return QA_ERR_INVALID;
 }
 
 // One step of the stream; frames null: every row takes all n code frames (qa_hcodec_stream_encode).  Every refusal comes before any launch
@@ -1793,11 +1878,14 @@ static int stream_encode_call(qa_hcodec* h, const char* fn, const float* wav, in
     for (int b = 1; b < st.B; ++b) together = together && st.off[b] == st.off[0];
     const hipStream_t s = static_cast<hipStream_t>(stream);
     Ctx& c = h->ctx;
+    int why = 0;
+    const int64_t bad_row = st.tr.ring() ? st.tr.first_bad_row(st.off, rs.cnt, 2, &why) : -1;
+    if (bad_row >= 0) return ring_refuse(fn, st.tr, bad_row, why, st.off[bad_row], rs.cnt[bad_row], 2);
     if (together) {
         QA_REQUIRE(!st.first() || n >= st.first_min, "%s: the first chunk of a stream has %lld code frames, it needs at least %d "
                    "(%d samples): its left padding is the reflection of its own frames, which a shorter chunk cannot fill the way the offline "
                    "encoder does - buffer %d frames before the first step", fn, (long long)n, st.first_min, st.first_min * hop, st.first_min);
-        QA_REQUIRE((int64_t)st.offset() + n <= st.cap, "%s: %d streamed + %lld new code frames exceed the capacity %d of this "
+        QA_REQUIRE(st.tr.ring() || (int64_t)st.offset() + n <= st.cap, "%s: %d streamed + %lld new code frames exceed the capacity %d of this "
                    "stream (max_frames of qa_hcodec_stream_begin, at most %d); begin a longer stream or reset this one", fn, st.offset(),
                    (long long)n, st.cap, MAX_POS / 2);
         QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
@@ -1813,11 +1901,12 @@ static int stream_encode_call(qa_hcodec* h, const char* fn, const float* wav, in
             QA_REQUIRE(!(st.off[b] == 0 && f > 0 && f < st.first_min), "%s: row %d starts its stream with %d code frames, a first chunk needs at "
                        "least %d (%d samples): its left padding is the reflection of its own frames - let the row idle (frames = 0) until %d "
                        "frames are buffered", fn, b, f, st.first_min, st.first_min * hop, st.first_min);
-            QA_REQUIRE((int64_t)st.off[b] + f <= st.cap, "%s: row %d has %d streamed + %d new code frames, beyond the capacity %d of this stream "
+            QA_REQUIRE(st.tr.ring() || (int64_t)st.off[b] + f <= st.cap, "%s: row %d has %d streamed + %d new code frames, beyond the capacity %d of this stream "
                        "(max_frames of qa_hcodec_stream_begin, at most %d); reset that row (qa_hcodec_stream_reset_rows) or begin a longer stream",
                        fn, b, st.off[b], f, st.cap, MAX_POS / 2);
         }
         QA_REQUIRE(live > 0, "%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
+        if (st.tr.ring()) QA_TRY(rows_under_window_check(fn, st.tr.window, st.B, 2 * n));  // in Transformer frames, two per code frame
         QA_REQUIRE(!emb || ((reinterpret_cast<uintptr_t>(emb) & 15) == 0 && h->spec.code_dim % 4 == 0),
                    "%s: emb must be 16-byte aligned (and code_dim a multiple of 4) in a step with per-row lengths: the rows behind a "
                    "length are written as float4", fn);
@@ -2327,6 +2416,26 @@ int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) 
     return QA_OK;
 }
 
+// A ring stream: the K / V rows are rings of ring::capacity(left_context, max_chunk) rows and the stream has no end
+int qa_transformer_stream_begin_ring(qa_transformer* h, int64_t B, int64_t max_chunk) {
+    QA_REQUIRE(h, "qa_transformer_stream_begin_ring: null handle");
+    QA_REQUIRE(h->spec.causal && h->spec.left_context > 0, "qa_transformer_stream_begin_ring: a ring needs a causal Transformer with a sliding "
+               "window (causal = %d, left_context = %d): without a window a query sees its whole history, which no ring holds", h->spec.causal,
+               h->spec.left_context);
+    QA_REQUIRE(B > 0 && B < (1 << 20) && max_chunk >= 1 && max_chunk <= MAX_POS, "qa_transformer_stream_begin_ring: batch %lld, max_chunk %lld "
+               "(1 .. %d)", (long long)B, (long long)max_chunk, MAX_POS);
+    const int64_t rows = ring::capacity(h->spec.left_context, max_chunk);
+    QA_REQUIRE(rows <= MAX_POS, "qa_transformer_stream_begin_ring: left_context %d with max_chunk %lld needs a ring of %lld rows, above the %d "
+               "a cache may have", h->spec.left_context, (long long)max_chunk, (long long)rows, MAX_POS);
+    QA_HIP(hipSetDevice(h->device));
+    h->off.clear();
+    QA_TRY(h->st.begin_ring(h->w, B, h->spec.left_context, max_chunk));  // in place of the state of a handle that is already streaming
+    h->off.assign((size_t)B, 0);
+    return QA_OK;
+}
+
+int64_t qa_transformer_stream_capacity(const qa_transformer* h) { return (h && h->st.B > 0) ? h->st.cap : -1; }
+
 // One step; frames null: every row takes all n frames (qa_transformer_stream_step).  Refusals come before any launch and leave the state
 // and all offsets as they were; rows that move together with all n frames take the rectangular step whichever entry point they came through
 static int transformer_stream_call(qa_transformer* h, const char* fn, const float* x, int64_t n, const int64_t* frames, float* y, void* stream) {
@@ -2345,8 +2454,11 @@ static int transformer_stream_call(qa_transformer* h, const char* fn, const floa
     bool together = full;
     for (int b = 1; b < B; ++b) together = together && h->off[b] == h->off[0];
     const hipStream_t s = static_cast<hipStream_t>(stream);
+    int why = 0;
+    const int64_t bad_row = h->st.ring() ? h->st.first_bad_row(h->off, rs.cnt, 1, &why) : -1;
+    if (bad_row >= 0) return ring_refuse(fn, h->st, bad_row, why, h->off[bad_row], rs.cnt[bad_row], 1);
     if (together) {
-        QA_REQUIRE((int64_t)h->offset() + n <= h->st.cap, "%s: %d streamed + %lld new frames exceed the capacity %d of "
+        QA_REQUIRE(h->st.ring() || (int64_t)h->offset() + n <= h->st.cap, "%s: %d streamed + %lld new frames exceed the capacity %d of "
                    "this stream (max_frames)", fn, h->offset(), (long long)n, h->st.cap);
         QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
         QA_HIP(hipSetDevice(h->device));
@@ -2358,21 +2470,13 @@ static int transformer_stream_call(qa_transformer* h, const char* fn, const floa
         int live = 0;
         for (int b = 0; b < B; ++b) {
             live += rs.cnt[b] > 0;
-            QA_REQUIRE((int64_t)h->off[b] + rs.cnt[b] <= h->st.cap, "%s: row %d has %d streamed + %d new frames, beyond the capacity %d of this "
+            QA_REQUIRE(h->st.ring() || (int64_t)h->off[b] + rs.cnt[b] <= h->st.cap, "%s: row %d has %d streamed + %d new frames, beyond the capacity %d of this "
                        "stream (max_frames); reset that row (qa_transformer_stream_reset_rows) or begin a longer stream", fn, b, h->off[b],
                        rs.cnt[b], h->st.cap);
         }
         QA_REQUIRE(live > 0, "%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
         // the long-chunk attention has its per-item form without a window only (attention.hip, section 34): nothing else runs in its place
-        if (h->spec.left_context > 0 && !tr_short_chunk(B, (int)n)) {
-            const long long mode = knob(K_TR_SHORT_ATTN);
-            const char* why = n > ATTN_SHORT_MAX_Q ? "this step has more frames" : mode == 0 ? "QA_TR_SHORT_ATTN = 0 turns that kernel off"
-                                                                                            : "QA_TR_SHORT_ATTN = 1 stops at 256 query rows";
-            set_error("%s: a step with per-row lengths under a sliding window (left_context = %d) runs on the short-chunk attention alone (at "
-                      "most %d frames per step) and %s; this step has %lld frames x %d rows - step fewer frames, set QA_TR_SHORT_ATTN = 2, or "
-                      "move the rows together", fn, h->spec.left_context, ATTN_SHORT_MAX_Q, why, (long long)n, B);
-            return QA_ERR_UNSUPPORTED;
-        }
+        if (h->spec.left_context > 0) QA_TRY(rows_under_window_check(fn, h->spec.left_context, B, n));
         QA_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0,
                    "%s: x and y must be 16-byte aligned in a step with per-row lengths (the rows behind a length are written as float4)", fn);
         QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));

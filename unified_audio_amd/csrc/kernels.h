@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "common.h"
 #include "lm_session_rows.h"
@@ -140,8 +141,13 @@ int launch_ring_append(const float* k, const float* v, long long ld, float* kc, 
 // roped k and v rows go to rows pos0 .. pos0 + n - 1 of the caches kc / vc [B, cap, d].  pos0 + n <= cap is the caller's check
 // row_pos0 / row_nq (device int [B], both or neither): item b's rows sit at row_pos0[b] + t and only its first
 // row_nq[b] are rotated and appended; the others write nothing.  row_pos0[b] + row_nq[b] <= cap is the caller's check
+// ring_inv_freq (device [hd / 2], transformer_rope_table's inv_freq): the caches are RINGS of cap rows - position p
+// goes to row p mod cap, and positions at or beyond TR_ROPE_POSITIONS take their angle from inv_freq instead of the table.  Positions
+// below 2^24 and n <= cap are the caller's check
+constexpr int TR_ROPE_POSITIONS = 8192;  // positions of the codec Transformer's static RoPE table
+void transformer_rope_table(int hd, std::vector<float>* cs, std::vector<float>* inv_freq);
 int launch_rope_append(float* qkv, const float* cs, float* kc, float* vc, int B, int n, int H, int hd, int pos0, int cap, hipStream_t s,
-                       const int* row_pos0 = nullptr, const int* row_nq = nullptr);
+                       const int* row_pos0 = nullptr, const int* row_nq = nullptr, const float* ring_inv_freq = nullptr);
 // Causal attention of a short chunk (n <= ATTN_SHORT_MAX_Q queries at positions pos0 + i) over such a cache, keys 0 .. pos0 + n - 1 under
 // the window `context` (0 = none), fp32 arithmetic.  A (row, head) is split over workgroups that own the FIXED key ranges
 // [s L, (s + 1) L), L = attn_short_split_keys(cap): a key lands in the same split, tile and lane whatever pos0 is.  Partial records
@@ -153,7 +159,10 @@ int attn_short_split_keys(int cap);
 size_t attn_short_part_floats(int B, int H, int hd, int n, int cap);
 int launch_attention_short(const float* q, long long ldq, const float* kc, const float* vc, float* out, float* part, int B, int n, int H,
                            int hd, int pos0, int cap, int context, hipStream_t s, const int* row_pos0 = nullptr, const int* row_nq = nullptr,
-                           int max_keys = 0);
+                           int max_keys = 0, bool ring = false);
+// ring (ring_geometry.h): the caches are rings of cap rows under the window `context` >= 1, cap >= context - 1 + n;
+// item b sits at positions pos0 (row_pos0[b]) .. + n (row_nq[b]) - 1, anywhere below 2^24, and its keys are the rows whose position p(s)
+// it can see.  The grid covers every split of the ring; max_keys is unused.  A row never written for the item may hold NaN
 
 // lstm.hip : one nn.LSTM layer (batch_first, zero initial state) given the precomputed input projection
 //   xw [B, T, 4d] = x W_ih^T + b_ih + b_hh with the 4d axis permuted to (unit, gate) order,

@@ -188,6 +188,13 @@ def _frames_arg(lengths, B: int, what: str = "lengths"):
 MAX_STREAM_FRAMES = 4096  # code frames a stream can hold: the encoder Transformer's 8192 positions at two per code frame
 
 
+class _DefaultInt(int):
+    """A default argument that can be told from the same number given by the caller (`x is DEFAULT`)."""
+
+
+_DEFAULT_STREAM_FRAMES = _DefaultInt(MAX_STREAM_FRAMES)
+
+
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -594,15 +601,35 @@ class Codec(torch.nn.Module):
         _lib.check(self._lib.qa_hcodec_stream_geometry(C.byref(spec_c), None, C.byref(first), None, 0, None))
         return int(first.value)
 
-    def streaming_forever(self, batch_size: int, max_frames: int = MAX_STREAM_FRAMES):
+    def streaming_forever(self, batch_size: int, max_frames: int = _DEFAULT_STREAM_FRAMES, *, left_context: Optional[int] = None,
+                          max_chunk: Optional[int] = None):
         """Enter streaming mode (causal H-Codec 1.0): `encode_stream(x)` is then one step on the next samples of `batch_size` rows.
         `max_frames` is the capacity in CODE frames (at most 4096, 163.84 s: the encoder's Transformer holds 8192 positions at two per code
         frame); a step that would pass it is refused and leaves the state as it was.  Offline `encode` / `decode` / `forward` stay
-        allowed meanwhile: the stream's state is its own allocation.  On a codec that already streams, the old stream is freed."""
+        allowed meanwhile: the stream's state is its own allocation.  On a codec that already streams, the old stream is freed.
+
+        `left_context` and `max_chunk` (both or neither, and then no `max_frames`): a stream WITHOUT an end.  The
+        encoder's Transformer runs under a sliding window of `left_context` Transformer frames (two per code frame) over a ring of K / V
+        rows, and a step takes at most `max_chunk` code frames per row.  This is NOT the shipped full-causal model: it equals the SEANet
+        encoder whose `Transformer` was built with `use_sliding_window=True, left_context=left_context` - a parameter the reference's block
+        takes and `vq/codec.py` never sets - and its embeddings and codes differ from the full-causal ones by a few percent."""
+        if (left_context is None) != (max_chunk is None):
+            raise _lib.QuarkAudioError(-1, "Codec.streaming: left_context and max_chunk come together (a ring stream) or not at all")
+        if max_chunk is not None and max_frames is not _DEFAULT_STREAM_FRAMES:
+            raise _lib.QuarkAudioError(-1, "Codec.streaming: max_frames is the capacity of a linear stream and max_chunk that of a ring's "
+                                           "steps - give one of them")
         self._require_loaded()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.qa_hcodec_stream_begin(self._handle, int(batch_size), int(max_frames)))
+            if max_chunk is None:
+                _lib.check(self._lib.qa_hcodec_stream_begin(self._handle, int(batch_size), int(max_frames)))
+            else:
+                _lib.check(self._lib.qa_hcodec_stream_begin_ring(self._handle, int(batch_size), int(left_context), int(max_chunk)))
         self._streaming_batch = int(batch_size)
+
+    @property
+    def streaming_capacity(self) -> int:
+        """The code frames the stream's K / V rows hold: `max_frames` of a linear stream, the ring of a windowed one; -1 when not streaming."""
+        return int(self._lib.qa_hcodec_stream_capacity(self._handle)) if self._handle.value else -1
 
     def _stop_streaming(self):
         if self._handle.value:
@@ -610,8 +637,9 @@ class Codec(torch.nn.Module):
         self._streaming_batch = 0
 
     @contextmanager
-    def streaming(self, batch_size: int, max_frames: int = MAX_STREAM_FRAMES):
-        self.streaming_forever(batch_size, max_frames)
+    def streaming(self, batch_size: int, max_frames: int = _DEFAULT_STREAM_FRAMES, *, left_context: Optional[int] = None,
+                  max_chunk: Optional[int] = None):
+        self.streaming_forever(batch_size, max_frames, left_context=left_context, max_chunk=max_chunk)
         try:
             yield
         finally:

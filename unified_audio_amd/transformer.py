@@ -18,9 +18,10 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
-from .hcodec import _frames_arg, _int_list
+from .hcodec import _DefaultInt, _frames_arg, _int_list
 
-MAX_FRAMES = 8192  # the library's RoPE table: the most frames a cache or a stream can hold
+MAX_FRAMES = 8192  # the library's RoPE table: the most frames a cache or a linear stream can hold
+_DEFAULT_FRAMES = _DefaultInt(MAX_FRAMES)
 
 
 class TransformerCache:
@@ -120,13 +121,28 @@ class Transformer(torch.nn.Module):
     def is_streaming(self) -> bool:
         return self._streaming_batch > 0
 
-    def streaming_forever(self, batch_size: int, max_frames: int = MAX_FRAMES):
+    def streaming_forever(self, batch_size: int, max_frames: int = _DEFAULT_FRAMES, *, max_chunk: Optional[int] = None):
         """Enter streaming mode: `forward(x)` is then one step on the next x.shape[1] frames.  `max_frames` is the capacity of the K / V
-        rows the stream keeps (at most 8192); a step that would pass it is refused and leaves the state as it was."""
+        rows the stream keeps (at most 8192); a step that would pass it is refused and leaves the state as it was.
+        `max_chunk` (in place of `max_frames`; needs causal, use_sliding_window and left_context): the K / V rows are a
+        ring of `streaming_capacity` >= left_context + max_chunk rows and the stream has no end - a step takes at most `max_chunk` frames
+        per row, at any offset below 2^24 frames."""
+        if max_chunk is not None and max_frames is not _DEFAULT_FRAMES:
+            raise _lib.QuarkAudioError(-1, "Transformer.streaming: max_frames is the capacity of a linear stream and max_chunk that of a "
+                                           "ring's steps - give one of them")
         self._require()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.qa_transformer_stream_begin(self._handle, int(batch_size), int(max_frames)))
+            if max_chunk is None:
+                _lib.check(self._lib.qa_transformer_stream_begin(self._handle, int(batch_size), int(max_frames)))
+            else:
+                _lib.check(self._lib.qa_transformer_stream_begin_ring(self._handle, int(batch_size), int(max_chunk)))
         self._streaming_batch = int(batch_size)
+
+    @property
+    def streaming_capacity(self) -> int:
+        """The rows of the stream's K / V cache: `max_frames` of a linear stream, the ring of one begun with `max_chunk`; -1 when not
+        streaming."""
+        return int(self._lib.qa_transformer_stream_capacity(self._handle)) if self._handle else -1
 
     def _stop_streaming(self):
         if self._handle:
@@ -134,8 +150,8 @@ class Transformer(torch.nn.Module):
         self._streaming_batch = 0
 
     @contextmanager
-    def streaming(self, batch_size: int, max_frames: int = MAX_FRAMES):
-        self.streaming_forever(batch_size, max_frames)
+    def streaming(self, batch_size: int, max_frames: int = _DEFAULT_FRAMES, *, max_chunk: Optional[int] = None):
+        self.streaming_forever(batch_size, max_frames, max_chunk=max_chunk)
         try:
             yield
         finally:
