@@ -641,9 +641,12 @@ __global__ __launch_bounds__(256) void align_kernel(const float* __restrict__ se
     }
 }
 
+constexpr int ALIGN_MAX_T = 64 * 1024 / (2 * (int)sizeof(float));  // 8192
 int launch_align(const float* sem, int B, int T, int D, float thr, int max_tokens, int* seg, int* start, int* len,
                  int* nseg, int* gmax, const int* lens, hipStream_t s) {
     QA_REQUIRE(D % 4 == 0 && T >= 1 && max_tokens >= 1, "align: bad shape");
+    // the kernel keeps 2 * T floats of dynamic LDS (1 / norm and sim per frame); 64 KB is what a launch gets without raising the limit
+    QA_REQUIRE(T <= ALIGN_MAX_T, "align: T=%d frames exceed %d (2 * T floats of LDS in 64 KB)", T, ALIGN_MAX_T);
     QA_HIP(hipMemsetAsync(gmax, 0, sizeof(int), s));
     hipLaunchKernelGGL(align_kernel, dim3(B), dim3(256), 2 * T * sizeof(float), s, sem, T, D, thr, max_tokens, seg, start, len,
                        nseg, gmax, lens);
@@ -705,6 +708,7 @@ __global__ __launch_bounds__(256) void agg_build_kernel(const float* __restrict_
 }
 int launch_agg_build(const float* feats, const int* seg, const int* start, const int* len, const int* nseg, const float* qemb,
                      float* out, int B, int T, int G, int D, const int* lens, hipStream_t s) {
+    QA_REQUIRE(D % 4 == 0, "agg_build: D=%d must be a multiple of 4", D);
     hipLaunchKernelGGL(agg_build_kernel, dim3(T + G, B), dim3(128), 0, s, feats, seg, start, len, nseg, qemb, out, T, G, D, lens);
     QA_LAUNCH_CHECK();
     return QA_OK;
@@ -741,6 +745,7 @@ __global__ __launch_bounds__(128) void agg_gather_kernel(const float* __restrict
 }
 int launch_agg_gather(const float* x, const int* start, const int* len, const int* nseg, float* out, int B, int T, int G,
                       int D, hipStream_t s) {
+    QA_REQUIRE(D % 4 == 0, "agg_gather: D=%d must be a multiple of 4", D);
     hipLaunchKernelGGL(agg_gather_kernel, dim3(G, B), dim3(128), 0, s, x, start, len, nseg, out, T, G, D);
     QA_LAUNCH_CHECK();
     return QA_OK;
@@ -776,6 +781,7 @@ __global__ __launch_bounds__(128) void agg_zero_padded_kernel(const int* __restr
         *reinterpret_cast<float4*>(out + ((long long)b * G + g) * D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 int launch_agg_zero_padded(const int* nseg, float* out, int B, int G, int D, hipStream_t s) {
+    QA_REQUIRE(D % 4 == 0, "agg_zero_padded: D=%d must be a multiple of 4", D);
     hipLaunchKernelGGL(agg_zero_padded_kernel, dim3(G, B), dim3(128), 0, s, nseg, out, G, D);
     QA_LAUNCH_CHECK();
     return QA_OK;
@@ -797,6 +803,7 @@ __global__ void codes_inject_kernel(const long long* __restrict__ idx, const int
 }
 int launch_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K, bool pad_minus1,
                         hipStream_t s) {
+    QA_REQUIRE(G <= T, "codes_inject: G=%d groups exceed the T=%d rows of len", G, T);
     const long long total = (long long)B * Q * G;
     hipLaunchKernelGGL(codes_inject_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, idx, len, dst, B, T, G, Q, K,
                        pad_minus1 ? 1 : 0);
@@ -1038,4 +1045,54 @@ extern "C" int qa_debug_row_ints(int* dst, const int* host_src, long long count,
 extern "C" int qa_debug_to_channel_last(const float* x, long long sb, long long sc, long long st, float* y, int B, int C, int T,
                                         void* stream) {
     return qa::launch_to_channel_last(x, sb, sc, st, y, B, C, T, static_cast<hipStream_t>(stream));
+}
+
+// the adaptive-rate, code-layout, mask and ring kernels, the same way (tests/test_agg_kernels_gpu.py): int32 / int64 / byte device buffers
+extern "C" int qa_debug_align(const float* sem, int B, int T, int D, float thr, int max_tokens, int* seg, int* start, int* len, int* nseg,
+                              int* gmax, const int* lens, void* stream) {
+    return qa::launch_align(sem, B, T, D, thr, max_tokens, seg, start, len, nseg, gmax, lens, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_agg_build(const float* feats, const int* seg, const int* start, const int* len, const int* nseg, const float* qemb,
+                                  float* out, int B, int T, int G, int D, const int* lens, void* stream) {
+    return qa::launch_agg_build(feats, seg, start, len, nseg, qemb, out, B, T, G, D, lens, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_agg_key_mask(unsigned char* valid, int B, int T, int G, const int* lens, const int* nseg, void* stream) {
+    return qa::launch_agg_key_mask(valid, B, T, G, lens, nseg, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_agg_gather(const float* x, const int* start, const int* len, const int* nseg, float* out, int B, int T, int G, int D,
+                                   void* stream) {
+    return qa::launch_agg_gather(x, start, len, nseg, out, B, T, G, D, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_agg_query_rows(const float* x, const float* qkv, const int* start, const int* len, const int* nseg, float* xq,
+                                       float* qq, int B, int T, int G, int D, void* stream) {
+    return qa::launch_agg_query_rows(x, qkv, start, len, nseg, xq, qq, B, T, G, D, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_agg_zero_padded(const int* nseg, float* out, int B, int G, int D, void* stream) {
+    return qa::launch_agg_zero_padded(nseg, out, B, G, D, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_codes_inject(const long long* idx, const int* len, long long* dst, int B, int T, int G, int Q, int K, int pad_minus1,
+                                     void* stream) {
+    return qa::launch_codes_inject(idx, len, dst, B, T, G, Q, K, pad_minus1 != 0, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_adaptive_frames(const long long* codes, int B, int Q, int G, int K, int* totals, int* tmax, void* stream) {
+    return qa::launch_adaptive_frames(codes, B, Q, G, K, totals, tmax, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_token_lengths(const long long* codes, long long* out, int B, int Q, int G, int K, void* stream) {
+    return qa::launch_token_lengths(codes, out, B, Q, G, K, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_deaggregate(const long long* codes, const long long* len_codes, long long* out, int B, int Q, int G, int T, int K,
+                                    const int* cap, void* stream) {
+    return qa::launch_deaggregate(codes, len_codes, out, B, Q, G, T, K, cap, static_cast<hipStream_t>(stream));
+}
+// dir 0: library [B * N, Q] -> reference [B, Q, N]; dir 1: back
+extern "C" int qa_debug_codes_bqn(int dir, const long long* src, long long* dst, int B, int N, int Q, const int* lens, void* stream) {
+    return dir == 0 ? qa::launch_codes_to_bqn(src, dst, B, N, Q, static_cast<hipStream_t>(stream), lens)
+                    : qa::launch_codes_from_bqn(src, dst, B, N, Q, static_cast<hipStream_t>(stream), lens);
+}
+extern "C" int qa_debug_len_mask(unsigned char* valid, int B, int N, const int* lens, int len_mul, void* stream) {
+    return qa::launch_len_mask(valid, B, N, qa::ClipLens{lens, len_mul}, static_cast<hipStream_t>(stream));
+}
+extern "C" int qa_debug_ring_append(const float* k, const float* v, long long ld, float* kc, float* vc, int B, int T, int d, int cap, int pos0,
+                                    void* stream) {
+    return qa::launch_ring_append(k, v, ld, kc, vc, B, T, d, cap, pos0, static_cast<hipStream_t>(stream));
 }
