@@ -8,8 +8,7 @@
 #include <memory>
 
 #include "host_util.h"
-#include "ring_geometry.h"
-#include "row_lengths.h"
+#include "stream_step.h"
 
 namespace qa {
 
@@ -78,22 +77,34 @@ void transformer_kv_views(float* mem, size_t layers, size_t lead, size_t per, st
 // [B, cap, d], one allocation of the handle's own (not arena memory).  B > 0: streaming.  qa_transformer and the streaming H-Codec encoder
 // (section 43) both carry one.
 struct TrStream {
-    int B = 0, cap = 0;
+    int B = 0, cap = 0, d = 0;
     // ring mode: the caches are rings of cap rows under the window `window` and the stream has no end; a step takes
     // at most max_chunk frames.  window = 0: linear, a step ends at or before row cap
     int window = 0, max_chunk = 0;
     bool ring() const { return window > 0; }
-    bool zero_state = false;  // the next step zeroes the LSTM states on its stream first (begin / reset)
+    // The rows' offsets (section 47), in the unit its owner counts in: `rate` Transformer frames each (code frames of the H-Codec stream at
+    // 2, frames of a Transformer stream at 1).  off[b]: units of row b since begin / its reset.  A row at 0 takes a first step next: its
+    // (h, c) zeroed, earlier K / V rows invisible (no step reads a row at or behind its own key count), the codec's reflect fill.  Begin
+    // and every reset are therefore host writes of zeros and nothing else
+    std::vector<int> off;
+    int rate = 1;
+    int offset() const { return off.empty() ? 0 : *std::max_element(off.begin(), off.end()); }
+    int cap_units() const { return cap / rate; }
+    StepPlan plan;                  // scratch of the step front, kept for its vectors' storage: a refused step overwrites it too, and
+                                    // nothing reads it outside a running step (what a refusal leaves as it was is `off` and the device state)
+    const int* dev[4] = {nullptr, nullptr, nullptr, nullptr};  // the device copies of plan.cnt / first / pos0 / nq in `ints`
+    bool rows = false;              // the running step has per-row lengths (set around its graph only): dev[] and plan.max_keys hold
     DeviceFloats mem;
-    DeviceInts ints{4};       // a step with per-row lengths: RowStep's four vectors, written once per step
+    DeviceInts ints{4};             // a step with per-row lengths (section 45): the plan's four vectors, written once per step
     std::vector<float*> kc, vc, hs, cs;
     void release() {  // not streaming any more (the caller has set the device)
         mem.release();
+        off.clear();
         B = cap = window = max_chunk = 0;
     }
-    // a fresh state for B sequences of up to `capacity` frames, in place of the one it held; never cleared: no kernel reads a K / V row at
-    // or behind the key count of its step, and (h, c) are zeroed by the first step
-    int begin(const TransformerW& w, int64_t batch, int64_t capacity) {
+    // a fresh state for B sequences of up to `capacity` Transformer frames counted `unit_rate` to the unit, in place of the one it held;
+    // never cleared: no kernel reads a K / V row at or behind the key count of its step, and (h, c) are zeroed by the first step
+    int begin(const TransformerW& w, int64_t batch, int64_t capacity, int unit_rate) {
         release();
         const size_t L = w.layers.size(), st = (size_t)batch * w.d, per = (size_t)batch * capacity * w.d;
         QA_TRY(mem.allocate(L * (2 * st + 2 * per)));
@@ -106,60 +117,30 @@ struct TrStream {
         }
         B = (int)batch;
         cap = (int)capacity;
-        zero_state = true;
+        d = w.d;
+        rate = unit_rate;
+        off.assign((size_t)batch, 0);
         return QA_OK;
     }
     // the same as a ring for chunks of up to `chunk` frames under the window `left_context`.  The rings ARE cleared, once: the short
     // kernel never loads a row its item has not written, but attention_kernel's ring mode (long chunks) loads every row and multiplies the
     // hidden ones by a zero probability, which needs them finite
-    int begin_ring(const TransformerW& w, int64_t batch, int left_context, int64_t chunk) {
+    int begin_ring(const TransformerW& w, int64_t batch, int left_context, int64_t chunk, int unit_rate) {
         const int64_t rows = ring::capacity(left_context, chunk);
-        QA_TRY(begin(w, batch, rows));
+        QA_TRY(begin(w, batch, rows, unit_rate));
         QA_HIP(hipMemset(mem.ptr, 0, sizeof(float) * w.layers.size() * 2 * ((size_t)batch * w.d + (size_t)batch * rows * w.d)));
         QA_HIP(hipDeviceSynchronize());  // the steps run on the caller's stream, which need not wait for the null stream
         window = left_context;
         max_chunk = (int)chunk;
         return QA_OK;
     }
-    // Host check of a ring step: row b at off[b] units takes cnt[b] more, `rate` Transformer frames per unit.  -1: fine; else the first row
-    // that does not fit: a chunk above max_chunk (*why = 0) or a position at or past 2^24 (*why = 1)
-    int64_t first_bad_row(const std::vector<int>& off, const std::vector<int>& cnt, int rate, int* why) const {
-        for (size_t b = 0; b < off.size(); ++b) {
-            const int64_t p = (int64_t)rate * off[b], n = (int64_t)rate * cnt[b];
-            *why = n > max_chunk ? 0 : 1;
-            if (n > max_chunk || !ring::positions_fit(p, n)) return (int64_t)b;
-        }
-        return -1;
-    }
-    // begin / reset: (h, c) = 0 of every layer, in stream order like the step itself
-    int zero_if_new(int d, hipStream_t s) {
-        if (!zero_state) return QA_OK;
+    StreamView view(int first_min) const { return StreamView{off.data(), B, rate, cap_units(), first_min, window, max_chunk}; }
+    // a rectangular step of rows at offset 0: (h, c) = 0 of every layer, in stream order like the step itself.  A step with per-row
+    // lengths zeroes the rows that start in its own kernel (plan.first)
+    int zero_lstm(hipStream_t s) {
         for (size_t l = 0; l < hs.size(); ++l) QA_HIP(hipMemsetAsync(hs[l], 0, sizeof(float) * 2 * (size_t)B * d, s));
-        zero_state = false;
         return QA_OK;
     }
-};
-
-// What a step with per-row lengths carries to its kernels: per row the count in the caller's unit (code frames of
-// the H-Codec stream, frames of a Transformer stream), whether the row starts a sequence in this step, and its Transformer position and
-// query count.  Host vectors checked before any launch; dev[] are their device copies in TrStream::ints (upload), in that order.
-struct RowStep {
-    std::vector<int> cnt, first, pos0, nq;
-    const int* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int max_keys = 0;  // max_b(pos0[b] + nq[b]): the split count of the short attention, the key walk of the long one
-    // off: the rows' offsets, cnt already set; tr_rate Transformer frames per unit of cnt
-    void fill(const std::vector<int>& off, int tr_rate) {
-        const size_t B = off.size();
-        first.resize(B); pos0.resize(B); nq.resize(B);
-        max_keys = 0;
-        for (size_t b = 0; b < B; ++b) {
-            first[b] = off[b] == 0 && cnt[b] > 0;
-            pos0[b] = tr_rate * off[b];
-            nq[b] = tr_rate * cnt[b];
-            max_keys = std::max(max_keys, pos0[b] + nq[b]);
-        }
-    }
-    int upload(DeviceInts& ints, hipStream_t s) { return ints.upload({&cnt, &first, &pos0, &nq}, s, dev); }
 };
 
 // One stateful convolution of the streaming SEANet encoder: its carried context, the last `ctx` rows [B, ctx, C]
@@ -168,14 +149,9 @@ struct StreamConv {
     int ctx = 0, C = 0;
     float* st[2] = {nullptr, nullptr};
 };
-// The streaming state of a causal H-Codec 1.0 encoder: B > 0 between qa_hcodec_stream_begin and _end
+// The streaming state of a causal H-Codec 1.0 encoder, between qa_hcodec_stream_begin and _end: what the convolutions add to the state
+// of its Transformer, which owns the rows' offsets (in code frames) and the running step's row arrays
 struct CodecStream {
-    int B = 0, cap = 0;              // capacity in CODE frames
-    std::vector<int> off;            // [B] code frames of every row since begin / its reset; a row at 0 takes a first step next: reflect
-                                     // fill, LSTM state zeroed, earlier K / V rows invisible
-    const RowStep* rows = nullptr;   // the running step has per-row lengths (set around its graph only); null: every row moves together
-    int offset() const { return off.empty() ? 0 : *std::max_element(off.begin(), off.end()); }
-    bool first() const { return offset() == 0; }  // of a step in which every row moves together
     int cur = 0;                     // which of the two state buffers of every convolution holds the current state
     int first_min = 0;               // the fewest code frames a first chunk may have (stream_geometry)
     DeviceFloats conv_mem;
@@ -280,10 +256,7 @@ struct qa_mimi : Handle {
 struct qa_transformer : Handle {
     qa_transformer_spec spec{};
     TransformerW w;
-    // streaming state (st.B > 0: between qa_transformer_stream_begin and _end); off[b] frames of row b seen since begin / its reset
-    TrStream st;
-    std::vector<int> off;
-    int offset() const { return off.empty() ? 0 : *std::max_element(off.begin(), off.end()); }
+    TrStream st;  // streaming state (st.B > 0: between qa_transformer_stream_begin and _end), its offsets in frames
 };
 // past_key_values of Transformer.forward(x, past_key_values, use_cache=True): per layer the roped K and V rows [B, cap, d] in fp32
 struct qa_transformer_cache {
@@ -569,18 +542,18 @@ int transformer_op(Ctx& c, const TransformerW& tw, float* x, const TimeAxis& t, 
     return QA_OK;
 }
 
-// the step of a streaming state at `pos0` frames: the K / V rows and the carried LSTM state of `st`
-// rows: the step has per-row lengths (uploaded); pos0 is then unused
-TrChunk stream_chunk(const TrStream& st, int pos0, const RowStep* rows = nullptr) {
+// the running step of a streaming state: the K / V rows and the carried LSTM state of `st`, at its rows' common position or, in a step
+// with per-row lengths (st.rows), with the uploaded row arrays
+TrChunk stream_chunk(const TrStream& st) {
     TrChunk ch;
     ch.kc = st.kc.data(); ch.vc = st.vc.data();
-    ch.cap = st.cap; ch.pos0 = pos0;
+    ch.cap = st.cap; ch.pos0 = st.rate * st.offset();
     ch.hs = st.hs.data(); ch.cs = st.cs.data();
     ch.window = st.window;
-    if (rows) {
+    if (st.rows) {
         ch.pos0 = 0;
-        ch.row_zero = rows->dev[1]; ch.row_pos0 = rows->dev[2]; ch.row_nq = rows->dev[3];
-        ch.max_keys = rows->max_keys;
+        ch.row_zero = st.dev[1]; ch.row_pos0 = st.dev[2]; ch.row_nq = st.dev[3];
+        ch.max_keys = st.plan.max_keys;
     }
     return ch;
 }
@@ -814,7 +787,7 @@ int encoder20(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float*
 // below) and the front: a step takes the unfused launches, as a ragged call does - the fused front stages whole halo tiles with a reflect
 // rule of its own (a carried-halo form of it is not built) - and has neither lengths nor taps.  The 1x1 shortcut and the 1x1 behind the k3
 // are row-wise and carry nothing.  The Transformer continues over its carried (h, c) and K / V rows at 2 frames per code frame.  A step
-// reads st->cur / off / rows, which the caller advances behind a successful step.  With st->rows (a step with per-row lengths, section 45)
+// reads st->cur and st->tr.off / rows, which the step front advances behind a successful step.  With rows (per-row lengths, section 45)
 // every window holds zeros behind a row's own frames, so whatever the caller's waveform holds there never enters the ladder; the launches
 // between the windows run on the rectangle.
 int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, float** emb_out, int* n50_out, int* n25_out,
@@ -835,9 +808,9 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
         const StreamConv& sc = st->convs[ci++];
         *win = c.arena.alloc<float>((size_t)B * (sc.ctx + L) * Cw);
         // per-row lengths: the row's live rows of this buffer are its code frames times the buffer's rows per code frame
-        const RowStep* rs = st->rows;
-        QA_RUN(c, launch_stream_window(sc.st[st->cur], chunk, *win, sc.st[st->cur ^ 1], B, sc.ctx, L, Cw, st->first() ? 1 : 0, c.stream,
-                                       rs ? ClipLens{rs->dev[0], L / code_frames} : ClipLens(), rs ? rs->dev[1] : nullptr));
+        const bool rs = st->tr.rows;
+        QA_RUN(c, launch_stream_window(sc.st[st->cur], chunk, *win, sc.st[st->cur ^ 1], B, sc.ctx, L, Cw, st->tr.offset() == 0 ? 1 : 0, c.stream,
+                                       rs ? ClipLens{st->tr.dev[0], L / code_frames} : ClipLens(), rs ? st->tr.dev[1] : nullptr));
         return QA_OK;
     };
     // SConv1d(k = w.ksize, stride) over x [B, ta.T, w.C_in] -> *y [B, *T_out, w.N] (*y null: an arena buffer); o: prologue and epilogue.
@@ -909,7 +882,7 @@ int seanet_encoder(qa_hcodec* h, Ctx& c, const float* wav, const TimeAxis& tw, f
     }
     QA_REQUIRE(C == sp.dimension, "encoder: channel ladder ends at %d, spec.dimension is %d", C, sp.dimension);
     QA_REQUIRE(!st || t.T * h->geom.samples == 2 * tw.T, "stream: the ladder ends at %d frames for a step of %d samples", t.T, tw.T);
-    const TrChunk ch = st ? stream_chunk(st->tr, 2 * st->offset(), st->rows) : TrChunk();
+    const TrChunk ch = st ? stream_chunk(st->tr) : TrChunk();
     QA_TRY(transformer_op(c, h->enc_tr, x, t, taps ? "encoder.model." + std::to_string(3 * sp.n_ratios + 2) : std::string(), 0, st ? &ch : nullptr));
     if (taps) c.tap("enc.transformer", x, t.rows() * C);
     ConvOpt eo;
@@ -972,19 +945,19 @@ StreamGeom stream_geometry(const qa_hcodec_spec& sp) {
 // one step of Codec.encode's acoustic half: SEANet step -> emb [B, n, code_dim] -> ResidualVQ -> codes [B, nq, n]; either output may be null
 int stream_encode_graph(qa_hcodec* h, Ctx& c, const float* wav, int n, long long* ac_out, float* emb_out) {
     const qa_hcodec_spec& sp = h->spec;
-    const int B = h->strm->B, Q = sp.num_quantizers;
+    const int B = h->strm->tr.B, Q = sp.num_quantizers;
     float* emb = emb_out ? emb_out : c.arena.alloc<float>((size_t)B * n * sp.code_dim);
     int n50 = 0, n25 = 0;
     QA_TRY(seanet_encoder(h, c, wav, TimeAxis{B, n * h->geom.samples, true, ClipLens()}, &emb, &n50, &n25, h->strm.get()));
     // per-row lengths: exact zeros behind a row's frames in emb (in front of the search, which then sees finite rows it would see anyway),
     // and the dropped code -1 there, as a ragged encode writes them
-    const RowStep* rs = h->strm->rows;
-    if (rs) QA_RUN(c, launch_lm_rows_zero_pad(emb, 0, 1, B, n, sp.code_dim, rs->dev[0], c.stream));
+    const int* rs = h->strm->tr.rows ? h->strm->tr.dev[0] : nullptr;
+    if (rs) QA_RUN(c, launch_lm_rows_zero_pad(emb, 0, 1, B, n, sp.code_dim, rs, c.stream));
     if (!ac_out) return QA_OK;
     long long* ia = c.arena.alloc<long long>((size_t)B * n * Q);
     float* rvq_ws = c.arena.alloc<float>(rvq_scratch_floats((long long)B * n, sp.codebook_size, sp.code_dim));
     QA_RUN(c, launch_rvq_search(emb, (long long)B * n, h->cb_a, h->e2_a, Q, sp.codebook_size, sp.code_dim, ia, nullptr, 0, rvq_ws, c.stream));
-    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, n, Q, c.stream, rs ? rs->dev[0] : nullptr));
+    QA_RUN(c, launch_codes_to_bqn(ia, ac_out, B, n, Q, c.stream, rs));
     return QA_OK;
 }
 
@@ -1615,6 +1588,145 @@ static int run(Handle* h, void* stream, F&& graph) {
     return run_graph_checked(h, graph);
 }
 
+// ---- what the two stream families share: the streaming H-Codec encoder (qa_hcodec_stream_*) and the codec
+// Transformer on its own (qa_transformer_stream_*) are one TrStream each and step through one front.  What differs is named here.
+struct StreamFamily {
+    const char *unit, *begin, *cap_arg, *reset_rows;  // the words of a message: what an offset counts, the entry points and the argument it points to
+    int first_min, unit_samples;            // the fewest units of a first chunk (1: none), and the samples of a unit for its message
+};
+static StreamFamily codec_stream(const qa_hcodec* h) {
+    return {"code frames", "qa_hcodec_stream_begin", "max_frames", "qa_hcodec_stream_reset_rows", h->strm ? h->strm->first_min : 1, h->geom.samples};
+}
+constexpr StreamFamily TRANSFORMER_STREAM = {"frames", "qa_transformer_stream_begin", "capacity", "qa_transformer_stream_reset_rows", 1, 0};
+
+// the stream of a handle, null when it is not streaming (or null itself); of a const Transformer handle, a const stream
+static TrStream* stream_of(const qa_hcodec* h) { return h && h->strm ? &h->strm->tr : nullptr; }
+template <typename H> static auto stream_of(H* h) -> decltype(&h->st) { return h && h->st.B > 0 ? &h->st : nullptr; }
+
+static int require_streaming(const char* fn, const TrStream* st, const char* begin) {
+    QA_REQUIRE(st, "%s: not streaming (call %s first)", fn, begin);
+    return QA_OK;
+}
+
+// _begin_ring of both: max_chunk units of `rate` Transformer frames under the window left_context
+static int ring_begin_check(const char* fn, const char* chunk_name, const char* unit, int64_t B, int left_context, int64_t max_chunk,
+                            int first_min, int rate) {
+    QA_REQUIRE(B > 0 && B < (1 << 20) && max_chunk >= first_min && max_chunk <= MAX_POS / rate, "%s: batch %lld, %s %lld (%s, %d .. %d%s)", fn,
+               (long long)B, chunk_name, (long long)max_chunk, unit, first_min, MAX_POS / rate, first_min > 1 ? ": a first chunk needs that many" : "");
+    const int64_t rows = ring::capacity(left_context, rate * max_chunk);
+    QA_REQUIRE(rows <= MAX_POS, "%s: left_context %d with %s %lld needs a ring of %lld rows, above the %d a cache may have", fn, left_context,
+               chunk_name, (long long)max_chunk, (long long)rows, MAX_POS);
+    return QA_OK;
+}
+
+// _reset: every row takes a first step next.  Host state alone (TrStream::off)
+static int stream_reset(const char* fn, TrStream* st, const char* begin) {
+    QA_TRY(require_streaming(fn, st, begin));
+    std::fill(st->off.begin(), st->off.end(), 0);
+    return QA_OK;
+}
+
+// _reset_rows: the named rows back to offset 0; an index out of range or named twice is refused and nothing changes
+static int stream_reset_rows(const char* fn, TrStream* st, const char* begin, const int64_t* rows, int64_t n_rows) {
+    QA_TRY(require_streaming(fn, st, begin));
+    const int64_t B = st->B;
+    QA_REQUIRE(rows && n_rows >= 1 && n_rows <= B, "%s: %lld rows to reset of a stream of %lld (1 .. %lld distinct row indices)", fn,
+               (long long)n_rows, (long long)B, (long long)B);
+    std::vector<char> seen((size_t)B, 0);
+    for (int64_t i = 0; i < n_rows; ++i) {
+        QA_REQUIRE(rows[i] >= 0 && rows[i] < B, "%s: rows[%lld] = %lld is outside 0 .. %lld, the rows of this stream", fn, (long long)i,
+                   (long long)rows[i], (long long)B - 1);
+        QA_REQUIRE(!seen[(size_t)rows[i]], "%s: row %lld is named twice - name every row to reset once", fn, (long long)rows[i]);
+        seen[(size_t)rows[i]] = 1;
+    }
+    for (int64_t i = 0; i < n_rows; ++i) st->off[(size_t)rows[i]] = 0;
+    return QA_OK;
+}
+
+// _offsets: out [B]
+static int stream_offsets(const char* fn, const TrStream* st, const char* begin, int64_t* out) {
+    QA_TRY(require_streaming(fn, st, begin));
+    QA_REQUIRE(out, "%s: null out", fn);
+    for (size_t b = 0; b < st->off.size(); ++b) out[b] = st->off[b];
+    return QA_OK;
+}
+
+// the long-chunk attention has its per-item form without a window only (attention.hip, section 34), and nothing else runs in its place: a
+// step of n Transformer frames x B rows with per-row lengths under a window is refused unless it takes the short kernel
+static int rows_under_window_check(const char* fn, int left_context, int B, int64_t n) {
+    if (n <= ATTN_SHORT_MAX_Q && tr_short_chunk(B, (int)n)) return QA_OK;
+    const long long mode = knob(K_TR_SHORT_ATTN);
+    const char* why = n > ATTN_SHORT_MAX_Q ? "this step has more frames" : mode == 0 ? "QA_TR_SHORT_ATTN = 0 turns that kernel off"
+                                                                                    : "QA_TR_SHORT_ATTN = 1 stops at 256 query rows";
+    set_error("%s: a step with per-row lengths under a sliding window (left_context = %d) runs on the short-chunk attention alone (at "
+              "most %d frames per step) and %s; this step has %lld frames x %d rows - step fewer frames, set QA_TR_SHORT_ATTN = 2, or "
+              "move the rows together", fn, left_context, ATTN_SHORT_MAX_Q, why, (long long)n, B);
+    return QA_ERR_UNSUPPORTED;
+}
+
+// the message of a step that plan_step refused (st.plan.row: the offending row); n and frames as the caller passed them
+static int step_refuse(const char* fn, const TrStream& st, const StreamFamily& fam, StepFault fault, const int64_t* frames, int64_t n) {
+    const long long row = st.plan.row, at = row >= 0 ? st.off[(size_t)row] : 0, take = row >= 0 && frames ? frames[row] : n;
+    const int cap = st.cap_units(), fmin = fam.first_min;
+    const char* all = st.plan.together ? " (and every row with it: they move together)" : "";
+    switch (fault) {
+    case STEP_COUNT_RANGE:
+        set_error("%s: frames[%lld] = %lld is outside 0 .. %lld, the %s of this step's rectangle (0: the row idles) - pass a wider rectangle "
+                  "or fewer frames", fn, row, take, (long long)n, fam.unit);
+        break;
+    case STEP_RING_CHUNK:
+        set_error("%s: row %lld takes %lld %s in this step, above the max_chunk %d this ring stream was begun for (a ring of %d rows holds "
+                  "no longer chunk under its window of %d) - step fewer frames or begin the stream with a larger max_chunk", fn, row, take,
+                  fam.unit, st.max_chunk / st.rate, st.cap, st.window);
+        break;
+    case STEP_RING_POSITIONS:
+        set_error("%s: row %lld has %lld streamed + %lld new %s, which passes 2^24 = %lld Transformer positions, the last a float holds "
+                  "exactly - reset that row", fn, row, at, take, fam.unit, (long long)ring::MAX_POSITIONS);
+        break;
+    case STEP_FIRST_SHORT:
+        set_error("%s: row %lld%s starts its stream with %lld %s, a first chunk needs at least %d (%d samples): its left padding is the "
+                  "reflection of its own frames, which a shorter chunk cannot fill the way the offline encoder does - buffer %d frames "
+                  "first (among rows that run, let this one idle meanwhile: frames = 0)", fn, row, all, take, fam.unit, fmin,
+                  fmin * fam.unit_samples, fmin);
+        break;
+    case STEP_OVER_CAPACITY:
+        set_error("%s: row %lld%s has %lld streamed + %lld new %s, beyond the capacity %d of this stream (%s of %s, at most %d); "
+                  "reset that row (%s) or begin a longer stream", fn, row, all, at, take, fam.unit, cap, fam.cap_arg, fam.begin, MAX_POS / st.rate,
+                  fam.reset_rows);
+        break;
+    default:
+        set_error("%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
+    }
+    return QA_ERR_INVALID;
+}
+
+// One step of a stream: n units per row, or frames[b] of them (frames null: all n).  Every refusal comes before any launch and leaves the
+// state and all offsets as they were.  When every row sits at one offset and takes all n the step is the rectangular one - no row arrays,
+// (h, c) zeroed here if the rows start - whichever entry point it came through (section 45); otherwise the plan's four vectors go to the
+// device and st.rows is set around the graph.  left_context: the window the attention runs under; misaligned: null, or what a step with
+// per-row lengths needs 16-byte aligned and is not; run(): the family's graph, which reads `st`.  The offsets advance behind run() alone.
+// In order: the plan, the window and alignment rules of row arrays, the capture rule, then the device, the state, the run.
+template <typename Run>
+static int stream_step(const char* fn, const Handle& h, TrStream& st, const StreamFamily& fam, int left_context, const int64_t* frames,
+                       int64_t n, const char* misaligned, hipStream_t s, Run&& run) {
+    StepPlan& p = st.plan;
+    const StepFault fault = plan_step(st.view(fam.first_min), frames, n, &p);
+    if (fault != STEP_OK) return step_refuse(fn, st, fam, fault, frames, n);
+    const bool rows = !p.together;
+    if (rows && left_context > 0) QA_TRY(rows_under_window_check(fn, left_context, st.B, st.rate * n));
+    QA_REQUIRE(!rows || !misaligned, "%s: %s", fn, misaligned);
+    QA_TRY(refuse_capture(fn, s, rows ? LENGTHS_ARE_HOST_DATA : CACHE_IS_HOST_STATE));
+    QA_HIP(hipSetDevice(h.device));
+    if (rows) QA_TRY(st.ints.upload({&p.cnt, &p.first, &p.pos0, &p.nq}, s, st.dev));
+    else if (st.offset() == 0) QA_TRY(st.zero_lstm(s));
+    st.rows = rows;
+    const int rc = run();
+    st.rows = false;
+    QA_TRY(rc);
+    for (size_t b = 0; b < st.off.size(); ++b) st.off[b] += p.cnt[b];
+    return QA_OK;
+}
+
 extern "C" {
 
 int qa_hcodec_create(qa_hcodec** out, const qa_hcodec_spec* spec, const qa_tensor* tensors, int64_t n_tensors, int device) {
@@ -1784,11 +1896,9 @@ static int hcodec_stream_begin(qa_hcodec* h, const StreamGeom& g, int64_t B, int
             sc.st[k] = p;
             p += round_up((int64_t)B * sc.ctx * sc.C, 64);
         }
-    if (left_context > 0) QA_TRY(st->tr.begin_ring(h->enc_tr, B, left_context, 2 * max_frames));
-    else QA_TRY(st->tr.begin(h->enc_tr, B, 2 * max_frames));
-    st->B = (int)B;
-    st->off.assign((size_t)B, 0);
-    st->cap = st->tr.cap / 2;  // a linear stream: max_frames
+    // offsets in code frames, two Transformer frames each; the capacity of a linear stream is max_frames of them
+    if (left_context > 0) QA_TRY(st->tr.begin_ring(h->enc_tr, B, left_context, 2 * max_frames, 2));
+    else QA_TRY(st->tr.begin(h->enc_tr, B, 2 * max_frames, 2));
     st->first_min = g.first_min;
     h->strm = std::move(st);
     return QA_OK;
@@ -1813,115 +1923,34 @@ int qa_hcodec_stream_begin_ring(qa_hcodec* h, int64_t B, int32_t left_context, i
     QA_REQUIRE(left_context > 0, "qa_hcodec_stream_begin_ring: left_context %d - a ring needs a sliding window of at least 1 Transformer frame "
                "(without a window a query sees its whole history, which no ring holds; qa_hcodec_stream_begin is the full-causal stream)",
                (int)left_context);
-    QA_REQUIRE(B > 0 && B < (1 << 20) && max_chunk_frames >= g.first_min && max_chunk_frames <= MAX_POS / 2,
-               "qa_hcodec_stream_begin_ring: batch %lld, max_chunk_frames %lld (code frames, %d .. %d: the first chunk alone needs %d)",
-               (long long)B, (long long)max_chunk_frames, g.first_min, MAX_POS / 2, g.first_min);
-    const int64_t rows = ring::capacity(left_context, 2 * max_chunk_frames);
-    QA_REQUIRE(rows <= MAX_POS, "qa_hcodec_stream_begin_ring: left_context %d with max_chunk_frames %lld needs a ring of %lld rows, above the "
-               "%d a cache may have", (int)left_context, (long long)max_chunk_frames, (long long)rows, MAX_POS);
+    QA_TRY(ring_begin_check("qa_hcodec_stream_begin_ring", "max_chunk_frames", "code frames", B, left_context, max_chunk_frames, g.first_min, 2));
     return hcodec_stream_begin(h, g, B, max_chunk_frames, left_context);
 }
 
-int64_t qa_hcodec_stream_capacity(const qa_hcodec* h) { return (h && h->strm) ? h->strm->cap : -1; }
+int64_t qa_hcodec_stream_capacity(const qa_hcodec* h) { return stream_of(h) ? stream_of(h)->cap_units() : -1; }
 
-// the long-chunk attention has its per-item form without a window only (attention.hip, section 34), and nothing else runs in its place: a
-// step of n Transformer frames x B rows with per-row lengths under a window is refused unless it takes the short kernel
-static int rows_under_window_check(const char* fn, int left_context, int B, int64_t n) {
-    if (n <= ATTN_SHORT_MAX_Q && tr_short_chunk(B, (int)n)) return QA_OK;
-    const long long mode = knob(K_TR_SHORT_ATTN);
-    const char* why = n > ATTN_SHORT_MAX_Q ? "this step has more frames" : mode == 0 ? "QA_TR_SHORT_ATTN = 0 turns that kernel off"
-                                                                                    : "QA_TR_SHORT_ATTN = 1 stops at 256 query rows";
-    set_error("%s: a step with per-row lengths under a sliding window (left_context = %d) runs on the short-chunk attention alone (at "
-              "most %d frames per step) and %s; this step has %lld frames x %d rows - step fewer frames, set QA_TR_SHORT_ATTN = 2, or "
-              "move the rows together", fn, left_context, ATTN_SHORT_MAX_Q, why, (long long)n, B);
-    return QA_ERR_UNSUPPORTED;
-}
-
-// the refusal of a ring step that first_bad_row has found: a chunk above max_chunk (why 0) or a row past 2^24 positions (1); offset and n
-// in the caller's unit, `rate` Transformer frames each
-static int ring_refuse(const char* fn, const TrStream& st, int64_t row, int why, int64_t offset, int64_t n, int rate) {
-    const char* unit = rate == 2 ? "code frames" : "frames";
-    if (why == 0)
-        set_error("%s: row %lld takes %lld %s in this step, above the max_chunk %d this ring stream was begun for (a ring of %d rows holds "
-                  "no longer chunk under its window of %d) - step fewer frames or begin the stream with a larger max_chunk", fn, (long long)row,
-                  (long long)n, unit, st.max_chunk / rate, st.cap, st.window);
-    else
-        set_error("%s: row %lld has %lld streamed + %lld new %s, which passes 2^24 = %lld Transformer positions, the last a float "
-                  "holds exactly - reset that row", fn, (long long)row, (long long)offset, (long long)n, unit, (long long)ring::MAX_POSITIONS);
-    return QA_ERR_INVALID;
-}
-
-// One step of the stream; frames null: every row takes all n code frames (qa_hcodec_stream_encode).  Every refusal comes before any launch
-// and leaves the state and all offsets as they were.  When every row sits at one offset and takes all n frames the step is the
-// rectangular one - no row arrays, today's launches, today's bits - whichever entry point it came through.
+// One step of the stream; frames null: every row takes all n code frames (qa_hcodec_stream_encode).  The codec's own checks, then the
+// shared front (stream_step), which reads the convolutions' current buffers and flips them behind a step that ran
 static int stream_encode_call(qa_hcodec* h, const char* fn, const float* wav, int64_t n_samples, const int64_t* frames, int64_t* acoustic_codes,
                               float* emb, void* stream) {
     QA_REQUIRE(h, "%s: null handle", fn);
-    QA_REQUIRE(h->strm, "%s: not streaming (call qa_hcodec_stream_begin first)", fn);
+    const StreamFamily fam = codec_stream(h);
+    QA_TRY(require_streaming(fn, stream_of(h), fam.begin));
     QA_REQUIRE(wav && (acoustic_codes || emb), "%s: null wav, or neither acoustic_codes nor emb asked for", fn);
-    CodecStream& st = *h->strm;
+    TrStream& st = h->strm->tr;
     const int hop = h->geom.samples;
     QA_REQUIRE(n_samples > 0 && n_samples % hop == 0, "%s: a step of %lld samples; it must be a positive multiple of the "
                "%d samples of a code frame (zero-pad a trailing partial frame, as HCodecTokenizer.pad_wav does)", fn, (long long)n_samples, hop);
     const int64_t n = n_samples / hop;
     QA_REQUIRE(st.B * n_samples < (1LL << 31), "%s: a step of %d x %lld samples is too large", fn, st.B, (long long)n_samples);
-    RowStep rs;
-    bool full = true;
-    if (frames) {
-        const int64_t bad = check_row_lengths(frames, st.B, 0, n, &rs.cnt, &full);
-        QA_REQUIRE(bad < 0, "%s: frames[%lld] = %lld is outside 0 .. %lld, the code frames of this step's rectangle (0: the row idles) - pass a "
-                   "wider rectangle or fewer frames", fn, (long long)bad, (long long)frames[bad], (long long)n);
-    } else {
-        rs.cnt.assign((size_t)st.B, (int)n);
-    }
-    bool together = full;
-    for (int b = 1; b < st.B; ++b) together = together && st.off[b] == st.off[0];
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    Ctx& c = h->ctx;
-    int why = 0;
-    const int64_t bad_row = st.tr.ring() ? st.tr.first_bad_row(st.off, rs.cnt, 2, &why) : -1;
-    if (bad_row >= 0) return ring_refuse(fn, st.tr, bad_row, why, st.off[bad_row], rs.cnt[bad_row], 2);
-    if (together) {
-        QA_REQUIRE(!st.first() || n >= st.first_min, "%s: the first chunk of a stream has %lld code frames, it needs at least %d "
-                   "(%d samples): its left padding is the reflection of its own frames, which a shorter chunk cannot fill the way the offline "
-                   "encoder does - buffer %d frames before the first step", fn, (long long)n, st.first_min, st.first_min * hop, st.first_min);
-        QA_REQUIRE(st.tr.ring() || (int64_t)st.offset() + n <= st.cap, "%s: %d streamed + %lld new code frames exceed the capacity %d of this "
-                   "stream (max_frames of qa_hcodec_stream_begin, at most %d); begin a longer stream or reset this one", fn, st.offset(),
-                   (long long)n, st.cap, MAX_POS / 2);
-        QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
-        QA_HIP(hipSetDevice(h->device));
-        if (st.first()) st.tr.zero_state = true;
-        QA_TRY(st.tr.zero_if_new(h->enc_tr.d, s));
-        QA_TRY(run_planned(*h, stream, [&] { return stream_encode_graph(h, c, wav, (int)n, (long long*)acoustic_codes, emb); }));
-    } else {
-        int live = 0;
-        for (int b = 0; b < st.B; ++b) {
-            const int f = rs.cnt[b];
-            live += f > 0;
-            QA_REQUIRE(!(st.off[b] == 0 && f > 0 && f < st.first_min), "%s: row %d starts its stream with %d code frames, a first chunk needs at "
-                       "least %d (%d samples): its left padding is the reflection of its own frames - let the row idle (frames = 0) until %d "
-                       "frames are buffered", fn, b, f, st.first_min, st.first_min * hop, st.first_min);
-            QA_REQUIRE(st.tr.ring() || (int64_t)st.off[b] + f <= st.cap, "%s: row %d has %d streamed + %d new code frames, beyond the capacity %d of this stream "
-                       "(max_frames of qa_hcodec_stream_begin, at most %d); reset that row (qa_hcodec_stream_reset_rows) or begin a longer stream",
-                       fn, b, st.off[b], f, st.cap, MAX_POS / 2);
-        }
-        QA_REQUIRE(live > 0, "%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
-        if (st.tr.ring()) QA_TRY(rows_under_window_check(fn, st.tr.window, st.B, 2 * n));  // in Transformer frames, two per code frame
-        QA_REQUIRE(!emb || ((reinterpret_cast<uintptr_t>(emb) & 15) == 0 && h->spec.code_dim % 4 == 0),
-                   "%s: emb must be 16-byte aligned (and code_dim a multiple of 4) in a step with per-row lengths: the rows behind a "
-                   "length are written as float4", fn);
-        QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
-        QA_HIP(hipSetDevice(h->device));
-        rs.fill(st.off, 2);
-        QA_TRY(rs.upload(st.tr.ints, s));
-        st.rows = &rs;
-        const int rc = run_planned(*h, stream, [&] { return stream_encode_graph(h, c, wav, (int)n, (long long*)acoustic_codes, emb); });
-        st.rows = nullptr;
-        QA_TRY(rc);
-        st.tr.zero_state = false;  // the rows that started were zeroed by the step's own kernel
-    }
-    for (int b = 0; b < st.B; ++b) st.off[b] += rs.cnt[b];
-    st.cur ^= 1;
+    const bool aligned = !emb || ((reinterpret_cast<uintptr_t>(emb) & 15) == 0 && h->spec.code_dim % 4 == 0);
+    const char* misaligned = aligned ? nullptr : "emb must be 16-byte aligned (and code_dim a multiple of 4) in a step with per-row lengths: "
+                                                 "the rows behind a length are written as float4";
+    // under a ring's window alone: a linear stream runs its Transformer without one
+    QA_TRY(stream_step(fn, *h, st, fam, st.window, frames, n, misaligned, static_cast<hipStream_t>(stream), [&] {
+        return run_planned(*h, stream, [&] { return stream_encode_graph(h, h->ctx, wav, (int)n, (long long*)acoustic_codes, emb); });
+    }));
+    h->strm->cur ^= 1;
     return QA_OK;
 }
 
@@ -1936,41 +1965,15 @@ int qa_hcodec_stream_encode_rows(qa_hcodec* h, const float* wav, int64_t n_sampl
     return stream_encode_call(h, "qa_hcodec_stream_encode_rows", wav, n_samples, frames, acoustic_codes, emb, stream);
 }
 
-int qa_hcodec_stream_reset(qa_hcodec* h) {
-    QA_REQUIRE(h && h->strm, "qa_hcodec_stream_reset: not streaming (call qa_hcodec_stream_begin first)");
-    // the next step is a first step again: reflect fill instead of the convolutions' states, (h, c) zeroed in stream order, and the K / V
-    // rows stay and become invisible (no step reads a row at or behind its own key count)
-    std::fill(h->strm->off.begin(), h->strm->off.end(), 0);
-    return QA_OK;
-}
-
-// the named rows of a stream of B rows back to offset 0; an index out of range or named twice is refused and nothing changes
-static int stream_reset_rows(const char* fn, const int64_t* rows, int64_t n_rows, std::vector<int>* off) {
-    const int64_t B = (int64_t)off->size();
-    QA_REQUIRE(rows && n_rows >= 1 && n_rows <= B, "%s: %lld rows to reset of a stream of %lld (1 .. %lld distinct row indices)", fn,
-               (long long)n_rows, (long long)B, (long long)B);
-    std::vector<char> seen((size_t)B, 0);
-    for (int64_t i = 0; i < n_rows; ++i) {
-        QA_REQUIRE(rows[i] >= 0 && rows[i] < B, "%s: rows[%lld] = %lld is outside 0 .. %lld, the rows of this stream", fn, (long long)i,
-                   (long long)rows[i], (long long)B - 1);
-        QA_REQUIRE(!seen[(size_t)rows[i]], "%s: row %lld is named twice - name every row to reset once", fn, (long long)rows[i]);
-        seen[(size_t)rows[i]] = 1;
-    }
-    for (int64_t i = 0; i < n_rows; ++i) (*off)[(size_t)rows[i]] = 0;
-    return QA_OK;
-}
+// a row at offset 0 takes a first step next: reflect fill instead of the convolutions' states, on top of what TrStream::off says
+int qa_hcodec_stream_reset(qa_hcodec* h) { return stream_reset("qa_hcodec_stream_reset", stream_of(h), "qa_hcodec_stream_begin"); }
 
 int qa_hcodec_stream_reset_rows(qa_hcodec* h, const int64_t* rows, int64_t n_rows) {
-    QA_REQUIRE(h && h->strm, "qa_hcodec_stream_reset_rows: not streaming (call qa_hcodec_stream_begin first)");
-    // host state alone: a row at offset 0 takes a first step next - reflect fill, (h, c) zeroed by that step, its K / V rows invisible
-    return stream_reset_rows("qa_hcodec_stream_reset_rows", rows, n_rows, &h->strm->off);
+    return stream_reset_rows("qa_hcodec_stream_reset_rows", stream_of(h), "qa_hcodec_stream_begin", rows, n_rows);
 }
 
 int qa_hcodec_stream_offsets(const qa_hcodec* h, int64_t* out) {
-    QA_REQUIRE(h && h->strm, "qa_hcodec_stream_offsets: not streaming (call qa_hcodec_stream_begin first)");
-    QA_REQUIRE(out, "qa_hcodec_stream_offsets: null out");
-    for (size_t b = 0; b < h->strm->off.size(); ++b) out[b] = h->strm->off[b];
-    return QA_OK;
+    return stream_offsets("qa_hcodec_stream_offsets", stream_of(h), "qa_hcodec_stream_begin", out);
 }
 
 int qa_hcodec_stream_end(qa_hcodec* h) {
@@ -1980,7 +1983,7 @@ int qa_hcodec_stream_end(qa_hcodec* h) {
     return QA_OK;
 }
 
-int64_t qa_hcodec_stream_offset(const qa_hcodec* h) { return (h && h->strm) ? h->strm->offset() : -1; }
+int64_t qa_hcodec_stream_offset(const qa_hcodec* h) { return stream_of(h) ? stream_of(h)->offset() : -1; }
 
 // The per-clip H-Codec 1.5 calls serve the non-causal model only: a causal aggregator or bottleneck attends by position, and their
 // attention takes no key-padding mask.
@@ -2410,10 +2413,7 @@ int qa_transformer_stream_begin(qa_transformer* h, int64_t B, int64_t capacity) 
     QA_REQUIRE(B > 0 && B < (1 << 20) && capacity >= 1 && capacity <= MAX_POS, "qa_transformer_stream_begin: batch %lld, capacity %lld (1 .. %d)",
                (long long)B, (long long)capacity, MAX_POS);
     QA_HIP(hipSetDevice(h->device));
-    h->off.clear();
-    QA_TRY(h->st.begin(h->w, B, capacity));  // in place of the state of a handle that is already streaming
-    h->off.assign((size_t)B, 0);
-    return QA_OK;
+    return h->st.begin(h->w, B, capacity, 1);  // in place of the state of a handle that is already streaming
 }
 
 // A ring stream: the K / V rows are rings of ring::capacity(left_context, max_chunk) rows and the stream has no end
@@ -2422,73 +2422,25 @@ int qa_transformer_stream_begin_ring(qa_transformer* h, int64_t B, int64_t max_c
     QA_REQUIRE(h->spec.causal && h->spec.left_context > 0, "qa_transformer_stream_begin_ring: a ring needs a causal Transformer with a sliding "
                "window (causal = %d, left_context = %d): without a window a query sees its whole history, which no ring holds", h->spec.causal,
                h->spec.left_context);
-    QA_REQUIRE(B > 0 && B < (1 << 20) && max_chunk >= 1 && max_chunk <= MAX_POS, "qa_transformer_stream_begin_ring: batch %lld, max_chunk %lld "
-               "(1 .. %d)", (long long)B, (long long)max_chunk, MAX_POS);
-    const int64_t rows = ring::capacity(h->spec.left_context, max_chunk);
-    QA_REQUIRE(rows <= MAX_POS, "qa_transformer_stream_begin_ring: left_context %d with max_chunk %lld needs a ring of %lld rows, above the %d "
-               "a cache may have", h->spec.left_context, (long long)max_chunk, (long long)rows, MAX_POS);
+    QA_TRY(ring_begin_check("qa_transformer_stream_begin_ring", "max_chunk", "frames", B, h->spec.left_context, max_chunk, 1, 1));
     QA_HIP(hipSetDevice(h->device));
-    h->off.clear();
-    QA_TRY(h->st.begin_ring(h->w, B, h->spec.left_context, max_chunk));  // in place of the state of a handle that is already streaming
-    h->off.assign((size_t)B, 0);
-    return QA_OK;
+    return h->st.begin_ring(h->w, B, h->spec.left_context, max_chunk, 1);  // in place of the state of a handle that is already streaming
 }
 
-int64_t qa_transformer_stream_capacity(const qa_transformer* h) { return (h && h->st.B > 0) ? h->st.cap : -1; }
+int64_t qa_transformer_stream_capacity(const qa_transformer* h) { return stream_of(h) ? stream_of(h)->cap_units() : -1; }
 
-// One step; frames null: every row takes all n frames (qa_transformer_stream_step).  Refusals come before any launch and leave the state
-// and all offsets as they were; rows that move together with all n frames take the rectangular step whichever entry point they came through
+// One step; frames null: every row takes all n frames (qa_transformer_stream_step).  Its own argument check, then the shared front
 static int transformer_stream_call(qa_transformer* h, const char* fn, const float* x, int64_t n, const int64_t* frames, float* y, void* stream) {
-    QA_REQUIRE(h && h->st.B > 0, "%s: not streaming (call qa_transformer_stream_begin)", fn);
+    QA_TRY(require_streaming(fn, stream_of(h), TRANSFORMER_STREAM.begin));
     QA_TRY(transformer_check_io(fn, h, x, y, h->st.B, n));
-    const int B = h->st.B;
-    RowStep rs;
-    bool full = true;
-    if (frames) {
-        const int64_t bad = check_row_lengths(frames, B, 0, n, &rs.cnt, &full);
-        QA_REQUIRE(bad < 0, "%s: frames[%lld] = %lld is outside 0 .. %lld, the frames of this step's rectangle (0: the row idles) - pass a wider "
-                   "rectangle or fewer frames", fn, (long long)bad, (long long)frames[bad], (long long)n);
-    } else {
-        rs.cnt.assign((size_t)B, (int)n);
-    }
-    bool together = full;
-    for (int b = 1; b < B; ++b) together = together && h->off[b] == h->off[0];
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int why = 0;
-    const int64_t bad_row = h->st.ring() ? h->st.first_bad_row(h->off, rs.cnt, 1, &why) : -1;
-    if (bad_row >= 0) return ring_refuse(fn, h->st, bad_row, why, h->off[bad_row], rs.cnt[bad_row], 1);
-    if (together) {
-        QA_REQUIRE(h->st.ring() || (int64_t)h->offset() + n <= h->st.cap, "%s: %d streamed + %lld new frames exceed the capacity %d of "
-                   "this stream (max_frames)", fn, h->offset(), (long long)n, h->st.cap);
-        QA_TRY(refuse_capture(fn, s, CACHE_IS_HOST_STATE));
-        QA_HIP(hipSetDevice(h->device));
-        if (h->offset() == 0) h->st.zero_state = true;
-        QA_TRY(h->st.zero_if_new(h->w.d, s));
-        const TrChunk ch = stream_chunk(h->st, h->offset());
-        QA_TRY(transformer_run(h, x, B, (int)n, y, stream, &ch));
-    } else {
-        int live = 0;
-        for (int b = 0; b < B; ++b) {
-            live += rs.cnt[b] > 0;
-            QA_REQUIRE(h->st.ring() || (int64_t)h->off[b] + rs.cnt[b] <= h->st.cap, "%s: row %d has %d streamed + %d new frames, beyond the capacity %d of this "
-                       "stream (max_frames); reset that row (qa_transformer_stream_reset_rows) or begin a longer stream", fn, b, h->off[b],
-                       rs.cnt[b], h->st.cap);
-        }
-        QA_REQUIRE(live > 0, "%s: every row idles (frames all 0) - a step needs at least one row with frames; skip the call instead", fn);
-        // the long-chunk attention has its per-item form without a window only (attention.hip, section 34): nothing else runs in its place
-        if (h->spec.left_context > 0) QA_TRY(rows_under_window_check(fn, h->spec.left_context, B, n));
-        QA_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0,
-                   "%s: x and y must be 16-byte aligned in a step with per-row lengths (the rows behind a length are written as float4)", fn);
-        QA_TRY(refuse_capture(fn, s, LENGTHS_ARE_HOST_DATA));
-        QA_HIP(hipSetDevice(h->device));
-        rs.fill(h->off, 1);
-        QA_TRY(rs.upload(h->st.ints, s));
-        const TrChunk ch = stream_chunk(h->st, 0, &rs);
-        QA_TRY(transformer_run(h, x, B, (int)n, y, stream, &ch));
-        h->st.zero_state = false;  // the rows that started were zeroed by the step's own kernel
-    }
-    for (int b = 0; b < B; ++b) h->off[b] += rs.cnt[b];
-    return QA_OK;
+    const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    const char* misaligned = aligned ? nullptr : "x and y must be 16-byte aligned in a step with per-row lengths (the rows behind a length are "
+                                                 "written as float4)";
+    // under the handle's window, on a linear stream too
+    return stream_step(fn, *h, h->st, TRANSFORMER_STREAM, h->spec.left_context, frames, n, misaligned, static_cast<hipStream_t>(stream), [&] {
+        const TrChunk ch = stream_chunk(h->st);
+        return transformer_run(h, x, h->st.B, (int)n, y, stream, &ch);
+    });
 }
 
 int qa_transformer_stream_step(qa_transformer* h, const float* x, int64_t n, float* y, void* stream) {
@@ -2501,33 +2453,23 @@ int qa_transformer_stream_step_rows(qa_transformer* h, const float* x, int64_t n
     return transformer_stream_call(h, "qa_transformer_stream_step_rows", x, n, frames, y, stream);
 }
 
-int qa_transformer_stream_reset(qa_transformer* h) {
-    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_reset: not streaming");
-    std::fill(h->off.begin(), h->off.end(), 0);  // the cached rows stay and become invisible: no step reads a row at or behind offset + n
-    h->st.zero_state = true;
-    return QA_OK;
-}
+int qa_transformer_stream_reset(qa_transformer* h) { return stream_reset("qa_transformer_stream_reset", stream_of(h), TRANSFORMER_STREAM.begin); }
 
 int qa_transformer_stream_reset_rows(qa_transformer* h, const int64_t* rows, int64_t n_rows) {
-    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_reset_rows: not streaming (call qa_transformer_stream_begin)");
-    return stream_reset_rows("qa_transformer_stream_reset_rows", rows, n_rows, &h->off);
+    return stream_reset_rows("qa_transformer_stream_reset_rows", stream_of(h), TRANSFORMER_STREAM.begin, rows, n_rows);
 }
 
 int qa_transformer_stream_offsets(const qa_transformer* h, int64_t* out) {
-    QA_REQUIRE(h && h->st.B > 0, "qa_transformer_stream_offsets: not streaming (call qa_transformer_stream_begin)");
-    QA_REQUIRE(out, "qa_transformer_stream_offsets: null out");
-    for (size_t b = 0; b < h->off.size(); ++b) out[b] = h->off[b];
-    return QA_OK;
+    return stream_offsets("qa_transformer_stream_offsets", stream_of(h), TRANSFORMER_STREAM.begin, out);
 }
 
 int qa_transformer_stream_end(qa_transformer* h) {
     QA_REQUIRE(h, "qa_transformer_stream_end: null handle");
     (void)hipSetDevice(h->device);
     h->st.release();
-    h->off.clear();
     return QA_OK;
 }
 
-int64_t qa_transformer_stream_offset(const qa_transformer* h) { return (h && h->st.B > 0) ? h->offset() : -1; }
+int64_t qa_transformer_stream_offset(const qa_transformer* h) { return stream_of(h) ? stream_of(h)->offset() : -1; }
 
 }  // extern "C"
